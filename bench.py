@@ -1,6 +1,6 @@
 """bench.py -- candidates/sec of the GP posterior + acquisition + argmax sweep on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 With N > 1 and no torch.distributed.run environment (RANK / WORLD_SIZE unset) the script launches its own N ranks
@@ -17,8 +17,17 @@ Hyper-parameters are pinned (theta = 0.01, sigma2 = 0.9, nugget 1e-6, simple kri
 section 8d prescribes; X ~ U[-5,5], y = sum x^2 standardised; seeds fixed.
 
 Prints ONE JSON line (rank 0) with the driver's fields + "roofline" (dominant kernel k_contract: algorithmic FP64
-flops / HIP-event duration on the library's stream) + "cpu_baseline" (the NumPy oracle timed on this box's host
-cores on a bounded sample of the same workload; also used as a parity check of the timed run).
+flops / HIP-event duration on the library's stream, both taken from the timed steps).  A plain run does nothing else:
+set-up, W warm-up steps, K timed steps, the outputs (`--dump-outputs`), the line.
+
+`--full` adds the secondary figures, each measured outside the timed steps: "fit" (likelihood, batched likelihood, lock-step
+MLE, commit), the PCIe-inclusive and device-generated ask() variants, the seed-1 / seed-2 repeats ("seeds", unless
+--no-seeds) and "cpu_baseline" (the NumPy oracle timed on the host cores on a bounded sample of the same workload, also
+a parity check of the timed run; unless --no-cpu).
+
+`--dump-outputs DIR` writes what the last timed step returned -- the q global winners -- as DIR/argmax_values.npy (q,),
+DIR/argmax_indices.npy (q,) and DIR/argmax_points.npy (q, d), float64.  The inputs are seeded: the same arguments give
+the same inputs in every run.
 """
 import argparse
 import ctypes
@@ -138,9 +147,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-sample", type=int, default=40960, help="candidates timed through the CPU oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-seeds", action="store_true", help="skip the seed-1 / seed-2 repeats of the workload (SURVEY.md 8d)")
+    ap.add_argument("--full", action="store_true", help="also measure the secondary figures: fit, ask() variants, seeds 1 / 2, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=40960, help="candidates timed through the CPU oracle (rank 0, N=1; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-seeds", action="store_true", help="--full without the seed-1 / seed-2 repeats of the workload (SURVEY.md 8d)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: M candidates per GPU (default); strong: the workload's total (C3 1e6, C4 8e6, C5 4e6) split over the ranks")
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)
@@ -151,6 +162,8 @@ def main():
     ap.add_argument("--dry-size", default="96,4,4001", help=argparse.SUPPRESS)
     ap.add_argument("--dry-fail-comm-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     dry = args.dry_run_engine is not None
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -218,7 +231,7 @@ def main():
     # fit is reported separately: one likelihood (+ gradient) evaluation at the pinned parameters = what the
     # MLE loop of GaussianProcess.fit pays per L-BFGS-B evaluation; the model is re-committed afterwards
     fit_ms = {}
-    if not dry:
+    if args.full and not dry:
         for name, eg in (("llf_ms", False), ("llf_grad_ms", True)):
             eng.nll(w["kernel"], _lib.MODE_NOISY, par, 1e-6, False, 0.0, eval_grad=eg)
             t0 = time.perf_counter()
@@ -322,10 +335,12 @@ def main():
         dist.all_gather(each, torch.tensor([elapsed], dtype=torch.float64, device=dev))
         per_rank_ms = [float(e.item()) / args.steps * 1e3 for e in each]
         elapsed = max(float(e.item()) for e in each)  # MAX over ranks
+    if args.dump_outputs and rank == 0:  # the winners are identical on every rank
+        dump_outputs(args.dump_outputs, out)
 
     # PCIe-inclusive ask(): H2D of the shard + one step (noted, never `value`)
     h2d_ms = gen_ms = full_ms = None
-    if rank == 0 and args.scaling == "weak" and not dry:
+    if args.full and rank == 0 and args.scaling == "weak" and not dry:
         Xh = Xs.cpu().numpy()
         h2d = []
         for i in range(4):  # (the first pass allocates the library's candidate buffer and creates the copy stream: not timed)
@@ -356,7 +371,7 @@ def main():
     # for seeds 1 and 2 -- another training set, another candidate shard, the model re-committed outside the timed steps -- and the
     # median / min / max step of each seed is reported beside it.  The committed model and candidates are seed 0's again afterwards.
     seed_stats = None
-    if rank == 0 and world == 1 and args.scaling == "weak" and not args.no_seeds and not dry:
+    if args.full and rank == 0 and world == 1 and args.scaling == "weak" and not args.no_seeds and not dry:
         seed_stats = {"0": {"median_ms": float(np.median(step_ms)), "min_ms": float(np.min(step_ms)), "max_ms": float(np.max(step_ms)), "steps": len(step_ms)}}
         for sd in (1, 2):
             r2 = np.random.default_rng(sd)
@@ -452,13 +467,14 @@ def main():
             "ask_ms_device_generated": gen_ms,
             "ask_ms_full": full_ms,
             "commit_s": commit_s,
-            "fit": fit_ms,
+            "fit": fit_ms if args.full else None,
+            "full": args.full,
             "llf": llf,
             "argmax": [int(i) for i in out[1]],
             "exchange": ("bogp_exchange_argmax over RCCL, world %d (executed inside every timed step)" % eng.comm_world) if comm_error is None
             else "torch.distributed all-gather (library communicator failed: %s)" % comm_error,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(w, X, y, par, plugin, Xs[: args.cpu_sample].cpu().numpy(), args.cpu_sample, eng)
         # RCCL prints a banner through C stdio, whose buffer would otherwise drain AFTER this line at exit: flush it first so
         # the JSON line is the LAST line of stdout
@@ -466,6 +482,14 @@ def main():
         print(json.dumps(res), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, out):
+    """`--dump-outputs DIR`: what one step returns to its caller, (values (q,), global indices (q,), points (q, d)), as float64
+    .npy files (the indices are exact in float64)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in zip(("argmax_values", "argmax_indices", "argmax_points"), out):
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def dry_candidates(first_row, n_rows, d):

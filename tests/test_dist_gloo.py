@@ -298,3 +298,22 @@ def test_whole_bench_step_on_eight_cpu_ranks_equals_the_single_process_argmax(sc
     assert res["argmax"] == [int(i) for i in idx]
     np.testing.assert_array_equal(res["values"], best)
     np.testing.assert_array_equal(res["points"], table[idx])
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_are_the_last_steps_winners(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps, what the last step returned (values, global indices, points) lands in DIR as
+    float64 .npy files equal to the JSON line's; a second run with the same arguments writes the same bits (seeded inputs)."""
+    names = ("argmax_values", "argmax_indices", "argmax_points")
+    runs = []
+    for i in range(2):
+        res = _run_bench_dry(1, ["--dump-outputs", str(tmp_path / str(i))])
+        assert res["dry_run"] and res["steps"] == 2
+        got = {n: np.load(str(tmp_path / str(i) / (n + ".npy"))) for n in names}
+        assert all(a.dtype == np.float64 for a in got.values())
+        np.testing.assert_array_equal(got["argmax_values"], res["values"])
+        assert got["argmax_indices"].tolist() == res["argmax"]
+        np.testing.assert_array_equal(got["argmax_points"], res["points"])
+        runs.append(got)
+    for n in names:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n])
