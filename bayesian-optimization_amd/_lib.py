@@ -22,6 +22,8 @@ SELFTEST_PROFILE, SELFTEST_BESSEL_K, SELFTEST_RGAMMA, SELFTEST_BESSEL_K_PAIRS, S
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
 MAX_Q = 64
 MAX_TARGETS = 8
+MAX_TOPK = 32
+MAX_EHVI_CELLS = 65536  # BOGP_MAX_EHVI_CELLS: cells one bogp_sweep_ehvi call takes
 COMM_ID_BYTES = 128
 SCALES = {"linear": 0, None: 0, "log": 1, "log10": 2, "logit": 3, "bilog": 4}  # Real.scale (variable.py:43-55)
 
@@ -62,6 +64,7 @@ SIGNATURES = {
     "bogp_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
+    "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_gradient": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "bogp_gradient_batch": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "bogp_hessian": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -545,6 +548,30 @@ class Engine:
         )  # fmt: skip
         self._last_topk = (q, int(k))
         return best, idx
+
+    def sweep_ehvi(self, lower, upper, k: int = 1, return_values=False, return_moments=False):
+        """Expected hypervolume improvement of the committed multi-target model over the current candidates, for the
+        cells (lower, upper) (C x m each; upper may hold +inf): (best_val (k,), best_idx (k,)[, values (M,)][, mu (M, m),
+        mse (M, m)]); rank 0 is the argmax, slots beyond M are (-inf, -1)."""
+        lower = _f64(lower)
+        upper = _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape")
+        C_, m = lower.shape
+        best = np.empty(int(k))
+        idx = np.empty(int(k), dtype=np.int64)
+        vals = np.empty(self.M) if return_values else None
+        mu = np.empty((self.M, m)) if return_moments else None
+        mse = np.empty((self.M, m)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_ehvi(self._h, int(m), int(C_), _ptr(lower), _ptr(upper), int(k), _ptr(best),
+                                              idx.ctypes.data_as(_lp), _ptr(vals), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_moments:
+            out += (mu, mse)
+        return out
 
     def gradient(self, x):
         x = _f64(x).ravel()

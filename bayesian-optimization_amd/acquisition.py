@@ -291,3 +291,84 @@ class MGFI(ImprovementBased):
             except FloatingPointError:  # the reference turns warnings into a zero gradient
                 slope = m.zeros()
         return value, slope
+
+
+class EHVI:
+    """Expected hypervolume improvement of a multi-target device model: drop-in for the reference's
+    `bayes_optim.multi_objective.analytic.EHVI` (analytic.py:99-274), which MOBO maximises (mobo.py:177-186).
+
+    The targets are maximised as given (MOBO passes `y * (-1) ** minimize`, mobo.py:66-76).  The cells of the region the
+    front does not dominate come from exactly one of
+      Y            the observed objective values (n x m), decomposed by `bogp.pareto.hypercell_bounds`;
+      partitioning the reference's partitioning object, read through `.pareto_Y` and `.get_hypercell_bounds()`;
+      cells        (lower, upper), each C x m (upper may hold +inf).
+    `criterion(X)` returns one value per row, shape (M,): row i is what the reference's one-row call returns for row i
+    (computed in float64 -- the reference casts mu / MSE to float32, analytic.py:228-233).  All rows are evaluated in one
+    device pass (`bogp_sweep_ehvi`); there is no input gradient."""
+
+    is_ehvi = True
+    minimize = False  # (the sweep helpers read it off every criterion)
+
+    def __init__(self, model=None, ref_point=None, partitioning=None, Y=None, cells=None):
+        if model is None:
+            raise ValueError("model cannot be None")
+        if sum(s is not None for s in (partitioning, Y, cells)) != 1:
+            raise ValueError("EHVI takes exactly one of partitioning=, Y= and cells=")
+        if ref_point is None:
+            raise ValueError("EHVI needs a ref_point")
+        self.model = model
+        self.ref_point = np.asarray(ref_point, dtype=float).ravel()
+        m = len(self.ref_point)
+        pareto_Y = None
+        if partitioning is not None:
+            pareto_Y = np.atleast_2d(np.asarray(partitioning.pareto_Y, dtype=float))
+            n_out = getattr(partitioning, "num_outcomes", pareto_Y.shape[1])
+            if n_out != m:
+                raise ValueError("The length of the reference point must match the number of outcomes. Got ref_point with "
+                                 "%d elements, but expected %d." % (m, n_out))  # fmt: skip
+            b = partitioning.get_hypercell_bounds()
+            lower, upper = np.asarray(b[0], dtype=float), np.asarray(b[1], dtype=float)
+        elif Y is not None:
+            Y = np.atleast_2d(np.asarray(Y, dtype=float))
+            if Y.shape[1] != m:
+                raise ValueError("The length of the reference point must match the number of outcomes. Got ref_point with "
+                                 "%d elements, but expected %d." % (m, Y.shape[1]))  # fmt: skip
+            from .pareto import hypercell_bounds, pareto_front
+
+            pareto_Y = pareto_front(Y, self.ref_point)  # (as the reference's partitioning keeps only points above the reference point)
+            lower, upper = hypercell_bounds(Y, self.ref_point)
+        else:
+            lower, upper = (np.asarray(c, dtype=float) for c in cells)
+        if pareto_Y is not None and len(pareto_Y) and not np.any(np.all(pareto_Y > self.ref_point, axis=1)):
+            raise ValueError("At least one pareto point must be better than the reference point.")
+        lower, upper = np.atleast_2d(lower), np.atleast_2d(upper)
+        if lower.shape != upper.shape or lower.shape[1] != m:
+            raise ValueError("cell bounds must be two C x %d arrays, got %s and %s" % (m, lower.shape, upper.shape))
+        if len(lower) > _lib.MAX_EHVI_CELLS:
+            raise ValueError("%d cells: at most %d per sweep" % (len(lower), _lib.MAX_EHVI_CELLS))
+        self.pareto_Y = pareto_Y
+        self.cell_lower_bounds = np.ascontiguousarray(lower)
+        self.cell_upper_bounds = np.ascontiguousarray(upper)
+
+    @property
+    def n_obj(self) -> int:
+        return len(self.ref_point)
+
+    def effective_plugin(self) -> float:
+        return 0.0
+
+    def sweep(self, k: int = 1, return_values: bool = False):
+        """The EHVI sweep over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
+        model = self.model
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        return model.engine.sweep_ehvi(self.cell_lower_bounds, self.cell_upper_bounds, k=k, return_values=return_values)
+
+    def __call__(self, X, return_dx: bool = False):
+        if return_dx:
+            raise NotImplementedError("EHVI has no input gradient (the reference's EHVI has none either)")
+        if getattr(self.model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        eng = self.model.engine
+        eng.upload_candidates(self.model._check_X(X))
+        return self.sweep(return_values=True)[2]

@@ -27,7 +27,7 @@ using namespace bogp;
 // The winners a sweep left on the device (dbest_* / dtopk_*) refer to rows of the candidate set they were computed on: any
 // change of that set -- and a sweep of the other flavour, which overwrites dbest_* -- makes them unusable for
 // bogp_exchange_* (stale or out-of-range rows would be packed otherwise).
-static void invalidate_sweep_results(bogp_handle* h) { h->last_q = h->last_topk_q = h->last_topk_k = 0; }
+void bogp::invalidate_sweep_results(bogp_handle* h) { h->last_q = h->last_topk_q = h->last_topk_k = 0; }
 
 // ---- lazy upload: the copy of chunk c + 1 runs beside the kernels of chunk c --------------------------------------------------------
 // rows [lazy_done, upto) onto the copy stream (a copy from pageable memory blocks the HOST while the runtime stages it, not the
@@ -335,8 +335,8 @@ static void collect_timing(bogp_handle* h) {
   }
 }
 
-static int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin,
-                     int minimize, bool want_acq_out, bool need_var = true, bool sync = true) {
+int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin,
+                    int minimize, bool want_acq_out, bool need_var, bool sync, const EhviArgs* eh) {
   collect_timing(h);  // the events are about to be re-recorded
   if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "no committed model: call bogp_commit first");
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "no candidates: call bogp_candidates_upload/bind first");
@@ -370,14 +370,16 @@ static int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, co
   // Small batches (the reference's one-point-per-call usage through L-BFGS-B): the tiled contraction would leave one
   // workgroup walking all N columns alone (~0.3 ms at N = 2048).  For M <= BOGP_SMALL_M the posterior is instead
   // r -> rt = V r (k_gemm64 with M right-hand sides) -> column reductions, feeding the same acquisition kernel.
+  // (bogp_sweep_ehvi -- eh non-null -- takes neither single-target shortcut: it always runs the chunked path below)
   const int small_m = 32;
-  const bool one_launch = h->p == 1 && sweep_small_supported(Np, d, h->kernel);
-  if (h->hXs_lazy && ((M <= small_m && h->p == 1) || one_launch || nchunk == 1)) {
+  const bool small_batch = !eh && M <= small_m && h->p == 1;
+  const bool one_launch = !eh && h->p == 1 && sweep_small_supported(Np, d, h->kernel);
+  if (h->hXs_lazy && (small_batch || one_launch || nchunk == 1)) {
     // nothing to overlap with: the whole upload first (one launch reads every candidate)
     const int el = lazy_finish(h);
     if (el) return el;
   }
-  if (M <= small_m && h->p == 1) {
+  if (small_batch) {
     const int B = (int)M, N = h->N;
     int e2;
     if ((e2 = ensure(h, &h->dbatch, &h->batch_cap, (size_t)3 * N * B + 3 * (size_t)B))) return e2;
@@ -512,9 +514,10 @@ static int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, co
     if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
     if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
   }
-  if (want_out) {
-    if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M))) return e;
-    if ((e = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M))) return e;
+  if (want_out) {  // (EHVI: M x m moments)
+    const size_t n_out = (size_t)M * (eh ? eh->m : 1);
+    if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, n_out))) return e;
+    if ((e = ensure(h, &h->dmse_out, &h->mse_out_cap, n_out))) return e;
   }
   if (want_acq_out)
     if ((e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e;
@@ -621,7 +624,16 @@ static int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, co
       aa.mtrend = h->dmtrend;
       aa.estimate_trend = 0;  // the scalar w_part path is for the constant basis
     }
-    HIPCHK(h, launch_acquisition(aa, st));
+    if (eh) {  // the m-target posterior + EHVI of this chunk in place of the q single-target criteria (kernels_ehvi.hip)
+      EhviArgs ea = *eh;
+      ea.rT = h->drT[b]; ea.ss_part = h->dss_part; ea.w_part = h->dw_part[b]; ea.S = S; ea.nJ = nJ_main; ea.Mc = Mc;
+      ea.mcount = mcount; ea.m0 = m0; ea.beta = h->beta; ea.G = h->G; ea.estimate_trend = h->estimate_trend;
+      ea.ehvi_out = h->dacq_out; ea.mu_out = want_out ? h->dmu_out : nullptr; ea.mse_out = want_out ? h->dmse_out : nullptr;
+      ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = blk_offset;
+      HIPCHK(h, launch_ehvi(ea, st));
+    } else {
+      HIPCHK(h, launch_acquisition(aa, st));
+    }
     HIPCHK(h, hipEventRecord(ev[4], st));
     blk_offset += (mcount + 255) / 256;
     if (h->hXs_lazy) {  // the next chunk's rows travel while this chunk's kernels (queued above) run

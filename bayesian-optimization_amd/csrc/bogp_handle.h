@@ -20,6 +20,11 @@ std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: t
 // array (B x d).  Outputs (host, any may be null): mu, mse (B), dmu, dmse (B x d), acq (B x q), dacq (B x q x d).
 int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, int q, const int* acq_id, const double* acq_par,
                     double plugin, int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq);
+// bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
+// m-target EHVI of bogp_api_ehvi.hip on the chunked path), and the reset of the winners a sweep left on the device
+int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+              bool want_acq_out, bool need_var = true, bool sync = true, const EhviArgs* eh = nullptr);
+void invalidate_sweep_results(bogp_handle* h);
 }
 
 struct bogp_handle {
@@ -108,6 +113,8 @@ struct bogp_handle {
   int64_t* dtopk_idx = nullptr;
   size_t topk_val_cap = 0, topk_idx_cap = 0;
   size_t blk_val_cap = 0, blk_idx_cap = 0, mu_out_cap = 0, mse_out_cap = 0, acq_out_cap = 0;
+  double* dehvi_cells = nullptr;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
+  size_t ehvi_cells_cap = 0;
 
   // polynomial trend bases with p > 1 columns (linear / quadratic; the constant basis keeps its scalar fast path)
   int trend = BOGP_TREND_CONSTANT, p = 1;  // committed

@@ -74,6 +74,32 @@ struct AcqArgs {
   int64_t nblk_total;
 };
 
+// expected hypervolume improvement of an m-target model over one chunk (kernels_ehvi.hip): replaces AcqArgs / k_acquisition
+// in the chunk loop of bogp_sweep_ehvi
+struct EhviArgs {
+  const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
+  const double* gamma;    // [m][ld_gamma] the targets' gamma columns
+  int ld_gamma, N;        // Np; training points summed over
+  const double* ss_part;  // [nJ][Mc]
+  const double* w_part;   // [S][Mc] (constant trend with estimate_trend only)
+  int S, nJ;
+  int64_t Mc, mcount, m0;
+  double beta, G;
+  int estimate_trend;
+  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
+  double sigma2[8];       // per target
+  const double* lower;    // [C][m] cell bounds (device)
+  const double* upper;    // [C][m] (+inf allowed)
+  int C;
+  double* ehvi_out;       // [M] (global index m0 + i)
+  double* mu_out;         // [M][m] or null
+  double* mse_out;        // [M][m] or null
+  double* blk_val;        // per-block partial argmax
+  int64_t* blk_idx;
+  int64_t blk_offset;
+};
+hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
+
 // the fused small-N sweep (kernels_small.hip): one launch = producer + contraction + posterior + q criteria + argmax
 struct SmallArgs {
   const double* Xs;          // candidates, M x d row-major

@@ -1,0 +1,115 @@
+// kernels_ehvi.hip -- expected hypervolume improvement of an m-target model over one correlation chunk (gfx950).
+//
+// Replaces, per candidate row, the reference's EHVI.forward (multi_objective/analytic.py:176-274) on the posterior of
+// GaussianProcess.predict (gpr.py:486-510) with several targets:
+//   mu_k  = beta + r.gamma_k                       (the chunk's r column; gamma_k the target's column of gamma_base)
+//   MSE_k = max(0, (1 - |L^-1 r|^2 + u^2) sigma2_k) (|L^-1 r|^2 from k_contract, shared by every target)
+//   sigma_k = sqrt(max(MSE_k, 1e-9))              (analytic.py:233)
+// and, for the cells (l_c, u_c) of a partition of the region the front does not dominate (maximised targets),
+//   EHVI = sum_c prod_k f_ck,  f_ck = psi(l,l) - psi(l,u) + nu(l,u) = E[(min(Y_k, u_ck) - l_ck)^+]
+//        = sigma_k (G(a) - G(b)),  a = (l - mu) / sigma, b = (u - mu) / sigma,  G(z) = phi(z) - z Phi(-z)
+// -- the reference's sum over the 2^m subsets of {psi_diff, nu} is the expansion of this product.  An upper bound at
+// +inf gives G(b) = 0 exactly (the reference clamps it to 1e10, where its terms vanish).  np.argmax order over the rows
+// (first maximum, NaN maximal) into the same per-block records k_argmax_final / the top-k passes read.
+#include "bogp_device.h"
+#include "bogp_internal.h"
+
+namespace bogp {
+
+__device__ __forceinline__ double ehvi_G(double z) { return norm_pdf(z) - z * ndtr(-z); }
+
+template <int MT>
+__global__ __launch_bounds__(256) void k_ehvi(EhviArgs a) {
+  __shared__ double sv[4];
+  __shared__ int64_t si[4];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // row inside the chunk
+  const bool valid = i < a.mcount;
+  double v = -INFINITY;
+  int64_t idx = INT64_MAX;
+  if (valid) {
+    double mu[MT];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) mu[k] = 0.0;
+    // one fixed order over n per lane: the bits do not depend on the chunk size
+    for (int n = 0; n < a.N; ++n) {
+      const double r = a.rT[(size_t)n * a.Mc + i];
+#pragma unroll
+      for (int k = 0; k < MT; ++k) mu[k] = fma(r, a.gamma[(size_t)k * a.ld_gamma + n], mu[k]);
+    }
+    double ss = 0.0, wd = 0.0;
+    for (int j = 0; j < a.nJ; ++j) ss += a.ss_part[(size_t)j * a.Mc + i];
+    double u2 = 0.0;
+    if (a.estimate_trend) {
+      for (int s = 0; s < a.S; ++s) wd += a.w_part[(size_t)s * a.Mc + i];
+      const double u = (wd - 1.0) / a.G;
+      u2 = u * u;
+    }
+    const int64_t g = a.m0 + i;
+    double sd[MT];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) {
+      mu[k] += a.beta;
+      double mse = (1.0 - ss + u2) * a.sigma2[k];
+      if (mse < 0.0) mse = 0.0;
+      if (a.mu_out) a.mu_out[(size_t)g * MT + k] = mu[k];
+      if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse;
+      sd[k] = sqrt(fmax(mse, 1e-9));
+    }
+    double acc = 0.0;
+    for (int c = 0; c < a.C; ++c) {  // the cell bounds are the same for every lane
+      double p = 1.0;
+#pragma unroll
+      for (int k = 0; k < MT; ++k) {
+        const double l = a.lower[(size_t)c * MT + k], u = a.upper[(size_t)c * MT + k];
+        const double gl = ehvi_G((l - mu[k]) / sd[k]);
+        const double gu = isinf(u) ? 0.0 : ehvi_G((u - mu[k]) / sd[k]);
+        p *= sd[k] * (gl - gu);
+      }
+      acc += p;
+    }
+    v = acc;
+    idx = g;
+    a.ehvi_out[g] = v;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ov = shfl_xor_f64(v, off);
+    const int64_t oi = shfl_xor_i64(idx, off);
+    if (better(ov, oi, v, idx)) {
+      v = ov;
+      idx = oi;
+    }
+  }
+  if (lane == 0) {
+    sv[w] = v;
+    si[w] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k)
+      if (better(sv[k], si[k], v, idx)) {
+        v = sv[k];
+        idx = si[k];
+      }
+    a.blk_val[a.blk_offset + blockIdx.x] = v;
+    a.blk_idx[a.blk_offset + blockIdx.x] = idx;
+  }
+}
+
+hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st) {
+  const unsigned nblk = (unsigned)((a.mcount + 255) / 256);
+  switch (a.m) {
+    case 2: hipLaunchKernelGGL(k_ehvi<2>, dim3(nblk), 256, 0, st, a); break;
+    case 3: hipLaunchKernelGGL(k_ehvi<3>, dim3(nblk), 256, 0, st, a); break;
+    case 4: hipLaunchKernelGGL(k_ehvi<4>, dim3(nblk), 256, 0, st, a); break;
+    case 5: hipLaunchKernelGGL(k_ehvi<5>, dim3(nblk), 256, 0, st, a); break;
+    case 6: hipLaunchKernelGGL(k_ehvi<6>, dim3(nblk), 256, 0, st, a); break;
+    case 7: hipLaunchKernelGGL(k_ehvi<7>, dim3(nblk), 256, 0, st, a); break;
+    case 8: hipLaunchKernelGGL(k_ehvi<8>, dim3(nblk), 256, 0, st, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace bogp

@@ -6,6 +6,8 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
                                                                              hands everything else to the original)
   bayes_optim.{base,bayes_opt,extension}.AcquisitionFunction -> a per-MODEL dispatching namespace (below)
   ParallelBO._batch_arg_max_acquisition         -> fused_batch_arg_max_acquisition
+  MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
+                                                   under the sweep family; the reference's EHVI otherwise)
   bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess -> a dispatching class that builds
                                                    `bogp.GaussianProcess` (so `bayes_optim.fmin` -- which resolves the
                                                    name at call time, `__init__.py:147-160` -- runs on the device)
@@ -33,6 +35,7 @@ other inner optimiser ("BFGS", ...) the reference's method runs unchanged.
 """
 from __future__ import annotations
 
+import functools
 import types
 import warnings
 from copy import copy
@@ -101,6 +104,18 @@ def _effective(optimizer, eval_budget):
     if optimizer == "BFGS" and _REROUTE:
         return _REROUTE["optimizer"], _REROUTE["budget"]
     return optimizer, eval_budget
+
+
+def mobo_create_acquisition(self, fixed=None, **kwargv):
+    """Drop-in body for `bayes_optim.mobo.MOBO._create_acquisition` (mobo.py:177-186): with a device model, an inner
+    optimiser of the sweep family ("sweep", "sweep-device[-lhs|-sobol]") and a continuous space the criterion is this
+    package's `EHVI` (float64, cells from `bogp.pareto`), wrapped exactly as the original wraps the reference's; every
+    other configuration runs the original unchanged."""
+    optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
+    if optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(getattr(self, "search_space", None)):
+        return _ORIGINAL["mobo"](self, fixed=fixed, **kwargv)
+    criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
+    return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
 
 
 def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=100, n_restart=10, wait_iter=3,
@@ -319,14 +334,21 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         rext = importlib.import_module(bayes_optim.__name__ + ".extension")
     except Exception:  # optional module with heavier dependencies
         rext = None
+    try:
+        rmobo = importlib.import_module(bayes_optim.__name__ + ".mobo")
+    except Exception:  # (the multi-objective driver needs torch)
+        rmobo = None
 
     if _ORIGINAL:
         return uninstall
     holders = [m for m in (rbase, ropt, rext) if m is not None and getattr(m, "AcquisitionFunction", None) is racq]
     _ORIGINAL.update(argmax=rbase.argmax_restart, acq_holders=holders, acq=racq, batch=ropt.ParallelBO._batch_arg_max_acquisition,
                      mods=(bayes_optim, rbase, ropt, rsur), gp=(getattr(bayes_optim, "GaussianProcess", None), rsur.GaussianProcess),
-                     surrogate=bool(surrogate))  # fmt: skip
+                     surrogate=bool(surrogate), mobo_cls=None)  # fmt: skip
     rbase.argmax_restart = routed_argmax_restart
+    if rmobo is not None and hasattr(rmobo, "MOBO"):
+        _ORIGINAL.update(mobo_cls=rmobo.MOBO, mobo=rmobo.MOBO.__dict__["_create_acquisition"], partial_argument=rmobo.partial_argument)
+        rmobo.MOBO._create_acquisition = mobo_create_acquisition
     ns = _AcquisitionNamespace(racq)
     for m in holders:
         m.AcquisitionFunction = ns
@@ -346,6 +368,8 @@ def uninstall():
     for m in _ORIGINAL["acq_holders"]:
         m.AcquisitionFunction = _ORIGINAL["acq"]
     ropt.ParallelBO._batch_arg_max_acquisition = _ORIGINAL["batch"]
+    if _ORIGINAL["mobo_cls"] is not None:
+        _ORIGINAL["mobo_cls"]._create_acquisition = _ORIGINAL["mobo"]
     if _ORIGINAL["surrogate"]:
         pkg.GaussianProcess, rsur.GaussianProcess = _ORIGINAL["gp"]
     _ORIGINAL.clear()

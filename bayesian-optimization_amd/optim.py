@@ -153,6 +153,23 @@ def candidate_block(bounds, M: int, seed: int, rank: int = 0, world: int = 1) ->
     return rng.uniform(lo, hi, size=(b_ - a, len(lo)))
 
 
+def is_ehvi(criterion) -> bool:
+    """True for `acquisition.EHVI` (the multi-objective criterion: its sweep is `bogp_sweep_ehvi`, not `bogp_sweep`)."""
+    return bool(getattr(criterion, "is_ehvi", False))
+
+
+def _ehvi_of(criteria: Sequence, eng, group=None):
+    """The EHVI criterion a sweep serves, or None when every criterion is single-objective.  EHVI sweeps alone, on one rank."""
+    flags = [is_ehvi(c) for c in criteria]
+    if not any(flags):
+        return None
+    if len(criteria) != 1:
+        raise ValueError("an EHVI criterion sweeps alone: it cannot share a sweep with other criteria")
+    if engine_rank_world(eng, group)[1] > 1:
+        raise NotImplementedError("the EHVI sweep runs on one rank (no multi-rank exchange of its winners)")
+    return criteria[0]
+
+
 def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, group=None, return_points: bool = True):
     """Evaluate q criteria (same model, same minimize / plugin) on this rank's candidates `Xs` and reduce across
     ranks.  Returns (best_val (q,), best_global_idx (q,), best_x (q, d) or None)."""
@@ -161,11 +178,15 @@ def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, grou
     eng = model.engine
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
+    ehvi = _ehvi_of(criteria, eng, group)
     for c in criteria[1:]:
         if c.model is not model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin():
             raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
     Xs = model._check_X(Xs)
     eng.upload_candidates(Xs, lazy=True)  # (the sweep right below overlaps the copy with its first chunks)
+    if ehvi is not None:
+        best, idx = ehvi.sweep(k=1)
+        return best, idx + int(index_offset), (Xs[idx] if return_points else None)
     acq = [(c.acq_id, c.acq_par()) for c in criteria]
     best, idx = eng.sweep(acq, c0.effective_plugin(), c0.minimize)
     if getattr(eng, "comm_world", 0):  # the library's own exchange: device records, ONE ncclAllGather, no host bounce
@@ -190,7 +211,11 @@ def sweep_generated(criteria: Sequence, bounds, M: int, seed: int, rank: int = 0
         raise Exception("The model is not fitted yet!")
     a, b_ = shard_bounds(int(M), rank, world)
     eng = model.engine
+    ehvi = _ehvi_of(criteria, eng, group)
     _generate(eng, bounds, b_ - a, seed, a, method, int(M))
+    if ehvi is not None:
+        best, idx = ehvi.sweep(k=1)
+        return best, idx + a, eng.read_candidates(idx)
     best, idx = eng.sweep([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize)
     if getattr(eng, "comm_world", 0):
         return eng.exchange_argmax(len(criteria), a, True)
@@ -206,8 +231,12 @@ def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0
         raise Exception("The model is not fitted yet!")
     Xs = model._check_X(Xs)
     eng = model.engine
+    ehvi = _ehvi_of(criteria, eng, group)
     eng.upload_candidates(Xs, lazy=True)  # (the sweep right below overlaps the copy with its first chunks)
-    best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
+    if ehvi is not None:
+        best, idx = (a[None, :] for a in ehvi.sweep(k=int(k)))
+    else:
+        best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
     if getattr(eng, "comm_world", 0):
         return eng.exchange_topk(len(criteria), k, int(index_offset), True)
     xb = np.where((idx >= 0)[..., None], Xs[np.clip(idx, 0, len(Xs) - 1)], np.nan)
@@ -225,8 +254,12 @@ def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, 
         raise Exception("The model is not fitted yet!")
     a, b_ = shard_bounds(int(M), rank, world)
     eng = model.engine
+    ehvi = _ehvi_of(criteria, eng, group)
     _generate(eng, bounds, b_ - a, seed, a, method, int(M))
-    best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
+    if ehvi is not None:
+        best, idx = (v[None, :] for v in ehvi.sweep(k=int(k)))
+    else:
+        best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
     if getattr(eng, "comm_world", 0):
         return eng.exchange_topk(len(criteria), k, a, True)
     flat = np.clip(idx, 0, b_ - a - 1).ravel()
@@ -304,7 +337,7 @@ def unwrap_criterion(obj):
     the wrapper fills in with the fixed `values` (None when nothing is fixed or `obj` is the criterion itself)."""
     masks = values = None
     for _ in range(8):
-        if hasattr(obj, "acq_id") and hasattr(obj, "acq_par"):
+        if (hasattr(obj, "acq_id") and hasattr(obj, "acq_par")) or is_ehvi(obj):
             return obj, masks, values
         if isinstance(obj, functools.partial):
             obj = obj.func
@@ -364,6 +397,9 @@ def argmax_restart(
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
     """
     ours = optimizer in DEVICE_DESIGNS or optimizer in ("sweep", "sweep-BFGS", "sweep-device-BFGS")
+    if is_ehvi(unwrap_criterion(obj_func)[0]) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS") and is_continuous(search_space):
+        raise NotImplementedError("optimizer=%r needs an input gradient, which EHVI does not have: use 'sweep' or "
+                                  "'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip
     if not ours and (optimizer != "BFGS" or h is not None or g is not None or not is_continuous(search_space)):
         ref = _reference_argmax_restart()
         if ref is None:

@@ -277,6 +277,23 @@ int bogp_sweep(bogp_handle* h, int q, const int* acq_id, const double* acq_par, 
 int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
                     int k, double* best_val, int64_t* best_idx);
 
+/* ---- sweep: expected hypervolume improvement of a multi-target model --------------------------------
+ * Replaces the reference's EHVI.forward (multi_objective/analytic.py:176-274) as MOBO maximises it
+ * (mobo.py:168-186), evaluated for every current candidate in one chunked device pass: the posterior of all m targets
+ * (gpr.py:486-510; the correlation chunk and |L^-1 r|^2 shared, mu_k / MSE_k per target), sigma_k =
+ * sqrt(max(MSE_k, 1e-9)) (analytic.py:233), and EHVI = sum over the C cells of prod_k E[(min(Y_k, u_ck) - l_ck)^+] --
+ * the reference's sum over 2^m subsets of psi / nu factors, as one product.  Targets are maximised as given.
+ *   m            targets of the committed model (n_targets), 2 <= m <= BOGP_MAX_TARGETS
+ *   lower/upper  C x m row-major HOST arrays of cell bounds, 1 <= C <= BOGP_MAX_EHVI_CELLS; lower finite, upper >= lower
+ *                and may be +inf (the exact limit; the reference clamps it to 1e10, :236-238); NaN is invalid
+ *   k            1 <= k <= BOGP_MAX_TOPK winners: best_val / best_idx (k) follow bogp_sweep_topk's rules (rank 0 is the
+ *                argmax, ties -> lower index, NaN maximal, slots beyond M are (-inf, -1))
+ *   ehvi_out (M), mu_out (M x m), mse_out (M x m): optional HOST buffers (NULL to skip)
+ * The time of the EHVI kernel is reported as acquisition_ms by bogp_last_timing.                               */
+#define BOGP_MAX_EHVI_CELLS 65536
+int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
+                    int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
+
 /* ---- input-gradient of the posterior at ONE point ---------------------------------------------------
  * Replaces GaussianProcess.gradient(x) (gpr.py:537-576, corr_dx :600-661): dmu (d), dmse (d).            */
 int bogp_gradient(bogp_handle* h, const double* x, double* dmu, double* dmse);
