@@ -6,6 +6,8 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
   bogp.acquisition.{EI,PI,EpsilonPI,UCB,MGFI} <-> bayes_optim.acquisition.acquisition_fun.*
   bogp.EHVI                      <-> bayes_optim.multi_objective.analytic.EHVI (MOBO's criterion; one device pass)
   bogp.pareto                    Pareto front + cell decomposition of the non-dominated region (numpy)
+  bogp.RandomForest              <-> bayes_optim.surrogate.RandomForest        (scikit-learn fits, the device predicts;
+                                 bogp.forest: packing, mixed-space sweep; built on first access, sklearn imported lazily)
   bogp.optim.argmax_restart      <-> bayes_optim.acquisition.optim.argmax_restart (+ optimizer="sweep")
   bogp.trend                     <-> bayes_optim.surrogate.trend
   bogp.install(bayes_optim)      re-points the reference's three extension points, ParallelBO's q-criterion loop and
@@ -17,9 +19,15 @@ a gfx950 device (or without the built library) raises -- there is no CPU fallbac
 """
 __version__ = "0.1.0"
 
-from . import _lib, acquisition, distributed, integration, optim, pareto  # noqa: E402,F401
+from . import _lib, acquisition, distributed, forest, integration, optim, pareto  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
 from .acquisition import EHVI, EI, MGFI, PI, UCB, EpsilonPI  # noqa: E402,F401
 from .optim import argmax_restart, batch_argmax, device_sample, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated  # noqa: E402,F401
 from .integration import install, uninstall  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401
+
+
+def __getattr__(name):  # bogp.RandomForest subclasses scikit-learn's regressor: built (and scikit-learn imported) on first access
+    if name == "RandomForest":
+        return forest.RandomForest
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

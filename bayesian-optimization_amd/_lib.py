@@ -25,6 +25,7 @@ MAX_TARGETS = 8
 MAX_TOPK = 32
 MAX_EHVI_CELLS = 65536  # BOGP_MAX_EHVI_CELLS: cells one bogp_sweep_ehvi call takes
 COMM_ID_BYTES = 128
+COLUMN_REAL, COLUMN_DISCRETE = 0, 1  # BOGP_COLUMN_*: column kinds of bogp_candidates_generate_mixed
 SCALES = {"linear": 0, None: 0, "log": 1, "log10": 2, "logit": 3, "bilog": 4}  # Real.scale (variable.py:43-55)
 
 _dp = C.POINTER(C.c_double)
@@ -65,6 +66,12 @@ SIGNATURES = {
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_forest_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _lp, _ip, _dp, _ip, _ip, _dp, _ip]),
+    "bogp_forest_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "bogp_forest_leaves": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp]),
+    "bogp_forest_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _dp]),
+    "bogp_forest_info": (C.c_int, [C.c_void_p, _lp]),
+    "bogp_candidates_generate_mixed": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int64, C.c_uint64, C.c_int64]),
     "bogp_gradient": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "bogp_gradient_batch": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "bogp_hessian": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -572,6 +579,77 @@ class Engine:
         if return_moments:
             out += (mu, mse)
         return out
+
+    # -- packed regression forest (the second model kind; bogp_api_forest.hip) ----------------------------------
+    def forest_set(self, d: int, tree_offset, feature, threshold, left, right, value, test=None):
+        """T trees over d columns as flat arrays (scikit-learn's layout per tree; `forest.pack` builds them).  Establishes d for
+        the candidate calls.  Raises on a malformed forest: validation is host-side, nothing is launched."""
+        off = np.ascontiguousarray(tree_offset, dtype=np.int64)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        feature, left, right = i32(feature), i32(left), i32(right)
+        threshold, value = _f64(threshold).ravel(), _f64(value).ravel()
+        n = int(off[-1]) if len(off) else 0
+        if not (len(feature) == len(left) == len(right) == len(threshold) == len(value) == n):
+            raise ValueError("the node arrays must all have tree_offset[-1] = %d entries" % n)
+        tst = None if test is None else i32(test)
+        if tst is not None and len(tst) != n:
+            raise ValueError("test must have %d entries" % n)
+        self._check(self._lib.bogp_forest_set(self._h, len(off) - 1, int(d), off.ctypes.data_as(_lp), feature.ctypes.data_as(_ip),
+                                              _ptr(threshold), left.ctypes.data_as(_ip), right.ctypes.data_as(_ip), _ptr(value),
+                                              None if tst is None else tst.ctypes.data_as(_ip)))  # fmt: skip
+        if int(d) != self.d:
+            self.M = 0
+        self.d, self.N, self.forest_T = int(d), 0, len(off) - 1
+        self._last_q, self._last_topk = -1, (-1, -1)
+
+    def forest_info(self) -> dict:
+        out = np.zeros(7, dtype=np.int64)
+        self._check(self._lib.bogp_forest_info(self._h, out.ctypes.data_as(_lp)))
+        return dict(zip(("T", "d", "nodes", "leaves", "depth", "bytes", "lds_bytes"), (int(v) for v in out)))
+
+    def forest_predict(self, eval_MSE=True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        mu = np.empty(self.M)
+        mse = np.empty(self.M) if eval_MSE else None
+        self._check(self._lib.bogp_forest_predict(self._h, _ptr(mu), _ptr(mse)))
+        return mu, mse
+
+    def forest_leaves(self, first_row: int, n: int) -> np.ndarray:
+        """Per-tree predictions (n, T) of candidate rows [first_row, first_row + n)."""
+        out = np.empty((int(n), int(getattr(self, "forest_T", 0))))
+        self._check(self._lib.bogp_forest_leaves(self._h, int(first_row), int(n), _ptr(out)))
+        return out
+
+    def forest_sweep_topk(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, k: int = 1, return_values=False):
+        """q criteria of the forest's moments over the current candidates: (values (q, k), indices (q, k)[, acq (q, M)])."""
+        q = len(acq)
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        best = np.empty((q, int(k)))
+        idx = np.empty((q, int(k)), dtype=np.int64)
+        vals = np.empty((q, self.M)) if return_values else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(
+            self._lib.bogp_forest_sweep_topk(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
+                                             int(k), _ptr(best), idx.ctypes.data_as(_lp), _ptr(vals))
+        )  # fmt: skip
+        self._last_q = q
+        if int(k) > 1:
+            self._last_topk = (q, int(k))
+        return (best, idx, vals) if return_values else (best, idx)
+
+    def generate_candidates_mixed(self, kind, lo, hi, n_levels, M: int, seed: int = 0, first_row: int = 0):
+        """M rows of a mixed space drawn ON the device: column k is real (kind 0: lo + (hi - lo) u, then the candidate transform)
+        or discrete (kind 1: index = min(floor(u L), L - 1), value lo + index (hi - lo) / (L - 1)) -- bogp_candidates_generate_mixed."""
+        kind = np.ascontiguousarray(kind, dtype=np.int32).ravel()
+        nl = np.ascontiguousarray(n_levels, dtype=np.int32).ravel()
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if not (len(kind) == len(nl) == len(lo) == len(hi) == self.d):
+            raise ValueError("kind, lo, hi and n_levels must have %d entries" % self.d)
+        self._check(self._lib.bogp_candidates_generate_mixed(self._h, kind.ctypes.data_as(_ip), _ptr(lo), _ptr(hi), nl.ctypes.data_as(_ip),
+                                                             int(M), C.c_uint64(int(seed) & (2**64 - 1)), int(first_row)))  # fmt: skip
+        self.M = int(M)
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._keep = None
 
     def gradient(self, x):
         x = _f64(x).ravel()

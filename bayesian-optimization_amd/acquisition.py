@@ -25,6 +25,7 @@ import numpy as np
 from scipy.special import ndtr
 
 from . import _lib
+from . import forest as _forest
 
 
 class norm:  # noqa: N801 -- the two members of scipy.stats.norm the chain rules use, without its argument-checking machinery
@@ -143,6 +144,11 @@ class AcquisitionFunction:
         return vals, mom
 
     def __call__(self, X, return_dx: bool = False):
+        if _forest.is_forest_model(self._model):  # moments of the packed forest (bogp_forest_sweep_topk); rows keep their level labels
+            if return_dx:
+                raise NotImplementedError("a forest has no input gradient (the reference's RandomForest has none either): return_dx=True is not served")
+            v = _forest.criterion_values(self, X)
+            return v.reshape(self._single_row_shape) if len(v) == 1 else v.reshape(-1, 1)
         X = self.check_X(X)
         if X.shape[0] == 1:  # the one-point call of the reference's inner optimisers: one device round trip
             fused = self._fused_point(X)

@@ -126,10 +126,12 @@ extern "C" void bogp_destroy(bogp_handle* h) {
   if (h->stream_upd) (void)hipStreamSynchronize(h->stream_upd);
   dfree(h->dXs_owned); dfree(h->dss_part); dfree(h->dbounds); dfree(h->dsobol); dfree(h->dxform);
   for (int b = 0; b < 2; ++b) { dfree(h->drT[b]); dfree(h->dmu_part[b]); dfree(h->dw_part[b]); }
-  dfree(h->dblk_val); dfree(h->dblk_idx); dfree(h->dmu_out); dfree(h->dmse_out); dfree(h->dacq_out); dfree(h->dehvi_cells);
+  dfree(h->dblk_val); dfree(h->dblk_idx); dfree(h->dmu_out); dfree(h->dmse_out); dfree(h->dacq_out); dfree(h->dehvi_cells); dfree(h->dforest_words); dfree(h->dforest_tree);
   dfree(h->dbest_val); dfree(h->dbest_idx); dfree(h->dtopk_val); dfree(h->dtopk_idx); dfree(h->dcounter); h->dinfo = nullptr; dfree(h->dscal); dfree(h->dgrad_partial); dfree(h->dbatch);
   dfree(h->dTt); dfree(h->dCS); dfree(h->duu); dfree(h->dmtrend); dfree(h->dtpart[0]); dfree(h->dtpart[1]);
   for (auto e : h->ev) (void)hipEventDestroy(e);
+  for (auto e : h->forest_ev)
+    if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; ++i)
     if (h->ev_chol[i]) (void)hipEventDestroy(h->ev_chol[i]);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -156,6 +158,7 @@ extern "C" int bogp_set_train(bogp_handle* h, const double* X, const double* y, 
   if (!h) return BOGP_ERR_INVALID;
   if (!X || !y || N <= 0 || d <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_set_train: X, y must be non-null and N, d > 0");
   if (n_targets < 1 || n_targets > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_set_train: n_targets = %d outside [1, %d]", n_targets, BOGP_MAX_TARGETS);
+  if (h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_set_train: the handle holds a forest (bogp_forest_set); a Gaussian process takes a handle of its own");
   if (d > BOGP_MAX_DIM) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_set_train: d = %d > %d: the sweep producer keeps a 64 x d candidate tile in the CU's 160 KB of LDS", d, BOGP_MAX_DIM);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -1,0 +1,314 @@
+// bogp_api_forest.hip -- the C ABI of libbogp.so (include/bogp.h) for the second model kind of a handle, a packed regression
+// forest: bogp_forest_set (validation + packing, host only), bogp_forest_predict / _leaves / _sweep_topk (k_forest of
+// kernels_forest.hip over the current candidates, then the argmax / top-k passes of kernels_acq.hip) and the candidate generator
+// of mixed spaces, bogp_candidates_generate_mixed.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/bogp.h"
+#include "bogp_handle.h"
+#include "bogp_internal.h"
+
+using namespace bogp;
+
+bool bogp::has_dim(const bogp_handle* h) { return h->dX != nullptr || h->forest_T > 0; }
+
+static constexpr size_t FOREST_LDS_LIMIT = 160 * 1024 - 128;  // the CU's LDS less the kernel's static words
+
+// largest float32 that is <= t (t finite or infinite, not NaN): x <= t holds for a float32 x exactly when x <= this
+static float round_down_f32(double t) {
+  float f = (float)t;
+  if ((double)f > t) f = std::nextafterf(f, -INFINITY);
+  return f;
+}
+
+extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree_offset, const int32_t* feature,
+                               const double* threshold, const int32_t* left, const int32_t* right, const double* value,
+                               const int32_t* test) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (h->dX) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: the handle holds a Gaussian-process training set; a forest takes a handle of its own");
+  if (T < 2) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: T = %d trees; the variance over the trees (ddof = 1) needs T >= 2", T);
+  if (d < 1 || d > BOGP_MAX_DIM) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: d = %d outside [1, %d]", d, BOGP_MAX_DIM);
+  if (!tree_offset || !feature || !threshold || !left || !right || !value) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree_offset, feature, threshold, left, right and value must be non-null");
+  if (tree_offset[0] != 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree_offset[0] must be 0");
+  std::vector<unsigned long long> words;
+  std::vector<ForestTree> trees((size_t)T);
+  int tree_words = 0, depth_max = 0;
+  int64_t nodes_total = 0, leaves_total = 0;
+  std::vector<int> order, newidx, dep;
+  for (int t = 0; t < T; ++t) {
+    const int64_t o = tree_offset[t], n64 = tree_offset[t + 1] - o;
+    if (n64 < 1 || n64 > 65535) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d has %lld nodes (1 .. 65535)", t, (long long)n64);
+    const int n = (int)n64;
+    // breadth-first walk from the root: every node is reached at most once (no cycle, no shared subtree), the children of a
+    // node get adjacent new indices, unreachable nodes are dropped, and the depth of the tree bounds the kernel's walk
+    order.assign(1, 0);
+    newidx.assign((size_t)n, -1);
+    dep.assign((size_t)n, 0);
+    newidx[0] = 0;
+    int next = 1, nleaf = 0, depth = 0;
+    for (size_t qi = 0; qi < order.size(); ++qi) {
+      const int u = order[qi];
+      const int l = left[o + u], r = right[o + u];
+      if (l == -1) {
+        if (r != -1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a right child but no left child", t, u);
+        if (!std::isfinite(value[o + u])) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d leaf %d has a non-finite value", t, u);
+        ++nleaf;
+        continue;
+      }
+      if (l < 0 || l >= n || r < 0 || r >= n) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a child outside [0, %d)", t, u, n);
+      if (l == r || newidx[l] != -1 || newidx[r] != -1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d points at a node that is already reached (cycle or shared subtree)", t, u);
+      if (feature[o + u] < 0 || feature[o + u] >= d) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d splits on feature %d outside [0, %d)", t, u, feature[o + u], d);
+      const double thr = threshold[o + u];
+      if (std::isnan(thr)) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a NaN threshold", t, u);
+      if (test && test[o + u] != 0) {
+        if (test[o + u] != 1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has test %d (0: x <= thr, 1: x != thr)", t, u, test[o + u]);
+        if (!(thr >= 0 && thr < 16777216.0 && thr == std::floor(thr))) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d: a level index must be an integer in [0, 2^24)", t, u);
+      }
+      newidx[l] = next;
+      newidx[r] = next + 1;
+      next += 2;
+      dep[l] = dep[r] = dep[u] + 1;
+      if (dep[l] > depth) depth = dep[l];
+      order.push_back(l);
+      order.push_back(r);
+    }
+    const int nn = next;  // reachable nodes (<= n <= 65535: a child index fits 16 bits)
+    const size_t base = words.size();
+    if (base + (size_t)nn + nleaf > (size_t)INT32_MAX) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_set: the packed forest exceeds 2^31 words");
+    words.resize(base + (size_t)nn + nleaf);
+    int li = 0;
+    for (size_t qi = 0; qi < order.size(); ++qi) {  // order[qi] has new index qi (children are appended pairwise as they are numbered)
+      const int u = order[qi];
+      uint32_t x, w;
+      if (left[o + u] == -1) {
+        x = (uint32_t)li;
+        w = 0u;
+        double v = value[o + u];
+        unsigned long long bits;
+        memcpy(&bits, &v, 8);
+        words[base + nn + li] = bits;
+        ++li;
+      } else {
+        const bool eq = test && test[o + u] == 1;
+        const float tf = eq ? (float)threshold[o + u] : round_down_f32(threshold[o + u]);
+        memcpy(&x, &tf, 4);
+        w = (eq ? 0x80000000u : 0u) | ((uint32_t)feature[o + u] << 16) | (uint32_t)newidx[left[o + u]];
+      }
+      words[base + newidx[u]] = ((unsigned long long)w << 32) | x;  // uint2 {x, y} in memory order
+    }
+    trees[t] = ForestTree{(int)base, nn, nleaf, depth, 1.0 / (double)(t + 1), 0.0};
+    if (nn + nleaf > tree_words) tree_words = nn + nleaf;
+    if (depth > depth_max) depth_max = depth;
+    nodes_total += nn;
+    leaves_total += nleaf;
+  }
+  const size_t lds = forest_lds_bytes(d, tree_words);
+  if (lds > FOREST_LDS_LIMIT)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_set: two buffers of the largest tree (%d words) and 256 rows of %d features need %zu bytes of LDS (limit %zu)", tree_words, d, lds, FOREST_LDS_LIMIT);
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // a forest call in flight still reads the old forest
+  int e;
+  if ((e = ensure(h, &h->dforest_words, &h->forest_words_cap, words.size()))) return e;
+  if ((e = ensure(h, &h->dforest_tree, &h->forest_tree_cap, (size_t)T))) return e;
+  HIPCHK(h, hipMemcpy(h->dforest_words, words.data(), words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->dforest_tree, trees.data(), (size_t)T * sizeof(ForestTree), hipMemcpyHostToDevice));
+  if (h->forest_T && d != h->d) {  // rows of another width are not candidates of this forest
+    if (h->hXs_lazy) {
+      HIPCHK(h, hipStreamSynchronize(h->stream_copy));
+      h->hXs_lazy = nullptr;
+    }
+    h->dXs = nullptr;
+    h->M = 0;
+    h->h_xform.clear();
+  }
+  invalidate_sweep_results(h);
+  h->forest_T = T;
+  h->d = d;
+  h->forest_tree_words = tree_words;
+  h->forest_depth = depth_max;
+  h->forest_nodes = nodes_total;
+  h->forest_leaves = leaves_total;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_forest_info(const bogp_handle* h, int64_t* out) {
+  if (!h || !out) return BOGP_ERR_INVALID;
+  out[0] = h->forest_T;
+  out[1] = h->forest_T ? h->d : 0;
+  out[2] = h->forest_nodes;
+  out[3] = h->forest_leaves;
+  out[4] = h->forest_depth;
+  out[5] = (h->forest_nodes + h->forest_leaves) * 8 + (int64_t)h->forest_T * (int64_t)sizeof(ForestTree);
+  out[6] = h->forest_T ? (int64_t)forest_lds_bytes(h->d, h->forest_tree_words) : 0;
+  return BOGP_OK;
+}
+
+// k_forest over rows [row0, row0 + nrows) of the current candidates, timed by two events (bogp_last_timing: acquisition_ms)
+static int run_forest(bogp_handle* h, const char* who, ForestArgs& a, int64_t row0, int64_t nrows) {
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "%s: no forest: call bogp_forest_set first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
+  if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
+  if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
+  for (int i = 0; i < 2; ++i)
+    if (!h->forest_ev[i]) HIPCHK(h, hipEventCreate(&h->forest_ev[i]));
+  a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d;
+  a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
+  HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
+  HIPCHK(h, launch_forest(a, h->stream));
+  HIPCHK(h, hipEventRecord(h->forest_ev[1], h->stream));
+  return BOGP_OK;
+}
+
+static int forest_timing(bogp_handle* h) {  // after the stream has been waited for
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->forest_ev[0], h->forest_ev[1]));
+  h->timing_pending = false;
+  h->t_corr_ms = h->t_contract_ms = 0;
+  h->t_acq_ms = ms;
+  h->n_chunks = 1;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_forest_predict(bogp_handle* h, double* mu, double* mse) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!mu) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: mu must be non-null");
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: no forest: call bogp_forest_set first");
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: no candidates");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t M = h->M;
+  int e;
+  if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M))) return e;
+  if ((e = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M))) return e;
+  ForestArgs a;
+  memset(&a, 0, sizeof(a));
+  a.mu_out = h->dmu_out; a.mse_out = mse ? h->dmse_out : nullptr; a.minimize = 1;
+  if ((e = run_forest(h, "bogp_forest_predict", a, 0, M))) return e;
+  HIPCHK(h, hipMemcpyAsync(mu, h->dmu_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (mse) HIPCHK(h, hipMemcpyAsync(mse, h->dmse_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return forest_timing(h);
+}
+
+extern "C" int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, double* per_tree) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!per_tree || n < 1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_leaves: per_tree must be non-null and n > 0");
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_leaves: no forest: call bogp_forest_set first");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)n * h->forest_T;
+  int e;
+  if ((e = ensure(h, &h->dbatch, &h->batch_cap, cnt))) return e;
+  ForestArgs a;
+  memset(&a, 0, sizeof(a));
+  a.leaves_out = h->dbatch; a.minimize = 1;
+  if ((e = run_forest(h, "bogp_forest_leaves", a, first_row, n))) return e;
+  HIPCHK(h, hipMemcpyAsync(per_tree, h->dbatch, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return forest_timing(h);
+}
+
+extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+                                      int k, double* best_val, int64_t* best_idx, double* acq_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (k <= 0 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: k = %d outside [1, %d]", k, BOGP_MAX_TOPK);
+  if (q <= 0 || q > BOGP_MAX_Q || !acq_id || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: 0 < q <= %d and non-null acq_id / best_val / best_idx required", BOGP_MAX_Q);
+  for (int i = 0; i < q; ++i) {
+    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: unknown acquisition id %d", acq_id[i]);
+    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;  // epsilon = 0 is plain PI
+    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
+      FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: acquisition parameter %d must be > 0 (the reference asserts alpha/epsilon/t > 0)", i);
+  }
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: no forest: call bogp_forest_set first");
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: no candidates");
+  HIPCHK(h, hipSetDevice(h->device));
+  invalidate_sweep_results(h);
+  const int64_t M = h->M, nblk = (M + 255) / 256;
+  const bool keep = k > 1 || acq_out;
+  hipStream_t st = h->stream;
+  int e;
+  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * (nblk + 1)))) return e;
+  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * (nblk + 1)))) return e;
+  if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
+  if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
+  if (keep && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e;
+  ForestArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = q;
+  for (int i = 0; i < q; ++i) {
+    a.acq_id[i] = acq_id[i];
+    a.acq_par[i] = acq_par ? acq_par[i] : 0.0;
+  }
+  a.plugin = plugin; a.minimize = minimize;
+  a.acq_out = keep ? h->dacq_out : nullptr;
+  a.blk_val = h->dblk_val; a.blk_idx = h->dblk_idx; a.nblk_total = nblk;
+  if ((e = run_forest(h, "bogp_forest_sweep_topk", a, 0, M))) return e;
+  // the block records -> the argmax per criterion (dbest_*: what bogp_exchange_argmax packs)
+  HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, q, h->dbest_val, h->dbest_idx, st));
+  if (k == 1) {
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk (dtopk_*: what bogp_exchange_topk packs)
+    if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  }
+  if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->last_q = q;
+  if (k > 1) {
+    h->last_topk_q = q;
+    h->last_topk_k = k;
+  }
+  for (int i = 0; i < q * k; ++i)
+    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
+      best_val[i] = -INFINITY;
+      best_idx[i] = -1;
+    }
+  return forest_timing(h);
+}
+
+extern "C" int bogp_candidates_generate_mixed(bogp_handle* h, const int* kind, const double* lo, const double* hi, const int* n_levels,
+                                              int64_t M, uint64_t seed, int64_t first_row) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_candidates_generate_mixed";
+  if (!has_dim(h)) FAIL(h, BOGP_ERR_INVALID, "%s: call bogp_forest_set or bogp_set_train first (d is unknown)", who);
+  if (!kind || !lo || !hi || !n_levels || M <= 0 || first_row < 0) FAIL(h, BOGP_ERR_INVALID, "%s: kind, lo, hi and n_levels must be non-null, M > 0, first_row >= 0", who);
+  const int d = h->d;
+  std::vector<double> spec((size_t)3 * d);
+  for (int k = 0; k < d; ++k) {
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && lo[k] <= hi[k])) FAIL(h, BOGP_ERR_INVALID, "%s: bad bounds in column %d", who, k);
+    if (kind[k] == BOGP_COLUMN_REAL) {
+      spec[2 * d + k] = 0.0;
+    } else if (kind[k] == BOGP_COLUMN_DISCRETE) {
+      if (n_levels[k] <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: column %d is discrete with n_levels = %d (must be > 0)", who, k, n_levels[k]);
+      spec[2 * d + k] = (double)n_levels[k];
+    } else {
+      FAIL(h, BOGP_ERR_INVALID, "%s: column %d has kind %d (BOGP_COLUMN_REAL or BOGP_COLUMN_DISCRETE)", who, k, kind[k]);
+    }
+    spec[k] = lo[k];
+    spec[d + k] = hi[k];
+  }
+  invalidate_sweep_results(h);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->hXs_lazy) {  // pending copies of the old candidates must not land later
+    HIPCHK(h, hipStreamSynchronize(h->stream_copy));
+    h->hXs_lazy = nullptr;
+  }
+  int e;
+  if ((e = ensure(h, &h->dXs_owned, &h->xs_cap, (size_t)M * d))) return e;
+  if ((e = ensure(h, &h->dbounds, &h->bounds_cap, (size_t)3 * d))) return e;
+  HIPCHK(h, hipMemcpyAsync(h->dbounds, spec.data(), spec.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, launch_generate_mixed(h->dXs_owned, M * d, d, h->dbounds, h->dbounds + d, h->dbounds + 2 * d, seed,
+                                  (uint64_t)first_row * (uint64_t)d, h->stream));
+  if (!h->h_xform.empty() && (int)h->h_xform.size() == 4 * d)
+    HIPCHK(h, launch_candidates_transform(h->dXs_owned, M * d, d, h->dxform, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // spec is host memory of this call
+  h->dXs = h->dXs_owned;
+  h->M = M;
+  return BOGP_OK;
+}

@@ -70,7 +70,7 @@ extern "C" int bogp_candidates_upload_lazy(bogp_handle* h, const double* Xs, int
   if (!h) return BOGP_ERR_INVALID;
   invalidate_sweep_results(h);
   if (!Xs || M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload_lazy: Xs must be non-null and M > 0");
-  if (!h->dX) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload_lazy: call bogp_set_train first (d is unknown)");
+  if (!has_dim(h)) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload_lazy: call bogp_set_train first (d is unknown)");
   HIPCHK(h, hipSetDevice(h->device));
   int e = lazy_drop(h);
   if (e) return e;
@@ -91,7 +91,7 @@ extern "C" int bogp_candidates_upload_lazy(bogp_handle* h, const double* Xs, int
 extern "C" int bogp_candidates_upload(bogp_handle* h, const double* Xs, int64_t M) {
   if (!h) return BOGP_ERR_INVALID;
   invalidate_sweep_results(h);
-  if (!h->dX) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload: call bogp_set_train first (d is unknown)");
+  if (!has_dim(h)) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload: call bogp_set_train first (d is unknown)");
   if (!Xs || M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_upload: Xs must be non-null and M > 0");
   HIPCHK(h, hipSetDevice(h->device));
   int e = lazy_drop(h);
@@ -107,7 +107,7 @@ extern "C" int bogp_candidates_upload(bogp_handle* h, const double* Xs, int64_t 
 // shared front end of the three on-device generators: validates the box, sizes the candidate buffer, stages lo / hi
 static int generate_prepare(bogp_handle* h, const char* who, const double* lo, const double* hi, int64_t M, int64_t first) {
   invalidate_sweep_results(h);
-  if (!h->dX) FAIL(h, BOGP_ERR_INVALID, "%s: call bogp_set_train first (d is unknown)", who);
+  if (!has_dim(h)) FAIL(h, BOGP_ERR_INVALID, "%s: call bogp_set_train first (d is unknown)", who);
   if (!lo || !hi || M <= 0 || first < 0) FAIL(h, BOGP_ERR_INVALID, "%s: bounds must be non-null, M > 0, first row/index >= 0", who);
   const int d = h->d;
   for (int k = 0; k < d; ++k)
@@ -125,7 +125,7 @@ static int generate_prepare(bogp_handle* h, const char* who, const double* lo, c
 extern "C" int bogp_candidates_set_transform(bogp_handle* h, const int* scale, const int* precision, const double* lo,
                                              const double* hi) {
   if (!h) return BOGP_ERR_INVALID;
-  if (!h->dX) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_set_transform: call bogp_set_train first (d is unknown)");
+  if (!has_dim(h)) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_set_transform: call bogp_set_train first (d is unknown)");
   HIPCHK(h, hipSetDevice(h->device));
   if (!scale && !precision) {  // back to plain designs
     h->h_xform.clear();

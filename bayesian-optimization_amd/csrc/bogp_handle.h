@@ -25,6 +25,8 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
 int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
               bool want_acq_out, bool need_var = true, bool sync = true, const EhviArgs* eh = nullptr);
 void invalidate_sweep_results(bogp_handle* h);
+// the candidate calls need the row width d: from bogp_set_train or from bogp_forest_set
+bool has_dim(const bogp_handle* h);
 }
 
 struct bogp_handle {
@@ -115,6 +117,15 @@ struct bogp_handle {
   size_t blk_val_cap = 0, blk_idx_cap = 0, mu_out_cap = 0, mse_out_cap = 0, acq_out_cap = 0;
   double* dehvi_cells = nullptr;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
   size_t ehvi_cells_cap = 0;
+
+  // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
+  // owns `d` (a handle carries a GP training set or a forest, never both)
+  int forest_T = 0, forest_tree_words = 0, forest_depth = 0;
+  int64_t forest_nodes = 0, forest_leaves = 0;
+  unsigned long long* dforest_words = nullptr;
+  bogp::ForestTree* dforest_tree = nullptr;
+  size_t forest_words_cap = 0, forest_tree_cap = 0;
+  hipEvent_t forest_ev[2] = {nullptr, nullptr};  // around k_forest of the last forest call
 
   // polynomial trend bases with p > 1 columns (linear / quadratic; the constant basis keeps its scalar fast path)
   int trend = BOGP_TREND_CONSTANT, p = 1;  // committed

@@ -100,6 +100,38 @@ struct EhviArgs {
 };
 hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
 
+// a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
+// the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
+struct ForestTree {  // one tree of the packed forest
+  int first, n_nodes, n_leaves, depth;  // first word; records; values behind them; longest root-to-leaf path (bounds the walk)
+  double inv_count;                     // 1 / (t + 1): the running mean's weight when tree t arrives
+  double pad;
+};
+struct ForestArgs {
+  const double* Xs;               // candidates, M x d row-major
+  int64_t M;                      // rows of Xs
+  int64_t row0, nrows;            // rows [row0, row0 + nrows) are evaluated by this launch
+  int d;
+  const unsigned long long* words;  // the packed trees: per tree [n_nodes node records | n_leaves leaf values (double bits)]
+  const ForestTree* tree;         // [T]
+  int T;
+  int tree_words;                 // largest n_nodes + n_leaves of a tree: one LDS buffer
+  double* mu_out;                 // [M] or null (indexed by the global row)
+  double* mse_out;                // [M] or null
+  double* leaves_out;             // [nrows][T] per-tree predictions or null (indexed by row - row0)
+  int q;                          // 0: moments only
+  int acq_id[64];
+  double acq_par[64];
+  double plugin;
+  int minimize;
+  double* acq_out;                // [q][M] or null
+  double* blk_val;                // [q][nblk_total]
+  int64_t* blk_idx;
+  int64_t nblk_total;
+};
+size_t forest_lds_bytes(int d, int tree_words);  // dynamic LDS of one workgroup of k_forest
+hipError_t launch_forest(const ForestArgs& a, hipStream_t st);
+
 // the fused small-N sweep (kernels_small.hip): one launch = producer + contraction + posterior + q criteria + argmax
 struct SmallArgs {
   const double* Xs;          // candidates, M x d row-major
@@ -149,6 +181,10 @@ hipError_t launch_generate_uniform(double* Xs, int64_t n_elem, int d, const doub
 hipError_t launch_generate_lhs(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, uint64_t seed,
                                uint64_t first_elem, uint64_t n_strata, hipStream_t st);
 hipError_t launch_candidates_transform(double* Xs, int64_t n_elem, int d, const double* spec, hipStream_t st);
+// mixed spaces: column k is real (levels[k] == 0: lo + (hi - lo) u) or discrete with levels[k] = L levels
+// (index = min(floor(u L), L - 1), value lo + index (hi - lo) / (L - 1)); levels holds d doubles
+hipError_t launch_generate_mixed(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, const double* levels,
+                                 uint64_t seed, uint64_t first_elem, hipStream_t st);
 hipError_t launch_generate_sobol(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, const uint64_t* sv,
                                  int bits, uint64_t first_elem, hipStream_t st);
 

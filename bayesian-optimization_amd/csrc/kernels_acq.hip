@@ -233,6 +233,50 @@ hipError_t launch_generate_uniform(double* Xs, int64_t n_elem, int d, const doub
   return hipGetLastError();
 }
 
+// Points of a MIXED space from the same stream (SearchSpace._sample column by column: Real.sample, variable.py:240-248, and
+// _Discrete.sample, :277-278, whose randint(0, L) every Integer / Ordinal / Discrete / Subset / Bool variable maps through its
+// levels).  Element E and its u are those of k_generate_uniform; a column with levels[k] = L > 0 is discrete:
+// index = min(floor(u L), L - 1) and x = lo + index * ((hi - lo) / (L - 1)) (lo for L = 1) -- lo + index for an Integer
+// column [lo, lo + L - 1], the level index itself for lo = 0, hi = L - 1; a column with levels[k] = 0 is real, lo + (hi - lo) u.
+// A different stream from np.random.randint: no parity with the reference's draws, as for the uniform generator.
+__global__ __launch_bounds__(256) void k_generate_mixed(double* __restrict__ Xs, int64_t n_elem, int d,
+                                                        const double* __restrict__ lo, const double* __restrict__ hi,
+                                                        const double* __restrict__ levels, uint64_t seed, uint64_t first_elem) {
+#pragma clang fp contract(off)
+  const uint64_t P = (first_elem >> 1) + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (2 * P >= first_elem + (uint64_t)n_elem) return;
+  uint32_t w[4];
+  philox4x32_10((uint32_t)P, (uint32_t)(P >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint64_t E = 2 * P + h;
+    if (E < first_elem || E >= first_elem + (uint64_t)n_elem) continue;
+    const double u = ((double)(w[2 * h] >> 5) * 67108864.0 + (double)(w[2 * h + 1] >> 6)) * (1.0 / 9007199254740992.0);
+    const int k = (int)(E % (uint64_t)d);
+    const double width = hi[k] - lo[k];
+    const double L = levels[k];
+    double x;
+    if (L > 0.0) {
+      const double scaled = u * L;
+      const double index = fmin(floor(scaled), L - 1.0);
+      const double step = L > 1.0 ? width / (L - 1.0) : 0.0;
+      const double off = index * step;
+      x = lo[k] + off;
+    } else {
+      const double scaled = width * u;
+      x = lo[k] + scaled;
+    }
+    Xs[E - first_elem] = x;
+  }
+}
+
+hipError_t launch_generate_mixed(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, const double* levels,
+                                 uint64_t seed, uint64_t first_elem, hipStream_t st) {
+  const int64_t npair = (n_elem + 1) / 2 + 1;
+  hipLaunchKernelGGL(k_generate_mixed, dim3((unsigned)((npair + 255) / 256)), 256, 0, st, Xs, n_elem, d, lo, hi, levels, seed, first_elem);
+  return hipGetLastError();
+}
+
 // Latin hypercube in a box (RealSpace._sample method "LHS", search_space.py:747-751, which calls pyDOE's lhs:
 // one point per stratum and dimension, strata shuffled independently per dimension).  Counter-based so that rank
 // shards are independent: row i of dimension k lands in stratum pi_k(i), a keyed pseudo-random PERMUTATION of

@@ -6,6 +6,8 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
                                                                              hands everything else to the original)
   bayes_optim.{base,bayes_opt,extension}.AcquisitionFunction -> a per-MODEL dispatching namespace (below)
   ParallelBO._batch_arg_max_acquisition         -> fused_batch_arg_max_acquisition
+  BaseBO._create_acquisition                    -> forest_create_acquisition (this package's criteria for a RandomForest model
+                                                   under "sweep" / "sweep-device"; the original otherwise, "MIES" included)
   MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
                                                    under the sweep family; the reference's EHVI otherwise)
   bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess -> a dispatching class that builds
@@ -43,6 +45,7 @@ from copy import copy
 import numpy as np
 
 from . import acquisition, optim
+from . import forest as _forest
 from .surrogate import GaussianProcess as _DeviceGP
 
 _SWEEPS = ("sweep",) + tuple(optim.DEVICE_DESIGNS)
@@ -118,6 +121,22 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
     return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
 
 
+def forest_create_acquisition(self, fun=None, par=None, return_dx=False, fixed=None):
+    """Drop-in body for `BaseBO._create_acquisition` (base.py:482-494): a `RandomForest` model (this package's or the reference's)
+    under "sweep" / "sweep-device" gets this package's criterion, which evaluates the packed forest on the device, wrapped exactly as
+    the original wraps the reference's.  Every other configuration -- "MIES" above all, the reference's default on mixed spaces --
+    runs the original unchanged."""
+    optimizer = getattr(self, "_optimizer", None)
+    name = fun if fun is not None else getattr(self, "_acquisition_fun", None)
+    if optimizer not in ("sweep", "sweep-device") or not _forest.is_forest_model(getattr(self, "model", None)) or not hasattr(acquisition, str(name)):
+        return _ORIGINAL["create"](self, fun=fun, par=par, return_dx=return_dx, fixed=fixed)
+    par = par if par is not None else copy(self._acquisition_par)
+    par.update({"model": self.model, "minimize": self.minimize})
+    criterion = getattr(acquisition, name)(**par)
+    return _ORIGINAL["base_partial_argument"](func=functools.partial(criterion, return_dx=return_dx), var_name=self.search_space.var_name,
+                                              fixed=fixed, reduce_output=return_dx)  # fmt: skip
+
+
 def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=100, n_restart=10, wait_iter=3,
                           optimizer="BFGS", logger=None):
     """`bayes_optim.base.argmax_restart` after `install()`.
@@ -129,7 +148,13 @@ def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=10
     bogp criterion is an ordinary callable.  A reroute (`install(reroute_bfgs=...)`) only ever applies to an
     unconstrained "BFGS" call on a continuous space whose criterion is this package's."""
     original = _ORIGINAL["argmax"]
-    mine = optim.unwrap_criterion(obj_func)[0] is not None and optim.is_continuous(search_space)
+    crit = optim.unwrap_criterion(obj_func)[0]
+    if crit is not None and optimizer in _OURS and _forest.is_forest_model(getattr(crit, "model", None)):
+        # this package's criterion on a forest model (forest_create_acquisition): any space of Real / Integer / Ordinal / Discrete /
+        # Subset / Bool variables; what a forest sweep does not take is refused there by name
+        return optim.argmax_restart(obj_func, search_space, h=h, g=g, eval_budget=eval_budget, n_restart=n_restart,
+                                    wait_iter=wait_iter, optimizer=optimizer, logger=logger)  # fmt: skip
+    mine = crit is not None and optim.is_continuous(search_space)
     opt2, budget2 = optimizer, eval_budget
     if mine and optimizer == "BFGS" and h is None and g is None:
         opt2, budget2 = _effective(optimizer, eval_budget)
@@ -346,6 +371,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
                      mods=(bayes_optim, rbase, ropt, rsur), gp=(getattr(bayes_optim, "GaussianProcess", None), rsur.GaussianProcess),
                      surrogate=bool(surrogate), mobo_cls=None)  # fmt: skip
     rbase.argmax_restart = routed_argmax_restart
+    _ORIGINAL.update(create=rbase.BaseBO.__dict__["_create_acquisition"], base_cls=rbase.BaseBO, base_partial_argument=rbase.partial_argument)
+    rbase.BaseBO._create_acquisition = forest_create_acquisition
     if rmobo is not None and hasattr(rmobo, "MOBO"):
         _ORIGINAL.update(mobo_cls=rmobo.MOBO, mobo=rmobo.MOBO.__dict__["_create_acquisition"], partial_argument=rmobo.partial_argument)
         rmobo.MOBO._create_acquisition = mobo_create_acquisition
@@ -365,6 +392,7 @@ def uninstall():
         return
     pkg, rbase, ropt, rsur = _ORIGINAL["mods"]
     rbase.argmax_restart = _ORIGINAL["argmax"]
+    _ORIGINAL["base_cls"]._create_acquisition = _ORIGINAL["create"]
     for m in _ORIGINAL["acq_holders"]:
         m.AcquisitionFunction = _ORIGINAL["acq"]
     ropt.ParallelBO._batch_arg_max_acquisition = _ORIGINAL["batch"]

@@ -21,6 +21,7 @@ import numpy as np
 from scipy.optimize import fmin_l_bfgs_b
 
 from . import distributed
+from . import forest as _forest
 
 
 _TRANS = {  # Real.scale -> (forward, inverse) (variable.py:22-55)
@@ -227,6 +228,9 @@ def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0
     (values (q, k), global indices (q, k), points (q, k, d)), identical on every rank."""
     c0 = criteria[0]
     model = c0.model
+    if _forest.is_forest_model(model):  # rows in the reference's format; points come back as q lists of k rows
+        _forest._one_rank(group)
+        return _forest.sweep_topk_host(criteria, Xs, k)
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
     Xs = model._check_X(Xs)
@@ -250,6 +254,11 @@ def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, 
     its block of the design; (values (q, k), global rows (q, k), points (q, k, d)) are identical on every rank."""
     c0 = criteria[0]
     model = c0.model
+    if _forest.is_forest_model(model):  # `bounds` is the mixed search space; points come back as q lists of k rows in its format
+        _forest._one_rank(group, rank, world)
+        if method != "uniform":
+            raise NotImplementedError("method=%r: a forest model on a mixed space takes the uniform design only" % method)
+        return _forest.sweep_topk_device(criteria, bounds, int(M), int(k), seed)
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
     a, b_ = shard_bounds(int(M), rank, world)
@@ -284,6 +293,10 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
     points hold the free variables (the caller's `fillin_fixed_value` completes them, base.py:476).  `h` / `g` (constraints
     over the free variables, one point as a list): only host-sampled candidates the reference would accept as a restart's
     outcome (`feasible_rows`) enter the sweep; with none, `((), ())` -- the reference's "no feasible restart" answer."""
+    if _forest.is_forest_model(criteria[0].model):
+        _forest.check_optimizer("sweep", h, g, masks)
+        _forest._one_rank(group, rank, world)
+        return _forest.batch_argmax(criteria, search_space, eval_budget, history=history, k=k, design=design, seed=seed, Xs=Xs)
     if rank is None or world is None:
         rank, world = engine_rank_world(criteria[0].model.engine, group)
     if design is not None:  # "uniform" | "LHS" | "sobol": the candidates are drawn on the GPU(s) and never touch the host
@@ -397,6 +410,11 @@ def argmax_restart(
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
     """
     ours = optimizer in DEVICE_DESIGNS or optimizer in ("sweep", "sweep-BFGS", "sweep-device-BFGS")
+    fcrit, fmasks, _ = unwrap_criterion(obj_func)
+    if fcrit is not None and _forest.is_forest_model(getattr(fcrit, "model", None)) and (ours or optimizer == "BFGS"):
+        # a forest model (any space of Real / Integer / Ordinal / Discrete / Subset / Bool variables): "sweep" and "sweep-device"
+        # are served, everything else this package knows is refused with the limitation named
+        return _forest.argmax_restart(fcrit, search_space, eval_budget, optimizer, h=h, g=g, masks=fmasks)
     if is_ehvi(unwrap_criterion(obj_func)[0]) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS") and is_continuous(search_space):
         raise NotImplementedError("optimizer=%r needs an input gradient, which EHVI does not have: use 'sweep' or "
                                   "'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip

@@ -294,6 +294,54 @@ int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_
 int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
                     int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 
+/* ---- second model kind: a packed regression forest ---------------------------------------------------
+ * Replaces RandomForest.predict(X, eval_MSE=True) (surrogate/random_forest.py:124-155): scikit-learn's Tree.predict per
+ * tree on the row cast to float32, mu = mean over the T trees, MSE = std(ddof = 1)^2 over the trees -- and, on these
+ * moments, the criteria of bogp_sweep (acquisition_fun.py:52-64, 127-135, 153-176, 208-217, 265-290; EI's guard is the
+ * one of a model without sigma2, :166-169).  The trees are fitted on the host (scikit-learn); the device evaluates them.
+ * A handle carries a Gaussian process (bogp_set_train) OR a forest, never both: each call refuses the other's handle.
+ *
+ * `forest_set`: T >= 2 trees over d columns as flat arrays in scikit-learn's layout; tree t owns nodes
+ * [tree_offset[t], tree_offset[t + 1]) (at most 65535), child indices are relative to the tree, node 0 is its root, a
+ * leaf has left == right == -1 and predicts value[node].  test[node] (NULL: all 0) selects the node's rule:
+ *   0  x32 <= threshold -> left  (x32 = the row's entry rounded to float32, threshold a double: Tree.predict)
+ *   1  x32 != threshold -> left  (a one-hot column of level `threshold`, split at 0.5, rewritten onto the raw column
+ *      that holds the level INDEX; threshold must be an integer in [0, 2^24))
+ * The call validates on the host -- children inside their tree, every node reached at most once (no cycle), feature in
+ * [0, d), finite leaf values, no NaN threshold -- packs (8-byte nodes, thresholds rounded toward -inf to float32, which
+ * decides x32 <= threshold identically) and records each tree's depth, which bounds the kernel's walk.  A malformed
+ * forest returns BOGP_ERR_INVALID and launches nothing.  It establishes d for the candidate calls; a forest of another
+ * d drops the current candidates and transform.  NaN candidates are not supported: a NaN entry goes right under rule 0.
+ * `forest_predict`: mu (M), mse (M, may be NULL) of the current candidates, HOST buffers.
+ * `forest_leaves`: the T per-tree predictions of rows [first_row, first_row + n), n x T row-major (tests, diagnostics).
+ * `forest_sweep_topk`: q criteria (ids / parameters / plugin / minimize as bogp_sweep) over the current candidates and
+ * the k best rows of each: best_val / best_idx are q x k (rank 0 the argmax, ties -> lower index, NaN maximal, slots
+ * beyond M (-inf, -1)); acq_out (q x M) optional.  The winners stay on the device as those of bogp_sweep (k = 1) and
+ * bogp_sweep_topk (k > 1) do, for bogp_exchange_*.  A row's result depends on the row and the forest alone: rows that
+ * reach the same leaves get the same bits.  The kernel's time is reported as acquisition_ms by bogp_last_timing.
+ * `forest_info`: out[7] = {T, d, nodes, leaves, largest depth, bytes of the packed forest, LDS bytes of a workgroup}. */
+int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree_offset, const int32_t* feature, const double* threshold,
+                    const int32_t* left, const int32_t* right, const double* value, const int32_t* test);
+int bogp_forest_predict(bogp_handle* h, double* mu, double* mse);
+int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, double* per_tree);
+int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+                           int k, double* best_val, int64_t* best_idx, double* acq_out);
+int bogp_forest_info(const bogp_handle* h, int64_t* out);
+/* Candidates of a MIXED space drawn on the device (replaces SearchSpace._sample column by column: Real.sample,
+ * search_space/variable.py:240-248, and _Discrete.sample, :260-278, whose randint(0, L) every Integer / Ordinal /
+ * Discrete / Subset / Bool variable maps through its levels): the Philox stream of bogp_candidates_generate, element
+ * (row, k) a pure function of (seed, (first_row + row) * d + k).  Per column k:
+ *   BOGP_COLUMN_REAL      x = lo + (hi - lo) u, then the handle's scale / precision transform, as bogp_candidates_generate
+ *   BOGP_COLUMN_DISCRETE  index = min(floor(u L), L - 1), L = n_levels[k] > 0; x = lo + index (hi - lo) / (L - 1)
+ *                         (lo for L = 1): lo + index for an Integer column [lo, lo + L - 1]; the level index itself
+ *                         for lo = 0, hi = L - 1, which the host maps to the level's label
+ * as a double in the M x d matrix that bogp_candidates_read hands back.  Not np.random.randint's stream: no parity
+ * with the reference's draws is claimed, as for the uniform generator.                                            */
+#define BOGP_COLUMN_REAL 0
+#define BOGP_COLUMN_DISCRETE 1
+int bogp_candidates_generate_mixed(bogp_handle* h, const int* kind, const double* lo, const double* hi, const int* n_levels,
+                                   int64_t M, uint64_t seed, int64_t first_row);
+
 /* ---- input-gradient of the posterior at ONE point ---------------------------------------------------
  * Replaces GaussianProcess.gradient(x) (gpr.py:537-576, corr_dx :600-661): dmu (d), dmse (d).            */
 int bogp_gradient(bogp_handle* h, const double* x, double* dmu, double* dmse);
