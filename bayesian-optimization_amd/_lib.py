@@ -23,6 +23,7 @@ ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was wri
 MAX_Q = 64
 MAX_TARGETS = 8
 MAX_TOPK = 32
+LIFT_MAX_R, LIFT_MAX_RD = 64, 4096  # BOGP_LIFT_MAX_R / BOGP_LIFT_MAX_RD: reduced dimensions and r x D of a lift
 MAX_EHVI_CELLS = 65536  # BOGP_MAX_EHVI_CELLS: cells one bogp_sweep_ehvi call takes
 COMM_ID_BYTES = 128
 COLUMN_REAL, COLUMN_DISCRETE = 0, 1  # BOGP_COLUMN_*: column kinds of bogp_candidates_generate_mixed
@@ -66,6 +67,10 @@ SIGNATURES = {
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_lift_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "bogp_lift_clear": (C.c_int, [C.c_void_p]),
+    "bogp_lift_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _lp, _dp, _dp]),
+    "bogp_lift_last": (C.c_int, [C.c_void_p, _lp, _dp, _dp]),
     "bogp_forest_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _lp, _ip, _dp, _ip, _ip, _dp, _ip]),
     "bogp_forest_predict": (C.c_int, [C.c_void_p, _dp, _dp]),
     "bogp_forest_leaves": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp]),
@@ -579,6 +584,53 @@ class Engine:
         if return_moments:
             out += (mu, mse)
         return out
+
+    # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------
+    def set_lift(self, A, mean, center, lo, hi):
+        """The lift of the lifted sweeps that follow (bogp_lift_set): A (r, D) = pca.components_ with r = the model's d, mean (D),
+        center (D, or None = 0), lo / hi (D) the original box.  Stays on the engine until clear_lift()."""
+        A = _f64(A)
+        if A.ndim != 2 or A.shape[0] != self.d:
+            raise ValueError("A must have shape (%d, D)" % self.d)
+        D = A.shape[1]
+        mean, lo, hi = _f64(mean).ravel(), _f64(lo).ravel(), _f64(hi).ravel()
+        center = None if center is None else _f64(center).ravel()
+        if any(v is not None and len(v) != D for v in (mean, center, lo, hi)):
+            raise ValueError("mean, center, lo and hi must have D = %d entries" % D)
+        self._check(self._lib.bogp_lift_set(self._h, int(D), _ptr(A), _ptr(mean), _ptr(center), _ptr(lo), _ptr(hi)))
+
+    def clear_lift(self):
+        self._check(self._lib.bogp_lift_clear(self._h))
+
+    def lift_sweep_topk(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, k: int = 1, return_values=False,
+                        return_penalty=False):
+        """k best candidates per criterion under the engine's lift (bogp_lift_sweep_topk): a row whose lifted point leaves the box
+        competes with its penalty, a feasible row with its criterion value.  (values (q, k), indices (q, k), n_feasible
+        [, values (q, M)][, penalty (M,)])."""
+        q = len(acq)
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        best = np.empty((q, int(k)))
+        idx = np.empty((q, int(k)), dtype=np.int64)
+        nf = C.c_int64()
+        vals = np.empty((q, self.M)) if return_values else None
+        pen = np.empty(self.M) if return_penalty else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_lift_sweep_topk(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
+                                                   int(k), _ptr(best), idx.ctypes.data_as(_lp), C.cast(C.byref(nf), _lp), _ptr(vals),
+                                                   _ptr(pen)))  # fmt: skip
+        out = (best, idx, int(nf.value))
+        if return_values:
+            out += (vals,)
+        if return_penalty:
+            out += (pen,)
+        return out
+
+    def lift_last(self) -> dict:
+        """Feasible rows, filter time and merge + ranking time (ms) of the last lifted sweep (bogp_lift_last)."""
+        nf, f, m = C.c_int64(), C.c_double(), C.c_double()
+        self._check(self._lib.bogp_lift_last(self._h, C.cast(C.byref(nf), _lp), C.cast(C.byref(f), _dp), C.cast(C.byref(m), _dp)))
+        return {"n_feasible": int(nf.value), "filter_ms": f.value, "merge_ms": m.value}
 
     # -- packed regression forest (the second model kind; bogp_api_forest.hip) ----------------------------------
     def forest_set(self, d: int, tree_offset, feature, threshold, left, right, value, test=None):

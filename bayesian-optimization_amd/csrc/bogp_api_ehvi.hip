@@ -18,6 +18,7 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   if (!h) return BOGP_ERR_INVALID;
   if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: no committed model: call bogp_commit first");
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: no candidates: call bogp_candidates_upload/bind first");
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_ehvi: a lift is set (bogp_lift_set) and EHVI has no lifted sweep: call bogp_lift_clear first");
   if (h->n_t < 2) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: the committed model has %d target; EHVI needs 2 .. %d", h->n_t, BOGP_MAX_TARGETS);
   if (m != h->n_t) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: m = %d but the committed model has %d targets", m, h->n_t);
   if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: m = %d outside [2, %d]", m, BOGP_MAX_TARGETS);

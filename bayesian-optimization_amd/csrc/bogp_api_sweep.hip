@@ -335,6 +335,13 @@ static void collect_timing(bogp_handle* h) {
   }
 }
 
+int bogp::candidates_ready(bogp_handle* h) { return lazy_finish(h); }
+void bogp::clear_sweep_timing(bogp_handle* h) {
+  collect_timing(h);
+  h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
+  h->n_chunks = 0;
+}
+
 int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin,
                     int minimize, bool want_acq_out, bool need_var, bool sync, const EhviArgs* eh) {
   collect_timing(h);  // the events are about to be re-recorded

@@ -25,6 +25,10 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
 int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
               bool want_acq_out, bool need_var = true, bool sync = true, const EhviArgs* eh = nullptr);
 void invalidate_sweep_results(bogp_handle* h);
+// bogp_api_sweep.hip, for bogp_api_lift.hip: a pending lazy upload finished (every candidate row on the device); the
+// sweep timing zeroed (a lifted sweep without a feasible row runs no posterior pass)
+int candidates_ready(bogp_handle* h);
+void clear_sweep_timing(bogp_handle* h);
 // the candidate calls need the row width d: from bogp_set_train or from bogp_forest_set
 bool has_dim(const bogp_handle* h);
 }
@@ -117,6 +121,21 @@ struct bogp_handle {
   size_t blk_val_cap = 0, blk_idx_cap = 0, mu_out_cap = 0, mse_out_cap = 0, acq_out_cap = 0;
   double* dehvi_cells = nullptr;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
   size_t ehvi_cells_cap = 0;
+
+  // lift of a reduced search space (bogp_api_lift.hip): lift_D > 0 <=> a lift is set, for a model of d = lift_r
+  int lift_D = 0, lift_r = 0;
+  double* dlift = nullptr;        // [A (r x D) | mean | center | lo | hi]
+  size_t lift_cap = 0;
+  double* dlift_pen = nullptr;    // [M] penalties of the last lifted sweep
+  int* dlift_cnt = nullptr;       // [ceil(M / 256)] feasible rows per workgroup
+  int64_t* dlift_off = nullptr;   // their exclusive scan, + M_f
+  double* dlift_Z = nullptr;      // [M_f][r] the feasible rows in their original order
+  int64_t* dlift_map = nullptr;   // [M_f] their original indices
+  double* dlift_val = nullptr;    // [q][M] merged values
+  size_t lift_pen_cap = 0, lift_cnt_cap = 0, lift_off_cap = 0, lift_Z_cap = 0, lift_map_cap = 0, lift_val_cap = 0;
+  hipEvent_t lift_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // filter begin / end, merge begin / end
+  int64_t lift_n_feasible = 0;
+  double lift_filter_ms = 0, lift_merge_ms = 0;
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

@@ -176,6 +176,24 @@ hipError_t launch_argmax_final(const double* blk_val, const int64_t* blk_idx, in
 hipError_t launch_topk(const double* vals, int64_t M, int q, int k, double* blk_val, int64_t* blk_idx, double* out_val,
                        int64_t* out_idx, hipStream_t st);
 
+// the box penalty of a lifted sweep and the compaction of its feasible rows (kernels_lift.hip)
+struct LiftArgs {
+  const double* Z;      // candidates of the reduced space, M x r row-major
+  int64_t M;
+  int r, D;             // reduced / original dimensions
+  const double* lift;   // [A (r x D row-major) | mean (D) | center (D) | lo (D) | hi (D)]
+  double* penalty;      // [M]: -(sum of the box violations of x_), -0.0 <=> feasible
+  int* blk_count;       // [ceil(M / 256)] feasible rows per workgroup
+};
+size_t lift_lds_bytes(int r, int D);  // dynamic LDS of one workgroup of k_lift_penalty
+hipError_t launch_lift_penalty(const LiftArgs& a, hipStream_t st);
+hipError_t launch_lift_scan(const int* blk_count, int64_t nblk, int64_t* offsets, hipStream_t st);  // offsets: nblk + 1, the last = M_f
+hipError_t launch_lift_compact(const double* Z, int64_t M, int r, const double* penalty, const int64_t* offsets, double* Zc,
+                               int64_t* map, hipStream_t st);
+// val[c][m] (q x M) = penalty[m], then val[c][map[i]] = acq[c][i] (q x Mf) for the Mf survivors
+hipError_t launch_lift_merge(const double* penalty, int64_t M, const double* acq, const int64_t* map, int64_t Mf, int q,
+                             double* val, hipStream_t st);
+
 hipError_t launch_generate_uniform(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, uint64_t seed,
                                    uint64_t first_elem, hipStream_t st);
 hipError_t launch_generate_lhs(double* Xs, int64_t n_elem, int d, const double* lo, const double* hi, uint64_t seed,

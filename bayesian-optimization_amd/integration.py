@@ -10,9 +10,11 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
                                                    under "sweep" / "sweep-device"; the original otherwise, "MIES" included)
   MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
                                                    under the sweep family; the reference's EHVI otherwise)
-  bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess -> a dispatching class that builds
+  bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess, bayes_optim.extension.GaussianProcess
+                                                -> a dispatching class that builds
                                                    `bogp.GaussianProcess` (so `bayes_optim.fmin` -- which resolves the
-                                                   name at call time, `__init__.py:147-160` -- runs on the device)
+                                                   name at call time, `__init__.py:147-160` -- and `PCABO.update_model`,
+                                                   extension.py:178-203, run on the device)
 
 The contract of install() is that NOTHING the reference could do before stops working afterwards:
 
@@ -23,6 +25,9 @@ The contract of install() is that NOTHING the reference could do before stops wo
     default "BFGS", see `install(reroute_bfgs=...)`) for this package's criteria; "BFGS" on a real space, constraints
     under BFGS / "OnePlusOne_Cholesky_CMA" / "MIES", non-real spaces and criteria that are not this package's all go
     to the saved original (`acquisition/optim/__init__.py:55-153`) -- our criteria are plain callables to it;
+  * PCA-BO's penalising wrapper (`functools.partial(penalized_acquisition, ...)`, extension.py:121-133) around one of this
+    package's criteria is served under the sweep family by the LIFTED sweep (`optim.unwrap_lift`); under
+    "BFGS" the reference's loop and its `penalized_acquisition` run unchanged on this package's one-point criterion;
   * the GaussianProcess name builds the reference's own class for configurations the device does not serve
     (`optimizer="CMA"`, a callable correlation it does not know), with a warning.
 
@@ -148,6 +153,11 @@ def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=10
     bogp criterion is an ordinary callable.  A reroute (`install(reroute_bfgs=...)`) only ever applies to an
     unconstrained "BFGS" call on a continuous space whose criterion is this package's."""
     original = _ORIGINAL["argmax"]
+    lifted = optim._lift_wrapper_parts(obj_func)
+    if optimizer in _OURS and lifted is not None and optim.unwrap_criterion(lifted[0])[0] is not None and optim.is_continuous(search_space):
+        # PCA-BO's penalising wrapper around one of this package's criteria: the lifted sweep over the reduced box
+        return optim.argmax_restart(obj_func, search_space, h=h, g=g, eval_budget=eval_budget, n_restart=n_restart,
+                                    wait_iter=wait_iter, optimizer=optimizer, logger=logger)  # fmt: skip
     crit = optim.unwrap_criterion(obj_func)[0]
     if crit is not None and optimizer in _OURS and _forest.is_forest_model(getattr(crit, "model", None)):
         # this package's criterion on a forest model (forest_create_acquisition): any space of Real / Integer / Ordinal / Discrete /
@@ -369,7 +379,7 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     holders = [m for m in (rbase, ropt, rext) if m is not None and getattr(m, "AcquisitionFunction", None) is racq]
     _ORIGINAL.update(argmax=rbase.argmax_restart, acq_holders=holders, acq=racq, batch=ropt.ParallelBO._batch_arg_max_acquisition,
                      mods=(bayes_optim, rbase, ropt, rsur), gp=(getattr(bayes_optim, "GaussianProcess", None), rsur.GaussianProcess),
-                     surrogate=bool(surrogate), mobo_cls=None)  # fmt: skip
+                     surrogate=bool(surrogate), mobo_cls=None, ext=None)  # fmt: skip
     rbase.argmax_restart = routed_argmax_restart
     _ORIGINAL.update(create=rbase.BaseBO.__dict__["_create_acquisition"], base_cls=rbase.BaseBO, base_partial_argument=rbase.partial_argument)
     rbase.BaseBO._create_acquisition = forest_create_acquisition
@@ -384,6 +394,9 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     if surrogate:
         gp = _dispatching_surrogate(rsur.GaussianProcess)
         bayes_optim.GaussianProcess = rsur.GaussianProcess = gp
+        if rext is not None and hasattr(rext, "GaussianProcess"):  # PCABO.update_model builds its surrogate through this name (extension.py:17,183)
+            _ORIGINAL["ext"] = (rext, rext.GaussianProcess)
+            rext.GaussianProcess = gp
     return uninstall
 
 
@@ -400,6 +413,9 @@ def uninstall():
         _ORIGINAL["mobo_cls"]._create_acquisition = _ORIGINAL["mobo"]
     if _ORIGINAL["surrogate"]:
         pkg.GaussianProcess, rsur.GaussianProcess = _ORIGINAL["gp"]
+        if _ORIGINAL.get("ext") is not None:
+            rext, ext_gp = _ORIGINAL["ext"]
+            rext.GaussianProcess = ext_gp
     _ORIGINAL.clear()
     _REROUTE.clear()
     _SURROGATE_DEFAULTS.clear()

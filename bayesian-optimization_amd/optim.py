@@ -22,6 +22,7 @@ from scipy.optimize import fmin_l_bfgs_b
 
 from . import distributed
 from . import forest as _forest
+from .lift import Lift
 
 
 _TRANS = {  # Real.scale -> (forward, inverse) (variable.py:22-55)
@@ -171,12 +172,45 @@ def _ehvi_of(criteria: Sequence, eng, group=None):
     return criteria[0]
 
 
-def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, group=None, return_points: bool = True):
+def _lifted_topk(criteria: Sequence, eng, lift: Lift, k: int, group=None):
+    """The k best rows per criterion of the engine's current candidates under `lift` (`bogp_lift_sweep_topk`): rows whose
+    lifted point leaves the original box compete with their penalty (extension.py:62-86).  The lift is taken off the engine
+    again before this returns, whatever happens: a later plain sweep never sees it."""
+    if any(is_ehvi(c) for c in criteria):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
+    if any(_forest.is_forest_model(c.model) for c in criteria):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves a Gaussian process model, not a forest")
+    if engine_rank_world(eng, group)[1] > 1:
+        raise NotImplementedError("a lifted sweep (PCA-BO) runs on one rank (no multi-rank exchange of penalised winners)")
+    c0 = criteria[0]
+    for c in criteria[1:]:
+        if c.model is not c0.model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin():
+            raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
+    if lift.r != eng.d:
+        raise ValueError("the lift maps %d reduced dimensions, the model has %d" % (lift.r, eng.d))
+    eng.set_lift(lift.A, lift.mean, lift.center, lift.lo, lift.hi)
+    try:
+        return eng.lift_sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, int(k))[:2]
+    finally:
+        eng.clear_lift()
+
+
+def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, group=None, return_points: bool = True,
+                 lift: Optional[Lift] = None):
     """Evaluate q criteria (same model, same minimize / plugin) on this rank's candidates `Xs` and reduce across
-    ranks.  Returns (best_val (q,), best_global_idx (q,), best_x (q, d) or None)."""
+    ranks.  Returns (best_val (q,), best_global_idx (q,), best_x (q, d) or None).  `lift` (a `Lift`, PCA-BO): `Xs` are rows
+    of the reduced space; a row whose lifted point leaves the original box competes with its penalty instead of its
+    criterion value; one rank only."""
     c0 = criteria[0]
     model = c0.model
     eng = model.engine
+    if lift is not None:
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        Xs = model._check_X(Xs)
+        eng.upload_candidates(Xs, lazy=True)
+        best, idx = _lifted_topk(criteria, eng, lift, 1, group)
+        return best[:, 0], idx[:, 0] + int(index_offset), (Xs[idx[:, 0]] if return_points else None)
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
     ehvi = _ehvi_of(criteria, eng, group)
@@ -198,20 +232,27 @@ def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, grou
 
 
 def sweep_generated(criteria: Sequence, bounds, M: int, seed: int, rank: int = 0, world: int = 1, group=None,
-                    method: str = "uniform"):
+                    method: str = "uniform", lift: Optional[Lift] = None):
     """`sweep_argmax` over M candidates in `bounds` (a list of (lo, hi) pairs, a `Box`, or the reference's `RealSpace` -- scales
     and precisions of its variables are honoured on the device) that never touch the host: rank r draws rows
     [r M / R, (r+1) M / R) of the design on its GPU, sweeps them, and the ranks exchange their winners (value, global
     row, point).  `method` names the design like `RealSpace._sample` does (search_space.py:742-754): "uniform" (Philox
     stream `seed`), "LHS" (an M-point Latin hypercube of stream `seed`; "LHS-maximin": pyDOE's criterion, one rank only),
     "sobol" (points 1..M of the unscrambled
-    sequence; `seed` unused).  The union of the shards is the same M-point set for every world size."""
+    sequence; `seed` unused).  The union of the shards is the same M-point set for every world size.  `lift`: as in
+    `sweep_argmax` (`bounds` is then the box of the reduced space; one rank only)."""
     c0 = criteria[0]
     model = c0.model
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
     a, b_ = shard_bounds(int(M), rank, world)
     eng = model.engine
+    if lift is not None:
+        if world > 1:
+            raise NotImplementedError("a lifted sweep (PCA-BO) runs on one rank (no multi-rank exchange of penalised winners)")
+        _generate(eng, bounds, int(M), seed, 0, method, int(M))
+        best, idx = _lifted_topk(criteria, eng, lift, 1, group)
+        return best[:, 0], idx[:, 0], eng.read_candidates(idx[:, 0])
     ehvi = _ehvi_of(criteria, eng, group)
     _generate(eng, bounds, b_ - a, seed, a, method, int(M))
     if ehvi is not None:
@@ -223,11 +264,27 @@ def sweep_generated(criteria: Sequence, bounds, M: int, seed: int, rank: int = 0
     return distributed.exchange_argmax(best, idx + a, eng.read_candidates(idx), group=group)
 
 
-def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0, group=None):
+def _topk_points(idx, rows, n_rows):
+    """(q, k, d) points of the (q, k) local indices `idx` through `rows(flat indices) -> (n, d)`; NaN where idx < 0."""
+    flat = np.clip(idx, 0, n_rows - 1).ravel()
+    pts = np.asarray(rows(flat), dtype=float)
+    return np.where((idx >= 0)[..., None], pts.reshape(idx.shape + (pts.shape[-1],)), np.nan)
+
+
+def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0, group=None, lift: Optional[Lift] = None):
     """As `sweep_argmax`, returning the k best candidates per criterion:
-    (values (q, k), global indices (q, k), points (q, k, d)), identical on every rank."""
+    (values (q, k), global indices (q, k), points (q, k, d)), identical on every rank.  `lift`: as in `sweep_argmax`."""
     c0 = criteria[0]
     model = c0.model
+    if lift is not None:
+        if _forest.is_forest_model(model):
+            raise NotImplementedError("a lifted sweep (PCA-BO) serves a Gaussian process model, not a forest")
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        Xs = model._check_X(Xs)
+        model.engine.upload_candidates(Xs, lazy=True)
+        best, idx = _lifted_topk(criteria, model.engine, lift, int(k), group)
+        return best, np.where(idx >= 0, idx + int(index_offset), -1), _topk_points(idx, lambda f: Xs[f], len(Xs))
     if _forest.is_forest_model(model):  # rows in the reference's format; points come back as q lists of k rows
         _forest._one_rank(group)
         return _forest.sweep_topk_host(criteria, Xs, k)
@@ -249,11 +306,23 @@ def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0
 
 
 def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, rank: int = 0, world: int = 1, group=None,
-                         method: str = "uniform"):
+                         method: str = "uniform", lift: Optional[Lift] = None):
     """`sweep_topk` over M candidates generated on the device (`method` as in `sweep_generated`): rank r draws and sweeps
-    its block of the design; (values (q, k), global rows (q, k), points (q, k, d)) are identical on every rank."""
+    its block of the design; (values (q, k), global rows (q, k), points (q, k, d)) are identical on every rank.  `lift`: as in
+    `sweep_generated`."""
     c0 = criteria[0]
     model = c0.model
+    if lift is not None:
+        if _forest.is_forest_model(model):
+            raise NotImplementedError("a lifted sweep (PCA-BO) serves a Gaussian process model, not a forest")
+        if world > 1:
+            raise NotImplementedError("a lifted sweep (PCA-BO) runs on one rank (no multi-rank exchange of penalised winners)")
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        eng = model.engine
+        _generate(eng, bounds, int(M), seed, 0, method, int(M))
+        best, idx = _lifted_topk(criteria, eng, lift, int(k), group)
+        return best, idx, _topk_points(idx, eng.read_candidates, int(M))
     if _forest.is_forest_model(model):  # `bounds` is the mixed search space; points come back as q lists of k rows in its format
         _forest._one_rank(group, rank, world)
         if method != "uniform":
@@ -367,6 +436,55 @@ def unwrap_criterion(obj):
     return None, None, None
 
 
+def _lift_wrapper_parts(obj):
+    """(inner acquisition callable, pca, bounds) of PCA-BO's wrapper (`PCABO._create_acquisition`, extension.py:121-133: a
+    `functools.partial` of `penalized_acquisition` whose keywords hold `acquisition_func`, `bounds` and `pca`), else None."""
+    kw = getattr(obj, "keywords", None) if isinstance(obj, functools.partial) else None
+    if not kw or not all(k in kw for k in ("acquisition_func", "bounds", "pca")):
+        return None
+    return kw["acquisition_func"], kw["pca"], kw["bounds"]
+
+
+def unwrap_lift(obj):
+    """(criterion, lift) behind PCA-BO's penalising wrapper: this package's criterion the wrapper maximises (None when it
+    wraps something else) and the `Lift` of its fitted PCA and original box.  (None, None) when `obj` is not that wrapper."""
+    parts = _lift_wrapper_parts(obj)
+    if parts is None:
+        return None, None
+    inner, pca, bounds = parts
+    return unwrap_criterion(inner)[0], Lift.from_pca(pca, bounds)
+
+
+def _lifted_argmax_restart(obj_func, search_space, h, g, eval_budget, optimizer):
+    """`argmax_restart` for PCA-BO's wrapper under the sweep family: the candidates are rows of the reduced box
+    `search_space`, swept under the wrapper's lift; the returned point is a reduced-space row (`PCABO.ask` maps it back
+    itself, extension.py:151-152)."""
+    inner = _lift_wrapper_parts(obj_func)[0]
+    crit, masks, _ = unwrap_criterion(inner)
+    if crit is None:
+        raise TypeError("optimizer=%r needs one of this package's criteria behind PCA-BO's wrapper (a bogp.GaussianProcess as the "
+                        "surrogate: construct the PCABO after bogp.install())" % optimizer)  # fmt: skip
+    if optimizer in ("sweep-BFGS", "sweep-device-BFGS"):
+        raise NotImplementedError("optimizer=%r under a lift (PCA-BO): the box penalty has no device polish; use 'sweep', "
+                                  "'sweep-device[-lhs|-sobol]' or the reference's 'BFGS'" % optimizer)  # fmt: skip
+    if masks is not None:
+        raise NotImplementedError("a lifted sweep (PCA-BO) takes no fixed variables")
+    if h is not None or g is not None:
+        raise NotImplementedError("a lifted sweep (PCA-BO) takes no constraints h / g")
+    if is_ehvi(crit):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
+    if engine_rank_world(crit.model.engine)[1] > 1:
+        raise NotImplementedError("a lifted sweep (PCA-BO) runs on one rank (no multi-rank exchange of penalised winners)")
+    lift = unwrap_lift(obj_func)[1]
+    if optimizer in DEVICE_DESIGNS:
+        best, _, xb = sweep_generated([crit], search_space, int(eval_budget), int(np.random.randint(0, 2**62)),
+                                      method=DEVICE_DESIGNS[optimizer], lift=lift)  # fmt: skip
+    else:
+        Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        best, _, xb = sweep_argmax([crit], Xs, return_points=True, lift=lift)
+    return np.asarray(xb[0], dtype=float).tolist(), float(best[0])
+
+
 # optimizer name -> sampling method of RealSpace._sample (search_space.py:742-754) realised on the device
 DEVICE_DESIGNS = {"sweep-device": "uniform", "sweep-device-lhs": "LHS", "sweep-device-sobol": "sobol"}
 
@@ -405,11 +523,16 @@ def argmax_restart(
     per iteration).
     optimizer="BFGS": the reference's multi-restart L-BFGS-B loop on `obj_func(x) -> (value, dx)` (host; every
     evaluation is one device call through the acquisition object).
+    PCA-BO's wrapper (`unwrap_lift`) under "sweep" / "sweep-device[-lhs|-sobol]": the candidates are rows of the reduced box and
+    are swept under the wrapper's lift (`sweep_argmax(..., lift=)`); the polish hybrids, fixed variables, constraints and
+    several ranks are refused by name.
     Anything else ("MIES", "OnePlusOne_Cholesky_CMA", constraints under "BFGS", a non-continuous space) is the
     reference's own business: the call is handed to its `argmax_restart` when `bayes_optim` is importable, for which a
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
     """
     ours = optimizer in DEVICE_DESIGNS or optimizer in ("sweep", "sweep-BFGS", "sweep-device-BFGS")
+    if ours and _lift_wrapper_parts(obj_func) is not None:  # PCA-BO's penalising wrapper: the lifted sweep
+        return _lifted_argmax_restart(obj_func, search_space, h, g, eval_budget, optimizer)
     fcrit, fmasks, _ = unwrap_criterion(obj_func)
     if fcrit is not None and _forest.is_forest_model(getattr(fcrit, "model", None)) and (ours or optimizer == "BFGS"):
         # a forest model (any space of Real / Integer / Ordinal / Discrete / Subset / Bool variables): "sweep" and "sweep-device"

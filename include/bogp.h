@@ -294,6 +294,44 @@ int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_
 int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
                     int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 
+/* ---- sweep in a reduced space: box-penalised criteria under a linear lift ---------------------------
+ * Replaces PCABO's inner maximisation (extension.py:113-133): the criterion is maximised over a box of the REDUCED
+ * space (r = the committed model's d, _compute_bounds :113-119) through penalized_acquisition (:62-86), which maps a
+ * candidate z back, x_ = (z A + mean) + center (LinearTransform.inverse_transform, :56-59, in this order), and returns
+ *   penalty = -( sum_{x_i < lo_i} (lo_i - x_i) + sum_{x_i > hi_i} (x_i - hi_i) )       INSTEAD of the criterion
+ * whenever penalty != 0 (:73); x_ exactly on a bound is feasible.  Typically 95 .. 100 % of a uniform design of the reduced
+ * box are such rows, so the device decides feasibility for all M rows first (M r D multiply-adds), compacts the feasible
+ * rows in their original order (no atomics: deterministic), runs the sweep of bogp_sweep_topk on them alone and ranks
+ * criterion values and penalties together.
+ * `lift_set`: A (r x D row-major = pca.components_), mean (D = pca.mean_), center (D = LinearTransform.center; NULL = 0),
+ * lo / hi (D, the original box; +-inf allowed).  Persists on the handle until bogp_lift_clear; needs a training set (r is
+ * its d; a later bogp_set_train of another d makes the lifted sweep return BOGP_ERR_INVALID until the lift is set again).
+ * BOGP_ERR_INVALID: no training set, a null array, D < 1, a non-finite A / mean / center, NaN bounds or lo > hi.
+ * BOGP_ERR_UNSUPPORTED: D > BOGP_MAX_DIM, r > BOGP_LIFT_MAX_R (a candidate row is held in registers), r D >
+ * BOGP_LIFT_MAX_RD (A is staged in LDS), a forest handle.  The plain calls (bogp_sweep, bogp_sweep_topk, bogp_predict)
+ * never look at the lift; bogp_sweep_ehvi refuses a handle with a lift (BOGP_ERR_UNSUPPORTED).
+ * `lift_sweep_topk`: q, acq_id, acq_par, plugin, minimize, k, best_val, best_idx (q x k) as bogp_sweep_topk, over
+ *   value_c[m] = penalty[m] if penalty[m] != 0, else criterion_c(z_m) -- the value bogp_sweep defines for that row --
+ * for ALL M current candidates: first maximum, ties -> lower index, a NaN wins at its first position, slots beyond M are
+ * (-inf, -1); indices number the M candidates as uploaded / generated.  Without a feasible row the winner is the least
+ * penalised row and no posterior pass runs; with every row feasible the result is bogp_sweep_topk's, bit for bit.  A
+ * feasible row's value is what the plain sweep returns for that row among the feasible rows alone.
+ *   n_feasible   out, may be NULL: feasible rows M_f
+ *   value_out    optional HOST buffer (q x M row-major): value_c[m];  penalty_out  optional HOST buffer (M): penalty[m]
+ *                (-0.0 for a feasible row)
+ * BOGP_ERR_UNSUPPORTED: a forest handle, a communicator of more than one rank.  bogp_last_timing reports the pass over
+ * the survivors (all zero when M_f = 0).
+ * `lift_last`: M_f of the last lifted sweep, the time of its filter (penalty + scan + the read-back of M_f + compaction)
+ * and of its merge + ranking, in ms; any pointer may be NULL.                                                        */
+#define BOGP_LIFT_MAX_R 64    /* reduced dimensions r of a lift */
+#define BOGP_LIFT_MAX_RD 4096 /* r x D of a lift: doubles of A one workgroup stages in LDS */
+int bogp_lift_set(bogp_handle* h, int D, const double* A, const double* mean, const double* center, const double* lo,
+                  const double* hi);
+int bogp_lift_clear(bogp_handle* h);
+int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int k,
+                         double* best_val, int64_t* best_idx, int64_t* n_feasible, double* value_out, double* penalty_out);
+int bogp_lift_last(bogp_handle* h, int64_t* n_feasible, double* filter_ms, double* merge_ms);
+
 /* ---- second model kind: a packed regression forest ---------------------------------------------------
  * Replaces RandomForest.predict(X, eval_MSE=True) (surrogate/random_forest.py:124-155): scikit-learn's Tree.predict per
  * tree on the row cast to float32, mu = mean over the T trees, MSE = std(ddof = 1)^2 over the trees -- and, on these
