@@ -5,6 +5,7 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
   bogp.GaussianProcess           <-> bayes_optim.surrogate.GaussianProcess      (fit / predict / gradient)
   bogp.acquisition.{EI,PI,EpsilonPI,UCB,MGFI} <-> bayes_optim.acquisition.acquisition_fun.*
   bogp.EHVI                      <-> bayes_optim.multi_objective.analytic.EHVI (MOBO's criterion; one device pass)
+                                 (on a multi-target GaussianProcess, or on a RandomForest fitted on y (N, m))
   bogp.pareto                    Pareto front + cell decomposition of the non-dominated region (numpy)
   bogp.RandomForest              <-> bayes_optim.surrogate.RandomForest        (scikit-learn fits, the device predicts;
                                  bogp.forest: packing, mixed-space sweep; built on first access, sklearn imported lazily)

@@ -76,6 +76,11 @@ SIGNATURES = {
     "bogp_forest_leaves": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp]),
     "bogp_forest_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _dp]),
     "bogp_forest_info": (C.c_int, [C.c_void_p, _lp]),
+    "bogp_forest_set_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _lp, _ip, _dp, _ip, _ip, _dp, _ip]),
+    "bogp_forest_outputs": (C.c_int, [C.c_void_p]),
+    "bogp_forest_predict_multi": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "bogp_forest_leaves_multi": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp]),
+    "bogp_forest_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_candidates_generate_mixed": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _ip, C.c_int64, C.c_uint64, C.c_int64]),
     "bogp_gradient": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "bogp_gradient_batch": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
@@ -688,6 +693,69 @@ class Engine:
         if int(k) > 1:
             self._last_topk = (q, int(k))
         return (best, idx, vals) if return_values else (best, idx)
+
+    # -- forests with several outputs (k_forest_ehvi) --------------------------------------------------------------
+    def forest_set_multi(self, d: int, m: int, tree_offset, feature, threshold, left, right, value, test=None):
+        """`forest_set` for a forest whose leaves hold m >= 2 values: `value` is (nodes, m) (scikit-learn's `tree_.value[:, :, 0]`)."""
+        off = np.ascontiguousarray(tree_offset, dtype=np.int64)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        feature, left, right = i32(feature), i32(left), i32(right)
+        threshold, value = _f64(threshold).ravel(), _f64(value)
+        n = int(off[-1]) if len(off) else 0
+        if not (len(feature) == len(left) == len(right) == len(threshold) == n) or value.shape != (n, int(m)):
+            raise ValueError("the node arrays must have tree_offset[-1] = %d entries and value the shape (%d, %d)" % (n, n, int(m)))
+        tst = None if test is None else i32(test)
+        if tst is not None and len(tst) != n:
+            raise ValueError("test must have %d entries" % n)
+        self._check(self._lib.bogp_forest_set_multi(self._h, len(off) - 1, int(d), int(m), off.ctypes.data_as(_lp),
+                                                    feature.ctypes.data_as(_ip), _ptr(threshold), left.ctypes.data_as(_ip),
+                                                    right.ctypes.data_as(_ip), _ptr(value),
+                                                    None if tst is None else tst.ctypes.data_as(_ip)))  # fmt: skip
+        if int(d) != self.d:
+            self.M = 0
+        self.d, self.N, self.forest_T = int(d), 0, len(off) - 1
+        self._last_q, self._last_topk = -1, (-1, -1)
+
+    def forest_outputs(self) -> int:
+        """Outputs a leaf of the engine's forest holds (0 without a forest)."""
+        return int(self._lib.bogp_forest_outputs(self._h))
+
+    def forest_predict_multi(self, eval_MSE=True) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """mu (M, m) and MSE (M, m) of a forest with several outputs over the current candidates."""
+        m = self.forest_outputs()
+        mu = np.empty((self.M, m))
+        mse = np.empty((self.M, m)) if eval_MSE else None
+        self._check(self._lib.bogp_forest_predict_multi(self._h, _ptr(mu), _ptr(mse)))
+        return mu, mse
+
+    def forest_leaves_multi(self, first_row: int, n: int) -> np.ndarray:
+        """Per-tree, per-output predictions (n, T, m) of candidate rows [first_row, first_row + n)."""
+        out = np.empty((int(n), int(getattr(self, "forest_T", 0)), self.forest_outputs()))
+        self._check(self._lib.bogp_forest_leaves_multi(self._h, int(first_row), int(n), _ptr(out)))
+        return out
+
+    def forest_sweep_ehvi(self, lower, upper, k: int = 1, return_values=False, return_moments=False):
+        """Expected hypervolume improvement on the moments of a forest with several outputs, over the current candidates:
+        arguments and results as `sweep_ehvi` (bogp_forest_sweep_ehvi)."""
+        lower = _f64(lower)
+        upper = _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape")
+        C_, m = lower.shape
+        best = np.empty(int(k))
+        idx = np.empty(int(k), dtype=np.int64)
+        vals = np.empty(self.M) if return_values else None
+        mu = np.empty((self.M, m)) if return_moments else None
+        mse = np.empty((self.M, m)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_forest_sweep_ehvi(self._h, int(m), int(C_), _ptr(lower), _ptr(upper), int(k), _ptr(best),
+                                                     idx.ctypes.data_as(_lp), _ptr(vals), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_moments:
+            out += (mu, mse)
+        return out
 
     def generate_candidates_mixed(self, kind, lo, hi, n_levels, M: int, seed: int = 0, first_row: int = 0):
         """M rows of a mixed space drawn ON the device: column k is real (kind 0: lo + (hi - lo) u, then the candidate transform)

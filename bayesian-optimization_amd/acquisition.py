@@ -310,7 +310,11 @@ class EHVI:
       cells        (lower, upper), each C x m (upper may hold +inf).
     `criterion(X)` returns one value per row, shape (M,): row i is what the reference's one-row call returns for row i
     (computed in float64 -- the reference casts mu / MSE to float32, analytic.py:228-233).  All rows are evaluated in one
-    device pass (`bogp_sweep_ehvi`); there is no input gradient."""
+    device pass (`bogp_sweep_ehvi`); there is no input gradient.
+
+    The model may also be a `RandomForest` fitted on y (N, m) -- this package's or the reference's, as MOBO fits it on mixed
+    spaces: rows then come in the reference's format (level labels in the categorical columns), and the forest walk and the
+    criterion are one device pass (`bogp_forest_sweep_ehvi`).  A forest whose outputs differ from `n_obj` is refused."""
 
     is_ehvi = True
     minimize = False  # (the sweep helpers read it off every criterion)
@@ -366,6 +370,8 @@ class EHVI:
     def sweep(self, k: int = 1, return_values: bool = False):
         """The EHVI sweep over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
         model = self.model
+        if _forest.is_forest_model(model):
+            return _forest.ehvi_sweep(self, k=k, return_values=return_values)
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         return model.engine.sweep_ehvi(self.cell_lower_bounds, self.cell_upper_bounds, k=k, return_values=return_values)
@@ -373,6 +379,8 @@ class EHVI:
     def __call__(self, X, return_dx: bool = False):
         if return_dx:
             raise NotImplementedError("EHVI has no input gradient (the reference's EHVI has none either)")
+        if _forest.is_forest_model(self.model):  # rows keep their level labels
+            return _forest.criterion_values(self, X)
         if getattr(self.model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         eng = self.model.engine

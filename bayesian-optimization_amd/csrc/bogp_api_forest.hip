@@ -1,7 +1,9 @@
 // bogp_api_forest.hip -- the C ABI of libbogp.so (include/bogp.h) for the second model kind of a handle, a packed regression
 // forest: bogp_forest_set (validation + packing, host only), bogp_forest_predict / _leaves / _sweep_topk (k_forest of
 // kernels_forest.hip over the current candidates, then the argmax / top-k passes of kernels_acq.hip) and the candidate generator
-// of mixed spaces, bogp_candidates_generate_mixed.
+// of mixed spaces, bogp_candidates_generate_mixed; and, for a forest whose leaves hold several outputs, bogp_forest_set_multi (the same
+// validation and packing with m values a leaf), bogp_forest_predict_multi / _leaves_multi / _sweep_ehvi (k_forest_ehvi of
+// kernels_forest_ehvi.hip, then the same argmax / top-k passes).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,15 +27,15 @@ static float round_down_f32(double t) {
   return f;
 }
 
-extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree_offset, const int32_t* feature,
-                               const double* threshold, const int32_t* left, const int32_t* right, const double* value,
-                               const int32_t* test) {
-  if (!h) return BOGP_ERR_INVALID;
-  if (h->dX) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: the handle holds a Gaussian-process training set; a forest takes a handle of its own");
-  if (T < 2) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: T = %d trees; the variance over the trees (ddof = 1) needs T >= 2", T);
-  if (d < 1 || d > BOGP_MAX_DIM) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: d = %d outside [1, %d]", d, BOGP_MAX_DIM);
-  if (!tree_offset || !feature || !threshold || !left || !right || !value) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree_offset, feature, threshold, left, right and value must be non-null");
-  if (tree_offset[0] != 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree_offset[0] must be 0");
+// validation walk + packing of bogp_forest_set (m = 1) and bogp_forest_set_multi (m outputs a leaf, value nodes x m row-major)
+static int forest_set_impl(bogp_handle* h, const char* who, int T, int d, int m, const int64_t* tree_offset, const int32_t* feature,
+                           const double* threshold, const int32_t* left, const int32_t* right, const double* value,
+                           const int32_t* test) {
+  if (h->dX) FAIL(h, BOGP_ERR_INVALID, "%s: the handle holds a Gaussian-process training set; a forest takes a handle of its own", who);
+  if (T < 2) FAIL(h, BOGP_ERR_INVALID, "%s: T = %d trees; the variance over the trees (ddof = 1) needs T >= 2", who, T);
+  if (d < 1 || d > BOGP_MAX_DIM) FAIL(h, BOGP_ERR_INVALID, "%s: d = %d outside [1, %d]", who, d, BOGP_MAX_DIM);
+  if (!tree_offset || !feature || !threshold || !left || !right || !value) FAIL(h, BOGP_ERR_INVALID, "%s: tree_offset, feature, threshold, left, right and value must be non-null", who);
+  if (tree_offset[0] != 0) FAIL(h, BOGP_ERR_INVALID, "%s: tree_offset[0] must be 0", who);
   std::vector<unsigned long long> words;
   std::vector<ForestTree> trees((size_t)T);
   int tree_words = 0, depth_max = 0;
@@ -41,7 +43,7 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
   std::vector<int> order, newidx, dep;
   for (int t = 0; t < T; ++t) {
     const int64_t o = tree_offset[t], n64 = tree_offset[t + 1] - o;
-    if (n64 < 1 || n64 > 65535) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d has %lld nodes (1 .. 65535)", t, (long long)n64);
+    if (n64 < 1 || n64 > 65535) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d has %lld nodes (1 .. 65535)", who, t, (long long)n64);
     const int n = (int)n64;
     // breadth-first walk from the root: every node is reached at most once (no cycle, no shared subtree), the children of a
     // node get adjacent new indices, unreachable nodes are dropped, and the depth of the tree bounds the kernel's walk
@@ -54,19 +56,20 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
       const int u = order[qi];
       const int l = left[o + u], r = right[o + u];
       if (l == -1) {
-        if (r != -1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a right child but no left child", t, u);
-        if (!std::isfinite(value[o + u])) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d leaf %d has a non-finite value", t, u);
+        if (r != -1) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d has a right child but no left child", who, t, u);
+        for (int k = 0; k < m; ++k)
+          if (!std::isfinite(value[(size_t)(o + u) * m + k])) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d leaf %d has a non-finite value", who, t, u);
         ++nleaf;
         continue;
       }
-      if (l < 0 || l >= n || r < 0 || r >= n) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a child outside [0, %d)", t, u, n);
-      if (l == r || newidx[l] != -1 || newidx[r] != -1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d points at a node that is already reached (cycle or shared subtree)", t, u);
-      if (feature[o + u] < 0 || feature[o + u] >= d) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d splits on feature %d outside [0, %d)", t, u, feature[o + u], d);
+      if (l < 0 || l >= n || r < 0 || r >= n) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d has a child outside [0, %d)", who, t, u, n);
+      if (l == r || newidx[l] != -1 || newidx[r] != -1) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d points at a node that is already reached (cycle or shared subtree)", who, t, u);
+      if (feature[o + u] < 0 || feature[o + u] >= d) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d splits on feature %d outside [0, %d)", who, t, u, feature[o + u], d);
       const double thr = threshold[o + u];
-      if (std::isnan(thr)) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has a NaN threshold", t, u);
+      if (std::isnan(thr)) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d has a NaN threshold", who, t, u);
       if (test && test[o + u] != 0) {
-        if (test[o + u] != 1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d has test %d (0: x <= thr, 1: x != thr)", t, u, test[o + u]);
-        if (!(thr >= 0 && thr < 16777216.0 && thr == std::floor(thr))) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set: tree %d node %d: a level index must be an integer in [0, 2^24)", t, u);
+        if (test[o + u] != 1) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d has test %d (0: x <= thr, 1: x != thr)", who, t, u, test[o + u]);
+        if (!(thr >= 0 && thr < 16777216.0 && thr == std::floor(thr))) FAIL(h, BOGP_ERR_INVALID, "%s: tree %d node %d: a level index must be an integer in [0, 2^24)", who, t, u);
       }
       newidx[l] = next;
       newidx[r] = next + 1;
@@ -78,8 +81,9 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
     }
     const int nn = next;  // reachable nodes (<= n <= 65535: a child index fits 16 bits)
     const size_t base = words.size();
-    if (base + (size_t)nn + nleaf > (size_t)INT32_MAX) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_set: the packed forest exceeds 2^31 words");
-    words.resize(base + (size_t)nn + nleaf);
+    const size_t nw = (size_t)nn + (size_t)m * nleaf;  // [records | leaves x m values, leaf-major]
+    if (base + nw > (size_t)INT32_MAX) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the packed forest exceeds 2^31 words", who);
+    words.resize(base + nw);
     int li = 0;
     for (size_t qi = 0; qi < order.size(); ++qi) {  // order[qi] has new index qi (children are appended pairwise as they are numbered)
       const int u = order[qi];
@@ -87,10 +91,12 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
       if (left[o + u] == -1) {
         x = (uint32_t)li;
         w = 0u;
-        double v = value[o + u];
-        unsigned long long bits;
-        memcpy(&bits, &v, 8);
-        words[base + nn + li] = bits;
+        for (int k = 0; k < m; ++k) {
+          double v = value[(size_t)(o + u) * m + k];
+          unsigned long long bits;
+          memcpy(&bits, &v, 8);
+          words[base + nn + (size_t)m * li + k] = bits;
+        }
         ++li;
       } else {
         const bool eq = test && test[o + u] == 1;
@@ -101,14 +107,14 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
       words[base + newidx[u]] = ((unsigned long long)w << 32) | x;  // uint2 {x, y} in memory order
     }
     trees[t] = ForestTree{(int)base, nn, nleaf, depth, 1.0 / (double)(t + 1), 0.0};
-    if (nn + nleaf > tree_words) tree_words = nn + nleaf;
+    if ((int)nw > tree_words) tree_words = (int)nw;
     if (depth > depth_max) depth_max = depth;
     nodes_total += nn;
     leaves_total += nleaf;
   }
   const size_t lds = forest_lds_bytes(d, tree_words);
   if (lds > FOREST_LDS_LIMIT)
-    FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_set: two buffers of the largest tree (%d words) and 256 rows of %d features need %zu bytes of LDS (limit %zu)", tree_words, d, lds, FOREST_LDS_LIMIT);
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: two buffers of the largest tree (%d words) and 256 rows of %d features need %zu bytes of LDS (limit %zu)", who, tree_words, d, lds, FOREST_LDS_LIMIT);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // a forest call in flight still reads the old forest
   int e;
@@ -127,6 +133,7 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
   }
   invalidate_sweep_results(h);
   h->forest_T = T;
+  h->forest_m = m;
   h->d = d;
   h->forest_tree_words = tree_words;
   h->forest_depth = depth_max;
@@ -135,6 +142,23 @@ extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree
   return BOGP_OK;
 }
 
+extern "C" int bogp_forest_set(bogp_handle* h, int T, int d, const int64_t* tree_offset, const int32_t* feature,
+                               const double* threshold, const int32_t* left, const int32_t* right, const double* value,
+                               const int32_t* test) {
+  if (!h) return BOGP_ERR_INVALID;
+  return forest_set_impl(h, "bogp_forest_set", T, d, 1, tree_offset, feature, threshold, left, right, value, test);
+}
+
+extern "C" int bogp_forest_set_multi(bogp_handle* h, int T, int d, int m, const int64_t* tree_offset, const int32_t* feature,
+                                     const double* threshold, const int32_t* left, const int32_t* right, const double* value,
+                                     const int32_t* test) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_set_multi: m = %d outputs outside [2, %d] (one output: bogp_forest_set)", m, BOGP_MAX_TARGETS);
+  return forest_set_impl(h, "bogp_forest_set_multi", T, d, m, tree_offset, feature, threshold, left, right, value, test);
+}
+
+extern "C" int bogp_forest_outputs(const bogp_handle* h) { return h && h->forest_T ? h->forest_m : 0; }
+
 extern "C" int bogp_forest_info(const bogp_handle* h, int64_t* out) {
   if (!h || !out) return BOGP_ERR_INVALID;
   out[0] = h->forest_T;
@@ -142,7 +166,7 @@ extern "C" int bogp_forest_info(const bogp_handle* h, int64_t* out) {
   out[2] = h->forest_nodes;
   out[3] = h->forest_leaves;
   out[4] = h->forest_depth;
-  out[5] = (h->forest_nodes + h->forest_leaves) * 8 + (int64_t)h->forest_T * (int64_t)sizeof(ForestTree);
+  out[5] = (h->forest_nodes + h->forest_leaves * h->forest_m) * 8 + (int64_t)h->forest_T * (int64_t)sizeof(ForestTree);
   out[6] = h->forest_T ? (int64_t)forest_lds_bytes(h->d, h->forest_tree_words) : 0;
   return BOGP_OK;
 }
@@ -177,6 +201,7 @@ extern "C" int bogp_forest_predict(bogp_handle* h, double* mu, double* mse) {
   if (!h) return BOGP_ERR_INVALID;
   if (!mu) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: mu must be non-null");
   if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: no forest: call bogp_forest_set first");
+  if (h->forest_m > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_predict: the forest has %d outputs: call bogp_forest_predict_multi", h->forest_m);
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict: no candidates");
   HIPCHK(h, hipSetDevice(h->device));
   const int64_t M = h->M;
@@ -197,6 +222,7 @@ extern "C" int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, doub
   if (!h) return BOGP_ERR_INVALID;
   if (!per_tree || n < 1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_leaves: per_tree must be non-null and n > 0");
   if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_leaves: no forest: call bogp_forest_set first");
+  if (h->forest_m > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_leaves: the forest has %d outputs: call bogp_forest_leaves_multi", h->forest_m);
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)n * h->forest_T;
   int e;
@@ -222,6 +248,7 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
       FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: acquisition parameter %d must be > 0 (the reference asserts alpha/epsilon/t > 0)", i);
   }
   if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: no forest: call bogp_forest_set first");
+  if (h->forest_m > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_forest_sweep_topk: the forest has %d outputs and the single-target criteria take one: call bogp_forest_sweep_ehvi", h->forest_m);
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_sweep_topk: no candidates");
   HIPCHK(h, hipSetDevice(h->device));
   invalidate_sweep_results(h);
@@ -265,6 +292,132 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
     h->last_topk_k = k;
   }
   for (int i = 0; i < q * k; ++i)
+    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
+      best_val[i] = -INFINITY;
+      best_idx[i] = -1;
+    }
+  return forest_timing(h);
+}
+
+// ---- forests with several outputs: k_forest_ehvi (kernels_forest_ehvi.hip) -------------------------------------------------------
+// the checks every multi-output call shares; launches k_forest_ehvi over rows [row0, row0 + nrows), timed as run_forest times k_forest
+static int run_forest_ehvi(bogp_handle* h, const char* who, ForestEhviArgs& a, int64_t row0, int64_t nrows) {
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "%s: no forest: call bogp_forest_set_multi first", who);
+  if (h->forest_m < 2) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the forest has one output: the one-output calls (bogp_forest_predict / _leaves / _sweep_topk) serve it", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
+  if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
+  if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
+  for (int i = 0; i < 2; ++i)
+    if (!h->forest_ev[i]) HIPCHK(h, hipEventCreate(&h->forest_ev[i]));
+  a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d; a.m = h->forest_m;
+  a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
+  HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
+  HIPCHK(h, launch_forest_ehvi(a, h->stream));
+  HIPCHK(h, hipEventRecord(h->forest_ev[1], h->stream));
+  return BOGP_OK;
+}
+
+// what run_forest_ehvi will refuse, asked before anything is allocated
+static int forest_multi_ready(bogp_handle* h, const char* who) {
+  if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "%s: no forest: call bogp_forest_set_multi first", who);
+  if (h->forest_m < 2) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the forest has one output: the one-output calls (bogp_forest_predict / _leaves / _sweep_topk) serve it", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
+  return BOGP_OK;
+}
+
+extern "C" int bogp_forest_predict_multi(bogp_handle* h, double* mu, double* mse) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!mu) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_predict_multi: mu must be non-null");
+  int e;
+  if ((e = forest_multi_ready(h, "bogp_forest_predict_multi"))) return e;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)h->M * h->forest_m;
+  if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, cnt))) return e;
+  if (mse && (e = ensure(h, &h->dmse_out, &h->mse_out_cap, cnt))) return e;
+  ForestEhviArgs a;
+  memset(&a, 0, sizeof(a));
+  a.mu_out = h->dmu_out; a.mse_out = mse ? h->dmse_out : nullptr;
+  if ((e = run_forest_ehvi(h, "bogp_forest_predict_multi", a, 0, h->M))) return e;
+  HIPCHK(h, hipMemcpyAsync(mu, h->dmu_out, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (mse) HIPCHK(h, hipMemcpyAsync(mse, h->dmse_out, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return forest_timing(h);
+}
+
+extern "C" int bogp_forest_leaves_multi(bogp_handle* h, int64_t first_row, int n, double* per_tree) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!per_tree || n < 1) FAIL(h, BOGP_ERR_INVALID, "bogp_forest_leaves_multi: per_tree must be non-null and n > 0");
+  int e;
+  if ((e = forest_multi_ready(h, "bogp_forest_leaves_multi"))) return e;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)n * h->forest_T * h->forest_m;
+  if ((e = ensure(h, &h->dbatch, &h->batch_cap, cnt))) return e;
+  ForestEhviArgs a;
+  memset(&a, 0, sizeof(a));
+  a.leaves_out = h->dbatch;
+  if ((e = run_forest_ehvi(h, "bogp_forest_leaves_multi", a, first_row, n))) return e;
+  HIPCHK(h, hipMemcpyAsync(per_tree, h->dbatch, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return forest_timing(h);
+}
+
+extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
+                                      int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_forest_sweep_ehvi";
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set) and EHVI has no lifted sweep: call bogp_lift_clear first", who);
+  int e;
+  if ((e = forest_multi_ready(h, who))) return e;
+  if (m != h->forest_m) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d but the forest has %d outputs", who, m, h->forest_m);
+  if (C < 1 || C > BOGP_MAX_EHVI_CELLS) FAIL(h, BOGP_ERR_INVALID, "%s: C = %d cells outside [1, %d]", who, C, BOGP_MAX_EHVI_CELLS);
+  if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
+  if (!lower || !upper || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: lower, upper, best_val and best_idx must be non-null", who);
+  const size_t nb = (size_t)C * m;
+  for (size_t i = 0; i < nb; ++i) {
+    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
+    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
+    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  invalidate_sweep_results(h);
+  hipStream_t st = h->stream;
+  const int64_t M = h->M, nblk = (M + 255) / 256;
+  const bool keep = k > 1 || ehvi_out;
+  if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
+  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)(nblk + 1)))) return e;
+  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)(nblk + 1)))) return e;
+  if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
+  if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
+  if (keep && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)M))) return e;
+  if (mu_out && (e = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M * m))) return e;
+  if (mse_out && (e = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M * m))) return e;
+  // (the cells are the kernel's arguments: copied in stream order before the kernel that reads them)
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // the caller's arrays are not needed past this call
+  ForestEhviArgs a;
+  memset(&a, 0, sizeof(a));
+  a.C = C; a.lower = h->dehvi_cells; a.upper = h->dehvi_cells + nb;
+  a.ehvi_out = keep ? h->dacq_out : nullptr;
+  a.mu_out = mu_out ? h->dmu_out : nullptr; a.mse_out = mse_out ? h->dmse_out : nullptr;
+  a.blk_val = h->dblk_val; a.blk_idx = h->dblk_idx;
+  if ((e = run_forest_ehvi(h, who, a, 0, M))) return e;
+  HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
+  if (k == 1) {
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_ehvi ranks them
+    if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  }
+  if (ehvi_out) HIPCHK(h, hipMemcpyAsync(ehvi_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  for (int i = 0; i < k; ++i)
     if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
       best_val[i] = -INFINITY;
       best_idx[i] = -1;

@@ -268,6 +268,29 @@ __device__ __forceinline__ double ndtr(double a) {
 // scipy.stats.norm.pdf: exp(-x**2/2.0) / sqrt(2*pi)
 __device__ __forceinline__ double norm_pdf(double x) { return exp(-(x * x) / 2.0) / 2.5066282746310002; }
 
+// EHVI of one row from its MT means and standard deviations (analytic.py:223-274 as one product per cell): the sum over the C
+// cells of prod_k sd_k (G(a) - G(b)), a = (l - mu) / sd, b = (u - mu) / sd, G(z) = phi(z) - z Phi(-z), G(b) = 0 for u = +inf.
+// The cell bounds (C x MT row-major, device memory) are read at lane-uniform addresses.  Shared by k_ehvi (a Gaussian process's
+// moments) and k_forest_ehvi (a forest's), so that both evaluate the same expressions.
+__device__ __forceinline__ double ehvi_G(double z) { return norm_pdf(z) - z * ndtr(-z); }
+
+template <int MT>
+__device__ __forceinline__ double ehvi_cells(const double* lower, const double* upper, int C, const double (&mu)[MT], const double (&sd)[MT]) {
+  double acc = 0.0;
+  for (int c = 0; c < C; ++c) {  // the cell bounds are the same for every lane
+    double p = 1.0;
+#pragma unroll
+    for (int k = 0; k < MT; ++k) {
+      const double l = lower[(size_t)c * MT + k], u = upper[(size_t)c * MT + k];
+      const double gl = ehvi_G((l - mu[k]) / sd[k]);
+      const double gu = isinf(u) ? 0.0 : ehvi_G((u - mu[k]) / sd[k]);
+      p *= sd[k] * (gl - gu);
+    }
+    acc += p;
+  }
+  return acc;
+}
+
 // The q acquisition criteria of one row, guards as selects (acquisition_fun.py:127-135, 153-176, 208-217, 265-290); shared by
 // k_acquisition (chunked sweep) and k_sweep_small (fused small-N sweep) so that both evaluate the same expressions.
 __device__ __forceinline__ double acq_value(int id, double par, double y_hat, double sd, double plugin, double sigma2) {

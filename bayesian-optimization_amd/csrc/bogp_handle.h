@@ -140,6 +140,7 @@ struct bogp_handle {
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)
   int forest_T = 0, forest_tree_words = 0, forest_depth = 0;
+  int forest_m = 1;  // outputs a leaf holds: 1 (bogp_forest_set) or 2 .. BOGP_MAX_TARGETS (bogp_forest_set_multi)
   int64_t forest_nodes = 0, forest_leaves = 0;
   unsigned long long* dforest_words = nullptr;
   bogp::ForestTree* dforest_tree = nullptr;

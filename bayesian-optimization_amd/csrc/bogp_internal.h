@@ -129,8 +129,33 @@ struct ForestArgs {
   int64_t* blk_idx;
   int64_t nblk_total;
 };
-size_t forest_lds_bytes(int d, int tree_words);  // dynamic LDS of one workgroup of k_forest
+size_t forest_lds_bytes(int d, int tree_words);  // dynamic LDS of one workgroup of k_forest / k_forest_ehvi
 hipError_t launch_forest(const ForestArgs& a, hipStream_t st);
+
+// a packed forest with m outputs per leaf over the current candidates (kernels_forest_ehvi.hip): per-tree traversal -> mean /
+// variance over the trees per output -> EHVI over the cells -> per-block argmax records, one launch for all M rows.  A tree is
+// [n_nodes records | n_leaves x m values], leaf-major; tree_words is the largest n_nodes + m n_leaves.
+struct ForestEhviArgs {
+  const double* Xs;               // candidates, M x d row-major
+  int64_t M;                      // rows of Xs
+  int64_t row0, nrows;            // rows [row0, row0 + nrows) are evaluated by this launch
+  int d;
+  const unsigned long long* words;
+  const ForestTree* tree;         // [T]
+  int T;
+  int tree_words;
+  int m;                          // outputs, 2 .. BOGP_MAX_TARGETS
+  double* mu_out;                 // [M][m] or null (indexed by the global row)
+  double* mse_out;                // [M][m] or null
+  double* leaves_out;             // [nrows][T][m] per-tree predictions or null (indexed by row - row0)
+  int C;                          // cells; 0: moments only (nothing below is touched)
+  const double* lower;            // [C][m] cell bounds (device)
+  const double* upper;            // [C][m] (+inf allowed)
+  double* ehvi_out;               // [M] or null
+  double* blk_val;                // [blocks of this launch] per-block partial argmax
+  int64_t* blk_idx;
+};
+hipError_t launch_forest_ehvi(const ForestEhviArgs& a, hipStream_t st);
 
 // the fused small-N sweep (kernels_small.hip): one launch = producer + contraction + posterior + q criteria + argmax
 struct SmallArgs {

@@ -16,8 +16,6 @@
 
 namespace bogp {
 
-__device__ __forceinline__ double ehvi_G(double z) { return norm_pdf(z) - z * ndtr(-z); }
-
 template <int MT>
 __global__ __launch_bounds__(256) void k_ehvi(EhviArgs a) {
   __shared__ double sv[4];
@@ -55,19 +53,7 @@ __global__ __launch_bounds__(256) void k_ehvi(EhviArgs a) {
       if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse;
       sd[k] = sqrt(fmax(mse, 1e-9));
     }
-    double acc = 0.0;
-    for (int c = 0; c < a.C; ++c) {  // the cell bounds are the same for every lane
-      double p = 1.0;
-#pragma unroll
-      for (int k = 0; k < MT; ++k) {
-        const double l = a.lower[(size_t)c * MT + k], u = a.upper[(size_t)c * MT + k];
-        const double gl = ehvi_G((l - mu[k]) / sd[k]);
-        const double gu = isinf(u) ? 0.0 : ehvi_G((u - mu[k]) / sd[k]);
-        p *= sd[k] * (gl - gu);
-      }
-      acc += p;
-    }
-    v = acc;
+    v = ehvi_cells<MT>(a.lower, a.upper, a.C, mu, sd);  // (bogp_device.h: shared with k_forest_ehvi)
     idx = g;
     a.ehvi_out[g] = v;
   }

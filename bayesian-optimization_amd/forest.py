@@ -7,7 +7,9 @@ caller's side, like scipy's L-BFGS-B in the default `tell`); everything after th
 csrc/kernels_forest.hip).  There is no CPU fallback for prediction.
 
   pack(model)            flat node arrays of anything shaped like a fitted RandomForestRegressor, plus the raw <-> encoded column map
-                         of the reference's `_check_X` (:105-110)
+                         of the reference's `_check_X` (:105-110); `multi_output=True` admits a forest fitted on y (N, m): one tree
+                         structure, m values a leaf (what MOBO fits, mobo.py:155-160), served by `bogp_forest_*_multi` and, for
+                         `bogp.EHVI`, `bogp_forest_sweep_ehvi` (csrc/kernels_forest_ehvi.hip)
   PackedForest.raw()     the same forest rewritten onto the RAW columns: a split of a one-hot column becomes `x[v] != level -> left`
                          on the column that holds the level index, so a mixed candidate stays d wide instead of d_enc wide
   RandomForest           scikit-learn's regressor with the reference's defaults; `predict(X, eval_MSE)` on the device
@@ -31,7 +33,8 @@ class PackedForest:
     """Flat arrays of T trees in the forest's own (encoded) feature space, and the column map.
 
     tree_offset (T + 1), feature / left / right (int32), threshold / value (float64): scikit-learn's `tree_` arrays, concatenated;
-    child indices are relative to their tree, a leaf has left == right == -1.
+    child indices are relative to their tree, a leaf has left == right == -1.  `value` is (nodes,) for one output (m = 1) and
+    (nodes, m) for a forest with several outputs.
     d_raw, d_enc; noncat: raw indices of the non-categorical columns in order (encoded columns 0 .. len(noncat) - 1); cat_idx: raw
     indices of the categorical columns, sorted; categories[j]: the level labels of cat_idx[j], one encoded column each, block after
     block behind the non-categorical ones -- as `_check_X` builds them."""
@@ -41,6 +44,7 @@ class PackedForest:
         self.left, self.right, self.value = left, right, value
         self.d_raw, self.noncat, self.cat_idx, self.categories = int(d_raw), list(noncat), list(cat_idx), [list(c) for c in categories]
         self.T = len(tree_offset) - 1
+        self.m = int(value.shape[1]) if np.ndim(value) == 2 else 1
         # encoded column -> (raw column, level index or -1)
         self.enc_cols = [(v, -1) for v in self.noncat]
         for v, cats in zip(self.cat_idx, self.categories):
@@ -121,27 +125,41 @@ def _label_lookup(cats):
     return find
 
 
-def pack(model) -> PackedForest:
+def n_outputs(model) -> int:
+    """Outputs of a fitted forest (1 before the fit)."""
+    return int(getattr(model, "n_outputs_", 1) or 1)
+
+
+def pack(model, multi_output: bool = False) -> PackedForest:
     """Flat arrays of a fitted forest: anything with `estimators_[t].tree_` (`children_left`, `children_right`, `feature`,
-    `threshold`, `value`) and, if present, the reference's `_cat_idx` / `_categories`."""
+    `threshold`, `value`) and, if present, the reference's `_cat_idx` / `_categories`.  A forest with several outputs is packed
+    only on request (`multi_output=True`: `value` becomes (nodes, m) = `tree_.value[:, :, 0]`); the one-output entry points do not
+    serve it."""
     est = getattr(model, "estimators_", None)
     if not est:
         raise ValueError("the forest is not fitted (no estimators_)")
-    if int(getattr(model, "n_outputs_", 1)) > 1:
-        raise NotImplementedError("forests with several outputs (n_outputs_ = %d) are not served" % int(model.n_outputs_))
+    m = n_outputs(model)
+    if m > 1 and not multi_output:
+        raise NotImplementedError("forests with several outputs (n_outputs_ = %d) are not served by the one-output calls: "
+                                  "pack(model, multi_output=True)" % m)
+    if m > _lib.MAX_TARGETS:
+        raise NotImplementedError("forests with several outputs: n_outputs_ = %d, at most %d are served" % (m, _lib.MAX_TARGETS))
     off, feat, thr, left, right, val = [0], [], [], [], [], []
     for e in est:
         t = e.tree_
         v = np.asarray(t.value, dtype=float)
-        if v.ndim > 1 and int(np.prod(v.shape[1:])) != 1:
-            raise NotImplementedError("forests with several outputs are not served")
         n = len(t.children_left)
+        if m > 1:
+            if v.shape != (n, m, 1):
+                raise ValueError("tree_.value has shape %s, expected (%d, %d, 1)" % (v.shape, n, m))
+        elif v.ndim > 1 and int(np.prod(v.shape[1:])) != 1:
+            raise NotImplementedError("forests with several outputs are not served")
         off.append(off[-1] + n)
         feat.append(np.asarray(t.feature, dtype=np.int32))
         thr.append(np.asarray(t.threshold, dtype=float))
         left.append(np.asarray(t.children_left, dtype=np.int32))
         right.append(np.asarray(t.children_right, dtype=np.int32))
-        val.append(v.reshape(n))
+        val.append(v.reshape(n, m) if m > 1 else v.reshape(n))
     d_enc = int(getattr(model, "n_features_in_", 0) or (max(int(f.max()) for f in feat) + 1))
     cat_idx = list(getattr(model, "_cat_idx", []) or [])
     categories = list(getattr(model, "_categories", []) or []) if cat_idx else []
@@ -169,9 +187,12 @@ class _Device:
         if not est:
             raise Exception("The model is not fitted yet!")
         if self.fitted_on is not est:  # a fit builds a new list
-            p = pack(model)
+            p = pack(model, multi_output=True)
             f, t, test = p.raw()
-            self.engine.forest_set(p.d_raw, p.tree_offset, f, t, p.left, p.right, p.value, test)
+            if p.m > 1:
+                self.engine.forest_set_multi(p.d_raw, p.m, p.tree_offset, f, t, p.left, p.right, p.value, test)
+            else:
+                self.engine.forest_set(p.d_raw, p.tree_offset, f, t, p.left, p.right, p.value, test)
             self.engine.set_candidate_transform()
             self.packed, self.fitted_on = p, est
         return self
@@ -186,10 +207,14 @@ def device_of(model) -> _Device:
 
 
 def predict(model, X, eval_MSE=False):
-    """`RandomForest.predict(X, eval_MSE)` (random_forest.py:124-155) of a fitted forest on the device."""
+    """`RandomForest.predict(X, eval_MSE)` (random_forest.py:124-155) of a fitted forest on the device: (M,) moments for one
+    output, (M, m) for a forest fitted on y (N, m), as the reference returns them."""
     dev = device_of(model)
     dev.engine.upload_candidates(dev.packed.to_index(X))
-    mu, mse = dev.engine.forest_predict(eval_MSE=bool(eval_MSE))
+    if dev.packed.m > 1:
+        mu, mse = dev.engine.forest_predict_multi(eval_MSE=bool(eval_MSE))
+    else:
+        mu, mse = dev.engine.forest_predict(eval_MSE=bool(eval_MSE))
     return (mu, mse) if eval_MSE else mu
 
 
@@ -367,17 +392,46 @@ def decode_rows(cols: Sequence[_Column], Xi: np.ndarray) -> list:
 # ---------------------------------------------------------------------------------------------------------------------------------
 # sweeps
 # ---------------------------------------------------------------------------------------------------------------------------------
+def _is_ehvi(c) -> bool:
+    return bool(getattr(c, "is_ehvi", False))
+
+
 def _shared(criteria):
+    """(first criterion, its model's device, [(acq_id, par)] -- None for an EHVI, which sweeps alone on a forest with n_obj outputs)."""
     c0 = criteria[0]
-    if any(getattr(c, "is_ehvi", False) for c in criteria):
-        raise NotImplementedError("EHVI takes a multi-target Gaussian process: a forest model has one target")
+    ehvi = any(_is_ehvi(c) for c in criteria)
+    m = n_outputs(c0.model)
+    fitted = bool(getattr(c0.model, "estimators_", None))  # (an unfitted model is device_of's to refuse)
+    if ehvi:
+        if len(criteria) != 1:
+            raise ValueError("an EHVI criterion sweeps alone: it cannot share a sweep with other criteria")
+        if fitted and (m < 2 or c0.n_obj != m):
+            raise NotImplementedError("EHVI over %d objectives on a forest with %d output%s: EHVI takes a forest fitted on y (N, n_obj), "
+                                      "2 <= n_obj <= %d" % (c0.n_obj, m, "" if m == 1 else "s", _lib.MAX_TARGETS))
+    elif m > 1:
+        raise NotImplementedError("%s on a forest with %d outputs: the single-target criteria (EI, PI, EpsilonPI, UCB, MGFI) take a "
+                                  "forest with one output; a forest with several takes EHVI" % (type(c0).__name__, m))
     for c in criteria[1:]:
         if c.model is not c0.model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin():
             raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
     dev = device_of(c0.model)
     if getattr(dev.engine, "comm_world", 0) > 1:
         raise NotImplementedError("a forest sweep runs on one rank (no multi-rank exchange of its winners)")
-    return c0, dev, [(c.acq_id, c.acq_par()) for c in criteria]
+    return c0, dev, (None if ehvi else [(c.acq_id, c.acq_par()) for c in criteria])
+
+
+def _sweep(c0, dev, acq, k: int, return_values: bool = False):
+    """The sweep over the engine's current candidates: (values (q, k), indices (q, k)[, criterion values (q, M)])."""
+    if acq is None:  # EHVI on the moments of a forest with several outputs (bogp_forest_sweep_ehvi)
+        out = dev.engine.forest_sweep_ehvi(c0.cell_lower_bounds, c0.cell_upper_bounds, k=int(k), return_values=return_values)
+        return tuple(np.asarray(a)[None, :] for a in out)
+    return dev.engine.forest_sweep_topk(acq, c0.effective_plugin(), c0.minimize, int(k), return_values=return_values)
+
+
+def ehvi_sweep(criterion, k: int = 1, return_values: bool = False):
+    """`EHVI.sweep` on a forest model, over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
+    c0, dev, acq = _shared([criterion])
+    return tuple(a[0] for a in _sweep(c0, dev, acq, k, return_values))
 
 
 def _one_rank(group=None, rank=None, world=None):
@@ -391,8 +445,7 @@ def criterion_values(criterion, X) -> np.ndarray:
     """The criterion at every row of X (rows in the reference's format): one device pass."""
     c0, dev, acq = _shared([criterion])
     dev.engine.upload_candidates(dev.packed.to_index(X))
-    _, _, vals = dev.engine.forest_sweep_topk(acq, c0.effective_plugin(), c0.minimize, 1, return_values=True)
-    return vals[0]
+    return _sweep(c0, dev, acq, 1, return_values=True)[2][0]
 
 
 def sweep_topk_host(criteria, X, k: int = 1):
@@ -400,7 +453,7 @@ def sweep_topk_host(criteria, X, k: int = 1):
     c0, dev, acq = _shared(criteria)
     X_ = dev.packed._object_rows(X)
     dev.engine.upload_candidates(dev.packed.to_index(X_))
-    vals, idx = dev.engine.forest_sweep_topk(acq, c0.effective_plugin(), c0.minimize, int(k))
+    vals, idx = _sweep(c0, dev, acq, k)
     rows = [[X_[i].tolist() if i >= 0 else None for i in r] for r in idx]
     return vals, idx, rows
 
@@ -411,7 +464,7 @@ def sweep_topk_device(criteria, space, M: int, k: int = 1, seed: int = 0):
     c0, dev, acq = _shared(criteria)
     cols = space_columns(space, dev.packed)
     generate(dev, cols, int(M), int(seed))
-    vals, idx = dev.engine.forest_sweep_topk(acq, c0.effective_plugin(), c0.minimize, int(k))
+    vals, idx = _sweep(c0, dev, acq, k)
     ok = idx >= 0
     Xi = dev.engine.read_candidates(np.clip(idx, 0, int(M) - 1).ravel())
     dec = decode_rows(cols, Xi)

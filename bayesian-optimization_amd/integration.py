@@ -117,8 +117,15 @@ def _effective(optimizer, eval_budget):
 def mobo_create_acquisition(self, fixed=None, **kwargv):
     """Drop-in body for `bayes_optim.mobo.MOBO._create_acquisition` (mobo.py:177-186): with a device model, an inner
     optimiser of the sweep family ("sweep", "sweep-device[-lhs|-sobol]") and a continuous space the criterion is this
-    package's `EHVI` (float64, cells from `bogp.pareto`), wrapped exactly as the original wraps the reference's; every
-    other configuration runs the original unchanged."""
+    package's `EHVI` (float64, cells from `bogp.pareto`), wrapped exactly as the original wraps the reference's; so it is with
+    a forest model (`is_forest_model`: this package's `RandomForest` or the reference's) under "sweep" / "sweep-device" on any
+    space a forest sweep serves.  Every other configuration -- "MIES", the reference's default on mixed spaces, CMA, BFGS --
+    runs the original unchanged."""
+    if getattr(self, "_optimizer", None) in ("sweep", "sweep-device") and _forest.is_forest_model(getattr(self, "model", None)):
+        # a RandomForest fitted on y (N, n_obj) (this package's or the reference's), on any space a forest sweep serves: the
+        # forest walk and EHVI are one device pass; what a forest sweep does not take is refused by optim.argmax_restart by name
+        criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
+        return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
     optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
     if optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(getattr(self, "search_space", None)):
         return _ORIGINAL["mobo"](self, fixed=fixed, **kwargv)

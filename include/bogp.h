@@ -365,6 +365,33 @@ int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, double* per_tre
 int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
                            int k, double* best_val, int64_t* best_idx, double* acq_out);
 int bogp_forest_info(const bogp_handle* h, int64_t* out);
+/* Forests with SEVERAL outputs, and the expected hypervolume improvement on their moments.  Replaces, for a RandomForest
+ * fitted on y (N, m), RandomForest.predict (surrogate/random_forest.py:141-155: scikit-learn grows one tree structure whose
+ * leaves hold m values, tree_.value (n_nodes, m, 1); mu = mean and MSE = std(ddof = 1)^2 over the trees, per output, both
+ * (M, m)) and, on these moments, EHVI.forward (multi_objective/analytic.py:223-274) as MOBO maximises it on mixed spaces
+ * (mobo.py:168-186) -- one kernel walks the forest and evaluates EHVI per candidate, with the arithmetic of bogp_sweep_ehvi
+ * on the moments (sigma_k = sqrt(max(MSE_k, 1e-9)), one product per cell, an upper bound at +inf exact).
+ * `forest_set_multi`: bogp_forest_set with `value` nodes x m row-major (tree_.value[:, :, 0]); 2 <= m <= BOGP_MAX_TARGETS,
+ * the same validation walk, the same BOGP_ERR_UNSUPPORTED when the largest tree (n_nodes + m n_leaves words, twice) and
+ * 256 rows of d features exceed a workgroup's LDS.  It replaces any forest the handle held.
+ * `forest_outputs`: m of the handle's forest (1 after bogp_forest_set; 0 without a forest).
+ * `forest_predict_multi`: mu (M x m), mse (M x m, may be NULL) of the current candidates, HOST buffers.
+ * `forest_leaves_multi`: per-tree, per-output predictions of rows [first_row, first_row + n), n x T x m row-major.
+ * `forest_sweep_ehvi`: m, C, lower, upper, k, best_val, best_idx, ehvi_out, mu_out, mse_out as bogp_sweep_ehvi (the same
+ * limits BOGP_MAX_EHVI_CELLS / BOGP_MAX_TOPK, first maximum, ties -> lower index, NaN maximal, slots beyond M (-inf, -1));
+ * m must equal the forest's outputs.  Rows that reach the same leaves get the same bits.  The kernel's time is reported
+ * as acquisition_ms by bogp_last_timing.
+ * The one-output calls (bogp_forest_predict / _leaves / _sweep_topk) return BOGP_ERR_UNSUPPORTED on a forest of several
+ * outputs, these calls on a forest of one output; bogp_sweep_ehvi refuses every forest handle; a handle with a lift is
+ * refused (BOGP_ERR_UNSUPPORTED).  A refused call launches nothing.                                                  */
+int bogp_forest_set_multi(bogp_handle* h, int T, int d, int m, const int64_t* tree_offset, const int32_t* feature,
+                          const double* threshold, const int32_t* left, const int32_t* right, const double* value,
+                          const int32_t* test);
+int bogp_forest_outputs(const bogp_handle* h);
+int bogp_forest_predict_multi(bogp_handle* h, double* mu, double* mse);
+int bogp_forest_leaves_multi(bogp_handle* h, int64_t first_row, int n, double* per_tree);
+int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
+                           int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 /* Candidates of a MIXED space drawn on the device (replaces SearchSpace._sample column by column: Real.sample,
  * search_space/variable.py:240-248, and _Discrete.sample, :260-278, whose randint(0, L) every Integer / Ordinal /
  * Discrete / Subset / Bool variable maps through its levels): the Philox stream of bogp_candidates_generate, element
