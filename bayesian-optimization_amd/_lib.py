@@ -23,6 +23,7 @@ ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was wri
 MAX_Q = 64
 MAX_TARGETS = 8
 MAX_TOPK = 32
+MAX_BELIEVED = 32  # BOGP_MAX_BELIEVED: q + pending points of one bogp_sweep_believer call
 LIFT_MAX_R, LIFT_MAX_RD = 64, 4096  # BOGP_LIFT_MAX_R / BOGP_LIFT_MAX_RD: reduced dimensions and r x D of a lift
 MAX_EHVI_CELLS = 65536  # BOGP_MAX_EHVI_CELLS: cells one bogp_sweep_ehvi call takes
 COMM_ID_BYTES = 128
@@ -67,6 +68,8 @@ SIGNATURES = {
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
+    "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_lift_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bogp_lift_clear": (C.c_int, [C.c_void_p]),
     "bogp_lift_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _lp, _dp, _dp]),
@@ -589,6 +592,40 @@ class Engine:
         if return_moments:
             out += (mu, mse)
         return out
+
+    def sweep_believer(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, pending=None, believe_plugin=True,
+                       return_values=False):
+        """Kriging-believer batch over the current candidates (bogp_sweep_believer): step j maximises criterion j on the mean and
+        on the variance conditioned on the `pending` rows (n, d) and on the winners of the steps before it.  Returns a dict:
+        best_val (q,), best_idx (q,), best_x (q, d), pivots (n + q,) and, with return_values, acq (q, M) and mse (q, M)."""
+        q = len(acq)
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        pend = None if pending is None or len(pending) == 0 else _f64(pending)
+        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
+            raise ValueError("pending points must have shape (n, %d)" % self.d)
+        n_pend = 0 if pend is None else pend.shape[0]
+        best = np.empty(q)
+        idx = np.empty(q, dtype=np.int64)
+        bx = np.empty((q, self.d))
+        piv = np.empty(n_pend + q)
+        vals = np.empty((q, self.M)) if return_values else None
+        mse = np.empty((q, self.M)) if return_values else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_believer(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
+                                                  int(bool(believe_plugin)), _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp),
+                                                  _ptr(bx), _ptr(piv), _ptr(vals), _ptr(mse)))  # fmt: skip
+        out = dict(best_val=best, best_idx=idx, best_x=bx, pivots=piv)
+        if return_values:
+            out.update(acq=vals, mse=mse)
+        return out
+
+    def believer_last(self) -> dict:
+        """Producer, solve and k_believer time (ms) and the candidate passes of the last sweep_believer (bogp_believer_last)."""
+        c, s, b, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_believer_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(b), _dp),
+                                                 C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, believer_ms=b.value, n_passes=n.value)
 
     # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------
     def set_lift(self, A, mean, center, lo, hi):

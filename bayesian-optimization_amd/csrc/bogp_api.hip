@@ -121,6 +121,7 @@ extern "C" void bogp_destroy(bogp_handle* h) {
   comm_release(h);
   point_release(h);
   batch_release(h);
+  believer_release(h);
   free_train(h);
   (void)hipStreamSynchronize(h->stream2);
   if (h->stream_upd) (void)hipStreamSynchronize(h->stream_upd);

@@ -15,6 +15,7 @@ namespace bogp {
 void comm_release(bogp_handle* h);   // bogp_comm.hip: destroys an owned communicator, frees the exchange buffers
 void point_release(bogp_handle* h);  // bogp_point.hip: frees the point-evaluation buffers
 void batch_release(bogp_handle* h);  // bogp_batch.hip: frees the batched-likelihood staging and workspaces
+void believer_release(bogp_handle* h);  // bogp_api_believer.hip: frees the Kriging-believer arrays and events
 std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: the handles a batch of one-evaluation calls is dealt over
 // bogp_point.hip: posterior, input-gradients and q criteria of B points through k_point_rhs + k_point_tri.  `Xb` is a HOST
 // array (B x d).  Outputs (host, any may be null): mu, mse (B), dmu, dmse (B x d), acq (B x q), dacq (B x q x d).
@@ -136,6 +137,16 @@ struct bogp_handle {
   hipEvent_t lift_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // filter begin / end, merge begin / end
   int64_t lift_n_feasible = 0;
   double lift_filter_ms = 0, lift_merge_ms = 0;
+
+  // Kriging-believer batches (bogp_api_believer.hip): the running variance and the stored c_k columns of the believed points
+  double* dbel_s = nullptr;      // [M] sigma2 s_B(x), unclamped below the sweep's own clamp of s_0
+  double* dbel_C = nullptr;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
+  double* dbel_row = nullptr;    // [2][M] criterion values / MSE of the step evaluated last
+  double* dbel_small = nullptr;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
+  size_t bel_s_cap = 0, bel_C_cap = 0, bel_row_cap = 0, bel_small_cap = 0;
+  std::vector<hipEvent_t> bel_ev;
+  double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
+  int bel_passes = 0;                                          // candidate passes it ran after pass 0
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

@@ -100,6 +100,44 @@ struct EhviArgs {
 };
 hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
 
+// one Kriging-believer pass over a chunk (kernels_believer.hip): the rank-one downdate of the running variance by the believed point p,
+// c(x) = (k(x, p) - r(x) . a + u(x) u(p) - sum_k c_k(x) c_k(p)) / sqrt(pivot), s(x) -= sigma2 c(x)^2, and -- for the pass in front of a
+// step -- that step's criterion on (mu, max(0, s)) with the per-block argmax records k_argmax_final reads (one record per 64 rows)
+struct BelieverArgs {
+  const double* Xs;       // candidates, M x d row-major
+  const double* theta;    // d (+ the exponent of generalized_exponential / the order of the general Matern kernel)
+  const double* pt;       // d: the believed point
+  const double* rT;       // [Np][Mc] the chunk's correlation columns
+  const double* w_part;   // [S][Mc] slice sums of w . r (ordinary kriging)
+  const double* avec;     // [N] R^-1 r(p)
+  int d, N, S;
+  int64_t Mc, mcount, m0, M;
+  int update;             // 0: criterion only (a guarded pivot: c = 0), nothing above is read
+  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
+  int n_taken;            // winners of the steps before: their rows keep their criterion value but leave the argmax
+  int64_t taken[32];
+  double u_p, inv_root;   // u(p); 1 / sqrt(pivot)
+  double G;
+  int estimate_trend;
+  int nprev;              // stored columns this point is orthogonalised against
+  int prev_slot[32];
+  double prev_c[32];      // c_k(p)
+  const double* C;        // [slots][M]
+  double* c_out;          // [M] this point's column, or null (the last believed point)
+  double* s;              // [M] in / out
+  double sigma2;
+  int eval;               // evaluate one criterion behind the update
+  int acq_id, minimize;
+  double acq_par, plugin;
+  const double* mu;       // [M]
+  double* acq_out;        // [M]
+  double* mse_out;        // [M]
+  double* blk_val;
+  int64_t* blk_idx;
+  int64_t blk_offset;
+};
+hipError_t launch_believer(int kernel, const BelieverArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

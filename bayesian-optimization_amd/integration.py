@@ -96,12 +96,21 @@ def fused_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=N
     design = optim.DEVICE_DESIGNS.get(optimizer)
     k = int(min(32, n_point + 8))  # fall-backs: at most n_point - 1 taken by earlier criteria + a few history hits
     xs, fs = optim.batch_argmax(crits, kw["search_space"], int(budget or kw["eval_budget"]), history=_history_of(self), k=k,
-                                design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"))  # fmt: skip
+                                design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"), **_strategy_of(masks, kw))  # fmt: skip
     return tuple(xs), tuple(fs)
+
+
+def _strategy_of(masks, kw) -> dict:
+    """The `strategy` keyword of the fused step's `batch_argmax` call: none under the default, and none for what the believer does
+    not serve -- fixed variables and constraints stay on the top-k strategy, which serves them."""
+    if _BATCH.get("strategy", "topk") == "topk" or masks is not None or kw.get("h") is not None or kw.get("g") is not None:
+        return {}
+    return {"strategy": _BATCH["strategy"]}
 
 
 _ORIGINAL: dict = {}
 _REROUTE: dict = {}
+_BATCH: dict = {}  # install(batch_strategy=...): how the fused ParallelBO step makes its q points differ ("topk" when empty)
 _SURROGATE_DEFAULTS: dict = {}  # keyword defaults install() gives the device GaussianProcess (e.g. restart_batch)
 
 
@@ -341,7 +350,7 @@ def _dispatching_surrogate(host_cls):
 
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
-            restart_batch: int = None):
+            restart_batch: int = None, batch_strategy: str = "topk"):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -354,7 +363,17 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     reroute their inner maximisation becomes one sweep of `sweep_budget` candidates instead -- no change to the driver's
     constructor call.  Constrained problems, foreign models and non-real spaces are never rerouted.
 
-    `restart_batch` = R: device models built through the re-pointed name get `restart_batch=R` unless the call names its own."""
+    `restart_batch` = R: device models built through the re-pointed name get `restart_batch=R` unless the call names its own.
+
+    `batch_strategy` = "topk" | "believer": how the fused `ParallelBO` step keeps its q points apart.  "topk" (default): each
+    criterion falls back through its top-k; "believer": `optim.believer_batch` -- criterion j sees the variance conditioned on
+    the winners before it (a step with fixed variables or constraints, which the believer does not serve, keeps "topk").  The q
+    parameters are drawn with the reference's sampler in the reference's order either way."""
+    if batch_strategy not in ("topk", "believer"):
+        raise ValueError("batch_strategy must be 'topk' or 'believer', not %r" % (batch_strategy,))
+    _BATCH.clear()
+    if batch_strategy != "topk":
+        _BATCH["strategy"] = batch_strategy
     if restart_batch is not None:
         # the models `fmin` / the drivers build through the re-pointed GaussianProcess name fit with their MLE restarts in lock step
         # (surrogate.GaussianProcess(restart_batch=R), DESIGN.md 5.13): `tell()` is most of a BO loop's wall time.  Opt-in: the
@@ -425,4 +444,5 @@ def uninstall():
             rext.GaussianProcess = ext_gp
     _ORIGINAL.clear()
     _REROUTE.clear()
+    _BATCH.clear()
     _SURROGATE_DEFAULTS.clear()

@@ -20,6 +20,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 from scipy.optimize import fmin_l_bfgs_b
 
+from . import _lib
 from . import distributed
 from . import forest as _forest
 from .lift import Lift
@@ -349,7 +350,7 @@ def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, 
 def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Optional[np.ndarray] = None, k: int = 8,
                  index_offset: Optional[int] = None, group=None, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
                  seed: Optional[int] = None, rank: Optional[int] = None, world: Optional[int] = None, masks=None, values=None,
-                 h: Optional[Callable] = None, g: Optional[Callable] = None):
+                 h: Optional[Callable] = None, g: Optional[Callable] = None, strategy: str = "topk"):
     """The q-point proposal of `ParallelBO._batch_arg_max_acquisition` (bayes_opt.py:100-115) in ONE posterior pass:
     q criteria (same model; they differ only in t / alpha) share (mu, MSE); each takes its best candidate that is
     neither already taken by an earlier criterion nor `np.isclose` to an evaluated point in `history`
@@ -361,7 +362,17 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
     free variables only, the fixed columns are filled in for the model, `history` holds full points, and the returned
     points hold the free variables (the caller's `fillin_fixed_value` completes them, base.py:476).  `h` / `g` (constraints
     over the free variables, one point as a list): only host-sampled candidates the reference would accept as a restart's
-    outcome (`feasible_rows`) enter the sweep; with none, `((), ())` -- the reference's "no feasible restart" answer."""
+    outcome (`feasible_rows`) enter the sweep; with none, `((), ())` -- the reference's "no feasible restart" answer.
+    `strategy`: "topk" (the above) or "believer" -- `believer_batch`: criterion j is maximised on the variance conditioned on
+    the winners before it, and a row that is a winner does not compete again: the q points differ by construction.  `history`
+    and `k` are not used then: a winner `np.isclose` to an evaluated point is left to the caller's padding, as the last
+    fall-back above is."""
+    if strategy == "believer":
+        xs, fs = believer_batch(list(criteria), search_space, eval_budget, Xs=Xs, design=design, seed=seed, masks=masks, values=values,
+                                h=h, g=g, group=group, rank=rank, world=world)
+        return xs, fs
+    if strategy != "topk":
+        raise ValueError("strategy must be 'topk' or 'believer', not %r" % (strategy,))
     if _forest.is_forest_model(criteria[0].model):
         _forest.check_optimizer("sweep", h, g, masks)
         _forest._one_rank(group, rank, world)
@@ -410,6 +421,64 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
         chosen_x.append((x[~masks] if masks is not None else x).tolist())
         chosen_f.append(float(vals[c, pick]))
     return tuple(chosen_x), tuple(chosen_f)
+
+
+def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = None, Xs: Optional[np.ndarray] = None,
+                   design: Optional[str] = None, seed: Optional[int] = None, pending=None, believe_plugin: bool = True, lift=None,
+                   masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):
+    """A q-point proposal by the Kriging believer (Ginsbourger et al. 2010; `bogp_sweep_believer`): ONE posterior pass, then one
+    streaming pass over the candidates per proposed point.  Step j maximises criterion j on the posterior mean and on the
+    variance conditioned on `pending` (rows submitted but not yet evaluated, (n, d)) and on the winners of the steps before it
+    -- believed at their predicted mean, which leaves the mean as it is.  `criteria`: one criterion (replicated `q` times; EI
+    and EpsilonPI serve as well as MGFI and UCB) or a sequence used in order (same model, minimize and plugin).  With
+    `believe_plugin` the plugin of a step is the best of the criterion's own and the believed means.  The candidates are
+    `eval_budget` rows of `search_space.sample`, the rows `Xs`, or -- `design` = "uniform" | "LHS" | "sobol" -- drawn on the
+    device, as in `batch_argmax`.  Returns (xopt: tuple of q lists, fopt: tuple of q floats) in `batch_argmax`'s format.
+    Refused (NotImplementedError): a forest model, EHVI, a lift, fixed variables, constraints, more than one rank."""
+    if hasattr(criteria, "acq_id") or is_ehvi(criteria) or not isinstance(criteria, (list, tuple)):
+        criteria = [criteria] * int(1 if q is None else q)
+    else:
+        criteria = list(criteria)
+        if q is not None and int(q) != len(criteria):
+            raise ValueError("q = %d but %d criteria were given" % (q, len(criteria)))
+    if len(criteria) == 0:
+        raise ValueError("the believer needs at least one criterion")
+    c0 = criteria[0]
+    model = c0.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if any(is_ehvi(c) for c in criteria):
+        raise NotImplementedError("EHVI has no believer batches: the front and its cells change with each believed point")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no believer batches")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no believer batches")
+    if h is not None or g is not None:
+        raise NotImplementedError("constraints have no believer batches")
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    plugins = {c.effective_plugin() for c in criteria if c.acq_id != _lib.ACQ_UCB}  # (UCB reads no plugin: it may join any batch)
+    if any(c.model is not model or c.minimize != c0.minimize for c in criteria[1:]) or len(plugins) > 1:
+        raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
+    plugin = plugins.pop() if plugins else 0.0
+    if len(criteria) + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
+        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
+    if design is not None:
+        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
+    out = eng.sweep_believer([(c.acq_id, c.acq_par()) for c in criteria], plugin, c0.minimize, pending=pend,
+                             believe_plugin=believe_plugin)
+    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
 
 
 def unwrap_criterion(obj):

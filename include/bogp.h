@@ -294,6 +294,42 @@ int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_
 int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
                     int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 
+/* ---- sweep: Kriging-believer batches ------------------------------------------------------------------
+ * q proposals per call from q criteria, where step j sees the variance conditioned on the points believed before it
+ * (Ginsbourger, Le Riche, Carraro 2010).  The reference has no such strategy: ParallelBO's q criteria share one posterior
+ * and differ only in a sampled t / alpha (bayes_opt.py:82-115; EI raises, :86), MOBO's "EHVI with Kriging believer" is a
+ * TODO (mobo.py:168-178) and set_X_pending raises (multi_objective/analytic.py:95-96).  Believing y = mu(p) at fixed
+ * hyper-parameters leaves the mean (gpr.py:490) unchanged and takes a rank-one term off the bracket of gpr.py:502-510.
+ * With kappa0(x, x') = k(x, x') - r(x)^T R^-1 r(x') + u(x) u(x') (k the committed correlation, u = (w.r - 1) / G under
+ * ordinary kriging, else 0) and the believed points p_1 .. p_B -- the pending rows first, then each step's winner:
+ *   b_i(x) = kappa0(x, p_i) - sum_{k<i} c_k(x) c_k(p_i),  pivot_i = b_i(p_i),  c_i(x) = b_i(x) / sqrt(pivot_i),
+ *   s_i(x) = s_{i-1}(x) - c_i(x)^2,  s_0(x) = kappa0(x, x),   MSE_j(x) = sigma2 max(0, s_B(x)),  mean mu(x)
+ * A pivot <= 1e-12 (a training point of a noiseless model, a repeated point) gives c_i = 0.  On the candidate row that is a
+ * winner, c_i(p_i)^2 = pivot_i = s_{i-1}(p_i): its s is set to exactly 0.  Step j maximises criterion j on (mu, MSE_j) with
+ * bogp_sweep's argmax rule OVER THE ROWS THAT ARE NOT WINNERS YET: a winner's row keeps its criterion value in acq_out but does
+ * not compete again (on its zero variance EpsilonPI is Phi(+-inf), exactly 1 once its mean has become the plugin, and UCB is
+ * its bare mean), so the q winners are q distinct rows and q <= M is required.  Without pending points step 0 IS bogp_sweep
+ * with criterion 0, bit for bit.
+ *   q, acq_id, acq_par, plugin, minimize   as bogp_sweep; 1 <= q, q + n_pending <= BOGP_MAX_BELIEVED
+ *   believe_plugin   1: the plugin of a step is the best of the given one and the means believed so far, in the
+ *                    criterion's sign -- min(plugin, mu(p)) when minimising, min(plugin, -mu(p)) otherwise (the plugin
+ *                    arrives negated when maximising: the largest believed mean); 0: as given
+ *   pending          n_pending x d HOST rows (submitted, not yet evaluated), NULL for n_pending = 0
+ *   best_val, best_idx (q), best_x (q x d, may be NULL): each step's winner among the current candidates
+ *   pivots (n_pending + q), acq_out (q x M), mse_out (q x M): optional HOST buffers; row j is what step j saw
+ * Per believed point: one solve R^-1 r(p) and ONE pass over the candidates (correlation producer + k_believer, 8 N bytes
+ * per candidate; the producer runs once when one chunk holds all candidates); the N^2 contraction runs once, in pass 0.  Works on the current candidates however they were set.
+ * BOGP_ERR_INVALID: no committed model, no candidates, q < 1, q > M, the limit exceeded, a null required array, a non-finite
+ * pending entry.  BOGP_ERR_UNSUPPORTED: a polynomial trend basis, several targets, a lift on the handle, a communicator of
+ * more than one rank.  The handle's model, candidates and later plain sweeps are unaffected.
+ * `believer_last`: of the last call, the time of the producer launches, of the solves and of k_believer in ms, and the
+ * candidate passes behind pass 0; any pointer may be NULL.                                                          */
+#define BOGP_MAX_BELIEVED 32
+int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+                        int believe_plugin, const double* pending, int n_pending, double* best_val, int64_t* best_idx,
+                        double* best_x, double* pivots, double* acq_out, double* mse_out);
+int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* believer_ms, int* n_passes);
+
 /* ---- sweep in a reduced space: box-penalised criteria under a linear lift ---------------------------
  * Replaces PCABO's inner maximisation (extension.py:113-133): the criterion is maximised over a box of the REDUCED
  * space (r = the committed model's d, _compute_bounds :113-119) through penalized_acquisition (:62-86), which maps a
