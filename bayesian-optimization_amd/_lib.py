@@ -70,6 +70,10 @@ SIGNATURES = {
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_ehvi_grid_cells": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
+    "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
+                                           _dp, _dp]),
+    "bogp_believer_ehvi_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
     "bogp_lift_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bogp_lift_clear": (C.c_int, [C.c_void_p]),
     "bogp_lift_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _lp, _dp, _dp]),
@@ -162,6 +166,25 @@ def _f64(a, shape=None) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def grid_cells(Y, ref_point):
+    """(lower, upper), each C x m: libbogp's grid decomposition of the region above `ref_point` that the front of Y (n x m, may
+    be empty) does not dominate (bogp_ehvi_grid_cells: `pareto.hypercell_bounds` restated on the host side of the library, the
+    same arrays bit for bit).  No device is touched.  ValueError for what the library refuses (m outside [2, MAX_TARGETS], a
+    non-finite input, more than MAX_EHVI_CELLS cells)."""
+    lib = load()
+    r = _f64(ref_point).ravel()
+    m = len(r)
+    Y = _f64(Y).reshape(-1, m) if np.size(Y) else np.empty((0, m))
+    n = lib.bogp_ehvi_grid_cells(m, len(Y), _ptr(Y), _ptr(r), None, None, 0)
+    if n < 0:
+        raise ValueError("bogp_ehvi_grid_cells refused a front of %d rows in %d objectives (non-finite input, m outside [2, %d] or "
+                         "more than %d cells)" % (len(Y), m, MAX_TARGETS, MAX_EHVI_CELLS))  # fmt: skip
+    lower, upper = np.empty((n, m)), np.empty((n, m))
+    if lib.bogp_ehvi_grid_cells(m, len(Y), _ptr(Y), _ptr(r), _ptr(lower), _ptr(upper), n) != n:
+        raise BogpError(ERR_INVALID, "bogp_ehvi_grid_cells: the count changed between two calls")
+    return lower, upper
 
 
 OBJECTIVE_FN = C.CFUNCTYPE(None, _dp, C.c_int, _dp, _dp, C.c_void_p)
@@ -626,6 +649,47 @@ class Engine:
         self._check(self._lib.bogp_believer_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(b), _dp),
                                                  C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, believer_ms=b.value, n_passes=n.value)
+
+    def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):
+        """Kriging-believer batch under EHVI over the current candidates (bogp_sweep_believer_ehvi): step j maximises EHVI on the m
+        means and on the variances conditioned on the `pending` rows (n, d) and on the winners of the steps before it, over the cells
+        of the front of `front` (n_front, m; may be empty) above `ref_point` -- extended by every believed mean when `believe_front`.
+        Returns a dict: best_val (q,), best_idx (q,), best_x (q, d), best_mu (q, m), pivots (n + q,), n_cells (q,) and, with
+        return_values, ehvi (q, M) and mse (q, M, m)."""
+        r = _f64(ref_point).ravel()
+        m, q = len(r), int(q)
+        F = None if front is None or np.size(front) == 0 else _f64(front)
+        if F is not None and (F.ndim != 2 or F.shape[1] != m):
+            raise ValueError("the front must have shape (n, %d)" % m)
+        pend = None if pending is None or len(pending) == 0 else _f64(pending)
+        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
+            raise ValueError("pending points must have shape (n, %d)" % self.d)
+        n_pend = 0 if pend is None else pend.shape[0]
+        qa = max(q, 0)
+        best = np.empty(qa)
+        idx = np.empty(qa, dtype=np.int64)
+        bx = np.empty((qa, self.d))
+        bmu = np.empty((qa, m))
+        piv = np.empty(n_pend + qa)
+        nc = np.zeros(qa, dtype=np.int32)
+        vals = np.empty((qa, self.M)) if return_values else None
+        mse = np.empty((qa, self.M, m)) if return_values else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_believer_ehvi(self._h, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F), int(bool(believe_front)),
+                                                       _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(bmu),
+                                                       _ptr(piv), nc.ctypes.data_as(_ip), _ptr(vals), _ptr(mse)))  # fmt: skip
+        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, n_cells=nc)
+        if return_values:
+            out.update(ehvi=vals, mse=mse)
+        return out
+
+    def believer_ehvi_last(self) -> dict:
+        """Producer, solve, k_believer and k_believer_ehvi time (ms) and the candidate passes of the last sweep_believer_ehvi
+        (bogp_believer_ehvi_last)."""
+        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_believer_ehvi_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
+                                                      C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, ehvi_ms=e.value, n_passes=n.value)
 
     # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------
     def set_lift(self, A, mean, center, lo, hi):

@@ -8,6 +8,7 @@
 // A row that is a winner keeps its criterion value in the outputs but leaves the argmax of the later steps.
 // The running variance is kept as sigma2 s, started from the sweep's clamped MSE_0: where s_0 < 0 the clamp changes nothing that is
 // returned (s only decreases, and every output is max(0, .) of it).
+// bogp_sweep_believer_ehvi (below) is the same recursion for an m-target model under EHVI; bogp_ehvi_grid_cells the host's cell decomposition.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,6 +55,104 @@ struct Plan {  // chunking of the candidate passes: the producer's geometry of r
   int S;
 };
 
+Plan make_plan(int64_t M, int Np) {  // (run_sweep's for p = 1: chunk bytes, slices of 8 x 32 training rows)
+  Plan pl;
+  size_t chunk_bytes = (size_t)1 << 30;
+  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
+  const int64_t Mpad = ((M + 63) / 64) * 64;
+  int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Np * sizeof(double)) / 64) * 64;
+  pl.Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
+  pl.nchunk = (M + pl.Mc - 1) / pl.Mc;
+  pl.nblk_total = (M + 63) / 64 + pl.nchunk;
+  pl.S = (Np / 32 + 7) / 8;
+  return pl;
+}
+
+struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point's correlations with the believed rows, those rows
+  double *dpt, *dr, *dvr, *da, *dkk, *drows;
+  static size_t doubles(int d, int N) { return (size_t)d + 3 * (size_t)N + 2 * BOGP_MAX_BELIEVED + (size_t)BOGP_MAX_BELIEVED * d; }
+  SolveBufs(double* base, int d, int N) {
+    dpt = base;                          // d
+    dr = dpt + d;                        // N
+    dvr = dr + N;                        // N
+    da = dvr + N;                        // N
+    dkk = da + N;                        // 32 correlations of the point with the believed rows, 32 distances
+    drows = dkk + 2 * BOGP_MAX_BELIEVED;  // 32 x d believed rows
+  }
+};
+
+// The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, between two events appended to
+// ev_solve -- and the host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
+int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const double* x, const std::vector<double>& hw, std::vector<double>& hk,
+                   double* pivots, size_t& nev, std::vector<size_t>& ev_solve) {
+  const int i = bl.n, d = h->d, N = h->N;
+  hipStream_t st = h->stream;
+  hipEvent_t e0 = bel_event(h, nev), e1 = bel_event(h, nev + 1);
+  if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  ev_solve.push_back(nev);
+  nev += 2;
+  HIPCHK(h, hipEventRecord(e0, st));
+  HIPCHK(h, hipMemcpyAsync(sb.dpt, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(sb.drows + (size_t)i * d, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, launch_batch_corr(h->kernel, h->dX, N, d, h->dtheta, sb.dpt, 1, sb.dr, sb.dvr, st));  // (dvr: the distances, overwritten next)
+  HIPCHK(h, launch_gemm(0, 0, N, 1, N, 1.0, h->dV, h->ldr, sb.dr, N, 0.0, sb.dvr, N, st, 1));   // V r
+  HIPCHK(h, launch_gemm(1, 0, N, 1, N, 1.0, h->dV, h->ldr, sb.dvr, N, 0.0, sb.da, N, st, 2));   // a = V^T (V r) = R^-1 r
+  HIPCHK(h, launch_batch_corr(h->kernel, sb.drows, i + 1, d, h->dtheta, sb.dpt, 1, sb.dkk, sb.dkk + BOGP_MAX_BELIEVED, st));  // k(p, p_k), k <= i
+  double* ri = &bl.r[(size_t)i * N];
+  double* ai = &bl.a[(size_t)i * N];
+  HIPCHK(h, hipMemcpyAsync(ri, sb.dr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(ai, sb.da, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(hk.data(), sb.dkk, (size_t)(i + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipEventRecord(e1, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  double rw = 0.0;
+  for (int n = 0; n < N; ++n) rw += ri[n] * hw[n];
+  bl.u[i] = h->estimate_trend ? (rw - 1.0) / h->G : 0.0;
+  // row i of the recursion: kappa0(p_i, p_k) = k - r_i . a_k + u_i u_k, orthogonalised against the rows before
+  for (int k = 0; k <= i; ++k) {
+    const double* ak = &bl.a[(size_t)k * N];
+    double dot = 0.0;
+    for (int n = 0; n < N; ++n) dot += ri[n] * ak[n];
+    double b = hk[k] - dot + bl.u[i] * bl.u[k];
+    for (int l = 0; l < k; ++l) b -= bl.L[i][l] * bl.L[k][l];
+    if (k < i) {
+      bl.L[i][k] = bl.L[k][k] > 0.0 ? b / bl.L[k][k] : 0.0;
+    } else {
+      if (pivots) pivots[i] = b;
+      bl.L[i][i] = b > PIVOT_FLOOR ? std::sqrt(b) : 0.0;  // (NaN fails the comparison: guarded)
+    }
+  }
+  bl.slot[i] = -1;
+  bl.n = i + 1;
+  return BOGP_OK;
+}
+
+// the producer of one chunk for a believer pass (run_sweep's arguments for a constant-trend model)
+hipError_t believer_corr_chunk(bogp_handle* h, const Plan& pl, int64_t m0, int64_t Mc_eff) {
+  CorrArgs ca;
+  ca.Xs = h->dXs; ca.M = h->M; ca.m0 = m0; ca.Mc = pl.Mc; ca.d = h->d; ca.Np = h->Np; ca.nblk_per_split = 8;
+  ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
+  ca.rT = h->drT[0]; ca.mu_part = h->dmu_part[0]; ca.w_part = h->dw_part[0];
+  return launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), pl.S, h->stream);
+}
+
+// times of the solves and of the chunks' producer / k_believer launches, once everything is complete
+void believer_times(bogp_handle* h, const std::vector<size_t>& ev_solve, const std::vector<size_t>& ev_chunk) {
+  h->bel_corr_ms = h->bel_solve_ms = h->bel_pass_ms = 0;
+  for (size_t k : ev_solve) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, h->bel_ev[k], h->bel_ev[k + 1]);
+    h->bel_solve_ms += ms;
+  }
+  for (size_t k : ev_chunk) {
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, h->bel_ev[k], h->bel_ev[k + 1]);
+    (void)hipEventElapsedTime(&b, h->bel_ev[k + 1], h->bel_ev[k + 2]);
+    h->bel_corr_ms += a;
+    h->bel_pass_ms += b;
+  }
+}
+
 }  // namespace
 
 extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
@@ -77,7 +176,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   for (size_t i = 0; i < (size_t)n_pending * d; ++i)
     if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: pending entry %zu is not finite", i);
   if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: constant trend basis only (the committed basis has %d columns)", h->p);
-  if (h->n_t != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: one target only (the committed model has %d)", h->n_t);
+  if (h->n_t != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: one target only (the committed model has %d): EHVI batches are bogp_sweep_believer_ehvi", h->n_t);
   if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: a lift is set (bogp_lift_set): call bogp_lift_clear first");
   if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: runs on one rank (the communicator has %d)", h->comm_world);
   HIPCHK(h, hipSetDevice(h->device));
@@ -92,19 +191,9 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   if (rc) return rc;
   if ((rc = candidates_ready(h))) return rc;
 
-  // ---- geometry of the later passes (run_sweep's for p = 1: chunk bytes, slices of 8 x 32 training rows)
-  Plan pl;
-  {
-    size_t chunk_bytes = (size_t)1 << 30;
-    if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
-    const int64_t Mpad = ((M + 63) / 64) * 64;
-    int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Np * sizeof(double)) / 64) * 64;
-    pl.Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
-    pl.nchunk = (M + pl.Mc - 1) / pl.Mc;
-    pl.nblk_total = (M + 63) / 64 + pl.nchunk;
-    pl.S = (Np / 32 + 7) / 8;
-  }
-  const size_t small_n = (size_t)d + 3 * (size_t)N + 2 * BOGP_MAX_BELIEVED + (size_t)BOGP_MAX_BELIEVED * d;
+  // ---- geometry of the later passes
+  const Plan pl = make_plan(M, Np);
+  const size_t small_n = SolveBufs::doubles(d, N);
   if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M))) return rc;
   if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)2 * M))) return rc;
   if ((rc = ensure(h, &h->dbel_small, &h->bel_small_cap, small_n))) return rc;
@@ -117,12 +206,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)pl.nblk_total))) return rc;
   if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
   if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
-  double* dpt = h->dbel_small;          // d
-  double* dr = dpt + d;                 // N
-  double* dvr = dr + N;                 // N
-  double* da = dvr + N;                 // N
-  double* dkk = da + N;                 // 32 correlations of the point with the believed rows, 32 distances
-  double* drows = dkk + 2 * BOGP_MAX_BELIEVED;  // 32 x d believed rows
+  const SolveBufs sb(h->dbel_small, d, N);
   double* dacq_row = h->dbel_row;
   double* dmse_row = h->dbel_row + M;
 
@@ -155,54 +239,20 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   // sweep's array by the caller).  `row`: the candidate row a winner is (its variance becomes exactly 0), -1 for a pending point.
   auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
     const int i = bl.n;
-    hipEvent_t e0 = bel_event(h, nev), e1 = bel_event(h, nev + 1);
-    if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-    ev_solve.push_back(nev);
-    nev += 2;
-    HIPCHK(h, hipEventRecord(e0, st));
-    HIPCHK(h, hipMemcpyAsync(dpt, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(drows + (size_t)i * d, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, launch_batch_corr(h->kernel, h->dX, N, d, h->dtheta, dpt, 1, dr, dvr, st));  // (dvr: the distances, overwritten next)
-    HIPCHK(h, launch_gemm(0, 0, N, 1, N, 1.0, h->dV, h->ldr, dr, N, 0.0, dvr, N, st, 1));   // V r
-    HIPCHK(h, launch_gemm(1, 0, N, 1, N, 1.0, h->dV, h->ldr, dvr, N, 0.0, da, N, st, 2));   // a = V^T (V r) = R^-1 r
-    HIPCHK(h, launch_batch_corr(h->kernel, drows, i + 1, d, h->dtheta, dpt, 1, dkk, dkk + BOGP_MAX_BELIEVED, st));  // k(p, p_k), k <= i
-    double* ri = &bl.r[(size_t)i * N];
-    double* ai = &bl.a[(size_t)i * N];
-    HIPCHK(h, hipMemcpyAsync(ri, dr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(ai, da, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(hk.data(), dkk, (size_t)(i + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipEventRecord(e1, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    double rg = 0.0, rw = 0.0;
-    for (int n = 0; n < N; ++n) {
-      rg += ri[n] * hgamma[n];
-      rw += ri[n] * hw[n];
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots, nev, ev_solve)) return rs;
+    if (is_pending) {
+      const double* ri = &bl.r[(size_t)i * N];
+      double rg = 0.0;
+      for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[n];
+      believe_mean(h->beta + rg);
     }
-    if (is_pending) believe_mean(h->beta + rg);
-    bl.u[i] = h->estimate_trend ? (rw - 1.0) / h->G : 0.0;
-    // row i of the recursion: kappa0(p_i, p_k) = k - r_i . a_k + u_i u_k, orthogonalised against the rows before
-    for (int k = 0; k <= i; ++k) {
-      const double* ak = &bl.a[(size_t)k * N];
-      double dot = 0.0;
-      for (int n = 0; n < N; ++n) dot += ri[n] * ak[n];
-      double b = hk[k] - dot + bl.u[i] * bl.u[k];
-      for (int l = 0; l < k; ++l) b -= bl.L[i][l] * bl.L[k][l];
-      if (k < i) {
-        bl.L[i][k] = bl.L[k][k] > 0.0 ? b / bl.L[k][k] : 0.0;
-      } else {
-        if (pivots) pivots[i] = b;
-        bl.L[i][i] = b > PIVOT_FLOOR ? std::sqrt(b) : 0.0;  // (NaN fails the comparison: guarded)
-      }
-    }
-    bl.slot[i] = -1;
-    bl.n = i + 1;
     const bool active = bl.L[i][i] > 0.0;
     if (!pass || (!active && step < 0)) return BOGP_OK;
     const bool store = active && (bl.n < Btot - 1);  // a later pass will read this column
     if (store) bl.slot[i] = slots++;
     BelieverArgs ba;
     memset(&ba, 0, sizeof(ba));
-    ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = da;
+    ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
     ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
     ba.update = active ? 1 : 0;
     ba.self_row = row;
@@ -230,11 +280,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
       nev += 3;
       HIPCHK(h, hipEventRecord(c0, st));
       if (active && !chunk_resident) {
-        CorrArgs ca;
-        ca.Xs = h->dXs; ca.M = M; ca.m0 = m0; ca.Mc = pl.Mc; ca.d = d; ca.Np = Np; ca.nblk_per_split = 8;
-        ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
-        ca.rT = h->drT[0]; ca.mu_part = h->dmu_part[0]; ca.w_part = h->dw_part[0];
-        HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), pl.S, st));
+        HIPCHK(h, believer_corr_chunk(h, pl, m0, Mc_eff));
         chunk_resident = pl.nchunk == 1;
       }
       HIPCHK(h, hipEventRecord(c1, st));
@@ -278,19 +324,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
 
   // times of the solves and of the passes (everything is complete: the last step was read back)
   HIPCHK(h, hipStreamSynchronize(st));
-  h->bel_corr_ms = h->bel_solve_ms = h->bel_pass_ms = 0;
-  for (size_t k : ev_solve) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, h->bel_ev[k], h->bel_ev[k + 1]);
-    h->bel_solve_ms += ms;
-  }
-  for (size_t k : ev_chunk) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, h->bel_ev[k], h->bel_ev[k + 1]);
-    (void)hipEventElapsedTime(&b, h->bel_ev[k + 1], h->bel_ev[k + 2]);
-    h->bel_corr_ms += a;
-    h->bel_pass_ms += b;
-  }
+  believer_times(h, ev_solve, ev_chunk);
   return BOGP_OK;
 }
 
@@ -299,6 +333,361 @@ extern "C" int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve
   if (corr_ms) *corr_ms = h->bel_corr_ms;
   if (solve_ms) *solve_ms = h->bel_solve_ms;
   if (believer_ms) *believer_ms = h->bel_pass_ms;
+  if (n_passes) *n_passes = h->bel_passes;
+  return BOGP_OK;
+}
+
+// ---- believer batches for EHVI: bogp_sweep_believer_ehvi ---------------------------------------------------------------------------
+// The m targets share the bracket of gpr.py:502-510, so ONE downdate in correlation units serves them all: k_believer forms c(x) per
+// chunk exactly as above (with a unit variance and a scratch s: its own s output is not used), k_believer_ehvi
+// (kernels_believer_ehvi.hip) takes sigma2_k c^2 off every target's MSE and evaluates EHVI.  The believed mean mu(p) is an m-vector
+// that joins the front, so the cells are rebuilt on the host between the steps (bogp_ehvi_grid_cells' decomposition).
+namespace {
+
+// pareto.pareto_front: the rows no other row dominates (of identical rows the first) that lie strictly above r in every objective
+std::vector<double> pareto_front_rows(int m, int64_t n, const double* Y, const double* r) {
+  std::vector<char> keep((size_t)n, 1);
+  for (int64_t i = 0; i < n; ++i) {
+    const double* yi = Y + (size_t)i * m;
+    for (int64_t j = 0; j < n && keep[i]; ++j) {
+      const double* yj = Y + (size_t)j * m;
+      bool ge = true, gt = false;
+      for (int k = 0; k < m; ++k) {
+        ge = ge && yj[k] >= yi[k];
+        gt = gt || yj[k] > yi[k];
+      }
+      if (ge && gt) keep[i] = 0;
+    }
+    for (int64_t j = 0; j < i && keep[i]; ++j)
+      if (keep[j] && std::equal(yi, yi + m, Y + (size_t)j * m)) keep[i] = 0;
+  }
+  std::vector<double> P;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!keep[i]) continue;
+    const double* yi = Y + (size_t)i * m;
+    bool above = true;
+    for (int k = 0; k < m; ++k) above = above && yi[k] > r[k];
+    if (above) P.insert(P.end(), yi, yi + m);
+  }
+  return P;
+}
+
+// pareto.hypercell_bounds on a front P (np rows): the grid's edges along the first m - 1 axes and the cell count, -1 past `limit`
+int64_t grid_edges(int m, const std::vector<double>& P, const double* r, int64_t limit, std::vector<std::vector<double>>& edges) {
+  const size_t np = P.size() / m;
+  edges.assign(m - 1, {});
+  int64_t count = 1;
+  for (int k = 0; k < m - 1; ++k) {
+    std::vector<double> v(np);
+    for (size_t i = 0; i < np; ++i) v[i] = P[i * m + k];
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    edges[k].push_back(r[k]);
+    edges[k].insert(edges[k].end(), v.begin(), v.end());
+    edges[k].push_back(INFINITY);
+    if (count >= 0) {
+      count *= (int64_t)v.size() + 1;  // (both factors at most 2^31 here: no wrap-around before the check)
+      if (count > limit) count = -1;
+    }
+  }
+  return count;
+}
+
+// the exact count of a grid past the limit, for the message (saturates at INT64_MAX)
+long long grid_count_saturated(const std::vector<std::vector<double>>& edges) {
+  long long c = 1;
+  for (const auto& e : edges) {
+    const long long f = (long long)e.size() - 1;
+    c = c > INT64_MAX / f ? INT64_MAX : c * f;
+  }
+  return c;
+}
+
+// the cells in itertools.product order (last grid axis fastest): lower / upper are count x m
+void grid_fill(int m, const std::vector<double>& P, const double* r, const std::vector<std::vector<double>>& edges, int64_t count,
+               double* lower, double* upper) {
+  const size_t np = P.size() / m;
+  std::vector<size_t> ix(m - 1, 0);
+  for (int64_t c = 0; c < count; ++c) {
+    double* lo = lower + (size_t)c * m;
+    double* hi = upper + (size_t)c * m;
+    for (int k = 0; k < m - 1; ++k) {
+      lo[k] = edges[k][ix[k]];
+      hi[k] = edges[k][ix[k] + 1];
+    }
+    double last = r[m - 1];
+    for (size_t i = 0; i < np; ++i) {  // the front points that cover the whole column: the largest last coordinate (every one is > r)
+      bool cover = true;
+      for (int k = 0; k < m - 1; ++k) cover = cover && P[i * m + k] >= hi[k];
+      if (cover && P[i * m + m - 1] > last) last = P[i * m + m - 1];
+    }
+    lo[m - 1] = last;
+    hi[m - 1] = INFINITY;
+    for (int k = m - 2; k >= 0; --k) {
+      if (++ix[k] + 1 < edges[k].size()) break;
+      ix[k] = 0;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int bogp_ehvi_grid_cells(int m, int n, const double* Y, const double* ref_point, double* lower, double* upper, int64_t cap) {
+  if (m < 2 || m > BOGP_MAX_TARGETS || n < 0 || !ref_point || (n > 0 && !Y) || (!lower != !upper)) return BOGP_ERR_INVALID;
+  for (int k = 0; k < m; ++k)
+    if (!std::isfinite(ref_point[k])) return BOGP_ERR_INVALID;
+  for (size_t i = 0; i < (size_t)n * m; ++i)
+    if (!std::isfinite(Y[i])) return BOGP_ERR_INVALID;
+  const std::vector<double> P = pareto_front_rows(m, n, Y, ref_point);
+  std::vector<std::vector<double>> edges;
+  const int64_t count = grid_edges(m, P, ref_point, BOGP_MAX_EHVI_CELLS, edges);
+  if (count < 0) return BOGP_ERR_INVALID;
+  if (!lower) return (int)count;
+  if (count > cap) return BOGP_ERR_INVALID;  // (checked before anything is written)
+  grid_fill(m, P, ref_point, edges, count, lower, upper);
+  return (int)count;
+}
+
+extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const double* ref_point, const double* front, int n_front,
+                                        int believe_front, const double* pending, int n_pending, double* best_val, int64_t* best_idx,
+                                        double* best_x, double* best_mu, double* pivots, int* n_cells, double* ehvi_out, double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_believer_ehvi";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior correlation to condition on", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (m != h->n_t) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d but the committed model has %d target(s)", who, m, h->n_t);
+  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d outside [2, %d]", who, m, BOGP_MAX_TARGETS);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  if (q < 1 || n_pending < 0 || q + n_pending > BOGP_MAX_BELIEVED)
+    FAIL(h, BOGP_ERR_INVALID, "%s: q = %d, n_pending = %d: q >= 1 and q + n_pending <= %d", who, q, n_pending, BOGP_MAX_BELIEVED);
+  if (q > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d proposals from %lld candidates (every step takes a row no step before it took)", who, q, (long long)h->M);
+  if (!ref_point || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point, best_val and best_idx must be non-null", who);
+  if (n_front < 0 || (n_front > 0 && !front)) FAIL(h, BOGP_ERR_INVALID, "%s: n_front = %d and front is %s", who, n_front, front ? "given" : "null");
+  if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
+  const int d = h->d, N = h->N, Np = h->Np;
+  for (int k = 0; k < m; ++k)
+    if (!std::isfinite(ref_point[k])) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point entry %d is not finite", who, k);
+  for (size_t i = 0; i < (size_t)n_front * m; ++i)
+    if (!std::isfinite(front[i])) FAIL(h, BOGP_ERR_INVALID, "%s: front entry %zu is not finite", who, i);
+  for (size_t i = 0; i < (size_t)n_pending * d; ++i)
+    if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+  const int64_t M = h->M;
+  const int P = n_pending, Btot = P + q;
+
+  // ---- the front and its cells (host): F_0 now, one believed mean more per step when believe_front is set
+  std::vector<double> F = pareto_front_rows(m, n_front, front, ref_point);
+  std::vector<std::vector<double>> edges;
+  std::vector<double> cells;  // [lower C x m | upper C x m] of the step evaluated next
+  int C = 0;
+  auto build_cells = [&](int step) -> int {
+    const int64_t count = grid_edges(m, F, ref_point, BOGP_MAX_EHVI_CELLS, edges);
+    if (count < 0)
+      FAIL(h, BOGP_ERR_INVALID, "%s: step %d: the front of %zu points in %d objectives gives %lld cells (more than %d)", who, step,
+           F.size() / m, m, grid_count_saturated(edges), BOGP_MAX_EHVI_CELLS);
+    C = (int)count;
+    cells.resize(2 * (size_t)C * m);
+    grid_fill(m, F, ref_point, edges, count, cells.data(), cells.data() + (size_t)C * m);
+    return BOGP_OK;
+  };
+  auto join_front = [&](const double* mu) {  // F <- pareto_front(F u {mu})
+    if (!believe_front) return;
+    F.insert(F.end(), mu, mu + m);
+    F = pareto_front_rows(m, (int64_t)(F.size() / m), F.data(), ref_point);
+  };
+  int rc;
+  if ((rc = build_cells(0))) return rc;  // before any device work (with pending points: the cells of F_0, which step 0 extends)
+
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  auto upload_cells = [&]() -> int {  // in stream order, before the pass that reads them; `cells` stays as it is until that pass is complete
+    const size_t nb = (size_t)C * m;
+    int e;
+    if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, std::max<size_t>(2 * nb, 2)))) return e;
+    if (nb == 0) return BOGP_OK;
+    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, cells.data(), nb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, cells.data() + nb, nb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return BOGP_OK;
+  };
+
+  // ---- pass 0: bogp_sweep_ehvi's sweep; with pending points over no cells, for the moments only
+  const int C0 = P == 0 ? C : 0;
+  if (P > 0) C = 0;
+  if ((rc = upload_cells())) return rc;
+  EhviArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.gamma = h->dgamma_base; ea.ld_gamma = Np; ea.N = N; ea.m = m; ea.C = C0;
+  for (int t = 0; t < m; ++t) ea.sigma2[t] = h->sigma2_t[t];
+  ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + (size_t)C0 * m;
+  invalidate_sweep_results(h);  // dbest_* are overwritten
+  const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
+  if ((rc = run_sweep(h, true, 1, &one_id, nullptr, 0.0, 0, true, true, true, &ea))) return rc;
+  if ((rc = candidates_ready(h))) return rc;
+  if (P == 0 && n_cells) n_cells[0] = C0;
+
+  // ---- the later passes
+  const Plan pl = make_plan(M, Np);
+  const int64_t nblk = (M + 255) / 256;
+  if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M * m))) return rc;
+  if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)(2 + m) * M))) return rc;
+  if ((rc = ensure(h, &h->dbel_small, &h->bel_small_cap, SolveBufs::doubles(d, N)))) return rc;
+  if (Btot > 1)
+    if ((rc = ensure(h, &h->dbel_C, &h->bel_C_cap, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_ehvi
+  if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * pl.Mc))) return rc;
+  if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)nblk))) return rc;
+  if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)nblk))) return rc;
+  const SolveBufs sb(h->dbel_small, d, N);
+  double* dehvi_row = h->dbel_row;
+  double* dscratch = h->dbel_row + M;      // k_believer's own s, in unit variance: not used
+  double* dmse_row = h->dbel_row + 2 * M;  // [M][m]
+
+  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(h, hipMemsetAsync(dscratch, 0, (size_t)M * sizeof(double), st));
+  std::vector<double> hgamma((size_t)m * Np), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED), hmu((size_t)m);
+  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base, (size_t)m * Np * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+
+  Believed bl;
+  bl.r.resize((size_t)Btot * N);
+  bl.a.resize((size_t)Btot * N);
+  bl.u.resize(Btot);
+  memset(bl.L, 0, sizeof(bl.L));
+  int slots = 0;
+  bool chunk_resident = false;
+  size_t nev = 0;
+  std::vector<size_t> ev_solve, ev_chunk, ev_ehvi;  // event indices: (begin, end) per solve; (begin, producer end, end) per chunk; (begin, end) per k_believer_ehvi
+  h->bel_passes = 0;
+
+  // One believed point, as in bogp_sweep_believer.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it joins the front (a
+  // winner's mean is read from the sweep's array by the caller, before this).  A step's cells are those of the front as it stands here.
+  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
+    const int i = bl.n;
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots, nev, ev_solve)) return rs;
+    if (is_pending) {
+      const double* ri = &bl.r[(size_t)i * N];
+      for (int t = 0; t < m; ++t) {
+        double rg = 0.0;
+        for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[(size_t)t * Np + n];
+        hmu[t] = h->beta + rg;
+      }
+      join_front(hmu.data());
+    }
+    const bool active = bl.L[i][i] > 0.0;
+    if (!pass || (!active && step < 0)) return BOGP_OK;
+    if (step >= 0) {
+      if (int rs = build_cells(step)) return rs;
+      if (int rs = upload_cells()) return rs;
+      if (n_cells) n_cells[step] = C;
+    }
+    if (active) {  // c(x) of this point for every candidate, chunk by chunk
+      bl.slot[i] = slots++;
+      BelieverArgs ba;
+      memset(&ba, 0, sizeof(ba));
+      ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
+      ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
+      ba.update = 1;
+      ba.self_row = -1;
+      ba.u_p = bl.u[i]; ba.inv_root = 1.0 / bl.L[i][i]; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
+      for (int k = 0; k < i; ++k)
+        if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
+          ba.prev_slot[ba.nprev] = bl.slot[k];
+          ba.prev_c[ba.nprev] = bl.L[i][k];
+          ++ba.nprev;
+        }
+      ba.C = h->dbel_C; ba.c_out = h->dbel_C + (size_t)bl.slot[i] * M; ba.s = dscratch; ba.sigma2 = 1.0;
+      ba.eval = 0;
+      for (int64_t c = 0; c < pl.nchunk; ++c) {
+        const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
+        hipEvent_t c0 = bel_event(h, nev), c1 = bel_event(h, nev + 1), c2 = bel_event(h, nev + 2);
+        if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+        ev_chunk.push_back(nev);
+        nev += 3;
+        HIPCHK(h, hipEventRecord(c0, st));
+        if (!chunk_resident) {
+          HIPCHK(h, believer_corr_chunk(h, pl, m0, Mc_eff));
+          chunk_resident = pl.nchunk == 1;
+        }
+        HIPCHK(h, hipEventRecord(c1, st));
+        ba.m0 = m0; ba.mcount = mcount;
+        HIPCHK(h, launch_believer(h->kernel, ba, st));
+        HIPCHK(h, hipEventRecord(c2, st));
+      }
+    }
+    BelieverEhviArgs be;
+    memset(&be, 0, sizeof(be));
+    be.M = M; be.m = m; be.update = active ? 1 : 0; be.c = active ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr;
+    be.self_row = row; be.s = h->dbel_s;
+    for (int t = 0; t < m; ++t) be.sigma2[t] = h->sigma2_t[t];
+    be.eval = step >= 0 ? 1 : 0;
+    if (step >= 0) {
+      be.n_taken = step;  // the winners of steps 0 .. step - 1
+      for (int k = 0; k < step; ++k) be.taken[k] = best_idx[k];
+      be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C;
+    }
+    be.mu = h->dmu_out; be.ehvi_out = dehvi_row; be.mse_out = dmse_row; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
+    hipEvent_t b0 = bel_event(h, nev), b1 = bel_event(h, nev + 1);
+    if (!b0 || !b1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+    ev_ehvi.push_back(nev);
+    nev += 2;
+    HIPCHK(h, hipEventRecord(b0, st));
+    HIPCHK(h, launch_believer_ehvi(be, st));
+    HIPCHK(h, hipEventRecord(b1, st));
+    ++h->bel_passes;
+    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
+    return BOGP_OK;
+  };
+
+  for (int i = 0; i < P; ++i)
+    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
+
+  for (int j = 0; j < q; ++j) {
+    // the winner of step j is in dbest_*[0]; its EHVI values / MSE in the sweep's own arrays (step 0 without pending points) or the row buffers
+    const bool from_sweep = j == 0 && P == 0;
+    int64_t idx = 0;
+    HIPCHK(h, hipMemcpyAsync(&best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (ehvi_out) HIPCHK(h, hipMemcpyAsync(ehvi_out + (size_t)j * M, from_sweep ? h->dacq_out : dehvi_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out + (size_t)j * M * m, from_sweep ? h->dmse_out : dmse_row, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    best_idx[j] = idx;
+    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "%s: step %d returned row %lld outside [0, %lld)", who, j, (long long)idx, (long long)M);
+    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hmu.data(), h->dmu_out + (size_t)idx * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (best_x) memcpy(best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
+    if (best_mu) memcpy(best_mu + (size_t)j * m, hmu.data(), (size_t)m * sizeof(double));
+    if (j == q - 1) {
+      if (pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
+      break;
+    }
+    join_front(hmu.data());
+    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
+  }
+
+  HIPCHK(h, hipStreamSynchronize(st));
+  believer_times(h, ev_solve, ev_chunk);
+  h->bel_ehvi_ms = 0;
+  for (size_t k : ev_ehvi) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, h->bel_ev[k], h->bel_ev[k + 1]);
+    h->bel_ehvi_ms += ms;
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* ehvi_ms, int* n_passes) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (corr_ms) *corr_ms = h->bel_corr_ms;
+  if (solve_ms) *solve_ms = h->bel_solve_ms;
+  if (update_ms) *update_ms = h->bel_pass_ms;
+  if (ehvi_ms) *ehvi_ms = h->bel_ehvi_ms;
   if (n_passes) *n_passes = h->bel_passes;
   return BOGP_OK;
 }

@@ -147,6 +147,8 @@ struct bogp_handle {
   std::vector<hipEvent_t> bel_ev;
   double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
+  // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
+  double bel_ehvi_ms = 0;  // k_believer_ehvi of the last bogp_sweep_believer_ehvi
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

@@ -138,6 +138,31 @@ struct BelieverArgs {
 };
 hipError_t launch_believer(int kernel, const BelieverArgs& a, hipStream_t st);
 
+// the m-target half of a believer pass (kernels_believer_ehvi.hip), ONE launch over all M rows behind the chunk loop in which
+// k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a step -- EHVI over that step's
+// cells on (mu, max(0, MSE)) with one argmax record per 256 rows
+struct BelieverEhviArgs {
+  int64_t M;
+  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
+  int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
+  const double* c;        // [M] c(x) of the believed point
+  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
+  double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
+  double sigma2[8];       // per target
+  int eval;               // evaluate EHVI behind the update
+  int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
+  int64_t taken[32];
+  const double* mu;       // [M][m]
+  const double* lower;    // [C][m] cell bounds of the step's front (device)
+  const double* upper;    // [C][m] (+inf allowed)
+  int C;
+  double* ehvi_out;       // [M]
+  double* mse_out;        // [M][m] max(0, MSE): what the step saw
+  double* blk_val;        // [ceil(M / 256)]
+  int64_t* blk_idx;
+};
+hipError_t launch_believer_ehvi(const BelieverEhviArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

@@ -142,6 +142,24 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
     return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
 
 
+def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=None):
+    """`MOBO._batch_arg_max_acquisition` under `install(batch_strategy="believer")`: the Kriging believer the reference's MOBO names
+    and leaves open (mobo.py:168-178; the inherited BaseBO method raises NotImplementedError, base.py:496-497).  Taken for a device
+    GP, an inner optimiser of the sweep family, a continuous space, nothing fixed and no constraints: `optim.ehvi_believer_batch` on
+    the criterion `mobo_create_acquisition` builds.  Everything else -- the default `install()` above all -- calls the inherited
+    method, which raises as it does without this package."""
+    inherited = super(_ORIGINAL["mobo_cls"], self)._batch_arg_max_acquisition
+    optimizer, budget = _effective(getattr(self, "_optimizer", None), None)
+    kw = getattr(getattr(self, "_argmax_restart", None), "keywords", None) or {}
+    if (_BATCH.get("strategy") != "believer" or fixed or optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None))
+            or not optim.is_continuous(kw.get("search_space")) or kw.get("h") is not None or kw.get("g") is not None):  # fmt: skip
+        return inherited(n_point, return_dx, fixed)
+    criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
+    xs, fs = optim.ehvi_believer_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
+                                       design=optim.DEVICE_DESIGNS.get(optimizer))  # fmt: skip
+    return tuple(xs), tuple(fs)
+
+
 def forest_create_acquisition(self, fun=None, par=None, return_dx=False, fixed=None):
     """Drop-in body for `BaseBO._create_acquisition` (base.py:482-494): a `RandomForest` model (this package's or the reference's)
     under "sweep" / "sweep-device" gets this package's criterion, which evaluates the packed forest on the device, wrapped exactly as
@@ -368,7 +386,9 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `batch_strategy` = "topk" | "believer": how the fused `ParallelBO` step keeps its q points apart.  "topk" (default): each
     criterion falls back through its top-k; "believer": `optim.believer_batch` -- criterion j sees the variance conditioned on
     the winners before it (a step with fixed variables or constraints, which the believer does not serve, keeps "topk").  The q
-    parameters are drawn with the reference's sampler in the reference's order either way."""
+    parameters are drawn with the reference's sampler in the reference's order either way.  Under "believer" the reference's
+    `MOBO(n_point=q)` proposes q points as well (`optim.ehvi_believer_batch`: EHVI on the variance conditioned on the winners before
+    and on the front their believed means extend); under "topk" its `ask(q)` raises NotImplementedError as in the reference."""
     if batch_strategy not in ("topk", "believer"):
         raise ValueError("batch_strategy must be 'topk' or 'believer', not %r" % (batch_strategy,))
     _BATCH.clear()
@@ -412,6 +432,9 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     if rmobo is not None and hasattr(rmobo, "MOBO"):
         _ORIGINAL.update(mobo_cls=rmobo.MOBO, mobo=rmobo.MOBO.__dict__["_create_acquisition"], partial_argument=rmobo.partial_argument)
         rmobo.MOBO._create_acquisition = mobo_create_acquisition
+        if "_batch_arg_max_acquisition" not in rmobo.MOBO.__dict__:  # inherited from BaseBO (raises): given, not replaced
+            rmobo.MOBO._batch_arg_max_acquisition = mobo_batch_arg_max_acquisition
+            _ORIGINAL["mobo_batch"] = True
     ns = _AcquisitionNamespace(racq)
     for m in holders:
         m.AcquisitionFunction = ns
@@ -437,6 +460,8 @@ def uninstall():
     ropt.ParallelBO._batch_arg_max_acquisition = _ORIGINAL["batch"]
     if _ORIGINAL["mobo_cls"] is not None:
         _ORIGINAL["mobo_cls"]._create_acquisition = _ORIGINAL["mobo"]
+        if _ORIGINAL.get("mobo_batch"):
+            del _ORIGINAL["mobo_cls"]._batch_arg_max_acquisition  # inherited again
     if _ORIGINAL["surrogate"]:
         pkg.GaussianProcess, rsur.GaussianProcess = _ORIGINAL["gp"]
         if _ORIGINAL.get("ext") is not None:

@@ -448,7 +448,8 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     if _forest.is_forest_model(model):
         raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
     if any(is_ehvi(c) for c in criteria):
-        raise NotImplementedError("EHVI has no believer batches: the front and its cells change with each believed point")
+        raise NotImplementedError("EHVI has no believer batches: the front and its cells change with each believed point "
+                                  "(`ehvi_believer_batch` rebuilds them between the steps)")
     if lift is not None:
         raise NotImplementedError("a lift (PCA-BO) has no believer batches")
     if masks is not None and np.any(masks):
@@ -478,6 +479,56 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
     out = eng.sweep_believer([(c.acq_id, c.acq_par()) for c in criteria], plugin, c0.minimize, pending=pend,
                              believe_plugin=believe_plugin)
+    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+
+
+def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
+                        seed: Optional[int] = None, pending=None, believe_front: bool = True, lift=None, masks=None, values=None,
+                        h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):
+    """A q-point proposal for a multi-objective run by the Kriging believer under EHVI (`bogp_sweep_believer_ehvi`): what the
+    reference's `MOBO` names and leaves open (mobo.py:168-178).  ONE posterior pass, then one streaming pass over the
+    candidates per proposed point: step j maximises EHVI on the m posterior means and on the variances conditioned on `pending`
+    (rows submitted but not yet evaluated, (n, d)) and on the winners of the steps before it, over the cells of the front --
+    which, with `believe_front`, every believed mean joins before the next step (without it only the variance is conditioned).
+    `criterion`: a `bogp.EHVI` built with `Y=` or `partitioning=`, so that it carries its front (`pareto_Y`); one built from
+    `cells=` has no front to extend and is refused (ValueError).  Candidates as in `believer_batch`.  Returns (xopt: tuple of q
+    lists, fopt: tuple of q floats) in `believer_batch`'s format.
+    Refused (NotImplementedError): a forest model, a lift, fixed variables, constraints, more than one rank."""
+    if not is_ehvi(criterion):
+        raise TypeError("ehvi_believer_batch takes a bogp.EHVI criterion (the single-objective criteria go to believer_batch)")
+    model = criterion.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no believer batches")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no believer batches")
+    if h is not None or g is not None:
+        raise NotImplementedError("constraints have no believer batches")
+    if getattr(criterion, "pareto_Y", None) is None:
+        raise ValueError("an EHVI built from cells= has no front to extend with the believed means: build it with Y= or partitioning=")
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    q = int(q)
+    if q < 1:
+        raise ValueError("q = %d: the believer proposes at least one point" % q)
+    if q + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
+        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
+    if design is not None:
+        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
+    out = eng.sweep_believer_ehvi(np.asarray(criterion.pareto_Y, dtype=float).reshape(-1, criterion.n_obj), criterion.ref_point, q,
+                                  pending=pend, believe_front=believe_front)
     return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
 
 

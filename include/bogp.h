@@ -330,6 +330,45 @@ int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, const double* 
                         double* best_x, double* pivots, double* acq_out, double* mse_out);
 int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* believer_ms, int* n_passes);
 
+/* ---- sweep: Kriging-believer batches for EHVI -------------------------------------------------------------
+ * q proposals per call for a multi-objective run -- what the reference names and leaves open: `class MOBO: """EHVI with
+ * Kriging believer"""` stands over `# TODO: implement the Kriging believer strategy` (mobo.py:168-178), and MOBO(n_point > 1)
+ * .ask() ends in BaseBO._batch_arg_max_acquisition, which raises NotImplementedError (base.py:496-497).  The model is
+ * bogp_sweep_ehvi's: m = 2 .. BOGP_MAX_TARGETS targets, constant basis, targets maximised as given.  With several targets the
+ * bracket 1 - |L^-1 r|^2 + u^2 is shared, MSE_k = sigma2_k bracket (gpr.py:502-510), so kappa0, b_i, pivot_i and c_i are those of
+ * bogp_sweep_believer above (pivot floor 1e-12 -> c_i = 0; the candidate row that is a winner gets variance exactly 0) and step j
+ * sees the means unchanged and  MSE_{k,j}(x) = max(0, MSE_{k,0}(x) - sigma2_k sum_i c_i(x)^2).
+ * The front: F_0 = the non-dominated rows of `front` strictly above ref_point in every objective (of identical rows the first);
+ * with believe_front = 1 every believed mean mu(p) (an m-vector: beta + r(p).gamma_k for a pending point, the sweep's own mean
+ * for a winner) joins it, F_B = front(F_{B-1} u {mu(p_B)}); with 0 the front stays F_0 and only the variance is conditioned.
+ * The cells of step j are bogp_ehvi_grid_cells of the front as it stands; EHVI is bogp_sweep_ehvi's (sd = sqrt(max(MSE, 1e-9))).
+ * Step j takes the argmax by bogp_sweep's rule over the rows that are not winners yet; the q winners are q distinct rows.
+ * Without pending points step 0 IS bogp_sweep_ehvi called with bogp_ehvi_grid_cells' cells, bit for bit.
+ *   front        n_front x m HOST rows (objective vectors seen so far), NULL for n_front = 0: one cell [ref_point, +inf)
+ *   pending      n_pending x d HOST rows, NULL for n_pending = 0;  1 <= q <= M, q + n_pending <= BOGP_MAX_BELIEVED
+ *   best_val, best_idx (q): each step's winner.  Optional HOST buffers (NULL to skip): best_x (q x d), best_mu (q x m: the
+ *   believed means), pivots (n_pending + q), n_cells (q: the cells step j used), ehvi_out (q x M), mse_out (q x M x m).
+ * Per believed point: the solve of bogp_sweep_believer, one streaming pass (producer + k_believer for c(x), per chunk) and one
+ * launch of k_believer_ehvi over all rows; the N^2 contraction runs once, in pass 0.
+ * BOGP_ERR_INVALID: no committed model, no candidates, m != n_targets, m outside [2, BOGP_MAX_TARGETS], q < 1, q > M, the limit
+ * exceeded, a null required array, a non-finite entry, more than BOGP_MAX_EHVI_CELLS cells at any step (the message names the
+ * step and the count; step 0's count is checked before any device work).  BOGP_ERR_UNSUPPORTED: a polynomial trend basis, a
+ * lift, a forest handle, a communicator of more than one rank.  The handle's model, candidates and later sweeps are unaffected.
+ * `believer_ehvi_last`: of the last call, the time of the producer launches, of the solves, of k_believer and of
+ * k_believer_ehvi in ms, and the candidate passes behind pass 0; any pointer may be NULL.
+ *
+ * `ehvi_grid_cells` (host only: no handle, no device call): the grid decomposition of the region above ref_point that the front
+ * of Y (n x m) does not dominate -- along each of the first m - 1 axes the edges are ref_k, the distinct front coordinates and
+ * +inf; cells in row-major order of the grid (last grid axis fastest); the last lower bound is the largest last coordinate of
+ * the front points covering the column, else ref_m; the last upper bound +inf.  Only input values are selected, none computed.
+ * Returns the cell count, also with lower == upper == NULL (count only; `cap` is then not looked at), or BOGP_ERR_INVALID: m
+ * outside [2, BOGP_MAX_TARGETS], a non-finite input, a count above `cap` (rows of lower / upper) or BOGP_MAX_EHVI_CELLS.     */
+int bogp_ehvi_grid_cells(int m, int n, const double* Y, const double* ref_point, double* lower, double* upper, int64_t cap);
+int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const double* ref_point, const double* front, int n_front,
+                             int believe_front, const double* pending, int n_pending, double* best_val, int64_t* best_idx,
+                             double* best_x, double* best_mu, double* pivots, int* n_cells, double* ehvi_out, double* mse_out);
+int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* ehvi_ms, int* n_passes);
+
 /* ---- sweep in a reduced space: box-penalised criteria under a linear lift ---------------------------
  * Replaces PCABO's inner maximisation (extension.py:113-133): the criterion is maximised over a box of the REDUCED
  * space (r = the committed model's d, _compute_bounds :113-119) through penalized_acquisition (:62-86), which maps a
