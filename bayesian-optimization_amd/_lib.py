@@ -107,6 +107,10 @@ SIGNATURES = {
     "bogp_reduce_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _lp, _dp]),
     "bogp_merge_topk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _lp, _dp]),
     "bogp_last_timing": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_set_prune": (C.c_int, [C.c_void_p, C.c_int]),
+    "bogp_last_contracted_rows": (C.c_int, [C.c_void_p, _lp]),
+    "bogp_acq_upper_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
     "bogp_flops_per_candidate": (C.c_double, [C.c_void_p]),
     "bogp_nll_path": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bogp_chol_wide_panels": (C.c_int, [C.c_int, _ip, C.c_int]),
@@ -1024,6 +1028,17 @@ class Engine:
         cast = lambda x: C.cast(C.byref(x), _dp)  # noqa: E731
         self._check(self._lib.bogp_last_timing(self._h, cast(a), cast(b), cast(c), C.cast(C.byref(n), _ip)))
         return dict(corr_ms=a.value, contract_ms=b.value, acquisition_ms=c.value, n_chunks=n.value)
+
+    def set_prune(self, on: bool = True):
+        """Pruned sweep on / off for this engine (default on): sweep() without return_values skips the variance contraction of
+        candidates that cannot win; winners and values are unchanged."""
+        self._check(self._lib.bogp_set_prune(self._h, int(bool(on))))
+
+    def last_contracted_rows(self) -> int:
+        """Candidates that went through the variance contraction in the last predict() / sweep() (waits for a queued sweep)."""
+        n = C.c_int64()
+        self._check(self._lib.bogp_last_contracted_rows(self._h, C.cast(C.byref(n), _lp)))
+        return int(n.value)
 
     def selftest_gemm(self, A, B, C_in=None, ta=False, tb=False, alpha=1.0, beta=0.0, tri=0, split=True):
         """alpha op(A) op(B) + beta C through k_gemm64 (kernels_gemm.hip); A, B, C_in Fortran-ordered 2-D float64 arrays."""

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bogp.h"
+#include "bogp_device.h"
 #include "bogp_handle.h"
 #include "bogp_internal.h"
 #include "bogp_fit.h"
@@ -332,6 +333,17 @@ static void collect_timing(bogp_handle* h) {
     (void)hipEventElapsedTime(&b2, ev[2], ev[3]);
     (void)hipEventElapsedTime(&c2, ev[3], ev[4]);
     h->t_corr_ms += a; h->t_contract_ms += b2; h->t_acq_ms += c2;
+    if (h->timing_prune) {  // bound, scan, compaction and gather of the chunk (and, in chunk 0, the pilot: split below)
+      float g = 0;
+      (void)hipEventElapsedTime(&g, ev[1], ev[2]);
+      h->t_acq_ms += g;
+    }
+  }
+  if (h->timing_prune) {  // the pilot's contraction ran between chunk 0's events [1] and [2]
+    float pc = 0;
+    hipEvent_t* evp = &h->ev[(size_t)(h->n_chunks * EPC + 1)];
+    (void)hipEventElapsedTime(&pc, evp[0], evp[1]);
+    h->t_contract_ms += pc; h->t_acq_ms -= pc;
   }
 }
 
@@ -424,6 +436,8 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
     h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
     h->n_chunks = 0;
     h->timing_pending = false;
+    h->prune_used = false;
+    h->contracted_rows = need_var ? M : 0;
     return BOGP_OK;
   }
 
@@ -473,6 +487,9 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
     h->n_chunks = 1;
     h->timing_pending = true;
     h->timing_fused = true;
+    h->timing_prune = false;
+    h->prune_used = false;
+    h->contracted_rows = need_var ? M : 0;
     if (sync || stamps) HIPCHK(h, hipStreamSynchronize(st));
     if (stamps) {
       collect_timing(h);
@@ -493,12 +510,38 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
   hipStream_t stP = overlap ? h->stream2 : st;
   const int nbuf = overlap ? 2 : 1;
   int e;
+  // Pruned sweep (kernels_prune.hip): only the winners leave this call, so a row whose criteria cannot reach the best
+  // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI -- runs as ever.
+  const bool prune = h->prune_on && need_var && q > 0 && !want_out && !want_acq_out && !eh && h->p == 1 && !vx_model && !overlap;
+#ifndef BOGP_PRUNE_PILOT
+#define BOGP_PRUNE_PILOT 4096  // (1024 / 8192 measured with `make EXTRA=-DBOGP_PRUNE_PILOT=...`: profiles/prune_sweep.txt)
+#endif
+  constexpr int64_t PRUNE_PILOT = BOGP_PRUNE_PILOT;  // rows of chunk 0 evaluated exactly to seed the thresholds; a multiple of 256
+  static_assert(PRUNE_PILOT % 256 == 0 && PRUNE_PILOT > 0 && PRUNE_PILOT <= 8192, "pilot rows");
+  const int64_t Ms = prune ? Mc : 0;  // rows of the survivor buffer: one chunk's, i.e. four chunks' worst case (half a chunk measured: profiles/prune_sweep.txt)
+  const int64_t prune_nbk = Mc / 256 + 1;
+  long long* pctl = nullptr;
+  int64_t *poffsets = nullptr, *pmap = nullptr;
+  int *psel = nullptr, *pblk_count = nullptr;
+  unsigned char* pflags = nullptr;
+  if (prune) {
+    const size_t w_off = PRUNE_CTL_WORDS, w_map = w_off + (size_t)prune_nbk + 1, w_sel = w_map + (size_t)Ms, w_cnt = w_sel + (size_t)(Mc / 4) / 2 + 1,
+                 w_flag = w_cnt + (size_t)prune_nbk / 2 + 1, w_end = w_flag + (size_t)Mc / 8 + 1;
+    if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
+    pctl = h->dprune; poffsets = (int64_t*)(h->dprune + w_off); pmap = (int64_t*)(h->dprune + w_map); psel = (int*)(h->dprune + w_sel);
+    pblk_count = (int*)(h->dprune + w_cnt); pflags = (unsigned char*)(h->dprune + w_flag);
+    // the survivor buffer = the second chunk buffer of the two-stream mode
+    if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)Nrows * Ms))) return e;
+    if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * Ms))) return e;
+    if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * Ms))) return e;
+  }
   for (int b = 0; b < nbuf; ++b) {
     if ((e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)Nrows * Mc))) return e;
     if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * Mc))) return e;
     if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * Mc))) return e;
   }
-  if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)nJ * Mc))) return e;
+  if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)nJ * (Mc + Ms)))) return e;  // (+ the survivor buffer's sums)
+  double* dss_surv = h->dss_part + (size_t)nJ * Mc;
   if (h->p > 1) {
     if (Mc > 0x7fffffff / 2) FAIL(h, BOGP_ERR_UNSUPPORTED, "chunk of %lld candidates is too large for the trend GEMM (lower BOGP_CHUNK_MB)", (long long)Mc);
     if (!vx_model) {
@@ -537,6 +580,8 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
       if (!get_event(h, (size_t)(c * EPC + k))) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   hipEvent_t ev_begin = get_event(h, (size_t)(nchunk * EPC));
   if (!ev_begin) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  if (!get_event(h, (size_t)(nchunk * EPC + 2))) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");  // the pilot's pair (pruned sweep)
+  int64_t prune_pending = 0;  // upper bound of the survivors waiting in the buffer (their count itself stays on the device)
   if (overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
     HIPCHK(h, hipEventRecord(ev_begin, st));
     HIPCHK(h, hipStreamWaitEvent(stP, ev_begin, 0));
@@ -579,6 +624,83 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
     }
     HIPCHK(h, hipEventRecord(ev[1], stP));
     if (overlap) HIPCHK(h, hipStreamWaitEvent(st, ev[1], 0));
+    if (prune) {
+      AcqArgs aa;
+      memset(&aa, 0, sizeof(aa));
+      aa.S = S; aa.nJ = nJ_main; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend; aa.sigma2 = h->sigma2; aa.q = q;
+      for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
+      aa.plugin = plugin; aa.minimize = minimize; aa.M = M; aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
+      int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
+      if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
+        const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
+        hipEvent_t* evp = &h->ev[(size_t)(nchunk * EPC + 1)];
+        HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
+        HIPCHK(h, hipEventRecord(evp[0], st));
+        ContractArgs kp = ka;
+        kp.nMt = (int)((P + 63) / 64);
+        HIPCHK(h, launch_contract(kp, st));
+        HIPCHK(h, hipEventRecord(evp[1], st));
+        AcqArgs ap = aa;
+        ap.mu_part = h->dmu_part[0]; ap.w_part = h->dw_part[0]; ap.ss_part = h->dss_part; ap.Mc = Mc; ap.mcount = P; ap.m0 = 0;
+        HIPCHK(h, launch_acquisition(ap, st));
+        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, P, q, h->dbest_val, h->dbest_idx, st));
+        i0 = P;  // (a multiple of 256 unless the chunk ends with it)
+      }
+      const int64_t rcount = mcount - i0;
+      if (rcount > 0) {  // bound -> scan + decision -> compaction -> gather
+        PruneBoundArgs pb;
+        memset(&pb, 0, sizeof(pb));
+        pb.mu_part = h->dmu_part[0] + i0; pb.w_part = h->dw_part[0] + i0; pb.S = S; pb.Mc = Mc; pb.rcount = rcount;
+        pb.beta = h->beta; pb.G = h->G; pb.sigma2 = h->sigma2; pb.plugin = plugin; pb.estimate_trend = h->estimate_trend;
+        pb.minimize = minimize; pb.q = q;
+        for (int i = 0; i < q; ++i) { pb.acq_id[i] = acq_id[i]; pb.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
+        pb.best_val = h->dbest_val; pb.flags = pflags; pb.blk_count = pblk_count;
+        HIPCHK(h, launch_prune_bound(pb, st));
+        HIPCHK(h, launch_prune_scan(pblk_count, (rcount + 255) / 256, poffsets, rcount, Ms, pctl, st));
+        PruneGatherArgs pg;
+        pg.ctl = pctl; pg.flags = pflags; pg.offsets = poffsets; pg.rcount = rcount; pg.m0 = m0 + i0; pg.Mc = Mc; pg.Ms = Ms; pg.S = S;
+        pg.Np = Np; pg.rT = h->drT[0] + i0; pg.mu_part = h->dmu_part[0] + i0; pg.w_part = h->dw_part[0] + i0;
+        pg.rTs = h->drT[1]; pg.mu_s = h->dmu_part[1]; pg.w_s = h->dw_part[1]; pg.sel = psel; pg.map = pmap;
+        HIPCHK(h, launch_prune_gather(pg, st));
+        prune_pending += rcount / 4;
+      }
+      // the buffer goes through the contraction behind the last chunk, and whenever the next chunk's quarter might not fit
+      const bool flush = prune_pending > 0 && (c + 1 == nchunk || prune_pending + Mc / 4 > Ms);
+      HIPCHK(h, hipEventRecord(ev[2], st));
+      // in place or gathered is decided on the device: both contractions are queued, workgroups past the live count return at once
+      ContractArgs kf = ka;
+      kf.rT = h->drT[1]; kf.ss_part = dss_surv; kf.Mc = Ms; kf.nMt = (int)(Ms / 64); kf.live = pctl + 0;
+      if (rcount > 0) {
+        ContractArgs ki = ka;
+        ki.rT = h->drT[0] + i0; ki.ss_part = h->dss_part + i0; ki.nMt = (int)((rcount + 63) / 64); ki.live = pctl + 1;
+        HIPCHK(h, launch_contract(ki, st));
+      }
+      if (flush) HIPCHK(h, launch_contract(kf, st));
+      HIPCHK(h, hipEventRecord(ev[3], st));
+      if (rcount > 0) {
+        AcqArgs ai = aa;
+        ai.mu_part = h->dmu_part[0] + i0; ai.w_part = h->dw_part[0] + i0; ai.ss_part = h->dss_part + i0; ai.Mc = Mc; ai.mcount = rcount;
+        ai.m0 = m0 + i0; ai.live = pctl + 1;
+        HIPCHK(h, launch_acquisition(ai, st));
+        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 1, 0, q, h->dbest_val, h->dbest_idx, st));
+      }
+      if (flush) {
+        AcqArgs af = aa;
+        af.mu_part = h->dmu_part[1]; af.w_part = h->dw_part[1]; af.ss_part = dss_surv; af.Mc = Ms; af.mcount = Ms; af.m0 = 0;
+        af.live = pctl + 0; af.map = pmap;
+        HIPCHK(h, launch_acquisition(af, st));
+        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 0, 0, q, h->dbest_val, h->dbest_idx, st));
+        HIPCHK(h, launch_prune_flushed(pctl, st));
+        prune_pending = 0;
+      }
+      HIPCHK(h, hipEventRecord(ev[4], st));
+      blk_offset += (mcount + 255) / 256;
+      if (h->hXs_lazy) {  // the next chunk's rows travel while this chunk's kernels (queued above) run
+        const int el = lazy_copy_to(h, m0 + mcount + Mc);
+        if (el) return el;
+      }
+      continue;
+    }
     HIPCHK(h, hipEventRecord(ev[2], st));
     // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
     // and k_acquisition sums zero variance groups (its MSE output is not read)
@@ -652,10 +774,14 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
     const int el = lazy_finish(h);
     if (el) return el;
   }
-  if (q > 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dbest_val, h->dbest_idx, st));
+  // (a pruned sweep kept its running best in dbest_* all along)
+  if (q > 0 && !prune) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dbest_val, h->dbest_idx, st));
   h->n_chunks = (int)nchunk;
   h->timing_pending = true;
   h->timing_fused = false;
+  h->timing_prune = prune;
+  h->prune_used = prune;
+  h->contracted_rows = need_var ? M : 0;
   if (sync || overlap) HIPCHK(h, hipStreamSynchronize(st));
   if (overlap) HIPCHK(h, hipStreamSynchronize(stP));
   return BOGP_OK;
@@ -741,6 +867,32 @@ extern "C" int bogp_last_timing(bogp_handle* h, double* corr_ms, double* contrac
   if (n_chunks) *n_chunks = h->n_chunks;
   return BOGP_OK;
 }
+
+extern "C" int bogp_set_prune(bogp_handle* h, int on) {
+  if (!h) return BOGP_ERR_INVALID;
+  h->prune_on = on != 0;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!rows) FAIL(h, BOGP_ERR_INVALID, "bogp_last_contracted_rows: null output");
+  *rows = h->contracted_rows;
+  if (h->prune_used && h->dprune) {  // the count of a pruned sweep never left the device: wait for the sweep, read it
+    HIPCHK(h, hipSetDevice(h->device));
+    long long n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, h->dprune + 4, sizeof(n), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *rows = (int64_t)n;
+  }
+  return BOGP_OK;
+}
+
+// host evaluations of the pruned sweep's bound and test (csrc/bogp_device.h): no device, no handle; tests/test_prune_bounds_host.py
+extern "C" double bogp_acq_upper_bound(int acq_id, double acq_par, double y_hat, double sd_ub, double plugin, double sigma2) {
+  return acq_upper_bound(acq_id, acq_par, y_hat, sd_ub, plugin, sigma2);
+}
+extern "C" int bogp_prune_below(double bound, double threshold) { return prune_below(bound, threshold) ? 1 : 0; }
 
 extern "C" double bogp_flops_per_candidate(const bogp_handle* h) {
   if (!h || !h->committed) return 0.0;

@@ -255,8 +255,8 @@ __device__ __forceinline__ void corr_pair(double s2, double& r0, double& h) {
 
 // scipy.special.ndtr (cephes ndtr.c) branch structure on top of the device erf/erfc:
 //   x = a * sqrt(1/2); z = |x|; z < sqrt(1/2): .5 + .5 erf(x); else y = .5 erfc(z), x > 0 -> 1 - y
-__device__ __forceinline__ double ndtr(double a) {
-  if (isnan(a)) return a;
+__host__ __device__ __forceinline__ double ndtr(double a) {
+  if (__builtin_isnan(a)) return a;
   const double x = a * 0.70710678118654752440;
   const double z = fabs(x);
   if (z < 0.70710678118654752440) return 0.5 + 0.5 * erf(x);
@@ -266,7 +266,7 @@ __device__ __forceinline__ double ndtr(double a) {
 }
 
 // scipy.stats.norm.pdf: exp(-x**2/2.0) / sqrt(2*pi)
-__device__ __forceinline__ double norm_pdf(double x) { return exp(-(x * x) / 2.0) / 2.5066282746310002; }
+__host__ __device__ __forceinline__ double norm_pdf(double x) { return exp(-(x * x) / 2.0) / 2.5066282746310002; }
 
 // EHVI of one row from its MT means and standard deviations (analytic.py:223-274 as one product per cell): the sum over the C
 // cells of prod_k sd_k (G(a) - G(b)), a = (l - mu) / sd, b = (u - mu) / sd, G(z) = phi(z) - z Phi(-z), G(b) = 0 for u = +inf.
@@ -293,7 +293,7 @@ __device__ __forceinline__ double ehvi_cells(const double* lower, const double* 
 
 // The q acquisition criteria of one row, guards as selects (acquisition_fun.py:127-135, 153-176, 208-217, 265-290); shared by
 // k_acquisition (chunked sweep) and k_sweep_small (fused small-N sweep) so that both evaluate the same expressions.
-__device__ __forceinline__ double acq_value(int id, double par, double y_hat, double sd, double plugin, double sigma2) {
+__host__ __device__ __forceinline__ double acq_value(int id, double par, double y_hat, double sd, double plugin, double sigma2) {
   switch (id) {
     case BOGP_ACQ_EI: {
       if (sd / sqrt(sigma2) < 1e-6) return 0.0;
@@ -315,9 +315,51 @@ __device__ __forceinline__ double acq_value(int id, double par, double y_hat, do
       const double term = t * (plugin - y_hat - 1);
       const double e = exp(term + (t * t) * sd2 / 2.0);
       const double f = ndtr(beta_p) * e;
-      return (isfinite(e) && isfinite(f)) ? f : 0.0;
+      return (__builtin_isfinite(e) && __builtin_isfinite(f)) ? f : 0.0;
     }
   }
+}
+
+// Upper bound of acq_value(id, par, y_hat, sd, ...) over sd in [0, sd_ub], guard branches (which return 0) included: what the pruned
+// sweep (kernels_prune.hip) compares with the best value found so far.  EI is non-decreasing in sd; UCB is linear in it; EpsilonPI is
+// ndtr(num / sd) with num = plugin - coef y_hat, i.e. 1 at most for num > 0, non-decreasing in sd for num < 0, and possibly NaN
+// (0 / 0, maximal in the argmax) for num == 0; MGFI is Phi(beta') e with both factors non-decreasing in sd for y_hat >= plugin, and
+// Phi <= 1 otherwise.  A NaN input gives NaN or +inf: such a row is never pruned.
+__host__ __device__ __forceinline__ double acq_upper_bound(int id, double par, double y_hat, double sd_ub, double plugin, double sigma2) {
+  switch (id) {
+    case BOGP_ACQ_EI: return acq_value(BOGP_ACQ_EI, par, y_hat, sd_ub, plugin, sigma2);
+    case BOGP_ACQ_EPSILON_PI: {
+      const double coef = y_hat > 0 ? 1 - par : 1 + par;
+      const double num = plugin - coef * y_hat;
+      if (num > 0) return 1.0;
+      if (num < 0) return ndtr(num / sd_ub);
+      return INFINITY;  // num == 0 (the value can be NaN at sd = 0) or NaN
+    }
+    case BOGP_ACQ_UCB: return par >= 0 ? y_hat + par * sd_ub : y_hat;
+    default: {  // MGFI
+      const double t = fmin(par, 22.36);
+      if (t < 0) return INFINITY;
+      double b;
+      if (y_hat >= plugin) {
+        if (fabs(sd_ub) <= 1e-8) return 0.0;  // every sd of the range takes the guard
+        const double sd2 = sd_ub * sd_ub;
+        const double y_hat_p = y_hat - t * sd2;
+        const double beta_p = (plugin - y_hat_p) / sd_ub;
+        const double term = t * (plugin - y_hat - 1);
+        b = ndtr(beta_p) * exp(term + (t * t) * sd2 / 2.0);
+      } else {
+        b = exp(t * (plugin - y_hat - 1) + (t * t) * (sd_ub * sd_ub) / 2.0);
+      }
+      return __builtin_isfinite(b) ? b : INFINITY;
+    }
+  }
+}
+
+// A row whose bound is `bound` cannot reach `thr`, a value an exactly evaluated row of the same sweep attained.  The margin covers the
+// few-ulp non-monotonicity of erf / erfc / exp and makes the pruned row STRICTLY worse (the lowest-index tie rule and the NaN-first rule
+// of the argmax are untouched); a NaN / infinite threshold or bound, and a zero or subnormal threshold, prune nothing.
+__host__ __device__ __forceinline__ bool prune_below(double bound, double thr) {
+  return __builtin_isfinite(thr) && bound + 1e-9 * (fabs(bound) + fabs(thr)) + 1e-300 < thr;
 }
 
 // posterior of one row from its three sums (gpr.py:490, 496-510): mu = beta + r.gamma, MSE = (1 - |L^-1 r|^2 + u^2) sigma2

@@ -116,6 +116,12 @@ struct bogp_handle {
   double *dblk_val = nullptr, *dmu_out = nullptr, *dmse_out = nullptr, *dacq_out = nullptr, *dbest_val = nullptr;
   int64_t *dblk_idx = nullptr, *dbest_idx = nullptr;
   unsigned int* dcounter = nullptr;  // arrival ticket of k_sweep_small's last workgroup (zero between launches)
+  // pruned sweep (kernels_prune.hip; bogp_set_prune): control words | block offsets | index map | selected rows | block counts | flags
+  bool prune_on = true;
+  long long* dprune = nullptr;
+  size_t prune_cap = 0;
+  bool prune_used = false;       // the last sweep pruned: its contracted-row count is on the device (dprune[4])
+  int64_t contracted_rows = 0;   // ... otherwise it is this
   double* dtopk_val = nullptr;   // [q][k] winners of bogp_sweep_topk (device-resident between its passes)
   int64_t* dtopk_idx = nullptr;
   size_t topk_val_cap = 0, topk_idx_cap = 0;
@@ -239,6 +245,7 @@ struct bogp_handle {
   double t_corr_ms = 0, t_contract_ms = 0, t_acq_ms = 0;
   int n_chunks = 0;
   bool timing_pending = false, timing_fused = false;  // event times not read back yet / of the one-launch small-N sweep
+  bool timing_prune = false;  // ... of a pruned sweep: bound / compaction / gather sit between a chunk's events [1] and [2], the pilot's events behind the chunks'
 };
 
 #define FAIL(h, code, ...)                              \

@@ -42,6 +42,7 @@ struct ContractArgs {
   int NJ16;  // Np / 16
   int NKP;   // Np / 8
   int64_t cross_B;  // launch_contract_cross: points (ss_part is then their record array, see k_contract16<NR, NCP>)
+  const long long* live = nullptr;  // pruned sweep: device word holding the live row count (workgroups of tiles past it return at once), or null
 };
 
 struct AcqArgs {
@@ -72,7 +73,49 @@ struct AcqArgs {
   int64_t* blk_idx;    // [q][nblk_total]
   int64_t blk_offset;  // first block slot of this chunk
   int64_t nblk_total;
+  // pruned sweep (kernels_prune.hip): the valid row count on the device (replaces mcount; workgroups past it return at once), and the
+  // global candidate index of every row of a gathered survivor buffer (replaces m0 + i); both null otherwise
+  const long long* live;
+  const int64_t* map;
 };
+
+// the pruned sweep (kernels_prune.hip): bound every row of a chunk region against the running best, compact the survivors in order,
+// gather their columns into the survivor buffer, and merge the block records of an acquisition launch into the running best
+constexpr int PRUNE_CTL_WORDS = 8;  // device control words: see kernels_prune.hip
+struct PruneBoundArgs {
+  const double* mu_part;  // [S][Mc] (offset to the region's first row)
+  const double* w_part;   // [S][Mc]
+  int S;
+  int64_t Mc;
+  int64_t rcount;         // rows of the region
+  double beta, G, sigma2, plugin;
+  int estimate_trend, minimize, q;
+  int acq_id[64];
+  double acq_par[64];
+  const double* best_val; // [q] running best per criterion (device): the thresholds
+  unsigned char* flags;   // [rcount] 1 = survives
+  int* blk_count;         // [ceil(rcount / 256)]
+};
+struct PruneGatherArgs {
+  const long long* ctl;
+  const unsigned char* flags;
+  const int64_t* offsets;   // exclusive scan of blk_count
+  int64_t rcount, m0;       // region rows; global index of the region's first row
+  int64_t Mc, Ms;           // strides of the chunk arrays / of the survivor arrays
+  int S, Np;
+  const double *rT, *mu_part, *w_part;  // chunk arrays (offset to the region's first row)
+  double *rTs, *mu_s, *w_s;             // survivor arrays
+  int* sel;                 // [<= rcount / 4] region row of this region's k-th survivor
+  int64_t* map;             // [Ms] global index of every buffered survivor
+};
+hipError_t launch_prune_init(long long* ctl, double* best_val, int64_t* best_idx, int q, int64_t pilot_rows, hipStream_t st);
+hipError_t launch_prune_bound(const PruneBoundArgs& a, hipStream_t st);
+hipError_t launch_prune_scan(const int* blk_count, int64_t nblk, int64_t* offsets, int64_t rcount, int64_t cap, long long* ctl, hipStream_t st);
+hipError_t launch_prune_gather(const PruneGatherArgs& a, hipStream_t st);
+// (value, index) records of the first ceil(rows / 256) blocks -> merged into best_val / best_idx; rows = *live if live, else count
+hipError_t launch_prune_update(const double* blk_val, const int64_t* blk_idx, int64_t stride, const long long* live, int64_t count, int q,
+                               double* best_val, int64_t* best_idx, hipStream_t st);
+hipError_t launch_prune_flushed(long long* ctl, hipStream_t st);  // the buffer went through the contraction: count it, empty it
 
 // expected hypervolume improvement of an m-target model over one chunk (kernels_ehvi.hip): replaces AcqArgs / k_acquisition
 // in the chunk loop of bogp_sweep_ehvi

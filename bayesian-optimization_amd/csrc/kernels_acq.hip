@@ -19,7 +19,9 @@ __global__ __launch_bounds__(256) void k_acquisition(AcqArgs a) {
   __shared__ double sv[4];
   __shared__ int64_t si[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // row inside the chunk
-  const bool valid = i < a.mcount;
+  const int64_t mcount = a.live ? (int64_t)*a.live : a.mcount;    // pruned sweep: the row count is on the device
+  if ((int64_t)blockIdx.x * 256 >= mcount) return;                // (never taken without a.live: the grid covers mcount)
+  const bool valid = i < mcount;
   double y_hat = 0.0, sd = 0.0;
   if (valid) {
     double mu = 0.0, wd = 0.0, ss = 0.0;
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(256) void k_acquisition(AcqArgs a) {
     int64_t idx = INT64_MAX;
     if (valid) {
       v = acq_value(a.acq_id[c], a.acq_par[c], y_hat, sd, a.plugin, a.sigma2);
-      idx = a.m0 + i;
+      idx = a.map ? a.map[i] : a.m0 + i;
       if (a.acq_out) a.acq_out[(size_t)c * a.M + idx] = v;
     }
 #pragma unroll

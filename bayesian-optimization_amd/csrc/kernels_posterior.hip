@@ -483,6 +483,7 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
   const int jg = a.nJ - 1 - (int)(blockIdx.x / nMt);
   const int mt = blockIdx.x % nMt;
   const int64_t mc0 = (int64_t)mt * 64;
+  if (a.live && mc0 >= *a.live) return;  // pruned sweep: the live row count is on the device, tiles past it have nothing to do
   const int NJ16 = a.NJ16, NKP = a.NKP;
   const int kmax16 = min((jg + 1) * JT16, NJ16);
 #ifdef CONTRACT_AB_NOZONE  // the 256-row diagonal zone is skipped (column group 0 then runs ONE block): what the zone costs = product - this
@@ -771,6 +772,7 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
   const int jg = a.nJ - 1 - (int)(blockIdx.x / nMt);  // heaviest column group first (k_contract16)
   const int mt = blockIdx.x % nMt;
   const int64_t mc0 = (int64_t)mt * 64;
+  if (a.live && mc0 >= *a.live) return;  // pruned sweep (k_contract16): wave-uniform, before any load
   const int NJ16 = a.NJ16, NKP = a.NKP;
   const int kmax16 = min((jg + 1) * JT16, NJ16);
   const int nkp_full = 2 * jg * JT16;    // k-pairs without a guard

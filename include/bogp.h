@@ -558,6 +558,23 @@ int bogp_merge_topk(int R, int q, int k, int d, const double* gathered, double* 
  * (k_contract, the dominant L^-1 MFMA contraction) and acquisition/argmax.  n_chunks = launches of each.  */
 int bogp_last_timing(bogp_handle* h, double* corr_ms, double* contract_ms, double* acquisition_ms, int* n_chunks);
 
+/* ---- pruned sweep -----------------------------------------------------------------------------------
+ * A bogp_sweep without acq_out returns only its q winners, so a candidate whose criteria cannot reach the best values found so
+ * far even with the most optimistic variance (|L^-1 r|^2 = 0) skips the N^2 contraction (constant basis, chunked path; DESIGN.md
+ * section 5.22).  Winners and their values are those of the full sweep, bit for bit.  on = 0 switches the pruning off for this
+ * handle (default: on): every row is then contracted, as for bogp_predict / bogp_sweep_topk / acq_out, which never prune.        */
+int bogp_set_prune(bogp_handle* h, int on);
+
+/* Rows that went through the contraction in the LAST bogp_predict / bogp_sweep call (M without pruning; waits for a queued sweep). */
+int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows);
+
+/* Host evaluations of the pruned sweep's two rules, no device and no handle (tests/test_prune_bounds_host.py): an upper bound of
+ * criterion acq_id over every standard deviation in [0, sd_ub] at the mean behind y_hat (guard branches included; NaN or +inf
+ * where no bound exists), and whether a row with that bound is pruned against a value another row attained:
+ * bound + 1e-9 (|bound| + |threshold|) + 1e-300 < threshold, threshold finite.                                                  */
+double bogp_acq_upper_bound(int acq_id, double acq_par, double y_hat, double sd_ub, double plugin, double sigma2);
+int bogp_prune_below(double bound, double threshold);
+
 /* Algorithmic FP64 flops per candidate of the posterior for the committed model:
  * N^2 + N (3d + 5 + 2p)  (SURVEY.md section 8d).                                                        */
 double bogp_flops_per_candidate(const bogp_handle* h);
