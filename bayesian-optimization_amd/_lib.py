@@ -97,6 +97,9 @@ SIGNATURES = {
     "bogp_point_eval_batch": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "bogp_polish": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double,
                               C.c_double, _dp, _dp, _ip]),
+    "bogp_point_eval_ehvi": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "bogp_polish_ehvi": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double,
+                                   _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -950,6 +953,51 @@ class Engine:
             self._lib.bogp_polish(self._h, _ptr(X0), B, _ptr(lo), _ptr(hi), int(acq[0]), float(acq[1]), float(plugin),
                                   int(bool(minimize)), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
                                   ne.ctypes.data_as(_ip))
+        )  # fmt: skip
+        return Xo, fo, ne
+
+    @staticmethod
+    def _cells(lower, upper):
+        lower, upper = _f64(lower), _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape")
+        return lower, upper
+
+    def point_eval_ehvi(self, X, lower, upper, moments: bool = False):
+        """EHVI of the committed multi-target model and its input gradient at the rows of `X` (B x d) in ONE device round trip
+        (bogp_point_eval_ehvi), for the cells (lower, upper) (C x m each; upper may hold +inf): (ehvi (B,), dehvi (B, d)) and,
+        with `moments`, also mu (B, m), mse (B, m), dmu (B, m, d), dmse (B, m, d).  Cells equal to those of the call before are
+        not uploaded again."""
+        X = np.atleast_2d(_f64(X))
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise Exception("x does not have the right size!")
+        lower, upper = self._cells(lower, upper)
+        C_, m = lower.shape
+        B, d = X.shape[0], self.d
+        ehvi, dehvi = np.empty(B), np.empty((B, d))
+        mom = (np.empty((B, m)), np.empty((B, m)), np.empty((B, m, d)), np.empty((B, m, d))) if moments else (None,) * 4
+        rc = self._lib.bogp_point_eval_ehvi(self._h, _ptr(X), B, int(m), int(C_), _ptr(lower), _ptr(upper), _ptr(ehvi), _ptr(dehvi),
+                                            *(_ptr(a) for a in mom))  # fmt: skip
+        if rc:
+            self._check(rc)
+        return (ehvi, dehvi) + (mom if moments else ())
+
+    def polish_ehvi(self, starts, lo, hi, lower, upper, max_evals: int = 50, pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local maximisation of EHVI inside the box (bogp_polish_ehvi): (points (B, d), values (B,),
+        evaluations used (B,)); values[i] >= EHVI at starts[i] clipped into the box."""
+        X0 = np.atleast_2d(_f64(starts))
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise Exception("x does not have the right size!")
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != self.d or len(hi) != self.d:
+            raise ValueError("lo / hi must have d entries")
+        lower, upper = self._cells(lower, upper)
+        C_, m = lower.shape
+        B = X0.shape[0]
+        Xo, fo, ne = np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
+        self._check(
+            self._lib.bogp_polish_ehvi(self._h, _ptr(X0), B, _ptr(lo), _ptr(hi), int(m), int(C_), _ptr(lower), _ptr(upper),
+                                       int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))
         )  # fmt: skip
         return Xo, fo, ne
 

@@ -310,7 +310,13 @@ class EHVI:
       cells        (lower, upper), each C x m (upper may hold +inf).
     `criterion(X)` returns one value per row, shape (M,): row i is what the reference's one-row call returns for row i
     (computed in float64 -- the reference casts mu / MSE to float32, analytic.py:228-233).  All rows are evaluated in one
-    device pass (`bogp_sweep_ehvi`); there is no input gradient.
+    device pass (`bogp_sweep_ehvi`); by default there is no input gradient, as in the reference.
+
+    `input_gradient=True` (an extension, Gaussian-process models only): `criterion(X, return_dx=True)` returns (values, dx)
+    in the shapes of the single-objective criteria -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through
+    `bogp_point_eval_ehvi` (the closed-form gradient in (mu_k, sd_k) chained with the posterior's input gradients on the
+    device), `criterion(X)` for at most 64 rows takes the same call, and `argmax_restart` serves "BFGS", "sweep-BFGS" and
+    "sweep-device-BFGS" for it.
 
     The model may also be a `RandomForest` fitted on y (N, m) -- this package's or the reference's, as MOBO fits it on mixed
     spaces: rows then come in the reference's format (level labels in the categorical columns), and the forest walk and the
@@ -319,9 +325,13 @@ class EHVI:
     is_ehvi = True
     minimize = False  # (the sweep helpers read it off every criterion)
 
-    def __init__(self, model=None, ref_point=None, partitioning=None, Y=None, cells=None):
+    def __init__(self, model=None, ref_point=None, partitioning=None, Y=None, cells=None, input_gradient: bool = False):
         if model is None:
             raise ValueError("model cannot be None")
+        if input_gradient and _forest.is_forest_model(model):
+            raise NotImplementedError("a forest has no input gradient (the reference's RandomForest has none either): "
+                                      "EHVI(input_gradient=True) takes a Gaussian process model")  # fmt: skip
+        self.input_gradient = bool(input_gradient)
         if sum(s is not None for s in (partitioning, Y, cells)) != 1:
             raise ValueError("EHVI takes exactly one of partitioning=, Y= and cells=")
         if ref_point is None:
@@ -377,12 +387,23 @@ class EHVI:
         return model.engine.sweep_ehvi(self.cell_lower_bounds, self.cell_upper_bounds, k=k, return_values=return_values)
 
     def __call__(self, X, return_dx: bool = False):
-        if return_dx:
+        if return_dx and not self.input_gradient:
             raise NotImplementedError("EHVI has no input gradient (the reference's EHVI has none either)")
         if _forest.is_forest_model(self.model):  # rows keep their level labels
+            if return_dx:
+                raise NotImplementedError("a forest has no input gradient: return_dx=True is not served")
             return _forest.criterion_values(self, X)
         if getattr(self.model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         eng = self.model.engine
+        if self.input_gradient:
+            rows = self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float)))
+            if return_dx or len(rows) <= 64:  # value and gradient in one device round trip (bogp_point_eval_ehvi)
+                if not hasattr(eng, "point_eval_ehvi"):
+                    raise NotImplementedError("the model's engine has no point_eval_ehvi: no input gradient of EHVI")
+                vals, dx = eng.point_eval_ehvi(rows, self.cell_lower_bounds, self.cell_upper_bounds)[:2]
+                if not return_dx:
+                    return vals
+                return (vals.reshape(1), dx.reshape(1, -1)) if len(rows) == 1 else (vals.reshape(-1, 1), dx)
         eng.upload_candidates(self.model._check_X(X))
         return self.sweep(return_values=True)[2]

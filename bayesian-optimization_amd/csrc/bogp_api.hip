@@ -127,7 +127,7 @@ extern "C" void bogp_destroy(bogp_handle* h) {
   if (h->stream_upd) (void)hipStreamSynchronize(h->stream_upd);
   dfree(h->dXs_owned); dfree(h->dss_part); dfree(h->dbounds); dfree(h->dsobol); dfree(h->dxform);
   for (int b = 0; b < 2; ++b) { dfree(h->drT[b]); dfree(h->dmu_part[b]); dfree(h->dw_part[b]); }
-  dfree(h->dblk_val); dfree(h->dblk_idx); dfree(h->dmu_out); dfree(h->dmse_out); dfree(h->dacq_out); dfree(h->dehvi_cells); dfree(h->dforest_words); dfree(h->dforest_tree);
+  dfree(h->dblk_val); dfree(h->dblk_idx); dfree(h->dmu_out); dfree(h->dmse_out); dfree(h->dacq_out); dfree(h->dehvi_cells); ehvi_cells_forget(h); dfree(h->dforest_words); dfree(h->dforest_tree);
   dfree(h->dbest_val); dfree(h->dbest_idx); dfree(h->dtopk_val); dfree(h->dtopk_idx); dfree(h->dcounter); dfree(h->dprune); h->dinfo = nullptr; dfree(h->dscal); dfree(h->dgrad_partial); dfree(h->dbatch);
   dfree(h->dTt); dfree(h->dCS); dfree(h->duu); dfree(h->dmtrend); dfree(h->dtpart[0]); dfree(h->dtpart[1]);
   dfree(h->dlift); dfree(h->dlift_pen); dfree(h->dlift_cnt); dfree(h->dlift_off); dfree(h->dlift_Z); dfree(h->dlift_map); dfree(h->dlift_val);

@@ -506,6 +506,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   auto upload_cells = [&]() -> int {  // in stream order, before the pass that reads them; `cells` stays as it is until that pass is complete
     const size_t nb = (size_t)C * m;
     int e;
+    ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
     if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, std::max<size_t>(2 * nb, 2)))) return e;
     if (nb == 0) return BOGP_OK;
     HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, cells.data(), nb * sizeof(double), hipMemcpyHostToDevice, st));

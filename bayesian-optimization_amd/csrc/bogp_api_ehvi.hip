@@ -36,6 +36,7 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
   int e;
+  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
   if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
   // (the cells are the kernel's arguments: copied in stream order, before the first chunk's kernels that read them)
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));

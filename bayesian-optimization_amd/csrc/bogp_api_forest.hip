@@ -383,6 +383,7 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
   hipStream_t st = h->stream;
   const int64_t M = h->M, nblk = (M + 255) / 256;
   const bool keep = k > 1 || ehvi_out;
+  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
   if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
   if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)(nblk + 1)))) return e;
   if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)(nblk + 1)))) return e;

@@ -32,6 +32,8 @@ int candidates_ready(bogp_handle* h);
 void clear_sweep_timing(bogp_handle* h);
 // the candidate calls need the row width d: from bogp_set_train or from bogp_forest_set
 bool has_dim(const bogp_handle* h);
+// dehvi_cells was overwritten by a sweep: bogp_point_eval_ehvi must upload its cells again
+void ehvi_cells_forget(bogp_handle* h);
 }
 
 struct bogp_handle {
@@ -128,6 +130,10 @@ struct bogp_handle {
   size_t blk_val_cap = 0, blk_idx_cap = 0, mu_out_cap = 0, mse_out_cap = 0, acq_out_cap = 0;
   double* dehvi_cells = nullptr;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
   size_t ehvi_cells_cap = 0;
+  // host copy of the cells bogp_point_eval_ehvi / bogp_polish_ehvi left in dehvi_cells ([lower | upper], ehvi_host_C x ehvi_host_m): a call
+  // with the same cells skips the upload.  Empty <=> unknown: every other writer of dehvi_cells clears it (ehvi_cells_forget)
+  std::vector<double> h_ehvi_cells;
+  int ehvi_host_m = 0, ehvi_host_C = 0;
 
   // lift of a reduced search space (bogp_api_lift.hip): lift_D > 0 <=> a lift is set, for a model of d = lift_r
   int lift_D = 0, lift_r = 0;

@@ -555,7 +555,7 @@ int point_columns_per_pass(int d);
 int point_passes(int d);
 void point_tri_geometry(int N, int d, int B, int* rb, int* nsplit);
 hipError_t launch_point_rhs(int kernel, const PointRhsArgs& a, int B, hipStream_t st);
-hipError_t launch_point_tri(const PointTriArgs& a, int B, hipStream_t st);
+hipError_t launch_point_tri(const PointTriArgs& a, int B, hipStream_t st, bool finish = true);  // !finish: k_point_tri alone (another finishing kernel follows)
 hipError_t launch_point_trend(const PointRhsArgs& ra, const double* W, int ldW, int p, const double* betav, const double* Sinv,
                               int estimate_trend, double* Tw, double* trec, int B, hipStream_t st);
 // MFMA flavour of the B-point path (kernels_point.hip): ncp = point_mfma_columns(d) right-hand-side columns per point (0: d too large)
@@ -566,5 +566,23 @@ hipError_t launch_point_gw(int ncp, const double* rT, long long Mc, const double
 hipError_t launch_point_finish_mfma(const PointTriArgs& a, int ncp, int B, hipStream_t st);
 size_t polish_state_doubles(int d);
 hipError_t launch_polish_step(const PolishArgs& a, int B, hipStream_t st);
+// EHVI and its input gradient at B points of an m-target model (kernels_point_ehvi.hip): the finishing kernel behind k_point_rhs + k_point_tri
+// (VALU flavour) in place of k_point_finish
+struct PointEhviArgs {
+  const double* part;   // [B][npass][nRB + 1][2 NC] block records of k_point_tri
+  const double* rhs;    // [B][npass][Npp][NC] right-hand sides of k_point_rhs
+  const double* gamma;  // [m][ld_gamma] the targets' gamma columns (gamma_base)
+  const double* lower;  // [C][m] cell bounds (device)
+  const double* upper;  // [C][m] (+inf allowed)
+  double* out;          // [B][rec_stride]: mu_0, MSE_0, EHVI, dmu_0 (d), dMSE_0 (d), dEHVI (d) -- k_point_finish's record with q = 1
+  double* mom;          // [B][mom_stride]: mu (m), MSE (m), dmu (m x d), dMSE (m x d), or null
+  int ld_gamma, N, Npp, nRB, npass, d, rec_stride, mom_stride;
+  int m, C, estimate_trend;
+  double beta, G, ftft;
+  double sigma2[8];     // per target
+  unsigned long long* done_flag;  // as PointTriArgs
+  unsigned long long done_seq;
+};
+hipError_t launch_point_ehvi_finish(const PointEhviArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

@@ -1,5 +1,6 @@
 // bogp_point.hip -- C ABI of the one-point / B-point consumption path (kernels_point.hip): bogp_point_eval,
-// bogp_point_eval_batch, bogp_gradient_batch, bogp_polish.  See include/bogp.h for the contracts.
+// bogp_point_eval_batch, bogp_gradient_batch, bogp_polish, and of its multi-objective finish (kernels_point_ehvi.hip):
+// bogp_point_eval_ehvi, bogp_polish_ehvi.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -71,7 +72,7 @@ int ensure_pinned(bogp_handle* h, size_t n) {
 // queue k_point_rhs + k_point_tri for B points; the records land in `out` (device or device-mapped host memory)
 int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, const double* x_host, int B, int q, const int* acq_id,
                      const double* acq_par, double plugin, int minimize, bool want_dacq, double* out,
-                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0) {
+                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0, const PointEhviArgs* eh = nullptr) {
   hipStream_t st = h->stream;
   int e;
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
@@ -83,7 +84,7 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   const int ncp = point_mfma_columns(h->d);
   const char* e_min = getenv("BOGP_POINT_MFMA_MIN");  // read per call: the tests run both flavours in one process
   const long long mfma_min = e_min ? atoll(e_min) : 768LL;
-  if (dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
+  if (!eh && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
     const int Np = h->Np, nJ = (Np + 255) / 256;
     const long long Mc = ((long long)B * ncp + 63) / 64 * 64;
     if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * Mc))) return e;
@@ -148,13 +149,137 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   for (int i = 0; i < q; ++i) { ta.acq_id[i] = acq_id[i]; ta.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
   ta.plugin = plugin; ta.beta = h->beta; ta.G = h->G; ta.ftft = h->ftft; ta.sigma2 = h->sigma2;
   ta.done_flag = done_flag; ta.done_seq = done_seq; ta.trend_rec = trend_rec;
+  if (eh) {  // the m-target finish in place of k_point_finish (eh: cells, targets, the moment blocks; the rest is filled in here)
+    HIPCHK(h, launch_point_tri(ta, B, st, false));
+    PointEhviArgs ea = *eh;
+    ea.part = h->dpt_part; ea.rhs = h->dpt_rhs; ea.gamma = h->dgamma_base; ea.ld_gamma = h->Np; ea.out = out;
+    ea.N = h->N; ea.Npp = pl.Npp; ea.nRB = pl.nRB; ea.npass = pl.npass; ea.d = h->d; ea.rec_stride = pl.rec_stride;
+    ea.estimate_trend = h->estimate_trend; ea.beta = h->beta; ea.G = h->G; ea.ftft = h->ftft;
+    for (int t = 0; t < ea.m; ++t) ea.sigma2[t] = h->sigma2_t[t];
+    ea.done_flag = done_flag; ea.done_seq = done_seq;
+    HIPCHK(h, launch_point_ehvi_finish(ea, B, st));
+    return BOGP_OK;
+  }
   HIPCHK(h, launch_point_tri(ta, B, st));
+  return BOGP_OK;
+}
+
+// the lock-step polish of B starts: bogp_polish's loop (one criterion of the single-target path) or -- eh non-null -- bogp_polish_ehvi's
+int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const double* lo, const double* hi, int acq_id, double acq_par,
+                double plugin, int minimize, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals,
+                const PointEhviArgs* eh) {
+  int e;
+  if (!X0 || !lo || !hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
+  const int d = h->d;
+  if (max_evals <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: max_evals must be positive", who);
+  double wmin = INFINITY;
+  for (int k = 0; k < d; ++k) {
+    if (!(hi[k] >= lo[k])) FAIL(h, BOGP_ERR_INVALID, "%s: lo[%d] > hi[%d]", who, k, k);
+    if (hi[k] > lo[k]) wmin = std::min(wmin, hi[k] - lo[k]);
+  }
+  if (!std::isfinite(wmin)) wmin = 1.0;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  const PointPlan pl = plan_of(h, B, 1, true);
+  const size_t ss = polish_state_doubles(d);
+  if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
+  if ((e = ensure(h, &h->dpt_out, &h->pt_out_cap, (size_t)B * pl.rec_stride))) return e;
+  if ((e = ensure(h, &h->dpt_state, &h->pt_state_cap, (size_t)B * ss))) return e;
+  if ((e = ensure(h, &h->dpt_box, &h->pt_box_cap, (size_t)2 * d))) return e;
+  if ((e = ensure_counters(h, (size_t)std::max(B, 64) + 1))) return e;
+  if ((e = ensure_pinned(h, std::max<size_t>((size_t)B * (d + 2) + 16, 1024)))) return e;
+  unsigned int* dn_done = h->dpt_counter + (h->pt_counter_cap - 1);
+  // starting points clipped into the box (scipy's L-BFGS-B projects x0 the same way)
+  std::vector<double> xs((size_t)B * d), box(2 * (size_t)d), st0((size_t)B * ss, 0.0);
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < d; ++k) xs[(size_t)b * d + k] = std::min(std::max(X0[(size_t)b * d + k], lo[k]), hi[k]);
+  for (int k = 0; k < d; ++k) { box[k] = lo[k]; box[d + k] = hi[k]; }
+  for (int b = 0; b < B; ++b) { st0[(size_t)b * ss + 1] = 1.0; st0[(size_t)b * ss + 7] = 1.0; }  // alpha = 1, first = 1
+  HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dpt_box, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dpt_state, st0.data(), st0.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemsetAsync(dn_done, 0, sizeof(unsigned int), st));
+  PolishArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.state = h->dpt_state; pa.rec = h->dpt_out; pa.Xt = h->dpt_Xb; pa.lo = h->dpt_box; pa.hi = h->dpt_box + d; pa.n_done = dn_done;
+  pa.d = d; pa.q = 1; pa.rec_stride = pl.rec_stride; pa.state_stride = (int)ss; pa.max_evals = max_evals;
+  pa.pgtol = pgtol; pa.factr_eps = factr * 2.220446049250313e-16; pa.first_step = 0.05 * wmin;
+  unsigned int* hdone = (unsigned int*)(h->hpin);
+  // every iteration = one batched evaluation of the B trial points + one optimiser step, all queued; the host looks at the
+  // count of finished starts every 8 iterations (one 4-byte read-back) to stop early
+  int it = 0;
+  while (it < max_evals) {
+    const int burst = std::min(8, max_evals - it);
+    for (int s = 0; s < burst; ++s, ++it) {
+      if ((e = queue_point_eval(h, pl, h->dpt_Xb, nullptr, B, 1, &acq_id, &acq_par, plugin, minimize, true, h->dpt_out, nullptr, 0, eh))) return e;
+      HIPCHK(h, launch_polish_step(pa, B, st));
+    }
+    HIPCHK(h, hipMemcpyAsync(hdone, dn_done, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (*hdone >= (unsigned int)B) break;
+  }
+  std::vector<double> fin((size_t)B * ss);
+  HIPCHK(h, hipMemcpyAsync(fin.data(), h->dpt_state, fin.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) {
+    const double* s = &fin[(size_t)b * ss];
+    fout[b] = s[0];
+    if (n_evals) n_evals[b] = (int)s[6];
+    memcpy(Xout + (size_t)b * d, s + 8, (size_t)d * sizeof(double));
+  }
+  return BOGP_OK;
+}
+
+// what bogp_point_eval_ehvi and bogp_polish_ehvi refuse alike (the cells are checked by ehvi_cells_resident)
+int check_ehvi(bogp_handle* h, const char* who, int m) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no input gradient", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model", who);
+  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP || h->kernel == BOGP_KERNEL_MATERN_NU)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the correlation has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
+  if (h->d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
+  if (m != h->n_t) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d but the committed model has %d targets", who, m, h->n_t);
+  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d outside [2, %d]", who, m, BOGP_MAX_TARGETS);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  return BOGP_OK;
+}
+
+// the cells on the device (bogp_sweep_ehvi's rules).  A call whose (m, C, bytes) equal the cells this path left there skips the
+// checks and the upload: the BFGS loop makes thousands of one-point calls over the same cells.
+int ehvi_cells_resident(bogp_handle* h, const char* who, int m, int C, const double* lower, const double* upper) {
+  if (C < 1 || C > BOGP_MAX_EHVI_CELLS) FAIL(h, BOGP_ERR_INVALID, "%s: C = %d cells outside [1, %d]", who, C, BOGP_MAX_EHVI_CELLS);
+  if (!lower || !upper) FAIL(h, BOGP_ERR_INVALID, "%s: lower and upper must be non-null", who);
+  const size_t nb = (size_t)C * m;
+  if (h->dehvi_cells && h->ehvi_host_m == m && h->ehvi_host_C == C && h->h_ehvi_cells.size() == 2 * nb &&
+      memcmp(h->h_ehvi_cells.data(), lower, nb * sizeof(double)) == 0 && memcmp(h->h_ehvi_cells.data() + nb, upper, nb * sizeof(double)) == 0)
+    return BOGP_OK;
+  for (size_t i = 0; i < nb; ++i) {
+    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
+    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
+    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  ehvi_cells_forget(h);
+  int e;
+  if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are not needed past this call
+  h->h_ehvi_cells.assign(lower, lower + nb);
+  h->h_ehvi_cells.insert(h->h_ehvi_cells.end(), upper, upper + nb);
+  h->ehvi_host_m = m;
+  h->ehvi_host_C = C;
   return BOGP_OK;
 }
 
 }  // namespace
 
 namespace bogp {
+
+void ehvi_cells_forget(bogp_handle* h) {
+  h->h_ehvi_cells.clear();
+  h->ehvi_host_m = h->ehvi_host_C = 0;
+}
 
 void point_release(bogp_handle* h) {
   dfree(h->dpt_rhs); dfree(h->dpt_part); dfree(h->dpt_out); dfree(h->dpt_Xb); dfree(h->dpt_state); dfree(h->dpt_box);
@@ -264,63 +389,97 @@ extern "C" int bogp_polish(bogp_handle* h, const double* X0, int B, const double
   if (!h) return BOGP_ERR_INVALID;
   int e = check_common(h, "bogp_polish", 1, &acq_id, &acq_par);
   if (e) return e;
-  if (!X0 || !lo || !hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_polish: null pointer or B <= 0");
-  const int d = h->d;
-  if (max_evals <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_polish: max_evals must be positive");
-  double wmin = INFINITY;
-  for (int k = 0; k < d; ++k) {
-    if (!(hi[k] >= lo[k])) FAIL(h, BOGP_ERR_INVALID, "bogp_polish: lo[%d] > hi[%d]", k, k);
-    if (hi[k] > lo[k]) wmin = std::min(wmin, hi[k] - lo[k]);
-  }
-  if (!std::isfinite(wmin)) wmin = 1.0;
-  HIPCHK(h, hipSetDevice(h->device));
+  return polish_loop(h, "bogp_polish", X0, B, lo, hi, acq_id, acq_par, plugin, minimize, max_evals, pgtol, factr, Xout, fout, n_evals, nullptr);
+}
+
+// ---- EHVI and its input gradient at B points of the committed m-target model (kernels_point_ehvi.hip) --------------------------
+static int point_eval_ehvi_chunk(bogp_handle* h, const PointEhviArgs& eh0, const double* Xb, int B, bool want_mom, double* ehvi, double* dehvi,
+                                 double* mu, double* mse, double* dmu, double* dmse) {
   hipStream_t st = h->stream;
+  const int d = h->d, m = eh0.m;
   const PointPlan pl = plan_of(h, B, 1, true);
-  const size_t ss = polish_state_doubles(d);
-  if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
-  if ((e = ensure(h, &h->dpt_out, &h->pt_out_cap, (size_t)B * pl.rec_stride))) return e;
-  if ((e = ensure(h, &h->dpt_state, &h->pt_state_cap, (size_t)B * ss))) return e;
-  if ((e = ensure(h, &h->dpt_box, &h->pt_box_cap, (size_t)2 * d))) return e;
-  if ((e = ensure_counters(h, (size_t)std::max(B, 64) + 1))) return e;
-  if ((e = ensure_pinned(h, std::max<size_t>((size_t)B * (d + 2) + 16, 1024)))) return e;
-  unsigned int* dn_done = h->dpt_counter + (h->pt_counter_cap - 1);
-  // starting points clipped into the box (scipy's L-BFGS-B projects x0 the same way)
-  std::vector<double> xs((size_t)B * d), box(2 * (size_t)d), st0((size_t)B * ss, 0.0);
-  for (int b = 0; b < B; ++b)
-    for (int k = 0; k < d; ++k) xs[(size_t)b * d + k] = std::min(std::max(X0[(size_t)b * d + k], lo[k]), hi[k]);
-  for (int k = 0; k < d; ++k) { box[k] = lo[k]; box[d + k] = hi[k]; }
-  for (int b = 0; b < B; ++b) { st0[(size_t)b * ss + 1] = 1.0; st0[(size_t)b * ss + 7] = 1.0; }  // alpha = 1, first = 1
-  HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(h->dpt_box, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(h->dpt_state, st0.data(), st0.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemsetAsync(dn_done, 0, sizeof(unsigned int), st));
-  PolishArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.state = h->dpt_state; pa.rec = h->dpt_out; pa.Xt = h->dpt_Xb; pa.lo = h->dpt_box; pa.hi = h->dpt_box + d; pa.n_done = dn_done;
-  pa.d = d; pa.q = 1; pa.rec_stride = pl.rec_stride; pa.state_stride = (int)ss; pa.max_evals = max_evals;
-  pa.pgtol = pgtol; pa.factr_eps = factr * 2.220446049250313e-16; pa.first_step = 0.05 * wmin;
-  unsigned int* hdone = (unsigned int*)(h->hpin);
-  // every iteration = one batched evaluation of the B trial points + one optimiser step, all queued; the host looks at the
-  // count of finished starts every 8 iterations (one 4-byte read-back) to stop early
-  int it = 0;
-  while (it < max_evals) {
-    const int burst = std::min(8, max_evals - it);
-    for (int s = 0; s < burst; ++s, ++it) {
-      if ((e = queue_point_eval(h, pl, h->dpt_Xb, nullptr, B, 1, &acq_id, &acq_par, plugin, minimize, true, h->dpt_out))) return e;
-      HIPCHK(h, launch_polish_step(pa, B, st));
-    }
-    HIPCHK(h, hipMemcpyAsync(hdone, dn_done, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (*hdone >= (unsigned int)B) break;
+  const size_t mom_stride = want_mom ? (size_t)2 * m + 2 * (size_t)m * d : 0;
+  const size_t nrec = (size_t)B * (pl.rec_stride + mom_stride);
+  int e;
+  if ((e = ensure_pinned(h, std::max<size_t>(nrec + 8, 1024)))) return e;
+  const double* dXb = nullptr;
+  if (B > 1 || d > BOGP_POINT_ARG_D) {
+    if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
+    HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
+    dXb = h->dpt_Xb;
   }
-  std::vector<double> fin((size_t)B * ss);
-  HIPCHK(h, hipMemcpyAsync(fin.data(), h->dpt_state, fin.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
+  PointEhviArgs eh = eh0;
+  eh.mom = want_mom ? h->hpin_dev + (size_t)B * pl.rec_stride : nullptr;
+  eh.mom_stride = (int)mom_stride;
+  const int one_id = BOGP_ACQ_EI;  // (sizes the record like one criterion; the id itself is not evaluated)
+  if (B == 1) {  // the BFGS loop's call: completion polled off the sequence word behind the records (point_eval_chunk)
+    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
+    const unsigned long long seq = ++h->pt_seq;
+    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin_dev + nrec);
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin_dev, dflag, seq, &eh))) return e;
+    bool seen = false;
+    for (int spin = 0; spin < 400000; ++spin) {
+      if (*flag == seq) { seen = true; break; }
+      __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!seen) HIPCHK(h, hipStreamSynchronize(st));
+  } else {
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin_dev, nullptr, 0, &eh))) return e;
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
   for (int b = 0; b < B; ++b) {
-    const double* s = &fin[(size_t)b * ss];
-    fout[b] = s[0];
-    if (n_evals) n_evals[b] = (int)s[6];
-    memcpy(Xout + (size_t)b * d, s + 8, (size_t)d * sizeof(double));
+    const double* o = h->hpin + (size_t)b * pl.rec_stride;
+    ehvi[b] = o[2];
+    if (dehvi) memcpy(dehvi + (size_t)b * d, o + 3 + 2 * d, (size_t)d * sizeof(double));
+    if (!want_mom) continue;
+    const double* q = h->hpin + (size_t)B * pl.rec_stride + (size_t)b * mom_stride;
+    if (mu) memcpy(mu + (size_t)b * m, q, (size_t)m * sizeof(double));
+    if (mse) memcpy(mse + (size_t)b * m, q + m, (size_t)m * sizeof(double));
+    if (dmu) memcpy(dmu + (size_t)b * m * d, q + 2 * m, (size_t)m * d * sizeof(double));
+    if (dmse) memcpy(dmse + (size_t)b * m * d, q + 2 * m + (size_t)m * d, (size_t)m * d * sizeof(double));
   }
   return BOGP_OK;
+}
+
+extern "C" int bogp_point_eval_ehvi(bogp_handle* h, const double* Xb, int B, int m, int C, const double* lower, const double* upper,
+                                    double* ehvi, double* dehvi, double* mu, double* mse, double* dmu, double* dmse) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_ehvi";
+  int e = check_ehvi(h, who, m);
+  if (e) return e;
+  if (!Xb || !ehvi || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null points, null ehvi or B <= 0", who);
+  if ((e = ehvi_cells_resident(h, who, m, C, lower, upper))) return e;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int d = h->d;
+  PointEhviArgs eh;
+  memset(&eh, 0, sizeof(eh));
+  eh.m = m; eh.C = C; eh.lower = h->dehvi_cells; eh.upper = h->dehvi_cells + (size_t)C * m;
+  const bool want_mom = mu || mse || dmu || dmse;
+  // chunks as point_eval_host's: the right-hand sides stay below 256 MB
+  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(chunk, B - b0);
+    e = point_eval_ehvi_chunk(h, eh, Xb + (size_t)b0 * d, nb, want_mom, ehvi + b0, dehvi ? dehvi + (size_t)b0 * d : nullptr,
+                              mu ? mu + (size_t)b0 * m : nullptr, mse ? mse + (size_t)b0 * m : nullptr,
+                              dmu ? dmu + (size_t)b0 * m * d : nullptr, dmse ? dmse + (size_t)b0 * m * d : nullptr);
+    if (e) return e;
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const double* lo, const double* hi, int m, int C,
+                                const double* lower, const double* upper, int max_evals, double pgtol, double factr, double* Xout,
+                                double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_ehvi";
+  int e = check_ehvi(h, who, m);
+  if (e) return e;
+  if (!X0 || !lo || !hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
+  if ((e = ehvi_cells_resident(h, who, m, C, lower, upper))) return e;
+  PointEhviArgs eh;
+  memset(&eh, 0, sizeof(eh));
+  eh.m = m; eh.C = C; eh.lower = h->dehvi_cells; eh.upper = h->dehvi_cells + (size_t)C * m;
+  return polish_loop(h, who, X0, B, lo, hi, BOGP_ACQ_EI, 0.0, 0.0, 0, max_evals, pgtol, factr, Xout, fout, n_evals, &eh);
 }

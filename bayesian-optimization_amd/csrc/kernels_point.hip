@@ -735,16 +735,16 @@ void point_tri_geometry(int N, int d, int B, int* rb, int* nsplit) {
   *nsplit = s;
 }
 
-hipError_t launch_point_tri(const PointTriArgs& a, int B, hipStream_t st) {
+hipError_t launch_point_tri(const PointTriArgs& a, int B, hipStream_t st, bool finish) {
   dim3 grid((a.nRB + 1) * a.nsplit, a.npass, B);
   if (point_columns_per_pass(a.d) == 12) {
     if (a.rb == 128) hipLaunchKernelGGL((k_point_tri<12, 2>), grid, 256, 0, st, a.V, a.gamma, a.wvec, a.rhs, a);
     else hipLaunchKernelGGL((k_point_tri<12, 1>), grid, 256, 0, st, a.V, a.gamma, a.wvec, a.rhs, a);
-    hipLaunchKernelGGL(k_point_finish<12>, dim3(B), 256, 0, st, a);
+    if (finish) hipLaunchKernelGGL(k_point_finish<12>, dim3(B), 256, 0, st, a);
   } else {
     if (a.rb == 128) hipLaunchKernelGGL((k_point_tri<22, 2>), grid, 256, 0, st, a.V, a.gamma, a.wvec, a.rhs, a);
     else hipLaunchKernelGGL((k_point_tri<22, 1>), grid, 256, 0, st, a.V, a.gamma, a.wvec, a.rhs, a);
-    hipLaunchKernelGGL(k_point_finish<22>, dim3(B), 256, 0, st, a);
+    if (finish) hipLaunchKernelGGL(k_point_finish<22>, dim3(B), 256, 0, st, a);
   }
   return hipGetLastError();
 }

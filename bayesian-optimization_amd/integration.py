@@ -111,6 +111,7 @@ def _strategy_of(masks, kw) -> dict:
 _ORIGINAL: dict = {}
 _REROUTE: dict = {}
 _BATCH: dict = {}  # install(batch_strategy=...): how the fused ParallelBO step makes its q points differ ("topk" when empty)
+_EHVI: dict = {}  # install(ehvi_gradient=True): MOBO's polish optimisers run on bogp.EHVI(input_gradient=True) (empty: the original)
 _SURROGATE_DEFAULTS: dict = {}  # keyword defaults install() gives the device GaussianProcess (e.g. restart_batch)
 
 
@@ -128,15 +129,25 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
     optimiser of the sweep family ("sweep", "sweep-device[-lhs|-sobol]") and a continuous space the criterion is this
     package's `EHVI` (float64, cells from `bogp.pareto`), wrapped exactly as the original wraps the reference's; so it is with
     a forest model (`is_forest_model`: this package's `RandomForest` or the reference's) under "sweep" / "sweep-device" on any
-    space a forest sweep serves.  Every other configuration -- "MIES", the reference's default on mixed spaces, CMA, BFGS --
-    runs the original unchanged."""
+    space a forest sweep serves.  Under `install(ehvi_gradient=True)` a device model on a continuous space is served under "BFGS",
+    "sweep-BFGS" and "sweep-device-BFGS" as well: the criterion is built with `input_gradient=True` and `return_dx` is bound as
+    `BO._create_acquisition` binds it (base.py:463, 489-494: true for "BFGS" only), so that the reference's `argmax_restart`
+    accepts the wrapper.  Every other configuration -- "MIES", the reference's default on mixed spaces, CMA, BFGS without that
+    switch -- runs the original unchanged."""
     if getattr(self, "_optimizer", None) in ("sweep", "sweep-device") and _forest.is_forest_model(getattr(self, "model", None)):
         # a RandomForest fitted on y (N, n_obj) (this package's or the reference's), on any space a forest sweep serves: the
         # forest walk and EHVI are one device pass; what a forest sweep does not take is refused by optim.argmax_restart by name
         criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
         return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
     optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
-    if optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(getattr(self, "search_space", None)):
+    served = is_device_model(getattr(self, "model", None)) and optim.is_continuous(getattr(self, "search_space", None))
+    if served and _EHVI.get("gradient") and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS"):
+        criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float),
+                                     input_gradient=True)  # fmt: skip
+        return_dx = optimizer == "BFGS"
+        return _ORIGINAL["partial_argument"](functools.partial(criterion, return_dx=return_dx), self.search_space.var_name, fixed,
+                                             reduce_output=return_dx)  # fmt: skip
+    if optimizer not in _SWEEPS or not served:
         return _ORIGINAL["mobo"](self, fixed=fixed, **kwargv)
     criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
     return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
@@ -368,7 +379,7 @@ def _dispatching_surrogate(host_cls):
 
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
-            restart_batch: int = None, batch_strategy: str = "topk"):
+            restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -388,9 +399,17 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     the winners before it (a step with fixed variables or constraints, which the believer does not serve, keeps "topk").  The q
     parameters are drawn with the reference's sampler in the reference's order either way.  Under "believer" the reference's
     `MOBO(n_point=q)` proposes q points as well (`optim.ehvi_believer_batch`: EHVI on the variance conditioned on the winners before
-    and on the front their believed means extend); under "topk" its `ask(q)` raises NotImplementedError as in the reference."""
+    and on the front their believed means extend); under "topk" its `ask(q)` raises NotImplementedError as in the reference.
+
+    `ehvi_gradient=True` (an extension: the reference's EHVI has no gradient): the reference's `MOBO` with a device GP on a
+    continuous space runs "BFGS", "sweep-BFGS" and "sweep-device-BFGS" on `bogp.EHVI(input_gradient=True)` -- the closed-form
+    input gradient of `bogp_point_eval_ehvi` and the lock-step polish `bogp_polish_ehvi`.  Without it `MOBO` with those
+    optimisers runs the original."""
     if batch_strategy not in ("topk", "believer"):
         raise ValueError("batch_strategy must be 'topk' or 'believer', not %r" % (batch_strategy,))
+    _EHVI.clear()
+    if ehvi_gradient:
+        _EHVI["gradient"] = True
     _BATCH.clear()
     if batch_strategy != "topk":
         _BATCH["strategy"] = batch_strategy
@@ -470,4 +489,5 @@ def uninstall():
     _ORIGINAL.clear()
     _REROUTE.clear()
     _BATCH.clear()
+    _EHVI.clear()
     _SURROGATE_DEFAULTS.clear()

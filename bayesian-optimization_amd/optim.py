@@ -658,9 +658,13 @@ def argmax_restart(
         # a forest model (any space of Real / Integer / Ordinal / Discrete / Subset / Bool variables): "sweep" and "sweep-device"
         # are served, everything else this package knows is refused with the limitation named
         return _forest.argmax_restart(fcrit, search_space, eval_budget, optimizer, h=h, g=g, masks=fmasks)
-    if is_ehvi(unwrap_criterion(obj_func)[0]) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS") and is_continuous(search_space):
-        raise NotImplementedError("optimizer=%r needs an input gradient, which EHVI does not have: use 'sweep' or "
-                                  "'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip
+    if is_ehvi(fcrit) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS") and is_continuous(search_space):
+        if not getattr(fcrit, "input_gradient", False):
+            raise NotImplementedError("optimizer=%r needs an input gradient, which EHVI does not have: use 'sweep' or "
+                                      "'sweep-device[-lhs|-sobol]' (or build the criterion with input_gradient=True)" % optimizer)  # fmt: skip
+        # EHVI(input_gradient=True): "BFGS" is the loop below on the one-point call (bogp_point_eval_ehvi), the hybrids are
+        # ehvi.sweep(k) + polish_topk (bogp_polish_ehvi); fixed variables, constraints, a lift and several ranks are refused
+        # by name where the single-objective polish hybrids refuse them
     if not ours and (optimizer != "BFGS" or h is not None or g is not None or not is_continuous(search_space)):
         ref = _reference_argmax_restart()
         if ref is None:
@@ -736,7 +740,7 @@ def argmax_restart(
     wait_count = 0
     bounds = np.array(search_space.bounds)
 
-    direct = hasattr(obj_func, "acq_id")  # our criterion object itself; otherwise the reference's one-point wrapper
+    direct = hasattr(obj_func, "acq_id") or is_ehvi(obj_func)  # our criterion object itself; otherwise the reference's one-point wrapper
 
     def neg(x):  # Penalized without constraints (optim/__init__.py:45-52)
         x = np.asarray(x, dtype=float)
@@ -767,7 +771,8 @@ def argmax_restart(
 def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50):
     """Local refinement of `starts` (k, d) inside the box `bounds` (d, 2); returns (points (k, d), values (k,)) with
     values[i] >= the criterion at starts[i].  On the device engine all k starts advance in lock step (`bogp_polish`:
-    one batched value + gradient evaluation per iteration, the optimiser state never leaves the GPU) -- the reference
+    one batched value + gradient evaluation per iteration, the optimiser state never leaves the GPU; an EHVI criterion built
+    with `input_gradient=True` goes to `bogp_polish_ehvi`) -- the reference
     runs its restarts one after the other, one point per call (optim/__init__.py:74-153).  An engine without `polish`
     (the test stand-ins) or a model the fused call does not serve (polynomial trend basis) gets the reference-style
     sequential L-BFGS-B through the one-point call."""
@@ -776,7 +781,13 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
     model = crit.model
     eng = getattr(model, "engine", None)
     fused = getattr(model, "_fused_point_ok", None)
-    if eng is not None and hasattr(eng, "polish") and fused is not None and fused():  # (r05: any d up to BOGP_MAX_DIM; r03-r04 stopped at 64)
+    if is_ehvi(crit) and eng is not None and hasattr(eng, "polish_ehvi"):  # EHVI(input_gradient=True): bogp_polish_ehvi
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        xs, fs, _ = eng.polish_ehvi(model._check_X(starts), bounds[:, 0], bounds[:, 1], crit.cell_lower_bounds, crit.cell_upper_bounds,
+                                    max_evals=int(max_iter))  # fmt: skip
+        return xs, fs
+    if not is_ehvi(crit) and eng is not None and hasattr(eng, "polish") and fused is not None and fused():  # (r05: any d up to BOGP_MAX_DIM; r03-r04 stopped at 64)
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         xs, fs, _ = eng.polish(model._check_X(starts), bounds[:, 0], bounds[:, 1], (crit.acq_id, crit.acq_par()), crit.effective_plugin(),

@@ -522,6 +522,30 @@ int bogp_point_eval_batch(bogp_handle* h, const double* Xb, int B, int q, const 
 int bogp_polish(bogp_handle* h, const double* X0, int B, const double* lo, const double* hi, int acq_id, double acq_par,
                 double plugin, int minimize, int max_evals, double pgtol, double factr, double* Xout, double* fout,
                 int* n_evals);
+/* Expected hypervolume improvement AND its input gradient at B points of the committed m-target model (an extension: the
+ * reference's EHVI has no gradient, analytic.py:99-274), and the lock-step polish on it.  k_point_rhs + k_point_tri run as for
+ * bogp_point_eval_batch (FP64 VALU flavour for every B); k_point_ehvi_finish (csrc/kernels_point_ehvi.hip) then forms the m means
+ * and their gradients from the m columns of gamma, MSE_k = sigma2_k (1 - |V r|^2 + u^2) clipped at 0, sd_k = sqrt(max(MSE_k, 1e-9))
+ * (analytic.py:233) and, over the cells, EHVI = sum_c prod_k f_ck with f = sd (G(a) - G(b)), df/dmu = Phi(-a) - Phi(-b),
+ * df/dsd = phi(a) - phi(b) (a = (l - mu) / sd, b = (u - mu) / sd, G(z) = phi(z) - z Phi(-z); the b terms are 0 for u = +inf).
+ * dsd_k/dx = dMSE_k/dx / (2 sd_k) where MSE_k > 1e-9 and exactly 0 where the clamp or the clip is active.  The value agrees with
+ * bogp_sweep_ehvi's to rounding (the summation orders differ); identical inputs give identical bits, and row b of a B-point call
+ * equals the one-point call on that row whenever both run the same row-block split (csrc/kernels_point.hip: point_tri_geometry).
+ *   m, C, lower, upper   as bogp_sweep_ehvi.  A call whose (m, C, bytes) equal the cells the previous call of these two left on
+ *                        the device skips their check and upload (the BFGS loop makes thousands of one-point calls).
+ *   `point_eval_ehvi`    Xb: B x d (host).  Outputs, row-major, any but ehvi may be NULL: ehvi (B), dehvi (B x d), mu, mse (B x m),
+ *                        dmu, dmse (B x m x d).
+ *   `polish_ehvi`        bogp_polish's loop, state, stop rules and read-back on this evaluation: X0, lo, hi, max_evals, pgtol,
+ *                        factr, Xout, fout, n_evals as there; fout[b] >= EHVI(clip(X0[b])).
+ * BOGP_ERR_INVALID: no committed model; m != n_targets or m < 2; C outside [1, BOGP_MAX_EHVI_CELLS], a non-finite lower bound, a
+ * NaN upper bound or one below its lower bound; a null required pointer; B <= 0; lo > hi; max_evals <= 0.
+ * BOGP_ERR_UNSUPPORTED: the cubic, generalized-exponential and general-nu kernels (no corr_dx); a polynomial basis;
+ * d > BOGP_MAX_DIM; a forest on the handle.  The handle's active target, its candidates and later sweeps are unaffected. */
+int bogp_point_eval_ehvi(bogp_handle* h, const double* Xb, int B, int m, int C, const double* lower, const double* upper,
+                         double* ehvi, double* dehvi, double* mu, double* mse, double* dmu, double* dmse);
+int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const double* lo, const double* hi, int m, int C,
+                     const double* lower, const double* upper, int max_evals, double pgtol, double factr, double* Xout,
+                     double* fout, int* n_evals);
 
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
