@@ -8,6 +8,7 @@ from oracle import gp_oracle as O
 pytestmark = pytest.mark.gpu
 
 import bogp  # noqa: E402
+import producer_cases as PC  # noqa: E402
 from bogp import _lib, integration  # noqa: E402
 from support.mini_driver import MiniParallelBO  # noqa: E402
 
@@ -193,28 +194,25 @@ def test_set_train_reuses_its_buffers_across_a_growing_training_set():
     (256, 10, O.KERNEL_SE, O.MODE_NOISY, False), (257, 3, O.KERNEL_MATERN32, O.MODE_NOISY, True),
     (500, 20, O.KERNEL_ABSEXP, O.MODE_NOISY, False), (512, 10, O.KERNEL_SE, O.MODE_NOISY, True),
     (480, 64, O.KERNEL_MATERN12, O.MODE_NOISY, False),
+    # cubic on the four-wave (Np <= 256, d <= 32) and the eight-wave schedule: rows picked so that every criterion has a clear
+    # winner at every M below (tests/producer_cases.py: DRIVER_CUBIC; asserted by tests/test_producer_cases_host.py)
+    (PC.DRIVER_CUBIC[0][0], PC.DRIVER_CUBIC[0][1], O.KERNEL_CUBIC, O.MODE_NOISY, True),
+    (PC.DRIVER_CUBIC[1][0], PC.DRIVER_CUBIC[1][1], O.KERNEL_CUBIC, O.MODE_NOISY, True),
 ])  # fmt: skip
 def test_fused_small_sweep_equals_the_chunked_schedule_and_the_oracle(N, d, kernel, mode, est):
     """k_sweep_small (N <= 512: producer + contraction + criteria + argmax in one launch, r resident in LDS) against the
     chunked three-kernel schedule of the same library (BOGP_NO_FUSED_SMALL=1) and against the oracle, ragged M included."""
     import os
 
-    rng = np.random.default_rng(N + d)
-    X = rng.uniform(-5, 5, size=(N, d))
-    y = np.sum(X**2, axis=1)
-    y = ((y - y.mean()) / y.std() + 0.05 * rng.standard_normal(N)).reshape(-1, 1)
-    theta = np.full(d, 0.4 / d) * rng.uniform(0.7, 1.3, size=d)
-    par = np.r_[theta, 0.9 if mode == O.MODE_NOISY else 0.98]
-    nv = 1e-6 if mode == O.MODE_NOISY else 0.0
+    rng, X, y, par, nv = PC.driver_model(N, d, mode)  # (shared with the host test of the cubic rows)
     st = O.make_state(par, X, y, kernel, mode, nv, estimate_trend=est, beta=0.0)
     eng = _lib.Engine(0)
     eng.set_train(X, y)
     eng.commit(kernel, mode, par, nv, est, 0.0)
     acq = [(_lib.ACQ_EI, 0.0), (_lib.ACQ_MGFI, 2.0), (_lib.ACQ_UCB, 0.5), (_lib.ACQ_EPSILON_PI, 1e-10)]
     pl = float(y.min())
-    for M in (33, 63, 64, 65, 1000, 4097, 16384 + 700, 16384 + 5000):  # the last two: bulk launch + 32- / 48-candidate tail launch
-        Xs = rng.uniform(-5, 5, size=(M, d))
-        Xs[M // 2] = X[3]  # a candidate on a training point: MSE at nugget level, guards in play
+    for M in PC.DRIVER_MS:  # (33, 63, 64, 65, 1000, 4097, 16384 + 700, 16384 + 5000: the last two a bulk launch + a 32- / 48-candidate tail launch)
+        Xs = PC.driver_candidates(rng, X, M)  # uniform in the box, row M // 2 ON a training point: MSE at nugget level, guards in play
         eng.upload_candidates(Xs)
         out = {}
         for tag, flag in (("fused", "0"), ("chunked", "1")):
