@@ -21,6 +21,7 @@ TREND_CONSTANT, TREND_LINEAR, TREND_QUADRATIC = 0, 1, 2
 SELFTEST_PROFILE, SELFTEST_BESSEL_K, SELFTEST_RGAMMA, SELFTEST_BESSEL_K_PAIRS, SELFTEST_MATERN_NU_PAIRS = range(5)
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
 MAX_Q = 64
+PRUNE_PATH_NONE, PRUNE_PATH_CHUNKS, PRUNE_PATH_ONEPASS, PRUNE_PATH_ONEPASS_FALLBACK = 0, 1, 2, 3  # bogp_last_prune_path
 MAX_TARGETS = 8
 MAX_TOPK = 32
 MAX_BELIEVED = 32  # BOGP_MAX_BELIEVED: q + pending points of one bogp_sweep_believer call
@@ -112,6 +113,8 @@ SIGNATURES = {
     "bogp_last_timing": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_set_prune": (C.c_int, [C.c_void_p, C.c_int]),
     "bogp_last_contracted_rows": (C.c_int, [C.c_void_p, _lp]),
+    "bogp_last_prune_path": (C.c_int, [C.c_void_p, _ip, _lp, _ip]),
+    "bogp_prune_decide": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "bogp_acq_upper_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
     "bogp_flops_per_candidate": (C.c_double, [C.c_void_p]),
@@ -1077,10 +1080,24 @@ class Engine:
         self._check(self._lib.bogp_last_timing(self._h, cast(a), cast(b), cast(c), C.cast(C.byref(n), _ip)))
         return dict(corr_ms=a.value, contract_ms=b.value, acquisition_ms=c.value, n_chunks=n.value)
 
-    def set_prune(self, on: bool = True):
-        """Pruned sweep on / off for this engine (default on): sweep() without return_values skips the variance contraction of
-        candidates that cannot win; winners and values are unchanged."""
-        self._check(self._lib.bogp_set_prune(self._h, int(bool(on))))
+    def set_prune(self, on=True):
+        """Pruned sweep for this engine: sweep() without return_values skips the variance contraction of candidates that cannot win;
+        winners and values are unchanged.  True (the default): automatic -- one bounding pass where it applies, else chunk by chunk;
+        "chunks": always chunk by chunk; False: off."""
+        if isinstance(on, str):
+            if on != "chunks":
+                raise ValueError('set_prune: %r is none of False, True, "chunks"' % (on,))
+            mode = 2
+        else:
+            mode = int(bool(on))
+        self._check(self._lib.bogp_set_prune(self._h, mode))
+
+    def last_prune_path(self):
+        """(path, survivors, rounds) of the last sweep: path is one of PRUNE_PATH_*; survivors behind the pilot and the rounds they
+        were contracted in, for the one-pass paths."""
+        path, rounds, surv = C.c_int(), C.c_int(), C.c_int64()
+        self._check(self._lib.bogp_last_prune_path(self._h, C.cast(C.byref(path), _ip), C.cast(C.byref(surv), _lp), C.cast(C.byref(rounds), _ip)))
+        return int(path.value), int(surv.value), int(rounds.value)
 
     def last_contracted_rows(self) -> int:
         """Candidates that went through the variance contraction in the last predict() / sweep() (waits for a queued sweep)."""

@@ -325,6 +325,28 @@ static void collect_timing(bogp_handle* h) {
   }
   constexpr int EPC = 5;
   h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
+  if (h->timing_onepass) {
+    // a sweep that began on the one-pass flow: its own producer / contraction launches are bracketed one by one (t_spans: kind, begin, end),
+    // the chunks of a fall-back keep their five events, and everything else between the sweep's first and last event -- the small kernels
+    // and the two host waits -- is the rest
+    float tot = 0;
+    (void)hipEventSynchronize(h->ev[(size_t)h->t_total[1]]);
+    (void)hipEventElapsedTime(&tot, h->ev[(size_t)h->t_total[0]], h->ev[(size_t)h->t_total[1]]);
+    for (size_t i = 0; i + 2 < h->t_spans.size(); i += 3) {
+      float a = 0;
+      (void)hipEventElapsedTime(&a, h->ev[(size_t)h->t_spans[i + 1]], h->ev[(size_t)h->t_spans[i + 2]]);
+      (h->t_spans[i] == 0 ? h->t_corr_ms : h->t_contract_ms) += a;
+    }
+    for (int64_t c : h->t_chunks) {
+      float a = 0, b2 = 0;
+      hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
+      (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+      (void)hipEventElapsedTime(&b2, ev[2], ev[3]);
+      h->t_corr_ms += a; h->t_contract_ms += b2;
+    }
+    h->t_acq_ms = tot - h->t_corr_ms - h->t_contract_ms;
+    return;
+  }
   for (int64_t c = 0; c < h->n_chunks; ++c) {
     float a = 0, b2 = 0, c2 = 0;
     hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
@@ -365,6 +387,10 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
   const int Np = h->Np, d = h->d;
   const int64_t M = h->M;
   const int64_t Mpad = ((M + 63) / 64) * 64;
+  h->prune_path = BOGP_PRUNE_PATH_NONE;
+  h->prune_survivors = 0;
+  h->prune_rounds = 0;
+  h->timing_onepass = false;
   size_t chunk_bytes = (size_t)1 << 30;
   if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
   // trend-rows path (k_pack_Vx): the chunk carries Nt - Np extra rows (the hole up to a whole column group, then -f(x*)), the contraction
@@ -512,33 +538,44 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
   int e;
   // Pruned sweep (kernels_prune.hip): only the winners leave this call, so a row whose criteria cannot reach the best
   // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI -- runs as ever.
-  const bool prune = h->prune_on && need_var && q > 0 && !want_out && !want_acq_out && !eh && h->p == 1 && !vx_model && !overlap;
+  const bool prune = h->prune_mode != 0 && need_var && q > 0 && !want_out && !want_acq_out && !eh && h->p == 1 && !vx_model && !overlap;
 #ifndef BOGP_PRUNE_PILOT
 #define BOGP_PRUNE_PILOT 4096  // (1024 / 8192 measured with `make EXTRA=-DBOGP_PRUNE_PILOT=...`: profiles/prune_sweep.txt)
 #endif
   constexpr int64_t PRUNE_PILOT = BOGP_PRUNE_PILOT;  // rows of chunk 0 evaluated exactly to seed the thresholds; a multiple of 256
   static_assert(PRUNE_PILOT % 256 == 0 && PRUNE_PILOT > 0 && PRUNE_PILOT <= 8192, "pilot rows");
   const int64_t Ms = prune ? Mc : 0;  // rows of the survivor buffer: one chunk's, i.e. four chunks' worst case (half a chunk measured: profiles/prune_sweep.txt)
-  const int64_t prune_nbk = Mc / 256 + 1;
+  // One pass: with every candidate resident and a producer that exists without its store, the rows behind the pilot are
+  // bounded a SEGMENT at a time -- as many whole chunks as keep the two partial-sum arrays within 256 MiB -- and only survivors get columns
+  const bool onepass = prune && h->prune_mode == 1 && nchunk > 1 && !h->hXs_lazy && corr_chunk_without_store(h->kernel, 0, h->dXnorm != nullptr);
+  const int64_t seg_rows = onepass ? std::max<int64_t>(1, (((int64_t)256 << 20) / (int64_t)(2 * S * sizeof(double))) / Mc) * Mc : 0;
+  const int64_t seg_stride = std::min<int64_t>(seg_rows, Mpad);       // row stride of a segment's partial sums
+  const int64_t Rmax = std::max<int64_t>(Mc, seg_stride);             // rows one bounding launch may cover
+  const int64_t sidx_cap = seg_stride / 4 + 1;                        // survivor indices kept: a fuller segment falls back
+  const int64_t prune_nbk = Rmax / 256 + 1;
   long long* pctl = nullptr;
-  int64_t *poffsets = nullptr, *pmap = nullptr;
+  int64_t *poffsets = nullptr, *pmap = nullptr, *psidx = nullptr;
   int *psel = nullptr, *pblk_count = nullptr;
   unsigned char* pflags = nullptr;
+  double* pxc = nullptr;
   if (prune) {
     const size_t w_off = PRUNE_CTL_WORDS, w_map = w_off + (size_t)prune_nbk + 1, w_sel = w_map + (size_t)Ms, w_cnt = w_sel + (size_t)(Mc / 4) / 2 + 1,
-                 w_flag = w_cnt + (size_t)prune_nbk / 2 + 1, w_end = w_flag + (size_t)Mc / 8 + 1;
+                 w_flag = w_cnt + (size_t)prune_nbk / 2 + 1, w_sidx = w_flag + (size_t)Rmax / 8 + 1, w_xc = w_sidx + (onepass ? (size_t)sidx_cap : 0),
+                 w_end = w_xc + (onepass ? (size_t)Ms * d : 0);
     if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
     pctl = h->dprune; poffsets = (int64_t*)(h->dprune + w_off); pmap = (int64_t*)(h->dprune + w_map); psel = (int*)(h->dprune + w_sel);
     pblk_count = (int*)(h->dprune + w_cnt); pflags = (unsigned char*)(h->dprune + w_flag);
+    psidx = (int64_t*)(h->dprune + w_sidx); pxc = (double*)(h->dprune + w_xc);  // one pass: survivor indices of a segment | candidate rows of a round
     // the survivor buffer = the second chunk buffer of the two-stream mode
     if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)Nrows * Ms))) return e;
     if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * Ms))) return e;
     if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * Ms))) return e;
   }
   for (int b = 0; b < nbuf; ++b) {
-    if ((e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)Nrows * Mc))) return e;
-    if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * Mc))) return e;
-    if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * Mc))) return e;
+    // (one pass: the chunk buffer is allocated only if a per-chunk path runs after all; the partial sums are a segment's)
+    if (!onepass && (e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)Nrows * Mc))) return e;
+    if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * (onepass ? Rmax : Mc)))) return e;
+    if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * (onepass ? Rmax : Mc)))) return e;
   }
   if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)nJ * (Mc + Ms)))) return e;  // (+ the survivor buffer's sums)
   double* dss_surv = h->dss_part + (size_t)nJ * Mc;
@@ -588,7 +625,10 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
   }
 
   int64_t blk_offset = 0;
-  for (int64_t c = 0; c < nchunk; ++c) {
+  // chunks [c_begin, c_end); pilot_done (a pruned sweep that began on the one-pass flow): thresholds, control words and the pilot rows'
+  // winners are in place -- chunk 0 starts behind the pilot
+  auto run_chunks = [&](int64_t c_begin, int64_t c_end, bool pilot_done) -> int {
+  for (int64_t c = c_begin; c < c_end; ++c) {
     const int b = overlap ? (int)(c & 1) : 0;
     hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
     const int64_t m0 = c * Mc;
@@ -616,7 +656,11 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
       if (stP != st && (el = lazy_wait(h, st))) return el;
     }
     HIPCHK(h, hipEventRecord(ev[0], stP));
-    HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), S, stP));
+    const int64_t skip = pilot_done && c == 0 ? std::min<int64_t>(PRUNE_PILOT, mcount) : 0;  // (a multiple of 64)
+    if (skip > 0) {
+      ca.m0 += skip; ca.rT += skip; ca.mu_part += skip; ca.w_part += skip;
+    }
+    if (Mc_eff > skip) HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)((Mc_eff - skip) / 64), S, stP));
     if (vx) {  // rows Np .. Ne - 1 = 0 (their columns of the factor are zero: any FINITE value would do), rows Ne .. = -f(x*), then zeros
       if (h->vx_Ne > Np) HIPCHK(h, hipMemsetAsync(h->drT[b] + (size_t)Np * Mc, 0, (size_t)(h->vx_Ne - Np) * Mc * sizeof(double), stP));
       HIPCHK(h, launch_trend_rows(h->trend, h->dXs, m0, mcount, Mc_eff, d, Mc, h->dbetav, h->drT[b] + (size_t)h->vx_Ne * Mc, h->p,
@@ -631,7 +675,8 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
       for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
       aa.plugin = plugin; aa.minimize = minimize; aa.M = M; aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
       int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
-      if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
+      if (skip > 0) i0 = skip;
+      else if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
         const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
         hipEvent_t* evp = &h->ev[(size_t)(nchunk * EPC + 1)];
         HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
@@ -665,7 +710,7 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
         prune_pending += rcount / 4;
       }
       // the buffer goes through the contraction behind the last chunk, and whenever the next chunk's quarter might not fit
-      const bool flush = prune_pending > 0 && (c + 1 == nchunk || prune_pending + Mc / 4 > Ms);
+      const bool flush = prune_pending > 0 && (c + 1 == c_end || prune_pending + Mc / 4 > Ms);
       HIPCHK(h, hipEventRecord(ev[2], st));
       // in place or gathered is decided on the device: both contractions are queued, workgroups past the live count return at once
       ContractArgs kf = ka;
@@ -770,13 +815,139 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
       if (el) return el;
     }
   }
+  return BOGP_OK;
+  };  // run_chunks
+
+  if (!onepass) {
+    if ((e = run_chunks(0, nchunk, false))) return e;
+    if (prune) h->prune_path = BOGP_PRUNE_PATH_CHUNKS;
+  } else {
+    // ---- one pass: pilot -> pilot estimate -> per segment: producer without the store, bound, scan, survivor indices -> rounds ----
+    const int64_t P = std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
+    long long* const hcount = reinterpret_cast<long long*>(h->hfit + 3504);  // pinned: the one count the host waits for
+    size_t ev_next = (size_t)(nchunk * EPC + 3);
+    h->t_spans.clear();
+    h->t_chunks.clear();
+    auto mark = [&](int* idx) -> int {
+      hipEvent_t ev1 = get_event(h, ev_next);
+      if (!ev1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+      HIPCHK(h, hipEventRecord(ev1, st));
+      *idx = (int)ev_next++;
+      return BOGP_OK;
+    };
+    // a producer (kind 0) or contraction (kind 1) launch between two events of its own
+    auto timed = [&](int kind, hipError_t (*launch)(const void*, hipStream_t), const void* args) -> int {
+      int a = 0, b2 = 0, e2;
+      if ((e2 = mark(&a))) return e2;
+      HIPCHK(h, launch(args, st));
+      if ((e2 = mark(&b2))) return e2;
+      h->t_spans.push_back(kind); h->t_spans.push_back(a); h->t_spans.push_back(b2);
+      return BOGP_OK;
+    };
+    struct CorrCall { int kernel; CorrArgs a; int nMt, S; };
+    auto corr_fn = [](const void* p, hipStream_t s2) { const CorrCall* c = (const CorrCall*)p; return launch_corr_chunk(c->kernel, c->a, c->nMt, c->S, s2); };
+    auto contract_fn = [](const void* p, hipStream_t s2) { return launch_contract(*(const ContractArgs*)p, s2); };
+    // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
+    auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out) -> int {
+      HIPCHK(h, launch_prune_scan(pblk_count, (rows + 255) / 256, poffsets, rows, -1, pctl, st));
+      if (index_from >= 0) HIPCHK(h, launch_prune_index(pflags, poffsets, rows, index_from, sidx_cap, psidx, st));
+      HIPCHK(h, hipMemcpyAsync(hcount, pctl + PRUNE_CTL_TOTAL, sizeof(long long), hipMemcpyDeviceToHost, st));
+      HIPCHK(h, hipStreamSynchronize(st));
+      *out = *hcount;
+      return BOGP_OK;
+    };
+    CorrCall cc;
+    cc.kernel = h->kernel; cc.S = S;
+    cc.a.Xs = h->dXs; cc.a.M = M; cc.a.m0 = 0; cc.a.Mc = Ms; cc.a.d = d; cc.a.Np = Np; cc.a.nblk_per_split = nblk_per_split;
+    cc.a.sqrt_theta = h->dsqrt_theta; cc.a.XthT = h->dXthT; cc.a.xnorm = h->dXnorm; cc.a.gamma = h->dgamma; cc.a.wvec = h->dw;
+    cc.a.rT = h->drT[1]; cc.a.mu_part = h->dmu_part[1]; cc.a.w_part = h->dw_part[1];
+    ContractArgs kc;  // the survivor buffer through the contraction: the pilot, then every round
+    kc.rT = h->drT[1]; kc.Vp = h->dVp; kc.ss_part = dss_surv; kc.Mc = Ms; kc.nJ = nJ; kc.NJ16 = NJ16; kc.NKP = Nrows / 8;
+    AcqArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.S = S; aa.nJ = nJ_main; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend; aa.sigma2 = h->sigma2; aa.q = q;
+    for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
+    aa.plugin = plugin; aa.minimize = minimize; aa.M = M; aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
+    aa.mu_part = h->dmu_part[1]; aa.w_part = h->dw_part[1]; aa.ss_part = dss_surv; aa.Mc = Ms; aa.m0 = 0;
+    PruneBoundArgs pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.S = S; pb.beta = h->beta; pb.G = h->G; pb.sigma2 = h->sigma2; pb.plugin = plugin; pb.estimate_trend = h->estimate_trend;
+    pb.minimize = minimize; pb.q = q;
+    for (int i = 0; i < q; ++i) { pb.acq_id[i] = acq_id[i]; pb.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
+    pb.best_val = h->dbest_val; pb.flags = pflags; pb.blk_count = pblk_count;
+    int contract_launches = 0;
+    // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
+    auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
+      kc.nMt = (int)((cnt + 63) / 64);
+      int e2 = timed(1, contract_fn, &kc);
+      if (e2) return e2;
+      ++contract_launches;
+      aa.mcount = cnt; aa.map = map;
+      HIPCHK(h, launch_acquisition(aa, st));
+      HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, cnt, q, h->dbest_val, h->dbest_idx, st));
+      return BOGP_OK;
+    };
+    if ((e = mark(&h->t_total[0]))) return e;
+    HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
+    cc.nMt = (int)(P / 64);
+    if ((e = timed(0, corr_fn, &cc))) return e;
+    if ((e = evaluate(P, nullptr))) return e;
+    // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
+    long long pilot_surv = 0;
+    pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
+    HIPCHK(h, launch_prune_bound(pb, st));
+    if ((e = survivors_of(P, -1, &pilot_surv))) return e;
+    if (prune_decide(P, pilot_surv, 1, 0) == BOGP_PRUNE_PATH_CHUNKS) {
+      if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Nrows * Mc))) return e;
+      if ((e = run_chunks(0, nchunk, true))) return e;
+      for (int64_t c = 0; c < nchunk; ++c) h->t_chunks.push_back(c);
+      contract_launches += (int)nchunk;
+      h->prune_path = BOGP_PRUNE_PATH_CHUNKS;
+    } else {
+      h->prune_path = BOGP_PRUNE_PATH_ONEPASS;
+      for (int64_t s0 = 0; s0 < M; s0 += seg_rows) {
+        const int64_t sb = std::max<int64_t>(P, s0), se = std::min<int64_t>(M, s0 + seg_rows), rows = se - sb;
+        if (rows <= 0) continue;
+        CorrCall cs = cc;  // the segment's partial sums, nothing else
+        cs.a.m0 = sb; cs.a.Mc = seg_stride; cs.a.rT = nullptr; cs.a.store = false; cs.a.mu_part = h->dmu_part[0]; cs.a.w_part = h->dw_part[0];
+        cs.nMt = (int)((rows + 63) / 64);
+        if ((e = timed(0, corr_fn, &cs))) return e;
+        pb.mu_part = h->dmu_part[0]; pb.w_part = h->dw_part[0]; pb.Mc = seg_stride; pb.rcount = rows;
+        HIPCHK(h, launch_prune_bound(pb, st));
+        long long surv = 0;
+        if ((e = survivors_of(rows, sb, &surv))) return e;
+        if (prune_decide(P, pilot_surv, rows, surv) == BOGP_PRUNE_PATH_ONEPASS_FALLBACK) {  // (needs ordered candidates: the pilot saw few such rows)
+          if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Nrows * Mc))) return e;
+          const int64_t c0 = sb / Mc, c1 = (se + Mc - 1) / Mc;
+          if ((e = run_chunks(c0, c1, true))) return e;
+          for (int64_t c = c0; c < c1; ++c) h->t_chunks.push_back(c);
+          contract_launches += (int)(c1 - c0);
+          h->prune_path = BOGP_PRUNE_PATH_ONEPASS_FALLBACK;
+          continue;
+        }
+        for (int64_t k0 = 0; k0 < surv; k0 += Ms) {  // rounds of at most one survivor buffer, in the survivors' order
+          const int64_t cnt = std::min<int64_t>(Ms, surv - k0);
+          HIPCHK(h, launch_prune_rows(h->dXs, psidx + k0, cnt, d, pxc, st));
+          CorrCall cr = cc;
+          cr.a.Xs = pxc; cr.a.M = cnt; cr.nMt = (int)((cnt + 63) / 64);
+          if ((e = timed(0, corr_fn, &cr))) return e;
+          if ((e = evaluate(cnt, psidx + k0))) return e;
+          ++h->prune_rounds;
+        }
+        h->prune_survivors += surv;
+      }
+    }
+    if ((e = mark(&h->t_total[1]))) return e;
+    h->timing_onepass = true;
+    h->n_chunks = contract_launches;
+  }
   if (h->hXs_lazy) {  // every row is on its way; once the copy stream is idle the caller's buffer is no longer needed
     const int el = lazy_finish(h);
     if (el) return el;
   }
   // (a pruned sweep kept its running best in dbest_* all along)
   if (q > 0 && !prune) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dbest_val, h->dbest_idx, st));
-  h->n_chunks = (int)nchunk;
+  if (!onepass) h->n_chunks = (int)nchunk;
   h->timing_pending = true;
   h->timing_fused = false;
   h->timing_prune = prune;
@@ -870,8 +1041,21 @@ extern "C" int bogp_last_timing(bogp_handle* h, double* corr_ms, double* contrac
 
 extern "C" int bogp_set_prune(bogp_handle* h, int on) {
   if (!h) return BOGP_ERR_INVALID;
-  h->prune_on = on != 0;
+  if (on < 0 || on > 2) FAIL(h, BOGP_ERR_INVALID, "bogp_set_prune: %d is none of 0 (off), 1 (automatic), 2 (per-chunk path)", on);
+  h->prune_mode = on;
   return BOGP_OK;
+}
+
+extern "C" int bogp_last_prune_path(bogp_handle* h, int* path, int64_t* survivors, int* rounds) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (path) *path = h->prune_path;
+  if (survivors) *survivors = h->prune_survivors;
+  if (rounds) *rounds = h->prune_rounds;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t segment_rows, int64_t segment_survivors) {
+  return prune_decide(pilot_rows, pilot_survivors, segment_rows, segment_survivors);
 }
 
 extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
@@ -881,9 +1065,9 @@ extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
   if (h->prune_used && h->dprune) {  // the count of a pruned sweep never left the device: wait for the sweep, read it
     HIPCHK(h, hipSetDevice(h->device));
     long long n = 0;
-    HIPCHK(h, hipMemcpyAsync(&n, h->dprune + 4, sizeof(n), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&n, h->dprune + PRUNE_CTL_CONTRACTED, sizeof(n), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    *rows = (int64_t)n;
+    *rows = (int64_t)n + h->prune_survivors;  // (+ the rows the one-pass rounds contracted: the host knows those)
   }
   return BOGP_OK;
 }

@@ -119,7 +119,10 @@ struct bogp_handle {
   int64_t *dblk_idx = nullptr, *dbest_idx = nullptr;
   unsigned int* dcounter = nullptr;  // arrival ticket of k_sweep_small's last workgroup (zero between launches)
   // pruned sweep (kernels_prune.hip; bogp_set_prune): control words | block offsets | index map | selected rows | block counts | flags
-  bool prune_on = true;
+  int prune_mode = 1;            // bogp_set_prune: 0 off, 1 automatic (one pass where it applies), 2 the per-chunk path
+  int prune_path = 0;            // BOGP_PRUNE_PATH_* of the last sweep; survivors behind the pilot and rounds of its one-pass segments
+  int64_t prune_survivors = 0;
+  int prune_rounds = 0;
   long long* dprune = nullptr;
   size_t prune_cap = 0;
   bool prune_used = false;       // the last sweep pruned: its contracted-row count is on the device (dprune[4])
@@ -251,6 +254,10 @@ struct bogp_handle {
   double t_corr_ms = 0, t_contract_ms = 0, t_acq_ms = 0;
   int n_chunks = 0;
   bool timing_pending = false, timing_fused = false;  // event times not read back yet / of the one-launch small-N sweep
+  bool timing_onepass = false;   // ... of a sweep that began on the one-pass flow: t_spans = (kind, begin event, end event) of each producer (0) /
+  std::vector<int> t_spans;      // contraction (1) launch of its own, t_chunks = the chunks a fall-back ran, t_total = first / last event
+  std::vector<int64_t> t_chunks;
+  int t_total[2] = {0, 0};
   bool timing_prune = false;  // ... of a pruned sweep: bound / compaction / gather sit between a chunk's events [1] and [2], the pilot's events behind the chunks'
 };
 

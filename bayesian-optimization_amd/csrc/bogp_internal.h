@@ -22,6 +22,7 @@ struct CorrArgs {
   const double* gamma;       // Np (zero padded)
   const double* wvec;        // Np (zero padded): L^-T Ft, or zeros for simple kriging
   double* rT;                // [Np][Mc] correlation chunk, n-major
+  bool store = true;         // false: r is not written and rT is not touched (may be null) -- only where corr_chunk_without_store()
   double* mu_part;           // [S][Mc]
   double* w_part;            // [S][Mc]
   // polynomial trend with few columns, fused into the producer (k_corr_chunk<K, PV>): pv = 0 (off) / 16 / 24 / 32 >= p
@@ -31,6 +32,7 @@ struct CorrArgs {
   double* t_part = nullptr;      // [S][pv][Mc] slice sums of W^T r
 };
 int corr_trend_columns(int p);  // the PV instantiation serving p trend columns, 0 if none does
+bool corr_chunk_without_store(int kernel, int pv, bool have_xnorm);  // launch_corr_chunk has a producer without the store for this call
 
 struct ContractArgs {
   const double* rT;   // [Np][Mc]
@@ -82,6 +84,7 @@ struct AcqArgs {
 // the pruned sweep (kernels_prune.hip): bound every row of a chunk region against the running best, compact the survivors in order,
 // gather their columns into the survivor buffer, and merge the block records of an acquisition launch into the running best
 constexpr int PRUNE_CTL_WORDS = 8;  // device control words: see kernels_prune.hip
+constexpr int PRUNE_CTL_CONTRACTED = 4, PRUNE_CTL_TOTAL = 5;  // ... the two the host reads: rows contracted on the per-chunk path; survivors of the region bounded last
 struct PruneBoundArgs {
   const double* mu_part;  // [S][Mc] (offset to the region's first row)
   const double* w_part;   // [S][Mc]
@@ -112,6 +115,20 @@ hipError_t launch_prune_init(long long* ctl, double* best_val, int64_t* best_idx
 hipError_t launch_prune_bound(const PruneBoundArgs& a, hipStream_t st);
 hipError_t launch_prune_scan(const int* blk_count, int64_t nblk, int64_t* offsets, int64_t rcount, int64_t cap, long long* ctl, hipStream_t st);
 hipError_t launch_prune_gather(const PruneGatherArgs& a, hipStream_t st);
+// one pass: the global indices m0 + i of the flagged rows, in order, into sidx[0 .. cap); rows sidx[0 .. count) of Xs -> Xc (count x d)
+hipError_t launch_prune_index(const unsigned char* flags, const int64_t* offsets, int64_t rcount, int64_t m0, int64_t cap, int64_t* sidx,
+                              hipStream_t st);
+hipError_t launch_prune_rows(const double* Xs, const int64_t* sidx, int64_t count, int d, double* Xc, hipStream_t st);
+
+// The two host decisions of the one-pass pruned sweep (exported as bogp_prune_decide; the values are BOGP_PRUNE_PATH_* of include/bogp.h).
+// A pilot of which more than an eighth survives its own thresholds sends the whole sweep to the per-chunk path (1); a segment of which
+// more than a quarter survives falls back to it alone (3); otherwise the survivors are contracted in rounds (2).  Shares of exactly
+// 1/8 and 1/4 stay on the one-pass side; products, not quotients, so that the edges are exact.
+inline int prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t segment_rows, int64_t segment_survivors) {
+  if (8 * pilot_survivors > pilot_rows) return 1;
+  if (4 * segment_survivors > segment_rows) return 3;
+  return 2;
+}
 // (value, index) records of the first ceil(rows / 256) blocks -> merged into best_val / best_idx; rows = *live if live, else count
 hipError_t launch_prune_update(const double* blk_val, const int64_t* blk_idx, int64_t stride, const long long* live, int64_t count, int q,
                                double* best_val, int64_t* best_idx, hipStream_t st);

@@ -175,171 +175,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                    const double* __restrict__ gamma, const double* __restrict__ wvec,
                                                    double* __restrict__ rT, double* __restrict__ mu_part, double* __restrict__ w_part,
                                                    CorrDims a) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int d = a.d;
-  const int KS = (d + 3) >> 2;       // k-steps of 4 dimensions; rows d .. 4 KS - 1 of the tile are zero
-  double* xs = smem;                 // [4 KS][64] theta-scaled candidate tile, k-major
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int g = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t mc0 = (int64_t)blockIdx.x * 64;
-  const int64_t mg0 = a.m0 + mc0;
-  for (int idx = tid; idx < 64 * d; idx += 256) {
-    const int row = idx / d, k = idx - row * d;
-    const int64_t gm = mg0 + row;
-    const double v = gm < a.M ? Xs[gm * d + k] : 0.0;
-    xs[k * 64 + row] = v * sqrt_theta[k];
-  }
-  for (int idx = tid + 64 * d; idx < 64 * 4 * KS; idx += 256) xs[idx] = 0.0;
-  __syncthreads();
-  const double pexp = kernel_exponent<KERNEL>(sqrt_theta, d);
-  const int li = lane & 15, lk = lane >> 4;
-  double na[4];  // |a_m|^2 of this lane's four candidates m = 16 t + li, summed in dimension order (as k_scale_transpose sums |b_n|^2)
-#pragma unroll
-  for (int t = 0; t < 4; ++t) na[t] = 0.0;
-  for (int k = 0; k < d; ++k) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const double v = xs[k * 64 + 16 * t + li];
-      na[t] = __builtin_fma(v, v, na[t]);
-    }
-  }
-  const int nb0 = blockIdx.y * a.nblk_per_split * 32;
-  const int nb1 = min(a.Np, nb0 + a.nblk_per_split * 32);
-  typedef double d4t __attribute__((ext_vector_type(4)));
-  double mu[4] = {0.0, 0.0, 0.0, 0.0}, wd[4] = {0.0, 0.0, 0.0, 0.0};
-  // (r06, from k_contract16d: every global address of the loop is a wave-uniform base + a lane-constant 32-bit offset, kept opaque inside the loop so that
-  // hipcc selects the `v_offset, s[base]` form -- hoisted, each access cost a v_lshl_add_u64 on the FP64 pipe that the MFMAs and the profile's arithmetic share)
-  unsigned offA = (unsigned)(((size_t)lk * a.Np + li) * sizeof(double));   // XthT: row lk of a k-step, training point li of the block
-  unsigned offN = (unsigned)(lk * sizeof(double));                          // xnorm / gamma / w: training point 4 c + lk
-  unsigned offR = (unsigned)(((size_t)lk * a.Mc + li) * sizeof(double));   // rT: row 4 c + lk of the block, candidate 16 t + li
-  const char* const xthB = reinterpret_cast<const char*>(XthT);
-  const char* const xnB = reinterpret_cast<const char*>(xnorm);
-  const char* const gaB = reinterpret_cast<const char*>(gamma);
-  const char* const wvB = reinterpret_cast<const char*>(wvec);
-  char* const rtB = reinterpret_cast<char*>(rT + mc0);
-  for (int n0 = nb0 + 16 * g; n0 < nb1; n0 += 64) {
-#define BOGP_OPQ(o_) asm("" : "+v"(o_))  /* (beside EVERY access: the zero-extension must sit in the access's own basic block to be matched) */
-    d4t acc[4];
-    // a_m . b_n over the dimensions, four at a time
-    {
-      const char* __restrict__ apb = xthB + (size_t)n0 * sizeof(double);
-      const double* bp = xs + lk * 64 + li;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = (d4t){0.0, 0.0, 0.0, 0.0};
-      constexpr int KB = 8;  // A fragments (128-byte runs of XthT: L2 round trips) requested together: 5.5 -> 5.1 ms at C3, 17.5 -> 14.3 ms at C5
-      for (int ks0 = 0; ks0 < KS; ks0 += KB) {
-        double av[KB];
-#pragma unroll
-        for (int u = 0; u < KB; ++u)
-        {
-          BOGP_OPQ(offA);
-          av[u] = (4 * (ks0 + u) + lk) < d ? *reinterpret_cast<const double*>(apb + (size_t)4 * (ks0 + u) * a.Np * sizeof(double) + offA) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < KB; ++u) {
-          if (ks0 + u < KS) {
-            const int ks = ks0 + u;
-            const double b0 = bp[ks * 256], b1 = bp[ks * 256 + 16], b2 = bp[ks * 256 + 32], b3 = bp[ks * 256 + 48];
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[0]) : "v"(av[u]), "v"(b0));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[1]) : "v"(av[u]), "v"(b1));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[2]) : "v"(av[u]), "v"(b2));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[3]) : "v"(av[u]), "v"(b3));
-          }
-        }
-      }
-    }
-    // this lane's four training rows n0 + 4 c + lk: norm, gamma, w (the loads fly while the matrix pipe drains)
-    double nbv[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      BOGP_OPQ(offN);
-      nbv[c] = *reinterpret_cast<const double*>(xnB + (size_t)(n0 + 4 * c) * sizeof(double) + offN);
-    }
-    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-#pragma unroll
-    for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(acc[t]));
-    double s2[4][4];
-    bool near = false;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const double nab = na[t] + nbv[c];
-        const double v = __builtin_fma(-2.0, acc[t][c], nab);
-        s2[t][c] = v;
-        near |= v * 64.0 < nab;
-      }
-    if (__builtin_expect(__ballot(near) != 0ull, 0)) {
-      // difference form, kernel A's operations in kernel A's order, for all 16 values of the lane in ONE loop over the dimensions (compact code:
-      // sixteen unrolled per-value loops cost 40 VGPRs and an occupancy step); only the FLAGGED values take it, so that r(x*_m, x_n) never
-      // depends on which other pairs share the wave
-      const double* __restrict__ xr = XthT + n0 + lk;
-#pragma unroll
-      for (int th = 0; th < 4; th += 2) {  // two candidate tiles at a time: eight accumulators
-        double e[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) e[t][c] = 0.0;
-        const double* xc = xs + 16 * th + li;
-#pragma unroll 1
-        for (int k = 0; k < d; ++k) {
-          double xcv[2], xrv[4];
-#pragma unroll
-          for (int t = 0; t < 2; ++t) xcv[t] = xc[k * 64 + 16 * t];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) xrv[c] = xr[(size_t)k * a.Np + 4 * c];
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const double df = xcv[t] - xrv[c];
-              e[t][c] = __builtin_fma(df, df, e[t][c]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (s2[th + t][c] * 64.0 < na[th + t] + nbv[c]) s2[th + t][c] = e[t][c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      char* __restrict__ rrow = rtB + (size_t)(n0 + 4 * c) * a.Mc * sizeof(double);
-      BOGP_OPQ(offN);
-      const double gv = *reinterpret_cast<const double*>(gaB + (size_t)(n0 + 4 * c) * sizeof(double) + offN);
-      const double wv = *reinterpret_cast<const double*>(wvB + (size_t)(n0 + 4 * c) * sizeof(double) + offN);
-      BOGP_OPQ(offR);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double r = corr_profile<KERNEL>(s2[t][c], pexp);
-        *reinterpret_cast<double*>(rrow + 16 * t * sizeof(double) + offR) = r;
-        mu[t] = __builtin_fma(r, gv, mu[t]);
-        wd[t] = __builtin_fma(r, wv, wd[t]);
-      }
-    }
-  }
-  // reduce over the 4 waves x 4 row groups of a lane (fixed order) -> partial sums of this slice
-  __syncthreads();
-  double* red = smem;  // [2][16][64]
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    red[(4 * g + lk) * 64 + 16 * t + li] = mu[t];
-    red[1024 + (4 * g + lk) * 64 + 16 * t + li] = wd[t];
-  }
-  __syncthreads();
-  if (tid < 64) {
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      s0 += red[j * 64 + tid];
-      s1 += red[1024 + j * 64 + tid];
-    }
-    mu_part[(size_t)blockIdx.y * a.Mc + mc0 + tid] = s0;
-    w_part[(size_t)blockIdx.y * a.Mc + mc0 + tid] = s1;
-  }
+#define BOGP_CORR_STORE 1
+#include "corr_mfma_body.inc"
+#undef BOGP_CORR_STORE
+}
+// the same producer without the store of r (the one-pass pruned sweep, kernels_prune.hip: the bounding pass needs mu_part / w_part only)
+template <int KERNEL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_corr_mfma_sums(const double* __restrict__ Xs, const double* __restrict__ sqrt_theta,
+                                                   const double* __restrict__ XthT, const double* __restrict__ xnorm,
+                                                   const double* __restrict__ gamma, const double* __restrict__ wvec,
+                                                   double* __restrict__ mu_part, double* __restrict__ w_part, CorrDims a) {
+#define BOGP_CORR_STORE 0
+#include "corr_mfma_body.inc"
+#undef BOGP_CORR_STORE
 }
 
 #undef BOGP_OPQ
@@ -966,12 +814,17 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
 // (kernel A' for the squared-distance kernels without a fused trend; against kernel A everywhere: profiles/r05_corr_mfma_ab.txt)
 static bool corr_mfma_enabled() { return true; }
 
+// the kernels launch_corr_chunk serves with kernel A' -- the producer that also exists without the store of r (CorrArgs::store = false)
+static bool corr_sqdist_kernel(int kernel) {
+  return kernel == BOGP_KERNEL_SE || kernel == BOGP_KERNEL_MATERN12 || kernel == BOGP_KERNEL_MATERN32 || kernel == BOGP_KERNEL_MATERN52;
+}
+bool corr_chunk_without_store(int kernel, int pv, bool have_xnorm) { return corr_sqdist_kernel(kernel) && pv == 0 && have_xnorm && corr_mfma_enabled(); }
+
 hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipStream_t st) {
   dim3 grid((unsigned)nMt, (unsigned)S);
   // (the general-nu Matern kernel is a squared-distance kernel too, but its profile -- K_nu: hundreds of operations a pair -- dwarfs the distance and
   // needs 270 VGPRs: it stays on kernel A, which holds it without spills)
-  const bool sqdist = kernel == BOGP_KERNEL_SE || kernel == BOGP_KERNEL_MATERN12 || kernel == BOGP_KERNEL_MATERN32 || kernel == BOGP_KERNEL_MATERN52;
-  if (sqdist && a.pv == 0 && a.xnorm && corr_mfma_enabled()) {
+  if (corr_chunk_without_store(kernel, a.pv, a.xnorm != nullptr)) {
     const int KS = (a.d + 3) / 4;
     const size_t shm = (size_t)max(4 * KS * 64, 2048) * sizeof(double);  // <= 160 KB up to d = 320, like kernel A
     CorrDims dm{a.M, a.m0, a.Mc, a.d, a.Np, a.nblk_per_split, a.wld};
@@ -985,6 +838,25 @@ hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipS
     hipLaunchKernelGGL((k_corr_mfma<K>), grid, 256, shm, st, a.Xs, a.sqrt_theta, a.XthT, a.xnorm, a.gamma, a.wvec, a.rT, a.mu_part,   \
                        a.w_part, dm);                                                                                                 \
   } while (0)
+#define BOGP_LAUNCH_CORR_SUMS(K)                                                                                                      \
+  do {                                                                                                                                \
+    if (shm > 64 * 1024) {                                                                                                            \
+      hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_corr_mfma_sums<K>),                                        \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                                      \
+      if (e_ != hipSuccess) return e_;                                                                                                \
+    }                                                                                                                                 \
+    hipLaunchKernelGGL((k_corr_mfma_sums<K>), grid, 256, shm, st, a.Xs, a.sqrt_theta, a.XthT, a.xnorm, a.gamma, a.wvec, a.mu_part,    \
+                       a.w_part, dm);                                                                                                 \
+  } while (0)
+    if (!a.store) {
+      switch (kernel) {
+        case BOGP_KERNEL_SE: BOGP_LAUNCH_CORR_SUMS(BOGP_KERNEL_SE); break;
+        case BOGP_KERNEL_MATERN12: BOGP_LAUNCH_CORR_SUMS(BOGP_KERNEL_MATERN12); break;
+        case BOGP_KERNEL_MATERN32: BOGP_LAUNCH_CORR_SUMS(BOGP_KERNEL_MATERN32); break;
+        default: BOGP_LAUNCH_CORR_SUMS(BOGP_KERNEL_MATERN52); break;
+      }
+      return hipGetLastError();
+    }
     switch (kernel) {
       case BOGP_KERNEL_SE: BOGP_LAUNCH_CORR_MFMA(BOGP_KERNEL_SE); break;
       case BOGP_KERNEL_MATERN12: BOGP_LAUNCH_CORR_MFMA(BOGP_KERNEL_MATERN12); break;
@@ -992,8 +864,10 @@ hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipS
       default: BOGP_LAUNCH_CORR_MFMA(BOGP_KERNEL_MATERN52); break;
     }
 #undef BOGP_LAUNCH_CORR_MFMA
+#undef BOGP_LAUNCH_CORR_SUMS
     return hipGetLastError();
   }
+  if (!a.store) return hipErrorInvalidValue;  // (kernel A always stores: corr_chunk_without_store() is false for it)
   size_t shm = (size_t)(max(64 * a.d, 512) + (a.pv > 0 ? 32 * 64 : 0)) * sizeof(double);
   CorrDims dm{a.M, a.m0, a.Mc, a.d, a.Np, a.nblk_per_split, a.wld};
   // the candidate tile is 64 x d doubles of dynamic LDS: above the 64 KB default (d > 128) the kernel has to be allowed

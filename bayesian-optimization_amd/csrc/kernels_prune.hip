@@ -13,9 +13,18 @@
 //   k_prune_gather   the survivors' columns of rT -> the survivor buffer (a bit copy)
 //   k_prune_update   the block records of an acquisition launch (in place, or of the flushed buffer) merged into the running best
 // The host never learns a count: every count lives in the control words below, k_contract16d / k_acquisition / the kernels here
-// read the one they need and workgroups beyond it return at once.  No atomic append: two runs give the same buffers.  A pruned
+// read the one they need and workgroups beyond it return at once.  (The one-pass flow below is the exception: it reads two counts.)
+// No atomic append: two runs give the same buffers.  A pruned
 // row is strictly worse than a value an evaluated row attained, so the winners (lowest index on ties, a NaN first) are those of
 // the full sweep, and their values are the full sweep's bits: rows of the contraction are independent of each other.
+//
+// One pass (run_sweep): where every candidate is resident and the producer exists without its store, the rows behind
+// the pilot are bounded in ONE launch per segment -- the producer leaves only its partial sums -- and only the survivors' correlation
+// columns are ever produced:
+//   k_prune_scan     with cap < 0: the exclusive scan and the survivor count (PC_TOTAL), which the host reads
+//   k_prune_index    survivors, in their original order -> their global indices
+//   k_prune_rows     a round of at most one survivor buffer: the survivors' candidate rows -> a compact candidate array, which the
+//                    storing producer, k_contract16d, k_acquisition (through the index map) and k_prune_update then take with exact grids
 #include "bogp_device.h"
 #include "bogp_internal.h"
 
@@ -24,7 +33,9 @@ namespace bogp {
 // control words (long long): [0] survivors in the buffer, [1] rows of the current region to contract in place (0: gathered),
 // [2] survivors of the current region to gather (0: in place), [3] their first slot in the buffer, [4] rows that went through the
 // contraction in this sweep
-enum { PC_BUF = 0, PC_INPLACE = 1, PC_GATHER = 2, PC_BASE = 3, PC_CONTRACTED = 4 };
+// [5] one pass: survivors of the region bounded last
+enum { PC_BUF = 0, PC_INPLACE = 1, PC_GATHER = 2, PC_BASE = 3, PC_CONTRACTED = 4, PC_TOTAL = 5 };
+static_assert(PC_TOTAL == PRUNE_CTL_TOTAL && PC_CONTRACTED == PRUNE_CTL_CONTRACTED && PC_TOTAL < PRUNE_CTL_WORDS, "control words");
 
 __global__ void k_prune_init(long long* ctl, double* best_val, int64_t* best_idx, int q, long long pilot_rows) {
   const int t = threadIdx.x;
@@ -72,6 +83,7 @@ __global__ __launch_bounds__(256) void k_prune_bound(PruneBoundArgs a) {
 
 // offsets[b] = survivors in workgroups 0 .. b - 1; then the region's decision.  `cap` = rows of the survivor buffer (the host
 // flushes it before a region whose quarter might not fit; a region that would not fit is contracted in place all the same).
+// cap < 0 (one pass): no decision here -- the count goes to PC_TOTAL for the host, nothing else changes.
 __global__ __launch_bounds__(1024) void k_prune_scan(const int* __restrict__ blk_count, int64_t nblk, int64_t* __restrict__ offsets,
                                                      int64_t rcount, int64_t cap, long long* __restrict__ ctl) {
   __shared__ int64_t s[1024];
@@ -95,6 +107,10 @@ __global__ __launch_bounds__(1024) void k_prune_scan(const int* __restrict__ blk
   }
   if (t == 1023) {
     const int64_t total = s[1023];
+    if (cap < 0) {
+      ctl[PC_TOTAL] = total;
+      return;
+    }
     const int64_t have = ctl[PC_BUF];
     const bool inplace = 4 * total > rcount || have + total > cap;
     ctl[PC_INPLACE] = inplace ? rcount : 0;
@@ -126,6 +142,32 @@ __global__ __launch_bounds__(256) void k_prune_compact(PruneGatherArgs a) {
     a.mu_s[(size_t)s * a.Ms + dst] = a.mu_part[(size_t)s * a.Mc + i];
     a.w_s[(size_t)s * a.Ms + dst] = a.w_part[(size_t)s * a.Mc + i];
   }
+}
+
+// one pass: k_prune_compact's enumeration, the global indices alone; `cap` entries (a region with more survivors falls back: its list is not read)
+__global__ __launch_bounds__(256) void k_prune_index(const unsigned char* __restrict__ flags, const int64_t* __restrict__ offsets, int64_t rcount,
+                                                     int64_t m0, int64_t cap, int64_t* __restrict__ sidx) {
+  __shared__ int s_cnt[4];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool keep = i < rcount && flags[i] != 0;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(keep);
+  if (lane == 0) s_cnt[w] = __popcll(bal);
+  __syncthreads();
+  if (!keep) return;
+  int before = __popcll(bal & ((1ull << lane) - 1ull));
+  for (int k = 0; k < w; ++k) before += s_cnt[k];
+  const int64_t k = offsets[blockIdx.x] + before;
+  if (k < cap) sidx[k] = m0 + i;
+}
+
+// one pass: rows sidx[0 .. count) of the candidates -> Xc (count x d, row-major)
+__global__ __launch_bounds__(256) void k_prune_rows(const double* __restrict__ Xs, const int64_t* __restrict__ sidx, int64_t count, int d,
+                                                    double* __restrict__ Xc) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count * d) return;
+  const int64_t row = e / d;
+  Xc[e] = Xs[sidx[row] * d + (e - row * d)];
 }
 
 // workgroup (x, y): survivors [64 x, 64 x + 64) of the region, rows [32 y, 32 y + 32) of rT; 64 consecutive doubles per store
@@ -216,6 +258,17 @@ hipError_t launch_prune_gather(const PruneGatherArgs& a, hipStream_t st) {
   const int64_t max_g = a.rcount / 4;  // a region with more survivors is contracted in place
   if (max_g > 0)
     hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)((max_g + 63) / 64), (unsigned)((a.Np + 31) / 32)), 256, 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_index(const unsigned char* flags, const int64_t* offsets, int64_t rcount, int64_t m0, int64_t cap, int64_t* sidx,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(k_prune_index, dim3((unsigned)((rcount + 255) / 256)), 256, 0, st, flags, offsets, rcount, m0, cap, sidx);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_rows(const double* Xs, const int64_t* sidx, int64_t count, int d, double* Xc, hipStream_t st) {
+  hipLaunchKernelGGL(k_prune_rows, dim3((unsigned)((count * d + 255) / 256)), 256, 0, st, Xs, sidx, count, d, Xc);
   return hipGetLastError();
 }
 

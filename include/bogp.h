@@ -586,8 +586,27 @@ int bogp_last_timing(bogp_handle* h, double* corr_ms, double* contract_ms, doubl
  * A bogp_sweep without acq_out returns only its q winners, so a candidate whose criteria cannot reach the best values found so
  * far even with the most optimistic variance (|L^-1 r|^2 = 0) skips the N^2 contraction (constant basis, chunked path; DESIGN.md
  * section 5.22).  Winners and their values are those of the full sweep, bit for bit.  on = 0 switches the pruning off for this
- * handle (default: on): every row is then contracted, as for bogp_predict / bogp_sweep_topk / acq_out, which never prune.        */
+ * handle: every row is then contracted, as for bogp_predict / bogp_sweep_topk / acq_out, which never prune.  on = 1 (the default)
+ * is automatic: a sweep of more than one chunk over fully resident candidates (not a lazy upload), with a squared-distance kernel,
+ * bounds all rows behind the pilot in ONE pass -- a producer launch that stores no correlations -- and produces correlation columns
+ * for the survivors alone; it waits on the host twice (the pilot's estimate, the survivor count of a segment), also where the sweep
+ * itself is queued.  Where that does not apply, or the pilot's own rows show that little can be pruned, it is the per-chunk path,
+ * which on = 2 forces.                                                                                                          */
 int bogp_set_prune(bogp_handle* h, int on);
+
+/* Which way the LAST sweep pruned: path = BOGP_PRUNE_PATH_*; for the one-pass paths, survivors = the rows behind the pilot that the
+ * bound let through and that were contracted in `rounds` rounds of at most one chunk's rows (0 and 0 otherwise).  Any output may
+ * be NULL.                                                                                                                      */
+#define BOGP_PRUNE_PATH_NONE 0             /* nothing was pruned (option off, value outputs, one launch, ...)      */
+#define BOGP_PRUNE_PATH_CHUNKS 1           /* bound, compaction and gather chunk by chunk                          */
+#define BOGP_PRUNE_PATH_ONEPASS 2          /* one bounding pass per segment, exact producer for survivors only     */
+#define BOGP_PRUNE_PATH_ONEPASS_FALLBACK 3 /* ... of which a segment with too many survivors ran chunk by chunk    */
+int bogp_last_prune_path(bogp_handle* h, int* path, int64_t* survivors, int* rounds);
+
+/* The two host decisions of the one-pass flow, no device and no handle (tests/test_prune_decide_host.py): BOGP_PRUNE_PATH_CHUNKS if
+ * more than an eighth of the pilot's rows survive the pilot's own thresholds, else BOGP_PRUNE_PATH_ONEPASS_FALLBACK if more than a
+ * quarter of the segment's rows survive, else BOGP_PRUNE_PATH_ONEPASS.                                                           */
+int bogp_prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t segment_rows, int64_t segment_survivors);
 
 /* Rows that went through the contraction in the LAST bogp_predict / bogp_sweep call (M without pruning; waits for a queued sweep). */
 int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows);
