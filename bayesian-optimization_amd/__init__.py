@@ -11,6 +11,8 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
                                  bogp.forest: packing, mixed-space sweep; built on first access, sklearn imported lazily)
   bogp.optim.argmax_restart      <-> bayes_optim.acquisition.optim.argmax_restart (+ optimizer="sweep")
   bogp.trend                     <-> bayes_optim.surrogate.trend
+  bogp.thompson                  posterior sample paths (GaussianProcess.sampling_posterior, stubs in the reference) and
+                                 bogp.thompson_batch: q-point proposals by Thompson sampling
   bogp.install(bayes_optim)      re-points the reference's three extension points, ParallelBO's q-criterion loop and
                                  MOBO's acquisition (EHVI under the sweep family)
   bogp._lib.Engine               ctypes binding of libbogp.so (include/bogp.h)
@@ -20,10 +22,10 @@ a gfx950 device (or without the built library) raises -- there is no CPU fallbac
 """
 __version__ = "0.1.0"
 
-from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto  # noqa: E402,F401
+from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto, thompson  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
 from .acquisition import EHVI, EI, MGFI, PI, UCB, EpsilonPI  # noqa: E402,F401
-from .optim import argmax_restart, batch_argmax, believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated  # noqa: E402,F401
+from .optim import argmax_restart, batch_argmax, believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
 from .integration import install, uninstall  # noqa: E402,F401
 from .lift import Lift  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401

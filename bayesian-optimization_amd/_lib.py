@@ -25,6 +25,7 @@ PRUNE_PATH_NONE, PRUNE_PATH_CHUNKS, PRUNE_PATH_ONEPASS, PRUNE_PATH_ONEPASS_FALLB
 MAX_TARGETS = 8
 MAX_TOPK = 32
 MAX_BELIEVED = 32  # BOGP_MAX_BELIEVED: q + pending points of one bogp_sweep_believer call
+MAX_PATHS, MAX_FEATURES = 16, 16384  # BOGP_MAX_PATHS / BOGP_MAX_FEATURES: paths and features of one bogp_sweep_thompson call
 LIFT_MAX_R, LIFT_MAX_RD = 64, 4096  # BOGP_LIFT_MAX_R / BOGP_LIFT_MAX_RD: reduced dimensions and r x D of a lift
 MAX_EHVI_CELLS = 65536  # BOGP_MAX_EHVI_CELLS: cells one bogp_sweep_ehvi call takes
 COMM_ID_BYTES = 128
@@ -71,6 +72,8 @@ SIGNATURES = {
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_thompson": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_thompson_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_ehvi_grid_cells": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
     "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
                                            _dp, _dp]),
@@ -659,6 +662,47 @@ class Engine:
         self._check(self._lib.bogp_believer_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(b), _dp),
                                                  C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, believer_ms=b.value, n_passes=n.value)
+
+    def sweep_thompson(self, draw, minimize=True, k: int = 1, conditioned=True, return_values=False):
+        """q sample paths of the committed model over the current candidates (bogp_sweep_thompson), each with its k best rows.
+        `draw`: the arrays of `bogp.thompson.draw` -- omega (L, d), phase (L,), weights (L, q), eps (N, q) or None.  Returns a dict:
+        best_val (q, k) in the criterion's sign (-path when minimising), best_idx (q, k), best_x (q, k, d) -- rank 0 is the argmax,
+        slots beyond M are (-inf, -1) -- coef = (gt (N, q), bt (q,)) and, with return_values, paths (q, M).  What the library
+        refuses as unsupported (a mode, kernel, trend, ...) raises NotImplementedError with its message."""
+        omega, phase, weights = _f64(draw.omega), _f64(draw.phase), _f64(draw.weights)
+        eps = None if draw.eps is None else _f64(draw.eps)
+        if weights.ndim != 2 or omega.ndim != 2 or omega.shape != (len(phase), self.d) or weights.shape[0] != len(phase):
+            raise ValueError("a draw holds omega (L, %d), phase (L,) and weights (L, q)" % self.d)
+        L, q = weights.shape
+        if eps is not None and eps.shape != (self.N, q):
+            raise ValueError("eps must have shape (%d, %d)" % (self.N, q))
+        k = int(k)
+        best = np.empty((q, k))
+        idx = np.empty((q, k), dtype=np.int64)
+        bx = np.empty((q, k, self.d))
+        paths = np.empty((q, self.M)) if return_values else None
+        coef = np.empty((self.N + 1, q))
+        self._last_q, self._last_topk = -1, (-1, -1)
+        try:
+            self._check(self._lib.bogp_sweep_thompson(self._h, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps), int(bool(conditioned)),
+                                                      int(bool(minimize)), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths),
+                                                      _ptr(coef)))  # fmt: skip
+        except BogpError as e:
+            if e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = dict(best_val=best, best_idx=idx, best_x=bx, coef=(coef[:-1].copy(), coef[-1].copy()))
+        if return_values:
+            out["paths"] = paths
+        return out
+
+    def thompson_last(self) -> dict:
+        """Producer time, time of the draw at the training rows with its solves, k_thompson time over the candidates (ms) and the
+        chunks of the last sweep_thompson (bogp_thompson_last)."""
+        c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_thompson_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(p), _dp),
+                                                 C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
 
     def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):
         """Kriging-believer batch under EHVI over the current candidates (bogp_sweep_believer_ehvi): step j maximises EHVI on the m

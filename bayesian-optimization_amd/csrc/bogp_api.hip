@@ -122,6 +122,7 @@ extern "C" void bogp_destroy(bogp_handle* h) {
   point_release(h);
   batch_release(h);
   believer_release(h);
+  thompson_release(h);
   free_train(h);
   (void)hipStreamSynchronize(h->stream2);
   if (h->stream_upd) (void)hipStreamSynchronize(h->stream_upd);

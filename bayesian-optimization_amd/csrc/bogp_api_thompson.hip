@@ -1,0 +1,257 @@
+// bogp_api_thompson.hip -- the C ABI of libbogp.so (include/bogp.h) for Thompson-sampling batches: bogp_sweep_thompson, q sample paths
+// of the committed surrogate over the current candidates, each with its k best rows.  The reference declares
+// GaussianProcess.sampling_prior / sampling_posterior and leaves both as `pass` (gpr.py:312-316); the paths here have the mean and
+// MSE of its predictor (gpr.py:486-510) by pathwise conditioning on a random-Fourier-feature draw that the HOST supplies.
+//   1  s = z(X) + sqrt(sigma2 (diag(R) - 1)) E      k_thompson's feature part over the N training rows (mode 0)
+//   2  A = V^T (V s) = R^-1 s                       the kernels of believed_solve, N x q; with w = R^-1 1 (the committed L^-T Ft)
+//      b_j = w . s_j / sum(w) (ordinary kriging, else 0), g_j = A_j - b_j w -- N q numbers, on the host
+//   3  per candidate chunk: the producer with its store, then k_thompson (kernels_thompson.hip)
+//   4  the argmax / top-k tail of bogp_sweep_topk
+// No contraction launch anywhere.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/bogp.h"
+#include "bogp_handle.h"
+#include "bogp_internal.h"
+
+using namespace bogp;
+
+void bogp::thompson_release(bogp_handle* h) {
+  dfree(h->dth_small);
+  h->th_small_cap = 0;
+  for (auto e : h->th_ev) (void)hipEventDestroy(e);
+  h->th_ev.clear();
+}
+
+namespace {
+
+hipEvent_t th_event(bogp_handle* h, size_t i) {
+  while (h->th_ev.size() <= i) {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    h->th_ev.push_back(e);
+  }
+  return h->th_ev[i];
+}
+
+bool all_finite(const double* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* omega, const double* phase, const double* weights,
+                                   const double* eps, int conditioned, int minimize, int k, double* best_val, int64_t* best_idx,
+                                   double* best_x, double* paths_out, double* coef_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_thompson";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior paths to draw", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (q < 1 || q > BOGP_MAX_PATHS) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_PATHS);
+  if (L < 16 || L > BOGP_MAX_FEATURES || L % 16 != 0)
+    FAIL(h, BOGP_ERR_INVALID, "%s: L = %d: a multiple of 16 in [16, %d] is required", who, L, BOGP_MAX_FEATURES);
+  if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
+  if (!omega || !phase || !weights || !best_val || !best_idx)
+    FAIL(h, BOGP_ERR_INVALID, "%s: omega, phase, weights, best_val and best_idx must be non-null", who);
+  const int d = h->d, N = h->N, Np = h->Np;
+  if (!all_finite(omega, (size_t)L * d)) FAIL(h, BOGP_ERR_INVALID, "%s: omega has a non-finite entry", who);
+  if (!all_finite(phase, (size_t)L)) FAIL(h, BOGP_ERR_INVALID, "%s: phase has a non-finite entry", who);
+  if (!all_finite(weights, (size_t)L * q)) FAIL(h, BOGP_ERR_INVALID, "%s: weights has a non-finite entry", who);
+  if (eps && !all_finite(eps, (size_t)N * q)) FAIL(h, BOGP_ERR_INVALID, "%s: eps has a non-finite entry", who);
+  if (h->mode != BOGP_MODE_NOISELESS)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: %s mode: the reference pairs an unscaled r(x) with a rescaled R there (gpr.py:949-979), which is no Gaussian process's conditional law",
+         who, h->mode == BOGP_MODE_NOISY ? "noisy" : "noise-estimating");
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (h->n_t != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: one target only (the committed model has %d)", who, h->n_t);
+  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: no spectral draw is defined for the %s kernel", who, h->kernel == BOGP_KERNEL_CUBIC ? "cubic" : "generalized-exponential");
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  int rc;
+  if ((rc = candidates_ready(h))) return rc;
+  invalidate_sweep_results(h);  // dacq_out and the records are overwritten
+  const int64_t M = h->M;
+  const int N4 = (N + 3) & ~3;
+
+  // ---- geometry: the producer's chunks as the believer plans them (chunk bytes, slices of 8 x 32 training rows)
+  size_t chunk_bytes = (size_t)1 << 30;
+  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
+  const int64_t Mpad = ((M + 63) / 64) * 64;
+  int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Np * sizeof(double)) / 64) * 64;
+  Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
+  const int64_t nchunk = (M + Mc - 1) / Mc, nblk_total = (M + 63) / 64 + nchunk, nblk256 = (M + 255) / 256;
+  const int S = (Np / 32 + 7) / 8;
+  const bool store = k > 1 || paths_out != nullptr;
+
+  // dth_small: omega (L d) | phase (L) | W (16 L) | -g (16 N4) | s (N q) | V s (N q) | R^-1 s (N q)
+  const size_t n_small = (size_t)L * d + L + (size_t)16 * L + (size_t)16 * N4 + (size_t)3 * N * q;
+  if ((rc = ensure(h, &h->dth_small, &h->th_small_cap, n_small))) return rc;
+  double* domega = h->dth_small;
+  double* dphase = domega + (size_t)L * d;
+  double* dW = dphase + L;
+  double* dng = dW + (size_t)16 * L;
+  double* ds = dng + (size_t)16 * N4;
+  double* dvs = ds + (size_t)N * q;
+  double* da = dvs + (size_t)N * q;
+  if (conditioned) {
+    if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * Mc))) return rc;
+    if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)S * Mc))) return rc;
+    if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)S * Mc))) return rc;
+  }
+  if ((rc = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
+  if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
+  if ((rc = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
+  if ((rc = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
+  if (store)
+    if ((rc = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return rc;
+
+  // ---- the draw: W scaled by sqrt(2 sigma2 / L) and padded to 16 columns
+  const double scale = std::sqrt(2.0 * h->sigma2 / (double)L);
+  std::vector<double> hW((size_t)16 * L, 0.0);
+  for (int l = 0; l < L; ++l)
+    for (int j = 0; j < q; ++j) hW[(size_t)l * 16 + j] = scale * weights[(size_t)l * q + j];
+  HIPCHK(h, hipMemcpyAsync(domega, omega, (size_t)L * d * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dphase, phase, (size_t)L * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dW, hW.data(), hW.size() * sizeof(double), hipMemcpyHostToDevice, st));
+
+  ThompsonArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.d = d; ta.L = L; ta.N = N; ta.q = q; ta.omega = domega; ta.phase = dphase; ta.W = dW;
+
+  size_t nev = 0;
+  auto event = [&]() -> hipEvent_t { return th_event(h, nev++); };
+  hipEvent_t s0 = event(), s1 = event();
+  if (!s0 || !s1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  HIPCHK(h, hipEventRecord(s0, st));
+  std::vector<double> hb(16, 0.0), hg((size_t)N * q, 0.0);
+  if (conditioned) {
+    // ---- 1: the draw at the training rows, plus what the nugget adds to an observation
+    ta.X = h->dX; ta.row0 = 0; ta.mcount = N; ta.mode = 0; ta.minimize = 0; ta.vals = ds; ta.M = N;
+    HIPCHK(h, launch_thompson(ta, st));
+    std::vector<double> hs((size_t)N * q), ha((size_t)N * q), hw((size_t)N);
+    HIPCHK(h, hipMemcpyAsync(hs.data(), ds, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    const double nug = h->sigma2 * (h->R_diag - 1.0);
+    if (eps && nug > 0.0) {
+      const double sn = std::sqrt(nug);
+      for (int j = 0; j < q; ++j)
+        for (int n = 0; n < N; ++n) hs[(size_t)j * N + n] += sn * eps[(size_t)n * q + j];
+      HIPCHK(h, hipMemcpyAsync(ds, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    // ---- 2: R^-1 s for the q columns, then b and g on the host
+    HIPCHK(h, launch_gemm(0, 0, N, q, N, 1.0, h->dV, h->ldr, ds, N, 0.0, dvs, N, st, 1));   // V s
+    HIPCHK(h, launch_gemm(1, 0, N, q, N, 1.0, h->dV, h->ldr, dvs, N, 0.0, da, N, st, 2));   // V^T (V s)
+    HIPCHK(h, hipMemcpyAsync(ha.data(), da, ha.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    double wsum = 0.0;
+    for (int n = 0; n < N; ++n) wsum += hw[n];  // 1^T R^-1 1
+    std::vector<double> hng((size_t)16 * N4, 0.0);
+    for (int j = 0; j < q; ++j) {
+      double ws = 0.0;
+      for (int n = 0; n < N; ++n) ws += hw[n] * hs[(size_t)j * N + n];
+      hb[j] = h->estimate_trend ? ws / wsum : 0.0;
+      for (int n = 0; n < N; ++n) {
+        const double g = h->estimate_trend ? ha[(size_t)j * N + n] - hb[j] * hw[n] : ha[(size_t)j * N + n];
+        hg[(size_t)n * q + j] = g;
+        hng[(size_t)n * 16 + j] = -1 * g;
+      }
+    }
+    HIPCHK(h, hipMemcpyAsync(dng, hng.data(), hng.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));  // (hng leaves scope)
+  }
+  HIPCHK(h, hipEventRecord(s1, st));
+  if (coef_out) {
+    memcpy(coef_out, hg.data(), (size_t)N * q * sizeof(double));
+    for (int j = 0; j < q; ++j) coef_out[(size_t)N * q + j] = hb[j];
+  }
+
+  // ---- 3: the candidate chunks
+  ta.X = h->dXs; ta.mode = conditioned ? 2 : 1; ta.minimize = minimize ? 1 : 0; ta.vals = store ? h->dacq_out : nullptr; ta.M = M;
+  ta.rT = h->drT[0]; ta.ld = Mc; ta.ngt = dng; ta.mu_part = h->dmu_part[0]; ta.S = S; ta.beta = h->beta;
+  for (int j = 0; j < 16; ++j) ta.bt[j] = hb[j];
+  ta.blk_val = h->dblk_val; ta.blk_idx = h->dblk_idx; ta.nblk_total = nblk_total;
+  std::vector<size_t> ev_chunk;
+  int64_t blk_offset = 0;
+  for (int64_t c = 0; c < nchunk; ++c) {
+    const int64_t m0 = c * Mc, mcount = std::min<int64_t>(Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
+    ev_chunk.push_back(nev);
+    hipEvent_t c0 = event(), c1 = event(), c2 = event();
+    if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(h, hipEventRecord(c0, st));
+    if (conditioned) {
+      CorrArgs ca;
+      ca.Xs = h->dXs; ca.M = M; ca.m0 = m0; ca.Mc = Mc; ca.d = d; ca.Np = Np; ca.nblk_per_split = 8;
+      ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
+      ca.rT = h->drT[0]; ca.mu_part = h->dmu_part[0]; ca.w_part = h->dw_part[0];
+      HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), S, st));
+    }
+    HIPCHK(h, hipEventRecord(c1, st));
+    ta.row0 = m0; ta.mcount = mcount; ta.blk_offset = blk_offset;
+    HIPCHK(h, launch_thompson(ta, st));
+    HIPCHK(h, hipEventRecord(c2, st));
+    blk_offset += (mcount + 63) / 64;
+  }
+
+  // ---- 4: the winners.  Rank 0 alone is the reduction of the kernel's records; k ranks are bogp_sweep_topk's passes over the stored values
+  if (k == 1)
+    HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dtopk_val, h->dtopk_idx, st));
+  else
+    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+  HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (paths_out) HIPCHK(h, hipMemcpyAsync(paths_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  if (paths_out && minimize)  // stored in the criterion's sign: back to the path's own
+    for (size_t i = 0; i < (size_t)q * M; ++i) paths_out[i] = -1 * paths_out[i];
+  for (int i = 0; i < q * k; ++i)
+    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
+      best_val[i] = -INFINITY;
+      best_idx[i] = -1;
+    }
+  if (best_x) {
+    for (int i = 0; i < q * k; ++i) {
+      double* dst = best_x + (size_t)i * d;
+      if (best_idx[i] < 0 || best_idx[i] >= M) {
+        for (int t = 0; t < d; ++t) dst[t] = NAN;
+        continue;
+      }
+      HIPCHK(h, hipMemcpyAsync(dst, h->dXs + (size_t)best_idx[i] * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
+
+  h->th_corr_ms = h->th_paths_ms = 0;
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, s0, s1);
+  h->th_solve_ms = ms;
+  for (size_t e : ev_chunk) {
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, h->th_ev[e], h->th_ev[e + 1]);
+    (void)hipEventElapsedTime(&b, h->th_ev[e + 1], h->th_ev[e + 2]);
+    h->th_corr_ms += a;
+    h->th_paths_ms += b;
+  }
+  h->th_chunks = (int)nchunk;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_thompson_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (corr_ms) *corr_ms = h->th_corr_ms;
+  if (solve_ms) *solve_ms = h->th_solve_ms;
+  if (paths_ms) *paths_ms = h->th_paths_ms;
+  if (n_chunks) *n_chunks = h->th_chunks;
+  return BOGP_OK;
+}

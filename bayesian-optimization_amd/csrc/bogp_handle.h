@@ -16,6 +16,7 @@ void comm_release(bogp_handle* h);   // bogp_comm.hip: destroys an owned communi
 void point_release(bogp_handle* h);  // bogp_point.hip: frees the point-evaluation buffers
 void batch_release(bogp_handle* h);  // bogp_batch.hip: frees the batched-likelihood staging and workspaces
 void believer_release(bogp_handle* h);  // bogp_api_believer.hip: frees the Kriging-believer arrays and events
+void thompson_release(bogp_handle* h);  // bogp_api_thompson.hip: frees the draw's buffer and the events
 std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: the handles a batch of one-evaluation calls is dealt over
 // bogp_point.hip: posterior, input-gradients and q criteria of B points through k_point_rhs + k_point_tri.  `Xb` is a HOST
 // array (B x d).  Outputs (host, any may be null): mu, mse (B), dmu, dmse (B x d), acq (B x q), dacq (B x q x d).
@@ -164,6 +165,13 @@ struct bogp_handle {
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
   // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
   double bel_ehvi_ms = 0;  // k_believer_ehvi of the last bogp_sweep_believer_ehvi
+
+  // Thompson-sampling batches (bogp_api_thompson.hip)
+  double* dth_small = nullptr;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight
+  size_t th_small_cap = 0;
+  std::vector<hipEvent_t> th_ev;
+  double th_corr_ms = 0, th_solve_ms = 0, th_paths_ms = 0;  // of the last bogp_sweep_thompson: producer, draw at X + solves, k_thompson
+  int th_chunks = 0;
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

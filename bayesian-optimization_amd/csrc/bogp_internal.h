@@ -223,6 +223,32 @@ struct BelieverEhviArgs {
 };
 hipError_t launch_believer_ehvi(const BelieverEhviArgs& a, hipStream_t st);
 
+// q sample paths over a chunk (kernels_thompson.hip): path_j(x) = mu(x) + z_j(x) - r(x) . g_j - b_j with the random-Fourier-feature draw
+// z_j(x) = sum_l W[l][j] cos(omega_l . x + phase_l), one np.argmax record per path and 64 rows
+struct ThompsonArgs {
+  const double* X;        // rows, row-major with d columns: the candidates, or the training points (mode 0)
+  int64_t row0, mcount;   // first row of this launch; rows it serves
+  int d, L, N, q;         // L: features, a multiple of 16; q <= 16 paths
+  const double* omega;    // [L][d]
+  const double* phase;    // [L]
+  const double* W;        // [L][16] weights times sqrt(2 sigma2 / L), zero columns from q on
+  int mode;               // 0: z alone; 1: beta + z (prior paths); 2: the conditioned paths (everything below is read)
+  const double* rT;       // [Np][ld] the chunk's correlation columns
+  int64_t ld;             // Mc: stride of rT and mu_part
+  const double* ngt;      // [ceil(N / 4) * 4][16] MINUS g, zero padded rows and columns
+  const double* mu_part;  // [S][ld] the producer's slice sums of r . gamma
+  int S;
+  double beta;
+  double bt[16];          // b_j
+  int minimize;           // the value is negated: records and stored values are in the criterion's sign
+  double* vals;           // [q][M] at the global row, or null
+  int64_t M;
+  double* blk_val;        // [q][nblk_total], or null (no records)
+  int64_t* blk_idx;
+  int64_t blk_offset, nblk_total;
+};
+hipError_t launch_thompson(const ThompsonArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

@@ -394,19 +394,22 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
 
     `restart_batch` = R: device models built through the re-pointed name get `restart_batch=R` unless the call names its own.
 
-    `batch_strategy` = "topk" | "believer": how the fused `ParallelBO` step keeps its q points apart.  "topk" (default): each
+    `batch_strategy` = "topk" | "believer" | "thompson": how the fused `ParallelBO` step keeps its q points apart.  "topk" (default): each
     criterion falls back through its top-k; "believer": `optim.believer_batch` -- criterion j sees the variance conditioned on
     the winners before it (a step with fixed variables or constraints, which the believer does not serve, keeps "topk").  The q
     parameters are drawn with the reference's sampler in the reference's order either way.  Under "believer" the reference's
     `MOBO(n_point=q)` proposes q points as well (`optim.ehvi_believer_batch`: EHVI on the variance conditioned on the winners before
     and on the front their believed means extend); under "topk" its `ask(q)` raises NotImplementedError as in the reference.
+    "thompson": `optim.thompson_batch` -- one posterior sample path per point, each optimised over the candidates; the criteria
+    supply model and direction only.  Fixed variables and constraints keep "topk" as under the believer; a model Thompson
+    sampling refuses (a nugget or noise estimate, a polynomial trend, ...) raises NotImplementedError naming it.
 
     `ehvi_gradient=True` (an extension: the reference's EHVI has no gradient): the reference's `MOBO` with a device GP on a
     continuous space runs "BFGS", "sweep-BFGS" and "sweep-device-BFGS" on `bogp.EHVI(input_gradient=True)` -- the closed-form
     input gradient of `bogp_point_eval_ehvi` and the lock-step polish `bogp_polish_ehvi`.  Without it `MOBO` with those
     optimisers runs the original."""
-    if batch_strategy not in ("topk", "believer"):
-        raise ValueError("batch_strategy must be 'topk' or 'believer', not %r" % (batch_strategy,))
+    if batch_strategy not in ("topk", "believer", "thompson"):
+        raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()
     if ehvi_gradient:
         _EHVI["gradient"] = True

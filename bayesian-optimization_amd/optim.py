@@ -366,13 +366,20 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
     `strategy`: "topk" (the above) or "believer" -- `believer_batch`: criterion j is maximised on the variance conditioned on
     the winners before it, and a row that is a winner does not compete again: the q points differ by construction.  `history`
     and `k` are not used then: a winner `np.isclose` to an evaluated point is left to the caller's padding, as the last
-    fall-back above is."""
+    fall-back above is.  "thompson" -- `thompson_batch`: one posterior sample path per criterion, each minimised (maximised) over
+    the candidates as the criteria's `minimize` says; the criteria supply model and direction, their kind is not used, and
+    `history` and `k` keep their meaning above."""
+    if strategy == "thompson":
+        criteria = list(criteria)
+        return thompson_batch(criteria[0].model, search_space, eval_budget, len(criteria), Xs=Xs, design=design, seed=seed, history=history,
+                              k=k, minimize=criteria[0].minimize, masks=masks, values=values, h=h, g=g, group=group, rank=rank, world=world,
+                              criteria=criteria)  # fmt: skip
     if strategy == "believer":
         xs, fs = believer_batch(list(criteria), search_space, eval_budget, Xs=Xs, design=design, seed=seed, masks=masks, values=values,
                                 h=h, g=g, group=group, rank=rank, world=world)
         return xs, fs
     if strategy != "topk":
-        raise ValueError("strategy must be 'topk' or 'believer', not %r" % (strategy,))
+        raise ValueError("strategy must be 'topk', 'believer' or 'thompson', not %r" % (strategy,))
     if _forest.is_forest_model(criteria[0].model):
         _forest.check_optimizer("sweep", h, g, masks)
         _forest._one_rank(group, rank, world)
@@ -480,6 +487,73 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     out = eng.sweep_believer([(c.acq_id, c.acq_par()) for c in criteria], plugin, c0.minimize, pending=pend,
                              believe_plugin=believe_plugin)
     return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+
+
+def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
+                   Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None, k: int = 8,
+                   minimize: bool = True, lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None,
+                   group=None, rank=None, world=None, criteria=None):
+    """A q-point proposal by Thompson sampling (`bogp_sweep_thompson`): q posterior sample paths of `model` (`bogp.thompson`:
+    pathwise conditioning on `n_features` random Fourier features), each minimised -- maximised with `minimize=False` -- over the
+    candidates.  ONE producer pass and one streaming pass serve 16 paths; the variance contraction never runs.  The candidates
+    are set as in `believer_batch` (`eval_budget` rows of `search_space.sample`, the rows `Xs`, or a `design` drawn on the
+    device).  Every path returns its `k` best rows and takes the first one that no earlier path took and that is not `np.isclose`
+    to a row of `history` (`batch_argmax`'s rule), so the q proposals are q distinct rows.  More than 16 paths run in calls of 16
+    with seeds derived from `seed` (`thompson.batch_seeds`).  Returns (xopt: tuple of q lists, fopt: tuple of q floats) in
+    `batch_argmax`'s format; fopt is the path's value at its proposal.
+    Refused (NotImplementedError): a forest model, EHVI / several targets, a lift, fixed variables, constraints, polynomial
+    trends, more than one rank, the cubic and generalized-exponential kernels, the noisy and noise-estimating modes."""
+    from . import thompson as _th
+
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
+    if criteria is not None and any(is_ehvi(c) for c in criteria):
+        raise NotImplementedError("EHVI / several targets have no Thompson batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no Thompson batches")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no Thompson batches")
+    if h is not None or g is not None:
+        raise NotImplementedError("constraints have no Thompson batches")
+    _th.state_of(model)  # the model's own refusals: not fitted, mode, trend, targets, kernel
+    q, k = int(q), int(k)
+    if q < 1:
+        raise ValueError("q = %d: Thompson sampling proposes at least one point" % q)
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
+    if design is not None:
+        dseed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), dseed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    hist = None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
+    sizes = [min(_th.MAX_PATHS, q - a) for a in range(0, q, _th.MAX_PATHS)]
+    chosen_x, chosen_f, taken = [], [], set()
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, k + len(taken))))  # a later call also steps over the rows the earlier ones took
+        out = eng.sweep_thompson(_th.draw(model, qb, n_features, sd), minimize=minimize, k=kk)
+        for c in range(qb):
+            pick = None
+            for r in range(kk):
+                gi = int(out["best_idx"][c, r])
+                if gi < 0 or gi in taken:
+                    continue
+                if hist is not None and np.any(np.all(np.isclose(hist, out["best_x"][c, r]), axis=1)):
+                    continue
+                pick = r
+                break
+            if pick is None:  # every fall-back exhausted: keep the argmax (the caller's duplicate check will pad)
+                pick = 0
+            taken.add(int(out["best_idx"][c, pick]))
+            chosen_x.append(np.asarray(out["best_x"][c, pick], dtype=float).tolist())
+            v = float(out["best_val"][c, pick])
+            chosen_f.append(-v if minimize else v)
+    return tuple(chosen_x), tuple(chosen_f)
 
 
 def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,

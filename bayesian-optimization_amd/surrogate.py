@@ -967,11 +967,18 @@ class GaussianProcess:
         dmu, dmse = self.engine.gradient(x[0])
         return dmu.reshape(-1, 1), dmse.reshape(-1, 1)
 
-    def sampling_prior(self, X):  # stubs in the reference as well (gpr.py:312-316)
-        pass
+    def sampling_prior(self, X, n_samples=1, n_features=1024, seed=None):
+        """`n_samples` prior paths beta + z(x) at the rows of X: (len(X), n_samples).  A stub in the reference (gpr.py:312-313)."""
+        from . import thompson
 
-    def sampling_posterior(self, X):
-        pass
+        return thompson.sample(self, X, n_samples, n_features, seed, conditioned=False)
+
+    def sampling_posterior(self, X, n_samples=1, n_features=1024, seed=None):
+        """`n_samples` posterior sample paths at the rows of X: (len(X), n_samples), mean `predict`'s mu and variance its MSE.  A
+        stub in the reference (gpr.py:315-316); `bogp.thompson` has the construction and what it refuses."""
+        from . import thompson
+
+        return thompson.sample(self, X, n_samples, n_features, seed, conditioned=True)
 
     def Hessian(self, x):
         """Hessian of the posterior mean at one row (gpr.py:578-598): (d, d).  As in the reference it exists for the

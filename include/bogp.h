@@ -330,6 +330,44 @@ int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, const double* 
                         double* best_x, double* pivots, double* acq_out, double* mse_out);
 int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* believer_ms, int* n_passes);
 
+/* ---- sweep: Thompson-sampling batches ------------------------------------------------------------------
+ * q sample paths of the committed surrogate over the current candidates, each with its k best rows.  The reference declares
+ * GaussianProcess.sampling_prior / sampling_posterior and leaves both as `pass` (gpr.py:312-316).  By pathwise conditioning
+ * (Matheron's rule on a random-Fourier-feature prior draw; Wilson et al. 2020), with R, r(x), sigma2, gamma, beta the committed
+ * model's (mu(x) = beta + r(x) . gamma, MSE(x) = sigma2 (1 - r^T R^-1 r + u^2), gpr.py:486-510) and L features shared by the paths:
+ *   z_j(x)    = sqrt(2 sigma2 / L) sum_l W[l][j] cos(omega_l . x + phase_l)          the prior draw
+ *   s_j       = z_j(X) + sqrt(sigma2 (diag(R) - 1)) E[:, j]                           what it "observes" at the training rows
+ *   b_j       = 1^T R^-1 s_j / (1^T R^-1 1) under ordinary kriging, 0 under simple kriging
+ *   g_j       = R^-1 (s_j - b_j 1)
+ *   path_j(x) = mu(x) + z_j(x) - r(x) . g_j - b_j                                     conditioned = 1
+ *   path_j(x) = beta + z_j(x)                                                         conditioned = 0 (a prior path)
+ * With omega drawn from the kernel's spectral density, phase ~ U[0, 2 pi) and W, E standard normal, E[path] = mu and
+ * Var[path] = MSE.  ALL of the draw is an input, made on the host (bogp.thompson.draw); the library never sees a seed.  In the
+ * noiseless mode -- the one served -- diag(R) = 1, so eps is validated and has no effect.
+ *   q (1 .. BOGP_MAX_PATHS), L (a multiple of 16 in [16, BOGP_MAX_FEATURES])
+ *   omega (L x d), phase (L), weights (L x q), eps (N x q or NULL = zeros): HOST arrays, row-major
+ *   minimize   1: each path is minimised (its criterion is -path), 0: maximised;  k (1 .. BOGP_MAX_TOPK) ranks per path
+ *   best_val, best_idx (q x k): the criterion values and rows by bogp_sweep's rule (first maximum, NaN maximal), rank 0 first;
+ *              slots beyond M are (-inf, -1).  best_x (q x k x d, may be NULL; NaN rows for such slots)
+ *   paths_out (q x M, may be NULL): the paths' own values;  coef_out ((N + 1) x q, may be NULL): the rows of g, then b
+ * Per call: the draw at the training rows and one N x q solve with the committed factor; per candidate chunk the correlation
+ * producer and k_thompson (kernels_thompson.hip: 8 N bytes and L cos per candidate for all q paths).  The N^2 variance
+ * contraction never runs.  Every sum's order depends on N, d and L alone: the outputs are bit-identical for any BOGP_CHUNK_MB,
+ * and path j does not depend on q.
+ * BOGP_ERR_INVALID: no committed model, no candidates, q, L or k out of range, a null required array, a non-finite entry in
+ * omega / phase / weights / eps.  BOGP_ERR_UNSUPPORTED: the noisy and noise-estimating modes (the reference pairs an unscaled
+ * r(x) with a rescaled R there, gpr.py:949-979: no Gaussian process has that mean / MSE pair as its conditional law), a
+ * polynomial trend basis, several targets, the cubic and generalized-exponential kernels (no spectral draw), a lift on the
+ * handle, a forest, a communicator of more than one rank.  The handle's model, candidates and later sweeps are unaffected.
+ * `thompson_last`: of the last call, the time of the producer launches, of the draw at the training rows with its solves, and
+ * of k_thompson over the candidates in ms, and the chunks; any pointer may be NULL.                                        */
+#define BOGP_MAX_PATHS 16
+#define BOGP_MAX_FEATURES 16384 /* L: a multiple of 16, >= 16 */
+int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* omega, const double* phase, const double* weights,
+                        const double* eps, int conditioned, int minimize, int k, double* best_val, int64_t* best_idx,
+                        double* best_x, double* paths_out, double* coef_out);
+int bogp_thompson_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
+
 /* ---- sweep: Kriging-believer batches for EHVI -------------------------------------------------------------
  * q proposals per call for a multi-objective run -- what the reference names and leaves open: `class MOBO: """EHVI with
  * Kriging believer"""` stands over `# TODO: implement the Kriging believer strategy` (mobo.py:168-178), and MOBO(n_point > 1)
