@@ -118,6 +118,7 @@ SIGNATURES = {
     "bogp_last_contracted_rows": (C.c_int, [C.c_void_p, _lp]),
     "bogp_last_prune_path": (C.c_int, [C.c_void_p, _ip, _lp, _ip]),
     "bogp_prune_decide": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "bogp_sweep_chunk_rows": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "bogp_acq_upper_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
     "bogp_flops_per_candidate": (C.c_double, [C.c_void_p]),

@@ -50,24 +50,6 @@ hipEvent_t bel_event(bogp_handle* h, size_t i) {
   return h->bel_ev[i];
 }
 
-struct Plan {  // chunking of the candidate passes: the producer's geometry of run_sweep for a constant-trend model
-  int64_t Mc, nchunk, nblk_total;
-  int S;
-};
-
-Plan make_plan(int64_t M, int Np) {  // (run_sweep's for p = 1: chunk bytes, slices of 8 x 32 training rows)
-  Plan pl;
-  size_t chunk_bytes = (size_t)1 << 30;
-  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
-  const int64_t Mpad = ((M + 63) / 64) * 64;
-  int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Np * sizeof(double)) / 64) * 64;
-  pl.Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
-  pl.nchunk = (M + pl.Mc - 1) / pl.Mc;
-  pl.nblk_total = (M + 63) / 64 + pl.nchunk;
-  pl.S = (Np / 32 + 7) / 8;
-  return pl;
-}
-
 struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point's correlations with the believed rows, those rows
   double *dpt, *dr, *dvr, *da, *dkk, *drows;
   static size_t doubles(int d, int N) { return (size_t)d + 3 * (size_t)N + 2 * BOGP_MAX_BELIEVED + (size_t)BOGP_MAX_BELIEVED * d; }
@@ -127,15 +109,6 @@ int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const doub
   return BOGP_OK;
 }
 
-// the producer of one chunk for a believer pass (run_sweep's arguments for a constant-trend model)
-hipError_t believer_corr_chunk(bogp_handle* h, const Plan& pl, int64_t m0, int64_t Mc_eff) {
-  CorrArgs ca;
-  ca.Xs = h->dXs; ca.M = h->M; ca.m0 = m0; ca.Mc = pl.Mc; ca.d = h->d; ca.Np = h->Np; ca.nblk_per_split = 8;
-  ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
-  ca.rT = h->drT[0]; ca.mu_part = h->dmu_part[0]; ca.w_part = h->dw_part[0];
-  return launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), pl.S, h->stream);
-}
-
 // times of the solves and of the chunks' producer / k_believer launches, once everything is complete
 void believer_times(bogp_handle* h, const std::vector<size_t>& ev_solve, const std::vector<size_t>& ev_chunk) {
   h->bel_corr_ms = h->bel_solve_ms = h->bel_pass_ms = 0;
@@ -165,12 +138,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
     FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: q = %d, n_pending = %d: q >= 1 and q + n_pending <= %d", q, n_pending, BOGP_MAX_BELIEVED);
   if (!acq_id || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: acq_id, best_val and best_idx must be non-null");
   if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: n_pending = %d but pending is null", n_pending);
-  for (int i = 0; i < q; ++i) {
-    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
-    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;  // epsilon = 0 is plain PI
-    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
-      FAIL(h, BOGP_ERR_INVALID, "acquisition parameter %d must be > 0 (the reference asserts alpha/epsilon/t > 0)", i);
-  }
+  if (int ec = check_criteria(h, q, acq_id, acq_par)) return ec;
   const int d = h->d, N = h->N, Np = h->Np;
   if (q > h->M) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: q = %d proposals from %lld candidates (every step takes a row no step before it took)", q, (long long)h->M);
   for (size_t i = 0; i < (size_t)n_pending * d; ++i)
@@ -186,13 +154,17 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   invalidate_sweep_results(h);  // dbest_* are overwritten
 
   // ---- pass 0: the plain sweep; with pending points only the moments (step 0 is evaluated behind the last pending point)
-  int rc = P == 0 ? run_sweep(h, true, 1, acq_id, acq_par, plugin, minimize, true, true, true)
-                  : run_sweep(h, true, 0, nullptr, nullptr, 0.0, minimize, false, true, true);
+  SweepRequest rq;
+  rq.want_out = true; rq.minimize = minimize;
+  if (P == 0) { rq.q = 1; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.want_acq_out = true; }
+  int rc = run_sweep(h, rq);
   if (rc) return rc;
   if ((rc = candidates_ready(h))) return rc;
 
   // ---- geometry of the later passes
-  const Plan pl = make_plan(M, Np);
+  SweepGeometry pl;  // the sweep's own for a constant-trend model
+  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
+  const int64_t nblk_total = (M + 63) / 64 + pl.nchunk;  // (one record per 64 rows)
   const size_t small_n = SolveBufs::doubles(d, N);
   if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M))) return rc;
   if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)2 * M))) return rc;
@@ -202,10 +174,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * pl.Mc))) return rc;
   if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
   if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)pl.nblk_total))) return rc;
-  if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)pl.nblk_total))) return rc;
-  if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-  if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
+  if ((rc = ensure_sweep_outputs(h, 1, nblk_total, 0, false))) return rc;
   const SolveBufs sb(h->dbel_small, d, N);
   double* dacq_row = h->dbel_row;
   double* dmse_row = h->dbel_row + M;
@@ -280,7 +249,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
       nev += 3;
       HIPCHK(h, hipEventRecord(c0, st));
       if (active && !chunk_resident) {
-        HIPCHK(h, believer_corr_chunk(h, pl, m0, Mc_eff));
+        HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, pl, m0, 0), (int)(Mc_eff / 64), pl.S, st));
         chunk_resident = pl.nchunk == 1;
       }
       HIPCHK(h, hipEventRecord(c1, st));
@@ -290,7 +259,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
       blk_offset += (mcount + 63) / 64;
     }
     ++h->bel_passes;
-    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, pl.nblk_total, 1, h->dbest_val, h->dbest_idx, st));
+    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, 1, h->dbest_val, h->dbest_idx, st));
     return BOGP_OK;
   };
 
@@ -526,12 +495,15 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + (size_t)C0 * m;
   invalidate_sweep_results(h);  // dbest_* are overwritten
   const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
-  if ((rc = run_sweep(h, true, 1, &one_id, nullptr, 0.0, 0, true, true, true, &ea))) return rc;
+  SweepRequest rq;
+  rq.want_out = true; rq.want_acq_out = true; rq.q = 1; rq.acq_id = &one_id; rq.minimize = 0; rq.eh = &ea;
+  if ((rc = run_sweep(h, rq))) return rc;
   if ((rc = candidates_ready(h))) return rc;
   if (P == 0 && n_cells) n_cells[0] = C0;
 
   // ---- the later passes
-  const Plan pl = make_plan(M, Np);
+  SweepGeometry pl;
+  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
   const int64_t nblk = (M + 255) / 256;
   if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M * m))) return rc;
   if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)(2 + m) * M))) return rc;
@@ -541,8 +513,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * pl.Mc))) return rc;
   if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
   if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)nblk))) return rc;
-  if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)nblk))) return rc;
+  if ((rc = ensure_sweep_outputs(h, 1, nblk, 0, false))) return rc;
   const SolveBufs sb(h->dbel_small, d, N);
   double* dehvi_row = h->dbel_row;
   double* dscratch = h->dbel_row + M;      // k_believer's own s, in unit variance: not used
@@ -612,7 +583,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
         nev += 3;
         HIPCHK(h, hipEventRecord(c0, st));
         if (!chunk_resident) {
-          HIPCHK(h, believer_corr_chunk(h, pl, m0, Mc_eff));
+          HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, pl, m0, 0), (int)(Mc_eff / 64), pl.S, st));
           chunk_resident = pl.nchunk == 1;
         }
         HIPCHK(h, hipEventRecord(c1, st));

@@ -50,7 +50,9 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   invalidate_sweep_results(h);  // dbest_* are overwritten and hold no single-target winners afterwards
   const bool want_out = mu_out || mse_out;
   const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
-  int rc = run_sweep(h, want_out, 1, &one_id, nullptr, 0.0, 0, true, true, true, &ea);
+  SweepRequest rq;
+  rq.want_out = want_out; rq.want_acq_out = true; rq.q = 1; rq.acq_id = &one_id; rq.minimize = 0; rq.eh = &ea;
+  int rc = run_sweep(h, rq);
   if (rc) return rc;
   const int64_t M = h->M;
   if (k == 1) {  // the chunk loop's own argmax

@@ -90,12 +90,7 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   if (h->lift_D <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_lift_sweep_topk: no lift: call bogp_lift_set first");
   if (k <= 0 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "bogp_lift_sweep_topk: k = %d outside [1, %d]", k, BOGP_MAX_TOPK);
   if (q <= 0 || q > BOGP_MAX_Q || !acq_id || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "bogp_lift_sweep_topk: 0 < q <= %d and non-null acq_id/best_val/best_idx required", BOGP_MAX_Q);
-  for (int i = 0; i < q; ++i) {
-    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
-    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;
-    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
-      FAIL(h, BOGP_ERR_INVALID, "acquisition parameter %d must be > 0", i);
-  }
+  if (int ec = check_criteria(h, q, acq_id, acq_par)) return ec;
   if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "no committed model: call bogp_commit first");
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "no candidates: call bogp_candidates_upload/bind first");
   if (h->lift_r != h->d) FAIL(h, BOGP_ERR_INVALID, "bogp_lift_sweep_topk: the lift was set for r = %d, the model has d = %d: call bogp_lift_set again", h->lift_r, h->d);
@@ -134,7 +129,10 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   // 3. the posterior sweep on the survivors, its q x M_f values kept on the device
   if (Mf > 0) {
     CandidateSwap swap(h, h->dlift_Z, Mf);
-    const int rc = run_sweep(h, false, q, acq_id, acq_par, plugin, minimize, true, true, false);
+    SweepRequest rq;
+    rq.q = q; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.minimize = minimize;
+    rq.want_acq_out = true; rq.sync = false;
+    const int rc = run_sweep(h, rq);
     if (rc) return rc;
   } else {
     clear_sweep_timing(h);

@@ -1,8 +1,8 @@
 // bogp_api_sweep.hip -- the C ABI of libbogp.so (include/bogp.h), part 3 of 3: candidate sets (upload, lazy upload, device generators),
-// the posterior / acquisition sweep (one launch for small training sets, chunked producer -> contraction -> acquisition otherwise),
-// top-k, the one-point gradient / Hessian calls, timing and the debug / self-test exports.  Part 1 = bogp_api.hip, part 2 = bogp_api_fit.hip.
-#include <hip/hip_runtime.h>
-
+// the posterior / acquisition sweep, top-k, the one-point gradient / Hessian calls, timing and the debug / self-test exports.
+// Part 1 = bogp_api.hip, part 2 = bogp_api_fit.hip.
+// run_sweep dispatches a SweepRequest to sweep_small_batch (M <= 32), sweep_one_launch (Np <= 512, everything fused), sweep_chunks (producer
+// -> contraction -> criteria per chunk; sweep_pruned_chunk, sweep_trend_chunk) or sweep_onepass (the one-pass pruned flow).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -310,6 +310,10 @@ static hipEvent_t get_event(bogp_handle* h, size_t i) {
   return h->ev[i];
 }
 
+// events per chunk: [0] corr start, [1] corr end (producer stream); [2] contract start, [3] contract end,
+// [4] acquisition end = chunk done (main stream)
+constexpr int EPC = 5;
+
 // Event times of the last sweep are read lazily (bogp_last_timing, or the next sweep): reading them needs the events
 // to have completed, and an un-synchronised sweep (bogp_sweep without host outputs) must not wait for them.
 static void collect_timing(bogp_handle* h) {
@@ -323,7 +327,6 @@ static void collect_timing(bogp_handle* h) {
     h->t_corr_ms = 0; h->t_contract_ms = ms; h->t_acq_ms = 0;  // one kernel: reported as the contraction's time
     return;
   }
-  constexpr int EPC = 5;
   h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
   if (h->timing_onepass) {
     // a sweep that began on the one-pass flow: its own producer / contraction launches are bracketed one by one (t_spans: kind, begin, end),
@@ -376,285 +379,360 @@ void bogp::clear_sweep_timing(bogp_handle* h) {
   h->n_chunks = 0;
 }
 
-int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin,
-                    int minimize, bool want_acq_out, bool need_var, bool sync, const EhviArgs* eh) {
-  collect_timing(h);  // the events are about to be re-recorded
-  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "no committed model: call bogp_commit first");
-  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "no candidates: call bogp_candidates_upload/bind first");
-  if (q < 0 || q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "q = %d outside [0, %d]", q, BOGP_MAX_Q);
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  const int Np = h->Np, d = h->d;
-  const int64_t M = h->M;
-  const int64_t Mpad = ((M + 63) / 64) * 64;
-  h->prune_path = BOGP_PRUNE_PATH_NONE;
-  h->prune_survivors = 0;
-  h->prune_rounds = 0;
-  h->timing_onepass = false;
-  size_t chunk_bytes = (size_t)1 << 30;
-  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
-  // trend-rows path (k_pack_Vx): the chunk carries Nt - Np extra rows (the hole up to a whole column group, then -f(x*)), the contraction
-  // runs over the extended factor
-  const bool vx_model = h->vx_Nt > 0 && h->p >= trend_rows_min() && h->estimate_trend;  // the committed model takes the trend-rows path ...
-  const bool vx = vx_model && need_var;                                                     // ... and this call needs the variance
-  const int Nrows = vx ? h->vx_Nt : Np;
-  int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Nrows * sizeof(double)) / 64) * 64;
-  Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
-  const int nblk32 = Np / 32;
-  // the training set is sliced into groups of 8 x 32 rows per producer workgroup: a function of N only, so that the
-  // grouping of the partial sums of mu (hence every output bit) does not depend on the chunk size
-  constexpr int nblk_per_split = 8;  // (4 / 16 measured: profiles/r05_corr_split_ab.txt)
-  const int S = (nblk32 + nblk_per_split - 1) / nblk_per_split;
-  const int cols = contract_cols_per_group();
-  const int NJ16 = Nrows / 16;
-  const int nJ_main = (Np + cols - 1) / cols;            // column groups of V: |L^-1 r|^2
-  const int nJ = vx ? (Nrows + cols - 1) / cols : nJ_main;  // ... + the groups of the trend rows: |u|^2
-  const int64_t nchunk = (M + Mc - 1) / Mc;
-  const int64_t nblk_total = (M + 255) / 256 + nchunk;  // per-chunk block counts are rounded up
+// ---- what the sweep shares with the believer and the Thompson passes (bogp_handle.h) -------------------------------------------------
+int bogp::sweep_geometry(bogp_handle* h, int rows, SweepGeometry* g) {
+  int64_t chunk_bytes = (int64_t)1 << 30;
+  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (int64_t)std::max(1, atoi(env)) << 20;
+  g->Mc = sweep_chunk_rows(rows, h->M, chunk_bytes);
+  if (g->Mc < 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "a chunk of more than %lld candidates is beyond the kernels' 32-bit row offsets: lower BOGP_CHUNK_MB", (long long)SWEEP_MAX_CHUNK_ROWS);
+  g->nchunk = (h->M + g->Mc - 1) / g->Mc;
+  g->S = sweep_slices(h->Np);
+  return BOGP_OK;
+}
 
-  // Small batches (the reference's one-point-per-call usage through L-BFGS-B): the tiled contraction would leave one
-  // workgroup walking all N columns alone (~0.3 ms at N = 2048).  For M <= BOGP_SMALL_M the posterior is instead
-  // r -> rt = V r (k_gemm64 with M right-hand sides) -> column reductions, feeding the same acquisition kernel.
-  // (bogp_sweep_ehvi -- eh non-null -- takes neither single-target shortcut: it always runs the chunked path below)
-  const int small_m = 32;
-  const bool small_batch = !eh && M <= small_m && h->p == 1;
-  const bool one_launch = !eh && h->p == 1 && sweep_small_supported(Np, d, h->kernel);
-  if (h->hXs_lazy && (small_batch || one_launch || nchunk == 1)) {
-    // nothing to overlap with: the whole upload first (one launch reads every candidate)
-    const int el = lazy_finish(h);
-    if (el) return el;
-  }
-  if (small_batch) {
-    const int B = (int)M, N = h->N;
-    int e2;
-    if ((e2 = ensure(h, &h->dbatch, &h->batch_cap, (size_t)3 * N * B + 3 * (size_t)B))) return e2;
-    double* dr = h->dbatch;
-    double* ds2 = dr + (size_t)N * B;
-    double* drt = ds2 + (size_t)N * B;
-    double* dred = drt + (size_t)N * B;  // mu[B], wd[B], ss[B]
-    if (q > 0) {
-      if ((e2 = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * 2))) return e2;
-      if ((e2 = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * 2))) return e2;
-      if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-      if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
-    }
-    if (want_out) {
-      if ((e2 = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M))) return e2;
-      if ((e2 = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M))) return e2;
-    }
-    if (want_acq_out)
-      if ((e2 = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e2;
-    HIPCHK(h, launch_batch_corr(h->kernel, h->dX, N, d, h->dtheta, h->dXs, B, dr, ds2, st));
-    HIPCHK(h, launch_gemm(0, 0, N, B, N, 1.0, h->dV, h->ldr, dr, N, 0.0, drt, N, st, 1));  // rt = V r, V lower with a zero upper triangle
-    HIPCHK(h, launch_col_reduce(dr, drt, N, B, h->dgamma, h->dw, dred, dred + B, dred + 2 * B, st));
-    AcqArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.mu_part = dred; aa.w_part = dred + B; aa.ss_part = dred + 2 * B; aa.S = 1; aa.nJ = 1; aa.Mc = B;
-    aa.mcount = B; aa.m0 = 0; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend;
-    aa.sigma2 = h->sigma2; aa.mu_out = want_out ? h->dmu_out : nullptr; aa.mse_out = want_out ? h->dmse_out : nullptr;
-    aa.q = q;
-    for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    aa.plugin = plugin; aa.minimize = minimize; aa.acq_out = want_acq_out ? h->dacq_out : nullptr; aa.M = M;
-    aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.blk_offset = 0; aa.nblk_total = 1;
-    HIPCHK(h, launch_acquisition(aa, st));
-    if (q > 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, 1, 1, q, h->dbest_val, h->dbest_idx, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
-    h->n_chunks = 0;
-    h->timing_pending = false;
-    h->prune_used = false;
-    h->contracted_rows = need_var ? M : 0;
-    return BOGP_OK;
-  }
+CorrArgs bogp::corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int64_t m0, int b) {
+  CorrArgs ca;
+  ca.Xs = h->dXs; ca.M = h->M; ca.m0 = m0; ca.Mc = g.Mc; ca.d = h->d; ca.Np = h->Np; ca.nblk_per_split = SWEEP_NBLK_PER_SPLIT;
+  ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
+  ca.rT = h->drT[b]; ca.mu_part = h->dmu_part[b]; ca.w_part = h->dw_part[b];
+  return ca;
+}
 
-  // Small training sets (Np <= 512, d <= 60, constant trend): the whole sweep is ONE launch of k_sweep_small -- producer,
-  // triangular contraction, posterior, criteria and argmax fused, r never leaves LDS (kernels_small.hip).
-  if (one_launch) {
-    const int64_t nblk = std::max<int64_t>(sweep_small_blocks(M, h->n_cu), (M + 15) / 16);
-    int e2;
-    if (q > 0) {
-      if ((e2 = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * nblk))) return e2;
-      if ((e2 = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * nblk))) return e2;
-      if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-      if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
-    }
-    if (want_out) {
-      if ((e2 = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M))) return e2;
-      if ((e2 = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M))) return e2;
-    }
-    if (want_acq_out)
-      if ((e2 = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e2;
-    if (!h->dcounter) {
-      HIPCHK(h, hipMalloc((void**)&h->dcounter, sizeof(unsigned int)));
-      HIPCHK(h, hipMemsetAsync(h->dcounter, 0, sizeof(unsigned int), st));
-    }
-    SmallArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.Xs = h->dXs; sa.sqrt_theta = h->dsqrt_theta; sa.XthT = h->dXthT; sa.gamma = h->dgamma; sa.wvec = h->dw; sa.Vp = h->dVp;
-    sa.M = M; sa.d = d; sa.Np = Np; sa.NJ16 = Np / 16; sa.NKP = Np / 8; sa.need_var = need_var ? 1 : 0;
-    sa.beta = h->beta; sa.G = h->G; sa.sigma2 = h->sigma2; sa.plugin = plugin;
-    sa.estimate_trend = h->estimate_trend; sa.minimize = minimize; sa.q = q;
-    for (int i = 0; i < q; ++i) { sa.acq_id[i] = acq_id[i]; sa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    sa.mu_out = want_out ? h->dmu_out : nullptr; sa.mse_out = want_out ? h->dmse_out : nullptr;
-    sa.acq_out = want_acq_out ? h->dacq_out : nullptr;
-    sa.blk_val = h->dblk_val; sa.blk_idx = h->dblk_idx; sa.nblk = nblk; sa.counter = h->dcounter;
-    sa.best_val = h->dbest_val; sa.best_idx = h->dbest_idx;
-    const bool stamps = getenv("BOGP_SMALL_STAMPS") && atoi(getenv("BOGP_SMALL_STAMPS"));
-    if (stamps) {  // measurement aid: per-phase wave-cycles of this launch, printed on stderr
-      if ((e2 = ensure(h, &h->dbatch, &h->batch_cap, (size_t)8))) return e2;
-      HIPCHK(h, hipMemsetAsync(h->dbatch, 0, 8 * sizeof(double), st));
-      sa.stamps = (long long*)h->dbatch;
-    }
-    hipEvent_t e0 = get_event(h, 0), e1 = get_event(h, 1);
-    if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(h, hipEventRecord(e0, st));
-    HIPCHK(h, launch_sweep_small(h->kernel, sa, h->n_cu, st));
-    HIPCHK(h, hipEventRecord(e1, st));
-    h->n_chunks = 1;
-    h->timing_pending = true;
-    h->timing_fused = true;
-    h->timing_prune = false;
-    h->prune_used = false;
-    h->contracted_rows = need_var ? M : 0;
-    if (sync || stamps) HIPCHK(h, hipStreamSynchronize(st));
-    if (stamps) {
-      collect_timing(h);
-      long long sv[5] = {0, 0, 0, 0, 0};
-      HIPCHK(h, hipMemcpy(sv, h->dbatch, sizeof(sv), hipMemcpyDeviceToHost));
-      const double nw = (double)std::max<long long>(1, sv[4]);
-      fprintf(stderr, "k_sweep_small M=%lld: %.3f ms; per wave: produce %.0f, contract %.0f, wait-at-barrier %.0f, epilogue %.0f cycles (%lld waves)\n",
-              (long long)M, h->t_contract_ms, sv[0] / nw, sv[1] / nw, sv[2] / nw, sv[3] / nw, sv[4]);
-    }
-    return BOGP_OK;
-  }
-
-  // Optional two-stream mode (BOGP_OVERLAP=1): the correlation producer of chunk c+1 (FP64 VALU) runs beside the
-  // contraction of chunk c (FP64 MFMA), everything the producer writes double buffered.  Measured on MI355X (r01,
-  // C3): the kernels do overlap (contract 75.9 -> 81.9 ms, corr 6.8 -> 11.7 ms) but the step time is unchanged
-  // (83.3 -> 83.0 ms): the DP pipe is the shared resource.  Off by default: it costs a second 1-GiB chunk buffer.
-  const bool overlap = nchunk > 1 && getenv("BOGP_OVERLAP") && atoi(getenv("BOGP_OVERLAP")) == 1;
-  hipStream_t stP = overlap ? h->stream2 : st;
-  const int nbuf = overlap ? 2 : 1;
+int bogp::ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out) {
   int e;
-  // Pruned sweep (kernels_prune.hip, DESIGN.md 5.22): only the winners leave this call, so a row whose criteria cannot reach the best
-  // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI -- runs as ever.
-  const bool prune = h->prune_mode != 0 && need_var && q > 0 && !want_out && !want_acq_out && !eh && h->p == 1 && !vx_model && !overlap;
-#ifndef BOGP_PRUNE_PILOT
-#define BOGP_PRUNE_PILOT 4096  // (1024 / 8192 measured with `make EXTRA=-DBOGP_PRUNE_PILOT=...`: profiles/prune_sweep.txt)
-#endif
-  constexpr int64_t PRUNE_PILOT = BOGP_PRUNE_PILOT;  // rows of chunk 0 evaluated exactly to seed the thresholds; a multiple of 256
-  static_assert(PRUNE_PILOT % 256 == 0 && PRUNE_PILOT > 0 && PRUNE_PILOT <= 8192, "pilot rows");
-  const int64_t Ms = prune ? Mc : 0;  // rows of the survivor buffer: one chunk's, i.e. four chunks' worst case (half a chunk measured: profiles/prune_sweep.txt)
-  // One pass: with every candidate resident and a producer that exists without its store, the rows behind the pilot are
-  // bounded a SEGMENT at a time -- as many whole chunks as keep the two partial-sum arrays within 256 MiB -- and only survivors get columns
-  const bool onepass = prune && h->prune_mode == 1 && nchunk > 1 && !h->hXs_lazy && corr_chunk_without_store(h->kernel, 0, h->dXnorm != nullptr);
-  const int64_t seg_rows = onepass ? std::max<int64_t>(1, (((int64_t)256 << 20) / (int64_t)(2 * S * sizeof(double))) / Mc) * Mc : 0;
-  const int64_t seg_stride = std::min<int64_t>(seg_rows, Mpad);       // row stride of a segment's partial sums
-  const int64_t Rmax = std::max<int64_t>(Mc, seg_stride);             // rows one bounding launch may cover
-  const int64_t sidx_cap = seg_stride / 4 + 1;                        // survivor indices kept: a fuller segment falls back
-  const int64_t prune_nbk = Rmax / 256 + 1;
-  long long* pctl = nullptr;
-  int64_t *poffsets = nullptr, *pmap = nullptr, *psidx = nullptr;
-  int *psel = nullptr, *pblk_count = nullptr;
-  unsigned char* pflags = nullptr;
-  double* pxc = nullptr;
-  if (prune) {
-    const size_t w_off = PRUNE_CTL_WORDS, w_map = w_off + (size_t)prune_nbk + 1, w_sel = w_map + (size_t)Ms, w_cnt = w_sel + (size_t)(Mc / 4) / 2 + 1,
-                 w_flag = w_cnt + (size_t)prune_nbk / 2 + 1, w_sidx = w_flag + (size_t)Rmax / 8 + 1, w_xc = w_sidx + (onepass ? (size_t)sidx_cap : 0),
-                 w_end = w_xc + (onepass ? (size_t)Ms * d : 0);
-    if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
-    pctl = h->dprune; poffsets = (int64_t*)(h->dprune + w_off); pmap = (int64_t*)(h->dprune + w_map); psel = (int*)(h->dprune + w_sel);
-    pblk_count = (int*)(h->dprune + w_cnt); pflags = (unsigned char*)(h->dprune + w_flag);
-    psidx = (int64_t*)(h->dprune + w_sidx); pxc = (double*)(h->dprune + w_xc);  // one pass: survivor indices of a segment | candidate rows of a round
-    // the survivor buffer = the second chunk buffer of the two-stream mode
-    if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)Nrows * Ms))) return e;
-    if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * Ms))) return e;
-    if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * Ms))) return e;
-  }
-  for (int b = 0; b < nbuf; ++b) {
-    // (one pass: the chunk buffer is allocated only if a per-chunk path runs after all; the partial sums are a segment's)
-    if (!onepass && (e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)Nrows * Mc))) return e;
-    if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * (onepass ? Rmax : Mc)))) return e;
-    if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * (onepass ? Rmax : Mc)))) return e;
-  }
-  if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)nJ * (Mc + Ms)))) return e;  // (+ the survivor buffer's sums)
-  double* dss_surv = h->dss_part + (size_t)nJ * Mc;
-  if (h->p > 1) {
-    if (Mc > 0x7fffffff / 2) FAIL(h, BOGP_ERR_UNSUPPORTED, "chunk of %lld candidates is too large for the trend GEMM (lower BOGP_CHUNK_MB)", (long long)Mc);
-    if (!vx_model) {
-      if ((e = ensure(h, &h->dTt, &h->Tt_cap, (size_t)Mc * ((h->p + 127) / 128 * 128)))) return e;  // whole 128-column tiles (k_mm128)
-      if ((e = ensure(h, &h->dCS, &h->CS_cap, (size_t)Mc * ((h->p + 127) / 128 * 128)))) return e;
-    }
-    if ((e = ensure(h, &h->duu, &h->uu_cap, (size_t)Mc))) return e;
-    if ((e = ensure(h, &h->dmtrend, &h->mtrend_cap, (size_t)Mc))) return e;
-  }
-  // a polynomial basis of at most 32 columns under universal kriging: T = W^T r is accumulated by the producer itself
-  // (k_corr_chunk<K, PV>) and finished by ONE per-candidate launch (k_trend_small); (the tile products it replaces: git 3357059)
-  // (a mean-only call of a trend-rows model keeps the producer the full call uses -- pv = 0 -- so that mu comes out bit-identical)
-  const int pv = (!vx_model && h->p > 1 && h->estimate_trend) ? corr_trend_columns(h->p) : 0;
-  if (pv > 0)
-    for (int b = 0; b < nbuf; ++b)
-      if ((e = ensure(h, &h->dtpart[b], &h->tpart_cap[b], (size_t)S * pv * Mc))) return e;
   if (q > 0) {
-    if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * nblk_total))) return e;
-    if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * nblk_total))) return e;
+    if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * nblk))) return e;
+    if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * nblk))) return e;
     if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
     if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
   }
-  if (want_out) {  // (EHVI: M x m moments)
-    const size_t n_out = (size_t)M * (eh ? eh->m : 1);
-    if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, n_out))) return e;
-    if ((e = ensure(h, &h->dmse_out, &h->mse_out_cap, n_out))) return e;
-  }
-  if (want_acq_out)
-    if ((e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e;
+  if (n_out > 0 && ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, n_out)) || (e = ensure(h, &h->dmse_out, &h->mse_out_cap, n_out)))) return e;
+  if (want_acq_out && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * h->M))) return e;
+  return BOGP_OK;
+}
 
-  // events per chunk: [0] corr start, [1] corr end (producer stream); [2] contract start, [3] contract end,
-  // [4] acquisition end = chunk done (main stream)
-  constexpr int EPC = 5;
-  for (int64_t c = 0; c < nchunk; ++c)
-    for (int k = 0; k < EPC; ++k)
-      if (!get_event(h, (size_t)(c * EPC + k))) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  hipEvent_t ev_begin = get_event(h, (size_t)(nchunk * EPC));
-  if (!ev_begin) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  if (!get_event(h, (size_t)(nchunk * EPC + 2))) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");  // the pilot's pair (pruned sweep)
-  int64_t prune_pending = 0;  // upper bound of the survivors waiting in the buffer (their count itself stays on the device)
-  if (overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
-    HIPCHK(h, hipEventRecord(ev_begin, st));
-    HIPCHK(h, hipStreamWaitEvent(stP, ev_begin, 0));
+int bogp::check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par) {
+  for (int i = 0; i < q; ++i) {
+    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
+    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;  // epsilon = 0 is plain PI
+    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
+      FAIL(h, BOGP_ERR_INVALID, "acquisition parameter %d must be > 0 (the reference asserts alpha/epsilon/t > 0)", i);
   }
+  return BOGP_OK;
+}
 
-  int64_t blk_offset = 0;
-  // chunks [c_begin, c_end); pilot_done (a pruned sweep that began on the one-pass flow): thresholds, control words and the pilot rows'
-  // winners are in place -- chunk 0 starts behind the pilot
-  auto run_chunks = [&](int64_t c_begin, int64_t c_end, bool pilot_done) -> int {
+#ifndef BOGP_PRUNE_PILOT
+#define BOGP_PRUNE_PILOT 4096  // (1024 / 8192 measured with `make EXTRA=-DBOGP_PRUNE_PILOT=...`: profiles/prune_sweep.txt)
+#endif
+constexpr int64_t PRUNE_PILOT = BOGP_PRUNE_PILOT;  // rows of chunk 0 evaluated exactly to seed the thresholds; a multiple of 256
+static_assert(PRUNE_PILOT % 256 == 0 && PRUNE_PILOT > 0 && PRUNE_PILOT <= 8192, "pilot rows");
+
+template <class Args>  // AcqArgs, SmallArgs, PruneBoundArgs
+static void set_criteria(Args& a, int q, const int* id, const double* par) { a.q = q; for (int i = 0; i < q; ++i) { a.acq_id[i] = id[i]; a.acq_par[i] = par ? par[i] : 0.0; } }
+
+// what the chunked paths share: built once by run_sweep
+struct SweepCtx {
+  SweepRequest rq;
+  SweepGeometry g;
+  int64_t M, nblk_total;  // (256-row block records; per-chunk block counts are rounded up)
+  int Nrows, nJ, nJ_main, NJ16, pv;
+  bool vx_model, vx, overlap, prune, onepass;
+  hipStream_t st, stP;
+  // pruned sweep: rows of the survivor buffer, segment geometry of the one-pass flow, the carved work space (sweep_workspace)
+  int64_t Ms, seg_rows, seg_stride, Rmax, sidx_cap, prune_nbk;
+  long long* pctl;
+  int64_t *poffsets, *pmap, *psidx;
+  int *psel, *pblk_count;
+  unsigned char* pflags;
+  double *pxc, *dss_surv;
+  int64_t blk_offset, prune_pending;  // block records written so far; upper bound of the survivors waiting in the buffer (their count stays on the device)
+};
+
+// the model's and the request's half of k_acquisition's arguments; the caller adds the arrays and the geometry of its launch
+static AcqArgs acq_model_args(const bogp_handle* h, const SweepRequest& rq, int S, int nJ, int64_t nblk_total) {
+  AcqArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.S = S; aa.nJ = nJ; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend; aa.sigma2 = h->sigma2;
+  set_criteria(aa, rq.q, rq.acq_id, rq.acq_par);
+  aa.plugin = rq.plugin; aa.minimize = rq.minimize; aa.M = h->M;
+  aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
+  aa.mu_out = rq.want_out ? h->dmu_out : nullptr; aa.mse_out = rq.want_out ? h->dmse_out : nullptr; aa.acq_out = rq.want_acq_out ? h->dacq_out : nullptr;
+  return aa;
+}
+
+// ... and of k_prune_bound's; the caller adds the region (partial sums, stride, rows)
+static PruneBoundArgs prune_bound_args(const bogp_handle* h, const SweepCtx& cx) {
+  PruneBoundArgs pb;
+  memset(&pb, 0, sizeof(pb));
+  pb.S = cx.g.S; pb.beta = h->beta; pb.G = h->G; pb.sigma2 = h->sigma2; pb.plugin = cx.rq.plugin; pb.estimate_trend = h->estimate_trend;
+  pb.minimize = cx.rq.minimize;
+  set_criteria(pb, cx.rq.q, cx.rq.acq_id, cx.rq.acq_par);
+  pb.best_val = h->dbest_val; pb.flags = cx.pflags; pb.blk_count = cx.pblk_count;
+  return pb;
+}
+
+// Small batches (the reference's one-point-per-call usage through L-BFGS-B): the tiled contraction would leave one
+// workgroup walking all N columns alone (~0.3 ms at N = 2048).  For M <= 32 the posterior is instead
+// r -> rt = V r (k_gemm64 with M right-hand sides) -> column reductions, feeding the same acquisition kernel.
+static int sweep_small_batch(bogp_handle* h, const SweepRequest& rq) {
+  hipStream_t st = h->stream;
+  const int64_t M = h->M;
+  int e, B = (int)M, N = h->N;
+  if ((e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)3 * N * B + 3 * (size_t)B))) return e;
+  double *dr = h->dbatch, *ds2 = dr + (size_t)N * B, *drt = ds2 + (size_t)N * B;
+  double* dred = drt + (size_t)N * B;  // mu[B], wd[B], ss[B]
+  if ((e = ensure_sweep_outputs(h, rq.q, 2, rq.want_out ? (size_t)M : 0, rq.want_acq_out))) return e;
+  HIPCHK(h, launch_batch_corr(h->kernel, h->dX, N, h->d, h->dtheta, h->dXs, B, dr, ds2, st));
+  HIPCHK(h, launch_gemm(0, 0, N, B, N, 1.0, h->dV, h->ldr, dr, N, 0.0, drt, N, st, 1));  // rt = V r, V lower with a zero upper triangle
+  HIPCHK(h, launch_col_reduce(dr, drt, N, B, h->dgamma, h->dw, dred, dred + B, dred + 2 * B, st));
+  AcqArgs aa = acq_model_args(h, rq, 1, 1, 1);
+  aa.mu_part = dred; aa.w_part = dred + B; aa.ss_part = dred + 2 * B; aa.Mc = B; aa.mcount = B; aa.m0 = 0;
+  HIPCHK(h, launch_acquisition(aa, st));
+  if (rq.q > 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, 1, 1, rq.q, h->dbest_val, h->dbest_idx, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
+  h->n_chunks = 0; h->timing_pending = false; h->prune_used = false;
+  h->contracted_rows = rq.need_var ? M : 0;
+  return BOGP_OK;
+}
+
+// Small training sets (Np <= 512, d <= 60, constant trend): the whole sweep is ONE launch of k_sweep_small -- producer,
+// triangular contraction, posterior, criteria and argmax fused, r never leaves LDS (kernels_small.hip).
+static int sweep_one_launch(bogp_handle* h, const SweepRequest& rq) {
+  hipStream_t st = h->stream;
+  const int Np = h->Np;
+  const int64_t M = h->M, nblk = std::max<int64_t>(sweep_small_blocks(M, h->n_cu), (M + 15) / 16);
+  int e;
+  if ((e = ensure_sweep_outputs(h, rq.q, nblk, rq.want_out ? (size_t)M : 0, rq.want_acq_out))) return e;
+  if (!h->dcounter) {
+    HIPCHK(h, hipMalloc((void**)&h->dcounter, sizeof(unsigned int)));
+    HIPCHK(h, hipMemsetAsync(h->dcounter, 0, sizeof(unsigned int), st));
+  }
+  SmallArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.Xs = h->dXs; sa.sqrt_theta = h->dsqrt_theta; sa.XthT = h->dXthT; sa.gamma = h->dgamma; sa.wvec = h->dw; sa.Vp = h->dVp;
+  sa.M = M; sa.d = h->d; sa.Np = Np; sa.NJ16 = Np / 16; sa.NKP = Np / 8; sa.need_var = rq.need_var ? 1 : 0;
+  sa.beta = h->beta; sa.G = h->G; sa.sigma2 = h->sigma2; sa.plugin = rq.plugin;
+  sa.estimate_trend = h->estimate_trend; sa.minimize = rq.minimize;
+  set_criteria(sa, rq.q, rq.acq_id, rq.acq_par);
+  sa.mu_out = rq.want_out ? h->dmu_out : nullptr; sa.mse_out = rq.want_out ? h->dmse_out : nullptr;
+  sa.acq_out = rq.want_acq_out ? h->dacq_out : nullptr;
+  sa.blk_val = h->dblk_val; sa.blk_idx = h->dblk_idx; sa.nblk = nblk; sa.counter = h->dcounter;
+  sa.best_val = h->dbest_val; sa.best_idx = h->dbest_idx;
+  const bool stamps = getenv("BOGP_SMALL_STAMPS") && atoi(getenv("BOGP_SMALL_STAMPS"));
+  if (stamps) {  // measurement aid: per-phase wave-cycles of this launch, printed on stderr
+    if ((e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)8))) return e;
+    HIPCHK(h, hipMemsetAsync(h->dbatch, 0, 8 * sizeof(double), st));
+    sa.stamps = (long long*)h->dbatch;
+  }
+  hipEvent_t e0 = get_event(h, 0), e1 = get_event(h, 1);
+  if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  HIPCHK(h, hipEventRecord(e0, st));
+  HIPCHK(h, launch_sweep_small(h->kernel, sa, h->n_cu, st));
+  HIPCHK(h, hipEventRecord(e1, st));
+  h->n_chunks = 1; h->timing_pending = true; h->timing_fused = true; h->timing_prune = false; h->prune_used = false;
+  h->contracted_rows = rq.need_var ? M : 0;
+  if (rq.sync || stamps) HIPCHK(h, hipStreamSynchronize(st));
+  if (stamps) {
+    collect_timing(h);
+    long long sv[5] = {0, 0, 0, 0, 0};
+    HIPCHK(h, hipMemcpy(sv, h->dbatch, sizeof(sv), hipMemcpyDeviceToHost));
+    const double nw = (double)std::max<long long>(1, sv[4]);
+    fprintf(stderr, "k_sweep_small M=%lld: %.3f ms; per wave: produce %.0f, contract %.0f, wait-at-barrier %.0f, epilogue %.0f cycles (%lld waves)\n",
+            (long long)M, h->t_contract_ms, sv[0] / nw, sv[1] / nw, sv[2] / nw, sv[3] / nw, sv[4]);
+  }
+  return BOGP_OK;
+}
+
+// The pruned sweep's sizes and work space (kernels_prune.hip): control words | block offsets | index map | selected rows |
+// block counts | flags | one pass: survivor indices of a segment | candidate rows of a round; the survivor buffer = the second chunk
+// buffer of the two-stream mode.  One pass: the rows behind the pilot are bounded a SEGMENT at a time -- as many
+// whole chunks as keep the two partial-sum arrays within 256 MiB -- and only survivors get columns.  Then the buffers every chunked path needs.
+static int sweep_workspace(bogp_handle* h, SweepCtx& cx) {
+  const int64_t Mc = cx.g.Mc, Mpad = ((cx.M + 63) / 64) * 64;
+  const int S = cx.g.S, nbuf = cx.overlap ? 2 : 1;
+  int e;
+  cx.Ms = cx.prune ? Mc : 0;  // rows of the survivor buffer: one chunk's, i.e. four chunks' worst case (half a chunk measured: profiles/prune_sweep.txt)
+  cx.seg_rows = cx.onepass ? std::max<int64_t>(1, (((int64_t)256 << 20) / (int64_t)(2 * S * sizeof(double))) / Mc) * Mc : 0;
+  cx.seg_stride = std::min<int64_t>(cx.seg_rows, Mpad);  // row stride of a segment's partial sums
+  cx.Rmax = std::max<int64_t>(Mc, cx.seg_stride);        // rows one bounding launch may cover
+  cx.sidx_cap = cx.seg_stride / 4 + 1;                   // survivor indices kept: a fuller segment falls back
+  cx.prune_nbk = cx.Rmax / 256 + 1;
+  if (cx.prune) {
+    const size_t w_off = PRUNE_CTL_WORDS, w_map = w_off + (size_t)cx.prune_nbk + 1, w_sel = w_map + (size_t)cx.Ms, w_cnt = w_sel + (size_t)(Mc / 4) / 2 + 1,
+                 w_flag = w_cnt + (size_t)cx.prune_nbk / 2 + 1, w_sidx = w_flag + (size_t)cx.Rmax / 8 + 1, w_xc = w_sidx + (cx.onepass ? (size_t)cx.sidx_cap : 0),
+                 w_end = w_xc + (cx.onepass ? (size_t)cx.Ms * h->d : 0);
+    if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
+    cx.pctl = h->dprune; cx.poffsets = (int64_t*)(h->dprune + w_off); cx.pmap = (int64_t*)(h->dprune + w_map); cx.psel = (int*)(h->dprune + w_sel);
+    cx.pblk_count = (int*)(h->dprune + w_cnt); cx.pflags = (unsigned char*)(h->dprune + w_flag);
+    cx.psidx = (int64_t*)(h->dprune + w_sidx); cx.pxc = (double*)(h->dprune + w_xc);
+    if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)cx.Nrows * cx.Ms))) return e;
+    if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * cx.Ms))) return e;
+    if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * cx.Ms))) return e;
+  }
+  for (int b = 0; b < nbuf; ++b) {
+    // (one pass: the chunk buffer is allocated only if a per-chunk path runs after all; the partial sums are a segment's)
+    if (!cx.onepass && (e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)cx.Nrows * Mc))) return e;
+    if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
+    if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
+  }
+  if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)cx.nJ * (Mc + cx.Ms)))) return e;  // (+ the survivor buffer's sums)
+  cx.dss_surv = h->dss_part + (size_t)cx.nJ * Mc;
+  if (h->p > 1) {
+    const size_t n_tiles = (size_t)Mc * ((h->p + 127) / 128 * 128);  // whole 128-column tiles (k_mm128)
+    if (!cx.vx_model && ((e = ensure(h, &h->dTt, &h->Tt_cap, n_tiles)) || (e = ensure(h, &h->dCS, &h->CS_cap, n_tiles)))) return e;
+    if ((e = ensure(h, &h->duu, &h->uu_cap, (size_t)Mc))) return e;
+    if ((e = ensure(h, &h->dmtrend, &h->mtrend_cap, (size_t)Mc))) return e;
+  }
+  if (cx.pv > 0)
+    for (int b = 0; b < nbuf; ++b)
+      if ((e = ensure(h, &h->dtpart[b], &h->tpart_cap[b], (size_t)S * cx.pv * Mc))) return e;
+  return BOGP_OK;
+}
+
+// Polynomial trend of one chunk: mean f(x*) . beta, and under universal kriging u = G^-T (Ft^T L^-1 r - f(x*)) (gpr.py:496-498):
+// T = r W (Mc x p, a tile product on the chunk that k_contract has just read), c = T - f(x*), u^T u = c^T (Ft^T Ft)^-1 c.
+// The two products run on k_mm128 (128 x 128 tiles, kernels_chol.hip) when the chunk is whole tiles -- the default
+// chunk sizes are; rows past Mc_eff of the last tile are computed on stale chunk data and never read -- and on the
+// generic k_gemm64 otherwise.  Leaves mtrend / uu in `aa`.
+static int sweep_trend_chunk(bogp_handle* h, const SweepCtx& cx, int b, int64_t m0, int64_t mcount, int64_t Mc_eff, AcqArgs& aa) {
+  hipStream_t st = cx.st;
+  const int64_t Mc = cx.g.Mc;
+  const int Np = h->Np, d = h->d, pt = h->p, pp = (pt + 127) / 128 * 128;
+  if (cx.vx) {
+    // (mtrend was written by k_trend_rows beside the chunk's extra rows; |u|^2 comes out of the contraction)
+  } else if (cx.pv > 0) {  // (T = W^T r was accumulated by the producer itself)
+    HIPCHK(h, launch_trend_small(h->trend, h->dXs, m0, mcount, d, Mc, h->dbetav, h->dtpart[b], cx.g.S, cx.pv, pt, h->dSinv, h->dmtrend, h->duu, st));
+    aa.uu = h->duu;
+  } else {
+    const bool tiles128 = Mc % 128 == 0, products = h->estimate_trend && !cx.vx_model;
+    const int TI = (int)((Mc_eff + 127) / 128);
+    const double one = 1.0, zero = 0.0;
+    if (products) {
+      if (tiles128)
+        HIPCHK(h, launch_mm128_gen(h->drT[b], (int)Mc, h->dWpT, pp, h->dTt, (int)Mc, TI, pp / 128, Np, st));
+      else
+        HIPCHK(h, launch_gemm(0, 0, (int)Mc_eff, pt, Np, one, h->drT[b], (int)Mc, h->dWp, Np, zero, h->dTt, (int)Mc, st, 0, &h->gsplit));
+    }
+    HIPCHK(h, launch_trend_terms(h->trend, h->dXs, m0, mcount, d, Mc, h->dbetav, products ? h->dTt : nullptr, h->dmtrend, st));
+    if (products) {
+      if (tiles128)
+        HIPCHK(h, launch_mm128_gen(h->dTt, (int)Mc, h->dSinvP, pp, h->dCS, (int)Mc, TI, pp / 128, pp, st));
+      else
+        HIPCHK(h, launch_gemm(0, 0, (int)Mc_eff, pt, pt, one, h->dTt, (int)Mc, h->dSinv, pt, zero, h->dCS, (int)Mc, st, 0, &h->gsplit));
+      HIPCHK(h, launch_rowdot(h->dTt, h->dCS, Mc, mcount, pt, h->duu, st));
+      aa.uu = h->duu;
+    }
+  }
+  aa.mtrend = h->dmtrend;
+  aa.estimate_trend = 0;  // the scalar w_part path is for the constant basis
+  return BOGP_OK;
+}
+
+// One chunk of the per-chunk pruned flow, behind its producer: in chunk 0 the pilot (unless `skip` rows of it are done already), then
+// bound -> scan + decision -> compaction -> gather, the contractions of both outcomes, criteria and the running best.  `model`: the
+// criteria kernel's arguments less the arrays; `ka`: the chunk's contraction.
+static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model, const ContractArgs& ka, int64_t c, int64_t c_end, int64_t m0, int64_t mcount, int64_t skip) {
+  hipStream_t st = cx.st;
+  long long* const pctl = cx.pctl;
+  const int64_t Mc = cx.g.Mc, Ms = cx.Ms, nblk_total = cx.nblk_total;
+  const int q = cx.rq.q;
+  hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
+  int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
+  if (skip > 0) i0 = skip;
+  else if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
+    const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
+    hipEvent_t* evp = &h->ev[(size_t)(cx.g.nchunk * EPC + 1)];
+    HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
+    HIPCHK(h, hipEventRecord(evp[0], st));
+    ContractArgs kp = ka;
+    kp.nMt = (int)((P + 63) / 64);
+    HIPCHK(h, launch_contract(kp, st));
+    HIPCHK(h, hipEventRecord(evp[1], st));
+    AcqArgs ap = model;
+    ap.mu_part = h->dmu_part[0]; ap.w_part = h->dw_part[0]; ap.ss_part = h->dss_part; ap.Mc = Mc; ap.mcount = P; ap.m0 = 0;
+    HIPCHK(h, launch_acquisition(ap, st));
+    HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, P, q, h->dbest_val, h->dbest_idx, st));
+    i0 = P;  // (a multiple of 256 unless the chunk ends with it)
+  }
+  const int64_t rcount = mcount - i0;
+  if (rcount > 0) {  // bound -> scan + decision -> compaction -> gather
+    PruneBoundArgs pb = prune_bound_args(h, cx);
+    pb.mu_part = h->dmu_part[0] + i0; pb.w_part = h->dw_part[0] + i0; pb.Mc = Mc; pb.rcount = rcount;
+    HIPCHK(h, launch_prune_bound(pb, st));
+    HIPCHK(h, launch_prune_scan(cx.pblk_count, (rcount + 255) / 256, cx.poffsets, rcount, Ms, pctl, st));
+    PruneGatherArgs pg;
+    pg.ctl = pctl; pg.flags = cx.pflags; pg.offsets = cx.poffsets; pg.rcount = rcount; pg.m0 = m0 + i0; pg.Mc = Mc; pg.Ms = Ms; pg.S = cx.g.S;
+    pg.Np = h->Np; pg.rT = h->drT[0] + i0; pg.mu_part = h->dmu_part[0] + i0; pg.w_part = h->dw_part[0] + i0;
+    pg.rTs = h->drT[1]; pg.mu_s = h->dmu_part[1]; pg.w_s = h->dw_part[1]; pg.sel = cx.psel; pg.map = cx.pmap;
+    HIPCHK(h, launch_prune_gather(pg, st));
+    cx.prune_pending += rcount / 4;
+  }
+  // the buffer goes through the contraction behind the last chunk, and whenever the next chunk's quarter might not fit
+  const bool flush = cx.prune_pending > 0 && (c + 1 == c_end || cx.prune_pending + Mc / 4 > Ms);
+  HIPCHK(h, hipEventRecord(ev[2], st));
+  // in place or gathered is decided on the device: both contractions are queued, workgroups past the live count return at once
+  if (rcount > 0) {
+    ContractArgs ki = ka;
+    ki.rT = h->drT[0] + i0; ki.ss_part = h->dss_part + i0; ki.nMt = (int)((rcount + 63) / 64); ki.live = pctl + 1;
+    HIPCHK(h, launch_contract(ki, st));
+  }
+  if (flush) {
+    ContractArgs kf = ka;
+    kf.rT = h->drT[1]; kf.ss_part = cx.dss_surv; kf.Mc = Ms; kf.nMt = (int)(Ms / 64); kf.live = pctl + 0;
+    HIPCHK(h, launch_contract(kf, st));
+  }
+  HIPCHK(h, hipEventRecord(ev[3], st));
+  if (rcount > 0) {
+    AcqArgs ai = model;
+    ai.mu_part = h->dmu_part[0] + i0; ai.w_part = h->dw_part[0] + i0; ai.ss_part = h->dss_part + i0; ai.Mc = Mc; ai.mcount = rcount;
+    ai.m0 = m0 + i0; ai.live = pctl + 1;
+    HIPCHK(h, launch_acquisition(ai, st));
+    HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 1, 0, q, h->dbest_val, h->dbest_idx, st));
+  }
+  if (flush) {
+    AcqArgs af = model;
+    af.mu_part = h->dmu_part[1]; af.w_part = h->dw_part[1]; af.ss_part = cx.dss_surv; af.Mc = Ms; af.mcount = Ms; af.m0 = 0;
+    af.live = pctl + 0; af.map = cx.pmap;
+    HIPCHK(h, launch_acquisition(af, st));
+    HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 0, 0, q, h->dbest_val, h->dbest_idx, st));
+    HIPCHK(h, launch_prune_flushed(pctl, st));
+    cx.prune_pending = 0;
+  }
+  HIPCHK(h, hipEventRecord(ev[4], st));
+  return BOGP_OK;
+}
+
+// Chunks [c_begin, c_end): producer -> contraction -> criteria (or the pruned flow).  pilot_done (a pruned sweep that began on the
+// one-pass flow): thresholds, control words and the pilot rows' winners are in place -- chunk 0 starts behind the pilot.
+// Two-stream mode (cx.overlap): the producer of chunk c + 1 runs on stP beside the contraction of chunk c, what it writes double buffered.
+static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c_end, bool pilot_done) {
+  const SweepRequest& rq = cx.rq;
+  hipStream_t st = cx.st, stP = cx.stP;
+  const int64_t M = cx.M, Mc = cx.g.Mc;
+  const int Np = h->Np, S = cx.g.S;
+  const bool overlap = cx.overlap, vx = cx.vx;
+  const AcqArgs model = acq_model_args(h, rq, S, cx.nJ_main, cx.nblk_total);
   for (int64_t c = c_begin; c < c_end; ++c) {
     const int b = overlap ? (int)(c & 1) : 0;
     hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
     const int64_t m0 = c * Mc;
     const int64_t mcount = std::min<int64_t>(Mc, M - m0);
     const int64_t Mc_eff = ((mcount + 63) / 64) * 64;  // rows actually launched; array stride stays Mc
-    CorrArgs ca;
-    ca.Xs = h->dXs; ca.M = M; ca.m0 = m0; ca.Mc = Mc; ca.d = d; ca.Np = Np; ca.nblk_per_split = nblk_per_split;
-    ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
-    ca.rT = h->drT[b]; ca.mu_part = h->dmu_part[b]; ca.w_part = h->dw_part[b];
-    if (pv > 0) {
-      ca.pv = pv; ca.Wrow = h->dWpT; ca.wld = (h->p + 127) / 128 * 128; ca.t_part = h->dtpart[b];
+    CorrArgs ca = corr_chunk_args(h, cx.g, m0, b);
+    if (cx.pv > 0) {
+      ca.pv = cx.pv; ca.Wrow = h->dWpT; ca.wld = (h->p + 127) / 128 * 128; ca.t_part = h->dtpart[b];
     }
     ContractArgs ka;
-    ka.rT = h->drT[b]; ka.Vp = vx ? h->dVpx : h->dVp; ka.ss_part = h->dss_part; ka.Mc = Mc; ka.nMt = (int)(Mc_eff / 64); ka.nJ = nJ;
-    ka.NJ16 = NJ16; ka.NKP = Nrows / 8;
+    ka.rT = h->drT[b]; ka.Vp = vx ? h->dVpx : h->dVp; ka.ss_part = h->dss_part; ka.Mc = Mc; ka.nMt = (int)(Mc_eff / 64); ka.nJ = cx.nJ;
+    ka.NJ16 = cx.NJ16; ka.NKP = cx.Nrows / 8;
     // producer: may reuse buffer b only after chunk c-2 (its previous user) is completely done
     if (overlap && c >= 2) HIPCHK(h, hipStreamWaitEvent(stP, h->ev[(size_t)((c - 2) * EPC + 4)], 0));
     // trend-rows models: k_trend_rows (below, on the producer stream) writes h->dmtrend, which is NOT double buffered -- chunk c - 1's
     // k_acquisition on the main stream must have read it first (without this wait chunk c - 1 could get chunk c's means)
     if (overlap && vx && c >= 1) HIPCHK(h, hipStreamWaitEvent(stP, h->ev[(size_t)((c - 1) * EPC + 4)], 0));
-    if (h->hXs_lazy) {  // lazily uploaded candidates: this chunk's rows must have arrived (chunk 0: copied here; later ones: below)
-      int el = lazy_copy_to(h, m0 + mcount);
-      if (el) return el;
-      if ((el = lazy_wait(h, stP))) return el;
-      if (stP != st && (el = lazy_wait(h, st))) return el;
-    }
+    int e;  // lazily uploaded candidates: this chunk's rows must have arrived (chunk 0: copied here; later ones: below)
+    if ((e = lazy_copy_to(h, m0 + mcount)) || (e = lazy_wait(h, stP)) || (stP != st && (e = lazy_wait(h, st)))) return e;
     HIPCHK(h, hipEventRecord(ev[0], stP));
     const int64_t skip = pilot_done && c == 0 ? std::min<int64_t>(PRUNE_PILOT, mcount) : 0;  // (a multiple of 64)
     if (skip > 0) {
@@ -663,306 +741,235 @@ int bogp::run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, con
     if (Mc_eff > skip) HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)((Mc_eff - skip) / 64), S, stP));
     if (vx) {  // rows Np .. Ne - 1 = 0 (their columns of the factor are zero: any FINITE value would do), rows Ne .. = -f(x*), then zeros
       if (h->vx_Ne > Np) HIPCHK(h, hipMemsetAsync(h->drT[b] + (size_t)Np * Mc, 0, (size_t)(h->vx_Ne - Np) * Mc * sizeof(double), stP));
-      HIPCHK(h, launch_trend_rows(h->trend, h->dXs, m0, mcount, Mc_eff, d, Mc, h->dbetav, h->drT[b] + (size_t)h->vx_Ne * Mc, h->p,
+      HIPCHK(h, launch_trend_rows(h->trend, h->dXs, m0, mcount, Mc_eff, h->d, Mc, h->dbetav, h->drT[b] + (size_t)h->vx_Ne * Mc, h->p,
                                   h->vx_Nt - h->vx_Ne, h->dmtrend, stP));
     }
     HIPCHK(h, hipEventRecord(ev[1], stP));
     if (overlap) HIPCHK(h, hipStreamWaitEvent(st, ev[1], 0));
-    if (prune) {
-      AcqArgs aa;
-      memset(&aa, 0, sizeof(aa));
-      aa.S = S; aa.nJ = nJ_main; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend; aa.sigma2 = h->sigma2; aa.q = q;
-      for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-      aa.plugin = plugin; aa.minimize = minimize; aa.M = M; aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
-      int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
-      if (skip > 0) i0 = skip;
-      else if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
-        const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
-        hipEvent_t* evp = &h->ev[(size_t)(nchunk * EPC + 1)];
-        HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
-        HIPCHK(h, hipEventRecord(evp[0], st));
-        ContractArgs kp = ka;
-        kp.nMt = (int)((P + 63) / 64);
-        HIPCHK(h, launch_contract(kp, st));
-        HIPCHK(h, hipEventRecord(evp[1], st));
-        AcqArgs ap = aa;
-        ap.mu_part = h->dmu_part[0]; ap.w_part = h->dw_part[0]; ap.ss_part = h->dss_part; ap.Mc = Mc; ap.mcount = P; ap.m0 = 0;
-        HIPCHK(h, launch_acquisition(ap, st));
-        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, P, q, h->dbest_val, h->dbest_idx, st));
-        i0 = P;  // (a multiple of 256 unless the chunk ends with it)
-      }
-      const int64_t rcount = mcount - i0;
-      if (rcount > 0) {  // bound -> scan + decision -> compaction -> gather
-        PruneBoundArgs pb;
-        memset(&pb, 0, sizeof(pb));
-        pb.mu_part = h->dmu_part[0] + i0; pb.w_part = h->dw_part[0] + i0; pb.S = S; pb.Mc = Mc; pb.rcount = rcount;
-        pb.beta = h->beta; pb.G = h->G; pb.sigma2 = h->sigma2; pb.plugin = plugin; pb.estimate_trend = h->estimate_trend;
-        pb.minimize = minimize; pb.q = q;
-        for (int i = 0; i < q; ++i) { pb.acq_id[i] = acq_id[i]; pb.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-        pb.best_val = h->dbest_val; pb.flags = pflags; pb.blk_count = pblk_count;
-        HIPCHK(h, launch_prune_bound(pb, st));
-        HIPCHK(h, launch_prune_scan(pblk_count, (rcount + 255) / 256, poffsets, rcount, Ms, pctl, st));
-        PruneGatherArgs pg;
-        pg.ctl = pctl; pg.flags = pflags; pg.offsets = poffsets; pg.rcount = rcount; pg.m0 = m0 + i0; pg.Mc = Mc; pg.Ms = Ms; pg.S = S;
-        pg.Np = Np; pg.rT = h->drT[0] + i0; pg.mu_part = h->dmu_part[0] + i0; pg.w_part = h->dw_part[0] + i0;
-        pg.rTs = h->drT[1]; pg.mu_s = h->dmu_part[1]; pg.w_s = h->dw_part[1]; pg.sel = psel; pg.map = pmap;
-        HIPCHK(h, launch_prune_gather(pg, st));
-        prune_pending += rcount / 4;
-      }
-      // the buffer goes through the contraction behind the last chunk, and whenever the next chunk's quarter might not fit
-      const bool flush = prune_pending > 0 && (c + 1 == c_end || prune_pending + Mc / 4 > Ms);
+    if (cx.prune) {
+      if ((e = sweep_pruned_chunk(h, cx, model, ka, c, c_end, m0, mcount, skip))) return e;
+    } else {
       HIPCHK(h, hipEventRecord(ev[2], st));
-      // in place or gathered is decided on the device: both contractions are queued, workgroups past the live count return at once
-      ContractArgs kf = ka;
-      kf.rT = h->drT[1]; kf.ss_part = dss_surv; kf.Mc = Ms; kf.nMt = (int)(Ms / 64); kf.live = pctl + 0;
-      if (rcount > 0) {
-        ContractArgs ki = ka;
-        ki.rT = h->drT[0] + i0; ki.ss_part = h->dss_part + i0; ki.nMt = (int)((rcount + 63) / 64); ki.live = pctl + 1;
-        HIPCHK(h, launch_contract(ki, st));
-      }
-      if (flush) HIPCHK(h, launch_contract(kf, st));
+      // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
+      // and k_acquisition sums zero variance groups (its MSE output is not read)
+      if (rq.need_var) HIPCHK(h, launch_contract(ka, st));
       HIPCHK(h, hipEventRecord(ev[3], st));
-      if (rcount > 0) {
-        AcqArgs ai = aa;
-        ai.mu_part = h->dmu_part[0] + i0; ai.w_part = h->dw_part[0] + i0; ai.ss_part = h->dss_part + i0; ai.Mc = Mc; ai.mcount = rcount;
-        ai.m0 = m0 + i0; ai.live = pctl + 1;
-        HIPCHK(h, launch_acquisition(ai, st));
-        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 1, 0, q, h->dbest_val, h->dbest_idx, st));
-      }
-      if (flush) {
-        AcqArgs af = aa;
-        af.mu_part = h->dmu_part[1]; af.w_part = h->dw_part[1]; af.ss_part = dss_surv; af.Mc = Ms; af.mcount = Ms; af.m0 = 0;
-        af.live = pctl + 0; af.map = pmap;
-        HIPCHK(h, launch_acquisition(af, st));
-        HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, pctl + 0, 0, q, h->dbest_val, h->dbest_idx, st));
-        HIPCHK(h, launch_prune_flushed(pctl, st));
-        prune_pending = 0;
+      AcqArgs aa = model;
+      aa.mu_part = h->dmu_part[b]; aa.w_part = h->dw_part[b]; aa.ss_part = h->dss_part; aa.nJ = rq.need_var ? cx.nJ_main : 0; aa.Mc = Mc;
+      aa.nJ_plus = vx ? cx.nJ - cx.nJ_main : 0;
+      aa.mcount = mcount; aa.m0 = m0; aa.blk_offset = cx.blk_offset;
+      if (h->p > 1 && (e = sweep_trend_chunk(h, cx, b, m0, mcount, Mc_eff, aa))) return e;
+      if (rq.eh) {  // the m-target posterior + EHVI of this chunk in place of the q single-target criteria (kernels_ehvi.hip)
+        EhviArgs ea = *rq.eh;
+        ea.rT = h->drT[b]; ea.ss_part = h->dss_part; ea.w_part = h->dw_part[b]; ea.S = S; ea.nJ = cx.nJ_main; ea.Mc = Mc;
+        ea.mcount = mcount; ea.m0 = m0; ea.beta = h->beta; ea.G = h->G; ea.estimate_trend = h->estimate_trend;
+        ea.ehvi_out = h->dacq_out; ea.mu_out = rq.want_out ? h->dmu_out : nullptr; ea.mse_out = rq.want_out ? h->dmse_out : nullptr;
+        ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = cx.blk_offset;
+        HIPCHK(h, launch_ehvi(ea, st));
+      } else {
+        HIPCHK(h, launch_acquisition(aa, st));
       }
       HIPCHK(h, hipEventRecord(ev[4], st));
-      blk_offset += (mcount + 255) / 256;
-      if (h->hXs_lazy) {  // the next chunk's rows travel while this chunk's kernels (queued above) run
-        const int el = lazy_copy_to(h, m0 + mcount + Mc);
-        if (el) return el;
-      }
-      continue;
     }
-    HIPCHK(h, hipEventRecord(ev[2], st));
-    // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
-    // and k_acquisition sums zero variance groups (its MSE output is not read)
-    if (need_var) HIPCHK(h, launch_contract(ka, st));
-    HIPCHK(h, hipEventRecord(ev[3], st));
-    AcqArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.mu_part = h->dmu_part[b]; aa.w_part = h->dw_part[b]; aa.ss_part = h->dss_part; aa.S = S; aa.nJ = need_var ? nJ_main : 0; aa.Mc = Mc;
-    aa.nJ_plus = vx ? nJ - nJ_main : 0;
-    aa.mcount = mcount; aa.m0 = m0; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend;
-    aa.sigma2 = h->sigma2; aa.mu_out = want_out ? h->dmu_out : nullptr; aa.mse_out = want_out ? h->dmse_out : nullptr;
-    aa.q = q;
-    for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    aa.plugin = plugin; aa.minimize = minimize; aa.acq_out = want_acq_out ? h->dacq_out : nullptr; aa.M = M;
-    aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.blk_offset = blk_offset; aa.nblk_total = nblk_total;
-    if (h->p > 1) {
-      // polynomial trend: mean f(x*) . beta, and under universal kriging u = G^-T (Ft^T L^-1 r - f(x*)) (gpr.py:496-498):
-      // T = r W (Mc x p, a tile product on the chunk that k_contract has just read), c = T - f(x*), u^T u = c^T (Ft^T Ft)^-1 c
-      // The two products run on k_mm128 (128 x 128 tiles, kernels_chol.hip) when the chunk is whole tiles -- the default
-      // chunk sizes are; rows past Mc_eff of the last tile are computed on stale chunk data and never read -- and on the
-      // generic k_gemm64 otherwise.
-      const int pt = h->p, pp = (pt + 127) / 128 * 128;
-      const bool tiles128 = Mc % 128 == 0;
-      const int TI = (int)((Mc_eff + 127) / 128);
-      const double one = 1.0, zero = 0.0;
-      double* Tt = nullptr;
-      if (vx) {
-        // (mtrend was written by k_trend_rows beside the chunk's extra rows; |u|^2 comes out of the contraction)
-      } else if (pv > 0) {
-        HIPCHK(h, launch_trend_small(h->trend, h->dXs, m0, mcount, d, Mc, h->dbetav, h->dtpart[b], S, pv, pt, h->dSinv, h->dmtrend, h->duu, st));
-        aa.uu = h->duu;
-      } else {
-      if (h->estimate_trend && !vx_model) {
-        if (tiles128)
-          HIPCHK(h, launch_mm128_gen(h->drT[b], (int)Mc, h->dWpT, pp, h->dTt, (int)Mc, TI, pp / 128, Np, st));
-        else
-          HIPCHK(h, launch_gemm(0, 0, (int)Mc_eff, pt, Np, one, h->drT[b], (int)Mc, h->dWp, Np, zero, h->dTt, (int)Mc, st, 0, &h->gsplit));
-        Tt = h->dTt;
-      }
-      HIPCHK(h, launch_trend_terms(h->trend, h->dXs, m0, mcount, d, Mc, h->dbetav, Tt, h->dmtrend, st));
-      if (h->estimate_trend && !vx_model) {
-        if (tiles128)
-          HIPCHK(h, launch_mm128_gen(h->dTt, (int)Mc, h->dSinvP, pp, h->dCS, (int)Mc, TI, pp / 128, pp, st));
-        else
-          HIPCHK(h, launch_gemm(0, 0, (int)Mc_eff, pt, pt, one, h->dTt, (int)Mc, h->dSinv, pt, zero, h->dCS, (int)Mc, st, 0, &h->gsplit));
-        HIPCHK(h, launch_rowdot(h->dTt, h->dCS, Mc, mcount, pt, h->duu, st));
-        aa.uu = h->duu;
-      }
-      }  // pv == 0
-      aa.mtrend = h->dmtrend;
-      aa.estimate_trend = 0;  // the scalar w_part path is for the constant basis
-    }
-    if (eh) {  // the m-target posterior + EHVI of this chunk in place of the q single-target criteria (kernels_ehvi.hip)
-      EhviArgs ea = *eh;
-      ea.rT = h->drT[b]; ea.ss_part = h->dss_part; ea.w_part = h->dw_part[b]; ea.S = S; ea.nJ = nJ_main; ea.Mc = Mc;
-      ea.mcount = mcount; ea.m0 = m0; ea.beta = h->beta; ea.G = h->G; ea.estimate_trend = h->estimate_trend;
-      ea.ehvi_out = h->dacq_out; ea.mu_out = want_out ? h->dmu_out : nullptr; ea.mse_out = want_out ? h->dmse_out : nullptr;
-      ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = blk_offset;
-      HIPCHK(h, launch_ehvi(ea, st));
-    } else {
-      HIPCHK(h, launch_acquisition(aa, st));
-    }
-    HIPCHK(h, hipEventRecord(ev[4], st));
-    blk_offset += (mcount + 255) / 256;
-    if (h->hXs_lazy) {  // the next chunk's rows travel while this chunk's kernels (queued above) run
-      const int el = lazy_copy_to(h, m0 + mcount + Mc);
-      if (el) return el;
-    }
+    cx.blk_offset += (mcount + 255) / 256;
+    if ((e = lazy_copy_to(h, m0 + mcount + Mc))) return e;  // the next chunk's rows travel while this chunk's kernels (queued above) run
   }
   return BOGP_OK;
-  };  // run_chunks
+}
 
-  if (!onepass) {
-    if ((e = run_chunks(0, nchunk, false))) return e;
-    if (prune) h->prune_path = BOGP_PRUNE_PATH_CHUNKS;
+// the next event of a one-pass sweep, recorded on st; *idx = its index in h->ev
+static int mark_event(bogp_handle* h, hipStream_t st, size_t* ev_next, int* idx) {
+  hipEvent_t ev1 = get_event(h, *ev_next);
+  if (!ev1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  HIPCHK(h, hipEventRecord(ev1, st));
+  *idx = (int)(*ev_next)++;
+  return BOGP_OK;
+}
+// a producer (kind 0) or contraction (kind 1) launch between two events of its own (h->t_spans: kind, begin, end)
+template <class Launch>
+static int timed_span(bogp_handle* h, hipStream_t st, size_t* ev_next, int kind, Launch launch) {
+  int a = 0, b = 0, e;
+  if ((e = mark_event(h, st, ev_next, &a))) return e;
+  HIPCHK(h, launch());
+  if ((e = mark_event(h, st, ev_next, &b))) return e;
+  h->t_spans.push_back(kind); h->t_spans.push_back(a); h->t_spans.push_back(b);
+  return BOGP_OK;
+}
+
+// One pass: pilot -> pilot estimate -> per segment: producer without the store, bound, scan, survivor indices ->
+// rounds.  Two fall-backs to sweep_chunks: the whole sweep where the pilot's own rows show that little can be pruned, one segment where
+// too many of its rows survive.  The host waits twice per decision (survivors_of).
+static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
+  hipStream_t st = cx.st;
+  const int64_t M = cx.M, Mc = cx.g.Mc, Ms = cx.Ms, nchunk = cx.g.nchunk, nblk_total = cx.nblk_total;
+  const int S = cx.g.S, q = cx.rq.q, kernel = h->kernel;
+  long long* const pctl = cx.pctl;
+  const int64_t P = std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
+  long long* const hcount = reinterpret_cast<long long*>(h->hfit + 3504);  // pinned: the one count the host waits for
+  size_t ev_next = (size_t)(nchunk * EPC + 3);
+  h->t_spans.clear(); h->t_chunks.clear();
+  int e;
+  // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
+  auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out) -> int {
+    HIPCHK(h, launch_prune_scan(cx.pblk_count, (rows + 255) / 256, cx.poffsets, rows, -1, pctl, st));
+    if (index_from >= 0) HIPCHK(h, launch_prune_index(cx.pflags, cx.poffsets, rows, index_from, cx.sidx_cap, cx.psidx, st));
+    HIPCHK(h, hipMemcpyAsync(hcount, pctl + PRUNE_CTL_TOTAL, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    *out = *hcount;
+    return BOGP_OK;
+  };
+  const CorrArgs cc = corr_chunk_args(h, cx.g, 0, 1);  // the survivor buffer's producer (Ms = Mc): the pilot, then every round
+  ContractArgs kc;                                     // ... and its contraction
+  kc.rT = h->drT[1]; kc.Vp = h->dVp; kc.ss_part = cx.dss_surv; kc.Mc = Ms; kc.nJ = cx.nJ; kc.NJ16 = cx.NJ16; kc.NKP = cx.Nrows / 8;
+  AcqArgs aa = acq_model_args(h, cx.rq, S, cx.nJ_main, nblk_total);
+  aa.mu_part = h->dmu_part[1]; aa.w_part = h->dw_part[1]; aa.ss_part = cx.dss_surv; aa.Mc = Ms; aa.m0 = 0;
+  PruneBoundArgs pb = prune_bound_args(h, cx);
+  int contract_launches = 0;
+  // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
+  auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
+    kc.nMt = (int)((cnt + 63) / 64);
+    if (int e2 = timed_span(h, st, &ev_next, 1, [&] { return launch_contract(kc, st); })) return e2;
+    ++contract_launches;
+    aa.mcount = cnt; aa.map = map;
+    HIPCHK(h, launch_acquisition(aa, st));
+    HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, cnt, q, h->dbest_val, h->dbest_idx, st));
+    return BOGP_OK;
+  };
+  // a per-chunk path after all: chunks [c0, c1) behind the pilot, with the chunk buffer they need
+  auto fall_back = [&](int64_t c0, int64_t c1, int path) -> int {
+    int e2;
+    if ((e2 = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)cx.Nrows * Mc))) return e2;
+    if ((e2 = sweep_chunks(h, cx, c0, c1, true))) return e2;
+    for (int64_t c = c0; c < c1; ++c) h->t_chunks.push_back(c);
+    contract_launches += (int)(c1 - c0);
+    h->prune_path = path;
+    return BOGP_OK;
+  };
+  if ((e = mark_event(h, st, &ev_next, &h->t_total[0]))) return e;
+  HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
+  if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cc, (int)(P / 64), S, st); }))) return e;
+  if ((e = evaluate(P, nullptr))) return e;
+  // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
+  long long pilot_surv = 0;
+  pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
+  HIPCHK(h, launch_prune_bound(pb, st));
+  if ((e = survivors_of(P, -1, &pilot_surv))) return e;
+  if (prune_decide(P, pilot_surv, 1, 0) == BOGP_PRUNE_PATH_CHUNKS) {
+    if ((e = fall_back(0, nchunk, BOGP_PRUNE_PATH_CHUNKS))) return e;
   } else {
-    // ---- one pass: pilot -> pilot estimate -> per segment: producer without the store, bound, scan, survivor indices -> rounds ----
-    const int64_t P = std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
-    long long* const hcount = reinterpret_cast<long long*>(h->hfit + 3504);  // pinned: the one count the host waits for
-    size_t ev_next = (size_t)(nchunk * EPC + 3);
-    h->t_spans.clear();
-    h->t_chunks.clear();
-    auto mark = [&](int* idx) -> int {
-      hipEvent_t ev1 = get_event(h, ev_next);
-      if (!ev1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-      HIPCHK(h, hipEventRecord(ev1, st));
-      *idx = (int)ev_next++;
-      return BOGP_OK;
-    };
-    // a producer (kind 0) or contraction (kind 1) launch between two events of its own
-    auto timed = [&](int kind, hipError_t (*launch)(const void*, hipStream_t), const void* args) -> int {
-      int a = 0, b2 = 0, e2;
-      if ((e2 = mark(&a))) return e2;
-      HIPCHK(h, launch(args, st));
-      if ((e2 = mark(&b2))) return e2;
-      h->t_spans.push_back(kind); h->t_spans.push_back(a); h->t_spans.push_back(b2);
-      return BOGP_OK;
-    };
-    struct CorrCall { int kernel; CorrArgs a; int nMt, S; };
-    auto corr_fn = [](const void* p, hipStream_t s2) { const CorrCall* c = (const CorrCall*)p; return launch_corr_chunk(c->kernel, c->a, c->nMt, c->S, s2); };
-    auto contract_fn = [](const void* p, hipStream_t s2) { return launch_contract(*(const ContractArgs*)p, s2); };
-    // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
-    auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out) -> int {
-      HIPCHK(h, launch_prune_scan(pblk_count, (rows + 255) / 256, poffsets, rows, -1, pctl, st));
-      if (index_from >= 0) HIPCHK(h, launch_prune_index(pflags, poffsets, rows, index_from, sidx_cap, psidx, st));
-      HIPCHK(h, hipMemcpyAsync(hcount, pctl + PRUNE_CTL_TOTAL, sizeof(long long), hipMemcpyDeviceToHost, st));
-      HIPCHK(h, hipStreamSynchronize(st));
-      *out = *hcount;
-      return BOGP_OK;
-    };
-    CorrCall cc;
-    cc.kernel = h->kernel; cc.S = S;
-    cc.a.Xs = h->dXs; cc.a.M = M; cc.a.m0 = 0; cc.a.Mc = Ms; cc.a.d = d; cc.a.Np = Np; cc.a.nblk_per_split = nblk_per_split;
-    cc.a.sqrt_theta = h->dsqrt_theta; cc.a.XthT = h->dXthT; cc.a.xnorm = h->dXnorm; cc.a.gamma = h->dgamma; cc.a.wvec = h->dw;
-    cc.a.rT = h->drT[1]; cc.a.mu_part = h->dmu_part[1]; cc.a.w_part = h->dw_part[1];
-    ContractArgs kc;  // the survivor buffer through the contraction: the pilot, then every round
-    kc.rT = h->drT[1]; kc.Vp = h->dVp; kc.ss_part = dss_surv; kc.Mc = Ms; kc.nJ = nJ; kc.NJ16 = NJ16; kc.NKP = Nrows / 8;
-    AcqArgs aa;
-    memset(&aa, 0, sizeof(aa));
-    aa.S = S; aa.nJ = nJ_main; aa.beta = h->beta; aa.G = h->G; aa.estimate_trend = h->estimate_trend; aa.sigma2 = h->sigma2; aa.q = q;
-    for (int i = 0; i < q; ++i) { aa.acq_id[i] = acq_id[i]; aa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    aa.plugin = plugin; aa.minimize = minimize; aa.M = M; aa.blk_val = h->dblk_val; aa.blk_idx = h->dblk_idx; aa.nblk_total = nblk_total;
-    aa.mu_part = h->dmu_part[1]; aa.w_part = h->dw_part[1]; aa.ss_part = dss_surv; aa.Mc = Ms; aa.m0 = 0;
-    PruneBoundArgs pb;
-    memset(&pb, 0, sizeof(pb));
-    pb.S = S; pb.beta = h->beta; pb.G = h->G; pb.sigma2 = h->sigma2; pb.plugin = plugin; pb.estimate_trend = h->estimate_trend;
-    pb.minimize = minimize; pb.q = q;
-    for (int i = 0; i < q; ++i) { pb.acq_id[i] = acq_id[i]; pb.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    pb.best_val = h->dbest_val; pb.flags = pflags; pb.blk_count = pblk_count;
-    int contract_launches = 0;
-    // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
-    auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
-      kc.nMt = (int)((cnt + 63) / 64);
-      int e2 = timed(1, contract_fn, &kc);
-      if (e2) return e2;
-      ++contract_launches;
-      aa.mcount = cnt; aa.map = map;
-      HIPCHK(h, launch_acquisition(aa, st));
-      HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, cnt, q, h->dbest_val, h->dbest_idx, st));
-      return BOGP_OK;
-    };
-    if ((e = mark(&h->t_total[0]))) return e;
-    HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
-    cc.nMt = (int)(P / 64);
-    if ((e = timed(0, corr_fn, &cc))) return e;
-    if ((e = evaluate(P, nullptr))) return e;
-    // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
-    long long pilot_surv = 0;
-    pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
-    HIPCHK(h, launch_prune_bound(pb, st));
-    if ((e = survivors_of(P, -1, &pilot_surv))) return e;
-    if (prune_decide(P, pilot_surv, 1, 0) == BOGP_PRUNE_PATH_CHUNKS) {
-      if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Nrows * Mc))) return e;
-      if ((e = run_chunks(0, nchunk, true))) return e;
-      for (int64_t c = 0; c < nchunk; ++c) h->t_chunks.push_back(c);
-      contract_launches += (int)nchunk;
-      h->prune_path = BOGP_PRUNE_PATH_CHUNKS;
-    } else {
-      h->prune_path = BOGP_PRUNE_PATH_ONEPASS;
-      for (int64_t s0 = 0; s0 < M; s0 += seg_rows) {
-        const int64_t sb = std::max<int64_t>(P, s0), se = std::min<int64_t>(M, s0 + seg_rows), rows = se - sb;
-        if (rows <= 0) continue;
-        CorrCall cs = cc;  // the segment's partial sums, nothing else
-        cs.a.m0 = sb; cs.a.Mc = seg_stride; cs.a.rT = nullptr; cs.a.store = false; cs.a.mu_part = h->dmu_part[0]; cs.a.w_part = h->dw_part[0];
-        cs.nMt = (int)((rows + 63) / 64);
-        if ((e = timed(0, corr_fn, &cs))) return e;
-        pb.mu_part = h->dmu_part[0]; pb.w_part = h->dw_part[0]; pb.Mc = seg_stride; pb.rcount = rows;
-        HIPCHK(h, launch_prune_bound(pb, st));
-        long long surv = 0;
-        if ((e = survivors_of(rows, sb, &surv))) return e;
-        if (prune_decide(P, pilot_surv, rows, surv) == BOGP_PRUNE_PATH_ONEPASS_FALLBACK) {  // (needs ordered candidates: the pilot saw few such rows)
-          if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Nrows * Mc))) return e;
-          const int64_t c0 = sb / Mc, c1 = (se + Mc - 1) / Mc;
-          if ((e = run_chunks(c0, c1, true))) return e;
-          for (int64_t c = c0; c < c1; ++c) h->t_chunks.push_back(c);
-          contract_launches += (int)(c1 - c0);
-          h->prune_path = BOGP_PRUNE_PATH_ONEPASS_FALLBACK;
-          continue;
-        }
-        for (int64_t k0 = 0; k0 < surv; k0 += Ms) {  // rounds of at most one survivor buffer, in the survivors' order
-          const int64_t cnt = std::min<int64_t>(Ms, surv - k0);
-          HIPCHK(h, launch_prune_rows(h->dXs, psidx + k0, cnt, d, pxc, st));
-          CorrCall cr = cc;
-          cr.a.Xs = pxc; cr.a.M = cnt; cr.nMt = (int)((cnt + 63) / 64);
-          if ((e = timed(0, corr_fn, &cr))) return e;
-          if ((e = evaluate(cnt, psidx + k0))) return e;
-          ++h->prune_rounds;
-        }
-        h->prune_survivors += surv;
+    h->prune_path = BOGP_PRUNE_PATH_ONEPASS;
+    for (int64_t s0 = 0; s0 < M; s0 += cx.seg_rows) {
+      const int64_t sb = std::max<int64_t>(P, s0), se = std::min<int64_t>(M, s0 + cx.seg_rows), rows = se - sb;
+      if (rows <= 0) continue;
+      CorrArgs cs = cc;  // the segment's partial sums, nothing else
+      cs.m0 = sb; cs.Mc = cx.seg_stride; cs.rT = nullptr; cs.store = false; cs.mu_part = h->dmu_part[0]; cs.w_part = h->dw_part[0];
+      if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
+      pb.mu_part = h->dmu_part[0]; pb.w_part = h->dw_part[0]; pb.Mc = cx.seg_stride; pb.rcount = rows;
+      HIPCHK(h, launch_prune_bound(pb, st));
+      long long surv = 0;
+      if ((e = survivors_of(rows, sb, &surv))) return e;
+      if (prune_decide(P, pilot_surv, rows, surv) == BOGP_PRUNE_PATH_ONEPASS_FALLBACK) {  // (needs ordered candidates: the pilot saw few such rows)
+        if ((e = fall_back(sb / Mc, (se + Mc - 1) / Mc, BOGP_PRUNE_PATH_ONEPASS_FALLBACK))) return e;
+        continue;
       }
+      for (int64_t k0 = 0; k0 < surv; k0 += Ms) {  // rounds of at most one survivor buffer, in the survivors' order
+        const int64_t cnt = std::min<int64_t>(Ms, surv - k0);
+        HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx + k0, cnt, h->d, cx.pxc, st));
+        CorrArgs cr = cc;
+        cr.Xs = cx.pxc; cr.M = cnt;
+        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cr, (int)((cnt + 63) / 64), S, st); }))) return e;
+        if ((e = evaluate(cnt, cx.psidx + k0))) return e;
+        ++h->prune_rounds;
+      }
+      h->prune_survivors += surv;
     }
-    if ((e = mark(&h->t_total[1]))) return e;
-    h->timing_onepass = true;
-    h->n_chunks = contract_launches;
   }
-  if (h->hXs_lazy) {  // every row is on its way; once the copy stream is idle the caller's buffer is no longer needed
-    const int el = lazy_finish(h);
-    if (el) return el;
+  if ((e = mark_event(h, st, &ev_next, &h->t_total[1]))) return e;
+  h->timing_onepass = true;
+  h->n_chunks = contract_launches;
+  return BOGP_OK;
+}
+
+int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
+  collect_timing(h);  // the events are about to be re-recorded
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "no committed model: call bogp_commit first");
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "no candidates: call bogp_candidates_upload/bind first");
+  if (rq.q < 0 || rq.q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "q = %d outside [0, %d]", rq.q, BOGP_MAX_Q);
+  HIPCHK(h, hipSetDevice(h->device));
+  const int Np = h->Np, q = rq.q;
+  const int64_t M = h->M;
+  h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0; h->timing_onepass = false;
+  int e;
+  // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- takes neither: it always runs the chunked path below); nothing
+  // to overlap a lazy upload with: the whole upload first (one launch reads every candidate)
+  const bool small_batch = !rq.eh && M <= 32 && h->p == 1;
+  if (small_batch || (!rq.eh && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
+    if ((e = lazy_finish(h))) return e;
+    return small_batch ? sweep_small_batch(h, rq) : sweep_one_launch(h, rq);
   }
+  SweepCtx cx{};
+  cx.rq = rq; cx.M = M; cx.st = h->stream;
+  // trend-rows path (k_pack_Vx): the chunk carries Nt - Np extra rows (the hole up to a whole column group, then -f(x*)), the contraction
+  // runs over the extended factor
+  cx.vx_model = h->vx_Nt > 0 && h->p >= trend_rows_min() && h->estimate_trend;  // the committed model takes the trend-rows path ...
+  cx.vx = cx.vx_model && rq.need_var;                                            // ... and this call needs the variance
+  cx.Nrows = cx.vx ? h->vx_Nt : Np;
+  if ((e = sweep_geometry(h, cx.Nrows, &cx.g))) return e;
+  const int64_t nchunk = cx.g.nchunk;
+  if (nchunk == 1 && (e = lazy_finish(h))) return e;  // (as above)
+  const int cols = contract_cols_per_group();
+  cx.NJ16 = cx.Nrows / 16;
+  cx.nJ_main = (Np + cols - 1) / cols;                             // column groups of V: |L^-1 r|^2
+  cx.nJ = cx.vx ? (cx.Nrows + cols - 1) / cols : cx.nJ_main;       // ... + the groups of the trend rows: |u|^2
+  cx.nblk_total = (M + 255) / 256 + nchunk;
+  // a polynomial basis of at most 32 columns under universal kriging: T = W^T r is accumulated by the producer itself
+  // (k_corr_chunk<K, PV>) and finished by ONE per-candidate launch (k_trend_small); (the tile products it replaces: git 3357059)
+  // (a mean-only call of a trend-rows model keeps the producer the full call uses -- pv = 0 -- so that mu comes out bit-identical)
+  cx.pv = (!cx.vx_model && h->p > 1 && h->estimate_trend) ? corr_trend_columns(h->p) : 0;
+  // Optional two-stream mode (BOGP_OVERLAP=1): the correlation producer of chunk c+1 (FP64 VALU) runs beside the
+  // contraction of chunk c (FP64 MFMA), everything the producer writes double buffered.  Measured on MI355X (r01,
+  // C3): the kernels do overlap (contract 75.9 -> 81.9 ms, corr 6.8 -> 11.7 ms) but the step time is unchanged
+  // (83.3 -> 83.0 ms): the DP pipe is the shared resource.  Off by default: it costs a second 1-GiB chunk buffer.
+  cx.overlap = nchunk > 1 && getenv("BOGP_OVERLAP") && atoi(getenv("BOGP_OVERLAP")) == 1;
+  cx.stP = cx.overlap ? h->stream2 : cx.st;
+  // Pruned sweep (kernels_prune.hip, DESIGN.md 5.22): only the winners leave this call, so a row whose criteria cannot reach the best
+  // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI -- runs as ever.
+  cx.prune = h->prune_mode != 0 && rq.need_var && q > 0 && !rq.want_out && !rq.want_acq_out && !rq.eh && h->p == 1 && !cx.vx_model && !cx.overlap;
+  // one pass: every candidate resident and a producer that exists without its store
+  cx.onepass = cx.prune && h->prune_mode == 1 && nchunk > 1 && !h->hXs_lazy && corr_chunk_without_store(h->kernel, 0, h->dXnorm != nullptr);
+  if ((e = sweep_workspace(h, cx))) return e;
+  if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * (rq.eh ? rq.eh->m : 1) : 0, rq.want_acq_out))) return e;
+  // the chunks' events, the two-stream mode's begin event, the pilot's pair (pruned sweep)
+  for (size_t i = 0; i <= (size_t)(nchunk * EPC + 2); ++i)
+    if (!get_event(h, i)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  if (cx.overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
+    HIPCHK(h, hipEventRecord(h->ev[(size_t)(nchunk * EPC)], cx.st));
+    HIPCHK(h, hipStreamWaitEvent(cx.stP, h->ev[(size_t)(nchunk * EPC)], 0));
+  }
+  if (!cx.onepass) {
+    if ((e = sweep_chunks(h, cx, 0, nchunk, false))) return e;
+    if (cx.prune) h->prune_path = BOGP_PRUNE_PATH_CHUNKS;
+    h->n_chunks = (int)nchunk;
+  } else if ((e = sweep_onepass(h, cx))) {
+    return e;
+  }
+  // every row is on its way; once the copy stream is idle the caller's buffer is no longer needed
+  if ((e = lazy_finish(h))) return e;
   // (a pruned sweep kept its running best in dbest_* all along)
-  if (q > 0 && !prune) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dbest_val, h->dbest_idx, st));
-  if (!onepass) h->n_chunks = (int)nchunk;
-  h->timing_pending = true;
-  h->timing_fused = false;
-  h->timing_prune = prune;
-  h->prune_used = prune;
-  h->contracted_rows = need_var ? M : 0;
-  if (sync || overlap) HIPCHK(h, hipStreamSynchronize(st));
-  if (overlap) HIPCHK(h, hipStreamSynchronize(stP));
+  if (q > 0 && !cx.prune) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, cx.blk_offset, cx.nblk_total, q, h->dbest_val, h->dbest_idx, cx.st));
+  h->timing_pending = true; h->timing_fused = false; h->timing_prune = cx.prune; h->prune_used = cx.prune;
+  h->contracted_rows = rq.need_var ? M : 0;
+  if (rq.sync || cx.overlap) HIPCHK(h, hipStreamSynchronize(cx.st));
+  if (cx.overlap) HIPCHK(h, hipStreamSynchronize(cx.stP));
   return BOGP_OK;
 }
 
 extern "C" int bogp_predict(bogp_handle* h, double* mu, double* mse) {
   if (!h) return BOGP_ERR_INVALID;
   if (!mu) FAIL(h, BOGP_ERR_INVALID, "bogp_predict: mu must be non-null");
-  int rc = run_sweep(h, true, 0, nullptr, nullptr, 0.0, 1, false, mse != nullptr);
-  if (rc) return rc;
+  SweepRequest rq;
+  rq.want_out = true; rq.need_var = mse != nullptr;
+  if (int rc = run_sweep(h, rq)) return rc;
   HIPCHK(h, hipMemcpy(mu, h->dmu_out, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
   if (mse) HIPCHK(h, hipMemcpy(mse, h->dmse_out, (size_t)h->M * sizeof(double), hipMemcpyDeviceToHost));
   return BOGP_OK;
@@ -974,15 +981,12 @@ extern "C" int bogp_sweep(bogp_handle* h, int q, const int* acq_id, const double
   if (q <= 0 || !acq_id || (!best_val != !best_idx)) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep: q > 0, non-null acq_id, and best_val / best_idx both given or both NULL");
   const bool local = best_val != nullptr;  // NULL outputs: the winners stay on the device for bogp_exchange_argmax
   if (!local && acq_out) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep: acq_out needs best_val / best_idx");
-  for (int i = 0; i < q; ++i) {
-    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
-    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;  // epsilon = 0 is plain PI
-    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
-      FAIL(h, BOGP_ERR_INVALID, "acquisition parameter %d must be > 0 (the reference asserts alpha/epsilon/t > 0)", i);
-  }
+  int rc;
+  if ((rc = check_criteria(h, q, acq_id, acq_par))) return rc;
   invalidate_sweep_results(h);
-  int rc = run_sweep(h, false, q, acq_id, acq_par, plugin, minimize, acq_out != nullptr, true, local);
-  if (rc) return rc;
+  SweepRequest rq;
+  rq.q = q; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.minimize = minimize; rq.want_acq_out = acq_out != nullptr; rq.sync = local;
+  if ((rc = run_sweep(h, rq))) return rc;
   h->last_q = q;  // dbest_val / dbest_idx hold this sweep's winners for bogp_exchange_argmax
   if (!local) return BOGP_OK;  // queued, not waited for: the exchange that follows is ordered behind it on the stream
   HIPCHK(h, hipMemcpy(best_val, h->dbest_val, q * sizeof(double), hipMemcpyDeviceToHost));
@@ -996,15 +1000,12 @@ extern "C" int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const d
   if (!h) return BOGP_ERR_INVALID;
   if (k <= 0 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_topk: k = %d outside [1, %d]", k, BOGP_MAX_TOPK);
   if (q <= 0 || !acq_id || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_topk: q > 0 and non-null acq_id/best_val/best_idx required");
-  for (int i = 0; i < q; ++i) {
-    if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
-    const bool zero_ok = acq_id[i] == BOGP_ACQ_EPSILON_PI;
-    if (acq_id[i] != BOGP_ACQ_EI && (!acq_par || !(acq_par[i] > 0 || (zero_ok && acq_par[i] == 0))))
-      FAIL(h, BOGP_ERR_INVALID, "acquisition parameter %d must be > 0", i);
-  }
+  int rc;
+  if ((rc = check_criteria(h, q, acq_id, acq_par))) return rc;
   invalidate_sweep_results(h);  // run_sweep below overwrites dbest_* as well
-  int rc = run_sweep(h, false, q, acq_id, acq_par, plugin, minimize, true);  // keeps the q x M values on the device
-  if (rc) return rc;
+  SweepRequest rq;  // (want_acq_out: keeps the q x M values on the device)
+  rq.q = q; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.minimize = minimize; rq.want_acq_out = true;
+  if ((rc = run_sweep(h, rq))) return rc;
   // rank 0 is the sweep's own argmax; ranks 1..k-1 repeat the argmax with the winners so far masked out -- all q criteria
   // per launch, the winners kept on the device: 2 k queued launches and ONE read-back of q x k (value, index) pairs
   const int64_t M = h->M;
@@ -1057,6 +1058,7 @@ extern "C" int bogp_last_prune_path(bogp_handle* h, int* path, int64_t* survivor
 extern "C" int bogp_prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t segment_rows, int64_t segment_survivors) {
   return prune_decide(pilot_rows, pilot_survivors, segment_rows, segment_survivors);
 }
+extern "C" int64_t bogp_sweep_chunk_rows(int64_t rows, int64_t M, int64_t chunk_bytes) { return sweep_chunk_rows(rows, M, chunk_bytes); }
 
 extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
   if (!h) return BOGP_ERR_INVALID;

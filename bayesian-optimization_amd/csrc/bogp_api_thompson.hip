@@ -84,14 +84,11 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   const int64_t M = h->M;
   const int N4 = (N + 3) & ~3;
 
-  // ---- geometry: the producer's chunks as the believer plans them (chunk bytes, slices of 8 x 32 training rows)
-  size_t chunk_bytes = (size_t)1 << 30;
-  if (const char* env = getenv("BOGP_CHUNK_MB")) chunk_bytes = (size_t)std::max(1, atoi(env)) << 20;
-  const int64_t Mpad = ((M + 63) / 64) * 64;
-  int64_t Mc = (int64_t)(chunk_bytes / ((size_t)Np * sizeof(double)) / 64) * 64;
-  Mc = std::max<int64_t>(64, std::min<int64_t>(Mc, Mpad));
-  const int64_t nchunk = (M + Mc - 1) / Mc, nblk_total = (M + 63) / 64 + nchunk, nblk256 = (M + 255) / 256;
-  const int S = (Np / 32 + 7) / 8;
+  // ---- geometry: the sweep's own for a constant-trend model; one block record per 64 rows
+  SweepGeometry geo;
+  if ((rc = sweep_geometry(h, Np, &geo))) return rc;
+  const int64_t Mc = geo.Mc, nchunk = geo.nchunk, nblk_total = (M + 63) / 64 + nchunk, nblk256 = (M + 255) / 256;
+  const int S = geo.S;
   const bool store = k > 1 || paths_out != nullptr;
 
   // dth_small: omega (L d) | phase (L) | W (16 L) | -g (16 N4) | s (N q) | V s (N q) | R^-1 s (N q)
@@ -190,13 +187,7 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
     hipEvent_t c0 = event(), c1 = event(), c2 = event();
     if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
     HIPCHK(h, hipEventRecord(c0, st));
-    if (conditioned) {
-      CorrArgs ca;
-      ca.Xs = h->dXs; ca.M = M; ca.m0 = m0; ca.Mc = Mc; ca.d = d; ca.Np = Np; ca.nblk_per_split = 8;
-      ca.sqrt_theta = h->dsqrt_theta; ca.XthT = h->dXthT; ca.xnorm = h->dXnorm; ca.gamma = h->dgamma; ca.wvec = h->dw;
-      ca.rT = h->drT[0]; ca.mu_part = h->dmu_part[0]; ca.w_part = h->dw_part[0];
-      HIPCHK(h, launch_corr_chunk(h->kernel, ca, (int)(Mc_eff / 64), S, st));
-    }
+    if (conditioned) HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, geo, m0, 0), (int)(Mc_eff / 64), S, st));
     HIPCHK(h, hipEventRecord(c1, st));
     ta.row0 = m0; ta.mcount = mcount; ta.blk_offset = blk_offset;
     HIPCHK(h, launch_thompson(ta, st));

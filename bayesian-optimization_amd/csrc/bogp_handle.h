@@ -24,9 +24,25 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
                     double plugin, int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq);
 // bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
 // m-target EHVI of bogp_api_ehvi.hip on the chunked path), and the reset of the winners a sweep left on the device
-int run_sweep(bogp_handle* h, bool want_out, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
-              bool want_acq_out, bool need_var = true, bool sync = true, const EhviArgs* eh = nullptr);
+struct SweepRequest {
+  bool want_out = false, want_acq_out = false;  // mu / MSE of every candidate into dmu_out / dmse_out (EHVI: M x m moments); the q x M values into dacq_out
+  bool need_var = true, sync = true;            // false: the contraction is skipped (predict without eval_MSE); false: queued, not waited for
+  int q = 0, minimize = 1;
+  const int* acq_id = nullptr;
+  const double* acq_par = nullptr;  // (may stay null: EI takes no parameter)
+  double plugin = 0.0;
+  const EhviArgs* eh = nullptr;
+};
+int run_sweep(bogp_handle* h, const SweepRequest& rq);
 void invalidate_sweep_results(bogp_handle* h);
+// bogp_api_sweep.hip, shared with the believer and the Thompson passes: the chunk geometry of a pass over columns of `rows` doubles (the ONE
+// reader of BOGP_CHUNK_MB; fails where sweep_chunk_rows does), the producer's arguments for the chunk at m0 on chunk buffer b, the argmax /
+// value arrays of a pass (nblk block records per criterion, n_out moments or 0), and the validation of q criteria
+struct SweepGeometry { int64_t Mc, nchunk; int S; };  // candidates per chunk (a multiple of 64), chunks, slices of the training set
+int sweep_geometry(bogp_handle* h, int rows, SweepGeometry* g);
+CorrArgs corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int64_t m0, int b);
+int ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out);
+int check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par);
 // bogp_api_sweep.hip, for bogp_api_lift.hip: a pending lazy upload finished (every candidate row on the device); the
 // sweep timing zeroed (a lifted sweep without a feasible row runs no posterior pass)
 int candidates_ready(bogp_handle* h);

@@ -31,6 +31,24 @@ struct CorrArgs {
   int wld = 0;
   double* t_part = nullptr;      // [S][pv][Mc] slice sums of W^T r
 };
+// Chunk geometry of every candidate pass (sweep, believer, Thompson).  The training set is sliced into groups of 8 x 32 rows per producer
+// workgroup: S is a function of N only, so that the grouping of the partial sums of mu (hence every output bit) does not depend on the chunk size.
+constexpr int SWEEP_NBLK_PER_SPLIT = 8;  // (4 / 16 measured: profiles/r05_corr_split_ab.txt)
+inline int sweep_slices(int Np) { return (Np / 32 + SWEEP_NBLK_PER_SPLIT - 1) / SWEEP_NBLK_PER_SPLIT; }
+// Candidates per chunk (exported as bogp_sweep_chunk_rows): what `chunk_bytes` hold of columns of `rows` doubles, in whole 64-row tiles,
+// at least one tile and at most the M candidates padded to one.  The LDS-free kernels address the rows of a chunk through 32-bit lane
+// byte offsets proportional to Mc, of which the largest is 8 (7 Mc + 30):
+//   kernels_posterior.hip  k_contract16d      voffA1 = ((lane >> 4) * Mc + 2 * (lane & 15)) * 8 + 4 * Mc * 8
+//   kernels_chol.hip       mm128_tile_direct  voffR1 = (lk * ldr + 2 * li) * 8 + 4 * ldr * 8, ldr = Mc in the trend product
+//   corr_mfma_body.inc     k_corr_mfma        offR   = (lk * Mc + li) * 8, the smaller one
+// with lane >> 4 = lk <= 3 and li <= 15.  8 (7 Mc + 30) < 2^32 holds up to Mc = 76 695 840, i.e. 76 695 808 in whole tiles; a larger
+// chunk returns -1 and the callers fail.  The trend GEMM's own limit, Mc <= INT_MAX / 2, lies far above and is subsumed.
+constexpr int64_t SWEEP_MAX_CHUNK_ROWS = ((((int64_t)1 << 29) - 31) / 7) / 64 * 64;
+inline int64_t sweep_chunk_rows(int64_t rows, int64_t M, int64_t chunk_bytes) {
+  const int64_t Mpad = (M + 63) / 64 * 64, fit = chunk_bytes / (rows * (int64_t)sizeof(double)) / 64 * 64;
+  const int64_t Mc = fit < 64 ? 64 : fit < Mpad ? fit : Mpad;  // (Mpad >= 64)
+  return Mc > SWEEP_MAX_CHUNK_ROWS ? -1 : Mc;
+}
 int corr_trend_columns(int p);  // the PV instantiation serving p trend columns, 0 if none does
 bool corr_chunk_without_store(int kernel, int pv, bool have_xnorm);  // launch_corr_chunk has a producer without the store for this call
 

@@ -646,6 +646,12 @@ int bogp_last_prune_path(bogp_handle* h, int* path, int64_t* survivors, int* rou
  * quarter of the segment's rows survive, else BOGP_PRUNE_PATH_ONEPASS.                                                           */
 int bogp_prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t segment_rows, int64_t segment_survivors);
 
+/* Candidates per chunk of a candidate pass, no device and no handle (tests/test_sweep_geometry_host.py): what chunk_bytes (the
+ * BOGP_CHUNK_MB switch, 1 GiB by default) hold of columns of `rows` doubles -- the padded training rows -- in whole 64-row tiles, at
+ * least 64 and at most M rounded up to 64.  Negative where that exceeds what the kernels' 32-bit row offsets reach (76 695 808): the
+ * sweeps then fail with BOGP_ERR_UNSUPPORTED.  rows, M, chunk_bytes > 0.                                                          */
+int64_t bogp_sweep_chunk_rows(int64_t rows, int64_t M, int64_t chunk_bytes);
+
 /* Rows that went through the contraction in the LAST bogp_predict / bogp_sweep call (M without pruning; waits for a queued sweep). */
 int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows);
 
