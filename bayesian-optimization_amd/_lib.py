@@ -121,6 +121,11 @@ SIGNATURES = {
     "bogp_sweep_chunk_rows": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "bogp_acq_upper_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
+    "bogp_set_prune_bound32": (C.c_int, [C.c_void_p, C.c_int]),
+    "bogp_last_bound32": (C.c_int, [C.c_void_p, _lp, _lp, _ip]),
+    "bogp_debug_bound32": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_ubyte), _lp]),
+    "bogp_bound32_margin": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]),
+    "bogp_acq_upper_bound_interval": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_flops_per_candidate": (C.c_double, [C.c_void_p]),
     "bogp_nll_path": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bogp_chol_wide_panels": (C.c_int, [C.c_int, _ip, C.c_int]),
@@ -1143,6 +1148,31 @@ class Engine:
         path, rounds, surv = C.c_int(), C.c_int(), C.c_int64()
         self._check(self._lib.bogp_last_prune_path(self._h, C.cast(C.byref(path), _ip), C.cast(C.byref(surv), _lp), C.cast(C.byref(rounds), _ip)))
         return int(path.value), int(surv.value), int(rounds.value)
+
+    def set_prune_bound32(self, on=True):
+        """FP32 bounding stage of the one-pass pruned sweep (on by default): the bounding pass runs in FP32 with a proven margin per
+        row, the exact FP64 pass only on the rows it cannot rule out.  Winners, values, survivors and paths are unchanged."""
+        self._check(self._lib.bogp_set_prune_bound32(self._h, int(bool(on))))
+
+    def last_bound32(self):
+        """(rows bounded in FP32, rows kept over the segments, segments that ran the exact pass over all rows) of the last sweep."""
+        rows, kept, fb = C.c_int64(), C.c_int64(), C.c_int()
+        self._check(self._lib.bogp_last_bound32(self._h, C.cast(C.byref(rows), _lp), C.cast(C.byref(kept), _lp), C.cast(C.byref(fb), _ip)))
+        return int(rows.value), int(kept.value), int(fb.value)
+
+    def debug_bound32(self):
+        """Per row of the last segment the FP32 stage bounded: (mu32, e_mu, wd32, e_w, flags) -- the FP32 sums r . gamma and w . r, their
+        margins, the stage's flag; empty arrays where the stage did not run."""
+        n = C.c_int64()
+        self._check(self._lib.bogp_debug_bound32(self._h, 0, None, None, None, None, None, C.cast(C.byref(n), _lp)))
+        n = int(n.value)
+        out = [np.empty(n) for _ in range(4)]
+        flags = np.empty(n, dtype=np.uint8)
+        if n:
+            m = C.c_int64()
+            self._check(self._lib.bogp_debug_bound32(self._h, n, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                                     flags.ctypes.data_as(C.POINTER(C.c_ubyte)), C.cast(C.byref(m), _lp)))
+        return out[0], out[1], out[2], out[3], flags
 
     def last_contracted_rows(self) -> int:
         """Candidates that went through the variance contraction in the last predict() / sweep() (waits for a queued sweep)."""

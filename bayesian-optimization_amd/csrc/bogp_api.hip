@@ -106,6 +106,7 @@ static void free_train(bogp_handle* h) {
   h->dyt = h->drho = h->dgamma = nullptr;
   h->n_t = 1; h->target = 0;
   dfree(h->dtheta); h->dsqrt_theta = nullptr; dfree(h->dXthT); dfree(h->dXnorm); dfree(h->dVp);
+  dfree(h->dX32); dfree(h->dvec32); dfree(h->dstats32); h->x32_cap = h->vec32_cap = 0; h->b32_gen = 0;
   free_trend(h);
   h->committed = false;
   h->cap_ld = h->cap_d = h->cap_nt = 0;

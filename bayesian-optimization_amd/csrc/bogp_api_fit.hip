@@ -719,8 +719,9 @@ extern "C" int bogp_commit(bogp_handle* h, int kernel, int mode, const double* p
   h->sigma2_t.assign(o.sigma2_t, o.sigma2_t + h->n_t);
   h->nv_t.assign(o.nv_t, o.nv_t + h->n_t);
   h->committed = true;
+  ++h->commit_gen;  // (the FP32 copies of the bounding stage belong to the model before)
   select_target(h, 0);
-  return BOGP_OK;
+  return bound32_prepare(h);
 }
 
 extern "C" int bogp_get_state(bogp_handle* h, double* C, double* gamma, double* rho, double* Yt, double* Ft, double* Q,

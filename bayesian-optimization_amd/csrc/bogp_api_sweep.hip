@@ -436,15 +436,16 @@ struct SweepCtx {
   SweepGeometry g;
   int64_t M, nblk_total;  // (256-row block records; per-chunk block counts are rounded up)
   int Nrows, nJ, nJ_main, NJ16, pv;
-  bool vx_model, vx, overlap, prune, onepass;
+  bool vx_model, vx, overlap, prune, onepass, bound32;
   hipStream_t st, stP;
   // pruned sweep: rows of the survivor buffer, segment geometry of the one-pass flow, the carved work space (sweep_workspace)
   int64_t Ms, seg_rows, seg_stride, Rmax, sidx_cap, prune_nbk;
   long long* pctl;
-  int64_t *poffsets, *pmap, *psidx;
+  int64_t *poffsets, *pmap, *psidx, *psidx1;
   int *psel, *pblk_count;
-  unsigned char* pflags;
+  unsigned char *pflags, *pflags1;
   double *pxc, *dss_surv;
+  double *pxc1, *pmu32, *pwd32, *pna32;  // FP32 stage: the candidate rows of S1; the per-row sums and squared norms of a segment
   int64_t blk_offset, prune_pending;  // block records written so far; upper bound of the survivors waiting in the buffer (their count stays on the device)
 };
 
@@ -561,11 +562,17 @@ static int sweep_workspace(bogp_handle* h, SweepCtx& cx) {
   if (cx.prune) {
     const size_t w_off = PRUNE_CTL_WORDS, w_map = w_off + (size_t)cx.prune_nbk + 1, w_sel = w_map + (size_t)cx.Ms, w_cnt = w_sel + (size_t)(Mc / 4) / 2 + 1,
                  w_flag = w_cnt + (size_t)cx.prune_nbk / 2 + 1, w_sidx = w_flag + (size_t)cx.Rmax / 8 + 1, w_xc = w_sidx + (cx.onepass ? (size_t)cx.sidx_cap : 0),
-                 w_end = w_xc + (cx.onepass ? (size_t)cx.Ms * h->d : 0);
+                 w_xc1 = w_xc + (cx.onepass ? (size_t)cx.Ms * h->d : 0),
+                 // FP32 stage: S1's indices and candidate rows, both capped like S's; the segment's flags, sums and norms
+                 w_sidx1 = w_xc1 + (cx.bound32 ? (size_t)cx.sidx_cap * h->d : 0), w_flag1 = w_sidx1 + (cx.bound32 ? (size_t)cx.sidx_cap : 0),
+                 w_row32 = w_flag1 + (cx.bound32 ? (size_t)cx.Rmax / 8 + 1 : 0), w_end = w_row32 + (cx.bound32 ? (size_t)3 * cx.Rmax : 0);
     if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
     cx.pctl = h->dprune; cx.poffsets = (int64_t*)(h->dprune + w_off); cx.pmap = (int64_t*)(h->dprune + w_map); cx.psel = (int*)(h->dprune + w_sel);
     cx.pblk_count = (int*)(h->dprune + w_cnt); cx.pflags = (unsigned char*)(h->dprune + w_flag);
     cx.psidx = (int64_t*)(h->dprune + w_sidx); cx.pxc = (double*)(h->dprune + w_xc);
+    cx.pxc1 = (double*)(h->dprune + w_xc1); cx.psidx1 = (int64_t*)(h->dprune + w_sidx1); cx.pflags1 = (unsigned char*)(h->dprune + w_flag1);
+    if (cx.bound32) { h->b32_ws_row32 = w_row32; h->b32_ws_flag1 = w_flag1; h->b32_ws_rmax = (size_t)cx.Rmax; }
+    cx.pmu32 = (double*)(h->dprune + w_row32); cx.pwd32 = cx.pmu32 + cx.Rmax; cx.pna32 = cx.pwd32 + cx.Rmax;
     if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)cx.Nrows * cx.Ms))) return e;
     if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * cx.Ms))) return e;
     if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * cx.Ms))) return e;
@@ -810,9 +817,10 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   h->t_spans.clear(); h->t_chunks.clear();
   int e;
   // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
-  auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out) -> int {
+  // (`through`: the flagged rows are rows of that list -- S out of S1 -- and their entries of it are what is kept)
+  auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out, const unsigned char* flags, int64_t* sidx, const int64_t* through) -> int {
     HIPCHK(h, launch_prune_scan(cx.pblk_count, (rows + 255) / 256, cx.poffsets, rows, -1, pctl, st));
-    if (index_from >= 0) HIPCHK(h, launch_prune_index(cx.pflags, cx.poffsets, rows, index_from, cx.sidx_cap, cx.psidx, st));
+    if (index_from >= 0) HIPCHK(h, launch_prune_index(flags, cx.poffsets, rows, index_from, cx.sidx_cap, sidx, st, through));
     HIPCHK(h, hipMemcpyAsync(hcount, pctl + PRUNE_CTL_TOTAL, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     *out = *hcount;
@@ -824,6 +832,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   AcqArgs aa = acq_model_args(h, cx.rq, S, cx.nJ_main, nblk_total);
   aa.mu_part = h->dmu_part[1]; aa.w_part = h->dw_part[1]; aa.ss_part = cx.dss_surv; aa.Mc = Ms; aa.m0 = 0;
   PruneBoundArgs pb = prune_bound_args(h, cx);
+  Bound32Model md32{h->dX32, h->dvec32, h->dvec32 + h->Np, h->dvec32 + 2 * (size_t)h->Np, h->stats32[0], h->stats32[1], h->stats32[2]};
   int contract_launches = 0;
   // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
   auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
@@ -853,7 +862,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   long long pilot_surv = 0;
   pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
   HIPCHK(h, launch_prune_bound(pb, st));
-  if ((e = survivors_of(P, -1, &pilot_surv))) return e;
+  if ((e = survivors_of(P, -1, &pilot_surv, cx.pflags, cx.psidx, nullptr))) return e;
   if (prune_decide(P, pilot_surv, 1, 0) == BOGP_PRUNE_PATH_CHUNKS) {
     if ((e = fall_back(0, nchunk, BOGP_PRUNE_PATH_CHUNKS))) return e;
   } else {
@@ -863,11 +872,38 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
       if (rows <= 0) continue;
       CorrArgs cs = cc;  // the segment's partial sums, nothing else
       cs.m0 = sb; cs.Mc = cx.seg_stride; cs.rT = nullptr; cs.store = false; cs.mu_part = h->dmu_part[0]; cs.w_part = h->dw_part[0];
-      if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
-      pb.mu_part = h->dmu_part[0]; pb.w_part = h->dw_part[0]; pb.Mc = cx.seg_stride; pb.rcount = rows;
-      HIPCHK(h, launch_prune_bound(pb, st));
-      long long surv = 0;
-      if ((e = survivors_of(rows, sb, &surv))) return e;
+      pb.mu_part = h->dmu_part[0]; pb.w_part = h->dw_part[0]; pb.Mc = cx.seg_stride;
+      long long surv = 0, s1 = -1;
+      if (cx.bound32) {
+        // stage 1: every row from FP32 sums, flagged unless its margins rule it out -> S1, a superset of the survivors
+        Bound32Args ba;
+        ba.Xs = h->dXs; ba.M = M; ba.m0 = sb; ba.rcount = rows; ba.d = h->d; ba.Np = h->Np; ba.sqrt_theta = h->dsqrt_theta;
+        ba.md = md32; ba.mu = cx.pmu32; ba.wd = cx.pwd32; ba.na = cx.pna32;
+        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_bound32_sums(kernel, ba, st); }))) return e;
+        PruneBoundArgs p1 = pb;
+        p1.mu_part = cx.pmu32; p1.w_part = cx.pwd32; p1.S = 1; p1.Mc = rows; p1.rcount = rows; p1.flags = cx.pflags1;
+        HIPCHK(h, launch_bound32_flags(p1, kernel, h->d, cx.pwd32, cx.pna32, md32, st));
+        if ((e = survivors_of(rows, sb, &s1, cx.pflags1, cx.psidx1, nullptr))) return e;
+        h->b32_rows += rows; h->b32_kept += s1; h->b32_last_rows = rows;
+        if (4 * s1 > rows) {  // the exact pass over the whole segment after all: the FP32 pass was wasted
+          ++h->b32_fallbacks;
+          s1 = -1;
+        }
+      }
+      if (s1 < 0) {
+        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
+        pb.rcount = rows;
+        HIPCHK(h, launch_prune_bound(pb, st));
+        if ((e = survivors_of(rows, sb, &surv, cx.pflags, cx.psidx, nullptr))) return e;
+      } else if (s1 > 0) {
+        // stage 2: the exact sums of S1's rows alone (a row's sums do not depend on its neighbours), the exact bound, S in the original order
+        HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx1, s1, h->d, cx.pxc1, st));
+        cs.Xs = cx.pxc1; cs.M = s1; cs.m0 = 0;
+        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((s1 + 63) / 64), S, st); }))) return e;
+        pb.rcount = s1;
+        HIPCHK(h, launch_prune_bound(pb, st));
+        if ((e = survivors_of(s1, 0, &surv, cx.pflags, cx.psidx, cx.psidx1))) return e;
+      }
       if (prune_decide(P, pilot_surv, rows, surv) == BOGP_PRUNE_PATH_ONEPASS_FALLBACK) {  // (needs ordered candidates: the pilot saw few such rows)
         if ((e = fall_back(sb / Mc, (se + Mc - 1) / Mc, BOGP_PRUNE_PATH_ONEPASS_FALLBACK))) return e;
         continue;
@@ -899,6 +935,7 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   const int Np = h->Np, q = rq.q;
   const int64_t M = h->M;
   h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0; h->timing_onepass = false;
+  h->b32_rows = h->b32_kept = h->b32_last_rows = 0; h->b32_fallbacks = 0;
   int e;
   // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- takes neither: it always runs the chunked path below); nothing
   // to overlap a lazy upload with: the whole upload first (one launch reads every candidate)
@@ -937,6 +974,9 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   cx.prune = h->prune_mode != 0 && rq.need_var && q > 0 && !rq.want_out && !rq.want_acq_out && !rq.eh && h->p == 1 && !cx.vx_model && !cx.overlap;
   // one pass: every candidate resident and a producer that exists without its store
   cx.onepass = cx.prune && h->prune_mode == 1 && nchunk > 1 && !h->hXs_lazy && corr_chunk_without_store(h->kernel, 0, h->dXnorm != nullptr);
+  // ... bounded in FP32 first where the kernel's profile has a bounded slope
+  cx.bound32 = cx.onepass && h->prune_bound32 != 0 && bound32_supported(h->kernel, h->d);
+  if (cx.bound32 && (h->b32_gen != h->commit_gen || h->b32_target != h->target) && (e = bound32_prepare(h))) return e;  // (another target since the commit)
   if ((e = sweep_workspace(h, cx))) return e;
   if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * (rq.eh ? rq.eh->m : 1) : 0, rq.want_acq_out))) return e;
   // the chunks' events, the two-stream mode's begin event, the pilot's pair (pruned sweep)
@@ -1045,6 +1085,72 @@ extern "C" int bogp_set_prune(bogp_handle* h, int on) {
   if (on < 0 || on > 2) FAIL(h, BOGP_ERR_INVALID, "bogp_set_prune: %d is none of 0 (off), 1 (automatic), 2 (per-chunk path)", on);
   h->prune_mode = on;
   return BOGP_OK;
+}
+
+// FP32 copies of the committed model for the bounding stage (kernels_bound32.hip): at commit, and for another target on demand
+int bogp::bound32_prepare(bogp_handle* h) {
+  if (!h->committed || h->p != 1 || !h->dXnorm || !bound32_supported(h->kernel, h->d)) return BOGP_OK;
+  const int d = h->d, Np = h->Np;
+  hipStream_t st = h->stream;
+  int e;
+  if ((e = ensure(h, &h->dX32, &h->x32_cap, (size_t)4 * ((d + 3) / 4) * Np)) || (e = ensure(h, &h->dvec32, &h->vec32_cap, (size_t)3 * Np))) return e;
+  if (!h->dstats32) HIPCHK(h, hipMalloc((void**)&h->dstats32, 3 * sizeof(double)));
+  HIPCHK(h, launch_bound32_prepare(h->dXthT, h->dXnorm, h->dgamma, h->dw, d, Np, h->dX32, h->dvec32, h->dstats32, st));
+  HIPCHK(h, hipMemcpyAsync(h->stats32, h->dstats32, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->b32_gen = h->commit_gen; h->b32_target = h->target;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_set_prune_bound32(bogp_handle* h, int on) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (on != 0 && on != 1) FAIL(h, BOGP_ERR_INVALID, "bogp_set_prune_bound32: %d is neither 0 (off) nor 1 (on)", on);
+  h->prune_bound32 = on;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_last_bound32(bogp_handle* h, int64_t* rows, int64_t* kept, int* fallbacks) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (rows) *rows = h->b32_rows;
+  if (kept) *kept = h->b32_kept;
+  if (fallbacks) *fallbacks = h->b32_fallbacks;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_debug_bound32(bogp_handle* h, int64_t cap, double* mu32, double* e_mu, double* wd32, double* e_w, unsigned char* flags, int64_t* rows) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!rows) FAIL(h, BOGP_ERR_INVALID, "bogp_debug_bound32: null row count");
+  *rows = h->b32_last_rows;
+  const int64_t n = h->b32_last_rows;
+  if (n == 0 || !(mu32 || e_mu || wd32 || e_w || flags)) return BOGP_OK;
+  if (cap < n) FAIL(h, BOGP_ERR_INVALID, "bogp_debug_bound32: %lld rows, room for %lld", (long long)n, (long long)cap);
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // the work space as sweep_workspace carved it for the last sweep: the three per-row arrays end it, the flags sit in front of them
+  const int64_t Rmax = (int64_t)(h->b32_ws_rmax);
+  const double* base = (const double*)(h->dprune + h->b32_ws_row32);
+  std::vector<double> na((size_t)n);
+  HIPCHK(h, hipMemcpy(na.data(), base + 2 * Rmax, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (mu32) HIPCHK(h, hipMemcpy(mu32, base, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (wd32) HIPCHK(h, hipMemcpy(wd32, base + Rmax, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (flags) HIPCHK(h, hipMemcpy(flags, h->dprune + h->b32_ws_flag1, (size_t)n, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    double a = 0, b = 0;
+    bound32_margin(h->kernel, h->d, na[(size_t)i], h->stats32[2], h->stats32[0], h->stats32[1], &a, &b);
+    if (e_mu) e_mu[i] = a;
+    if (e_w) e_w[i] = b;
+  }
+  return BOGP_OK;
+}
+
+// host evaluations of the FP32 stage's margin and interval bound (csrc/bogp_device.h): no device, no handle; tests/test_bound32_host.py
+extern "C" int bogp_bound32_margin(int kernel, int d, double na, double nb_max, double gamma_l1, double w_l1, double* e_mu, double* e_w) {
+  if (!e_mu || !e_w) return BOGP_ERR_INVALID;
+  bound32_margin(kernel, d, na, nb_max, gamma_l1, w_l1, e_mu, e_w);
+  return BOGP_OK;
+}
+extern "C" double bogp_acq_upper_bound_interval(int acq_id, double acq_par, double y_hat, double e, double sd_ub, double plugin, double sigma2) {
+  return acq_upper_bound_interval(acq_id, acq_par, y_hat, e, sd_ub, plugin, sigma2);
 }
 
 extern "C" int bogp_last_prune_path(bogp_handle* h, int* path, int64_t* survivors, int* rounds) {

@@ -362,6 +362,52 @@ __host__ __device__ __forceinline__ bool prune_below(double bound, double thr) {
   return __builtin_isfinite(thr) && bound + 1e-9 * (fabs(bound) + fabs(thr)) + 1e-300 < thr;
 }
 
+// The largest acq_upper_bound over y_hat in [y32 - e, y32 + e] at the (already optimistic) sd_ub: what the FP32 bounding stage of the
+// one-pass pruned sweep (kernels_bound32.hip) compares with the best value found so far.  Every criterion's bound is
+// monotone in y_hat between its switch points (UCB rises; EI and MGFI fall; EpsilonPI is linear in y_hat on either side of 0), so the
+// larger of the two ends bounds the interval; an interval that holds a switch point (EpsilonPI: 0, or a sign change of its numerator;
+// MGFI: the plugin), a NaN or an infinity gives +inf: such a row is never dropped.  The result is raised by 1e-12 relative -- far below
+// prune_below's margin -- for the few-ulp non-monotonicity of erf / erfc / exp between the ends.
+__host__ __device__ __forceinline__ double acq_upper_bound_interval(int id, double par, double y32, double e, double sd_ub, double plugin, double sigma2) {
+  if (!(__builtin_isfinite(y32) && __builtin_isfinite(e) && e >= 0.0 && __builtin_isfinite(sd_ub))) return INFINITY;
+  const double lo = y32 - e, hi = y32 + e;
+  if (id == BOGP_ACQ_EPSILON_PI) {
+    if (lo <= 0.0 && hi >= 0.0) return INFINITY;
+    const double coef = lo > 0 ? 1 - par : 1 + par;
+    const double n0 = plugin - coef * lo, n1 = plugin - coef * hi;
+    if (!((n0 > 0 && n1 > 0) || (n0 < 0 && n1 < 0))) return INFINITY;
+  }
+  if (id == BOGP_ACQ_MGFI && lo <= plugin && hi >= plugin) return INFINITY;
+  const double b0 = acq_upper_bound(id, par, lo, sd_ub, plugin, sigma2), b1 = acq_upper_bound(id, par, hi, sd_ub, plugin, sigma2);
+  if (!(__builtin_isfinite(b0) && __builtin_isfinite(b1))) return INFINITY;
+  const double b = b0 > b1 ? b0 : b1;
+  return b + 1e-12 * fabs(b);
+}
+
+// The FP32 bounding stage's margins (the derivation).  slope: the largest |d profile / d s| of the kernels the stage
+// serves in the squared distance s -- SE 1, Matern-3/2 3/2, Matern-5/2 5/6 -- and 0 for every other kernel (not served).
+__host__ __device__ __forceinline__ double bound32_slope(int kernel) {
+  return kernel == BOGP_KERNEL_SE ? 1.0 : kernel == BOGP_KERNEL_MATERN32 ? 1.5 : kernel == BOGP_KERNEL_MATERN52 ? 5.0 / 6.0 : 0.0;
+}
+constexpr int BOUND32_FLUSH = 4;  // 16-pair steps a lane accumulates in FP32 before the sums go to its FP64 accumulators
+// |mu32 - r . gamma| <= *e_mu and |wd32 - w . r| <= *e_w for a row with squared norm na (of its FP64 theta-scaled point), given the
+// largest squared norm nb_max of the scaled training points and the 1-norms of gamma and w.  u = 2^-24.
+//   ds = 1.01 (d + 16) u (na + nb_max) + 1e-30   input rounding, the two norms, the fma chain of the cross term, the combination
+//   dr = slope ds + 32 u + 1e-30                 profile: square root, exponential, polynomial; flushed denormals
+//   e  = |v|_1 (dr + (4 FLUSH + 4) u)            rounding of v to FP32, FP32 accumulation over 4 FLUSH terms, the FP64 tail
+// +inf where FP32 would overflow (na + nb_max >= 1e37) or an input is negative or not finite.
+__host__ __device__ __forceinline__ void bound32_margin(int kernel, int d, double na, double nb_max, double gamma_l1, double w_l1, double* e_mu, double* e_w) {
+  const double u = 5.9604644775390625e-08, slope = bound32_slope(kernel), nn = na + nb_max;
+  if (!(slope > 0.0 && na >= 0.0 && nb_max >= 0.0 && nn < 1e37 && __builtin_isfinite(gamma_l1) && __builtin_isfinite(w_l1))) {
+    *e_mu = INFINITY; *e_w = INFINITY;
+    return;
+  }
+  const double ds = 1.01 * (d + 16) * u * nn + 1e-30;
+  const double dr = slope * ds + 32.0 * u + 1e-30 + (4 * BOUND32_FLUSH + 4) * u;
+  *e_mu = gamma_l1 * dr + 1e-30;  // (+ entries of v below FP32's normal range: N 2^-150 at most)
+  *e_w = w_l1 * dr + 1e-30;
+}
+
 // posterior of one row from its three sums (gpr.py:490, 496-510): mu = beta + r.gamma, MSE = (1 - |L^-1 r|^2 + u^2) sigma2
 // clipped at 0, u = (w.r - 1) / G under ordinary kriging with the constant basis
 __device__ __forceinline__ void posterior_of_sums(double rgamma, double wr, double ss, double beta, double G, int estimate_trend,

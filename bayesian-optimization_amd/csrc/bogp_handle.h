@@ -43,6 +43,7 @@ int sweep_geometry(bogp_handle* h, int rows, SweepGeometry* g);
 CorrArgs corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int64_t m0, int b);
 int ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out);
 int check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par);
+int bound32_prepare(bogp_handle* h);  // bogp_api_sweep.hip: the FP32 copies of the committed model's active target, where the stage serves it
 // bogp_api_sweep.hip, for bogp_api_lift.hip: a pending lazy upload finished (every candidate row on the device); the
 // sweep timing zeroed (a lifted sweep without a feasible row runs no posterior pass)
 int candidates_ready(bogp_handle* h);
@@ -142,6 +143,20 @@ struct bogp_handle {
   int prune_rounds = 0;
   long long* dprune = nullptr;
   size_t prune_cap = 0;
+  // FP32 bounding stage of the one-pass flow (kernels_bound32.hip; bogp_set_prune_bound32): FP32 copies of the committed
+  // model -- [4 ceil(d / 4)][Np] scaled points | norms, gamma, w (Np each) | three statistics -- valid while b32_gen == commit_gen and
+  // b32_target == target (rebuilt by bound32_prepare at commit and, for another target, by the sweep that needs them)
+  int prune_bound32 = 1;
+  float *dX32 = nullptr, *dvec32 = nullptr;
+  double* dstats32 = nullptr;
+  size_t x32_cap = 0, vec32_cap = 0;
+  double stats32[3] = {0, 0, 0};
+  uint64_t commit_gen = 0, b32_gen = 0;
+  int b32_target = -1;
+  int64_t b32_rows = 0, b32_kept = 0;  // bogp_last_bound32: rows bounded in FP32, |S1| over the segments, segments that fell back
+  int b32_fallbacks = 0;
+  size_t b32_ws_row32 = 0, b32_ws_flag1 = 0, b32_ws_rmax = 0;  // where the last sweep's work space holds the segment's sums / flags (words of dprune)
+  int64_t b32_last_rows = 0;           // rows of the last segment bounded in FP32: what bogp_debug_bound32 reads back
   bool prune_used = false;       // the last sweep pruned: its contracted-row count is on the device (dprune[4])
   int64_t contracted_rows = 0;   // ... otherwise it is this
   double* dtopk_val = nullptr;   // [q][k] winners of bogp_sweep_topk (device-resident between its passes)

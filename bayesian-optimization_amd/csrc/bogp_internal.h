@@ -5,6 +5,8 @@
 
 #include <string>
 
+#include "../../include/bogp.h"
+
 namespace bogp {
 
 // ---- kernel argument blocks (passed by value) -------------------------------------------------------
@@ -135,7 +137,7 @@ hipError_t launch_prune_scan(const int* blk_count, int64_t nblk, int64_t* offset
 hipError_t launch_prune_gather(const PruneGatherArgs& a, hipStream_t st);
 // one pass: the global indices m0 + i of the flagged rows, in order, into sidx[0 .. cap); rows sidx[0 .. count) of Xs -> Xc (count x d)
 hipError_t launch_prune_index(const unsigned char* flags, const int64_t* offsets, int64_t rcount, int64_t m0, int64_t cap, int64_t* sidx,
-                              hipStream_t st);
+                              hipStream_t st, const int64_t* through = nullptr);  // through: sidx[k] = through[i] instead of m0 + i
 hipError_t launch_prune_rows(const double* Xs, const int64_t* sidx, int64_t count, int d, double* Xc, hipStream_t st);
 
 // The two host decisions of the one-pass pruned sweep (exported as bogp_prune_decide; the values are BOGP_PRUNE_PATH_* of include/bogp.h).
@@ -151,6 +153,34 @@ inline int prune_decide(int64_t pilot_rows, int64_t pilot_survivors, int64_t seg
 hipError_t launch_prune_update(const double* blk_val, const int64_t* blk_idx, int64_t stride, const long long* live, int64_t count, int q,
                                double* best_val, int64_t* best_idx, hipStream_t st);
 hipError_t launch_prune_flushed(long long* ctl, hipStream_t st);  // the buffer went through the contraction: count it, empty it
+
+// The FP32 bounding stage of the one-pass pruned sweep (kernels_bound32.hip): the sums r . gamma and w . r of every
+// row of a segment from FP32 correlations, the rows that cannot be ruled out within their margins flagged for the exact pass.
+constexpr int BOUND32_MAX_D = 128;  // the FP32 candidate tile stays within the default 64 KB of dynamic LDS
+inline bool bound32_supported(int kernel, int d) {
+  return (kernel == BOGP_KERNEL_SE || kernel == BOGP_KERNEL_MATERN32 || kernel == BOGP_KERNEL_MATERN52) && d <= BOUND32_MAX_D;
+}
+struct Bound32Model {        // FP32 copies of the committed model (built at commit: bound32_prepare)
+  const float* XthT;         // [4 ceil(d / 4)][Np] theta-scaled training points, transposed; zero rows from d on
+  const float* xnorm;        // [Np] squared norms of the FP64 scaled points, rounded
+  const float* gamma;        // [Np]
+  const float* wvec;         // [Np]
+  double gamma_l1, w_l1, nb_max;  // 1-norms of gamma and w, the largest squared norm
+};
+struct Bound32Args {
+  const double* Xs;          // candidates, M x d row-major
+  int64_t M, m0, rcount;     // total candidates; first row of the region; its rows
+  int d, Np;
+  const double* sqrt_theta;
+  Bound32Model md;
+  double *mu, *wd, *na;      // [rcount] r . gamma, w . r, |a|^2 of the row's FP64 scaled point
+};
+hipError_t launch_bound32_prepare(const double* XthT, const double* xnorm, const double* gamma, const double* wvec, int d, int Np,
+                                  float* XthT32, float* vec32, double* stats, hipStream_t st);
+hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st);
+// PruneBoundArgs' region with mu_part = the FP32 sums (S = 1): flags and block counts as launch_prune_bound leaves them
+hipError_t launch_bound32_flags(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
+                                hipStream_t st);
 
 // expected hypervolume improvement of an m-target model over one chunk (kernels_ehvi.hip): replaces AcqArgs / k_acquisition
 // in the chunk loop of bogp_sweep_ehvi

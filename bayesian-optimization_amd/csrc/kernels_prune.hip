@@ -144,9 +144,10 @@ __global__ __launch_bounds__(256) void k_prune_compact(PruneGatherArgs a) {
   }
 }
 
+// (`through`, FP32 stage: the region is a list of rows -- S1 -- and a survivor's entry of that list is kept instead of m0 + i)
 // one pass: k_prune_compact's enumeration, the global indices alone; `cap` entries (a region with more survivors falls back: its list is not read)
 __global__ __launch_bounds__(256) void k_prune_index(const unsigned char* __restrict__ flags, const int64_t* __restrict__ offsets, int64_t rcount,
-                                                     int64_t m0, int64_t cap, int64_t* __restrict__ sidx) {
+                                                     int64_t m0, int64_t cap, int64_t* __restrict__ sidx, const int64_t* __restrict__ through) {
   __shared__ int s_cnt[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool keep = i < rcount && flags[i] != 0;
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(256) void k_prune_index(const unsigned char* __rest
   int before = __popcll(bal & ((1ull << lane) - 1ull));
   for (int k = 0; k < w; ++k) before += s_cnt[k];
   const int64_t k = offsets[blockIdx.x] + before;
-  if (k < cap) sidx[k] = m0 + i;
+  if (k < cap) sidx[k] = through ? through[i] : m0 + i;
 }
 
 // one pass: rows sidx[0 .. count) of the candidates -> Xc (count x d, row-major)
@@ -262,8 +263,8 @@ hipError_t launch_prune_gather(const PruneGatherArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_prune_index(const unsigned char* flags, const int64_t* offsets, int64_t rcount, int64_t m0, int64_t cap, int64_t* sidx,
-                              hipStream_t st) {
-  hipLaunchKernelGGL(k_prune_index, dim3((unsigned)((rcount + 255) / 256)), 256, 0, st, flags, offsets, rcount, m0, cap, sidx);
+                              hipStream_t st, const int64_t* through) {
+  hipLaunchKernelGGL(k_prune_index, dim3((unsigned)((rcount + 255) / 256)), 256, 0, st, flags, offsets, rcount, m0, cap, sidx, through);
   return hipGetLastError();
 }
 

@@ -662,6 +662,27 @@ int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows);
 double bogp_acq_upper_bound(int acq_id, double acq_par, double y_hat, double sd_ub, double plugin, double sigma2);
 int bogp_prune_below(double bound, double threshold);
 
+/* FP32 bounding stage of the one-pass pruned sweep.  For the squared-exponential, Matern-3/2 and Matern-5/2
+ * kernels up to 128 dimensions, the bounding pass of a segment first runs in FP32 with a proven error margin per row; only the rows
+ * it cannot rule out get the exact FP64 sums and the exact bound, which decides as before: survivors, rounds, paths and every output
+ * bit are unchanged.  A segment of which the FP32 stage keeps more than a quarter runs the exact pass over all its rows instead.
+ * on = 1 (the default) / 0 for this handle.                                                                                         */
+int bogp_set_prune_bound32(bogp_handle* h, int on);
+
+/* What the FP32 stage did in the LAST sweep: rows it bounded, rows it kept (summed over the segments), segments that ran the exact
+ * pass over all rows after all.  All zero where the stage did not run.  Any output may be NULL.                                     */
+int bogp_last_bound32(bogp_handle* h, int64_t* rows, int64_t* kept, int* fallbacks);
+
+/* Debug read-back of the last segment the FP32 stage bounded (waits for a queued sweep): *rows = its rows (0: none); per row the FP32
+ * sums r . gamma and w . r, their margins and the stage's flag.  Arrays of `cap` >= *rows entries, any of them NULL.                 */
+int bogp_debug_bound32(bogp_handle* h, int64_t cap, double* mu32, double* e_mu, double* wd32, double* e_w, unsigned char* flags, int64_t* rows);
+
+/* Host evaluations of the FP32 stage's two rules, no device and no handle (tests/test_bound32_host.py): the margins of a row whose
+ * scaled point has squared norm na (+inf where the stage cannot bound the row), and the largest bogp_acq_upper_bound over y_hat in
+ * [y_hat - e, y_hat + e] (+inf where the interval holds a switch point of the criterion, a NaN or an infinity).                     */
+int bogp_bound32_margin(int kernel, int d, double na, double nb_max, double gamma_l1, double w_l1, double* e_mu, double* e_w);
+double bogp_acq_upper_bound_interval(int acq_id, double acq_par, double y_hat, double e, double sd_ub, double plugin, double sigma2);
+
 /* Algorithmic FP64 flops per candidate of the posterior for the committed model:
  * N^2 + N (3d + 5 + 2p)  (SURVEY.md section 8d).                                                        */
 double bogp_flops_per_candidate(const bogp_handle* h);
