@@ -5,6 +5,7 @@ restatement of gpr.py:772-808 / :931-1038) -- every correlation family, all thre
 estimated and fixed trend coefficient, sizes on every side of the 4 x 4 register blocks, a non-positive-definite matrix.
 Tolerances: log-likelihood 1e-10 + 8 eps cond(R) relative (both are Cholesky-based), gradient 1e-7 + 200 eps cond(R) relative to its
 largest entry.
+d > 7, where the kernels' blocks of 16 and 64 dimensions end: tests/test_gpu_nll_dims.py (each gradient component against the oracle).
 Needs a real MI355X: `pytest -m gpu`."""
 import os
 
@@ -166,7 +167,9 @@ def test_against_the_oracle(eng):
 
 
 def test_large_d_falls_back_when_the_workgroup_would_not_fit(eng):
-    """N = 150, d = 40: X + the image of the blocks exceed the LDS of one CU -- the evaluation takes the general path, same numbers."""
+    """N = 150, d = 40: X + the image of the blocks exceed the LDS of one CU -- the evaluation takes the next path, the elimination
+    (bogp_nll_path; ld = 192), and is compared with the general path: same numbers.  Both run k_grad_contract: the oracle holds it
+    at d > 16 in test_gpu_nll_dims.py."""
     X, y = make(150, 40, 11)
     eng.set_train(X, y)
     par = np.r_[np.full(40, 0.02), 0.9]
