@@ -124,6 +124,7 @@ SIGNATURES = {
     "bogp_set_prune_bound32": (C.c_int, [C.c_void_p, C.c_int]),
     "bogp_last_bound32": (C.c_int, [C.c_void_p, _lp, _lp, _ip]),
     "bogp_debug_bound32": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_ubyte), _lp]),
+    "bogp_debug_live": (None, [_lp, _lp, _lp]),
     "bogp_bound32_margin": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]),
     "bogp_acq_upper_bound_interval": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_flops_per_candidate": (C.c_double, [C.c_void_p]),
@@ -269,6 +270,13 @@ def merge_topk_c(gathered: np.ndarray):
     if rc != OK:
         raise BogpError(rc, "bogp_merge_topk: invalid arguments")
     return val, idx, x
+
+
+def debug_live():
+    """bogp_debug_live: (live device + mapped pinned allocations, their bytes, live events) held by the handles of this process."""
+    a, b, e = C.c_int64(), C.c_int64(), C.c_int64()
+    load().bogp_debug_live(C.byref(a), C.byref(b), C.byref(e))
+    return int(a.value), int(b.value), int(e.value)
 
 
 def trend_size_of(trend: int, d: int) -> int:

@@ -59,19 +59,18 @@ extern "C" int bogp_create(int device, bogp_handle** out) {
   if (hipSetDevice(device) != hipSuccess || hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess ||
       hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
       hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_least) != hipSuccess ||
-      hipMalloc((void**)&h->dscal, 64 * sizeof(double)) != hipSuccess) {
+      h->dscal.ensure(h, 64) != BOGP_OK) {
     g_create_error = "stream creation failed";
     delete h;
     return BOGP_ERR_HIP;
   }
-  if (hipHostMalloc((void**)&h->hfit, 4096 * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&h->hfit_dev, h->hfit, 0) != hipSuccess) {
+  if (h->hfit.ensure(h, 4096) != BOGP_OK) {  // (zero-filled)
     g_create_error = "pinned host buffer allocation failed";
     delete h;
     return BOGP_ERR_HIP;
   }
-  memset(h->hfit, 0, 4096 * sizeof(double));
-  if (hipMalloc((void**)&h->dfin_ticket, sizeof(unsigned int)) != hipSuccess || hipMemset(h->dfin_ticket, 0, sizeof(unsigned int)) != hipSuccess) {
+  h->hfit_dev = h->hfit.dev;
+  if (h->dfin_ticket.ensure(h, 1) != BOGP_OK || hipMemset(h->dfin_ticket, 0, sizeof(unsigned int)) != hipSuccess) {
     g_create_error = "device allocation failed";
     delete h;
     return BOGP_ERR_HIP;
@@ -79,9 +78,8 @@ extern "C" int bogp_create(int device, bogp_handle** out) {
   // the factorisation's info word lives in the same block as its scalars (doubles 62-63): ONE read-back fetches both
   h->dinfo = reinterpret_cast<int*>(h->dscal + 62);
   // (r04 experiment, removed in r06: the look-ahead update of the two-level factorisation on a CU-masked stream -- tools/ab/ab_big_chol_cumask.sh,
-  // EXPERIMENTS.md; no gain.  h->stream_upd stays null: the update runs on stream2.)
-  if (hipEventCreateWithFlags(&h->ev_chol[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_chol[1], hipEventDisableTiming) != hipSuccess) {
+  // EXPERIMENTS.md; no gain: the update runs on stream2.)
+  if (!h->ev_chol.at(1)) {
     g_create_error = "event creation failed";
     delete h;
     return BOGP_ERR_HIP;
@@ -92,62 +90,43 @@ extern "C" int bogp_create(int device, bogp_handle** out) {
 
 
 static void free_trend(bogp_handle* h) {
-  dfree(h->dF); dfree(h->dFt); dfree(h->dQ1); dfree(h->dQ); dfree(h->dWp); dfree(h->dWpT); dfree(h->dSinvP);
-  dfree(h->gsplit.scratch); dfree(h->gsplit.tickets); h->gsplit.cap = 0; h->gsplit.max_tiles = 0;
-  for (int b = 0; b < 2; ++b) { dfree(h->dA[b]); dfree(h->dAV[b]); dfree(h->dAU[b]); }
-  dfree(h->dAw); dfree(h->dAT); dfree(h->dGinv); dfree(h->dSinv); dfree(h->dbetav); dfree(h->dqty); dfree(h->dinfo2);
-  dfree(h->dVpx); h->vpx_cap = 0; dfree(h->dAtx); h->atx_cap = 0; h->vx_Ne = h->vx_Nt = 0;
+  for (auto* b : {&h->dF, &h->dFt, &h->dQ1, &h->dQ, &h->dWp, &h->dWpT, &h->dSinvP, &h->dgsplit_scratch, &h->dA[0], &h->dA[1], &h->dAV[0], &h->dAV[1],
+                  &h->dAU[0], &h->dAU[1], &h->dAw, &h->dAT, &h->dGinv, &h->dSinv, &h->dbetav, &h->dqty, &h->dAtx})
+    b->free();
+  h->dgsplit_tickets.free(); h->gsplit = {nullptr, 0, nullptr, 0};
+  h->dinfo2.free(); h->dVpx.free(); h->vx_Ne = h->vx_Nt = 0;
   h->tr_built = -1; h->tr_p = 0; h->ldp = 0; h->trend = BOGP_TREND_CONSTANT; h->p = 1; h->reml_ftf_basis = -1;
 }
 
 static void free_train(bogp_handle* h) {
-  dfree(h->dX); dfree(h->dy_base); h->dy = nullptr; dfree(h->dR); dfree(h->dV); dfree(h->dU); dfree(h->dT); dfree(h->dRinv); dfree(h->ddinv); dfree(h->dchain_flags); dfree(h->dones); dfree(h->dgemv_scratch);
-  dfree(h->dyt_base); dfree(h->dft); dfree(h->drho_base); dfree(h->dtmp); dfree(h->dgamma_base); dfree(h->dw);
-  h->dyt = h->drho = h->dgamma = nullptr;
+  for (auto* b : {&h->dX, &h->dy_base, &h->dR, &h->dV, &h->dU, &h->dT, &h->dRinv, &h->ddinv, &h->dones, &h->dgemv_scratch, &h->dyt_base, &h->dft,
+                  &h->drho_base, &h->dtmp, &h->dgamma_base, &h->dw, &h->dtheta, &h->dXthT, &h->dXnorm, &h->dstats32})
+    b->free();
+  h->dchain_flags.free(); h->dVp.free(); h->dX32.free(); h->dvec32.free(); h->b32_gen = 0;
+  h->dy = h->dyt = h->drho = h->dgamma = h->dsqrt_theta = nullptr;
   h->n_t = 1; h->target = 0;
-  dfree(h->dtheta); h->dsqrt_theta = nullptr; dfree(h->dXthT); dfree(h->dXnorm); dfree(h->dVp);
-  dfree(h->dX32); dfree(h->dvec32); dfree(h->dstats32); h->x32_cap = h->vec32_cap = 0; h->b32_gen = 0;
   free_trend(h);
   h->committed = false;
   h->cap_ld = h->cap_d = h->cap_nt = 0;
 }
 
+// Every device buffer, pinned block and event is released by its member's destructor (bogp_handle.h)
 extern "C" void bogp_destroy(bogp_handle* h) {
   if (!h) return;
   for (bogp_handle* a : h->aux) bogp_destroy(a);
-  h->aux.clear();
-  h->aux_gen.clear();
   (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
+  for (hipStream_t st : {h->stream, h->stream2, h->stream_copy})
+    if (st) (void)hipStreamSynchronize(st);
   comm_release(h);
-  point_release(h);
-  batch_release(h);
-  believer_release(h);
-  thompson_release(h);
-  free_train(h);
-  (void)hipStreamSynchronize(h->stream2);
-  if (h->stream_upd) (void)hipStreamSynchronize(h->stream_upd);
-  dfree(h->dXs_owned); dfree(h->dss_part); dfree(h->dbounds); dfree(h->dsobol); dfree(h->dxform);
-  for (int b = 0; b < 2; ++b) { dfree(h->drT[b]); dfree(h->dmu_part[b]); dfree(h->dw_part[b]); }
-  dfree(h->dblk_val); dfree(h->dblk_idx); dfree(h->dmu_out); dfree(h->dmse_out); dfree(h->dacq_out); dfree(h->dehvi_cells); ehvi_cells_forget(h); dfree(h->dforest_words); dfree(h->dforest_tree);
-  dfree(h->dbest_val); dfree(h->dbest_idx); dfree(h->dtopk_val); dfree(h->dtopk_idx); dfree(h->dcounter); dfree(h->dprune); h->dinfo = nullptr; dfree(h->dscal); dfree(h->dgrad_partial); dfree(h->dbatch);
-  dfree(h->dTt); dfree(h->dCS); dfree(h->duu); dfree(h->dmtrend); dfree(h->dtpart[0]); dfree(h->dtpart[1]);
-  dfree(h->dlift); dfree(h->dlift_pen); dfree(h->dlift_cnt); dfree(h->dlift_off); dfree(h->dlift_Z); dfree(h->dlift_map); dfree(h->dlift_val);
-  for (auto e : h->lift_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto e : h->ev) (void)hipEventDestroy(e);
-  for (auto e : h->forest_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (int i = 0; i < 2; ++i)
-    if (h->ev_chol[i]) (void)hipEventDestroy(h->ev_chol[i]);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  if (h->stream_upd) (void)hipStreamDestroy(h->stream_upd);
-  if (h->stream_copy) (void)hipStreamDestroy(h->stream_copy);
-  if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
-  if (h->hfit) (void)hipHostFree(h->hfit);
-  if (h->dfin_ticket) (void)hipFree(h->dfin_ticket);
+  for (hipStream_t st : {h->stream, h->stream2, h->stream_copy})
+    if (st) (void)hipStreamDestroy(st);
   delete h;
+}
+
+extern "C" void bogp_debug_live(int64_t* allocations, int64_t* bytes, int64_t* events) {
+  if (allocations) *allocations = g_live.allocations;
+  if (bytes) *bytes = g_live.bytes;
+  if (events) *events = g_live.events;
 }
 
 // point the per-target views (and the committed sigma2) at target t
@@ -180,8 +159,8 @@ extern "C" int bogp_set_train(bogp_handle* h, const double* X, const double* y, 
     h->M = 0;
     h->last_q = h->last_topk_q = h->last_topk_k = 0;
   }
-  // leading dimension: N rounded up to 64; to 128 above N = 3072 (r06; 6080 before), where the inverse, R^-1 and the Cholesky's wide panels work on 128 x 128 tiles
-  const int ld_need = N > 3072 ? ((N + 127) / 128) * 128 : ((N + 63) / 64) * 64;  // (above the elimination's limit the fit runs on 128 x 128 tiles: kernels_chol.hip, BIG_LD)
+  const int ld_need = train_ld(N);
+  int e;
   const bool fits = h->dX && h->dtheta && ld_need <= h->cap_ld && d <= h->cap_d && n_targets <= h->cap_nt;
   if (fits) {
     free_trend(h);  // N x p buffers of a polynomial basis: rebuilt on demand
@@ -192,26 +171,26 @@ extern "C" int bogp_set_train(bogp_handle* h, const double* X, const double* y, 
     // grow in steps of 256 rows once the set is larger than a block, so that a BO loop reallocates every 256 tell()s
     const int new_cap_ld = ld_need <= 256 ? ld_need : ((ld_need + 255) / 256) * 256;
     const size_t cl = (size_t)new_cap_ld, NNc = cl * cl, ntc = (size_t)n_targets;
-    HIPCHK(h, hipMalloc((void**)&h->dX, cl * d * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dy_base, ntc * cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dR, NNc * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->ddinv, cl * 64 * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dV, NNc * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dU, NNc * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dT, NNc * sizeof(double)));
+    if ((e = h->dX.ensure(h, cl * d))) return e;
+    if ((e = h->dy_base.ensure(h, ntc * cl))) return e;
+    if ((e = h->dR.ensure(h, NNc))) return e;
+    if ((e = h->ddinv.ensure(h, cl * 64))) return e;
+    if ((e = h->dV.ensure(h, NNc))) return e;
+    if ((e = h->dU.ensure(h, NNc))) return e;
+    if ((e = h->dT.ensure(h, NNc))) return e;
     {
       std::vector<double> ones(cl, 1.0);
-      HIPCHK(h, hipMalloc((void**)&h->dones, cl * sizeof(double)));
-      HIPCHK(h, hipMalloc((void**)&h->dgemv_scratch, gemv2_scratch_doubles((int)cl) * sizeof(double)));
+      if ((e = h->dones.ensure(h, cl))) return e;
+      if ((e = h->dgemv_scratch.ensure(h, gemv2_scratch_doubles((int)cl)))) return e;
       HIPCHK(h, hipMemcpy(h->dones, ones.data(), cl * sizeof(double), hipMemcpyHostToDevice));
     }
-    HIPCHK(h, hipMalloc((void**)&h->dyt_base, ntc * cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dft, cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->drho_base, ntc * cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dtmp, cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dgamma_base, ntc * cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dw, cl * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dtheta, 2 * (d + 1) * sizeof(double)));  // [theta (d + 1) | sqrt_theta (d + 1)]: one upload
+    if ((e = h->dyt_base.ensure(h, ntc * cl))) return e;
+    if ((e = h->dft.ensure(h, cl))) return e;
+    if ((e = h->drho_base.ensure(h, ntc * cl))) return e;
+    if ((e = h->dtmp.ensure(h, cl))) return e;
+    if ((e = h->dgamma_base.ensure(h, ntc * cl))) return e;
+    if ((e = h->dw.ensure(h, cl))) return e;
+    if ((e = h->dtheta.ensure(h, 2 * (d + 1)))) return e;  // [theta (d + 1) | sqrt_theta (d + 1)]: one upload
     h->dsqrt_theta = h->dtheta + (d + 1);
     h->cap_ld = new_cap_ld;
     h->cap_d = d;
@@ -273,10 +252,9 @@ extern "C" int bogp_set_trend_beta(bogp_handle* h, const double* beta, int p) {
 // split-K scratch of k_gemm64: tiles x slices <= 512 partial tiles of 64 x 64 (16 MB), 128 zeroed ticket words
 int bogp::ensure_gsplit(bogp_handle* h) {
   if (h->gsplit.scratch) return BOGP_OK;
-  h->gsplit.max_tiles = 128;
-  h->gsplit.cap = (size_t)512 * 64 * 64;
-  HIPCHK(h, hipMalloc((void**)&h->gsplit.scratch, h->gsplit.cap * sizeof(double)));
-  HIPCHK(h, hipMalloc((void**)&h->gsplit.tickets, 128 * sizeof(unsigned int)));
+  int e;
+  if ((e = h->dgsplit_scratch.ensure(h, (size_t)512 * 64 * 64)) || (e = h->dgsplit_tickets.ensure(h, 128))) return e;
+  h->gsplit = {h->dgsplit_scratch, h->dgsplit_scratch.cap, h->dgsplit_tickets, 128};
   HIPCHK(h, hipMemsetAsync(h->gsplit.tickets, 0, 128 * sizeof(unsigned int), h->stream));
   return BOGP_OK;
 }
@@ -287,6 +265,7 @@ static int ensure_trend(bogp_handle* h, int trend) {
   if (p > 1024) FAIL(h, BOGP_ERR_UNSUPPORTED, "trend with p = %d basis functions (> 1024)", p);
   if (p > N) FAIL(h, BOGP_ERR_INVALID, "trend with p = %d basis functions needs at least as many training points (N = %d)", p, N);
   hipStream_t st = h->stream;
+  int e;
   if (h->tr_p != p) {
     const bool was_committed = h->committed;
     const int tr0 = h->trend, p0 = h->p;
@@ -295,28 +274,28 @@ static int ensure_trend(bogp_handle* h, int trend) {
     if (was_committed && p0 > 1) h->committed = false;  // the committed W / beta lived in the freed buffers
     const int ldp = ((p + 63) / 64) * 64;
     const size_t np_ = (size_t)N * p, pp = (size_t)ldp * ldp;
-    HIPCHK(h, hipMalloc((void**)&h->dF, np_ * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dFt, np_ * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dQ1, np_ * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dQ, np_ * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dWp, (size_t)Np * p * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dWpT, (size_t)Np * ((p + 127) / 128 * 128) * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dSinvP, (size_t)((p + 127) / 128 * 128) * ((p + 127) / 128 * 128) * sizeof(double)));
+    if ((e = h->dF.ensure(h, np_))) return e;
+    if ((e = h->dFt.ensure(h, np_))) return e;
+    if ((e = h->dQ1.ensure(h, np_))) return e;
+    if ((e = h->dQ.ensure(h, np_))) return e;
+    if ((e = h->dWp.ensure(h, (size_t)Np * p))) return e;
+    if ((e = h->dWpT.ensure(h, (size_t)Np * ((p + 127) / 128 * 128)))) return e;
+    if ((e = h->dSinvP.ensure(h, (size_t)((p + 127) / 128 * 128) * ((p + 127) / 128 * 128)))) return e;
     for (int b = 0; b < 2; ++b) {
-      HIPCHK(h, hipMalloc((void**)&h->dA[b], pp * sizeof(double)));
-      HIPCHK(h, hipMalloc((void**)&h->dAV[b], pp * sizeof(double)));
-      HIPCHK(h, hipMalloc((void**)&h->dAU[b], pp * sizeof(double)));
+      if ((e = h->dA[b].ensure(h, pp))) return e;
+      if ((e = h->dAV[b].ensure(h, pp))) return e;
+      if ((e = h->dAU[b].ensure(h, pp))) return e;
       HIPCHK(h, hipMemsetAsync(h->dAV[b], 0, pp * sizeof(double), st));  // launch_tri_inverse keeps the other triangle zero
       HIPCHK(h, hipMemsetAsync(h->dAU[b], 0, pp * sizeof(double), st));
     }
-    HIPCHK(h, hipMalloc((void**)&h->dAw, (size_t)ldp * 64 * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dAT, pp * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dGinv, (size_t)p * p * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dSinv, (size_t)p * p * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dbetav, p * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dqty, p * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&h->dinfo2, 2 * sizeof(int)));
-    { const int eg = ensure_gsplit(h); if (eg) return eg; }
+    if ((e = h->dAw.ensure(h, (size_t)ldp * 64))) return e;
+    if ((e = h->dAT.ensure(h, pp))) return e;
+    if ((e = h->dGinv.ensure(h, (size_t)p * p))) return e;
+    if ((e = h->dSinv.ensure(h, (size_t)p * p))) return e;
+    if ((e = h->dbetav.ensure(h, p))) return e;
+    if ((e = h->dqty.ensure(h, p))) return e;
+    if ((e = h->dinfo2.ensure(h, 2))) return e;
+    if ((e = ensure_gsplit(h))) return e;
     HIPCHK(h, hipMemsetAsync(h->dinfo2, 0, 2 * sizeof(int), st));
     h->tr_p = p;
     h->ldp = ldp;

@@ -23,13 +23,6 @@
 
 using namespace bogp;
 
-void bogp::believer_release(bogp_handle* h) {
-  dfree(h->dbel_s); dfree(h->dbel_C); dfree(h->dbel_row); dfree(h->dbel_small);
-  h->bel_s_cap = h->bel_C_cap = h->bel_row_cap = h->bel_small_cap = 0;
-  for (auto e : h->bel_ev) (void)hipEventDestroy(e);
-  h->bel_ev.clear();
-}
-
 namespace {
 
 constexpr double PIVOT_FLOOR = 1e-12;  // the noise floor of a unit prior variance: a point at or below it is already determined
@@ -40,15 +33,6 @@ struct Believed {  // host side of the recursion: row i of L holds c_k(p_i) for 
   double L[BOGP_MAX_BELIEVED][BOGP_MAX_BELIEVED];
   int slot[BOGP_MAX_BELIEVED];  // column of dbel_C, -1: guarded or never stored
 };
-
-hipEvent_t bel_event(bogp_handle* h, size_t i) {
-  while (h->bel_ev.size() <= i) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    h->bel_ev.push_back(e);
-  }
-  return h->bel_ev[i];
-}
 
 struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point's correlations with the believed rows, those rows
   double *dpt, *dr, *dvr, *da, *dkk, *drows;
@@ -69,7 +53,7 @@ int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const doub
                    double* pivots, size_t& nev, std::vector<size_t>& ev_solve) {
   const int i = bl.n, d = h->d, N = h->N;
   hipStream_t st = h->stream;
-  hipEvent_t e0 = bel_event(h, nev), e1 = bel_event(h, nev + 1);
+  hipEvent_t e0 = h->bel_ev.at(nev), e1 = h->bel_ev.at(nev + 1);
   if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   ev_solve.push_back(nev);
   nev += 2;
@@ -166,14 +150,14 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   if ((rc = sweep_geometry(h, Np, &pl))) return rc;
   const int64_t nblk_total = (M + 63) / 64 + pl.nchunk;  // (one record per 64 rows)
   const size_t small_n = SolveBufs::doubles(d, N);
-  if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M))) return rc;
-  if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)2 * M))) return rc;
-  if ((rc = ensure(h, &h->dbel_small, &h->bel_small_cap, small_n))) return rc;
+  if ((rc = h->dbel_s.ensure(h, (size_t)M))) return rc;
+  if ((rc = h->dbel_row.ensure(h, (size_t)2 * M))) return rc;
+  if ((rc = h->dbel_small.ensure(h, small_n))) return rc;
   if (Btot > 2)
-    if ((rc = ensure(h, &h->dbel_C, &h->bel_C_cap, (size_t)(Btot - 2) * M))) return rc;  // the last winner runs no pass, the point before it stores no column
-  if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
+    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 2) * M))) return rc;  // the last winner runs no pass, the point before it stores no column
+  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
+  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
   if ((rc = ensure_sweep_outputs(h, 1, nblk_total, 0, false))) return rc;
   const SolveBufs sb(h->dbel_small, d, N);
   double* dacq_row = h->dbel_row;
@@ -243,7 +227,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
     int64_t blk_offset = 0;
     for (int64_t c = 0; c < pl.nchunk; ++c) {
       const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
-      hipEvent_t c0 = bel_event(h, nev), c1 = bel_event(h, nev + 1), c2 = bel_event(h, nev + 2);
+      hipEvent_t c0 = h->bel_ev.at(nev), c1 = h->bel_ev.at(nev + 1), c2 = h->bel_ev.at(nev + 2);
       if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
       ev_chunk.push_back(nev);
       nev += 3;
@@ -476,7 +460,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
     const size_t nb = (size_t)C * m;
     int e;
     ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-    if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, std::max<size_t>(2 * nb, 2)))) return e;
+    if ((e = h->dehvi_cells.ensure(h, std::max<size_t>(2 * nb, 2)))) return e;
     if (nb == 0) return BOGP_OK;
     HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, cells.data(), nb * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, cells.data() + nb, nb * sizeof(double), hipMemcpyHostToDevice, st));
@@ -505,14 +489,14 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   SweepGeometry pl;
   if ((rc = sweep_geometry(h, Np, &pl))) return rc;
   const int64_t nblk = (M + 255) / 256;
-  if ((rc = ensure(h, &h->dbel_s, &h->bel_s_cap, (size_t)M * m))) return rc;
-  if ((rc = ensure(h, &h->dbel_row, &h->bel_row_cap, (size_t)(2 + m) * M))) return rc;
-  if ((rc = ensure(h, &h->dbel_small, &h->bel_small_cap, SolveBufs::doubles(d, N)))) return rc;
+  if ((rc = h->dbel_s.ensure(h, (size_t)M * m))) return rc;
+  if ((rc = h->dbel_row.ensure(h, (size_t)(2 + m) * M))) return rc;
+  if ((rc = h->dbel_small.ensure(h, SolveBufs::doubles(d, N)))) return rc;
   if (Btot > 1)
-    if ((rc = ensure(h, &h->dbel_C, &h->bel_C_cap, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_ehvi
-  if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)pl.S * pl.Mc))) return rc;
+    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_ehvi
+  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
+  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
   if ((rc = ensure_sweep_outputs(h, 1, nblk, 0, false))) return rc;
   const SolveBufs sb(h->dbel_small, d, N);
   double* dehvi_row = h->dbel_row;
@@ -577,7 +561,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
       ba.eval = 0;
       for (int64_t c = 0; c < pl.nchunk; ++c) {
         const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
-        hipEvent_t c0 = bel_event(h, nev), c1 = bel_event(h, nev + 1), c2 = bel_event(h, nev + 2);
+        hipEvent_t c0 = h->bel_ev.at(nev), c1 = h->bel_ev.at(nev + 1), c2 = h->bel_ev.at(nev + 2);
         if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
         ev_chunk.push_back(nev);
         nev += 3;
@@ -604,7 +588,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
       be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C;
     }
     be.mu = h->dmu_out; be.ehvi_out = dehvi_row; be.mse_out = dmse_row; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
-    hipEvent_t b0 = bel_event(h, nev), b1 = bel_event(h, nev + 1);
+    hipEvent_t b0 = h->bel_ev.at(nev), b1 = h->bel_ev.at(nev + 1);
     if (!b0 || !b1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
     ev_ehvi.push_back(nev);
     nev += 2;

@@ -37,7 +37,7 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   hipStream_t st = h->stream;
   int e;
   ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-  if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
+  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
   // (the cells are the kernel's arguments: copied in stream order, before the first chunk's kernels that read them)
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
@@ -60,10 +60,10 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
     HIPCHK(h, hipMemcpy(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost));
   } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks one criterion
     const int64_t nblk = (M + 255) / 256;
-    if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)(nblk + 1)))) return e;
-    if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)(nblk + 1)))) return e;
-    if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dblk_val.ensure(h, (size_t)(nblk + 1)))) return e;
+    if ((e = h->dblk_idx.ensure(h, (size_t)(nblk + 1)))) return e;
+    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
     HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
     HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));

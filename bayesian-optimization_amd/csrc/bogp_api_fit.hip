@@ -56,14 +56,13 @@ static int fit_readback(bogp_handle* h, const double* dS, int nS, double* blk /*
   return BOGP_OK;
 }
 
-// pend == nullptr: queue the device work, read info + scalars back, finish (ONE host synchronisation).
-// pend != nullptr: queue only -- the caller appends its own device work (the likelihood gradient), reads everything back in ONE
-// synchronisation and calls factorize_finish itself.
 extern "C" int bogp_chol_wide_panels(int N, int* widths, int cap) {
   if (N <= 0) return 0;
-  const int ld = N > 3072 ? ((N + 127) / 128) * 128 : ((N + 63) / 64) * 64;  // bogp_set_train's leading dimension
-  return chol_wide_panels(ld, widths, cap < 0 ? 0 : cap);
+  return chol_wide_panels(train_ld(N), widths, cap < 0 ? 0 : cap);
 }
+
+// R^-1 and the UUT_PARTS partial sums of U U^T
+static int ensure_Rinv(bogp_handle* h) { return h->dRinv.ensure(h, (size_t)UUT_PARTS * h->cap_ld * h->cap_ld); }
 
 extern "C" int bogp_nll_path(int N, int d, int trend, int n_targets) {
   if (N <= 0 || d <= 0 || trend != BOGP_TREND_CONSTANT || n_targets != 1) return BOGP_NLL_PATH_GENERAL;
@@ -75,7 +74,7 @@ extern "C" int bogp_nll_path(int N, int d, int trend, int n_targets) {
   // Cholesky / recursive-doubling / U U^T kernels
   constexpr int elim_max = 3072;
   const int ld = ((N + 63) / 64) * 64;
-  if (N <= elim_max && N <= 6080 && ld >= 192 && !(getenv("BOGP_NLL_ELIM") && atoi(getenv("BOGP_NLL_ELIM")) == 0)) return BOGP_NLL_PATH_ELIM;
+  if (N <= elim_max && ld >= 192 && !(getenv("BOGP_NLL_ELIM") && atoi(getenv("BOGP_NLL_ELIM")) == 0)) return BOGP_NLL_PATH_ELIM;
   return BOGP_NLL_PATH_GENERAL;
 }
 
@@ -87,6 +86,9 @@ struct FusedNll {
   bool mid = false;  // 157 <= N <= 3072: k_build_R + k_elim_* left R^-1, gamma, the scalars and the gradient weights; the caller's tail follows
   double S[64 + 3];
 };
+// pend == nullptr: queue the device work, read info + scalars back, finish (ONE host synchronisation).
+// pend != nullptr: queue only -- the caller appends its own device work (the likelihood gradient), reads everything back in ONE
+// synchronisation and calls factorize_finish itself.
 static int factorize(bogp_handle* h, int kernel, int mode, const double* par, int n_par, double noise_var, int trend,
                      int estimate_trend, double beta, bool want_gamma, FitOut* o, std::vector<double>* theta_out,
                      bool reject_positive = true, FitPending* pend = nullptr, FusedNll* fz = nullptr) {
@@ -204,7 +206,7 @@ static int factorize(bogp_handle* h, int kernel, int mode, const double* par, in
   //   gamma = U rho (:788 / :996)
   const int n_t = h->n_t;
   if (elim) {
-    if (!h->dRinv) HIPCHK(h, hipMalloc((void**)&h->dRinv, (size_t)UUT_PARTS * h->cap_ld * h->cap_ld * sizeof(double)));
+    if (int rc = ensure_Rinv(h)) return rc;
     // scratch behind the first of the UUT_PARTS slices of dRinv (the result goes into that slice): two raw panels, block row nb,
     // Yt, Ft, the log-determinant parts
     double* sc0 = h->dRinv + (size_t)ldr * ldr;
@@ -221,8 +223,8 @@ static int factorize(bogp_handle* h, int kernel, int mode, const double* par, in
                           estimate_trend, mode, beta, s2t, st));
     fz->mid = true;
   } else {
-  if (!h->dchain_flags) HIPCHK(h, hipMalloc((void**)&h->dchain_flags, (size_t)2 * (h->cap_ld / 64 + 1) * sizeof(unsigned int)));
-  HIPCHK(h, launch_chol_lower(h->dR, ldr, h->ddinv, h->dinfo, st, h->stream_upd ? h->stream_upd : h->stream2, h->ev_chol, h->dT, N, h->dchain_flags));  // dT: free until the inverse
+  if (int rc = h->dchain_flags.ensure(h, (size_t)2 * (h->cap_ld / 64 + 1))) return rc;
+  HIPCHK(h, launch_chol_lower(h->dR, ldr, h->ddinv, h->dinfo, st, h->stream2, &h->ev_chol[0], h->dT, N, h->dchain_flags));  // dT: free until the inverse
   const bool logdet_in_rho = trend_size(trend, h->d) == 1;  // constant basis: k_fit_rho of target 0 forms sum(log diag L) too (one launch less)
   if (!logdet_in_rho) HIPCHK(h, launch_logdet(h->dR, N, ldr, h->dscal, st));
   HIPCHK(h, launch_tri_inverse(h->dR, h->ddinv, h->dV, h->dU, h->dT, ldr, st));
@@ -395,12 +397,12 @@ extern "C" int bogp_nll(bogp_handle* h, int kernel, int mode, const double* par,
   hipStream_t st = h->stream;
   // R^-1 = cho_solve(L, I) (:997) via potri on a copy of L
   const int ldr = h->ldr;
-  if (!h->dRinv) HIPCHK(h, hipMalloc((void**)&h->dRinv, (size_t)UUT_PARTS * h->cap_ld * h->cap_ld * sizeof(double)));
+  if (int rc = ensure_Rinv(h)) return rc;
   int nparts = UUT_PARTS;
   if (fz.mid) nparts = 1;  // (k_elim_finish left R^-1 itself)
   else HIPCHK(h, launch_uut(h->dU, h->dRinv, ldr, st, &nparts));  // R^-1 = L^-T L^-1, lower triangle
   const int nblk = grad_contract_blocks(N);
-  int e = ensure(h, &h->dgrad_partial, &h->grad_partial_cap, (size_t)nblk * (d + 1) + (d + 4));
+  int e = h->dgrad_partial.ensure(h, (size_t)nblk * (d + 1) + (d + 4));
   if (e) return e;
   // Per-target weights of gamma_t gamma_t^T (single target: 1 / sigma2 resp. 1 / sigma2_total).  With several targets the
   // reference sums gamma gamma^T over ALL targets before dividing by each target's variance in the theta rows of the
@@ -564,7 +566,7 @@ extern "C" int bogp_nll_restricted(bogp_handle* h, int kernel, int mode, const d
   *llf = v;
   if (grad) {
     hipStream_t st = h->stream;
-    if (!h->dRinv) HIPCHK(h, hipMalloc((void**)&h->dRinv, (size_t)UUT_PARTS * h->cap_ld * h->cap_ld * sizeof(double)));
+    if (int rc = ensure_Rinv(h)) return rc;
     int nparts = UUT_PARTS;
     HIPCHK(h, launch_uut(h->dU, h->dRinv, ldr, st, &nparts));
     const double* qv = nullptr;
@@ -584,7 +586,7 @@ extern "C" int bogp_nll_restricted(bogp_handle* h, int kernel, int mode, const d
       c2 = tv / o.ftft;
     }
     const int nblk = grad_contract_blocks(N);
-    int e = ensure(h, &h->dgrad_partial, &h->grad_partial_cap, (size_t)nblk * (d + 1) + (d + 4));
+    int e = h->dgrad_partial.ensure(h, (size_t)nblk * (d + 1) + (d + 4));
     if (e) return e;
     GradVecs gv;
     gv.v = h->dgamma; gv.stride = 0; gv.n = 1; gv.c0 = 1.0; gv.cA[0] = gv.cB[0] = 1.0 / tv;
@@ -643,7 +645,7 @@ extern "C" int bogp_commit(bogp_handle* h, int kernel, int mode, const double* p
     constexpr int steps = 1;  // (0 / 2 steps: tools/refine_experiment.py, r04 -- one step is what the accuracy tests were fixed with)
     const int pt = trend_size(trend, d);
     if (steps > 0) {
-      int e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)4 * N);
+      int e = h->dbatch.ensure(h, (size_t)4 * N);
       if (e) return e;
       double *dres = h->dbatch, *dt1 = dres + N, *dt2 = dt1 + N, *db = dt2 + N;
       for (int t = 0; t < h->n_t; ++t) {
@@ -666,7 +668,7 @@ extern "C" int bogp_commit(bogp_handle* h, int kernel, int mode, const double* p
     }
   }
   // V = L^-1 (the triangular solve of gpr.py:494 becomes a triangular GEMM against V)
-  if (!h->dVp) HIPCHK(h, hipMalloc((void**)&h->dVp, (size_t)h->cap_ld * h->cap_ld * sizeof(double)));
+  if (int rc = h->dVp.ensure(h, (size_t)h->cap_ld * h->cap_ld / 2)) return rc;
   HIPCHK(h, launch_pack_V(h->dV, N, ldr, Np, h->dVp, st));
   // w = L^-T Ft  (so that Ft^T L^-1 r = w . r, gpr.py:496-498)
   HIPCHK(h, hipMemsetAsync(h->dw, 0, Np * sizeof(double), st));
@@ -694,13 +696,8 @@ extern "C" int bogp_commit(bogp_handle* h, int kernel, int mode, const double* p
         const int cols = contract_cols_per_group();
         const int Ne = (Np + cols - 1) / cols * cols, Nt = Ne + (ptrend + 31) / 32 * 32;
         int e2;
-        if ((e2 = ensure(h, &h->dAtx, &h->atx_cap, (size_t)N * ptrend))) return e2;
-        if (h->vpx_cap < (size_t)Nt * Nt / 2 || !h->dVpx) {
-          dfree(h->dVpx);
-          h->vpx_cap = 0;
-          HIPCHK(h, hipMalloc((void**)&h->dVpx, (size_t)Nt * Nt / 2 * sizeof(double2)));
-          h->vpx_cap = (size_t)Nt * Nt / 2;
-        }
+        if ((e2 = h->dAtx.ensure(h, (size_t)N * ptrend))) return e2;
+        if ((e2 = h->dVpx.ensure(h, (size_t)Nt * Nt / 2))) return e2;
         HIPCHK(h, launch_gemm(0, 0, N, ptrend, ptrend, one, h->dWp, Np, h->dGinv, ptrend, zero, h->dAtx, N, st, 0, &h->gsplit));  // W G^-1
         HIPCHK(h, launch_pack_Vx(h->dV, N, ldr, h->dAtx, N, h->dGinv, ptrend, Ne, Nt, h->dVpx, st));
         h->vx_Ne = Ne; h->vx_Nt = Nt;
@@ -708,8 +705,8 @@ extern "C" int bogp_commit(bogp_handle* h, int kernel, int mode, const double* p
     }
   }
   // [d][Np] + two zero rows: k_sweep_small walks the dimensions three at a time
-  if (!h->dXthT) HIPCHK(h, hipMalloc((void**)&h->dXthT, (size_t)(h->cap_d + 2) * h->cap_ld * sizeof(double)));
-  if (!h->dXnorm) HIPCHK(h, hipMalloc((void**)&h->dXnorm, (size_t)h->cap_ld * sizeof(double)));
+  if (int rc = h->dXthT.ensure(h, (size_t)(h->cap_d + 2) * h->cap_ld)) return rc;
+  if (int rc = h->dXnorm.ensure(h, (size_t)h->cap_ld)) return rc;
   HIPCHK(h, launch_scale_transpose(h->dX, N, d, Np, h->dsqrt_theta, h->dXthT, h->dXnorm, st));
   HIPCHK(h, hipMemsetAsync(h->dXthT + (size_t)d * Np, 0, (size_t)2 * Np * sizeof(double), st));
   HIPCHK(h, hipStreamSynchronize(st));
@@ -732,7 +729,7 @@ extern "C" int bogp_get_state(bogp_handle* h, double* C, double* gamma, double* 
   hipStream_t st = h->stream;
   HIPCHK(h, hipSetDevice(h->device));
   if (C) {
-    if (!h->dRinv) HIPCHK(h, hipMalloc((void**)&h->dRinv, (size_t)UUT_PARTS * h->cap_ld * h->cap_ld * sizeof(double)));
+    if (int rc = ensure_Rinv(h)) return rc;
     HIPCHK(h, launch_copy_lower(h->dR, N, h->ldr, h->dRinv, st));
     HIPCHK(h, hipMemcpyAsync(C, h->dRinv, (size_t)N * N * sizeof(double), hipMemcpyDeviceToHost, st));
   }

@@ -118,8 +118,8 @@ static int forest_set_impl(bogp_handle* h, const char* who, int T, int d, int m,
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // a forest call in flight still reads the old forest
   int e;
-  if ((e = ensure(h, &h->dforest_words, &h->forest_words_cap, words.size()))) return e;
-  if ((e = ensure(h, &h->dforest_tree, &h->forest_tree_cap, (size_t)T))) return e;
+  if ((e = h->dforest_words.ensure(h, words.size()))) return e;
+  if ((e = h->dforest_tree.ensure(h, (size_t)T))) return e;
   HIPCHK(h, hipMemcpy(h->dforest_words, words.data(), words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->dforest_tree, trees.data(), (size_t)T * sizeof(ForestTree), hipMemcpyHostToDevice));
   if (h->forest_T && d != h->d) {  // rows of another width are not candidates of this forest
@@ -177,8 +177,7 @@ static int run_forest(bogp_handle* h, const char* who, ForestArgs& a, int64_t ro
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
   if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
   if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
-  for (int i = 0; i < 2; ++i)
-    if (!h->forest_ev[i]) HIPCHK(h, hipEventCreate(&h->forest_ev[i]));
+  if (!h->forest_ev.at(1)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d;
   a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
   HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
@@ -206,8 +205,8 @@ extern "C" int bogp_forest_predict(bogp_handle* h, double* mu, double* mse) {
   HIPCHK(h, hipSetDevice(h->device));
   const int64_t M = h->M;
   int e;
-  if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M))) return e;
-  if ((e = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M))) return e;
+  if ((e = h->dmu_out.ensure(h, (size_t)M))) return e;
+  if ((e = h->dmse_out.ensure(h, (size_t)M))) return e;
   ForestArgs a;
   memset(&a, 0, sizeof(a));
   a.mu_out = h->dmu_out; a.mse_out = mse ? h->dmse_out : nullptr; a.minimize = 1;
@@ -226,7 +225,7 @@ extern "C" int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, doub
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)n * h->forest_T;
   int e;
-  if ((e = ensure(h, &h->dbatch, &h->batch_cap, cnt))) return e;
+  if ((e = h->dbatch.ensure(h, cnt))) return e;
   ForestArgs a;
   memset(&a, 0, sizeof(a));
   a.leaves_out = h->dbatch; a.minimize = 1;
@@ -256,11 +255,10 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
   const bool keep = k > 1 || acq_out;
   hipStream_t st = h->stream;
   int e;
-  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * (nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * (nblk + 1)))) return e;
-  if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-  if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
-  if (keep && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return e;
+  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dbest_val.ensure(h, BOGP_MAX_Q)) || (e = h->dbest_idx.ensure(h, BOGP_MAX_Q))) return e;
+  if (keep && (e = h->dacq_out.ensure(h, (size_t)q * M))) return e;
   ForestArgs a;
   memset(&a, 0, sizeof(a));
   a.q = q;
@@ -278,8 +276,8 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
     HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk (dtopk_*: what bogp_exchange_topk packs)
-    if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
     HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
     HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -307,8 +305,7 @@ static int run_forest_ehvi(bogp_handle* h, const char* who, ForestEhviArgs& a, i
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
   if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
   if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
-  for (int i = 0; i < 2; ++i)
-    if (!h->forest_ev[i]) HIPCHK(h, hipEventCreate(&h->forest_ev[i]));
+  if (!h->forest_ev.at(1)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d; a.m = h->forest_m;
   a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
   HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
@@ -332,8 +329,8 @@ extern "C" int bogp_forest_predict_multi(bogp_handle* h, double* mu, double* mse
   if ((e = forest_multi_ready(h, "bogp_forest_predict_multi"))) return e;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)h->M * h->forest_m;
-  if ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, cnt))) return e;
-  if (mse && (e = ensure(h, &h->dmse_out, &h->mse_out_cap, cnt))) return e;
+  if ((e = h->dmu_out.ensure(h, cnt))) return e;
+  if (mse && (e = h->dmse_out.ensure(h, cnt))) return e;
   ForestEhviArgs a;
   memset(&a, 0, sizeof(a));
   a.mu_out = h->dmu_out; a.mse_out = mse ? h->dmse_out : nullptr;
@@ -351,7 +348,7 @@ extern "C" int bogp_forest_leaves_multi(bogp_handle* h, int64_t first_row, int n
   if ((e = forest_multi_ready(h, "bogp_forest_leaves_multi"))) return e;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)n * h->forest_T * h->forest_m;
-  if ((e = ensure(h, &h->dbatch, &h->batch_cap, cnt))) return e;
+  if ((e = h->dbatch.ensure(h, cnt))) return e;
   ForestEhviArgs a;
   memset(&a, 0, sizeof(a));
   a.leaves_out = h->dbatch;
@@ -384,14 +381,13 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
   const int64_t M = h->M, nblk = (M + 255) / 256;
   const bool keep = k > 1 || ehvi_out;
   ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-  if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
-  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)(nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)(nblk + 1)))) return e;
-  if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-  if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
-  if (keep && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)M))) return e;
-  if (mu_out && (e = ensure(h, &h->dmu_out, &h->mu_out_cap, (size_t)M * m))) return e;
-  if (mse_out && (e = ensure(h, &h->dmse_out, &h->mse_out_cap, (size_t)M * m))) return e;
+  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
+  if ((e = h->dblk_val.ensure(h, (size_t)(nblk + 1)))) return e;
+  if ((e = h->dblk_idx.ensure(h, (size_t)(nblk + 1)))) return e;
+  if ((e = h->dbest_val.ensure(h, BOGP_MAX_Q)) || (e = h->dbest_idx.ensure(h, BOGP_MAX_Q))) return e;
+  if (keep && (e = h->dacq_out.ensure(h, (size_t)M))) return e;
+  if (mu_out && (e = h->dmu_out.ensure(h, (size_t)M * m))) return e;
+  if (mse_out && (e = h->dmse_out.ensure(h, (size_t)M * m))) return e;
   // (the cells are the kernel's arguments: copied in stream order before the kernel that reads them)
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
@@ -408,8 +404,8 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
     HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_ehvi ranks them
-    if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
     HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
     HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -454,8 +450,8 @@ extern "C" int bogp_candidates_generate_mixed(bogp_handle* h, const int* kind, c
     h->hXs_lazy = nullptr;
   }
   int e;
-  if ((e = ensure(h, &h->dXs_owned, &h->xs_cap, (size_t)M * d))) return e;
-  if ((e = ensure(h, &h->dbounds, &h->bounds_cap, (size_t)3 * d))) return e;
+  if ((e = h->dXs_owned.ensure(h, (size_t)M * d))) return e;
+  if ((e = h->dbounds.ensure(h, (size_t)3 * d))) return e;
   HIPCHK(h, hipMemcpyAsync(h->dbounds, spec.data(), spec.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, launch_generate_mixed(h->dXs_owned, M * d, d, h->dbounds, h->dbounds + d, h->dbounds + 2 * d, seed,
                                   (uint64_t)first_row * (uint64_t)d, h->stream));

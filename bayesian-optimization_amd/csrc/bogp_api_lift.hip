@@ -41,7 +41,7 @@ extern "C" int bogp_lift_set(bogp_handle* h, int D, const double* A, const doubl
   memcpy(p + 2 * D, lo, D * sizeof(double));
   memcpy(p + 3 * D, hi, D * sizeof(double));
   h->lift_D = 0;
-  int e = ensure(h, &h->dlift, &h->lift_cap, blk.size());
+  int e = h->dlift.ensure(h, blk.size());
   if (e) return e;
   HIPCHK(h, hipStreamSynchronize(h->stream));  // (a queued sweep may still read the old block)
   HIPCHK(h, hipMemcpy(h->dlift, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -102,12 +102,11 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   const int64_t M = h->M;
   const int r = h->d;
   const int64_t nblk = (M + 255) / 256;
-  for (auto& ev : h->lift_ev)
-    if (!ev) HIPCHK(h, hipEventCreate(&ev));
-  if ((e = ensure(h, &h->dlift_pen, &h->lift_pen_cap, (size_t)M))) return e;
-  if ((e = ensure(h, &h->dlift_cnt, &h->lift_cnt_cap, (size_t)nblk))) return e;
-  if ((e = ensure(h, &h->dlift_off, &h->lift_off_cap, (size_t)nblk + 1))) return e;
-  if ((e = ensure(h, &h->dlift_val, &h->lift_val_cap, (size_t)q * M))) return e;
+  if (!h->lift_ev.at(3)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  if ((e = h->dlift_pen.ensure(h, (size_t)M))) return e;
+  if ((e = h->dlift_cnt.ensure(h, (size_t)nblk))) return e;
+  if ((e = h->dlift_off.ensure(h, (size_t)nblk + 1))) return e;
+  if ((e = h->dlift_val.ensure(h, (size_t)q * M))) return e;
 
   // 1. feasibility of all M rows, the scan of the workgroup counts, M_f to the host (it sizes the compact buffers and the sweep)
   LiftArgs la;
@@ -121,8 +120,8 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   if (Mf < 0 || Mf > M) FAIL(h, BOGP_ERR_HIP, "bogp_lift_sweep_topk: the scan returned %lld feasible rows of %lld", (long long)Mf, (long long)M);
   // 2. the feasible rows in their original order
   if (Mf > 0) {
-    if ((e = ensure(h, &h->dlift_Z, &h->lift_Z_cap, (size_t)Mf * r))) return e;
-    if ((e = ensure(h, &h->dlift_map, &h->lift_map_cap, (size_t)Mf))) return e;
+    if ((e = h->dlift_Z.ensure(h, (size_t)Mf * r))) return e;
+    if ((e = h->dlift_map.ensure(h, (size_t)Mf))) return e;
     HIPCHK(h, launch_lift_compact(h->dXs, M, r, h->dlift_pen, h->dlift_off, h->dlift_Z, h->dlift_map, st));
   }
   HIPCHK(h, hipEventRecord(h->lift_ev[1], st));
@@ -140,10 +139,10 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   // 4. criterion values and penalties side by side over all M rows, ranked as bogp_sweep_topk ranks
   HIPCHK(h, hipEventRecord(h->lift_ev[2], st));
   HIPCHK(h, launch_lift_merge(h->dlift_pen, M, h->dacq_out, h->dlift_map, Mf, q, h->dlift_val, st));
-  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * (nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * (nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
   HIPCHK(h, launch_topk(h->dlift_val, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
   HIPCHK(h, hipEventRecord(h->lift_ev[3], st));
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));

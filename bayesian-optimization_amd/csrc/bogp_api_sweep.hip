@@ -40,14 +40,14 @@ static int lazy_copy_to(bogp_handle* h, int64_t upto) {
   const size_t d = (size_t)h->d;
   HIPCHK(h, hipMemcpyAsync(h->dXs_owned + (size_t)h->lazy_done * d, h->hXs_lazy + (size_t)h->lazy_done * d,
                            (size_t)(upto - h->lazy_done) * d * sizeof(double), hipMemcpyHostToDevice, h->stream_copy));
-  HIPCHK(h, hipEventRecord(h->ev_copy, h->stream_copy));
+  HIPCHK(h, hipEventRecord(h->ev_copy[0], h->stream_copy));
   h->lazy_done = upto;
   return BOGP_OK;
 }
 // `st` waits for every copy enqueued so far
 static int lazy_wait(bogp_handle* h, hipStream_t st) {
   if (!h->hXs_lazy || h->lazy_done == 0) return BOGP_OK;
-  HIPCHK(h, hipStreamWaitEvent(st, h->ev_copy, 0));
+  HIPCHK(h, hipStreamWaitEvent(st, h->ev_copy[0], 0));
   return BOGP_OK;
 }
 // everything copied and visible to the main stream; the host rows are not needed any more
@@ -76,11 +76,11 @@ extern "C" int bogp_candidates_upload_lazy(bogp_handle* h, const double* Xs, int
   int e = lazy_drop(h);
   if (e) return e;
   if (!h->stream_copy) HIPCHK(h, hipStreamCreateWithFlags(&h->stream_copy, hipStreamNonBlocking));
-  if (!h->ev_copy) HIPCHK(h, hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
-  if ((e = ensure(h, &h->dXs_owned, &h->xs_cap, (size_t)M * h->d))) return e;
+  if (!h->ev_copy.at(0)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  if ((e = h->dXs_owned.ensure(h, (size_t)M * h->d))) return e;
   // (the buffer may have been re-allocated, and the last sweep may still read the old candidates: the copies start behind it)
-  HIPCHK(h, hipEventRecord(h->ev_copy, h->stream));
-  HIPCHK(h, hipStreamWaitEvent(h->stream_copy, h->ev_copy, 0));
+  HIPCHK(h, hipEventRecord(h->ev_copy[0], h->stream));
+  HIPCHK(h, hipStreamWaitEvent(h->stream_copy, h->ev_copy[0], 0));
   h->dXs = h->dXs_owned;
   h->M = M;
   h->hXs_lazy = Xs;
@@ -97,7 +97,7 @@ extern "C" int bogp_candidates_upload(bogp_handle* h, const double* Xs, int64_t 
   HIPCHK(h, hipSetDevice(h->device));
   int e = lazy_drop(h);
   if (e) return e;
-  if ((e = ensure(h, &h->dXs_owned, &h->xs_cap, (size_t)M * h->d))) return e;
+  if ((e = h->dXs_owned.ensure(h, (size_t)M * h->d))) return e;
   HIPCHK(h, hipMemcpyAsync(h->dXs_owned, Xs, (size_t)M * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->dXs = h->dXs_owned;
@@ -116,8 +116,8 @@ static int generate_prepare(bogp_handle* h, const char* who, const double* lo, c
   HIPCHK(h, hipSetDevice(h->device));
   int e = lazy_drop(h);
   if (e) return e;
-  if ((e = ensure(h, &h->dXs_owned, &h->xs_cap, (size_t)M * d))) return e;
-  if ((e = ensure(h, &h->dbounds, &h->bounds_cap, (size_t)2 * d))) return e;
+  if ((e = h->dXs_owned.ensure(h, (size_t)M * d))) return e;
+  if ((e = h->dbounds.ensure(h, (size_t)2 * d))) return e;
   HIPCHK(h, hipMemcpyAsync(h->dbounds, lo, d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->dbounds + d, hi, d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   return BOGP_OK;
@@ -148,7 +148,7 @@ extern "C" int bogp_candidates_set_transform(bogp_handle* h, const int* scale, c
     h->h_xform.clear();
     return BOGP_OK;
   }
-  if (!h->dxform) HIPCHK(h, hipMalloc((void**)&h->dxform, (size_t)4 * BOGP_MAX_DIM * sizeof(double)));
+  if (int rc = h->dxform.ensure(h, (size_t)4 * BOGP_MAX_DIM)) return rc;
   h->h_xform = spec;
   HIPCHK(h, hipMemcpy(h->dxform, spec.data(), spec.size() * sizeof(double), hipMemcpyHostToDevice));
   return BOGP_OK;
@@ -197,7 +197,7 @@ extern "C" int bogp_candidates_min_pdist2(bogp_handle* h, double* min_sq) {
     const int e = lazy_finish(h);
     if (e) return e;
   }
-  unsigned long long* dout = (unsigned long long*)h->dscal;
+  unsigned long long* dout = (unsigned long long*)h->dscal.ptr;
   HIPCHK(h, launch_min_pdist2(h->dXs, (int)h->M, h->d, dout, h->stream));
   unsigned long long bits = 0;
   HIPCHK(h, hipMemcpyAsync(&bits, dout, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
@@ -219,11 +219,11 @@ extern "C" int bogp_candidates_generate_lhs_maximin(bogp_handle* h, const double
   if (e) return e;
   const int d = h->d;
   // trial designs live in the unit cube, un-transformed (pyDOE measures the design before the caller scales it)
-  if ((e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)2 * d))) return e;
+  if ((e = h->dbatch.ensure(h, (size_t)2 * d))) return e;
   std::vector<double> unit((size_t)2 * d, 0.0);
   for (int k = 0; k < d; ++k) unit[d + k] = 1.0;
   HIPCHK(h, hipMemcpyAsync(h->dbatch, unit.data(), (size_t)2 * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  unsigned long long* dout = (unsigned long long*)h->dscal;
+  unsigned long long* dout = (unsigned long long*)h->dscal.ptr;
   double best = -1.0;
   int best_it = 0;
   for (int it = 0; it < iterations; ++it) {
@@ -256,9 +256,9 @@ extern "C" int bogp_candidates_generate_sobol(bogp_handle* h, const double* lo, 
   if (!sv || bits < 1 || bits > 53) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_generate_sobol: direction numbers must be non-null with 1 <= bits <= 53");
   if (((uint64_t)(first_index + M - 1) >> bits) != 0) FAIL(h, BOGP_ERR_INVALID, "bogp_candidates_generate_sobol: index %lld needs more than %d bits", (long long)(first_index + M - 1), bits);
   const int d = h->d;
-  if ((e = ensure(h, &h->dsobol, &h->sobol_cap, (size_t)d * bits))) return e;
+  if ((e = h->dsobol.ensure(h, (size_t)d * bits))) return e;
   HIPCHK(h, hipMemcpyAsync(h->dsobol, sv, (size_t)d * bits * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, launch_generate_sobol(h->dXs_owned, M * d, d, h->dbounds, h->dbounds + d, (const uint64_t*)h->dsobol, bits,
+  HIPCHK(h, launch_generate_sobol(h->dXs_owned, M * d, d, h->dbounds, h->dbounds + d, (const uint64_t*)h->dsobol.ptr, bits,
                                   (uint64_t)first_index * (uint64_t)d, h->stream));
   return generate_finish(h, M);
 }
@@ -301,15 +301,6 @@ extern "C" int bogp_candidates_bind(bogp_handle* h, const void* d_Xs, int64_t M)
 // ------------------------------------------------------------------------------------------------------
 // posterior + acquisition sweep
 // ------------------------------------------------------------------------------------------------------
-static hipEvent_t get_event(bogp_handle* h, size_t i) {
-  while (h->ev.size() <= i) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    h->ev.push_back(e);
-  }
-  return h->ev[i];
-}
-
 // events per chunk: [0] corr start, [1] corr end (producer stream); [2] contract start, [3] contract end,
 // [4] acquisition end = chunk done (main stream)
 constexpr int EPC = 5;
@@ -401,13 +392,12 @@ CorrArgs bogp::corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int
 int bogp::ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out) {
   int e;
   if (q > 0) {
-    if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * nblk))) return e;
-    if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * nblk))) return e;
-    if (!h->dbest_val) HIPCHK(h, hipMalloc((void**)&h->dbest_val, BOGP_MAX_Q * sizeof(double)));
-    if (!h->dbest_idx) HIPCHK(h, hipMalloc((void**)&h->dbest_idx, BOGP_MAX_Q * sizeof(int64_t)));
+    if ((e = h->dblk_val.ensure(h, (size_t)q * nblk))) return e;
+    if ((e = h->dblk_idx.ensure(h, (size_t)q * nblk))) return e;
+    if ((e = h->dbest_val.ensure(h, BOGP_MAX_Q)) || (e = h->dbest_idx.ensure(h, BOGP_MAX_Q))) return e;
   }
-  if (n_out > 0 && ((e = ensure(h, &h->dmu_out, &h->mu_out_cap, n_out)) || (e = ensure(h, &h->dmse_out, &h->mse_out_cap, n_out)))) return e;
-  if (want_acq_out && (e = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * h->M))) return e;
+  if (n_out > 0 && ((e = h->dmu_out.ensure(h, n_out)) || (e = h->dmse_out.ensure(h, n_out)))) return e;
+  if (want_acq_out && (e = h->dacq_out.ensure(h, (size_t)q * h->M))) return e;
   return BOGP_OK;
 }
 
@@ -479,7 +469,7 @@ static int sweep_small_batch(bogp_handle* h, const SweepRequest& rq) {
   hipStream_t st = h->stream;
   const int64_t M = h->M;
   int e, B = (int)M, N = h->N;
-  if ((e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)3 * N * B + 3 * (size_t)B))) return e;
+  if ((e = h->dbatch.ensure(h, (size_t)3 * N * B + 3 * (size_t)B))) return e;
   double *dr = h->dbatch, *ds2 = dr + (size_t)N * B, *drt = ds2 + (size_t)N * B;
   double* dred = drt + (size_t)N * B;  // mu[B], wd[B], ss[B]
   if ((e = ensure_sweep_outputs(h, rq.q, 2, rq.want_out ? (size_t)M : 0, rq.want_acq_out))) return e;
@@ -506,7 +496,7 @@ static int sweep_one_launch(bogp_handle* h, const SweepRequest& rq) {
   int e;
   if ((e = ensure_sweep_outputs(h, rq.q, nblk, rq.want_out ? (size_t)M : 0, rq.want_acq_out))) return e;
   if (!h->dcounter) {
-    HIPCHK(h, hipMalloc((void**)&h->dcounter, sizeof(unsigned int)));
+    if ((e = h->dcounter.ensure(h, 1))) return e;
     HIPCHK(h, hipMemsetAsync(h->dcounter, 0, sizeof(unsigned int), st));
   }
   SmallArgs sa;
@@ -522,11 +512,11 @@ static int sweep_one_launch(bogp_handle* h, const SweepRequest& rq) {
   sa.best_val = h->dbest_val; sa.best_idx = h->dbest_idx;
   const bool stamps = getenv("BOGP_SMALL_STAMPS") && atoi(getenv("BOGP_SMALL_STAMPS"));
   if (stamps) {  // measurement aid: per-phase wave-cycles of this launch, printed on stderr
-    if ((e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)8))) return e;
+    if ((e = h->dbatch.ensure(h, (size_t)8))) return e;
     HIPCHK(h, hipMemsetAsync(h->dbatch, 0, 8 * sizeof(double), st));
-    sa.stamps = (long long*)h->dbatch;
+    sa.stamps = (long long*)h->dbatch.ptr;
   }
-  hipEvent_t e0 = get_event(h, 0), e1 = get_event(h, 1);
+  hipEvent_t e0 = h->ev.at(0), e1 = h->ev.at(1);
   if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   HIPCHK(h, hipEventRecord(e0, st));
   HIPCHK(h, launch_sweep_small(h->kernel, sa, h->n_cu, st));
@@ -566,34 +556,34 @@ static int sweep_workspace(bogp_handle* h, SweepCtx& cx) {
                  // FP32 stage: S1's indices and candidate rows, both capped like S's; the segment's flags, sums and norms
                  w_sidx1 = w_xc1 + (cx.bound32 ? (size_t)cx.sidx_cap * h->d : 0), w_flag1 = w_sidx1 + (cx.bound32 ? (size_t)cx.sidx_cap : 0),
                  w_row32 = w_flag1 + (cx.bound32 ? (size_t)cx.Rmax / 8 + 1 : 0), w_end = w_row32 + (cx.bound32 ? (size_t)3 * cx.Rmax : 0);
-    if ((e = ensure(h, &h->dprune, &h->prune_cap, w_end))) return e;
+    if ((e = h->dprune.ensure(h, w_end))) return e;
     cx.pctl = h->dprune; cx.poffsets = (int64_t*)(h->dprune + w_off); cx.pmap = (int64_t*)(h->dprune + w_map); cx.psel = (int*)(h->dprune + w_sel);
     cx.pblk_count = (int*)(h->dprune + w_cnt); cx.pflags = (unsigned char*)(h->dprune + w_flag);
     cx.psidx = (int64_t*)(h->dprune + w_sidx); cx.pxc = (double*)(h->dprune + w_xc);
     cx.pxc1 = (double*)(h->dprune + w_xc1); cx.psidx1 = (int64_t*)(h->dprune + w_sidx1); cx.pflags1 = (unsigned char*)(h->dprune + w_flag1);
     if (cx.bound32) { h->b32_ws_row32 = w_row32; h->b32_ws_flag1 = w_flag1; h->b32_ws_rmax = (size_t)cx.Rmax; }
     cx.pmu32 = (double*)(h->dprune + w_row32); cx.pwd32 = cx.pmu32 + cx.Rmax; cx.pna32 = cx.pwd32 + cx.Rmax;
-    if ((e = ensure(h, &h->drT[1], &h->rT_cap[1], (size_t)cx.Nrows * cx.Ms))) return e;
-    if ((e = ensure(h, &h->dmu_part[1], &h->mu_part_cap[1], (size_t)S * cx.Ms))) return e;
-    if ((e = ensure(h, &h->dw_part[1], &h->w_part_cap[1], (size_t)S * cx.Ms))) return e;
+    if ((e = h->drT[1].ensure(h, (size_t)cx.Nrows * cx.Ms))) return e;
+    if ((e = h->dmu_part[1].ensure(h, (size_t)S * cx.Ms))) return e;
+    if ((e = h->dw_part[1].ensure(h, (size_t)S * cx.Ms))) return e;
   }
   for (int b = 0; b < nbuf; ++b) {
     // (one pass: the chunk buffer is allocated only if a per-chunk path runs after all; the partial sums are a segment's)
-    if (!cx.onepass && (e = ensure(h, &h->drT[b], &h->rT_cap[b], (size_t)cx.Nrows * Mc))) return e;
-    if ((e = ensure(h, &h->dmu_part[b], &h->mu_part_cap[b], (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
-    if ((e = ensure(h, &h->dw_part[b], &h->w_part_cap[b], (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
+    if (!cx.onepass && (e = h->drT[b].ensure(h, (size_t)cx.Nrows * Mc))) return e;
+    if ((e = h->dmu_part[b].ensure(h, (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
+    if ((e = h->dw_part[b].ensure(h, (size_t)S * (cx.onepass ? cx.Rmax : Mc)))) return e;
   }
-  if ((e = ensure(h, &h->dss_part, &h->ss_part_cap, (size_t)cx.nJ * (Mc + cx.Ms)))) return e;  // (+ the survivor buffer's sums)
+  if ((e = h->dss_part.ensure(h, (size_t)cx.nJ * (Mc + cx.Ms)))) return e;  // (+ the survivor buffer's sums)
   cx.dss_surv = h->dss_part + (size_t)cx.nJ * Mc;
   if (h->p > 1) {
     const size_t n_tiles = (size_t)Mc * ((h->p + 127) / 128 * 128);  // whole 128-column tiles (k_mm128)
-    if (!cx.vx_model && ((e = ensure(h, &h->dTt, &h->Tt_cap, n_tiles)) || (e = ensure(h, &h->dCS, &h->CS_cap, n_tiles)))) return e;
-    if ((e = ensure(h, &h->duu, &h->uu_cap, (size_t)Mc))) return e;
-    if ((e = ensure(h, &h->dmtrend, &h->mtrend_cap, (size_t)Mc))) return e;
+    if (!cx.vx_model && ((e = h->dTt.ensure(h, n_tiles)) || (e = h->dCS.ensure(h, n_tiles)))) return e;
+    if ((e = h->duu.ensure(h, (size_t)Mc))) return e;
+    if ((e = h->dmtrend.ensure(h, (size_t)Mc))) return e;
   }
   if (cx.pv > 0)
     for (int b = 0; b < nbuf; ++b)
-      if ((e = ensure(h, &h->dtpart[b], &h->tpart_cap[b], (size_t)S * cx.pv * Mc))) return e;
+      if ((e = h->dtpart[b].ensure(h, (size_t)S * cx.pv * Mc))) return e;
   return BOGP_OK;
 }
 
@@ -786,7 +776,7 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
 
 // the next event of a one-pass sweep, recorded on st; *idx = its index in h->ev
 static int mark_event(bogp_handle* h, hipStream_t st, size_t* ev_next, int* idx) {
-  hipEvent_t ev1 = get_event(h, *ev_next);
+  hipEvent_t ev1 = h->ev.at(*ev_next);
   if (!ev1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   HIPCHK(h, hipEventRecord(ev1, st));
   *idx = (int)(*ev_next)++;
@@ -847,7 +837,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   // a per-chunk path after all: chunks [c0, c1) behind the pilot, with the chunk buffer they need
   auto fall_back = [&](int64_t c0, int64_t c1, int path) -> int {
     int e2;
-    if ((e2 = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)cx.Nrows * Mc))) return e2;
+    if ((e2 = h->drT[0].ensure(h, (size_t)cx.Nrows * Mc))) return e2;
     if ((e2 = sweep_chunks(h, cx, c0, c1, true))) return e2;
     for (int64_t c = c0; c < c1; ++c) h->t_chunks.push_back(c);
     contract_launches += (int)(c1 - c0);
@@ -981,7 +971,7 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * (rq.eh ? rq.eh->m : 1) : 0, rq.want_acq_out))) return e;
   // the chunks' events, the two-stream mode's begin event, the pilot's pair (pruned sweep)
   for (size_t i = 0; i <= (size_t)(nchunk * EPC + 2); ++i)
-    if (!get_event(h, i)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+    if (!h->ev.at(i)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   if (cx.overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
     HIPCHK(h, hipEventRecord(h->ev[(size_t)(nchunk * EPC)], cx.st));
     HIPCHK(h, hipStreamWaitEvent(cx.stP, h->ev[(size_t)(nchunk * EPC)], 0));
@@ -1052,10 +1042,10 @@ extern "C" int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const d
   const int64_t nblk = (M + 255) / 256;
   hipStream_t st = h->stream;
   int e;
-  if ((e = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * (nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * (nblk + 1)))) return e;
-  if ((e = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  if ((e = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
   HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -1093,8 +1083,8 @@ int bogp::bound32_prepare(bogp_handle* h) {
   const int d = h->d, Np = h->Np;
   hipStream_t st = h->stream;
   int e;
-  if ((e = ensure(h, &h->dX32, &h->x32_cap, (size_t)4 * ((d + 3) / 4) * Np)) || (e = ensure(h, &h->dvec32, &h->vec32_cap, (size_t)3 * Np))) return e;
-  if (!h->dstats32) HIPCHK(h, hipMalloc((void**)&h->dstats32, 3 * sizeof(double)));
+  if ((e = h->dX32.ensure(h, (size_t)4 * ((d + 3) / 4) * Np)) || (e = h->dvec32.ensure(h, (size_t)3 * Np))) return e;
+  if ((e = h->dstats32.ensure(h, 3))) return e;
   HIPCHK(h, launch_bound32_prepare(h->dXthT, h->dXnorm, h->dgamma, h->dw, d, Np, h->dX32, h->dvec32, h->dstats32, st));
   HIPCHK(h, hipMemcpyAsync(h->stats32, h->dstats32, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
@@ -1208,7 +1198,7 @@ extern "C" int bogp_gradient(bogp_handle* h, const double* x, double* dmu, doubl
     return point_eval_host(h, "bogp_gradient", x, 1, 0, nullptr, nullptr, 0.0, 1, nullptr, nullptr, dmu, dmse, nullptr, nullptr);
   if (pt > 1 && h->trend == BOGP_TREND_QUADRATIC)
     FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_gradient: the quadratic trend has no Jacobian in the reference either (trend.py:138-139)");
-  int e = ensure(h, &h->dgrad_partial, &h->grad_partial_cap, (size_t)N * (d + 3) + 4 * d + 8 + (size_t)pt * (d + 1));
+  int e = h->dgrad_partial.ensure(h, (size_t)N * (d + 3) + 4 * d + 8 + (size_t)pt * (d + 1));
   if (e) return e;
   double* dr = h->dgrad_partial;            // N
   double* drdx = dr + N;                    // d x N (column k = dr/dx_k); [r | dr/dx] is one N x (d+1) column-major matrix
@@ -1269,7 +1259,7 @@ extern "C" int bogp_hessian(bogp_handle* h, const double* x, double* H) {
   const int N = h->N, d = h->d;
   hipStream_t st = h->stream;
   HIPCHK(h, hipSetDevice(h->device));
-  int e = ensure(h, &h->dgrad_partial, &h->grad_partial_cap, (size_t)N * (d + 1) + d + (size_t)d * d);
+  int e = h->dgrad_partial.ensure(h, (size_t)N * (d + 1) + d + (size_t)d * d);
   if (e) return e;
   double* dr = h->dgrad_partial;
   double* drdx = dr + N;
@@ -1292,7 +1282,7 @@ extern "C" int bogp_prior_corr(bogp_handle* h, const double* X1, int n1, double*
   const int d = h->d;
   hipStream_t st = h->stream;
   HIPCHK(h, hipSetDevice(h->device));
-  int e = ensure(h, &h->dbatch, &h->batch_cap, (size_t)n1 * d + 2 * (size_t)n1 * n1);
+  int e = h->dbatch.ensure(h, (size_t)n1 * d + 2 * (size_t)n1 * n1);
   if (e) return e;
   double* dX1 = h->dbatch;
   double* dr = dX1 + (size_t)n1 * d;
@@ -1346,21 +1336,16 @@ extern "C" int bogp_selftest_gemm(bogp_handle* h, int ta, int tb, int m, int n, 
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const size_t na = (size_t)lda * (ta ? m : k), nb = (size_t)ldb * (tb ? k : n), nc = (size_t)ldc * n;
-  double *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  DevBuf<double> dA, dB, dC;
   int rc = BOGP_OK;
   if (split && (rc = ensure_gsplit(h))) return rc;
-  if (hipMalloc((void**)&dA, na * sizeof(double)) != hipSuccess || hipMalloc((void**)&dB, nb * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&dC, nc * sizeof(double)) != hipSuccess) {
-    dfree(dA); dfree(dB); dfree(dC);
-    FAIL(h, BOGP_ERR_HIP, "bogp_selftest_gemm: hipMalloc failed");
-  }
+  if (dA.ensure(h, na) || dB.ensure(h, nb) || dC.ensure(h, nc)) FAIL(h, BOGP_ERR_HIP, "bogp_selftest_gemm: hipMalloc failed");
   hipError_t e = hipMemcpyAsync(dA, A, na * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dB, B, nb * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dC, C, nc * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = launch_gemm(ta, tb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, st, tri, split ? &h->gsplit : nullptr);
   if (e == hipSuccess) e = hipMemcpyAsync(C, dC, nc * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  dfree(dA); dfree(dB); dfree(dC);
   if (e != hipSuccess) FAIL(h, BOGP_ERR_HIP, "bogp_selftest_gemm: %s", hipGetErrorString(e));
   return BOGP_OK;
 }

@@ -22,23 +22,7 @@
 
 using namespace bogp;
 
-void bogp::thompson_release(bogp_handle* h) {
-  dfree(h->dth_small);
-  h->th_small_cap = 0;
-  for (auto e : h->th_ev) (void)hipEventDestroy(e);
-  h->th_ev.clear();
-}
-
 namespace {
-
-hipEvent_t th_event(bogp_handle* h, size_t i) {
-  while (h->th_ev.size() <= i) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    h->th_ev.push_back(e);
-  }
-  return h->th_ev[i];
-}
 
 bool all_finite(const double* v, size_t n) {
   for (size_t i = 0; i < n; ++i)
@@ -93,7 +77,7 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
 
   // dth_small: omega (L d) | phase (L) | W (16 L) | -g (16 N4) | s (N q) | V s (N q) | R^-1 s (N q)
   const size_t n_small = (size_t)L * d + L + (size_t)16 * L + (size_t)16 * N4 + (size_t)3 * N * q;
-  if ((rc = ensure(h, &h->dth_small, &h->th_small_cap, n_small))) return rc;
+  if ((rc = h->dth_small.ensure(h, n_small))) return rc;
   double* domega = h->dth_small;
   double* dphase = domega + (size_t)L * d;
   double* dW = dphase + L;
@@ -102,16 +86,16 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   double* dvs = ds + (size_t)N * q;
   double* da = dvs + (size_t)N * q;
   if (conditioned) {
-    if ((rc = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * Mc))) return rc;
-    if ((rc = ensure(h, &h->dmu_part[0], &h->mu_part_cap[0], (size_t)S * Mc))) return rc;
-    if ((rc = ensure(h, &h->dw_part[0], &h->w_part_cap[0], (size_t)S * Mc))) return rc;
+    if ((rc = h->drT[0].ensure(h, (size_t)Np * Mc))) return rc;
+    if ((rc = h->dmu_part[0].ensure(h, (size_t)S * Mc))) return rc;
+    if ((rc = h->dw_part[0].ensure(h, (size_t)S * Mc))) return rc;
   }
-  if ((rc = ensure(h, &h->dblk_val, &h->blk_val_cap, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
-  if ((rc = ensure(h, &h->dblk_idx, &h->blk_idx_cap, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
-  if ((rc = ensure(h, &h->dtopk_val, &h->topk_val_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
-  if ((rc = ensure(h, &h->dtopk_idx, &h->topk_idx_cap, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
+  if ((rc = h->dblk_val.ensure(h, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
+  if ((rc = h->dblk_idx.ensure(h, (size_t)q * std::max(nblk_total, nblk256 + 1)))) return rc;
+  if ((rc = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
+  if ((rc = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return rc;
   if (store)
-    if ((rc = ensure(h, &h->dacq_out, &h->acq_out_cap, (size_t)q * M))) return rc;
+    if ((rc = h->dacq_out.ensure(h, (size_t)q * M))) return rc;
 
   // ---- the draw: W scaled by sqrt(2 sigma2 / L) and padded to 16 columns
   const double scale = std::sqrt(2.0 * h->sigma2 / (double)L);
@@ -127,7 +111,7 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   ta.d = d; ta.L = L; ta.N = N; ta.q = q; ta.omega = domega; ta.phase = dphase; ta.W = dW;
 
   size_t nev = 0;
-  auto event = [&]() -> hipEvent_t { return th_event(h, nev++); };
+  auto event = [&]() -> hipEvent_t { return h->th_ev.at(nev++); };
   hipEvent_t s0 = event(), s1 = event();
   if (!s0 || !s1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   HIPCHK(h, hipEventRecord(s0, st));

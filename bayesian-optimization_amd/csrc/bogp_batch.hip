@@ -77,22 +77,12 @@ bool prep_slot(int kernel, int mode, int d, const double* par, int n_par, double
   return true;
 }
 
-// pinned, device-mapped staging of the batch: [cap doubles] (parameter rows, then result records) + the sequence word behind them
+// pinned, device-mapped staging of the batch: parameter rows, then result records, + the sequence word in the block's last 8 doubles
 int ensure_pinned(bogp_handle* h, size_t doubles) {
-  if (h->hbatch && h->hbatch_cap >= doubles) return BOGP_OK;
-  if (h->hbatch) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipHostFree(h->hbatch));
-    h->hbatch = h->hbatch_dev = nullptr;
-    h->hbatch_cap = 0;
-  }
-  const size_t cap = std::max<size_t>(doubles, 16384);
-  HIPCHK(h, hipHostMalloc((void**)&h->hbatch, (cap + 8) * sizeof(double), hipHostMallocMapped));
-  HIPCHK(h, hipHostGetDevicePointer((void**)&h->hbatch_dev, h->hbatch, 0));
-  memset(h->hbatch, 0, (cap + 8) * sizeof(double));
-  h->hbatch_cap = cap;
+  int e;
+  if ((e = h->hbatch.ensure(h, std::max<size_t>(doubles, 16384) + 8))) return e;
   if (!h->dbatch_ticket) {
-    HIPCHK(h, hipMalloc((void**)&h->dbatch_ticket, 2 * sizeof(unsigned int)));
+    if ((e = h->dbatch_ticket.ensure(h, 2))) return e;
     HIPCHK(h, hipMemset(h->dbatch_ticket, 0, 2 * sizeof(unsigned int)));
   }
   return BOGP_OK;
@@ -138,24 +128,18 @@ int ensure_slots(bogp_handle* h, int P, int ld, int d, int N) {
   const SlotLayout L = slot_layout(ld, d, N);
   const size_t row = up8((size_t)d + 1) + 8;  // a parameter row: theta, exponent | a, b, diag, s2t
   const size_t need = (size_t)P * (L.total + row + 8);
-  if (h->bws_cap < need) {
+  int e;
+  if (h->dbws.cap < need) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    dfree(h->dbws);
-    h->bws_cap = 0;
     h->bws_P = 0;
     // (a BO loop grows N by one point per tell(): a quarter of head room keeps the slab for ~60 iterations instead of re-allocating
     // every time a tile count ticks up)
-    const size_t cap = need + need / 4;
-    HIPCHK(h, hipMalloc((void**)&h->dbws, cap * sizeof(double)));
-    h->bws_cap = cap;
+    if ((e = h->dbws.ensure(h, need + need / 4))) return e;
   }
-  if (h->bslots_cap < (size_t)P) {
+  if (h->dbslots.cap < (size_t)P) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    dfree(h->dbslots);
-    h->bslots_cap = 0;
     h->bws_P = 0;
-    HIPCHK(h, hipMalloc((void**)&h->dbslots, (size_t)P * sizeof(BatchSlot)));
-    h->bslots_cap = (size_t)P;
+    if ((e = h->dbslots.ensure(h, (size_t)P))) return e;
   }
   std::vector<BatchSlot> tab((size_t)P);
   double* rows = h->dbws + (size_t)P * L.total;
@@ -183,19 +167,6 @@ int ensure_slots(bogp_handle* h, int P, int ld, int d, int N) {
 
 }  // namespace
 
-namespace bogp {
-void batch_release(bogp_handle* h) {
-  if (h->hbatch) (void)hipHostFree(h->hbatch);
-  h->hbatch = h->hbatch_dev = nullptr;
-  h->hbatch_cap = 0;
-  dfree(h->dbatch_ticket);
-  dfree(h->dbws);
-  dfree(h->dbslots);
-  h->bws_cap = h->bslots_cap = 0;
-  h->bws_P = 0;
-}
-}  // namespace bogp
-
 // One group of at most `Pg` slots that all take the same device path.  slot_of[i] = index into the caller's arrays.
 static int run_group(bogp_handle* h, int path, int kernel, int mode, const std::vector<int>& slot_of, const double* par, int n_par,
                      double noise_var, int estimate_trend, double beta, const std::vector<SlotPrep>& prep, const std::vector<double>& theta,
@@ -213,9 +184,9 @@ static int run_group(bogp_handle* h, int path, int kernel, int mode, const std::
   }
   double* hin = h->hbatch;
   double* hout = h->hbatch + (size_t)Pg * in_stride;
-  double* dout = h->hbatch_dev + (size_t)Pg * in_stride;
-  unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hbatch_dev + h->hbatch_cap);
-  const void* hflag = h->hbatch + h->hbatch_cap;
+  double* dout = h->hbatch.dev + (size_t)Pg * in_stride;
+  unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hbatch.dev + (h->hbatch.cap - 8));
+  const void* hflag = h->hbatch + (h->hbatch.cap - 8);
   const unsigned long long seq = ++h->batch_seq;
 
   if (path == BOGP_NLL_PATH_ONE_LAUNCH) {
@@ -236,7 +207,7 @@ static int run_group(bogp_handle* h, int path, int kernel, int mode, const std::
     na.estimate_trend = estimate_trend; na.mode = mode; na.beta = beta;
     na.out_scal = nullptr; na.out_S = nullptr;
     na.flag = dflag; na.seq = seq;
-    na.bpar = h->hbatch_dev; na.bout = dout; na.bticket = h->dbatch_ticket; na.P = Pg; na.bout_stride = (int)out_stride;
+    na.bpar = h->hbatch.dev; na.bout = dout; na.bticket = h->dbatch_ticket; na.P = Pg; na.bout_stride = (int)out_stride;
     HIPCHK(h, launch_nll_small(kernel, want_grad, na, st));
   } else {  // BOGP_NLL_PATH_ELIM
     const int ld = h->ldr;

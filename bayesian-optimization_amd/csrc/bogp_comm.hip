@@ -162,11 +162,7 @@ extern "C" int bogp_comm_destroy(bogp_handle* h) {
 }
 
 namespace bogp {
-void comm_release(bogp_handle* h) {  // from bogp_destroy
-  (void)bogp_comm_destroy(h);
-  dfree(h->dxchg_send);
-  dfree(h->dxchg_recv);
-}
+void comm_release(bogp_handle* h) { (void)bogp_comm_destroy(h); }  // from bogp_destroy
 }  // namespace bogp
 
 // ---- the deterministic reduces (host; a few hundred bytes) ----------------------------------------------------------
@@ -238,8 +234,8 @@ static int exchange(bogp_handle* h, const double* dval, const int64_t* didx, int
   const int rec = 2 + (with_points ? d : 0);
   const size_t nsend = (size_t)n * rec;
   int e;
-  if ((e = ensure(h, &h->dxchg_send, &h->xchg_send_cap, nsend))) return e;
-  if ((e = ensure(h, &h->dxchg_recv, &h->xchg_recv_cap, nsend * R))) return e;
+  if ((e = h->dxchg_send.ensure(h, nsend))) return e;
+  if ((e = h->dxchg_recv.ensure(h, nsend * R))) return e;
   hipLaunchKernelGGL(k_pack_winners, dim3(n), 64, 0, st, dval, didx, n, index_offset, h->dXs, d, with_points, h->dxchg_send);
   HIPCHK(h, hipGetLastError());
   NCCLCHK(h, g_rccl.AllGather(h->dxchg_send, h->dxchg_recv, nsend, ncclDouble, (ncclComm_t)h->comm, st));

@@ -1,9 +1,11 @@
-// bogp_handle.h -- the device state behind an opaque bogp_handle (include/bogp.h) and the error plumbing shared by the
-// translation units that implement the C ABI (bogp_api.hip, bogp_comm.hip).
+// bogp_handle.h -- the device state behind an opaque bogp_handle (include/bogp.h), the three types that own its device memory,
+// pinned blocks and events (DevBuf, MappedBuf, EventPool), and the error plumbing shared by the translation units that implement the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -12,11 +14,7 @@
 
 struct bogp_handle;
 namespace bogp {
-void comm_release(bogp_handle* h);   // bogp_comm.hip: destroys an owned communicator, frees the exchange buffers
-void point_release(bogp_handle* h);  // bogp_point.hip: frees the point-evaluation buffers
-void batch_release(bogp_handle* h);  // bogp_batch.hip: frees the batched-likelihood staging and workspaces
-void believer_release(bogp_handle* h);  // bogp_api_believer.hip: frees the Kriging-believer arrays and events
-void thompson_release(bogp_handle* h);  // bogp_api_thompson.hip: frees the draw's buffer and the events
+void comm_release(bogp_handle* h);   // bogp_comm.hip: destroys an owned communicator
 std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: the handles a batch of one-evaluation calls is dealt over
 // bogp_point.hip: posterior, input-gradients and q criteria of B points through k_point_rhs + k_point_tri.  `Xb` is a HOST
 // array (B x d).  Outputs (host, any may be null): mu, mse (B), dmu, dmse (B x d), acq (B x q), dacq (B x q x d).
@@ -54,13 +52,85 @@ bool has_dim(const bogp_handle* h);
 void ehvi_cells_forget(bogp_handle* h);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Ownership.  Every device allocation, mapped pinned block and event of a handle is a member of one of the three types below and is
+// released by that member's destructor (bogp_destroy only synchronises, then deletes the handle).  A raw pointer in bogp_handle is a
+// VIEW into one of them and is never freed.  Non-copyable; bogp_debug_live reads the process-wide counts.
+// ------------------------------------------------------------------------------------------------------
+namespace bogp {
+struct LiveCounts { std::atomic<int64_t> allocations{0}, bytes{0}, events{0}; };
+inline LiveCounts g_live;
+inline void live_note(int64_t n, size_t bytes) { g_live.allocations += n; g_live.bytes += n * (int64_t)bytes; }
+
+// one hipMalloc allocation of `cap` elements
+template <typename T>
+struct DevBuf {
+  T* ptr = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { free(); }
+  operator T*() const { return ptr; }
+  // at least n elements: nothing if they are there; otherwise the old block is freed FIRST and exactly n are allocated (no copy, no
+  // growth factor, never shrinks).  On failure the buffer is empty and the handle's error is set.
+  int ensure(bogp_handle* h, size_t n);
+  void free() {
+    if (ptr) { (void)hipFree(ptr); live_note(-1, cap * sizeof(T)); }
+    ptr = nullptr;
+    cap = 0;
+  }
+};
+
+// one hipHostMallocMapped block of `cap` doubles and its device address (hfit, hpin, hbatch)
+struct MappedBuf {
+  double *ptr = nullptr, *dev = nullptr;
+  size_t cap = 0;
+  MappedBuf() = default;
+  MappedBuf(const MappedBuf&) = delete;
+  MappedBuf& operator=(const MappedBuf&) = delete;
+  ~MappedBuf() { free(); }
+  operator double*() const { return ptr; }
+  int ensure(bogp_handle* h, size_t n);  // as DevBuf::ensure; the handle's stream is synchronised before a block is replaced, a new block is zero-filled
+  void free() {
+    if (ptr) { (void)hipHostFree(ptr); live_note(-1, cap * sizeof(double)); }
+    ptr = dev = nullptr;
+    cap = 0;
+  }
+};
+
+// events created on demand and kept for the handle's life
+struct EventPool {
+  std::vector<hipEvent_t> ev;
+  unsigned flags;
+  explicit EventPool(unsigned f = hipEventDefault) : flags(f) {}
+  EventPool(const EventPool&) = delete;
+  EventPool& operator=(const EventPool&) = delete;
+  ~EventPool() {
+    for (auto e : ev) (void)hipEventDestroy(e);
+    g_live.events -= (int64_t)ev.size();
+  }
+  hipEvent_t at(size_t i) {  // event i, created with those before it where it does not exist yet; null on failure
+    while (ev.size() <= i) {
+      hipEvent_t e;
+      if (hipEventCreateWithFlags(&e, flags) != hipSuccess) return nullptr;
+      ev.push_back(e);
+      ++g_live.events;
+    }
+    return ev[i];
+  }
+  hipEvent_t& operator[](size_t i) { return ev[i]; }  // an event that at() has created
+};
+}  // namespace bogp
+
 struct bogp_handle {
+  // The views (raw pointers into a member below, never freed): dy, dyt, drho, dgamma (the active target's part of d*_base), dsqrt_theta
+  // (dtheta), dinfo (dscal), dXs (dXs_owned), bws_rows (dbws), hfit_dev (hfit), gsplit's two pointers (dgsplit_*).  hXs_lazy is the caller's.
   int device = 0;
   int n_cu = 256;  // compute units of the device (launch planning of the fused small-N sweep)
   hipStream_t stream = nullptr;
-  unsigned int* dchain_flags = nullptr;  // 2 * (cap_ld / 64) words: hand-over flags of the resident diagonal chain (k_chol_chain)
-  hipEvent_t ev_chol[2] = {nullptr, nullptr};  // look-ahead of the large-matrix Cholesky (second stream)
-  hipStream_t stream_upd = nullptr;  // (r04 experiment, always null since r06: a CU-masked stream for the look-ahead update of the two-level Cholesky)
+  bogp::DevBuf<unsigned int> dchain_flags;  // 2 * (cap_ld / 64) words: hand-over flags of the resident diagonal chain (k_chol_chain)
+  bogp::EventPool ev_chol{hipEventDisableTiming};  // [2] look-ahead of the large-matrix Cholesky (second stream)
   hipStream_t stream2 = nullptr;  // producer stream: k_corr_chunk of chunk c+1 runs beside k_contract of chunk c
   std::string err;
 
@@ -69,28 +139,28 @@ struct bogp_handle {
   int cap_ld = 0, cap_d = 0, cap_nt = 0;
   int N = 0, d = 0, Np = 0;
   int ldr = 0;  // leading dimension of dR / dV / dRinv: N rounded up to 64 (identity padding, kernels_chol.hip)
-  double *dX = nullptr, *dy = nullptr;
-  // multi-target y (gpr.py:463,490,502-505): the factorisation is shared, the vectors exist once per target.  dy / dyt /
-  // drho / dgamma above and `sigma2` below always point at the ACTIVE target (bogp_select_target) inside these slabs.
+  bogp::DevBuf<double> dX;
+  // multi-target y (gpr.py:463,490,502-505): the factorisation is shared, the vectors exist once per target.  The views dy / dyt /
+  // drho / dgamma and `sigma2` below always point at the ACTIVE target (bogp_select_target) inside these slabs.
   int n_t = 1, target = 0;
-  double *dy_base = nullptr, *dyt_base = nullptr, *drho_base = nullptr, *dgamma_base = nullptr;
+  bogp::DevBuf<double> dy_base, dyt_base, drho_base, dgamma_base;  // N, N, N, Np (zero padded) per target
+  double *dy = nullptr, *dyt = nullptr, *drho = nullptr, *dgamma = nullptr;  // views
   std::vector<double> sigma2_t, nv_t;  // committed, per target
 
   // factorisation workspace (column-major, ld = ldr)
-  double *dR = nullptr, *dV = nullptr, *dU = nullptr, *dT = nullptr, *dRinv = nullptr;  // L, L^-1, L^-T, scratch, R^-1
-  double* dones = nullptr;  // N ones (the constant trend basis)
-  double* dgemv_scratch = nullptr;  // segment partials of launch_gemv2
+  bogp::DevBuf<double> dR, dV, dU, dT, dRinv;  // L, L^-1, L^-T, scratch, R^-1
+  bogp::DevBuf<double> dones;  // N ones (the constant trend basis)
+  bogp::DevBuf<double> dgemv_scratch;  // segment partials of launch_gemv2
   std::vector<double> h_theta;  // [theta (d + 1) | sqrt_theta (d + 1)]: the block uploaded by factorize
-  double* ddinv = nullptr;  // ldr x 64: inverses of the diagonal blocks of the running factorisation (kernels_chol.hip)
-  double *dyt = nullptr, *dft = nullptr, *drho = nullptr, *dtmp = nullptr;  // N each
-  double *dgamma = nullptr, *dw = nullptr;                                  // Np each (zero padded)
-  double *dtheta = nullptr, *dsqrt_theta = nullptr;                         // d each
-  double* dscal = nullptr;                                                  // small scalar scratch
-  int* dinfo = nullptr;
-  double* dgrad_partial = nullptr;
-  size_t grad_partial_cap = 0;
-  double* dbatch = nullptr;
-  size_t batch_cap = 0;
+  bogp::DevBuf<double> ddinv;  // ldr x 64: inverses of the diagonal blocks of the running factorisation (kernels_chol.hip)
+  bogp::DevBuf<double> dft, dtmp;  // N each
+  bogp::DevBuf<double> dw;         // Np (zero padded)
+  bogp::DevBuf<double> dtheta;     // [theta (d + 1) | sqrt_theta (d + 1)]
+  double* dsqrt_theta = nullptr;   // view: the second half of dtheta
+  bogp::DevBuf<double> dscal;      // small scalar scratch
+  int* dinfo = nullptr;            // view: doubles 62-63 of dscal
+  bogp::DevBuf<double> dgrad_partial;
+  bogp::DevBuf<double> dbatch;
 
   // how the last factorisation formed R from the correlations (k_build_R's arguments): what bogp_commit's refinement of
   // gamma recomputes R with
@@ -101,55 +171,47 @@ struct bogp_handle {
   bool committed = false;
   int kernel = 0, mode = 0, estimate_trend = 0;
   double beta = 0, G = 0, sigma2 = 0, noise_var = 0, llf = 0, ftft = 0;
-  double* dXthT = nullptr;  // [d][Np]
-  double* dXnorm = nullptr;  // [Np] squared norms of the columns of XthT (k_corr_mfma)
+  bogp::DevBuf<double> dXthT;  // [d][Np]
+  bogp::DevBuf<double> dXnorm;  // [Np] squared norms of the columns of XthT (k_corr_mfma)
   // trend-rows path (p > 32 columns under universal kriging, kernels_fit.hip: k_pack_Vx): the packed extended factor, its row offsets
-  double2* dVpx = nullptr;
-  size_t vpx_cap = 0;
-  double* dAtx = nullptr;  // W G^-1 (N x p)
-  size_t atx_cap = 0;
+  bogp::DevBuf<double2> dVpx;
+  bogp::DevBuf<double> dAtx;  // W G^-1 (N x p)
   int vx_Ne = 0, vx_Nt = 0;  // 0: the committed model does not use the path
-  double2* dVp = nullptr;   // [Np/16][Np/8][64]
+  bogp::DevBuf<double2> dVp;  // [Np/16][Np/8][64]
 
   // candidates
-  const double* dXs = nullptr;
-  double* dXs_owned = nullptr;
-  size_t xs_cap = 0;
-  double* dbounds = nullptr;
-  size_t bounds_cap = 0;
-  double* dxform = nullptr;  // per dimension [scale id, precision, lo, hi] of bogp_candidates_set_transform, or null
+  const double* dXs = nullptr;  // view: dXs_owned once candidates are set
+  bogp::DevBuf<double> dXs_owned;
+  bogp::DevBuf<double> dbounds;
+  bogp::DevBuf<double> dxform;  // per dimension [scale id, precision, lo, hi] of bogp_candidates_set_transform, or null
   std::vector<double> h_xform;
-  double* dsobol = nullptr;  // d x bits direction numbers (uint64 bit patterns)
-  size_t sobol_cap = 0;
+  bogp::DevBuf<double> dsobol;  // d x bits direction numbers (uint64 bit patterns)
   int64_t M = 0;
   // bogp_candidates_upload_lazy: host rows that are copied chunk by chunk on `stream_copy` WHILE the sweep contracts the chunk before
   // (run_sweep); lazy_done = rows whose copy has been enqueued, ev_copy = recorded behind the last enqueued copy
   const double* hXs_lazy = nullptr;
   int64_t lazy_done = 0;
   hipStream_t stream_copy = nullptr;
-  hipEvent_t ev_copy = nullptr;
+  bogp::EventPool ev_copy{hipEventDisableTiming};  // [1]
 
   // sweep scratch
-  double *drT[2] = {nullptr, nullptr}, *dmu_part[2] = {nullptr, nullptr}, *dw_part[2] = {nullptr, nullptr};
-  double* dss_part = nullptr;
-  size_t rT_cap[2] = {0, 0}, mu_part_cap[2] = {0, 0}, w_part_cap[2] = {0, 0}, ss_part_cap = 0;
-  double *dblk_val = nullptr, *dmu_out = nullptr, *dmse_out = nullptr, *dacq_out = nullptr, *dbest_val = nullptr;
-  int64_t *dblk_idx = nullptr, *dbest_idx = nullptr;
-  unsigned int* dcounter = nullptr;  // arrival ticket of k_sweep_small's last workgroup (zero between launches)
+  bogp::DevBuf<double> drT[2], dmu_part[2], dw_part[2];
+  bogp::DevBuf<double> dss_part;
+  bogp::DevBuf<double> dblk_val, dmu_out, dmse_out, dacq_out, dbest_val;
+  bogp::DevBuf<int64_t> dblk_idx, dbest_idx;
+  bogp::DevBuf<unsigned int> dcounter;  // arrival ticket of k_sweep_small's last workgroup (zero between launches)
   // pruned sweep (kernels_prune.hip; bogp_set_prune): control words | block offsets | index map | selected rows | block counts | flags
   int prune_mode = 1;            // bogp_set_prune: 0 off, 1 automatic (one pass where it applies), 2 the per-chunk path
   int prune_path = 0;            // BOGP_PRUNE_PATH_* of the last sweep; survivors behind the pilot and rounds of its one-pass segments
   int64_t prune_survivors = 0;
   int prune_rounds = 0;
-  long long* dprune = nullptr;
-  size_t prune_cap = 0;
+  bogp::DevBuf<long long> dprune;
   // FP32 bounding stage of the one-pass flow (kernels_bound32.hip; bogp_set_prune_bound32): FP32 copies of the committed
   // model -- [4 ceil(d / 4)][Np] scaled points | norms, gamma, w (Np each) | three statistics -- valid while b32_gen == commit_gen and
   // b32_target == target (rebuilt by bound32_prepare at commit and, for another target, by the sweep that needs them)
   int prune_bound32 = 1;
-  float *dX32 = nullptr, *dvec32 = nullptr;
-  double* dstats32 = nullptr;
-  size_t x32_cap = 0, vec32_cap = 0;
+  bogp::DevBuf<float> dX32, dvec32;
+  bogp::DevBuf<double> dstats32;
   double stats32[3] = {0, 0, 0};
   uint64_t commit_gen = 0, b32_gen = 0;
   int b32_target = -1;
@@ -159,12 +221,9 @@ struct bogp_handle {
   int64_t b32_last_rows = 0;           // rows of the last segment bounded in FP32: what bogp_debug_bound32 reads back
   bool prune_used = false;       // the last sweep pruned: its contracted-row count is on the device (dprune[4])
   int64_t contracted_rows = 0;   // ... otherwise it is this
-  double* dtopk_val = nullptr;   // [q][k] winners of bogp_sweep_topk (device-resident between its passes)
-  int64_t* dtopk_idx = nullptr;
-  size_t topk_val_cap = 0, topk_idx_cap = 0;
-  size_t blk_val_cap = 0, blk_idx_cap = 0, mu_out_cap = 0, mse_out_cap = 0, acq_out_cap = 0;
-  double* dehvi_cells = nullptr;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
-  size_t ehvi_cells_cap = 0;
+  bogp::DevBuf<double> dtopk_val;  // [q][k] winners of bogp_sweep_topk (device-resident between its passes)
+  bogp::DevBuf<int64_t> dtopk_idx;
+  bogp::DevBuf<double> dehvi_cells;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
   // host copy of the cells bogp_point_eval_ehvi / bogp_polish_ehvi left in dehvi_cells ([lower | upper], ehvi_host_C x ehvi_host_m): a call
   // with the same cells skips the upload.  Empty <=> unknown: every other writer of dehvi_cells clears it (ehvi_cells_forget)
   std::vector<double> h_ehvi_cells;
@@ -172,35 +231,31 @@ struct bogp_handle {
 
   // lift of a reduced search space (bogp_api_lift.hip): lift_D > 0 <=> a lift is set, for a model of d = lift_r
   int lift_D = 0, lift_r = 0;
-  double* dlift = nullptr;        // [A (r x D) | mean | center | lo | hi]
-  size_t lift_cap = 0;
-  double* dlift_pen = nullptr;    // [M] penalties of the last lifted sweep
-  int* dlift_cnt = nullptr;       // [ceil(M / 256)] feasible rows per workgroup
-  int64_t* dlift_off = nullptr;   // their exclusive scan, + M_f
-  double* dlift_Z = nullptr;      // [M_f][r] the feasible rows in their original order
-  int64_t* dlift_map = nullptr;   // [M_f] their original indices
-  double* dlift_val = nullptr;    // [q][M] merged values
-  size_t lift_pen_cap = 0, lift_cnt_cap = 0, lift_off_cap = 0, lift_Z_cap = 0, lift_map_cap = 0, lift_val_cap = 0;
-  hipEvent_t lift_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // filter begin / end, merge begin / end
+  bogp::DevBuf<double> dlift;       // [A (r x D) | mean | center | lo | hi]
+  bogp::DevBuf<double> dlift_pen;   // [M] penalties of the last lifted sweep
+  bogp::DevBuf<int> dlift_cnt;      // [ceil(M / 256)] feasible rows per workgroup
+  bogp::DevBuf<int64_t> dlift_off;  // their exclusive scan, + M_f
+  bogp::DevBuf<double> dlift_Z;     // [M_f][r] the feasible rows in their original order
+  bogp::DevBuf<int64_t> dlift_map;  // [M_f] their original indices
+  bogp::DevBuf<double> dlift_val;   // [q][M] merged values
+  bogp::EventPool lift_ev;          // [4] filter begin / end, merge begin / end
   int64_t lift_n_feasible = 0;
   double lift_filter_ms = 0, lift_merge_ms = 0;
 
   // Kriging-believer batches (bogp_api_believer.hip): the running variance and the stored c_k columns of the believed points
-  double* dbel_s = nullptr;      // [M] sigma2 s_B(x), unclamped below the sweep's own clamp of s_0
-  double* dbel_C = nullptr;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
-  double* dbel_row = nullptr;    // [2][M] criterion values / MSE of the step evaluated last
-  double* dbel_small = nullptr;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
-  size_t bel_s_cap = 0, bel_C_cap = 0, bel_row_cap = 0, bel_small_cap = 0;
-  std::vector<hipEvent_t> bel_ev;
+  bogp::DevBuf<double> dbel_s;      // [M] sigma2 s_B(x), unclamped below the sweep's own clamp of s_0
+  bogp::DevBuf<double> dbel_C;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
+  bogp::DevBuf<double> dbel_row;    // [2][M] criterion values / MSE of the step evaluated last
+  bogp::DevBuf<double> dbel_small;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
+  bogp::EventPool bel_ev;
   double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
   // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
   double bel_ehvi_ms = 0;  // k_believer_ehvi of the last bogp_sweep_believer_ehvi
 
   // Thompson-sampling batches (bogp_api_thompson.hip)
-  double* dth_small = nullptr;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight
-  size_t th_small_cap = 0;
-  std::vector<hipEvent_t> th_ev;
+  bogp::DevBuf<double> dth_small;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight
+  bogp::EventPool th_ev;
   double th_corr_ms = 0, th_solve_ms = 0, th_paths_ms = 0;  // of the last bogp_sweep_thompson: producer, draw at X + solves, k_thompson
   int th_chunks = 0;
 
@@ -209,10 +264,9 @@ struct bogp_handle {
   int forest_T = 0, forest_tree_words = 0, forest_depth = 0;
   int forest_m = 1;  // outputs a leaf holds: 1 (bogp_forest_set) or 2 .. BOGP_MAX_TARGETS (bogp_forest_set_multi)
   int64_t forest_nodes = 0, forest_leaves = 0;
-  unsigned long long* dforest_words = nullptr;
-  bogp::ForestTree* dforest_tree = nullptr;
-  size_t forest_words_cap = 0, forest_tree_cap = 0;
-  hipEvent_t forest_ev[2] = {nullptr, nullptr};  // around k_forest of the last forest call
+  bogp::DevBuf<unsigned long long> dforest_words;
+  bogp::DevBuf<bogp::ForestTree> dforest_tree;
+  bogp::EventPool forest_ev;  // [2] around k_forest of the last forest call
 
   // polynomial trend bases with p > 1 columns (linear / quadratic; the constant basis keeps its scalar fast path)
   int trend = BOGP_TREND_CONSTANT, p = 1;  // committed
@@ -230,66 +284,56 @@ struct bogp_handle {
   bool aux_fail_valid = false;         // a helper could not be loaded (device memory) at train_gen == aux_fail_gen: not retried until the training set changes
   unsigned long aux_fail_gen = 0;
   std::vector<double> h_betav, h_Sinv;     // committed beta (p) and (Ft^T Ft)^-1 (p x p, column-major) for bogp_gradient
-  double *dF = nullptr, *dFt = nullptr, *dQ1 = nullptr, *dQ = nullptr;  // N x p, column-major, ld = N
-  double* dWp = nullptr;                                                // Np x p: L^-T Ft, zero-padded rows
-  bogp::GemmSplit gsplit = {nullptr, 0, nullptr, 0};  // split-K scratch of the small products (kernels_gemm.hip), allocated with the trend buffers
-  double* dWpT = nullptr;    // pp x Np (pp = p rounded up to 128): W^T, zero rows in the padding -- column side of the k_mm128 trend product
-  double* dSinvP = nullptr;  // pp x pp: (Ft^T Ft)^-1, zero padded
-  double *dA[2] = {nullptr, nullptr}, *dAV[2] = {nullptr, nullptr}, *dAU[2] = {nullptr, nullptr};  // ldp x ldp (CholeskyQR2)
-  double *dAw = nullptr, *dAT = nullptr;                                // ldp x 64, ldp x ldp scratch
-  double *dGinv = nullptr, *dSinv = nullptr, *dbetav = nullptr, *dqty = nullptr;  // p x p, p x p, p, p
-  int* dinfo2 = nullptr;
-  double *dTt = nullptr, *dCS = nullptr, *duu = nullptr, *dmtrend = nullptr;  // per sweep chunk: Mc x p, Mc x p, Mc, Mc
-  size_t Tt_cap = 0, CS_cap = 0, uu_cap = 0, mtrend_cap = 0;
-  double* dtpart[2] = {nullptr, nullptr};  // [S][pv][Mc] slice sums of W^T r from the fused producer (p <= 32)
-  size_t tpart_cap[2] = {0, 0};
+  bogp::DevBuf<double> dF, dFt, dQ1, dQ;  // N x p, column-major, ld = N
+  bogp::DevBuf<double> dWp;               // Np x p: L^-T Ft, zero-padded rows
+  // split-K scratch of the small products (kernels_gemm.hip), allocated with the trend buffers; gsplit = what launch_gemm takes: views of the two
+  bogp::DevBuf<double> dgsplit_scratch;
+  bogp::DevBuf<unsigned int> dgsplit_tickets;
+  bogp::GemmSplit gsplit = {nullptr, 0, nullptr, 0};
+  bogp::DevBuf<double> dWpT;    // pp x Np (pp = p rounded up to 128): W^T, zero rows in the padding -- column side of the k_mm128 trend product
+  bogp::DevBuf<double> dSinvP;  // pp x pp: (Ft^T Ft)^-1, zero padded
+  bogp::DevBuf<double> dA[2], dAV[2], dAU[2];  // ldp x ldp (CholeskyQR2)
+  bogp::DevBuf<double> dAw, dAT;               // ldp x 64, ldp x ldp scratch
+  bogp::DevBuf<double> dGinv, dSinv, dbetav, dqty;  // p x p, p x p, p, p
+  bogp::DevBuf<int> dinfo2;
+  bogp::DevBuf<double> dTt, dCS, duu, dmtrend;  // per sweep chunk: Mc x p, Mc x p, Mc, Mc
+  bogp::DevBuf<double> dtpart[2];  // [S][pv][Mc] slice sums of W^T r from the fused producer (p <= 32)
 
   // cross-rank exchange (bogp_comm.hip): RCCL communicator (owned or borrowed), send / receive records on the device, and
   // what the last sweep left in dbest_* / dtopk_* for bogp_exchange_* to pack
   void* comm = nullptr;
   bool comm_owned = false;
   int comm_rank = 0, comm_world = 0;
-  double *dxchg_send = nullptr, *dxchg_recv = nullptr;
-  size_t xchg_send_cap = 0, xchg_recv_cap = 0;
+  bogp::DevBuf<double> dxchg_send, dxchg_recv;
   int last_q = 0, last_topk_q = 0, last_topk_k = 0;
 
   // one-point / B-point evaluation and the lock-step polish (kernels_point.hip, bogp_point.hip)
-  double *dpt_rhs = nullptr, *dpt_part = nullptr, *dpt_out = nullptr, *dpt_Xb = nullptr, *dpt_state = nullptr, *dpt_box = nullptr;
-  size_t pt_rhs_cap = 0, pt_part_cap = 0, pt_out_cap = 0, pt_Xb_cap = 0, pt_state_cap = 0, pt_box_cap = 0;
-  unsigned int* dpt_counter = nullptr;  // [cap] arrival tickets (zero between launches) + 1 word: finished starts of the polish
-  size_t pt_counter_cap = 0;
-  double* dpt_split = nullptr;  // partial tiles of split row blocks (one-point latency mode of k_point_tri)
-  double *dpt_tw = nullptr, *dpt_trec = nullptr;  // linear trend in the one-point path: W^T [r | dr/dx] per point, the trend records
-  size_t pt_tw_cap = 0, pt_trec_cap = 0;
-  unsigned int* dpt_splitc = nullptr;
-  size_t pt_split_cap = 0, pt_splitc_cap = 0;
+  bogp::DevBuf<double> dpt_rhs, dpt_part, dpt_out, dpt_Xb, dpt_state, dpt_box;
+  bogp::DevBuf<unsigned int> dpt_counter;  // [cap] arrival tickets (zero between launches) + 1 word: finished starts of the polish
+  bogp::DevBuf<double> dpt_split;  // partial tiles of split row blocks (one-point latency mode of k_point_tri)
+  bogp::DevBuf<double> dpt_tw, dpt_trec;  // linear trend in the one-point path: W^T [r | dr/dx] per point, the trend records
+  bogp::DevBuf<unsigned int> dpt_splitc;
   // the likelihood's host traffic (r03): theta travels through a pinned staging block, the scalars / gradient sums come back through
   // a device-mapped pinned block that one gather kernel fills, completion read off a sequence word (bogp_api.hip: fit_readback)
-  double* hfit = nullptr;      // pinned: [0, 2048) theta staging | [2048, 2112) the 64 scalars | [2112, 2112 + 512) gradient sums | [3000] sequence word
-  double* hfit_dev = nullptr;  // its device address
+  double* hfit_dev = nullptr;  // view: hfit's device address
+  bogp::MappedBuf hfit;  // pinned: [0, 2048) theta staging | [2048, 2112) the 64 scalars | [2112, 2112 + 512) gradient sums | [3000] sequence word
   unsigned long long fit_seq = 0;
-  unsigned int* dfin_ticket = nullptr;  // k_grad_finish: which workgroup finished last
-  double* hpin = nullptr;  // pinned host buffer the finishing workgroup writes its records into (device-mapped)
-  double* hpin_dev = nullptr;
-  size_t hpin_cap = 0;
+  bogp::DevBuf<unsigned int> dfin_ticket;  // k_grad_finish: which workgroup finished last
+  bogp::MappedBuf hpin;  // pinned host buffer the finishing workgroup writes its records into (device-mapped)
   unsigned long long pt_seq = 0;  // sequence number of the last one-point call (completion word behind its record)
-  // bogp_nll_batch (bogp_batch.hip): pinned device-mapped staging (parameter rows in, records out; the sequence word sits behind
-  // hbatch_cap doubles), the slot-completion ticket, and the P workspaces of the elimination path with their BatchSlot table
-  double* hbatch = nullptr;
-  double* hbatch_dev = nullptr;
-  size_t hbatch_cap = 0;
-  unsigned int* dbatch_ticket = nullptr;
+  // bogp_nll_batch (bogp_batch.hip): pinned device-mapped staging (parameter rows in, records out; the sequence word sits in the
+  // block's last 8 doubles), the slot-completion ticket, and the P workspaces of the elimination path with their BatchSlot table
+  bogp::MappedBuf hbatch;
+  bogp::DevBuf<unsigned int> dbatch_ticket;
   unsigned long long batch_seq = 0;
-  double* dbws = nullptr;
-  size_t bws_cap = 0;
-  bogp::BatchSlot* dbslots = nullptr;
-  size_t bslots_cap = 0;
+  bogp::DevBuf<double> dbws;
+  bogp::DevBuf<bogp::BatchSlot> dbslots;
   int bws_P = 0, bws_ld = 0, bws_d = 0, bws_N = 0;
-  double* bws_rows = nullptr;  // [bws_P][bws_row] parameter rows on the device
+  double* bws_rows = nullptr;  // view into dbws: [bws_P][bws_row] parameter rows on the device
   size_t bws_row = 0;
 
   // timing of the last sweep/predict
-  std::vector<hipEvent_t> ev;
+  bogp::EventPool ev;
   double t_corr_ms = 0, t_contract_ms = 0, t_acq_ms = 0;
   int n_chunks = 0;
   bool timing_pending = false, timing_fused = false;  // event times not read back yet / of the one-launch small-N sweep
@@ -313,18 +357,39 @@ struct bogp_handle {
     if (_e != hipSuccess) FAIL(h, BOGP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
 template <typename T>
-static inline int ensure(bogp_handle* h, T** p, size_t* cap, size_t n) {
-  if (*cap >= n && *p) return BOGP_OK;
-  if (*p) HIPCHK(h, hipFree(*p));
+inline int bogp::DevBuf<T>::ensure(bogp_handle* h, size_t n) {
+  if (cap >= n && ptr) return BOGP_OK;
+  T** p = &ptr;  // (HIPCHK's message quotes its expression: the two below read as they did in the free-standing ensure(h, &ptr, &cap, n))
+  if (*p) {
+    HIPCHK(h, hipFree(*p));
+    live_note(-1, cap * sizeof(T));
+  }
   *p = nullptr;
-  *cap = 0;
+  cap = 0;
   HIPCHK(h, hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
+  cap = n;
+  live_note(1, n * sizeof(T));
   return BOGP_OK;
 }
+inline int bogp::MappedBuf::ensure(bogp_handle* h, size_t n) {
+  if (cap >= n && dev) return BOGP_OK;
+  if (ptr) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipHostFree(ptr));
+    live_note(-1, cap * sizeof(double));
+    ptr = dev = nullptr;
+    cap = 0;
+  }
+  HIPCHK(h, hipHostMalloc((void**)&ptr, n * sizeof(double), hipHostMallocMapped));
+  cap = n;
+  live_note(1, n * sizeof(double));
+  HIPCHK(h, hipHostGetDevicePointer((void**)&dev, ptr, 0));
+  memset(ptr, 0, n * sizeof(double));
+  return BOGP_OK;
+}
+// (for the two local temporaries of bogp_selftest_profile, kernels_profile.hip; the handle's buffers free themselves)
 template <typename T>
 static inline void dfree(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
 }
-

@@ -33,6 +33,9 @@ struct CorrArgs {
   int wld = 0;
   double* t_part = nullptr;      // [S][pv][Mc] slice sums of W^T r
 };
+// Leading dimension of the factor buffers for N training points: N rounded up to 64; to 128 above the elimination's limit (N > 3072), where the
+// inverse, R^-1 and the Cholesky's wide panels work on 128 x 128 tiles (kernels_chol.hip, BIG_LD)
+inline int train_ld(int N) { return N > 3072 ? ((N + 127) / 128) * 128 : ((N + 63) / 64) * 64; }
 // Chunk geometry of every candidate pass (sweep, believer, Thompson).  The training set is sliced into groups of 8 x 32 rows per producer
 // workgroup: S is a function of N only, so that the grouping of the partial sums of mu (hence every output bit) does not depend on the chunk size.
 constexpr int SWEEP_NBLK_PER_SPLIT = 8;  // (4 / 16 measured: profiles/r05_corr_split_ab.txt)

@@ -47,27 +47,15 @@ int check_common(bogp_handle* h, const char* who, int q, const int* acq_id, cons
   return BOGP_OK;
 }
 
-int ensure_counters(bogp_handle* h, size_t n) {
-  if (h->pt_counter_cap >= n && h->dpt_counter) return BOGP_OK;
-  if (h->dpt_counter) HIPCHK(h, hipFree(h->dpt_counter));
-  h->dpt_counter = nullptr;
-  h->pt_counter_cap = 0;
-  HIPCHK(h, hipMalloc((void**)&h->dpt_counter, n * sizeof(unsigned int)));
-  HIPCHK(h, hipMemsetAsync(h->dpt_counter, 0, n * sizeof(unsigned int), h->stream));
-  h->pt_counter_cap = n;
+// arrival tickets: a new block is zeroed
+int ensure_tickets(bogp_handle* h, DevBuf<unsigned int>& c, size_t n) {
+  if (c.cap >= n && c) return BOGP_OK;
+  const int e = c.ensure(h, n);
+  if (e) return e;
+  HIPCHK(h, hipMemsetAsync(c, 0, n * sizeof(unsigned int), h->stream));
   return BOGP_OK;
 }
-
-int ensure_pinned(bogp_handle* h, size_t n) {
-  if (h->hpin_cap >= n && h->hpin) return BOGP_OK;
-  if (h->hpin) HIPCHK(h, hipHostFree(h->hpin));
-  h->hpin = h->hpin_dev = nullptr;
-  h->hpin_cap = 0;
-  HIPCHK(h, hipHostMalloc((void**)&h->hpin, n * sizeof(double), hipHostMallocMapped));
-  HIPCHK(h, hipHostGetDevicePointer((void**)&h->hpin_dev, h->hpin, 0));
-  h->hpin_cap = n;
-  return BOGP_OK;
-}
+int ensure_counters(bogp_handle* h, size_t n) { return ensure_tickets(h, h->dpt_counter, n); }
 
 // queue k_point_rhs + k_point_tri for B points; the records land in `out` (device or device-mapped host memory)
 int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, const double* x_host, int B, int q, const int* acq_id,
@@ -87,8 +75,8 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   if (!eh && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
     const int Np = h->Np, nJ = (Np + 255) / 256;
     const long long Mc = ((long long)B * ncp + 63) / 64 * 64;
-    if ((e = ensure(h, &h->drT[0], &h->rT_cap[0], (size_t)Np * Mc))) return e;
-    if ((e = ensure(h, &h->dpt_part, &h->pt_part_cap, (size_t)B * (nJ + 1) * 2 * ncp))) return e;
+    if ((e = h->drT[0].ensure(h, (size_t)Np * Mc))) return e;
+    if ((e = h->dpt_part.ensure(h, (size_t)B * (nJ + 1) * 2 * ncp))) return e;
     PointRhsArgs ra;
     memset(&ra, 0, sizeof(ra));
     ra.X = h->dX; ra.theta = h->dtheta; ra.Xb = dXb; ra.N = h->N; ra.d = h->d;
@@ -110,20 +98,13 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
     HIPCHK(h, launch_point_finish_mfma(fa, ncp, B, st));
     return BOGP_OK;
   }
-  if ((e = ensure(h, &h->dpt_rhs, &h->pt_rhs_cap, (size_t)B * pl.npass * pl.Npp * pl.NC))) return e;
-  if ((e = ensure(h, &h->dpt_part, &h->pt_part_cap, (size_t)B * pl.npass * (pl.nRB + 1) * 2 * pl.NC))) return e;
+  if ((e = h->dpt_rhs.ensure(h, (size_t)B * pl.npass * pl.Npp * pl.NC))) return e;
+  if ((e = h->dpt_part.ensure(h, (size_t)B * pl.npass * (pl.nRB + 1) * 2 * pl.NC))) return e;
   const size_t nslots = (size_t)B * pl.npass * (pl.nRB + 1);
   if ((e = ensure_counters(h, (size_t)std::max(B, 64) + 1))) return e;
   if (pl.nsplit > 1) {
-    if ((e = ensure(h, &h->dpt_split, &h->pt_split_cap, nslots * pl.nsplit * pl.rb * pl.NC))) return e;
-    if (h->pt_splitc_cap < nslots || !h->dpt_splitc) {
-      if (h->dpt_splitc) HIPCHK(h, hipFree(h->dpt_splitc));
-      h->dpt_splitc = nullptr;
-      h->pt_splitc_cap = 0;
-      HIPCHK(h, hipMalloc((void**)&h->dpt_splitc, nslots * sizeof(unsigned int)));
-      HIPCHK(h, hipMemsetAsync(h->dpt_splitc, 0, nslots * sizeof(unsigned int), st));
-      h->pt_splitc_cap = nslots;
-    }
+    if ((e = h->dpt_split.ensure(h, nslots * pl.nsplit * pl.rb * pl.NC))) return e;
+    if ((e = ensure_tickets(h, h->dpt_splitc, nslots))) return e;
   }
   PointRhsArgs ra;
   memset(&ra, 0, sizeof(ra));
@@ -133,8 +114,8 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   HIPCHK(h, launch_point_rhs(h->kernel, ra, B, st));
   const double* trend_rec = nullptr;
   if (h->p > 1) {  // linear basis: (Ft^T L^-1) [r | dr/dx] and the trend's share of mu, MSE and their gradients (kernels_point.hip)
-    if ((e = ensure(h, &h->dpt_tw, &h->pt_tw_cap, (size_t)B * pl.npass * h->p * pl.NC))) return e;
-    if ((e = ensure(h, &h->dpt_trec, &h->pt_trec_cap, (size_t)B * (2 + 2 * h->d)))) return e;
+    if ((e = h->dpt_tw.ensure(h, (size_t)B * pl.npass * h->p * pl.NC))) return e;
+    if ((e = h->dpt_trec.ensure(h, (size_t)B * (2 + 2 * h->d)))) return e;
     HIPCHK(h, launch_point_trend(ra, h->dWp, h->Np, h->p, h->dbetav, h->dSinv, h->estimate_trend, h->dpt_tw, h->dpt_trec, B, st));
     trend_rec = h->dpt_trec;
   }
@@ -182,13 +163,13 @@ int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const 
   hipStream_t st = h->stream;
   const PointPlan pl = plan_of(h, B, 1, true);
   const size_t ss = polish_state_doubles(d);
-  if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
-  if ((e = ensure(h, &h->dpt_out, &h->pt_out_cap, (size_t)B * pl.rec_stride))) return e;
-  if ((e = ensure(h, &h->dpt_state, &h->pt_state_cap, (size_t)B * ss))) return e;
-  if ((e = ensure(h, &h->dpt_box, &h->pt_box_cap, (size_t)2 * d))) return e;
+  if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
+  if ((e = h->dpt_out.ensure(h, (size_t)B * pl.rec_stride))) return e;
+  if ((e = h->dpt_state.ensure(h, (size_t)B * ss))) return e;
+  if ((e = h->dpt_box.ensure(h, (size_t)2 * d))) return e;
   if ((e = ensure_counters(h, (size_t)std::max(B, 64) + 1))) return e;
-  if ((e = ensure_pinned(h, std::max<size_t>((size_t)B * (d + 2) + 16, 1024)))) return e;
-  unsigned int* dn_done = h->dpt_counter + (h->pt_counter_cap - 1);
+  if ((e = h->hpin.ensure(h, std::max<size_t>((size_t)B * (d + 2) + 16, 1024)))) return e;
+  unsigned int* dn_done = h->dpt_counter + (h->dpt_counter.cap - 1);
   // starting points clipped into the box (scipy's L-BFGS-B projects x0 the same way)
   std::vector<double> xs((size_t)B * d), box(2 * (size_t)d), st0((size_t)B * ss, 0.0);
   for (int b = 0; b < B; ++b)
@@ -204,7 +185,7 @@ int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const 
   pa.state = h->dpt_state; pa.rec = h->dpt_out; pa.Xt = h->dpt_Xb; pa.lo = h->dpt_box; pa.hi = h->dpt_box + d; pa.n_done = dn_done;
   pa.d = d; pa.q = 1; pa.rec_stride = pl.rec_stride; pa.state_stride = (int)ss; pa.max_evals = max_evals;
   pa.pgtol = pgtol; pa.factr_eps = factr * 2.220446049250313e-16; pa.first_step = 0.05 * wmin;
-  unsigned int* hdone = (unsigned int*)(h->hpin);
+  unsigned int* hdone = (unsigned int*)h->hpin.ptr;
   // every iteration = one batched evaluation of the B trial points + one optimiser step, all queued; the host looks at the
   // count of finished starts every 8 iterations (one 4-byte read-back) to stop early
   int it = 0;
@@ -261,7 +242,7 @@ int ehvi_cells_resident(bogp_handle* h, const char* who, int m, int C, const dou
   HIPCHK(h, hipSetDevice(h->device));
   ehvi_cells_forget(h);
   int e;
-  if ((e = ensure(h, &h->dehvi_cells, &h->ehvi_cells_cap, 2 * nb))) return e;
+  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are not needed past this call
@@ -281,17 +262,6 @@ void ehvi_cells_forget(bogp_handle* h) {
   h->ehvi_host_m = h->ehvi_host_C = 0;
 }
 
-void point_release(bogp_handle* h) {
-  dfree(h->dpt_rhs); dfree(h->dpt_part); dfree(h->dpt_out); dfree(h->dpt_Xb); dfree(h->dpt_state); dfree(h->dpt_box);
-  dfree(h->dpt_counter); dfree(h->dpt_split); dfree(h->dpt_splitc); dfree(h->dpt_tw); dfree(h->dpt_trec);
-  h->pt_tw_cap = h->pt_trec_cap = 0;
-  h->pt_split_cap = h->pt_splitc_cap = 0;
-  h->pt_rhs_cap = h->pt_part_cap = h->pt_out_cap = h->pt_Xb_cap = h->pt_state_cap = h->pt_box_cap = h->pt_counter_cap = 0;
-  if (h->hpin) (void)hipHostFree(h->hpin);
-  h->hpin = h->hpin_dev = nullptr;
-  h->hpin_cap = 0;
-}
-
 static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, const int* acq_id, const double* acq_par, double plugin,
                             int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq) {
   hipStream_t st = h->stream;
@@ -301,10 +271,10 @@ static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, cons
   const size_t nrec = (size_t)B * pl.rec_stride;
   int e;
   // the finishing workgroups write straight into pinned host memory: one stream synchronisation, no copy command
-  if ((e = ensure_pinned(h, std::max<size_t>(nrec + 8, 1024)))) return e;
+  if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
   const double* dXb = nullptr;
   if (B > 1 || d > BOGP_POINT_ARG_D) {
-    if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
+    if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
     HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     dXb = h->dpt_Xb;
   }
@@ -314,8 +284,8 @@ static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, cons
   if (B == 1) {
     volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
     const unsigned long long seq = ++h->pt_seq;
-    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin_dev + nrec);
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin_dev, dflag, seq))) return e;
+    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin.dev, dflag, seq))) return e;
     bool seen = false;
     for (int spin = 0; spin < 400000; ++spin) {
       if (*flag == seq) { seen = true; break; }
@@ -324,7 +294,7 @@ static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, cons
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) HIPCHK(h, hipStreamSynchronize(st));
   } else {
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin_dev))) return e;
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin.dev))) return e;
     HIPCHK(h, hipStreamSynchronize(st));
   }
   for (int b = 0; b < B; ++b) {
@@ -401,22 +371,22 @@ static int point_eval_ehvi_chunk(bogp_handle* h, const PointEhviArgs& eh0, const
   const size_t mom_stride = want_mom ? (size_t)2 * m + 2 * (size_t)m * d : 0;
   const size_t nrec = (size_t)B * (pl.rec_stride + mom_stride);
   int e;
-  if ((e = ensure_pinned(h, std::max<size_t>(nrec + 8, 1024)))) return e;
+  if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
   const double* dXb = nullptr;
   if (B > 1 || d > BOGP_POINT_ARG_D) {
-    if ((e = ensure(h, &h->dpt_Xb, &h->pt_Xb_cap, (size_t)B * d))) return e;
+    if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
     HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     dXb = h->dpt_Xb;
   }
   PointEhviArgs eh = eh0;
-  eh.mom = want_mom ? h->hpin_dev + (size_t)B * pl.rec_stride : nullptr;
+  eh.mom = want_mom ? h->hpin.dev + (size_t)B * pl.rec_stride : nullptr;
   eh.mom_stride = (int)mom_stride;
   const int one_id = BOGP_ACQ_EI;  // (sizes the record like one criterion; the id itself is not evaluated)
   if (B == 1) {  // the BFGS loop's call: completion polled off the sequence word behind the records (point_eval_chunk)
     volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
     const unsigned long long seq = ++h->pt_seq;
-    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin_dev + nrec);
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin_dev, dflag, seq, &eh))) return e;
+    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin.dev, dflag, seq, &eh))) return e;
     bool seen = false;
     for (int spin = 0; spin < 400000; ++spin) {
       if (*flag == seq) { seen = true; break; }
@@ -425,7 +395,7 @@ static int point_eval_ehvi_chunk(bogp_handle* h, const PointEhviArgs& eh0, const
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) HIPCHK(h, hipStreamSynchronize(st));
   } else {
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin_dev, nullptr, 0, &eh))) return e;
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin.dev, nullptr, 0, &eh))) return e;
     HIPCHK(h, hipStreamSynchronize(st));
   }
   for (int b = 0; b < B; ++b) {

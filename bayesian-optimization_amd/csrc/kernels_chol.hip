@@ -502,7 +502,7 @@ namespace {
 constexpr int MB = 128;        // tile edge
 // r02-r05: 6144 (the staged tile core: 4096 5.1 vs 4.8 ms, 6144 9.9 vs 10.2, 8192 17.6 vs 20.2).  With the LDS-free core (mm128_tile_direct) the 128-tile products win wherever
 // the general path runs at all (profiles/r06_mm128_direct_ab.txt: llf + gradient 3.52 -> 3.40 ms at N = 3584, 4.51 -> 4.00 at 4096, 6.86 -> 5.83 at 5120, 9.07 -> 7.64 at 6016), so
-// every training set above the elimination's limit (N > 3072: bogp_set_train rounds the leading dimension to 128 there) takes them.
+// every training set above the elimination's limit (N > 3072: train_ld rounds the leading dimension to 128 there) takes them.
 constexpr int BIG_LD = 3200;
 
 struct MmTile {

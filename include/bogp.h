@@ -677,6 +677,11 @@ int bogp_last_bound32(bogp_handle* h, int64_t* rows, int64_t* kept, int* fallbac
  * sums r . gamma and w . r, their margins and the stage's flag.  Arrays of `cap` >= *rows entries, any of them NULL.                 */
 int bogp_debug_bound32(bogp_handle* h, int64_t cap, double* mu32, double* e_mu, double* wd32, double* e_w, unsigned char* flags, int64_t* rows);
 
+/* Debug count of what the handles of this process hold on the device right now: live device and mapped pinned allocations, their
+ * bytes, live events.  A handle owns every buffer and event through a member that frees it (csrc/bogp_handle.h), so the counts
+ * return to their earlier values after bogp_destroy (tests/test_gpu_handle_lifetime.py).  No handle; any output may be NULL.        */
+void bogp_debug_live(int64_t* allocations, int64_t* bytes, int64_t* events);
+
 /* Host evaluations of the FP32 stage's two rules, no device and no handle (tests/test_bound32_host.py): the margins of a row whose
  * scaled point has squared norm na (+inf where the stage cannot bound the row), and the largest bogp_acq_upper_bound over y_hat in
  * [y_hat - e, y_hat + e] (+inf where the interval holds a switch point of the criterion, a NaN or an infinity).                     */
