@@ -6,6 +6,7 @@
 
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_mfma.h"  // d4, mfma16, the drains and their rules
 
 namespace bogp {
 
@@ -13,16 +14,6 @@ namespace {
 
 constexpr int CB = 64;           // block size
 constexpr int CPITCH = 64 + 16;  // LDS pitch (doubles) of a k-major tile: conflict-free rotated A-fragment reads
-
-// v_mfma_f64_16x16x4_f64 accumulating in place in ARCHITECTURAL VGPRs: 64-cycle issue = the FP64 matrix peak (with AGPR
-// accumulators the same instruction takes 130 cycles, tools/probes/ubench_mfma16.hip); one A and one B register per 2048 flop.
-// Lanes: A = 16 k + i, B = 16 k + j, D[i][j] in lane 16 (i % 4) + j, component i / 4.
-typedef double d4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void mfma16(double a, double b, d4& c) {
-  asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// 16 passes: nothing may read the last results before they have left the pipe
-#define BOGP_CHOL_DRAIN() asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory")
 
 // 1/sqrt(x): hardware estimate + ONE third-order (Halley) step, e = 1 - x y^2, y' = y (1 + e/2 + 3 e^2/8): five dependent
 // operations after v_rsq_f64 instead of the eight of two Newton steps.  A dependent FP64 operation costs ~26 cycles on
@@ -84,8 +75,7 @@ __device__ __forceinline__ void mma_64(const double* lds, const double (&bv)[16]
   d4 c[4];
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) c[mi] = (d4){acc[mi][0], acc[mi][1], acc[mi][2], acc[mi][3]};
-  // The MFMAs are inline asm, invisible to the compiler's hazard recogniser: the VALU moves that build c (and whatever
-  // register they recycle) must retire before the first MFMA reads c as SrcC -- these wait states are placed by hand.
+  // the VALU moves that build c (and whatever register they recycle) must retire before the first MFMA reads c as SrcC (bogp_mfma.h, 4.)
   asm volatile("s_nop 7\n\ts_nop 7" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
 #pragma unroll
   for (int ks = 0; ks < 16; ++ks) {
@@ -94,9 +84,7 @@ __device__ __forceinline__ void mma_64(const double* lds, const double (&bv)[16]
     for (int mi = 0; mi < 4; ++mi)
       if (!TRI || ks < 4 * (mi + 1)) mfma16(trow[aoff + 16 * mi], bv[ks], c[mi]);
   }
-  // the drain names the accumulators as in/out operands so that no read of them can be scheduled above it
-  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
-               : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
+  mfma16_drain(c[0], c[1], c[2], c[3]);
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll

@@ -33,7 +33,6 @@
   }
   const int nb0 = blockIdx.y * a.nblk_per_split * 32;
   const int nb1 = min(a.Np, nb0 + a.nblk_per_split * 32);
-  typedef double d4t __attribute__((ext_vector_type(4)));
   double mu[4] = {0.0, 0.0, 0.0, 0.0}, wd[4] = {0.0, 0.0, 0.0, 0.0};
   // (r06, from k_contract16d: every global address of the loop is a wave-uniform base + a lane-constant 32-bit offset, kept opaque inside the loop so that
   // hipcc selects the `v_offset, s[base]` form -- hoisted, each access cost a v_lshl_add_u64 on the FP64 pipe that the MFMAs and the profile's arithmetic share)
@@ -51,13 +50,13 @@
 #endif
   for (int n0 = nb0 + 16 * g; n0 < nb1; n0 += 64) {
 #define BOGP_OPQ(o_) asm("" : "+v"(o_))  /* (beside EVERY access: the zero-extension must sit in the access's own basic block to be matched) */
-    d4t acc[4];
+    d4 acc[4];
     // a_m . b_n over the dimensions, four at a time
     {
       const char* __restrict__ apb = xthB + (size_t)n0 * sizeof(double);
       const double* bp = xs + lk * 64 + li;
 #pragma unroll
-      for (int t = 0; t < 4; ++t) acc[t] = (d4t){0.0, 0.0, 0.0, 0.0};
+      for (int t = 0; t < 4; ++t) acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
       constexpr int KB = 8;  // A fragments (128-byte runs of XthT: L2 round trips) requested together: 5.5 -> 5.1 ms at C3, 17.5 -> 14.3 ms at C5
       for (int ks0 = 0; ks0 < KS; ks0 += KB) {
         double av[KB];
@@ -72,10 +71,10 @@
           if (ks0 + u < KS) {
             const int ks = ks0 + u;
             const double b0 = bp[ks * 256], b1 = bp[ks * 256 + 16], b2 = bp[ks * 256 + 32], b3 = bp[ks * 256 + 48];
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[0]) : "v"(av[u]), "v"(b0));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[1]) : "v"(av[u]), "v"(b1));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[2]) : "v"(av[u]), "v"(b2));
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[3]) : "v"(av[u]), "v"(b3));
+            mfma16_pinned(av[u], b0, acc[0]);
+            mfma16_pinned(av[u], b1, acc[1]);
+            mfma16_pinned(av[u], b2, acc[2]);
+            mfma16_pinned(av[u], b3, acc[3]);
           }
         }
       }
@@ -87,9 +86,9 @@
       BOGP_OPQ(offN);
       nbv[c] = *reinterpret_cast<const double*>(xnB + (size_t)(n0 + 4 * c) * sizeof(double) + offN);
     }
-    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");  // (shorter than mfma16_drain(): bogp_mfma.h, the sites with their own text)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(acc[t]));
+    for (int t = 0; t < 4; ++t) mfma16_fence(acc[t]);
     double s2[4][4];
     bool near = false;
 #pragma unroll

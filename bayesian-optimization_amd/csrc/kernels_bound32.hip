@@ -131,7 +131,8 @@ __global__ __launch_bounds__(256) void k_bound32_sums(Bound32Args a) {
         if (ks0 + u < KS) {
           const int ks = ks0 + u;
           const float b0 = bp[ks * 4 * XS_LD], b1 = bp[ks * 4 * XS_LD + 16], b2 = bp[ks * 4 * XS_LD + 32], b3 = bp[ks * 4 * XS_LD + 48];
-          // (inline asm like every matrix instruction of the library: the accumulators stay in VGPRs; the drain below is by hand)
+          // (inline asm like every matrix instruction of the library: the accumulators stay in VGPRs; the drain below is by hand -- the rules are in
+          // bogp_mfma.h, whose FP64 wrappers do not fit this FP32 chain and its shorter drain)
           asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[0]) : "v"(av[u]), "v"(b0));
           asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[1]) : "v"(av[u]), "v"(b1));
           asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[2]) : "v"(av[u]), "v"(b2));

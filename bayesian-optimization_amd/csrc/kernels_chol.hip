@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void k_chol_step(double* __restrict__ A, int l
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int t = 0; t < 4; ++t) bv[4 * mi + t] = xi[mi][t];
-  // (register moves feeding inline-asm MFMAs: the hazard recogniser does not see the consumer)
+  // (register moves feeding inline-asm MFMAs: bogp_mfma.h, 4.)
   asm volatile("s_nop 7\n\ts_nop 7"
                : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3]), "+v"(bv[4]), "+v"(bv[5]), "+v"(bv[6]), "+v"(bv[7]), "+v"(bv[8]),
                  "+v"(bv[9]), "+v"(bv[10]), "+v"(bv[11]), "+v"(bv[12]), "+v"(bv[13]), "+v"(bv[14]), "+v"(bv[15]));
@@ -605,11 +605,11 @@ __device__ __forceinline__ void mm128_tile_direct(const MmTile& t) {
     }
 #undef BOGP_MMD_KPAIR
 #undef BOGP_MMD_LOADS
-    BOGP_CHOL_DRAIN();
+    mfma16_drain();
 #pragma unroll
     for (int ci = 0; ci < 4; ++ci)
 #pragma unroll
-      for (int rj = 0; rj < 4; ++rj) asm volatile("" : "+v"(acc[ci][rj]));  // the stores' reads of the accumulators stay behind the drain
+      for (int rj = 0; rj < 4; ++rj) mfma16_fence(acc[ci][rj]);  // the stores' reads of the accumulators stay behind the drain
   }
   // (out = alpha * acc: with beta the accumulators started from alpha * out, and alpha^2 = 1)
 #pragma unroll

@@ -757,12 +757,13 @@ __global__ __launch_bounds__(256, 2) void k_elim_updateS_b(const BatchSlot* __re
           mfma16(a_, bv[sl_][1][h_], acc[1][ib_][mi_]);                                                                \
         }                                                                                                              \
   } while (0)
-#define BOGP_ES_ALL_ACC                                                                                                                    \
+// (sixteen accumulators named by one drain: more than bogp_mfma.h's mfma16_drain() takes, so the operand list and the asm stay here)
+#define BOGP_ES_ALL_ACC                                                                                                             \
   "+v"(acc[0][0][0]), "+v"(acc[0][0][1]), "+v"(acc[0][0][2]), "+v"(acc[0][0][3]), "+v"(acc[0][1][0]), "+v"(acc[0][1][1]), "+v"(acc[0][1][2]), \
       "+v"(acc[0][1][3]), "+v"(acc[1][0][0]), "+v"(acc[1][0][1]), "+v"(acc[1][0][2]), "+v"(acc[1][0][3]), "+v"(acc[1][1][0]), "+v"(acc[1][1][1]), \
       "+v"(acc[1][1][2]), "+v"(acc[1][1][3])
   BOGP_ES_LOADS(0, k, 0);
-  // the VALU moves that built the accumulators must retire before the first MFMA reads them as SrcC (inline-asm MFMAs: wait states by hand)
+  // the VALU moves that built the accumulators must retire before the first MFMA reads them as SrcC (bogp_mfma.h, 4.)
   asm volatile("s_nop 7\n\ts_nop 7" : BOGP_ES_ALL_ACC);
   for (int sidx = k; sidx <= klast; ++sidx) {
     bool restart = false;
@@ -771,7 +772,7 @@ __global__ __launch_bounds__(256, 2) void k_elim_updateS_b(const BatchSlot* __re
 #pragma unroll
       for (int ib = 0; ib < 2; ++ib) restart = restart || sidx == first[ia][ib];
     if (restart) {  // (uniform) T <- 0 - X_i X_j^T from this step on: behind the drain of what the block gathered so far, in front of the step's first MFMA
-      asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : BOGP_ES_ALL_ACC);
+      asm volatile(BOGP_MFMA16_NOPS : BOGP_ES_ALL_ACC);
 #pragma unroll
       for (int ia = 0; ia < 2; ++ia)
 #pragma unroll
@@ -792,7 +793,7 @@ __global__ __launch_bounds__(256, 2) void k_elim_updateS_b(const BatchSlot* __re
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : BOGP_ES_ALL_ACC);
+  asm volatile(BOGP_MFMA16_NOPS : BOGP_ES_ALL_ACC);
 #undef BOGP_ES_LOADS
 #undef BOGP_ES_MFMAS
 #undef BOGP_ES_AVAL

@@ -11,6 +11,7 @@
 //   k_transpose_pad   out (ldo x cols_out, zero padded) = in^T for the column side of those products.
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_mfma.h"
 
 namespace bogp {
 
@@ -18,11 +19,6 @@ namespace {
 constexpr int GT = 64;        // tile edge
 constexpr int GK = 32;        // k-block
 constexpr int GP = 64 + 16;   // LDS pitch in doubles
-
-typedef double d4g __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void mfma16g(double a, double b, d4g& c) {
-  asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
 
 // tile[kk][x] = op(M)(x0 + x, k0 + kk), element (x, kk) of op(M) at M[x * sx + kk * sk]; zero outside (nx, nk).
 // The thread -> element map follows the unit stride so that either orientation loads coalesced.
@@ -55,10 +51,10 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i0 = blockIdx.x * GT, j0 = blockIdx.y * GT;
   const int lk = lane >> 4, li = lane & 15;
-  d4g c[4];
+  d4 c[4];
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi) c[mi] = (d4g){0.0, 0.0, 0.0, 0.0};
-  // the MFMAs are inline asm, invisible to the hazard recogniser: the moves that zero c must retire before the first one
+  for (int mi = 0; mi < 4; ++mi) c[mi] = (d4){0.0, 0.0, 0.0, 0.0};
+  // the moves that zero c must retire before the first MFMA (bogp_mfma.h, 4.)
   asm volatile("s_nop 7\n\ts_nop 7" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
   // op(A) lower triangular (tri = 1): columns k > row are zero -> stop at the tile's last row; upper (tri = 2): start at its first
   int kbeg = a.tri == 2 ? (i0 / GK) * GK : 0;
@@ -79,10 +75,10 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmArgs a) {
     for (int ks = 0; ks < GK / 4; ++ks) {
       const double rv = As[(4 * ks + lk) * GP + 16 * w + li];  // MFMA B operand: lane (k, row)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) mfma16g(Bs[(4 * ks + lk) * GP + 16 * mi + li], rv, c[mi]);  // A operand: lane (k, column)
+      for (int mi = 0; mi < 4; ++mi) mfma16(Bs[(4 * ks + lk) * GP + 16 * mi + li], rv, c[mi]);  // A operand: lane (k, column)
     }
   }
-  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]));
+  mfma16_drain(c[0], c[1], c[2], c[3]);
   if (nz > 1) {
     // Split K (products with a small C and a long k, e.g. the p x p Gram matrices of the trend basis over k = N): every slice
     // parks its partial tile in scratch (write-through stores), the LAST slice to arrive at the tile's ticket adds all nz

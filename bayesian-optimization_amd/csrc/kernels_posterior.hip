@@ -30,6 +30,7 @@
 
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_mfma.h"
 
 namespace bogp {
 
@@ -81,10 +82,9 @@ __global__ __launch_bounds__(256) void k_corr_chunk(const double* __restrict__ X
   const int nb1 = min(a.Np, nb0 + a.nblk_per_split * 32);
   double mu = 0.0, wd = 0.0;
   constexpr int NTT = PV > 0 ? PV / 16 : 1;
-  typedef double d4t __attribute__((ext_vector_type(4)));
-  d4t tacc[NTT];
+  d4 tacc[NTT];
 #pragma unroll
-  for (int c = 0; c < NTT; ++c) tacc[c] = (d4t){0.0, 0.0, 0.0, 0.0};
+  for (int c = 0; c < NTT; ++c) tacc[c] = (d4){0.0, 0.0, 0.0, 0.0};
   double* rtile = smem + max(64 * d, 512);  // PV > 0: [32][64] the block of r being contracted (behind the candidate tile / the reduction arrays)
   const int lk = m >> 4, li = m & 15;
   for (int nb = nb0; nb < nb1; nb += 32) {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_corr_chunk(const double* __restrict__ X
 #pragma unroll
         for (int t = 0; t < NTT; ++t) {
           const double bv = wr[16 * t];
-          asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(tacc[t]) : "v"(av), "v"(bv));
+          mfma16(av, bv, tacc[t]);
         }
       }
       __syncthreads();  // the block is overwritten by the next trip
@@ -139,9 +139,9 @@ __global__ __launch_bounds__(256) void k_corr_chunk(const double* __restrict__ X
   }
   if (PV > 0) {
     // the trend tiles: D[i][j] sits in lane 16 (i % 4) + j, component i / 4 (i = candidate in the fragment, j = column in the tile)
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+    mfma16_drain();
 #pragma unroll
-    for (int t = 0; t < NTT; ++t) asm volatile("" : "+v"(tacc[t]));
+    for (int t = 0; t < NTT; ++t) mfma16_fence(tacc[t]);
 #pragma unroll
     for (int t = 0; t < NTT; ++t)
 #pragma unroll
@@ -196,8 +196,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // ---------------------------------------------------------------------------------------------------
 constexpr int MR = 4;                // 16-row fragments per wave  (64 candidates)
 constexpr int NWJ = 4;               // waves per workgroup (along j)
-// NR = 16-column fragments per wave (template parameter): NR = 4 -> 256 columns per workgroup, 128 accumulator
-// VGPRs, one workgroup per CU (512-register budget); NR = 2 -> 128 columns, two workgroups per CU.
+// NR = 16-column fragments per wave (template parameter, 4 in every instantiation): 256 columns per workgroup, 128 accumulator VGPRs.
+// (NR = 2 -- 128-column groups, three workgroups per CU -- lost in r01, was never the default and went with its switch in r06.)
 constexpr int KB = 32;               // training points per staged block
 constexpr int PITCH = 64 + 16;       // LDS row pitch in doubles: 640 B == 128 (mod 256) -> conflict-free A reads
 
@@ -208,49 +208,36 @@ constexpr int PITCH = 64 + 16;       // LDS row pitch in doubles: 640 B == 128 (
 // ---------------------------------------------------------------------------------------------------
 // Kernel B': the same contraction on v_mfma_f64_16x16x4_f64.
 //
-// The first probe of this instruction (builtin, accumulators where the compiler put them: AGPRs) measured 130-150
-// cycles = half the FP64 rate, which is why kernel B was built on the 4x4x4 form.  With the accumulator tied in place in
-// ARCHITECTURAL VGPRs it issues every 64.0 cycles = 77.5 TF/s, at 1-4 waves per SIMD (tools/probes/ubench_mfma16.hip,
-// profiles/r01_ubench_mfma16.txt; AGPR accumulators: 130 cycles) -- and it needs ONE A register and ONE B register per
-// 2048 flop where the 4x4x4 form needs four rotated A registers: a quarter of the LDS reads, no rotation, a quarter
-// of the MFMA issue slots.  Lane layout (tools/probes/probe_mfma_layout.hip): A lane = 16 k + i, B lane = 16 k + j (the SAME
-// order k_pack_V already produces), D[i][j] in lane 16 (i % 4) + j, register i / 4.
-// Tiling, staging, guards and the epilogue's summation order are those of kernel B.
+// The first probe of this instruction (builtin, AGPR accumulators) measured half the FP64 rate, which is why kernel B was built on
+// the 4x4x4 form; as inline asm with the accumulator in architectural VGPRs it runs at the peak, at 1-4 waves per SIMD (bogp_mfma.h, 1.)
+// -- and it needs ONE A register and ONE B register per 2048 flop where the 4x4x4 form needs four rotated A registers: a quarter of
+// the LDS reads, no rotation, a quarter of the MFMA issue slots.  Lane layout: bogp_mfma.h (the B order is the one k_pack_V already
+// produces).
+// Tiling, staging, guards and the epilogue's summation order are those of kernel B.  (The wrapper, the drain and their rules: bogp_mfma.h.)
+// (The stamped build of this kernel that produced the MFMA-idle attribution of profiles/r06_contract_att.txt, and the removal experiments of the
+// same file, went when kernel B'' below became the default; they are in git 6cdd2df.)
 // ---------------------------------------------------------------------------------------------------
-typedef double d4 __attribute__((ext_vector_type(4)));
-#ifdef CONTRACT_TRACE
-// (profiling builds only, `make EXTRA=-DCONTRACT_TRACE`: shader-clock stamps of every wave of every workgroup of k_contract16<4>, parked in LDS and
-// written out at the end -- tools/contract_trace.py turns them into the MFMA-idle attribution of profiles/r06_contract_att.txt.  This image has
-// no thread-trace decoder and the driver offers no PC sampling (same file), so the kernel keeps its own time.  The MFMAs are volatile here so
-// that they stay on their side of a stamp.)
-constexpr int TR_BLK = 64;                // blocks with stamps (N <= 2048)
-constexpr int TR_NST = 8 + 8 * TR_BLK;    // words per wave: 8 header + 8 per block
-__device__ __forceinline__ unsigned long long tr_now() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-  return t;
-}
-#define BOGP_TR(p, i) ((p)[(i)] = tr_now())
-#define BOGP_TR_PARAM , unsigned long long* trb
-#define BOGP_TR_ARG(x) , (x)
-__device__ __forceinline__ void mfma16_acc(double a, double b, d4& c) {
-  asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-#else
-#define BOGP_TR(p, i) ((void)0)
-#define BOGP_TR_PARAM
-#define BOGP_TR_ARG(x)
-__device__ __forceinline__ void mfma16_acc(double a, double b, d4& c) {
-  asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
+
+// The epilogue idiom of both contraction kernels: the operand-less drain, then a fence on every accumulator (bogp_mfma.h, 3.).
+// (BOGP_LINT_NO_DRAIN / BOGP_LINT_NO_FENCE: negative controls of tests/test_isa_lint.py -- builds WITHOUT the drain / the fences must be
+// flagged by the ISA lint; never defined in the product build)
+template <int NR>
+__device__ __forceinline__ void contract_drain(d4 (&acc)[MR][NR]) {
+#ifndef BOGP_LINT_NO_DRAIN
+  mfma16_drain();
 #endif
-// 16 passes: the result of the last MFMA must not be read by the VALU before it has left the pipe
-#define BOGP_MFMA16_DRAIN() asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory")
+#ifndef BOGP_LINT_NO_FENCE
+#pragma unroll
+  for (int mi = 0; mi < MR; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NR; ++ni) mfma16_fence(acc[mi][ni]);
+#endif
+}
 
 template <int NR, bool GUARDED>
 __device__ __forceinline__ void contract_block16(const double* __restrict__ tile, const double2* __restrict__ vp,
                                                  const size_t (&boff)[NR], const int (&jt)[NR], int aoff, int kb, int kp_last,
-                                                 double2 (&bq)[4][NR], d4 (&acc)[MR][NR] BOGP_TR_PARAM) {
+                                                 double2 (&bq)[4][NR], d4 (&acc)[MR][NR]) {
   // A fragments are read one k-step AHEAD of the MFMAs that use them (two register sets): with only four LDS reads per
   // sixteen MFMAs their latency would otherwise sit in front of every k-step
   double af[2][MR];
@@ -260,13 +247,8 @@ __device__ __forceinline__ void contract_block16(const double* __restrict__ tile
   for (int s = 0; s < 4; ++s) {
     const int kp = kb * 4 + s;
     const int kb16 = kp >> 1;
-    if (s > 0) BOGP_TR(trb, s);
     {  // B fragments are requested TWO k-pairs ahead (four slots = the four k-pairs of a block; clamped at the end)
-#ifdef CONTRACT_AB_FIXB  // every B fragment from the tile's first k-pair (L2 / L1-hot)
-      const int kpn = min(0, kp_last);
-#else
       const int kpn = min(kp + 2, kp_last);
-#endif
 #pragma unroll
       for (int ni = 0; ni < NR; ++ni) bq[(s + 2) & 3][ni] = vp[boff[ni] + (size_t)kpn * 64];
     }
@@ -283,12 +265,11 @@ __device__ __forceinline__ void contract_block16(const double* __restrict__ tile
         if (!GUARDED || kb16 <= jt[ni]) {
           const double bv = h == 0 ? bq[s][ni].x : bq[s][ni].y;
 #pragma unroll
-          for (int mi = 0; mi < MR; ++mi) mfma16_acc(af[sub & 1][mi], bv, acc[mi][ni]);
+          for (int mi = 0; mi < MR; ++mi) mfma16(af[sub & 1][mi], bv, acc[mi][ni]);
         }
       }
     }
   }
-  BOGP_TR(trb, 4);
 }
 
 // NCP != 0 (16 / 32 / 64): the batched one-point path (kernels_point.hip, k_point_rhs_T).  The 64 "candidates" of a workgroup are
@@ -298,31 +279,13 @@ __device__ __forceinline__ void contract_block16(const double* __restrict__ tile
 // differs: the first row of every NCP-row group (fragment head, register 0, lane quarter 0) is broadcast to the other quarters
 // and multiplies instead of the square; the sums land as the row-block records k_point_finish reads.
 template <int NR, int NCP = 0>
-#ifdef CONTRACT_TRACE
-__global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArgs a, unsigned long long* trace_out) {
-#else
-__global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArgs a) {
-#endif
+__global__ __launch_bounds__(256, 2) void k_contract16(ContractArgs a) {
   constexpr int JT16 = NWJ * NR;
   __shared__ __attribute__((aligned(16))) double lds[2 * KB * PITCH];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef CONTRACT_TRACE
-  __shared__ unsigned long long trc_all[NWJ][TR_NST];
-  unsigned long long* trc = trc_all[w];
-  {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trc[0] = (unsigned long long)hwid | ((unsigned long long)xcc << 32);
-  }
-  BOGP_TR(trc, 1);
-#define BOGP_TRB(kb_) ((kb_) < TR_BLK ? trc + 8 + 8 * (kb_) : trc + 8)
-#else
-#define BOGP_TRB(kb_) 0
-#endif
   const int nMt = a.nMt;
   // Column-group-major order, heaviest group first: concurrent workgroups then walk the SAME 256-column panel of V, which
   // stays hot in every XCD's L2 (the B fragments feed the MFMAs straight from global loads).  Measured alternative (r02,
@@ -334,11 +297,7 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
   if (a.live && mc0 >= *a.live) return;  // pruned sweep: the live row count is on the device, tiles past it have nothing to do
   const int NJ16 = a.NJ16, NKP = a.NKP;
   const int kmax16 = min((jg + 1) * JT16, NJ16);
-#ifdef CONTRACT_AB_NOZONE  // the 256-row diagonal zone is skipped (column group 0 then runs ONE block): what the zone costs = product - this
-  const int nkb = max(jg * (JT16 / 2), 1);
-#else
   const int nkb = kmax16 >> 1;
-#endif
   const int nkb_full = jg * (JT16 / 2);
   const int kp_last = 2 * kmax16 - 1;
 
@@ -371,7 +330,7 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
   double2 sa0, sa1, sa2, sa3, sb0, sb1, sb2, sb3;
 #define BOGP_STAGE_LOAD(S, kb_)                                                                      \
   do {                                                                                               \
-    const double* p_ = rbase + (size_t)(BOGP_STAGE_ROW(kb_)*KB + srow) * Mc;                                       \
+    const double* p_ = rbase + (size_t)((kb_)*KB + srow) * Mc;                                       \
     S##0 = *reinterpret_cast<const double2*>(p_);                                                    \
     S##1 = *reinterpret_cast<const double2*>(p_ + 8 * Mc);                                           \
     S##2 = *reinterpret_cast<const double2*>(p_ + 16 * Mc);                                          \
@@ -386,22 +345,6 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
     *reinterpret_cast<double2*>(q_ + 24 * PITCH) = S##3;                                             \
   } while (0)
 
-// (removal experiments of r06, profiles/r06_contract_att.txt: -DCONTRACT_AB_NOBAR drops the per-block barrier, -DCONTRACT_AB_NOSTS the stage
-// stores -- both give WRONG sums and exist only to price the two phases; never defined in the product build)
-#ifdef CONTRACT_AB_NOBAR
-#define BOGP_LOOP_BARRIER() asm volatile("" ::: "memory")
-#else
-#define BOGP_LOOP_BARRIER() __syncthreads()
-#endif
-#ifdef CONTRACT_AB_NOSTS
-#undef BOGP_STAGE_STORE
-#define BOGP_STAGE_STORE(S, buf_) asm volatile("" :: "v"((S##0).x), "v"((S##1).x), "v"((S##2).x), "v"((S##3).x))
-#endif
-#ifdef CONTRACT_AB_NOSTL  // every stage load reads tile 0 (L2-hot): no HBM latency behind the stage stores
-#define BOGP_STAGE_ROW(kb_) 0
-#else
-#define BOGP_STAGE_ROW(kb_) (kb_)
-#endif
   const double2* __restrict__ vp = a.Vp + lane;
   double2 bq[4][NR];
 #pragma unroll
@@ -417,57 +360,33 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
   BOGP_STAGE_LOAD(sa, 0);
   BOGP_STAGE_STORE(sa, 0);
   BOGP_STAGE_LOAD(sa, min(1, nkb - 1));  // tile 1 -> set A (stored at the end of block 0)
-  BOGP_TR(trc, 2);
 
   // Two loops, one body each (r06): the full blocks run WITHOUT the per-tile guards -- as one code path with a run-time guard the compiler put a
   // compare / select / branch chain in front of every four MFMAs of the full blocks too and moved three of the four tile groups out of line
   // (six taken branches a k-step); an if / else of the two bodies inside ONE loop made the register allocator shuffle the 128 accumulators
   // (734 spills).  nkb_full = 8 jg is even, so the zone starts on buffer 0.
-#define BOGP_BLOCK_PAIR(G)                                                                                                    \
-  do {                                                                                                                        \
-    BOGP_LOOP_BARRIER(); /* tile kb is in lds[0]; every wave is done with lds[1] */                                           \
-    BOGP_TR(BOGP_TRB(kb), 0);                                                                                                 \
-    BOGP_STAGE_LOAD(sb, min(kb + 2, nkb - 1));                                                                                \
-    contract_block16<NR, G>(&lds[0], vp, boff, jt, aoff, kb, kp_last, bq, acc BOGP_TR_ARG(BOGP_TRB(kb)));                     \
-    BOGP_STAGE_STORE(sa, 1); /* tile kb + 1 */                                                                                \
-    BOGP_TR(BOGP_TRB(kb), 5);                                                                                                 \
-    if (kb + 1 >= nkb) break;                                                                                                 \
-    BOGP_LOOP_BARRIER(); /* tile kb + 1 is in lds[1]; every wave is done with lds[0] */                                       \
-    BOGP_TR(BOGP_TRB(kb + 1), 0);                                                                                             \
-    BOGP_STAGE_LOAD(sa, min(kb + 3, nkb - 1));                                                                                \
-    contract_block16<NR, G>(&lds[KB * PITCH], vp, boff, jt, aoff, kb + 1, kp_last, bq, acc BOGP_TR_ARG(BOGP_TRB(kb + 1)));    \
-    BOGP_STAGE_STORE(sb, 0); /* tile kb + 2 */                                                                                \
-    BOGP_TR(BOGP_TRB(kb + 1), 5);                                                                                             \
+#define BOGP_BLOCK_PAIR(G)                                                                           \
+  do {                                                                                               \
+    __syncthreads(); /* tile kb is in lds[0]; every wave is done with lds[1] */                      \
+    BOGP_STAGE_LOAD(sb, min(kb + 2, nkb - 1));                                                       \
+    contract_block16<NR, G>(&lds[0], vp, boff, jt, aoff, kb, kp_last, bq, acc);                      \
+    BOGP_STAGE_STORE(sa, 1); /* tile kb + 1 */                                                       \
+    if (kb + 1 >= nkb) break;                                                                        \
+    __syncthreads(); /* tile kb + 1 is in lds[1]; every wave is done with lds[0] */                  \
+    BOGP_STAGE_LOAD(sa, min(kb + 3, nkb - 1));                                                       \
+    contract_block16<NR, G>(&lds[KB * PITCH], vp, boff, jt, aoff, kb + 1, kp_last, bq, acc);         \
+    BOGP_STAGE_STORE(sb, 0); /* tile kb + 2 */                                                       \
   } while (0)
   int kb = 0;
   for (; kb < nkb_full; kb += 2) BOGP_BLOCK_PAIR(false);
   for (; kb < nkb; kb += 2) BOGP_BLOCK_PAIR(true);
 #undef BOGP_BLOCK_PAIR
-  BOGP_TR(trc, 3);
 #undef BOGP_STAGE_LOAD
 #undef BOGP_STAGE_STORE
-#undef BOGP_LOOP_BARRIER
 
   // ---- epilogue: D[i][j] sits in lane 16 (i % 4) + j, register i / 4 ---------------------------------
-  // (BOGP_LINT_NO_DRAIN / BOGP_LINT_NO_FENCE: negative controls of tests/test_isa_lint.py -- builds WITHOUT the drain / the fences must
-  // be flagged by the ISA lint; never defined in the product build)
-#ifndef BOGP_LINT_NO_DRAIN
-  BOGP_MFMA16_DRAIN();
-#endif
-  // (the drain has no register operands: an empty volatile asm per accumulator behind it keeps the epilogue's reads from being
-  // scheduled above it -- the MFMAs are inline asm whose results look ready at once to the compiler; kernels_small.hip)
-#ifndef BOGP_LINT_NO_FENCE
-#pragma unroll
-  for (int mi = 0; mi < MR; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NR; ++ni) asm volatile("" : "+v"(acc[mi][ni]));
-#endif
+  contract_drain(acc);
   __syncthreads();
-  BOGP_TR(trc, 4);
-#ifdef CONTRACT_AB_NOEPI  // no reduction: one accumulator word per thread keeps the MFMAs alive
-  if (acc[0][0][0] == 12345.678) a.ss_part[tid] = acc[1][1][1] + acc[2][2][2] + acc[3][3][3];
-  return;
-#endif
   // red[slot][wave][row] with a row pitch of 65 doubles: the writes (lanes = 4 rows x 16 slots) fall on (4 slot + row)
   // mod 32 = every bank pair twice, the reads (lanes = 64 consecutive rows) are conflict free.  (The first layout,
   // [wave][row][slot], made every read a 64-way bank conflict: 13.7k cycles of epilogue per workgroup.)
@@ -505,7 +424,6 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
       }
   }
   __syncthreads();
-  BOGP_TR(trc, 5);
   {  // every thread adds the 16 slots of one (wave, row) in a fixed order, then 64 threads add the four waves
     double s = 0.0;
 #pragma unroll
@@ -524,15 +442,6 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
       if (b < a.cross_B) a.ss_part[((size_t)b * (a.nJ + 1) + 1 + jg) * (2 * NCP) + c] = tot;
     }
   }
-#ifdef CONTRACT_TRACE
-  BOGP_TR(trc, 6);
-  __syncthreads();
-  if (trace_out) {
-    unsigned long long* dst = trace_out + (size_t)blockIdx.x * (NWJ * TR_NST);
-    const unsigned long long* src = &trc_all[0][0];
-    for (int i = tid; i < NWJ * TR_NST; i += 256) dst[i] = src[i];
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -544,33 +453,18 @@ __global__ __launch_bounds__(256, NR == 2 ? 3 : 2) void k_contract16(ContractArg
 // alone.  Here every wave fetches its own operands: the A fragment of a k-step is 4 rows x 16 candidates = four 128-byte runs of rT,
 // read as ONE global_load_dwordx4 per PAIR of fragments (lane (k, i) takes candidates 2 i and 2 i + 1 of a 32-candidate half: fragment
 // mi = 2 half + e holds candidates 32 half + 2 i + e -- any bijection of fragment rows onto candidates will do, the epilogue knows it),
-// the B fragments as before.  A and B of k-pair t + DEPTH are requested before k-pair t is multiplied (DEPTH + 1 register slots of
+// the B fragments as before.  A and B of k-pair t + DD are requested before k-pair t is multiplied (DD + 1 register slots of
 // 32 VGPRs beside the 128 accumulators), the four waves of a workgroup run free of each other (the sibling waves' A requests hit
 // L1 / L2 behind the first one) and meet only in the epilogue, which is k_contract16's and adds in the same order: the sums are
 // bit-identical to k_contract16's.
+// Measured and settled (profiles/r06_contract_direct_ab.txt, contract ms per sweep at C3 against 58.4 - 58.6 for the first version of this kernel; the build switches
+// of these experiments are in git 6cdd2df): ONE k-pair in flight 58.7; non-temporal A loads 61.4, non-temporal B loads 59.2; no reduction
+// epilogue 58.3.  Removal experiments (wrong sums, priced only): no diagonal zone 50.1, every A pair / every B fragment from the tile's first
+// k-pair (cache-hot) 57.1 / 56.4, both 55.3.
 // ---------------------------------------------------------------------------------------------------
-#ifndef CONTRACT_D_DEPTH
-#define CONTRACT_D_DEPTH 2
-#endif
-typedef double v2d_t __attribute__((ext_vector_type(2)));
-// (A/B switches of profiles/r06_contract_direct_ab.txt: -DCONTRACT_D_NTA / -DCONTRACT_D_NTB = the A / B loads carry the non-temporal hint)
 __device__ __forceinline__ double2 ld2_plain(const char* p) { return *reinterpret_cast<const double2*>(p); }
-__device__ __forceinline__ double2 ld2_nt(const char* p) {
-  const v2d_t v = __builtin_nontemporal_load(reinterpret_cast<const v2d_t*>(p));
-  return make_double2(v.x, v.y);
-}
-#ifdef CONTRACT_D_NTA
-#define BOGP_D_LDA ld2_nt
-#else
-#define BOGP_D_LDA ld2_plain
-#endif
-#ifdef CONTRACT_D_NTB
-#define BOGP_D_LDB ld2_nt
-#else
-#define BOGP_D_LDB ld2_plain
-#endif
-constexpr int DD = CONTRACT_D_DEPTH;  // k-pairs in flight
-constexpr int DR = DD + 1;            // register slots
+constexpr int DD = 2;       // k-pairs in flight
+constexpr int DR = DD + 1;  // register slots
 
 #ifdef CONTRACT_D_TRACE
 // (profiling builds only, -DCONTRACT_D_TRACE: shader-clock stamps of every wave -- entry, loop start, the start of EVERY k-pair, loop end, drain, reduction, exit --
@@ -624,13 +518,9 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
   const int NJ16 = a.NJ16, NKP = a.NKP;
   const int kmax16 = min((jg + 1) * JT16, NJ16);
   const int nkp_full = 2 * jg * JT16;    // k-pairs without a guard
-#ifdef CONTRACT_AB_NOZONE  // (removal experiment, wrong sums: the diagonal zone is skipped -- what it costs = product - this)
-  const int nkp = max(nkp_full, 2);
-#else
   // k-pairs of this WAVE: its last tile (15 - w of the group, serpentine below) ends 2 w k-pairs before the group does -- the waves do not
   // wait for each other before the epilogue, so a wave that has nothing left to multiply stops requesting operands too
   const int nkp = min(2 * kmax16, max(2 * ((jg + 1) * JT16 - w), 2));
-#endif
   const int kp_last = nkp - 1;
 
   int jt[NR];
@@ -661,40 +551,26 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
   // 0, 1 = the A pairs of k-step 0 (candidate halves 0 / 1), 2 .. 5 = the B fragments of tiles 0 .. 3, 6, 7 = the A pairs of k-step 1
 #define BOGP_D_LOAD1(slot, g, ap_, kpc_, vb_)                                                                         \
   do {                                                                                                                \
-    if ((g) < 2) av[slot][0][(g) & 1] = BOGP_D_LDA((ap_) + voffA0 + (((g) & 1) ? 256 : 0));                           \
-    else if ((g) >= 6) av[slot][1][(g) & 1] = BOGP_D_LDA((ap_) + voffA1 + (((g) & 1) ? 256 : 0));                     \
-    else bv[slot][(g) - 2] = BOGP_D_LDB((vb_)[(g) - 2] + (size_t)BOGP_D_BROW(kpc_) * 1024 + voffB);                   \
+    if ((g) < 2) av[slot][0][(g) & 1] = ld2_plain((ap_) + voffA0 + (((g) & 1) ? 256 : 0));                            \
+    else if ((g) >= 6) av[slot][1][(g) & 1] = ld2_plain((ap_) + voffA1 + (((g) & 1) ? 256 : 0));                      \
+    else bv[slot][(g) - 2] = ld2_plain((vb_)[(g) - 2] + (size_t)(kpc_) * 1024 + voffB);                               \
   } while (0)
-  // The k-pair's eight loads go out as ONE block in front of its 32 MFMAs (CONTRACT_D_LBLOCK = 8; 1 / 2 / 4 = one load in front of every group / every second /
-  // every fourth: the first version of this kernel).  The phase trace (profiles/r06_contract_d_trace.txt) showed a FULL k-pair taking 4284 cycles where the two waves
-  // of a SIMD need 4096: every hand-over of the issue port between them costs a few cycles, and a load between two groups of MFMAs is a hand-over.  58.4 -> 58.0 ms.
+  // The eight loads of k-pair kp_ + DD go out as ONE block in front of the 32 MFMAs of k-pair kp_ (the first version of this kernel sent load g in front of
+  // group g).  The phase trace (profiles/r06_contract_d_trace.txt) showed a FULL k-pair taking 4284 cycles where the two waves of a SIMD need 4096: every
+  // hand-over of the issue port between them costs a few cycles, and a load between two groups of MFMAs is a hand-over.  58.4 -> 58.0 ms.
   // NO VALU IN THE LOOP: the address of every load is a scalar base (advanced by scalar arithmetic) + the lane's constant 32-bit offset, the `v_offset, s[base]`
   // form of global_load.  hipcc only selects that form when it sees the zero-extension of the offset next to the load; hoisted out of the loop (it is loop
   // invariant) the offset is a 64-bit register pair and every load gets a v_lshl_add_u64 -- a 64-bit VALU operation, i.e. one that runs on the SAME FP64 pipe as
   // the MFMAs: eight of them per k-pair and wave.  Passing the three offsets through an empty asm inside the loop keeps the zero-extension where the load is.
-  // 58.0 -> 55.9 ms a step at C3 (0.917 -> 0.956 of peak), 454.9 -> 439.1 ms at C5.  (-DCONTRACT_D_NO_SADDR: the A/B switch of profiles/r06_contract_d_trace.txt.)
-#ifndef CONTRACT_D_NO_SADDR
-#define BOGP_D_OPAQUE_OFFSETS() asm volatile("" : "+v"(voffA0), "+v"(voffA1), "+v"(voffB))
-#else
-#define BOGP_D_OPAQUE_OFFSETS() ((void)0)
-#endif
-#ifndef CONTRACT_D_LBLOCK
-#define CONTRACT_D_LBLOCK 8
-#endif
-#define BOGP_D_LOADS_AT(g, slot, ap_, kpc_, vb_)                                                                      \
-  do {                                                                                                                \
-    if ((g) % CONTRACT_D_LBLOCK == 0) {                                                                               \
-      _Pragma("unroll") for (int l_ = 0; l_ < CONTRACT_D_LBLOCK; ++l_) BOGP_D_LOAD1(slot, (g) + l_, ap_, kpc_, vb_);  \
-    }                                                                                                                 \
-  } while (0)
-  // one k-pair: 8 groups of 4 MFMAs (k-step h = g / 4, tile ni = g % 4); load g of k-pair kp_ + DD goes out in front of group g, so
-  // that the requests ride in the shadow of the MFMAs instead of in a block between two k-pairs (the sched_barriers pin that order)
+  // 58.0 -> 55.9 ms a step at C3 (0.917 -> 0.956 of peak), 454.9 -> 439.1 ms at C5 (profiles/r06_contract_d_trace.txt).
+  // one k-pair: 8 groups of 4 MFMAs (k-step h = g / 4, tile ni = g % 4), the eight loads in front of group 0; the sched_barriers pin that order.
+  // (The loads stay INSIDE the group loop: hoisted in front of it the compiler orders the scalar code of the k-pair differently.)
 #define BOGP_D_KPAIR(G, u, kp_)                                                                                       \
   do {                                                                                                                \
     const int kpc_ = min((kp_) + DD, kp_last);                                                                        \
-    const char* ap_ = ab + (size_t)BOGP_D_AROW(kpc_) * kp_stride;                                                     \
+    const char* ap_ = ab + (size_t)kpc_ * kp_stride;                                                                  \
     const int k16_ = (kp_) >> 1;                                                                                      \
-    BOGP_D_OPAQUE_OFFSETS();                                                                                          \
+    asm volatile("" : "+v"(voffA0), "+v"(voffA1), "+v"(voffB));                                                       \
     /* diagonal zone: a tile that is past its diagonal at k-pair kpc_ needs no fragment -- its request goes to the address */ \
     /* of the wave's last tile instead (an L1 hit on a line that is on its way anyway, no second L2 request)            */ \
     const char* vbe_[NR];                                                                                             \
@@ -702,27 +578,19 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
     BOGP_DT_ISSUE();                                                                                                  \
     _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                                   \
       if (g == 1) BOGP_DT_STORE(8 + (kp_));                                                                           \
-      BOGP_D_LOADS_AT(g, ((u) + DD) % DR, ap_, kpc_, vbe_);                                                           \
+      if (g == 0) {                                                                                                   \
+        _Pragma("unroll") for (int l_ = 0; l_ < 8; ++l_) BOGP_D_LOAD1(((u) + DD) % DR, l_, ap_, kpc_, vbe_);          \
+      }                                                                                                               \
       __builtin_amdgcn_sched_barrier(0);                                                                              \
       if (!(G) || k16_ <= jt[g & 3]) {                                                                                \
         const double b_ = (g >> 2) == 0 ? bv[u][g & 3].x : bv[u][g & 3].y;                                            \
         _Pragma("unroll") for (int mi = 0; mi < MR; ++mi)                                                             \
-          mfma16_acc((mi & 1) ? av[u][g >> 2][mi >> 1].y : av[u][g >> 2][mi >> 1].x, b_, acc[mi][g & 3]);             \
+          mfma16((mi & 1) ? av[u][g >> 2][mi >> 1].y : av[u][g >> 2][mi >> 1].x, b_, acc[mi][g & 3]);             \
       }                                                                                                               \
       __builtin_amdgcn_sched_barrier(0);                                                                              \
     }                                                                                                                 \
   } while (0)
 
-#ifdef CONTRACT_AB_FIXB  // (removal experiment, wrong sums: every B fragment from the tile's first k-pair)
-#define BOGP_D_BROW(k_) 0
-#else
-#define BOGP_D_BROW(k_) (k_)
-#endif
-#ifdef CONTRACT_AB_FIXA  // (removal experiment, wrong sums: every A pair from the tile's first k-pair -- L1 / L2 hits, no HBM latency)
-#define BOGP_D_AROW(k_) 0
-#else
-#define BOGP_D_AROW(k_) (k_)
-#endif
 #pragma unroll
   for (int t = 0; t < DD; ++t) {
     const int kpc = min(t, kp_last);
@@ -749,20 +617,7 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
 
   // ---- epilogue (k_contract16's): D[i][j] sits in lane 16 (i % 4) + j, register i / 4; row i of fragment mi = candidate
   // 32 (mi / 2) + 2 i + (mi % 2)
-  // (BOGP_LINT_NO_DRAIN / BOGP_LINT_NO_FENCE: the negative controls of tests/test_isa_lint.py, as in k_contract16)
-#ifndef BOGP_LINT_NO_DRAIN
-  BOGP_MFMA16_DRAIN();
-#endif
-#ifndef BOGP_LINT_NO_FENCE
-#pragma unroll
-  for (int mi = 0; mi < MR; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NR; ++ni) asm volatile("" : "+v"(acc[mi][ni]));
-#endif
-#ifdef CONTRACT_AB_NOEPI  // (removal experiment: no reduction; one accumulator word per thread keeps the MFMAs alive)
-  if (acc[0][0][0] == 12345.678) a.ss_part[tid] = acc[1][1][1] + acc[2][2][2] + acc[3][3][3];
-  return;
-#endif
+  contract_drain(acc);
   BOGP_DT_NOW(4);
   double* red = lds;                    // [16 slots][NWJ][RP]
   double* red2 = lds + 16 * NWJ * RP;   // [NWJ][64]: per-wave partial sums
@@ -811,14 +666,12 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
 // ---------------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------------
-// (kernel A' for the squared-distance kernels without a fused trend; against kernel A everywhere: profiles/r05_corr_mfma_ab.txt)
-static bool corr_mfma_enabled() { return true; }
-
-// the kernels launch_corr_chunk serves with kernel A' -- the producer that also exists without the store of r (CorrArgs::store = false)
+// the kernels launch_corr_chunk serves with kernel A' (the squared-distance kernels without a fused trend; against kernel A everywhere:
+// profiles/r05_corr_mfma_ab.txt) -- the producer that also exists without the store of r (CorrArgs::store = false)
 static bool corr_sqdist_kernel(int kernel) {
   return kernel == BOGP_KERNEL_SE || kernel == BOGP_KERNEL_MATERN12 || kernel == BOGP_KERNEL_MATERN32 || kernel == BOGP_KERNEL_MATERN52;
 }
-bool corr_chunk_without_store(int kernel, int pv, bool have_xnorm) { return corr_sqdist_kernel(kernel) && pv == 0 && have_xnorm && corr_mfma_enabled(); }
+bool corr_chunk_without_store(int kernel, int pv, bool have_xnorm) { return corr_sqdist_kernel(kernel) && pv == 0 && have_xnorm; }
 
 hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipStream_t st) {
   dim3 grid((unsigned)nMt, (unsigned)S);
@@ -910,60 +763,11 @@ hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipS
 // profiles/r04_trend_timing.txt)
 int corr_trend_columns(int p) { return p <= 1 ? 0 : (p <= 16 ? 16 : (p <= 32 ? 32 : 0)); }
 
-// four 16-column fragments per wave = 256-column groups (the NR = 2 instantiation of k_contract16 -- 128-column groups, three workgroups
-// per CU -- lost in r01 and was never the default; removed with its switch in r06)
-static constexpr int contract_nr() { return 4; }
-
-#ifdef CONTRACT_TRACE
+#ifdef CONTRACT_D_TRACE
 static unsigned long long* g_trace = nullptr;
 static size_t g_trace_words = 0, g_trace_used = 0;
 static int g_trace_dims[4] = {0, 0, 0, 0};
-hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
-  const size_t need = (size_t)a.nMt * a.nJ * NWJ * TR_NST;
-  if (need > g_trace_words) {
-    if (g_trace) (void)hipFree(g_trace);
-    hipError_t e = hipMalloc((void**)&g_trace, need * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    g_trace_words = need;
-  }
-  // the stamps of the LARGEST launch seen are kept (a sweep's last chunk is a short one); smaller launches run the same code without the dump
-  const bool keep = need >= g_trace_used;
-  if (keep) {
-    g_trace_used = need;
-    g_trace_dims[0] = a.nMt; g_trace_dims[1] = a.nJ; g_trace_dims[2] = a.NJ16; g_trace_dims[3] = TR_NST;
-  }
-  hipLaunchKernelGGL(k_contract16<4>, dim3((unsigned)(a.nMt * a.nJ)), 256, 0, st, a, keep ? g_trace : (unsigned long long*)nullptr);
-  return hipGetLastError();
-}
-// the last launch's stamps: dims = {nMt, nJ, NJ16, words per wave}; out may be NULL (size query)
-hipError_t debug_contract_trace(unsigned long long* out, size_t cap_words, size_t* used_words, int* dims) {
-  if (used_words) *used_words = g_trace_used;
-  if (dims) for (int i = 0; i < 4; ++i) dims[i] = g_trace_dims[i];
-  if (!out) return hipSuccess;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return e;
-  return hipMemcpy(out, g_trace, std::min(cap_words, g_trace_used) * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-}
-#elif defined(CONTRACT_D_TRACE)
-static unsigned long long* g_trace = nullptr;
-static size_t g_trace_words = 0, g_trace_used = 0;
-static int g_trace_dims[4] = {0, 0, 0, 0};
-hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
-  const size_t need = (size_t)a.nMt * a.nJ * NWJ * DT_NST;
-  if (need > g_trace_words) {
-    if (g_trace) (void)hipFree(g_trace);
-    hipError_t e = hipMalloc((void**)&g_trace, need * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    g_trace_words = need;
-  }
-  const bool keep = need >= g_trace_used;  // the stamps of the LARGEST launch seen are kept
-  if (keep) {
-    g_trace_used = need;
-    g_trace_dims[0] = a.nMt; g_trace_dims[1] = a.nJ; g_trace_dims[2] = a.NJ16; g_trace_dims[3] = DT_NST;
-  }
-  hipLaunchKernelGGL(k_contract16d, dim3((unsigned)(a.nMt * a.nJ)), 256, 0, st, a, keep ? g_trace : (unsigned long long*)nullptr);
-  return hipGetLastError();
-}
+// the stamps of the largest launch so far: dims = {nMt, nJ, NJ16, words per wave}; out may be NULL (size query)
 hipError_t debug_contract_trace(unsigned long long* out, size_t cap_words, size_t* used_words, int* dims) {
   if (used_words) *used_words = g_trace_used;
   if (dims) for (int i = 0; i < 4; ++i) dims[i] = g_trace_dims[i];
@@ -981,32 +785,43 @@ static bool contract_direct() {
   }();
   return on;
 }
-
-hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
-  if (contract_direct()) hipLaunchKernelGGL(k_contract16d, dim3((unsigned)(a.nMt * a.nJ)), 256, 0, st, a);
-  else hipLaunchKernelGGL(k_contract16<4>, dim3((unsigned)(a.nMt * a.nJ)), 256, 0, st, a);
-  return hipGetLastError();
-}
 #endif
 
-int contract_cols_per_group() { return NWJ * contract_nr() * 16; }
+hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nMt * a.nJ));
+#ifdef CONTRACT_D_TRACE  // always k_contract16d, with the stamp buffer as its second argument
+  const size_t need = (size_t)a.nMt * a.nJ * NWJ * DT_NST;
+  if (need > g_trace_words) {
+    if (g_trace) (void)hipFree(g_trace);
+    hipError_t e = hipMalloc((void**)&g_trace, need * sizeof(unsigned long long));
+    if (e != hipSuccess) return e;
+    g_trace_words = need;
+  }
+  // the stamps of the LARGEST launch seen are kept (a sweep's last chunk is a short one); smaller launches run the same code without the dump
+  const bool keep = need >= g_trace_used;
+  if (keep) {
+    g_trace_used = need;
+    g_trace_dims[0] = a.nMt; g_trace_dims[1] = a.nJ; g_trace_dims[2] = a.NJ16; g_trace_dims[3] = DT_NST;
+  }
+  hipLaunchKernelGGL(k_contract16d, grid, 256, 0, st, a, keep ? g_trace : (unsigned long long*)nullptr);
+#else
+  if (contract_direct()) hipLaunchKernelGGL(k_contract16d, grid, 256, 0, st, a);
+  else hipLaunchKernelGGL(k_contract16<4>, grid, 256, 0, st, a);
+#endif
+  return hipGetLastError();
+}
+
+// four 16-column fragments per wave (both kernels) = 256-column groups
+int contract_cols_per_group() { return NWJ * 4 * 16; }
 
 // the cross-product flavour for the batched one-point path: ncp = 16 / 32 / 64 right-hand-side columns per point; always the
 // 256-column workgroups (a.nJ must be ceil(Np / 256)); a.ss_part = the points' record array, a.cross_B = points
 hipError_t launch_contract_cross(const ContractArgs& a, int ncp, hipStream_t st) {
   const dim3 grid((unsigned)(a.nMt * a.nJ));
-#ifdef CONTRACT_TRACE
-  unsigned long long* none = nullptr;
-  if (ncp == 16) hipLaunchKernelGGL((k_contract16<4, 16>), grid, 256, 0, st, a, none);
-  else if (ncp == 32) hipLaunchKernelGGL((k_contract16<4, 32>), grid, 256, 0, st, a, none);
-  else if (ncp == 64) hipLaunchKernelGGL((k_contract16<4, 64>), grid, 256, 0, st, a, none);
-  else return hipErrorInvalidValue;
-#else
   if (ncp == 16) hipLaunchKernelGGL((k_contract16<4, 16>), grid, 256, 0, st, a);
   else if (ncp == 32) hipLaunchKernelGGL((k_contract16<4, 32>), grid, 256, 0, st, a);
   else if (ncp == 64) hipLaunchKernelGGL((k_contract16<4, 64>), grid, 256, 0, st, a);
   else return hipErrorInvalidValue;
-#endif
   return hipGetLastError();
 }
 

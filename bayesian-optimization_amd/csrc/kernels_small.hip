@@ -26,6 +26,7 @@
 
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_mfma.h"
 
 namespace bogp {
 
@@ -33,12 +34,6 @@ namespace {
 constexpr int SM_MT = 64;        // candidates per workgroup
 constexpr int SM_PANEL = 256;    // training rows resident in LDS at a time
 constexpr int SM_WAVES = 8;      // 512 threads: two waves per SIMD; each owns 4 / 2 sixteen-column tiles (SM_NR: Np <= 512 / 256)
-
-typedef double d4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void mfma16s(double a, double b, d4s& c) {
-  asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-#define BOGP_SM_DRAIN() asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory")
 
 // One 32-row block (4 k-pairs x 2 k-steps) of the resident panel for the wave's SM_NR column tiles.  `tile` points at the
 // block's first row in LDS (pitch 64 doubles, swizzled: element (row, c) sits at row * 64 + (c ^ 16 (row & 1))); aoffm[mi]
@@ -53,7 +48,7 @@ __device__ __forceinline__ void mfma16s(double a, double b, d4s& c) {
 template <int SM_MR, int SM_NR, int RING, int PH, bool KPB>
 __device__ __forceinline__ void small_block16(const bool GUARDED, const double* __restrict__ tile, const char* const (&vbase)[SM_NR],
                                               unsigned& voffB, const int (&jt)[SM_NR], const int (&aoffm)[SM_MR],
-                                              int kb, int kp_clamp, double2 (&bq)[RING][SM_NR], d4s (&acc)[SM_MR][SM_NR]) {
+                                              int kb, int kp_clamp, double2 (&bq)[RING][SM_NR], d4 (&acc)[SM_MR][SM_NR]) {
   if constexpr (KPB) {
   // (r06, default: the k-pair's four B requests AND the eight A reads of its two k-steps in ONE block in front of its MFMAs -- one hand-over of the issue port a
   // k-pair instead of three; the LDS round trip is then exposed once a k-pair and left to the SIMD's other wave.  KPB = the eight-wave workgroups with four tiles a
@@ -90,7 +85,7 @@ __device__ __forceinline__ void small_block16(const bool GUARDED, const double* 
         for (int h = 0; h < 2; ++h) {
           const double bv = h == 0 ? bq[(4 * PH + s) & (RING - 1)][ni].x : bq[(4 * PH + s) & (RING - 1)][ni].y;
 #pragma unroll
-          for (int mi = 0; mi < SM_MR; ++mi) mfma16s(af[h][mi], bv, acc[mi][ni]);
+          for (int mi = 0; mi < SM_MR; ++mi) mfma16(af[h][mi], bv, acc[mi][ni]);
         }
       }
     }
@@ -126,7 +121,7 @@ __device__ __forceinline__ void small_block16(const bool GUARDED, const double* 
         if (!GUARDED || kb16 <= jt[ni]) {
           const double bv = h == 0 ? bq[(4 * PH + s) & (RING - 1)][ni].x : bq[(4 * PH + s) & (RING - 1)][ni].y;
 #pragma unroll
-          for (int mi = 0; mi < SM_MR; ++mi) mfma16s(af[sub & 1][mi], bv, acc[mi][ni]);
+          for (int mi = 0; mi < SM_MR; ++mi) mfma16(af[sub & 1][mi], bv, acc[mi][ni]);
         }
       }
     }
@@ -189,11 +184,11 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep_small(const double* __rest
     jt[ni] = valid[ni] ? j : -1;
     vbase[ni] = reinterpret_cast<const char*>(Vp + (size_t)min(j, NJ16 - 1) * NKP * 64);
   }
-  d4s acc[SM_MR][SM_NR];
+  d4 acc[SM_MR][SM_NR];
 #pragma unroll
   for (int mi = 0; mi < SM_MR; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < SM_NR; ++ni) acc[mi][ni] = (d4s){0.0, 0.0, 0.0, 0.0};
+    for (int ni = 0; ni < SM_NR; ++ni) acc[mi][ni] = (d4){0.0, 0.0, 0.0, 0.0};
 
   // A lane = 16 k + i reads row k of the k-step, candidate 16 mi + i; the row parity of a lane is (lane >> 4) & 1
   int aoffm[SM_MR];
@@ -317,15 +312,13 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep_small(const double* __rest
   }
 
   // ---- epilogue ---------------------------------------------------------------------------------------------------
-  BOGP_SM_DRAIN();
-  // The MFMAs are inline asm: to the compiler their results are ready at once, and the drain above (no register operands) does
-  // not keep the epilogue's reads of the accumulators behind it.  With ONE tile per wave the scheduler did hoist the read of
-  // the last-written component of the last accumulator above the drain (rows 60-63 of every workgroup wrong: found by
-  // tests/test_gpu_driver.py at N = 100).  Naming every accumulator in an (empty) volatile asm behind the drain pins the order.
+  mfma16_drain();
+  // the fences behind the operand-less drain (bogp_mfma.h, 3.): with ONE tile per wave the scheduler did hoist the read of the last-written
+  // component of the last accumulator above it (rows 60-63 of every workgroup wrong: found by tests/test_gpu_driver.py at N = 100)
 #pragma unroll
   for (int mi = 0; mi < SM_MR; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < SM_NR; ++ni) asm volatile("" : "+v"(acc[mi][ni]));
+    for (int ni = 0; ni < SM_NR; ++ni) mfma16_fence(acc[mi][ni]);
   BOGP_STAMP(t_mfma);
   __syncthreads();
   BOGP_STAMP(t_pro);

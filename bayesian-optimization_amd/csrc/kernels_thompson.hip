@@ -21,19 +21,17 @@
 // mode 0 writes z alone (the draw at the training rows), mode 1 beta + z (prior paths); neither reads the chunk.
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_mfma.h"
 
 namespace bogp {
 
 namespace {
-typedef double d4t __attribute__((ext_vector_type(4)));
-// The MFMAs are inline asm, invisible to the hazard recogniser.  Operands built by VALU code (selects, cos, the zeroed accumulator)
-// must have retired: the empty-bodied nop pins all three in registers two wait states ahead of the instruction.
-__device__ __forceinline__ void mfma16t(double a, double b, d4t& c) {
+// Operands built by VALU code (selects, cos, the zeroed accumulator) must have retired (bogp_mfma.h, 4.): the nop pins all three in
+// registers two wait states ahead of the instruction.
+__device__ __forceinline__ void mfma16t(double a, double b, d4& c) {
   asm volatile("s_nop 1" : "+v"(a), "+v"(b), "+v"(c));
-  asm("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
+  mfma16(a, b, c);
 }
-// the drain between the last MFMA of a chain and the first read of its accumulator (the epilogue idiom of k_gemm64 / k_contract16)
-#define BOGP_TS_DRAIN(c) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(c))
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
@@ -45,12 +43,12 @@ __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
   const int64_t c0 = (int64_t)blockIdx.x * 64 + 16 * w;  // first row of this wave inside the launch
   const int d = a.d;
 
-  d4t acc = (d4t){0.0, 0.0, 0.0, 0.0};
+  d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
   // ---- feature term
   const bool xrow = c0 + li < a.mcount;
   const double* xp = a.X + (size_t)(a.row0 + c0 + li) * d;  // dereferenced under xrow only
   for (int f0 = 0; f0 < a.L; f0 += 16) {
-    d4t ph = (d4t){0.0, 0.0, 0.0, 0.0};
+    d4 ph = (d4){0.0, 0.0, 0.0, 0.0};
     const double* op = a.omega + (size_t)(f0 + li) * d;
     for (int k0 = 0; k0 < d; k0 += 4) {
       const int k = k0 + lk;
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
       wv[r] = a.W[(size_t)(f0 + 4 * r + lk) * 16 + li];
       pv[r] = a.phase[f0 + 4 * r + lk];
     }
-    BOGP_TS_DRAIN(ph);
+    mfma16_drain(ph);
 #pragma unroll
     for (int r = 0; r < 4; ++r) pv[r] = cos(ph[r] + pv[r]);
 #pragma unroll
@@ -92,7 +90,7 @@ __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
       mfma16t(rv, gv, acc);
     }
   }
-  BOGP_TS_DRAIN(acc);
+  mfma16_drain(acc);
 
   // ---- epilogue: lane l holds path li of the candidates c0 + 4 reg + lk
   double v = -INFINITY;
