@@ -868,6 +868,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         // stage 1: every row from FP32 sums, flagged unless its margins rule it out -> S1, a superset of the survivors
         Bound32Args ba;
         ba.Xs = h->dXs; ba.M = M; ba.m0 = sb; ba.rcount = rows; ba.d = h->d; ba.Np = h->Np; ba.sqrt_theta = h->dsqrt_theta;
+        ba.estimate_trend = pb.estimate_trend;
         ba.md = md32; ba.mu = cx.pmu32; ba.wd = cx.pwd32; ba.na = cx.pna32;
         if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_bound32_sums(kernel, ba, st); }))) return e;
         PruneBoundArgs p1 = pb;
@@ -1085,7 +1086,7 @@ int bogp::bound32_prepare(bogp_handle* h) {
   int e;
   if ((e = h->dX32.ensure(h, (size_t)4 * ((d + 3) / 4) * Np)) || (e = h->dvec32.ensure(h, (size_t)3 * Np))) return e;
   if ((e = h->dstats32.ensure(h, 3))) return e;
-  HIPCHK(h, launch_bound32_prepare(h->dXthT, h->dXnorm, h->dgamma, h->dw, d, Np, h->dX32, h->dvec32, h->dstats32, st));
+  HIPCHK(h, launch_bound32_prepare(h->kernel, h->dXthT, h->dXnorm, h->dgamma, h->dw, d, Np, h->dX32, h->dvec32, h->dstats32, st));
   HIPCHK(h, hipMemcpyAsync(h->stats32, h->dstats32, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   h->b32_gen = h->commit_gen; h->b32_target = h->target;

@@ -390,9 +390,12 @@ __host__ __device__ __forceinline__ double bound32_slope(int kernel) {
   return kernel == BOGP_KERNEL_SE ? 1.0 : kernel == BOGP_KERNEL_MATERN32 ? 1.5 : kernel == BOGP_KERNEL_MATERN52 ? 5.0 / 6.0 : 0.0;
 }
 constexpr int BOUND32_FLUSH = 4;  // 16-pair steps a lane accumulates in FP32 before the sums go to its FP64 accumulators
+constexpr int BOUND32_REG_D = 32;  // up to here k_bound32_sums runs (the squared distance straight from the matrix chain), above k_bound32_sums_any
 // |mu32 - r . gamma| <= *e_mu and |wd32 - w . r| <= *e_w for a row with squared norm na (of its FP64 theta-scaled point), given the
 // largest squared norm nb_max of the scaled training points and the 1-norms of gamma and w.  u = 2^-24.
-//   ds = 1.01 (d + 16) u (na + nb_max) + 1e-30   input rounding, the two norms, the fma chain of the cross term, the combination
+//   ds = 1.01 (2 d + 8) u (na + nb_max) + 1e-30  d <= BOUND32_REG_D: input rounding, the two norms, their sum, and an fma chain that
+//                                                starts at that sum -- its partial sums reach 2 (na + nb), four times the cross term's
+//      = 1.01 (d + 16) u (na + nb_max) + 1e-30   above: input rounding, the two norms, the fma chain of the cross term, the combination
 //   dr = slope ds + 32 u + 1e-30                 profile: square root, exponential, polynomial; flushed denormals
 //   e  = |v|_1 (dr + (4 FLUSH + 4) u)            rounding of v to FP32, FP32 accumulation over 4 FLUSH terms, the FP64 tail
 // +inf where FP32 would overflow (na + nb_max >= 1e37) or an input is negative or not finite.
@@ -402,7 +405,7 @@ __host__ __device__ __forceinline__ void bound32_margin(int kernel, int d, doubl
     *e_mu = INFINITY; *e_w = INFINITY;
     return;
   }
-  const double ds = 1.01 * (d + 16) * u * nn + 1e-30;
+  const double ds = 1.01 * (d <= BOUND32_REG_D ? 2 * d + 8 : d + 16) * u * nn + 1e-30;
   const double dr = slope * ds + 32.0 * u + 1e-30 + (4 * BOUND32_FLUSH + 4) * u;
   *e_mu = gamma_l1 * dr + 1e-30;  // (+ entries of v below FP32's normal range: N 2^-150 at most)
   *e_w = w_l1 * dr + 1e-30;

@@ -174,11 +174,12 @@ struct Bound32Args {
   const double* Xs;          // candidates, M x d row-major
   int64_t M, m0, rcount;     // total candidates; first row of the region; its rows
   int d, Np;
+  int estimate_trend;        // as k_bound32_flags receives it: without a trend nothing reads w . r, and it is not summed (d <= 32)
   const double* sqrt_theta;
   Bound32Model md;
   double *mu, *wd, *na;      // [rcount] r . gamma, w . r, |a|^2 of the row's FP64 scaled point
 };
-hipError_t launch_bound32_prepare(const double* XthT, const double* xnorm, const double* gamma, const double* wvec, int d, int Np,
+hipError_t launch_bound32_prepare(int kernel, const double* XthT, const double* xnorm, const double* gamma, const double* wvec, int d, int Np,
                                   float* XthT32, float* vec32, double* stats, hipStream_t st);
 hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st);
 // PruneBoundArgs' region with mu_part = the FP32 sums (S = 1): flags and block counts as launch_prune_bound leaves them
