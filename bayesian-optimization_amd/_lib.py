@@ -22,6 +22,8 @@ SELFTEST_PROFILE, SELFTEST_BESSEL_K, SELFTEST_RGAMMA, SELFTEST_BESSEL_K_PAIRS, S
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
 MAX_Q = 64
 PRUNE_PATH_NONE, PRUNE_PATH_CHUNKS, PRUNE_PATH_ONEPASS, PRUNE_PATH_ONEPASS_FALLBACK = 0, 1, 2, 3  # bogp_last_prune_path
+# bogp_contract_tile_rows: workgroups of the 64-row grid per four CUs from which a launch takes 64 / 32 rows (csrc/bogp_internal.h)
+CONTRACT_TILE64_MIN_WG_PER_4CU, CONTRACT_TILE32_MIN_WG_PER_4CU = 14, 6
 MAX_TARGETS = 8
 MAX_TOPK = 32
 MAX_BELIEVED = 32  # BOGP_MAX_BELIEVED: q + pending points of one bogp_sweep_believer call
@@ -118,6 +120,9 @@ SIGNATURES = {
     "bogp_last_contracted_rows": (C.c_int, [C.c_void_p, _lp]),
     "bogp_last_prune_path": (C.c_int, [C.c_void_p, _ip, _lp, _ip]),
     "bogp_prune_decide": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "bogp_set_contract_tile": (C.c_int, [C.c_void_p, C.c_int]),
+    "bogp_last_contract_tile": (C.c_int, [C.c_void_p, _ip]),
+    "bogp_contract_tile_rows": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "bogp_sweep_chunk_rows": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "bogp_acq_upper_bound": (C.c_double, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
@@ -1186,6 +1191,19 @@ class Engine:
         """Candidates that went through the variance contraction in the last predict() / sweep() (waits for a queued sweep)."""
         n = C.c_int64()
         self._check(self._lib.bogp_last_contracted_rows(self._h, C.cast(C.byref(n), _lp)))
+        return int(n.value)
+
+    def set_contract_tile(self, rows=0):
+        """Candidates per workgroup of the direct variance contraction: 0 (the default) chooses per launch, 16 / 32 / 64 force one tile
+        for this engine (tests and A/B).  No output bit depends on it."""
+        if rows not in (0, 16, 32, 64):
+            raise ValueError("set_contract_tile: %r is none of 0 (automatic), 16, 32, 64" % (rows,))
+        self._check(self._lib.bogp_set_contract_tile(self._h, int(rows)))
+
+    def last_contract_tile(self) -> int:
+        """Tile rows (16, 32 or 64) of the last contraction launch of this engine."""
+        n = C.c_int()
+        self._check(self._lib.bogp_last_contract_tile(self._h, C.cast(C.byref(n), _ip)))
         return int(n.value)
 
     def selftest_gemm(self, A, B, C_in=None, ta=False, tb=False, alpha=1.0, beta=0.0, tri=0, split=True):

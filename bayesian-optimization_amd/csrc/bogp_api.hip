@@ -51,6 +51,7 @@ extern "C" int bogp_create(int device, bogp_handle** out) {
   bogp_handle* h = new bogp_handle();
   h->device = device;
   h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  h->contract_tile.n_cu = h->n_cu;
   // The second stream carries work that runs BESIDE the main stream's dependent chain (the look-ahead remainder of the
   // two-level factorisation, the optional producer overlap): lowest priority, so that a freed workgroup slot should go to
   // the chain's small kernels first instead of to the next workgroup of the bulk kernel (measured neutral for the two-level

@@ -644,7 +644,7 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
     HIPCHK(h, hipEventRecord(evp[0], st));
     ContractArgs kp = ka;
     kp.nMt = (int)((P + 63) / 64);
-    HIPCHK(h, launch_contract(kp, st));
+    HIPCHK(h, launch_contract(kp, st, h->contract_tile));
     HIPCHK(h, hipEventRecord(evp[1], st));
     AcqArgs ap = model;
     ap.mu_part = h->dmu_part[0]; ap.w_part = h->dw_part[0]; ap.ss_part = h->dss_part; ap.Mc = Mc; ap.mcount = P; ap.m0 = 0;
@@ -672,12 +672,12 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
   if (rcount > 0) {
     ContractArgs ki = ka;
     ki.rT = h->drT[0] + i0; ki.ss_part = h->dss_part + i0; ki.nMt = (int)((rcount + 63) / 64); ki.live = pctl + 1;
-    HIPCHK(h, launch_contract(ki, st));
+    HIPCHK(h, launch_contract(ki, st, h->contract_tile));
   }
   if (flush) {
     ContractArgs kf = ka;
     kf.rT = h->drT[1]; kf.ss_part = cx.dss_surv; kf.Mc = Ms; kf.nMt = (int)(Ms / 64); kf.live = pctl + 0;
-    HIPCHK(h, launch_contract(kf, st));
+    HIPCHK(h, launch_contract(kf, st, h->contract_tile));
   }
   HIPCHK(h, hipEventRecord(ev[3], st));
   if (rcount > 0) {
@@ -749,7 +749,7 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
       HIPCHK(h, hipEventRecord(ev[2], st));
       // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
       // and k_acquisition sums zero variance groups (its MSE output is not read)
-      if (rq.need_var) HIPCHK(h, launch_contract(ka, st));
+      if (rq.need_var) HIPCHK(h, launch_contract(ka, st, h->contract_tile));
       HIPCHK(h, hipEventRecord(ev[3], st));
       AcqArgs aa = model;
       aa.mu_part = h->dmu_part[b]; aa.w_part = h->dw_part[b]; aa.ss_part = h->dss_part; aa.nJ = rq.need_var ? cx.nJ_main : 0; aa.Mc = Mc;
@@ -827,7 +827,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
   auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
     kc.nMt = (int)((cnt + 63) / 64);
-    if (int e2 = timed_span(h, st, &ev_next, 1, [&] { return launch_contract(kc, st); })) return e2;
+    if (int e2 = timed_span(h, st, &ev_next, 1, [&] { return launch_contract(kc, st, h->contract_tile); })) return e2;
     ++contract_launches;
     aa.mcount = cnt; aa.map = map;
     HIPCHK(h, launch_acquisition(aa, st));
@@ -1170,6 +1170,20 @@ extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
   }
   return BOGP_OK;
 }
+
+extern "C" int bogp_set_contract_tile(bogp_handle* h, int rows) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (rows != 0 && rows != 16 && rows != 32 && rows != 64) FAIL(h, BOGP_ERR_INVALID, "bogp_set_contract_tile: %d is none of 0 (automatic), 16, 32, 64", rows);
+  h->contract_tile.forced = rows;
+  return BOGP_OK;
+}
+extern "C" int bogp_last_contract_tile(bogp_handle* h, int* rows) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!rows) FAIL(h, BOGP_ERR_INVALID, "bogp_last_contract_tile: null output");
+  *rows = h->contract_tile.last;
+  return BOGP_OK;
+}
+extern "C" int bogp_contract_tile_rows(int64_t row_tiles64, int nJ, int n_cu, int live) { return contract_tile_rows(row_tiles64, nJ, n_cu, live != 0); }
 
 // host evaluations of the pruned sweep's bound and test (csrc/bogp_device.h): no device, no handle; tests/test_prune_bounds_host.py
 extern "C" double bogp_acq_upper_bound(int acq_id, double acq_par, double y_hat, double sd_ub, double plugin, double sigma2) {

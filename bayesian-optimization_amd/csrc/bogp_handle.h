@@ -197,6 +197,7 @@ struct bogp_handle {
   // sweep scratch
   bogp::DevBuf<double> drT[2], dmu_part[2], dw_part[2];
   bogp::DevBuf<double> dss_part;
+  bogp::ContractTile contract_tile;  // candidate tile of the direct contraction: bogp_set_contract_tile / bogp_last_contract_tile
   bogp::DevBuf<double> dblk_val, dmu_out, dmse_out, dacq_out, dbest_val;
   bogp::DevBuf<int64_t> dblk_idx, dbest_idx;
   bogp::DevBuf<unsigned int> dcounter;  // arrival ticket of k_sweep_small's last workgroup (zero between launches)

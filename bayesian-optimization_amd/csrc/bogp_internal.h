@@ -70,6 +70,25 @@ struct ContractArgs {
   const long long* live = nullptr;  // pruned sweep: device word holding the live row count (workgroups of tiles past it return at once), or null
 };
 
+// Candidates per workgroup of a direct contraction launch (exported as bogp_contract_tile_rows; DESIGN.md 5.2'''): 64 (k_contract16d) while the
+// 64-row grid fills the chip, else 32, else 16 (k_contract16n).  tiles64 x nJ = the workgroups of the 64-row grid; the crossovers are workgroups of
+// that grid per CU, in quarters so that the edges are exact in integers (measured: profiles/contract_rows.txt, section B).  The gated launches of the
+// per-chunk pruned path (live) keep 64 rows.  The bits do not depend on the choice.
+constexpr int CONTRACT_TILE64_MIN_WG_PER_4CU = 14;  // from 3.5 workgroups a CU: 64 rows              (profiles/contract_rows.txt, section B)
+constexpr int CONTRACT_TILE32_MIN_WG_PER_4CU = 6;   // from 1.5 workgroups a CU: 32 rows, below: 16   (profiles/contract_rows.txt, section B)
+inline int contract_tile_rows(int64_t tiles64, int nJ, int n_cu, bool live) {
+  if (live) return 64;
+  const int64_t wg4 = 4 * tiles64 * (int64_t)(nJ > 0 ? nJ : 1), cu = n_cu > 0 ? n_cu : 1;
+  if (wg4 >= CONTRACT_TILE64_MIN_WG_PER_4CU * cu) return 64;
+  if (wg4 >= CONTRACT_TILE32_MIN_WG_PER_4CU * cu) return 32;
+  return 16;
+}
+struct ContractTile {
+  int n_cu = 0;    // compute units of the handle's device
+  int forced = 0;  // bogp_set_contract_tile: 0 automatic, 16 / 32 / 64
+  int last = 64;   // bogp_last_contract_tile: tile rows of the last contraction launch
+};
+
 struct AcqArgs {
   const double* mu_part;  // [S][Mc]
   const double* w_part;   // [S][Mc]
@@ -392,7 +411,7 @@ int64_t sweep_small_blocks(int64_t M, int n_cu);
 hipError_t launch_sweep_small(int kernel, const SmallArgs& a, int n_cu, hipStream_t st);
 
 hipError_t launch_corr_chunk(int kernel, const CorrArgs& a, int nMt, int S, hipStream_t st);
-hipError_t launch_contract(const ContractArgs& a, hipStream_t st);
+hipError_t launch_contract(const ContractArgs& a, hipStream_t st, ContractTile& ct);
 hipError_t launch_contract_cross(const ContractArgs& a, int ncp, hipStream_t st);
 int contract_cols_per_group();
 hipError_t launch_acquisition(const AcqArgs& a, hipStream_t st);

@@ -221,14 +221,14 @@ constexpr int PITCH = 64 + 16;       // LDS row pitch in doubles: 640 B == 128 (
 // The epilogue idiom of both contraction kernels: the operand-less drain, then a fence on every accumulator (bogp_mfma.h, 3.).
 // (BOGP_LINT_NO_DRAIN / BOGP_LINT_NO_FENCE: negative controls of tests/test_isa_lint.py -- builds WITHOUT the drain / the fences must be
 // flagged by the ISA lint; never defined in the product build)
-template <int NR>
-__device__ __forceinline__ void contract_drain(d4 (&acc)[MR][NR]) {
+template <int MRT, int NR>
+__device__ __forceinline__ void contract_drain(d4 (&acc)[MRT][NR]) {
 #ifndef BOGP_LINT_NO_DRAIN
   mfma16_drain();
 #endif
 #ifndef BOGP_LINT_NO_FENCE
 #pragma unroll
-  for (int mi = 0; mi < MR; ++mi)
+  for (int mi = 0; mi < MRT; ++mi)
 #pragma unroll
     for (int ni = 0; ni < NR; ++ni) mfma16_fence(acc[mi][ni]);
 #endif
@@ -664,6 +664,162 @@ __global__ __launch_bounds__(256, 2) void k_contract16d(ContractArgs a) {
 #undef BOGP_DT_STORE
 
 // ---------------------------------------------------------------------------------------------------
+// Kernel B'' with a narrower candidate tile: 16 MRN = 32 or 16 candidates a workgroup instead of 64 (DESIGN.md 5.2''').
+//
+// A launch of kernel B'' with few candidate tiles is bound by ONE workgroup's walk over the heaviest 256-column group: at N = 2048 that is 256 k-pairs x
+// 32 MFMAs x 64 cycles = 0.22 ms however few rows there are, with most of the chip idle (the survivors' round of a pruned sweep: 13 x 8 workgroups on 256
+// CUs).  With MRN fragments a wave the chain is MRN / 4 as long and the grid 4 / MRN as large; every workgroup still reads all of its column group's V, so
+// the V bytes per row grow by the same factor (from L2 and the Infinity Cache) -- which is why launch_contract only takes this kernel while the 64-row
+// grid leaves the chip idle (contract_tile_rows, bogp_internal.h).
+// The column side is kernel B'' unchanged: four waves x NR = 4 tiles in serpentine order, the guarded diagonal zone, the per-wave early stop, the
+// `v_offset, s[base]` loads with the empty asm that keeps them, the sched_barriers, ss_part[jg][m].  The A fragment of a k-step is ONE load a lane: a
+// double2 (lane (k, i): candidates 2 i and 2 i + 1 -- fragment e holds candidate 2 i + e) for 32 rows, a double (candidate i) for 16: 256- / 128-byte
+// runs of rT.  A k-pair is six loads in front of 8 MRN MFMAs; the 64 / 32 accumulator registers leave room for DDN k-pairs in flight.
+// WHY NO BIT CAN CHANGE: rows of the contraction are independent.  Element D[i][j] of a fragment is the same k-ordered chain of matrix instructions from
+// zero whatever other fragments the wave holds, and the order in which a row's columns are added -- ni within a lane, then the 16 slots, then the four
+// waves, then jg in k_acquisition -- belongs to the column side.  ss_part, hence MSE, every criterion value and every winner, is bit-identical at 16, 32
+// and 64 rows a tile; a difference is a bug, not rounding (tests/test_gpu_contract_tile.py).
+// ---------------------------------------------------------------------------------------------------
+template <int MRN> struct ContractAFrag;
+template <> struct ContractAFrag<1> { typedef double type; };
+template <> struct ContractAFrag<2> { typedef double2 type; };
+__device__ __forceinline__ double afrag_row(double a, int) { return a; }
+__device__ __forceinline__ double afrag_row(const double2& a, int mi) { return mi ? a.y : a.x; }
+
+template <int MRN, int DDN, int WPE>
+__global__ __launch_bounds__(256, WPE) void k_contract16n(ContractArgs a) {
+  constexpr int NR = 4;
+  constexpr int JT16 = NWJ * NR;
+  constexpr int ROWS = 16 * MRN;  // candidates a workgroup
+  constexpr int RP = ROWS + 1;
+  constexpr int DRN = DDN + 1;    // register slots
+  typedef typename ContractAFrag<MRN>::type afrag;
+  __shared__ __attribute__((aligned(16))) double lds[16 * NWJ * RP + NWJ * ROWS];  // the epilogue's reduction arrays only
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nMt = a.nMt * (64 / ROWS);                // a.nMt counts 64-row tiles
+  const int jg = a.nJ - 1 - (int)(blockIdx.x / nMt);  // heaviest column group first (k_contract16)
+  const int mt = blockIdx.x % nMt;
+  const int64_t mc0 = (int64_t)mt * ROWS;
+  if (a.live && mc0 >= *a.live) return;  // (launch_contract keeps the gated launches on 64 rows; kept for the same meaning of the argument)
+  const int NJ16 = a.NJ16, NKP = a.NKP;
+  const int kmax16 = min((jg + 1) * JT16, NJ16);
+  const int nkp_full = 2 * jg * JT16;    // k-pairs without a guard
+  const int nkp = min(2 * kmax16, max(2 * ((jg + 1) * JT16 - w), 2));  // k-pairs of this WAVE (k_contract16d)
+  const int kp_last = nkp - 1;
+
+  int jt[NR];
+  bool valid[NR];
+  const char* vb[NR];
+#pragma unroll
+  for (int ni = 0; ni < NR; ++ni) {
+    const int j = jg * JT16 + ((ni & 1) ? NWJ * (ni + 1) - 1 - w : NWJ * ni + w);  // serpentine (k_contract16)
+    valid[ni] = j < NJ16;
+    jt[ni] = valid[ni] ? j : -1;
+    vb[ni] = reinterpret_cast<const char*>(a.Vp + (size_t)min(j, NJ16 - 1) * NKP * 64);
+  }
+  const size_t Mc = (size_t)a.Mc;
+  const char* ab = reinterpret_cast<const char*>(a.rT + mc0);
+  const size_t kp_stride = 8 * Mc * sizeof(double);                                                      // 8 rows a k-pair
+  unsigned voffA0 = (unsigned)(((size_t)(lane >> 4) * Mc + MRN * (lane & 15)) * sizeof(double));   // k-step 0 of the pair (below k_contract16d's offsets)
+  unsigned voffA1 = voffA0 + (unsigned)(4 * Mc * sizeof(double));                                  // k-step 1
+  unsigned voffB = (unsigned)lane * 16u;
+
+  d4 acc[MRN][NR];
+#pragma unroll
+  for (int mi = 0; mi < MRN; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NR; ++ni) acc[mi][ni] = (d4){0.0, 0.0, 0.0, 0.0};
+
+  afrag av[DRN][2];
+  double2 bv[DRN][NR];
+  // load g of a k-pair, in the order the groups need them: 0 = the A fragments of k-step 0, 1 .. 4 = the B fragments of tiles 0 .. 3, 5 = the A fragments of k-step 1
+#define BOGP_N_LOAD1(slot, g, ap_, kpc_, vb_)                                                                         \
+  do {                                                                                                                \
+    if ((g) == 0) av[slot][0] = *reinterpret_cast<const afrag*>((ap_) + voffA0);                                      \
+    else if ((g) == 5) av[slot][1] = *reinterpret_cast<const afrag*>((ap_) + voffA1);                                 \
+    else bv[slot][(g) - 1] = ld2_plain((vb_)[(g) - 1] + (size_t)(kpc_) * 1024 + voffB);                               \
+  } while (0)
+  // one k-pair: 8 groups of MRN MFMAs (k-step h = g / 4, tile ni = g % 4), the six loads of k-pair kp_ + DDN as one block in front of group 0, the offsets
+  // through the empty asm, the zone's dead requests sent to the wave's last tile: all as in k_contract16d, whose comments give the measurements
+#define BOGP_N_KPAIR(G, u, kp_)                                                                                       \
+  do {                                                                                                                \
+    const int kpc_ = min((kp_) + DDN, kp_last);                                                                       \
+    const char* ap_ = ab + (size_t)kpc_ * kp_stride;                                                                  \
+    const int k16_ = (kp_) >> 1;                                                                                      \
+    asm volatile("" : "+v"(voffA0), "+v"(voffA1), "+v"(voffB));                                                       \
+    const char* vbe_[NR];                                                                                             \
+    _Pragma("unroll") for (int ni = 0; ni < NR; ++ni) vbe_[ni] = (!(G) || ((kpc_ >> 1) <= jt[ni])) ? vb[ni] : vb[NR - 1]; \
+    _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                                   \
+      if (g == 0) {                                                                                                   \
+        _Pragma("unroll") for (int l_ = 0; l_ < 6; ++l_) BOGP_N_LOAD1(((u) + DDN) % DRN, l_, ap_, kpc_, vbe_);        \
+      }                                                                                                               \
+      __builtin_amdgcn_sched_barrier(0);                                                                              \
+      if (!(G) || k16_ <= jt[g & 3]) {                                                                                \
+        const double b_ = (g >> 2) == 0 ? bv[u][g & 3].x : bv[u][g & 3].y;                                            \
+        _Pragma("unroll") for (int mi = 0; mi < MRN; ++mi) mfma16(afrag_row(av[u][g >> 2], mi), b_, acc[mi][g & 3]);  \
+      }                                                                                                               \
+      __builtin_amdgcn_sched_barrier(0);                                                                              \
+    }                                                                                                                 \
+  } while (0)
+
+#pragma unroll
+  for (int t = 0; t < DDN; ++t) {
+    const int kpc = min(t, kp_last);
+    const char* ap = ab + (size_t)kpc * kp_stride;
+#pragma unroll
+    for (int g = 0; g < 6; ++g) BOGP_N_LOAD1(t, g, ap, kpc, vb);
+  }
+
+  int kp = 0;
+  // full k-pairs, DRN at a time (static register slots); what is left of them goes through the guarded loop (its guards hold there)
+  for (; kp + DRN <= nkp_full; kp += DRN) {
+#pragma unroll
+    for (int u = 0; u < DRN; ++u) BOGP_N_KPAIR(false, u, kp + u);
+  }
+  for (; kp < nkp; kp += DRN) {
+#pragma unroll
+    for (int u = 0; u < DRN; ++u)
+      if (kp + u < nkp) BOGP_N_KPAIR(true, u, kp + u);
+  }
+#undef BOGP_N_KPAIR
+#undef BOGP_N_LOAD1
+
+  // ---- epilogue (k_contract16's): D[i][j] sits in lane 16 (i % 4) + j, register i / 4; row i of fragment mi = candidate MRN i + mi
+  contract_drain(acc);
+  double* red = lds;                    // [16 slots][NWJ][RP]
+  double* red2 = lds + 16 * NWJ * RP;   // [NWJ][ROWS]: per-wave partial sums
+  const int q = lane >> 4, jc = lane & 15;
+#pragma unroll
+  for (int mi = 0; mi < MRN; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int ni = 0; ni < NR; ++ni)
+        if (valid[ni]) s = __builtin_fma(acc[mi][ni][r], acc[mi][ni][r], s);
+      red[(jc * NWJ + w) * RP + MRN * (4 * r + q) + mi] = s;  // slot = column inside the 16-tile
+    }
+  // the wave's own slots: no workgroup barrier needed between its writes and its reads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (lane < ROWS) {
+    double s = 0.0;
+#pragma unroll
+    for (int sl = 0; sl < 16; ++sl) s += red[(sl * NWJ + w) * RP + lane];
+    red2[w * ROWS + lane] = s;
+  }
+  __syncthreads();
+  if (tid < ROWS) {
+    const double tot = ((red2[tid] + red2[ROWS + tid]) + red2[2 * ROWS + tid]) + red2[3 * ROWS + tid];
+    a.ss_part[(size_t)jg * a.Mc + mc0 + tid] = tot;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------------
 // the kernels launch_corr_chunk serves with kernel A' (the squared-distance kernels without a fused trend; against kernel A everywhere:
@@ -787,8 +943,14 @@ static bool contract_direct() {
 }
 #endif
 
-hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
+// k-pairs in flight and waves a SIMD of the narrow forms (profiles/contract_rows.txt, section C)
+constexpr int CONTRACT_DD32 = 4, CONTRACT_WPE32 = 2;
+constexpr int CONTRACT_DD16 = 4, CONTRACT_WPE16 = 3;
+
+// ct.forced = 0: the candidate tile by contract_tile_rows (bogp_internal.h); ct.last = the rows a tile of this launch had
+hipError_t launch_contract(const ContractArgs& a, hipStream_t st, ContractTile& ct) {
   const dim3 grid((unsigned)(a.nMt * a.nJ));
+  ct.last = 64;
 #ifdef CONTRACT_D_TRACE  // always k_contract16d, with the stamp buffer as its second argument
   const size_t need = (size_t)a.nMt * a.nJ * NWJ * DT_NST;
   if (need > g_trace_words) {
@@ -805,8 +967,17 @@ hipError_t launch_contract(const ContractArgs& a, hipStream_t st) {
   }
   hipLaunchKernelGGL(k_contract16d, grid, 256, 0, st, a, keep ? g_trace : (unsigned long long*)nullptr);
 #else
-  if (contract_direct()) hipLaunchKernelGGL(k_contract16d, grid, 256, 0, st, a);
-  else hipLaunchKernelGGL(k_contract16<4>, grid, 256, 0, st, a);
+  if (!contract_direct()) {
+    hipLaunchKernelGGL(k_contract16<4>, grid, 256, 0, st, a);
+    return hipGetLastError();
+  }
+  // the gated launches of the per-chunk pruned path (a.live) keep 64 rows whatever is forced: most of their workgroups return at once
+  const int rows = a.live ? 64 : ct.forced ? ct.forced : contract_tile_rows(a.nMt, a.nJ, ct.n_cu, false);
+  const dim3 gridn((unsigned)(a.nMt * (64 / rows) * a.nJ));  // a.nMt counts 64-row tiles: the narrow tiles stay inside the same rows
+  if (rows == 16) hipLaunchKernelGGL((k_contract16n<1, CONTRACT_DD16, CONTRACT_WPE16>), gridn, 256, 0, st, a);
+  else if (rows == 32) hipLaunchKernelGGL((k_contract16n<2, CONTRACT_DD32, CONTRACT_WPE32>), gridn, 256, 0, st, a);
+  else hipLaunchKernelGGL(k_contract16d, grid, 256, 0, st, a);
+  ct.last = rows;
 #endif
   return hipGetLastError();
 }

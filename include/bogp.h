@@ -655,6 +655,18 @@ int64_t bogp_sweep_chunk_rows(int64_t rows, int64_t M, int64_t chunk_bytes);
 /* Rows that went through the contraction in the LAST bogp_predict / bogp_sweep call (M without pruning; waits for a queued sweep). */
 int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows);
 
+/* Candidate tile of the direct variance contraction (DESIGN.md section 5.2'''): a workgroup contracts 64, 32 or 16 candidates with
+ * 256 columns of L^-1.  rows = 0 (the default) chooses per launch -- 64 while the 64-row grid fills the device, narrower tiles for
+ * launches of few rows --, 16 / 32 / 64 force one tile for this handle (tests and A/B); anything else is BOGP_ERR_INVALID.  No output
+ * bit depends on the tile.  The gated launches of the per-chunk pruned path always take 64 rows, and so does every launch under
+ * BOGP_CONTRACT_DIRECT=0.  bogp_last_contract_tile: the tile rows of the last contraction launch of this handle (64 before any).   */
+int bogp_set_contract_tile(bogp_handle* h, int rows);
+int bogp_last_contract_tile(bogp_handle* h, int* rows);
+
+/* The automatic choice, no device and no handle (tests/test_contract_tile_host.py): tile rows for a launch of row_tiles64 64-row
+ * tiles x nJ column groups on a device of n_cu compute units; live != 0: a gated launch.                                         */
+int bogp_contract_tile_rows(int64_t row_tiles64, int nJ, int n_cu, int live);
+
 /* Host evaluations of the pruned sweep's two rules, no device and no handle (tests/test_prune_bounds_host.py): an upper bound of
  * criterion acq_id over every standard deviation in [0, sd_ub] at the mean behind y_hat (guard branches included; NaN or +inf
  * where no bound exists), and whether a row with that bound is pruned against a value another row attained:

@@ -194,8 +194,9 @@ for k, lst in by.items():
         if cand:
             x = max(cand); gaps.append(s - x); ends.remove(x)
         ends.append(e)
-gaps = np.asarray(gaps)
-print("\n== workgroup turnover: gap between a wave's exit stamp and the next wave's entry stamp in the same SIMD slot: n=%d mean %.0f median %.0f p90 %.0f cycles" % (len(gaps), gaps.mean(), np.median(gaps), np.percentile(gaps, 90)))
+n_gaps = len(gaps)  # (a launch of no more workgroups than slots -- the pruned sweep's pilot -- has no turnover: n = 0, zeros printed)
+gaps = np.asarray(gaps if gaps else [0])
+print("\n== workgroup turnover: gap between a wave's exit stamp and the next wave's entry stamp in the same SIMD slot: n=%d mean %.0f median %.0f p90 %.0f cycles" % (n_gaps, gaps.mean(), np.median(gaps), np.percentile(gaps, 90)))
 pro = np.asarray([st[2] - st[0] for (_, st, _, _) in waves])
 print("   entry -> end of the first k-pair (set-up + the first operands' round trip to HBM + 32 MFMAs): mean %.0f median %.0f p90 %.0f cycles" % (pro.mean(), np.median(pro), np.percentile(pro, 90)))
 epi = np.asarray([st[-1] - st[-4] for (_, st, _, _) in waves])
