@@ -6,6 +6,8 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
   bogp.acquisition.{EI,PI,EpsilonPI,UCB,MGFI} <-> bayes_optim.acquisition.acquisition_fun.*
   bogp.EHVI                      <-> bayes_optim.multi_objective.analytic.EHVI (MOBO's criterion; one device pass)
                                  (on a multi-target GaussianProcess, or on a RandomForest fitted on y (N, m))
+  bogp.Constrained               EI / PI / EpsilonPI / MGFI weighted by the probability that modelled constraints hold: the
+                                 h_vals / g_vals the reference's tell() accepts and drops (one device pass, bogp_sweep_constrained)
   bogp.pareto                    Pareto front + cell decomposition of the non-dominated region (numpy)
   bogp.RandomForest              <-> bayes_optim.surrogate.RandomForest        (scikit-learn fits, the device predicts;
                                  bogp.forest: packing, mixed-space sweep; built on first access, sklearn imported lazily)
@@ -24,9 +26,9 @@ __version__ = "0.1.0"
 
 from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto, thompson  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
-from .acquisition import EHVI, EI, MGFI, PI, UCB, EpsilonPI  # noqa: E402,F401
+from .acquisition import EHVI, EI, MGFI, PI, UCB, Constrained, EpsilonPI  # noqa: E402,F401
 from .optim import argmax_restart, batch_argmax, believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
-from .integration import install, uninstall  # noqa: E402,F401
+from .integration import feasible_xopt, install, uninstall  # noqa: E402,F401
 from .lift import Lift  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401
 

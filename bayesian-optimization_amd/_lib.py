@@ -17,6 +17,7 @@ ERR_INVALID, ERR_HIP, ERR_NOT_POSDEF, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_LLF_PO
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_ABSEXP, KERNEL_CUBIC, KERNEL_GENEXP, KERNEL_MATERN_NU = 0, 1, 2, 3, 4, 5, 6, 7
 MODE_NOISELESS, MODE_NOISY, MODE_NOISE_ESTIM = 0, 1, 2
 ACQ_EI, ACQ_EPSILON_PI, ACQ_UCB, ACQ_MGFI = 0, 1, 2, 3
+ACQ_NONE = -1  # BOGP_ACQ_NONE: bogp_sweep_constrained's feasibility-only criterion
 TREND_CONSTANT, TREND_LINEAR, TREND_QUADRATIC = 0, 1, 2
 SELFTEST_PROFILE, SELFTEST_BESSEL_K, SELFTEST_RGAMMA, SELFTEST_BESSEL_K_PAIRS, SELFTEST_MATERN_NU_PAIRS = range(5)
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
@@ -72,6 +73,8 @@ SIGNATURES = {
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_feasibility": (C.c_double, [C.c_double] * 5),
+    "bogp_sweep_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _lp, _dp, _dp, _dp]),
@@ -191,6 +194,12 @@ def _f64(a, shape=None) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def feasibility(mu: float, mse: float, sigma2: float, lo: float, hi: float) -> float:
+    """P(lo <= Y <= hi) for Y ~ N(mu, mse) as the constrained sweep forms it (bogp_feasibility: the indicator under EI's
+    small-variance guard, else the difference of two normal cdfs taken in the tail the interval lies in).  No device is touched."""
+    return float(load().bogp_feasibility(float(mu), float(mse), float(sigma2), float(lo), float(hi)))
 
 
 def grid_cells(Y, ref_point):
@@ -644,6 +653,39 @@ class Engine:
         out = (best, idx)
         if return_values:
             out += (vals,)
+        if return_moments:
+            out += (mu, mse)
+        return out
+
+    def sweep_constrained(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize, lo, hi, k: int = 1, return_values=False,
+                          return_pof=False, return_moments=False):
+        """q feasibility-weighted criteria of the committed multi-target model over the current candidates (bogp_sweep_constrained):
+        target 0 is the objective, target j the constraint feasible in [lo[j - 1], hi[j - 1]] (either side may be infinite); value =
+        criterion on target 0 (EI, EpsilonPI, MGFI; ACQ_NONE: 1) x the product of the constraints' probabilities of feasibility.
+        Returns (best_val (q, k), best_idx (q, k)[, values (q, M)][, pof (M,)][, mu (M, m), mse (M, m)]); rank 0 is the argmax, slots
+        beyond M are (-inf, -1)."""
+        q, k = len(acq), int(k)
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        m = len(lo) + 1
+        best = np.empty((q, k))
+        idx = np.empty((q, k), dtype=np.int64)
+        vals = np.empty((q, self.M)) if return_values else None
+        pof = np.empty(self.M) if return_pof else None
+        mu = np.empty((self.M, m)) if return_moments else None
+        mse = np.empty((self.M, m)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_constrained(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
+                                                     len(lo), _ptr(lo), _ptr(hi), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(vals),
+                                                     _ptr(pof), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_pof:
+            out += (pof,)
         if return_moments:
             out += (mu, mse)
         return out

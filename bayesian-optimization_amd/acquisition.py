@@ -407,3 +407,102 @@ class EHVI:
                 return (vals.reshape(1), dx.reshape(1, -1)) if len(rows) == 1 else (vals.reshape(-1, 1), dx)
         eng.upload_candidates(self.model._check_X(X))
         return self.sweep(return_values=True)[2]
+
+
+class Constrained:
+    """A single-objective criterion weighted by the probability that modelled constraints hold (`bogp_sweep_constrained`): what the
+    reference accepts as `h_vals` / `g_vals` and leaves open (`BaseBO.tell`, base.py:328).  `model` is a device GaussianProcess
+    fitted on y (N, m), m >= 2: column 0 the objective, column k the constraint feasible when lo[k - 1] <= c_k(x) <= hi[k - 1]
+    (default (-inf, 0] each: g <= 0; an equality |h| <= tol is [-tol, tol]).  Per row
+
+        value = fun(x on column 0) * prod_k P(lo_k <= c_k(x) <= hi_k)
+
+    with `fun` one of "EI" | "PI" | "EpsilonPI" | "MGFI" (the non-negative criteria; `par`: `epsilon` or `t`, defaults as in the
+    single-objective classes) or None: the probability of feasibility alone (Gelbart, Snoek, Adams 2014).  "UCB" changes sign
+    -- its product with a probability orders nothing -- and raises ValueError.  `plugin=None` takes the best column-0 value among
+    the training rows whose constraint columns all lie inside their bounds; with no such row the criterion is feasibility-only
+    whatever `fun` says.  The stored plugin is oriented for minimisation, as `ImprovementBased` stores it.
+
+    `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the
+    engine's current candidates as `EHVI.sweep` does.  There is no input gradient (`return_dx=True` raises)."""
+
+    is_constrained = True
+    _IDS = {"EI": _lib.ACQ_EI, "PI": _lib.ACQ_EPSILON_PI, "EpsilonPI": _lib.ACQ_EPSILON_PI, "MGFI": _lib.ACQ_MGFI, None: _lib.ACQ_NONE}
+
+    def __init__(self, model=None, fun="EI", minimize: bool = True, plugin: float = None, lo=None, hi=None, **par):
+        if model is None:
+            raise ValueError("model cannot be None")
+        if _forest.is_forest_model(model):
+            raise NotImplementedError("modelled constraints take a multi-target Gaussian process: a forest model is not served")
+        if fun == "UCB":
+            raise ValueError("UCB changes sign, so its product with a probability of feasibility orders nothing: use EI, PI, "
+                             "EpsilonPI, MGFI or fun=None (feasibility only)")  # fmt: skip
+        if fun not in self._IDS:
+            raise ValueError("fun must be 'EI', 'PI', 'EpsilonPI', 'MGFI' or None, not %r" % (fun,))
+        y = np.asarray(getattr(model, "y", np.zeros((0, 0))), dtype=float)
+        if y.ndim != 2 or y.shape[1] < 2:
+            raise ValueError("modelled constraints need a model fitted on y (N, m) with m >= 2 columns (objective, constraints)")
+        if y.shape[1] > _lib.MAX_TARGETS:
+            raise ValueError("%d columns: at most %d targets (one objective and %d constraints)" % (y.shape[1], _lib.MAX_TARGETS, _lib.MAX_TARGETS - 1))
+        n_con = y.shape[1] - 1
+        lo = np.full(n_con, -np.inf) if lo is None else np.asarray(lo, dtype=float).ravel()
+        hi = np.zeros(n_con) if hi is None else np.asarray(hi, dtype=float).ravel()
+        if len(lo) != n_con or len(hi) != n_con:
+            raise ValueError("lo and hi must hold one bound for each of the %d constraint columns of model.y" % n_con)
+        if np.any(np.isnan(lo)) or np.any(np.isnan(hi)) or np.any(hi < lo):
+            raise ValueError("constraint bounds must not be NaN, and hi >= lo")
+        allowed = {"EI": (), "PI": (), "EpsilonPI": ("epsilon",), "MGFI": ("t",), None: ()}[fun]
+        for name in par:
+            if name not in allowed:
+                raise TypeError("fun=%r takes no parameter %r" % (fun, name))
+        self.model, self.fun, self.minimize = model, fun, bool(minimize)
+        self.lo, self.hi = np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+        self._par = 0.0
+        if fun == "EpsilonPI":
+            self._par = float(par.get("epsilon", 1e-10))
+            assert self._par > 0
+        elif fun == "MGFI":
+            assert par.get("t", 1) > 0
+            self._par = float(min(par.get("t", 1), 22.36))
+        sign = 1.0 if self.minimize else -1.0
+        feasible = np.all((y[:, 1:] >= self.lo) & (y[:, 1:] <= self.hi), axis=1)
+        self.n_feasible = int(feasible.sum())
+        if plugin is not None:
+            self._plugin = sign * float(plugin)
+        elif self.n_feasible:
+            self._plugin = float(np.min(sign * y[feasible, 0]))
+        else:
+            self._plugin = None
+        # without a feasible observation there is nothing to improve on: the probability of feasibility alone
+        self.acq_id = self._IDS[fun] if self._plugin is not None else _lib.ACQ_NONE
+
+    @property
+    def plugin(self):
+        return self._plugin
+
+    @property
+    def feasibility_only(self) -> bool:
+        return self.acq_id == _lib.ACQ_NONE
+
+    def acq_par(self) -> float:
+        return 0.0 if self.feasibility_only else self._par
+
+    def effective_plugin(self) -> float:
+        return 0.0 if self._plugin is None else float(self._plugin)
+
+    def sweep(self, k: int = 1, return_values: bool = False):
+        """The sweep over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
+        if getattr(self.model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        out = self.model.engine.sweep_constrained([(self.acq_id, self.acq_par())], self.effective_plugin(), self.minimize, self.lo, self.hi,
+                                                  k=int(k), return_values=return_values)  # fmt: skip
+        return tuple(a[0] for a in out)
+
+    def __call__(self, X, return_dx: bool = False):
+        if return_dx:
+            raise NotImplementedError("the feasibility-weighted criterion has no input gradient yet (the gradient of the probability of "
+                                      "feasibility is not implemented): use 'sweep' or 'sweep-device[-lhs|-sobol]'")  # fmt: skip
+        if getattr(self.model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        self.model.engine.upload_candidates(self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float))))
+        return self.sweep(return_values=True)[2]

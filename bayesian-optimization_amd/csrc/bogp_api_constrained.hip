@@ -1,0 +1,90 @@
+// bogp_api_constrained.hip -- the C ABI of libbogp.so (include/bogp.h) for modelled constraints: bogp_sweep_constrained, q
+// feasibility-weighted criteria of an m-target model (target 0 the objective, targets 1 .. m - 1 the constraints) over the current
+// candidates, and bogp_feasibility, the factor one constraint contributes, on the host.  The sweep is the chunked sweep of
+// bogp_api_sweep.hip (producer -> contraction per chunk) with k_constrained (kernels_constrained.hip) in place of k_acquisition.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "../../include/bogp.h"
+#include "bogp_device.h"
+#include "bogp_handle.h"
+#include "bogp_internal.h"
+
+using namespace bogp;
+
+extern "C" double bogp_feasibility(double mu, double mse, double sigma2, double lo, double hi) { return feasibility(mu, mse, sigma2, lo, hi); }
+
+extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int n_con,
+                                      const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,
+                                      double* pof_out, double* mu_out, double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_constrained";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set) and modelled constraints have no lifted sweep: call bogp_lift_clear first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
+  const int m = h->n_t;
+  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has %d target(s); an objective and its constraints need 2 .. %d", who, m, BOGP_MAX_TARGETS);
+  if (n_con != m - 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d but the committed model has %d targets (one objective, %d constraints)", who, n_con, m, m - 1);
+  if (q < 1 || q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_Q);
+  if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
+  if (!acq_id || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo, hi, best_val and best_idx must be non-null", who);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  for (int c = 0; c < q; ++c) {
+    const int id = acq_id[c];
+    if (id == BOGP_ACQ_UCB) FAIL(h, BOGP_ERR_INVALID, "%s: criterion %d is UCB, which changes sign: its product with a probability orders nothing (EI, EpsilonPI, MGFI or BOGP_ACQ_NONE)", who, c);
+    if (id != BOGP_ACQ_EI && id != BOGP_ACQ_EPSILON_PI && id != BOGP_ACQ_MGFI && id != BOGP_ACQ_NONE) FAIL(h, BOGP_ERR_INVALID, "%s: unknown acquisition id %d", who, id);
+    if (id == BOGP_ACQ_EPSILON_PI && (!acq_par || !(acq_par[c] >= 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be >= 0 (epsilon = 0 is plain PI)", who, c);
+    if (id == BOGP_ACQ_MGFI && (!acq_par || !(acq_par[c] > 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be > 0 (the reference asserts t > 0)", who, c);
+  }
+  for (int j = 0; j < n_con; ++j) {
+    if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
+    if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  const int64_t M = h->M;
+  int e;
+  if (pof_out && (e = h->dpof_out.ensure(h, (size_t)M))) return e;
+  ConstrainedArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.gamma = h->dgamma_base; ca.ld_gamma = h->Np; ca.N = h->N; ca.m = m;
+  for (int t = 0; t < m; ++t) ca.sigma2[t] = h->sigma2_t[t];
+  for (int j = 0; j < n_con; ++j) { ca.lo[j + 1] = lo[j]; ca.hi[j + 1] = hi[j]; }
+  ca.q = q;
+  for (int c = 0; c < q; ++c) { ca.acq_id[c] = acq_id[c]; ca.acq_par[c] = acq_par ? acq_par[c] : 0.0; }
+  ca.plugin = plugin; ca.minimize = minimize; ca.pof_out = pof_out ? h->dpof_out.ptr : nullptr;
+  invalidate_sweep_results(h);  // dbest_* are overwritten and hold no single-target winners afterwards
+  SweepRequest rq;  // (q sizes the chunk loop's block records and dacq_out; the criteria themselves travel in ca)
+  rq.want_out = mu_out || mse_out; rq.want_acq_out = true; rq.q = q; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin;
+  rq.minimize = minimize; rq.cn = &ca;
+  int rc = run_sweep(h, rq);
+  if (rc) return rc;
+  if (k == 1) {  // the chunk loop's own argmax
+    HIPCHK(h, hipMemcpy(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost));
+  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks q criteria
+    const int64_t nblk = (M + 255) / 256;
+    if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
+    if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
+    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < q * k; ++i)
+    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
+      best_val[i] = -INFINITY;
+      best_idx[i] = -1;
+    }
+  if (acq_out) HIPCHK(h, hipMemcpy(acq_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost));
+  if (pof_out) HIPCHK(h, hipMemcpy(pof_out, h->dpof_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+  if (mu_out) HIPCHK(h, hipMemcpy(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
+  if (mse_out) HIPCHK(h, hipMemcpy(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
+  return BOGP_OK;
+}

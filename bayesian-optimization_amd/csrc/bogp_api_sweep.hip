@@ -763,6 +763,13 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
         ea.ehvi_out = h->dacq_out; ea.mu_out = rq.want_out ? h->dmu_out : nullptr; ea.mse_out = rq.want_out ? h->dmse_out : nullptr;
         ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = cx.blk_offset;
         HIPCHK(h, launch_ehvi(ea, st));
+      } else if (rq.cn) {  // ... or the q feasibility-weighted criteria of the m-target posterior (kernels_constrained.hip)
+        ConstrainedArgs cn = *rq.cn;
+        cn.rT = h->drT[b]; cn.ss_part = h->dss_part; cn.w_part = h->dw_part[b]; cn.S = S; cn.nJ = cx.nJ_main; cn.Mc = Mc;
+        cn.mcount = mcount; cn.m0 = m0; cn.beta = h->beta; cn.G = h->G; cn.estimate_trend = h->estimate_trend;
+        cn.acq_out = h->dacq_out; cn.M = M; cn.mu_out = rq.want_out ? h->dmu_out : nullptr; cn.mse_out = rq.want_out ? h->dmse_out : nullptr;
+        cn.blk_val = h->dblk_val; cn.blk_idx = h->dblk_idx; cn.blk_offset = cx.blk_offset; cn.nblk_total = cx.nblk_total;
+        HIPCHK(h, launch_constrained(cn, st));
       } else {
         HIPCHK(h, launch_acquisition(aa, st));
       }
@@ -928,10 +935,11 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0; h->timing_onepass = false;
   h->b32_rows = h->b32_kept = h->b32_last_rows = 0; h->b32_fallbacks = 0;
   int e;
-  // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- takes neither: it always runs the chunked path below); nothing
-  // to overlap a lazy upload with: the whole upload first (one launch reads every candidate)
-  const bool small_batch = !rq.eh && M <= 32 && h->p == 1;
-  if (small_batch || (!rq.eh && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
+  // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- and bogp_sweep_constrained -- cn non-null -- take neither: they
+  // always run the chunked path below); nothing to overlap a lazy upload with: the whole upload first (one launch reads every candidate)
+  const bool multi = rq.eh || rq.cn;
+  const bool small_batch = !multi && M <= 32 && h->p == 1;
+  if (small_batch || (!multi && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
     if ((e = lazy_finish(h))) return e;
     return small_batch ? sweep_small_batch(h, rq) : sweep_one_launch(h, rq);
   }
@@ -961,15 +969,15 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   cx.overlap = nchunk > 1 && getenv("BOGP_OVERLAP") && atoi(getenv("BOGP_OVERLAP")) == 1;
   cx.stP = cx.overlap ? h->stream2 : cx.st;
   // Pruned sweep (kernels_prune.hip): only the winners leave this call, so a row whose criteria cannot reach the best
-  // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI -- runs as ever.
-  cx.prune = h->prune_mode != 0 && rq.need_var && q > 0 && !rq.want_out && !rq.want_acq_out && !rq.eh && h->p == 1 && !cx.vx_model && !cx.overlap;
+  // values found so far even with ss = 0 skips the contraction.  Everything else -- value outputs, polynomial bases, EHVI, modelled constraints -- runs as ever.
+  cx.prune = h->prune_mode != 0 && rq.need_var && q > 0 && !rq.want_out && !rq.want_acq_out && !multi && h->p == 1 && !cx.vx_model && !cx.overlap;
   // one pass: every candidate resident and a producer that exists without its store
   cx.onepass = cx.prune && h->prune_mode == 1 && nchunk > 1 && !h->hXs_lazy && corr_chunk_without_store(h->kernel, 0, h->dXnorm != nullptr);
   // ... bounded in FP32 first where the kernel's profile has a bounded slope
   cx.bound32 = cx.onepass && h->prune_bound32 != 0 && bound32_supported(h->kernel, h->d);
   if (cx.bound32 && (h->b32_gen != h->commit_gen || h->b32_target != h->target) && (e = bound32_prepare(h))) return e;  // (another target since the commit)
   if ((e = sweep_workspace(h, cx))) return e;
-  if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * (rq.eh ? rq.eh->m : 1) : 0, rq.want_acq_out))) return e;
+  if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * rq.targets() : 0, rq.want_acq_out))) return e;
   // the chunks' events, the two-stream mode's begin event, the pilot's pair (pruned sweep)
   for (size_t i = 0; i <= (size_t)(nchunk * EPC + 2); ++i)
     if (!h->ev.at(i)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");

@@ -320,6 +320,18 @@ __host__ __device__ __forceinline__ double acq_value(int id, double par, double 
   }
 }
 
+// Probability that a Gaussian target with the posterior (mu, mse) lies in [lo, hi] (either bound may be infinite): the factor a modelled
+// constraint contributes to a feasibility-weighted criterion (k_constrained).  sd = sqrt(mse) without a floor; under EI's small-variance
+// guard (sd / sqrt(sigma2) < 1e-6, acquisition_fun.py:153-176) the indicator of lo <= mu <= hi.  The difference is taken in the tail the
+// interval lies in -- Phi(-za) - Phi(-zb) above the mean, Phi(zb) - Phi(za) otherwise -- so that an interval in the upper tail does not
+// cancel against 1.  ndtr(-inf) = 0 and ndtr(+inf) = 1 exactly: an infinite side drops out, two give 1.0; lo == hi gives 0.0.
+__host__ __device__ __forceinline__ double feasibility(double mu, double mse, double sigma2, double lo, double hi) {
+  const double sd = sqrt(mse);
+  if (sd / sqrt(sigma2) < 1e-6) return (lo <= mu && mu <= hi) ? 1.0 : 0.0;
+  const double za = (lo - mu) / sd, zb = (hi - mu) / sd;
+  return za > 0 ? ndtr(-za) - ndtr(-zb) : ndtr(zb) - ndtr(za);
+}
+
 // Upper bound of acq_value(id, par, y_hat, sd, ...) over sd in [0, sd_ub], guard branches (which return 0) included: what the pruned
 // sweep (kernels_prune.hip) compares with the best value found so far.  EI is non-decreasing in sd; UCB is linear in it; EpsilonPI is
 // ndtr(num / sd) with num = plugin - coef y_hat, i.e. 1 at most for num > 0, non-decreasing in sd for num < 0, and possibly NaN
@@ -423,6 +435,53 @@ __device__ __forceinline__ void posterior_of_sums(double rgamma, double wr, doub
   }
   mse = (1.0 - ss + u2) * sigma2;
   if (mse < 0.0) mse = 0.0;
+}
+
+// posterior of row i of a chunk for the MT targets of a multi-target model (gpr.py:490, 496-510 with n_targets > 1; constant basis):
+//   mu_k = beta + r . gamma_k, one fma chain over n = 0 .. N - 1 from 0 per target (the bits do not depend on the chunk size),
+//   MSE_k = max(0, (1 - ss + u^2) sigma2_k), ss the sum of the nJ column groups of |L^-1 r|^2, u = (w.r - 1) / G under ordinary kriging.
+// Shared by k_ehvi and k_constrained, so that both leave the same bits for the same model and rows.  AHEAD > 1: the loads of AHEAD rows are
+// issued before their fmas -- a lane streams its column alone, so the loads in flight are what hides the memory latency (k_constrained at
+// N = 2048, 1e6 rows: 12.1 -> 2.9 ms with 8, profiles/constrained_sweep.txt); the fmas keep the order n = 0 .. N - 1, so the bits are
+// those of the plain loop (AHEAD = 1).
+template <int MT, int AHEAD = 1>
+__device__ __forceinline__ void multi_target_moments(const double* rT, const double* gamma, int ld_gamma, int N, const double* ss_part, int nJ,
+                                                     const double* w_part, int S, int64_t Mc, int64_t i, double beta, double G, int estimate_trend,
+                                                     const double* sigma2, double (&mu)[MT], double (&mse)[MT]) {
+#pragma unroll
+  for (int k = 0; k < MT; ++k) mu[k] = 0.0;
+  int n = 0;
+  if constexpr (AHEAD > 1) {
+    for (; n + AHEAD <= N; n += AHEAD) {
+      double r[AHEAD];
+#pragma unroll
+      for (int u = 0; u < AHEAD; ++u) r[u] = rT[(size_t)(n + u) * Mc + i];
+#pragma unroll
+      for (int u = 0; u < AHEAD; ++u) {
+#pragma unroll
+        for (int k = 0; k < MT; ++k) mu[k] = fma(r[u], gamma[(size_t)k * ld_gamma + n + u], mu[k]);
+      }
+    }
+  }
+  for (; n < N; ++n) {
+    const double r = rT[(size_t)n * Mc + i];
+#pragma unroll
+    for (int k = 0; k < MT; ++k) mu[k] = fma(r, gamma[(size_t)k * ld_gamma + n], mu[k]);
+  }
+  double ss = 0.0, wd = 0.0;
+  for (int j = 0; j < nJ; ++j) ss += ss_part[(size_t)j * Mc + i];
+  double u2 = 0.0;
+  if (estimate_trend) {
+    for (int s = 0; s < S; ++s) wd += w_part[(size_t)s * Mc + i];
+    const double u = (wd - 1.0) / G;
+    u2 = u * u;
+  }
+#pragma unroll
+  for (int k = 0; k < MT; ++k) {
+    mu[k] += beta;
+    mse[k] = (1.0 - ss + u2) * sigma2[k];
+    if (mse[k] < 0.0) mse[k] = 0.0;
+  }
 }
 
 // argmax ordering identical to np.argmax over a 1-D float64 array: first maximal element, where a NaN

@@ -21,7 +21,8 @@ std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: t
 int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, int q, const int* acq_id, const double* acq_par,
                     double plugin, int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq);
 // bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
-// m-target EHVI of bogp_api_ehvi.hip on the chunked path), and the reset of the winners a sweep left on the device
+// m-target EHVI of bogp_api_ehvi.hip, or -- cn non-null -- the feasibility-weighted criteria of bogp_api_constrained.hip, both on the
+// chunked path), and the reset of the winners a sweep left on the device
 struct SweepRequest {
   bool want_out = false, want_acq_out = false;  // mu / MSE of every candidate into dmu_out / dmse_out (EHVI: M x m moments); the q x M values into dacq_out
   bool need_var = true, sync = true;            // false: the contraction is skipped (predict without eval_MSE); false: queued, not waited for
@@ -30,6 +31,8 @@ struct SweepRequest {
   const double* acq_par = nullptr;  // (may stay null: EI takes no parameter)
   double plugin = 0.0;
   const EhviArgs* eh = nullptr;
+  const ConstrainedArgs* cn = nullptr;  // (q, acq_id, acq_par, plugin, minimize above are the criteria it weights)
+  int targets() const { return eh ? eh->m : cn ? cn->m : 1; }  // moments per candidate in dmu_out / dmse_out
 };
 int run_sweep(bogp_handle* h, const SweepRequest& rq);
 void invalidate_sweep_results(bogp_handle* h);
@@ -225,6 +228,7 @@ struct bogp_handle {
   bogp::DevBuf<double> dtopk_val;  // [q][k] winners of bogp_sweep_topk (device-resident between its passes)
   bogp::DevBuf<int64_t> dtopk_idx;
   bogp::DevBuf<double> dehvi_cells;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
+  bogp::DevBuf<double> dpof_out;     // bogp_sweep_constrained: [M] probability of feasibility (pof_out requested)
   // host copy of the cells bogp_point_eval_ehvi / bogp_polish_ehvi left in dehvi_cells ([lower | upper], ehvi_host_C x ehvi_host_m): a call
   // with the same cells skips the upload.  Empty <=> unknown: every other writer of dehvi_cells clears it (ehvi_cells_forget)
   std::vector<double> h_ehvi_cells;

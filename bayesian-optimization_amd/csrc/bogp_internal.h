@@ -231,6 +231,37 @@ struct EhviArgs {
 };
 hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
 
+// q feasibility-weighted criteria of an m-target model over one chunk (kernels_constrained.hip): target 0 is the objective, targets
+// 1 .. m - 1 are constraints feasible in [lo_k, hi_k]; replaces AcqArgs / k_acquisition in the chunk loop of bogp_sweep_constrained
+struct ConstrainedArgs {
+  const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
+  const double* gamma;    // [m][ld_gamma] the targets' gamma columns
+  int ld_gamma, N;        // Np; training points summed over
+  const double* ss_part;  // [nJ][Mc]
+  const double* w_part;   // [S][Mc] (constant trend with estimate_trend only)
+  int S, nJ;
+  int64_t Mc, mcount, m0;
+  double beta, G;
+  int estimate_trend;
+  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
+  double sigma2[8];       // per target
+  double lo[8], hi[8];    // per target; entry 0 is not read
+  int q;
+  int acq_id[64];         // BOGP_ACQ_EI / EPSILON_PI / MGFI, or BOGP_ACQ_NONE: the probability of feasibility alone
+  double acq_par[64];
+  double plugin;
+  int minimize;
+  double* acq_out;        // [q][M] (global index m0 + i)
+  int64_t M;              // row stride of acq_out
+  double* pof_out;        // [M] or null
+  double* mu_out;         // [M][m] or null
+  double* mse_out;        // [M][m] or null
+  double* blk_val;        // [q][nblk_total] per-block partial argmax
+  int64_t* blk_idx;
+  int64_t blk_offset, nblk_total;
+};
+hipError_t launch_constrained(const ConstrainedArgs& a, hipStream_t st);
+
 // one Kriging-believer pass over a chunk (kernels_believer.hip): the rank-one downdate of the running variance by the believed point p,
 // c(x) = (k(x, p) - r(x) . a + u(x) u(p) - sum_k c_k(x) c_k(p)) / sqrt(pivot), s(x) -= sigma2 c(x)^2, and -- for the pass in front of a
 // step -- that step's criterion on (mu, max(0, s)) with the per-block argmax records k_argmax_final reads (one record per 64 rows)

@@ -25,33 +25,15 @@ __global__ __launch_bounds__(256) void k_ehvi(EhviArgs a) {
   double v = -INFINITY;
   int64_t idx = INT64_MAX;
   if (valid) {
-    double mu[MT];
-#pragma unroll
-    for (int k = 0; k < MT; ++k) mu[k] = 0.0;
-    // one fixed order over n per lane: the bits do not depend on the chunk size
-    for (int n = 0; n < a.N; ++n) {
-      const double r = a.rT[(size_t)n * a.Mc + i];
-#pragma unroll
-      for (int k = 0; k < MT; ++k) mu[k] = fma(r, a.gamma[(size_t)k * a.ld_gamma + n], mu[k]);
-    }
-    double ss = 0.0, wd = 0.0;
-    for (int j = 0; j < a.nJ; ++j) ss += a.ss_part[(size_t)j * a.Mc + i];
-    double u2 = 0.0;
-    if (a.estimate_trend) {
-      for (int s = 0; s < a.S; ++s) wd += a.w_part[(size_t)s * a.Mc + i];
-      const double u = (wd - 1.0) / a.G;
-      u2 = u * u;
-    }
+    double mu[MT], mse[MT];  // (bogp_device.h: shared with k_constrained)
+    multi_target_moments<MT>(a.rT, a.gamma, a.ld_gamma, a.N, a.ss_part, a.nJ, a.w_part, a.S, a.Mc, i, a.beta, a.G, a.estimate_trend, a.sigma2, mu, mse);
     const int64_t g = a.m0 + i;
     double sd[MT];
 #pragma unroll
     for (int k = 0; k < MT; ++k) {
-      mu[k] += a.beta;
-      double mse = (1.0 - ss + u2) * a.sigma2[k];
-      if (mse < 0.0) mse = 0.0;
       if (a.mu_out) a.mu_out[(size_t)g * MT + k] = mu[k];
-      if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse;
-      sd[k] = sqrt(fmax(mse, 1e-9));
+      if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse[k];
+      sd[k] = sqrt(fmax(mse[k], 1e-9));
     }
     v = ehvi_cells<MT>(a.lower, a.upper, a.C, mu, sd);  // (bogp_device.h: shared with k_forest_ehvi)
     idx = g;

@@ -6,8 +6,12 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
                                                                              hands everything else to the original)
   bayes_optim.{base,bayes_opt,extension}.AcquisitionFunction -> a per-MODEL dispatching namespace (below)
   ParallelBO._batch_arg_max_acquisition         -> fused_batch_arg_max_acquisition
-  BaseBO._create_acquisition                    -> forest_create_acquisition (this package's criteria for a RandomForest model
-                                                   under "sweep" / "sweep-device"; the original otherwise, "MIES" included)
+  BaseBO._create_acquisition                    -> constrained_create_acquisition -> forest_create_acquisition (this package's criteria
+                                                   for a RandomForest model under "sweep" / "sweep-device"; the original otherwise,
+                                                   "MIES" included; under install(expensive_constraints=True) and with stored
+                                                   constraint values: bogp.Constrained)
+  BaseBO.tell, BaseBO.update_model              -> constrained_tell, constrained_update_model (the originals unless
+                                                   install(expensive_constraints=True) AND the tell carries h_vals / g_vals)
   MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
                                                    under the sweep family; the reference's EHVI otherwise)
   bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess, bayes_optim.extension.GaussianProcess
@@ -96,14 +100,16 @@ def fused_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=N
     design = optim.DEVICE_DESIGNS.get(optimizer)
     k = int(min(32, n_point + 8))  # fall-backs: at most n_point - 1 taken by earlier criteria + a few history hits
     xs, fs = optim.batch_argmax(crits, kw["search_space"], int(budget or kw["eval_budget"]), history=_history_of(self), k=k,
-                                design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"), **_strategy_of(masks, kw))  # fmt: skip
+                                design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"), **_strategy_of(masks, kw, crits))  # fmt: skip
     return tuple(xs), tuple(fs)
 
 
-def _strategy_of(masks, kw) -> dict:
+def _strategy_of(masks, kw, crits=()) -> dict:
     """The `strategy` keyword of the fused step's `batch_argmax` call: none under the default, and none for what the believer does
-    not serve -- fixed variables and constraints stay on the top-k strategy, which serves them."""
+    not serve -- fixed variables, constraints and modelled constraints (`bogp.Constrained`) stay on the top-k strategy, which serves them."""
     if _BATCH.get("strategy", "topk") == "topk" or masks is not None or kw.get("h") is not None or kw.get("g") is not None:
+        return {}
+    if any(optim.is_constrained(c) for c in crits):
         return {}
     return {"strategy": _BATCH["strategy"]}
 
@@ -113,6 +119,7 @@ _REROUTE: dict = {}
 _BATCH: dict = {}  # install(batch_strategy=...): how the fused ParallelBO step makes its q points differ ("topk" when empty)
 _EHVI: dict = {}  # install(ehvi_gradient=True): MOBO's polish optimisers run on bogp.EHVI(input_gradient=True) (empty: the original)
 _SURROGATE_DEFAULTS: dict = {}  # keyword defaults install() gives the device GaussianProcess (e.g. restart_batch)
+_CONSTRAINTS: dict = {}  # install(expensive_constraints=True): {"tol": equality_tol}; empty: tell() drops h_vals / g_vals as the reference does
 
 
 def _effective(optimizer, eval_budget):
@@ -185,6 +192,143 @@ def forest_create_acquisition(self, fun=None, par=None, return_dx=False, fixed=N
     criterion = getattr(acquisition, name)(**par)
     return _ORIGINAL["base_partial_argument"](func=functools.partial(criterion, return_dx=return_dx), var_name=self.search_space.var_name,
                                               fixed=fixed, reduce_output=return_dx)  # fmt: skip
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# install(expensive_constraints=True): the h_vals / g_vals of tell() become columns of the surrogate
+# ----------------------------------------------------------------------------------------------------------------------
+_CONSTRAINED_FUNS = ("EI", "PI", "EpsilonPI", "MGFI")
+
+
+def _constraint_columns(vals, n, what):
+    """`vals` of a tell() of n points as an (n, k) float array: a flat list of n numbers is one constraint."""
+    a = np.asarray(vals, dtype=float)
+    if a.ndim == 1 and len(a) == n:
+        return a.reshape(n, 1)
+    if a.ndim == 2 and a.shape[0] == n and a.shape[1] >= 1:
+        return a
+    raise ValueError("%s must hold one value, or one list of values, for each of the %d points told (got shape %s)" % (what, n, a.shape))
+
+
+def constrained_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, warm_start=False):
+    """`BaseBO.tell` under `install(expensive_constraints=True)` (the reference drops `h_vals` / `g_vals`, base.py:328): for a `BO` /
+    `ParallelBO` (or a subclass) with a device GP the values are kept, row for row with `self.data`, in `self._bogp_constraints` (the
+    g columns first, then the h columns), and the original `tell` -- whose `update_model` then fits objective and constraints
+    together -- runs.  ValueError: values missing after a tell() that had them, or given after one that had none; a changed number
+    of constraints; a non-finite value.  Another model (a forest) is refused by name."""
+    given = h_vals is not None or g_vals is not None
+    if not _CONSTRAINTS or (not given and getattr(self, "_bogp_constraints", None) is None):
+        return _ORIGINAL["tell"](self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
+    if not is_device_model(getattr(self, "model", None)):
+        raise NotImplementedError("expensive constraints (h_vals / g_vals) are modelled by a device GaussianProcess: the %s model of this "
+                                  "driver is not served" % type(getattr(self, "model", None)).__name__)  # fmt: skip
+    if getattr(self, "n_obj", 1) != 1:
+        raise NotImplementedError("expensive constraints (h_vals / g_vals) are served for single-objective drivers (BO, ParallelBO), not for %d objectives" % self.n_obj)
+    stored = getattr(self, "_bogp_constraints", None)
+    if not given:
+        raise ValueError("this tell() carries no h_vals / g_vals, but earlier ones did: every point needs its constraint values")
+    if stored is None and hasattr(self, "data") and len(self.data) > 0:
+        raise ValueError("this tell() carries h_vals / g_vals, but %d points were told without them: every point needs its constraint values" % len(self.data))
+    n = len(X)
+    g = np.zeros((n, 0)) if g_vals is None else _constraint_columns(g_vals, n, "g_vals")
+    h = np.zeros((n, 0)) if h_vals is None else _constraint_columns(h_vals, n, "h_vals")
+    counts = (g.shape[1], h.shape[1])
+    if stored is not None and counts != self._bogp_constraint_counts:
+        raise ValueError("this tell() carries %d g and %d h values a point, earlier ones %d and %d" % (counts + tuple(self._bogp_constraint_counts)))
+    fitness = np.asarray(func_vals, dtype=float).ravel()
+    keep = ~(np.isnan(fitness) | np.isinf(fitness))  # the rows post_eval_check keeps (base.py:413-421)
+    rows = np.hstack([g, h])[keep]
+    if not np.all(np.isfinite(rows)):
+        raise ValueError("h_vals / g_vals hold a non-finite value: a modelled constraint needs a number for every evaluated point")
+    before = (stored, getattr(self, "_bogp_constraint_counts", None))
+    self._bogp_constraints = rows if stored is None else np.vstack([stored, rows])
+    self._bogp_constraint_counts = counts
+    try:
+        return _ORIGINAL["tell"](self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
+    except BaseException:
+        if not hasattr(self, "data") or len(self.data) != len(self._bogp_constraints):  # the points did not arrive: nor do their values
+            self._bogp_constraints, self._bogp_constraint_counts = before
+        raise
+
+
+def refusing_mobo_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, warm_start=False):
+    """`BaseMOBO.tell` under `install(expensive_constraints=True)`: constraint values are refused by name, everything else is the original."""
+    if _CONSTRAINTS and (h_vals is not None or g_vals is not None):
+        raise NotImplementedError("expensive constraints (h_vals / g_vals) are served for single-objective drivers (BO, ParallelBO), "
+                                  "not for the multi-objective MOBO")  # fmt: skip
+    return _ORIGINAL["mobo_tell"](self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
+
+
+def constrained_update_model(self):
+    """`BaseBO.update_model` (base.py:423-446) with stored constraint values: column 0 is the reference's standardised fitness (fmin,
+    fmax, frange as there), each constraint column is divided by its standard deviation (left as is where that is 0) and never
+    shifted -- its boundary stays at 0, and the fixed trend beta = 0 is the prior "undecided" --, and the model is fitted on
+    Y (N, 1 + n_g + n_h).  Without stored values: the original."""
+    C = getattr(self, "_bogp_constraints", None)
+    if not _CONSTRAINTS or C is None:
+        return _ORIGINAL["update_model"](self)
+    rbase = _ORIGINAL["mods"][1]
+    data = self.data
+    fitness = np.asarray(data.fitness, dtype=float)
+    if len(C) != len(fitness):
+        raise ValueError("%d points hold constraint values, %d are stored in data" % (len(C), len(fitness)))
+    _std = np.std(fitness)
+    if len(fitness) > 5 and np.isclose(_std, 0):
+        raise rbase.FlatFitnessError()
+    fitness_ = fitness if np.isclose(_std, 0) else (fitness - np.mean(fitness)) / np.std(fitness)
+    self.fmin, self.fmax = np.min(fitness_), np.max(fitness_)
+    self.frange = self.fmax - self.fmin
+    std = np.std(C, axis=0)
+    self._bogp_constraint_scale = np.where(np.isclose(std, 0), 1.0, std)
+    Y = np.column_stack([fitness_.reshape(-1, 1), C / self._bogp_constraint_scale])
+    self.model.fit(data, Y)
+    fitness_hat = np.asarray(self.model.predict(data)).reshape(len(fitness_), -1)[:, 0]
+    r2 = rbase.r2_score(fitness_, fitness_hat)
+    MAPE = rbase.mean_absolute_percentage_error(fitness_, fitness_hat)
+    self.logger.info(f"model r2: {r2}, MAPE: {MAPE}")
+
+
+def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fixed=None):
+    """`BaseBO._create_acquisition` in front of `forest_create_acquisition`: with stored constraint values the criterion is
+    `bogp.Constrained` -- (-inf, 0] for the g columns, [-tol, tol] / std for the h columns (tol = `install(equality_tol=)`), the plugin
+    the best FEASIBLE observation instead of the fmin / fmax `BO._create_acquisition` passes.  UCB raises ValueError; an inner optimiser
+    outside the sweep family raises NotImplementedError instead of dropping the constraints."""
+    C = getattr(self, "_bogp_constraints", None)
+    if not _CONSTRAINTS or C is None or not is_device_model(getattr(self, "model", None)):
+        return forest_create_acquisition(self, fun=fun, par=par, return_dx=return_dx, fixed=fixed)
+    name = fun if fun is not None else getattr(self, "_acquisition_fun", None)
+    if name not in _CONSTRAINED_FUNS:
+        raise ValueError("acquisition_fun=%r under expensive constraints: the feasibility-weighted criterion takes EI, PI, EpsilonPI or "
+                         "MGFI (UCB changes sign, so its product with a probability orders nothing)" % (name,))  # fmt: skip
+    optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
+    if optimizer not in _SWEEPS:
+        raise NotImplementedError("optimizer=%r under expensive constraints: the feasibility-weighted criterion is served by the sweep "
+                                  "family only %s; the constraint values are not dropped silently" % (optimizer, _SWEEPS))  # fmt: skip
+    par = dict(par if par is not None else self._acquisition_par)
+    for k in ("plugin", "model", "minimize"):
+        par.pop(k, None)
+    n_g, n_h = self._bogp_constraint_counts
+    tol = _CONSTRAINTS["tol"] / np.asarray(self._bogp_constraint_scale, dtype=float)[n_g:]
+    lo, hi = np.r_[np.full(n_g, -np.inf), -tol], np.r_[np.zeros(n_g), tol]
+    criterion = acquisition.Constrained(model=self.model, fun=name, minimize=self.minimize, lo=lo, hi=hi, **par)
+    return _ORIGINAL["base_partial_argument"](func=functools.partial(criterion, return_dx=return_dx), var_name=self.search_space.var_name,
+                                              fixed=fixed, reduce_output=return_dx)  # fmt: skip
+
+
+def feasible_xopt(bo):
+    """The best observed point of `bo` whose stored constraint values are all feasible (g <= 0, |h| <= `install(equality_tol=)`), as a row
+    of `bo.data`, or None when there is none (or nothing stored).  The reference's `xopt` ignores constraint values and is untouched."""
+    C = getattr(bo, "_bogp_constraints", None)
+    if C is None or not hasattr(bo, "data") or len(C) != len(bo.data):
+        return None
+    n_g, _ = bo._bogp_constraint_counts
+    tol = _CONSTRAINTS.get("tol", 0.1)
+    ok = np.all(C[:, :n_g] <= 0, axis=1) & np.all(np.abs(C[:, n_g:]) <= tol, axis=1)
+    if not ok.any():
+        return None
+    f = np.asarray(bo.data.fitness, dtype=float)
+    rows = np.flatnonzero(ok)
+    return bo.data[int(rows[np.argmin(f[rows]) if bo.minimize else np.argmax(f[rows])])]
 
 
 def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=100, n_restart=10, wait_iter=3,
@@ -379,7 +523,8 @@ def _dispatching_surrogate(host_cls):
 
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
-            restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False):
+            restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
+            equality_tol: float = 0.1):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -407,7 +552,19 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `ehvi_gradient=True` (an extension: the reference's EHVI has no gradient): the reference's `MOBO` with a device GP on a
     continuous space runs "BFGS", "sweep-BFGS" and "sweep-device-BFGS" on `bogp.EHVI(input_gradient=True)` -- the closed-form
     input gradient of `bogp_point_eval_ehvi` and the lock-step polish `bogp_polish_ehvi`.  Without it `MOBO` with those
-    optimisers runs the original."""
+    optimisers runs the original.
+
+    `expensive_constraints=True` (an extension: the reference's `tell` accepts `h_vals` / `g_vals` and drops them, base.py:328): a `BO` /
+    `ParallelBO` with a device GP keeps them (`constrained_tell`), fits objective and constraints as one multi-target model
+    (`constrained_update_model`) and maximises `bogp.Constrained` -- EI / PI / EpsilonPI / MGFI times the probability that g <= 0 and
+    |h| <= `equality_tol` (the reference's own equality threshold, `dynamic_penalty`, utils.py:280) -- under the sweep family
+    (`constrained_create_acquisition`); `bogp.feasible_xopt(bo)` is the best feasible observation.  Off (the default): nothing of
+    this is patched in effect and `tell` drops the values as before."""
+    _CONSTRAINTS.clear()
+    if expensive_constraints:
+        if not (float(equality_tol) >= 0):
+            raise ValueError("equality_tol must be >= 0")
+        _CONSTRAINTS["tol"] = float(equality_tol)
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()
@@ -450,7 +607,12 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
                      surrogate=bool(surrogate), mobo_cls=None, ext=None)  # fmt: skip
     rbase.argmax_restart = routed_argmax_restart
     _ORIGINAL.update(create=rbase.BaseBO.__dict__["_create_acquisition"], base_cls=rbase.BaseBO, base_partial_argument=rbase.partial_argument)
-    rbase.BaseBO._create_acquisition = forest_create_acquisition
+    rbase.BaseBO._create_acquisition = constrained_create_acquisition  # (hands on to forest_create_acquisition)
+    _ORIGINAL.update(tell=rbase.BaseBO.__dict__["tell"], update_model=rbase.BaseBO.__dict__["update_model"])
+    rbase.BaseBO.tell, rbase.BaseBO.update_model = constrained_tell, constrained_update_model
+    if rmobo is not None and "tell" in getattr(rmobo, "BaseMOBO", type("", (), {})).__dict__:
+        _ORIGINAL.update(mobo_tell_cls=rmobo.BaseMOBO, mobo_tell=rmobo.BaseMOBO.__dict__["tell"])
+        rmobo.BaseMOBO.tell = refusing_mobo_tell
     if rmobo is not None and hasattr(rmobo, "MOBO"):
         _ORIGINAL.update(mobo_cls=rmobo.MOBO, mobo=rmobo.MOBO.__dict__["_create_acquisition"], partial_argument=rmobo.partial_argument)
         rmobo.MOBO._create_acquisition = mobo_create_acquisition
@@ -477,6 +639,9 @@ def uninstall():
     pkg, rbase, ropt, rsur = _ORIGINAL["mods"]
     rbase.argmax_restart = _ORIGINAL["argmax"]
     _ORIGINAL["base_cls"]._create_acquisition = _ORIGINAL["create"]
+    _ORIGINAL["base_cls"].tell, _ORIGINAL["base_cls"].update_model = _ORIGINAL["tell"], _ORIGINAL["update_model"]
+    if _ORIGINAL.get("mobo_tell_cls") is not None:
+        _ORIGINAL["mobo_tell_cls"].tell = _ORIGINAL["mobo_tell"]
     for m in _ORIGINAL["acq_holders"]:
         m.AcquisitionFunction = _ORIGINAL["acq"]
     ropt.ParallelBO._batch_arg_max_acquisition = _ORIGINAL["batch"]
@@ -493,4 +658,5 @@ def uninstall():
     _REROUTE.clear()
     _BATCH.clear()
     _EHVI.clear()
+    _CONSTRAINTS.clear()
     _SURROGATE_DEFAULTS.clear()

@@ -173,12 +173,45 @@ def _ehvi_of(criteria: Sequence, eng, group=None):
     return criteria[0]
 
 
+def is_constrained(criterion) -> bool:
+    """True for `acquisition.Constrained` (a criterion weighted by the probability that modelled constraints hold: its sweep is
+    `bogp_sweep_constrained` on a multi-target model, not `bogp_sweep`)."""
+    return bool(getattr(criterion, "is_constrained", False))
+
+
+def _constrained_of(criteria: Sequence, eng, group=None):
+    """The first of the `Constrained` criteria a sweep serves together, or None when none of them is one.  They share one call of
+    `bogp_sweep_constrained`, hence model, bounds, plugin and direction; a list that mixes them with other criteria is refused."""
+    flags = [is_constrained(c) for c in criteria]
+    if not any(flags):
+        return None
+    if not all(flags):
+        raise ValueError("feasibility-weighted criteria (bogp.Constrained) cannot share a sweep with other criteria")
+    c0 = criteria[0]
+    for c in criteria[1:]:
+        if (c.model is not c0.model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin()
+                or not np.array_equal(c.lo, c0.lo) or not np.array_equal(c.hi, c0.hi)):  # fmt: skip
+            raise ValueError("Constrained criteria sharing one sweep must share model, bounds, plugin and minimize")
+    if engine_rank_world(eng, group)[1] > 1:
+        raise NotImplementedError("the constrained sweep (bogp.Constrained) runs on one rank (no multi-rank exchange of its winners)")
+    return c0
+
+
+def _constrained_topk(criteria: Sequence, k: int):
+    """(values (q, k), local indices (q, k)) of q `Constrained` criteria over the engine's current candidates, in one call."""
+    c0 = criteria[0]
+    return c0.model.engine.sweep_constrained([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, c0.lo, c0.hi,
+                                             k=int(k))[:2]  # fmt: skip
+
+
 def _lifted_topk(criteria: Sequence, eng, lift: Lift, k: int, group=None):
     """The k best rows per criterion of the engine's current candidates under `lift` (`bogp_lift_sweep_topk`): rows whose
     lifted point leaves the original box compete with their penalty (extension.py:62-86).  The lift is taken off the engine
     again before this returns, whatever happens: a later plain sweep never sees it."""
     if any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
+    if any(is_constrained(c) for c in criteria):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not modelled constraints (bogp.Constrained)")
     if any(_forest.is_forest_model(c.model) for c in criteria):
         raise NotImplementedError("a lifted sweep (PCA-BO) serves a Gaussian process model, not a forest")
     if engine_rank_world(eng, group)[1] > 1:
@@ -215,6 +248,7 @@ def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, grou
     if getattr(model, "_committed_par", None) is None:
         raise Exception("The model is not fitted yet!")
     ehvi = _ehvi_of(criteria, eng, group)
+    con = _constrained_of(criteria, eng, group)
     for c in criteria[1:]:
         if c.model is not model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin():
             raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
@@ -222,6 +256,9 @@ def sweep_argmax(criteria: Sequence, Xs: np.ndarray, index_offset: int = 0, grou
     eng.upload_candidates(Xs, lazy=True)  # (the sweep right below overlaps the copy with its first chunks)
     if ehvi is not None:
         best, idx = ehvi.sweep(k=1)
+        return best, idx + int(index_offset), (Xs[idx] if return_points else None)
+    if con is not None:
+        best, idx = (a[:, 0] for a in _constrained_topk(criteria, 1))
         return best, idx + int(index_offset), (Xs[idx] if return_points else None)
     acq = [(c.acq_id, c.acq_par()) for c in criteria]
     best, idx = eng.sweep(acq, c0.effective_plugin(), c0.minimize)
@@ -255,9 +292,13 @@ def sweep_generated(criteria: Sequence, bounds, M: int, seed: int, rank: int = 0
         best, idx = _lifted_topk(criteria, eng, lift, 1, group)
         return best[:, 0], idx[:, 0], eng.read_candidates(idx[:, 0])
     ehvi = _ehvi_of(criteria, eng, group)
+    con = _constrained_of(criteria, eng, group)
     _generate(eng, bounds, b_ - a, seed, a, method, int(M))
     if ehvi is not None:
         best, idx = ehvi.sweep(k=1)
+        return best, idx + a, eng.read_candidates(idx)
+    if con is not None:
+        best, idx = (v[:, 0] for v in _constrained_topk(criteria, 1))
         return best, idx + a, eng.read_candidates(idx)
     best, idx = eng.sweep([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize)
     if getattr(eng, "comm_world", 0):
@@ -294,9 +335,12 @@ def sweep_topk(criteria: Sequence, Xs: np.ndarray, k: int, index_offset: int = 0
     Xs = model._check_X(Xs)
     eng = model.engine
     ehvi = _ehvi_of(criteria, eng, group)
+    con = _constrained_of(criteria, eng, group)
     eng.upload_candidates(Xs, lazy=True)  # (the sweep right below overlaps the copy with its first chunks)
     if ehvi is not None:
         best, idx = (a[None, :] for a in ehvi.sweep(k=int(k)))
+    elif con is not None:
+        best, idx = _constrained_topk(criteria, k)
     else:
         best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
     if getattr(eng, "comm_world", 0):
@@ -334,9 +378,12 @@ def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, 
     a, b_ = shard_bounds(int(M), rank, world)
     eng = model.engine
     ehvi = _ehvi_of(criteria, eng, group)
+    con = _constrained_of(criteria, eng, group)
     _generate(eng, bounds, b_ - a, seed, a, method, int(M))
     if ehvi is not None:
         best, idx = (v[None, :] for v in ehvi.sweep(k=int(k)))
+    elif con is not None:
+        best, idx = _constrained_topk(criteria, k)
     else:
         best, idx = eng.sweep_topk([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, k)
     if getattr(eng, "comm_world", 0):
@@ -457,6 +504,8 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     if any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("EHVI has no believer batches: the front and its cells change with each believed point "
                                   "(`ehvi_believer_batch` rebuilds them between the steps)")
+    if any(is_constrained(c) for c in criteria):
+        raise NotImplementedError("modelled constraints (bogp.Constrained) have no believer batches: strategy='topk' serves them")
     if lift is not None:
         raise NotImplementedError("a lift (PCA-BO) has no believer batches")
     if masks is not None and np.any(masks):
@@ -509,6 +558,8 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
         raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
     if criteria is not None and any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("EHVI / several targets have no Thompson batches")
+    if criteria is not None and any(is_constrained(c) for c in criteria):
+        raise NotImplementedError("modelled constraints (bogp.Constrained) have no Thompson batches: strategy='topk' serves them")
     if lift is not None:
         raise NotImplementedError("a lift (PCA-BO) has no Thompson batches")
     if masks is not None and np.any(masks):
@@ -667,6 +718,8 @@ def _lifted_argmax_restart(obj_func, search_space, h, g, eval_budget, optimizer)
         raise NotImplementedError("a lifted sweep (PCA-BO) takes no constraints h / g")
     if is_ehvi(crit):
         raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
+    if is_constrained(crit):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not modelled constraints (bogp.Constrained)")
     if engine_rank_world(crit.model.engine)[1] > 1:
         raise NotImplementedError("a lifted sweep (PCA-BO) runs on one rank (no multi-rank exchange of penalised winners)")
     lift = unwrap_lift(obj_func)[1]
@@ -720,6 +773,8 @@ def argmax_restart(
     PCA-BO's wrapper (`unwrap_lift`) under "sweep" / "sweep-device[-lhs|-sobol]": the candidates are rows of the reduced box and
     are swept under the wrapper's lift (`sweep_argmax(..., lift=)`); the polish hybrids, fixed variables, constraints and
     several ranks are refused by name.
+    A `bogp.Constrained` criterion (modelled constraints) is served under "sweep" and "sweep-device[-lhs|-sobol]" through
+    `bogp_sweep_constrained`; "BFGS" and the "-BFGS" hybrids are refused by name (it has no input gradient).
     Anything else ("MIES", "OnePlusOne_Cholesky_CMA", constraints under "BFGS", a non-continuous space) is the
     reference's own business: the call is handed to its `argmax_restart` when `bayes_optim` is importable, for which a
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
@@ -739,6 +794,9 @@ def argmax_restart(
         # EHVI(input_gradient=True): "BFGS" is the loop below on the one-point call (bogp_point_eval_ehvi), the hybrids are
         # ehvi.sweep(k) + polish_topk (bogp_polish_ehvi); fixed variables, constraints, a lift and several ranks are refused
         # by name where the single-objective polish hybrids refuse them
+    if is_constrained(fcrit) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS"):
+        raise NotImplementedError("optimizer=%r needs an input gradient, which the feasibility-weighted criterion (bogp.Constrained) "
+                                  "does not have: use 'sweep' or 'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip
     if not ours and (optimizer != "BFGS" or h is not None or g is not None or not is_continuous(search_space)):
         ref = _reference_argmax_restart()
         if ref is None:

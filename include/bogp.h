@@ -294,6 +294,34 @@ int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_
 int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
                     int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 
+/* ---- sweep: modelled constraints, feasibility-weighted criteria ---------------------------------------
+ * The reference accepts the values of expensive constraints and drops them (BaseBO.tell: base.py:328; BaseMOBO.tell:
+ * mobo.py:117-118); its cheap callables h / g are handled by a penalty or a filter.  Here the committed model has m = n_targets
+ * >= 2 columns: target 0 is the objective, targets 1 .. m - 1 are constraints, constraint j feasible when lo_j <= c_j(x) <= hi_j
+ * (g <= 0 is (-inf, 0]; |h| <= tol is [-tol, tol]).  Per candidate, from the posterior of all m targets (as bogp_sweep_ehvi forms
+ * it, the same bits -- the correlation chunk and |L^-1 r|^2 are shared, so the constraints cost one more read of the chunk):
+ *   PoF_j  = bogp_feasibility(mu_j, MSE_j, sigma2_j, lo_j, hi_j);  P = PoF_1 * ... * PoF_{m-1} (in this order, from 1.0)
+ *   value_c = base_c * P,  base_c the criterion c of bogp_sweep on target 0 (EI, EpsilonPI or MGFI: the non-negative ones), or 1 for
+ *             BOGP_ACQ_NONE: the probability of feasibility alone, the usual criterion while no feasible point is known
+ *             (Gelbart, Snoek, Adams 2014).  UCB changes sign and is refused.  NaN propagates and is maximal in the argmax.
+ *   n_con        m - 1;  lo / hi: n_con HOST values each, either may be infinite, NaN and hi < lo are invalid (hi == lo is allowed)
+ *   k            1 <= k <= BOGP_MAX_TOPK: best_val / best_idx are q x k row-major and follow bogp_sweep_topk's rules
+ *   acq_out (q x M), pof_out (M), mu_out (M x m), mse_out (M x m): optional HOST buffers (NULL to skip)
+ * Always the chunked, unpruned sweep with the variance; the kernel's time is reported as acquisition_ms by bogp_last_timing.
+ * BOGP_ERR_INVALID: no committed model, no candidates, n_targets < 2, n_con != n_targets - 1, q outside [1, BOGP_MAX_Q], k outside
+ * [1, BOGP_MAX_TOPK], an id other than EI / EpsilonPI / MGFI / BOGP_ACQ_NONE, a parameter the criterion refuses, a NaN bound,
+ * hi < lo, a null required array.  BOGP_ERR_UNSUPPORTED: a lift is set, the handle holds a forest, a polynomial trend basis.
+ *
+ * bogp_feasibility (host only, no handle, no device call): P(lo <= Y <= hi) for Y ~ N(mu, mse), sd = sqrt(mse) without a floor;
+ * sd / sqrt(sigma2) < 1e-6 (EI's guard, acquisition_fun.py:153-176) gives the indicator of lo <= mu <= hi; otherwise, with
+ * za = (lo - mu) / sd and zb = (hi - mu) / sd, Phi(-za) - Phi(-zb) for za > 0 and Phi(zb) - Phi(za) else (the difference is taken
+ * in the tail the interval lies in), Phi(-inf) = 0 and Phi(+inf) = 1 exactly.                                           */
+#define BOGP_ACQ_NONE (-1)
+double bogp_feasibility(double mu, double mse, double sigma2, double lo, double hi);
+int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int n_con,
+                           const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,
+                           double* pof_out, double* mu_out, double* mse_out);
+
 /* ---- sweep: Kriging-believer batches ------------------------------------------------------------------
  * q proposals per call from q criteria, where step j sees the variance conditioned on the points believed before it
  * (Ginsbourger, Le Riche, Carraro 2010).  The reference has no such strategy: ParallelBO's q criteria share one posterior
