@@ -20,6 +20,9 @@ ACQ_EI, ACQ_EPSILON_PI, ACQ_UCB, ACQ_MGFI = 0, 1, 2, 3
 ACQ_NONE = -1  # BOGP_ACQ_NONE: bogp_sweep_constrained's feasibility-only criterion
 TREND_CONSTANT, TREND_LINEAR, TREND_QUADRATIC = 0, 1, 2
 SELFTEST_PROFILE, SELFTEST_BESSEL_K, SELFTEST_RGAMMA, SELFTEST_BESSEL_K_PAIRS, SELFTEST_MATERN_NU_PAIRS = range(5)
+(CRITERIA_NDTR, CRITERIA_NORM_PDF, CRITERIA_EHVI_G, CRITERIA_ACQ_VALUE, CRITERIA_FEASIBILITY, CRITERIA_ACQ_UPPER_BOUND,
+ CRITERIA_ACQ_UPPER_BOUND_INTERVAL, CRITERIA_PRUNE_BELOW) = range(8)  # BOGP_CRITERIA_*: selectors of bogp_selftest_criteria
+CRITERIA_COLUMNS = 8
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
 MAX_Q = 64
 PRUNE_PATH_NONE, PRUNE_PATH_CHUNKS, PRUNE_PATH_ONEPASS, PRUNE_PATH_ONEPASS_FALLBACK = 0, 1, 2, 3  # bogp_last_prune_path
@@ -139,6 +142,7 @@ SIGNATURES = {
     "bogp_nll_path": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bogp_chol_wide_panels": (C.c_int, [C.c_int, _ip, C.c_int]),
     "bogp_selftest_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, C.c_int64, _dp]),
+    "bogp_selftest_criteria": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int64, _dp]),
     "bogp_selftest_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_int]),
 }
 
@@ -1273,4 +1277,18 @@ class Engine:
             raise ValueError("the *_PAIRS selectors take an (n, 2) array")
         out = np.empty(n)
         self._check(self._lib.bogp_selftest_profile(self._h, int(what), int(kernel), float(pexp), _ptr(arg), n, _ptr(out)))
+        return out
+
+    def selftest_criteria(self, what, *columns):
+        """`what` (CRITERIA_*) of every row on the device: the scalar criterion functions of csrc/bogp_device.h themselves (ndtr, norm_pdf,
+        ehvi_G, acq_value, feasibility, acq_upper_bound, acq_upper_bound_interval, prune_below), one row of arguments each.  `columns`:
+        the function's arguments in order, scalars or arrays, broadcast against each other (bogp_selftest_criteria's columns)."""
+        if not 1 <= len(columns) <= CRITERIA_COLUMNS:
+            raise ValueError("between 1 and %d argument columns" % CRITERIA_COLUMNS)
+        cols = np.broadcast_arrays(*[np.asarray(c, dtype=np.float64).ravel() for c in columns])
+        rows = np.zeros((len(cols[0]), CRITERIA_COLUMNS))
+        for k, c in enumerate(cols):
+            rows[:, k] = c
+        out = np.empty(len(rows))
+        self._check(self._lib.bogp_selftest_criteria(self._h, int(what), _ptr(rows), len(rows), _ptr(out)))
         return out

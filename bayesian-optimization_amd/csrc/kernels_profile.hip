@@ -1,6 +1,7 @@
 // kernels_profile.hip -- bogp_selftest_profile: the radial profile of a correlation function (or one of its building blocks) evaluated on the
 // device for an array of arguments, so that tests can hold the special functions of bogp_device.h (K_nu, 1 / Gamma) to committed
-// tables one argument at a time instead of through a posterior.  See include/bogp.h.
+// tables one argument at a time instead of through a posterior; bogp_selftest_criteria: the same for the scalar criterion functions
+// (ndtr, acq_value, feasibility, the two upper bounds, prune_below).  See include/bogp.h.
 #include "bogp_device.h"
 #include "bogp_handle.h"
 
@@ -25,7 +26,47 @@ __global__ void k_special(const double* __restrict__ in, double* __restrict__ ou
   }
 }
 
+// one row of BOGP_CRITERIA_COLUMNS doubles per thread; the functions of bogp_device.h themselves, no expression of theirs restated
+__global__ void k_criteria(const double* __restrict__ rows, double* __restrict__ out, int64_t n, int what) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* r = rows + i * BOGP_CRITERIA_COLUMNS;
+  switch (what) {
+    case BOGP_CRITERIA_NDTR: out[i] = ndtr(r[0]); break;
+    case BOGP_CRITERIA_NORM_PDF: out[i] = norm_pdf(r[0]); break;
+    case BOGP_CRITERIA_EHVI_G: out[i] = ehvi_G(r[0]); break;
+    case BOGP_CRITERIA_ACQ_VALUE: out[i] = acq_value((int)r[0], r[1], r[2], r[3], r[4], r[5]); break;
+    case BOGP_CRITERIA_FEASIBILITY: out[i] = feasibility(r[0], r[1], r[2], r[3], r[4]); break;
+    case BOGP_CRITERIA_ACQ_UPPER_BOUND: out[i] = acq_upper_bound((int)r[0], r[1], r[2], r[3], r[4], r[5]); break;
+    case BOGP_CRITERIA_ACQ_UPPER_BOUND_INTERVAL: out[i] = acq_upper_bound_interval((int)r[0], r[1], r[2], r[3], r[4], r[5], r[6]); break;
+    default: out[i] = prune_below(r[0], r[1]) ? 1.0 : 0.0; break;
+  }
+}
+
 }  // namespace
+
+extern "C" int bogp_selftest_criteria(bogp_handle* h, int what, const double* rows, int64_t n, double* out) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!rows || !out || n <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_selftest_criteria: null pointer or empty array");
+  if (what < BOGP_CRITERIA_NDTR || what > BOGP_CRITERIA_PRUNE_BELOW) FAIL(h, BOGP_ERR_INVALID, "bogp_selftest_criteria: unknown selector %d", what);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  double *din = nullptr, *dout = nullptr;
+  if (hipMalloc((void**)&din, n * BOGP_CRITERIA_COLUMNS * sizeof(double)) != hipSuccess || hipMalloc((void**)&dout, n * sizeof(double)) != hipSuccess) {
+    dfree(din); dfree(dout);
+    FAIL(h, BOGP_ERR_HIP, "bogp_selftest_criteria: hipMalloc failed");
+  }
+  hipError_t e = hipMemcpyAsync(din, rows, n * BOGP_CRITERIA_COLUMNS * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_criteria, dim3((unsigned)((n + 255) / 256)), 256, 0, st, din, dout, n, what);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  dfree(din); dfree(dout);
+  if (e != hipSuccess) FAIL(h, BOGP_ERR_HIP, "bogp_selftest_criteria: %s", hipGetErrorString(e));
+  return BOGP_OK;
+}
 
 extern "C" int bogp_selftest_profile(bogp_handle* h, int what, int kernel, double pexp, const double* arg, int64_t n, double* out) {
   if (!h) return BOGP_ERR_INVALID;

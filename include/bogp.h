@@ -754,6 +754,26 @@ int bogp_selftest_gemm(bogp_handle* h, int ta, int tb, int m, int n, int k, doub
 #define BOGP_SELFTEST_MATERN_NU_PAIRS 4
 int bogp_selftest_profile(bogp_handle* h, int what, int kernel, double pexp, const double* arg, int64_t n, double* out);
 
+/* The scalar criterion functions of csrc/bogp_device.h -- what every sweep ends in and what the pruned paths decide with -- evaluated
+ * on the device at arguments the caller chooses: `rows` is n x 8 doubles (row-major), one thread per row writes one double to out.
+ * Columns per selector (the remaining ones are ignored; ids and parameters travel as doubles):
+ *   NDTR (a)   NORM_PDF (x)   EHVI_G (z)
+ *   ACQ_VALUE (id, par, y_hat, sd, plugin, sigma2)             FEASIBILITY (mu, mse, sigma2, lo, hi)
+ *   ACQ_UPPER_BOUND (id, par, y_hat, sd_ub, plugin, sigma2)    ACQ_UPPER_BOUND_INTERVAL (id, par, y32, e, sd_ub, plugin, sigma2)
+ *   PRUNE_BELOW (bound, thr) -> 0.0 / 1.0
+ * The kernel calls the functions themselves and holds no copy of any expression.  Used by tests/test_gpu_criteria.py to hold them to
+ * the committed table tests/golden/G46_criteria_truth.npz argument by argument.                                                      */
+#define BOGP_CRITERIA_NDTR 0
+#define BOGP_CRITERIA_NORM_PDF 1
+#define BOGP_CRITERIA_EHVI_G 2
+#define BOGP_CRITERIA_ACQ_VALUE 3
+#define BOGP_CRITERIA_FEASIBILITY 4
+#define BOGP_CRITERIA_ACQ_UPPER_BOUND 5
+#define BOGP_CRITERIA_ACQ_UPPER_BOUND_INTERVAL 6
+#define BOGP_CRITERIA_PRUNE_BELOW 7
+#define BOGP_CRITERIA_COLUMNS 8
+int bogp_selftest_criteria(bogp_handle* h, int what, const double* rows, int64_t n, double* out);
+
 /* The optimiser behind bogp_mle_batch (csrc/bogp_lbfgsb.h: L-BFGS-B after Byrd, Lu, Nocedal & Zhu 1995 with the More'-Thuente
  * line search) on a HOST objective: what the reference gets from scipy.optimize.fmin_l_bfgs_b (gpr.py:1136).  No device, no handle;
  * used by tests/test_lbfgsb.py to compare it with scipy on the CPU.  x: in the start, out the minimiser (n); fn fills *f and g (n).

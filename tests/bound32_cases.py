@@ -119,6 +119,46 @@ def interval_bound(a_id, par, y_hat, e, sd_ub, plugin, s2):
     return float(_lib.load().bogp_acq_upper_bound_interval(int(a_id), float(par), float(y_hat), float(e), float(sd_ub), float(plugin), float(s2)))
 
 
+INTERVAL_PARS = {0: (0.0,), 1: (0.0, 0.05, 0.5, 1.5), 2: (0.5, 8.0, 50.0), 3: (0.5, 2.0, 10.0, 30.0)}  # by criterion id
+
+
+def interval_cases(a_id, minimize, trials=60, tail_trials=12, ulp_trials=24):
+    """(sigma2, plugin, y_hat, e, sd_ub) of the interval bound's domination property (tests/test_bound32_host.py on the host wrappers,
+    tests/test_gpu_criteria.py on the device): random intervals, every fifth around the plugin and every fifth around 0; then
+    `tail_trials` intervals around z = (plugin - y_hat) / sd_ub in [-37, -20], narrow enough to stay clear of the plugin; then
+    `ulp_trials` intervals 1 to 4 ulp of y_hat wide on either side."""
+    rng = np.random.default_rng(23 + a_id + 10 * minimize)
+    for trial in range(trials):
+        s2 = float(10.0 ** rng.uniform(-4, 1))
+        plugin = float(rng.normal(0, 2))
+        y_hat = float(rng.normal(0, 2)) * (1 if minimize else -1)
+        e = float(10.0 ** rng.uniform(-8, 0.5))
+        if trial % 5 == 0:
+            y_hat = plugin + float(rng.uniform(-1, 1)) * e  # the plugin inside the interval
+        if trial % 5 == 1:
+            y_hat = float(rng.uniform(-1, 1)) * e           # 0 inside the interval
+        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
+        yield s2, plugin, y_hat, e, sd_ub
+    rng = np.random.default_rng(323 + a_id + 10 * minimize)
+    for trial in range(tail_trials):
+        s2 = float(10.0 ** rng.uniform(-4, 1))
+        plugin = float(rng.normal(0, 2))
+        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
+        y_hat = float(plugin - rng.uniform(-37.0, -20.0) * sd_ub)
+        yield s2, plugin, y_hat, float(10.0 ** rng.uniform(-8, 0) * sd_ub), sd_ub
+    for trial in range(ulp_trials):  # intervals of a few ulp of y_hat: what the bound's 1e-12 raise is for, a dip of erf / erfc / exp between the ends
+        s2 = float(10.0 ** rng.uniform(-4, 1))
+        plugin = float(rng.normal(0, 2))
+        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
+        y_hat = float(plugin + rng.uniform(0.05, 6.0) * sd_ub * (1 if trial % 3 else -1)) * (1 if minimize else -1)
+        yield s2, plugin, y_hat, float((1 + trial % 4) * np.spacing(abs(y_hat))), sd_ub
+
+
+def interval_points(y_hat, e):
+    """201 points of [y_hat - e, y_hat + e], then both ends and the centre as the bound forms them"""
+    return np.r_[np.linspace(y_hat - e, y_hat + e, 201), y_hat - e, y_hat + e, y_hat]
+
+
 def stage1_flags(st, Xs, acq, plugin, minimize=True, pilot=PC.CHUNK_ROWS, rs=None):
     """The stage's flags for every row from the restatement's sums and margins, against the thresholds the pilot sets (k_bound32_flags'
     statements); and the exact test's flags (PC.surviving_fraction's) -> (flags32, flags64), both over all rows."""

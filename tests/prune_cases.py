@@ -60,6 +60,40 @@ def prune_margin(bound, thr):
     return 1e-9 * (np.abs(bound) + np.abs(thr)) + 1e-300
 
 
+DOMINATION_PARS = {0: (0.0,), 1: (0.0, 0.05, 0.5, 1.5), 2: (0.5, 50.0, -0.5, -3.0), 3: (0.5, 2.0, 10.0, 30.0)}  # by criterion id
+
+
+def sd_grid(sd_ub, s2):
+    """[0, sd_ub] with both ends, the guard edges of EI (sd / sqrt(sigma2) = 1e-6) and MGFI (sd = 1e-8) and their neighbours, and
+    the rungs 1 and 2 ulp under sd_ub."""
+    edges = [0.0, 1e-8, np.nextafter(1e-8, 0), np.nextafter(1e-8, 1), 1e-6 * np.sqrt(s2), np.nextafter(1e-6 * np.sqrt(s2), 0),
+             np.nextafter(1e-6 * np.sqrt(s2), 1), 1e-300, sd_ub, np.nextafter(sd_ub, 0), np.nextafter(np.nextafter(sd_ub, 0), 0)]  # fmt: skip
+    g = np.r_[edges, sd_ub * np.linspace(0, 1, 41), sd_ub * np.logspace(-12, 0, 25)]
+    return np.unique(g[(g >= 0) & (g <= sd_ub)])
+
+
+def domination_cases(a_id, trials=120, tail_trials=24):
+    """(sigma2, plugin, y_hat, sd_ub) of the domination property (tests/test_prune_bounds_host.py on the host wrappers,
+    tests/test_gpu_criteria.py on the device): random values on both sides of plugin - y_hat and exactly on it, ranges that end inside
+    the guards; then `tail_trials` rows with z = (plugin - y_hat) / sd_ub in [-37, -20], where Phi and phi amplify a rounding of z by z^2."""
+    rng = np.random.default_rng(11 + a_id)
+    for trial in range(trials):
+        s2 = float(10.0 ** rng.uniform(-4, 1))
+        plugin = float(rng.normal(0, 2))
+        gap = float(10.0 ** rng.uniform(-6, 1.3) * np.sqrt(s2)) * (1 if trial % 2 else -1)  # y_hat below / above plugin
+        y_hat = plugin - gap if trial % 7 else plugin                                     # ... and exactly on it
+        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
+        if trial % 11 == 0:
+            sd_ub = float(10.0 ** rng.uniform(-10, -5))  # ranges that end inside the guards
+        yield s2, plugin, y_hat, sd_ub
+    rng = np.random.default_rng(311 + a_id)
+    for trial in range(tail_trials):
+        s2 = float(10.0 ** rng.uniform(-4, 1))
+        plugin = float(rng.normal(0, 2))
+        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
+        yield s2, plugin, float(plugin - rng.uniform(-37.0, -20.0) * sd_ub), sd_ub
+
+
 def surviving_fraction(st, Xs, acq, plugin, minimize=True, pilot=CHUNK_ROWS):
     """Rows behind the pilot that the prune test lets through when the thresholds are the pilot's best values (the device's thresholds
     only rise from there), as a fraction of all rows."""

@@ -57,23 +57,15 @@ def test_margin_is_infinite_where_fp32_cannot_bound():
 @pytest.mark.parametrize("a_id,pars", [(EI, (0.0,)), (PI, (0.0, 0.05, 0.5, 1.5)), (UCB, (0.5, 8.0, 50.0)), (MGFI, (0.5, 2.0, 10.0, 30.0))])
 @pytest.mark.parametrize("minimize", [True, False])
 def test_interval_bound_dominates_the_bound_on_the_whole_interval(a_id, pars, minimize):
-    """Random (y_hat, plugin, sigma2, sd_ub, e), intervals straddling 0 and the plugin among them: the interval bound is at least
+    """Random (y_hat, plugin, sigma2, sd_ub, e), intervals straddling 0 and the plugin and intervals in the tail z in [-37, -20] among them
+    (BC.interval_cases, shared with the device's run of the same property in tests/test_gpu_criteria.py): the interval bound is at least
     bogp_acq_upper_bound at 201 points of the interval, both ends included (minimize only decides the sign of y_hat the caller passes:
     both signs are drawn)."""
-    rng = np.random.default_rng(23 + a_id + 10 * minimize)
+    assert pars == BC.INTERVAL_PARS[a_id]
     lib = _lib.load()
     n_inf = 0
-    for trial in range(60):
-        s2 = float(10.0 ** rng.uniform(-4, 1))
-        plugin = float(rng.normal(0, 2))
-        y_hat = float(rng.normal(0, 2)) * (1 if minimize else -1)
-        e = float(10.0 ** rng.uniform(-8, 0.5))
-        if trial % 5 == 0:
-            y_hat = plugin + float(rng.uniform(-1, 1)) * e  # the plugin inside the interval
-        if trial % 5 == 1:
-            y_hat = float(rng.uniform(-1, 1)) * e           # 0 inside the interval
-        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
-        ys = np.r_[np.linspace(y_hat - e, y_hat + e, 201), y_hat - e, y_hat + e, y_hat]
+    for s2, plugin, y_hat, e, sd_ub in BC.interval_cases(a_id, minimize):
+        ys = BC.interval_points(y_hat, e)
         for par in pars:
             b = BC.interval_bound(a_id, par, y_hat, e, sd_ub, plugin, s2)
             inner = np.array([lib.bogp_acq_upper_bound(int(a_id), float(par), float(v), sd_ub, plugin, s2) for v in ys])

@@ -20,30 +20,16 @@ def _below(bound, thr):
     return bool(_lib.load().bogp_prune_below(float(bound), float(thr)))
 
 
-def _sd_grid(sd_ub, s2):
-    """[0, sd_ub] with both ends, the guard edges of EI (sd / sqrt(sigma2) = 1e-6) and MGFI (sd = 1e-8) and their neighbours."""
-    edges = [0.0, 1e-8, np.nextafter(1e-8, 0), np.nextafter(1e-8, 1), 1e-6 * np.sqrt(s2), np.nextafter(1e-6 * np.sqrt(s2), 0),
-             np.nextafter(1e-6 * np.sqrt(s2), 1), 1e-300, sd_ub, np.nextafter(sd_ub, 0)]  # fmt: skip
-    g = np.r_[edges, sd_ub * np.linspace(0, 1, 41), sd_ub * np.logspace(-12, 0, 25)]
-    return np.unique(g[(g >= 0) & (g <= sd_ub)])
-
-
 @pytest.mark.parametrize("a_id,pars", [(EI, (0.0,)), (PI, (0.0, 0.05, 0.5, 1.5)), (UCB, (0.5, 50.0, -0.5, -3.0)), (MGFI, (0.5, 2.0, 10.0, 30.0))])
 def test_bound_dominates_the_criterion_on_the_whole_range(a_id, pars):
-    """Random (y_hat, plugin, sigma2) on both sides of plugin - y_hat, every parameter, sd on a grid over [0, sd_ub]: the oracle's
+    """Random (y_hat, plugin, sigma2) on both sides of plugin - y_hat and in the tail z in [-37, -20] (PC.domination_cases, shared with
+    the device's run of the same property in tests/test_gpu_criteria.py), every parameter, sd on a grid over [0, sd_ub]: the oracle's
     value never exceeds the bound by more than the prune margin -- i.e. the prune test, given that value as the threshold, would
     not prune the row itself -- and a NaN value only occurs where the bound is +inf or NaN."""
-    rng = np.random.default_rng(11 + a_id)
+    assert pars == PC.DOMINATION_PARS[a_id]
     worst = 0.0
-    for trial in range(120):
-        s2 = float(10.0 ** rng.uniform(-4, 1))
-        plugin = float(rng.normal(0, 2))
-        gap = float(10.0 ** rng.uniform(-6, 1.3) * np.sqrt(s2)) * (1 if trial % 2 else -1)  # y_hat below / above plugin
-        y_hat = plugin - gap if trial % 7 else plugin                                     # ... and exactly on it
-        sd_ub = float(np.sqrt(s2 * (1.0 + rng.uniform(0, 2) ** 2)))
-        if trial % 11 == 0:
-            sd_ub = float(10.0 ** rng.uniform(-10, -5))  # ranges that end inside the guards
-        sd = _sd_grid(sd_ub, s2)
+    for s2, plugin, y_hat, sd_ub in PC.domination_cases(a_id):
+        sd = PC.sd_grid(sd_ub, s2)
         for par in pars:
             b = _bound(a_id, par, y_hat, sd_ub, plugin, s2)
             with np.errstate(all="ignore"):
