@@ -47,17 +47,17 @@ struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point
   }
 };
 
-// The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, between two events appended to
-// ev_solve -- and the host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
+// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi
+enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI };
+
+// The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, one solve span -- and the
+// host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
 int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const double* x, const std::vector<double>& hw, std::vector<double>& hk,
-                   double* pivots, size_t& nev, std::vector<size_t>& ev_solve) {
+                   double* pivots) {
   const int i = bl.n, d = h->d, N = h->N;
   hipStream_t st = h->stream;
-  hipEvent_t e0 = h->bel_ev.at(nev), e1 = h->bel_ev.at(nev + 1);
-  if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  ev_solve.push_back(nev);
-  nev += 2;
-  HIPCHK(h, hipEventRecord(e0, st));
+  int e0 = 0, e1 = 0;
+  if (int e = h->bel_timer.mark(h, st, &e0)) return e;
   HIPCHK(h, hipMemcpyAsync(sb.dpt, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpyAsync(sb.drows + (size_t)i * d, x, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(h, launch_batch_corr(h->kernel, h->dX, N, d, h->dtheta, sb.dpt, 1, sb.dr, sb.dvr, st));  // (dvr: the distances, overwritten next)
@@ -69,7 +69,8 @@ int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const doub
   HIPCHK(h, hipMemcpyAsync(ri, sb.dr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(ai, sb.da, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(hk.data(), sb.dkk, (size_t)(i + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipEventRecord(e1, st));
+  if (int e = h->bel_timer.mark(h, st, &e1)) return e;
+  h->bel_timer.span(B_SOLVE, e0, e1);
   HIPCHK(h, hipStreamSynchronize(st));
   double rw = 0.0;
   for (int n = 0; n < N; ++n) rw += ri[n] * hw[n];
@@ -93,21 +94,19 @@ int believed_solve(bogp_handle* h, Believed& bl, const SolveBufs& sb, const doub
   return BOGP_OK;
 }
 
-// times of the solves and of the chunks' producer / k_believer launches, once everything is complete
-void believer_times(bogp_handle* h, const std::vector<size_t>& ev_solve, const std::vector<size_t>& ev_chunk) {
-  h->bel_corr_ms = h->bel_solve_ms = h->bel_pass_ms = 0;
-  for (size_t k : ev_solve) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, h->bel_ev[k], h->bel_ev[k + 1]);
-    h->bel_solve_ms += ms;
-  }
-  for (size_t k : ev_chunk) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, h->bel_ev[k], h->bel_ev[k + 1]);
-    (void)hipEventElapsedTime(&b, h->bel_ev[k + 1], h->bel_ev[k + 2]);
-    h->bel_corr_ms += a;
-    h->bel_pass_ms += b;
-  }
+// One chunk of a candidate pass: the producer (where `produce`), then k_believer over rows [ba.m0, ba.m0 + ba.mcount); three marks,
+// a producer and a pass span.
+int believer_chunk(bogp_handle* h, const SweepGeometry& pl, const BelieverArgs& ba, bool produce) {
+  hipStream_t st = h->stream;
+  SpanTimer& tm = h->bel_timer;
+  int e, c0 = 0, c1 = 0, c2 = 0;
+  if ((e = tm.mark(h, st, &c0))) return e;
+  if (produce) HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, pl, ba.m0, 0), (int)((ba.mcount + 63) / 64), pl.S, st));
+  if ((e = tm.mark(h, st, &c1))) return e;
+  HIPCHK(h, launch_believer(h->kernel, ba, st));
+  if ((e = tm.mark(h, st, &c2))) return e;
+  tm.span(B_PRODUCER, c0, c1); tm.span(B_PASS, c1, c2);
+  return BOGP_OK;
 }
 
 }  // namespace
@@ -176,8 +175,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   memset(bl.L, 0, sizeof(bl.L));
   int slots = 0;
   bool chunk_resident = false;  // all candidates fit one chunk and the producer has filled it: r(x) and the w-sums stay for the later points
-  size_t nev = 0;
-  std::vector<size_t> ev_solve, ev_chunk;  // event indices: (begin, end) per solve; (begin, producer end, end) per chunk
+  h->bel_timer.begin();
   h->bel_passes = 0;
   double plug = plugin;
   auto believe_mean = [&](double mu) {
@@ -192,7 +190,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   // sweep's array by the caller).  `row`: the candidate row a winner is (its variance becomes exactly 0), -1 for a pending point.
   auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
     const int i = bl.n;
-    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots, nev, ev_solve)) return rs;
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
     if (is_pending) {
       const double* ri = &bl.r[(size_t)i * N];
       double rg = 0.0;
@@ -226,20 +224,10 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
     ba.mu = h->dmu_out; ba.acq_out = dacq_row; ba.mse_out = dmse_row; ba.blk_val = h->dblk_val; ba.blk_idx = h->dblk_idx;
     int64_t blk_offset = 0;
     for (int64_t c = 0; c < pl.nchunk; ++c) {
-      const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
-      hipEvent_t c0 = h->bel_ev.at(nev), c1 = h->bel_ev.at(nev + 1), c2 = h->bel_ev.at(nev + 2);
-      if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-      ev_chunk.push_back(nev);
-      nev += 3;
-      HIPCHK(h, hipEventRecord(c0, st));
-      if (active && !chunk_resident) {
-        HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, pl, m0, 0), (int)(Mc_eff / 64), pl.S, st));
-        chunk_resident = pl.nchunk == 1;
-      }
-      HIPCHK(h, hipEventRecord(c1, st));
+      const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0);
       ba.m0 = m0; ba.mcount = mcount; ba.blk_offset = blk_offset;
-      HIPCHK(h, launch_believer(h->kernel, ba, st));
-      HIPCHK(h, hipEventRecord(c2, st));
+      if (int rs = believer_chunk(h, pl, ba, active && !chunk_resident)) return rs;
+      if (active) chunk_resident = pl.nchunk == 1;
       blk_offset += (mcount + 63) / 64;
     }
     ++h->bel_passes;
@@ -277,7 +265,7 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
 
   // times of the solves and of the passes (everything is complete: the last step was read back)
   HIPCHK(h, hipStreamSynchronize(st));
-  believer_times(h, ev_solve, ev_chunk);
+  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
   return BOGP_OK;
 }
 
@@ -517,15 +505,14 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   memset(bl.L, 0, sizeof(bl.L));
   int slots = 0;
   bool chunk_resident = false;
-  size_t nev = 0;
-  std::vector<size_t> ev_solve, ev_chunk, ev_ehvi;  // event indices: (begin, end) per solve; (begin, producer end, end) per chunk; (begin, end) per k_believer_ehvi
+  h->bel_timer.begin();
   h->bel_passes = 0;
 
   // One believed point, as in bogp_sweep_believer.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it joins the front (a
   // winner's mean is read from the sweep's array by the caller, before this).  A step's cells are those of the front as it stands here.
   auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
     const int i = bl.n;
-    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots, nev, ev_solve)) return rs;
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
     if (is_pending) {
       const double* ri = &bl.r[(size_t)i * N];
       for (int t = 0; t < m; ++t) {
@@ -560,20 +547,9 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
       ba.C = h->dbel_C; ba.c_out = h->dbel_C + (size_t)bl.slot[i] * M; ba.s = dscratch; ba.sigma2 = 1.0;
       ba.eval = 0;
       for (int64_t c = 0; c < pl.nchunk; ++c) {
-        const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
-        hipEvent_t c0 = h->bel_ev.at(nev), c1 = h->bel_ev.at(nev + 1), c2 = h->bel_ev.at(nev + 2);
-        if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-        ev_chunk.push_back(nev);
-        nev += 3;
-        HIPCHK(h, hipEventRecord(c0, st));
-        if (!chunk_resident) {
-          HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, pl, m0, 0), (int)(Mc_eff / 64), pl.S, st));
-          chunk_resident = pl.nchunk == 1;
-        }
-        HIPCHK(h, hipEventRecord(c1, st));
-        ba.m0 = m0; ba.mcount = mcount;
-        HIPCHK(h, launch_believer(h->kernel, ba, st));
-        HIPCHK(h, hipEventRecord(c2, st));
+        ba.m0 = c * pl.Mc; ba.mcount = std::min<int64_t>(pl.Mc, M - ba.m0);
+        if (int rs = believer_chunk(h, pl, ba, !chunk_resident)) return rs;
+        chunk_resident = pl.nchunk == 1;
       }
     }
     BelieverEhviArgs be;
@@ -588,13 +564,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
       be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C;
     }
     be.mu = h->dmu_out; be.ehvi_out = dehvi_row; be.mse_out = dmse_row; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
-    hipEvent_t b0 = h->bel_ev.at(nev), b1 = h->bel_ev.at(nev + 1);
-    if (!b0 || !b1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-    ev_ehvi.push_back(nev);
-    nev += 2;
-    HIPCHK(h, hipEventRecord(b0, st));
-    HIPCHK(h, launch_believer_ehvi(be, st));
-    HIPCHK(h, hipEventRecord(b1, st));
+    if (int rs = timed_span(h, h->bel_timer, st, B_EHVI, [&] { return launch_believer_ehvi(be, st); })) return rs;
     ++h->bel_passes;
     if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
     return BOGP_OK;
@@ -628,13 +598,8 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   }
 
   HIPCHK(h, hipStreamSynchronize(st));
-  believer_times(h, ev_solve, ev_chunk);
-  h->bel_ehvi_ms = 0;
-  for (size_t k : ev_ehvi) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, h->bel_ev[k], h->bel_ev[k + 1]);
-    h->bel_ehvi_ms += ms;
-  }
+  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  h->bel_ehvi_ms = h->bel_timer.sum(B_EHVI);
   return BOGP_OK;
 }
 

@@ -171,29 +171,24 @@ extern "C" int bogp_forest_info(const bogp_handle* h, int64_t* out) {
   return BOGP_OK;
 }
 
-// k_forest over rows [row0, row0 + nrows) of the current candidates, timed by two events (bogp_last_timing: acquisition_ms)
+// one criteria span on the sweep's timer around a forest kernel (bogp_last_timing: acquisition_ms, one chunk), read when it is asked for
+template <class Launch>
+static int forest_span(bogp_handle* h, Launch launch) {
+  h->timer.begin();
+  if (int e = timed_span(h, h->timer, h->stream, T_CRITERIA, launch)) return e;
+  h->n_chunks = 1; h->timing_pending = true;
+  return BOGP_OK;
+}
+
+// k_forest over rows [row0, row0 + nrows) of the current candidates
 static int run_forest(bogp_handle* h, const char* who, ForestArgs& a, int64_t row0, int64_t nrows) {
   if (!h->forest_T) FAIL(h, BOGP_ERR_INVALID, "%s: no forest: call bogp_forest_set first", who);
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
   if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
   if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
-  if (!h->forest_ev.at(1)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d;
   a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
-  HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
-  HIPCHK(h, launch_forest(a, h->stream));
-  HIPCHK(h, hipEventRecord(h->forest_ev[1], h->stream));
-  return BOGP_OK;
-}
-
-static int forest_timing(bogp_handle* h) {  // after the stream has been waited for
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->forest_ev[0], h->forest_ev[1]));
-  h->timing_pending = false;
-  h->t_corr_ms = h->t_contract_ms = 0;
-  h->t_acq_ms = ms;
-  h->n_chunks = 1;
-  return BOGP_OK;
+  return forest_span(h, [&] { return launch_forest(a, h->stream); });
 }
 
 extern "C" int bogp_forest_predict(bogp_handle* h, double* mu, double* mse) {
@@ -214,7 +209,7 @@ extern "C" int bogp_forest_predict(bogp_handle* h, double* mu, double* mse) {
   HIPCHK(h, hipMemcpyAsync(mu, h->dmu_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (mse) HIPCHK(h, hipMemcpyAsync(mse, h->dmse_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 extern "C" int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, double* per_tree) {
@@ -232,7 +227,7 @@ extern "C" int bogp_forest_leaves(bogp_handle* h, int64_t first_row, int n, doub
   if ((e = run_forest(h, "bogp_forest_leaves", a, first_row, n))) return e;
   HIPCHK(h, hipMemcpyAsync(per_tree, h->dbatch, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
@@ -294,7 +289,7 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
       best_val[i] = -INFINITY;
       best_idx[i] = -1;
     }
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 // ---- forests with several outputs: k_forest_ehvi (kernels_forest_ehvi.hip) -------------------------------------------------------
@@ -305,13 +300,9 @@ static int run_forest_ehvi(bogp_handle* h, const char* who, ForestEhviArgs& a, i
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload / bind / generate_mixed first", who);
   if (h->hXs_lazy) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lazy upload is pending; forest calls take bogp_candidates_upload", who);
   if (row0 < 0 || nrows < 1 || row0 + nrows > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: rows [%lld, %lld) outside the %lld candidates", who, (long long)row0, (long long)(row0 + nrows), (long long)h->M);
-  if (!h->forest_ev.at(1)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   a.Xs = h->dXs; a.M = h->M; a.row0 = row0; a.nrows = nrows; a.d = h->d; a.m = h->forest_m;
   a.words = h->dforest_words; a.tree = h->dforest_tree; a.T = h->forest_T; a.tree_words = h->forest_tree_words;
-  HIPCHK(h, hipEventRecord(h->forest_ev[0], h->stream));
-  HIPCHK(h, launch_forest_ehvi(a, h->stream));
-  HIPCHK(h, hipEventRecord(h->forest_ev[1], h->stream));
-  return BOGP_OK;
+  return forest_span(h, [&] { return launch_forest_ehvi(a, h->stream); });
 }
 
 // what run_forest_ehvi will refuse, asked before anything is allocated
@@ -338,7 +329,7 @@ extern "C" int bogp_forest_predict_multi(bogp_handle* h, double* mu, double* mse
   HIPCHK(h, hipMemcpyAsync(mu, h->dmu_out, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (mse) HIPCHK(h, hipMemcpyAsync(mse, h->dmse_out, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 extern "C" int bogp_forest_leaves_multi(bogp_handle* h, int64_t first_row, int n, double* per_tree) {
@@ -355,7 +346,7 @@ extern "C" int bogp_forest_leaves_multi(bogp_handle* h, int64_t first_row, int n
   if ((e = run_forest_ehvi(h, "bogp_forest_leaves_multi", a, first_row, n))) return e;
   HIPCHK(h, hipMemcpyAsync(per_tree, h->dbatch, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
@@ -419,7 +410,7 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
       best_val[i] = -INFINITY;
       best_idx[i] = -1;
     }
-  return forest_timing(h);
+  return BOGP_OK;
 }
 
 extern "C" int bogp_candidates_generate_mixed(bogp_handle* h, const int* kind, const double* lo, const double* hi, const int* n_levels,

@@ -102,7 +102,10 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   const int64_t M = h->M;
   const int r = h->d;
   const int64_t nblk = (M + 255) / 256;
-  if (!h->lift_ev.at(3)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  enum { L_FILTER, L_MERGE };  // kinds of the spans on h->lift_timer
+  SpanTimer& tm = h->lift_timer;
+  tm.begin();
+  int f0 = 0, f1 = 0, m0 = 0, m1 = 0;
   if ((e = h->dlift_pen.ensure(h, (size_t)M))) return e;
   if ((e = h->dlift_cnt.ensure(h, (size_t)nblk))) return e;
   if ((e = h->dlift_off.ensure(h, (size_t)nblk + 1))) return e;
@@ -111,7 +114,7 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   // 1. feasibility of all M rows, the scan of the workgroup counts, M_f to the host (it sizes the compact buffers and the sweep)
   LiftArgs la;
   la.Z = h->dXs; la.M = M; la.r = r; la.D = h->lift_D; la.lift = h->dlift; la.penalty = h->dlift_pen; la.blk_count = h->dlift_cnt;
-  HIPCHK(h, hipEventRecord(h->lift_ev[0], st));
+  if ((e = tm.mark(h, st, &f0))) return e;
   HIPCHK(h, launch_lift_penalty(la, st));
   HIPCHK(h, launch_lift_scan(h->dlift_cnt, nblk, h->dlift_off, st));
   int64_t Mf = 0;
@@ -124,7 +127,8 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
     if ((e = h->dlift_map.ensure(h, (size_t)Mf))) return e;
     HIPCHK(h, launch_lift_compact(h->dXs, M, r, h->dlift_pen, h->dlift_off, h->dlift_Z, h->dlift_map, st));
   }
-  HIPCHK(h, hipEventRecord(h->lift_ev[1], st));
+  if ((e = tm.mark(h, st, &f1))) return e;
+  tm.span(L_FILTER, f0, f1);
   // 3. the posterior sweep on the survivors, its q x M_f values kept on the device
   if (Mf > 0) {
     CandidateSwap swap(h, h->dlift_Z, Mf);
@@ -137,14 +141,15 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
     clear_sweep_timing(h);
   }
   // 4. criterion values and penalties side by side over all M rows, ranked as bogp_sweep_topk ranks
-  HIPCHK(h, hipEventRecord(h->lift_ev[2], st));
+  if ((e = tm.mark(h, st, &m0))) return e;
   HIPCHK(h, launch_lift_merge(h->dlift_pen, M, h->dacq_out, h->dlift_map, Mf, q, h->dlift_val, st));
   if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
   if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
   if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
   if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
   HIPCHK(h, launch_topk(h->dlift_val, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-  HIPCHK(h, hipEventRecord(h->lift_ev[3], st));
+  if ((e = tm.mark(h, st, &m1))) return e;
+  tm.span(L_MERGE, m0, m1);
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
@@ -153,12 +158,9 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
       best_val[i] = -INFINITY;
       best_idx[i] = -1;
     }
-  float f_ms = 0, m_ms = 0;
-  (void)hipEventElapsedTime(&f_ms, h->lift_ev[0], h->lift_ev[1]);
-  (void)hipEventElapsedTime(&m_ms, h->lift_ev[2], h->lift_ev[3]);
   h->lift_n_feasible = Mf;
-  h->lift_filter_ms = f_ms;
-  h->lift_merge_ms = m_ms;
+  h->lift_filter_ms = tm.sum(L_FILTER);
+  h->lift_merge_ms = tm.sum(L_MERGE);
   if (n_feasible) *n_feasible = Mf;
   if (value_out) HIPCHK(h, hipMemcpy(value_out, h->dlift_val, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost));
   if (penalty_out) HIPCHK(h, hipMemcpy(penalty_out, h->dlift_pen, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));

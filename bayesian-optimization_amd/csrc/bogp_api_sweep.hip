@@ -301,67 +301,35 @@ extern "C" int bogp_candidates_bind(bogp_handle* h, const void* d_Xs, int64_t M)
 // ------------------------------------------------------------------------------------------------------
 // posterior + acquisition sweep
 // ------------------------------------------------------------------------------------------------------
-// events per chunk: [0] corr start, [1] corr end (producer stream); [2] contract start, [3] contract end,
-// [4] acquisition end = chunk done (main stream)
-constexpr int EPC = 5;
+// What bogp_last_timing reports, from the spans a call leaves on h->timer (SpanTimer, bogp_handle.h): corr_ms = the producer spans,
+// contract_ms = the contraction spans, acquisition_ms = the criteria spans -- or, where a whole-sweep span exists, that span less the
+// other two sums (the criteria spans are then not read).  A chunk has five marks: 0 / 1 around its producer (producer stream), 2, 3, 4 on
+// the main stream; p0 / p1 are the two marks around the pilot's contraction.
+//
+//   path                  | producer                     | contraction                  | criteria
+//   ----------------------+------------------------------+------------------------------+-----------------------------------------------
+//   small batch           | -                            | -                            | -                               (n_chunks = 0)
+//   one launch            | -                            | k_sweep_small                | -
+//   chunks                | (0,1)                        | (2,3)                        | (3,4)
+//   pruned chunks         | (0,1)                        | (2,3); the pilot's (p0,p1)   | (1,2) bound / scan / gather, (3,4); in the pilot's
+//                         |                              |                              | chunk (1,p0) and (p1,2) in place of (1,2)
+//   one pass              | every producer and FP32-sums | every contraction launch;    | whole sweep less the two: the small kernels and
+//                         | launch; a fall-back's (0,1)  | a fall-back's (2,3)          | the host's waits
+//   forest calls          | -                            | -                            | k_forest / k_forest_ehvi         (n_chunks = 1)
 
-// Event times of the last sweep are read lazily (bogp_last_timing, or the next sweep): reading them needs the events
+// The spans of the last sweep are read lazily (bogp_last_timing, or the next sweep): reading them needs the events
 // to have completed, and an un-synchronised sweep (bogp_sweep without host outputs) must not wait for them.
 static void collect_timing(bogp_handle* h) {
   if (!h->timing_pending) return;
   h->timing_pending = false;
   (void)hipSetDevice(h->device);
-  if (h->timing_fused) {
-    float ms = 0;
-    (void)hipEventSynchronize(h->ev[1]);
-    (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-    h->t_corr_ms = 0; h->t_contract_ms = ms; h->t_acq_ms = 0;  // one kernel: reported as the contraction's time
-    return;
-  }
-  h->t_corr_ms = h->t_contract_ms = h->t_acq_ms = 0;
-  if (h->timing_onepass) {
-    // a sweep that began on the one-pass flow: its own producer / contraction launches are bracketed one by one (t_spans: kind, begin, end),
-    // the chunks of a fall-back keep their five events, and everything else between the sweep's first and last event -- the small kernels
-    // and the two host waits -- is the rest
-    float tot = 0;
-    (void)hipEventSynchronize(h->ev[(size_t)h->t_total[1]]);
-    (void)hipEventElapsedTime(&tot, h->ev[(size_t)h->t_total[0]], h->ev[(size_t)h->t_total[1]]);
-    for (size_t i = 0; i + 2 < h->t_spans.size(); i += 3) {
-      float a = 0;
-      (void)hipEventElapsedTime(&a, h->ev[(size_t)h->t_spans[i + 1]], h->ev[(size_t)h->t_spans[i + 2]]);
-      (h->t_spans[i] == 0 ? h->t_corr_ms : h->t_contract_ms) += a;
-    }
-    for (int64_t c : h->t_chunks) {
-      float a = 0, b2 = 0;
-      hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
-      (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-      (void)hipEventElapsedTime(&b2, ev[2], ev[3]);
-      h->t_corr_ms += a; h->t_contract_ms += b2;
-    }
-    h->t_acq_ms = tot - h->t_corr_ms - h->t_contract_ms;
-    return;
-  }
-  for (int64_t c = 0; c < h->n_chunks; ++c) {
-    float a = 0, b2 = 0, c2 = 0;
-    hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
-    (void)hipEventSynchronize(ev[4]);
-    (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&b2, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&c2, ev[3], ev[4]);
-    h->t_corr_ms += a; h->t_contract_ms += b2; h->t_acq_ms += c2;
-    if (h->timing_prune) {  // bound, scan, compaction and gather of the chunk (and, in chunk 0, the pilot: split below)
-      float g = 0;
-      (void)hipEventElapsedTime(&g, ev[1], ev[2]);
-      h->t_acq_ms += g;
-    }
-  }
-  if (h->timing_prune) {  // the pilot's contraction ran between chunk 0's events [1] and [2]
-    float pc = 0;
-    hipEvent_t* evp = &h->ev[(size_t)(h->n_chunks * EPC + 1)];
-    (void)hipEventElapsedTime(&pc, evp[0], evp[1]);
-    h->t_contract_ms += pc; h->t_acq_ms -= pc;
-  }
+  SpanTimer& t = h->timer;
+  h->t_corr_ms = t.sum(T_PRODUCER);
+  h->t_contract_ms = t.sum(T_CONTRACT);
+  const bool whole = std::any_of(t.spans.begin(), t.spans.end(), [](const SpanTimer::Span& s) { return s.kind == T_WHOLE; });
+  h->t_acq_ms = whole ? t.sum(T_WHOLE) - h->t_corr_ms - h->t_contract_ms : t.sum(T_CRITERIA);
 }
+
 
 int bogp::candidates_ready(bogp_handle* h) { return lazy_finish(h); }
 void bogp::clear_sweep_timing(bogp_handle* h) {
@@ -516,12 +484,8 @@ static int sweep_one_launch(bogp_handle* h, const SweepRequest& rq) {
     HIPCHK(h, hipMemsetAsync(h->dbatch, 0, 8 * sizeof(double), st));
     sa.stamps = (long long*)h->dbatch.ptr;
   }
-  hipEvent_t e0 = h->ev.at(0), e1 = h->ev.at(1);
-  if (!e0 || !e1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  HIPCHK(h, hipEventRecord(e0, st));
-  HIPCHK(h, launch_sweep_small(h->kernel, sa, h->n_cu, st));
-  HIPCHK(h, hipEventRecord(e1, st));
-  h->n_chunks = 1; h->timing_pending = true; h->timing_fused = true; h->timing_prune = false; h->prune_used = false;
+  if ((e = timed_span(h, h->timer, st, T_CONTRACT, [&] { return launch_sweep_small(h->kernel, sa, h->n_cu, st); }))) return e;  // one kernel: reported as the contraction's time
+  h->n_chunks = 1; h->timing_pending = true; h->prune_used = false;
   h->contracted_rows = rq.need_var ? M : 0;
   if (rq.sync || stamps) HIPCHK(h, hipStreamSynchronize(st));
   if (stamps) {
@@ -628,24 +592,24 @@ static int sweep_trend_chunk(bogp_handle* h, const SweepCtx& cx, int b, int64_t 
 
 // One chunk of the per-chunk pruned flow, behind its producer: in chunk 0 the pilot (unless `skip` rows of it are done already), then
 // bound -> scan + decision -> compaction -> gather, the contractions of both outcomes, criteria and the running best.  `model`: the
-// criteria kernel's arguments less the arrays; `ka`: the chunk's contraction.
-static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model, const ContractArgs& ka, int64_t c, int64_t c_end, int64_t m0, int64_t mcount, int64_t skip) {
+// criteria kernel's arguments less the arrays; `ka`: the chunk's contraction; `e1`: the mark behind the chunk's producer.
+static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model, const ContractArgs& ka, int64_t c, int64_t c_end, int64_t m0, int64_t mcount, int64_t skip, int e1) {
   hipStream_t st = cx.st;
   long long* const pctl = cx.pctl;
   const int64_t Mc = cx.g.Mc, Ms = cx.Ms, nblk_total = cx.nblk_total;
   const int q = cx.rq.q;
-  hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
+  SpanTimer& tm = h->timer;
+  int e, p0 = -1, p1 = -1, e2 = 0, e3 = 0, e4 = 0;
   int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
   if (skip > 0) i0 = skip;
   else if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
     const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
-    hipEvent_t* evp = &h->ev[(size_t)(cx.g.nchunk * EPC + 1)];
     HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
-    HIPCHK(h, hipEventRecord(evp[0], st));
+    if ((e = tm.mark(h, st, &p0))) return e;
     ContractArgs kp = ka;
     kp.nMt = (int)((P + 63) / 64);
     HIPCHK(h, launch_contract(kp, st, h->contract_tile));
-    HIPCHK(h, hipEventRecord(evp[1], st));
+    if ((e = tm.mark(h, st, &p1))) return e;
     AcqArgs ap = model;
     ap.mu_part = h->dmu_part[0]; ap.w_part = h->dw_part[0]; ap.ss_part = h->dss_part; ap.Mc = Mc; ap.mcount = P; ap.m0 = 0;
     HIPCHK(h, launch_acquisition(ap, st));
@@ -667,7 +631,12 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
   }
   // the buffer goes through the contraction behind the last chunk, and whenever the next chunk's quarter might not fit
   const bool flush = cx.prune_pending > 0 && (c + 1 == c_end || cx.prune_pending + Mc / 4 > Ms);
-  HIPCHK(h, hipEventRecord(ev[2], st));
+  if ((e = tm.mark(h, st, &e2))) return e;
+  if (p0 < 0) {
+    tm.span(T_CRITERIA, e1, e2);
+  } else {  // (the pilot's contraction ran in between)
+    tm.span(T_CRITERIA, e1, p0); tm.span(T_CONTRACT, p0, p1); tm.span(T_CRITERIA, p1, e2);
+  }
   // in place or gathered is decided on the device: both contractions are queued, workgroups past the live count return at once
   if (rcount > 0) {
     ContractArgs ki = ka;
@@ -679,7 +648,7 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
     kf.rT = h->drT[1]; kf.ss_part = cx.dss_surv; kf.Mc = Ms; kf.nMt = (int)(Ms / 64); kf.live = pctl + 0;
     HIPCHK(h, launch_contract(kf, st, h->contract_tile));
   }
-  HIPCHK(h, hipEventRecord(ev[3], st));
+  if ((e = tm.mark(h, st, &e3))) return e;
   if (rcount > 0) {
     AcqArgs ai = model;
     ai.mu_part = h->dmu_part[0] + i0; ai.w_part = h->dw_part[0] + i0; ai.ss_part = h->dss_part + i0; ai.Mc = Mc; ai.mcount = rcount;
@@ -696,7 +665,8 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
     HIPCHK(h, launch_prune_flushed(pctl, st));
     cx.prune_pending = 0;
   }
-  HIPCHK(h, hipEventRecord(ev[4], st));
+  if ((e = tm.mark(h, st, &e4))) return e;
+  tm.span(T_CONTRACT, e2, e3); tm.span(T_CRITERIA, e3, e4);
   return BOGP_OK;
 }
 
@@ -710,9 +680,11 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
   const int Np = h->Np, S = cx.g.S;
   const bool overlap = cx.overlap, vx = cx.vx;
   const AcqArgs model = acq_model_args(h, rq, S, cx.nJ_main, cx.nblk_total);
+  SpanTimer& tm = h->timer;
+  int done[2] = {-1, -1};  // two-stream mode: chunk c leaves its last mark in [c & 1], where chunk c + 2 finds it
   for (int64_t c = c_begin; c < c_end; ++c) {
     const int b = overlap ? (int)(c & 1) : 0;
-    hipEvent_t* ev = &h->ev[(size_t)(c * EPC)];
+    int e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;
     const int64_t m0 = c * Mc;
     const int64_t mcount = std::min<int64_t>(Mc, M - m0);
     const int64_t Mc_eff = ((mcount + 63) / 64) * 64;  // rows actually launched; array stride stays Mc
@@ -724,13 +696,13 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
     ka.rT = h->drT[b]; ka.Vp = vx ? h->dVpx : h->dVp; ka.ss_part = h->dss_part; ka.Mc = Mc; ka.nMt = (int)(Mc_eff / 64); ka.nJ = cx.nJ;
     ka.NJ16 = cx.NJ16; ka.NKP = cx.Nrows / 8;
     // producer: may reuse buffer b only after chunk c-2 (its previous user) is completely done
-    if (overlap && c >= 2) HIPCHK(h, hipStreamWaitEvent(stP, h->ev[(size_t)((c - 2) * EPC + 4)], 0));
+    if (overlap && c >= 2) HIPCHK(h, hipStreamWaitEvent(stP, tm.event(done[c & 1]), 0));
     // trend-rows models: k_trend_rows (below, on the producer stream) writes h->dmtrend, which is NOT double buffered -- chunk c - 1's
     // k_acquisition on the main stream must have read it first (without this wait chunk c - 1 could get chunk c's means)
-    if (overlap && vx && c >= 1) HIPCHK(h, hipStreamWaitEvent(stP, h->ev[(size_t)((c - 1) * EPC + 4)], 0));
+    if (overlap && vx && c >= 1) HIPCHK(h, hipStreamWaitEvent(stP, tm.event(done[(c - 1) & 1]), 0));
     int e;  // lazily uploaded candidates: this chunk's rows must have arrived (chunk 0: copied here; later ones: below)
     if ((e = lazy_copy_to(h, m0 + mcount)) || (e = lazy_wait(h, stP)) || (stP != st && (e = lazy_wait(h, st)))) return e;
-    HIPCHK(h, hipEventRecord(ev[0], stP));
+    if ((e = tm.mark(h, stP, &e0))) return e;
     const int64_t skip = pilot_done && c == 0 ? std::min<int64_t>(PRUNE_PILOT, mcount) : 0;  // (a multiple of 64)
     if (skip > 0) {
       ca.m0 += skip; ca.rT += skip; ca.mu_part += skip; ca.w_part += skip;
@@ -741,16 +713,17 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
       HIPCHK(h, launch_trend_rows(h->trend, h->dXs, m0, mcount, Mc_eff, h->d, Mc, h->dbetav, h->drT[b] + (size_t)h->vx_Ne * Mc, h->p,
                                   h->vx_Nt - h->vx_Ne, h->dmtrend, stP));
     }
-    HIPCHK(h, hipEventRecord(ev[1], stP));
-    if (overlap) HIPCHK(h, hipStreamWaitEvent(st, ev[1], 0));
+    if ((e = tm.mark(h, stP, &e1))) return e;
+    tm.span(T_PRODUCER, e0, e1);
+    if (overlap) HIPCHK(h, hipStreamWaitEvent(st, tm.event(e1), 0));
     if (cx.prune) {
-      if ((e = sweep_pruned_chunk(h, cx, model, ka, c, c_end, m0, mcount, skip))) return e;
+      if ((e = sweep_pruned_chunk(h, cx, model, ka, c, c_end, m0, mcount, skip, e1))) return e;
     } else {
-      HIPCHK(h, hipEventRecord(ev[2], st));
+      if ((e = tm.mark(h, st, &e2))) return e;
       // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
       // and k_acquisition sums zero variance groups (its MSE output is not read)
       if (rq.need_var) HIPCHK(h, launch_contract(ka, st, h->contract_tile));
-      HIPCHK(h, hipEventRecord(ev[3], st));
+      if ((e = tm.mark(h, st, &e3))) return e;
       AcqArgs aa = model;
       aa.mu_part = h->dmu_part[b]; aa.w_part = h->dw_part[b]; aa.ss_part = h->dss_part; aa.nJ = rq.need_var ? cx.nJ_main : 0; aa.Mc = Mc;
       aa.nJ_plus = vx ? cx.nJ - cx.nJ_main : 0;
@@ -773,30 +746,13 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
       } else {
         HIPCHK(h, launch_acquisition(aa, st));
       }
-      HIPCHK(h, hipEventRecord(ev[4], st));
+      if ((e = tm.mark(h, st, &e4))) return e;
+      tm.span(T_CONTRACT, e2, e3); tm.span(T_CRITERIA, e3, e4);
+      done[c & 1] = e4;
     }
     cx.blk_offset += (mcount + 255) / 256;
     if ((e = lazy_copy_to(h, m0 + mcount + Mc))) return e;  // the next chunk's rows travel while this chunk's kernels (queued above) run
   }
-  return BOGP_OK;
-}
-
-// the next event of a one-pass sweep, recorded on st; *idx = its index in h->ev
-static int mark_event(bogp_handle* h, hipStream_t st, size_t* ev_next, int* idx) {
-  hipEvent_t ev1 = h->ev.at(*ev_next);
-  if (!ev1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  HIPCHK(h, hipEventRecord(ev1, st));
-  *idx = (int)(*ev_next)++;
-  return BOGP_OK;
-}
-// a producer (kind 0) or contraction (kind 1) launch between two events of its own (h->t_spans: kind, begin, end)
-template <class Launch>
-static int timed_span(bogp_handle* h, hipStream_t st, size_t* ev_next, int kind, Launch launch) {
-  int a = 0, b = 0, e;
-  if ((e = mark_event(h, st, ev_next, &a))) return e;
-  HIPCHK(h, launch());
-  if ((e = mark_event(h, st, ev_next, &b))) return e;
-  h->t_spans.push_back(kind); h->t_spans.push_back(a); h->t_spans.push_back(b);
   return BOGP_OK;
 }
 
@@ -810,9 +766,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   long long* const pctl = cx.pctl;
   const int64_t P = std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
   long long* const hcount = reinterpret_cast<long long*>(h->hfit + 3504);  // pinned: the one count the host waits for
-  size_t ev_next = (size_t)(nchunk * EPC + 3);
-  h->t_spans.clear(); h->t_chunks.clear();
-  int e;
+  int e, w0 = 0, w1 = 0;  // (the marks around the whole sweep)
   // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
   // (`through`: the flagged rows are rows of that list -- S out of S1 -- and their entries of it are what is kept)
   auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out, const unsigned char* flags, int64_t* sidx, const int64_t* through) -> int {
@@ -834,7 +788,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   // rows [0, cnt) of the survivor buffer (already produced) -> contraction, criteria (global indices through `map`, or m0 = 0), running best
   auto evaluate = [&](int64_t cnt, const int64_t* map) -> int {
     kc.nMt = (int)((cnt + 63) / 64);
-    if (int e2 = timed_span(h, st, &ev_next, 1, [&] { return launch_contract(kc, st, h->contract_tile); })) return e2;
+    if (int e2 = timed_span(h, h->timer, st, T_CONTRACT, [&] { return launch_contract(kc, st, h->contract_tile); })) return e2;
     ++contract_launches;
     aa.mcount = cnt; aa.map = map;
     HIPCHK(h, launch_acquisition(aa, st));
@@ -846,14 +800,13 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
     int e2;
     if ((e2 = h->drT[0].ensure(h, (size_t)cx.Nrows * Mc))) return e2;
     if ((e2 = sweep_chunks(h, cx, c0, c1, true))) return e2;
-    for (int64_t c = c0; c < c1; ++c) h->t_chunks.push_back(c);
     contract_launches += (int)(c1 - c0);
     h->prune_path = path;
     return BOGP_OK;
   };
-  if ((e = mark_event(h, st, &ev_next, &h->t_total[0]))) return e;
+  if ((e = h->timer.mark(h, st, &w0))) return e;
   HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
-  if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cc, (int)(P / 64), S, st); }))) return e;
+  if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cc, (int)(P / 64), S, st); }))) return e;
   if ((e = evaluate(P, nullptr))) return e;
   // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
   long long pilot_surv = 0;
@@ -877,7 +830,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         ba.Xs = h->dXs; ba.M = M; ba.m0 = sb; ba.rcount = rows; ba.d = h->d; ba.Np = h->Np; ba.sqrt_theta = h->dsqrt_theta;
         ba.estimate_trend = pb.estimate_trend;
         ba.md = md32; ba.mu = cx.pmu32; ba.wd = cx.pwd32; ba.na = cx.pna32;
-        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_bound32_sums(kernel, ba, st); }))) return e;
+        if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_bound32_sums(kernel, ba, st); }))) return e;
         PruneBoundArgs p1 = pb;
         p1.mu_part = cx.pmu32; p1.w_part = cx.pwd32; p1.S = 1; p1.Mc = rows; p1.rcount = rows; p1.flags = cx.pflags1;
         HIPCHK(h, launch_bound32_flags(p1, kernel, h->d, cx.pwd32, cx.pna32, md32, st));
@@ -889,7 +842,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         }
       }
       if (s1 < 0) {
-        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
+        if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
         pb.rcount = rows;
         HIPCHK(h, launch_prune_bound(pb, st));
         if ((e = survivors_of(rows, sb, &surv, cx.pflags, cx.psidx, nullptr))) return e;
@@ -897,7 +850,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         // stage 2: the exact sums of S1's rows alone (a row's sums do not depend on its neighbours), the exact bound, S in the original order
         HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx1, s1, h->d, cx.pxc1, st));
         cs.Xs = cx.pxc1; cs.M = s1; cs.m0 = 0;
-        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cs, (int)((s1 + 63) / 64), S, st); }))) return e;
+        if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cs, (int)((s1 + 63) / 64), S, st); }))) return e;
         pb.rcount = s1;
         HIPCHK(h, launch_prune_bound(pb, st));
         if ((e = survivors_of(s1, 0, &surv, cx.pflags, cx.psidx, cx.psidx1))) return e;
@@ -911,28 +864,29 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx + k0, cnt, h->d, cx.pxc, st));
         CorrArgs cr = cc;
         cr.Xs = cx.pxc; cr.M = cnt;
-        if ((e = timed_span(h, st, &ev_next, 0, [&] { return launch_corr_chunk(kernel, cr, (int)((cnt + 63) / 64), S, st); }))) return e;
+        if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cr, (int)((cnt + 63) / 64), S, st); }))) return e;
         if ((e = evaluate(cnt, cx.psidx + k0))) return e;
         ++h->prune_rounds;
       }
       h->prune_survivors += surv;
     }
   }
-  if ((e = mark_event(h, st, &ev_next, &h->t_total[1]))) return e;
-  h->timing_onepass = true;
+  if ((e = h->timer.mark(h, st, &w1))) return e;
+  h->timer.span(T_WHOLE, w0, w1);
   h->n_chunks = contract_launches;
   return BOGP_OK;
 }
 
 int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   collect_timing(h);  // the events are about to be re-recorded
+  h->timer.begin();
   if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "no committed model: call bogp_commit first");
   if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "no candidates: call bogp_candidates_upload/bind first");
   if (rq.q < 0 || rq.q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "q = %d outside [0, %d]", rq.q, BOGP_MAX_Q);
   HIPCHK(h, hipSetDevice(h->device));
   const int Np = h->Np, q = rq.q;
   const int64_t M = h->M;
-  h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0; h->timing_onepass = false;
+  h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0;
   h->b32_rows = h->b32_kept = h->b32_last_rows = 0; h->b32_fallbacks = 0;
   int e;
   // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- and bogp_sweep_constrained -- cn non-null -- take neither: they
@@ -978,12 +932,10 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   if (cx.bound32 && (h->b32_gen != h->commit_gen || h->b32_target != h->target) && (e = bound32_prepare(h))) return e;  // (another target since the commit)
   if ((e = sweep_workspace(h, cx))) return e;
   if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * rq.targets() : 0, rq.want_acq_out))) return e;
-  // the chunks' events, the two-stream mode's begin event, the pilot's pair (pruned sweep)
-  for (size_t i = 0; i <= (size_t)(nchunk * EPC + 2); ++i)
-    if (!h->ev.at(i)) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
   if (cx.overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
-    HIPCHK(h, hipEventRecord(h->ev[(size_t)(nchunk * EPC)], cx.st));
-    HIPCHK(h, hipStreamWaitEvent(cx.stP, h->ev[(size_t)(nchunk * EPC)], 0));
+    int b0 = 0;
+    if ((e = h->timer.mark(h, cx.st, &b0))) return e;
+    HIPCHK(h, hipStreamWaitEvent(cx.stP, h->timer.event(b0), 0));
   }
   if (!cx.onepass) {
     if ((e = sweep_chunks(h, cx, 0, nchunk, false))) return e;
@@ -996,7 +948,7 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   if ((e = lazy_finish(h))) return e;
   // (a pruned sweep kept its running best in dbest_* all along)
   if (q > 0 && !cx.prune) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, cx.blk_offset, cx.nblk_total, q, h->dbest_val, h->dbest_idx, cx.st));
-  h->timing_pending = true; h->timing_fused = false; h->timing_prune = cx.prune; h->prune_used = cx.prune;
+  h->timing_pending = true; h->prune_used = cx.prune;
   h->contracted_rows = rq.need_var ? M : 0;
   if (rq.sync || cx.overlap) HIPCHK(h, hipStreamSynchronize(cx.st));
   if (cx.overlap) HIPCHK(h, hipStreamSynchronize(cx.stP));

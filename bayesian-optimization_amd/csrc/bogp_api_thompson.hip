@@ -110,11 +110,11 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   memset(&ta, 0, sizeof(ta));
   ta.d = d; ta.L = L; ta.N = N; ta.q = q; ta.omega = domega; ta.phase = dphase; ta.W = dW;
 
-  size_t nev = 0;
-  auto event = [&]() -> hipEvent_t { return h->th_ev.at(nev++); };
-  hipEvent_t s0 = event(), s1 = event();
-  if (!s0 || !s1) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-  HIPCHK(h, hipEventRecord(s0, st));
+  enum { TH_SOLVE, TH_PRODUCER, TH_PATHS };  // kinds of the spans on h->th_timer
+  SpanTimer& tm = h->th_timer;
+  tm.begin();
+  int s0 = 0, s1 = 0;
+  if ((rc = tm.mark(h, st, &s0))) return rc;
   std::vector<double> hb(16, 0.0), hg((size_t)N * q, 0.0);
   if (conditioned) {
     // ---- 1: the draw at the training rows, plus what the nugget adds to an observation
@@ -152,7 +152,8 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
     HIPCHK(h, hipMemcpyAsync(dng, hng.data(), hng.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));  // (hng leaves scope)
   }
-  HIPCHK(h, hipEventRecord(s1, st));
+  if ((rc = tm.mark(h, st, &s1))) return rc;
+  tm.span(TH_SOLVE, s0, s1);
   if (coef_out) {
     memcpy(coef_out, hg.data(), (size_t)N * q * sizeof(double));
     for (int j = 0; j < q; ++j) coef_out[(size_t)N * q + j] = hb[j];
@@ -163,19 +164,17 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   ta.rT = h->drT[0]; ta.ld = Mc; ta.ngt = dng; ta.mu_part = h->dmu_part[0]; ta.S = S; ta.beta = h->beta;
   for (int j = 0; j < 16; ++j) ta.bt[j] = hb[j];
   ta.blk_val = h->dblk_val; ta.blk_idx = h->dblk_idx; ta.nblk_total = nblk_total;
-  std::vector<size_t> ev_chunk;
   int64_t blk_offset = 0;
   for (int64_t c = 0; c < nchunk; ++c) {
     const int64_t m0 = c * Mc, mcount = std::min<int64_t>(Mc, M - m0), Mc_eff = ((mcount + 63) / 64) * 64;
-    ev_chunk.push_back(nev);
-    hipEvent_t c0 = event(), c1 = event(), c2 = event();
-    if (!c0 || !c1 || !c2) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(h, hipEventRecord(c0, st));
+    int c0 = 0, c1 = 0, c2 = 0;
+    if ((rc = tm.mark(h, st, &c0))) return rc;
     if (conditioned) HIPCHK(h, launch_corr_chunk(h->kernel, corr_chunk_args(h, geo, m0, 0), (int)(Mc_eff / 64), S, st));
-    HIPCHK(h, hipEventRecord(c1, st));
+    if ((rc = tm.mark(h, st, &c1))) return rc;
     ta.row0 = m0; ta.mcount = mcount; ta.blk_offset = blk_offset;
     HIPCHK(h, launch_thompson(ta, st));
-    HIPCHK(h, hipEventRecord(c2, st));
+    if ((rc = tm.mark(h, st, &c2))) return rc;
+    tm.span(TH_PRODUCER, c0, c1); tm.span(TH_PATHS, c1, c2);
     blk_offset += (mcount + 63) / 64;
   }
 
@@ -207,17 +206,7 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
     HIPCHK(h, hipStreamSynchronize(st));
   }
 
-  h->th_corr_ms = h->th_paths_ms = 0;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, s0, s1);
-  h->th_solve_ms = ms;
-  for (size_t e : ev_chunk) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, h->th_ev[e], h->th_ev[e + 1]);
-    (void)hipEventElapsedTime(&b, h->th_ev[e + 1], h->th_ev[e + 2]);
-    h->th_corr_ms += a;
-    h->th_paths_ms += b;
-  }
+  h->th_solve_ms = tm.sum(TH_SOLVE); h->th_corr_ms = tm.sum(TH_PRODUCER); h->th_paths_ms = tm.sum(TH_PATHS);
   h->th_chunks = (int)nchunk;
   return BOGP_OK;
 }

@@ -1,5 +1,6 @@
 // bogp_handle.h -- the device state behind an opaque bogp_handle (include/bogp.h), the three types that own its device memory,
-// pinned blocks and events (DevBuf, MappedBuf, EventPool), and the error plumbing shared by the translation units that implement the C ABI.
+// pinned blocks and events (DevBuf, MappedBuf, EventPool), the span ledger of its event timing (SpanTimer), and the error plumbing shared
+// by the translation units that implement the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,6 +50,8 @@ int bound32_prepare(bogp_handle* h);  // bogp_api_sweep.hip: the FP32 copies of 
 // sweep timing zeroed (a lifted sweep without a feasible row runs no posterior pass)
 int candidates_ready(bogp_handle* h);
 void clear_sweep_timing(bogp_handle* h);
+// kinds of the spans on the handle's `timer` (what bogp_last_timing makes of them per path: the table above collect_timing, bogp_api_sweep.hip)
+enum { T_PRODUCER, T_CONTRACT, T_CRITERIA, T_WHOLE };
 // the candidate calls need the row width d: from bogp_set_train or from bogp_forest_set
 bool has_dim(const bogp_handle* h);
 // dehvi_cells was overwritten by a sweep: bogp_point_eval_ehvi must upload its cells again
@@ -124,6 +127,32 @@ struct EventPool {
   }
   hipEvent_t& operator[](size_t i) { return ev[i]; }  // an event that at() has created
 };
+
+// The event timing of one call: marks (events of the pool, recorded in the order they are taken) and spans (two marks that bracket work
+// of one kind; adjacent spans may share a mark).  What a kind means is its user's business.
+struct SpanTimer {
+  struct Span { int kind, a, b; };
+  EventPool pool;
+  size_t next = 0;
+  std::vector<Span> spans;
+  void begin() { next = 0; spans.clear(); }             // a new call: the events are handed out from the first again
+  int mark(bogp_handle* h, hipStream_t st, int* idx);  // the next event, created on demand and recorded on st; *idx = its index
+  hipEvent_t event(int idx) { return pool[(size_t)idx]; }
+  void span(int kind, int a, int b) { spans.push_back({kind, a, b}); }
+  double sum(int kind) {  // ms over the spans of `kind`, each waited for
+    double ms = 0;
+    for (const Span& s : spans) {
+      float t = 0;
+      if (s.kind != kind) continue;
+      (void)hipEventSynchronize(pool[(size_t)s.b]);
+      (void)hipEventElapsedTime(&t, pool[(size_t)s.a], pool[(size_t)s.b]);
+      ms += t;
+    }
+    return ms;
+  }
+};
+template <class Launch>  // a launch between two marks of its own on tm: one span of `kind` (defined behind HIPCHK, below)
+int timed_span(bogp_handle* h, SpanTimer& tm, hipStream_t st, int kind, Launch launch);
 }  // namespace bogp
 
 struct bogp_handle {
@@ -243,7 +272,7 @@ struct bogp_handle {
   bogp::DevBuf<double> dlift_Z;     // [M_f][r] the feasible rows in their original order
   bogp::DevBuf<int64_t> dlift_map;  // [M_f] their original indices
   bogp::DevBuf<double> dlift_val;   // [q][M] merged values
-  bogp::EventPool lift_ev;          // [4] filter begin / end, merge begin / end
+  bogp::SpanTimer lift_timer;       // filter, merge (run_sweep, on the sweep's own timer, runs between them)
   int64_t lift_n_feasible = 0;
   double lift_filter_ms = 0, lift_merge_ms = 0;
 
@@ -252,7 +281,7 @@ struct bogp_handle {
   bogp::DevBuf<double> dbel_C;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
   bogp::DevBuf<double> dbel_row;    // [2][M] criterion values / MSE of the step evaluated last
   bogp::DevBuf<double> dbel_small;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
-  bogp::EventPool bel_ev;
+  bogp::SpanTimer bel_timer;        // solves, chunk producers, k_believer, k_believer_ehvi (run_sweep restarts the sweep's own)
   double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
   // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
@@ -260,7 +289,7 @@ struct bogp_handle {
 
   // Thompson-sampling batches (bogp_api_thompson.hip)
   bogp::DevBuf<double> dth_small;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight
-  bogp::EventPool th_ev;
+  bogp::SpanTimer th_timer;        // draw at X + solves, chunk producers, k_thompson
   double th_corr_ms = 0, th_solve_ms = 0, th_paths_ms = 0;  // of the last bogp_sweep_thompson: producer, draw at X + solves, k_thompson
   int th_chunks = 0;
 
@@ -271,7 +300,6 @@ struct bogp_handle {
   int64_t forest_nodes = 0, forest_leaves = 0;
   bogp::DevBuf<unsigned long long> dforest_words;
   bogp::DevBuf<bogp::ForestTree> dforest_tree;
-  bogp::EventPool forest_ev;  // [2] around k_forest of the last forest call
 
   // polynomial trend bases with p > 1 columns (linear / quadratic; the constant basis keeps its scalar fast path)
   int trend = BOGP_TREND_CONSTANT, p = 1;  // committed
@@ -338,15 +366,10 @@ struct bogp_handle {
   size_t bws_row = 0;
 
   // timing of the last sweep/predict
-  bogp::EventPool ev;
+  bogp::SpanTimer timer;  // spans of the last sweep / predict / forest call (kinds and their meaning per path: collect_timing, bogp_api_sweep.hip)
   double t_corr_ms = 0, t_contract_ms = 0, t_acq_ms = 0;
   int n_chunks = 0;
-  bool timing_pending = false, timing_fused = false;  // event times not read back yet / of the one-launch small-N sweep
-  bool timing_onepass = false;   // ... of a sweep that began on the one-pass flow: t_spans = (kind, begin event, end event) of each producer (0) /
-  std::vector<int> t_spans;      // contraction (1) launch of its own, t_chunks = the chunks a fall-back ran, t_total = first / last event
-  std::vector<int64_t> t_chunks;
-  int t_total[2] = {0, 0};
-  bool timing_prune = false;  // ... of a pruned sweep: bound / compaction / gather sit between a chunk's events [1] and [2], the pilot's events behind the chunks'
+  bool timing_pending = false;  // the spans have not been read into the three times yet
 };
 
 #define FAIL(h, code, ...)                              \
@@ -390,6 +413,22 @@ inline int bogp::MappedBuf::ensure(bogp_handle* h, size_t n) {
   live_note(1, n * sizeof(double));
   HIPCHK(h, hipHostGetDevicePointer((void**)&dev, ptr, 0));
   memset(ptr, 0, n * sizeof(double));
+  return BOGP_OK;
+}
+inline int bogp::SpanTimer::mark(bogp_handle* h, hipStream_t st, int* idx) {
+  hipEvent_t e = pool.at(next);
+  if (!e) FAIL(h, BOGP_ERR_HIP, "hipEventCreate failed");
+  HIPCHK(h, hipEventRecord(e, st));
+  *idx = (int)next++;
+  return BOGP_OK;
+}
+template <class Launch>
+inline int bogp::timed_span(bogp_handle* h, SpanTimer& tm, hipStream_t st, int kind, Launch launch) {
+  int a = 0, b = 0, e;
+  if ((e = tm.mark(h, st, &a))) return e;
+  HIPCHK(h, launch());
+  if ((e = tm.mark(h, st, &b))) return e;
+  tm.span(kind, a, b);
   return BOGP_OK;
 }
 // (for the two local temporaries of bogp_selftest_profile, kernels_profile.hip; the handle's buffers free themselves)

@@ -645,7 +645,9 @@ int bogp_merge_topk(int R, int q, int k, int d, const double* gathered, double* 
 /* ---- measurement ----------------------------------------------------------------------------------
  * HIP-event durations (ms, summed over candidate chunks) of the kernels of the LAST bogp_predict /
  * bogp_sweep call, recorded on the library's own stream: corr (k_corr_chunk, the K* producer), contract
- * (k_contract, the dominant L^-1 MFMA contraction) and acquisition/argmax.  n_chunks = launches of each.  */
+ * (k_contract, the dominant L^-1 MFMA contraction) and acquisition/argmax.  n_chunks = launches of each.
+ * Which intervals each field sums on each sweep path (one launch, chunks, pruned chunks, one pass, forest):
+ * the table above collect_timing in csrc/bogp_api_sweep.hip.  */
 int bogp_last_timing(bogp_handle* h, double* corr_ms, double* contract_ms, double* acquisition_ms, int* n_chunks);
 
 /* ---- pruned sweep -----------------------------------------------------------------------------------

@@ -38,6 +38,6 @@ def test_the_handle_keeps_no_capacity_field():
     src = _code(DEFINING)
     start = src.index("struct bogp_handle {")
     body = src[start : src.index("\n};", start)]
-    assert "DevBuf<double> dX" in body and "EventPool ev;" in body and "MappedBuf hfit;" in body  # the struct, not a forward declaration
+    assert "DevBuf<double> dX" in body and "SpanTimer timer;" in body and "MappedBuf hfit;" in body  # the struct, not a forward declaration
     caps = set(re.findall(r"\b(\w*_cap\w*|cap_\w+)\b", body))
     assert caps == {"cap_ld", "cap_d", "cap_nt"}, sorted(caps)  # the training set's geometry, not buffer capacities
