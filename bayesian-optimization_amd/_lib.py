@@ -112,6 +112,11 @@ SIGNATURES = {
     "bogp_point_eval_ehvi": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "bogp_polish_ehvi": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double,
                                    _dp, _dp, _ip]),
+    "bogp_feasibility_grad": (C.c_int, [C.c_double] * 5 + [_dp]),
+    "bogp_point_eval_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp,
+                                              _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "bogp_polish_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp,
+                                          C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -143,6 +148,7 @@ SIGNATURES = {
     "bogp_chol_wide_panels": (C.c_int, [C.c_int, _ip, C.c_int]),
     "bogp_selftest_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, C.c_int64, _dp]),
     "bogp_selftest_criteria": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int64, _dp]),
+    "bogp_selftest_feasibility_grad": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp]),
     "bogp_selftest_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_int, C.c_int]),
 }
 
@@ -204,6 +210,16 @@ def feasibility(mu: float, mse: float, sigma2: float, lo: float, hi: float) -> f
     """P(lo <= Y <= hi) for Y ~ N(mu, mse) as the constrained sweep forms it (bogp_feasibility: the indicator under EI's
     small-variance guard, else the difference of two normal cdfs taken in the tail the interval lies in).  No device is touched."""
     return float(load().bogp_feasibility(float(mu), float(mse), float(sigma2), float(lo), float(hi)))
+
+
+def feasibility_grad(mu: float, mse: float, sigma2: float, lo: float, hi: float) -> Tuple[float, float, float]:
+    """(F, dF/dmu, dF/dsd) of `feasibility` in the posterior's mean and standard deviation (bogp_feasibility_grad): F has the bits of
+    `feasibility`; both derivatives are exactly 0 under the small-variance guard, and an infinite side contributes exactly 0.  No
+    device is touched."""
+    out = np.empty(3)
+    if load().bogp_feasibility_grad(float(mu), float(mse), float(sigma2), float(lo), float(hi), _ptr(out)):
+        raise BogpError(ERR_INVALID, "bogp_feasibility_grad refused its arguments")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def grid_cells(Y, ref_point):
@@ -1112,6 +1128,68 @@ class Engine:
                                        int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))
         )  # fmt: skip
         return Xo, fo, ne
+
+    @staticmethod
+    def _constraint_bounds(lo, hi):
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        return lo, hi
+
+    def point_eval_constrained(self, X, acq: Sequence[Tuple[int, float]], plugin: float, minimize, lo, hi, moments: bool = False):
+        """q feasibility-weighted criteria of the committed multi-target model and their input gradients at the rows of `X` (B x d) in
+        ONE device round trip (bogp_point_eval_constrained); criteria, plugin, direction and the constraints' bounds as
+        `sweep_constrained`: (acq (B, q), dacq (B, q, d)) and, with `moments`, also pof (B,), dpof (B, d), mu (B, m), mse (B, m),
+        dmu (B, m, d), dmse (B, m, d)."""
+        X = np.atleast_2d(_f64(X))
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise Exception("x does not have the right size!")
+        lo, hi = self._constraint_bounds(lo, hi)
+        q, m = len(acq), len(lo) + 1
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        B, d = X.shape[0], self.d
+        vals, dvals = np.empty((B, q)), np.empty((B, q, d))
+        mom = ((np.empty(B), np.empty((B, d)), np.empty((B, m)), np.empty((B, m)), np.empty((B, m, d)), np.empty((B, m, d)))
+               if moments else (None,) * 6)  # fmt: skip
+        rc = self._lib.bogp_point_eval_constrained(self._h, _ptr(X), B, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin),
+                                                   int(bool(minimize)), len(lo), _ptr(lo), _ptr(hi), _ptr(vals), _ptr(dvals),
+                                                   *(_ptr(a) for a in mom))  # fmt: skip
+        if rc:
+            self._check(rc)
+        return (vals, dvals) + (mom if moments else ())
+
+    def polish_constrained(self, starts, box_lo, box_hi, acq: Tuple[int, float], plugin: float, minimize, lo, hi, max_evals: int = 50,
+                           pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local maximisation of one feasibility-weighted criterion inside the box (bogp_polish_constrained):
+        (points (B, d), values (B,), evaluations used (B,)); values[i] >= the criterion at starts[i] clipped into the box."""
+        X0 = np.atleast_2d(_f64(starts))
+        if X0.ndim != 2 or X0.shape[1] != self.d:
+            raise Exception("x does not have the right size!")
+        box_lo, box_hi = _f64(box_lo).ravel(), _f64(box_hi).ravel()
+        if len(box_lo) != self.d or len(box_hi) != self.d:
+            raise ValueError("box_lo / box_hi must have d entries")
+        lo, hi = self._constraint_bounds(lo, hi)
+        B = X0.shape[0]
+        Xo, fo, ne = np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
+        self._check(
+            self._lib.bogp_polish_constrained(self._h, _ptr(X0), B, _ptr(box_lo), _ptr(box_hi), int(acq[0]),
+                                              float(acq[1]) if acq[1] is not None else 0.0, float(plugin), int(bool(minimize)), len(lo),
+                                              _ptr(lo), _ptr(hi), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
+                                              ne.ctypes.data_as(_ip))
+        )  # fmt: skip
+        return Xo, fo, ne
+
+    feasibility_grad = staticmethod(feasibility_grad)
+
+    def selftest_feasibility_grad(self, mu, mse, sigma2, lo, hi):
+        """feasibility_grad of csrc/bogp_device.h on the device, one row of (mu, mse, sigma2, lo, hi) each (scalars or arrays, broadcast):
+        (n, 3) = F, dF/dmu, dF/dsd (bogp_selftest_feasibility_grad)."""
+        cols = np.broadcast_arrays(*[np.asarray(c, dtype=np.float64).ravel() for c in (mu, mse, sigma2, lo, hi)])
+        rows = np.ascontiguousarray(np.stack(cols, axis=1))
+        out = np.empty((len(rows), 3))
+        self._check(self._lib.bogp_selftest_feasibility_grad(self._h, _ptr(rows), len(rows), _ptr(out)))
+        return out
 
     def hessian(self, x) -> np.ndarray:
         """(d, d) Hessian of the posterior mean at x (squared exponential; constant / linear trend)."""

@@ -424,16 +424,23 @@ class Constrained:
     whatever `fun` says.  The stored plugin is oriented for minimisation, as `ImprovementBased` stores it.
 
     `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the
-    engine's current candidates as `EHVI.sweep` does.  There is no input gradient (`return_dx=True` raises)."""
+    engine's current candidates as `EHVI.sweep` does.  By default there is no input gradient (`return_dx=True` raises).
+
+    `input_gradient=True` (an extension): `criterion(X, return_dx=True)` returns (values, dx) in the shapes
+    `EHVI(input_gradient=True)` returns -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through `bogp_point_eval_constrained`
+    (the derivative of the probability of feasibility and the criterion's chain rule on the device), `criterion(X)` for at most 64
+    rows takes the same call, and `argmax_restart` serves "BFGS", "sweep-BFGS" and "sweep-device-BFGS" for it."""
 
     is_constrained = True
     _IDS = {"EI": _lib.ACQ_EI, "PI": _lib.ACQ_EPSILON_PI, "EpsilonPI": _lib.ACQ_EPSILON_PI, "MGFI": _lib.ACQ_MGFI, None: _lib.ACQ_NONE}
 
-    def __init__(self, model=None, fun="EI", minimize: bool = True, plugin: float = None, lo=None, hi=None, **par):
+    def __init__(self, model=None, fun="EI", minimize: bool = True, plugin: float = None, lo=None, hi=None, input_gradient: bool = False,
+                 **par):
         if model is None:
             raise ValueError("model cannot be None")
         if _forest.is_forest_model(model):
             raise NotImplementedError("modelled constraints take a multi-target Gaussian process: a forest model is not served")
+        self.input_gradient = bool(input_gradient)
         if fun == "UCB":
             raise ValueError("UCB changes sign, so its product with a probability of feasibility orders nothing: use EI, PI, "
                              "EpsilonPI, MGFI or fun=None (feasibility only)")  # fmt: skip
@@ -499,10 +506,23 @@ class Constrained:
         return tuple(a[0] for a in out)
 
     def __call__(self, X, return_dx: bool = False):
-        if return_dx:
+        if return_dx and not self.input_gradient:
             raise NotImplementedError("the feasibility-weighted criterion has no input gradient yet (the gradient of the probability of "
                                       "feasibility is not implemented): use 'sweep' or 'sweep-device[-lhs|-sobol]'")  # fmt: skip
         if getattr(self.model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
+        if self.input_gradient:
+            rows = self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float)))
+            if return_dx or len(rows) <= 64:  # value and gradient in one device round trip (bogp_point_eval_constrained)
+                eng = self.model.engine
+                if not hasattr(eng, "point_eval_constrained"):
+                    raise NotImplementedError("the model's engine has no point_eval_constrained: no input gradient of the "
+                                              "feasibility-weighted criterion")  # fmt: skip
+                vals, dx = eng.point_eval_constrained(rows, [(self.acq_id, self.acq_par())], self.effective_plugin(), self.minimize,
+                                                      self.lo, self.hi)[:2]  # fmt: skip
+                vals, dx = vals[:, 0], dx[:, 0, :]
+                if not return_dx:
+                    return vals
+                return (vals.reshape(1), dx.reshape(1, -1)) if len(rows) == 1 else (vals.reshape(-1, 1), dx)
         self.model.engine.upload_candidates(self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float))))
         return self.sweep(return_values=True)[2]

@@ -1,6 +1,6 @@
 // bogp_api_constrained.hip -- the C ABI of libbogp.so (include/bogp.h) for modelled constraints: bogp_sweep_constrained, q
 // feasibility-weighted criteria of an m-target model (target 0 the objective, targets 1 .. m - 1 the constraints) over the current
-// candidates, and bogp_feasibility, the factor one constraint contributes, on the host.  The sweep is the chunked sweep of
+// candidates, and bogp_feasibility / bogp_feasibility_grad, the factor one constraint contributes and its derivatives, on the host.  The sweep is the chunked sweep of
 // bogp_api_sweep.hip (producer -> contraction per chunk) with k_constrained (kernels_constrained.hip) in place of k_acquisition.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,12 @@
 using namespace bogp;
 
 extern "C" double bogp_feasibility(double mu, double mse, double sigma2, double lo, double hi) { return feasibility(mu, mse, sigma2, lo, hi); }
+
+extern "C" int bogp_feasibility_grad(double mu, double mse, double sigma2, double lo, double hi, double* out3) {
+  if (!out3) return BOGP_ERR_INVALID;
+  feasibility_grad(mu, mse, sigma2, lo, hi, &out3[0], &out3[1], &out3[2]);
+  return BOGP_OK;
+}
 
 extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int n_con,
                                       const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,

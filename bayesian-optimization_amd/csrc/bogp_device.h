@@ -332,6 +332,70 @@ __host__ __device__ __forceinline__ double feasibility(double mu, double mse, do
   return za > 0 ? ndtr(-za) - ndtr(-zb) : ndtr(zb) - ndtr(za);
 }
 
+// feasibility() and its derivatives in the posterior's mean and standard deviation (the input gradient of a feasibility-weighted
+// criterion chains them with dmu/dx and dsd/dx, kernels_point_constrained.hip).  F is feasibility() itself.  With sd = sqrt(mse),
+// za = (lo - mu) / sd, zb = (hi - mu) / sd:  dF/dmu = (phi(za) - phi(zb)) / sd,  dF/dsd = (za phi(za) - zb phi(zb)) / sd.  An infinite
+// side contributes exactly 0 to both (selected, never inf * 0); under the small-variance guard F is an indicator and both derivatives
+// are exactly 0, as the reference's guards return a zero gradient.  lo == hi gives (0, 0, 0), two infinite sides (1, 0, 0).
+__host__ __device__ __forceinline__ void feasibility_grad(double mu, double mse, double sigma2, double lo, double hi, double* F, double* dF_dmu,
+                                                          double* dF_dsd) {
+  *F = feasibility(mu, mse, sigma2, lo, hi);
+  *dF_dmu = 0.0;
+  *dF_dsd = 0.0;
+  const double sd = sqrt(mse);
+  if (sd / sqrt(sigma2) < 1e-6) return;
+  const double za = (lo - mu) / sd, zb = (hi - mu) / sd;
+  const bool fa = !__builtin_isinf(lo), fb = !__builtin_isinf(hi);
+  const double pa = fa ? norm_pdf(za) : 0.0, pb = fb ? norm_pdf(zb) : 0.0;
+  const double ta = fa ? za * pa : 0.0, tb = fb ? zb * pb : 0.0;
+  *dF_dmu = (pa - pb) / sd;
+  *dF_dsd = (ta - tb) / sd;
+}
+
+// d acq / d x_k = a_dy * dy_k + a_dsd * dsd_k   (acquisition_fun.py:139-146, 181-188, 220-227, 292-309); the guards of
+// the reference return a zero gradient, its FloatingPointError path (np.errstate(all="raise")) likewise
+__device__ __forceinline__ void acq_grad_coef(int id, double par, double y, double sd, double plugin, double sigma2, double& a_dy,
+                                              double& a_dsd) {
+  a_dy = 0.0;
+  a_dsd = 0.0;
+  switch (id) {
+    case BOGP_ACQ_UCB:
+      a_dy = 1.0;
+      a_dsd = par;
+      return;
+    case BOGP_ACQ_EI: {
+      if (sd / sqrt(sigma2) < 1e-6) return;
+      const double z = (plugin - y) / sd;
+      a_dsd = norm_pdf(z);
+      a_dy = -ndtr(z);
+      return;
+    }
+    case BOGP_ACQ_EPSILON_PI: {
+      const double shrink = y > 0 ? 1 - par : 1 + par;
+      const double z = (plugin - shrink * y) / sd;
+      const double f = norm_pdf(z) / sd;
+      a_dy = -shrink * f;
+      a_dsd = -z * f;
+      return;
+    }
+    default: {  // MGFI
+      if (fabs(sd) <= 1e-8) return;
+      const double t = fmin(par, 22.36);
+      const double var = sd * sd;
+      const double z = (plugin - (y - t * var)) / sd;
+      const double scale = exp(t * (plugin + t * var / 2 - y - 1));
+      const double pdf = norm_pdf(z), cdf = ndtr(z);
+      const double c_dy = scale * (-pdf / sd - cdf * t);
+      const double c_dsd = scale * (pdf * (2.0 * t * sd - z) / sd + cdf * (t * t) * sd);
+      if (isfinite(c_dy) && isfinite(c_dsd) && isfinite(scale)) {
+        a_dy = c_dy;
+        a_dsd = c_dsd;
+      }
+      return;
+    }
+  }
+}
+
 // Upper bound of acq_value(id, par, y_hat, sd, ...) over sd in [0, sd_ub], guard branches (which return 0) included: what the pruned
 // sweep (kernels_prune.hip) compares with the best value found so far.  EI is non-decreasing in sd; UCB is linear in it; EpsilonPI is
 // ndtr(num / sd) with num = plugin - coef y_hat, i.e. 1 at most for num > 0, non-decreasing in sd for num < 0, and possibly NaN

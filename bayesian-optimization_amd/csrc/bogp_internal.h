@@ -729,5 +729,25 @@ struct PointEhviArgs {
   unsigned long long done_seq;
 };
 hipError_t launch_point_ehvi_finish(const PointEhviArgs& a, int B, hipStream_t st);
+// q feasibility-weighted criteria and their input gradients at B points of an m-target model (kernels_point_constrained.hip): the
+// finishing kernel behind k_point_rhs + k_point_tri (VALU flavour) in place of k_point_finish; target 0 the objective, targets
+// 1 .. m - 1 constraints feasible in [lo_k, hi_k] (ConstrainedArgs' convention)
+struct PointConstrainedArgs {
+  const double* part;   // [B][npass][nRB + 1][2 NC] block records of k_point_tri
+  const double* rhs;    // [B][npass][Npp][NC] right-hand sides of k_point_rhs
+  const double* gamma;  // [m][ld_gamma] the targets' gamma columns (gamma_base)
+  double* out;          // [B][rec_stride]: mu_0, MSE_0, acq (q), dmu_0 (d), dMSE_0 (d), dacq (q x d) -- k_point_finish's record
+  double* mom;          // [B][mom_stride]: P, dP (d), mu (m), MSE (m), dmu (m x d), dMSE (m x d), or null
+  int ld_gamma, N, Npp, nRB, npass, d, rec_stride, mom_stride;
+  int m, q, estimate_trend, minimize;
+  double beta, G, ftft, plugin;
+  double sigma2[8];     // per target
+  double lo[8], hi[8];  // per target; entry 0 is not read
+  int acq_id[64];       // BOGP_ACQ_EI / EPSILON_PI / MGFI, or BOGP_ACQ_NONE
+  double acq_par[64];
+  unsigned long long* done_flag;  // as PointTriArgs
+  unsigned long long done_seq;
+};
+hipError_t launch_point_constrained_finish(const PointConstrainedArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

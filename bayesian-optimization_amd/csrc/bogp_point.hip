@@ -1,6 +1,7 @@
 // bogp_point.hip -- C ABI of the one-point / B-point consumption path (kernels_point.hip): bogp_point_eval,
 // bogp_point_eval_batch, bogp_gradient_batch, bogp_polish, and of its multi-objective finish (kernels_point_ehvi.hip):
-// bogp_point_eval_ehvi, bogp_polish_ehvi.  See include/bogp.h for the contracts.
+// bogp_point_eval_ehvi, bogp_polish_ehvi, and of its feasibility-weighted finish (kernels_point_constrained.hip):
+// bogp_point_eval_constrained, bogp_polish_constrained.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -60,7 +61,8 @@ int ensure_counters(bogp_handle* h, size_t n) { return ensure_tickets(h, h->dpt_
 // queue k_point_rhs + k_point_tri for B points; the records land in `out` (device or device-mapped host memory)
 int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, const double* x_host, int B, int q, const int* acq_id,
                      const double* acq_par, double plugin, int minimize, bool want_dacq, double* out,
-                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0, const PointEhviArgs* eh = nullptr) {
+                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0, const PointEhviArgs* eh = nullptr,
+                     const PointConstrainedArgs* cn = nullptr) {
   hipStream_t st = h->stream;
   int e;
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
@@ -72,7 +74,7 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   const int ncp = point_mfma_columns(h->d);
   const char* e_min = getenv("BOGP_POINT_MFMA_MIN");  // read per call: the tests run both flavours in one process
   const long long mfma_min = e_min ? atoll(e_min) : 768LL;
-  if (!eh && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
+  if (!eh && !cn && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
     const int Np = h->Np, nJ = (Np + 255) / 256;
     const long long Mc = ((long long)B * ncp + 63) / 64 * 64;
     if ((e = h->drT[0].ensure(h, (size_t)Np * Mc))) return e;
@@ -141,14 +143,26 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
     HIPCHK(h, launch_point_ehvi_finish(ea, B, st));
     return BOGP_OK;
   }
+  if (cn) {  // the feasibility-weighted finish in place of k_point_finish (cn: criteria, bounds, the second blocks; the rest is filled in here)
+    HIPCHK(h, launch_point_tri(ta, B, st, false));
+    PointConstrainedArgs ca = *cn;
+    ca.part = h->dpt_part; ca.rhs = h->dpt_rhs; ca.gamma = h->dgamma_base; ca.ld_gamma = h->Np; ca.out = out;
+    ca.N = h->N; ca.Npp = pl.Npp; ca.nRB = pl.nRB; ca.npass = pl.npass; ca.d = h->d; ca.rec_stride = pl.rec_stride;
+    ca.estimate_trend = h->estimate_trend; ca.beta = h->beta; ca.G = h->G; ca.ftft = h->ftft;
+    for (int t = 0; t < ca.m; ++t) ca.sigma2[t] = h->sigma2_t[t];
+    ca.done_flag = done_flag; ca.done_seq = done_seq;
+    HIPCHK(h, launch_point_constrained_finish(ca, B, st));
+    return BOGP_OK;
+  }
   HIPCHK(h, launch_point_tri(ta, B, st));
   return BOGP_OK;
 }
 
-// the lock-step polish of B starts: bogp_polish's loop (one criterion of the single-target path) or -- eh non-null -- bogp_polish_ehvi's
+// the lock-step polish of B starts: bogp_polish's loop (one criterion of the single-target path), -- eh non-null -- bogp_polish_ehvi's or
+// -- cn non-null -- bogp_polish_constrained's
 int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const double* lo, const double* hi, int acq_id, double acq_par,
                 double plugin, int minimize, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals,
-                const PointEhviArgs* eh) {
+                const PointEhviArgs* eh, const PointConstrainedArgs* cn = nullptr) {
   int e;
   if (!X0 || !lo || !hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
   const int d = h->d;
@@ -192,7 +206,7 @@ int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const 
   while (it < max_evals) {
     const int burst = std::min(8, max_evals - it);
     for (int s = 0; s < burst; ++s, ++it) {
-      if ((e = queue_point_eval(h, pl, h->dpt_Xb, nullptr, B, 1, &acq_id, &acq_par, plugin, minimize, true, h->dpt_out, nullptr, 0, eh))) return e;
+      if ((e = queue_point_eval(h, pl, h->dpt_Xb, nullptr, B, 1, &acq_id, &acq_par, plugin, minimize, true, h->dpt_out, nullptr, 0, eh, cn))) return e;
       HIPCHK(h, launch_polish_step(pa, B, st));
     }
     HIPCHK(h, hipMemcpyAsync(hdone, dn_done, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -452,4 +466,134 @@ extern "C" int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const d
   memset(&eh, 0, sizeof(eh));
   eh.m = m; eh.C = C; eh.lower = h->dehvi_cells; eh.upper = h->dehvi_cells + (size_t)C * m;
   return polish_loop(h, who, X0, B, lo, hi, BOGP_ACQ_EI, 0.0, 0.0, 0, max_evals, pgtol, factr, Xout, fout, n_evals, &eh);
+}
+
+// ---- feasibility-weighted criteria and their input gradients at B points of the committed m-target model (kernels_point_constrained.hip) ----
+// what bogp_point_eval_constrained and bogp_polish_constrained refuse alike: check_ehvi's model checks and bogp_sweep_constrained's
+// checks of the criteria and the bounds, with its codes and wording
+static int check_constrained(bogp_handle* h, const char* who, int q, const int* acq_id, const double* acq_par, int n_con, const double* lo,
+                             const double* hi) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP || h->kernel == BOGP_KERNEL_MATERN_NU)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the correlation has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
+  if (h->d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
+  const int m = h->n_t;
+  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has %d target(s); an objective and its constraints need 2 .. %d", who, m, BOGP_MAX_TARGETS);
+  if (n_con != m - 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d but the committed model has %d targets (one objective, %d constraints)", who, n_con, m, m - 1);
+  if (q < 1 || q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_Q);
+  if (!acq_id || !lo || !hi) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo and hi must be non-null", who);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  for (int c = 0; c < q; ++c) {
+    const int id = acq_id[c];
+    if (id == BOGP_ACQ_UCB) FAIL(h, BOGP_ERR_INVALID, "%s: criterion %d is UCB, which changes sign: its product with a probability orders nothing (EI, EpsilonPI, MGFI or BOGP_ACQ_NONE)", who, c);
+    if (id != BOGP_ACQ_EI && id != BOGP_ACQ_EPSILON_PI && id != BOGP_ACQ_MGFI && id != BOGP_ACQ_NONE) FAIL(h, BOGP_ERR_INVALID, "%s: unknown acquisition id %d", who, id);
+    if (id == BOGP_ACQ_EPSILON_PI && (!acq_par || !(acq_par[c] >= 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be >= 0 (epsilon = 0 is plain PI)", who, c);
+    if (id == BOGP_ACQ_MGFI && (!acq_par || !(acq_par[c] > 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be > 0 (the reference asserts t > 0)", who, c);
+  }
+  for (int j = 0; j < n_con; ++j) {
+    if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
+    if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
+  }
+  return BOGP_OK;
+}
+
+static void fill_constrained(const bogp_handle* h, PointConstrainedArgs* cn, int q, const int* acq_id, const double* acq_par, double plugin,
+                             int minimize, int n_con, const double* lo, const double* hi) {
+  memset(cn, 0, sizeof(*cn));
+  cn->m = h->n_t; cn->q = q; cn->plugin = plugin; cn->minimize = minimize;
+  for (int c = 0; c < q; ++c) { cn->acq_id[c] = acq_id[c]; cn->acq_par[c] = acq_par ? acq_par[c] : 0.0; }
+  for (int j = 0; j < n_con; ++j) { cn->lo[j + 1] = lo[j]; cn->hi[j + 1] = hi[j]; }
+}
+
+static int point_eval_constrained_chunk(bogp_handle* h, const PointConstrainedArgs& cn0, const double* Xb, int B, bool want_mom, double* acq,
+                                        double* dacq, double* pof, double* dpof, double* mu, double* mse, double* dmu, double* dmse) {
+  hipStream_t st = h->stream;
+  const int d = h->d, m = cn0.m, q = cn0.q;
+  const PointPlan pl = plan_of(h, B, q, true);
+  const size_t mom_stride = want_mom ? (size_t)1 + d + 2 * m + 2 * (size_t)m * d : 0;
+  const size_t nrec = (size_t)B * (pl.rec_stride + mom_stride);
+  int e;
+  if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
+  const double* dXb = nullptr;
+  if (B > 1 || d > BOGP_POINT_ARG_D) {
+    if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
+    HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
+    dXb = h->dpt_Xb;
+  }
+  PointConstrainedArgs cn = cn0;
+  cn.mom = want_mom ? h->hpin.dev + (size_t)B * pl.rec_stride : nullptr;
+  cn.mom_stride = (int)mom_stride;
+  if (B == 1) {  // the BFGS loop's call: completion polled off the sequence word behind the records (point_eval_chunk)
+    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
+    const unsigned long long seq = ++h->pt_seq;
+    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, cn.acq_id, cn.acq_par, cn.plugin, cn.minimize, true, h->hpin.dev, dflag, seq, nullptr, &cn))) return e;
+    bool seen = false;
+    for (int spin = 0; spin < 400000; ++spin) {
+      if (*flag == seq) { seen = true; break; }
+      __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!seen) HIPCHK(h, hipStreamSynchronize(st));
+  } else {
+    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, cn.acq_id, cn.acq_par, cn.plugin, cn.minimize, true, h->hpin.dev, nullptr, 0, nullptr, &cn))) return e;
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
+  for (int b = 0; b < B; ++b) {
+    const double* o = h->hpin + (size_t)b * pl.rec_stride;
+    if (acq) memcpy(acq + (size_t)b * q, o + 2, (size_t)q * sizeof(double));
+    if (dacq) memcpy(dacq + (size_t)b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
+    if (!want_mom) continue;
+    const double* r = h->hpin + (size_t)B * pl.rec_stride + (size_t)b * mom_stride;
+    if (pof) pof[b] = r[0];
+    if (dpof) memcpy(dpof + (size_t)b * d, r + 1, (size_t)d * sizeof(double));
+    r += 1 + d;
+    if (mu) memcpy(mu + (size_t)b * m, r, (size_t)m * sizeof(double));
+    if (mse) memcpy(mse + (size_t)b * m, r + m, (size_t)m * sizeof(double));
+    if (dmu) memcpy(dmu + (size_t)b * m * d, r + 2 * m, (size_t)m * d * sizeof(double));
+    if (dmse) memcpy(dmse + (size_t)b * m * d, r + 2 * m + (size_t)m * d, (size_t)m * d * sizeof(double));
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int B, int q, const int* acq_id, const double* acq_par, double plugin,
+                                           int minimize, int n_con, const double* lo, const double* hi, double* acq, double* dacq, double* pof,
+                                           double* dpof, double* mu, double* mse, double* dmu, double* dmse) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_constrained";
+  int e = check_constrained(h, who, q, acq_id, acq_par, n_con, lo, hi);
+  if (e) return e;
+  if (!Xb || !acq || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null points, null acq or B <= 0", who);
+  HIPCHK(h, hipSetDevice(h->device));
+  const int d = h->d, m = h->n_t;
+  PointConstrainedArgs cn;
+  fill_constrained(h, &cn, q, acq_id, acq_par, plugin, minimize, n_con, lo, hi);
+  const bool want_mom = pof || dpof || mu || mse || dmu || dmse;
+  // chunks as point_eval_host's: the right-hand sides stay below 256 MB
+  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(chunk, B - b0);
+    e = point_eval_constrained_chunk(h, cn, Xb + (size_t)b0 * d, nb, want_mom, acq + (size_t)b0 * q, dacq ? dacq + (size_t)b0 * q * d : nullptr,
+                                     pof ? pof + b0 : nullptr, dpof ? dpof + (size_t)b0 * d : nullptr, mu ? mu + (size_t)b0 * m : nullptr,
+                                     mse ? mse + (size_t)b0 * m : nullptr, dmu ? dmu + (size_t)b0 * m * d : nullptr,
+                                     dmse ? dmse + (size_t)b0 * m * d : nullptr);
+    if (e) return e;
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int acq_id,
+                                       double acq_par, double plugin, int minimize, int n_con, const double* lo, const double* hi, int max_evals,
+                                       double pgtol, double factr, double* Xout, double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_constrained";
+  int e = check_constrained(h, who, 1, &acq_id, &acq_par, n_con, lo, hi);
+  if (e) return e;
+  if (!X0 || !box_lo || !box_hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
+  PointConstrainedArgs cn;
+  fill_constrained(h, &cn, 1, &acq_id, &acq_par, plugin, minimize, n_con, lo, hi);
+  return polish_loop(h, who, X0, B, box_lo, box_hi, acq_id, acq_par, plugin, minimize, max_evals, pgtol, factr, Xout, fout, n_evals, nullptr, &cn);
 }

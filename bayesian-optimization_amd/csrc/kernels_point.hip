@@ -243,49 +243,7 @@ __global__ __launch_bounds__(256) void k_point_trend_fin(PointRhsArgs pa, const 
   }
 }
 
-// d acq / d x_k = a_dy * dy_k + a_dsd * dsd_k   (acquisition_fun.py:139-146, 181-188, 220-227, 292-309); the guards of
-// the reference return a zero gradient, its FloatingPointError path (np.errstate(all="raise")) likewise
-__device__ __forceinline__ void acq_grad_coef(int id, double par, double y, double sd, double plugin, double sigma2, double& a_dy,
-                                              double& a_dsd) {
-  a_dy = 0.0;
-  a_dsd = 0.0;
-  switch (id) {
-    case BOGP_ACQ_UCB:
-      a_dy = 1.0;
-      a_dsd = par;
-      return;
-    case BOGP_ACQ_EI: {
-      if (sd / sqrt(sigma2) < 1e-6) return;
-      const double z = (plugin - y) / sd;
-      a_dsd = norm_pdf(z);
-      a_dy = -ndtr(z);
-      return;
-    }
-    case BOGP_ACQ_EPSILON_PI: {
-      const double shrink = y > 0 ? 1 - par : 1 + par;
-      const double z = (plugin - shrink * y) / sd;
-      const double f = norm_pdf(z) / sd;
-      a_dy = -shrink * f;
-      a_dsd = -z * f;
-      return;
-    }
-    default: {  // MGFI
-      if (fabs(sd) <= 1e-8) return;
-      const double t = fmin(par, 22.36);
-      const double var = sd * sd;
-      const double z = (plugin - (y - t * var)) / sd;
-      const double scale = exp(t * (plugin + t * var / 2 - y - 1));
-      const double pdf = norm_pdf(z), cdf = ndtr(z);
-      const double c_dy = scale * (-pdf / sd - cdf * t);
-      const double c_dsd = scale * (pdf * (2.0 * t * sd - z) / sd + cdf * (t * t) * sd);
-      if (isfinite(c_dy) && isfinite(c_dsd) && isfinite(scale)) {
-        a_dy = c_dy;
-        a_dsd = c_dsd;
-      }
-      return;
-    }
-  }
-}
+// (acq_grad_coef, the chain-rule coefficients of the criteria, lives in bogp_device.h: kernels_point_constrained.hip uses it too)
 
 // NC columns per pass.  A workgroup owns RB = 64 rows of V -- one row per lane, so that every lane of a wave works on the
 // SAME column n and the right-hand-side row of that column is a wave-uniform (scalar, SMEM) load: rhs values sit in SGPRs

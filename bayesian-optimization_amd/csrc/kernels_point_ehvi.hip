@@ -23,6 +23,7 @@
 //   6. the completion word of one-point calls, as k_point_finish stores it.
 #include "bogp_device.h"
 #include "bogp_internal.h"
+#include "bogp_point_multi.h"
 
 namespace bogp {
 
@@ -36,8 +37,6 @@ __device__ __forceinline__ double wave_sum_fixed(double v) {
 
 template <int MT, int NC>
 __global__ __launch_bounds__(256) void k_point_ehvi_finish(PointEhviArgs a) {
-  constexpr int CW = NC <= 16 ? 16 : 32;  // lanes per row slice of the right-hand sides (>= NC); 256 / CW slices walk the rows
-  constexpr int NS = 256 / CW;
   constexpr int NV = 2 * MT + 1;          // value | dEHVI/dmu_k | dEHVI/dsd_k
   extern __shared__ double dyn[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -51,86 +50,13 @@ __global__ __launch_bounds__(256) void k_point_ehvi_finish(PointEhviArgs a) {
   __shared__ double red[4][NV];
   __shared__ double coef[NV];
 
-  // 1. the row-block records (k_point_finish's order: every 4th block per wave, then ((w0 + w1) + w2) + w3)
-  for (int gg = 0; gg < npass; ++gg) {
-    const double* base = a.part + ((size_t)b * npass + gg) * (a.nRB + 1) * (2 * NC);
-    if (lane < NC) {
-      double s = 0.0;
-#pragma unroll 8
-      for (int w2 = 1 + wv; w2 <= a.nRB; w2 += 4) s += base[(size_t)w2 * (2 * NC) + lane];
-      fin[wv][lane] = s;
-    }
-    __syncthreads();
-    if (tid < NC) {
-      const double tot = ((fin[0][tid] + fin[1][tid]) + fin[2][tid]) + fin[3][tid];
-      const double wv2 = base[NC + tid];
-      if (tid == 0) {
-        if (gg == 0) {
-          sc[0] = tot;
-          sc[1] = wv2;
-        }
-      } else {
-        const int k = gg * (NC - 1) + tid - 1;
-        if (k < d) {
-          zdr[k] = tot;
-          wdr[k] = wv2;
-        }
-      }
-    }
-    __syncthreads();
-  }
-
-  // 2. gamma_k . rhs_c: slice s of the rows n = s, s + NS, ... per lane group; the slices of a wave meet by shuffles, the waves in LDS
-  {
-    const int c = tid & (CW - 1), s = tid / CW;
-    for (int gg = 0; gg < npass; ++gg) {
-      const double* __restrict__ rhs = a.rhs + ((size_t)b * npass + gg) * (size_t)a.Npp * NC;
-      double acc[MT];
-#pragma unroll
-      for (int k = 0; k < MT; ++k) acc[k] = 0.0;
-      if (c < NC) {
-#pragma unroll 4
-        for (int n = s; n < a.N; n += NS) {
-          const double r = rhs[(size_t)n * NC + c];
-#pragma unroll
-          for (int k = 0; k < MT; ++k) acc[k] = __builtin_fma(a.gamma[(size_t)k * a.ld_gamma + n], r, acc[k]);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < MT; ++k) {
-        acc[k] += shfl_xor_f64(acc[k], 32);
-        if (CW == 16) acc[k] += shfl_xor_f64(acc[k], 16);
-      }
-      if (lane < CW && c < NC) {
-#pragma unroll
-        for (int k = 0; k < MT; ++k) wpart[wv][c][k] = acc[k];
-      }
-      __syncthreads();
-      if (tid < NC * MT) {
-        const int cc = tid / MT, k = tid - cc * MT;
-        dots[((size_t)gg * NC + cc) * MT + k] = ((wpart[0][cc][k] + wpart[1][cc][k]) + wpart[2][cc][k]) + wpart[3][cc][k];
-      }
-      __syncthreads();
-    }
-  }
-
-  // 3. the moments (every thread forms all of them: the cell loop below reads them from registers)
-  double u2 = 0.0, mfac = 0.0;
-  if (a.estimate_trend) {
-    const double u = (sc[1] - 1.0) / a.G;
-    u2 = u * u;
-    mfac = (sc[1] - 1.0) * (1.0 / a.ftft);
-  }
-  const double bracket = 1.0 - sc[0] + u2;
+  // 1.-3. the sums and the moments (bogp_point_multi.h; every thread forms all moments: the cell loop below reads them from registers)
+  point_multi_sums<MT, NC>(a, b, dots, zdr, wdr, fin, wpart, sc);
+  double mfac;
   double mu[MT], mse[MT], sd[MT];
+  point_multi_moments<MT>(a, dots, sc, mu, mse, mfac);
 #pragma unroll
-  for (int k = 0; k < MT; ++k) {
-    mu[k] = a.beta + dots[k];
-    double v = bracket * a.sigma2[k];
-    if (v < 0.0) v = 0.0;
-    mse[k] = v;
-    sd[k] = sqrt(fmax(v, 1e-9));
-  }
+  for (int k = 0; k < MT; ++k) sd[k] = sqrt(fmax(mse[k], 1e-9));
 
   // 4. the cells
   double acc[NV];

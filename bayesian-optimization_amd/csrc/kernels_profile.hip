@@ -1,7 +1,8 @@
 // kernels_profile.hip -- bogp_selftest_profile: the radial profile of a correlation function (or one of its building blocks) evaluated on the
 // device for an array of arguments, so that tests can hold the special functions of bogp_device.h (K_nu, 1 / Gamma) to committed
 // tables one argument at a time instead of through a posterior; bogp_selftest_criteria: the same for the scalar criterion functions
-// (ndtr, acq_value, feasibility, the two upper bounds, prune_below).  See include/bogp.h.
+// (ndtr, acq_value, feasibility, the two upper bounds, prune_below); bogp_selftest_feasibility_grad: feasibility_grad, three results a row.
+// See include/bogp.h.
 #include "bogp_device.h"
 #include "bogp_handle.h"
 
@@ -43,7 +44,41 @@ __global__ void k_criteria(const double* __restrict__ rows, double* __restrict__
   }
 }
 
+// feasibility_grad itself on rows of (mu, mse, sigma2, lo, hi): F, dF/dmu, dF/dsd
+__global__ void k_feasibility_grad(const double* __restrict__ rows, double* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* r = rows + i * 5;
+  double F, dm, ds;
+  feasibility_grad(r[0], r[1], r[2], r[3], r[4], &F, &dm, &ds);
+  out[3 * i] = F;
+  out[3 * i + 1] = dm;
+  out[3 * i + 2] = ds;
+}
+
 }  // namespace
+
+extern "C" int bogp_selftest_feasibility_grad(bogp_handle* h, const double* rows, int64_t n, double* out) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (!rows || !out || n <= 0) FAIL(h, BOGP_ERR_INVALID, "bogp_selftest_feasibility_grad: null pointer or empty array");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  double *din = nullptr, *dout = nullptr;
+  if (hipMalloc((void**)&din, n * 5 * sizeof(double)) != hipSuccess || hipMalloc((void**)&dout, n * 3 * sizeof(double)) != hipSuccess) {
+    dfree(din); dfree(dout);
+    FAIL(h, BOGP_ERR_HIP, "bogp_selftest_feasibility_grad: hipMalloc failed");
+  }
+  hipError_t e = hipMemcpyAsync(din, rows, n * 5 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_feasibility_grad, dim3((unsigned)((n + 255) / 256)), 256, 0, st, din, dout, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, n * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  dfree(din); dfree(dout);
+  if (e != hipSuccess) FAIL(h, BOGP_ERR_HIP, "bogp_selftest_feasibility_grad: %s", hipGetErrorString(e));
+  return BOGP_OK;
+}
 
 extern "C" int bogp_selftest_criteria(bogp_handle* h, int what, const double* rows, int64_t n, double* out) {
   if (!h) return BOGP_ERR_INVALID;

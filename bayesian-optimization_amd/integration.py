@@ -292,7 +292,8 @@ def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fi
     """`BaseBO._create_acquisition` in front of `forest_create_acquisition`: with stored constraint values the criterion is
     `bogp.Constrained` -- (-inf, 0] for the g columns, [-tol, tol] / std for the h columns (tol = `install(equality_tol=)`), the plugin
     the best FEASIBLE observation instead of the fmin / fmax `BO._create_acquisition` passes.  UCB raises ValueError; an inner optimiser
-    outside the sweep family raises NotImplementedError instead of dropping the constraints."""
+    outside the sweep family raises NotImplementedError instead of dropping the constraints -- except, under
+    `install(constraint_gradient=True)`, "BFGS", "sweep-BFGS" and "sweep-device-BFGS", which get the criterion with `input_gradient=True`."""
     C = getattr(self, "_bogp_constraints", None)
     if not _CONSTRAINTS or C is None or not is_device_model(getattr(self, "model", None)):
         return forest_create_acquisition(self, fun=fun, par=par, return_dx=return_dx, fixed=fixed)
@@ -301,7 +302,8 @@ def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fi
         raise ValueError("acquisition_fun=%r under expensive constraints: the feasibility-weighted criterion takes EI, PI, EpsilonPI or "
                          "MGFI (UCB changes sign, so its product with a probability orders nothing)" % (name,))  # fmt: skip
     optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
-    if optimizer not in _SWEEPS:
+    gradient = bool(_CONSTRAINTS.get("gradient")) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS")
+    if optimizer not in _SWEEPS and not gradient:
         raise NotImplementedError("optimizer=%r under expensive constraints: the feasibility-weighted criterion is served by the sweep "
                                   "family only %s; the constraint values are not dropped silently" % (optimizer, _SWEEPS))  # fmt: skip
     par = dict(par if par is not None else self._acquisition_par)
@@ -310,7 +312,7 @@ def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fi
     n_g, n_h = self._bogp_constraint_counts
     tol = _CONSTRAINTS["tol"] / np.asarray(self._bogp_constraint_scale, dtype=float)[n_g:]
     lo, hi = np.r_[np.full(n_g, -np.inf), -tol], np.r_[np.zeros(n_g), tol]
-    criterion = acquisition.Constrained(model=self.model, fun=name, minimize=self.minimize, lo=lo, hi=hi, **par)
+    criterion = acquisition.Constrained(model=self.model, fun=name, minimize=self.minimize, lo=lo, hi=hi, input_gradient=gradient, **par)
     return _ORIGINAL["base_partial_argument"](func=functools.partial(criterion, return_dx=return_dx), var_name=self.search_space.var_name,
                                               fixed=fixed, reduce_output=return_dx)  # fmt: skip
 
@@ -360,6 +362,10 @@ def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=10
     if mine and opt2 in _OURS:
         return optim.argmax_restart(obj_func, search_space, h=h, g=g, eval_budget=budget2, n_restart=n_restart,
                                     wait_iter=wait_iter, optimizer=opt2, logger=logger)  # fmt: skip
+    if mine and optimizer == "BFGS" and optim.is_constrained(crit) and getattr(crit, "input_gradient", False):
+        # Constrained(input_gradient=True): the reference-style loop on bogp_point_eval_constrained; cheap callables h / g are refused by name
+        return optim.argmax_restart(obj_func, search_space, h=h, g=g, eval_budget=eval_budget, n_restart=n_restart,
+                                    wait_iter=wait_iter, optimizer=optimizer, logger=logger)  # fmt: skip
     if optimizer in _OURS:  # asked for by name, but not servable: say why instead of a KeyError deep in the reference
         raise TypeError("optimizer=%r needs one of this package's criteria (a bogp.GaussianProcess as model=) on a "
                         "continuous search space" % optimizer)  # fmt: skip
@@ -524,7 +530,7 @@ def _dispatching_surrogate(host_cls):
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
-            equality_tol: float = 0.1):
+            equality_tol: float = 0.1, constraint_gradient: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -559,12 +565,20 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     (`constrained_update_model`) and maximises `bogp.Constrained` -- EI / PI / EpsilonPI / MGFI times the probability that g <= 0 and
     |h| <= `equality_tol` (the reference's own equality threshold, `dynamic_penalty`, utils.py:280) -- under the sweep family
     (`constrained_create_acquisition`); `bogp.feasible_xopt(bo)` is the best feasible observation.  Off (the default): nothing of
-    this is patched in effect and `tell` drops the values as before."""
+    this is patched in effect and `tell` drops the values as before.
+
+    `constraint_gradient=True` (with `expensive_constraints=True`; alone it raises ValueError): such a driver also accepts "BFGS",
+    "sweep-BFGS" and "sweep-device-BFGS" and maximises `bogp.Constrained(input_gradient=True)` -- the input gradient of
+    `bogp_point_eval_constrained` and the lock-step polish `bogp_polish_constrained`.  Without it those optimisers raise as before."""
+    if constraint_gradient and not expensive_constraints:
+        raise ValueError("constraint_gradient=True needs expensive_constraints=True (it is the input gradient of the feasibility-weighted criterion)")
     _CONSTRAINTS.clear()
     if expensive_constraints:
         if not (float(equality_tol) >= 0):
             raise ValueError("equality_tol must be >= 0")
         _CONSTRAINTS["tol"] = float(equality_tol)
+        if constraint_gradient:
+            _CONSTRAINTS["gradient"] = True
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

@@ -774,7 +774,9 @@ def argmax_restart(
     are swept under the wrapper's lift (`sweep_argmax(..., lift=)`); the polish hybrids, fixed variables, constraints and
     several ranks are refused by name.
     A `bogp.Constrained` criterion (modelled constraints) is served under "sweep" and "sweep-device[-lhs|-sobol]" through
-    `bogp_sweep_constrained`; "BFGS" and the "-BFGS" hybrids are refused by name (it has no input gradient).
+    `bogp_sweep_constrained`; "BFGS" and the "-BFGS" hybrids are refused by name (it has no input gradient) unless it was built with
+    `input_gradient=True`: then "BFGS" is the loop on `bogp_point_eval_constrained` and the hybrids polish the sweep's best rows with
+    `bogp_polish_constrained`; fixed variables, cheap callables h / g, a lift and several ranks are refused by name.
     Anything else ("MIES", "OnePlusOne_Cholesky_CMA", constraints under "BFGS", a non-continuous space) is the
     reference's own business: the call is handed to its `argmax_restart` when `bayes_optim` is importable, for which a
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
@@ -795,8 +797,20 @@ def argmax_restart(
         # ehvi.sweep(k) + polish_topk (bogp_polish_ehvi); fixed variables, constraints, a lift and several ranks are refused
         # by name where the single-objective polish hybrids refuse them
     if is_constrained(fcrit) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS"):
-        raise NotImplementedError("optimizer=%r needs an input gradient, which the feasibility-weighted criterion (bogp.Constrained) "
-                                  "does not have: use 'sweep' or 'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip
+        if not getattr(fcrit, "input_gradient", False):
+            raise NotImplementedError("optimizer=%r needs an input gradient, which the feasibility-weighted criterion (bogp.Constrained) "
+                                      "does not have: use 'sweep' or 'sweep-device[-lhs|-sobol]'" % optimizer)  # fmt: skip
+        # Constrained(input_gradient=True): "BFGS" is the loop below on the one-point call (bogp_point_eval_constrained), the hybrids are
+        # crit.sweep(k) + polish_topk (bogp_polish_constrained); what the single-objective polish hybrids refuse is refused by name
+        if not is_continuous(search_space):
+            raise NotImplementedError("optimizer=%r for modelled constraints (bogp.Constrained) takes a continuous space" % optimizer)
+        if fmasks is not None:
+            raise NotImplementedError("optimizer=%r for modelled constraints (bogp.Constrained) takes no fixed variables" % optimizer)
+        if h is not None or g is not None:
+            raise NotImplementedError("optimizer=%r for modelled constraints (bogp.Constrained) takes no cheap constraints h / g: they "
+                                      "would be dropped or filtered outside the polish; model them as columns instead" % optimizer)  # fmt: skip
+        if engine_rank_world(fcrit.model.engine)[1] > 1:
+            raise NotImplementedError("optimizer=%r for modelled constraints (bogp.Constrained) runs on one rank" % optimizer)
     if not ours and (optimizer != "BFGS" or h is not None or g is not None or not is_continuous(search_space)):
         ref = _reference_argmax_restart()
         if ref is None:
@@ -904,7 +918,7 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
     """Local refinement of `starts` (k, d) inside the box `bounds` (d, 2); returns (points (k, d), values (k,)) with
     values[i] >= the criterion at starts[i].  On the device engine all k starts advance in lock step (`bogp_polish`:
     one batched value + gradient evaluation per iteration, the optimiser state never leaves the GPU; an EHVI criterion built
-    with `input_gradient=True` goes to `bogp_polish_ehvi`) -- the reference
+    with `input_gradient=True` goes to `bogp_polish_ehvi`, a Constrained one to `bogp_polish_constrained`) -- the reference
     runs its restarts one after the other, one point per call (optim/__init__.py:74-153).  An engine without `polish`
     (the test stand-ins) or a model the fused call does not serve (polynomial trend basis) gets the reference-style
     sequential L-BFGS-B through the one-point call."""
@@ -919,7 +933,13 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
         xs, fs, _ = eng.polish_ehvi(model._check_X(starts), bounds[:, 0], bounds[:, 1], crit.cell_lower_bounds, crit.cell_upper_bounds,
                                     max_evals=int(max_iter))  # fmt: skip
         return xs, fs
-    if not is_ehvi(crit) and eng is not None and hasattr(eng, "polish") and fused is not None and fused():  # (r05: any d up to BOGP_MAX_DIM; r03-r04 stopped at 64)
+    if is_constrained(crit) and eng is not None and hasattr(eng, "polish_constrained"):  # Constrained(input_gradient=True)
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        xs, fs, _ = eng.polish_constrained(model._check_X(starts), bounds[:, 0], bounds[:, 1], (crit.acq_id, crit.acq_par()),
+                                           crit.effective_plugin(), crit.minimize, crit.lo, crit.hi, max_evals=int(max_iter))  # fmt: skip
+        return xs, fs
+    if not is_ehvi(crit) and not is_constrained(crit) and eng is not None and hasattr(eng, "polish") and fused is not None and fused():  # (r05: any d up to BOGP_MAX_DIM; r03-r04 stopped at 64)
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         xs, fs, _ = eng.polish(model._check_X(starts), bounds[:, 0], bounds[:, 1], (crit.acq_id, crit.acq_par()), crit.effective_plugin(),

@@ -612,6 +612,44 @@ int bogp_point_eval_ehvi(bogp_handle* h, const double* Xb, int B, int m, int C, 
 int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const double* lo, const double* hi, int m, int C,
                      const double* lower, const double* upper, int max_evals, double pgtol, double factr, double* Xout,
                      double* fout, int* n_evals);
+/* The feasibility-weighted criteria of bogp_sweep_constrained AND their input gradients at B points of the committed m-target model,
+ * and the lock-step polish on one of them (an extension: the reference drops constraint values, base.py:328).  k_point_rhs +
+ * k_point_tri run as for bogp_point_eval_ehvi (FP64 VALU flavour for every B); k_point_constrained_finish
+ * (csrc/kernels_point_constrained.hip) then forms the m means and their gradients from the m columns of gamma, MSE_k = sigma2_k
+ * (1 - |V r|^2 + u^2) clipped at 0, sd_k = sqrt(MSE_k) without a floor (as bogp_sweep_constrained), and
+ *   F_k, dF_k/dmu, dF_k/dsd = bogp_feasibility_grad(mu_k, MSE_k, sigma2_k, lo_k, hi_k);   P = F_1 * ... * F_{m-1} (this order, from 1.0)
+ *   value_c = base_c * P   (base_c as bogp_sweep_constrained: EI, EpsilonPI, MGFI on target 0, or 1 for BOGP_ACQ_NONE)
+ *   dP/dx   = sum_k (prod_{j != k} F_j) (dF_k/dmu dmu_k/dx + dF_k/dsd dsd_k/dx),   dsd_k/dx = dMSE_k/dx / (2 sd_k)
+ *   dvalue_c/dx = P (c_dy (+-dmu_0/dx) + c_dsd dsd_0/dx) + base_c dP/dx   (c_dy, c_dsd: bogp_point_eval_batch's chain-rule coefficients)
+ * The products over j != k come from prefix and suffix products, never from a division.  A zero coefficient times anything is 0: P == 0
+ * removes the first term, base_c == 0 the second, a guard of the criterion or of the feasibility (sd / sqrt(sigma2) < 1e-6: the
+ * indicator) its own; where sd_0 == 0 exactly the criterion's coefficients are 0.  A gradient is never NaN where the value is finite.
+ * The values agree with bogp_sweep_constrained's to rounding (the summation orders differ); identical inputs give identical bits, the
+ * bits of a criterion do not depend on the other criteria of the call, and row b of a B-point call equals the one-point call on that
+ * row whenever both run the same row-block split (csrc/kernels_point.hip: point_tri_geometry).
+ *   q, acq_id, acq_par, plugin, minimize, n_con, lo, hi   as bogp_sweep_constrained.
+ *   `point_eval_constrained`  Xb: B x d (host).  Outputs, row-major, any but acq may be NULL: acq (B x q), dacq (B x q x d), pof (B),
+ *                        dpof (B x d), mu, mse (B x m), dmu, dmse (B x m x d).
+ *   `polish_constrained` bogp_polish's loop, state, stop rules and read-back on this evaluation of ONE criterion: X0, box_lo, box_hi
+ *                        (the box), max_evals, pgtol, factr, Xout, fout, n_evals as there; a start never moves to a worse point, Xout
+ *                        lies in the box and fout[b] >= value(clip(X0[b])).
+ * BOGP_ERR_INVALID: no committed model, n_targets < 2, n_con != n_targets - 1, q outside [1, BOGP_MAX_Q], UCB or an id other than EI /
+ * EpsilonPI / MGFI / BOGP_ACQ_NONE, a parameter the criterion refuses, a NaN bound, hi < lo, a null required pointer, B <= 0,
+ * box_lo > box_hi, max_evals <= 0.  BOGP_ERR_UNSUPPORTED: the cubic, generalized-exponential and general-nu kernels (no corr_dx); a
+ * polynomial basis; d > BOGP_MAX_DIM; a forest on the handle.  The handle's active target, its candidates and later sweeps are
+ * unaffected.
+ *
+ * bogp_feasibility_grad (host only, no handle, no device call): out3 = [F, dF/dmu, dF/dsd] with F = bogp_feasibility(...) itself (the
+ * same bits) and, with sd = sqrt(mse), za = (lo - mu) / sd, zb = (hi - mu) / sd:  dF/dmu = (phi(za) - phi(zb)) / sd,  dF/dsd =
+ * (za phi(za) - zb phi(zb)) / sd.  An infinite side contributes exactly 0 to both; under the guard sd / sqrt(sigma2) < 1e-6 both are
+ * exactly 0; lo == hi gives (0, 0, 0), two infinite sides (1, 0, 0).  Returns BOGP_ERR_INVALID for a null out3, else BOGP_OK. */
+int bogp_feasibility_grad(double mu, double mse, double sigma2, double lo, double hi, double* out3);
+int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int B, int q, const int* acq_id, const double* acq_par, double plugin,
+                                int minimize, int n_con, const double* lo, const double* hi, double* acq, double* dacq, double* pof,
+                                double* dpof, double* mu, double* mse, double* dmu, double* dmse);
+int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int acq_id, double acq_par,
+                            double plugin, int minimize, int n_con, const double* lo, const double* hi, int max_evals, double pgtol,
+                            double factr, double* Xout, double* fout, int* n_evals);
 
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
@@ -775,6 +813,10 @@ int bogp_selftest_profile(bogp_handle* h, int what, int kernel, double pexp, con
 #define BOGP_CRITERIA_PRUNE_BELOW 7
 #define BOGP_CRITERIA_COLUMNS 8
 int bogp_selftest_criteria(bogp_handle* h, int what, const double* rows, int64_t n, double* out);
+/* feasibility_grad of csrc/bogp_device.h itself on the device: rows n x 5 (mu, mse, sigma2, lo, hi), out n x 3 (F, dF/dmu, dF/dsd),
+ * both HOST arrays; out[:, 0] has the bits of bogp_selftest_criteria(BOGP_CRITERIA_FEASIBILITY).  Used by
+ * tests/test_gpu_constrained_grad.py against tests/golden/G47_feasibility_grad_truth.npz.  BOGP_ERR_INVALID: null pointer or n <= 0. */
+int bogp_selftest_feasibility_grad(bogp_handle* h, const double* rows, int64_t n, double* out);
 
 /* The optimiser behind bogp_mle_batch (csrc/bogp_lbfgsb.h: L-BFGS-B after Byrd, Lu, Nocedal & Zhu 1995 with the More'-Thuente
  * line search) on a HOST objective: what the reference gets from scipy.optimize.fmin_l_bfgs_b (gpr.py:1136).  No device, no handle;
