@@ -1065,18 +1065,28 @@ class Engine:
         )  # fmt: skip
         return mu, mse, dmu, dmse, vals[:, :q], (dvals[:, :q] if dvals is not None else None)
 
-    def polish(self, X0, lo, hi, acq: Tuple[int, float], plugin: float = 0.0, minimize: bool = True, max_evals: int = 50,
-               pgtol: float = 1e-8, factr: float = 1e6):
-        """Lock-step multi-start local maximisation of one criterion inside the box (bogp_polish): (points (B, d), values (B,),
-        evaluations used (B,)); values[i] >= the criterion at X0[i]."""
-        X0 = _f64(X0)
+    def _rows(self, X):
+        """The points of a multi-target call as B x d: one point may come as a vector."""
+        X = np.atleast_2d(_f64(X))
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise Exception("x does not have the right size!")
+        return X
+
+    def _polish_io(self, X0, lo, hi, names):
+        """The starts (B x d) and the box of a polish checked, its outputs allocated: (X0, lo, hi, B, Xo, fo, ne)."""
         if X0.ndim != 2 or X0.shape[1] != self.d:
             raise Exception("x does not have the right size!")
         lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
         if len(lo) != self.d or len(hi) != self.d:
-            raise ValueError("lo / hi must have d entries")
+            raise ValueError(names + " must have d entries")
         B = X0.shape[0]
-        Xo, fo, ne = np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
+        return X0, lo, hi, B, np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
+
+    def polish(self, X0, lo, hi, acq: Tuple[int, float], plugin: float = 0.0, minimize: bool = True, max_evals: int = 50,
+               pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local maximisation of one criterion inside the box (bogp_polish): (points (B, d), values (B,),
+        evaluations used (B,)); values[i] >= the criterion at X0[i]."""
+        X0, lo, hi, B, Xo, fo, ne = self._polish_io(_f64(X0), lo, hi, "lo / hi")
         self._check(
             self._lib.bogp_polish(self._h, _ptr(X0), B, _ptr(lo), _ptr(hi), int(acq[0]), float(acq[1]), float(plugin),
                                   int(bool(minimize)), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
@@ -1096,9 +1106,7 @@ class Engine:
         (bogp_point_eval_ehvi), for the cells (lower, upper) (C x m each; upper may hold +inf): (ehvi (B,), dehvi (B, d)) and,
         with `moments`, also mu (B, m), mse (B, m), dmu (B, m, d), dmse (B, m, d).  Cells equal to those of the call before are
         not uploaded again."""
-        X = np.atleast_2d(_f64(X))
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise Exception("x does not have the right size!")
+        X = self._rows(X)
         lower, upper = self._cells(lower, upper)
         C_, m = lower.shape
         B, d = X.shape[0], self.d
@@ -1113,16 +1121,9 @@ class Engine:
     def polish_ehvi(self, starts, lo, hi, lower, upper, max_evals: int = 50, pgtol: float = 1e-8, factr: float = 1e6):
         """Lock-step multi-start local maximisation of EHVI inside the box (bogp_polish_ehvi): (points (B, d), values (B,),
         evaluations used (B,)); values[i] >= EHVI at starts[i] clipped into the box."""
-        X0 = np.atleast_2d(_f64(starts))
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise Exception("x does not have the right size!")
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != self.d or len(hi) != self.d:
-            raise ValueError("lo / hi must have d entries")
+        X0, lo, hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), lo, hi, "lo / hi")
         lower, upper = self._cells(lower, upper)
         C_, m = lower.shape
-        B = X0.shape[0]
-        Xo, fo, ne = np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
         self._check(
             self._lib.bogp_polish_ehvi(self._h, _ptr(X0), B, _ptr(lo), _ptr(hi), int(m), int(C_), _ptr(lower), _ptr(upper),
                                        int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))
@@ -1141,9 +1142,7 @@ class Engine:
         ONE device round trip (bogp_point_eval_constrained); criteria, plugin, direction and the constraints' bounds as
         `sweep_constrained`: (acq (B, q), dacq (B, q, d)) and, with `moments`, also pof (B,), dpof (B, d), mu (B, m), mse (B, m),
         dmu (B, m, d), dmse (B, m, d)."""
-        X = np.atleast_2d(_f64(X))
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise Exception("x does not have the right size!")
+        X = self._rows(X)
         lo, hi = self._constraint_bounds(lo, hi)
         q, m = len(acq), len(lo) + 1
         ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
@@ -1163,15 +1162,8 @@ class Engine:
                            pgtol: float = 1e-8, factr: float = 1e6):
         """Lock-step multi-start local maximisation of one feasibility-weighted criterion inside the box (bogp_polish_constrained):
         (points (B, d), values (B,), evaluations used (B,)); values[i] >= the criterion at starts[i] clipped into the box."""
-        X0 = np.atleast_2d(_f64(starts))
-        if X0.ndim != 2 or X0.shape[1] != self.d:
-            raise Exception("x does not have the right size!")
-        box_lo, box_hi = _f64(box_lo).ravel(), _f64(box_hi).ravel()
-        if len(box_lo) != self.d or len(box_hi) != self.d:
-            raise ValueError("box_lo / box_hi must have d entries")
+        X0, box_lo, box_hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), box_lo, box_hi, "box_lo / box_hi")
         lo, hi = self._constraint_bounds(lo, hi)
-        B = X0.shape[0]
-        Xo, fo, ne = np.empty((B, self.d)), np.empty(B), np.zeros(B, dtype=np.int32)
         self._check(
             self._lib.bogp_polish_constrained(self._h, _ptr(X0), B, _ptr(box_lo), _ptr(box_hi), int(acq[0]),
                                               float(acq[1]) if acq[1] is not None else 0.0, float(plugin), int(bool(minimize)), len(lo),

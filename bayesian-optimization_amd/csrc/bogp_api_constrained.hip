@@ -22,22 +22,13 @@ extern "C" int bogp_feasibility_grad(double mu, double mse, double sigma2, doubl
   return BOGP_OK;
 }
 
-extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int n_con,
-                                      const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,
-                                      double* pof_out, double* mu_out, double* mse_out) {
-  if (!h) return BOGP_ERR_INVALID;
-  const char* who = "bogp_sweep_constrained";
-  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
-  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
-  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
-  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set) and modelled constraints have no lifted sweep: call bogp_lift_clear first", who);
-  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
+int bogp::check_constrained_request(bogp_handle* h, const char* who, int q, const int* acq_id, const double* acq_par, int n_con,
+                                    const double* lo, const double* hi) {
   const int m = h->n_t;
   if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has %d target(s); an objective and its constraints need 2 .. %d", who, m, BOGP_MAX_TARGETS);
   if (n_con != m - 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d but the committed model has %d targets (one objective, %d constraints)", who, n_con, m, m - 1);
   if (q < 1 || q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_Q);
-  if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
-  if (!acq_id || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo, hi, best_val and best_idx must be non-null", who);
+  if (!acq_id || !lo || !hi) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo and hi must be non-null", who);
   if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
   for (int c = 0; c < q; ++c) {
     const int id = acq_id[c];
@@ -50,10 +41,28 @@ extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, 
     if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
     if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
   }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize, int n_con,
+                                      const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,
+                                      double* pof_out, double* mu_out, double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_constrained";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set) and modelled constraints have no lifted sweep: call bogp_lift_clear first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
+  // (every check from here on returns BOGP_ERR_INVALID: the sweep's own two stand before the shared ones, which name three pointers only)
+  if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
+  if (!acq_id || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo, hi, best_val and best_idx must be non-null", who);
+  int e = check_constrained_request(h, who, q, acq_id, acq_par, n_con, lo, hi);
+  if (e) return e;
+  const int m = h->n_t;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const int64_t M = h->M;
-  int e;
   if (pof_out && (e = h->dpof_out.ensure(h, (size_t)M))) return e;
   ConstrainedArgs ca;
   memset(&ca, 0, sizeof(ca));

@@ -45,6 +45,10 @@ int sweep_geometry(bogp_handle* h, int rows, SweepGeometry* g);
 CorrArgs corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int64_t m0, int b);
 int ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out);
 int check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par);
+// bogp_api_constrained.hip, shared with the point path: what every entry with modelled constraints refuses alike, from the target count
+// through the criteria down to the bounds (all BOGP_ERR_INVALID; hidden: the library's dynamic symbols stay the ones they were)
+__attribute__((visibility("hidden"))) int check_constrained_request(bogp_handle* h, const char* who, int q, const int* acq_id, const double* acq_par, int n_con, const double* lo,
+                              const double* hi);
 int bound32_prepare(bogp_handle* h);  // bogp_api_sweep.hip: the FP32 copies of the committed model's active target, where the stage serves it
 // bogp_api_sweep.hip, for bogp_api_lift.hip: a pending lazy upload finished (every candidate row on the device); the
 // sweep timing zeroed (a lifted sweep without a feasible row runs no posterior pass)

@@ -58,11 +58,54 @@ int ensure_tickets(bogp_handle* h, DevBuf<unsigned int>& c, size_t n) {
 }
 int ensure_counters(bogp_handle* h, size_t n) { return ensure_tickets(h, h->dpt_counter, n); }
 
-// queue k_point_rhs + k_point_tri for B points; the records land in `out` (device or device-mapped host memory)
-int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, const double* x_host, int B, int q, const int* acq_id,
-                     const double* acq_par, double plugin, int minimize, bool want_dacq, double* out,
-                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0, const PointEhviArgs* eh = nullptr,
-                     const PointConstrainedArgs* cn = nullptr) {
+// What one evaluation computes at each of its points, whichever entry asks: q criteria and -- want_dacq -- their input gradients behind
+// k_point_finish, or the finish of an m-target model in its place (at most one of eh / cn; they hold what that family alone knows: cells
+// and targets, or criteria and bounds).  The record then keeps k_point_finish's layout for q criteria, which EHVI fills like ONE.
+struct PointCall {
+  int q;
+  const int* acq_id;
+  const double* acq_par;  // null: zeros
+  double plugin;
+  int minimize;
+  bool want_dacq;
+  const PointEhviArgs* eh;
+  const PointConstrainedArgs* cn;
+  size_t mom_stride;  // doubles per point of the m-target finishes' second block, written behind the B records; 0: not wanted
+};
+
+// the EHVI request: a record sized like one criterion's with its gradient (the id itself is not evaluated)
+PointCall ehvi_call(const PointEhviArgs* eh, size_t mom_stride) {
+  static const int one_id = BOGP_ACQ_EI;
+  return PointCall{1, &one_id, nullptr, 0.0, 0, true, eh, nullptr, mom_stride};
+}
+
+// the criterion block of PointTriArgs, for k_point_finish and its MFMA flavour alike
+void fill_criteria(const bogp_handle* h, const PointPlan& pl, const PointCall& c, unsigned long long* done_flag, unsigned long long done_seq,
+                   PointTriArgs* a) {
+  a->rec_stride = pl.rec_stride; a->q = c.q; a->want_dacq = c.want_dacq ? 1 : 0; a->estimate_trend = h->estimate_trend;
+  a->minimize = c.minimize;
+  for (int i = 0; i < c.q; ++i) { a->acq_id[i] = c.acq_id[i]; a->acq_par[i] = c.acq_par ? c.acq_par[i] : 0.0; }
+  a->plugin = c.plugin; a->beta = h->beta; a->G = h->G; a->ftft = h->ftft; a->sigma2 = h->sigma2;
+  a->done_flag = done_flag; a->done_seq = done_seq;
+}
+
+// the arguments of an m-target finish: `a` arrives with its family's own fields and leaves with those PointEhviArgs and
+// PointConstrainedArgs share (the ones point_multi_sums reads, the second block and the done word)
+template <class Args>
+Args multi_finish_args(const bogp_handle* h, const PointPlan& pl, Args a, int B, size_t mom_stride, double* out, unsigned long long* done_flag,
+                       unsigned long long done_seq) {
+  a.part = h->dpt_part; a.rhs = h->dpt_rhs; a.gamma = h->dgamma_base; a.ld_gamma = h->Np; a.out = out;
+  a.mom = mom_stride ? out + (size_t)B * pl.rec_stride : nullptr; a.mom_stride = (int)mom_stride;
+  a.N = h->N; a.Npp = pl.Npp; a.nRB = pl.nRB; a.npass = pl.npass; a.d = h->d; a.rec_stride = pl.rec_stride;
+  a.estimate_trend = h->estimate_trend; a.beta = h->beta; a.G = h->G; a.ftft = h->ftft;
+  for (int t = 0; t < a.m; ++t) a.sigma2[t] = h->sigma2_t[t];
+  a.done_flag = done_flag; a.done_seq = done_seq;
+  return a;
+}
+
+// queue k_point_rhs + k_point_tri and the finish of `c` for B points; the records land in `out` (device or device-mapped host memory)
+int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, const double* dXb, const double* x_host, int B, double* out,
+                     unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0) {
   hipStream_t st = h->stream;
   int e;
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
@@ -74,7 +117,7 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   const int ncp = point_mfma_columns(h->d);
   const char* e_min = getenv("BOGP_POINT_MFMA_MIN");  // read per call: the tests run both flavours in one process
   const long long mfma_min = e_min ? atoll(e_min) : 768LL;
-  if (!eh && !cn && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
+  if (!c.eh && !c.cn && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
     const int Np = h->Np, nJ = (Np + 255) / 256;
     const long long Mc = ((long long)B * ncp + 63) / 64 * 64;
     if ((e = h->drT[0].ensure(h, (size_t)Np * Mc))) return e;
@@ -92,11 +135,7 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
     PointTriArgs fa;
     memset(&fa, 0, sizeof(fa));
     fa.part = h->dpt_part; fa.out = out; fa.nRB = nJ; fa.npass = 1; fa.d = h->d;
-    fa.rec_stride = pl.rec_stride; fa.q = q; fa.want_dacq = want_dacq ? 1 : 0; fa.estimate_trend = h->estimate_trend;
-    fa.minimize = minimize;
-    for (int i = 0; i < q; ++i) { fa.acq_id[i] = acq_id[i]; fa.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-    fa.plugin = plugin; fa.beta = h->beta; fa.G = h->G; fa.ftft = h->ftft; fa.sigma2 = h->sigma2;
-    fa.done_flag = done_flag; fa.done_seq = done_seq;
+    fill_criteria(h, pl, c, done_flag, done_seq, &fa);
     HIPCHK(h, launch_point_finish_mfma(fa, ncp, B, st));
     return BOGP_OK;
   }
@@ -127,42 +166,18 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const double* dXb, con
   ta.counter = h->dpt_counter; ta.out = out;
   ta.split_scratch = h->dpt_split; ta.split_counter = h->dpt_splitc; ta.rb = pl.rb; ta.nsplit = pl.nsplit;
   ta.ld = h->ldr; ta.Npp = pl.Npp; ta.Nr32 = pl.Nr32; ta.nRB = pl.nRB; ta.npass = pl.npass; ta.d = h->d;
-  ta.rec_stride = pl.rec_stride; ta.q = q; ta.want_dacq = want_dacq ? 1 : 0; ta.estimate_trend = h->estimate_trend;
-  ta.minimize = minimize;
-  for (int i = 0; i < q; ++i) { ta.acq_id[i] = acq_id[i]; ta.acq_par[i] = acq_par ? acq_par[i] : 0.0; }
-  ta.plugin = plugin; ta.beta = h->beta; ta.G = h->G; ta.ftft = h->ftft; ta.sigma2 = h->sigma2;
-  ta.done_flag = done_flag; ta.done_seq = done_seq; ta.trend_rec = trend_rec;
-  if (eh) {  // the m-target finish in place of k_point_finish (eh: cells, targets, the moment blocks; the rest is filled in here)
-    HIPCHK(h, launch_point_tri(ta, B, st, false));
-    PointEhviArgs ea = *eh;
-    ea.part = h->dpt_part; ea.rhs = h->dpt_rhs; ea.gamma = h->dgamma_base; ea.ld_gamma = h->Np; ea.out = out;
-    ea.N = h->N; ea.Npp = pl.Npp; ea.nRB = pl.nRB; ea.npass = pl.npass; ea.d = h->d; ea.rec_stride = pl.rec_stride;
-    ea.estimate_trend = h->estimate_trend; ea.beta = h->beta; ea.G = h->G; ea.ftft = h->ftft;
-    for (int t = 0; t < ea.m; ++t) ea.sigma2[t] = h->sigma2_t[t];
-    ea.done_flag = done_flag; ea.done_seq = done_seq;
-    HIPCHK(h, launch_point_ehvi_finish(ea, B, st));
-    return BOGP_OK;
-  }
-  if (cn) {  // the feasibility-weighted finish in place of k_point_finish (cn: criteria, bounds, the second blocks; the rest is filled in here)
-    HIPCHK(h, launch_point_tri(ta, B, st, false));
-    PointConstrainedArgs ca = *cn;
-    ca.part = h->dpt_part; ca.rhs = h->dpt_rhs; ca.gamma = h->dgamma_base; ca.ld_gamma = h->Np; ca.out = out;
-    ca.N = h->N; ca.Npp = pl.Npp; ca.nRB = pl.nRB; ca.npass = pl.npass; ca.d = h->d; ca.rec_stride = pl.rec_stride;
-    ca.estimate_trend = h->estimate_trend; ca.beta = h->beta; ca.G = h->G; ca.ftft = h->ftft;
-    for (int t = 0; t < ca.m; ++t) ca.sigma2[t] = h->sigma2_t[t];
-    ca.done_flag = done_flag; ca.done_seq = done_seq;
-    HIPCHK(h, launch_point_constrained_finish(ca, B, st));
-    return BOGP_OK;
-  }
-  HIPCHK(h, launch_point_tri(ta, B, st));
+  fill_criteria(h, pl, c, done_flag, done_seq, &ta);
+  ta.trend_rec = trend_rec;
+  HIPCHK(h, launch_point_tri(ta, B, st, !c.eh && !c.cn));  // an m-target finish takes k_point_finish's place
+  if (c.eh) HIPCHK(h, launch_point_ehvi_finish(multi_finish_args(h, pl, *c.eh, B, c.mom_stride, out, done_flag, done_seq), B, st));
+  if (c.cn) HIPCHK(h, launch_point_constrained_finish(multi_finish_args(h, pl, *c.cn, B, c.mom_stride, out, done_flag, done_seq), B, st));
   return BOGP_OK;
 }
 
-// the lock-step polish of B starts: bogp_polish's loop (one criterion of the single-target path), -- eh non-null -- bogp_polish_ehvi's or
-// -- cn non-null -- bogp_polish_constrained's
-int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const double* lo, const double* hi, int acq_id, double acq_par,
-                double plugin, int minimize, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals,
-                const PointEhviArgs* eh, const PointConstrainedArgs* cn = nullptr) {
+// the lock-step polish of B starts with the evaluation of `call` (one criterion and its gradient: q = 1) queued every iteration:
+// the loop of bogp_polish, bogp_polish_ehvi and bogp_polish_constrained
+int polish_loop(bogp_handle* h, const char* who, const PointCall& call, const double* X0, int B, const double* lo, const double* hi,
+                int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals) {
   int e;
   if (!X0 || !lo || !hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
   const int d = h->d;
@@ -206,7 +221,7 @@ int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const 
   while (it < max_evals) {
     const int burst = std::min(8, max_evals - it);
     for (int s = 0; s < burst; ++s, ++it) {
-      if ((e = queue_point_eval(h, pl, h->dpt_Xb, nullptr, B, 1, &acq_id, &acq_par, plugin, minimize, true, h->dpt_out, nullptr, 0, eh, cn))) return e;
+      if ((e = queue_point_eval(h, pl, call, h->dpt_Xb, nullptr, B, h->dpt_out))) return e;
       HIPCHK(h, launch_polish_step(pa, B, st));
     }
     HIPCHK(h, hipMemcpyAsync(hdone, dn_done, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -225,14 +240,21 @@ int polish_loop(bogp_handle* h, const char* who, const double* X0, int B, const 
   return BOGP_OK;
 }
 
-// what bogp_point_eval_ehvi and bogp_polish_ehvi refuse alike (the cells are checked by ehvi_cells_resident)
-int check_ehvi(bogp_handle* h, const char* who, int m) {
-  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no input gradient", who);
-  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model", who);
+// the committed model of an m-target finish: what check_ehvi and check_constrained refuse in the same words, behind their own forest
+// and "no committed model" lines
+int check_multi_model(bogp_handle* h, const char* who) {
   if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP || h->kernel == BOGP_KERNEL_MATERN_NU)
     FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the correlation has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who);
   if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
   if (h->d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
+  return BOGP_OK;
+}
+
+// what bogp_point_eval_ehvi and bogp_polish_ehvi refuse alike (the cells are checked by ehvi_cells_resident)
+int check_ehvi(bogp_handle* h, const char* who, int m) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no input gradient", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model", who);
+  if (int e = check_multi_model(h, who)) return e;
   if (m != h->n_t) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d but the committed model has %d targets", who, m, h->n_t);
   if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d outside [2, %d]", who, m, BOGP_MAX_TARGETS);
   if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
@@ -267,22 +289,12 @@ int ehvi_cells_resident(bogp_handle* h, const char* who, int m, int C, const dou
   return BOGP_OK;
 }
 
-}  // namespace
-
-namespace bogp {
-
-void ehvi_cells_forget(bogp_handle* h) {
-  h->h_ehvi_cells.clear();
-  h->ehvi_host_m = h->ehvi_host_C = 0;
-}
-
-static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, const int* acq_id, const double* acq_par, double plugin,
-                            int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq) {
+// stage the B rows of Xb, queue the evaluation of `call` and wait for it: afterwards the B records lie at h->hpin, the second blocks
+// (call.mom_stride doubles a point) behind them
+int point_eval_wait(bogp_handle* h, const PointPlan& pl, const PointCall& call, const double* Xb, int B) {
   hipStream_t st = h->stream;
   const int d = h->d;
-  const bool want_dacq = dacq != nullptr && q > 0;
-  const PointPlan pl = plan_of(h, B, q, want_dacq);
-  const size_t nrec = (size_t)B * pl.rec_stride;
+  const size_t nrec = (size_t)B * (pl.rec_stride + call.mom_stride);
   int e;
   // the finishing workgroups write straight into pinned host memory: one stream synchronisation, no copy command
   if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
@@ -299,7 +311,7 @@ static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, cons
     volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
     const unsigned long long seq = ++h->pt_seq;
     unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin.dev, dflag, seq))) return e;
+    if ((e = queue_point_eval(h, pl, call, dXb, Xb, B, h->hpin.dev, dflag, seq))) return e;
     bool seen = false;
     for (int spin = 0; spin < 400000; ++spin) {
       if (*flag == seq) { seen = true; break; }
@@ -308,19 +320,37 @@ static int point_eval_chunk(bogp_handle* h, const double* Xb, int B, int q, cons
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) HIPCHK(h, hipStreamSynchronize(st));
   } else {
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, acq_id, acq_par, plugin, minimize, want_dacq, h->hpin.dev))) return e;
+    if ((e = queue_point_eval(h, pl, call, dXb, Xb, B, h->hpin.dev))) return e;
     HIPCHK(h, hipStreamSynchronize(st));
   }
-  for (int b = 0; b < B; ++b) {
-    const double* o = h->hpin + (size_t)b * pl.rec_stride;
-    if (mu) mu[b] = o[0];
-    if (mse) mse[b] = o[1];
-    if (acq) memcpy(acq + (size_t)b * q, o + 2, (size_t)q * sizeof(double));
-    if (dmu) memcpy(dmu + (size_t)b * d, o + 2 + q, (size_t)d * sizeof(double));
-    if (dmse) memcpy(dmse + (size_t)b * d, o + 2 + q + d, (size_t)d * sizeof(double));
-    if (want_dacq) memcpy(dacq + (size_t)b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
+  return BOGP_OK;
+}
+
+// The B rows of Xb through point_eval_wait in chunks whose right-hand sides (8 ld NC bytes per point and pass) stay below 256 MB, and
+// never more than 4096 points; unpack(row of Xb, its record, its second block) copies a point's results out of the pinned buffer.
+template <class Unpack>
+int point_eval_chunks(bogp_handle* h, const PointCall& call, const double* Xb, int B, Unpack unpack) {
+  const int d = h->d;
+  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(chunk, B - b0);
+    const PointPlan pl = plan_of(h, nb, call.q, call.want_dacq);
+    const int e = point_eval_wait(h, pl, call, Xb + (size_t)b0 * d, nb);
+    if (e) return e;
+    const double* mom = h->hpin + (size_t)nb * pl.rec_stride;
+    for (int b = 0; b < nb; ++b) unpack((size_t)b0 + b, h->hpin + (size_t)b * pl.rec_stride, mom + (size_t)b * call.mom_stride);
   }
   return BOGP_OK;
+}
+
+}  // namespace
+
+namespace bogp {
+
+void ehvi_cells_forget(bogp_handle* h) {
+  h->h_ehvi_cells.clear();
+  h->ehvi_host_m = h->ehvi_host_C = 0;
 }
 
 int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, int q, const int* acq_id, const double* acq_par,
@@ -331,17 +361,16 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
   if (q > 0 && !acq && !dacq) FAIL(h, BOGP_ERR_INVALID, "%s: q > 0 needs acq or dacq", who);
   HIPCHK(h, hipSetDevice(h->device));
   const int d = h->d;
-  // points are served in chunks whose right-hand sides (8 ld NC bytes per point and pass) stay below 256 MB
-  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = std::min(chunk, B - b0);
-    e = point_eval_chunk(h, Xb + (size_t)b0 * d, nb, q, acq_id, acq_par, plugin, minimize, mu ? mu + b0 : nullptr, mse ? mse + b0 : nullptr,
-                         dmu ? dmu + (size_t)b0 * d : nullptr, dmse ? dmse + (size_t)b0 * d : nullptr, acq ? acq + (size_t)b0 * q : nullptr,
-                         dacq ? dacq + (size_t)b0 * q * d : nullptr);
-    if (e) return e;
-  }
-  return BOGP_OK;
+  const bool want_dacq = dacq != nullptr && q > 0;
+  const PointCall call{q, acq_id, acq_par, plugin, minimize, want_dacq, nullptr, nullptr, 0};
+  return point_eval_chunks(h, call, Xb, B, [=](size_t b, const double* o, const double*) {
+    if (mu) mu[b] = o[0];
+    if (mse) mse[b] = o[1];
+    if (acq) memcpy(acq + b * q, o + 2, (size_t)q * sizeof(double));
+    if (dmu) memcpy(dmu + b * d, o + 2 + q, (size_t)d * sizeof(double));
+    if (dmse) memcpy(dmse + b * d, o + 2 + q + d, (size_t)d * sizeof(double));
+    if (want_dacq) memcpy(dacq + b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
+  });
 }
 
 }  // namespace bogp
@@ -373,59 +402,11 @@ extern "C" int bogp_polish(bogp_handle* h, const double* X0, int B, const double
   if (!h) return BOGP_ERR_INVALID;
   int e = check_common(h, "bogp_polish", 1, &acq_id, &acq_par);
   if (e) return e;
-  return polish_loop(h, "bogp_polish", X0, B, lo, hi, acq_id, acq_par, plugin, minimize, max_evals, pgtol, factr, Xout, fout, n_evals, nullptr);
+  const PointCall call{1, &acq_id, &acq_par, plugin, minimize, true, nullptr, nullptr, 0};
+  return polish_loop(h, "bogp_polish", call, X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }
 
 // ---- EHVI and its input gradient at B points of the committed m-target model (kernels_point_ehvi.hip) --------------------------
-static int point_eval_ehvi_chunk(bogp_handle* h, const PointEhviArgs& eh0, const double* Xb, int B, bool want_mom, double* ehvi, double* dehvi,
-                                 double* mu, double* mse, double* dmu, double* dmse) {
-  hipStream_t st = h->stream;
-  const int d = h->d, m = eh0.m;
-  const PointPlan pl = plan_of(h, B, 1, true);
-  const size_t mom_stride = want_mom ? (size_t)2 * m + 2 * (size_t)m * d : 0;
-  const size_t nrec = (size_t)B * (pl.rec_stride + mom_stride);
-  int e;
-  if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
-  const double* dXb = nullptr;
-  if (B > 1 || d > BOGP_POINT_ARG_D) {
-    if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
-    HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
-    dXb = h->dpt_Xb;
-  }
-  PointEhviArgs eh = eh0;
-  eh.mom = want_mom ? h->hpin.dev + (size_t)B * pl.rec_stride : nullptr;
-  eh.mom_stride = (int)mom_stride;
-  const int one_id = BOGP_ACQ_EI;  // (sizes the record like one criterion; the id itself is not evaluated)
-  if (B == 1) {  // the BFGS loop's call: completion polled off the sequence word behind the records (point_eval_chunk)
-    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
-    const unsigned long long seq = ++h->pt_seq;
-    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin.dev, dflag, seq, &eh))) return e;
-    bool seen = false;
-    for (int spin = 0; spin < 400000; ++spin) {
-      if (*flag == seq) { seen = true; break; }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) HIPCHK(h, hipStreamSynchronize(st));
-  } else {
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, 1, &one_id, nullptr, 0.0, 0, true, h->hpin.dev, nullptr, 0, &eh))) return e;
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  for (int b = 0; b < B; ++b) {
-    const double* o = h->hpin + (size_t)b * pl.rec_stride;
-    ehvi[b] = o[2];
-    if (dehvi) memcpy(dehvi + (size_t)b * d, o + 3 + 2 * d, (size_t)d * sizeof(double));
-    if (!want_mom) continue;
-    const double* q = h->hpin + (size_t)B * pl.rec_stride + (size_t)b * mom_stride;
-    if (mu) memcpy(mu + (size_t)b * m, q, (size_t)m * sizeof(double));
-    if (mse) memcpy(mse + (size_t)b * m, q + m, (size_t)m * sizeof(double));
-    if (dmu) memcpy(dmu + (size_t)b * m * d, q + 2 * m, (size_t)m * d * sizeof(double));
-    if (dmse) memcpy(dmse + (size_t)b * m * d, q + 2 * m + (size_t)m * d, (size_t)m * d * sizeof(double));
-  }
-  return BOGP_OK;
-}
-
 extern "C" int bogp_point_eval_ehvi(bogp_handle* h, const double* Xb, int B, int m, int C, const double* lower, const double* upper,
                                     double* ehvi, double* dehvi, double* mu, double* mse, double* dmu, double* dmse) {
   if (!h) return BOGP_ERR_INVALID;
@@ -440,17 +421,16 @@ extern "C" int bogp_point_eval_ehvi(bogp_handle* h, const double* Xb, int B, int
   memset(&eh, 0, sizeof(eh));
   eh.m = m; eh.C = C; eh.lower = h->dehvi_cells; eh.upper = h->dehvi_cells + (size_t)C * m;
   const bool want_mom = mu || mse || dmu || dmse;
-  // chunks as point_eval_host's: the right-hand sides stay below 256 MB
-  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = std::min(chunk, B - b0);
-    e = point_eval_ehvi_chunk(h, eh, Xb + (size_t)b0 * d, nb, want_mom, ehvi + b0, dehvi ? dehvi + (size_t)b0 * d : nullptr,
-                              mu ? mu + (size_t)b0 * m : nullptr, mse ? mse + (size_t)b0 * m : nullptr,
-                              dmu ? dmu + (size_t)b0 * m * d : nullptr, dmse ? dmse + (size_t)b0 * m * d : nullptr);
-    if (e) return e;
-  }
-  return BOGP_OK;
+  const size_t md = (size_t)m * d;
+  return point_eval_chunks(h, ehvi_call(&eh, want_mom ? 2 * m + 2 * md : 0), Xb, B, [=](size_t b, const double* o, const double* mom) {
+    ehvi[b] = o[2];
+    if (dehvi) memcpy(dehvi + b * d, o + 3 + 2 * d, (size_t)d * sizeof(double));
+    if (!want_mom) return;
+    if (mu) memcpy(mu + b * m, mom, (size_t)m * sizeof(double));
+    if (mse) memcpy(mse + b * m, mom + m, (size_t)m * sizeof(double));
+    if (dmu) memcpy(dmu + b * md, mom + 2 * m, md * sizeof(double));
+    if (dmse) memcpy(dmse + b * md, mom + 2 * m + md, md * sizeof(double));
+  });
 }
 
 extern "C" int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const double* lo, const double* hi, int m, int C,
@@ -465,38 +445,17 @@ extern "C" int bogp_polish_ehvi(bogp_handle* h, const double* X0, int B, const d
   PointEhviArgs eh;
   memset(&eh, 0, sizeof(eh));
   eh.m = m; eh.C = C; eh.lower = h->dehvi_cells; eh.upper = h->dehvi_cells + (size_t)C * m;
-  return polish_loop(h, who, X0, B, lo, hi, BOGP_ACQ_EI, 0.0, 0.0, 0, max_evals, pgtol, factr, Xout, fout, n_evals, &eh);
+  return polish_loop(h, who, ehvi_call(&eh, 0), X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }
 
 // ---- feasibility-weighted criteria and their input gradients at B points of the committed m-target model (kernels_point_constrained.hip) ----
-// what bogp_point_eval_constrained and bogp_polish_constrained refuse alike: check_ehvi's model checks and bogp_sweep_constrained's
-// checks of the criteria and the bounds, with its codes and wording
+// what bogp_point_eval_constrained and bogp_polish_constrained refuse alike: the model, then what bogp_sweep_constrained refuses too
 static int check_constrained(bogp_handle* h, const char* who, int q, const int* acq_id, const double* acq_par, int n_con, const double* lo,
                              const double* hi) {
   if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
   if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
-  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP || h->kernel == BOGP_KERNEL_MATERN_NU)
-    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the correlation has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who);
-  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: several targets take the constant trend only (gpr.py:787)", who);
-  if (h->d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
-  const int m = h->n_t;
-  if (m < 2 || m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has %d target(s); an objective and its constraints need 2 .. %d", who, m, BOGP_MAX_TARGETS);
-  if (n_con != m - 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d but the committed model has %d targets (one objective, %d constraints)", who, n_con, m, m - 1);
-  if (q < 1 || q > BOGP_MAX_Q) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_Q);
-  if (!acq_id || !lo || !hi) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo and hi must be non-null", who);
-  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
-  for (int c = 0; c < q; ++c) {
-    const int id = acq_id[c];
-    if (id == BOGP_ACQ_UCB) FAIL(h, BOGP_ERR_INVALID, "%s: criterion %d is UCB, which changes sign: its product with a probability orders nothing (EI, EpsilonPI, MGFI or BOGP_ACQ_NONE)", who, c);
-    if (id != BOGP_ACQ_EI && id != BOGP_ACQ_EPSILON_PI && id != BOGP_ACQ_MGFI && id != BOGP_ACQ_NONE) FAIL(h, BOGP_ERR_INVALID, "%s: unknown acquisition id %d", who, id);
-    if (id == BOGP_ACQ_EPSILON_PI && (!acq_par || !(acq_par[c] >= 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be >= 0 (epsilon = 0 is plain PI)", who, c);
-    if (id == BOGP_ACQ_MGFI && (!acq_par || !(acq_par[c] > 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be > 0 (the reference asserts t > 0)", who, c);
-  }
-  for (int j = 0; j < n_con; ++j) {
-    if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
-    if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
-  }
-  return BOGP_OK;
+  if (int e = check_multi_model(h, who)) return e;
+  return check_constrained_request(h, who, q, acq_id, acq_par, n_con, lo, hi);
 }
 
 static void fill_constrained(const bogp_handle* h, PointConstrainedArgs* cn, int q, const int* acq_id, const double* acq_par, double plugin,
@@ -505,57 +464,6 @@ static void fill_constrained(const bogp_handle* h, PointConstrainedArgs* cn, int
   cn->m = h->n_t; cn->q = q; cn->plugin = plugin; cn->minimize = minimize;
   for (int c = 0; c < q; ++c) { cn->acq_id[c] = acq_id[c]; cn->acq_par[c] = acq_par ? acq_par[c] : 0.0; }
   for (int j = 0; j < n_con; ++j) { cn->lo[j + 1] = lo[j]; cn->hi[j + 1] = hi[j]; }
-}
-
-static int point_eval_constrained_chunk(bogp_handle* h, const PointConstrainedArgs& cn0, const double* Xb, int B, bool want_mom, double* acq,
-                                        double* dacq, double* pof, double* dpof, double* mu, double* mse, double* dmu, double* dmse) {
-  hipStream_t st = h->stream;
-  const int d = h->d, m = cn0.m, q = cn0.q;
-  const PointPlan pl = plan_of(h, B, q, true);
-  const size_t mom_stride = want_mom ? (size_t)1 + d + 2 * m + 2 * (size_t)m * d : 0;
-  const size_t nrec = (size_t)B * (pl.rec_stride + mom_stride);
-  int e;
-  if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
-  const double* dXb = nullptr;
-  if (B > 1 || d > BOGP_POINT_ARG_D) {
-    if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
-    HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
-    dXb = h->dpt_Xb;
-  }
-  PointConstrainedArgs cn = cn0;
-  cn.mom = want_mom ? h->hpin.dev + (size_t)B * pl.rec_stride : nullptr;
-  cn.mom_stride = (int)mom_stride;
-  if (B == 1) {  // the BFGS loop's call: completion polled off the sequence word behind the records (point_eval_chunk)
-    volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(h->hpin + nrec);
-    const unsigned long long seq = ++h->pt_seq;
-    unsigned long long* dflag = reinterpret_cast<unsigned long long*>(h->hpin.dev + nrec);
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, cn.acq_id, cn.acq_par, cn.plugin, cn.minimize, true, h->hpin.dev, dflag, seq, nullptr, &cn))) return e;
-    bool seen = false;
-    for (int spin = 0; spin < 400000; ++spin) {
-      if (*flag == seq) { seen = true; break; }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) HIPCHK(h, hipStreamSynchronize(st));
-  } else {
-    if ((e = queue_point_eval(h, pl, dXb, Xb, B, q, cn.acq_id, cn.acq_par, cn.plugin, cn.minimize, true, h->hpin.dev, nullptr, 0, nullptr, &cn))) return e;
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  for (int b = 0; b < B; ++b) {
-    const double* o = h->hpin + (size_t)b * pl.rec_stride;
-    if (acq) memcpy(acq + (size_t)b * q, o + 2, (size_t)q * sizeof(double));
-    if (dacq) memcpy(dacq + (size_t)b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
-    if (!want_mom) continue;
-    const double* r = h->hpin + (size_t)B * pl.rec_stride + (size_t)b * mom_stride;
-    if (pof) pof[b] = r[0];
-    if (dpof) memcpy(dpof + (size_t)b * d, r + 1, (size_t)d * sizeof(double));
-    r += 1 + d;
-    if (mu) memcpy(mu + (size_t)b * m, r, (size_t)m * sizeof(double));
-    if (mse) memcpy(mse + (size_t)b * m, r + m, (size_t)m * sizeof(double));
-    if (dmu) memcpy(dmu + (size_t)b * m * d, r + 2 * m, (size_t)m * d * sizeof(double));
-    if (dmse) memcpy(dmse + (size_t)b * m * d, r + 2 * m + (size_t)m * d, (size_t)m * d * sizeof(double));
-  }
-  return BOGP_OK;
 }
 
 extern "C" int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int B, int q, const int* acq_id, const double* acq_par, double plugin,
@@ -571,18 +479,20 @@ extern "C" int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int
   PointConstrainedArgs cn;
   fill_constrained(h, &cn, q, acq_id, acq_par, plugin, minimize, n_con, lo, hi);
   const bool want_mom = pof || dpof || mu || mse || dmu || dmse;
-  // chunks as point_eval_host's: the right-hand sides stay below 256 MB
-  const size_t per_point = (size_t)point_passes(d) * h->ldr * point_columns_per_pass(d) * sizeof(double);
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / per_point));
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = std::min(chunk, B - b0);
-    e = point_eval_constrained_chunk(h, cn, Xb + (size_t)b0 * d, nb, want_mom, acq + (size_t)b0 * q, dacq ? dacq + (size_t)b0 * q * d : nullptr,
-                                     pof ? pof + b0 : nullptr, dpof ? dpof + (size_t)b0 * d : nullptr, mu ? mu + (size_t)b0 * m : nullptr,
-                                     mse ? mse + (size_t)b0 * m : nullptr, dmu ? dmu + (size_t)b0 * m * d : nullptr,
-                                     dmse ? dmse + (size_t)b0 * m * d : nullptr);
-    if (e) return e;
-  }
-  return BOGP_OK;
+  const size_t md = (size_t)m * d;
+  const PointCall call{q, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, want_mom ? 1 + d + 2 * m + 2 * md : 0};
+  return point_eval_chunks(h, call, Xb, B, [=](size_t b, const double* o, const double* mom) {
+    memcpy(acq + b * q, o + 2, (size_t)q * sizeof(double));
+    if (dacq) memcpy(dacq + b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
+    if (!want_mom) return;
+    if (pof) pof[b] = mom[0];
+    if (dpof) memcpy(dpof + b * d, mom + 1, (size_t)d * sizeof(double));
+    mom += 1 + d;
+    if (mu) memcpy(mu + b * m, mom, (size_t)m * sizeof(double));
+    if (mse) memcpy(mse + b * m, mom + m, (size_t)m * sizeof(double));
+    if (dmu) memcpy(dmu + b * md, mom + 2 * m, md * sizeof(double));
+    if (dmse) memcpy(dmse + b * md, mom + 2 * m + md, md * sizeof(double));
+  });
 }
 
 extern "C" int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int acq_id,
@@ -592,8 +502,8 @@ extern "C" int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, 
   const char* who = "bogp_polish_constrained";
   int e = check_constrained(h, who, 1, &acq_id, &acq_par, n_con, lo, hi);
   if (e) return e;
-  if (!X0 || !box_lo || !box_hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
   PointConstrainedArgs cn;
   fill_constrained(h, &cn, 1, &acq_id, &acq_par, plugin, minimize, n_con, lo, hi);
-  return polish_loop(h, who, X0, B, box_lo, box_hi, acq_id, acq_par, plugin, minimize, max_evals, pgtol, factr, Xout, fout, n_evals, nullptr, &cn);
+  const PointCall call{1, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, 0};
+  return polish_loop(h, who, call, X0, B, box_lo, box_hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }

@@ -215,6 +215,22 @@ def test_bits(eng, N, d):
             assert g1[:, 0].tobytes() == np.ascontiguousarray(full[1][:, c]).tobytes()
 
 
+def test_large_batches_are_served_in_chunks(eng):
+    """More rows than one launch takes (4096 points a chunk): at N = 37, d = 2 the row blocks split 3-fold for every B, so a row's bytes
+    do not depend on the chunk it fell into.  Rows at both ends of both chunks equal their one-row calls byte for byte, every array."""
+    N, d, m, B = 37, 2, 3, 4100
+    assert _tri_split(N, d, 1) == _tri_split(N, d, 4096)
+    assert _tri_split(N, d, 4096) == _tri_split(N, d, B - 4096)
+    par, mode, X, Y, lo, hi, plugin = _problem(_lib.KERNEL_SE, True, N, d, m, 1, seed=N)
+    _commit(eng, _lib.KERNEL_SE, par, mode, X, Y)
+    rows = _rows(np.random.default_rng(8), X, B, d)
+    batch = eng.point_eval_constrained(rows, ACQ4, plugin, True, lo, hi, moments=True)
+    assert [a.shape for a in batch] == [(B, 4), (B, 4, d), (B,), (B, d), (B, m), (B, m), (B, m, d), (B, m, d)]
+    for b in (0, 4095, 4096, 4099):
+        one = eng.point_eval_constrained(rows[b : b + 1], ACQ4, plugin, True, lo, hi, moments=True)
+        assert all(np.ascontiguousarray(o[0]).tobytes() == np.ascontiguousarray(a[b]).tobytes() for o, a in zip(one, batch)), b
+
+
 @pytest.mark.parametrize("kernel,N,d,m,B", [(_lib.KERNEL_MATERN52, 100, 12, 3, 33), (_lib.KERNEL_SE, 37, 2, 2, 1), (_lib.KERNEL_ABSEXP, 157, 23, 8, 33)])
 def test_all_bounds_infinite(eng, kernel, N, d, m, B):
     """Check (d): P = 1.0 and dpof = 0 exactly; acq / dacq equal bogp_point_eval_batch on a model committed on column 0 alone at rtol 1e-6."""

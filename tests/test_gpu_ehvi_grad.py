@@ -172,6 +172,21 @@ def test_independent_of_B_and_deterministic(eng, N, d):
             assert max(_excess(np.asarray(o[0]), np.asarray(a[b])) for o, a in zip(one, batch)) <= 1.0
 
 
+def test_large_batches_are_served_in_chunks(eng):
+    """More rows than one launch takes (4096 points a chunk): at N = 37, d = 2 the row blocks split 3-fold for every B, so a row's bytes
+    do not depend on the chunk it fell into.  Rows at both ends of both chunks equal their one-row calls byte for byte, every array."""
+    N, d, m, B = 37, 2, 2, 4100
+    assert _tri_split(N, d, 1) == _tri_split(N, d, 4096) == _tri_split(N, d, B - 4096) == 3
+    par, mode, X, Y, lo, hi = _problem(_lib.KERNEL_SE, True, N, d, m, "front5", seed=N)
+    _commit(eng, _lib.KERNEL_SE, par, mode, X, Y)
+    rows = _rows(np.random.default_rng(8), X, B, d)
+    batch = eng.point_eval_ehvi(rows, lo, hi, moments=True)
+    assert [a.shape for a in batch] == [(B,), (B, d), (B, m), (B, m), (B, m, d), (B, m, d)]
+    for b in (0, 4095, 4096, 4099):
+        one = eng.point_eval_ehvi(rows[b : b + 1], lo, hi, moments=True)
+        assert all(np.ascontiguousarray(o[0]).tobytes() == np.ascontiguousarray(a[b]).tobytes() for o, a in zip(one, batch)), b
+
+
 def test_clamp_edges(eng):
     """Check 5.  A row ON a training point of a noiseless model: MSE is rounding noise below the 1e-9 clamp, the gradient is finite
     and is the mean path alone.  So it is 1e-6 away from the training point, where MSE is still below the clamp but its gradient is
