@@ -27,7 +27,7 @@ __version__ = "0.1.0"
 from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto, thompson  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
 from .acquisition import EHVI, EI, MGFI, PI, UCB, Constrained, EpsilonPI  # noqa: E402,F401
-from .optim import argmax_restart, batch_argmax, believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
+from .optim import argmax_restart, batch_argmax, believer_batch, constrained_believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
 from .integration import feasible_xopt, install, uninstall  # noqa: E402,F401
 from .lift import Lift  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401

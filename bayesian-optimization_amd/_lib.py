@@ -86,6 +86,9 @@ SIGNATURES = {
     "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
                                            _dp, _dp]),
     "bogp_believer_ehvi_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_believer_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                  _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "bogp_believer_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
     "bogp_lift_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bogp_lift_clear": (C.c_int, [C.c_void_p]),
     "bogp_lift_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _lp, _dp, _dp]),
@@ -825,6 +828,58 @@ class Engine:
         self._check(self._lib.bogp_believer_ehvi_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
                                                       C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, ehvi_ms=e.value, n_passes=n.value)
+
+    def sweep_believer_constrained(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize, lo, hi, pending=None, believe_plugin=True,
+                                   return_values=False):
+        """Kriging-believer batch under modelled constraints over the current candidates (bogp_sweep_believer_constrained): step j
+        maximises criterion j of `acq` (EI, EpsilonPI, MGFI on target 0; ACQ_NONE: 1) x the constraints' probabilities of feasibility
+        in [lo, hi], on the m means and on the variances conditioned on the `pending` rows (n, d) and on the winners of the steps
+        before it.  With `believe_plugin` a believed point whose means are feasible lowers the plugin.  Returns a dict: best_val (q,),
+        best_idx (q,), best_x (q, d), best_mu (q, m), pivots (n + q,), plugins (q,) and, with return_values, acq (q, M), pof (q, M)
+        and mse (q, M, m).  What the library refuses as unsupported (a forest, a lift, a polynomial basis, several ranks) raises
+        NotImplementedError with its message."""
+        q = len(acq)
+        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
+        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        m = len(lo) + 1
+        pend = None if pending is None or len(pending) == 0 else _f64(pending)
+        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
+            raise ValueError("pending points must have shape (n, %d)" % self.d)
+        n_pend = 0 if pend is None else pend.shape[0]
+        best = np.empty(q)
+        idx = np.empty(q, dtype=np.int64)
+        bx = np.empty((q, self.d))
+        bmu = np.empty((q, m))
+        piv = np.empty(n_pend + q)
+        plugs = np.empty(q)
+        vals = np.empty((q, self.M)) if return_values else None
+        pof = np.empty((q, self.M)) if return_values else None
+        mse = np.empty((q, self.M, m)) if return_values else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        try:
+            self._check(self._lib.bogp_sweep_believer_constrained(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin),
+                                                                  int(bool(minimize)), int(bool(believe_plugin)), len(lo), _ptr(lo), _ptr(hi),
+                                                                  _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(bmu),
+                                                                  _ptr(piv), _ptr(plugs), _ptr(vals), _ptr(pof), _ptr(mse)))  # fmt: skip
+        except BogpError as e:
+            if e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, plugins=plugs)
+        if return_values:
+            out.update(acq=vals, pof=pof, mse=mse)
+        return out
+
+    def believer_constrained_last(self) -> dict:
+        """Producer, solve, k_believer and k_believer_constrained time (ms) and the candidate passes of the last
+        sweep_believer_constrained (bogp_believer_constrained_last)."""
+        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_believer_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
+                                                             C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, criterion_ms=e.value, n_passes=n.value)
 
     # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------
     def set_lift(self, A, mean, center, lo, hi):

@@ -9,6 +9,7 @@
 // The running variance is kept as sigma2 s, started from the sweep's clamped MSE_0: where s_0 < 0 the clamp changes nothing that is
 // returned (s only decreases, and every output is max(0, .) of it).
 // bogp_sweep_believer_ehvi (below) is the same recursion for an m-target model under EHVI; bogp_ehvi_grid_cells the host's cell decomposition.
+// bogp_sweep_believer_constrained (last) is that recursion again under modelled constraints: target 0 the objective, the others constraints.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,8 +48,8 @@ struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point
   }
 };
 
-// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi
-enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI };
+// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi, k_believer_constrained
+enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI, B_CONSTRAINED };
 
 // The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, one solve span -- and the
 // host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
@@ -609,6 +610,204 @@ extern "C" int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* 
   if (solve_ms) *solve_ms = h->bel_solve_ms;
   if (update_ms) *update_ms = h->bel_pass_ms;
   if (ehvi_ms) *ehvi_ms = h->bel_ehvi_ms;
+  if (n_passes) *n_passes = h->bel_passes;
+  return BOGP_OK;
+}
+
+// ---- believer batches under modelled constraints: bogp_sweep_believer_constrained --------------------------------------------------
+// bogp_sweep_believer_ehvi's recursion with bogp_sweep_constrained's criterion: pass 0 is the constrained sweep (k_constrained) with
+// criterion 0, every believed point costs the solve, k_believer for c(x) in unit variance and ONE launch of k_believer_constrained
+// (kernels_believer_constrained.hip), which takes sigma2_k c^2 off every target's MSE and evaluates the step's criterion.  The plugin
+// follows the believed points that are feasible by belief; the criteria, the bounds, the hyper-parameters and sigma2_k stay fixed.
+extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+                                               int believe_plugin, int n_con, const double* lo, const double* hi, const double* pending,
+                                               int n_pending, double* best_val, int64_t* best_idx, double* best_x, double* best_mu,
+                                               double* pivots, double* plugin_out, double* acq_out, double* pof_out, double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_believer_constrained";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior correlation to condition on", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+  if (q < 1 || n_pending < 0 || q + n_pending > BOGP_MAX_BELIEVED)
+    FAIL(h, BOGP_ERR_INVALID, "%s: q = %d, n_pending = %d: q >= 1 and q + n_pending <= %d", who, q, n_pending, BOGP_MAX_BELIEVED);
+  if (q > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d proposals from %lld candidates (every step takes a row no step before it took)", who, q, (long long)h->M);
+  if (!acq_id || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: acq_id, lo, hi, best_val and best_idx must be non-null", who);
+  if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
+  int rc = check_constrained_request(h, who, q, acq_id, acq_par, n_con, lo, hi);
+  if (rc) return rc;
+  const int d = h->d, N = h->N, Np = h->Np, m = h->n_t;
+  for (size_t i = 0; i < (size_t)n_pending * d; ++i)
+    if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
+  const int64_t M = h->M;
+  const int P = n_pending, Btot = P + q;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+
+  // ---- pass 0: bogp_sweep_constrained's sweep with criterion 0; with pending points it serves the moments only
+  if ((rc = h->dpof_out.ensure(h, (size_t)M))) return rc;
+  ConstrainedArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.gamma = h->dgamma_base; ca.ld_gamma = Np; ca.N = N; ca.m = m;
+  for (int t = 0; t < m; ++t) ca.sigma2[t] = h->sigma2_t[t];
+  for (int j = 0; j < n_con; ++j) { ca.lo[j + 1] = lo[j]; ca.hi[j + 1] = hi[j]; }
+  ca.q = 1; ca.acq_id[0] = acq_id[0]; ca.acq_par[0] = acq_par ? acq_par[0] : 0.0;
+  ca.plugin = plugin; ca.minimize = minimize; ca.pof_out = h->dpof_out.ptr;
+  invalidate_sweep_results(h);  // dbest_* are overwritten
+  SweepRequest rq;
+  rq.want_out = true; rq.want_acq_out = true; rq.q = 1; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.minimize = minimize;
+  rq.cn = &ca;
+  if ((rc = run_sweep(h, rq))) return rc;
+  if ((rc = candidates_ready(h))) return rc;
+
+  // ---- the later passes
+  SweepGeometry pl;
+  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
+  const int64_t nblk = (M + 255) / 256;
+  if ((rc = h->dbel_s.ensure(h, (size_t)M * m))) return rc;
+  if ((rc = h->dbel_row.ensure(h, (size_t)(3 + m) * M))) return rc;
+  if ((rc = h->dbel_small.ensure(h, SolveBufs::doubles(d, N)))) return rc;
+  if (Btot > 1)
+    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_constrained
+  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
+  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = ensure_sweep_outputs(h, 1, nblk, 0, false))) return rc;
+  const SolveBufs sb(h->dbel_small, d, N);
+  double* dacq_row = h->dbel_row;
+  double* dpof_row = h->dbel_row + M;
+  double* dscratch = h->dbel_row + 2 * M;  // k_believer's own s, in unit variance: not used
+  double* dmse_row = h->dbel_row + 3 * M;  // [M][m]
+
+  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(h, hipMemsetAsync(dscratch, 0, (size_t)M * sizeof(double), st));
+  std::vector<double> hgamma((size_t)m * Np), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED), hmu((size_t)m);
+  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base, (size_t)m * Np * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+
+  Believed bl;
+  bl.r.resize((size_t)Btot * N);
+  bl.a.resize((size_t)Btot * N);
+  bl.u.resize(Btot);
+  memset(bl.L, 0, sizeof(bl.L));
+  int slots = 0;
+  bool chunk_resident = false;
+  h->bel_timer.begin();
+  h->bel_passes = 0;
+  double plug = plugin;
+  // a believed point that is feasible by belief -- every constraint's mean inside its interval -- may lower the plugin, which
+  // arrives in the criterion's own sign (already negated when maximising); an infeasible one leaves it
+  auto believe_means = [&](const double* mu) {
+    if (!believe_plugin) return;
+    for (int k = 1; k < m; ++k)
+      if (!(lo[k - 1] <= mu[k] && mu[k] <= hi[k - 1])) return;
+    const double y_hat = minimize ? mu[0] : -1 * mu[0];
+    if (y_hat < plug) plug = y_hat;
+  };
+
+  // One believed point, as in bogp_sweep_believer_ehvi.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it joins the plugin
+  // before the pass (a winner's means are read from the sweep's array by the caller, before this).
+  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
+    const int i = bl.n;
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
+    if (is_pending) {
+      const double* ri = &bl.r[(size_t)i * N];
+      for (int t = 0; t < m; ++t) {
+        double rg = 0.0;
+        for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[(size_t)t * Np + n];
+        hmu[t] = h->beta + rg;
+      }
+      believe_means(hmu.data());
+    }
+    const bool active = bl.L[i][i] > 0.0;
+    if (!pass || (!active && step < 0)) return BOGP_OK;
+    if (active) {  // c(x) of this point for every candidate, chunk by chunk
+      bl.slot[i] = slots++;
+      BelieverArgs ba;
+      memset(&ba, 0, sizeof(ba));
+      ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
+      ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
+      ba.update = 1;
+      ba.self_row = -1;
+      ba.u_p = bl.u[i]; ba.inv_root = 1.0 / bl.L[i][i]; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
+      for (int k = 0; k < i; ++k)
+        if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
+          ba.prev_slot[ba.nprev] = bl.slot[k];
+          ba.prev_c[ba.nprev] = bl.L[i][k];
+          ++ba.nprev;
+        }
+      ba.C = h->dbel_C; ba.c_out = h->dbel_C + (size_t)bl.slot[i] * M; ba.s = dscratch; ba.sigma2 = 1.0;
+      ba.eval = 0;
+      for (int64_t c = 0; c < pl.nchunk; ++c) {
+        ba.m0 = c * pl.Mc; ba.mcount = std::min<int64_t>(pl.Mc, M - ba.m0);
+        if (int rs = believer_chunk(h, pl, ba, !chunk_resident)) return rs;
+        chunk_resident = pl.nchunk == 1;
+      }
+    }
+    BelieverConstrainedArgs bc;
+    memset(&bc, 0, sizeof(bc));
+    bc.M = M; bc.m = m; bc.update = active ? 1 : 0; bc.c = active ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr;
+    bc.self_row = row; bc.s = h->dbel_s;
+    for (int t = 0; t < m; ++t) { bc.sigma2[t] = ca.sigma2[t]; bc.lo[t] = ca.lo[t]; bc.hi[t] = ca.hi[t]; }
+    bc.eval = step >= 0 ? 1 : 0;
+    if (step >= 0) {
+      bc.acq_id = acq_id[step]; bc.acq_par = acq_par ? acq_par[step] : 0.0; bc.plugin = plug; bc.minimize = minimize;
+      bc.n_taken = step;  // the winners of steps 0 .. step - 1
+      for (int k = 0; k < step; ++k) bc.taken[k] = best_idx[k];
+      if (plugin_out) plugin_out[step] = plug;
+    }
+    bc.mu = h->dmu_out; bc.acq_out = dacq_row; bc.pof_out = dpof_row; bc.mse_out = dmse_row; bc.blk_val = h->dblk_val; bc.blk_idx = h->dblk_idx;
+    if (int rs = timed_span(h, h->bel_timer, st, B_CONSTRAINED, [&] { return launch_believer_constrained(bc, st); })) return rs;
+    ++h->bel_passes;
+    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
+    return BOGP_OK;
+  };
+
+  if (P == 0 && plugin_out) plugin_out[0] = plugin;
+  for (int i = 0; i < P; ++i)
+    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
+
+  for (int j = 0; j < q; ++j) {
+    // the winner of step j is in dbest_*[0]; its values / PoF / MSE in the sweep's own arrays (step 0 without pending points) or the row buffers
+    const bool from_sweep = j == 0 && P == 0;
+    int64_t idx = 0;
+    HIPCHK(h, hipMemcpyAsync(&best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out + (size_t)j * M, from_sweep ? h->dacq_out : dacq_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pof_out) HIPCHK(h, hipMemcpyAsync(pof_out + (size_t)j * M, from_sweep ? h->dpof_out : dpof_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out + (size_t)j * M * m, from_sweep ? h->dmse_out : dmse_row, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    best_idx[j] = idx;
+    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "%s: step %d returned row %lld outside [0, %lld)", who, j, (long long)idx, (long long)M);
+    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hmu.data(), h->dmu_out + (size_t)idx * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (best_x) memcpy(best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
+    if (best_mu) memcpy(best_mu + (size_t)j * m, hmu.data(), (size_t)m * sizeof(double));
+    if (j == q - 1) {
+      if (pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
+      break;
+    }
+    believe_means(hmu.data());
+    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
+  }
+
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  h->bel_con_ms = h->bel_timer.sum(B_CONSTRAINED);
+  return BOGP_OK;
+}
+
+extern "C" int bogp_believer_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
+                                              int* n_passes) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (corr_ms) *corr_ms = h->bel_corr_ms;
+  if (solve_ms) *solve_ms = h->bel_solve_ms;
+  if (update_ms) *update_ms = h->bel_pass_ms;
+  if (criterion_ms) *criterion_ms = h->bel_con_ms;
   if (n_passes) *n_passes = h->bel_passes;
   return BOGP_OK;
 }

@@ -285,11 +285,13 @@ struct bogp_handle {
   bogp::DevBuf<double> dbel_C;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
   bogp::DevBuf<double> dbel_row;    // [2][M] criterion values / MSE of the step evaluated last
   bogp::DevBuf<double> dbel_small;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
-  bogp::SpanTimer bel_timer;        // solves, chunk producers, k_believer, k_believer_ehvi (run_sweep restarts the sweep's own)
+  bogp::SpanTimer bel_timer;        // solves, chunk producers, k_believer, k_believer_ehvi / k_believer_constrained (run_sweep restarts the sweep's own)
   double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
   // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
   double bel_ehvi_ms = 0;  // k_believer_ehvi of the last bogp_sweep_believer_ehvi
+  // bogp_sweep_believer_constrained likewise (dbel_s [M][m], dbel_row [values M | PoF M | scratch M | MSE M x m])
+  double bel_con_ms = 0;   // k_believer_constrained of the last bogp_sweep_believer_constrained
 
   // Thompson-sampling batches (bogp_api_thompson.hip)
   bogp::DevBuf<double> dth_small;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight

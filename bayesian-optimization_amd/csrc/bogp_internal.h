@@ -325,6 +325,33 @@ struct BelieverEhviArgs {
 };
 hipError_t launch_believer_ehvi(const BelieverEhviArgs& a, hipStream_t st);
 
+// the m-target half of a believer pass under modelled constraints (kernels_believer_constrained.hip), ONE launch over all M rows
+// behind the chunk loop in which k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a
+// step -- that step's feasibility-weighted criterion on (mu, max(0, MSE)) in k_constrained's expressions (target 0 the objective,
+// targets 1 .. m - 1 constraints feasible in [lo_k, hi_k]) with one argmax record per 256 rows
+struct BelieverConstrainedArgs {
+  int64_t M;
+  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
+  int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
+  const double* c;        // [M] c(x) of the believed point
+  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
+  double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
+  double sigma2[8];       // per target
+  double lo[8], hi[8];    // per target; entry 0 is not read
+  int eval;               // evaluate the criterion behind the update
+  int acq_id, minimize;   // BOGP_ACQ_EI / EPSILON_PI / MGFI, or BOGP_ACQ_NONE: the probability of feasibility alone
+  double acq_par, plugin;
+  int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
+  int64_t taken[32];
+  const double* mu;       // [M][m]
+  double* acq_out;        // [M]
+  double* pof_out;        // [M]
+  double* mse_out;        // [M][m] max(0, MSE): what the step saw
+  double* blk_val;        // [ceil(M / 256)]
+  int64_t* blk_idx;
+};
+hipError_t launch_believer_constrained(const BelieverConstrainedArgs& a, hipStream_t st);
+
 // q sample paths over a chunk (kernels_thompson.hip): path_j(x) = mu(x) + z_j(x) - r(x) . g_j - b_j with the random-Fourier-feature draw
 // z_j(x) = sum_l W[l][j] cos(omega_l . x + phase_l), one np.argmax record per path and 64 rows
 struct ThompsonArgs {

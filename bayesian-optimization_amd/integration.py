@@ -98,6 +98,11 @@ def fused_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=N
         crits.append(c)
         masks, values = m, v
     design = optim.DEVICE_DESIGNS.get(optimizer)
+    if (_CONSTRAINTS.get("batches") == "believer" and all(optim.is_constrained(c) for c in crits) and masks is None and not fixed
+            and kw.get("h") is None and kw.get("g") is None):  # fmt: skip
+        # install(constraint_batches="believer"): the q feasibility-weighted criteria condition each other (every other case: below)
+        xs, fs = optim.constrained_believer_batch(crits, kw["search_space"], int(budget or kw["eval_budget"]), design=design)
+        return tuple(xs), tuple(fs)
     k = int(min(32, n_point + 8))  # fall-backs: at most n_point - 1 taken by earlier criteria + a few history hits
     xs, fs = optim.batch_argmax(crits, kw["search_space"], int(budget or kw["eval_budget"]), history=_history_of(self), k=k,
                                 design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"), **_strategy_of(masks, kw, crits))  # fmt: skip
@@ -530,7 +535,7 @@ def _dispatching_surrogate(host_cls):
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
-            equality_tol: float = 0.1, constraint_gradient: bool = False):
+            equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk"):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -569,7 +574,18 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
 
     `constraint_gradient=True` (with `expensive_constraints=True`; alone it raises ValueError): such a driver also accepts "BFGS",
     "sweep-BFGS" and "sweep-device-BFGS" and maximises `bogp.Constrained(input_gradient=True)` -- the input gradient of
-    `bogp_point_eval_constrained` and the lock-step polish `bogp_polish_constrained`.  Without it those optimisers raise as before."""
+    `bogp_point_eval_constrained` and the lock-step polish `bogp_polish_constrained`.  Without it those optimisers raise as before.
+
+    `constraint_batches` = "topk" | "believer" ("believer" with `expensive_constraints=True`; alone it raises ValueError): how the fused
+    `ParallelBO` step keeps the q points of a driver with modelled constraints apart.  "topk" (default): as before, whatever
+    `batch_strategy` says.  "believer": `optim.constrained_believer_batch` -- criterion j sees the m variances conditioned on the
+    winners before it, and a believed point that is feasible by belief lowers the plugin -- when every criterion of the step is a
+    `bogp.Constrained`, the inner optimiser is of the sweep family, nothing is fixed and no cheap h / g is given; every other step
+    takes the route it took before."""
+    if constraint_batches not in ("topk", "believer"):
+        raise ValueError("constraint_batches must be 'topk' or 'believer', not %r" % (constraint_batches,))
+    if constraint_batches == "believer" and not expensive_constraints:
+        raise ValueError("constraint_batches='believer' needs expensive_constraints=True (it batches the feasibility-weighted criterion)")
     if constraint_gradient and not expensive_constraints:
         raise ValueError("constraint_gradient=True needs expensive_constraints=True (it is the input gradient of the feasibility-weighted criterion)")
     _CONSTRAINTS.clear()
@@ -579,6 +595,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         _CONSTRAINTS["tol"] = float(equality_tol)
         if constraint_gradient:
             _CONSTRAINTS["gradient"] = True
+        if constraint_batches == "believer":
+            _CONSTRAINTS["batches"] = "believer"
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

@@ -657,6 +657,67 @@ def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: O
     return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
 
 
+def constrained_believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = None, Xs: Optional[np.ndarray] = None,
+                               design: Optional[str] = None, seed: Optional[int] = None, pending=None, believe_plugin: bool = True,
+                               lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None, group=None,
+                               rank=None, world=None):
+    """A q-point proposal under modelled constraints by the Kriging believer (`bogp_sweep_believer_constrained`): ONE posterior
+    pass over the m targets, then one streaming pass over the candidates per proposed point.  Step j maximises criterion j -- its
+    criterion on the objective times the constraints' probabilities of feasibility -- on the m posterior means and on the variances
+    conditioned on `pending` (rows submitted but not yet evaluated, (n, d)) and on the winners of the steps before it.  `criteria`:
+    one `bogp.Constrained` (replicated `q` times) or a sequence used in order, sharing model, bounds, minimize and plugin; a
+    feasibility-only step stays feasibility-only.  With `believe_plugin` a believed point whose believed constraint values all
+    lie inside their bounds lowers the plugin of the later steps; an infeasible one leaves it.  Candidates as in `believer_batch`.
+    Returns (xopt: tuple of q lists, fopt: tuple of q floats) in `believer_batch`'s format.
+    TypeError: a criterion that is not `bogp.Constrained`.  Refused (NotImplementedError): a forest model, a lift, fixed
+    variables, cheap constraints h / g, more than one rank."""
+    if is_constrained(criteria) or not isinstance(criteria, (list, tuple)):
+        criteria = [criteria] * int(1 if q is None else q)
+    else:
+        criteria = list(criteria)
+        if q is not None and int(q) != len(criteria):
+            raise ValueError("q = %d but %d criteria were given" % (q, len(criteria)))
+    if len(criteria) == 0:
+        raise ValueError("the believer needs at least one criterion")
+    if not all(is_constrained(c) for c in criteria):
+        raise TypeError("constrained_believer_batch takes bogp.Constrained criteria (the single-objective criteria go to believer_batch, "
+                        "EHVI to ehvi_believer_batch)")  # fmt: skip
+    c0 = criteria[0]
+    model = c0.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no believer batches under modelled constraints")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no believer batches under modelled constraints")
+    if h is not None or g is not None:
+        raise NotImplementedError("cheap constraints h / g have no believer batches under modelled constraints: model them as columns of y")
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    for c in criteria[1:]:
+        if (c.model is not model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin()
+                or not np.array_equal(c.lo, c0.lo) or not np.array_equal(c.hi, c0.hi)):  # fmt: skip
+            raise ValueError("Constrained criteria sharing one sweep must share model, bounds, plugin and minimize")
+    if len(criteria) + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
+        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
+    if design is not None:
+        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
+    out = eng.sweep_believer_constrained([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, c0.lo, c0.hi,
+                                         pending=pend, believe_plugin=believe_plugin)
+    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+
+
 def unwrap_criterion(obj):
     """Find the acquisition object behind what `BaseBO._create_acquisition` hands to `argmax_restart`
     (base.py:482-494): `partial_argument(functools.partial(criterion, return_dx=...), var_name, fixed)` -- a

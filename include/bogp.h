@@ -435,6 +435,41 @@ int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const double* ref_poi
                              double* best_x, double* best_mu, double* pivots, int* n_cells, double* ehvi_out, double* mse_out);
 int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* ehvi_ms, int* n_passes);
 
+/* ---- sweep: Kriging-believer batches under modelled constraints --------------------------------------------
+ * q proposals per call for a run whose simulation returns the objective and its constraints (bogp_sweep_constrained's model:
+ * target 0 the objective, targets 1 .. m - 1 constraints feasible in [lo_k, hi_k], constant basis).  The bracket is shared by
+ * the m targets, so kappa0, b_i, pivot_i and c_i are those of bogp_sweep_believer (pivot floor 1e-12 -> c_i = 0; the candidate
+ * row that is a winner gets variance exactly 0) and step j sees the means unchanged and
+ *   MSE_{k,j}(x) = max(0, MSE_{k,0}(x) - sigma2_k sum_i c_i(x)^2),   value_j = base_j * P   as bogp_sweep_constrained forms them
+ * from these moments (sd = sqrt(MSE) without a floor, P the product of bogp_feasibility over the constraints in index order).
+ * The criteria are exactly acq_id / acq_par (q of them: EI, EpsilonPI, MGFI or BOGP_ACQ_NONE; a BOGP_ACQ_NONE step stays
+ * feasibility-only); the bounds, the hyper-parameters and sigma2_k stay fixed.
+ * The plugin: with believe_plugin = 1, a believed point p whose m means mu(p) (beta + r(p).gamma_k for a pending point, the
+ * sweep's own means for a winner) are feasible by belief -- lo_k <= mu_k(p) <= hi_k for every constraint -- lowers it,
+ * plug = min(plug, +-mu_0(p)) (the plugin arrives in the criterion's own sign: negated when maximising); an infeasible one and
+ * believe_plugin = 0 leave it.  Step j takes the argmax by bogp_sweep's rule over the rows that are not winners yet; the q
+ * winners are q distinct rows.  Without pending points step 0 IS bogp_sweep_constrained(q = 1, criterion 0), bit for bit.
+ *   n_con, lo, hi   as bogp_sweep_constrained;  pending: n_pending x d HOST rows, NULL for n_pending = 0
+ *   1 <= q <= M, q + n_pending <= BOGP_MAX_BELIEVED
+ *   best_val, best_idx (q): each step's winner.  Optional HOST buffers (NULL to skip): best_x (q x d), best_mu (q x m: the
+ *   believed means), pivots (n_pending + q), plugin_out (q: the plugin step j used), acq_out (q x M), pof_out (q x M),
+ *   mse_out (q x M x m).
+ * Per believed point: the solve of bogp_sweep_believer, one streaming pass (producer + k_believer for c(x), per chunk) and one
+ * launch of k_believer_constrained over all rows (8 (3 + 4 m) bytes a row); the N^2 contraction runs once, in pass 0.  No bit
+ * depends on BOGP_CHUNK_MB.
+ * BOGP_ERR_INVALID: no committed model, no candidates, everything bogp_sweep_constrained refuses about the targets, the criteria
+ * and the bounds, q < 1, q > M, the limit exceeded, a null required array, a non-finite pending entry.  BOGP_ERR_UNSUPPORTED: a
+ * forest handle, a lift, a polynomial trend basis, a communicator of more than one rank.  Every failure returns before the first
+ * launch; the handle's model, candidates and later sweeps are unaffected.
+ * `believer_constrained_last`: of the last call, the time of the producer launches, of the solves, of k_believer and of
+ * k_believer_constrained in ms, and the candidate passes behind pass 0; any pointer may be NULL.                             */
+int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
+                                    int believe_plugin, int n_con, const double* lo, const double* hi, const double* pending,
+                                    int n_pending, double* best_val, int64_t* best_idx, double* best_x, double* best_mu,
+                                    double* pivots, double* plugin_out, double* acq_out, double* pof_out, double* mse_out);
+int bogp_believer_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
+                                   int* n_passes);
+
 /* ---- sweep in a reduced space: box-penalised criteria under a linear lift ---------------------------
  * Replaces PCABO's inner maximisation (extension.py:113-133): the criterion is maximised over a box of the REDUCED
  * space (r = the committed model's d, _compute_bounds :113-119) through penalized_acquisition (:62-86), which maps a
