@@ -78,6 +78,7 @@ SIGNATURES = {
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_feasibility": (C.c_double, [C.c_double] * 5),
     "bogp_sweep_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
+    "bogp_sweep_ehvi_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _lp, _dp, _dp, _dp]),
@@ -704,6 +705,41 @@ class Engine:
         self._check(self._lib.bogp_sweep_constrained(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
                                                      len(lo), _ptr(lo), _ptr(hi), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(vals),
                                                      _ptr(pof), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_pof:
+            out += (pof,)
+        if return_moments:
+            out += (mu, mse)
+        return out
+
+    def sweep_ehvi_constrained(self, lower, upper, lo, hi, k: int = 1, return_values=False, return_pof=False, return_moments=False):
+        """Feasibility-weighted EHVI of the committed multi-target model over the current candidates (bogp_sweep_ehvi_constrained):
+        targets 0 .. m - 1 are the objectives of the cells (lower, upper) (C x m each, as `sweep_ehvi` takes them; two empty (0, m) arrays
+        give the probability of feasibility alone), target m + j the constraint feasible in [lo[j], hi[j]] (either side
+        may be infinite); value = EHVI x the product of the constraints' probabilities of feasibility P, and +0.0 where P == 0.
+        Returns (best_val (k,), best_idx (k,)[, values (M,)][, pof (M,)][, mu (M, m + c), mse (M, m + c)]); rank 0 is the argmax,
+        slots beyond M are (-inf, -1)."""
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        lower = _f64(lower)
+        upper = _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape (C = 0: two empty (0, m) arrays)")
+        C_, m = lower.shape
+        mt = m + len(lo)
+        best = np.empty(int(k))
+        idx = np.empty(int(k), dtype=np.int64)
+        vals = np.empty(self.M) if return_values else None
+        pof = np.empty(self.M) if return_pof else None
+        mu = np.empty((self.M, mt)) if return_moments else None
+        mse = np.empty((self.M, mt)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_ehvi_constrained(self._h, int(m), int(C_), _ptr(lower) if C_ else None, _ptr(upper) if C_ else None,
+                                                          len(lo), _ptr(lo), _ptr(hi), int(k), _ptr(best), idx.ctypes.data_as(_lp),
+                                                          _ptr(vals), _ptr(pof), _ptr(mu), _ptr(mse)))  # fmt: skip
         out = (best, idx)
         if return_values:
             out += (vals,)

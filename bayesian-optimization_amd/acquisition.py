@@ -526,3 +526,105 @@ class Constrained:
                 return (vals.reshape(1), dx.reshape(1, -1)) if len(rows) == 1 else (vals.reshape(-1, 1), dx)
         self.model.engine.upload_candidates(self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float))))
         return self.sweep(return_values=True)[2]
+
+
+class ConstrainedEHVI:
+    """Expected hypervolume improvement weighted by the probability that modelled constraints hold (`bogp_sweep_ehvi_constrained`): what
+    the reference's multi-objective `tell` names and leaves open (`BaseMOBO.tell`, mobo.py:117-118).  `model` is a device
+    GaussianProcess fitted on y (N, m + c), m = len(ref_point) >= 2, c >= 1: columns 0 .. m - 1 are the objectives, maximised as
+    given (as `EHVI` takes them), column m + j the constraint feasible when lo[j] <= c_j(x) <= hi[j] (default (-inf, 0] each).  Per row
+
+        value = EHVI(x on the objective columns) * prod_j P(lo_j <= c_j(x) <= hi_j),   and exactly +0.0 where that probability is 0
+
+    over the cells of the FEASIBLE front: `pareto.hypercell_bounds(Y[feasible], ref_point)`, `Y` (N, m) defaulting to
+    `model.y[:, :m]`, the feasible rows those whose constraint columns of `model.y` lie inside their bounds (`n_feasible` of them).  A
+    feasible set with no row above the reference point has the one cell [ref, +inf); with no feasible row at all the criterion
+    is the probability of feasibility alone (`feasibility_only`; Gelbart, Snoek, Adams 2014).  `cells=(lower, upper)` replaces the
+    decomposition.
+
+    `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the engine's
+    current candidates as `EHVI.sweep` does.  There is no input gradient (`return_dx=True` raises) and no batch strategy; the sweep
+    helpers serve it where they serve `EHVI`: alone in its sweep, on one rank."""
+
+    is_ehvi = True  # (the sweep helpers serve it through `.sweep()`, as they serve EHVI)
+    is_constrained_ehvi = True  # ... and everything that does more than call `.sweep()` asks for this flag first
+    is_constrained = False
+    input_gradient = False
+    minimize = False  # (the sweep helpers read it off every criterion)
+
+    def __init__(self, model=None, ref_point=None, lo=None, hi=None, Y=None, cells=None):
+        if model is None:
+            raise ValueError("model cannot be None")
+        if _forest.is_forest_model(model):
+            raise NotImplementedError("constrained EHVI (bogp.ConstrainedEHVI) takes a multi-target Gaussian process: a forest model is not served")
+        if ref_point is None:
+            raise ValueError("ConstrainedEHVI needs a ref_point")
+        if Y is not None and cells is not None:
+            raise ValueError("ConstrainedEHVI takes at most one of Y= and cells=")
+        self.model = model
+        self.ref_point = np.asarray(ref_point, dtype=float).ravel()
+        m = len(self.ref_point)
+        y = np.asarray(getattr(model, "y", np.zeros((0, 0))), dtype=float)
+        if m < 2 or y.ndim != 2 or y.shape[1] < m + 1:
+            raise ValueError("constrained EHVI needs a ref_point of m >= 2 objectives and a model fitted on y (N, m + c) with c >= 1 constraint "
+                             "columns: got ref_point %s and model.y %s" % (self.ref_point.shape, y.shape))  # fmt: skip
+        if y.shape[1] > _lib.MAX_TARGETS:
+            raise ValueError("model.y %s: at most %d targets (objectives and constraints together)" % (y.shape, _lib.MAX_TARGETS))
+        n_con = y.shape[1] - m
+        lo = np.full(n_con, -np.inf) if lo is None else np.asarray(lo, dtype=float).ravel()
+        hi = np.zeros(n_con) if hi is None else np.asarray(hi, dtype=float).ravel()
+        if len(lo) != n_con or len(hi) != n_con:
+            raise ValueError("lo and hi must hold one bound for each of the %d constraint columns of model.y %s (ref_point %s)"
+                             % (n_con, y.shape, self.ref_point.shape))  # fmt: skip
+        if np.any(np.isnan(lo)) or np.any(np.isnan(hi)) or np.any(hi < lo):
+            raise ValueError("constraint bounds must not be NaN, and hi >= lo")
+        self.lo, self.hi = np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+        feasible = np.all((y[:, m:] >= self.lo) & (y[:, m:] <= self.hi), axis=1)
+        self.n_feasible = int(feasible.sum())
+        self.pareto_Y = None
+        if cells is not None:
+            lower, upper = (np.atleast_2d(np.asarray(c, dtype=float)) for c in cells)
+        else:
+            Y = y[:, :m] if Y is None else np.atleast_2d(np.asarray(Y, dtype=float))
+            if Y.shape != (len(y), m):
+                raise ValueError("Y must hold the %d objectives of the model's %d rows, got %s" % (m, len(y), Y.shape))
+            if self.n_feasible:
+                from .pareto import hypercell_bounds, pareto_front
+
+                self.pareto_Y = pareto_front(Y[feasible], self.ref_point)
+                lower, upper = (np.atleast_2d(b) for b in hypercell_bounds(Y[feasible], self.ref_point))
+            else:  # nothing to improve on yet: the probability of feasibility alone
+                lower = upper = np.zeros((0, m))
+        if lower.shape != upper.shape or lower.shape[1] != m:
+            raise ValueError("cell bounds must be two C x %d arrays, got %s and %s" % (m, lower.shape, upper.shape))
+        if len(lower) > _lib.MAX_EHVI_CELLS:
+            raise ValueError("%d cells: at most %d per sweep" % (len(lower), _lib.MAX_EHVI_CELLS))
+        self.cell_lower_bounds = np.ascontiguousarray(lower)
+        self.cell_upper_bounds = np.ascontiguousarray(upper)
+
+    @property
+    def n_obj(self) -> int:
+        return len(self.ref_point)
+
+    @property
+    def feasibility_only(self) -> bool:
+        return len(self.cell_lower_bounds) == 0
+
+    def effective_plugin(self) -> float:
+        return 0.0
+
+    def sweep(self, k: int = 1, return_values: bool = False):
+        """The sweep over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
+        if getattr(self.model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        return self.model.engine.sweep_ehvi_constrained(self.cell_lower_bounds, self.cell_upper_bounds, self.lo, self.hi, k=int(k),
+                                                        return_values=return_values)  # fmt: skip
+
+    def __call__(self, X, return_dx: bool = False):
+        if return_dx:
+            raise NotImplementedError("constrained EHVI (bogp.ConstrainedEHVI) has no input gradient: use 'sweep' or "
+                                      "'sweep-device[-lhs|-sobol]'")  # fmt: skip
+        if getattr(self.model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        self.model.engine.upload_candidates(self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float))))
+        return self.sweep(return_values=True)[2]

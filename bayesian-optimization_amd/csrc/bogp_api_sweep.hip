@@ -753,6 +753,13 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
         cn.acq_out = h->dacq_out; cn.M = M; cn.mu_out = rq.want_out ? h->dmu_out : nullptr; cn.mse_out = rq.want_out ? h->dmse_out : nullptr;
         cn.blk_val = h->dblk_val; cn.blk_idx = h->dblk_idx; cn.blk_offset = cx.blk_offset; cn.nblk_total = cx.nblk_total;
         HIPCHK(h, launch_constrained(cn, st));
+      } else if (rq.ec) {  // ... or EHVI of its objectives weighted by its constraints' feasibility (kernels_ehvi_constrained.hip)
+        ConstrainedEhviArgs ec = *rq.ec;
+        ec.rT = h->drT[b]; ec.ss_part = h->dss_part; ec.w_part = h->dw_part[b]; ec.S = S; ec.nJ = cx.nJ_main; ec.Mc = Mc;
+        ec.mcount = mcount; ec.m0 = m0; ec.beta = h->beta; ec.G = h->G; ec.estimate_trend = h->estimate_trend;
+        ec.val_out = h->dacq_out; ec.mu_out = rq.want_out ? h->dmu_out : nullptr; ec.mse_out = rq.want_out ? h->dmse_out : nullptr;
+        ec.blk_val = h->dblk_val; ec.blk_idx = h->dblk_idx; ec.blk_offset = cx.blk_offset;
+        HIPCHK(h, launch_ehvi_constrained(ec, st));
       } else {
         HIPCHK(h, launch_acquisition(aa, st));
       }
@@ -899,9 +906,10 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0;
   h->b32_rows = h->b32_kept = h->b32_last_rows = 0; h->b32_fallbacks = 0;
   int e;
-  // the two single-target shortcuts (bogp_sweep_ehvi -- eh non-null -- and bogp_sweep_constrained -- cn non-null -- take neither: they
-  // always run the chunked path below); nothing to overlap a lazy upload with: the whole upload first (one launch reads every candidate)
-  const bool multi = rq.eh || rq.cn;
+  // the two single-target shortcuts (the multi-target requests -- bogp_sweep_ehvi: eh non-null, bogp_sweep_constrained: cn non-null,
+  // bogp_sweep_ehvi_constrained: ec non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
+  // with: the whole upload first (one launch reads every candidate)
+  const bool multi = rq.eh || rq.cn || rq.ec;
   const bool small_batch = !multi && M <= 32 && h->p == 1;
   if (small_batch || (!multi && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
     if ((e = lazy_finish(h))) return e;

@@ -22,8 +22,9 @@ std::vector<bogp_handle*> nll_team(bogp_handle* h, int P);  // bogp_batch.hip: t
 int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, int q, const int* acq_id, const double* acq_par,
                     double plugin, int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq);
 // bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
-// m-target EHVI of bogp_api_ehvi.hip, or -- cn non-null -- the feasibility-weighted criteria of bogp_api_constrained.hip, both on the
-// chunked path), and the reset of the winners a sweep left on the device
+// m-target EHVI of bogp_api_ehvi.hip, or -- cn non-null -- the feasibility-weighted criteria of bogp_api_constrained.hip, or -- ec
+// non-null -- the feasibility-weighted EHVI of bogp_api_ehvi_constrained.hip, all on the chunked path), and the reset of the winners a
+// sweep left on the device
 struct SweepRequest {
   bool want_out = false, want_acq_out = false;  // mu / MSE of every candidate into dmu_out / dmse_out (EHVI: M x m moments); the q x M values into dacq_out
   bool need_var = true, sync = true;            // false: the contraction is skipped (predict without eval_MSE); false: queued, not waited for
@@ -33,7 +34,8 @@ struct SweepRequest {
   double plugin = 0.0;
   const EhviArgs* eh = nullptr;
   const ConstrainedArgs* cn = nullptr;  // (q, acq_id, acq_par, plugin, minimize above are the criteria it weights)
-  int targets() const { return eh ? eh->m : cn ? cn->m : 1; }  // moments per candidate in dmu_out / dmse_out
+  const ConstrainedEhviArgs* ec = nullptr;  // bogp_sweep_ehvi_constrained: EHVI of the objectives times the constraints' feasibility
+  int targets() const { return eh ? eh->m : cn ? cn->m : ec ? ec->m : 1; }  // moments per candidate in dmu_out / dmse_out
 };
 int run_sweep(bogp_handle* h, const SweepRequest& rq);
 void invalidate_sweep_results(bogp_handle* h);

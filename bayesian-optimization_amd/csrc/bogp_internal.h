@@ -262,6 +262,39 @@ struct ConstrainedArgs {
 };
 hipError_t launch_constrained(const ConstrainedArgs& a, hipStream_t st);
 
+// feasibility-weighted EHVI of an m-target model over one chunk (kernels_ehvi_constrained.hip): targets 0 .. m_obj - 1 are the objectives
+// of EhviArgs' cells, targets m_obj .. m - 1 are constraints feasible in [lo_j, hi_j]; replaces AcqArgs / k_acquisition in the chunk
+// loop of bogp_sweep_ehvi_constrained
+struct ConstrainedEhviArgs {
+  // (the fields stand in the order the kernel reads them -- what the loop over the training points reads first, then what the moments,
+  // the feasibility, the cells and the argmax read after it -- so that no group of scalars loaded together is live on both sides of that
+  // loop, which holds 16 m scalar registers of gamma: with EhviArgs' order the instances with m_obj >= 4 and one constraint kept a
+  // 36-byte stack frame; check -Rpass-analysis=kernel-resource-usage after moving one)
+  const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
+  const double* gamma;    // [m][ld_gamma] the targets' gamma columns
+  int ld_gamma, N;        // Np; training points summed over
+  int64_t Mc, mcount, m0;
+  const double* ss_part;  // [nJ][Mc]
+  const double* w_part;   // [S][Mc] (constant trend with estimate_trend only)
+  int S, nJ;
+  double beta, G;
+  int estimate_trend;
+  int m, m_obj;           // targets, 3 .. BOGP_MAX_TARGETS; objectives among them, 2 .. m - 1
+  double sigma2[8];       // per target
+  double* mu_out;         // [M][m] or null
+  double* mse_out;        // [M][m] or null
+  double lo[8], hi[8];    // per constraint: entry j belongs to target m_obj + j
+  double* pof_out;        // [M] or null
+  const double* lower;    // [C][m_obj] cell bounds (device); not read for C == 0
+  const double* upper;    // [C][m_obj] (+inf allowed)
+  int C;                  // 0: the probability of feasibility alone
+  double* val_out;        // [M] (global index m0 + i)
+  double* blk_val;        // per-block partial argmax
+  int64_t* blk_idx;
+  int64_t blk_offset;
+};
+hipError_t launch_ehvi_constrained(const ConstrainedEhviArgs& a, hipStream_t st);
+
 // one Kriging-believer pass over a chunk (kernels_believer.hip): the rank-one downdate of the running variance by the believed point p,
 // c(x) = (k(x, p) - r(x) . a + u(x) u(p) - sum_k c_k(x) c_k(p)) / sqrt(pivot), s(x) -= sigma2 c(x)^2, and -- for the pass in front of a
 // step -- that step's criterion on (mu, max(0, s)) with the per-block argmax records k_argmax_final reads (one record per 64 rows)

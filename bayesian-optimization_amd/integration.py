@@ -13,7 +13,10 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
   BaseBO.tell, BaseBO.update_model              -> constrained_tell, constrained_update_model (the originals unless
                                                    install(expensive_constraints=True) AND the tell carries h_vals / g_vals)
   MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
-                                                   under the sweep family; the reference's EHVI otherwise)
+                                                   under the sweep family; the reference's EHVI otherwise; with constraint
+                                                   values stored under install(constrained_mobo=True): bogp.ConstrainedEHVI)
+  BaseMOBO.tell, BaseMOBO.update_model          -> refusing_mobo_tell, constrained_mobo_update_model (the originals unless
+                                                   install(expensive_constraints=True) AND the tell carries h_vals / g_vals)
   bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess, bayes_optim.extension.GaussianProcess
                                                 -> a dispatching class that builds
                                                    `bogp.GaussianProcess` (so `bayes_optim.fmin` -- which resolves the
@@ -146,6 +149,20 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
     `BO._create_acquisition` binds it (base.py:463, 489-494: true for "BFGS" only), so that the reference's `argmax_restart`
     accepts the wrapper.  Every other configuration -- "MIES", the reference's default on mixed spaces, CMA, BFGS without that
     switch -- runs the original unchanged."""
+    if _CONSTRAINTS.get("mobo") and getattr(self, "_bogp_constraints", None) is not None:
+        # install(expensive_constraints=True, constrained_mobo=True) and a tell() that carried h_vals / g_vals: EHVI of the feasible front
+        # times the probability of feasibility, or an error -- never the plain criterion, which would drop the constraints
+        optimizer, _ = _effective(getattr(self, "_optimizer", None), None)
+        if not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(getattr(self, "search_space", None)):
+            raise NotImplementedError("expensive constraints of a multi-objective run (bogp.ConstrainedEHVI) take a device GaussianProcess on "
+                                      "a continuous search space; the constraint values are not dropped silently")  # fmt: skip
+        if optimizer not in _SWEEPS:
+            raise NotImplementedError("optimizer=%r under expensive constraints of a multi-objective run: constrained EHVI "
+                                      "(bogp.ConstrainedEHVI) is served by the sweep family only %s; the constraint values are not dropped "
+                                      "silently" % (optimizer, _SWEEPS))  # fmt: skip
+        lo, hi = _constraint_bounds(self)
+        criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
+        return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
     if getattr(self, "_optimizer", None) in ("sweep", "sweep-device") and _forest.is_forest_model(getattr(self, "model", None)):
         # a RandomForest fitted on y (N, n_obj) (this package's or the reference's), on any space a forest sweep serves: the
         # forest walk and EHVI are one device pass; what a forest sweep does not take is refused by optim.argmax_restart by name
@@ -171,6 +188,9 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
     GP, an inner optimiser of the sweep family, a continuous space, nothing fixed and no constraints: `optim.ehvi_believer_batch` on
     the criterion `mobo_create_acquisition` builds.  Everything else -- the default `install()` above all -- calls the inherited
     method, which raises as it does without this package."""
+    if getattr(self, "_bogp_constraints", None) is not None:
+        raise NotImplementedError("MOBO(n_point=q) under expensive constraints: constrained EHVI (bogp.ConstrainedEHVI) has no batch "
+                                  "strategy; ask for one point at a time")  # fmt: skip
     inherited = super(_ORIGINAL["mobo_cls"], self)._batch_arg_max_acquisition
     optimizer, budget = _effective(getattr(self, "_optimizer", None), None)
     kw = getattr(getattr(self, "_argmax_restart", None), "keywords", None) or {}
@@ -229,6 +249,14 @@ def constrained_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, w
                                   "driver is not served" % type(getattr(self, "model", None)).__name__)  # fmt: skip
     if getattr(self, "n_obj", 1) != 1:
         raise NotImplementedError("expensive constraints (h_vals / g_vals) are served for single-objective drivers (BO, ParallelBO), not for %d objectives" % self.n_obj)
+    return _tell_storing_constraints(self, _ORIGINAL["tell"], X, func_vals, h_vals, g_vals, index, warm_start)
+
+
+def _tell_storing_constraints(self, original_tell, X, func_vals, h_vals, g_vals, index, warm_start):
+    """What `constrained_tell` and the multi-objective tell share: the rules and error cases of storing the constraint values of a
+    tell() row for row with `self.data`, around `original_tell` (a row is kept where `post_eval_check` keeps it: all of its
+    fitness values finite)."""
+    given = h_vals is not None or g_vals is not None
     stored = getattr(self, "_bogp_constraints", None)
     if not given:
         raise ValueError("this tell() carries no h_vals / g_vals, but earlier ones did: every point needs its constraint values")
@@ -240,8 +268,8 @@ def constrained_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, w
     counts = (g.shape[1], h.shape[1])
     if stored is not None and counts != self._bogp_constraint_counts:
         raise ValueError("this tell() carries %d g and %d h values a point, earlier ones %d and %d" % (counts + tuple(self._bogp_constraint_counts)))
-    fitness = np.asarray(func_vals, dtype=float).ravel()
-    keep = ~(np.isnan(fitness) | np.isinf(fitness))  # the rows post_eval_check keeps (base.py:413-421)
+    fitness = np.asarray(func_vals, dtype=float).reshape(n, -1)
+    keep = ~np.any(np.isnan(fitness) | np.isinf(fitness), axis=1)  # the rows post_eval_check keeps (base.py:413-421)
     rows = np.hstack([g, h])[keep]
     if not np.all(np.isfinite(rows)):
         raise ValueError("h_vals / g_vals hold a non-finite value: a modelled constraint needs a number for every evaluated point")
@@ -249,7 +277,7 @@ def constrained_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, w
     self._bogp_constraints = rows if stored is None else np.vstack([stored, rows])
     self._bogp_constraint_counts = counts
     try:
-        return _ORIGINAL["tell"](self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
+        return original_tell(self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
     except BaseException:
         if not hasattr(self, "data") or len(self.data) != len(self._bogp_constraints):  # the points did not arrive: nor do their values
             self._bogp_constraints, self._bogp_constraint_counts = before
@@ -257,8 +285,17 @@ def constrained_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, w
 
 
 def refusing_mobo_tell(self, X, func_vals, h_vals=None, g_vals=None, index=None, warm_start=False):
-    """`BaseMOBO.tell` under `install(expensive_constraints=True)`: constraint values are refused by name, everything else is the original."""
-    if _CONSTRAINTS and (h_vals is not None or g_vals is not None):
+    """`BaseMOBO.tell` under `install(expensive_constraints=True)`: constraint values are refused by name, everything else is the
+    original.  With `constrained_mobo=True` as well they are kept instead (the TODO of mobo.py:117-118): row for row with `self.data`
+    in `self._bogp_constraints`, by `constrained_tell`'s rules and with its error cases, for a device GP; `constrained_mobo_update_model`
+    then fits objectives and constraints together."""
+    given = h_vals is not None or g_vals is not None
+    if _CONSTRAINTS.get("mobo") and (given or getattr(self, "_bogp_constraints", None) is not None):
+        if not is_device_model(getattr(self, "model", None)):
+            raise NotImplementedError("expensive constraints (h_vals / g_vals) are modelled by a device GaussianProcess: the %s model of this "
+                                      "driver is not served" % type(getattr(self, "model", None)).__name__)  # fmt: skip
+        return _tell_storing_constraints(self, _ORIGINAL["mobo_tell"], X, func_vals, h_vals, g_vals, index, warm_start)
+    if _CONSTRAINTS and given:
         raise NotImplementedError("expensive constraints (h_vals / g_vals) are served for single-objective drivers (BO, ParallelBO), "
                                   "not for the multi-objective MOBO")  # fmt: skip
     return _ORIGINAL["mobo_tell"](self, X, func_vals, h_vals=h_vals, g_vals=g_vals, index=index, warm_start=warm_start)
@@ -293,6 +330,36 @@ def constrained_update_model(self):
     self.logger.info(f"model r2: {r2}, MAPE: {MAPE}")
 
 
+def constrained_mobo_update_model(self):
+    """`BaseMOBO.update_model` (mobo.py:155-165) with stored constraint values: the model is fitted on
+    column_stack([self.y, C / scale]) -- the objectives as the reference transforms them (min-max scaled, maximised), each constraint
+    column divided by its standard deviation (1 where that is 0) and never shifted, as `constrained_update_model` scales them -- and
+    r2 / MSE are logged for the objective columns only.  Without stored values: the original."""
+    C = getattr(self, "_bogp_constraints", None)
+    if not _CONSTRAINTS.get("mobo") or C is None:
+        return _ORIGINAL["mobo_update_model"](self)
+    rmobo = _ORIGINAL["mobo_mod"]
+    X, y = self.data, np.asarray(self.y, dtype=float)
+    if len(C) != len(y):
+        raise ValueError("%d points hold constraint values, %d are stored in data" % (len(C), len(y)))
+    std = np.std(C, axis=0)
+    self._bogp_constraint_scale = np.where(np.isclose(std, 0), 1.0, std)
+    self.model.fit(X, np.column_stack([y, C / self._bogp_constraint_scale]))
+    y_ = np.asarray(self.model.predict(X)).reshape(len(y), -1)[:, : y.shape[1]]
+    r2 = rmobo.r2_score(y, y_, multioutput="raw_values")
+    MSE = rmobo.mean_squared_error(y, y_, multioutput="raw_values")
+    for i in range(self.n_obj):
+        self.logger.info(f"model of f{i + 1} r2: {r2[i]}, MSE: {MSE[i]}")
+
+
+def _constraint_bounds(self):
+    """(lo, hi) of the stored constraint columns as the model sees them: (-inf, 0] for the g columns, [-tol, tol] / std for the h columns
+    (tol = `install(equality_tol=)`)."""
+    n_g, _ = self._bogp_constraint_counts
+    tol = _CONSTRAINTS["tol"] / np.asarray(self._bogp_constraint_scale, dtype=float)[n_g:]
+    return np.r_[np.full(n_g, -np.inf), -tol], np.r_[np.zeros(n_g), tol]
+
+
 def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fixed=None):
     """`BaseBO._create_acquisition` in front of `forest_create_acquisition`: with stored constraint values the criterion is
     `bogp.Constrained` -- (-inf, 0] for the g columns, [-tol, tol] / std for the h columns (tol = `install(equality_tol=)`), the plugin
@@ -314,9 +381,7 @@ def constrained_create_acquisition(self, fun=None, par=None, return_dx=False, fi
     par = dict(par if par is not None else self._acquisition_par)
     for k in ("plugin", "model", "minimize"):
         par.pop(k, None)
-    n_g, n_h = self._bogp_constraint_counts
-    tol = _CONSTRAINTS["tol"] / np.asarray(self._bogp_constraint_scale, dtype=float)[n_g:]
-    lo, hi = np.r_[np.full(n_g, -np.inf), -tol], np.r_[np.zeros(n_g), tol]
+    lo, hi = _constraint_bounds(self)
     criterion = acquisition.Constrained(model=self.model, fun=name, minimize=self.minimize, lo=lo, hi=hi, input_gradient=gradient, **par)
     return _ORIGINAL["base_partial_argument"](func=functools.partial(criterion, return_dx=return_dx), var_name=self.search_space.var_name,
                                               fixed=fixed, reduce_output=return_dx)  # fmt: skip
@@ -336,6 +401,25 @@ def feasible_xopt(bo):
     f = np.asarray(bo.data.fitness, dtype=float)
     rows = np.flatnonzero(ok)
     return bo.data[int(rows[np.argmin(f[rows]) if bo.minimize else np.argmax(f[rows])])]
+
+
+def feasible_front(bo):
+    """The non-dominated rows of `bo.data` among those whose stored constraint values are all feasible (g <= 0, |h| <=
+    `install(equality_tol=)`) -- the multi-objective counterpart of `feasible_xopt` --, an empty selection when no row is feasible, or
+    None when nothing is stored.  The reference's `xopt` ignores constraint values and is untouched."""
+    C = getattr(bo, "_bogp_constraints", None)
+    if C is None or not hasattr(bo, "data") or len(C) != len(bo.data):
+        return None
+    from .pareto import is_non_dominated
+
+    n_g, _ = bo._bogp_constraint_counts
+    tol = _CONSTRAINTS.get("tol", 0.1)
+    rows = np.flatnonzero(np.all(C[:, :n_g] <= 0, axis=1) & np.all(np.abs(C[:, n_g:]) <= tol, axis=1))
+    if len(rows):
+        rows = rows[is_non_dominated(np.asarray(bo.y, dtype=float)[rows])]
+    mask = np.zeros(len(C), dtype=bool)
+    mask[rows] = True
+    return bo.data[mask, :]  # (selected as the reference's xopt selects, mobo.py:56-57)
 
 
 def routed_argmax_restart(obj_func, search_space, h=None, g=None, eval_budget=100, n_restart=10, wait_iter=3,
@@ -535,7 +619,7 @@ def _dispatching_surrogate(host_cls):
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
-            equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk"):
+            equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -581,7 +665,17 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `batch_strategy` says.  "believer": `optim.constrained_believer_batch` -- criterion j sees the m variances conditioned on the
     winners before it, and a believed point that is feasible by belief lowers the plugin -- when every criterion of the step is a
     `bogp.Constrained`, the inner optimiser is of the sweep family, nothing is fixed and no cheap h / g is given; every other step
-    takes the route it took before."""
+    takes the route it took before.
+
+    `constrained_mobo=True` (with `expensive_constraints=True`; alone it raises ValueError; an extension: `BaseMOBO.tell` leaves the
+    values as a TODO, mobo.py:117-118): the reference's `MOBO` with a device GP keeps the `h_vals` / `g_vals` of its tell()
+    (`refusing_mobo_tell`, by `constrained_tell`'s rules), fits objectives and constraints as one multi-target model
+    (`constrained_mobo_update_model`) and maximises `bogp.ConstrainedEHVI` -- EHVI over the cells of the feasible front times the
+    probability that g <= 0 and |h| <= `equality_tol` -- under the sweep family on a continuous space; any other inner optimiser and
+    `MOBO(n_point=q)` raise instead of dropping the constraints.  `bogp.feasible_front(bo)` is the feasible non-dominated set.  Without
+    it a MOBO tell() with constraint values is refused by name as before."""
+    if constrained_mobo and not expensive_constraints:
+        raise ValueError("constrained_mobo=True needs expensive_constraints=True (it keeps the h_vals / g_vals of a multi-objective tell())")
     if constraint_batches not in ("topk", "believer"):
         raise ValueError("constraint_batches must be 'topk' or 'believer', not %r" % (constraint_batches,))
     if constraint_batches == "believer" and not expensive_constraints:
@@ -597,6 +691,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["gradient"] = True
         if constraint_batches == "believer":
             _CONSTRAINTS["batches"] = "believer"
+        if constrained_mobo:
+            _CONSTRAINTS["mobo"] = True
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()
@@ -645,6 +741,9 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     if rmobo is not None and "tell" in getattr(rmobo, "BaseMOBO", type("", (), {})).__dict__:
         _ORIGINAL.update(mobo_tell_cls=rmobo.BaseMOBO, mobo_tell=rmobo.BaseMOBO.__dict__["tell"])
         rmobo.BaseMOBO.tell = refusing_mobo_tell
+        if "update_model" in rmobo.BaseMOBO.__dict__:
+            _ORIGINAL.update(mobo_mod=rmobo, mobo_update_model=rmobo.BaseMOBO.__dict__["update_model"])
+            rmobo.BaseMOBO.update_model = constrained_mobo_update_model
     if rmobo is not None and hasattr(rmobo, "MOBO"):
         _ORIGINAL.update(mobo_cls=rmobo.MOBO, mobo=rmobo.MOBO.__dict__["_create_acquisition"], partial_argument=rmobo.partial_argument)
         rmobo.MOBO._create_acquisition = mobo_create_acquisition
@@ -674,6 +773,8 @@ def uninstall():
     _ORIGINAL["base_cls"].tell, _ORIGINAL["base_cls"].update_model = _ORIGINAL["tell"], _ORIGINAL["update_model"]
     if _ORIGINAL.get("mobo_tell_cls") is not None:
         _ORIGINAL["mobo_tell_cls"].tell = _ORIGINAL["mobo_tell"]
+        if _ORIGINAL.get("mobo_update_model") is not None:
+            _ORIGINAL["mobo_tell_cls"].update_model = _ORIGINAL["mobo_update_model"]
     for m in _ORIGINAL["acq_holders"]:
         m.AcquisitionFunction = _ORIGINAL["acq"]
     ropt.ParallelBO._batch_arg_max_acquisition = _ORIGINAL["batch"]

@@ -161,13 +161,26 @@ def is_ehvi(criterion) -> bool:
     return bool(getattr(criterion, "is_ehvi", False))
 
 
+def is_constrained_ehvi(criterion) -> bool:
+    """True for `acquisition.ConstrainedEHVI` (EHVI weighted by the probability that modelled constraints hold: its sweep is
+    `bogp_sweep_ehvi_constrained`).  It is `is_ehvi` as well -- the sweep helpers call its `.sweep()` as they call EHVI's -- and not
+    `is_constrained`; whatever does more with an EHVI than call `.sweep()` (the polish, the believer) asks for this flag first."""
+    return bool(getattr(criterion, "is_constrained_ehvi", False))
+
+
+_CEHVI = "constrained EHVI (bogp.ConstrainedEHVI)"
+
+
 def _ehvi_of(criteria: Sequence, eng, group=None):
-    """The EHVI criterion a sweep serves, or None when every criterion is single-objective.  EHVI sweeps alone, on one rank."""
+    """The EHVI criterion a sweep serves (`EHVI` or `ConstrainedEHVI`), or None when every criterion is single-objective.  It sweeps
+    alone, on one rank."""
     flags = [is_ehvi(c) for c in criteria]
     if not any(flags):
         return None
     if len(criteria) != 1:
         raise ValueError("an EHVI criterion sweeps alone: it cannot share a sweep with other criteria")
+    if is_constrained_ehvi(criteria[0]) and engine_rank_world(eng, group)[1] > 1:
+        raise NotImplementedError("the sweep of %s runs on one rank (no multi-rank exchange of its winners)" % _CEHVI)
     if engine_rank_world(eng, group)[1] > 1:
         raise NotImplementedError("the EHVI sweep runs on one rank (no multi-rank exchange of its winners)")
     return criteria[0]
@@ -208,6 +221,8 @@ def _lifted_topk(criteria: Sequence, eng, lift: Lift, k: int, group=None):
     """The k best rows per criterion of the engine's current candidates under `lift` (`bogp_lift_sweep_topk`): rows whose
     lifted point leaves the original box compete with their penalty (extension.py:62-86).  The lift is taken off the engine
     again before this returns, whatever happens: a later plain sweep never sees it."""
+    if any(is_constrained_ehvi(c) for c in criteria):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not %s" % _CEHVI)
     if any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
     if any(is_constrained(c) for c in criteria):
@@ -501,6 +516,8 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     model = c0.model
     if _forest.is_forest_model(model):
         raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if any(is_constrained_ehvi(c) for c in criteria):
+        raise NotImplementedError("%s has no believer batches" % _CEHVI)
     if any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("EHVI has no believer batches: the front and its cells change with each believed point "
                                   "(`ehvi_believer_batch` rebuilds them between the steps)")
@@ -556,6 +573,8 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
 
     if _forest.is_forest_model(model):
         raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
+    if criteria is not None and any(is_constrained_ehvi(c) for c in criteria):
+        raise NotImplementedError("%s has no Thompson batches" % _CEHVI)
     if criteria is not None and any(is_ehvi(c) for c in criteria):
         raise NotImplementedError("EHVI / several targets have no Thompson batches")
     if criteria is not None and any(is_constrained(c) for c in criteria):
@@ -619,6 +638,9 @@ def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: O
     `cells=` has no front to extend and is refused (ValueError).  Candidates as in `believer_batch`.  Returns (xopt: tuple of q
     lists, fopt: tuple of q floats) in `believer_batch`'s format.
     Refused (NotImplementedError): a forest model, a lift, fixed variables, constraints, more than one rank."""
+    if is_constrained_ehvi(criterion):
+        raise NotImplementedError("%s has no believer batches: ehvi_believer_batch conditions the objectives only and would drop "
+                                  "the constraints" % _CEHVI)  # fmt: skip
     if not is_ehvi(criterion):
         raise TypeError("ehvi_believer_batch takes a bogp.EHVI criterion (the single-objective criteria go to believer_batch)")
     model = criterion.model
@@ -679,6 +701,8 @@ def constrained_believer_batch(criteria, search_space, eval_budget: int, q: Opti
             raise ValueError("q = %d but %d criteria were given" % (q, len(criteria)))
     if len(criteria) == 0:
         raise ValueError("the believer needs at least one criterion")
+    if any(is_constrained_ehvi(c) for c in criteria):
+        raise NotImplementedError("%s has no believer batches: constrained_believer_batch takes one objective" % _CEHVI)
     if not all(is_constrained(c) for c in criteria):
         raise TypeError("constrained_believer_batch takes bogp.Constrained criteria (the single-objective criteria go to believer_batch, "
                         "EHVI to ehvi_believer_batch)")  # fmt: skip
@@ -777,6 +801,8 @@ def _lifted_argmax_restart(obj_func, search_space, h, g, eval_budget, optimizer)
         raise NotImplementedError("a lifted sweep (PCA-BO) takes no fixed variables")
     if h is not None or g is not None:
         raise NotImplementedError("a lifted sweep (PCA-BO) takes no constraints h / g")
+    if is_constrained_ehvi(crit):
+        raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not %s" % _CEHVI)
     if is_ehvi(crit):
         raise NotImplementedError("a lifted sweep (PCA-BO) serves the single-objective criteria, not EHVI")
     if is_constrained(crit):
@@ -838,6 +864,8 @@ def argmax_restart(
     `bogp_sweep_constrained`; "BFGS" and the "-BFGS" hybrids are refused by name (it has no input gradient) unless it was built with
     `input_gradient=True`: then "BFGS" is the loop on `bogp_point_eval_constrained` and the hybrids polish the sweep's best rows with
     `bogp_polish_constrained`; fixed variables, cheap callables h / g, a lift and several ranks are refused by name.
+    A `bogp.ConstrainedEHVI` criterion is served under "sweep" and "sweep-device[-lhs|-sobol]" through `bogp_sweep_ehvi_constrained`;
+    every other optimiser, fixed variables, cheap callables h / g, a lift and several ranks are refused by name.
     Anything else ("MIES", "OnePlusOne_Cholesky_CMA", constraints under "BFGS", a non-continuous space) is the
     reference's own business: the call is handed to its `argmax_restart` when `bayes_optim` is importable, for which a
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
@@ -850,6 +878,18 @@ def argmax_restart(
         # a forest model (any space of Real / Integer / Ordinal / Discrete / Subset / Bool variables): "sweep" and "sweep-device"
         # are served, everything else this package knows is refused with the limitation named
         return _forest.argmax_restart(fcrit, search_space, eval_budget, optimizer, h=h, g=g, masks=fmasks)
+    if is_constrained_ehvi(fcrit):  # served under "sweep" and "sweep-device[-lhs|-sobol]" alone; nothing else may drop its constraints
+        if optimizer not in DEVICE_DESIGNS and optimizer != "sweep":
+            raise NotImplementedError("optimizer=%r for %s: it has no input gradient and no polish; use 'sweep' or "
+                                      "'sweep-device[-lhs|-sobol]'" % (optimizer, _CEHVI))  # fmt: skip
+        if not is_continuous(search_space):
+            raise NotImplementedError("optimizer=%r for %s takes a continuous space" % (optimizer, _CEHVI))
+        if fmasks is not None:
+            raise NotImplementedError("optimizer=%r for %s takes no fixed variables" % (optimizer, _CEHVI))
+        if h is not None or g is not None:
+            raise NotImplementedError("optimizer=%r for %s takes no cheap constraints h / g: model them as columns instead" % (optimizer, _CEHVI))
+        if engine_rank_world(fcrit.model.engine)[1] > 1:
+            raise NotImplementedError("optimizer=%r for %s runs on one rank" % (optimizer, _CEHVI))
     if is_ehvi(fcrit) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS") and is_continuous(search_space):
         if not getattr(fcrit, "input_gradient", False):
             raise NotImplementedError("optimizer=%r needs an input gradient, which EHVI does not have: use 'sweep' or "
@@ -988,6 +1028,8 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
     model = crit.model
     eng = getattr(model, "engine", None)
     fused = getattr(model, "_fused_point_ok", None)
+    if is_constrained_ehvi(crit):
+        raise NotImplementedError("%s has no polish: bogp_polish_ehvi knows the objectives only and would drop the constraints" % _CEHVI)
     if is_ehvi(crit) and eng is not None and hasattr(eng, "polish_ehvi"):  # EHVI(input_gradient=True): bogp_polish_ehvi
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")

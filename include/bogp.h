@@ -322,6 +322,32 @@ int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, const doubl
                            const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx, double* acq_out,
                            double* pof_out, double* mu_out, double* mse_out);
 
+/* ---- sweep: modelled constraints of a multi-objective run, feasibility-weighted EHVI ------------------
+ * The reference leaves this as a TODO (BaseMOBO.tell, mobo.py:117-118: "implement method to handle known, expensive constraints
+ * `h_vals` and `g_vals`").  Here the committed model has n_targets = m_obj + n_con columns: targets 0 .. m_obj - 1 are the objectives,
+ * maximised as given (bogp_sweep_ehvi's convention), targets m_obj .. m_obj + n_con - 1 are constraints, constraint j feasible when
+ * lo_j <= c_j(x) <= hi_j.  Per candidate, from the posterior of all targets (as bogp_sweep_ehvi and bogp_sweep_constrained form it, the
+ * same bits -- the correlation chunk and |L^-1 r|^2 are shared):
+ *   P     = PoF_0 * ... * PoF_{n_con-1} (in this order, from 1.0),  PoF_j = bogp_feasibility(mu, MSE, sigma2 of target m_obj + j, lo_j, hi_j)
+ *   E     = bogp_sweep_ehvi's EHVI of the objectives over the C cells (sd_k = sqrt(max(MSE_k, 1e-9)))
+ *   value = +0.0 where P == 0.0 (whatever E is: such a row's cells are not evaluated);  otherwise E * P for C >= 1;  otherwise P for
+ *           C == 0: the probability of feasibility alone, the criterion while no feasible observation exists (Gelbart, Snoek,
+ *           Adams 2014).  A NaN P is not == 0: it propagates and is maximal in the argmax.
+ *   m_obj        2 <= m_obj;  n_con >= 1;  m_obj + n_con == n_targets <= BOGP_MAX_TARGETS
+ *   lower/upper  C x m_obj row-major HOST arrays of cell bounds as bogp_sweep_ehvi takes them, 0 <= C <= BOGP_MAX_EHVI_CELLS; with
+ *                C == 0 both may be NULL
+ *   lo / hi      n_con HOST values each, either may be infinite, NaN and hi < lo are invalid (hi == lo is allowed: every value is +0.0)
+ *   k            1 <= k <= BOGP_MAX_TOPK winners: best_val / best_idx (k) follow bogp_sweep_topk's rules
+ *   val_out (M), pof_out (M), mu_out (M x n_targets), mse_out (M x n_targets): optional HOST buffers (NULL to skip)
+ * Always the chunked, unpruned sweep with the variance; the kernel's time is reported as acquisition_ms by bogp_last_timing.
+ * BOGP_ERR_INVALID: no committed model, no candidates, m_obj < 2, n_con < 1, m_obj + n_con != n_targets, C outside
+ * [0, BOGP_MAX_EHVI_CELLS], k outside [1, BOGP_MAX_TOPK], a non-finite lower cell bound, a NaN upper cell bound, upper < lower, a NaN
+ * constraint bound, hi < lo, a null required array.  BOGP_ERR_UNSUPPORTED: a lift is set, the handle holds a forest, a polynomial
+ * trend basis.                                                                                                          */
+int bogp_sweep_ehvi_constrained(bogp_handle* h, int m_obj, int C, const double* lower, const double* upper, int n_con, const double* lo,
+                                const double* hi, int k, double* best_val, int64_t* best_idx, double* val_out, double* pof_out,
+                                double* mu_out, double* mse_out);
+
 /* ---- sweep: Kriging-believer batches ------------------------------------------------------------------
  * q proposals per call from q criteria, where step j sees the variance conditioned on the points believed before it
  * (Ginsbourger, Le Riche, Carraro 2010).  The reference has no such strategy: ParallelBO's q criteria share one posterior
