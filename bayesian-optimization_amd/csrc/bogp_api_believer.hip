@@ -1,21 +1,29 @@
-// bogp_api_believer.hip -- the C ABI of libbogp.so (include/bogp.h) for Kriging-believer batches: bogp_sweep_believer, q proposals from q
-// criteria where step j sees the variance conditioned on the pending points and on the winners of the steps before it.
-//   pass 0            the plain sweep of bogp_api_sweep.hip (run_sweep): mu, MSE_0 = sigma2 max(0, s_0) per candidate, and -- without pending
-//                     points -- step 0's criterion and argmax, which are therefore bogp_sweep's bit for bit
+// bogp_api_believer.hip -- the C ABI of libbogp.so (include/bogp.h) for Kriging-believer batches: q proposals from q steps where step j
+// sees the variance conditioned on the pending points and on the winners of the steps before it.  Three entries, ONE recursion
+// (believer_run): an entry keeps its argument checks, its pass 0 (run_sweep with the family's request: mu, the clamped MSE_0 and --
+// without pending points -- step 0's criterion and argmax, the family's plain sweep bit for bit) and hands over what differs.
 //   per believed p    a solve a = V^T (V r(p)) with the kernels of bogp_gradient, the p-by-p terms on the host (at most 32 x 32), then ONE
 //                     pass over the candidates: producer per chunk -> k_believer (kernels_believer.hip); when one chunk holds every
 //                     candidate the producer runs for the first believed point only
-// A row that is a winner keeps its criterion value in the outputs but leaves the argmax of the later steps.
-// The running variance is kept as sigma2 s, started from the sweep's clamped MSE_0: where s_0 < 0 the clamp changes nothing that is
-// returned (s only decreases, and every output is max(0, .) of it).
-// bogp_sweep_believer_ehvi (below) is the same recursion for an m-target model under EHVI; bogp_ehvi_grid_cells the host's cell decomposition.
-// bogp_sweep_believer_constrained (last) is that recursion again under modelled constraints: target 0 the objective, the others constraints.
+// A row that is a winner keeps its criterion value in the outputs but leaves the argmax of the later steps.  The running variance
+// is kept as sigma2 s, started from the sweep's clamped MSE_0: where s_0 < 0 the clamp changes nothing that is returned (s only
+// decreases, and every output is max(0, .) of it).
+//                                 bogp_sweep_believer            bogp_sweep_believer_ehvi               bogp_sweep_believer_constrained
+//   a believed mean               lowers the plugin              joins the front (m-vector)             lowers the plugin if feasible
+//   a step's criterion            k_believer itself, per chunk   k_believer_ehvi, one launch, after     k_believer_constrained, likewise
+//                                 (one record per 64 rows)       k_believer stored c(x) in unit variance (one record per 256 rows)
+//   a column c_k(x) is stored     when a later pass reads it     for every point past the guard         likewise
+//   a guarded pivot before a step k_believer without the update  the criterion kernel alone (c = null)  likewise
+//   before a step                 --                             the front's cells, rebuilt + uploaded  --
+//   a winner's mean is believed   also behind the last step      between two steps only                 likewise
+// The m targets share the bracket of gpr.py:502-510, so ONE downdate in correlation units serves them all.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "../../include/bogp.h"
@@ -110,6 +118,186 @@ int believer_chunk(bogp_handle* h, const SweepGeometry& pl, const BelieverArgs& 
   return BOGP_OK;
 }
 
+// ---- the recursion, once ----------------------------------------------------------------------------------------------------------
+// The handle's believer arrays are shared by the three families and laid out per call (M candidates, m targets, B = n_pending + q
+// believed points; every call sizes and fills them anew, nothing is carried from the call before):
+//                  dbel_s    dbel_row: `lead` rows of M, then the MSE block        dbel_C [columns][M] c_k(x)
+//   one target     [M]       [values | MSE M]                          lead 1      B - 2: the last winner runs no pass, the point before
+//                                                                                  it stores no column (no pass reads it)
+//   EHVI           [M][m]    [EHVI | scratch | MSE M x m]              lead 2      B - 1: the criterion kernel reads every column
+//   constrained    [M][m]    [values | PoF | scratch | MSE M x m]      lead 3      B - 1
+// dbel_s is sigma2_k s_B(x), unclamped below the sweep's own clamp of s_0; `scratch` is k_believer's own s in unit variance (m > 1: not
+// used); dbel_small is SolveBufs; dehvi_cells ([lower C x m | upper C x m]) is the EHVI entry's alone.
+
+struct StepRows {  // rows of step j for the caller: out + j n <- the sweep's own array (step 0 without pending points) or dbel_row + at M
+  double* out;     // null: not wanted
+  const DevBuf<double>* sweep;
+  int at, width;   // in units of M doubles; n = width M
+};
+
+// What a family hands the recursion: its layout, its outputs and what differs in code.
+struct BelieverFamily {
+  const char* who;
+  int m = 1;  // targets.  1: k_believer itself evaluates a step, with the four fields below; > 1: it stores c(x), then `criterion` runs
+  const int* acq_id = nullptr;
+  const double* acq_par = nullptr;  // null: zeros
+  int minimize = 0;
+  const double* plugin = nullptr;   // the running plugin, as `mean` leaves it
+  int lead = 1;                     // rows of dbel_row in front of the MSE block (the table above)
+  int span = B_PASS;                // kind of `criterion`'s span
+  double* best_val = nullptr;
+  int64_t* best_idx = nullptr;
+  double *best_x = nullptr, *best_mu = nullptr, *pivots = nullptr;  // each may be null
+  StepRows rows[3] = {};
+  std::function<void(const double* mu)> mean;  // a believed mean (m values): a pending point's as the host forms it, a winner's from the sweep's array
+  std::function<int(int step)> step_begin;     // (may be empty) in front of a step's pass, behind the believed mean
+  // m > 1: the launch over all M rows behind the column pass: c the believed point's column (null: guarded, no update), `row` the
+  // candidate row a winner is (its variance becomes exactly 0; -1: a pending point), step >= 0: evaluate it into dblk_* (256 rows a record)
+  std::function<hipError_t(int step, int64_t row, const double* c)> criterion;
+};
+
+// Behind pass 0 (dmu_out, dmse_out and -- without pending points -- step 0's winner in dbest_*[0] are in place): the pending points,
+// then per step the read-back of its winner and the pass that believes it.
+int believer_run(bogp_handle* h, const BelieverFamily& f, int q, const double* pending, int P) {
+  const int d = h->d, N = h->N, Np = h->Np, m = f.m, Btot = P + q;
+  const bool one = m == 1;
+  const int64_t M = h->M;
+  hipStream_t st = h->stream;
+  int rc;
+  SweepGeometry pl;  // the sweep's own for a constant-trend model
+  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
+  const int64_t nblk_total = one ? (M + 63) / 64 + pl.nchunk : (M + 255) / 256;
+  const int ncol = Btot - (one ? 2 : 1);
+  if ((rc = h->dbel_s.ensure(h, (size_t)M * m))) return rc;
+  if ((rc = h->dbel_row.ensure(h, (size_t)(f.lead + m) * M))) return rc;
+  if ((rc = h->dbel_small.ensure(h, SolveBufs::doubles(d, N)))) return rc;
+  if (ncol > 0)
+    if ((rc = h->dbel_C.ensure(h, (size_t)ncol * M))) return rc;
+  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
+  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
+  if ((rc = ensure_sweep_outputs(h, 1, nblk_total, 0, false))) return rc;
+  const SolveBufs sb(h->dbel_small, d, N);
+  double* dscratch = h->dbel_row + (size_t)(f.lead - 1) * M;  // (m > 1)
+  double* dmse_row = h->dbel_row + (size_t)f.lead * M;
+
+  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (!one) HIPCHK(h, hipMemsetAsync(dscratch, 0, (size_t)M * sizeof(double), st));
+  const size_t n_gamma = one ? (size_t)N : (size_t)m * Np;  // the active target's gamma, or every target's with Np a row
+  std::vector<double> hgamma(n_gamma), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED), hmu((size_t)m);
+  HIPCHK(h, hipMemcpyAsync(hgamma.data(), one ? h->dgamma : h->dgamma_base.ptr, n_gamma * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+
+  Believed bl;
+  bl.r.resize((size_t)Btot * N);
+  bl.a.resize((size_t)Btot * N);
+  bl.u.resize(Btot);
+  memset(bl.L, 0, sizeof(bl.L));
+  int slots = 0;
+  bool chunk_resident = false;  // all candidates fit one chunk and the producer has filled it: r(x) and the w-sums stay for the later points
+  h->bel_timer.begin();
+  h->bel_passes = 0;
+
+  // One believed point: solve, the host's row of the recursion, and -- unless the pivot is guarded and no step follows -- a candidate pass.
+  // `step` >= 0: the pass also evaluates that step's criterion and leaves its winner in dbest_*[0]; `pass`: false for the last winner, whose
+  // pivot alone is reported.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it is believed before the pass (a winner's mean is
+  // read from the sweep's array by the winner loop).  `row`: the candidate row a winner is, -1 for a pending point.
+  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
+    const int i = bl.n;
+    if (int rs = believed_solve(h, bl, sb, x, hw, hk, f.pivots)) return rs;
+    if (is_pending) {
+      const double* ri = &bl.r[(size_t)i * N];
+      for (int t = 0; t < m; ++t) {
+        double rg = 0.0;
+        for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[(size_t)t * Np + n];
+        hmu[t] = h->beta + rg;
+      }
+      f.mean(hmu.data());
+    }
+    const bool active = bl.L[i][i] > 0.0;
+    if (!pass || (!active && step < 0)) return BOGP_OK;
+    if (step >= 0 && f.step_begin)
+      if (int rs = f.step_begin(step)) return rs;
+    const bool store = active && (!one || bl.n < Btot - 1);  // one target: only where a later pass will read this column
+    if (store) bl.slot[i] = slots++;
+    double* col = store ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr;
+    int64_t blk_offset = 0;
+    if (one || active) {  // m > 1 behind a guarded pivot: no column to form, the criterion launch alone
+      BelieverArgs ba;
+      memset(&ba, 0, sizeof(ba));
+      ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
+      ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
+      ba.update = active ? 1 : 0;
+      ba.self_row = one ? row : -1;
+      ba.u_p = bl.u[i]; ba.inv_root = active ? 1.0 / bl.L[i][i] : 0.0; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
+      for (int k = 0; k < i; ++k)
+        if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
+          ba.prev_slot[ba.nprev] = bl.slot[k];
+          ba.prev_c[ba.nprev] = bl.L[i][k];
+          ++ba.nprev;
+        }
+      ba.C = h->dbel_C; ba.c_out = col;
+      ba.s = one ? h->dbel_s.ptr : dscratch; ba.sigma2 = one ? h->sigma2 : 1.0;
+      if (one) {
+        ba.eval = step >= 0 ? 1 : 0;
+        if (step >= 0) {
+          ba.acq_id = f.acq_id[step]; ba.acq_par = f.acq_par ? f.acq_par[step] : 0.0; ba.plugin = *f.plugin; ba.minimize = f.minimize;
+          ba.n_taken = step;  // the winners of steps 0 .. step - 1
+          for (int k = 0; k < step; ++k) ba.taken[k] = f.best_idx[k];
+        }
+        ba.mu = h->dmu_out; ba.acq_out = h->dbel_row; ba.mse_out = dmse_row; ba.blk_val = h->dblk_val; ba.blk_idx = h->dblk_idx;
+      }
+      for (int64_t c = 0; c < pl.nchunk; ++c) {
+        ba.m0 = c * pl.Mc; ba.mcount = std::min<int64_t>(pl.Mc, M - ba.m0); ba.blk_offset = blk_offset;
+        if (int rs = believer_chunk(h, pl, ba, active && !chunk_resident)) return rs;
+        if (active) chunk_resident = pl.nchunk == 1;
+        if (one) blk_offset += (ba.mcount + 63) / 64;  // one record per 64 rows of every chunk
+      }
+    }
+    if (!one)
+      if (int rs = timed_span(h, h->bel_timer, st, f.span, [&] { return f.criterion(step, row, col); })) return rs;
+    ++h->bel_passes;
+    if (step >= 0)
+      HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, one ? blk_offset : nblk_total, nblk_total, 1, h->dbest_val, h->dbest_idx, st));
+    return BOGP_OK;
+  };
+
+  for (int i = 0; i < P; ++i)
+    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
+
+  for (int j = 0; j < q; ++j) {
+    // the winner of step j is in dbest_*[0]; its rows in the sweep's own arrays (step 0 without pending points) or in dbel_row
+    const bool from_sweep = j == 0 && P == 0;
+    int64_t idx = 0;
+    HIPCHK(h, hipMemcpyAsync(&f.best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    for (const StepRows& r : f.rows) {
+      const size_t n = (size_t)r.width * M;
+      if (r.out) HIPCHK(h, hipMemcpyAsync(r.out + (size_t)j * n, from_sweep ? r.sweep->ptr : h->dbel_row + (size_t)r.at * M, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    f.best_idx[j] = idx;
+    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "%s: step %d returned row %lld outside [0, %lld)", f.who, j, (long long)idx, (long long)M);
+    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(hmu.data(), h->dmu_out + (size_t)idx * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (f.best_x) memcpy(f.best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
+    if (f.best_mu) memcpy(f.best_mu + (size_t)j * m, hmu.data(), (size_t)m * sizeof(double));
+    if (one || j < q - 1) f.mean(hmu.data());  // (one target believes the last winner's mean too; no step reads the plugin after it)
+    if (j == q - 1) {
+      if (f.pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
+      break;
+    }
+    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
+  }
+
+  // times of the solves and of the passes (everything is complete: the last step was read back)
+  HIPCHK(h, hipStreamSynchronize(st));
+  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  return BOGP_OK;
+}
+
 }  // namespace
 
 extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
@@ -123,151 +311,37 @@ extern "C" int bogp_sweep_believer(bogp_handle* h, int q, const int* acq_id, con
   if (!acq_id || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: acq_id, best_val and best_idx must be non-null");
   if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: n_pending = %d but pending is null", n_pending);
   if (int ec = check_criteria(h, q, acq_id, acq_par)) return ec;
-  const int d = h->d, N = h->N, Np = h->Np;
   if (q > h->M) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: q = %d proposals from %lld candidates (every step takes a row no step before it took)", q, (long long)h->M);
-  for (size_t i = 0; i < (size_t)n_pending * d; ++i)
+  for (size_t i = 0; i < (size_t)n_pending * h->d; ++i)
     if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_believer: pending entry %zu is not finite", i);
   if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: constant trend basis only (the committed basis has %d columns)", h->p);
   if (h->n_t != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: one target only (the committed model has %d): EHVI batches are bogp_sweep_believer_ehvi", h->n_t);
   if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: a lift is set (bogp_lift_set): call bogp_lift_clear first");
   if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_believer: runs on one rank (the communicator has %d)", h->comm_world);
   HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  const int64_t M = h->M;
-  const int P = n_pending, Btot = P + q;
   invalidate_sweep_results(h);  // dbest_* are overwritten
 
   // ---- pass 0: the plain sweep; with pending points only the moments (step 0 is evaluated behind the last pending point)
   SweepRequest rq;
   rq.want_out = true; rq.minimize = minimize;
-  if (P == 0) { rq.q = 1; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.want_acq_out = true; }
+  if (n_pending == 0) { rq.q = 1; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.want_acq_out = true; }
   int rc = run_sweep(h, rq);
   if (rc) return rc;
   if ((rc = candidates_ready(h))) return rc;
 
-  // ---- geometry of the later passes
-  SweepGeometry pl;  // the sweep's own for a constant-trend model
-  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
-  const int64_t nblk_total = (M + 63) / 64 + pl.nchunk;  // (one record per 64 rows)
-  const size_t small_n = SolveBufs::doubles(d, N);
-  if ((rc = h->dbel_s.ensure(h, (size_t)M))) return rc;
-  if ((rc = h->dbel_row.ensure(h, (size_t)2 * M))) return rc;
-  if ((rc = h->dbel_small.ensure(h, small_n))) return rc;
-  if (Btot > 2)
-    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 2) * M))) return rc;  // the last winner runs no pass, the point before it stores no column
-  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
-  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure_sweep_outputs(h, 1, nblk_total, 0, false))) return rc;
-  const SolveBufs sb(h->dbel_small, d, N);
-  double* dacq_row = h->dbel_row;
-  double* dmse_row = h->dbel_row + M;
-
-  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, st));
-  std::vector<double> hgamma((size_t)N), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED);
-  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-
-  Believed bl;
-  bl.r.resize((size_t)Btot * N);
-  bl.a.resize((size_t)Btot * N);
-  bl.u.resize(Btot);
-  memset(bl.L, 0, sizeof(bl.L));
-  int slots = 0;
-  bool chunk_resident = false;  // all candidates fit one chunk and the producer has filled it: r(x) and the w-sums stay for the later points
-  h->bel_timer.begin();
-  h->bel_passes = 0;
   double plug = plugin;
-  auto believe_mean = [&](double mu) {
+  BelieverFamily f;
+  f.who = "bogp_sweep_believer";
+  f.acq_id = acq_id; f.acq_par = acq_par; f.minimize = minimize; f.plugin = &plug;
+  f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.pivots = pivots;
+  f.rows[0] = {acq_out, &h->dacq_out, 0, 1};
+  f.rows[1] = {mse_out, &h->dmse_out, 1, 1};
+  f.mean = [&](const double* mu) {
     if (!believe_plugin) return;
-    const double y_hat = minimize ? mu : -1 * mu;  // the plugin arrives in the criterion's own sign (already negated when maximising)
+    const double y_hat = minimize ? mu[0] : -1 * mu[0];  // the plugin arrives in the criterion's own sign (already negated when maximising)
     if (y_hat < plug) plug = y_hat;
   };
-
-  // One believed point: solve, the host's row of the recursion, and -- unless the pivot is guarded and no step follows -- a candidate pass.
-  // `step` >= 0: the pass also evaluates that step's criterion and leaves its winner in dbest_*[0]; `pass`: false for the last winner, whose
-  // pivot alone is reported.  `is_pending`: mu(p) as the host forms it joins the plugin before the pass (a winner's mean is read from the
-  // sweep's array by the caller).  `row`: the candidate row a winner is (its variance becomes exactly 0), -1 for a pending point.
-  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
-    const int i = bl.n;
-    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
-    if (is_pending) {
-      const double* ri = &bl.r[(size_t)i * N];
-      double rg = 0.0;
-      for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[n];
-      believe_mean(h->beta + rg);
-    }
-    const bool active = bl.L[i][i] > 0.0;
-    if (!pass || (!active && step < 0)) return BOGP_OK;
-    const bool store = active && (bl.n < Btot - 1);  // a later pass will read this column
-    if (store) bl.slot[i] = slots++;
-    BelieverArgs ba;
-    memset(&ba, 0, sizeof(ba));
-    ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
-    ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
-    ba.update = active ? 1 : 0;
-    ba.self_row = row;
-    ba.u_p = bl.u[i]; ba.inv_root = active ? 1.0 / bl.L[i][i] : 0.0; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
-    for (int k = 0; k < i; ++k)
-      if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
-        ba.prev_slot[ba.nprev] = bl.slot[k];
-        ba.prev_c[ba.nprev] = bl.L[i][k];
-        ++ba.nprev;
-      }
-    ba.C = h->dbel_C; ba.c_out = store ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr; ba.s = h->dbel_s; ba.sigma2 = h->sigma2;
-    ba.eval = step >= 0 ? 1 : 0;
-    if (step >= 0) {
-      ba.acq_id = acq_id[step]; ba.acq_par = acq_par ? acq_par[step] : 0.0; ba.plugin = plug; ba.minimize = minimize;
-      ba.n_taken = step;  // the winners of steps 0 .. step - 1
-      for (int k = 0; k < step; ++k) ba.taken[k] = best_idx[k];
-    }
-    ba.mu = h->dmu_out; ba.acq_out = dacq_row; ba.mse_out = dmse_row; ba.blk_val = h->dblk_val; ba.blk_idx = h->dblk_idx;
-    int64_t blk_offset = 0;
-    for (int64_t c = 0; c < pl.nchunk; ++c) {
-      const int64_t m0 = c * pl.Mc, mcount = std::min<int64_t>(pl.Mc, M - m0);
-      ba.m0 = m0; ba.mcount = mcount; ba.blk_offset = blk_offset;
-      if (int rs = believer_chunk(h, pl, ba, active && !chunk_resident)) return rs;
-      if (active) chunk_resident = pl.nchunk == 1;
-      blk_offset += (mcount + 63) / 64;
-    }
-    ++h->bel_passes;
-    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, 1, h->dbest_val, h->dbest_idx, st));
-    return BOGP_OK;
-  };
-
-  for (int i = 0; i < P; ++i) {
-    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
-  }
-
-  for (int j = 0; j < q; ++j) {
-    // the winner of step j is in dbest_*[0]; its criterion values / MSE in the sweep's own arrays (step 0 without pending points) or the row buffers
-    const bool from_sweep = j == 0 && P == 0;
-    int64_t idx = 0;
-    HIPCHK(h, hipMemcpyAsync(&best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out + (size_t)j * M, from_sweep ? h->dacq_out : dacq_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out + (size_t)j * M, from_sweep ? h->dmse_out : dmse_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    best_idx[j] = idx;
-    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "bogp_sweep_believer: step %d returned row %lld outside [0, %lld)", j, (long long)idx, (long long)M);
-    double mu_w = 0.0;
-    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(&mu_w, h->dmu_out + idx, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (best_x) memcpy(best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
-    believe_mean(mu_w);
-    if (j == q - 1) {
-      if (pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
-      break;
-    }
-    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
-  }
-
-  // times of the solves and of the passes (everything is complete: the last step was read back)
-  HIPCHK(h, hipStreamSynchronize(st));
-  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
-  return BOGP_OK;
+  return believer_run(h, f, q, pending, n_pending);
 }
 
 extern "C" int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* believer_ms, int* n_passes) {
@@ -280,10 +354,8 @@ extern "C" int bogp_believer_last(bogp_handle* h, double* corr_ms, double* solve
 }
 
 // ---- believer batches for EHVI: bogp_sweep_believer_ehvi ---------------------------------------------------------------------------
-// The m targets share the bracket of gpr.py:502-510, so ONE downdate in correlation units serves them all: k_believer forms c(x) per
-// chunk exactly as above (with a unit variance and a scratch s: its own s output is not used), k_believer_ehvi
-// (kernels_believer_ehvi.hip) takes sigma2_k c^2 off every target's MSE and evaluates EHVI.  The believed mean mu(p) is an m-vector
-// that joins the front, so the cells are rebuilt on the host between the steps (bogp_ehvi_grid_cells' decomposition).
+// k_believer_ehvi (kernels_believer_ehvi.hip) takes sigma2_k c^2 off every target's MSE and evaluates EHVI.  The believed mean mu(p) is
+// an m-vector that joins the front, so the cells are rebuilt on the host between the steps (bogp_ehvi_grid_cells' decomposition).
 namespace {
 
 // pareto.pareto_front: the rows no other row dominates (of identical rows the first) that lie strictly above r in every objective
@@ -418,7 +490,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
   if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
   const int64_t M = h->M;
-  const int P = n_pending, Btot = P + q;
+  const int P = n_pending;
 
   // ---- the front and its cells (host): F_0 now, one believed mean more per step when believe_front is set
   std::vector<double> F = pareto_front_rows(m, n_front, front, ref_point);
@@ -434,11 +506,6 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
     cells.resize(2 * (size_t)C * m);
     grid_fill(m, F, ref_point, edges, count, cells.data(), cells.data() + (size_t)C * m);
     return BOGP_OK;
-  };
-  auto join_front = [&](const double* mu) {  // F <- pareto_front(F u {mu})
-    if (!believe_front) return;
-    F.insert(F.end(), mu, mu + m);
-    F = pareto_front_rows(m, (int64_t)(F.size() / m), F.data(), ref_point);
   };
   int rc;
   if ((rc = build_cells(0))) return rc;  // before any device work (with pending points: the cells of F_0, which step 0 extends)
@@ -474,88 +541,26 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if ((rc = candidates_ready(h))) return rc;
   if (P == 0 && n_cells) n_cells[0] = C0;
 
-  // ---- the later passes
-  SweepGeometry pl;
-  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
-  const int64_t nblk = (M + 255) / 256;
-  if ((rc = h->dbel_s.ensure(h, (size_t)M * m))) return rc;
-  if ((rc = h->dbel_row.ensure(h, (size_t)(2 + m) * M))) return rc;
-  if ((rc = h->dbel_small.ensure(h, SolveBufs::doubles(d, N)))) return rc;
-  if (Btot > 1)
-    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_ehvi
-  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
-  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure_sweep_outputs(h, 1, nblk, 0, false))) return rc;
-  const SolveBufs sb(h->dbel_small, d, N);
-  double* dehvi_row = h->dbel_row;
-  double* dscratch = h->dbel_row + M;      // k_believer's own s, in unit variance: not used
-  double* dmse_row = h->dbel_row + 2 * M;  // [M][m]
-
-  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToDevice, st));
-  HIPCHK(h, hipMemsetAsync(dscratch, 0, (size_t)M * sizeof(double), st));
-  std::vector<double> hgamma((size_t)m * Np), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED), hmu((size_t)m);
-  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base, (size_t)m * Np * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-
-  Believed bl;
-  bl.r.resize((size_t)Btot * N);
-  bl.a.resize((size_t)Btot * N);
-  bl.u.resize(Btot);
-  memset(bl.L, 0, sizeof(bl.L));
-  int slots = 0;
-  bool chunk_resident = false;
-  h->bel_timer.begin();
-  h->bel_passes = 0;
-
-  // One believed point, as in bogp_sweep_believer.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it joins the front (a
-  // winner's mean is read from the sweep's array by the caller, before this).  A step's cells are those of the front as it stands here.
-  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
-    const int i = bl.n;
-    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
-    if (is_pending) {
-      const double* ri = &bl.r[(size_t)i * N];
-      for (int t = 0; t < m; ++t) {
-        double rg = 0.0;
-        for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[(size_t)t * Np + n];
-        hmu[t] = h->beta + rg;
-      }
-      join_front(hmu.data());
-    }
-    const bool active = bl.L[i][i] > 0.0;
-    if (!pass || (!active && step < 0)) return BOGP_OK;
-    if (step >= 0) {
-      if (int rs = build_cells(step)) return rs;
-      if (int rs = upload_cells()) return rs;
-      if (n_cells) n_cells[step] = C;
-    }
-    if (active) {  // c(x) of this point for every candidate, chunk by chunk
-      bl.slot[i] = slots++;
-      BelieverArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
-      ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
-      ba.update = 1;
-      ba.self_row = -1;
-      ba.u_p = bl.u[i]; ba.inv_root = 1.0 / bl.L[i][i]; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
-      for (int k = 0; k < i; ++k)
-        if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
-          ba.prev_slot[ba.nprev] = bl.slot[k];
-          ba.prev_c[ba.nprev] = bl.L[i][k];
-          ++ba.nprev;
-        }
-      ba.C = h->dbel_C; ba.c_out = h->dbel_C + (size_t)bl.slot[i] * M; ba.s = dscratch; ba.sigma2 = 1.0;
-      ba.eval = 0;
-      for (int64_t c = 0; c < pl.nchunk; ++c) {
-        ba.m0 = c * pl.Mc; ba.mcount = std::min<int64_t>(pl.Mc, M - ba.m0);
-        if (int rs = believer_chunk(h, pl, ba, !chunk_resident)) return rs;
-        chunk_resident = pl.nchunk == 1;
-      }
-    }
+  BelieverFamily f;
+  f.who = who; f.m = m; f.lead = 2; f.span = B_EHVI;
+  f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
+  f.rows[0] = {ehvi_out, &h->dacq_out, 0, 1};
+  f.rows[1] = {mse_out, &h->dmse_out, 2, m};
+  f.mean = [&](const double* mu) {  // F <- pareto_front(F u {mu})
+    if (!believe_front) return;
+    F.insert(F.end(), mu, mu + m);
+    F = pareto_front_rows(m, (int64_t)(F.size() / m), F.data(), ref_point);
+  };
+  f.step_begin = [&](int step) -> int {  // the step's cells are those of the front as it stands here
+    if (int rs = build_cells(step)) return rs;
+    if (int rs = upload_cells()) return rs;
+    if (n_cells) n_cells[step] = C;
+    return BOGP_OK;
+  };
+  f.criterion = [&](int step, int64_t row, const double* c) {
     BelieverEhviArgs be;
     memset(&be, 0, sizeof(be));
-    be.M = M; be.m = m; be.update = active ? 1 : 0; be.c = active ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr;
+    be.M = M; be.m = m; be.update = c ? 1 : 0; be.c = c;
     be.self_row = row; be.s = h->dbel_s;
     for (int t = 0; t < m; ++t) be.sigma2[t] = h->sigma2_t[t];
     be.eval = step >= 0 ? 1 : 0;
@@ -564,42 +569,10 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
       for (int k = 0; k < step; ++k) be.taken[k] = best_idx[k];
       be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C;
     }
-    be.mu = h->dmu_out; be.ehvi_out = dehvi_row; be.mse_out = dmse_row; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
-    if (int rs = timed_span(h, h->bel_timer, st, B_EHVI, [&] { return launch_believer_ehvi(be, st); })) return rs;
-    ++h->bel_passes;
-    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
-    return BOGP_OK;
+    be.mu = h->dmu_out; be.ehvi_out = h->dbel_row; be.mse_out = h->dbel_row + 2 * M; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
+    return launch_believer_ehvi(be, st);
   };
-
-  for (int i = 0; i < P; ++i)
-    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
-
-  for (int j = 0; j < q; ++j) {
-    // the winner of step j is in dbest_*[0]; its EHVI values / MSE in the sweep's own arrays (step 0 without pending points) or the row buffers
-    const bool from_sweep = j == 0 && P == 0;
-    int64_t idx = 0;
-    HIPCHK(h, hipMemcpyAsync(&best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (ehvi_out) HIPCHK(h, hipMemcpyAsync(ehvi_out + (size_t)j * M, from_sweep ? h->dacq_out : dehvi_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out + (size_t)j * M * m, from_sweep ? h->dmse_out : dmse_row, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    best_idx[j] = idx;
-    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "%s: step %d returned row %lld outside [0, %lld)", who, j, (long long)idx, (long long)M);
-    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(hmu.data(), h->dmu_out + (size_t)idx * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (best_x) memcpy(best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
-    if (best_mu) memcpy(best_mu + (size_t)j * m, hmu.data(), (size_t)m * sizeof(double));
-    if (j == q - 1) {
-      if (pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
-      break;
-    }
-    join_front(hmu.data());
-    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
-  }
-
-  HIPCHK(h, hipStreamSynchronize(st));
-  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  if ((rc = believer_run(h, f, q, pending, P))) return rc;
   h->bel_ehvi_ms = h->bel_timer.sum(B_EHVI);
   return BOGP_OK;
 }
@@ -615,9 +588,8 @@ extern "C" int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* 
 }
 
 // ---- believer batches under modelled constraints: bogp_sweep_believer_constrained --------------------------------------------------
-// bogp_sweep_believer_ehvi's recursion with bogp_sweep_constrained's criterion: pass 0 is the constrained sweep (k_constrained) with
-// criterion 0, every believed point costs the solve, k_believer for c(x) in unit variance and ONE launch of k_believer_constrained
-// (kernels_believer_constrained.hip), which takes sigma2_k c^2 off every target's MSE and evaluates the step's criterion.  The plugin
+// Pass 0 is the constrained sweep (k_constrained) with criterion 0; k_believer_constrained (kernels_believer_constrained.hip) takes
+// sigma2_k c^2 off every target's MSE and evaluates the step's criterion: target 0 the objective, the others constraints.  The plugin
 // follows the believed points that are feasible by belief; the criteria, the bounds, the hyper-parameters and sigma2_k stay fixed.
 extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int* acq_id, const double* acq_par, double plugin, int minimize,
                                                int believe_plugin, int n_con, const double* lo, const double* hi, const double* pending,
@@ -638,11 +610,10 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
   if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
   int rc = check_constrained_request(h, who, q, acq_id, acq_par, n_con, lo, hi);
   if (rc) return rc;
-  const int d = h->d, N = h->N, Np = h->Np, m = h->n_t;
-  for (size_t i = 0; i < (size_t)n_pending * d; ++i)
+  const int N = h->N, Np = h->Np, m = h->n_t;
+  for (size_t i = 0; i < (size_t)n_pending * h->d; ++i)
     if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
   const int64_t M = h->M;
-  const int P = n_pending, Btot = P + q;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
 
@@ -662,94 +633,26 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
   if ((rc = run_sweep(h, rq))) return rc;
   if ((rc = candidates_ready(h))) return rc;
 
-  // ---- the later passes
-  SweepGeometry pl;
-  if ((rc = sweep_geometry(h, Np, &pl))) return rc;
-  const int64_t nblk = (M + 255) / 256;
-  if ((rc = h->dbel_s.ensure(h, (size_t)M * m))) return rc;
-  if ((rc = h->dbel_row.ensure(h, (size_t)(3 + m) * M))) return rc;
-  if ((rc = h->dbel_small.ensure(h, SolveBufs::doubles(d, N)))) return rc;
-  if (Btot > 1)
-    if ((rc = h->dbel_C.ensure(h, (size_t)(Btot - 1) * M))) return rc;  // the last winner runs no pass; every other column is read by k_believer_constrained
-  if ((rc = h->drT[0].ensure(h, (size_t)Np * pl.Mc))) return rc;
-  if ((rc = h->dmu_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = h->dw_part[0].ensure(h, (size_t)pl.S * pl.Mc))) return rc;
-  if ((rc = ensure_sweep_outputs(h, 1, nblk, 0, false))) return rc;
-  const SolveBufs sb(h->dbel_small, d, N);
-  double* dacq_row = h->dbel_row;
-  double* dpof_row = h->dbel_row + M;
-  double* dscratch = h->dbel_row + 2 * M;  // k_believer's own s, in unit variance: not used
-  double* dmse_row = h->dbel_row + 3 * M;  // [M][m]
-
-  HIPCHK(h, hipMemcpyAsync(h->dbel_s, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToDevice, st));
-  HIPCHK(h, hipMemsetAsync(dscratch, 0, (size_t)M * sizeof(double), st));
-  std::vector<double> hgamma((size_t)m * Np), hw((size_t)N), hrow((size_t)d), hk(BOGP_MAX_BELIEVED), hmu((size_t)m);
-  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base, (size_t)m * Np * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(hw.data(), h->dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-
-  Believed bl;
-  bl.r.resize((size_t)Btot * N);
-  bl.a.resize((size_t)Btot * N);
-  bl.u.resize(Btot);
-  memset(bl.L, 0, sizeof(bl.L));
-  int slots = 0;
-  bool chunk_resident = false;
-  h->bel_timer.begin();
-  h->bel_passes = 0;
   double plug = plugin;
+  BelieverFamily f;
+  f.who = who; f.m = m; f.lead = 3; f.span = B_CONSTRAINED;
+  f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
+  f.rows[0] = {acq_out, &h->dacq_out, 0, 1};
+  f.rows[1] = {pof_out, &h->dpof_out, 1, 1};
+  f.rows[2] = {mse_out, &h->dmse_out, 3, m};
   // a believed point that is feasible by belief -- every constraint's mean inside its interval -- may lower the plugin, which
   // arrives in the criterion's own sign (already negated when maximising); an infeasible one leaves it
-  auto believe_means = [&](const double* mu) {
+  f.mean = [&](const double* mu) {
     if (!believe_plugin) return;
     for (int k = 1; k < m; ++k)
       if (!(lo[k - 1] <= mu[k] && mu[k] <= hi[k - 1])) return;
     const double y_hat = minimize ? mu[0] : -1 * mu[0];
     if (y_hat < plug) plug = y_hat;
   };
-
-  // One believed point, as in bogp_sweep_believer_ehvi.  `is_pending`: mu(p) = beta + r . gamma_k as the host forms it joins the plugin
-  // before the pass (a winner's means are read from the sweep's array by the caller, before this).
-  auto believe = [&](const double* x, int step, bool pass, bool is_pending, int64_t row) -> int {
-    const int i = bl.n;
-    if (int rs = believed_solve(h, bl, sb, x, hw, hk, pivots)) return rs;
-    if (is_pending) {
-      const double* ri = &bl.r[(size_t)i * N];
-      for (int t = 0; t < m; ++t) {
-        double rg = 0.0;
-        for (int n = 0; n < N; ++n) rg += ri[n] * hgamma[(size_t)t * Np + n];
-        hmu[t] = h->beta + rg;
-      }
-      believe_means(hmu.data());
-    }
-    const bool active = bl.L[i][i] > 0.0;
-    if (!pass || (!active && step < 0)) return BOGP_OK;
-    if (active) {  // c(x) of this point for every candidate, chunk by chunk
-      bl.slot[i] = slots++;
-      BelieverArgs ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.Xs = h->dXs; ba.theta = h->dtheta; ba.pt = sb.dpt; ba.rT = h->drT[0]; ba.w_part = h->dw_part[0]; ba.avec = sb.da;
-      ba.d = d; ba.N = N; ba.S = pl.S; ba.Mc = pl.Mc; ba.M = M;
-      ba.update = 1;
-      ba.self_row = -1;
-      ba.u_p = bl.u[i]; ba.inv_root = 1.0 / bl.L[i][i]; ba.G = h->G; ba.estimate_trend = h->estimate_trend;
-      for (int k = 0; k < i; ++k)
-        if (bl.slot[k] >= 0 && bl.L[k][k] > 0.0) {
-          ba.prev_slot[ba.nprev] = bl.slot[k];
-          ba.prev_c[ba.nprev] = bl.L[i][k];
-          ++ba.nprev;
-        }
-      ba.C = h->dbel_C; ba.c_out = h->dbel_C + (size_t)bl.slot[i] * M; ba.s = dscratch; ba.sigma2 = 1.0;
-      ba.eval = 0;
-      for (int64_t c = 0; c < pl.nchunk; ++c) {
-        ba.m0 = c * pl.Mc; ba.mcount = std::min<int64_t>(pl.Mc, M - ba.m0);
-        if (int rs = believer_chunk(h, pl, ba, !chunk_resident)) return rs;
-        chunk_resident = pl.nchunk == 1;
-      }
-    }
+  f.criterion = [&](int step, int64_t row, const double* c) {
     BelieverConstrainedArgs bc;
     memset(&bc, 0, sizeof(bc));
-    bc.M = M; bc.m = m; bc.update = active ? 1 : 0; bc.c = active ? h->dbel_C + (size_t)bl.slot[i] * M : nullptr;
+    bc.M = M; bc.m = m; bc.update = c ? 1 : 0; bc.c = c;
     bc.self_row = row; bc.s = h->dbel_s;
     for (int t = 0; t < m; ++t) { bc.sigma2[t] = ca.sigma2[t]; bc.lo[t] = ca.lo[t]; bc.hi[t] = ca.hi[t]; }
     bc.eval = step >= 0 ? 1 : 0;
@@ -759,44 +662,12 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
       for (int k = 0; k < step; ++k) bc.taken[k] = best_idx[k];
       if (plugin_out) plugin_out[step] = plug;
     }
-    bc.mu = h->dmu_out; bc.acq_out = dacq_row; bc.pof_out = dpof_row; bc.mse_out = dmse_row; bc.blk_val = h->dblk_val; bc.blk_idx = h->dblk_idx;
-    if (int rs = timed_span(h, h->bel_timer, st, B_CONSTRAINED, [&] { return launch_believer_constrained(bc, st); })) return rs;
-    ++h->bel_passes;
-    if (step >= 0) HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
-    return BOGP_OK;
+    bc.mu = h->dmu_out; bc.acq_out = h->dbel_row; bc.pof_out = h->dbel_row + M; bc.mse_out = h->dbel_row + 3 * M;
+    bc.blk_val = h->dblk_val; bc.blk_idx = h->dblk_idx;
+    return launch_believer_constrained(bc, st);
   };
-
-  if (P == 0 && plugin_out) plugin_out[0] = plugin;
-  for (int i = 0; i < P; ++i)
-    if ((rc = believe(pending + (size_t)i * d, i == P - 1 ? 0 : -1, true, true, -1))) return rc;
-
-  for (int j = 0; j < q; ++j) {
-    // the winner of step j is in dbest_*[0]; its values / PoF / MSE in the sweep's own arrays (step 0 without pending points) or the row buffers
-    const bool from_sweep = j == 0 && P == 0;
-    int64_t idx = 0;
-    HIPCHK(h, hipMemcpyAsync(&best_val[j], h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(&idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out + (size_t)j * M, from_sweep ? h->dacq_out : dacq_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (pof_out) HIPCHK(h, hipMemcpyAsync(pof_out + (size_t)j * M, from_sweep ? h->dpof_out : dpof_row, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out + (size_t)j * M * m, from_sweep ? h->dmse_out : dmse_row, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    best_idx[j] = idx;
-    if (idx < 0 || idx >= M) FAIL(h, BOGP_ERR_HIP, "%s: step %d returned row %lld outside [0, %lld)", who, j, (long long)idx, (long long)M);
-    HIPCHK(h, hipMemcpyAsync(hrow.data(), h->dXs + (size_t)idx * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(hmu.data(), h->dmu_out + (size_t)idx * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (best_x) memcpy(best_x + (size_t)j * d, hrow.data(), (size_t)d * sizeof(double));
-    if (best_mu) memcpy(best_mu + (size_t)j * m, hmu.data(), (size_t)m * sizeof(double));
-    if (j == q - 1) {
-      if (pivots && (rc = believe(hrow.data(), -1, false, false, idx))) return rc;
-      break;
-    }
-    believe_means(hmu.data());
-    if ((rc = believe(hrow.data(), j + 1, true, false, idx))) return rc;
-  }
-
-  HIPCHK(h, hipStreamSynchronize(st));
-  h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  if (n_pending == 0 && plugin_out) plugin_out[0] = plugin;
+  if ((rc = believer_run(h, f, q, pending, n_pending))) return rc;
   h->bel_con_ms = h->bel_timer.sum(B_CONSTRAINED);
   return BOGP_OK;
 }

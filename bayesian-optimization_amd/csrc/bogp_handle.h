@@ -282,17 +282,16 @@ struct bogp_handle {
   int64_t lift_n_feasible = 0;
   double lift_filter_ms = 0, lift_merge_ms = 0;
 
-  // Kriging-believer batches (bogp_api_believer.hip): the running variance and the stored c_k columns of the believed points
-  bogp::DevBuf<double> dbel_s;      // [M] sigma2 s_B(x), unclamped below the sweep's own clamp of s_0
+  // Kriging-believer batches (bogp_api_believer.hip): shared by its three families and laid out anew by every call -- the table above
+  // believer_run there states the three layouts
+  bogp::DevBuf<double> dbel_s;      // the running variances sigma2_k s_B(x)
   bogp::DevBuf<double> dbel_C;      // [slots][M] c_k(x) of the believed points whose pivot passed the guard
-  bogp::DevBuf<double> dbel_row;    // [2][M] criterion values / MSE of the step evaluated last
+  bogp::DevBuf<double> dbel_row;    // criterion values (PoF, k_believer's scratch) / MSE of the step evaluated last
   bogp::DevBuf<double> dbel_small;  // point, r(p), V r(p), R^-1 r(p), the believed rows and their mutual correlations
   bogp::SpanTimer bel_timer;        // solves, chunk producers, k_believer, k_believer_ehvi / k_believer_constrained (run_sweep restarts the sweep's own)
-  double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last bogp_sweep_believer: producer, solves, k_believer
+  double bel_corr_ms = 0, bel_solve_ms = 0, bel_pass_ms = 0;  // of the last believer call of any family: producer, solves, k_believer
   int bel_passes = 0;                                          // candidate passes it ran after pass 0
-  // bogp_sweep_believer_ehvi shares the arrays above (dbel_s is then [M][m], dbel_row [EHVI M | scratch M | MSE M x m]) and the times
   double bel_ehvi_ms = 0;  // k_believer_ehvi of the last bogp_sweep_believer_ehvi
-  // bogp_sweep_believer_constrained likewise (dbel_s [M][m], dbel_row [values M | PoF M | scratch M | MSE M x m])
   double bel_con_ms = 0;   // k_believer_constrained of the last bogp_sweep_believer_constrained
 
   // Thompson-sampling batches (bogp_api_thompson.hip)

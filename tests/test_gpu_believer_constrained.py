@@ -187,6 +187,42 @@ def test_step0_is_sweep_constrained_and_nothing_leaks(eng, N):
         np.testing.assert_array_equal(b_before[k], b_after[k], err_msg=k)
 
 
+def test_families_share_one_handle():
+    """`sweep_believer_ehvi`, `sweep_believer_constrained` and `sweep_believer_ehvi` again on ONE engine: the two families lay out the
+    handle's shared believer arrays (running variances, row buffers, columns, the solve's scratch, the cells) differently, and every
+    array of every call must equal the same call's on a freshly created engine -- nothing is sized or offset from the call before."""
+    X, Y, args, Xs, pend = problem(70, 2, _lib.KERNEL_MATERN52, False, rows=300)
+    lo, hi = quantile_bounds(Y)
+    plugin = plugin_of(Y, lo, hi, True)
+    rp = Y.min(axis=0) - 0.1 * np.abs(Y.min(axis=0))
+    ehvi = lambda e: e.sweep_believer_ehvi(Y[:24], rp, 3, pending=pend[:1], return_values=True)  # noqa: E731
+    constrained = lambda e: e.sweep_believer_constrained(ACQ_MIXED[:3], plugin, True, lo, hi, pending=pend[:1], return_values=True)  # noqa: E731
+
+    def engine():
+        e = _lib.Engine(0)
+        e.set_train(X, Y)
+        e.commit(*args)
+        e.upload_candidates(Xs)
+        return e
+
+    fresh = []
+    for call in (ehvi, constrained):
+        e = engine()
+        try:
+            fresh.append(call(e))
+        finally:
+            e.close()
+    e = engine()
+    try:
+        shared = [ehvi(e), constrained(e), ehvi(e)]
+    finally:
+        e.close()
+    for got, want in zip(shared, fresh + fresh[:1]):
+        assert sorted(got) == sorted(want)
+        for k in want:
+            np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+
+
 @pytest.mark.parametrize("minimize", [True, False], ids=["min", "max"])
 def test_infinite_bounds_give_the_single_target_believer(eng, minimize):
     """Every bound infinite and no feasibility-only step: P is exactly 1.0 on every row, so a value is its base criterion's bits on the

@@ -8,7 +8,8 @@ exactly when their listings agree line for line:
 
 The cases are the smallest that reach each branch of run_sweep (csrc/bogp_api_sweep.hip): the <= 32-row batch, the one-launch
 sweep, the chunk loop with its trend variants / two streams / lazy upload, the queued sweep, both pruned flows with their
-fall-backs, EHVI, the believer batches, Thompson batches and the lifted sweep.  Needs an MI355X."""
+fall-backs, EHVI, the believer batches of the three families (several chunks, one resident chunk, a guarded pivot in front of step 0),
+Thompson batches and the lifted sweep.  Needs an MI355X."""
 import argparse
 import collections
 import hashlib
@@ -176,6 +177,15 @@ def case_batches(_lib, np, rng, what):
         report(eng, "believer/q3", *[out[k] for k in sorted(out)])
         out = eng.sweep_believer(acq, float(y.min()), True, pending=rng.uniform(-5, 5, (2, 4)), return_values=True)
         report(eng, "believer/q3-pending", *[out[k] for k in sorted(out)])
+    elif what == "believer-constrained":  # m = 3: two constraints at inner quantiles; q = 3 with a feasibility-only step, without and with pending points
+        eng, X, y = smooth_model(_lib, rng, N, 4, targets=3)
+        eng.upload_candidates(rng.uniform(-5, 5, (M, 4)))
+        lo, hi = np.quantile(y[:, 1:], [0.25, 0.75], axis=0)
+        acq = [(_lib.ACQ_EI, 0.0), (_lib.ACQ_NONE, 0.0), (_lib.ACQ_MGFI, 2.0)]
+        out = eng.sweep_believer_constrained(acq, float(y[:, 0].min()), True, lo, hi, return_values=True)
+        report(eng, "believer-constrained/q3", *[out[k] for k in sorted(out)])
+        out = eng.sweep_believer_constrained(acq, float(y[:, 0].min()), True, lo, hi, pending=rng.uniform(-5, 5, (2, 4)), return_values=True)
+        report(eng, "believer-constrained/q3-pending", *[out[k] for k in sorted(out)])
     elif what == "thompson":  # conditioned, L = 64, q = 2, k = 1 and k = 3 (a noiseless model: the only mode it takes)
         d = 4
         X = rng.uniform(-2, 2, (N, d))
@@ -201,6 +211,39 @@ def case_batches(_lib, np, rng, what):
     eng.close()
 
 
+def case_guard(_lib, np, rng, what):
+    """The guarded pivot in front of step 0, as the three test_pivot_guard tests construct it: the last pending point is a training
+    row of a noiseless model (pivot <= 1e-12), the plugin / front held fixed.  One, two and three targets."""
+    N, M, d = 700, 3000, 4
+    X = rng.uniform(-2, 2, (N, d))
+    Y = np.sin(X @ rng.normal(size=(d, 3))) * (1.0 + np.arange(3)) + 0.3 * rng.normal(size=(N, 3))
+    Xs = rng.uniform(-2.2, 2.2, (M, d))
+    pend = np.vstack([rng.uniform(-2, 2, (1, d)), X[5]])
+    eng = _lib.Engine(0)
+
+    def commit(m):
+        eng.set_train(X, Y[:, :m])
+        eng.commit(_lib.KERNEL_MATERN52, _lib.MODE_NOISELESS, np.array([1.0, 0.8, 1.3, 1.1]) * 8.0, 0.0, m == 1, 0.1)
+        eng.upload_candidates(Xs)
+
+    def guarded(name, out):
+        assert out["pivots"][1] <= 1e-12, out["pivots"]
+        report(eng, name, *[out[k] for k in sorted(out)])
+
+    commit(1)
+    acq = [(_lib.ACQ_EI, 0.0), (_lib.ACQ_UCB, 2.0), (_lib.ACQ_EPSILON_PI, 1.5)]
+    guarded("believer/q3-guarded", eng.sweep_believer(acq, float(Y[:, 0].min()), True, pending=pend, believe_plugin=False, return_values=True))
+    commit(2)
+    front, rp = np.array([[-0.5, 0.3], [0.4, -0.6]]), np.array([-3.0, -3.0])
+    guarded("believer-ehvi/q2-guarded", eng.sweep_believer_ehvi(front, rp, 2, pending=pend, believe_front=False, return_values=True))
+    commit(3)
+    lo, hi = np.quantile(Y[:, 1:], [0.25, 0.75], axis=0)
+    acq = [(_lib.ACQ_EI, 0.0), (_lib.ACQ_NONE, 0.0), (_lib.ACQ_MGFI, 2.0)]
+    guarded("believer-constrained/q3-guarded",
+            eng.sweep_believer_constrained(acq, float(Y[:, 0].min()), True, lo, hi, pending=pend, believe_plugin=False, return_values=True))  # fmt: skip
+    eng.close()
+
+
 # name -> (function, argument, environment)
 CASES = collections.OrderedDict([
     ("small-batch", (case_small, "batch", {})),
@@ -213,6 +256,12 @@ CASES = collections.OrderedDict([
     ("pruned-large", (case_pruned, "large", {"BOGP_CHUNK_MB": "24"})),
     ("ehvi", (case_batches, "ehvi", {"BOGP_CHUNK_MB": "8"})),
     ("believer", (case_batches, "believer", {"BOGP_CHUNK_MB": "8"})),
+    ("believer-constrained", (case_batches, "believer-constrained", {"BOGP_CHUNK_MB": "8"})),
+    ("ehvi-one-chunk", (case_batches, "ehvi", {})),  # the believers again with every candidate in one chunk: the producer runs once
+    ("believer-one-chunk", (case_batches, "believer", {})),
+    ("believer-constrained-one-chunk", (case_batches, "believer-constrained", {})),
+    ("believer-guard", (case_guard, "", {"BOGP_CHUNK_MB": "8"})),
+    ("believer-guard-one-chunk", (case_guard, "", {})),
     ("thompson", (case_batches, "thompson", {"BOGP_CHUNK_MB": "8"})),
     ("lift", (case_batches, "lift", {"BOGP_CHUNK_MB": "8"})),
 ])  # fmt: skip
