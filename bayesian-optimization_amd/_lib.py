@@ -121,6 +121,10 @@ SIGNATURES = {
                                               _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "bogp_polish_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp,
                                           C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
+    "bogp_point_eval_ehvi_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp,
+                                                   _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "bogp_polish_ehvi_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp,
+                                               C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1260,6 +1264,48 @@ class Engine:
                                               float(acq[1]) if acq[1] is not None else 0.0, float(plugin), int(bool(minimize)), len(lo),
                                               _ptr(lo), _ptr(hi), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
                                               ne.ctypes.data_as(_ip))
+        )  # fmt: skip
+        return Xo, fo, ne
+
+    def _constrained_cells(self, lower, upper, lo, hi):
+        """The cells (C x m, C = 0: two empty (0, m) arrays) and the constraints' bounds of a constrained-EHVI point call, checked."""
+        lo, hi = self._constraint_bounds(lo, hi)
+        lower, upper = _f64(lower), _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape (C = 0: two empty (0, m) arrays)")
+        return lower, upper, lo, hi
+
+    def point_eval_ehvi_constrained(self, X, lower, upper, lo, hi, moments: bool = False):
+        """Feasibility-weighted EHVI of the committed multi-target model and its input gradient at the rows of `X` (B x d) in ONE device
+        round trip (bogp_point_eval_ehvi_constrained); cells and constraint bounds as `sweep_ehvi_constrained`: (val (B,), dval (B, d))
+        and, with `moments`, also pof (B,), dpof (B, d), ehvi (B,), dehvi (B, d), mu (B, m + c), mse (B, m + c), dmu (B, m + c, d),
+        dmse (B, m + c, d).  Cells equal to those of the call before are not uploaded again."""
+        X = self._rows(X)
+        lower, upper, lo, hi = self._constrained_cells(lower, upper, lo, hi)
+        C_, m = lower.shape
+        mt = m + len(lo)
+        B, d = X.shape[0], self.d
+        val, dval = np.empty(B), np.empty((B, d))
+        mom = ((np.empty(B), np.empty((B, d)), np.empty(B), np.empty((B, d)), np.empty((B, mt)), np.empty((B, mt)), np.empty((B, mt, d)),
+                np.empty((B, mt, d))) if moments else (None,) * 8)  # fmt: skip
+        rc = self._lib.bogp_point_eval_ehvi_constrained(self._h, _ptr(X), B, int(m), int(C_), _ptr(lower) if C_ else None,
+                                                        _ptr(upper) if C_ else None, len(lo), _ptr(lo), _ptr(hi), _ptr(val), _ptr(dval),
+                                                        *(_ptr(a) for a in mom))  # fmt: skip
+        if rc:
+            self._check(rc)
+        return (val, dval) + (mom if moments else ())
+
+    def polish_ehvi_constrained(self, starts, box_lo, box_hi, lower, upper, lo, hi, max_evals: int = 50, pgtol: float = 1e-8,
+                                factr: float = 1e6):
+        """Lock-step multi-start local maximisation of feasibility-weighted EHVI inside the box (bogp_polish_ehvi_constrained):
+        (points (B, d), values (B,), evaluations used (B,)); values[i] >= the criterion at starts[i] clipped into the box."""
+        X0, box_lo, box_hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), box_lo, box_hi, "box_lo / box_hi")
+        lower, upper, lo, hi = self._constrained_cells(lower, upper, lo, hi)
+        C_, m = lower.shape
+        self._check(
+            self._lib.bogp_polish_ehvi_constrained(self._h, _ptr(X0), B, _ptr(box_lo), _ptr(box_hi), int(m), int(C_),
+                                                   _ptr(lower) if C_ else None, _ptr(upper) if C_ else None, len(lo), _ptr(lo), _ptr(hi),
+                                                   int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))
         )  # fmt: skip
         return Xo, fo, ne
 

@@ -543,8 +543,14 @@ class ConstrainedEHVI:
     decomposition.
 
     `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the engine's
-    current candidates as `EHVI.sweep` does.  There is no input gradient (`return_dx=True` raises) and no batch strategy; the sweep
-    helpers serve it where they serve `EHVI`: alone in its sweep, on one rank."""
+    current candidates as `EHVI.sweep` does.  By default there is no input gradient (`return_dx=True` raises); there is no batch
+    strategy; the sweep helpers serve it where they serve `EHVI`: alone in its sweep, on one rank.
+
+    `input_gradient=True` (an extension): `criterion(X, return_dx=True)` returns (values, dx) in the shapes
+    `EHVI(input_gradient=True)` returns -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through
+    `bogp_point_eval_ehvi_constrained` (EHVI's gradient and the gradient of the probability of feasibility multiplied on the device;
+    a feasibility-only criterion has the gradient of that probability), `criterion(X)` for at most 64 rows takes the same call, and
+    `argmax_restart` serves "BFGS", "sweep-BFGS" and "sweep-device-BFGS" for it."""
 
     is_ehvi = True  # (the sweep helpers serve it through `.sweep()`, as they serve EHVI)
     is_constrained_ehvi = True  # ... and everything that does more than call `.sweep()` asks for this flag first
@@ -552,9 +558,10 @@ class ConstrainedEHVI:
     input_gradient = False
     minimize = False  # (the sweep helpers read it off every criterion)
 
-    def __init__(self, model=None, ref_point=None, lo=None, hi=None, Y=None, cells=None):
+    def __init__(self, model=None, ref_point=None, lo=None, hi=None, Y=None, cells=None, input_gradient: bool = False):
         if model is None:
             raise ValueError("model cannot be None")
+        self.input_gradient = bool(input_gradient)
         if _forest.is_forest_model(model):
             raise NotImplementedError("constrained EHVI (bogp.ConstrainedEHVI) takes a multi-target Gaussian process: a forest model is not served")
         if ref_point is None:
@@ -621,10 +628,20 @@ class ConstrainedEHVI:
                                                         return_values=return_values)  # fmt: skip
 
     def __call__(self, X, return_dx: bool = False):
-        if return_dx:
+        if return_dx and not self.input_gradient:
             raise NotImplementedError("constrained EHVI (bogp.ConstrainedEHVI) has no input gradient: use 'sweep' or "
                                       "'sweep-device[-lhs|-sobol]'")  # fmt: skip
         if getattr(self.model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
+        if self.input_gradient:
+            rows = self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float)))
+            if return_dx or len(rows) <= 64:  # value and gradient in one device round trip (bogp_point_eval_ehvi_constrained)
+                eng = self.model.engine
+                if not hasattr(eng, "point_eval_ehvi_constrained"):
+                    raise NotImplementedError("the model's engine has no point_eval_ehvi_constrained: no input gradient of constrained EHVI")
+                vals, dx = eng.point_eval_ehvi_constrained(rows, self.cell_lower_bounds, self.cell_upper_bounds, self.lo, self.hi)[:2]
+                if not return_dx:
+                    return vals
+                return (vals.reshape(1), dx.reshape(1, -1)) if len(rows) == 1 else (vals.reshape(-1, 1), dx)
         self.model.engine.upload_candidates(self.model._check_X(np.atleast_2d(np.asarray(X, dtype=float))))
         return self.sweep(return_values=True)[2]

@@ -809,5 +809,28 @@ struct PointConstrainedArgs {
   unsigned long long done_seq;
 };
 hipError_t launch_point_constrained_finish(const PointConstrainedArgs& a, int B, hipStream_t st);
+// feasibility-weighted EHVI and its input gradient at B points of an (m_obj + n_con)-target model (kernels_point_ehvi_constrained.hip): the
+// finishing kernel behind k_point_rhs + k_point_tri (VALU flavour) in place of k_point_finish; targets 0 .. m_obj - 1 the objectives of
+// the cells, target m_obj + j the constraint feasible in [lo[j], hi[j]] (ConstrainedEhviArgs' convention).  The fields stand in the
+// order the kernel reads them (sums, moments, constraints, cells, records), as ConstrainedEhviArgs' do.
+struct PointEhviConstrainedArgs {
+  const double* part;   // [B][npass][nRB + 1][2 NC] block records of k_point_tri
+  const double* rhs;    // [B][npass][Npp][NC] right-hand sides of k_point_rhs
+  const double* gamma;  // [m][ld_gamma] the targets' gamma columns (gamma_base)
+  int ld_gamma, N, Npp, nRB, npass, d;
+  int m, m_obj, estimate_trend;
+  double beta, G, ftft;
+  double sigma2[8];     // per target
+  double lo[8], hi[8];  // per constraint: target m_obj + j
+  const double* lower;  // [C][m_obj] cell bounds (device), or null for C == 0
+  const double* upper;  // [C][m_obj] (+inf allowed)
+  int C;                // 0: the probability of feasibility alone
+  int rec_stride, mom_stride;
+  double* out;          // [B][rec_stride]: mu_0, MSE_0, value, dmu_0 (d), dMSE_0 (d), dvalue (d) -- k_point_finish's record with q = 1
+  double* mom;          // [B][mom_stride]: P, dP (d), E, dE (d), mu (m), MSE (m), dmu (m x d), dMSE (m x d), or null
+  unsigned long long* done_flag;  // as PointTriArgs
+  unsigned long long done_seq;
+};
+hipError_t launch_point_ehvi_constrained_finish(const PointEhviConstrainedArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

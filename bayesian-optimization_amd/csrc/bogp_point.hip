@@ -1,7 +1,8 @@
 // bogp_point.hip -- C ABI of the one-point / B-point consumption path (kernels_point.hip): bogp_point_eval,
 // bogp_point_eval_batch, bogp_gradient_batch, bogp_polish, and of its multi-objective finish (kernels_point_ehvi.hip):
 // bogp_point_eval_ehvi, bogp_polish_ehvi, and of its feasibility-weighted finish (kernels_point_constrained.hip):
-// bogp_point_eval_constrained, bogp_polish_constrained.  See include/bogp.h for the contracts.
+// bogp_point_eval_constrained, bogp_polish_constrained, and of the product of the two (kernels_point_ehvi_constrained.hip):
+// bogp_point_eval_ehvi_constrained, bogp_polish_ehvi_constrained.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -59,8 +60,8 @@ int ensure_tickets(bogp_handle* h, DevBuf<unsigned int>& c, size_t n) {
 int ensure_counters(bogp_handle* h, size_t n) { return ensure_tickets(h, h->dpt_counter, n); }
 
 // What one evaluation computes at each of its points, whichever entry asks: q criteria and -- want_dacq -- their input gradients behind
-// k_point_finish, or the finish of an m-target model in its place (at most one of eh / cn; they hold what that family alone knows: cells
-// and targets, or criteria and bounds).  The record then keeps k_point_finish's layout for q criteria, which EHVI fills like ONE.
+// k_point_finish, or the finish of an m-target model in its place (at most one of eh / cn / ec; they hold what that family alone knows:
+// cells and targets, or criteria and bounds, or cells and bounds).  The record then keeps k_point_finish's layout for q criteria, which EHVI fills like ONE.
 struct PointCall {
   int q;
   const int* acq_id;
@@ -70,13 +71,19 @@ struct PointCall {
   bool want_dacq;
   const PointEhviArgs* eh;
   const PointConstrainedArgs* cn;
+  const PointEhviConstrainedArgs* ec;
   size_t mom_stride;  // doubles per point of the m-target finishes' second block, written behind the B records; 0: not wanted
 };
 
 // the EHVI request: a record sized like one criterion's with its gradient (the id itself is not evaluated)
 PointCall ehvi_call(const PointEhviArgs* eh, size_t mom_stride) {
   static const int one_id = BOGP_ACQ_EI;
-  return PointCall{1, &one_id, nullptr, 0.0, 0, true, eh, nullptr, mom_stride};
+  return PointCall{1, &one_id, nullptr, 0.0, 0, true, eh, nullptr, nullptr, mom_stride};
+}
+// ... and the constrained-EHVI request, sized the same way
+PointCall ehvi_constrained_call(const PointEhviConstrainedArgs* ec, size_t mom_stride) {
+  static const int one_id = BOGP_ACQ_EI;
+  return PointCall{1, &one_id, nullptr, 0.0, 0, true, nullptr, nullptr, ec, mom_stride};
 }
 
 // the criterion block of PointTriArgs, for k_point_finish and its MFMA flavour alike
@@ -89,8 +96,8 @@ void fill_criteria(const bogp_handle* h, const PointPlan& pl, const PointCall& c
   a->done_flag = done_flag; a->done_seq = done_seq;
 }
 
-// the arguments of an m-target finish: `a` arrives with its family's own fields and leaves with those PointEhviArgs and
-// PointConstrainedArgs share (the ones point_multi_sums reads, the second block and the done word)
+// the arguments of an m-target finish: `a` arrives with its family's own fields and leaves with those PointEhviArgs,
+// PointConstrainedArgs and PointEhviConstrainedArgs share (the ones point_multi_sums reads, the second block and the done word)
 template <class Args>
 Args multi_finish_args(const bogp_handle* h, const PointPlan& pl, Args a, int B, size_t mom_stride, double* out, unsigned long long* done_flag,
                        unsigned long long done_seq) {
@@ -117,7 +124,7 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, co
   const int ncp = point_mfma_columns(h->d);
   const char* e_min = getenv("BOGP_POINT_MFMA_MIN");  // read per call: the tests run both flavours in one process
   const long long mfma_min = e_min ? atoll(e_min) : 768LL;
-  if (!c.eh && !c.cn && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
+  if (!c.eh && !c.cn && !c.ec && dXb && ncp > 0 && h->dVp && h->p == 1 && mfma_min > 0 && (((long long)B * ncp + 63) / 64) * ((h->Np + 255) / 256) >= mfma_min) {
     const int Np = h->Np, nJ = (Np + 255) / 256;
     const long long Mc = ((long long)B * ncp + 63) / 64 * 64;
     if ((e = h->drT[0].ensure(h, (size_t)Np * Mc))) return e;
@@ -168,14 +175,15 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, co
   ta.ld = h->ldr; ta.Npp = pl.Npp; ta.Nr32 = pl.Nr32; ta.nRB = pl.nRB; ta.npass = pl.npass; ta.d = h->d;
   fill_criteria(h, pl, c, done_flag, done_seq, &ta);
   ta.trend_rec = trend_rec;
-  HIPCHK(h, launch_point_tri(ta, B, st, !c.eh && !c.cn));  // an m-target finish takes k_point_finish's place
+  HIPCHK(h, launch_point_tri(ta, B, st, !c.eh && !c.cn && !c.ec));  // an m-target finish takes k_point_finish's place
   if (c.eh) HIPCHK(h, launch_point_ehvi_finish(multi_finish_args(h, pl, *c.eh, B, c.mom_stride, out, done_flag, done_seq), B, st));
   if (c.cn) HIPCHK(h, launch_point_constrained_finish(multi_finish_args(h, pl, *c.cn, B, c.mom_stride, out, done_flag, done_seq), B, st));
+  if (c.ec) HIPCHK(h, launch_point_ehvi_constrained_finish(multi_finish_args(h, pl, *c.ec, B, c.mom_stride, out, done_flag, done_seq), B, st));
   return BOGP_OK;
 }
 
 // the lock-step polish of B starts with the evaluation of `call` (one criterion and its gradient: q = 1) queued every iteration:
-// the loop of bogp_polish, bogp_polish_ehvi and bogp_polish_constrained
+// the loop of bogp_polish, bogp_polish_ehvi, bogp_polish_constrained and bogp_polish_ehvi_constrained
 int polish_loop(bogp_handle* h, const char* who, const PointCall& call, const double* X0, int B, const double* lo, const double* hi,
                 int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals) {
   int e;
@@ -362,7 +370,7 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
   HIPCHK(h, hipSetDevice(h->device));
   const int d = h->d;
   const bool want_dacq = dacq != nullptr && q > 0;
-  const PointCall call{q, acq_id, acq_par, plugin, minimize, want_dacq, nullptr, nullptr, 0};
+  const PointCall call{q, acq_id, acq_par, plugin, minimize, want_dacq, nullptr, nullptr, nullptr, 0};
   return point_eval_chunks(h, call, Xb, B, [=](size_t b, const double* o, const double*) {
     if (mu) mu[b] = o[0];
     if (mse) mse[b] = o[1];
@@ -402,7 +410,7 @@ extern "C" int bogp_polish(bogp_handle* h, const double* X0, int B, const double
   if (!h) return BOGP_ERR_INVALID;
   int e = check_common(h, "bogp_polish", 1, &acq_id, &acq_par);
   if (e) return e;
-  const PointCall call{1, &acq_id, &acq_par, plugin, minimize, true, nullptr, nullptr, 0};
+  const PointCall call{1, &acq_id, &acq_par, plugin, minimize, true, nullptr, nullptr, nullptr, 0};
   return polish_loop(h, "bogp_polish", call, X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }
 
@@ -480,7 +488,7 @@ extern "C" int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int
   fill_constrained(h, &cn, q, acq_id, acq_par, plugin, minimize, n_con, lo, hi);
   const bool want_mom = pof || dpof || mu || mse || dmu || dmse;
   const size_t md = (size_t)m * d;
-  const PointCall call{q, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, want_mom ? 1 + d + 2 * m + 2 * md : 0};
+  const PointCall call{q, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, nullptr, want_mom ? 1 + d + 2 * m + 2 * md : 0};
   return point_eval_chunks(h, call, Xb, B, [=](size_t b, const double* o, const double* mom) {
     memcpy(acq + b * q, o + 2, (size_t)q * sizeof(double));
     if (dacq) memcpy(dacq + b * q * d, o + 2 + q + 2 * d, (size_t)q * d * sizeof(double));
@@ -504,6 +512,76 @@ extern "C" int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, 
   if (e) return e;
   PointConstrainedArgs cn;
   fill_constrained(h, &cn, 1, &acq_id, &acq_par, plugin, minimize, n_con, lo, hi);
-  const PointCall call{1, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, 0};
+  const PointCall call{1, cn.acq_id, cn.acq_par, plugin, minimize, true, nullptr, &cn, nullptr, 0};
   return polish_loop(h, who, call, X0, B, box_lo, box_hi, max_evals, pgtol, factr, Xout, fout, n_evals);
+}
+
+// ---- feasibility-weighted EHVI and its input gradient at B points of the committed (m_obj + n_con)-target model (kernels_point_ehvi_constrained.hip) ----
+// what bogp_point_eval_ehvi_constrained and bogp_polish_ehvi_constrained refuse alike, in bogp_sweep_ehvi_constrained's words where it
+// refuses the same; then the cells on the device (ehvi_cells_resident with m = m_obj: a repeated call skips check and upload) and the request
+static int ehvi_constrained_request(bogp_handle* h, const char* who, int m_obj, int C, const double* lower, const double* upper, int n_con,
+                                    const double* lo, const double* hi, PointEhviConstrainedArgs* ec) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest; modelled constraints take a multi-target Gaussian process", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (int e = check_multi_model(h, who)) return e;
+  const int m = h->n_t;
+  if (m_obj < 2) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj = %d objectives; EHVI needs at least 2", who, m_obj);
+  if (n_con < 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d constraints; without one this is the EHVI call", who, n_con);
+  if (m > BOGP_MAX_TARGETS || m_obj + n_con != m) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj + n_con = %d + %d but the committed model has %d targets (at most %d)", who, m_obj, n_con, m, BOGP_MAX_TARGETS);
+  if (C < 0 || C > BOGP_MAX_EHVI_CELLS) FAIL(h, BOGP_ERR_INVALID, "%s: C = %d cells outside [0, %d]", who, C, BOGP_MAX_EHVI_CELLS);
+  if (!lo || !hi) FAIL(h, BOGP_ERR_INVALID, "%s: lo and hi must be non-null", who);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  for (int j = 0; j < n_con; ++j) {
+    if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
+    if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
+  }
+  if (C > 0)
+    if (int e = ehvi_cells_resident(h, who, m_obj, C, lower, upper)) return e;
+  memset(ec, 0, sizeof(*ec));
+  ec->m = m; ec->m_obj = m_obj; ec->C = C;
+  if (C > 0) { ec->lower = h->dehvi_cells; ec->upper = h->dehvi_cells + (size_t)C * m_obj; }
+  for (int j = 0; j < n_con; ++j) { ec->lo[j] = lo[j]; ec->hi[j] = hi[j]; }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_point_eval_ehvi_constrained(bogp_handle* h, const double* Xb, int B, int m_obj, int C, const double* lower, const double* upper,
+                                                int n_con, const double* lo, const double* hi, double* val, double* dval, double* pof, double* dpof,
+                                                double* ehvi, double* dehvi, double* mu, double* mse, double* dmu, double* dmse) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_ehvi_constrained";
+  if (!Xb || !val || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null points, null val or B <= 0", who);
+  PointEhviConstrainedArgs ec;
+  int e = ehvi_constrained_request(h, who, m_obj, C, lower, upper, n_con, lo, hi, &ec);
+  if (e) return e;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int d = h->d, m = h->n_t;
+  const bool want_mom = pof || dpof || ehvi || dehvi || mu || mse || dmu || dmse;
+  const size_t md = (size_t)m * d;
+  return point_eval_chunks(h, ehvi_constrained_call(&ec, want_mom ? 2 + 2 * d + 2 * m + 2 * md : 0), Xb, B,
+                           [=](size_t b, const double* o, const double* mom) {
+    val[b] = o[2];
+    if (dval) memcpy(dval + b * d, o + 3 + 2 * d, (size_t)d * sizeof(double));
+    if (!want_mom) return;
+    if (pof) pof[b] = mom[0];
+    if (dpof) memcpy(dpof + b * d, mom + 1, (size_t)d * sizeof(double));
+    if (ehvi) ehvi[b] = mom[1 + d];
+    if (dehvi) memcpy(dehvi + b * d, mom + 2 + d, (size_t)d * sizeof(double));
+    mom += 2 + 2 * d;
+    if (mu) memcpy(mu + b * m, mom, (size_t)m * sizeof(double));
+    if (mse) memcpy(mse + b * m, mom + m, (size_t)m * sizeof(double));
+    if (dmu) memcpy(dmu + b * md, mom + 2 * m, md * sizeof(double));
+    if (dmse) memcpy(dmse + b * md, mom + 2 * m + md, md * sizeof(double));
+  });
+}
+
+extern "C" int bogp_polish_ehvi_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int m_obj, int C,
+                                            const double* lower, const double* upper, int n_con, const double* lo, const double* hi, int max_evals,
+                                            double pgtol, double factr, double* Xout, double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_ehvi_constrained";
+  if (!X0 || !box_lo || !box_hi || !Xout || !fout || B <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer or B <= 0", who);
+  PointEhviConstrainedArgs ec;
+  int e = ehvi_constrained_request(h, who, m_obj, C, lower, upper, n_con, lo, hi, &ec);
+  if (e) return e;
+  return polish_loop(h, who, ehvi_constrained_call(&ec, 0), X0, B, box_lo, box_hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }

@@ -29,17 +29,11 @@ namespace bogp {
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_fixed(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_f64(v, m);
-  return v;
-}
-
 template <int MT, int NC>
 __global__ __launch_bounds__(256) void k_point_ehvi_finish(PointEhviArgs a) {
   constexpr int NV = 2 * MT + 1;          // value | dEHVI/dmu_k | dEHVI/dsd_k
   extern __shared__ double dyn[];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x, d = a.d, npass = a.npass;
   double* dots = dyn;                            // [npass][NC][MT] gamma_k . rhs_c
   double* zdr = dots + (size_t)npass * NC * MT;  // [d] z . dr/dx_i
@@ -58,51 +52,10 @@ __global__ __launch_bounds__(256) void k_point_ehvi_finish(PointEhviArgs a) {
 #pragma unroll
   for (int k = 0; k < MT; ++k) sd[k] = sqrt(fmax(mse[k], 1e-9));
 
-  // 4. the cells
+  // 4. the cells and their fixed-order reduction (bogp_point_multi.h, shared with k_point_ehvi_constrained_finish)
   double acc[NV];
-#pragma unroll
-  for (int t = 0; t < NV; ++t) acc[t] = 0.0;
-  for (int c = tid; c < a.C; c += 256) {
-    double f[MT], fm[MT], fs[MT];
-#pragma unroll
-    for (int k = 0; k < MT; ++k) {
-      const double l = a.lower[(size_t)c * MT + k], u = a.upper[(size_t)c * MT + k];
-      const double za = (l - mu[k]) / sd[k];
-      const double pa = norm_pdf(za), ca = ndtr(-za);
-      double g = pa - za * ca, dm = ca, ds = pa;
-      if (!isinf(u)) {
-        const double zb = (u - mu[k]) / sd[k];
-        const double pb = norm_pdf(zb), cb = ndtr(-zb);
-        g -= pb - zb * cb;
-        dm -= cb;
-        ds -= pb;
-      }
-      f[k] = sd[k] * g;
-      fm[k] = dm;
-      fs[k] = ds;
-    }
-    double pre[MT];  // pre[k] = prod_{j < k} f_j
-    pre[0] = 1.0;
-#pragma unroll
-    for (int k = 1; k < MT; ++k) pre[k] = pre[k - 1] * f[k - 1];
-    acc[0] += pre[MT - 1] * f[MT - 1];
-    double suf = 1.0;  // prod_{j > k} f_j
-#pragma unroll
-    for (int k = MT - 1; k >= 0; --k) {
-      const double others = pre[k] * suf;
-      acc[1 + k] += others * fm[k];
-      acc[1 + MT + k] += others * fs[k];
-      suf *= f[k];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < NV; ++t) {
-    const double s = wave_sum_fixed(acc[t]);
-    if (lane == 0) red[wv][t] = s;
-  }
-  __syncthreads();
-  if (tid < NV) coef[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-  __syncthreads();
+  point_ehvi_cell_sums<MT, MT>(a.lower, a.upper, a.C, mu, sd, acc);
+  point_ehvi_reduce<NV>(acc, red, coef);
 
   // 5. the record(s)
   double* out = a.out + (size_t)b * a.rec_stride;  // [mu_0, MSE_0, EHVI, dmu_0 (d), dMSE_0 (d), dEHVI (d)]

@@ -156,11 +156,18 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
         if not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(getattr(self, "search_space", None)):
             raise NotImplementedError("expensive constraints of a multi-objective run (bogp.ConstrainedEHVI) take a device GaussianProcess on "
                                       "a continuous search space; the constraint values are not dropped silently")  # fmt: skip
+        lo, hi = _constraint_bounds(self)
+        if _CONSTRAINTS.get("mobo_gradient") and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS"):
+            # install(constrained_mobo_gradient=True): the criterion with its input gradient; return_dx bound as the ehvi_gradient branch binds it
+            criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi,
+                                                    input_gradient=True)  # fmt: skip
+            return_dx = optimizer == "BFGS"
+            return _ORIGINAL["partial_argument"](functools.partial(criterion, return_dx=return_dx), self.search_space.var_name, fixed,
+                                                 reduce_output=return_dx)  # fmt: skip
         if optimizer not in _SWEEPS:
             raise NotImplementedError("optimizer=%r under expensive constraints of a multi-objective run: constrained EHVI "
                                       "(bogp.ConstrainedEHVI) is served by the sweep family only %s; the constraint values are not dropped "
                                       "silently" % (optimizer, _SWEEPS))  # fmt: skip
-        lo, hi = _constraint_bounds(self)
         criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
         return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
     if getattr(self, "_optimizer", None) in ("sweep", "sweep-device") and _forest.is_forest_model(getattr(self, "model", None)):
@@ -619,7 +626,8 @@ def _dispatching_surrogate(host_cls):
 
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
-            equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False):
+            equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
+            constrained_mobo_gradient: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -673,9 +681,16 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     (`constrained_mobo_update_model`) and maximises `bogp.ConstrainedEHVI` -- EHVI over the cells of the feasible front times the
     probability that g <= 0 and |h| <= `equality_tol` -- under the sweep family on a continuous space; any other inner optimiser and
     `MOBO(n_point=q)` raise instead of dropping the constraints.  `bogp.feasible_front(bo)` is the feasible non-dominated set.  Without
-    it a MOBO tell() with constraint values is refused by name as before."""
+    it a MOBO tell() with constraint values is refused by name as before.
+
+    `constrained_mobo_gradient=True` (with `constrained_mobo=True`; without it ValueError): such a MOBO also accepts "BFGS", "sweep-BFGS"
+    and "sweep-device-BFGS" after a tell() that carried constraint values and maximises `bogp.ConstrainedEHVI(input_gradient=True)` --
+    the input gradient of `bogp_point_eval_ehvi_constrained` and the lock-step polish `bogp_polish_ehvi_constrained`.  Without it
+    those optimisers raise as before."""
     if constrained_mobo and not expensive_constraints:
         raise ValueError("constrained_mobo=True needs expensive_constraints=True (it keeps the h_vals / g_vals of a multi-objective tell())")
+    if constrained_mobo_gradient and not constrained_mobo:
+        raise ValueError("constrained_mobo_gradient=True needs constrained_mobo=True (it is the input gradient of constrained EHVI)")
     if constraint_batches not in ("topk", "believer"):
         raise ValueError("constraint_batches must be 'topk' or 'believer', not %r" % (constraint_batches,))
     if constraint_batches == "believer" and not expensive_constraints:
@@ -693,6 +708,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["batches"] = "believer"
         if constrained_mobo:
             _CONSTRAINTS["mobo"] = True
+        if constrained_mobo_gradient:
+            _CONSTRAINTS["mobo_gradient"] = True
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

@@ -865,7 +865,9 @@ def argmax_restart(
     `input_gradient=True`: then "BFGS" is the loop on `bogp_point_eval_constrained` and the hybrids polish the sweep's best rows with
     `bogp_polish_constrained`; fixed variables, cheap callables h / g, a lift and several ranks are refused by name.
     A `bogp.ConstrainedEHVI` criterion is served under "sweep" and "sweep-device[-lhs|-sobol]" through `bogp_sweep_ehvi_constrained`;
-    every other optimiser, fixed variables, cheap callables h / g, a lift and several ranks are refused by name.
+    built with `input_gradient=True` also under "BFGS" (the loop on `bogp_point_eval_ehvi_constrained`) and the hybrids (the sweep's
+    best rows polished with `bogp_polish_ehvi_constrained`); every other optimiser, fixed variables, cheap callables h / g, a lift and
+    several ranks are refused by name.
     Anything else ("MIES", "OnePlusOne_Cholesky_CMA", constraints under "BFGS", a non-continuous space) is the
     reference's own business: the call is handed to its `argmax_restart` when `bayes_optim` is importable, for which a
     bogp criterion is an ordinary callable; without the reference, NotImplementedError.
@@ -878,8 +880,11 @@ def argmax_restart(
         # a forest model (any space of Real / Integer / Ordinal / Discrete / Subset / Bool variables): "sweep" and "sweep-device"
         # are served, everything else this package knows is refused with the limitation named
         return _forest.argmax_restart(fcrit, search_space, eval_budget, optimizer, h=h, g=g, masks=fmasks)
-    if is_constrained_ehvi(fcrit):  # served under "sweep" and "sweep-device[-lhs|-sobol]" alone; nothing else may drop its constraints
-        if optimizer not in DEVICE_DESIGNS and optimizer != "sweep":
+    if is_constrained_ehvi(fcrit):  # served under "sweep" and "sweep-device[-lhs|-sobol]"; nothing else may drop its constraints
+        # ConstrainedEHVI(input_gradient=True): "BFGS" is the loop below on the one-point call (bogp_point_eval_ehvi_constrained), the
+        # hybrids are crit.sweep(k) + polish_topk (bogp_polish_ehvi_constrained)
+        polishes = getattr(fcrit, "input_gradient", False) and optimizer in ("BFGS", "sweep-BFGS", "sweep-device-BFGS")
+        if optimizer not in DEVICE_DESIGNS and optimizer != "sweep" and not polishes:
             raise NotImplementedError("optimizer=%r for %s: it has no input gradient and no polish; use 'sweep' or "
                                       "'sweep-device[-lhs|-sobol]'" % (optimizer, _CEHVI))  # fmt: skip
         if not is_continuous(search_space):
@@ -1019,7 +1024,8 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
     """Local refinement of `starts` (k, d) inside the box `bounds` (d, 2); returns (points (k, d), values (k,)) with
     values[i] >= the criterion at starts[i].  On the device engine all k starts advance in lock step (`bogp_polish`:
     one batched value + gradient evaluation per iteration, the optimiser state never leaves the GPU; an EHVI criterion built
-    with `input_gradient=True` goes to `bogp_polish_ehvi`, a Constrained one to `bogp_polish_constrained`) -- the reference
+    with `input_gradient=True` goes to `bogp_polish_ehvi`, a Constrained one to `bogp_polish_constrained`, a ConstrainedEHVI one to
+    `bogp_polish_ehvi_constrained`) -- the reference
     runs its restarts one after the other, one point per call (optim/__init__.py:74-153).  An engine without `polish`
     (the test stand-ins) or a model the fused call does not serve (polynomial trend basis) gets the reference-style
     sequential L-BFGS-B through the one-point call."""
@@ -1028,9 +1034,15 @@ def polish_topk(crit, starts: np.ndarray, bounds: np.ndarray, max_iter: int = 50
     model = crit.model
     eng = getattr(model, "engine", None)
     fused = getattr(model, "_fused_point_ok", None)
-    if is_constrained_ehvi(crit):
+    if is_constrained_ehvi(crit) and not getattr(crit, "input_gradient", False):
         raise NotImplementedError("%s has no polish: bogp_polish_ehvi knows the objectives only and would drop the constraints" % _CEHVI)
-    if is_ehvi(crit) and eng is not None and hasattr(eng, "polish_ehvi"):  # EHVI(input_gradient=True): bogp_polish_ehvi
+    if is_constrained_ehvi(crit) and eng is not None and hasattr(eng, "polish_ehvi_constrained"):  # ConstrainedEHVI(input_gradient=True)
+        if getattr(model, "_committed_par", None) is None:
+            raise Exception("The model is not fitted yet!")
+        xs, fs, _ = eng.polish_ehvi_constrained(model._check_X(starts), bounds[:, 0], bounds[:, 1], crit.cell_lower_bounds,
+                                                crit.cell_upper_bounds, crit.lo, crit.hi, max_evals=int(max_iter))  # fmt: skip
+        return xs, fs
+    if is_ehvi(crit) and not is_constrained_ehvi(crit) and eng is not None and hasattr(eng, "polish_ehvi"):  # EHVI(input_gradient=True): bogp_polish_ehvi
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
         xs, fs, _ = eng.polish_ehvi(model._check_X(starts), bounds[:, 0], bounds[:, 1], crit.cell_lower_bounds, crit.cell_upper_bounds,

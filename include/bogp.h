@@ -711,6 +711,43 @@ int bogp_point_eval_constrained(bogp_handle* h, const double* Xb, int B, int q, 
 int bogp_polish_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int acq_id, double acq_par,
                             double plugin, int minimize, int n_con, const double* lo, const double* hi, int max_evals, double pgtol,
                             double factr, double* Xout, double* fout, int* n_evals);
+/* The criterion of bogp_sweep_ehvi_constrained AND its input gradient at B points of the committed (m_obj + n_con)-target model, and the
+ * lock-step polish on it (an extension: BaseMOBO.tell leaves constraint values as a TODO, mobo.py:117-118).  k_point_rhs + k_point_tri
+ * run as for bogp_point_eval_ehvi (FP64 VALU flavour for every B); k_point_ehvi_constrained_finish
+ * (csrc/kernels_point_ehvi_constrained.hip) then forms the moments of all targets as its two siblings do -- mu_k, MSE_k = sigma2_k
+ * (1 - |V r|^2 + u^2) clipped at 0, dmu_k/dx = gamma_k . dr/dx, dMSE_k/dx = sigma2_k ds/dx -- and, with targets 0 .. m_obj - 1 the
+ * objectives (maximised as given) and target m_obj + j the constraint feasible in [lo_j, hi_j]:
+ *   objectives   sd_k = sqrt(max(MSE_k, 1e-9)); dsd_k/dx = dMSE_k/dx / (2 sd_k) where MSE_k > 1e-9 and exactly 0 otherwise
+ *   constraints  sd_k = sqrt(MSE_k) without a floor;  F_j, dF_j/dmu, dF_j/dsd = bogp_feasibility_grad(mu, MSE, sigma2, lo_j, hi_j)
+ *   P = F_0 * ... * F_{n_con-1} (this order, from 1.0);  dP/dx = sum_j (prod_{l != j} F_l) (dF_j/dmu dmu/dx + dF_j/dsd dsd/dx)
+ *   E, dE/dmu_k, dE/dsd_k over the C cells of the objectives as bogp_point_eval_ehvi;  dE/dx = sum_{k < m_obj} (dE/dmu_k dmu_k/dx + dE/dsd_k dsd_k/dx)
+ *   P == 0.0:   value = +0.0 exactly, gradient 0 in every component (by definition, as in the sweep; the cells are not read)
+ *   C == 0:     value = P,   gradient dP/dx
+ *   otherwise:  value = E P, gradient (P != 0 ? P dE/dx : 0) + (E != 0 ? E dP/dx : 0)
+ * The products over l != j come from prefix and suffix products, never from a division; a zero coefficient times anything is 0.  A NaN
+ * P is not == 0 and propagates; a gradient is never NaN where the value is finite.  The values agree with bogp_sweep_ehvi_constrained's
+ * to rounding (the summation orders differ); identical inputs give identical bits, and row b of a B-point call equals the one-point
+ * call on that row whenever both run the same row-block split (csrc/kernels_point.hip: point_tri_geometry).
+ *   m_obj, C, lower, upper, n_con, lo, hi   as bogp_sweep_ehvi_constrained: 0 <= C <= BOGP_MAX_EHVI_CELLS, lower / upper C x m_obj and
+ *                        may be NULL for C == 0.  Cells equal to those this path left on the device -- same m_obj, C and bytes -- are not
+ *                        checked or uploaded again (the BFGS loop makes thousands of one-point calls over one front).
+ *   `point_eval_ehvi_constrained`  Xb: B x d (host).  Outputs, row-major, any but val may be NULL: val (B), dval (B x d), pof (B),
+ *                        dpof (B x d), ehvi (B), dehvi (B x d) -- both 0 where P == 0 or C == 0: the cells were not read --, mu, mse
+ *                        (B x m), dmu, dmse (B x m x d), m = m_obj + n_con.
+ *   `polish_ehvi_constrained`  bogp_polish's loop, state, stop rules and read-back on this evaluation: X0, box_lo, box_hi (the box),
+ *                        max_evals, pgtol, factr, Xout, fout, n_evals as there; a start never moves to a worse point, Xout lies in the
+ *                        box and fout[b] >= value(clip(X0[b])).
+ * BOGP_ERR_INVALID: no committed model, m_obj < 2, n_con < 1, m_obj + n_con != n_targets, C out of range, a cell bound that is not
+ * finite (lower), NaN or below its lower bound (upper), a NaN constraint bound, hi < lo, a null required pointer, B <= 0,
+ * box_lo > box_hi, max_evals <= 0.  BOGP_ERR_UNSUPPORTED: the cubic, generalized-exponential and general-nu kernels (no corr_dx); a
+ * polynomial basis; d > BOGP_MAX_DIM; a forest on the handle.  The handle's active target, its candidates and later sweeps are
+ * unaffected. */
+int bogp_point_eval_ehvi_constrained(bogp_handle* h, const double* Xb, int B, int m_obj, int C, const double* lower, const double* upper,
+                                     int n_con, const double* lo, const double* hi, double* val, double* dval, double* pof, double* dpof,
+                                     double* ehvi, double* dehvi, double* mu, double* mse, double* dmu, double* dmse);
+int bogp_polish_ehvi_constrained(bogp_handle* h, const double* X0, int B, const double* box_lo, const double* box_hi, int m_obj, int C,
+                                 const double* lower, const double* upper, int n_con, const double* lo, const double* hi,
+                                 int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals);
 
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
