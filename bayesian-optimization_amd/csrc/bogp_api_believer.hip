@@ -480,7 +480,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if (!ref_point || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point, best_val and best_idx must be non-null", who);
   if (n_front < 0 || (n_front > 0 && !front)) FAIL(h, BOGP_ERR_INVALID, "%s: n_front = %d and front is %s", who, n_front, front ? "given" : "null");
   if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
-  const int d = h->d, N = h->N, Np = h->Np;
+  const int d = h->d;
   for (int k = 0; k < m; ++k)
     if (!std::isfinite(ref_point[k])) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point entry %d is not finite", who, k);
   for (size_t i = 0; i < (size_t)n_front * m; ++i)
@@ -514,14 +514,8 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   hipStream_t st = h->stream;
   auto upload_cells = [&]() -> int {  // in stream order, before the pass that reads them; `cells` stays as it is until that pass is complete
     const size_t nb = (size_t)C * m;
-    int e;
-    ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-    if ((e = h->dehvi_cells.ensure(h, std::max<size_t>(2 * nb, 2)))) return e;
-    if (nb == 0) return BOGP_OK;
-    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, cells.data(), nb * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, cells.data() + nb, nb * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return BOGP_OK;
+    if (int e = h->dehvi_cells.ensure(h, std::max<size_t>(2 * nb, 2))) return e;  // (allocated for a pass over no cells too)
+    return stage_ehvi_cells(h, cells.data(), cells.data() + nb, nb, st);
   };
 
   // ---- pass 0: bogp_sweep_ehvi's sweep; with pending points over no cells, for the moments only
@@ -530,9 +524,8 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if ((rc = upload_cells())) return rc;
   EhviArgs ea;
   memset(&ea, 0, sizeof(ea));
-  ea.gamma = h->dgamma_base; ea.ld_gamma = Np; ea.N = N; ea.m = m; ea.C = C0;
-  for (int t = 0; t < m; ++t) ea.sigma2[t] = h->sigma2_t[t];
-  ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + (size_t)C0 * m;
+  multi_target_model(h, ea);
+  ea.C = C0; ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + (size_t)C0 * m;
   invalidate_sweep_results(h);  // dbest_* are overwritten
   const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
   SweepRequest rq;
@@ -610,7 +603,7 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
   if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
   int rc = check_constrained_request(h, who, q, acq_id, acq_par, n_con, lo, hi);
   if (rc) return rc;
-  const int N = h->N, Np = h->Np, m = h->n_t;
+  const int m = h->n_t;
   for (size_t i = 0; i < (size_t)n_pending * h->d; ++i)
     if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
   const int64_t M = h->M;
@@ -621,8 +614,7 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
   if ((rc = h->dpof_out.ensure(h, (size_t)M))) return rc;
   ConstrainedArgs ca;
   memset(&ca, 0, sizeof(ca));
-  ca.gamma = h->dgamma_base; ca.ld_gamma = Np; ca.N = N; ca.m = m;
-  for (int t = 0; t < m; ++t) ca.sigma2[t] = h->sigma2_t[t];
+  multi_target_model(h, ca);
   for (int j = 0; j < n_con; ++j) { ca.lo[j + 1] = lo[j]; ca.hi[j + 1] = hi[j]; }
   ca.q = 1; ca.acq_id[0] = acq_id[0]; ca.acq_par[0] = acq_par ? acq_par[0] : 0.0;
   ca.plugin = plugin; ca.minimize = minimize; ca.pof_out = h->dpof_out.ptr;

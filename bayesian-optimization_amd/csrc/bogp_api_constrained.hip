@@ -37,6 +37,10 @@ int bogp::check_constrained_request(bogp_handle* h, const char* who, int q, cons
     if (id == BOGP_ACQ_EPSILON_PI && (!acq_par || !(acq_par[c] >= 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be >= 0 (epsilon = 0 is plain PI)", who, c);
     if (id == BOGP_ACQ_MGFI && (!acq_par || !(acq_par[c] > 0))) FAIL(h, BOGP_ERR_INVALID, "%s: acquisition parameter %d must be > 0 (the reference asserts t > 0)", who, c);
   }
+  return check_constraint_bounds(h, who, n_con, lo, hi);
+}
+
+int bogp::check_constraint_bounds(bogp_handle* h, const char* who, int n_con, const double* lo, const double* hi) {
   for (int j = 0; j < n_con; ++j) {
     if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
     if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
@@ -66,8 +70,7 @@ extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, 
   if (pof_out && (e = h->dpof_out.ensure(h, (size_t)M))) return e;
   ConstrainedArgs ca;
   memset(&ca, 0, sizeof(ca));
-  ca.gamma = h->dgamma_base; ca.ld_gamma = h->Np; ca.N = h->N; ca.m = m;
-  for (int t = 0; t < m; ++t) ca.sigma2[t] = h->sigma2_t[t];
+  multi_target_model(h, ca);
   for (int j = 0; j < n_con; ++j) { ca.lo[j + 1] = lo[j]; ca.hi[j + 1] = hi[j]; }
   ca.q = q;
   for (int c = 0; c < q; ++c) { ca.acq_id[c] = acq_id[c]; ca.acq_par[c] = acq_par ? acq_par[c] : 0.0; }
@@ -78,28 +81,10 @@ extern "C" int bogp_sweep_constrained(bogp_handle* h, int q, const int* acq_id, 
   rq.minimize = minimize; rq.cn = &ca;
   int rc = run_sweep(h, rq);
   if (rc) return rc;
-  if (k == 1) {  // the chunk loop's own argmax
-    HIPCHK(h, hipMemcpy(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost));
-  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks q criteria
-    const int64_t nblk = (M + 255) / 256;
-    if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
-    if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
-    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  for (int i = 0; i < q * k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
-  if (acq_out) HIPCHK(h, hipMemcpy(acq_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost));
-  if (pof_out) HIPCHK(h, hipMemcpy(pof_out, h->dpof_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-  if (mu_out) HIPCHK(h, hipMemcpy(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  if (mse_out) HIPCHK(h, hipMemcpy(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  return BOGP_OK;
+  // (the downloads are queued in front of the winners: fetch_winners waits for the stream)
+  if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (pof_out) HIPCHK(h, hipMemcpyAsync(pof_out, h->dpof_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  return fetch_winners(h, q, k, h->dacq_out, best_val, best_idx, st);
 }

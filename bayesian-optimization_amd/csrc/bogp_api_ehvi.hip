@@ -28,25 +28,15 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "bogp_sweep_ehvi: several targets take the constant trend only (gpr.py:787)");
   if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: the commit holds %d target variances", (int)h->sigma2_t.size());
   const size_t nb = (size_t)C * m;
-  for (size_t i = 0; i < nb; ++i) {
-    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: lower bound %zu is not finite", i);
-    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: upper bound %zu is NaN", i);
-    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "bogp_sweep_ehvi: upper bound %zu (%g) is below its lower bound (%g)", i, upper[i], lower[i]);
-  }
+  int e;
+  if ((e = check_ehvi_cells(h, "bogp_sweep_ehvi", nb, lower, upper))) return e;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
-  int e;
-  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
-  // (the cells are the kernel's arguments: copied in stream order, before the first chunk's kernels that read them)
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipStreamSynchronize(st));  // the caller's arrays are not needed past this call
+  if ((e = stage_ehvi_cells(h, lower, upper, nb, st))) return e;
   EhviArgs ea;
   memset(&ea, 0, sizeof(ea));
-  ea.gamma = h->dgamma_base; ea.ld_gamma = h->Np; ea.N = h->N; ea.m = m; ea.C = C;
-  for (int t = 0; t < m; ++t) ea.sigma2[t] = h->sigma2_t[t];
-  ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + nb;
+  multi_target_model(h, ea);
+  ea.C = C; ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + nb;
   invalidate_sweep_results(h);  // dbest_* are overwritten and hold no single-target winners afterwards
   const bool want_out = mu_out || mse_out;
   const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
@@ -55,27 +45,9 @@ extern "C" int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower
   int rc = run_sweep(h, rq);
   if (rc) return rc;
   const int64_t M = h->M;
-  if (k == 1) {  // the chunk loop's own argmax
-    HIPCHK(h, hipMemcpy(best_val, h->dbest_val, sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost));
-  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks one criterion
-    const int64_t nblk = (M + 255) / 256;
-    if ((e = h->dblk_val.ensure(h, (size_t)(nblk + 1)))) return e;
-    if ((e = h->dblk_idx.ensure(h, (size_t)(nblk + 1)))) return e;
-    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  for (int i = 0; i < k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
-  if (ehvi_out) HIPCHK(h, hipMemcpy(ehvi_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-  if (mu_out) HIPCHK(h, hipMemcpy(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  if (mse_out) HIPCHK(h, hipMemcpy(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  return BOGP_OK;
+  // (the downloads are queued in front of the winners: fetch_winners waits for the stream)
+  if (ehvi_out) HIPCHK(h, hipMemcpyAsync(ehvi_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  return fetch_winners(h, 1, k, h->dacq_out, best_val, best_idx, st);
 }

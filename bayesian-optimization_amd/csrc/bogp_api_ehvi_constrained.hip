@@ -32,27 +32,13 @@ extern "C" int bogp_sweep_ehvi_constrained(bogp_handle* h, int m_obj, int C, con
   if ((C > 0 && (!lower || !upper)) || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: lower and upper (C > 0), lo, hi, best_val and best_idx must be non-null", who);
   if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
   const size_t nb = (size_t)C * m_obj;
-  for (size_t i = 0; i < nb; ++i) {
-    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
-    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
-    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
-  }
-  for (int j = 0; j < n_con; ++j) {
-    if (std::isnan(lo[j]) || std::isnan(hi[j])) FAIL(h, BOGP_ERR_INVALID, "%s: a bound of constraint %d is NaN", who, j);
-    if (hi[j] < lo[j]) FAIL(h, BOGP_ERR_INVALID, "%s: the upper bound of constraint %d (%g) is below its lower bound (%g)", who, j, hi[j], lo[j]);
-  }
+  int e;
+  if ((e = check_ehvi_cells(h, who, nb, lower, upper))) return e;
+  if ((e = check_constraint_bounds(h, who, n_con, lo, hi))) return e;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
   const int64_t M = h->M;
-  int e;
-  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-  if (nb > 0) {
-    if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
-    // (the cells are the kernel's arguments: copied in stream order, before the first chunk's kernels that read them)
-    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));  // the caller's arrays are not needed past this call
-  }
+  if ((e = stage_ehvi_cells(h, lower, upper, nb, st))) return e;
   if (pof_out && (e = h->dpof_out.ensure(h, (size_t)M))) return e;
   ConstrainedEhviArgs ea;
   memset(&ea, 0, sizeof(ea));
@@ -67,28 +53,10 @@ extern "C" int bogp_sweep_ehvi_constrained(bogp_handle* h, int m_obj, int C, con
   rq.want_out = mu_out || mse_out; rq.want_acq_out = true; rq.q = 1; rq.acq_id = &one_id; rq.minimize = 0; rq.ec = &ea;
   int rc = run_sweep(h, rq);
   if (rc) return rc;
-  if (k == 1) {  // the chunk loop's own argmax
-    HIPCHK(h, hipMemcpy(best_val, h->dbest_val, sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost));
-  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks one criterion
-    const int64_t nblk = (M + 255) / 256;
-    if ((e = h->dblk_val.ensure(h, (size_t)(nblk + 1)))) return e;
-    if ((e = h->dblk_idx.ensure(h, (size_t)(nblk + 1)))) return e;
-    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
-  for (int i = 0; i < k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
-  if (val_out) HIPCHK(h, hipMemcpy(val_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-  if (pof_out) HIPCHK(h, hipMemcpy(pof_out, h->dpof_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-  if (mu_out) HIPCHK(h, hipMemcpy(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  if (mse_out) HIPCHK(h, hipMemcpy(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost));
-  return BOGP_OK;
+  // (the downloads are queued in front of the winners: fetch_winners waits for the stream)
+  if (val_out) HIPCHK(h, hipMemcpyAsync(val_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (pof_out) HIPCHK(h, hipMemcpyAsync(pof_out, h->dpof_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
+  return fetch_winners(h, 1, k, h->dacq_out, best_val, best_idx, st);
 }

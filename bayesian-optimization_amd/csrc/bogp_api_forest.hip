@@ -267,28 +267,13 @@ extern "C" int bogp_forest_sweep_topk(bogp_handle* h, int q, const int* acq_id, 
   if ((e = run_forest(h, "bogp_forest_sweep_topk", a, 0, M))) return e;
   // the block records -> the argmax per criterion (dbest_*: what bogp_exchange_argmax packs)
   HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, q, h->dbest_val, h->dbest_idx, st));
-  if (k == 1) {
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk (dtopk_*: what bogp_exchange_topk packs)
-    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  }
   if (acq_out) HIPCHK(h, hipMemcpyAsync(acq_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
+  if ((e = fetch_winners(h, q, k, h->dacq_out, best_val, best_idx, st))) return e;  // (waits for the stream: acq_out is complete)
   h->last_q = q;
   if (k > 1) {
     h->last_topk_q = q;
     h->last_topk_k = k;
   }
-  for (int i = 0; i < q * k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
   return BOGP_OK;
 }
 
@@ -361,28 +346,19 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
   if (k < 1 || k > BOGP_MAX_TOPK) FAIL(h, BOGP_ERR_INVALID, "%s: k = %d outside [1, %d]", who, k, BOGP_MAX_TOPK);
   if (!lower || !upper || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: lower, upper, best_val and best_idx must be non-null", who);
   const size_t nb = (size_t)C * m;
-  for (size_t i = 0; i < nb; ++i) {
-    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
-    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
-    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
-  }
+  if ((e = check_ehvi_cells(h, who, nb, lower, upper))) return e;
   HIPCHK(h, hipSetDevice(h->device));
   invalidate_sweep_results(h);
   hipStream_t st = h->stream;
   const int64_t M = h->M, nblk = (M + 255) / 256;
   const bool keep = k > 1 || ehvi_out;
-  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
-  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
   if ((e = h->dblk_val.ensure(h, (size_t)(nblk + 1)))) return e;
   if ((e = h->dblk_idx.ensure(h, (size_t)(nblk + 1)))) return e;
   if ((e = h->dbest_val.ensure(h, BOGP_MAX_Q)) || (e = h->dbest_idx.ensure(h, BOGP_MAX_Q))) return e;
   if (keep && (e = h->dacq_out.ensure(h, (size_t)M))) return e;
   if (mu_out && (e = h->dmu_out.ensure(h, (size_t)M * m))) return e;
   if (mse_out && (e = h->dmse_out.ensure(h, (size_t)M * m))) return e;
-  // (the cells are the kernel's arguments: copied in stream order before the kernel that reads them)
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipStreamSynchronize(st));  // the caller's arrays are not needed past this call
+  if ((e = stage_ehvi_cells(h, lower, upper, nb, st))) return e;
   ForestEhviArgs a;
   memset(&a, 0, sizeof(a));
   a.C = C; a.lower = h->dehvi_cells; a.upper = h->dehvi_cells + nb;
@@ -391,26 +367,10 @@ extern "C" int bogp_forest_sweep_ehvi(bogp_handle* h, int m, int C, const double
   a.blk_val = h->dblk_val; a.blk_idx = h->dblk_idx;
   if ((e = run_forest_ehvi(h, who, a, 0, M))) return e;
   HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, nblk, nblk, 1, h->dbest_val, h->dbest_idx, st));
-  if (k == 1) {
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_ehvi ranks them
-    if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-    HIPCHK(h, launch_topk(h->dacq_out, M, 1, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
-    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  }
   if (ehvi_out) HIPCHK(h, hipMemcpyAsync(ehvi_out, h->dacq_out, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
   if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->dmu_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
   if (mse_out) HIPCHK(h, hipMemcpyAsync(mse_out, h->dmse_out, (size_t)M * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  for (int i = 0; i < k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
-  return BOGP_OK;
+  return fetch_winners(h, 1, k, h->dacq_out, best_val, best_idx, st);  // (waits for the stream: the three outputs are complete)
 }
 
 extern "C" int bogp_candidates_generate_mixed(bogp_handle* h, const int* kind, const double* lo, const double* hi, const int* n_levels,

@@ -143,21 +143,13 @@ extern "C" int bogp_lift_sweep_topk(bogp_handle* h, int q, const int* acq_id, co
   // 4. criterion values and penalties side by side over all M rows, ranked as bogp_sweep_topk ranks
   if ((e = tm.mark(h, st, &m0))) return e;
   HIPCHK(h, launch_lift_merge(h->dlift_pen, M, h->dacq_out, h->dlift_map, Mf, q, h->dlift_val, st));
-  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
-  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
-  if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  HIPCHK(h, launch_topk(h->dlift_val, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+  if ((e = rank_stored_values(h, h->dlift_val, M, q, k, st))) return e;
   if ((e = tm.mark(h, st, &m1))) return e;
   tm.span(L_MERGE, m0, m1);
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
-  for (int i = 0; i < q * k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
+  pad_short_ranks(best_val, best_idx, q * k);
   h->lift_n_feasible = Mf;
   h->lift_filter_ms = tm.sum(L_FILTER);
   h->lift_merge_ms = tm.sum(L_MERGE);

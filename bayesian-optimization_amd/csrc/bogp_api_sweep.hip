@@ -379,6 +379,46 @@ int bogp::ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out
   return BOGP_OK;
 }
 
+int bogp::rank_stored_values(bogp_handle* h, const double* vals, int64_t M, int q, int k, hipStream_t st) {
+  // rank 0 is the argmax over the stored values; ranks 1 .. k-1 repeat it with the winners so far masked out -- all q criteria per
+  // launch, the winners kept on the device: 2 k queued launches (launch_topk)
+  const int64_t nblk = (M + 255) / 256;
+  int e;
+  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
+  if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
+  HIPCHK(h, launch_topk(vals, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+  return BOGP_OK;
+}
+
+void bogp::pad_short_ranks(double* best_val, int64_t* best_idx, int n) {
+  for (int i = 0; i < n; ++i)
+    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
+      best_val[i] = -INFINITY;
+      best_idx[i] = -1;
+    }
+}
+
+int bogp::fetch_winners(bogp_handle* h, int q, int k, const double* vals, double* best_val, int64_t* best_idx, hipStream_t st) {
+  if (k == 1) {  // the sweep's own argmax
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dbest_val, (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dbest_idx, (size_t)q * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  } else {  // ranks 0 .. k-1 over the stored values, as bogp_sweep_topk ranks them (dtopk_*: what bogp_exchange_topk packs)
+    if (int e = rank_stored_values(h, vals, h->M, q, k, st)) return e;
+    HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  pad_short_ranks(best_val, best_idx, q * k);
+  return BOGP_OK;
+}
+
+void bogp::multi_target_model(const bogp_handle* h, MultiTargetChunk& a) {
+  a.gamma = h->dgamma_base; a.ld_gamma = h->Np; a.N = h->N; a.m = h->n_t;
+  for (int t = 0; t < a.m; ++t) a.sigma2[t] = h->sigma2_t[t];
+}
+
 int bogp::check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par) {
   for (int i = 0; i < q; ++i) {
     if (acq_id[i] < 0 || acq_id[i] > 3) FAIL(h, BOGP_ERR_INVALID, "unknown acquisition id %d", acq_id[i]);
@@ -680,6 +720,13 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
   return BOGP_OK;
 }
 
+// What the chunk loop fills for a multi-target tail kernel (the model's half came with the request: multi_target_model): the arrays of
+// the chunk at m0 on chunk buffer b, its geometry and the trend's scalars
+static void multi_target_chunk(const bogp_handle* h, const SweepCtx& cx, int b, int64_t m0, int64_t mcount, MultiTargetChunk& a) {
+  a.rT = h->drT[b]; a.ss_part = h->dss_part; a.w_part = h->dw_part[b]; a.S = cx.g.S; a.nJ = cx.nJ_main; a.Mc = cx.g.Mc;
+  a.mcount = mcount; a.m0 = m0; a.beta = h->beta; a.G = h->G; a.estimate_trend = h->estimate_trend;
+}
+
 // Chunks [c_begin, c_end): producer -> contraction -> criteria (or the pruned flow).  pilot_done (a pruned sweep that began on the
 // one-pass flow): thresholds, control words and the pilot rows' winners are in place -- chunk 0 starts behind the pilot.
 // Two-stream mode (cx.overlap): the producer of chunk c + 1 runs on stP beside the contraction of chunk c, what it writes double buffered.
@@ -741,20 +788,18 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
       if (h->p > 1 && (e = sweep_trend_chunk(h, cx, b, m0, mcount, Mc_eff, aa))) return e;
       if (rq.eh) {  // the m-target posterior + EHVI of this chunk in place of the q single-target criteria (kernels_ehvi.hip)
         EhviArgs ea = *rq.eh;
-        ea.rT = h->drT[b]; ea.ss_part = h->dss_part; ea.w_part = h->dw_part[b]; ea.S = S; ea.nJ = cx.nJ_main; ea.Mc = Mc;
-        ea.mcount = mcount; ea.m0 = m0; ea.beta = h->beta; ea.G = h->G; ea.estimate_trend = h->estimate_trend;
+        multi_target_chunk(h, cx, b, m0, mcount, ea);
         ea.ehvi_out = h->dacq_out; ea.mu_out = rq.want_out ? h->dmu_out : nullptr; ea.mse_out = rq.want_out ? h->dmse_out : nullptr;
         ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = cx.blk_offset;
         HIPCHK(h, launch_ehvi(ea, st));
       } else if (rq.cn) {  // ... or the q feasibility-weighted criteria of the m-target posterior (kernels_constrained.hip)
         ConstrainedArgs cn = *rq.cn;
-        cn.rT = h->drT[b]; cn.ss_part = h->dss_part; cn.w_part = h->dw_part[b]; cn.S = S; cn.nJ = cx.nJ_main; cn.Mc = Mc;
-        cn.mcount = mcount; cn.m0 = m0; cn.beta = h->beta; cn.G = h->G; cn.estimate_trend = h->estimate_trend;
+        multi_target_chunk(h, cx, b, m0, mcount, cn);
         cn.acq_out = h->dacq_out; cn.M = M; cn.mu_out = rq.want_out ? h->dmu_out : nullptr; cn.mse_out = rq.want_out ? h->dmse_out : nullptr;
         cn.blk_val = h->dblk_val; cn.blk_idx = h->dblk_idx; cn.blk_offset = cx.blk_offset; cn.nblk_total = cx.nblk_total;
         HIPCHK(h, launch_constrained(cn, st));
       } else if (rq.ec) {  // ... or EHVI of its objectives weighted by its constraints' feasibility (kernels_ehvi_constrained.hip)
-        ConstrainedEhviArgs ec = *rq.ec;
+        ConstrainedEhviArgs ec = *rq.ec;  // (its own field order: it does not hold MultiTargetChunk, bogp_internal.h)
         ec.rT = h->drT[b]; ec.ss_part = h->dss_part; ec.w_part = h->dw_part[b]; ec.S = S; ec.nJ = cx.nJ_main; ec.Mc = Mc;
         ec.mcount = mcount; ec.m0 = m0; ec.beta = h->beta; ec.G = h->G; ec.estimate_trend = h->estimate_trend;
         ec.val_out = h->dacq_out; ec.mu_out = rq.want_out ? h->dmu_out : nullptr; ec.mse_out = rq.want_out ? h->dmse_out : nullptr;
@@ -1015,27 +1060,15 @@ extern "C" int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const d
   SweepRequest rq;  // (want_acq_out: keeps the q x M values on the device)
   rq.q = q; rq.acq_id = acq_id; rq.acq_par = acq_par; rq.plugin = plugin; rq.minimize = minimize; rq.want_acq_out = true;
   if ((rc = run_sweep(h, rq))) return rc;
-  // rank 0 is the sweep's own argmax; ranks 1..k-1 repeat the argmax with the winners so far masked out -- all q criteria
-  // per launch, the winners kept on the device: 2 k queued launches and ONE read-back of q x k (value, index) pairs
-  const int64_t M = h->M;
-  const int64_t nblk = (M + 255) / 256;
+  // the k ranks of every criterion (rank 0 repeats the sweep's own argmax) and ONE read-back of q x k (value, index) pairs
   hipStream_t st = h->stream;
-  int e;
-  if ((e = h->dblk_val.ensure(h, (size_t)q * (nblk + 1)))) return e;
-  if ((e = h->dblk_idx.ensure(h, (size_t)q * (nblk + 1)))) return e;
-  if ((e = h->dtopk_val.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  if ((e = h->dtopk_idx.ensure(h, (size_t)BOGP_MAX_Q * BOGP_MAX_TOPK))) return e;
-  HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+  if ((rc = rank_stored_values(h, h->dacq_out, h->M, q, k, st))) return rc;
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   h->last_topk_q = q;
   h->last_topk_k = k;
-  for (int i = 0; i < q * k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
+  pad_short_ranks(best_val, best_idx, q * k);
   return BOGP_OK;
 }
 

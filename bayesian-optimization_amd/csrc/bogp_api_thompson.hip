@@ -181,19 +181,15 @@ extern "C" int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* o
   // ---- 4: the winners.  Rank 0 alone is the reduction of the kernel's records; k ranks are bogp_sweep_topk's passes over the stored values
   if (k == 1)
     HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, blk_offset, nblk_total, q, h->dtopk_val, h->dtopk_idx, st));
-  else
-    HIPCHK(h, launch_topk(h->dacq_out, M, q, k, h->dblk_val, h->dblk_idx, h->dtopk_val, h->dtopk_idx, st));
+  else if ((rc = rank_stored_values(h, h->dacq_out, M, q, k, st)))
+    return rc;
   HIPCHK(h, hipMemcpyAsync(best_val, h->dtopk_val, (size_t)q * k * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipMemcpyAsync(best_idx, h->dtopk_idx, (size_t)q * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   if (paths_out) HIPCHK(h, hipMemcpyAsync(paths_out, h->dacq_out, (size_t)q * M * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   if (paths_out && minimize)  // stored in the criterion's sign: back to the path's own
     for (size_t i = 0; i < (size_t)q * M; ++i) paths_out[i] = -1 * paths_out[i];
-  for (int i = 0; i < q * k; ++i)
-    if (best_idx[i] == INT64_MAX) {  // fewer candidates than k: pad with (-inf, -1)
-      best_val[i] = -INFINITY;
-      best_idx[i] = -1;
-    }
+  pad_short_ranks(best_val, best_idx, q * k);
   if (best_x) {
     for (int i = 0; i < q * k; ++i) {
       double* dst = best_x + (size_t)i * d;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/bogp.h"
+#include "bogp_internal.h"  // for ONE argument block, MultiTargetChunk (the overload of multi_target_moments below): the other helpers here know none
 
 namespace bogp {
 
@@ -504,7 +505,7 @@ __device__ __forceinline__ void posterior_of_sums(double rgamma, double wr, doub
 // posterior of row i of a chunk for the MT targets of a multi-target model (gpr.py:490, 496-510 with n_targets > 1; constant basis):
 //   mu_k = beta + r . gamma_k, one fma chain over n = 0 .. N - 1 from 0 per target (the bits do not depend on the chunk size),
 //   MSE_k = max(0, (1 - ss + u^2) sigma2_k), ss the sum of the nJ column groups of |L^-1 r|^2, u = (w.r - 1) / G under ordinary kriging.
-// Shared by k_ehvi and k_constrained, so that both leave the same bits for the same model and rows.  AHEAD > 1: the loads of AHEAD rows are
+// Shared by k_ehvi, k_constrained and k_ehvi_constrained, so that all leave the same bits for the same model and rows.  AHEAD > 1: the loads of AHEAD rows are
 // issued before their fmas -- a lane streams its column alone, so the loads in flight are what hides the memory latency (k_constrained at
 // N = 2048, 1e6 rows: 12.1 -> 2.9 ms with 8, profiles/constrained_sweep.txt); the fmas keep the order n = 0 .. N - 1, so the bits are
 // those of the plain loop (AHEAD = 1).
@@ -547,6 +548,21 @@ __device__ __forceinline__ void multi_target_moments(const double* rT, const dou
     if (mse[k] < 0.0) mse[k] = 0.0;
   }
 }
+// ... of row i of the chunk a tail kernel's argument block describes: k_ehvi and k_constrained (k_ehvi_constrained spells the call
+// out: its block keeps its own field order), and the stores of the moments of global row g where the caller asked for them: all three
+template <int MT, int AHEAD = 1>
+__device__ __forceinline__ void multi_target_moments(const MultiTargetChunk& a, int64_t i, double (&mu)[MT], double (&mse)[MT]) {
+  multi_target_moments<MT, AHEAD>(a.rT, a.gamma, a.ld_gamma, a.N, a.ss_part, a.nJ, a.w_part, a.S, a.Mc, i, a.beta, a.G, a.estimate_trend,
+                                  a.sigma2, mu, mse);
+}
+template <int MT>
+__device__ __forceinline__ void store_moments(double* mu_out, double* mse_out, int64_t g, const double (&mu)[MT], const double (&mse)[MT]) {
+#pragma unroll
+  for (int k = 0; k < MT; ++k) {
+    if (mu_out) mu_out[(size_t)g * MT + k] = mu[k];
+    if (mse_out) mse_out[(size_t)g * MT + k] = mse[k];
+  }
+}
 
 // argmax ordering identical to np.argmax over a 1-D float64 array: first maximal element, where a NaN
 // (if any) is maximal.  (value, index) pairs; `better(a,b)` == a should replace b.
@@ -570,6 +586,34 @@ __device__ __forceinline__ int64_t shfl_xor_i64(int64_t v, int mask) {
   int lo = __shfl_xor((int)(v & 0xffffffffll), mask, 64);
   int hi = __shfl_xor((int)(v >> 32), mask, 64);
   return ((int64_t)hi << 32) | (uint32_t)lo;
+}
+// The np.argmax pair of a 256-thread workgroup from every thread's own (v, idx): a butterfly over `better` in each wavefront, one LDS
+// slot per wavefront, thread 0 folds the four.  THREAD 0's return value is the block's pair (the other threads get a partial one).
+// sv / si: the kernel's two __shared__ arrays of 4; a kernel that calls this in a loop synchronises before the next call.
+__device__ __forceinline__ ArgMax block_argmax(double v, int64_t idx, double* sv, int64_t* si) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double ov = shfl_xor_f64(v, off);
+    const int64_t oi = shfl_xor_i64(idx, off);
+    if (better(ov, oi, v, idx)) {
+      v = ov;
+      idx = oi;
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    sv[w] = v;
+    si[w] = idx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k)
+      if (better(sv[k], si[k], v, idx)) {
+        v = sv[k];
+        idx = si[k];
+      }
+  }
+  return {v, idx};
 }
 
 // ---- 4 x 4 pivot arithmetic of the in-place elimination (kernels_nllsmall.hip: k_nll_small; kernels_chol.hip: elim_diag) ----

@@ -47,6 +47,27 @@ int sweep_geometry(bogp_handle* h, int rows, SweepGeometry* g);
 CorrArgs corr_chunk_args(const bogp_handle* h, const SweepGeometry& g, int64_t m0, int b);
 int ensure_sweep_outputs(bogp_handle* h, int q, int64_t nblk, size_t n_out, bool want_acq_out);
 int check_criteria(bogp_handle* h, int q, const int* acq_id, const double* acq_par);
+#pragma GCC visibility push(hidden)  // (the library's dynamic symbols stay the ones they were)
+// bogp_api_sweep.hip, the ranked tail of every entry that returns k winners per criterion.  None of the three touches last_q /
+// last_topk_q / last_topk_k: the caller records what bogp_exchange_argmax / bogp_exchange_topk may pack.
+//   rank_stored_values: ranks 0 .. k-1 of the q criteria over vals[q][M] into dtopk_* (queued; the block records are sized here)
+//   pad_short_ranks:    ranks beyond the number of candidates, which the device leaves as (-inf, INT64_MAX), become (-inf, -1)
+//   fetch_winners:      k == 1: dbest_*, which the sweep left, else rank_stored_values over vals[q][h->M] and dtopk_*, copied to
+//                       best_val / best_idx [q][k]; waits for st -- everything queued on it before is complete -- and pads
+int rank_stored_values(bogp_handle* h, const double* vals, int64_t M, int q, int k, hipStream_t st);
+void pad_short_ranks(double* best_val, int64_t* best_idx, int n);
+int fetch_winners(bogp_handle* h, int q, int k, const double* vals, double* best_val, int64_t* best_idx, hipStream_t st);
+// bogp_api_sweep.hip: the model's half of a multi-target tail kernel's arguments -- gamma, ld_gamma, N, m and sigma2[] of the commit
+void multi_target_model(const bogp_handle* h, MultiTargetChunk& a);
+// bogp_point.hip, what every entry that takes EHVI cells does alike.  check_ehvi_cells: the nb = C m bounds -- a finite lower, a
+// non-NaN upper, upper >= lower (BOGP_ERR_INVALID; the cell count and the pointers are checked by each entry where its own order of
+// refusals has them).  stage_ehvi_cells: the bounds into dehvi_cells ([lower nb | upper nb]) in stream order and waited for, so that
+// the caller's arrays are not needed afterwards; whatever bogp_point_eval_ehvi left there is forgotten; nb == 0 copies nothing.
+int check_ehvi_cells(bogp_handle* h, const char* who, size_t nb, const double* lower, const double* upper);
+int stage_ehvi_cells(bogp_handle* h, const double* lower, const double* upper, size_t nb, hipStream_t st);
+// bogp_api_constrained.hip: the n_con intervals of modelled constraints -- no NaN, hi >= lo (BOGP_ERR_INVALID)
+int check_constraint_bounds(bogp_handle* h, const char* who, int n_con, const double* lo, const double* hi);
+#pragma GCC visibility pop
 // bogp_api_constrained.hip, shared with the point path: what every entry with modelled constraints refuses alike, from the target count
 // through the criteria down to the bounds (all BOGP_ERR_INVALID; hidden: the library's dynamic symbols stay the ones they were)
 __attribute__((visibility("hidden"))) int check_constrained_request(bogp_handle* h, const char* who, int q, const int* acq_id, const double* acq_par, int n_con, const double* lo,

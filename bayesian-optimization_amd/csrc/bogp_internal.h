@@ -205,9 +205,14 @@ hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st)
 hipError_t launch_bound32_flags(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
                                 hipStream_t st);
 
-// expected hypervolume improvement of an m-target model over one chunk (kernels_ehvi.hip): replaces AcqArgs / k_acquisition
-// in the chunk loop of bogp_sweep_ehvi
-struct EhviArgs {
+// What the chunk loop and the committed model fill for a kernel that evaluates an m-target posterior over one chunk: the first part
+// of EhviArgs and ConstrainedArgs, read by multi_target_moments (bogp_device.h).  Both blocks lie in memory as they did before they
+// shared it (mu_out / mse_out stay where each had them): moving those two into this part cost k_ehvi<2> 2 % and gained k_ehvi<3> 2 %.
+// (ConstrainedEhviArgs holds the same fields in another order, and neither order serves both: under ConstrainedEhviArgs' order
+// k_constrained<5> no longer keeps its five groups of 16 gamma scalars in flight -- the fifth load waits behind the fmas of the other
+// four, 2.97 -> 4.75 ms at N = 2048 over 1e6 rows --, under this one k_ehvi_constrained gets the stack frame its comment names:
+// profiles/multi_target_fold.txt.  Check -Rpass-analysis=kernel-resource-usage and the loop's s_load_dwordx16 after moving a field.)
+struct MultiTargetChunk {
   const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
   const double* gamma;    // [m][ld_gamma] the targets' gamma columns
   int ld_gamma, N;        // Np; training points summed over
@@ -219,6 +224,11 @@ struct EhviArgs {
   int estimate_trend;
   int m;                  // targets, 2 .. BOGP_MAX_TARGETS
   double sigma2[8];       // per target
+};
+
+// expected hypervolume improvement of an m-target model over one chunk (kernels_ehvi.hip): replaces AcqArgs / k_acquisition
+// in the chunk loop of bogp_sweep_ehvi
+struct EhviArgs : MultiTargetChunk {
   const double* lower;    // [C][m] cell bounds (device)
   const double* upper;    // [C][m] (+inf allowed)
   int C;
@@ -233,18 +243,7 @@ hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
 
 // q feasibility-weighted criteria of an m-target model over one chunk (kernels_constrained.hip): target 0 is the objective, targets
 // 1 .. m - 1 are constraints feasible in [lo_k, hi_k]; replaces AcqArgs / k_acquisition in the chunk loop of bogp_sweep_constrained
-struct ConstrainedArgs {
-  const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
-  const double* gamma;    // [m][ld_gamma] the targets' gamma columns
-  int ld_gamma, N;        // Np; training points summed over
-  const double* ss_part;  // [nJ][Mc]
-  const double* w_part;   // [S][Mc] (constant trend with estimate_trend only)
-  int S, nJ;
-  int64_t Mc, mcount, m0;
-  double beta, G;
-  int estimate_trend;
-  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
-  double sigma2[8];       // per target
+struct ConstrainedArgs : MultiTargetChunk {
   double lo[8], hi[8];    // per target; entry 0 is not read
   int q;
   int acq_id[64];         // BOGP_ACQ_EI / EPSILON_PI / MGFI, or BOGP_ACQ_NONE: the probability of feasibility alone

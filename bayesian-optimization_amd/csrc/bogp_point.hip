@@ -278,18 +278,10 @@ int ehvi_cells_resident(bogp_handle* h, const char* who, int m, int C, const dou
   if (h->dehvi_cells && h->ehvi_host_m == m && h->ehvi_host_C == C && h->h_ehvi_cells.size() == 2 * nb &&
       memcmp(h->h_ehvi_cells.data(), lower, nb * sizeof(double)) == 0 && memcmp(h->h_ehvi_cells.data() + nb, upper, nb * sizeof(double)) == 0)
     return BOGP_OK;
-  for (size_t i = 0; i < nb; ++i) {
-    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
-    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
-    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  ehvi_cells_forget(h);
   int e;
-  if ((e = h->dehvi_cells.ensure(h, 2 * nb))) return e;
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));  // the caller's arrays are not needed past this call
+  if ((e = check_ehvi_cells(h, who, nb, lower, upper))) return e;
+  HIPCHK(h, hipSetDevice(h->device));
+  if ((e = stage_ehvi_cells(h, lower, upper, nb, h->stream))) return e;
   h->h_ehvi_cells.assign(lower, lower + nb);
   h->h_ehvi_cells.insert(h->h_ehvi_cells.end(), upper, upper + nb);
   h->ehvi_host_m = m;
@@ -359,6 +351,26 @@ namespace bogp {
 void ehvi_cells_forget(bogp_handle* h) {
   h->h_ehvi_cells.clear();
   h->ehvi_host_m = h->ehvi_host_C = 0;
+}
+
+int check_ehvi_cells(bogp_handle* h, const char* who, size_t nb, const double* lower, const double* upper) {
+  for (size_t i = 0; i < nb; ++i) {
+    if (!std::isfinite(lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: lower bound %zu is not finite", who, i);
+    if (std::isnan(upper[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu is NaN", who, i);
+    if (!(upper[i] >= lower[i])) FAIL(h, BOGP_ERR_INVALID, "%s: upper bound %zu (%g) is below its lower bound (%g)", who, i, upper[i], lower[i]);
+  }
+  return BOGP_OK;
+}
+
+int stage_ehvi_cells(bogp_handle* h, const double* lower, const double* upper, size_t nb, hipStream_t st) {
+  ehvi_cells_forget(h);  // (bogp_point_eval_ehvi keeps a host copy of what it left in this buffer)
+  if (nb == 0) return BOGP_OK;
+  if (int e = h->dehvi_cells.ensure(h, 2 * nb)) return e;
+  // (the cells are the kernel's arguments: copied in stream order, before the kernels that read them)
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells, lower, nb * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dehvi_cells + nb, upper, nb * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // the caller's arrays are not needed past this call
+  return BOGP_OK;
 }
 
 int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, int q, const int* acq_id, const double* acq_par,

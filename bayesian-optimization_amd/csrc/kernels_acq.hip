@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256) void k_acquisition(AcqArgs a) {
     y_hat = a.minimize ? mu : -1 * mu;
     sd = sqrt(mse);
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int c = 0; c < a.q; ++c) {
     double v = -INFINITY;
     int64_t idx = INT64_MAX;
@@ -56,28 +55,10 @@ __global__ __launch_bounds__(256) void k_acquisition(AcqArgs a) {
       idx = a.map ? a.map[i] : a.m0 + i;
       if (a.acq_out) a.acq_out[(size_t)c * a.M + idx] = v;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double ov = shfl_xor_f64(v, off);
-      const int64_t oi = shfl_xor_i64(idx, off);
-      if (better(ov, oi, v, idx)) {
-        v = ov;
-        idx = oi;
-      }
-    }
-    if (lane == 0) {
-      sv[w] = v;
-      si[w] = idx;
-    }
-    __syncthreads();
+    const ArgMax best = block_argmax(v, idx, sv, si);
     if (threadIdx.x == 0) {
-      for (int k = 1; k < 4; ++k)
-        if (better(sv[k], si[k], v, idx)) {
-          v = sv[k];
-          idx = si[k];
-        }
-      a.blk_val[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = v;
-      a.blk_idx[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = idx;
+      a.blk_val[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = best.v;
+      a.blk_idx[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = best.i;
     }
     __syncthreads();
   }
@@ -100,29 +81,10 @@ __global__ __launch_bounds__(256) void k_argmax_final(const double* blk_val, con
       idx = oi;
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double ov = shfl_xor_f64(v, off);
-    const int64_t oi = shfl_xor_i64(idx, off);
-    if (better(ov, oi, v, idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[w] = v;
-    si[w] = idx;
-  }
-  __syncthreads();
+  const ArgMax best = block_argmax(v, idx, sv, si);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < 4; ++k)
-      if (better(sv[k], si[k], v, idx)) {
-        v = sv[k];
-        idx = si[k];
-      }
-    out_val[(size_t)c * out_stride + out_off] = v;
-    out_idx[(size_t)c * out_stride + out_off] = idx;
+    out_val[(size_t)c * out_stride + out_off] = best.v;
+    out_idx[(size_t)c * out_stride + out_off] = best.i;
   }
 }
 
@@ -147,29 +109,10 @@ __global__ __launch_bounds__(256) void k_block_argmax_excl(const double* __restr
       idx = i;
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double ov = shfl_xor_f64(v, off);
-    const int64_t oi = shfl_xor_i64(idx, off);
-    if (better(ov, oi, v, idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[w] = v;
-    si[w] = idx;
-  }
-  __syncthreads();
+  const ArgMax best = block_argmax(v, idx, sv, si);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < 4; ++k)
-      if (better(sv[k], si[k], v, idx)) {
-        v = sv[k];
-        idx = si[k];
-      }
-    blk_val[(size_t)c * nblk + blockIdx.x] = v;
-    blk_idx[(size_t)c * nblk + blockIdx.x] = idx;
+    blk_val[(size_t)c * nblk + blockIdx.x] = best.v;
+    blk_idx[(size_t)c * nblk + blockIdx.x] = best.i;
   }
 }
 

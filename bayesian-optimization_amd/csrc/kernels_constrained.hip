@@ -23,20 +23,15 @@ __global__ __launch_bounds__(256) void k_constrained(ConstrainedArgs a) {
   const int64_t g = a.m0 + i;
   double y_hat = 0.0, sd = 0.0, P = 1.0;
   if (valid) {
-    double mu[MT], mse[MT];  // (bogp_device.h: shared with k_ehvi)
-    multi_target_moments<MT, 8>(a.rT, a.gamma, a.ld_gamma, a.N, a.ss_part, a.nJ, a.w_part, a.S, a.Mc, i, a.beta, a.G, a.estimate_trend, a.sigma2, mu, mse);
-#pragma unroll
-    for (int k = 0; k < MT; ++k) {
-      if (a.mu_out) a.mu_out[(size_t)g * MT + k] = mu[k];
-      if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse[k];
-    }
+    double mu[MT], mse[MT];  // (bogp_device.h: shared with k_ehvi and k_ehvi_constrained)
+    multi_target_moments<MT, 8>(a, i, mu, mse);
+    store_moments<MT>(a.mu_out, a.mse_out, g, mu, mse);
     y_hat = a.minimize ? mu[0] : -1 * mu[0];
     sd = sqrt(mse[0]);
 #pragma unroll
     for (int k = 1; k < MT; ++k) P *= feasibility(mu[k], mse[k], a.sigma2[k], a.lo[k], a.hi[k]);
     if (a.pof_out) a.pof_out[g] = P;
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int c = 0; c < a.q; ++c) {
     double v = -INFINITY;
     int64_t idx = INT64_MAX;
@@ -46,28 +41,10 @@ __global__ __launch_bounds__(256) void k_constrained(ConstrainedArgs a) {
       idx = g;
       a.acq_out[(size_t)c * a.M + g] = v;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double ov = shfl_xor_f64(v, off);
-      const int64_t oi = shfl_xor_i64(idx, off);
-      if (better(ov, oi, v, idx)) {
-        v = ov;
-        idx = oi;
-      }
-    }
-    if (lane == 0) {
-      sv[w] = v;
-      si[w] = idx;
-    }
-    __syncthreads();
+    const ArgMax best = block_argmax(v, idx, sv, si);
     if (threadIdx.x == 0) {
-      for (int k = 1; k < 4; ++k)
-        if (better(sv[k], si[k], v, idx)) {
-          v = sv[k];
-          idx = si[k];
-        }
-      a.blk_val[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = v;
-      a.blk_idx[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = idx;
+      a.blk_val[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = best.v;
+      a.blk_idx[(size_t)c * a.nblk_total + a.blk_offset + blockIdx.x] = best.i;
     }
     __syncthreads();
   }

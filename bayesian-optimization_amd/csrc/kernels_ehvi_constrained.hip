@@ -34,12 +34,9 @@ __global__ __launch_bounds__(256) void k_ehvi_constrained(ConstrainedEhviArgs a)
   }
   if (valid) {
     double mu[MT], mse[MT];  // (bogp_device.h: shared with k_ehvi and k_constrained)
+    // (ConstrainedEhviArgs keeps its own field order, so it does not hold MultiTargetChunk: bogp_internal.h)
     multi_target_moments<MT, 8>(a.rT, a.gamma, a.ld_gamma, a.N, a.ss_part, a.nJ, a.w_part, a.S, a.Mc, i, a.beta, a.G, a.estimate_trend, a.sigma2, mu, mse);
-#pragma unroll
-    for (int k = 0; k < MT; ++k) {
-      if (a.mu_out) a.mu_out[(size_t)g * MT + k] = mu[k];
-      if (a.mse_out) a.mse_out[(size_t)g * MT + k] = mse[k];
-    }
+    store_moments<MT>(a.mu_out, a.mse_out, g, mu, mse);
 #pragma unroll
     for (int k = 0; k < MO; ++k) {
       mu_o[k] = mu[k];
@@ -53,7 +50,7 @@ __global__ __launch_bounds__(256) void k_ehvi_constrained(ConstrainedEhviArgs a)
   const bool live = valid && !(P == 0.0);
   double E = 1.0;
   if (a.C > 0 && __ballot(live) != 0ull) {
-    if (live) E = ehvi_cells<MO>(a.lower, a.upper, a.C, mu_o, sd);  // (bogp_device.h: shared with k_ehvi)
+    if (live) E = ehvi_cells<MO>(a.lower, a.upper, a.C, mu_o, sd);  // (bogp_device.h: shared with k_ehvi, k_believer_ehvi and k_forest_ehvi)
   }
   double v = -INFINITY;
   int64_t idx = INT64_MAX;
@@ -62,29 +59,10 @@ __global__ __launch_bounds__(256) void k_ehvi_constrained(ConstrainedEhviArgs a)
     idx = g;
     a.val_out[g] = v;
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double ov = shfl_xor_f64(v, off);
-    const int64_t oi = shfl_xor_i64(idx, off);
-    if (better(ov, oi, v, idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  if (lane == 0) {
-    sv[w] = v;
-    si[w] = idx;
-  }
-  __syncthreads();
+  const ArgMax best = block_argmax(v, idx, sv, si);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < 4; ++k)
-      if (better(sv[k], si[k], v, idx)) {
-        v = sv[k];
-        idx = si[k];
-      }
-    a.blk_val[a.blk_offset + blockIdx.x] = v;
-    a.blk_idx[a.blk_offset + blockIdx.x] = idx;
+    a.blk_val[a.blk_offset + blockIdx.x] = best.v;
+    a.blk_idx[a.blk_offset + blockIdx.x] = best.i;
   }
 }
 

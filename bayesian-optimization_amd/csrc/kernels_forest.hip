@@ -117,7 +117,6 @@ __global__ __launch_bounds__(256) void k_forest(ForestArgs a) {
     y_hat = a.minimize ? mu : -1 * mu;
     sd = sqrt(mse);
   }
-  const int lane = tid & 63, w = tid >> 6;
   for (int c = 0; c < a.q; ++c) {
     double v = -INFINITY;
     int64_t idx = INT64_MAX;
@@ -126,28 +125,10 @@ __global__ __launch_bounds__(256) void k_forest(ForestArgs a) {
       idx = row;
       if (a.acq_out) a.acq_out[(size_t)c * a.M + row] = v;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double ov = shfl_xor_f64(v, off);
-      const int64_t oi = shfl_xor_i64(idx, off);
-      if (better(ov, oi, v, idx)) {
-        v = ov;
-        idx = oi;
-      }
-    }
-    if (lane == 0) {
-      sv[w] = v;
-      si[w] = idx;
-    }
-    __syncthreads();
+    const ArgMax best = block_argmax(v, idx, sv, si);
     if (tid == 0) {
-      for (int k = 1; k < 4; ++k)
-        if (better(sv[k], si[k], v, idx)) {
-          v = sv[k];
-          idx = si[k];
-        }
-      a.blk_val[(size_t)c * a.nblk_total + blockIdx.x] = v;
-      a.blk_idx[(size_t)c * a.nblk_total + blockIdx.x] = idx;
+      a.blk_val[(size_t)c * a.nblk_total + blockIdx.x] = best.v;
+      a.blk_idx[(size_t)c * a.nblk_total + blockIdx.x] = best.i;
     }
     __syncthreads();
   }

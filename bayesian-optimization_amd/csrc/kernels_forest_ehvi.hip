@@ -125,29 +125,10 @@ __global__ __launch_bounds__(256) void k_forest_ehvi(ForestEhviArgs a) {
     idx = row;
     if (a.ehvi_out) a.ehvi_out[row] = v;
   }
-  const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double ov = shfl_xor_f64(v, off);
-    const int64_t oi = shfl_xor_i64(idx, off);
-    if (better(ov, oi, v, idx)) {
-      v = ov;
-      idx = oi;
-    }
-  }
-  if (lane == 0) {
-    sv[w] = v;
-    si[w] = idx;
-  }
-  __syncthreads();
+  const ArgMax best = block_argmax(v, idx, sv, si);
   if (tid == 0) {
-    for (int k = 1; k < 4; ++k)
-      if (better(sv[k], si[k], v, idx)) {
-        v = sv[k];
-        idx = si[k];
-      }
-    a.blk_val[blockIdx.x] = v;
-    a.blk_idx[blockIdx.x] = idx;
+    a.blk_val[blockIdx.x] = best.v;
+    a.blk_idx[blockIdx.x] = best.i;
   }
 }
 

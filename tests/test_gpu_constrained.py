@@ -8,6 +8,7 @@ import pytest
 
 from bogp import _lib
 from support import constrained_ref as R
+from support.ranked_tail import pin_ranked_tail
 from test_gpu_ehvi import _check_argmax, _close_mse, _close_mu, _model
 
 pytestmark = pytest.mark.gpu
@@ -134,6 +135,12 @@ def test_chunk_criteria_and_topk_invariance(eng, monkeypatch):
     for c in range(3):  # k = 7: the stable sort of the stored values
         order = sorted(range(len(vals[c])), key=lambda j: (-vals[c][j], j))[:7]
         assert list(ik[c]) == order and np.array_equal(bk[c], vals[c][order])
+    # the edges of the ranked tail on a tiny model: more ranks than candidates, a tie across the partial second workgroup
+    X, Y, _, _ = _model(eng, 2, 16, 2, _lib.KERNEL_SE, True, seed=9)
+    lo, hi = _bounds(Y)
+    Xt = np.random.default_rng(3).uniform(-2.5, 2.5, size=(257, 2))
+    one = lambda k: [a[0] for a in eng.sweep_constrained(acq[:1], float(Y[:, 0].min()), True, lo, hi, k=k, return_values=True)]  # noqa: E731
+    pin_ranked_tail(eng.upload_candidates, one, Xt)
 
 
 def test_single_target_sweep_unchanged_around_constrained(eng):

@@ -13,6 +13,7 @@ import pytest
 
 from bogp import _lib, pareto
 from support import constrained_ehvi_ref as R
+from support.ranked_tail import pin_ranked_tail
 from test_gpu_ehvi import _check_argmax, _close_mse, _close_mu, _model
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +148,9 @@ def test_chunk_and_topk_invariance(eng, monkeypatch):
     eng.upload_candidates(Xs[:1])
     b, i = eng.sweep_ehvi_constrained(lower, upper, lo, hi, k=3)
     assert list(i) == [0, -1, -1] and b[0] == vals[0] and np.all(b[1:] == -INF)
+    # the edges of the ranked tail on a tiny model: more ranks than candidates, a tie across the partial second workgroup
+    X, Y, Xt, lower, upper, lo, hi = _setup(eng, 2, 1, 16, 2, _lib.KERNEL_SE, True, 9, 257)
+    pin_ranked_tail(eng.upload_candidates, lambda k: eng.sweep_ehvi_constrained(lower[:4], upper[:4], lo, hi, k=k, return_values=True), Xt)
 
 
 def test_wavefronts_whose_rows_are_all_infeasible_skip_the_cells(eng):

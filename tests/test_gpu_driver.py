@@ -11,6 +11,7 @@ import bogp  # noqa: E402
 import producer_cases as PC  # noqa: E402
 from bogp import _lib, integration  # noqa: E402
 from support.mini_driver import MiniParallelBO  # noqa: E402
+from support.ranked_tail import pin_ranked_tail  # noqa: E402
 
 
 def _fitted_model(N=300, d=4, seed=3):
@@ -110,6 +111,13 @@ def test_topk_is_repeated_argmax_for_every_criterion():
     eng.upload_candidates(Xs[:5])
     tv, ti = eng.sweep_topk(acq[:1], pl, True, 8)
     assert np.all(ti[0, 5:] == -1) and np.all(np.isneginf(tv[0, 5:])) and sorted(ti[0, :5]) == [0, 1, 2, 3, 4]
+    # ... in the stable order of the five values; and a tie across the partial second workgroup of 257 candidates
+
+    def one(k):
+        tv, ti = eng.sweep_topk(acq[:1], pl, True, k)
+        return tv[0], ti[0], eng.sweep(acq[:1], pl, True, return_values=True)[2][0]
+
+    pin_ranked_tail(eng.upload_candidates, one, Xs[200:457])  # (rows without the tie above)
 
 
 def _smooth(n=40, d=2, seed=2):

@@ -10,6 +10,7 @@ import pytest
 from bogp import _lib
 from bogp import pareto
 from support.ehvi_ref64 import ehvi as ehvi_ref
+from support.ranked_tail import pin_ranked_tail
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +147,10 @@ def test_chunk_invariance_and_topk(eng, monkeypatch):
     order = sorted(range(len(v1)), key=lambda j: (-v1[j], j))[:7]
     assert list(ik) == order and np.array_equal(bk, v1[order])
     assert ik[0] == i1[0]
+    # the edges of the ranked tail on a tiny model: more ranks than candidates, a tie across the partial second workgroup
+    _, _, lo, hi = _model(eng, 2, 16, 2, _lib.KERNEL_SE, True, seed=9)
+    Xt = np.random.default_rng(3).uniform(-2.5, 2.5, size=(257, 2))
+    pin_ranked_tail(eng.upload_candidates, lambda k: eng.sweep_ehvi(lo[:4], hi[:4], k=k, return_values=True), Xt)
 
 
 def test_small_lazy_generated_and_cells(eng):

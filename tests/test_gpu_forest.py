@@ -407,3 +407,14 @@ def test_error_returns_launch_nothing(eng):
     # fewer candidates than k: padded
     best, idx = eng.forest_sweep_topk([(_lib.ACQ_UCB, 0.5)], 0.0, True, 6)
     assert np.array_equal(idx[0, 4:], [-1, -1]) and np.all(np.isneginf(best[0, 4:])) and idx[0, 0] == 1
+    # M = 5, k = 8: the ties in index order, three padded ranks
+    eng.upload_candidates(np.array([[0.0, 0.0], [1.0, 1.0], [0.5, 0.25], [0.6, 0.3], [0.0, 0.0]]))
+    best, idx = eng.forest_sweep_topk([(_lib.ACQ_UCB, 0.5)], 0.0, True, 8)
+    assert idx[0].tolist() == [1, 3, 0, 2, 4, -1, -1, -1] and np.all(np.isneginf(best[0, 5:])) and best[0, 0] == best[0, 1] > best[0, 2]
+    # M = 257, the maximum in rows 255 and 256 alone (around the boundary of the partial second workgroup): the lower index first
+    X257 = np.zeros((257, 2))
+    X257[255:] = 1.0
+    eng.upload_candidates(X257)
+    for k in (1, 2):
+        best, idx = eng.forest_sweep_topk([(_lib.ACQ_UCB, 0.5)], 0.0, True, k)
+        assert idx[0].tolist() == [255, 256][:k] and np.all(best[0] == best[0, 0])

@@ -434,6 +434,18 @@ def test_error_returns_launch_nothing(eng):
     assert np.array_equal(mse[:, 0], np.std(per_tree, axis=1, ddof=1) ** 2.0) and np.array_equal(mse[:, 1], mse[:, 0])
     best, idx = eng.forest_sweep_ehvi(lo, hi, k=6)  # fewer candidates than k: padded
     assert np.array_equal(idx[4:], [-1, -1]) and np.all(np.isneginf(best[4:])) and idx[0] == 1 and idx[1] == 3 and best[0] == best[1]
+    # M = 5, k = 8: the ties in index order, three padded ranks
+    eng.upload_candidates(np.array([[0.0, 0.0], [1.0, 1.0], [0.5, 0.25], [0.6, 0.3], [0.0, 0.0]]))
+    best, idx = eng.forest_sweep_ehvi(lo, hi, k=8)
+    assert idx.tolist() == [1, 3, 0, 2, 4, -1, -1, -1] and np.all(np.isneginf(best[5:])) and best[0] == best[1] > best[2]
+    # M = 257, the maximum in rows 255 and 256 alone (around the boundary of the partial second workgroup): the lower index first
+    X257 = np.zeros((257, 2))
+    X257[255:] = 1.0
+    eng.upload_candidates(X257)
+    for k in (1, 2):
+        best, idx = eng.forest_sweep_ehvi(lo, hi, k=k)
+        assert idx.tolist() == [255, 256][:k] and np.all(best == best[0])
+    eng.upload_candidates(np.array([[0.0, 0.0], [1.0, 1.0], [0.5, 0.25], [0.6, 0.3]]))  # (the four rows the lines below read)
     # a one-output forest on the same handle sweeps as before, and the multi-output calls refuse it
     t1 = dict(_tiny(1), value=_tiny(1)["value"][:, 0])
     t1.pop("m")
