@@ -9,7 +9,8 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
   bogp.Constrained               EI / PI / EpsilonPI / MGFI weighted by the probability that modelled constraints hold: the
                                  h_vals / g_vals the reference's tell() accepts and drops (one device pass, bogp_sweep_constrained)
   bogp.ConstrainedEHVI           EHVI of the feasible front weighted by the same probability: the h_vals / g_vals BaseMOBO.tell leaves
-                                 as a TODO (mobo.py:117-118; one device pass, bogp_sweep_ehvi_constrained)
+                                 as a TODO (mobo.py:117-118; one device pass, bogp_sweep_ehvi_constrained);
+                                 bogp.constrained_ehvi_believer_batch: its q-point proposals by the Kriging believer
   bogp.pareto                    Pareto front + cell decomposition of the non-dominated region (numpy)
   bogp.RandomForest              <-> bayes_optim.surrogate.RandomForest        (scikit-learn fits, the device predicts;
                                  bogp.forest: packing, mixed-space sweep; built on first access, sklearn imported lazily)
@@ -29,7 +30,7 @@ __version__ = "0.1.0"
 from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto, thompson  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
 from .acquisition import EHVI, EI, MGFI, PI, UCB, Constrained, ConstrainedEHVI, EpsilonPI  # noqa: E402,F401
-from .optim import argmax_restart, batch_argmax, believer_batch, constrained_believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
+from .optim import argmax_restart, batch_argmax, believer_batch, constrained_believer_batch, constrained_ehvi_believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
 from .integration import feasible_front, feasible_xopt, install, uninstall  # noqa: E402,F401
 from .lift import Lift  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401

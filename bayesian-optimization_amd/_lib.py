@@ -90,6 +90,9 @@ SIGNATURES = {
     "bogp_sweep_believer_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int,
                                                   _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "bogp_believer_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_believer_ehvi_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                       C.c_int, _dp, _lp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "bogp_believer_ehvi_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
     "bogp_lift_set": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bogp_lift_clear": (C.c_int, [C.c_void_p]),
     "bogp_lift_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp, _lp, _dp, _dp]),
@@ -919,6 +922,65 @@ class Engine:
         c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
         self._check(self._lib.bogp_believer_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
                                                              C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, criterion_ms=e.value, n_passes=n.value)
+
+    def sweep_believer_ehvi_constrained(self, front, ref_point, q: int, lo, hi, pending=None, believe_front=True, feasibility_only=False,
+                                        return_values=False):
+        """Kriging-believer batch under constrained EHVI over the current candidates (bogp_sweep_believer_ehvi_constrained): step j
+        maximises EHVI of the first m = len(ref_point) targets x the probabilities that the remaining c = len(lo) targets are feasible
+        in [lo, hi], on the m + c means and on the variances conditioned on the `pending` rows (n, d) and on the winners of the steps
+        before it, over the cells of the front of `front` (the objective rows of the feasible observations, (n_front, m); may be
+        empty) above `ref_point`.  With `believe_front` the objective part of a believed mean joins that front when every constraint
+        mean lies in its closed interval.  `feasibility_only`: no feasible observation exists; every step maximises the probability of
+        feasibility alone (no cells, `front` must be empty).  Returns a dict: best_val (q,), best_idx (q,), best_x (q, d), best_mu
+        (q, m + c), pivots (n + q,), n_cells (q,) and, with return_values, val (q, M), pof (q, M) and mse (q, M, m + c).  What the
+        library refuses as unsupported (a forest, a lift, a polynomial basis, several ranks) raises NotImplementedError with its
+        message."""
+        r = _f64(ref_point).ravel()
+        m, q = len(r), int(q)
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        mt = m + len(lo)
+        F = None if front is None or np.size(front) == 0 else _f64(front)
+        if F is not None and (F.ndim != 2 or F.shape[1] != m):
+            raise ValueError("the front must have shape (n, %d)" % m)
+        pend = None if pending is None or len(pending) == 0 else _f64(pending)
+        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
+            raise ValueError("pending points must have shape (n, %d)" % self.d)
+        n_pend = 0 if pend is None else pend.shape[0]
+        qa = max(q, 0)
+        best = np.empty(qa)
+        idx = np.empty(qa, dtype=np.int64)
+        bx = np.empty((qa, self.d))
+        bmu = np.empty((qa, mt))
+        piv = np.empty(n_pend + qa)
+        nc = np.zeros(qa, dtype=np.int32)
+        vals = np.empty((qa, self.M)) if return_values else None
+        pof = np.empty((qa, self.M)) if return_values else None
+        mse = np.empty((qa, self.M, mt)) if return_values else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        try:
+            self._check(self._lib.bogp_sweep_believer_ehvi_constrained(self._h, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F),
+                                                                       int(bool(feasibility_only)), int(bool(believe_front)), len(lo), _ptr(lo),
+                                                                       _ptr(hi), _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx),
+                                                                       _ptr(bmu), _ptr(piv), nc.ctypes.data_as(_ip), _ptr(vals), _ptr(pof),
+                                                                       _ptr(mse)))  # fmt: skip
+        except BogpError as e:
+            if e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, n_cells=nc)
+        if return_values:
+            out.update(val=vals, pof=pof, mse=mse)
+        return out
+
+    def believer_ehvi_constrained_last(self) -> dict:
+        """Producer, solve, k_believer and k_believer_ehvi_constrained time (ms) and the candidate passes of the last
+        sweep_believer_ehvi_constrained (bogp_believer_ehvi_constrained_last)."""
+        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_believer_ehvi_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp),
+                                                                  C.cast(C.byref(u), _dp), C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, criterion_ms=e.value, n_passes=n.value)
 
     # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------

@@ -540,11 +540,13 @@ class ConstrainedEHVI:
     `model.y[:, :m]`, the feasible rows those whose constraint columns of `model.y` lie inside their bounds (`n_feasible` of them).  A
     feasible set with no row above the reference point has the one cell [ref, +inf); with no feasible row at all the criterion
     is the probability of feasibility alone (`feasibility_only`; Gelbart, Snoek, Adams 2014).  `cells=(lower, upper)` replaces the
-    decomposition.
+    decomposition; such a criterion carries no front (`from_cells` is True and `pareto_Y` None -- `pareto_Y` is also None when no
+    row is feasible, which `from_cells` tells apart).
 
     `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the engine's
-    current candidates as `EHVI.sweep` does.  By default there is no input gradient (`return_dx=True` raises); there is no batch
-    strategy; the sweep helpers serve it where they serve `EHVI`: alone in its sweep, on one rank.
+    current candidates as `EHVI.sweep` does.  By default there is no input gradient (`return_dx=True` raises); the sweep helpers
+    serve it where they serve `EHVI`: alone in its sweep, on one rank.  Its one batch strategy is the Kriging believer of
+    `optim.constrained_ehvi_believer_batch` (`bogp_sweep_believer_ehvi_constrained`); every other batch entry refuses it by name.
 
     `input_gradient=True` (an extension): `criterion(X, return_dx=True)` returns (values, dx) in the shapes
     `EHVI(input_gradient=True)` returns -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through
@@ -589,6 +591,7 @@ class ConstrainedEHVI:
         feasible = np.all((y[:, m:] >= self.lo) & (y[:, m:] <= self.hi), axis=1)
         self.n_feasible = int(feasible.sum())
         self.pareto_Y = None
+        self.from_cells = cells is not None  # (pareto_Y is None both for cells= and for "no feasible row": this tells them apart)
         if cells is not None:
             lower, upper = (np.atleast_2d(np.asarray(c, dtype=float)) for c in cells)
         else:

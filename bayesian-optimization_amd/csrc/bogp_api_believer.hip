@@ -1,5 +1,5 @@
 // bogp_api_believer.hip -- the C ABI of libbogp.so (include/bogp.h) for Kriging-believer batches: q proposals from q steps where step j
-// sees the variance conditioned on the pending points and on the winners of the steps before it.  Three entries, ONE recursion
+// sees the variance conditioned on the pending points and on the winners of the steps before it.  Four entries, ONE recursion
 // (believer_run): an entry keeps its argument checks, its pass 0 (run_sweep with the family's request: mu, the clamped MSE_0 and --
 // without pending points -- step 0's criterion and argmax, the family's plain sweep bit for bit) and hands over what differs.
 //   per believed p    a solve a = V^T (V r(p)) with the kernels of bogp_gradient, the p-by-p terms on the host (at most 32 x 32), then ONE
@@ -8,14 +8,14 @@
 // A row that is a winner keeps its criterion value in the outputs but leaves the argmax of the later steps.  The running variance
 // is kept as sigma2 s, started from the sweep's clamped MSE_0: where s_0 < 0 the clamp changes nothing that is returned (s only
 // decreases, and every output is max(0, .) of it).
-//                                 bogp_sweep_believer            bogp_sweep_believer_ehvi               bogp_sweep_believer_constrained
-//   a believed mean               lowers the plugin              joins the front (m-vector)             lowers the plugin if feasible
-//   a step's criterion            k_believer itself, per chunk   k_believer_ehvi, one launch, after     k_believer_constrained, likewise
+//                                 bogp_sweep_believer            bogp_sweep_believer_ehvi               bogp_sweep_believer_constrained        bogp_sweep_believer_ehvi_constrained
+//   a believed mean               lowers the plugin              joins the front (m-vector)             lowers the plugin if feasible          its objectives join the front if feasible
+//   a step's criterion            k_believer itself, per chunk   k_believer_ehvi, one launch, after     k_believer_constrained, likewise       k_believer_ehvi_constrained, likewise
 //                                 (one record per 64 rows)       k_believer stored c(x) in unit variance (one record per 256 rows)
-//   a column c_k(x) is stored     when a later pass reads it     for every point past the guard         likewise
-//   a guarded pivot before a step k_believer without the update  the criterion kernel alone (c = null)  likewise
-//   before a step                 --                             the front's cells, rebuilt + uploaded  --
-//   a winner's mean is believed   also behind the last step      between two steps only                 likewise
+//   a column c_k(x) is stored     when a later pass reads it     for every point past the guard         likewise                               likewise
+//   a guarded pivot before a step k_believer without the update  the criterion kernel alone (c = null)  likewise                               likewise
+//   before a step                 --                             the front's cells, rebuilt + uploaded  --                                     the feasible front's cells, likewise
+//   a winner's mean is believed   also behind the last step      between two steps only                 likewise                               likewise
 // The m targets share the bracket of gpr.py:502-510, so ONE downdate in correlation units serves them all.
 #include <hip/hip_runtime.h>
 
@@ -56,8 +56,9 @@ struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point
   }
 };
 
-// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi, k_believer_constrained
-enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI, B_CONSTRAINED };
+// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi, k_believer_constrained,
+// k_believer_ehvi_constrained
+enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI, B_CONSTRAINED, B_EHVI_CONSTRAINED };
 
 // The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, one solve span -- and the
 // host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
@@ -119,15 +120,16 @@ int believer_chunk(bogp_handle* h, const SweepGeometry& pl, const BelieverArgs& 
 }
 
 // ---- the recursion, once ----------------------------------------------------------------------------------------------------------
-// The handle's believer arrays are shared by the three families and laid out per call (M candidates, m targets, B = n_pending + q
+// The handle's believer arrays are shared by the four families and laid out per call (M candidates, m targets, B = n_pending + q
 // believed points; every call sizes and fills them anew, nothing is carried from the call before):
 //                  dbel_s    dbel_row: `lead` rows of M, then the MSE block        dbel_C [columns][M] c_k(x)
 //   one target     [M]       [values | MSE M]                          lead 1      B - 2: the last winner runs no pass, the point before
 //                                                                                  it stores no column (no pass reads it)
 //   EHVI           [M][m]    [EHVI | scratch | MSE M x m]              lead 2      B - 1: the criterion kernel reads every column
 //   constrained    [M][m]    [values | PoF | scratch | MSE M x m]      lead 3      B - 1
+//   constr. EHVI   [M][m]    [values | PoF | scratch | MSE M x m]      lead 3      B - 1   (m = objectives + constraints)
 // dbel_s is sigma2_k s_B(x), unclamped below the sweep's own clamp of s_0; `scratch` is k_believer's own s in unit variance (m > 1: not
-// used); dbel_small is SolveBufs; dehvi_cells ([lower C x m | upper C x m]) is the EHVI entry's alone.
+// used); dbel_small is SolveBufs; dehvi_cells ([lower C x m | upper C x m], m the objectives) is the two EHVI entries' alone.
 
 struct StepRows {  // rows of step j for the caller: out + j n <- the sweep's own array (step 0 without pending points) or dbel_row + at M
   double* out;     // null: not wanted
@@ -671,6 +673,149 @@ extern "C" int bogp_believer_constrained_last(bogp_handle* h, double* corr_ms, d
   if (solve_ms) *solve_ms = h->bel_solve_ms;
   if (update_ms) *update_ms = h->bel_pass_ms;
   if (criterion_ms) *criterion_ms = h->bel_con_ms;
+  if (n_passes) *n_passes = h->bel_passes;
+  return BOGP_OK;
+}
+
+// ---- believer batches for constrained EHVI: bogp_sweep_believer_ehvi_constrained ---------------------------------------------------
+// Pass 0 is the constrained EHVI sweep (k_ehvi_constrained); k_believer_ehvi_constrained (kernels_believer_ehvi_constrained.hip) takes
+// sigma2_k c^2 off every target's MSE and evaluates EHVI of the objectives times the constraints' feasibility.  A believed mean is the
+// full (m_obj + n_con)-vector: its objective part joins the feasible front if and only if every constraint mean lies in its closed
+// interval -- the test bogp_sweep_believer_constrained uses for the plugin; a point infeasible by belief conditions the variances only.
+// A feasibility-only call (no feasible observation: C = 0, the probability of feasibility alone) stays so for all q steps.
+extern "C" int bogp_sweep_believer_ehvi_constrained(bogp_handle* h, int m_obj, int q, const double* ref_point, const double* front, int n_front,
+                                                    int feasibility_only, int believe_front, int n_con, const double* lo, const double* hi,
+                                                    const double* pending, int n_pending, double* best_val, int64_t* best_idx, double* best_x,
+                                                    double* best_mu, double* pivots, int* n_cells, double* val_out, double* pof_out,
+                                                    double* mse_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_believer_ehvi_constrained";
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior correlation to condition on", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (!h->dXs || h->M <= 0) FAIL(h, BOGP_ERR_INVALID, "%s: no candidates: call bogp_candidates_upload/bind first", who);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+  const int m = h->n_t;
+  if (m_obj < 2) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj = %d objectives; EHVI needs at least 2", who, m_obj);
+  if (n_con < 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d constraints; without one this is bogp_sweep_believer_ehvi", who, n_con);
+  if (m > BOGP_MAX_TARGETS || m_obj + n_con != m) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj + n_con = %d + %d but the committed model has %d targets (at most %d)", who, m_obj, n_con, m, BOGP_MAX_TARGETS);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  if (q < 1 || n_pending < 0 || q + n_pending > BOGP_MAX_BELIEVED)
+    FAIL(h, BOGP_ERR_INVALID, "%s: q = %d, n_pending = %d: q >= 1 and q + n_pending <= %d", who, q, n_pending, BOGP_MAX_BELIEVED);
+  if (q > h->M) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d proposals from %lld candidates (every step takes a row no step before it took)", who, q, (long long)h->M);
+  if (!ref_point || !lo || !hi || !best_val || !best_idx) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point, lo, hi, best_val and best_idx must be non-null", who);
+  if (n_front < 0 || (n_front > 0 && !front)) FAIL(h, BOGP_ERR_INVALID, "%s: n_front = %d and front is %s", who, n_front, front ? "given" : "null");
+  if (n_pending > 0 && !pending) FAIL(h, BOGP_ERR_INVALID, "%s: n_pending = %d but pending is null", who, n_pending);
+  if (feasibility_only && n_front > 0) FAIL(h, BOGP_ERR_INVALID, "%s: feasibility_only means no feasible observation, but n_front = %d", who, n_front);
+  const int d = h->d;
+  for (int k = 0; k < m_obj; ++k)
+    if (!std::isfinite(ref_point[k])) FAIL(h, BOGP_ERR_INVALID, "%s: ref_point entry %d is not finite", who, k);
+  for (size_t i = 0; i < (size_t)n_front * m_obj; ++i)
+    if (!std::isfinite(front[i])) FAIL(h, BOGP_ERR_INVALID, "%s: front entry %zu is not finite", who, i);
+  for (size_t i = 0; i < (size_t)n_pending * d; ++i)
+    if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
+  int rc;
+  if ((rc = check_constraint_bounds(h, who, n_con, lo, hi))) return rc;
+  const int64_t M = h->M;
+  const int P = n_pending;
+
+  // ---- the feasible front and its cells (host): F_0 now, one believed mean more per step where it is feasible by belief
+  std::vector<double> F = pareto_front_rows(m_obj, n_front, front, ref_point);
+  std::vector<std::vector<double>> edges;
+  std::vector<double> cells;  // [lower C x m_obj | upper C x m_obj] of the step evaluated next
+  int C = 0;
+  auto build_cells = [&](int step) -> int {
+    if (feasibility_only) return BOGP_OK;  // (C stays 0: no cells in any step)
+    const int64_t count = grid_edges(m_obj, F, ref_point, BOGP_MAX_EHVI_CELLS, edges);
+    if (count < 0)
+      FAIL(h, BOGP_ERR_INVALID, "%s: step %d: the front of %zu points in %d objectives gives %lld cells (more than %d)", who, step,
+           F.size() / m_obj, m_obj, grid_count_saturated(edges), BOGP_MAX_EHVI_CELLS);
+    C = (int)count;
+    cells.resize(2 * (size_t)C * m_obj);
+    grid_fill(m_obj, F, ref_point, edges, count, cells.data(), cells.data() + (size_t)C * m_obj);
+    return BOGP_OK;
+  };
+  if ((rc = build_cells(0))) return rc;  // before any device work (with pending points: the cells of F_0, which step 0 extends)
+
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  auto upload_cells = [&]() -> int {  // in stream order, before the pass that reads them; `cells` stays as it is until that pass is complete
+    const size_t nb = (size_t)C * m_obj;
+    if (int e = h->dehvi_cells.ensure(h, std::max<size_t>(2 * nb, 2))) return e;  // (allocated for a pass over no cells too)
+    return stage_ehvi_cells(h, cells.data(), cells.data() + nb, nb, st);
+  };
+
+  // ---- pass 0: bogp_sweep_ehvi_constrained's sweep; with pending points over no cells, for the moments only
+  const int C0 = P == 0 ? C : 0;
+  if (P > 0) C = 0;
+  if ((rc = upload_cells())) return rc;
+  if ((rc = h->dpof_out.ensure(h, (size_t)M))) return rc;
+  ConstrainedEhviArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.gamma = h->dgamma_base; ea.ld_gamma = h->Np; ea.N = h->N; ea.m = m; ea.m_obj = m_obj; ea.C = C0;
+  for (int t = 0; t < m; ++t) ea.sigma2[t] = h->sigma2_t[t];
+  for (int j = 0; j < n_con; ++j) { ea.lo[j] = lo[j]; ea.hi[j] = hi[j]; }
+  if (C0 > 0) { ea.lower = h->dehvi_cells; ea.upper = h->dehvi_cells + (size_t)C0 * m_obj; }
+  ea.pof_out = h->dpof_out.ptr;
+  invalidate_sweep_results(h);  // dbest_* are overwritten
+  const int one_id = BOGP_ACQ_EI;  // (q = 1 sizes the chunk loop's block records; the id itself is not evaluated)
+  SweepRequest rq;
+  rq.want_out = true; rq.want_acq_out = true; rq.q = 1; rq.acq_id = &one_id; rq.minimize = 0; rq.ec = &ea;
+  if ((rc = run_sweep(h, rq))) return rc;
+  if ((rc = candidates_ready(h))) return rc;
+  if (P == 0 && n_cells) n_cells[0] = C0;
+
+  BelieverFamily f;
+  f.who = who; f.m = m; f.lead = 3; f.span = B_EHVI_CONSTRAINED;
+  f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
+  f.rows[0] = {val_out, &h->dacq_out, 0, 1};
+  f.rows[1] = {pof_out, &h->dpof_out, 1, 1};
+  f.rows[2] = {mse_out, &h->dmse_out, 3, m};
+  // a believed point that is feasible by belief -- every constraint's mean inside its closed interval -- joins the front with its
+  // objective part, F <- pareto_front(F u {mu_0 .. mu_{m_obj-1}}); an infeasible one leaves it
+  f.mean = [&](const double* mu) {
+    if (!believe_front || feasibility_only) return;
+    for (int j = 0; j < n_con; ++j)
+      if (!(lo[j] <= mu[m_obj + j] && mu[m_obj + j] <= hi[j])) return;
+    F.insert(F.end(), mu, mu + m_obj);
+    F = pareto_front_rows(m_obj, (int64_t)(F.size() / m_obj), F.data(), ref_point);
+  };
+  f.step_begin = [&](int step) -> int {  // the step's cells are those of the feasible front as it stands here
+    if (int rs = build_cells(step)) return rs;
+    if (int rs = upload_cells()) return rs;
+    if (n_cells) n_cells[step] = C;
+    return BOGP_OK;
+  };
+  f.criterion = [&](int step, int64_t row, const double* c) {
+    BelieverEhviConstrainedArgs be;
+    memset(&be, 0, sizeof(be));
+    be.M = M; be.m = m; be.m_obj = m_obj; be.update = c ? 1 : 0; be.c = c;
+    be.self_row = row; be.s = h->dbel_s;
+    for (int t = 0; t < m; ++t) be.sigma2[t] = ea.sigma2[t];
+    for (int j = 0; j < n_con; ++j) { be.lo[j] = lo[j]; be.hi[j] = hi[j]; }
+    be.eval = step >= 0 ? 1 : 0;
+    if (step >= 0) {
+      be.n_taken = step;  // the winners of steps 0 .. step - 1
+      for (int k = 0; k < step; ++k) be.taken[k] = best_idx[k];
+      be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m_obj; be.C = C;
+    }
+    be.mu = h->dmu_out; be.val_out = h->dbel_row; be.pof_out = h->dbel_row + M; be.mse_out = h->dbel_row + 3 * M;
+    be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
+    return launch_believer_ehvi_constrained(be, st);
+  };
+  if ((rc = believer_run(h, f, q, pending, P))) return rc;
+  h->bel_ehvi_con_ms = h->bel_timer.sum(B_EHVI_CONSTRAINED);
+  return BOGP_OK;
+}
+
+extern "C" int bogp_believer_ehvi_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
+                                                   int* n_passes) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (corr_ms) *corr_ms = h->bel_corr_ms;
+  if (solve_ms) *solve_ms = h->bel_solve_ms;
+  if (update_ms) *update_ms = h->bel_pass_ms;
+  if (criterion_ms) *criterion_ms = h->bel_ehvi_con_ms;
   if (n_passes) *n_passes = h->bel_passes;
   return BOGP_OK;
 }

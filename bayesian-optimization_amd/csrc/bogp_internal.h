@@ -384,6 +384,34 @@ struct BelieverConstrainedArgs {
 };
 hipError_t launch_believer_constrained(const BelieverConstrainedArgs& a, hipStream_t st);
 
+// the (m + c)-target half of a believer pass for constrained EHVI (kernels_believer_ehvi_constrained.hip), ONE launch over all M rows
+// behind the chunk loop in which k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a
+// step -- feasibility-weighted EHVI over that step's cells on (mu, max(0, MSE)) by k_ehvi_constrained's conventions (targets
+// 0 .. m_obj - 1 the objectives, target m_obj + j the constraint feasible in [lo[j], hi[j]]) with one argmax record per 256 rows
+struct BelieverEhviConstrainedArgs {
+  int64_t M;
+  int m, m_obj;           // targets, 3 .. BOGP_MAX_TARGETS; objectives among them, 2 .. m - 1
+  int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
+  const double* c;        // [M] c(x) of the believed point
+  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
+  double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
+  double sigma2[8];       // per target
+  double lo[8], hi[8];    // per constraint: entry j belongs to target m_obj + j
+  int eval;               // evaluate the criterion behind the update
+  int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
+  int64_t taken[32];
+  const double* mu;       // [M][m]
+  const double* lower;    // [C][m_obj] cell bounds of the step's feasible front (device); not read for C == 0
+  const double* upper;    // [C][m_obj] (+inf allowed)
+  int C;                  // 0: the probability of feasibility alone
+  double* val_out;        // [M]
+  double* pof_out;        // [M]
+  double* mse_out;        // [M][m] max(0, MSE): what the step saw
+  double* blk_val;        // [ceil(M / 256)]
+  int64_t* blk_idx;
+};
+hipError_t launch_believer_ehvi_constrained(const BelieverEhviConstrainedArgs& a, hipStream_t st);
+
 // q sample paths over a chunk (kernels_thompson.hip): path_j(x) = mu(x) + z_j(x) - r(x) . g_j - b_j with the random-Fourier-feature draw
 // z_j(x) = sum_l W[l][j] cos(omega_l . x + phase_l), one np.argmax record per path and 64 rows
 struct ThompsonArgs {

@@ -15,6 +15,10 @@ What is re-pointed (INTEGRATION.md sections 3-4; all undone by the returned call
   MOBO._create_acquisition                      -> mobo_create_acquisition (this package's EHVI for a device model
                                                    under the sweep family; the reference's EHVI otherwise; with constraint
                                                    values stored under install(constrained_mobo=True): bogp.ConstrainedEHVI)
+  MOBO._batch_arg_max_acquisition (inherited)   -> mobo_batch_arg_max_acquisition (raises as the inherited method unless
+                                                   install(batch_strategy="believer"): optim.ehvi_believer_batch; with constraint
+                                                   values stored, unless install(constrained_mobo_batches="believer"):
+                                                   optim.constrained_ehvi_believer_batch)
   BaseMOBO.tell, BaseMOBO.update_model          -> refusing_mobo_tell, constrained_mobo_update_model (the originals unless
                                                    install(expensive_constraints=True) AND the tell carries h_vals / g_vals)
   bayes_optim.GaussianProcess, bayes_optim.surrogate.GaussianProcess, bayes_optim.extension.GaussianProcess
@@ -194,13 +198,26 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
     and leaves open (mobo.py:168-178; the inherited BaseBO method raises NotImplementedError, base.py:496-497).  Taken for a device
     GP, an inner optimiser of the sweep family, a continuous space, nothing fixed and no constraints: `optim.ehvi_believer_batch` on
     the criterion `mobo_create_acquisition` builds.  Everything else -- the default `install()` above all -- calls the inherited
-    method, which raises as it does without this package."""
+    method, which raises as it does without this package.
+    After a tell() that carried constraint values (`install(constrained_mobo=True)`) the batch is
+    `optim.constrained_ehvi_believer_batch` on `bogp.ConstrainedEHVI` under `install(constrained_mobo_batches="believer")` and the
+    same conditions (no cheap h / g); without that switch, and in every other configuration, it raises NotImplementedError."""
+    optimizer, budget = _effective(getattr(self, "_optimizer", None), None)
+    kw = getattr(getattr(self, "_argmax_restart", None), "keywords", None) or {}
     if getattr(self, "_bogp_constraints", None) is not None:
+        # install(..., constrained_mobo_batches="believer"): the believer under constrained EHVI, where everything it needs holds;
+        # every other configuration -- the default above all -- raises instead of dropping the constraints
+        if (_CONSTRAINTS.get("mobo_batches") == "believer" and _CONSTRAINTS.get("mobo") and not fixed and optimizer in _SWEEPS
+                and is_device_model(getattr(self, "model", None)) and optim.is_continuous(kw.get("search_space"))
+                and kw.get("h") is None and kw.get("g") is None):  # fmt: skip
+            lo, hi = _constraint_bounds(self)
+            criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
+            xs, fs = optim.constrained_ehvi_believer_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
+                                                           design=optim.DEVICE_DESIGNS.get(optimizer))  # fmt: skip
+            return tuple(xs), tuple(fs)
         raise NotImplementedError("MOBO(n_point=q) under expensive constraints: constrained EHVI (bogp.ConstrainedEHVI) has no batch "
                                   "strategy; ask for one point at a time")  # fmt: skip
     inherited = super(_ORIGINAL["mobo_cls"], self)._batch_arg_max_acquisition
-    optimizer, budget = _effective(getattr(self, "_optimizer", None), None)
-    kw = getattr(getattr(self, "_argmax_restart", None), "keywords", None) or {}
     if (_BATCH.get("strategy") != "believer" or fixed or optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None))
             or not optim.is_continuous(kw.get("search_space")) or kw.get("h") is not None or kw.get("g") is not None):  # fmt: skip
         return inherited(n_point, return_dx, fixed)
@@ -627,7 +644,7 @@ def _dispatching_surrogate(host_cls):
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
-            constrained_mobo_gradient: bool = False):
+            constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk"):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -680,13 +697,25 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     (`refusing_mobo_tell`, by `constrained_tell`'s rules), fits objectives and constraints as one multi-target model
     (`constrained_mobo_update_model`) and maximises `bogp.ConstrainedEHVI` -- EHVI over the cells of the feasible front times the
     probability that g <= 0 and |h| <= `equality_tol` -- under the sweep family on a continuous space; any other inner optimiser and
-    `MOBO(n_point=q)` raise instead of dropping the constraints.  `bogp.feasible_front(bo)` is the feasible non-dominated set.  Without
+    `MOBO(n_point=q)` (without `constrained_mobo_batches="believer"`) raise instead of dropping the constraints.  `bogp.feasible_front(bo)` is the feasible non-dominated set.  Without
     it a MOBO tell() with constraint values is refused by name as before.
 
     `constrained_mobo_gradient=True` (with `constrained_mobo=True`; without it ValueError): such a MOBO also accepts "BFGS", "sweep-BFGS"
     and "sweep-device-BFGS" after a tell() that carried constraint values and maximises `bogp.ConstrainedEHVI(input_gradient=True)` --
     the input gradient of `bogp_point_eval_ehvi_constrained` and the lock-step polish `bogp_polish_ehvi_constrained`.  Without it
-    those optimisers raise as before."""
+    those optimisers raise as before.
+
+    `constrained_mobo_batches` = "topk" | "believer" ("believer" with `constrained_mobo=True`; alone it raises ValueError; any other
+    value raises ValueError): what `MOBO(n_point=q)` does after a tell() that carried constraint values.  "topk" (default): it raises
+    NotImplementedError as before (top-k batches of constrained EHVI crowd into one pocket of the feasibility boundary and are
+    not offered).  "believer": `optim.constrained_ehvi_believer_batch` -- step j sees the m + c variances conditioned on the
+    winners before it, and a believed point that is feasible by belief joins the feasible front -- for a device GP, an inner
+    optimiser of the sweep family, a continuous space, nothing fixed and no cheap h / g; every other configuration raises as
+    before."""
+    if constrained_mobo_batches not in ("topk", "believer"):
+        raise ValueError("constrained_mobo_batches must be 'topk' or 'believer', not %r" % (constrained_mobo_batches,))
+    if constrained_mobo_batches == "believer" and not constrained_mobo:
+        raise ValueError("constrained_mobo_batches='believer' needs constrained_mobo=True (it batches constrained EHVI)")
     if constrained_mobo and not expensive_constraints:
         raise ValueError("constrained_mobo=True needs expensive_constraints=True (it keeps the h_vals / g_vals of a multi-objective tell())")
     if constrained_mobo_gradient and not constrained_mobo:
@@ -710,6 +739,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["mobo"] = True
         if constrained_mobo_gradient:
             _CONSTRAINTS["mobo_gradient"] = True
+        if constrained_mobo_batches == "believer":
+            _CONSTRAINTS["mobo_batches"] = "believer"
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

@@ -742,6 +742,66 @@ def constrained_believer_batch(criteria, search_space, eval_budget: int, q: Opti
     return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
 
 
+def constrained_ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None,
+                                    design: Optional[str] = None, seed: Optional[int] = None, pending=None, believe_front: bool = True,
+                                    lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None,
+                                    group=None, rank=None, world=None):
+    """A q-point proposal for a multi-objective run under modelled constraints by the Kriging believer
+    (`bogp_sweep_believer_ehvi_constrained`): ONE posterior pass over the m + c targets, then one streaming pass over the candidates
+    per proposed point.  Step j maximises EHVI of the objectives times the constraints' probabilities of feasibility on the
+    posterior means and on the variances conditioned on `pending` (rows submitted but not yet evaluated, (n, d)) and on the
+    winners of the steps before it, over the cells of the FEASIBLE front -- which, with `believe_front`, the objective part of a
+    believed mean joins before the next step if and only if every believed constraint value lies inside its closed interval (a
+    point infeasible by belief conditions the variances only).  A criterion without a feasible row (`feasibility_only`) stays the
+    probability of feasibility alone for all q steps.
+    `criterion`: a `bogp.ConstrainedEHVI` built with `Y=` or from the model's own rows; one built from `cells=` has no front to
+    extend and is refused (ValueError).  Candidates as in `believer_batch`.  Returns (xopt: tuple of q lists, fopt: tuple of q
+    floats) in `believer_batch`'s format.
+    TypeError: a criterion that is not `bogp.ConstrainedEHVI`.  Refused (NotImplementedError): a forest model, a lift, fixed
+    variables, cheap constraints h / g, more than one rank."""
+    if not is_constrained_ehvi(criterion):
+        raise TypeError("constrained_ehvi_believer_batch takes a %s criterion (EHVI goes to ehvi_believer_batch, bogp.Constrained to "
+                        "constrained_believer_batch, the single-objective criteria to believer_batch)" % _CEHVI)  # fmt: skip
+    model = criterion.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no believer batches under constrained EHVI")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no believer batches under constrained EHVI")
+    if h is not None or g is not None:
+        raise NotImplementedError("cheap constraints h / g have no believer batches under constrained EHVI: model them as columns of y")
+    if getattr(criterion, "from_cells", False):
+        raise ValueError("a ConstrainedEHVI built from cells= has no front to extend with the believed means: build it with Y= or "
+                         "from the model's rows")  # fmt: skip
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    q = int(q)
+    if q < 1:
+        raise ValueError("q = %d: the believer proposes at least one point" % q)
+    if q + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
+        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
+    if design is not None:
+        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
+    m = criterion.n_obj
+    feasibility_only = criterion.n_feasible == 0  # (no feasible observation; a feasible set below ref_point has the one cell)
+    front = np.zeros((0, m)) if criterion.pareto_Y is None else np.asarray(criterion.pareto_Y, dtype=float).reshape(-1, m)
+    out = eng.sweep_believer_ehvi_constrained(front, criterion.ref_point, q, criterion.lo, criterion.hi, pending=pend,
+                                              believe_front=believe_front, feasibility_only=feasibility_only)
+    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+
+
 def unwrap_criterion(obj):
     """Find the acquisition object behind what `BaseBO._create_acquisition` hands to `argmax_restart`
     (base.py:482-494): `partial_argument(functools.partial(criterion, return_dx=...), var_name, fixed)` -- a

@@ -496,6 +496,50 @@ int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int* acq_id, co
 int bogp_believer_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
                                    int* n_passes);
 
+/* ---- sweep: Kriging-believer batches for constrained EHVI --------------------------------------------------
+ * q proposals per call for a multi-objective run whose simulation also returns constraints (bogp_sweep_ehvi_constrained's model:
+ * targets 0 .. m_obj - 1 the objectives, maximised as given, target m_obj + j the constraint feasible in [lo_j, hi_j], constant
+ * basis).  The bracket is shared by the m = m_obj + n_con targets, so kappa0, b_i, pivot_i and c_i are those of
+ * bogp_sweep_believer (pivot floor 1e-12 -> c_i = 0; the candidate row that is a winner gets variance exactly 0) and step j sees
+ * the means unchanged and
+ *   MSE_{k,j}(x) = max(0, MSE_{k,0}(x) - sigma2_k sum_i c_i(x)^2),   value_j = EHVI_j * P   as bogp_sweep_ehvi_constrained forms them
+ * from these moments: sd_k = sqrt(max(MSE_k, 1e-9)) for the objectives, P the product of bogp_feasibility over the constraints in
+ * index order from 1.0, the value exactly +0.0 where P == 0, P alone over no cells, a NaN P propagated.
+ * The front: F_0 = the non-dominated rows of `front` (the objective rows of the FEASIBLE observations) strictly above ref_point.
+ * A believed mean mu(p) is the full m-vector (beta + r(p).gamma_k for a pending point, the sweep's own means for a winner).
+ * With believe_front = 1 its objective part joins the front, F_B = front(F_{B-1} u {mu_{0..m_obj-1}(p_B)}), if and only if the
+ * point is feasible by belief -- lo_j <= mu_{m_obj+j}(p) <= hi_j for every constraint, the test bogp_sweep_believer_constrained
+ * applies to its plugin; a point infeasible by belief, and believe_front = 0, leave the front and condition the variances only.
+ * The cells of step j are bogp_ehvi_grid_cells of the front as it stands.
+ * feasibility_only != 0: no feasible observation exists; the criterion is P alone (C = 0, n_cells[j] = 0) in ALL q steps -- the
+ * criterion is the caller's, as a BOGP_ACQ_NONE step of bogp_sweep_believer_constrained stays feasibility-only -- and no believed
+ * mean starts a front.  It requires n_front = 0.
+ * Step j takes the argmax by bogp_sweep's rule over the rows that are not winners yet; the q winners are q distinct rows.
+ * Without pending points step 0 IS bogp_sweep_ehvi_constrained called with bogp_ehvi_grid_cells' cells (or C = 0), bit for bit.
+ *   front        n_front x m_obj HOST rows, NULL for n_front = 0: one cell [ref_point, +inf) unless feasibility_only
+ *   n_con, lo, hi   as bogp_sweep_ehvi_constrained;  pending: n_pending x d HOST rows, NULL for n_pending = 0
+ *   1 <= q <= M, q + n_pending <= BOGP_MAX_BELIEVED
+ *   best_val, best_idx (q): each step's winner.  Optional HOST buffers (NULL to skip): best_x (q x d), best_mu (q x m: the
+ *   believed means), pivots (n_pending + q), n_cells (q: the cells step j used), val_out (q x M), pof_out (q x M),
+ *   mse_out (q x M x m).
+ * Per believed point: the solve of bogp_sweep_believer, one streaming pass (producer + k_believer for c(x), per chunk) and one
+ * launch of k_believer_ehvi_constrained over all rows (8 (3 + 4 m) bytes a row plus the cell loop); the N^2 contraction runs
+ * once, in pass 0.  No bit depends on BOGP_CHUNK_MB.
+ * BOGP_ERR_INVALID: no committed model, no candidates, m_obj < 2, n_con < 1, m_obj + n_con != n_targets, q < 1, q > M, the limit
+ * exceeded, a null required array, feasibility_only with n_front > 0, a non-finite entry of ref_point / front / pending, NaN
+ * bounds or lo > hi, more than BOGP_MAX_EHVI_CELLS cells at any step (the message names the step and the count; step 0's count
+ * is checked before any device work).  BOGP_ERR_UNSUPPORTED: a forest handle, a lift, a polynomial trend basis, a communicator
+ * of more than one rank.  The handle's model, candidates and later sweeps are unaffected.
+ * `believer_ehvi_constrained_last`: of the last call, the time of the producer launches, of the solves, of k_believer and of
+ * k_believer_ehvi_constrained in ms, and the candidate passes behind pass 0; any pointer may be NULL.                        */
+int bogp_sweep_believer_ehvi_constrained(bogp_handle* h, int m_obj, int q, const double* ref_point, const double* front, int n_front,
+                                         int feasibility_only, int believe_front, int n_con, const double* lo, const double* hi,
+                                         const double* pending, int n_pending, double* best_val, int64_t* best_idx, double* best_x,
+                                         double* best_mu, double* pivots, int* n_cells, double* val_out, double* pof_out,
+                                         double* mse_out);
+int bogp_believer_ehvi_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
+                                        int* n_passes);
+
 /* ---- sweep in a reduced space: box-penalised criteria under a linear lift ---------------------------
  * Replaces PCABO's inner maximisation (extension.py:113-133): the criterion is maximised over a box of the REDUCED
  * space (r = the committed model's d, _compute_bounds :113-119) through penalized_acquisition (:62-86), which maps a

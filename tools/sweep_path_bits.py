@@ -8,7 +8,7 @@ exactly when their listings agree line for line:
 
 The cases are the smallest that reach each branch of run_sweep (csrc/bogp_api_sweep.hip): the <= 32-row batch, the one-launch
 sweep, the chunk loop with its trend variants / two streams / lazy upload, the queued sweep, both pruned flows with their
-fall-backs, EHVI, the believer batches of the three families (several chunks, one resident chunk, a guarded pivot in front of step 0),
+fall-backs, EHVI, the believer batches of the four families (several chunks, one resident chunk, a guarded pivot in front of step 0),
 Thompson batches and the lifted sweep.  Needs an MI355X."""
 import argparse
 import collections
@@ -186,6 +186,19 @@ def case_batches(_lib, np, rng, what):
         report(eng, "believer-constrained/q3", *[out[k] for k in sorted(out)])
         out = eng.sweep_believer_constrained(acq, float(y[:, 0].min()), True, lo, hi, pending=rng.uniform(-5, 5, (2, 4)), return_values=True)
         report(eng, "believer-constrained/q3-pending", *[out[k] for k in sorted(out)])
+    elif what == "believer-ehvi-constrained":  # m = 2 objectives + 1 constraint at inner quantiles; q = 3 over a front, then feasibility only
+        eng, X, y = smooth_model(_lib, rng, N, 4, targets=3)
+        eng.upload_candidates(rng.uniform(-5, 5, (M, 4)))
+        lo, hi = np.quantile(y[:, 2:], [0.25, 0.75], axis=0)
+        ok = np.all((y[:, 2:] >= lo) & (y[:, 2:] <= hi), axis=1)
+        rp = y[:, :2].min(axis=0) - 0.1
+        out = eng.sweep_believer_ehvi_constrained(y[ok, :2], rp, 3, lo, hi, return_values=True)
+        report(eng, "believer-ehvi-constrained/q3", *[out[k] for k in sorted(out)])
+        pend = rng.uniform(-5, 5, (2, 4))
+        out = eng.sweep_believer_ehvi_constrained(y[ok, :2], rp, 3, lo, hi, pending=pend, return_values=True)
+        report(eng, "believer-ehvi-constrained/q3-pending", *[out[k] for k in sorted(out)])
+        out = eng.sweep_believer_ehvi_constrained(None, rp, 3, lo, hi, pending=pend, feasibility_only=True, return_values=True)
+        report(eng, "believer-ehvi-constrained/q3-pending-feasibility-only", *[out[k] for k in sorted(out)])
     elif what == "thompson":  # conditioned, L = 64, q = 2, k = 1 and k = 3 (a noiseless model: the only mode it takes)
         d = 4
         X = rng.uniform(-2, 2, (N, d))
@@ -212,8 +225,8 @@ def case_batches(_lib, np, rng, what):
 
 
 def case_guard(_lib, np, rng, what):
-    """The guarded pivot in front of step 0, as the three test_pivot_guard tests construct it: the last pending point is a training
-    row of a noiseless model (pivot <= 1e-12), the plugin / front held fixed.  One, two and three targets."""
+    """The guarded pivot in front of step 0, as the test_pivot_guard tests construct it: the last pending point is a training
+    row of a noiseless model (pivot <= 1e-12), the plugin / front held fixed.  One, two and three targets (the three read as objective + constraints and as two objectives + one constraint)."""
     N, M, d = 700, 3000, 4
     X = rng.uniform(-2, 2, (N, d))
     Y = np.sin(X @ rng.normal(size=(d, 3))) * (1.0 + np.arange(3)) + 0.3 * rng.normal(size=(N, 3))
@@ -241,6 +254,8 @@ def case_guard(_lib, np, rng, what):
     acq = [(_lib.ACQ_EI, 0.0), (_lib.ACQ_NONE, 0.0), (_lib.ACQ_MGFI, 2.0)]
     guarded("believer-constrained/q3-guarded",
             eng.sweep_believer_constrained(acq, float(Y[:, 0].min()), True, lo, hi, pending=pend, believe_plugin=False, return_values=True))  # fmt: skip
+    guarded("believer-ehvi-constrained/q2-guarded",  # the same three-target model read as two objectives and one constraint
+            eng.sweep_believer_ehvi_constrained(front, rp, 2, lo[1:], hi[1:], pending=pend, believe_front=False, return_values=True))  # fmt: skip
     eng.close()
 
 
@@ -257,9 +272,11 @@ CASES = collections.OrderedDict([
     ("ehvi", (case_batches, "ehvi", {"BOGP_CHUNK_MB": "8"})),
     ("believer", (case_batches, "believer", {"BOGP_CHUNK_MB": "8"})),
     ("believer-constrained", (case_batches, "believer-constrained", {"BOGP_CHUNK_MB": "8"})),
+    ("believer-ehvi-constrained", (case_batches, "believer-ehvi-constrained", {"BOGP_CHUNK_MB": "8"})),
     ("ehvi-one-chunk", (case_batches, "ehvi", {})),  # the believers again with every candidate in one chunk: the producer runs once
     ("believer-one-chunk", (case_batches, "believer", {})),
     ("believer-constrained-one-chunk", (case_batches, "believer-constrained", {})),
+    ("believer-ehvi-constrained-one-chunk", (case_batches, "believer-ehvi-constrained", {})),
     ("believer-guard", (case_guard, "", {"BOGP_CHUNK_MB": "8"})),
     ("believer-guard-one-chunk", (case_guard, "", {})),
     ("thompson", (case_batches, "thompson", {"BOGP_CHUNK_MB": "8"})),
