@@ -217,6 +217,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
+def _pack_acq(acq: Sequence[Tuple[int, float]]) -> Tuple[np.ndarray, np.ndarray]:
+    """(ids int32 (q,), pars float64 (q,)) of q criteria; a parameter of None is 0."""
+    return np.ascontiguousarray([a for a, _ in acq], dtype=np.int32), _f64([float(p) if p is not None else 0.0 for _, p in acq])
+
+
 def feasibility(mu: float, mse: float, sigma2: float, lo: float, hi: float) -> float:
     """P(lo <= Y <= hi) for Y ~ N(mu, mse) as the constrained sweep forms it (bogp_feasibility: the indicator under EI's
     small-variance guard, else the difference of two normal cdfs taken in the tail the interval lies in).  No device is touched."""
@@ -631,8 +636,7 @@ class Engine:
         local_result=False only queues the sweep (no host wait, returns None): its winners stay on the device for the
         exchange_argmax() call that follows."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        ids, pars = _pack_acq(acq)
         self._last_q, self._last_topk = -1, (-1, -1)
         if not local_result:
             self._check(self._lib.bogp_sweep(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
@@ -652,8 +656,7 @@ class Engine:
     def sweep_topk(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, k: int = 1):
         """k best candidates per criterion: (values (q, k), indices (q, k)); rank 0 is the argmax."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        ids, pars = _pack_acq(acq)
         best = np.empty((q, k))
         idx = np.empty((q, k), dtype=np.int64)
         self._last_q, self._last_topk = -1, (-1, -1)
@@ -696,11 +699,8 @@ class Engine:
         Returns (best_val (q, k), best_idx (q, k)[, values (q, M)][, pof (M,)][, mu (M, m), mse (M, m)]); rank 0 is the argmax, slots
         beyond M are (-inf, -1)."""
         q, k = len(acq), int(k)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != len(hi):
-            raise ValueError("lo and hi must hold one bound per constraint each")
+        ids, pars = _pack_acq(acq)
+        lo, hi = self._constraint_bounds(lo, hi)
         m = len(lo) + 1
         best = np.empty((q, k))
         idx = np.empty((q, k), dtype=np.int64)
@@ -728,9 +728,7 @@ class Engine:
         may be infinite); value = EHVI x the product of the constraints' probabilities of feasibility P, and +0.0 where P == 0.
         Returns (best_val (k,), best_idx (k,)[, values (M,)][, pof (M,)][, mu (M, m + c), mse (M, m + c)]); rank 0 is the argmax,
         slots beyond M are (-inf, -1)."""
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != len(hi):
-            raise ValueError("lo and hi must hold one bound per constraint each")
+        lo, hi = self._constraint_bounds(lo, hi)
         lower = _f64(lower)
         upper = _f64(upper)
         if lower.ndim != 2 or lower.shape != upper.shape:
@@ -756,29 +754,71 @@ class Engine:
             out += (mu, mse)
         return out
 
+    # -- Kriging-believer batches (bogp_api_believer.hip): what the four families' methods do alike ----------------
+    @staticmethod
+    def _constraint_bounds(lo, hi):
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(lo) != len(hi):
+            raise ValueError("lo and hi must hold one bound per constraint each")
+        return lo, hi
+
+    def _pending(self, pending):
+        """(the pending rows (n, d) or None, n)"""
+        pend = None if pending is None or len(pending) == 0 else _f64(pending)
+        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
+            raise ValueError("pending points must have shape (n, %d)" % self.d)
+        return pend, 0 if pend is None else pend.shape[0]
+
+    @staticmethod
+    def _front(front, m):
+        """The observed front (n, m), or None for an empty one."""
+        F = None if front is None or np.size(front) == 0 else _f64(front)
+        if F is not None and (F.ndim != 2 or F.shape[1] != m):
+            raise ValueError("the front must have shape (n, %d)" % m)
+        return F
+
+    def _believer_outputs(self, q, n_pend, m=None):
+        """(the result dict every family starts from: q winners, their rows, their m means, n + q pivots; the pointers to those
+        arrays in the order every entry takes them)"""
+        q = max(q, 0)
+        val, idx, x, piv = np.empty(q), np.empty(q, dtype=np.int64), np.empty((q, self.d)), np.empty(n_pend + q)
+        if m is None:
+            return dict(best_val=val, best_idx=idx, best_x=x, pivots=piv), (_ptr(val), idx.ctypes.data_as(_lp), _ptr(x), _ptr(piv))
+        mu = np.empty((q, m))
+        return (dict(best_val=val, best_idx=idx, best_x=x, best_mu=mu, pivots=piv),
+                (_ptr(val), idx.ctypes.data_as(_lp), _ptr(x), _ptr(mu), _ptr(piv)))  # fmt: skip
+
+    def _believer_call(self, fn, *args, unsupported=False):
+        """One believer entry: no sweep's winners stay readable behind it; `unsupported`: what the library refuses as unsupported
+        raises NotImplementedError with its message."""
+        self._last_q, self._last_topk = -1, (-1, -1)
+        try:
+            self._check(fn(self._h, *args))
+        except BogpError as e:
+            if unsupported and e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+
+    def _believer_last(self, fn, criterion_key):
+        """The five figures of a multi-target family's *_last entry: producer, solves, k_believer, the criterion kernel, passes."""
+        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(fn(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp), C.cast(C.byref(e), _dp),
+                       C.cast(C.byref(n), _ip)))  # fmt: skip
+        return {"corr_ms": c.value, "solve_ms": s.value, "update_ms": u.value, criterion_key: e.value, "n_passes": n.value}
+
     def sweep_believer(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, pending=None, believe_plugin=True,
                        return_values=False):
         """Kriging-believer batch over the current candidates (bogp_sweep_believer): step j maximises criterion j on the mean and
         on the variance conditioned on the `pending` rows (n, d) and on the winners of the steps before it.  Returns a dict:
         best_val (q,), best_idx (q,), best_x (q, d), pivots (n + q,) and, with return_values, acq (q, M) and mse (q, M)."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
-        pend = None if pending is None or len(pending) == 0 else _f64(pending)
-        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
-            raise ValueError("pending points must have shape (n, %d)" % self.d)
-        n_pend = 0 if pend is None else pend.shape[0]
-        best = np.empty(q)
-        idx = np.empty(q, dtype=np.int64)
-        bx = np.empty((q, self.d))
-        piv = np.empty(n_pend + q)
+        ids, pars = _pack_acq(acq)
+        pend, n_pend = self._pending(pending)
+        out, winners = self._believer_outputs(q, n_pend)
         vals = np.empty((q, self.M)) if return_values else None
         mse = np.empty((q, self.M)) if return_values else None
-        self._last_q, self._last_topk = -1, (-1, -1)
-        self._check(self._lib.bogp_sweep_believer(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
-                                                  int(bool(believe_plugin)), _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp),
-                                                  _ptr(bx), _ptr(piv), _ptr(vals), _ptr(mse)))  # fmt: skip
-        out = dict(best_val=best, best_idx=idx, best_x=bx, pivots=piv)
+        self._believer_call(self._lib.bogp_sweep_believer, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin), int(bool(minimize)),
+                            int(bool(believe_plugin)), _ptr(pend), n_pend, *winners, _ptr(vals), _ptr(mse))  # fmt: skip
         if return_values:
             out.update(acq=vals, mse=mse)
         return out
@@ -839,27 +879,15 @@ class Engine:
         return_values, ehvi (q, M) and mse (q, M, m)."""
         r = _f64(ref_point).ravel()
         m, q = len(r), int(q)
-        F = None if front is None or np.size(front) == 0 else _f64(front)
-        if F is not None and (F.ndim != 2 or F.shape[1] != m):
-            raise ValueError("the front must have shape (n, %d)" % m)
-        pend = None if pending is None or len(pending) == 0 else _f64(pending)
-        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
-            raise ValueError("pending points must have shape (n, %d)" % self.d)
-        n_pend = 0 if pend is None else pend.shape[0]
+        F = self._front(front, m)
+        pend, n_pend = self._pending(pending)
         qa = max(q, 0)
-        best = np.empty(qa)
-        idx = np.empty(qa, dtype=np.int64)
-        bx = np.empty((qa, self.d))
-        bmu = np.empty((qa, m))
-        piv = np.empty(n_pend + qa)
-        nc = np.zeros(qa, dtype=np.int32)
+        out, winners = self._believer_outputs(q, n_pend, m)
+        nc = out["n_cells"] = np.zeros(qa, dtype=np.int32)
         vals = np.empty((qa, self.M)) if return_values else None
         mse = np.empty((qa, self.M, m)) if return_values else None
-        self._last_q, self._last_topk = -1, (-1, -1)
-        self._check(self._lib.bogp_sweep_believer_ehvi(self._h, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F), int(bool(believe_front)),
-                                                       _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(bmu),
-                                                       _ptr(piv), nc.ctypes.data_as(_ip), _ptr(vals), _ptr(mse)))  # fmt: skip
-        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, n_cells=nc)
+        self._believer_call(self._lib.bogp_sweep_believer_ehvi, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F), int(bool(believe_front)),
+                            _ptr(pend), n_pend, *winners, nc.ctypes.data_as(_ip), _ptr(vals), _ptr(mse))  # fmt: skip
         if return_values:
             out.update(ehvi=vals, mse=mse)
         return out
@@ -867,10 +895,7 @@ class Engine:
     def believer_ehvi_last(self) -> dict:
         """Producer, solve, k_believer and k_believer_ehvi time (ms) and the candidate passes of the last sweep_believer_ehvi
         (bogp_believer_ehvi_last)."""
-        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        self._check(self._lib.bogp_believer_ehvi_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
-                                                      C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
-        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, ehvi_ms=e.value, n_passes=n.value)
+        return self._believer_last(self._lib.bogp_believer_ehvi_last, "ehvi_ms")
 
     def sweep_believer_constrained(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize, lo, hi, pending=None, believe_plugin=True,
                                    return_values=False):
@@ -882,36 +907,18 @@ class Engine:
         and mse (q, M, m).  What the library refuses as unsupported (a forest, a lift, a polynomial basis, several ranks) raises
         NotImplementedError with its message."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != len(hi):
-            raise ValueError("lo and hi must hold one bound per constraint each")
+        ids, pars = _pack_acq(acq)
+        lo, hi = self._constraint_bounds(lo, hi)
         m = len(lo) + 1
-        pend = None if pending is None or len(pending) == 0 else _f64(pending)
-        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
-            raise ValueError("pending points must have shape (n, %d)" % self.d)
-        n_pend = 0 if pend is None else pend.shape[0]
-        best = np.empty(q)
-        idx = np.empty(q, dtype=np.int64)
-        bx = np.empty((q, self.d))
-        bmu = np.empty((q, m))
-        piv = np.empty(n_pend + q)
-        plugs = np.empty(q)
+        pend, n_pend = self._pending(pending)
+        out, winners = self._believer_outputs(q, n_pend, m)
+        plugs = out["plugins"] = np.empty(q)
         vals = np.empty((q, self.M)) if return_values else None
         pof = np.empty((q, self.M)) if return_values else None
         mse = np.empty((q, self.M, m)) if return_values else None
-        self._last_q, self._last_topk = -1, (-1, -1)
-        try:
-            self._check(self._lib.bogp_sweep_believer_constrained(self._h, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin),
-                                                                  int(bool(minimize)), int(bool(believe_plugin)), len(lo), _ptr(lo), _ptr(hi),
-                                                                  _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(bmu),
-                                                                  _ptr(piv), _ptr(plugs), _ptr(vals), _ptr(pof), _ptr(mse)))  # fmt: skip
-        except BogpError as e:
-            if e.code == ERR_UNSUPPORTED:
-                raise NotImplementedError(str(e)) from None
-            raise
-        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, plugins=plugs)
+        self._believer_call(self._lib.bogp_sweep_believer_constrained, q, ids.ctypes.data_as(_ip), _ptr(pars), float(plugin),
+                            int(bool(minimize)), int(bool(believe_plugin)), len(lo), _ptr(lo), _ptr(hi), _ptr(pend), n_pend, *winners,
+                            _ptr(plugs), _ptr(vals), _ptr(pof), _ptr(mse), unsupported=True)  # fmt: skip
         if return_values:
             out.update(acq=vals, pof=pof, mse=mse)
         return out
@@ -919,10 +926,7 @@ class Engine:
     def believer_constrained_last(self) -> dict:
         """Producer, solve, k_believer and k_believer_constrained time (ms) and the candidate passes of the last
         sweep_believer_constrained (bogp_believer_constrained_last)."""
-        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        self._check(self._lib.bogp_believer_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(u), _dp),
-                                                             C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
-        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, criterion_ms=e.value, n_passes=n.value)
+        return self._believer_last(self._lib.bogp_believer_constrained_last, "criterion_ms")
 
     def sweep_believer_ehvi_constrained(self, front, ref_point, q: int, lo, hi, pending=None, believe_front=True, feasibility_only=False,
                                         return_values=False):
@@ -938,39 +942,19 @@ class Engine:
         message."""
         r = _f64(ref_point).ravel()
         m, q = len(r), int(q)
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != len(hi):
-            raise ValueError("lo and hi must hold one bound per constraint each")
+        lo, hi = self._constraint_bounds(lo, hi)
         mt = m + len(lo)
-        F = None if front is None or np.size(front) == 0 else _f64(front)
-        if F is not None and (F.ndim != 2 or F.shape[1] != m):
-            raise ValueError("the front must have shape (n, %d)" % m)
-        pend = None if pending is None or len(pending) == 0 else _f64(pending)
-        if pend is not None and (pend.ndim != 2 or pend.shape[1] != self.d):
-            raise ValueError("pending points must have shape (n, %d)" % self.d)
-        n_pend = 0 if pend is None else pend.shape[0]
+        F = self._front(front, m)
+        pend, n_pend = self._pending(pending)
         qa = max(q, 0)
-        best = np.empty(qa)
-        idx = np.empty(qa, dtype=np.int64)
-        bx = np.empty((qa, self.d))
-        bmu = np.empty((qa, mt))
-        piv = np.empty(n_pend + qa)
-        nc = np.zeros(qa, dtype=np.int32)
+        out, winners = self._believer_outputs(q, n_pend, mt)
+        nc = out["n_cells"] = np.zeros(qa, dtype=np.int32)
         vals = np.empty((qa, self.M)) if return_values else None
         pof = np.empty((qa, self.M)) if return_values else None
         mse = np.empty((qa, self.M, mt)) if return_values else None
-        self._last_q, self._last_topk = -1, (-1, -1)
-        try:
-            self._check(self._lib.bogp_sweep_believer_ehvi_constrained(self._h, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F),
-                                                                       int(bool(feasibility_only)), int(bool(believe_front)), len(lo), _ptr(lo),
-                                                                       _ptr(hi), _ptr(pend), n_pend, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx),
-                                                                       _ptr(bmu), _ptr(piv), nc.ctypes.data_as(_ip), _ptr(vals), _ptr(pof),
-                                                                       _ptr(mse)))  # fmt: skip
-        except BogpError as e:
-            if e.code == ERR_UNSUPPORTED:
-                raise NotImplementedError(str(e)) from None
-            raise
-        out = dict(best_val=best, best_idx=idx, best_x=bx, best_mu=bmu, pivots=piv, n_cells=nc)
+        self._believer_call(self._lib.bogp_sweep_believer_ehvi_constrained, m, q, _ptr(r), _ptr(F), 0 if F is None else len(F),
+                            int(bool(feasibility_only)), int(bool(believe_front)), len(lo), _ptr(lo), _ptr(hi), _ptr(pend), n_pend,
+                            *winners, nc.ctypes.data_as(_ip), _ptr(vals), _ptr(pof), _ptr(mse), unsupported=True)  # fmt: skip
         if return_values:
             out.update(val=vals, pof=pof, mse=mse)
         return out
@@ -978,10 +962,7 @@ class Engine:
     def believer_ehvi_constrained_last(self) -> dict:
         """Producer, solve, k_believer and k_believer_ehvi_constrained time (ms) and the candidate passes of the last
         sweep_believer_ehvi_constrained (bogp_believer_ehvi_constrained_last)."""
-        c, s, u, e, n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        self._check(self._lib.bogp_believer_ehvi_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp),
-                                                                  C.cast(C.byref(u), _dp), C.cast(C.byref(e), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
-        return dict(corr_ms=c.value, solve_ms=s.value, update_ms=u.value, criterion_ms=e.value, n_passes=n.value)
+        return self._believer_last(self._lib.bogp_believer_ehvi_constrained_last, "criterion_ms")
 
     # -- lift of a reduced search space (PCA-BO; bogp_api_lift.hip) ------------------------------------------------
     def set_lift(self, A, mean, center, lo, hi):
@@ -1006,8 +987,7 @@ class Engine:
         competes with its penalty, a feasible row with its criterion value.  (values (q, k), indices (q, k), n_feasible
         [, values (q, M)][, penalty (M,)])."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        ids, pars = _pack_acq(acq)
         best = np.empty((q, int(k)))
         idx = np.empty((q, int(k)), dtype=np.int64)
         nf = C.c_int64()
@@ -1072,8 +1052,7 @@ class Engine:
     def forest_sweep_topk(self, acq: Sequence[Tuple[int, float]], plugin: float, minimize=True, k: int = 1, return_values=False):
         """q criteria of the forest's moments over the current candidates: (values (q, k), indices (q, k)[, acq (q, M)])."""
         q = len(acq)
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        ids, pars = _pack_acq(acq)
         best = np.empty((q, int(k)))
         idx = np.empty((q, int(k)), dtype=np.int64)
         vals = np.empty((q, self.M)) if return_values else None
@@ -1287,13 +1266,6 @@ class Engine:
         )  # fmt: skip
         return Xo, fo, ne
 
-    @staticmethod
-    def _constraint_bounds(lo, hi):
-        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
-        if len(lo) != len(hi):
-            raise ValueError("lo and hi must hold one bound per constraint each")
-        return lo, hi
-
     def point_eval_constrained(self, X, acq: Sequence[Tuple[int, float]], plugin: float, minimize, lo, hi, moments: bool = False):
         """q feasibility-weighted criteria of the committed multi-target model and their input gradients at the rows of `X` (B x d) in
         ONE device round trip (bogp_point_eval_constrained); criteria, plugin, direction and the constraints' bounds as
@@ -1302,8 +1274,7 @@ class Engine:
         X = self._rows(X)
         lo, hi = self._constraint_bounds(lo, hi)
         q, m = len(acq), len(lo) + 1
-        ids = np.ascontiguousarray([a for a, _ in acq], dtype=np.int32)
-        pars = _f64([float(p) if p is not None else 0.0 for _, p in acq])
+        ids, pars = _pack_acq(acq)
         B, d = X.shape[0], self.d
         vals, dvals = np.empty((B, q)), np.empty((B, q, d))
         mom = ((np.empty(B), np.empty((B, d)), np.empty((B, m)), np.empty((B, m)), np.empty((B, m, d)), np.empty((B, m, d)))

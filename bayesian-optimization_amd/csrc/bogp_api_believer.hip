@@ -56,9 +56,8 @@ struct SolveBufs {  // dbel_small: the point, r(p), V r(p), R^-1 r(p), the point
   }
 };
 
-// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, k_believer_ehvi, k_believer_constrained,
-// k_believer_ehvi_constrained
-enum { B_SOLVE, B_PRODUCER, B_PASS, B_EHVI, B_CONSTRAINED, B_EHVI_CONSTRAINED };
+// kinds of the spans on h->bel_timer: the solves, the chunks' producer and k_believer launches, the family's criterion kernel (m > 1)
+enum { B_SOLVE, B_PRODUCER, B_PASS, B_CRITERION };
 
 // The solve of one believed point x -- a = V^T (V r(x)) = R^-1 r(x) with the kernels of bogp_gradient, one solve span -- and the
 // host's row of the recursion: bl gains r, a, u and row bl.n of L, pivots[bl.n] (if given) the pivot.  hw: L^-T Ft.
@@ -146,16 +145,16 @@ struct BelieverFamily {
   int minimize = 0;
   const double* plugin = nullptr;   // the running plugin, as `mean` leaves it
   int lead = 1;                     // rows of dbel_row in front of the MSE block (the table above)
-  int span = B_PASS;                // kind of `criterion`'s span
   double* best_val = nullptr;
   int64_t* best_idx = nullptr;
   double *best_x = nullptr, *best_mu = nullptr, *pivots = nullptr;  // each may be null
   StepRows rows[3] = {};
   std::function<void(const double* mu)> mean;  // a believed mean (m values): a pending point's as the host forms it, a winner's from the sweep's array
   std::function<int(int step)> step_begin;     // (may be empty) in front of a step's pass, behind the believed mean
-  // m > 1: the launch over all M rows behind the column pass: c the believed point's column (null: guarded, no update), `row` the
-  // candidate row a winner is (its variance becomes exactly 0; -1: a pending point), step >= 0: evaluate it into dblk_* (256 rows a record)
-  std::function<hipError_t(int step, int64_t row, const double* c)> criterion;
+  // m > 1: the launch over all M rows behind the column pass.  The step arrives filled (BelieverStep, bogp_internal.h); with `eval` set,
+  // n_taken is the step's number and the values go to dbel_row, the MSE block to dbel_row + lead M.  The family copies it into its
+  // argument block, adds what is its own and launches.
+  std::function<hipError_t(const BelieverStep& bs)> criterion;
 };
 
 // Behind pass 0 (dmu_out, dmse_out and -- without pending points -- step 0's winner in dbest_*[0] are in place): the pending points,
@@ -257,8 +256,20 @@ int believer_run(bogp_handle* h, const BelieverFamily& f, int q, const double* p
         if (one) blk_offset += (ba.mcount + 63) / 64;  // one record per 64 rows of every chunk
       }
     }
-    if (!one)
-      if (int rs = timed_span(h, h->bel_timer, st, f.span, [&] { return f.criterion(step, row, col); })) return rs;
+    if (!one) {
+      BelieverStep bs;
+      memset(&bs, 0, sizeof(bs));
+      bs.M = M; bs.m = m; bs.update = col ? 1 : 0; bs.c = col;  // (col null: a guarded pivot, the criterion alone)
+      bs.self_row = row; bs.s = h->dbel_s;
+      for (int t = 0; t < m; ++t) bs.sigma2[t] = h->sigma2_t[t];
+      bs.eval = step >= 0 ? 1 : 0;
+      if (step >= 0) {
+        bs.n_taken = step;  // the winners of steps 0 .. step - 1
+        for (int k = 0; k < step; ++k) bs.taken[k] = f.best_idx[k];
+      }
+      bs.mu = h->dmu_out; bs.mse_out = dmse_row; bs.blk_val = h->dblk_val; bs.blk_idx = h->dblk_idx;
+      if (int rs = timed_span(h, h->bel_timer, st, B_CRITERION, [&] { return f.criterion(bs); })) return rs;
+    }
     ++h->bel_passes;
     if (step >= 0)
       HIPCHK(h, launch_argmax_final(h->dblk_val, h->dblk_idx, one ? blk_offset : nblk_total, nblk_total, 1, h->dbest_val, h->dbest_idx, st));
@@ -297,6 +308,18 @@ int believer_run(bogp_handle* h, const BelieverFamily& f, int q, const double* p
   // times of the solves and of the passes (everything is complete: the last step was read back)
   HIPCHK(h, hipStreamSynchronize(st));
   h->bel_solve_ms = h->bel_timer.sum(B_SOLVE); h->bel_corr_ms = h->bel_timer.sum(B_PRODUCER); h->bel_pass_ms = h->bel_timer.sum(B_PASS);
+  if (!one) h->bel_criterion_ms = h->bel_timer.sum(B_CRITERION);
+  return BOGP_OK;
+}
+
+// bogp_believer_ehvi_last, _constrained_last and _ehvi_constrained_last: the spans of the last believer call
+int believer_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms, int* n_passes) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (corr_ms) *corr_ms = h->bel_corr_ms;
+  if (solve_ms) *solve_ms = h->bel_solve_ms;
+  if (update_ms) *update_ms = h->bel_pass_ms;
+  if (criterion_ms) *criterion_ms = h->bel_criterion_ms;
+  if (n_passes) *n_passes = h->bel_passes;
   return BOGP_OK;
 }
 
@@ -491,7 +514,6 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
     if (!std::isfinite(pending[i])) FAIL(h, BOGP_ERR_INVALID, "%s: pending entry %zu is not finite", who, i);
   if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
   if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
-  const int64_t M = h->M;
   const int P = n_pending;
 
   // ---- the front and its cells (host): F_0 now, one believed mean more per step when believe_front is set
@@ -537,7 +559,7 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
   if (P == 0 && n_cells) n_cells[0] = C0;
 
   BelieverFamily f;
-  f.who = who; f.m = m; f.lead = 2; f.span = B_EHVI;
+  f.who = who; f.m = m; f.lead = 2;
   f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
   f.rows[0] = {ehvi_out, &h->dacq_out, 0, 1};
   f.rows[1] = {mse_out, &h->dmse_out, 2, m};
@@ -552,34 +574,23 @@ extern "C" int bogp_sweep_believer_ehvi(bogp_handle* h, int m, int q, const doub
     if (n_cells) n_cells[step] = C;
     return BOGP_OK;
   };
-  f.criterion = [&](int step, int64_t row, const double* c) {
+  f.criterion = [&](const BelieverStep& bs) {
     BelieverEhviArgs be;
     memset(&be, 0, sizeof(be));
-    be.M = M; be.m = m; be.update = c ? 1 : 0; be.c = c;
-    be.self_row = row; be.s = h->dbel_s;
-    for (int t = 0; t < m; ++t) be.sigma2[t] = h->sigma2_t[t];
-    be.eval = step >= 0 ? 1 : 0;
-    if (step >= 0) {
-      be.n_taken = step;  // the winners of steps 0 .. step - 1
-      for (int k = 0; k < step; ++k) be.taken[k] = best_idx[k];
-      be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C;
-    }
-    be.mu = h->dmu_out; be.ehvi_out = h->dbel_row; be.mse_out = h->dbel_row + 2 * M; be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
+    be.M = bs.M; be.m = bs.m; be.update = bs.update; be.c = bs.c; be.self_row = bs.self_row; be.s = bs.s;  // (its own field order)
+    memcpy(be.sigma2, bs.sigma2, sizeof(be.sigma2));
+    be.eval = bs.eval; be.n_taken = bs.n_taken;
+    memcpy(be.taken, bs.taken, sizeof(be.taken));
+    be.mu = bs.mu; be.mse_out = bs.mse_out; be.blk_val = bs.blk_val; be.blk_idx = bs.blk_idx;
+    if (bs.eval) { be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m; be.C = C; }
+    be.ehvi_out = h->dbel_row;
     return launch_believer_ehvi(be, st);
   };
-  if ((rc = believer_run(h, f, q, pending, P))) return rc;
-  h->bel_ehvi_ms = h->bel_timer.sum(B_EHVI);
-  return BOGP_OK;
+  return believer_run(h, f, q, pending, P);
 }
 
 extern "C" int bogp_believer_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* ehvi_ms, int* n_passes) {
-  if (!h) return BOGP_ERR_INVALID;
-  if (corr_ms) *corr_ms = h->bel_corr_ms;
-  if (solve_ms) *solve_ms = h->bel_solve_ms;
-  if (update_ms) *update_ms = h->bel_pass_ms;
-  if (ehvi_ms) *ehvi_ms = h->bel_ehvi_ms;
-  if (n_passes) *n_passes = h->bel_passes;
-  return BOGP_OK;
+  return believer_last(h, corr_ms, solve_ms, update_ms, ehvi_ms, n_passes);
 }
 
 // ---- believer batches under modelled constraints: bogp_sweep_believer_constrained --------------------------------------------------
@@ -629,7 +640,7 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
 
   double plug = plugin;
   BelieverFamily f;
-  f.who = who; f.m = m; f.lead = 3; f.span = B_CONSTRAINED;
+  f.who = who; f.m = m; f.lead = 3;
   f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
   f.rows[0] = {acq_out, &h->dacq_out, 0, 1};
   f.rows[1] = {pof_out, &h->dpof_out, 1, 1};
@@ -643,38 +654,26 @@ extern "C" int bogp_sweep_believer_constrained(bogp_handle* h, int q, const int*
     const double y_hat = minimize ? mu[0] : -1 * mu[0];
     if (y_hat < plug) plug = y_hat;
   };
-  f.criterion = [&](int step, int64_t row, const double* c) {
+  f.criterion = [&](const BelieverStep& bs) {
     BelieverConstrainedArgs bc;
     memset(&bc, 0, sizeof(bc));
-    bc.M = M; bc.m = m; bc.update = c ? 1 : 0; bc.c = c;
-    bc.self_row = row; bc.s = h->dbel_s;
-    for (int t = 0; t < m; ++t) { bc.sigma2[t] = ca.sigma2[t]; bc.lo[t] = ca.lo[t]; bc.hi[t] = ca.hi[t]; }
-    bc.eval = step >= 0 ? 1 : 0;
-    if (step >= 0) {
+    bc.step = bs;
+    for (int t = 0; t < m; ++t) { bc.lo[t] = ca.lo[t]; bc.hi[t] = ca.hi[t]; }
+    if (bs.eval) {
+      const int step = bs.n_taken;
       bc.acq_id = acq_id[step]; bc.acq_par = acq_par ? acq_par[step] : 0.0; bc.plugin = plug; bc.minimize = minimize;
-      bc.n_taken = step;  // the winners of steps 0 .. step - 1
-      for (int k = 0; k < step; ++k) bc.taken[k] = best_idx[k];
       if (plugin_out) plugin_out[step] = plug;
     }
-    bc.mu = h->dmu_out; bc.acq_out = h->dbel_row; bc.pof_out = h->dbel_row + M; bc.mse_out = h->dbel_row + 3 * M;
-    bc.blk_val = h->dblk_val; bc.blk_idx = h->dblk_idx;
+    bc.acq_out = h->dbel_row; bc.pof_out = h->dbel_row + M;
     return launch_believer_constrained(bc, st);
   };
   if (n_pending == 0 && plugin_out) plugin_out[0] = plugin;
-  if ((rc = believer_run(h, f, q, pending, n_pending))) return rc;
-  h->bel_con_ms = h->bel_timer.sum(B_CONSTRAINED);
-  return BOGP_OK;
+  return believer_run(h, f, q, pending, n_pending);
 }
 
 extern "C" int bogp_believer_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
                                               int* n_passes) {
-  if (!h) return BOGP_ERR_INVALID;
-  if (corr_ms) *corr_ms = h->bel_corr_ms;
-  if (solve_ms) *solve_ms = h->bel_solve_ms;
-  if (update_ms) *update_ms = h->bel_pass_ms;
-  if (criterion_ms) *criterion_ms = h->bel_con_ms;
-  if (n_passes) *n_passes = h->bel_passes;
-  return BOGP_OK;
+  return believer_last(h, corr_ms, solve_ms, update_ms, criterion_ms, n_passes);
 }
 
 // ---- believer batches for constrained EHVI: bogp_sweep_believer_ehvi_constrained ---------------------------------------------------
@@ -767,7 +766,7 @@ extern "C" int bogp_sweep_believer_ehvi_constrained(bogp_handle* h, int m_obj, i
   if (P == 0 && n_cells) n_cells[0] = C0;
 
   BelieverFamily f;
-  f.who = who; f.m = m; f.lead = 3; f.span = B_EHVI_CONSTRAINED;
+  f.who = who; f.m = m; f.lead = 3;
   f.best_val = best_val; f.best_idx = best_idx; f.best_x = best_x; f.best_mu = best_mu; f.pivots = pivots;
   f.rows[0] = {val_out, &h->dacq_out, 0, 1};
   f.rows[1] = {pof_out, &h->dpof_out, 1, 1};
@@ -787,35 +786,19 @@ extern "C" int bogp_sweep_believer_ehvi_constrained(bogp_handle* h, int m_obj, i
     if (n_cells) n_cells[step] = C;
     return BOGP_OK;
   };
-  f.criterion = [&](int step, int64_t row, const double* c) {
+  f.criterion = [&](const BelieverStep& bs) {
     BelieverEhviConstrainedArgs be;
     memset(&be, 0, sizeof(be));
-    be.M = M; be.m = m; be.m_obj = m_obj; be.update = c ? 1 : 0; be.c = c;
-    be.self_row = row; be.s = h->dbel_s;
-    for (int t = 0; t < m; ++t) be.sigma2[t] = ea.sigma2[t];
+    be.step = bs; be.m_obj = m_obj;
     for (int j = 0; j < n_con; ++j) { be.lo[j] = lo[j]; be.hi[j] = hi[j]; }
-    be.eval = step >= 0 ? 1 : 0;
-    if (step >= 0) {
-      be.n_taken = step;  // the winners of steps 0 .. step - 1
-      for (int k = 0; k < step; ++k) be.taken[k] = best_idx[k];
-      be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m_obj; be.C = C;
-    }
-    be.mu = h->dmu_out; be.val_out = h->dbel_row; be.pof_out = h->dbel_row + M; be.mse_out = h->dbel_row + 3 * M;
-    be.blk_val = h->dblk_val; be.blk_idx = h->dblk_idx;
+    if (bs.eval) { be.lower = h->dehvi_cells; be.upper = h->dehvi_cells + (size_t)C * m_obj; be.C = C; }
+    be.val_out = h->dbel_row; be.pof_out = h->dbel_row + M;
     return launch_believer_ehvi_constrained(be, st);
   };
-  if ((rc = believer_run(h, f, q, pending, P))) return rc;
-  h->bel_ehvi_con_ms = h->bel_timer.sum(B_EHVI_CONSTRAINED);
-  return BOGP_OK;
+  return believer_run(h, f, q, pending, P);
 }
 
 extern "C" int bogp_believer_ehvi_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* update_ms, double* criterion_ms,
                                                    int* n_passes) {
-  if (!h) return BOGP_ERR_INVALID;
-  if (corr_ms) *corr_ms = h->bel_corr_ms;
-  if (solve_ms) *solve_ms = h->bel_solve_ms;
-  if (update_ms) *update_ms = h->bel_pass_ms;
-  if (criterion_ms) *criterion_ms = h->bel_ehvi_con_ms;
-  if (n_passes) *n_passes = h->bel_passes;
-  return BOGP_OK;
+  return believer_last(h, corr_ms, solve_ms, update_ms, criterion_ms, n_passes);
 }

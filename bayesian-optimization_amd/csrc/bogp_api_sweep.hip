@@ -318,14 +318,14 @@ extern "C" int bogp_candidates_bind(bogp_handle* h, const void* d_Xs, int64_t M)
 //   forest calls          | -                            | -                            | k_forest / k_forest_ehvi         (n_chunks = 1)
 //
 // The believer batches (bogp_api_believer.hip) leave pass 0 here as "chunks" -- its criteria span is k_acquisition, k_ehvi or
-// k_constrained -- and the passes behind it on h->bel_timer, which bogp_believer_last / _ehvi_last / _constrained_last report:
+// k_constrained / k_ehvi_constrained -- and the passes behind it on h->bel_timer, which bogp_believer_last / _ehvi_last / _constrained_last /
+// _ehvi_constrained_last report (the last three read the B_CRITERION sum, h->bel_criterion_ms):
 //
 //   kind                  | spans
 //   ----------------------+------------------------------------------------------------------------------------------------------
 //   B_SOLVE               | one per believed point: upload, r(p), the two solves with V, the read-back
 //   B_PRODUCER, B_PASS    | per chunk of a candidate pass: the producer (first believed point only when one chunk holds every row), k_believer
-//   B_EHVI                | one per pass of bogp_sweep_believer_ehvi: k_believer_ehvi over all rows
-//   B_CONSTRAINED         | one per pass of bogp_sweep_believer_constrained: k_believer_constrained over all rows
+//   B_CRITERION           | one per pass of a multi-target family: k_believer_ehvi, k_believer_constrained or k_believer_ehvi_constrained over all rows
 
 // The spans of the last sweep are read lazily (bogp_last_timing, or the next sweep): reading them needs the events
 // to have completed, and an un-synchronised sweep (bogp_sweep without host outputs) must not wait for them.

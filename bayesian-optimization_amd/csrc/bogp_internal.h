@@ -332,10 +332,12 @@ struct BelieverArgs {
 };
 hipError_t launch_believer(int kernel, const BelieverArgs& a, hipStream_t st);
 
-// the m-target half of a believer pass (kernels_believer_ehvi.hip), ONE launch over all M rows behind the chunk loop in which
-// k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a step -- EHVI over that step's
-// cells on (mu, max(0, MSE)) with one argmax record per 256 rows
-struct BelieverEhviArgs {
+// What the m-target halves of a believer pass share (bogp_believer_multi.h), ONE launch over all M rows behind the chunk loop in which
+// k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a step -- that step's criterion on
+// (mu, max(0, MSE)) with one argmax record per 256 rows.  believer_run fills every field (sigma2 from the handle's sigma2_t) and hands
+// it to BelieverFamily::criterion; it is the first member, `step`, of the two constrained families' argument blocks below.  It stands
+// here and not in bogp_believer_multi.h because that host code needs it and that header pulls in bogp_device.h.
+struct BelieverStep {
   int64_t M;
   int m;                  // targets, 2 .. BOGP_MAX_TARGETS
   int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
@@ -343,72 +345,60 @@ struct BelieverEhviArgs {
   int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
   double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
   double sigma2[8];       // per target
-  int eval;               // evaluate EHVI behind the update
+  int eval;               // evaluate the criterion behind the update
   int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
   int64_t taken[32];
   const double* mu;       // [M][m]
+  double* mse_out;        // [M][m] max(0, MSE): what the step saw
+  double* blk_val;        // [ceil(M / 256)]
+  int64_t* blk_idx;
+};
+
+// EHVI over the step's cells (kernels_believer_ehvi.hip).  This family holds no `step`: its kernel keeps the step's fields under
+// their names in its own order, the cells in front of mse_out, and its own text (profiles/believer_multi_fold.txt section 7: through
+// the embedded step and the helpers k_believer_ehvi<7> gained a branch); the family copies the step it is handed field by field.
+struct BelieverEhviArgs {
+  int64_t M;
+  int m, update;
+  const double* c;
+  int64_t self_row;
+  double* s;
+  double sigma2[8];
+  int eval, n_taken;
+  int64_t taken[32];
+  const double* mu;
   const double* lower;    // [C][m] cell bounds of the step's front (device)
   const double* upper;    // [C][m] (+inf allowed)
   int C;
   double* ehvi_out;       // [M]
-  double* mse_out;        // [M][m] max(0, MSE): what the step saw
-  double* blk_val;        // [ceil(M / 256)]
+  double *mse_out, *blk_val;
   int64_t* blk_idx;
 };
 hipError_t launch_believer_ehvi(const BelieverEhviArgs& a, hipStream_t st);
 
-// the m-target half of a believer pass under modelled constraints (kernels_believer_constrained.hip), ONE launch over all M rows
-// behind the chunk loop in which k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a
-// step -- that step's feasibility-weighted criterion on (mu, max(0, MSE)) in k_constrained's expressions (target 0 the objective,
-// targets 1 .. m - 1 constraints feasible in [lo_k, hi_k]) with one argmax record per 256 rows
+// the step's feasibility-weighted criterion in k_constrained's expressions (kernels_believer_constrained.hip): target 0 the
+// objective, targets 1 .. m - 1 constraints feasible in [lo_k, hi_k]
 struct BelieverConstrainedArgs {
-  int64_t M;
-  int m;                  // targets, 2 .. BOGP_MAX_TARGETS
-  int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
-  const double* c;        // [M] c(x) of the believed point
-  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
-  double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
-  double sigma2[8];       // per target
+  BelieverStep step;
   double lo[8], hi[8];    // per target; entry 0 is not read
-  int eval;               // evaluate the criterion behind the update
   int acq_id, minimize;   // BOGP_ACQ_EI / EPSILON_PI / MGFI, or BOGP_ACQ_NONE: the probability of feasibility alone
   double acq_par, plugin;
-  int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
-  int64_t taken[32];
-  const double* mu;       // [M][m]
   double* acq_out;        // [M]
   double* pof_out;        // [M]
-  double* mse_out;        // [M][m] max(0, MSE): what the step saw
-  double* blk_val;        // [ceil(M / 256)]
-  int64_t* blk_idx;
 };
 hipError_t launch_believer_constrained(const BelieverConstrainedArgs& a, hipStream_t st);
 
-// the (m + c)-target half of a believer pass for constrained EHVI (kernels_believer_ehvi_constrained.hip), ONE launch over all M rows
-// behind the chunk loop in which k_believer stored c(x): MSE_k(x) -= sigma2_k c(x)^2 per target and -- for the pass in front of a
-// step -- feasibility-weighted EHVI over that step's cells on (mu, max(0, MSE)) by k_ehvi_constrained's conventions (targets
-// 0 .. m_obj - 1 the objectives, target m_obj + j the constraint feasible in [lo[j], hi[j]]) with one argmax record per 256 rows
+// feasibility-weighted EHVI over the step's cells by k_ehvi_constrained's conventions (kernels_believer_ehvi_constrained.hip):
+// targets 0 .. m_obj - 1 the objectives, target m_obj + j the constraint feasible in [lo[j], hi[j]]; step.m is 3 .. BOGP_MAX_TARGETS
 struct BelieverEhviConstrainedArgs {
-  int64_t M;
-  int m, m_obj;           // targets, 3 .. BOGP_MAX_TARGETS; objectives among them, 2 .. m - 1
-  int update;             // 0: criterion only (a guarded pivot: c = 0), c is not read
-  const double* c;        // [M] c(x) of the believed point
-  int64_t self_row;       // the candidate row that is the believed point (a winner), -1 for a pending point
-  double* s;              // [M][m] running MSE per target, in / out (unclamped below pass 0's own clamp)
-  double sigma2[8];       // per target
+  BelieverStep step;
+  int m_obj;              // objectives among the targets, 2 .. m - 1
   double lo[8], hi[8];    // per constraint: entry j belongs to target m_obj + j
-  int eval;               // evaluate the criterion behind the update
-  int n_taken;            // winners of the steps before: their rows keep their value but leave the argmax
-  int64_t taken[32];
-  const double* mu;       // [M][m]
   const double* lower;    // [C][m_obj] cell bounds of the step's feasible front (device); not read for C == 0
   const double* upper;    // [C][m_obj] (+inf allowed)
   int C;                  // 0: the probability of feasibility alone
   double* val_out;        // [M]
   double* pof_out;        // [M]
-  double* mse_out;        // [M][m] max(0, MSE): what the step saw
-  double* blk_val;        // [ceil(M / 256)]
-  int64_t* blk_idx;
 };
 hipError_t launch_believer_ehvi_constrained(const BelieverEhviConstrainedArgs& a, hipStream_t st);
 

@@ -14,69 +14,47 @@
 // Elementwise in the global row index: one launch serves all M rows behind the chunk loop, so no bit depends on the chunk size.
 // Streams 8 (3 + 4 m) bytes per candidate (c, the value and P out, and per target the running variance in and out, the mean and the
 // clamped variance); no MFMA, LDS for the block reduction only.
-#include "bogp_device.h"
-#include "bogp_internal.h"
+#include "bogp_believer_multi.h"
 
 namespace bogp {
 
 template <int MT>
 __global__ __launch_bounds__(256) void k_believer_constrained(BelieverConstrainedArgs a) {
-  __shared__ double sv[4];
-  __shared__ int64_t si[4];
+  const BelieverStep& b = a.step;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;  // candidate row
   double v = -INFINITY;
   int64_t idx = INT64_MAX;
-  if (g < a.M) {
+  if (g < b.M) {
     double s[MT];
 #pragma unroll
-    for (int k = 0; k < MT; ++k) s[k] = a.s[(size_t)g * MT + k];
-    if (a.update) {
-      const double c = a.c[g];
-#pragma unroll
-      for (int k = 0; k < MT; ++k) {
-        s[k] = __builtin_fma(-(a.sigma2[k] * c), c, s[k]);
-        if (g == a.self_row) s[k] = 0.0;  // the believed row itself is determined: rounding must not leave sd > 0 there
-        a.s[(size_t)g * MT + k] = s[k];
-      }
-    }
-    if (a.eval) {
+    for (int k = 0; k < MT; ++k) s[k] = b.s[(size_t)g * MT + k];
+    if (b.update) believer_downdate<MT>(b, g, b.c[g], s);
+    if (b.eval) {
       double mu[MT], mse[MT];
 #pragma unroll
       for (int k = 0; k < MT; ++k) {
-        mse[k] = s[k];
-        if (mse[k] < 0.0) mse[k] = 0.0;
-        mu[k] = a.mu[(size_t)g * MT + k];
-        a.mse_out[(size_t)g * MT + k] = mse[k];
+        mu[k] = b.mu[(size_t)g * MT + k];
+        mse[k] = believer_clamped<MT>(b, g, k, s[k]);
       }
       const double y_hat = a.minimize ? mu[0] : -1 * mu[0];
       const double sd = sqrt(mse[0]);
       double P = 1.0;
 #pragma unroll
-      for (int k = 1; k < MT; ++k) P *= feasibility(mu[k], mse[k], a.sigma2[k], a.lo[k], a.hi[k]);
-      const double base = a.acq_id == BOGP_ACQ_NONE ? 1.0 : acq_value(a.acq_id, a.acq_par, y_hat, sd, a.plugin, a.sigma2[0]);
+      for (int k = 1; k < MT; ++k) P *= feasibility(mu[k], mse[k], b.sigma2[k], a.lo[k], a.hi[k]);
+      const double base = a.acq_id == BOGP_ACQ_NONE ? 1.0 : acq_value(a.acq_id, a.acq_par, y_hat, sd, a.plugin, b.sigma2[0]);
       v = base * P;
       idx = g;
       a.acq_out[g] = v;
       a.pof_out[g] = P;
-      // a row that already is a winner keeps its value in the outputs and does not compete again
-      for (int k = 0; k < a.n_taken; ++k)
-        if (a.taken[k] == g) {
-          v = -INFINITY;
-          idx = INT64_MAX;
-        }
     }
   }
-  if (!a.eval) return;  // (uniform: no barrier is skipped by part of a workgroup)
-  const ArgMax best = block_argmax(v, idx, sv, si);
-  if (threadIdx.x == 0) {
-    a.blk_val[blockIdx.x] = best.v;
-    a.blk_idx[blockIdx.x] = best.i;
-  }
+  if (!b.eval) return;  // (uniform: no barrier is skipped by part of a workgroup)
+  believer_tail(b, g, v, idx);
 }
 
 hipError_t launch_believer_constrained(const BelieverConstrainedArgs& a, hipStream_t st) {
-  const unsigned nblk = (unsigned)((a.M + 255) / 256);
-  switch (a.m) {
+  const unsigned nblk = (unsigned)((a.step.M + 255) / 256);
+  switch (a.step.m) {
     case 2: hipLaunchKernelGGL(k_believer_constrained<2>, dim3(nblk), 256, 0, st, a); break;
     case 3: hipLaunchKernelGGL(k_believer_constrained<3>, dim3(nblk), 256, 0, st, a); break;
     case 4: hipLaunchKernelGGL(k_believer_constrained<4>, dim3(nblk), 256, 0, st, a); break;

@@ -9,6 +9,8 @@
 // kind over the rows that are not winners yet.
 // Elementwise in the global row index: one launch serves all M rows behind the chunk loop, so no bit depends on the chunk size.
 // Streams 8 (1 + 3 m) bytes per candidate; no MFMA, LDS for the block reduction only.
+// The steps around the criterion are those of bogp_believer_multi.h, written out: through that header's helpers, under either field
+// order and either place of the exclusion loop, k_believer_ehvi<7> gains branches (profiles/believer_multi_fold.txt section 7).
 #include "bogp_device.h"
 #include "bogp_internal.h"
 

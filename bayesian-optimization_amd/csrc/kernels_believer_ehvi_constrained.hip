@@ -15,18 +15,16 @@
 // Streams 8 (3 + 4 MT) bytes per candidate (c, the value and P out, and per target the running variance in and out, the mean and the
 // clamped variance) plus the cell loop; the 2 MT + 1 loads of a row are issued before the first arithmetic that waits for one.
 // No MFMA, LDS for the block reduction only.
-#include "bogp_device.h"
-#include "bogp_internal.h"
+#include "bogp_believer_multi.h"
 
 namespace bogp {
 
 template <int MO, int MT>
 __global__ __launch_bounds__(256) void k_believer_ehvi_constrained(BelieverEhviConstrainedArgs a) {
   static_assert(MO >= 2 && MO < MT && MT <= 8, "objectives 2 .. MT - 1, at least one constraint");
-  __shared__ double sv[4];
-  __shared__ int64_t si[4];
+  const BelieverStep& b = a.step;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;  // candidate row
-  const bool valid = g < a.M;
+  const bool valid = g < b.M;
   double P = 1.0;
   double mu_o[MO], sd[MO];  // the objectives' moments, all the cell loop reads
 #pragma unroll
@@ -38,41 +36,30 @@ __global__ __launch_bounds__(256) void k_believer_ehvi_constrained(BelieverEhviC
     // every load of the row first: the running variances, c and the means do not depend on one another
     double s[MT], mu[MT];
 #pragma unroll
-    for (int k = 0; k < MT; ++k) s[k] = a.s[(size_t)g * MT + k];
-    const double c = a.update ? a.c[g] : 0.0;
+    for (int k = 0; k < MT; ++k) s[k] = b.s[(size_t)g * MT + k];
+    const double c = b.update ? b.c[g] : 0.0;
 #pragma unroll
     for (int k = 0; k < MT; ++k) mu[k] = 0.0;
-    if (a.eval) {
+    if (b.eval) {
 #pragma unroll
-      for (int k = 0; k < MT; ++k) mu[k] = a.mu[(size_t)g * MT + k];
+      for (int k = 0; k < MT; ++k) mu[k] = b.mu[(size_t)g * MT + k];
     }
-    if (a.update) {
-#pragma unroll
-      for (int k = 0; k < MT; ++k) {
-        s[k] = __builtin_fma(-(a.sigma2[k] * c), c, s[k]);
-        if (g == a.self_row) s[k] = 0.0;  // the believed row itself is determined: rounding must not leave sd > 0 there
-        a.s[(size_t)g * MT + k] = s[k];
-      }
-    }
-    if (a.eval) {
+    if (b.update) believer_downdate<MT>(b, g, c, s);
+    if (b.eval) {
       double mse[MT];
 #pragma unroll
-      for (int k = 0; k < MT; ++k) {
-        mse[k] = s[k];
-        if (mse[k] < 0.0) mse[k] = 0.0;
-        a.mse_out[(size_t)g * MT + k] = mse[k];
-      }
+      for (int k = 0; k < MT; ++k) mse[k] = believer_clamped<MT>(b, g, k, s[k]);
 #pragma unroll
       for (int k = 0; k < MO; ++k) {
         mu_o[k] = mu[k];
         sd[k] = sqrt(fmax(mse[k], 1e-9));
       }
 #pragma unroll
-      for (int k = MO; k < MT; ++k) P *= feasibility(mu[k], mse[k], a.sigma2[k], a.lo[k - MO], a.hi[k - MO]);
+      for (int k = MO; k < MT; ++k) P *= feasibility(mu[k], mse[k], b.sigma2[k], a.lo[k - MO], a.hi[k - MO]);
       a.pof_out[g] = P;
     }
   }
-  if (!a.eval) return;  // (uniform: no barrier is skipped by part of a workgroup)
+  if (!b.eval) return;  // (uniform: no barrier is skipped by part of a workgroup)
   // k_ehvi_constrained's value rule: the cell loop runs where some lane of the wavefront is live; the others never read E
   const bool live = valid && !(P == 0.0);
   double E = 1.0;
@@ -85,18 +72,8 @@ __global__ __launch_bounds__(256) void k_believer_ehvi_constrained(BelieverEhviC
     v = live ? (a.C > 0 ? E * P : P) : 0.0;
     idx = g;
     a.val_out[g] = v;
-    // a row that already is a winner keeps its value in the outputs and does not compete again
-    for (int k = 0; k < a.n_taken; ++k)
-      if (a.taken[k] == g) {
-        v = -INFINITY;
-        idx = INT64_MAX;
-      }
   }
-  const ArgMax best = block_argmax(v, idx, sv, si);
-  if (threadIdx.x == 0) {
-    a.blk_val[blockIdx.x] = best.v;
-    a.blk_idx[blockIdx.x] = best.i;
-  }
+  believer_tail(b, g, v, idx);
 }
 
 template <int MO, int MT>
@@ -120,9 +97,9 @@ static bool launch_objectives(const BelieverEhviConstrainedArgs& a, unsigned nbl
 }
 
 hipError_t launch_believer_ehvi_constrained(const BelieverEhviConstrainedArgs& a, hipStream_t st) {
-  const unsigned nblk = (unsigned)((a.M + 255) / 256);
+  const unsigned nblk = (unsigned)((a.step.M + 255) / 256);
   bool ok = false;
-  switch (a.m) {
+  switch (a.step.m) {
     case 3: ok = launch_objectives<3>(a, nblk, st); break;
     case 4: ok = launch_objectives<4>(a, nblk, st); break;
     case 5: ok = launch_objectives<5>(a, nblk, st); break;

@@ -492,6 +492,56 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def _stage_candidates(model, search_space, eval_budget, Xs, design, seed):
+    """The candidates of a believer or Thompson batch onto the model's engine: `design` drawn on the device (a missing seed from
+    NumPy's global stream, drawn here and only then), else the rows `Xs` or `eval_budget` rows of `search_space.sample`."""
+    eng = model.engine
+    if design is not None:
+        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
+        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
+    else:
+        if Xs is None:
+            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
+        eng.upload_candidates(model._check_X(Xs), lazy=True)
+
+
+def _believer_preamble(model, lift, masks, h, g, group, rank, world, under="", no_front=None):
+    """What every believer batch refuses alike, in the order all four keep: a forest, a lift, fixed variables, constraints h / g,
+    a criterion without a front (`no_front`: that ValueError's message, None where the criterion has one), a model that is not
+    fitted, several ranks.
+    `under`: the family's wording behind "have no believer batches".  Returns the model's engine."""
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no believer batches" + under)
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no believer batches" + under)
+    if h is not None or g is not None:
+        if under:
+            raise NotImplementedError("cheap constraints h / g have no believer batches%s: model them as columns of y" % under)
+        raise NotImplementedError("constraints have no believer batches")
+    if no_front is not None:
+        raise ValueError(no_front)
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    return eng
+
+
+def _believed_cap(q, pending):  # (behind each family's own checks of its criteria and of q, so not part of the preamble)
+    if q + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
+        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
+
+
+def _believer_result(out):
+    """(xopt: tuple of q lists, fopt: tuple of q floats) of an engine's believer dict, in `batch_argmax`'s format."""
+    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+
+
 def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = None, Xs: Optional[np.ndarray] = None,
                    design: Optional[str] = None, seed: Optional[int] = None, pending=None, believe_plugin: bool = True, lift=None,
                    masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):
@@ -514,7 +564,7 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
         raise ValueError("the believer needs at least one criterion")
     c0 = criteria[0]
     model = c0.model
-    if _forest.is_forest_model(model):
+    if _forest.is_forest_model(model):  # (here too: in front of the refusals of the criteria's kinds, which the preamble follows)
         raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
     if any(is_constrained_ehvi(c) for c in criteria):
         raise NotImplementedError("%s has no believer batches" % _CEHVI)
@@ -523,36 +573,17 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
                                   "(`ehvi_believer_batch` rebuilds them between the steps)")
     if any(is_constrained(c) for c in criteria):
         raise NotImplementedError("modelled constraints (bogp.Constrained) have no believer batches: strategy='topk' serves them")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no believer batches")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no believer batches")
-    if h is not None or g is not None:
-        raise NotImplementedError("constraints have no believer batches")
-    if getattr(model, "_committed_par", None) is None:
-        raise Exception("The model is not fitted yet!")
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    eng = _believer_preamble(model, lift, masks, h, g, group, rank, world)
     plugins = {c.effective_plugin() for c in criteria if c.acq_id != _lib.ACQ_UCB}  # (UCB reads no plugin: it may join any batch)
     if any(c.model is not model or c.minimize != c0.minimize for c in criteria[1:]) or len(plugins) > 1:
         raise ValueError("criteria sharing one sweep must share model, minimize and plugin")
     plugin = plugins.pop() if plugins else 0.0
-    if len(criteria) + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
-        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
-    if design is not None:
-        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
-        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
-    else:
-        if Xs is None:
-            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
-        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    _believed_cap(len(criteria), pending)
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
     pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
     out = eng.sweep_believer([(c.acq_id, c.acq_par()) for c in criteria], plugin, c0.minimize, pending=pend,
                              believe_plugin=believe_plugin)
-    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+    return _believer_result(out)
 
 
 def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
@@ -594,13 +625,7 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
         rank, world = engine_rank_world(eng, group)
     if world > 1:
         raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
-    if design is not None:
-        dseed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
-        _generate(eng, search_space, int(eval_budget), dseed, 0, design, int(eval_budget))
-    else:
-        if Xs is None:
-            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
-        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
     hist = None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
     sizes = [min(_th.MAX_PATHS, q - a) for a in range(0, q, _th.MAX_PATHS)]
     chosen_x, chosen_f, taken = [], [], set()
@@ -644,39 +669,19 @@ def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: O
     if not is_ehvi(criterion):
         raise TypeError("ehvi_believer_batch takes a bogp.EHVI criterion (the single-objective criteria go to believer_batch)")
     model = criterion.model
-    if _forest.is_forest_model(model):
-        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no believer batches")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no believer batches")
-    if h is not None or g is not None:
-        raise NotImplementedError("constraints have no believer batches")
+    no_front = None
     if getattr(criterion, "pareto_Y", None) is None:
-        raise ValueError("an EHVI built from cells= has no front to extend with the believed means: build it with Y= or partitioning=")
-    if getattr(model, "_committed_par", None) is None:
-        raise Exception("The model is not fitted yet!")
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+        no_front = "an EHVI built from cells= has no front to extend with the believed means: build it with Y= or partitioning="
+    eng = _believer_preamble(model, lift, masks, h, g, group, rank, world, no_front=no_front)
     q = int(q)
     if q < 1:
         raise ValueError("q = %d: the believer proposes at least one point" % q)
-    if q + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
-        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
-    if design is not None:
-        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
-        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
-    else:
-        if Xs is None:
-            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
-        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    _believed_cap(q, pending)
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
     pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
     out = eng.sweep_believer_ehvi(np.asarray(criterion.pareto_Y, dtype=float).reshape(-1, criterion.n_obj), criterion.ref_point, q,
                                   pending=pend, believe_front=believe_front)
-    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+    return _believer_result(out)
 
 
 def constrained_believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = None, Xs: Optional[np.ndarray] = None,
@@ -708,38 +713,17 @@ def constrained_believer_batch(criteria, search_space, eval_budget: int, q: Opti
                         "EHVI to ehvi_believer_batch)")  # fmt: skip
     c0 = criteria[0]
     model = c0.model
-    if _forest.is_forest_model(model):
-        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no believer batches under modelled constraints")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no believer batches under modelled constraints")
-    if h is not None or g is not None:
-        raise NotImplementedError("cheap constraints h / g have no believer batches under modelled constraints: model them as columns of y")
-    if getattr(model, "_committed_par", None) is None:
-        raise Exception("The model is not fitted yet!")
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+    eng = _believer_preamble(model, lift, masks, h, g, group, rank, world, under=" under modelled constraints")
     for c in criteria[1:]:
         if (c.model is not model or c.minimize != c0.minimize or c.effective_plugin() != c0.effective_plugin()
                 or not np.array_equal(c.lo, c0.lo) or not np.array_equal(c.hi, c0.hi)):  # fmt: skip
             raise ValueError("Constrained criteria sharing one sweep must share model, bounds, plugin and minimize")
-    if len(criteria) + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
-        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
-    if design is not None:
-        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
-        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
-    else:
-        if Xs is None:
-            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
-        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    _believed_cap(len(criteria), pending)
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
     pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
     out = eng.sweep_believer_constrained([(c.acq_id, c.acq_par()) for c in criteria], c0.effective_plugin(), c0.minimize, c0.lo, c0.hi,
                                          pending=pend, believe_plugin=believe_plugin)
-    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+    return _believer_result(out)
 
 
 def constrained_ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None,
@@ -763,43 +747,22 @@ def constrained_ehvi_believer_batch(criterion, search_space, eval_budget: int, q
         raise TypeError("constrained_ehvi_believer_batch takes a %s criterion (EHVI goes to ehvi_believer_batch, bogp.Constrained to "
                         "constrained_believer_batch, the single-objective criteria to believer_batch)" % _CEHVI)  # fmt: skip
     model = criterion.model
-    if _forest.is_forest_model(model):
-        raise NotImplementedError("the Kriging believer conditions a Gaussian process: a forest model has no believer batches")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no believer batches under constrained EHVI")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no believer batches under constrained EHVI")
-    if h is not None or g is not None:
-        raise NotImplementedError("cheap constraints h / g have no believer batches under constrained EHVI: model them as columns of y")
+    no_front = None
     if getattr(criterion, "from_cells", False):
-        raise ValueError("a ConstrainedEHVI built from cells= has no front to extend with the believed means: build it with Y= or "
-                         "from the model's rows")  # fmt: skip
-    if getattr(model, "_committed_par", None) is None:
-        raise Exception("The model is not fitted yet!")
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("the Kriging believer runs on one rank (every step depends on the winner before it)")
+        no_front = "a ConstrainedEHVI built from cells= has no front to extend with the believed means: build it with Y= or from the model's rows"
+    eng = _believer_preamble(model, lift, masks, h, g, group, rank, world, under=" under constrained EHVI", no_front=no_front)
     q = int(q)
     if q < 1:
         raise ValueError("q = %d: the believer proposes at least one point" % q)
-    if q + (0 if pending is None else len(pending)) > _lib.MAX_BELIEVED:
-        raise ValueError("at most %d points are believed in one call (q + pending)" % _lib.MAX_BELIEVED)
-    if design is not None:
-        seed = int(np.random.randint(0, 2**62)) if seed is None else int(seed)
-        _generate(eng, search_space, int(eval_budget), seed, 0, design, int(eval_budget))
-    else:
-        if Xs is None:
-            Xs = np.asarray(search_space.sample(int(eval_budget), method="uniform"), dtype=float)
-        eng.upload_candidates(model._check_X(Xs), lazy=True)
+    _believed_cap(q, pending)
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
     pend = None if pending is None or len(pending) == 0 else model._check_X(pending)
     m = criterion.n_obj
     feasibility_only = criterion.n_feasible == 0  # (no feasible observation; a feasible set below ref_point has the one cell)
     front = np.zeros((0, m)) if criterion.pareto_Y is None else np.asarray(criterion.pareto_Y, dtype=float).reshape(-1, m)
     out = eng.sweep_believer_ehvi_constrained(front, criterion.ref_point, q, criterion.lo, criterion.hi, pending=pend,
                                               believe_front=believe_front, feasibility_only=feasibility_only)
-    return tuple(np.asarray(x, dtype=float).tolist() for x in out["best_x"]), tuple(float(v) for v in out["best_val"])
+    return _believer_result(out)
 
 
 def unwrap_criterion(obj):
