@@ -17,7 +17,8 @@ The directory is named `bayesian-optimization_amd/`; import it as `bogp` (bogp/_
   bogp.optim.argmax_restart      <-> bayes_optim.acquisition.optim.argmax_restart (+ optimizer="sweep")
   bogp.trend                     <-> bayes_optim.surrogate.trend
   bogp.thompson                  posterior sample paths (GaussianProcess.sampling_posterior, stubs in the reference) and
-                                 bogp.thompson_batch: q-point proposals by Thompson sampling
+                                 bogp.thompson_batch: q-point proposals by Thompson sampling;
+                                 bogp.constrained_thompson_batch: the same under modelled constraints (joint paths)
   bogp.install(bayes_optim)      re-points the reference's three extension points, ParallelBO's q-criterion loop and
                                  MOBO's acquisition (EHVI under the sweep family)
   bogp._lib.Engine               ctypes binding of libbogp.so (include/bogp.h)
@@ -30,7 +31,7 @@ __version__ = "0.1.0"
 from . import _lib, acquisition, distributed, forest, integration, lift, optim, pareto, thompson  # noqa: E402,F401
 from . import prior_mean as trend  # noqa: E402,F401
 from .acquisition import EHVI, EI, MGFI, PI, UCB, Constrained, ConstrainedEHVI, EpsilonPI  # noqa: E402,F401
-from .optim import argmax_restart, batch_argmax, believer_batch, constrained_believer_batch, constrained_ehvi_believer_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
+from .optim import argmax_restart, batch_argmax, believer_batch, constrained_believer_batch, constrained_ehvi_believer_batch, constrained_thompson_batch, device_sample, ehvi_believer_batch, sweep_argmax, sweep_generated, sweep_topk, sweep_topk_generated, thompson_batch  # noqa: E402,F401
 from .integration import feasible_front, feasible_xopt, install, uninstall  # noqa: E402,F401
 from .lift import Lift  # noqa: E402,F401
 from .surrogate import GaussianProcess  # noqa: E402,F401

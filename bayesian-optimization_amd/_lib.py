@@ -83,6 +83,8 @@ SIGNATURES = {
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_thompson_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_thompson_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_thompson_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_ehvi_grid_cells": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
     "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
                                            _dp, _dp]),
@@ -869,6 +871,53 @@ class Engine:
         c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
         self._check(self._lib.bogp_thompson_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(p), _dp),
                                                  C.cast(C.byref(n), _ip)))  # fmt: skip
+        return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
+
+    def sweep_thompson_constrained(self, draw, q: int, lo, hi, minimize=True, k: int = 1, return_values=False):
+        """Joint sample paths of the objective and the modelled constraints of the committed multi-target model over the current
+        candidates (bogp_sweep_thompson_constrained): `q` batch members of m = 1 + len(lo) targets, q m <= 16 columns.  `draw`: the
+        arrays of `bogp.thompson.draw_multi` -- omega (L, d), phase (L,), weights (L, q m), eps (N, q m) or None, column j m + t.
+        Returns a dict: best_val / best_idx (q, 2, k) -- per member the k best rows of A (the objective path, negated when
+        minimising, where the drawn constraints hold, else -inf), then of B (minus the largest scaled excess) -- best_x
+        (q, 2, k, d), coef (N, q m) and, with return_values, paths (q, m, M) in the paths' own sign.  What the library refuses as
+        unsupported raises NotImplementedError with its message."""
+        omega, phase, weights = _f64(draw.omega), _f64(draw.phase), _f64(draw.weights)
+        eps = None if draw.eps is None else _f64(draw.eps)
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        q, k, m = int(q), int(k), len(lo) + 1
+        if len(hi) != len(lo):
+            raise ValueError("lo and hi hold one bound per constraint")
+        if weights.ndim != 2 or omega.ndim != 2 or omega.shape != (len(phase), self.d) or weights.shape != (len(phase), q * m):
+            raise ValueError("a draw holds omega (L, %d), phase (L,) and weights (L, %d)" % (self.d, q * m))
+        if eps is not None and eps.shape != (self.N, q * m):
+            raise ValueError("eps must have shape (%d, %d)" % (self.N, q * m))
+        L = len(phase)
+        qa, ka = max(q, 1), max(k, 1)
+        best = np.empty((qa, 2, ka))
+        idx = np.empty((qa, 2, ka), dtype=np.int64)
+        bx = np.empty((qa, 2, ka, self.d))
+        paths = np.empty((qa, m, self.M)) if return_values else None
+        coef = np.empty((self.N, qa * m))
+        self._last_q, self._last_topk = -1, (-1, -1)
+        try:
+            self._check(self._lib.bogp_sweep_thompson_constrained(self._h, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps),
+                                                                  int(bool(minimize)), len(lo), _ptr(lo), _ptr(hi), k, _ptr(best),
+                                                                  idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths), _ptr(coef)))  # fmt: skip
+        except BogpError as e:
+            if e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+        out = dict(best_val=best, best_idx=idx, best_x=bx, coef=coef)
+        if return_values:
+            out["paths"] = paths
+        return out
+
+    def thompson_constrained_last(self) -> dict:
+        """Producer time, time of the draw at the training rows with its solves, k_thompson_constrained time over the candidates
+        (ms) and the chunks of the last sweep_thompson_constrained (bogp_thompson_constrained_last)."""
+        c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(self._lib.bogp_thompson_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp),
+                                                             C.cast(C.byref(p), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
 
     def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):

@@ -319,6 +319,8 @@ struct bogp_handle {
   bogp::SpanTimer th_timer;        // draw at X + solves, chunk producers, k_thompson
   double th_corr_ms = 0, th_solve_ms = 0, th_paths_ms = 0;  // of the last bogp_sweep_thompson: producer, draw at X + solves, k_thompson
   int th_chunks = 0;
+  double thc_corr_ms = 0, thc_solve_ms = 0, thc_paths_ms = 0;  // of the last bogp_sweep_thompson_constrained, on th_timer's spans
+  int thc_chunks = 0;
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

@@ -428,6 +428,32 @@ struct ThompsonArgs {
 };
 hipError_t launch_thompson(const ThompsonArgs& a, hipStream_t st);
 
+// q batch members' joint sample paths of the m targets of a multi-target model over a chunk (kernels_thompson_constrained.hip):
+// path_{j,t}(x) = beta + r(x) . (gamma_t - g_{j,t}) + z_{j,t}(x), target 0 the objective, target t >= 1 a constraint feasible in
+// [lo[t], hi[t]].  Per row and member A = feasible ? +-path_{j,0} : -inf and B = 0 - max_t(excess_t inv_sd[t]); one np.argmax record
+// per score and 64 rows.  DEVICE column of (member j, target t): t q + j (the ABI's is j m + t; the host permutes W and coef).
+struct ThompsonConstrainedArgs {
+  const double* X;        // [M][d] the candidates
+  int64_t row0, mcount;   // first row of this launch; rows it serves
+  int d, L, N, q, m;      // L: features, a multiple of 16; q m <= 16
+  const double* omega;    // [L][d]
+  const double* phase;    // [L]
+  const double* W;        // [L][16] weights times sqrt(2 sigma2_t / L) in device column order, zero columns from q m on
+  const double* rT;       // [Np][ld] the chunk's correlation columns
+  int64_t ld;             // Mc: stride of rT
+  const double* coef;     // [ceil(N / 4) * 4][16] gamma_t - g_{j,t} in device column order, zero padded rows and columns
+  double beta;
+  double lo[8], hi[8], inv_sd[8];  // per target; entry 0 is not read
+  int minimize;           // A = -path_{j,0} where feasible
+  double* scores;         // [2 q][M] at the global row: row 2 j is A_j, row 2 j + 1 is B_j; or null
+  double* paths;          // [q m][M] at the global row, row j m + t, in the path's own sign; or null
+  int64_t M;
+  double* blk_val;        // [2 q][nblk_total]
+  int64_t* blk_idx;
+  int64_t blk_offset, nblk_total;
+};
+hipError_t launch_thompson_constrained(const ThompsonConstrainedArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

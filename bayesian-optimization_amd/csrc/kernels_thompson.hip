@@ -6,6 +6,7 @@
 // with W pre-scaled by sqrt(2 sigma2 / L) and (g_j, b_j) the kriging of the draw's own "data" (bogp_api_thompson.hip).  It needs the
 // correlation column r(x) once -- the producer's n-major chunk -- and never the N^2 variance contraction.
 //
+// The feature term and the conditioning term below live in bogp_thompson_phases.h, which k_thompson_constrained shares.
 // k_thompson: one workgroup of 256 serves 64 candidates, one wave 16 candidates x 16 paths (q padded by zero columns of W and g) in
 // ONE v_mfma_f64_16x16x4_f64 accumulator acc[cand][path]: D row = candidate = (lane >> 4) + 4 reg, D column = path = lane & 15.
 //   feature term, per tile of 16 features f0 ..: the phase tile TRANSPOSED, P[feature][cand] = Omega_tile X^T, ceil(d / 4) k-steps with
@@ -22,17 +23,9 @@
 #include "bogp_device.h"
 #include "bogp_internal.h"
 #include "bogp_mfma.h"
+#include "bogp_thompson_phases.h"
 
 namespace bogp {
-
-namespace {
-// Operands built by VALU code (selects, cos, the zeroed accumulator) must have retired (bogp_mfma.h, 4.): the nop pins all three in
-// registers two wait states ahead of the instruction.
-__device__ __forceinline__ void mfma16t(double a, double b, d4& c) {
-  asm volatile("s_nop 1" : "+v"(a), "+v"(b), "+v"(c));
-  mfma16(a, b, c);
-}
-}  // namespace
 
 __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
   __shared__ double sv[4][16];
@@ -47,49 +40,9 @@ __global__ __launch_bounds__(256) void k_thompson(ThompsonArgs a) {
   // ---- feature term
   const bool xrow = c0 + li < a.mcount;
   const double* xp = a.X + (size_t)(a.row0 + c0 + li) * d;  // dereferenced under xrow only
-  for (int f0 = 0; f0 < a.L; f0 += 16) {
-    d4 ph = (d4){0.0, 0.0, 0.0, 0.0};
-    const double* op = a.omega + (size_t)(f0 + li) * d;
-    for (int k0 = 0; k0 < d; k0 += 4) {
-      const int k = k0 + lk;
-      const double ov = k < d ? op[k] : 0.0;
-      const double xv = (k < d && xrow) ? xp[k] : 0.0;
-      mfma16t(ov, xv, ph);
-    }
-    double wv[4], pv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      wv[r] = a.W[(size_t)(f0 + 4 * r + lk) * 16 + li];
-      pv[r] = a.phase[f0 + 4 * r + lk];
-    }
-    mfma16_drain(ph);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) pv[r] = cos(ph[r] + pv[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mfma16t(pv[r], wv[r], acc);
-  }
+  thompson_feature_term(a.omega, a.phase, a.W, a.L, d, xp, xrow, li, lk, acc);
   // ---- conditioning term: acc -= r . g (the host uploads -g)
-  if (a.mode == 2) {
-    const double* rp = a.rT + c0 + li;
-    const int nfull = a.N & ~3, N4 = (a.N + 3) & ~3;
-    int n0 = 0;
-    for (; n0 + 16 <= nfull; n0 += 16) {
-      double rv[4], gv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        rv[u] = rp[(size_t)(n0 + 4 * u + lk) * a.ld];
-        gv[u] = a.ngt[(size_t)(n0 + 4 * u + lk) * 16 + li];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) mfma16t(rv[u], gv[u], acc);
-    }
-    for (; n0 < N4; n0 += 4) {
-      const int n = n0 + lk;
-      const double rv = n < a.N ? rp[(size_t)n * a.ld] : 0.0;
-      const double gv = a.ngt[(size_t)n * 16 + li];
-      mfma16t(rv, gv, acc);
-    }
-  }
+  if (a.mode == 2) thompson_conditioning_term(a.rT + c0 + li, a.ld, a.ngt, a.N, li, lk, acc);
   mfma16_drain(acc);
 
   // ---- epilogue: lane l holds path li of the candidates c0 + 4 reg + lk

@@ -110,6 +110,13 @@ def fused_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=N
         # install(constraint_batches="believer"): the q feasibility-weighted criteria condition each other (every other case: below)
         xs, fs = optim.constrained_believer_batch(crits, kw["search_space"], int(budget or kw["eval_budget"]), design=design)
         return tuple(xs), tuple(fs)
+    if (_CONSTRAINTS.get("batches") == "thompson" and all(optim.is_constrained(c) for c in crits) and masks is None and not fixed
+            and kw.get("h") is None and kw.get("g") is None):  # fmt: skip
+        # install(constraint_thompson=True): one joint draw of objective and constraints per point; the criteria supply model, bounds
+        # and direction only
+        xs, fs = optim.constrained_thompson_batch(crits[0], kw["search_space"], int(budget or kw["eval_budget"]), n_point, design=design,
+                                                  history=_history_of(self))  # fmt: skip
+        return tuple(xs), tuple(fs)
     k = int(min(32, n_point + 8))  # fall-backs: at most n_point - 1 taken by earlier criteria + a few history hits
     xs, fs = optim.batch_argmax(crits, kw["search_space"], int(budget or kw["eval_budget"]), history=_history_of(self), k=k,
                                 design=design, masks=masks, values=values, h=kw.get("h"), g=kw.get("g"), **_strategy_of(masks, kw, crits))  # fmt: skip
@@ -644,7 +651,7 @@ def _dispatching_surrogate(host_cls):
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
-            constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk"):
+            constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -692,6 +699,12 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `bogp.Constrained`, the inner optimiser is of the sweep family, nothing is fixed and no cheap h / g is given; every other step
     takes the route it took before.
 
+    `constraint_thompson=True` (with `expensive_constraints=True`; alone, or together with `constraint_batches="believer"`, it raises
+    ValueError): the same steps go to `optim.constrained_thompson_batch` instead -- per point one joint draw of the objective and
+    the constraints, the best drawn objective where the drawn constraints hold, the least violating row where they hold nowhere
+    (Eriksson & Poloczek 2021) -- with the run's history; the criteria supply model, bounds and direction only.  A model that
+    Thompson sampling refuses (a nugget or noise estimate, ...) raises NotImplementedError naming it.
+
     `constrained_mobo=True` (with `expensive_constraints=True`; alone it raises ValueError; an extension: `BaseMOBO.tell` leaves the
     values as a TODO, mobo.py:117-118): the reference's `MOBO` with a device GP keeps the `h_vals` / `g_vals` of its tell()
     (`refusing_mobo_tell`, by `constrained_tell`'s rules), fits objectives and constraints as one multi-target model
@@ -724,6 +737,10 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         raise ValueError("constraint_batches must be 'topk' or 'believer', not %r" % (constraint_batches,))
     if constraint_batches == "believer" and not expensive_constraints:
         raise ValueError("constraint_batches='believer' needs expensive_constraints=True (it batches the feasibility-weighted criterion)")
+    if constraint_thompson and not expensive_constraints:
+        raise ValueError("constraint_thompson=True needs expensive_constraints=True (it draws the objective and the modelled constraints jointly)")
+    if constraint_thompson and constraint_batches == "believer":
+        raise ValueError("constraint_thompson=True and constraint_batches='believer' name two batch strategies for one step: choose one")
     if constraint_gradient and not expensive_constraints:
         raise ValueError("constraint_gradient=True needs expensive_constraints=True (it is the input gradient of the feasibility-weighted criterion)")
     _CONSTRAINTS.clear()
@@ -735,6 +752,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["gradient"] = True
         if constraint_batches == "believer":
             _CONSTRAINTS["batches"] = "believer"
+        if constraint_thompson:
+            _CONSTRAINTS["batches"] = "thompson"
         if constrained_mobo:
             _CONSTRAINTS["mobo"] = True
         if constrained_mobo_gradient:

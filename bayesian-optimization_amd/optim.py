@@ -651,6 +651,84 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
+                               Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None,
+                               k: int = 8, lift=None, masks=None, values=None, h: Optional[Callable] = None,
+                               g: Optional[Callable] = None, group=None, rank=None, world=None):
+    """A q-point proposal under modelled constraints by Thompson sampling (`bogp_sweep_thompson_constrained`; Eriksson & Poloczek
+    2021): per proposed point ONE joint draw of the objective and the constraints of `criterion.model` (`bogp.thompson`:
+    `draw_multi`, independent weights over shared random Fourier features), and among the candidates the best objective value where
+    the DRAWN constraints hold -- the least violating row (largest excess over a bound in units of that constraint's prior standard
+    deviation) where they hold nowhere, so a run without a feasible observation needs no other criterion.  `criterion`: one
+    `bogp.Constrained`; it supplies model, `lo`, `hi` and `minimize` -- its `fun` is not used, and a feasibility-only criterion is
+    served as any other.  ONE producer pass and one streaming pass serve `16 // m` members (m targets); more run in further calls
+    with seeds derived from `seed` (`thompson.batch_seeds`).  Candidates as in `believer_batch`.  Every member lists its `k` best
+    rows (`thompson.merge_ranks`: feasible rows first) and takes the first that no earlier member took and that is not `np.isclose`
+    to a row of `history` (`thompson_batch`'s rule), so the q proposals are q distinct rows.  Returns (xopt: tuple of q lists, fopt:
+    tuple of q floats) in `batch_argmax`'s format; fopt is the objective path's value at the proposal (for a least violating row:
+    that row of the dense restatement, `thompson.objective_path_at`).
+    TypeError: a criterion that is not `bogp.Constrained`.  Refused (NotImplementedError): `ConstrainedEHVI`, a forest model, a
+    lift, fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    from . import thompson as _th
+
+    if is_constrained_ehvi(criterion):
+        raise NotImplementedError("%s has no Thompson batches: constrained_thompson_batch takes one objective" % _CEHVI)
+    if not is_constrained(criterion):
+        raise TypeError("constrained_thompson_batch takes one bogp.Constrained criterion (a model alone goes to thompson_batch)")
+    model = criterion.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no Thompson batches under modelled constraints")
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no Thompson batches under modelled constraints")
+    if h is not None or g is not None:
+        raise NotImplementedError("cheap constraints h / g have no Thompson batches under modelled constraints: model them as columns of y")
+    st = _th.state_of_multi(model)  # the model's own refusals: not fitted, mode, trend, kernel
+    q, k = int(q), int(k)
+    if q < 1:
+        raise ValueError("q = %d: Thompson sampling proposes at least one point" % q)
+    if k < 1:
+        raise ValueError("k = %d: every member lists at least one row" % k)
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
+    hist = None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
+    m = st.y.shape[1]
+    per_call = _th.MAX_PATHS // m
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    minimize = bool(criterion.minimize)
+    chosen_x, chosen_f, taken = [], [], set()
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, k + len(taken))))  # a later call also steps over the rows the earlier ones took
+        dr = _th.draw_multi(model, qb, n_features, sd)
+        out = eng.sweep_thompson_constrained(dr, qb, criterion.lo, criterion.hi, minimize=minimize, k=kk)
+        for c in range(qb):
+            ranks = _th.merge_ranks(out["best_val"][c], out["best_idx"][c], kk)
+            pick = None
+            for gi, which, r in ranks:
+                if gi in taken:
+                    continue
+                if hist is not None and np.any(np.all(np.isclose(hist, out["best_x"][c, which, r]), axis=1)):
+                    continue
+                pick = (gi, which, r)
+                break
+            if pick is None:  # every fall-back exhausted: keep the first listed row (the caller's duplicate check will pad)
+                pick = ranks[0] if ranks else (int(out["best_idx"][c, 1, 0]), 1, 0)
+            gi, which, r = pick
+            taken.add(gi)
+            chosen_x.append(np.asarray(out["best_x"][c, which, r], dtype=float).tolist())
+            if which == 0:  # an A rank is the objective path's value in the criterion's sign
+                v = float(out["best_val"][c, 0, r])
+                chosen_f.append(-v if minimize else v)
+            else:  # a least violating row: its objective value is in no ranking -- one row of the restatement on the device's g
+                chosen_f.append(_th.objective_path_at(st, dr, out["coef"], c, out["best_x"][c, which, r]))
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
                         seed: Optional[int] = None, pending=None, believe_front: bool = True, lift=None, masks=None, values=None,
                         h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):

@@ -23,7 +23,11 @@ exp(-sum theta_i d_i^2), Matern on dists = sqrt(sum theta_i d_i^2), absolute-exp
 Cauchy variates (L x d; absolute-exponential), then b (L), W (L x q), E (N x q) -- and the device consumes the same arrays as
 `paths_numpy`, the dense float64 restatement.  The noisy and noise-estimating modes are refused: there the reference pairs an
 unscaled r(x) with a rescaled R (gpr.py:949-979), R - K(X, X) is indefinite, and no Gaussian process has that mean / MSE pair as
-its conditional law."""
+its conditional law.
+
+The second half of the module is the multi-target form for Thompson batches under modelled constraints
+(`bogp_sweep_thompson_constrained`): `state_of_multi`, `draw_multi`, `paths_multi_numpy`, the selection rule `select_numpy` and
+`merge_ranks`.  `state_of`, `draw`, `paths_numpy` and `sampling_posterior` serve one target and refuse several, as before."""
 from __future__ import annotations
 
 import math
@@ -207,3 +211,187 @@ def sample(model, X, n_samples=1, n_features=1024, seed=None, conditioned=True):
         out = eng.sweep_thompson(draw(model, qb, n_features, sd), conditioned=conditioned, return_values=True)
         cols.append(np.asarray(out["paths"]).T)
     return np.concatenate(cols, axis=1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# joint paths of a multi-target model: Thompson batches under modelled constraints (`bogp_sweep_thompson_constrained`)
+# ----------------------------------------------------------------------------------------------------------------------
+# The targets of a multi-target model share R (and so theta and r(x)) and are a priori independent; its trend is a FIXED constant, so the
+# conditional law is the simple-kriging one.  A call carries q batch members of m targets over shared features; column j m + t of the
+# weights and of eps is member j's path of target t:
+#
+#     z_{j,t}(x)    = sqrt(2 sigma2_t / L) sum_l W[l, j m + t] cos(omega_l . x + b_l)
+#     s_{j,t}       = z_{j,t}(X) + sqrt(sigma2_t (diag(R) - 1)) * E[:, j m + t]
+#     gt_{j,t}      = R^-1 s_{j,t}
+#     path_{j,t}(x) = beta + r(x) . (gamma_t - gt_{j,t}) + z_{j,t}(x),      gamma_t = R^-1 (y_t - beta)
+#
+# Independent weights over shared features give independent targets.  The selection rule is Eriksson & Poloczek's (2021): the best
+# objective value among the rows whose drawn constraints hold, the least violating row when there is none (`select_numpy`).
+
+
+def dense_state_multi(X, Y, theta, kernel, beta=0.0, nu=None, sigma2=None):
+    """A multi-target model for `draw_multi` / `paths_multi_numpy` without an engine: Y (N, m), a fixed constant trend `beta`, sigma2
+    (m,) concentrated per target unless given."""
+    X = np.ascontiguousarray(X, dtype=float)
+    Y = np.asarray(Y, dtype=float).reshape(len(X), -1)
+    st = SimpleNamespace(X=X, y=Y, theta=np.broadcast_to(np.asarray(theta, dtype=float).ravel(), (X.shape[1],)).copy(), kernel=int(kernel),
+                         nu=nu, estimate_trend=False, nugget=np.zeros(len(X)), beta=float(beta), sigma2=sigma2, multi=True)  # fmt: skip
+    res = Y - st.beta
+    st.gamma = np.linalg.solve(correlation(st, X, X), res)  # (N, m)
+    if sigma2 is None:
+        st.sigma2 = np.einsum("nt,nt->t", res, st.gamma) / len(X)
+    st.sigma2 = np.asarray(st.sigma2, dtype=float).ravel()
+    return st
+
+
+def state_of_multi(model):
+    """What the joint formulas read, from a `GaussianProcess` fitted on y (N, m), m >= 2 (or a `dense_state_multi`, returned as it
+    is): X, y (N, m), theta, kernel, beta, and per target sigma2 (m,) and gamma (N, m).  The refusals live here."""
+    if isinstance(model, SimpleNamespace):
+        refuse_kernel(model.kernel)
+        if not getattr(model, "multi", False):
+            raise ValueError("joint paths need a multi-target state (thompson.dense_state_multi)")
+        return model
+    if type(model).__name__ == "RandomForest" or hasattr(model, "estimators_"):
+        raise NotImplementedError("a forest model has no posterior paths to draw (Thompson sampling conditions a Gaussian process)")
+    if getattr(model, "_committed_par", None) is None:
+        raise Exception("The model is not fitted yet!")
+    mode = "noisy" if getattr(model, "_committed_restricted", False) else model.estimation_mode
+    if mode != "noiseless":
+        raise NotImplementedError("posterior paths in the %s mode: the reference pairs an unscaled r(x) with a rescaled R there "
+                                  "(gpr.py:949-979), which is no Gaussian process's conditional law; use nugget=0, noise_estim=False" % mode)  # fmt: skip
+    if type(model.mean).__name__ != "constant_trend":
+        raise NotImplementedError("posterior paths serve the constant trend basis, not the polynomial trends (%s)" % type(model.mean).__name__)
+    if np.ndim(model.y) < 2 or model.y.shape[1] < 2:
+        raise ValueError("joint paths need a model fitted on y (N, m) with m >= 2 columns (objective, constraints): one target goes to "
+                         "thompson.state_of")  # fmt: skip
+    if model.estimate_trend:
+        raise NotImplementedError("a multi-target model has a fixed constant trend (gpr.py:787): joint paths with an estimated one")
+    refuse_kernel(model.kernel_id)
+    d, m = model.X.shape[1], model.y.shape[1]
+    return SimpleNamespace(X=model.X, y=np.asarray(model.y, dtype=float), kernel=model.kernel_id, nu=model._nu,
+                           theta=np.broadcast_to(np.asarray(model.theta_, dtype=float).ravel(), (d,)).copy(), nugget=np.zeros(len(model.X)),
+                           estimate_trend=False, beta=float(np.ravel(model.mean.beta)[0]),
+                           sigma2=np.broadcast_to(np.asarray(model.sigma2, dtype=float).ravel(), (m,)).copy(),
+                           gamma=np.asarray(model.gamma, dtype=float).reshape(len(model.X), m), multi=True)  # fmt: skip
+
+
+def draw_multi(model, q, n_features=1024, seed=None):
+    """The random numbers of q members' joint paths of the m targets: `draw`'s arrays in `draw`'s RNG order with q m columns, column
+    j m + t member j's path of target t.  q m <= 16."""
+    st = state_of_multi(model)
+    q, m = int(q), st.y.shape[1]
+    if q < 1:
+        raise ValueError("q = %d: at least one member" % q)
+    if q * m > MAX_PATHS:
+        raise ValueError("q = %d members of %d targets: at most %d columns in one call" % (q, m, MAX_PATHS))
+    return draw(SimpleNamespace(X=st.X, kernel=st.kernel, theta=st.theta, nu=st.nu), q * m, n_features, seed)
+
+
+def paths_multi_numpy(model, dr, X):
+    """The dense float64 restatement of the joint formulas: (paths (q, m, len(X)), gt (N, q m))."""
+    st = state_of_multi(model)
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    N, m = st.y.shape
+    qm = dr.weights.shape[1]
+    if qm % m:
+        raise ValueError("the draw has %d columns, no multiple of the %d targets" % (qm, m))
+    L = len(dr.phase)
+    scale = np.tile(np.sqrt(2.0 * st.sigma2 / L), qm // m)  # column j m + t: target t's
+    R = correlation(st, st.X, st.X) + np.diag(st.nugget)
+    z = (np.cos(X @ dr.omega.T + dr.phase) @ dr.weights) * scale
+    s = (np.cos(st.X @ dr.omega.T + dr.phase) @ dr.weights) * scale
+    if dr.eps is not None:
+        s = s + np.sqrt(np.outer(st.nugget, np.tile(st.sigma2, qm // m))) * dr.eps
+    gt = np.linalg.solve(R, s)
+    gamma = np.tile(np.linalg.solve(R, st.y - st.beta), (1, qm // m))
+    r = correlation(st, X, st.X)
+    paths = st.beta + r @ (gamma - gt) + z
+    return paths.T.reshape(qm // m, m, len(X)), gt
+
+
+def objective_path_at(model, dr, gt, j, x):
+    """path_{j,0}(x) at ONE point from the coefficients `gt` (N, q m) a call returned and the model's own gamma_0:
+    beta + r(x) . (gamma_0 - gt_{j,0}) + z_{j,0}(x).  O(N d + L d), no solve."""
+    st = state_of_multi(model)
+    m = st.y.shape[1]
+    x = np.asarray(x, dtype=float).reshape(1, -1)
+    gamma0 = st.gamma[:, 0]
+    z = math.sqrt(2.0 * st.sigma2[0] / len(dr.phase)) * (np.cos(x @ dr.omega.T + dr.phase) @ dr.weights[:, j * m])
+    return float(st.beta + correlation(st, x, st.X)[0] @ (gamma0 - np.asarray(gt)[:, j * m]) + z[0])
+
+
+def moments_multi_numpy(model, X):
+    """mu (M, m) and MSE (M, m) of the multi-target predictor the joint paths are conditioned on, densely."""
+    st = state_of_multi(model)
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    R = correlation(st, st.X, st.X) + np.diag(st.nugget)
+    r = correlation(st, X, st.X)
+    mu = st.beta + r @ np.linalg.solve(R, st.y - st.beta)
+    return mu, np.outer(1.0 - np.einsum("mn,nm->m", r, np.linalg.solve(R, r.T)), st.sigma2)
+
+
+def rank_numpy(crit, k):
+    """`bogp_sweep_topk`'s ranking of every row of `crit` (n, M): first maximum, ties to the lower index, NaN maximal; slots beyond
+    M are (-inf, -1).  (values (n, k), indices (n, k))."""
+    n, M = crit.shape
+    val, idx = np.full((n, k), -np.inf), np.full((n, k), -1, dtype=np.int64)
+    for j in range(n):
+        order = np.argsort(-np.where(np.isnan(crit[j]), np.inf, crit[j]), kind="stable")[:k]
+        val[j, : len(order)], idx[j, : len(order)] = crit[j][order], order
+    return val, idx
+
+
+def select_numpy(paths, lo, hi, sigma2, minimize=True, k=1):
+    """The selection of `bogp_sweep_thompson_constrained` on path values (q, m, M), in the device's own operations -- comparisons,
+    differences and single products, no sum -- so that it reproduces the device's scores from the device's paths exactly:
+
+        e_t = max(lo_t - c_t, c_t - hi_t, 0),  viol = max_{t >= 1} e_t / sqrt(sigma2_t),  feas = every lo_t <= c_t <= hi_t
+        A = feas ? (-c_0 if minimize else c_0) : -inf,   B = 0.0 - viol,   a NaN among the m values: A = B = -inf
+
+    Returns a dict: A, B (q, M), feas (q, M), best_val / best_idx (q, 2, k): per member the ranking of A, then of B."""
+    paths = np.asarray(paths, dtype=float)
+    q, m, M = paths.shape
+    lo, hi = np.asarray(lo, dtype=float).ravel(), np.asarray(hi, dtype=float).ravel()
+    inv_sd = 1.0 / np.sqrt(np.asarray(sigma2, dtype=float).ravel()[1:])
+    if len(lo) != m - 1 or len(hi) != m - 1 or len(inv_sd) != m - 1:
+        raise ValueError("lo, hi hold one bound per constraint, sigma2 one value per target (%d targets)" % m)
+    feas = np.ones((q, M), dtype=bool)
+    viol = np.zeros((q, M))
+    with np.errstate(invalid="ignore"):
+        for t in range(1, m):
+            c = paths[:, t]
+            d1, d2 = lo[t - 1] - c, c - hi[t - 1]
+            e = np.where(d1 > 0.0, d1, 0.0)
+            e = np.where(d2 > e, d2, e)
+            p = e * inv_sd[t - 1]
+            viol = np.where(p > viol, p, viol)
+            feas &= (lo[t - 1] <= c) & (c <= hi[t - 1])
+    bad = np.isnan(paths).any(axis=1)
+    A = np.where(feas, -1 * paths[:, 0] if minimize else paths[:, 0], -np.inf)
+    B = 0.0 - viol
+    A[bad], B[bad] = -np.inf, -np.inf
+    k = int(k)
+    va, ia = rank_numpy(A, k)
+    vb, ib = rank_numpy(B, k)
+    return dict(A=A, B=B, feas=feas & ~bad, best_val=np.stack([va, vb], axis=1), best_idx=np.stack([ia, ib], axis=1))
+
+
+def merge_ranks(best_val, best_idx, k=None):
+    """A member's proposal list from its rankings (2, k'): the A ranks whose value is above -inf (rows whose drawn constraints
+    hold, best objective first), then the B ranks (least violating first) whose row is not already listed; unfilled slots (-1) are
+    dropped and the list is cut to `k` (default k').  Returns a list of (row, which, rank): which = 0 for an A rank, 1 for a B rank."""
+    best_val, best_idx = np.asarray(best_val), np.asarray(best_idx)
+    k = best_val.shape[-1] if k is None else int(k)
+    out, seen = [], set()
+    for r in range(best_val.shape[-1]):
+        gi = int(best_idx[0, r])
+        if gi >= 0 and best_val[0, r] > -np.inf and gi not in seen:
+            out.append((gi, 0, r))
+            seen.add(gi)
+    for r in range(best_val.shape[-1]):
+        gi = int(best_idx[1, r])
+        if gi >= 0 and best_val[1, r] > -np.inf and gi not in seen:
+            out.append((gi, 1, r))
+            seen.add(gi)
+    return out[:k]

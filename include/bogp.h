@@ -422,6 +422,42 @@ int bogp_sweep_thompson(bogp_handle* h, int q, int L, const double* omega, const
                         double* best_x, double* paths_out, double* coef_out);
 int bogp_thompson_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
 
+/* ---- sweep: Thompson-sampling batches under modelled constraints ------------------------------------------
+ * Joint sample paths of the objective and the modelled constraints (Eriksson & Poloczek 2021, SCBO).  The model is
+ * bogp_sweep_constrained's: a committed multi-target model with m = 1 + n_con targets, target 0 the objective, target t >= 1 a
+ * constraint that is feasible in [lo[t-1], hi[t-1]]; noiseless mode, constant basis (a multi-target commit has a FIXED constant
+ * trend, so the conditional law is the simple-kriging one and there is no b).  A call carries q batch members, q m <=
+ * BOGP_MAX_PATHS columns; column (j, t) -- index j m + t in weights, eps, paths_out and coef_out -- is member j's path of
+ * target t.  The L features are shared, weights and eps are per column, so the targets are independent as in the model:
+ *   z_{j,t}(x)    = sqrt(2 sigma2_t / L) sum_l W[l][j m + t] cos(omega_l . x + phase_l)
+ *   s_{j,t}       = z_{j,t}(X) + sqrt(sigma2_t (diag(R) - 1)) E[:, j m + t]
+ *   g_{j,t}       = R^-1 s_{j,t}
+ *   path_{j,t}(x) = beta + r(x) . (gamma_t - g_{j,t}) + z_{j,t}(x)
+ * Selection per row x and member j, with c_t = path_{j,t}(x), s = -1 when minimising and +1 otherwise:
+ *   e_t    = max(lo_t - c_t, c_t - hi_t, 0)
+ *   viol   = max_{t >= 1} (e_t inv_sd_t),   inv_sd_t = 1 / sqrt(sigma2_t) (formed on the host)
+ *   feas   = every (lo_t <= c_t) and (c_t <= hi_t) holds
+ *   A_j(x) = feas ? s path_{j,0}(x) : -inf          the objective among the rows whose drawn constraints hold
+ *   B_j(x) = 0.0 - viol                             the least violating row, for a member without a feasible row
+ * A row with a NaN among its m path values has A = B = -inf.  viol is a maximum of single products: no sum is formed, so A and B
+ * follow from the returned path values exactly.
+ *   omega (L x d), phase (L), weights (L x q m), eps (N x q m or NULL = zeros): HOST arrays, row-major
+ *   best_val, best_idx (q x 2 x k): per member the k best rows of A, then the k best rows of B, by bogp_sweep_topk's rules (first
+ *              maximum, ties to the lower index, slots beyond M are (-inf, -1));  best_x (q x 2 x k x d, may be NULL)
+ *   paths_out (q x m x M, may be NULL): the paths' own values;  coef_out (N x q m, may be NULL): g
+ * Per call: the draw at the training rows and one N x q m solve; per candidate chunk the correlation producer and
+ * k_thompson_constrained (kernels_thompson_constrained.hip).  The outputs are bit-identical for any BOGP_CHUNK_MB, with and
+ * without paths_out, and a member's do not depend on the members beside it.
+ * BOGP_ERR_INVALID: no committed model, no candidates, a model of one target (bogp_sweep_thompson serves it), n_con != n_targets
+ * - 1, q < 1 or q m > BOGP_MAX_PATHS, L or k out of range, a null required array, a NaN bound, hi < lo, a non-finite entry in
+ * omega / phase / weights / eps.  BOGP_ERR_UNSUPPORTED: the noisy and noise-estimating modes, the cubic and
+ * generalized-exponential kernels, a polynomial trend basis, a lift on the handle, a forest, a communicator of more than one
+ * rank.  `thompson_constrained_last`: as bogp_thompson_last, of the last constrained call.                                  */
+int bogp_sweep_thompson_constrained(bogp_handle* h, int q, int L, const double* omega, const double* phase, const double* weights,
+                                    const double* eps, int minimize, int n_con, const double* lo, const double* hi, int k,
+                                    double* best_val, int64_t* best_idx, double* best_x, double* paths_out, double* coef_out);
+int bogp_thompson_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
+
 /* ---- sweep: Kriging-believer batches for EHVI -------------------------------------------------------------
  * q proposals per call for a multi-objective run -- what the reference names and leaves open: `class MOBO: """EHVI with
  * Kriging believer"""` stands over `# TODO: implement the Kriging believer strategy` (mobo.py:168-178), and MOBO(n_point > 1)

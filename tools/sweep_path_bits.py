@@ -9,7 +9,7 @@ exactly when their listings agree line for line:
 The cases are the smallest that reach each branch of run_sweep (csrc/bogp_api_sweep.hip): the <= 32-row batch, the one-launch
 sweep, the chunk loop with its trend variants / two streams / lazy upload, the queued sweep, both pruned flows with their
 fall-backs, EHVI, the believer batches of the four families (several chunks, one resident chunk, a guarded pivot in front of step 0),
-Thompson batches and the lifted sweep.  Needs an MI355X."""
+Thompson batches, the lifted sweep and Thompson batches under modelled constraints.  Needs an MI355X."""
 import argparse
 import collections
 import hashlib
@@ -213,6 +213,21 @@ def case_batches(_lib, np, rng, what):
         for k in (1, 3):
             out = eng.sweep_thompson(dr, minimize=True, k=k, conditioned=True, return_values=k == 3)
             report(eng, "thompson/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"][0], out["coef"][1], out.get("paths"))
+    elif what == "thompson-constrained":  # m = 3 joint paths, q = 5 members (15 columns), L = 64, k = 1 and k = 3
+        d, m, q = 4, 3, 5
+        X = rng.uniform(-2, 2, (N, d))
+        Y = np.column_stack([2 * np.sin(X @ rng.normal(size=d) / np.sqrt(d)) + 0.1 * rng.normal(size=N) for _ in range(m)])
+        nn = 4.0 / N ** (1.0 / d)
+        eng = _lib.Engine(0)
+        eng.set_train(X, Y)
+        eng.commit(3, _lib.MODE_NOISELESS, np.full(d, 1.0 / (d * nn * nn)), 0.0, False, 0.3)
+        eng.upload_candidates(rng.uniform(-2.2, 2.2, (M, d)))
+        Draw = collections.namedtuple("Draw", "omega phase weights eps")
+        dr = Draw(rng.normal(size=(64, d)), rng.uniform(0, 2 * np.pi, 64), rng.normal(size=(64, q * m)), rng.normal(size=(N, q * m)))
+        lo, hi = np.full(m - 1, -np.inf), np.median(Y[:, 1:], axis=0)
+        for k in (1, 3):
+            out = eng.sweep_thompson_constrained(dr, q, lo, hi, minimize=True, k=k, return_values=k == 3)
+            report(eng, "thompson-constrained/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"], out.get("paths"))
     else:  # one lifted sweep: r = 3 model, D = 5 box, part of the rows infeasible
         eng, X, y = smooth_model(_lib, rng, N, 3)
         eng.upload_candidates(rng.uniform(-5, 5, (M, 3)))
@@ -281,6 +296,7 @@ CASES = collections.OrderedDict([
     ("believer-guard-one-chunk", (case_guard, "", {})),
     ("thompson", (case_batches, "thompson", {"BOGP_CHUNK_MB": "8"})),
     ("lift", (case_batches, "lift", {"BOGP_CHUNK_MB": "8"})),
+    ("thompson-constrained", (case_batches, "thompson-constrained", {"BOGP_CHUNK_MB": "8"})),  # (behind the older cases: their lines keep their place)
 ])  # fmt: skip
 
 
