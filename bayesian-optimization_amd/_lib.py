@@ -832,34 +832,44 @@ class Engine:
                                                  C.cast(C.byref(n), _ip)))  # fmt: skip
         return dict(corr_ms=c.value, solve_ms=s.value, believer_ms=b.value, n_passes=n.value)
 
+    def _thompson_draw(self, draw, ncol=None):
+        """A draw's arrays as the entries take them: (L, omega, phase, weights, eps or None), checked against `ncol` columns -- the
+        weights' own count (and so q) where it is None."""
+        omega, phase, weights = _f64(draw.omega), _f64(draw.phase), _f64(draw.weights)
+        eps = None if draw.eps is None else _f64(draw.eps)
+        bad = weights.ndim != 2 or omega.ndim != 2 or omega.shape != (len(phase), self.d) or weights.shape[0] != len(phase)
+        if bad or (ncol is not None and weights.shape[1] != ncol):
+            raise ValueError("a draw holds omega (L, %d), phase (L,) and weights (L, %s)" % (self.d, "q" if ncol is None else ncol))
+        if eps is not None and eps.shape != (self.N, weights.shape[1]):
+            raise ValueError("eps must have shape (%d, %d)" % (self.N, weights.shape[1]))
+        return len(phase), omega, phase, weights, eps
+
+    def _thompson_call(self, fn, *args):
+        """One Thompson entry: no sweep's winners stay readable behind it; what the library refuses as unsupported raises
+        NotImplementedError with its message."""
+        self._believer_call(fn, *args, unsupported=True)
+
+    def _thompson_last(self, fn):
+        """The four figures of a family's *_last entry: producer, draw at the training rows with its solves, the kernel, chunks."""
+        c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        self._check(fn(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(p), _dp), C.cast(C.byref(n), _ip)))
+        return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
+
     def sweep_thompson(self, draw, minimize=True, k: int = 1, conditioned=True, return_values=False):
         """q sample paths of the committed model over the current candidates (bogp_sweep_thompson), each with its k best rows.
         `draw`: the arrays of `bogp.thompson.draw` -- omega (L, d), phase (L,), weights (L, q), eps (N, q) or None.  Returns a dict:
         best_val (q, k) in the criterion's sign (-path when minimising), best_idx (q, k), best_x (q, k, d) -- rank 0 is the argmax,
         slots beyond M are (-inf, -1) -- coef = (gt (N, q), bt (q,)) and, with return_values, paths (q, M).  What the library
         refuses as unsupported (a mode, kernel, trend, ...) raises NotImplementedError with its message."""
-        omega, phase, weights = _f64(draw.omega), _f64(draw.phase), _f64(draw.weights)
-        eps = None if draw.eps is None else _f64(draw.eps)
-        if weights.ndim != 2 or omega.ndim != 2 or omega.shape != (len(phase), self.d) or weights.shape[0] != len(phase):
-            raise ValueError("a draw holds omega (L, %d), phase (L,) and weights (L, q)" % self.d)
-        L, q = weights.shape
-        if eps is not None and eps.shape != (self.N, q):
-            raise ValueError("eps must have shape (%d, %d)" % (self.N, q))
-        k = int(k)
+        L, omega, phase, weights, eps = self._thompson_draw(draw)
+        q, k = weights.shape[1], int(k)
         best = np.empty((q, k))
         idx = np.empty((q, k), dtype=np.int64)
         bx = np.empty((q, k, self.d))
         paths = np.empty((q, self.M)) if return_values else None
         coef = np.empty((self.N + 1, q))
-        self._last_q, self._last_topk = -1, (-1, -1)
-        try:
-            self._check(self._lib.bogp_sweep_thompson(self._h, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps), int(bool(conditioned)),
-                                                      int(bool(minimize)), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths),
-                                                      _ptr(coef)))  # fmt: skip
-        except BogpError as e:
-            if e.code == ERR_UNSUPPORTED:
-                raise NotImplementedError(str(e)) from None
-            raise
+        self._thompson_call(self._lib.bogp_sweep_thompson, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps), int(bool(conditioned)),
+                            int(bool(minimize)), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths), _ptr(coef))  # fmt: skip
         out = dict(best_val=best, best_idx=idx, best_x=bx, coef=(coef[:-1].copy(), coef[-1].copy()))
         if return_values:
             out["paths"] = paths
@@ -868,10 +878,7 @@ class Engine:
     def thompson_last(self) -> dict:
         """Producer time, time of the draw at the training rows with its solves, k_thompson time over the candidates (ms) and the
         chunks of the last sweep_thompson (bogp_thompson_last)."""
-        c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        self._check(self._lib.bogp_thompson_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp), C.cast(C.byref(p), _dp),
-                                                 C.cast(C.byref(n), _ip)))  # fmt: skip
-        return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
+        return self._thompson_last(self._lib.bogp_thompson_last)
 
     def sweep_thompson_constrained(self, draw, q: int, lo, hi, minimize=True, k: int = 1, return_values=False):
         """Joint sample paths of the objective and the modelled constraints of the committed multi-target model over the current
@@ -881,32 +888,20 @@ class Engine:
         minimising, where the drawn constraints hold, else -inf), then of B (minus the largest scaled excess) -- best_x
         (q, 2, k, d), coef (N, q m) and, with return_values, paths (q, m, M) in the paths' own sign.  What the library refuses as
         unsupported raises NotImplementedError with its message."""
-        omega, phase, weights = _f64(draw.omega), _f64(draw.phase), _f64(draw.weights)
-        eps = None if draw.eps is None else _f64(draw.eps)
         lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
         q, k, m = int(q), int(k), len(lo) + 1
         if len(hi) != len(lo):
             raise ValueError("lo and hi hold one bound per constraint")
-        if weights.ndim != 2 or omega.ndim != 2 or omega.shape != (len(phase), self.d) or weights.shape != (len(phase), q * m):
-            raise ValueError("a draw holds omega (L, %d), phase (L,) and weights (L, %d)" % (self.d, q * m))
-        if eps is not None and eps.shape != (self.N, q * m):
-            raise ValueError("eps must have shape (%d, %d)" % (self.N, q * m))
-        L = len(phase)
+        L, omega, phase, weights, eps = self._thompson_draw(draw, q * m)
         qa, ka = max(q, 1), max(k, 1)
         best = np.empty((qa, 2, ka))
         idx = np.empty((qa, 2, ka), dtype=np.int64)
         bx = np.empty((qa, 2, ka, self.d))
         paths = np.empty((qa, m, self.M)) if return_values else None
         coef = np.empty((self.N, qa * m))
-        self._last_q, self._last_topk = -1, (-1, -1)
-        try:
-            self._check(self._lib.bogp_sweep_thompson_constrained(self._h, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps),
-                                                                  int(bool(minimize)), len(lo), _ptr(lo), _ptr(hi), k, _ptr(best),
-                                                                  idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths), _ptr(coef)))  # fmt: skip
-        except BogpError as e:
-            if e.code == ERR_UNSUPPORTED:
-                raise NotImplementedError(str(e)) from None
-            raise
+        self._thompson_call(self._lib.bogp_sweep_thompson_constrained, q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps),
+                            int(bool(minimize)), len(lo), _ptr(lo), _ptr(hi), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths),
+                            _ptr(coef))  # fmt: skip
         out = dict(best_val=best, best_idx=idx, best_x=bx, coef=coef)
         if return_values:
             out["paths"] = paths
@@ -915,10 +910,7 @@ class Engine:
     def thompson_constrained_last(self) -> dict:
         """Producer time, time of the draw at the training rows with its solves, k_thompson_constrained time over the candidates
         (ms) and the chunks of the last sweep_thompson_constrained (bogp_thompson_constrained_last)."""
-        c, s, p, n = C.c_double(), C.c_double(), C.c_double(), C.c_int()
-        self._check(self._lib.bogp_thompson_constrained_last(self._h, C.cast(C.byref(c), _dp), C.cast(C.byref(s), _dp),
-                                                             C.cast(C.byref(p), _dp), C.cast(C.byref(n), _ip)))  # fmt: skip
-        return dict(corr_ms=c.value, solve_ms=s.value, paths_ms=p.value, n_chunks=n.value)
+        return self._thompson_last(self._lib.bogp_thompson_constrained_last)
 
     def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):
         """Kriging-believer batch under EHVI over the current candidates (bogp_sweep_believer_ehvi): step j maximises EHVI on the m

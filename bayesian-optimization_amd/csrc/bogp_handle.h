@@ -180,6 +180,8 @@ struct SpanTimer {
 };
 template <class Launch>  // a launch between two marks of its own on tm: one span of `kind` (defined behind HIPCHK, below)
 int timed_span(bogp_handle* h, SpanTimer& tm, hipStream_t st, int kind, Launch launch);
+// what a Thompson entry leaves for its *_last reader (ms): producer, draw at X + solves, the family's kernel; candidate chunks
+struct ThompsonLast { double corr_ms = 0, solve_ms = 0, paths_ms = 0; int chunks = 0; };
 }  // namespace bogp
 
 struct bogp_handle {
@@ -315,12 +317,9 @@ struct bogp_handle {
   double bel_criterion_ms = 0;  // the criterion kernel of the last multi-target believer call (k_believer_ehvi / _constrained / _ehvi_constrained)
 
   // Thompson-sampling batches (bogp_api_thompson.hip)
-  bogp::DevBuf<double> dth_small;  // omega | phase | W | -g | s, V s, R^-1 s of the call in flight
-  bogp::SpanTimer th_timer;        // draw at X + solves, chunk producers, k_thompson
-  double th_corr_ms = 0, th_solve_ms = 0, th_paths_ms = 0;  // of the last bogp_sweep_thompson: producer, draw at X + solves, k_thompson
-  int th_chunks = 0;
-  double thc_corr_ms = 0, thc_solve_ms = 0, thc_paths_ms = 0;  // of the last bogp_sweep_thompson_constrained, on th_timer's spans
-  int thc_chunks = 0;
+  bogp::DevBuf<double> dth_small;  // omega | phase | W | coefficient block (-g, or gamma - g) | s, V s, R^-1 s of the call in flight
+  bogp::SpanTimer th_timer;        // draw at X + solves, chunk producers, k_thompson / k_thompson_constrained
+  bogp::ThompsonLast th_last, thc_last;  // of the last bogp_sweep_thompson / bogp_sweep_thompson_constrained, both on th_timer's spans
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

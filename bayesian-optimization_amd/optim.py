@@ -586,6 +586,53 @@ def believer_batch(criteria, search_space, eval_budget: int, q: Optional[int] = 
     return _believer_result(out)
 
 
+def _thompson_preamble(model, lift, masks, h, g, state_of, q, k, under=""):
+    """What both Thompson batches refuse alike behind their refusals of the criterion's kind, in the order both keep: a lift, fixed
+    variables, constraints h / g, what `state_of` refuses of the model, q < 1.  `under`: the family's wording behind "have no
+    Thompson batches".  Returns (the model's state, q, k)."""
+    if lift is not None:
+        raise NotImplementedError("a lift (PCA-BO) has no Thompson batches" + under)
+    if masks is not None and np.any(masks):
+        raise NotImplementedError("fixed variables have no Thompson batches" + under)
+    if h is not None or g is not None:
+        if under:
+            raise NotImplementedError("cheap constraints h / g have no Thompson batches%s: model them as columns of y" % under)
+        raise NotImplementedError("constraints have no Thompson batches")
+    st = state_of(model)
+    q, k = int(q), int(k)
+    if q < 1:
+        raise ValueError("q = %d: Thompson sampling proposes at least one point" % q)
+    return st, q, k
+
+
+def _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world):
+    """Behind every check of the arguments: one rank only, the candidates onto the engine.  Returns (engine, history rows or None)."""
+    eng = model.engine
+    if rank is None or world is None:
+        rank, world = engine_rank_world(eng, group)
+    if world > 1:
+        raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
+    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
+    return eng, None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
+
+
+def _thompson_picks(sizes, seed, k, hist, call):
+    """The calls of a Thompson batch (`sizes` members each, seeds derived from `seed`) and every member's pick: its first candidate
+    that no earlier member took and that is not `np.isclose` to a row of `hist`.  `call(qb, sd, kk)` runs one call and returns (what
+    is yielded back, per member ([(row, x, tag)] in order, the candidate kept with an empty list)).  Yields (that, member, candidate)."""
+    from . import thompson as _th
+
+    taken = set()
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, k + len(taken))))  # a later call also steps over the rows the earlier ones took
+        back, members = call(qb, sd, kk)
+        for c, (cands, kept) in enumerate(members):
+            free = (e for e in cands if e[0] not in taken and not (hist is not None and np.any(np.all(np.isclose(hist, e[1]), axis=1))))
+            pick = next(free, cands[0] if cands else kept)  # every fall-back exhausted: the first listed row (the caller's check will pad)
+            taken.add(pick[0])
+            yield back, c, pick
+
+
 def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
                    Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None, k: int = 8,
                    minimize: bool = True, lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None,
@@ -610,44 +657,20 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
         raise NotImplementedError("EHVI / several targets have no Thompson batches")
     if criteria is not None and any(is_constrained(c) for c in criteria):
         raise NotImplementedError("modelled constraints (bogp.Constrained) have no Thompson batches: strategy='topk' serves them")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no Thompson batches")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no Thompson batches")
-    if h is not None or g is not None:
-        raise NotImplementedError("constraints have no Thompson batches")
-    _th.state_of(model)  # the model's own refusals: not fitted, mode, trend, targets, kernel
-    q, k = int(q), int(k)
-    if q < 1:
-        raise ValueError("q = %d: Thompson sampling proposes at least one point" % q)
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
-    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
-    hist = None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
-    sizes = [min(_th.MAX_PATHS, q - a) for a in range(0, q, _th.MAX_PATHS)]
-    chosen_x, chosen_f, taken = [], [], set()
-    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
-        kk = int(max(1, min(_lib.MAX_TOPK, k + len(taken))))  # a later call also steps over the rows the earlier ones took
+    _, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of, q, k)  # (state_of: not fitted, mode, trend, targets, kernel)
+    eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
+
+    def call(qb, sd, kk):  # a path lists its ranks in order; every fall-back exhausted, it keeps the argmax
         out = eng.sweep_thompson(_th.draw(model, qb, n_features, sd), minimize=minimize, k=kk)
-        for c in range(qb):
-            pick = None
-            for r in range(kk):
-                gi = int(out["best_idx"][c, r])
-                if gi < 0 or gi in taken:
-                    continue
-                if hist is not None and np.any(np.all(np.isclose(hist, out["best_x"][c, r]), axis=1)):
-                    continue
-                pick = r
-                break
-            if pick is None:  # every fall-back exhausted: keep the argmax (the caller's duplicate check will pad)
-                pick = 0
-            taken.add(int(out["best_idx"][c, pick]))
-            chosen_x.append(np.asarray(out["best_x"][c, pick], dtype=float).tolist())
-            v = float(out["best_val"][c, pick])
-            chosen_f.append(-v if minimize else v)
+        idx, bx = out["best_idx"], out["best_x"]
+        return out, [([(int(idx[c, r]), bx[c, r], r) for r in range(kk) if idx[c, r] >= 0], (int(idx[c, 0]), bx[c, 0], 0)) for c in range(qb)]
+
+    chosen_x, chosen_f = [], []
+    sizes = [min(_th.MAX_PATHS, q - a) for a in range(0, q, _th.MAX_PATHS)]
+    for out, c, (_, x, r) in _thompson_picks(sizes, seed, k, hist, call):
+        chosen_x.append(np.asarray(x, dtype=float).tolist())
+        v = float(out["best_val"][c, r])
+        chosen_f.append(-v if minimize else v)
     return tuple(chosen_x), tuple(chosen_f)
 
 
@@ -678,54 +701,29 @@ def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int
     model = criterion.model
     if _forest.is_forest_model(model):
         raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
-    if lift is not None:
-        raise NotImplementedError("a lift (PCA-BO) has no Thompson batches under modelled constraints")
-    if masks is not None and np.any(masks):
-        raise NotImplementedError("fixed variables have no Thompson batches under modelled constraints")
-    if h is not None or g is not None:
-        raise NotImplementedError("cheap constraints h / g have no Thompson batches under modelled constraints: model them as columns of y")
-    st = _th.state_of_multi(model)  # the model's own refusals: not fitted, mode, trend, kernel
-    q, k = int(q), int(k)
-    if q < 1:
-        raise ValueError("q = %d: Thompson sampling proposes at least one point" % q)
+    st, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of_multi, q, k, " under modelled constraints")  # (the model's among them)
     if k < 1:
         raise ValueError("k = %d: every member lists at least one row" % k)
-    eng = model.engine
-    if rank is None or world is None:
-        rank, world = engine_rank_world(eng, group)
-    if world > 1:
-        raise NotImplementedError("Thompson batches run on one rank (the paths of a call share one candidate set)")
-    _stage_candidates(model, search_space, eval_budget, Xs, design, seed)
-    hist = None if history is None or len(history) == 0 else np.asarray(history, dtype=float)
-    m = st.y.shape[1]
-    per_call = _th.MAX_PATHS // m
-    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
     minimize = bool(criterion.minimize)
-    chosen_x, chosen_f, taken = [], [], set()
-    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
-        kk = int(max(1, min(_lib.MAX_TOPK, k + len(taken))))  # a later call also steps over the rows the earlier ones took
+
+    def call(qb, sd, kk):  # a member lists `merge_ranks`; with an empty list it keeps the first B rank
         dr = _th.draw_multi(model, qb, n_features, sd)
         out = eng.sweep_thompson_constrained(dr, qb, criterion.lo, criterion.hi, minimize=minimize, k=kk)
-        for c in range(qb):
-            ranks = _th.merge_ranks(out["best_val"][c], out["best_idx"][c], kk)
-            pick = None
-            for gi, which, r in ranks:
-                if gi in taken:
-                    continue
-                if hist is not None and np.any(np.all(np.isclose(hist, out["best_x"][c, which, r]), axis=1)):
-                    continue
-                pick = (gi, which, r)
-                break
-            if pick is None:  # every fall-back exhausted: keep the first listed row (the caller's duplicate check will pad)
-                pick = ranks[0] if ranks else (int(out["best_idx"][c, 1, 0]), 1, 0)
-            gi, which, r = pick
-            taken.add(gi)
-            chosen_x.append(np.asarray(out["best_x"][c, which, r], dtype=float).tolist())
-            if which == 0:  # an A rank is the objective path's value in the criterion's sign
-                v = float(out["best_val"][c, 0, r])
-                chosen_f.append(-v if minimize else v)
-            else:  # a least violating row: its objective value is in no ranking -- one row of the restatement on the device's g
-                chosen_f.append(_th.objective_path_at(st, dr, out["coef"], c, out["best_x"][c, which, r]))
+        idx, bx = out["best_idx"], out["best_x"]
+        return (out, dr), [([(gi, bx[c, which, r], (which, r)) for gi, which, r in _th.merge_ranks(out["best_val"][c], idx[c], kk)],
+                            (int(idx[c, 1, 0]), bx[c, 1, 0], (1, 0))) for c in range(qb)]  # fmt: skip
+
+    chosen_x, chosen_f = [], []
+    per_call = _th.MAX_PATHS // st.y.shape[1]
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    for (out, dr), c, (_, x, (which, r)) in _thompson_picks(sizes, seed, k, hist, call):
+        chosen_x.append(np.asarray(x, dtype=float).tolist())
+        if which == 0:  # an A rank is the objective path's value in the criterion's sign
+            v = float(out["best_val"][c, 0, r])
+            chosen_f.append(-v if minimize else v)
+        else:  # a least violating row: its objective value is in no ranking -- one row of the restatement on the device's g
+            chosen_f.append(_th.objective_path_at(st, dr, out["coef"], c, x))
     return tuple(chosen_x), tuple(chosen_f)
 
 

@@ -64,11 +64,8 @@ def dense_state(X, y, theta, kernel, estimate_trend=True, beta=0.0, nugget=0.0, 
     return st
 
 
-def state_of(model):
-    """What the formulas read, from a fitted `GaussianProcess` (or a `dense_state`, returned as it is).  The refusals live here."""
-    if isinstance(model, SimpleNamespace):
-        refuse_kernel(model.kernel)
-        return model
+def _gp_refusals(model):
+    """What `state_of` and `state_of_multi` refuse of a model alike, in this order: a forest, no fit, the mode, the trend basis."""
     if type(model).__name__ == "RandomForest" or hasattr(model, "estimators_"):
         raise NotImplementedError("a forest model has no posterior paths to draw (Thompson sampling conditions a Gaussian process)")
     if getattr(model, "_committed_par", None) is None:
@@ -79,6 +76,14 @@ def state_of(model):
                                   "(gpr.py:949-979), which is no Gaussian process's conditional law; use nugget=0, noise_estim=False" % mode)  # fmt: skip
     if type(model.mean).__name__ != "constant_trend":
         raise NotImplementedError("posterior paths serve the constant trend basis, not the polynomial trends (%s)" % type(model.mean).__name__)
+
+
+def state_of(model):
+    """What the formulas read, from a fitted `GaussianProcess` (or a `dense_state`, returned as it is).  The refusals live here."""
+    if isinstance(model, SimpleNamespace):
+        refuse_kernel(model.kernel)
+        return model
+    _gp_refusals(model)
     if np.ndim(model.y) > 1 and model.y.shape[1] > 1:
         raise NotImplementedError("posterior paths serve one target (EHVI / several targets: the model has %d)" % model.y.shape[1])
     refuse_kernel(model.kernel_id)
@@ -252,16 +257,7 @@ def state_of_multi(model):
         if not getattr(model, "multi", False):
             raise ValueError("joint paths need a multi-target state (thompson.dense_state_multi)")
         return model
-    if type(model).__name__ == "RandomForest" or hasattr(model, "estimators_"):
-        raise NotImplementedError("a forest model has no posterior paths to draw (Thompson sampling conditions a Gaussian process)")
-    if getattr(model, "_committed_par", None) is None:
-        raise Exception("The model is not fitted yet!")
-    mode = "noisy" if getattr(model, "_committed_restricted", False) else model.estimation_mode
-    if mode != "noiseless":
-        raise NotImplementedError("posterior paths in the %s mode: the reference pairs an unscaled r(x) with a rescaled R there "
-                                  "(gpr.py:949-979), which is no Gaussian process's conditional law; use nugget=0, noise_estim=False" % mode)  # fmt: skip
-    if type(model.mean).__name__ != "constant_trend":
-        raise NotImplementedError("posterior paths serve the constant trend basis, not the polynomial trends (%s)" % type(model.mean).__name__)
+    _gp_refusals(model)
     if np.ndim(model.y) < 2 or model.y.shape[1] < 2:
         raise ValueError("joint paths need a model fitted on y (N, m) with m >= 2 columns (objective, constraints): one target goes to "
                          "thompson.state_of")  # fmt: skip

@@ -13,12 +13,13 @@ sum_m |R^-1_nm| (S_j + |bt_j|), bt against sum_m |w_m| S_j / |sum w|, S_j the fi
 padding moves a value by A / L or more, 1e3 above the tolerance.  The largest excess ratio measured over the 40 shapes is in
 profiles/thompson_parity.txt (README ledger T16)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from bogp import _lib, thompson
+from support.chunk_mb import with_chunk_mb as _with_chunk_mb
+from support.thompson_engine import ranking
 
 pytestmark = pytest.mark.gpu
 
@@ -91,15 +92,6 @@ def restate(st, dr, Xs, conditioned=True):
     return dict(paths=paths, gt=gt, bt=bt, tol=tol, tol_g=ptol * (np.abs(gt) + A_g), tol_b=ptol * (np.abs(bt) + A_b), ptol=ptol)
 
 
-def ranking(crit, k):
-    q, M = crit.shape
-    val, idx = np.full((q, k), -np.inf), np.full((q, k), -1, dtype=np.int64)
-    for j in range(q):
-        order = np.argsort(-np.where(np.isnan(crit[j]), np.inf, crit[j]), kind="stable")[:k]
-        val[j, : len(order)], idx[j, : len(order)] = crit[j][order], order
-    return val, idx
-
-
 _excess = {}
 
 
@@ -160,18 +152,6 @@ def test_winners_equal_the_restatements_ranking(eng, N, kernel, est, minimize, s
                 for r in range(2, min(k, Mc)):
                     assert abs(out["best_val"][j, r] - val[j, r]) <= ref["tol"][j, idx[j, r]], (j, r)
             assert np.all(np.isnan(out["best_val"][:, : min(k, 2)]))
-
-
-def _with_chunk_mb(mb, fn):
-    old = os.environ.get("BOGP_CHUNK_MB")
-    os.environ["BOGP_CHUNK_MB"] = str(mb)
-    try:
-        return fn()
-    finally:
-        if old is None:
-            del os.environ["BOGP_CHUNK_MB"]
-        else:
-            os.environ["BOGP_CHUNK_MB"] = old
 
 
 def test_bit_identity(eng):
@@ -315,3 +295,38 @@ def test_error_returns():
         assert rc == _lib.ERR_UNSUPPORTED and "forest" in msg
     finally:
         f.close()
+
+
+def test_refusals_keep_their_precedence():
+    """Two faults in one call: the one that comes first in the entry's order of checks -- forest, not committed, no candidates, q, L,
+    k, null pointers, non-finite omega / phase / weights / eps, mode, trend columns, targets, kernel, lift, ranks -- is reported."""
+    e = _lib.Engine(0)
+    try:
+        X, y, theta, Xs = problem(100, 3, 67, _lib.KERNEL_SE)
+        e.set_train(X, y)
+        e.commit(_lib.KERNEL_SE, _lib.MODE_NOISELESS, theta, 0.0, True, 0.0)
+        e.upload_candidates(Xs)
+        assert _call(e)[0] == _lib.OK
+        for kw, first in ((dict(q=0, L=24), "q = 0 outside"), (dict(L=24, k=0), "L = 24"), (dict(k=0, omega=False), "k = 0 outside")):
+            rc, msg = _call(e, **kw)
+            assert rc == _lib.ERR_INVALID and first in msg, (kw, msg)
+        # q = 17 and a lift on the handle: q
+        e.set_lift(np.eye(3), np.zeros(3), None, -np.ones(3), np.ones(3))
+        rc, msg = _call(e, q=17)
+        assert rc == _lib.ERR_INVALID and "q = 17 outside" in msg, msg
+        e.clear_lift()
+        # a non-finite omega and a noisy-mode commit: the non-finite entry
+        e.commit(_lib.KERNEL_SE, _lib.MODE_NOISY, np.r_[theta, 0.7], 1e-6, True, 0.0)
+        rc, msg = _call(e, bad="omega")
+        assert rc == _lib.ERR_INVALID and "omega has a non-finite entry" in msg, msg
+        # the noisy mode and a linear trend: the mode
+        e.commit(_lib.KERNEL_SE, _lib.MODE_NOISY, np.r_[theta, 0.7], 1e-6, True, 0.0, trend=_lib.TREND_LINEAR)
+        rc, msg = _call(e)
+        assert rc == _lib.ERR_UNSUPPORTED and "noisy mode" in msg, msg
+        # the cubic kernel and a lift: the kernel
+        e.commit(_lib.KERNEL_CUBIC, _lib.MODE_NOISELESS, np.full(3, 2.0), 0.0, True, 0.0)
+        e.set_lift(np.eye(3), np.zeros(3), None, -np.ones(3), np.ones(3))
+        rc, msg = _call(e)
+        assert rc == _lib.ERR_UNSUPPORTED and "cubic" in msg, msg
+    finally:
+        e.close()

@@ -13,13 +13,13 @@ tests/test_thompson_constrained_host.py and again here on the state the engine c
   `bogp_sweep_thompson` before and after a constrained call;  every error return through the real ABI;
   `bogp.constrained_thompson_batch` on a real model against the device's own scores."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import thompson_constrained_cases as TC
 from bogp import _lib, thompson
+from support.chunk_mb import with_chunk_mb as _with_chunk_mb
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -125,18 +125,6 @@ def test_a_nan_candidate_row_is_never_listed(eng):
     for j in range(c.q):
         rows = [gi for gi, _, _ in thompson.merge_ranks(out["best_val"][j], out["best_idx"][j], 32)]
         assert rows and 3 not in rows and 7 not in rows
-
-
-def _with_chunk_mb(mb, fn):
-    old = os.environ.get("BOGP_CHUNK_MB")
-    os.environ["BOGP_CHUNK_MB"] = str(mb)
-    try:
-        return fn()
-    finally:
-        if old is None:
-            del os.environ["BOGP_CHUNK_MB"]
-        else:
-            os.environ["BOGP_CHUNK_MB"] = old
 
 
 def test_bit_identity(eng):
@@ -311,6 +299,38 @@ def test_error_returns():
         assert rc == _lib.ERR_UNSUPPORTED and "forest" in msg
     finally:
         f.close()
+
+
+def test_refusals_keep_their_precedence():
+    """Two faults in one call: the one that comes first in the entry's order of checks -- forest, not committed, no candidates, lift,
+    trend columns, one target, n_con, variance count, q m, L, k, null pointers, bounds, non-finite omega / phase / weights / eps, mode,
+    kernel, ranks -- is reported."""
+    e = _lib.Engine(0)
+    try:
+        X, Y, theta, Xs = TC.problem(100, 3, 67, _lib.KERNEL_SE, 2)
+        e.set_train(X, Y)
+        e.commit(_lib.KERNEL_SE, _lib.MODE_NOISELESS, theta, 0.0, False, 0.3)
+        e.upload_candidates(Xs)
+        assert _call(e)[0] == _lib.OK
+        for kw, first in ((dict(n_con=2, q=0), "n_con = 2"), (dict(q=9, L=24), "q = 9 members"), (dict(k=0, null="lo"), "k = 0 outside"),
+                          (dict(lo=[1.0], hi=[0.0], bad="omega"), "below its lower bound")):  # fmt: skip
+            rc, msg = _call(e, **kw)
+            assert rc == _lib.ERR_INVALID and first in msg, (kw, msg)
+        # a lift on the handle and q = 0: the lift
+        e.set_lift(np.eye(3), np.zeros(3), None, -np.ones(3), np.ones(3))
+        rc, msg = _call(e, q=0)
+        assert rc == _lib.ERR_UNSUPPORTED and "lift" in msg, msg
+        e.clear_lift()
+        # non-finite weights and a noisy-mode commit: the non-finite entry
+        e.commit(_lib.KERNEL_SE, _lib.MODE_NOISY, np.r_[theta, 0.7], 1e-6, False, 0.3)
+        rc, msg = _call(e, bad="weights")
+        assert rc == _lib.ERR_INVALID and "weights has a non-finite entry" in msg, msg
+        # the noisy mode and the cubic kernel: the mode
+        e.commit(_lib.KERNEL_CUBIC, _lib.MODE_NOISY, np.r_[np.full(3, 2.0), 0.7], 1e-6, False, 0.3)
+        rc, msg = _call(e)
+        assert rc == _lib.ERR_UNSUPPORTED and "noisy mode" in msg, msg
+    finally:
+        e.close()
 
 
 def test_the_python_batch_on_the_device():
