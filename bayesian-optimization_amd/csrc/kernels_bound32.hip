@@ -254,17 +254,44 @@ __global__ __launch_bounds__(256, 4) void k_bound32_sums(Bound32Args a) {  // (f
     for (int t = 0; t < 4; ++t) bf[u][t] = xs[(4 * u + lk) * XS_LD + 16 * t + li];
   float mu32[4] = {0.0f, 0.0f, 0.0f, 0.0f}, wd32[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   double mu[4] = {0.0, 0.0, 0.0, 0.0}, wd[4] = {0.0, 0.0, 0.0, 0.0};
-  const float* __restrict__ xth = a.md.XthT + (size_t)lk * Np + li;
+  // NO VECTOR ADDRESS ARITHMETIC IN THE LOOP (the form k_contract16d's loads have, DESIGN.md 5.2''): every address is a scalar base --
+  // the operand's row at column n0, stepped by scalar arithmetic -- plus one of the lane's two loop-invariant 32-bit byte offsets, the
+  // `v_offset, s[base]` form of global_load.  hipcc selects that form only where it sees the zero-extension of the offset next to the load,
+  // so the offsets pass through an empty asm inside the loop; hoisted, each load gets a 64-bit vector add on the pipe the chain needs.
+  // (offA <= 4 (3 Np + 15) bytes: launch_bound32_sums refuses an Np at which that would not fit 32 bits, for this kernel alone.)
+  unsigned offA = 4u * ((unsigned)lk * (unsigned)Np + (unsigned)li);  // fragment row 4 u + lk, column n0 + li
+  unsigned offV = 16u * (unsigned)lk;                                 // the lane's four training points n0 + 4 lk + c
+  const size_t rowstep = (size_t)16 * Np;                             // four rows of the commit-time copy, in bytes
+  typedef const __attribute__((address_space(1))) char* gbytes;  // (a global pointer: through the asm below a generic one would load flat)
+  typedef const __attribute__((address_space(1))) float* gfloat;
+  typedef const __attribute__((address_space(1))) f4t* gf4;
+  const gbytes xthb = (gbytes) reinterpret_cast<const char*>(a.md.XthT);
+  const gbytes nbb = (gbytes) reinterpret_cast<const char*>(a.md.xnorm);
+  const gbytes gb = (gbytes) reinterpret_cast<const char*>(a.md.gamma);
+  const gbytes wb = (gbytes) reinterpret_cast<const char*>(a.md.wvec);
   struct Operands {  // of one 16-point block: this lane's A fragments, and norm, gamma, w of its four training points n0 + 4 lk + c
     float av[KS];
     f4t nbv, gv, wv;
   };
   auto load = [&](int n0, Operands& o) {  // (16-byte loads: Np and n0 are multiples of 16)
+    asm volatile("" : "+v"(offA), "+v"(offV));
+    const size_t col = (size_t)4 * n0;  // (wave-uniform: n0 comes from g)
+    // (each base passes through an empty asm as a scalar, or the compiler adds the column to the lane's offset first -- a vector add again)
+    gbytes pn = nbb + col, pg = gb + col, pw = wb + col;
+    asm volatile("" : "+s"(pn), "+s"(pg));
+    o.nbv = *(gf4)(pn + offV);
+    o.gv = *(gf4)(pg + offV);
+    if (WD) {
+      asm volatile("" : "+s"(pw));
+      o.wv = *(gf4)(pw + offV);
+    }
 #pragma unroll
-    for (int u = 0; u < KS; ++u) o.av[u] = xth[(size_t)(4 * u) * Np + n0];
-    o.nbv = *reinterpret_cast<const f4t*>(a.md.xnorm + n0 + 4 * lk);
-    o.gv = *reinterpret_cast<const f4t*>(a.md.gamma + n0 + 4 * lk);
-    if (WD) o.wv = *reinterpret_cast<const f4t*>(a.md.wvec + n0 + 4 * lk);
+    for (int u = 0; u < KS; ++u) {
+      gbytes pa = xthb + u * rowstep + col;
+      asm volatile("" : "+s"(pa));
+      o.av[u] = *(gfloat)(pa + offA);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every request of the block goes out before the first of them is waited for
   };
   int step = 0;
   // (the operands are asked for at the top of their own block: asking one block ahead cost 5 registers, the fifth wave a SIMD and 0.14 ms
@@ -404,6 +431,8 @@ static void launch_bound32_sums_of(const Bound32Args& a, dim3 grid, size_t shm, 
 
 hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st) {
   if (!bound32_supported(kernel, a.d)) return hipErrorInvalidValue;
+  // k_bound32_sums (d <= 32) addresses a fragment by a 32-bit byte offset of at most 4 (3 Np + 15) from its row's base
+  if ((a.d + 3) / 4 <= BOUND32_REG_KS && 4 * (3 * (int64_t)a.Np + 15) > (int64_t)UINT32_MAX) return hipErrorInvalidValue;
   static_assert(BOUND32_REG_KS == 8, "launch_bound32_sums_of lists the register-fragment kernels case by case");
   const dim3 grid((unsigned)((a.rcount + 63) / 64));
   const size_t shm = (size_t)4 * ((a.d + 3) / 4) * XS_LD * sizeof(float);  // <= 40 KB (BOUND32_MAX_D)
