@@ -85,6 +85,8 @@ SIGNATURES = {
     "bogp_thompson_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_thompson_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_thompson_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_thompson_ehvi_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_ehvi_grid_cells": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
     "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
                                            _dp, _dp]),
@@ -911,6 +913,38 @@ class Engine:
         """Producer time, time of the draw at the training rows with its solves, k_thompson_constrained time over the candidates
         (ms) and the chunks of the last sweep_thompson_constrained (bogp_thompson_constrained_last)."""
         return self._thompson_last(self._lib.bogp_thompson_constrained_last)
+
+    def sweep_thompson_ehvi(self, draw, q: int, lower, upper, k: int = 1, return_values=False):
+        """Joint sample paths of the m objectives of the committed multi-target model over the current candidates, selected by the
+        hypervolume the drawn vector adds to the front (bogp_sweep_thompson_ehvi): `q` batch members, q m <= 16 columns, over the
+        cells (lower, upper) (C x m each, as `sweep_ehvi` takes them).  `draw`: the arrays of `bogp.thompson.draw_multi`, column
+        j m + t.  Returns a dict: best_val / best_idx (q, 2, k) -- per member the k best rows of A (the hypervolume improvement of
+        the draw where positive, else -inf), then of B (minus the scaled distance to the region the front does not dominate) --
+        best_x (q, 2, k, d), coef (N, q m) and, with return_values, paths (q, m, M).  What the library refuses as unsupported raises
+        NotImplementedError with its message."""
+        lower, upper = _f64(lower), _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m arrays of one shape")
+        C_, m = lower.shape
+        q, k = int(q), int(k)
+        L, omega, phase, weights, eps = self._thompson_draw(draw, q * m)
+        qa, ka = max(q, 1), max(k, 1)
+        best = np.empty((qa, 2, ka))
+        idx = np.empty((qa, 2, ka), dtype=np.int64)
+        bx = np.empty((qa, 2, ka, self.d))
+        paths = np.empty((qa, m, self.M)) if return_values else None
+        coef = np.empty((self.N, qa * m))
+        self._thompson_call(self._lib.bogp_sweep_thompson_ehvi, int(m), q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps), int(C_),
+                            _ptr(lower), _ptr(upper), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx), _ptr(paths), _ptr(coef))  # fmt: skip
+        out = dict(best_val=best, best_idx=idx, best_x=bx, coef=coef)
+        if return_values:
+            out["paths"] = paths
+        return out
+
+    def thompson_ehvi_last(self) -> dict:
+        """Producer time, time of the draw at the training rows with its solves, k_thompson_ehvi time over the candidates (ms) and
+        the chunks of the last sweep_thompson_ehvi (bogp_thompson_ehvi_last)."""
+        return self._thompson_last(self._lib.bogp_thompson_ehvi_last)
 
     def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):
         """Kriging-believer batch under EHVI over the current candidates (bogp_sweep_believer_ehvi): step j maximises EHVI on the m

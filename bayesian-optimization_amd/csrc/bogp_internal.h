@@ -454,6 +454,34 @@ struct ThompsonConstrainedArgs {
 };
 hipError_t launch_thompson_constrained(const ThompsonConstrainedArgs& a, hipStream_t st);
 
+// q batch members' joint sample paths of the m objectives of a multi-target model over a chunk, selected by the hypervolume improvement
+// of the drawn vector over the cells of the front (kernels_thompson_ehvi.hip): with y_k = path_{j,k}(x),
+// A = sum_c prod_k max(0, min(y_k, u_ck) - l_ck) where positive (else -inf), B = 0 - min_c max_k(max(l_ck - y_k, y_k - u_ck, 0) inv_sd[k]);
+// one np.argmax record per score and 64 rows.  DEVICE column of (member j, target t): j m + t, the ABI's own.
+struct ThompsonEhviArgs {
+  const double* X;        // [M][d] the candidates
+  int64_t row0, mcount;   // first row of this launch; rows it serves
+  int d, L, N, q, m;      // L: features, a multiple of 16; 2 <= m <= 8, q m <= 16
+  const double* omega;    // [L][d]
+  const double* phase;    // [L]
+  const double* W;        // [L][16] weights times sqrt(2 sigma2_t / L), zero columns from q m on
+  const double* rT;       // [Np][ld] the chunk's correlation columns
+  int64_t ld;             // Mc: stride of rT
+  const double* coef;     // [ceil(N / 4) * 4][16] gamma_t - g_{j,t}, zero padded rows and columns
+  double beta;
+  double inv_sd[8];       // per target: 1 / sqrt(sigma2_t)
+  const double* lower;    // [C][m] cell bounds (device), finite
+  const double* upper;    // [C][m] (+inf allowed)
+  int C;                  // >= 1
+  double* scores;         // [2 q][M] at the global row: row 2 j is A_j, row 2 j + 1 is B_j; or null
+  double* paths;          // [q m][M] at the global row, row j m + t; or null
+  int64_t M;
+  double* blk_val;        // [2 q][nblk_total]
+  int64_t* blk_idx;
+  int64_t blk_offset, nblk_total;
+};
+hipError_t launch_thompson_ehvi(const ThompsonEhviArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

@@ -225,10 +225,18 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
         raise NotImplementedError("MOBO(n_point=q) under expensive constraints: constrained EHVI (bogp.ConstrainedEHVI) has no batch "
                                   "strategy; ask for one point at a time")  # fmt: skip
     inherited = super(_ORIGINAL["mobo_cls"], self)._batch_arg_max_acquisition
-    if (_BATCH.get("strategy") != "believer" or fixed or optimizer not in _SWEEPS or not is_device_model(getattr(self, "model", None))
-            or not optim.is_continuous(kw.get("search_space")) or kw.get("h") is not None or kw.get("g") is not None):  # fmt: skip
+    # (batch_strategy="thompson" names the single-objective batches: for a MOBO it stays what it was, the inherited refusal)
+    strategy = "thompson" if _EHVI.get("thompson") else "believer" if _BATCH.get("strategy") == "believer" else None
+    if (strategy is None or fixed or optimizer not in _SWEEPS
+            or not is_device_model(getattr(self, "model", None)) or not optim.is_continuous(kw.get("search_space"))
+            or kw.get("h") is not None or kw.get("g") is not None):  # fmt: skip
         return inherited(n_point, return_dx, fixed)
     criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
+    if strategy == "thompson":
+        # install(ehvi_thompson=True): one joint draw of the objectives per point; the criterion supplies model, reference point and cells
+        xs, fs = optim.ehvi_thompson_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
+                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self))  # fmt: skip
+        return tuple(xs), tuple(fs)
     xs, fs = optim.ehvi_believer_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
                                        design=optim.DEVICE_DESIGNS.get(optimizer))  # fmt: skip
     return tuple(xs), tuple(fs)
@@ -651,7 +659,8 @@ def _dispatching_surrogate(host_cls):
 def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None, sweep_budget: int = 1_000_000, surrogate: bool = True,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
-            constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False):
+            constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
+            ehvi_thompson: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -724,7 +733,17 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     not offered).  "believer": `optim.constrained_ehvi_believer_batch` -- step j sees the m + c variances conditioned on the
     winners before it, and a believed point that is feasible by belief joins the feasible front -- for a device GP, an inner
     optimiser of the sweep family, a continuous space, nothing fixed and no cheap h / g; every other configuration raises as
-    before."""
+    before.
+
+    `ehvi_thompson=True` (together with `batch_strategy="believer"` it raises ValueError): the reference's `MOBO(n_point=q)` proposes
+    its q points by `optim.ehvi_thompson_batch` -- per point one joint draw of the objectives, and the candidate whose drawn vector
+    adds the most hypervolume to the front (the one nearest to the non-dominated region where the draw improves nowhere) -- with the
+    run's history, for a device GP, an inner optimiser of the sweep family, a continuous space, nothing fixed and no cheap h / g;
+    every other configuration takes the route it took before.  No variance contraction runs: a batch costs about one EHVI sweep
+    where the believer costs q.  A model that Thompson sampling refuses (a nugget or noise estimate, ...) raises
+    NotImplementedError naming it."""
+    if ehvi_thompson and batch_strategy == "believer":
+        raise ValueError("ehvi_thompson=True and batch_strategy='believer' name two batch strategies for one step: choose one")
     if constrained_mobo_batches not in ("topk", "believer"):
         raise ValueError("constrained_mobo_batches must be 'topk' or 'believer', not %r" % (constrained_mobo_batches,))
     if constrained_mobo_batches == "believer" and not constrained_mobo:
@@ -765,6 +784,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     _EHVI.clear()
     if ehvi_gradient:
         _EHVI["gradient"] = True
+    if ehvi_thompson:
+        _EHVI["thompson"] = True
     _BATCH.clear()
     if batch_strategy != "topk":
         _BATCH["strategy"] = batch_strategy

@@ -727,6 +727,55 @@ def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
+                        Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None, k: int = 8,
+                        lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None, group=None,
+                        rank=None, world=None):
+    """A q-point proposal for a multi-objective run by Thompson sampling (`bogp_sweep_thompson_ehvi`): per proposed point ONE joint
+    draw of the m objectives of `criterion.model` (`thompson.draw_multi`), and among the candidates the row whose DRAWN vector adds
+    the most hypervolume to the front -- the row nearest to the region the front does not dominate (scaled Chebyshev distance)
+    where the draw improves nowhere.  `criterion`: one `bogp.EHVI`; it supplies the model and the cells of its front above its
+    reference point.  ONE producer pass and one streaming pass serve `16 // m` members; more run in further calls with seeds derived
+    from `seed` (`thompson.batch_seeds`).  No variance contraction runs.  Candidates as in `believer_batch`.  Members are
+    independent; every member lists its `k` best rows (`thompson.merge_ranks`: improving rows first) and takes the first that no
+    earlier member took and that is not `np.isclose` to a row of `history` (`thompson_batch`'s rule), so the q proposals are q
+    distinct rows.  Returns (xopt: tuple of q lists, fopt: tuple of q floats) in `batch_argmax`'s format; fopt is the hypervolume
+    the member's draw adds at its proposal (A), or minus its distance (B) where no listed row improved.
+    TypeError: a criterion that is not `bogp.EHVI`.  Refused (NotImplementedError): `ConstrainedEHVI`, a forest model, a lift,
+    fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    from . import thompson as _th
+
+    if is_constrained_ehvi(criterion):
+        raise NotImplementedError("%s has no Thompson batches: ehvi_thompson_batch draws the objectives only and would drop the "
+                                  "constraints" % _CEHVI)  # fmt: skip
+    if not is_ehvi(criterion):
+        raise TypeError("ehvi_thompson_batch takes a bogp.EHVI criterion (a model alone goes to thompson_batch)")
+    model = criterion.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
+    st, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of_multi, q, k, " for EHVI")
+    if k < 1:
+        raise ValueError("k = %d: every member lists at least one row" % k)
+    if st.y.shape[1] != criterion.n_obj:
+        raise ValueError("the model has %d targets, the criterion %d objectives" % (st.y.shape[1], criterion.n_obj))
+    eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
+    lower, upper = criterion.cell_lower_bounds, criterion.cell_upper_bounds
+
+    def call(qb, sd, kk):  # a member lists `merge_ranks`; with an empty list it keeps the first B rank
+        out = eng.sweep_thompson_ehvi(_th.draw_multi(model, qb, n_features, sd), qb, lower, upper, k=kk)
+        idx, bx = out["best_idx"], out["best_x"]
+        return out, [([(gi, bx[c, which, r], (which, r)) for gi, which, r in _th.merge_ranks(out["best_val"][c], idx[c], kk)],
+                      (int(idx[c, 1, 0]), bx[c, 1, 0], (1, 0))) for c in range(qb)]  # fmt: skip
+
+    chosen_x, chosen_f = [], []
+    per_call = _th.MAX_PATHS // st.y.shape[1]
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    for out, c, (_, x, (which, r)) in _thompson_picks(sizes, seed, k, hist, call):
+        chosen_x.append(np.asarray(x, dtype=float).tolist())
+        chosen_f.append(float(out["best_val"][c, which, r]))
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
                         seed: Optional[int] = None, pending=None, believe_front: bool = True, lift=None, masks=None, values=None,
                         h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):

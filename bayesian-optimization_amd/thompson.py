@@ -27,7 +27,8 @@ its conditional law.
 
 The second half of the module is the multi-target form for Thompson batches under modelled constraints
 (`bogp_sweep_thompson_constrained`): `state_of_multi`, `draw_multi`, `paths_multi_numpy`, the selection rule `select_numpy` and
-`merge_ranks`.  `state_of`, `draw`, `paths_numpy` and `sampling_posterior` serve one target and refuse several, as before."""
+`merge_ranks`; `hvi_select_numpy` is the selection rule of `bogp_sweep_thompson_ehvi`, which draws the same joint paths for the
+objectives of a multi-objective run.  `state_of`, `draw`, `paths_numpy` and `sampling_posterior` serve one target and refuse several, as before."""
 from __future__ import annotations
 
 import math
@@ -371,6 +372,46 @@ def select_numpy(paths, lo, hi, sigma2, minimize=True, k=1):
     va, ia = rank_numpy(A, k)
     vb, ib = rank_numpy(B, k)
     return dict(A=A, B=B, feas=feas & ~bad, best_val=np.stack([va, vb], axis=1), best_idx=np.stack([ia, ib], axis=1))
+
+
+def hvi_select_numpy(paths, lower, upper, sigma2, k=1):
+    """The selection of `bogp_sweep_thompson_ehvi` on path values (q, m, M) over the cells (lower, upper) (C x m; targets
+    maximised), in the device's own operations and order -- so that it reproduces the device's scores from the device's paths
+    exactly.  With y_k = paths[j, k, row]:
+
+        per cell c in order:  t_k = max(min(y_k, u_ck) - l_ck, 0);  p = t_0, p = p t_1, ...;  acc = acc + p              (acc from 0.0)
+                              cm = max_k (max(l_ck - y_k, y_k - u_ck, 0) / sqrt(sigma2_k)) (from 0.0);  dist = min(dist, cm) (from +inf)
+        A = acc > 0 ? acc : -inf,   B = 0.0 - dist,   a NaN among the m values: A = B = -inf
+
+    A is the hypervolume the drawn vector would add to the front whose non-dominated region the cells partition; B ranks the rows
+    whose draw adds none by their scaled Chebyshev distance to that region.  Returns a dict: A, B (q, M), best_val / best_idx
+    (q, 2, k): per member the ranking of A, then of B (`select_numpy`'s shapes, for `merge_ranks`)."""
+    paths = np.asarray(paths, dtype=float)
+    q, m, M = paths.shape
+    lower, upper = np.atleast_2d(np.asarray(lower, dtype=float)), np.atleast_2d(np.asarray(upper, dtype=float))
+    inv_sd = 1.0 / np.sqrt(np.asarray(sigma2, dtype=float).ravel())
+    if lower.shape != upper.shape or lower.shape[1] != m or len(inv_sd) != m:
+        raise ValueError("lower, upper hold C x %d cell bounds, sigma2 one value per target" % m)
+    acc, dist = np.zeros((q, M)), np.full((q, M), np.inf)
+    with np.errstate(invalid="ignore"):
+        for c in range(len(lower)):
+            p, cm = None, np.zeros((q, M))
+            for t in range(m):
+                y, lb, ub = paths[:, t], lower[c, t], upper[c, t]
+                s = np.fmax(np.fmin(y, ub) - lb, 0.0)
+                p = s if t == 0 else p * s
+                e = np.fmax(np.fmax(lb - y, y - ub), 0.0)
+                cm = np.fmax(cm, e * inv_sd[t])
+            acc = acc + p
+            dist = np.fmin(dist, cm)
+        A = np.where(acc > 0.0, acc, -np.inf)
+    B = 0.0 - dist
+    bad = np.isnan(paths).any(axis=1)
+    A[bad], B[bad] = -np.inf, -np.inf
+    k = int(k)
+    va, ia = rank_numpy(A, k)
+    vb, ib = rank_numpy(B, k)
+    return dict(A=A, B=B, best_val=np.stack([va, vb], axis=1), best_idx=np.stack([ia, ib], axis=1))
 
 
 def merge_ranks(best_val, best_idx, k=None):

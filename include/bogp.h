@@ -458,6 +458,41 @@ int bogp_sweep_thompson_constrained(bogp_handle* h, int q, int L, const double* 
                                     double* best_val, int64_t* best_idx, double* best_x, double* paths_out, double* coef_out);
 int bogp_thompson_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
 
+/* ---- sweep: Thompson-sampling batches for multi-objective runs ----------------------------------------------
+ * Joint sample paths of the m objectives, selected by the hypervolume the drawn vector would add to the front.  The model is
+ * bogp_sweep_ehvi's: a committed multi-target model with 2 <= m <= BOGP_MAX_TARGETS targets, maximised as given; noiseless mode,
+ * constant basis (a FIXED constant trend: simple kriging, no b).  A call carries q batch members, q m <= BOGP_MAX_PATHS columns;
+ * column (j, t) -- index j m + t in weights, eps, paths_out and coef_out -- is member j's path of target t, formed exactly as
+ * bogp_sweep_thompson_constrained forms it (shared features, independent weights).  The cells (l_c, u_c), c = 0 .. C - 1, are what
+ * bogp_sweep_ehvi takes: they partition the region above the reference point that the front does not dominate.  Selection per row
+ * x and member j, with y_k = path_{j,k}(x):
+ *   HVI    = sum_c prod_k max(0, min(y_k, u_ck) - l_ck)       the exact hypervolume the drawn vector adds
+ *   dist   = min_c max_k (max(l_ck - y_k, y_k - u_ck, 0) inv_sd_k),   inv_sd_k = 1 / sqrt(sigma2_k) (formed on the host)
+ *   A_j(x) = HVI > 0 ? HVI : -inf
+ *   B_j(x) = 0.0 - dist                                       the row nearest to that region, for a member whose draw improves nowhere
+ * A row with a NaN among its m path values has A = B = -inf.  The order is fixed -- acc = 0.0, cells in order, inside a cell
+ * p = t_0, p = p t_1, ..., acc = acc + p; dist a running minimum from +inf of a running maximum from 0.0; no fused multiply-add --
+ * so A and B follow from the returned path values exactly (bogp.thompson.hvi_select_numpy).
+ *   omega (L x d), phase (L), weights (L x q m), eps (N x q m or NULL = zeros): HOST arrays, row-major
+ *   lower / upper (C x m, HOST, row-major): 1 <= C <= BOGP_MAX_EHVI_CELLS, lower finite, upper >= lower (+inf allowed)
+ *   best_val, best_idx (q x 2 x k): per member the k best rows of A, then the k best rows of B, by bogp_sweep_topk's rules (first
+ *              maximum, ties to the lower index, slots beyond M are (-inf, -1));  best_x (q x 2 x k x d, may be NULL)
+ *   paths_out (q x m x M, may be NULL): the path values;  coef_out (N x q m, may be NULL): g
+ * Members are independent: none sees another's pick.  Per call: the draw at the training rows and one N x q m solve; per candidate
+ * chunk the correlation producer and k_thompson_ehvi (kernels_thompson_ehvi.hip: the constrained kernel's matrix part, then one
+ * pass over the C cells per row and member).  The variance contraction never runs.  The outputs are bit-identical for any
+ * BOGP_CHUNK_MB, with and without paths_out, and a member's do not depend on the members beside it; the path values are
+ * bogp_sweep_thompson_constrained's bits for the same columns.
+ * BOGP_ERR_INVALID: no committed model, no candidates, a model of one target (bogp_sweep_thompson serves it), m != n_targets,
+ * q < 1 or q m > BOGP_MAX_PATHS, L or k out of range, C outside [1, BOGP_MAX_EHVI_CELLS], a null required array, a non-finite
+ * lower bound, a NaN upper bound, upper < lower, a non-finite entry in omega / phase / weights / eps.  BOGP_ERR_UNSUPPORTED: the
+ * noisy and noise-estimating modes, the cubic and generalized-exponential kernels, a polynomial trend basis, a lift on the handle,
+ * a forest, a communicator of more than one rank.  `thompson_ehvi_last`: as bogp_thompson_last, of the last such call.        */
+int bogp_sweep_thompson_ehvi(bogp_handle* h, int m, int q, int L, const double* omega, const double* phase, const double* weights,
+                             const double* eps, int C, const double* lower, const double* upper, int k, double* best_val,
+                             int64_t* best_idx, double* best_x, double* paths_out, double* coef_out);
+int bogp_thompson_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
+
 /* ---- sweep: Kriging-believer batches for EHVI -------------------------------------------------------------
  * q proposals per call for a multi-objective run -- what the reference names and leaves open: `class MOBO: """EHVI with
  * Kriging believer"""` stands over `# TODO: implement the Kriging believer strategy` (mobo.py:168-178), and MOBO(n_point > 1)
