@@ -26,6 +26,7 @@ CRITERIA_COLUMNS = 8
 ABI_VERSION = 9  # BOGP_ABI_VERSION of include/bogp.h this binding table was written for
 MAX_Q = 64
 PRUNE_PATH_NONE, PRUNE_PATH_CHUNKS, PRUNE_PATH_ONEPASS, PRUNE_PATH_ONEPASS_FALLBACK = 0, 1, 2, 3  # bogp_last_prune_path
+PRUNE_PILOT_NONE, PRUNE_PILOT_FIRST_ROWS, PRUNE_PILOT_BEST_BOUND = 0, 1, 2  # bogp_last_prune_pilot
 # bogp_contract_tile_rows: workgroups of the 64-row grid per four CUs from which a launch takes 64 / 32 rows (csrc/bogp_internal.h)
 CONTRACT_TILE64_MIN_WG_PER_4CU, CONTRACT_TILE32_MIN_WG_PER_4CU = 14, 6
 MAX_TARGETS = 8
@@ -154,6 +155,8 @@ SIGNATURES = {
     "bogp_prune_below": (C.c_int, [C.c_double, C.c_double]),
     "bogp_set_prune_bound32": (C.c_int, [C.c_void_p, C.c_int]),
     "bogp_last_bound32": (C.c_int, [C.c_void_p, _lp, _lp, _ip]),
+    "bogp_set_prune_pilot": (C.c_int, [C.c_void_p, C.c_int, C.c_int64]),
+    "bogp_last_prune_pilot": (C.c_int, [C.c_void_p, _ip, _lp, _lp, C.c_int64]),
     "bogp_debug_bound32": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_ubyte), _lp]),
     "bogp_debug_live": (None, [_lp, _lp, _lp]),
     "bogp_bound32_margin": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]),
@@ -1533,6 +1536,21 @@ class Engine:
         rows, kept, fb = C.c_int64(), C.c_int64(), C.c_int()
         self._check(self._lib.bogp_last_bound32(self._h, C.cast(C.byref(rows), _lp), C.cast(C.byref(kept), _lp), C.cast(C.byref(fb), _ip)))
         return int(rows.value), int(kept.value), int(fb.value)
+
+    def set_prune_pilot(self, mode=1, block_rows=0):
+        """Which rows of a pruned sweep set the thresholds: 0 the first rows always, 2 per block of `block_rows` rows (0: the default,
+        else a multiple of 256) and per criterion the row with the best FP32 bound wherever the FP32 stage runs, 1 (the default) the
+        latter in sweeps of at least 262144 candidates.  Winners and values are unchanged."""
+        self._check(self._lib.bogp_set_prune_pilot(self._h, int(mode), int(block_rows)))
+
+    def last_prune_pilot(self):
+        """(kind, indices) of the last sweep's pilot: kind is one of PRUNE_PILOT_*, indices the pilot's candidate rows in order."""
+        kind, n = C.c_int(), C.c_int64()
+        self._check(self._lib.bogp_last_prune_pilot(self._h, C.cast(C.byref(kind), _ip), C.cast(C.byref(n), _lp), None, 0))
+        idx = np.empty(int(n.value), dtype=np.int64)
+        if idx.size:
+            self._check(self._lib.bogp_last_prune_pilot(self._h, None, None, idx.ctypes.data_as(_lp), idx.size))
+        return int(kind.value), idx
 
     def debug_bound32(self):
         """Per row of the last segment the FP32 stage bounded: (mu32, e_mu, wd32, e_w, flags) -- the FP32 sums r . gamma and w . r, their

@@ -315,6 +315,9 @@ extern "C" int bogp_candidates_bind(bogp_handle* h, const void* d_Xs, int64_t M)
 //                         |                              |                              | chunk (1,p0) and (p1,2) in place of (1,2)
 //   one pass              | every producer and FP32-sums | every contraction launch;    | whole sweep less the two: the small kernels and
 //                         | launch; a fall-back's (0,1)  | a fall-back's (2,3)          | the host's waits
+//   one pass, best-bound  | the same; the FP32 sums come | the same: the pilot's rounds | the same, k_bound32_select / _pick and the wait for
+//   pilot                 | first, the pilot's producer  | are contraction launches     | the pilot's count among them
+//                         | launches behind them         |                              |
 //   forest calls          | -                            | -                            | k_forest / k_forest_ehvi         (n_chunks = 1)
 //
 // The believer batches (bogp_api_believer.hip) leave pass 0 here as "chunks" -- its criteria span is k_acquisition, k_ehvi or
@@ -434,6 +437,10 @@ int bogp::check_criteria(bogp_handle* h, int q, const int* acq_id, const double*
 #endif
 constexpr int64_t PRUNE_PILOT = BOGP_PRUNE_PILOT;  // rows of chunk 0 evaluated exactly to seed the thresholds; a multiple of 256
 static_assert(PRUNE_PILOT % 256 == 0 && PRUNE_PILOT > 0 && PRUNE_PILOT <= 8192, "pilot rows");
+// rows per block of the best-bound pilot (one pilot row per block and criterion) unless bogp_set_prune_pilot names another: 1024 / 2048 /
+// 4096 measured at C3 and C4 (profiles/bound_pilot.txt); and the rows from which the automatic mode takes that pilot
+constexpr int64_t PRUNE_PILOT_BLOCK = 1024, PRUNE_PILOT_AUTO_ROWS = 64 * PRUNE_PILOT;
+static_assert(PRUNE_PILOT_BLOCK % 256 == 0, "k_bound32_select's records are of 256 rows");
 
 template <class Args>  // AcqArgs, SmallArgs, PruneBoundArgs
 static void set_criteria(Args& a, int q, const int* id, const double* par) { a.q = q; for (int i = 0; i < q; ++i) { a.acq_id[i] = id[i]; a.acq_par[i] = par ? par[i] : 0.0; } }
@@ -444,7 +451,7 @@ struct SweepCtx {
   SweepGeometry g;
   int64_t M, nblk_total;  // (256-row block records; per-chunk block counts are rounded up)
   int Nrows, nJ, nJ_main, NJ16, pv;
-  bool vx_model, vx, overlap, prune, onepass, bound32;
+  bool vx_model, vx, overlap, prune, onepass, bound32, bound_pilot;  // (bound_pilot: the one-pass flow picks its pilot by the FP32 bounds)
   hipStream_t st, stP;
   // pruned sweep: rows of the survivor buffer, segment geometry of the one-pass flow, the carved work space (sweep_workspace)
   int64_t Ms, seg_rows, seg_stride, Rmax, sidx_cap, prune_nbk;
@@ -454,6 +461,7 @@ struct SweepCtx {
   unsigned char *pflags, *pflags1;
   double *pxc, *dss_surv;
   double *pxc1, *pmu32, *pwd32, *pna32;  // FP32 stage: the candidate rows of S1; the per-row sums and squared norms of a segment
+  int64_t pilot_head;  // one pass: rows at the head of chunk 0 that the pilot evaluated (0 under the best-bound pilot): what a fall-back skips
   int64_t blk_offset, prune_pending;  // block records written so far; upper bound of the survivors waiting in the buffer (their count stays on the device)
 };
 
@@ -640,10 +648,10 @@ static int sweep_trend_chunk(bogp_handle* h, const SweepCtx& cx, int b, int64_t 
   return BOGP_OK;
 }
 
-// One chunk of the per-chunk pruned flow, behind its producer: in chunk 0 the pilot (unless `skip` rows of it are done already), then
+// One chunk of the per-chunk pruned flow, behind its producer: in chunk 0 the pilot (unless pilot_done: `skip` rows at its head are done already), then
 // bound -> scan + decision -> compaction -> gather, the contractions of both outcomes, criteria and the running best.  `model`: the
 // criteria kernel's arguments less the arrays; `ka`: the chunk's contraction; `e1`: the mark behind the chunk's producer.
-static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model, const ContractArgs& ka, int64_t c, int64_t c_end, int64_t m0, int64_t mcount, int64_t skip, int e1) {
+static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model, const ContractArgs& ka, int64_t c, int64_t c_end, int64_t m0, int64_t mcount, bool pilot_done, int64_t skip, int e1) {
   hipStream_t st = cx.st;
   long long* const pctl = cx.pctl;
   const int64_t Mc = cx.g.Mc, Ms = cx.Ms, nblk_total = cx.nblk_total;
@@ -651,7 +659,7 @@ static int sweep_pruned_chunk(bogp_handle* h, SweepCtx& cx, const AcqArgs& model
   SpanTimer& tm = h->timer;
   int e, p0 = -1, p1 = -1, e2 = 0, e3 = 0, e4 = 0;
   int64_t i0 = 0;  // first row of the chunk's region: behind the pilot in chunk 0
-  if (skip > 0) i0 = skip;
+  if (pilot_done) i0 = skip;
   else if (c == 0) {  // pilot: the first rows through the contraction and the criteria as ever -> the first thresholds
     const int64_t P = std::min<int64_t>(PRUNE_PILOT, mcount);
     HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
@@ -728,7 +736,7 @@ static void multi_target_chunk(const bogp_handle* h, const SweepCtx& cx, int b, 
 }
 
 // Chunks [c_begin, c_end): producer -> contraction -> criteria (or the pruned flow).  pilot_done (a pruned sweep that began on the
-// one-pass flow): thresholds, control words and the pilot rows' winners are in place -- chunk 0 starts behind the pilot.
+// one-pass flow): thresholds, control words and the pilot rows' winners are in place -- chunk 0 starts behind cx.pilot_head.
 // Two-stream mode (cx.overlap): the producer of chunk c + 1 runs on stP beside the contraction of chunk c, what it writes double buffered.
 static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c_end, bool pilot_done) {
   const SweepRequest& rq = cx.rq;
@@ -760,7 +768,7 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
     int e;  // lazily uploaded candidates: this chunk's rows must have arrived (chunk 0: copied here; later ones: below)
     if ((e = lazy_copy_to(h, m0 + mcount)) || (e = lazy_wait(h, stP)) || (stP != st && (e = lazy_wait(h, st)))) return e;
     if ((e = tm.mark(h, stP, &e0))) return e;
-    const int64_t skip = pilot_done && c == 0 ? std::min<int64_t>(PRUNE_PILOT, mcount) : 0;  // (a multiple of 64)
+    const int64_t skip = pilot_done && c == 0 ? std::min<int64_t>(cx.pilot_head, mcount) : 0;  // (a multiple of 64)
     if (skip > 0) {
       ca.m0 += skip; ca.rT += skip; ca.mu_part += skip; ca.w_part += skip;
     }
@@ -774,7 +782,7 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
     tm.span(T_PRODUCER, e0, e1);
     if (overlap) HIPCHK(h, hipStreamWaitEvent(st, tm.event(e1), 0));
     if (cx.prune) {
-      if ((e = sweep_pruned_chunk(h, cx, model, ka, c, c_end, m0, mcount, skip, e1))) return e;
+      if ((e = sweep_pruned_chunk(h, cx, model, ka, c, c_end, m0, mcount, pilot_done, skip, e1))) return e;
     } else {
       if ((e = tm.mark(h, st, &e2))) return e;
       // predict(X) without eval_MSE (gpr.py:486-491 returns before the triangular solve): the N^2 contraction is skipped
@@ -821,19 +829,24 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
 // One pass: pilot -> pilot estimate -> per segment: producer without the store, bound, scan, survivor indices ->
 // rounds.  Two fall-backs to sweep_chunks: the whole sweep where the pilot's own rows show that little can be pruned, one segment where
 // too many of its rows survive.  The host waits twice per decision (survivors_of).
+// Best-bound pilot (cx.bound_pilot): no rows in front of the segments and no estimate; per segment the FP32 sums of
+// ALL its rows come first, the rows with the largest bounds are evaluated as survivors are -- they set the thresholds -- and only then
+// are the sums flagged, those rows left out.
 static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
   hipStream_t st = cx.st;
   const int64_t M = cx.M, Mc = cx.g.Mc, Ms = cx.Ms, nchunk = cx.g.nchunk, nblk_total = cx.nblk_total;
   const int S = cx.g.S, q = cx.rq.q, kernel = h->kernel;
   long long* const pctl = cx.pctl;
-  const int64_t P = std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
+  const int64_t P = cx.bound_pilot ? 0 : std::min<int64_t>(PRUNE_PILOT, Mc);  // (nchunk > 1: chunk 0 is a whole chunk)
+  const int64_t B = h->pilot_block_rows > 0 ? h->pilot_block_rows : PRUNE_PILOT_BLOCK;
   long long* const hcount = reinterpret_cast<long long*>(h->hfit + 3504);  // pinned: the one count the host waits for
   int e, w0 = 0, w1 = 0;  // (the marks around the whole sweep)
   // scan of the bound's block counts (and, index_from >= 0, the survivors' global indices in order); the host waits for the count
-  // (`through`: the flagged rows are rows of that list -- S out of S1 -- and their entries of it are what is kept)
-  auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out, const unsigned char* flags, int64_t* sidx, const int64_t* through) -> int {
+  // (`through`: the flagged rows are rows of that list -- S out of S1 -- and their entries of it are what is kept; `cap`: entries of sidx)
+  auto survivors_of = [&](int64_t rows, int64_t index_from, long long* out, const unsigned char* flags, int64_t* sidx, const int64_t* through,
+                          int64_t cap) -> int {
     HIPCHK(h, launch_prune_scan(cx.pblk_count, (rows + 255) / 256, cx.poffsets, rows, -1, pctl, st));
-    if (index_from >= 0) HIPCHK(h, launch_prune_index(flags, cx.poffsets, rows, index_from, cx.sidx_cap, sidx, st, through));
+    if (index_from >= 0) HIPCHK(h, launch_prune_index(flags, cx.poffsets, rows, index_from, cap, sidx, st, through));
     HIPCHK(h, hipMemcpyAsync(hcount, pctl + PRUNE_CTL_TOTAL, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     *out = *hcount;
@@ -857,6 +870,20 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
     HIPCHK(h, launch_prune_update(h->dblk_val, h->dblk_idx, nblk_total, nullptr, cnt, q, h->dbest_val, h->dbest_idx, st));
     return BOGP_OK;
   };
+  // rows list[0 .. n) of the candidates, in rounds of at most one survivor buffer and in the list's order: candidate rows, the storing
+  // producer, evaluate
+  auto evaluate_rows = [&](const int64_t* list, int64_t n, int* rounds) -> int {
+    for (int64_t k0 = 0; k0 < n; k0 += Ms) {
+      const int64_t cnt = std::min<int64_t>(Ms, n - k0);
+      HIPCHK(h, launch_prune_rows(h->dXs, list + k0, cnt, h->d, cx.pxc, st));
+      CorrArgs cr = cc;
+      cr.Xs = cx.pxc; cr.M = cnt;
+      if (int e2 = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cr, (int)((cnt + 63) / 64), S, st); })) return e2;
+      if (int e2 = evaluate(cnt, list + k0)) return e2;
+      ++*rounds;
+    }
+    return BOGP_OK;
+  };
   // a per-chunk path after all: chunks [c0, c1) behind the pilot, with the chunk buffer they need
   auto fall_back = [&](int64_t c0, int64_t c1, int path) -> int {
     int e2;
@@ -866,15 +893,29 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
     h->prune_path = path;
     return BOGP_OK;
   };
+  cx.pilot_head = P;
+  h->pilot_rows = P;
+  if (cx.bound_pilot) {  // the pilots' indices outlive their segments: bogp_last_prune_pilot reads them
+    size_t room = 0;
+    for (int64_t s0 = 0; s0 < M; s0 += cx.seg_rows) {
+      const int64_t rows = std::min<int64_t>(M, s0 + cx.seg_rows) - s0;
+      room += (size_t)std::min<int64_t>(rows, q * ((rows + B - 1) / B));
+    }
+    if ((e = h->dpilot_idx.ensure(h, room))) return e;
+    h->pilot_kind = BOGP_PRUNE_PILOT_BEST_BOUND;
+  }
   if ((e = h->timer.mark(h, st, &w0))) return e;
   HIPCHK(h, launch_prune_init(pctl, h->dbest_val, h->dbest_idx, q, P, st));
-  if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cc, (int)(P / 64), S, st); }))) return e;
-  if ((e = evaluate(P, nullptr))) return e;
-  // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
   long long pilot_surv = 0;
-  pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
-  HIPCHK(h, launch_prune_bound(pb, st));
-  if ((e = survivors_of(P, -1, &pilot_surv, cx.pflags, cx.psidx, nullptr))) return e;
+  if (!cx.bound_pilot) {
+    if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cc, (int)(P / 64), S, st); }))) return e;
+    if ((e = evaluate(P, nullptr))) return e;
+    // pilot estimate: the pilot's own rows against the thresholds they set -- what share of such rows the bound lets through
+    pb.mu_part = h->dmu_part[1]; pb.w_part = h->dw_part[1]; pb.Mc = Ms; pb.rcount = P;
+    HIPCHK(h, launch_prune_bound(pb, st));
+    if ((e = survivors_of(P, -1, &pilot_surv, cx.pflags, cx.psidx, nullptr, cx.sidx_cap))) return e;
+  }
+  // (best-bound pilot: no estimate -- 0 of 0 rows -- so a flat landscape shows only in the segment's own counts, behind a wasted FP32 pass)
   if (prune_decide(P, pilot_surv, 1, 0) == BOGP_PRUNE_PATH_CHUNKS) {
     if ((e = fall_back(0, nchunk, BOGP_PRUNE_PATH_CHUNKS))) return e;
   } else {
@@ -894,12 +935,32 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         ba.md = md32; ba.mu = cx.pmu32; ba.wd = cx.pwd32; ba.na = cx.pna32;
         if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_bound32_sums(kernel, ba, st); }))) return e;
         PruneBoundArgs p1 = pb;
-        p1.mu_part = cx.pmu32; p1.w_part = cx.pwd32; p1.S = 1; p1.Mc = rows; p1.rcount = rows; p1.flags = cx.pflags1;
-        HIPCHK(h, launch_bound32_flags(p1, kernel, h->d, cx.pwd32, cx.pna32, md32, st));
-        if ((e = survivors_of(rows, sb, &s1, cx.pflags1, cx.psidx1, nullptr))) return e;
+        p1.mu_part = cx.pmu32; p1.w_part = cx.pwd32; p1.S = 1; p1.Mc = rows; p1.rcount = rows;
+        if (cx.bound_pilot) {
+          // the segment's pilot: per block of B rows and criterion the row with the largest bound (flags in pflags, which stage 2 reuses only
+          // after k_bound32_flags has read them), its ordered indices, the exact evaluation that sets or raises the thresholds
+          int64_t* const plist = h->dpilot_idx + h->pilot_rows;
+          const int64_t room = std::min<int64_t>(rows, q * ((rows + B - 1) / B));
+          long long np = 0;
+          int pilot_rounds = 0;
+          HIPCHK(h, launch_bound32_select(p1, kernel, h->d, cx.pwd32, cx.pna32, md32, B, h->dblk_val, h->dblk_idx, nblk_total, st));
+          if ((e = survivors_of(rows, sb, &np, cx.pflags, plist, nullptr, room))) return e;
+          if (np > room) FAIL(h, BOGP_ERR_HIP, "best-bound pilot: %lld rows selected, at most %lld possible", np, (long long)room);
+          if ((e = evaluate_rows(plist, np, &pilot_rounds))) return e;
+          h->pilot_rows += np;
+        }
+        p1.flags = cx.pflags1;
+        HIPCHK(h, launch_bound32_flags(p1, kernel, h->d, cx.pwd32, cx.pna32, md32, st, cx.bound_pilot ? cx.pflags : nullptr));
+        if ((e = survivors_of(rows, sb, &s1, cx.pflags1, cx.psidx1, nullptr, cx.sidx_cap))) return e;
         h->b32_rows += rows; h->b32_kept += s1; h->b32_last_rows = rows;
         if (4 * s1 > rows) {  // the exact pass over the whole segment after all: the FP32 pass was wasted
           ++h->b32_fallbacks;
+          if (cx.bound_pilot) {
+            // no estimate stood in front of this segment, so this is where a flat landscape (or a threshold that prunes nothing) shows: chunk
+            // by chunk at once -- the exact pass over all rows would be a second wasted pass (4.7 ms at C3, profiles/bound_pilot.txt)
+            if ((e = fall_back(sb / Mc, (se + Mc - 1) / Mc, BOGP_PRUNE_PATH_ONEPASS_FALLBACK))) return e;
+            continue;
+          }
           s1 = -1;
         }
       }
@@ -907,7 +968,7 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cs, (int)((rows + 63) / 64), S, st); }))) return e;
         pb.rcount = rows;
         HIPCHK(h, launch_prune_bound(pb, st));
-        if ((e = survivors_of(rows, sb, &surv, cx.pflags, cx.psidx, nullptr))) return e;
+        if ((e = survivors_of(rows, sb, &surv, cx.pflags, cx.psidx, nullptr, cx.sidx_cap))) return e;
       } else if (s1 > 0) {
         // stage 2: the exact sums of S1's rows alone (a row's sums do not depend on its neighbours), the exact bound, S in the original order
         HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx1, s1, h->d, cx.pxc1, st));
@@ -915,21 +976,13 @@ static int sweep_onepass(bogp_handle* h, SweepCtx& cx) {
         if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cs, (int)((s1 + 63) / 64), S, st); }))) return e;
         pb.rcount = s1;
         HIPCHK(h, launch_prune_bound(pb, st));
-        if ((e = survivors_of(s1, 0, &surv, cx.pflags, cx.psidx, cx.psidx1))) return e;
+        if ((e = survivors_of(s1, 0, &surv, cx.pflags, cx.psidx, cx.psidx1, cx.sidx_cap))) return e;
       }
       if (prune_decide(P, pilot_surv, rows, surv) == BOGP_PRUNE_PATH_ONEPASS_FALLBACK) {  // (needs ordered candidates: the pilot saw few such rows)
         if ((e = fall_back(sb / Mc, (se + Mc - 1) / Mc, BOGP_PRUNE_PATH_ONEPASS_FALLBACK))) return e;
         continue;
       }
-      for (int64_t k0 = 0; k0 < surv; k0 += Ms) {  // rounds of at most one survivor buffer, in the survivors' order
-        const int64_t cnt = std::min<int64_t>(Ms, surv - k0);
-        HIPCHK(h, launch_prune_rows(h->dXs, cx.psidx + k0, cnt, h->d, cx.pxc, st));
-        CorrArgs cr = cc;
-        cr.Xs = cx.pxc; cr.M = cnt;
-        if ((e = timed_span(h, h->timer, st, T_PRODUCER, [&] { return launch_corr_chunk(kernel, cr, (int)((cnt + 63) / 64), S, st); }))) return e;
-        if ((e = evaluate(cnt, cx.psidx + k0))) return e;
-        ++h->prune_rounds;
-      }
+      if ((e = evaluate_rows(cx.psidx, surv, &h->prune_rounds))) return e;
       h->prune_survivors += surv;
     }
   }
@@ -950,6 +1003,7 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   const int64_t M = h->M;
   h->prune_path = BOGP_PRUNE_PATH_NONE; h->prune_survivors = 0; h->prune_rounds = 0;
   h->b32_rows = h->b32_kept = h->b32_last_rows = 0; h->b32_fallbacks = 0;
+  h->pilot_kind = BOGP_PRUNE_PILOT_NONE; h->pilot_rows = 0;
   int e;
   // the two single-target shortcuts (the multi-target requests -- bogp_sweep_ehvi: eh non-null, bogp_sweep_constrained: cn non-null,
   // bogp_sweep_ehvi_constrained: ec non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
@@ -993,6 +1047,12 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   // ... bounded in FP32 first where the kernel's profile has a bounded slope
   cx.bound32 = cx.onepass && h->prune_bound32 != 0 && bound32_supported(h->kernel, h->d);
   if (cx.bound32 && (h->b32_gen != h->commit_gen || h->b32_target != h->target) && (e = bound32_prepare(h))) return e;  // (another target since the commit)
+  // ... and, in a sweep whose rows far outnumber any pilot, its pilot chosen by those bounds
+  cx.bound_pilot = cx.bound32 && (h->pilot_mode == 2 || (h->pilot_mode == 1 && M >= PRUNE_PILOT_AUTO_ROWS));
+  if (cx.prune) {
+    h->pilot_kind = BOGP_PRUNE_PILOT_FIRST_ROWS;
+    h->pilot_rows = std::min<int64_t>(PRUNE_PILOT, std::min<int64_t>(cx.g.Mc, M));
+  }
   if ((e = sweep_workspace(h, cx))) return e;
   if ((e = ensure_sweep_outputs(h, q, cx.nblk_total, rq.want_out ? (size_t)M * rq.targets() : 0, rq.want_acq_out))) return e;
   if (cx.overlap) {  // the producer stream must see everything queued on the main stream so far (commit, uploads)
@@ -1111,6 +1171,32 @@ extern "C" int bogp_set_prune_bound32(bogp_handle* h, int on) {
   return BOGP_OK;
 }
 
+extern "C" int bogp_set_prune_pilot(bogp_handle* h, int mode, int64_t block_rows) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (mode < 0 || mode > 2) FAIL(h, BOGP_ERR_INVALID, "bogp_set_prune_pilot: mode %d is none of 0 (the first rows), 1 (automatic), 2 (best-bound)", mode);
+  if (block_rows < 0 || block_rows % 256 != 0)
+    FAIL(h, BOGP_ERR_INVALID, "bogp_set_prune_pilot: block_rows = %lld is neither 0 (the default) nor a positive multiple of 256", (long long)block_rows);
+  h->pilot_mode = mode;
+  h->pilot_block_rows = block_rows;
+  return BOGP_OK;
+}
+
+extern "C" int bogp_last_prune_pilot(bogp_handle* h, int* kind, int64_t* rows, int64_t* idx_out, int64_t cap) {
+  if (!h) return BOGP_ERR_INVALID;
+  if (kind) *kind = h->pilot_kind;
+  if (rows) *rows = h->pilot_rows;
+  if (!idx_out || h->pilot_rows == 0) return BOGP_OK;
+  if (cap < h->pilot_rows) FAIL(h, BOGP_ERR_INVALID, "bogp_last_prune_pilot: %lld rows, room for %lld", (long long)h->pilot_rows, (long long)cap);
+  if (h->pilot_kind == BOGP_PRUNE_PILOT_BEST_BOUND) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(idx_out, h->dpilot_idx, (size_t)h->pilot_rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+  } else {
+    for (int64_t i = 0; i < h->pilot_rows; ++i) idx_out[i] = i;
+  }
+  return BOGP_OK;
+}
+
 extern "C" int bogp_last_bound32(bogp_handle* h, int64_t* rows, int64_t* kept, int* fallbacks) {
   if (!h) return BOGP_ERR_INVALID;
   if (rows) *rows = h->b32_rows;
@@ -1178,6 +1264,7 @@ extern "C" int bogp_last_contracted_rows(bogp_handle* h, int64_t* rows) {
     HIPCHK(h, hipMemcpyAsync(&n, h->dprune + PRUNE_CTL_CONTRACTED, sizeof(n), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *rows = (int64_t)n + h->prune_survivors;  // (+ the rows the one-pass rounds contracted: the host knows those)
+    if (h->pilot_kind == BOGP_PRUNE_PILOT_BEST_BOUND) *rows += h->pilot_rows;  // (... and a best-bound pilot's: the device counted none)
   }
   return BOGP_OK;
 }

@@ -281,6 +281,13 @@ struct bogp_handle {
   int b32_fallbacks = 0;
   size_t b32_ws_row32 = 0, b32_ws_flag1 = 0, b32_ws_rmax = 0;  // where the last sweep's work space holds the segment's sums / flags (words of dprune)
   int64_t b32_last_rows = 0;           // rows of the last segment bounded in FP32: what bogp_debug_bound32 reads back
+  // the pilot of the pruned sweep (bogp_set_prune_pilot): the first rows, or per block of rows and criterion the row
+  // with the best FP32 bound
+  int pilot_mode = 1;            // 0 the first rows always, 1 automatic, 2 best-bound wherever the FP32 stage runs
+  int64_t pilot_block_rows = 0;  // rows per block of the best-bound pilot; 0: the default
+  int pilot_kind = 0;            // BOGP_PRUNE_PILOT_* of the last sweep
+  int64_t pilot_rows = 0;        // ... its rows (best-bound: over the segments, their indices in dpilot_idx, in order)
+  bogp::DevBuf<int64_t> dpilot_idx;
   bool prune_used = false;       // the last sweep pruned: its contracted-row count is on the device (dprune[4])
   int64_t contracted_rows = 0;   // ... otherwise it is this
   bogp::DevBuf<double> dtopk_val;  // [q][k] winners of bogp_sweep_topk (device-resident between its passes)

@@ -202,8 +202,14 @@ hipError_t launch_bound32_prepare(int kernel, const double* XthT, const double* 
                                   float* XthT32, float* vec32, double* stats, hipStream_t st);
 hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st);
 // PruneBoundArgs' region with mu_part = the FP32 sums (S = 1): flags and block counts as launch_prune_bound leaves them
+// (exclude: flags of rows that are not flagged again -- the best-bound pilot's -- or null)
 hipError_t launch_bound32_flags(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
-                                hipStream_t st);
+                                hipStream_t st, const unsigned char* exclude = nullptr);
+// The best-bound pilot: per block of block_rows consecutive rows (a multiple of 256) and criterion, the row with the
+// largest interval bound -- a NaN first, the lowest index on a tie.  pb.flags: 1 for those rows, 0 for every other row of the region;
+// pb.blk_count as launch_bound32_flags leaves it; blk_val / blk_idx [q][stride]: scratch records, stride >= ceil(rcount / 256).
+hipError_t launch_bound32_select(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
+                                 int64_t block_rows, double* blk_val, int64_t* blk_idx, int64_t stride, hipStream_t st);
 
 // What the chunk loop and the committed model fill for a kernel that evaluates an m-target posterior over one chunk: the first part
 // of EhviArgs and ConstrainedArgs, read by multi_target_moments (bogp_device.h).  Both blocks lie in memory as they did before they

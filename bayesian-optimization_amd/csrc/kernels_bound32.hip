@@ -12,6 +12,8 @@
 //                      the profile's constants folded into the operands, the squared distance straight from the matrix chain
 //   k_bound32_sums_any the same for any d up to BOUND32_MAX_D: fragments re-read from LDS, the k loop at run time, unscaled operands
 //   k_bound32_flags    k_prune_bound with margins: flags and block counts for k_prune_scan / k_prune_index
+//   k_bound32_select, k_bound32_pick   the best-bound pilot: per block of B rows and criterion the row whose bound is
+//                      largest, flagged for the same scan
 // Served: SE, Matern-3/2 and Matern-5/2 (profiles with a bounded slope in the squared distance) up to d = BOUND32_MAX_D.
 #include "bogp_device.h"
 #include "bogp_internal.h"
@@ -362,40 +364,113 @@ __global__ __launch_bounds__(256, 4) void k_bound32_sums(Bound32Args a) {  // (f
   }
 }
 
-// k_prune_bound's statements on the FP32 sums and their margins: y_hat within e_mu of the row's exact value, sd_ub from the largest
-// |w . r - 1| the margin allows.  A row is dropped only when every criterion's interval bound is below its threshold.
+// k_prune_bound's statements on the FP32 sums and their margins: y_hat within e_y of the row's exact value, sd_ub from the largest
+// |w . r - 1| the margin allows -- what k_bound32_flags and k_bound32_select know of row i before a criterion is named.
+struct Bound32Row { double y_hat, e_y, sd_ub; };
+__device__ __forceinline__ Bound32Row bound32_row(const PruneBoundArgs& a, int kernel, int d, const double* __restrict__ wdv,
+                                                  const double* __restrict__ nav, const Bound32Model& md, int64_t i) {
+  double e_mu, e_w;
+  bound32_margin(kernel, d, nav[i], md.nb_max, md.gamma_l1, md.w_l1, &e_mu, &e_w);
+  const double mu = a.beta + a.mu_part[i];
+  double u2 = 0.0;
+  if (a.estimate_trend) {
+    const double u = (fabs(wdv[i] - 1.0) + e_w) / fabs(a.G);
+    u2 = u * u;
+  }
+  Bound32Row r;
+  // (1e-12: the roundings of the exact bound's own u, u2, mse and square root, each of which this one must not fall below)
+  r.sd_ub = sqrt((1.0 + u2) * a.sigma2) * (1.0 + 1e-12);
+  r.y_hat = a.minimize ? mu : -1 * mu;
+  r.e_y = e_mu + 1e-15 * fabs(mu);  // (the rounding of beta + the sum, on both sides)
+  return r;
+}
+
+// A row is dropped only when every criterion's interval bound is below its threshold.  `exclude` (the best-bound pilot, DESIGN.md
+// 5.22.3): rows that were evaluated exactly before the thresholds were read are not flagged again.
 __global__ __launch_bounds__(256) void k_bound32_flags(PruneBoundArgs a, int kernel, int d, const double* __restrict__ wdv,
-                                                       const double* __restrict__ nav, Bound32Model md) {
+                                                       const double* __restrict__ nav, Bound32Model md,
+                                                       const unsigned char* __restrict__ exclude) {
   __shared__ int s_cnt[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool valid = i < a.rcount;
   bool keep = false;
   if (valid) {
-    double e_mu, e_w;
-    bound32_margin(kernel, d, nav[i], md.nb_max, md.gamma_l1, md.w_l1, &e_mu, &e_w);
-    const double mu = a.beta + a.mu_part[i];
-    double u2 = 0.0;
-    if (a.estimate_trend) {
-      const double u = (fabs(wdv[i] - 1.0) + e_w) / fabs(a.G);
-      u2 = u * u;
-    }
-    // (1e-12: the roundings of the exact bound's own u, u2, mse and square root, each of which this one must not fall below)
-    const double sd_ub = sqrt((1.0 + u2) * a.sigma2) * (1.0 + 1e-12);
-    const double y_hat = a.minimize ? mu : -1 * mu;
-    const double e_y = e_mu + 1e-15 * fabs(mu);  // (the rounding of beta + the sum, on both sides)
-    keep = true;
+    const Bound32Row r = bound32_row(a, kernel, d, wdv, nav, md, i);
     bool below = true;
     for (int c = 0; c < a.q; ++c) {
-      const double b = acq_upper_bound_interval(a.acq_id[c], a.acq_par[c], y_hat, e_y, sd_ub, a.plugin, a.sigma2);
+      const double b = acq_upper_bound_interval(a.acq_id[c], a.acq_par[c], r.y_hat, r.e_y, r.sd_ub, a.plugin, a.sigma2);
       below = below && prune_below(b, a.best_val[c]);  // (false for a NaN or an infinity)
     }
-    keep = !below;
+    keep = !below && !(exclude && exclude[i]);
     a.flags[i] = keep ? 1 : 0;
   }
   const unsigned long long bal = __ballot(keep);
   if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(bal);
   __syncthreads();
   if (threadIdx.x == 0) a.blk_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// Best-bound pilot, step 1: the same interval bounds with no threshold -- per 256 rows and criterion the row with the largest bound
+// (np.argmax's order: a NaN first, the lowest index on a tie) as a record blk_val / blk_idx [c][stride]; every flag of the region cleared.
+__global__ __launch_bounds__(256) void k_bound32_select(PruneBoundArgs a, int kernel, int d, const double* __restrict__ wdv,
+                                                        const double* __restrict__ nav, Bound32Model md, double* __restrict__ blk_val,
+                                                        int64_t* __restrict__ blk_idx, int64_t stride) {
+  __shared__ double sv[4];
+  __shared__ int64_t si[4];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < a.rcount;
+  Bound32Row r = {0.0, 0.0, 0.0};
+  if (valid) {
+    r = bound32_row(a, kernel, d, wdv, nav, md, i);
+    a.flags[i] = 0;
+  }
+  for (int c = 0; c < a.q; ++c) {
+    const double b = valid ? acq_upper_bound_interval(a.acq_id[c], a.acq_par[c], r.y_hat, r.e_y, r.sd_ub, a.plugin, a.sigma2) : -INFINITY;
+    const ArgMax best = block_argmax(b, valid ? i : INT64_MAX, sv, si);
+    if (threadIdx.x == 0) {
+      blk_val[(size_t)c * stride + blockIdx.x] = best.v;
+      blk_idx[(size_t)c * stride + blockIdx.x] = best.i;
+    }
+    __syncthreads();  // (sv / si are written again by the next criterion)
+  }
+}
+
+// Step 2, one workgroup per block of `nsub` records (B = 256 nsub rows): thread c folds criterion c's records in order, the winners'
+// flags are set, and the 256-row counts k_prune_scan reads are those of the DISTINCT winners (a row that wins several criteria is one
+// pilot row).  Every block begins below nblk, so it holds a valid row and a winner is never the INT64_MAX of a padding lane.
+__global__ __launch_bounds__(256) void k_bound32_pick(const double* __restrict__ blk_val, const int64_t* __restrict__ blk_idx, int64_t stride,
+                                                      int64_t nblk, int nsub, int q, unsigned char* __restrict__ flags,
+                                                      int* __restrict__ blk_count) {
+  __shared__ int64_t win[BOGP_MAX_Q];
+  __shared__ int first[BOGP_MAX_Q];
+  const int t = threadIdx.x;
+  const int64_t k0 = (int64_t)blockIdx.x * nsub, k1 = k0 + nsub < nblk ? k0 + nsub : nblk;
+  if (t < q) {
+    double v = blk_val[(size_t)t * stride + k0];
+    int64_t idx = blk_idx[(size_t)t * stride + k0];
+    for (int64_t k = k0 + 1; k < k1; ++k) {
+      const double ov = blk_val[(size_t)t * stride + k];
+      const int64_t oi = blk_idx[(size_t)t * stride + k];
+      if (better(ov, oi, v, idx)) {
+        v = ov;
+        idx = oi;
+      }
+    }
+    win[t] = idx;
+  }
+  __syncthreads();
+  if (t < q) {
+    int f = 1;
+    for (int c = 0; c < t; ++c) f = f && win[c] != win[t];
+    first[t] = f;
+    if (f) flags[win[t]] = 1;
+  }
+  __syncthreads();
+  for (int64_t k = k0 + t; k < k1; k += 256) {
+    int n = 0;
+    for (int c = 0; c < q; ++c) n += first[c] && (win[c] >> 8) == k;
+    blk_count[k] = n;
+  }
 }
 
 hipError_t launch_bound32_prepare(int kernel, const double* XthT, const double* xnorm, const double* gamma, const double* wvec, int d, int Np,
@@ -445,8 +520,19 @@ hipError_t launch_bound32_sums(int kernel, const Bound32Args& a, hipStream_t st)
 }
 
 hipError_t launch_bound32_flags(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
-                                hipStream_t st) {
-  hipLaunchKernelGGL(k_bound32_flags, dim3((unsigned)((pb.rcount + 255) / 256)), 256, 0, st, pb, kernel, d, wd, na, md);
+                                hipStream_t st, const unsigned char* exclude) {
+  hipLaunchKernelGGL(k_bound32_flags, dim3((unsigned)((pb.rcount + 255) / 256)), 256, 0, st, pb, kernel, d, wd, na, md, exclude);
+  return hipGetLastError();
+}
+
+hipError_t launch_bound32_select(const PruneBoundArgs& pb, int kernel, int d, const double* wd, const double* na, const Bound32Model& md,
+                                 int64_t block_rows, double* blk_val, int64_t* blk_idx, int64_t stride, hipStream_t st) {
+  const int64_t nblk = (pb.rcount + 255) / 256;
+  if (block_rows <= 0 || block_rows % 256 != 0 || pb.q < 1 || pb.q > BOGP_MAX_Q || nblk > stride) return hipErrorInvalidValue;
+  const int nsub = (int)(block_rows / 256);
+  hipLaunchKernelGGL(k_bound32_select, dim3((unsigned)nblk), 256, 0, st, pb, kernel, d, wd, na, md, blk_val, blk_idx, stride);
+  hipLaunchKernelGGL(k_bound32_pick, dim3((unsigned)((nblk + nsub - 1) / nsub)), 256, 0, st, blk_val, blk_idx, stride, nblk, nsub, pb.q,
+                     pb.flags, pb.blk_count);
   return hipGetLastError();
 }
 

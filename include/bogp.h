@@ -966,6 +966,22 @@ int bogp_set_prune_bound32(bogp_handle* h, int on);
  * pass over all rows after all.  All zero where the stage did not run.  Any output may be NULL.                                     */
 int bogp_last_bound32(bogp_handle* h, int64_t* rows, int64_t* kept, int* fallbacks);
 
+/* Which rows of a pruned sweep are evaluated first to set the thresholds (the pilot).  mode 0: the first 4096 rows, always.  mode 2:
+ * wherever the FP32 stage runs, the sums of a whole segment come first and the pilot is, per block of block_rows consecutive rows and
+ * per criterion, the row whose bound is largest -- rows likely to win, so the thresholds are (nearly) the final ones and few rows,
+ * often none, are left behind them.  mode 1 (the default): as mode 2 in a sweep of at least 262144 candidates, else
+ * as mode 0.  block_rows: 0 for the default (1024) or a positive multiple of 256.  Winners and values are the same bits under every
+ * mode.  BOGP_ERR_INVALID: another mode, a negative block_rows or one that is no multiple of 256.                                   */
+int bogp_set_prune_pilot(bogp_handle* h, int mode, int64_t block_rows);
+
+/* The pilot of the LAST sweep: kind = BOGP_PRUNE_PILOT_*, rows = its size (summed over the segments), and -- idx_out non-NULL, cap >=
+ * rows entries, else BOGP_ERR_INVALID -- its candidate indices in ascending order per segment (waits for a queued sweep).  kind and
+ * rows may be NULL.                                                                                                                */
+#define BOGP_PRUNE_PILOT_NONE 0       /* the sweep did not prune                                    */
+#define BOGP_PRUNE_PILOT_FIRST_ROWS 1 /* the first rows of the first chunk                          */
+#define BOGP_PRUNE_PILOT_BEST_BOUND 2 /* per block and criterion the row with the largest FP32 bound */
+int bogp_last_prune_pilot(bogp_handle* h, int* kind, int64_t* rows, int64_t* idx_out, int64_t cap);
+
 /* Debug read-back of the last segment the FP32 stage bounded (waits for a queued sweep): *rows = its rows (0: none); per row the FP32
  * sums r . gamma and w . r, their margins and the stage's flag.  Arrays of `cap` >= *rows entries, any of them NULL.                 */
 int bogp_debug_bound32(bogp_handle* h, int64_t cap, double* mu32, double* e_mu, double* wd32, double* e_w, unsigned char* flags, int64_t* rows);
