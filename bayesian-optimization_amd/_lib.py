@@ -133,6 +133,9 @@ SIGNATURES = {
                                                    _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "bogp_polish_ehvi_constrained": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp,
                                                C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
+    "bogp_point_eval_path": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]),
+    "bogp_polish_path": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+                                   C.c_double, C.c_double, _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1418,6 +1421,53 @@ class Engine:
                                                    _ptr(lower) if C_ else None, _ptr(upper) if C_ else None, len(lo), _ptr(lo), _ptr(hi),
                                                    int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))
         )  # fmt: skip
+        return Xo, fo, ne
+
+    def _path_operands(self, draw, coef, members, B):
+        """A sample-path call's operands as the entries take them: (member (B,) int32, q, L, omega, phase, weights, coef (N + 1, q) or
+        None).  `coef`: the (gt, bt) pair a `sweep_thompson` returned for this draw, or None for the prior paths."""
+        L, omega, phase, weights, _ = self._thompson_draw(draw)
+        q = weights.shape[1]
+        member = np.ascontiguousarray(members, dtype=np.int32).ravel()
+        if len(member) != B:
+            raise ValueError("members must name one path for each of the %d points" % B)
+        if coef is not None:
+            gt, bt = _f64(coef[0]), _f64(coef[1]).ravel()
+            if gt.shape != (self.N, q) or len(bt) != q:
+                raise ValueError("coef must be the (gt (%d, %d), bt (%d,)) pair of sweep_thompson" % (self.N, q, q))
+            coef = np.ascontiguousarray(np.vstack([gt, bt[None, :]]))
+        return member, q, L, omega, phase, weights, coef
+
+    def _path_call(self, fn, *args):
+        """One sample-path entry: what the library refuses as unsupported raises NotImplementedError with its message."""
+        try:
+            self._check(fn(self._h, *args))
+        except BogpError as e:
+            if e.code == ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+
+    def point_eval_path(self, X, draw, coef, members, minimize=True):
+        """Value and input gradient of posterior sample paths of the committed model at the rows of `X` (B x d) in ONE launch
+        (bogp_point_eval_path): row b on path members[b] of `draw` (the arrays `sweep_thompson` took), conditioned by `coef` (the pair
+        it returned) or, with None, the prior path.  Returns (values (B,), gradients (B, d)), both in the path's own sign."""
+        X = self._rows(X)
+        B = X.shape[0]
+        member, q, L, omega, phase, weights, coef = self._path_operands(draw, coef, members, B)
+        val, grad = np.empty(B), np.empty((B, self.d))
+        self._path_call(self._lib.bogp_point_eval_path, _ptr(X), B, member.ctypes.data_as(_ip), q, L, _ptr(omega), _ptr(phase), _ptr(weights),
+                        _ptr(coef), int(bool(minimize)), _ptr(val), _ptr(grad))  # fmt: skip
+        return val, grad
+
+    def polish_path(self, starts, lo, hi, draw, coef, members, minimize=True, max_evals: int = 50, pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local minimisation (maximisation with `minimize=False`) of sample paths inside the box
+        (bogp_polish_path): start b climbs path members[b]; two launches an iteration, none reads L^-1.  Returns (points (B, d), path
+        values (B,) in the path's own sign, evaluations used (B,)); values[b] is no worse than the path at starts[b] clipped into the box."""
+        X0, lo, hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), lo, hi, "lo / hi")
+        member, q, L, omega, phase, weights, coef = self._path_operands(draw, coef, members, B)
+        self._path_call(self._lib.bogp_polish_path, _ptr(X0), B, member.ctypes.data_as(_ip), _ptr(lo), _ptr(hi), q, L, _ptr(omega), _ptr(phase),
+                        _ptr(weights), _ptr(coef), int(bool(minimize)), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
+                        ne.ctypes.data_as(_ip))  # fmt: skip
         return Xo, fo, ne
 
     feasibility_grad = staticmethod(feasibility_grad)

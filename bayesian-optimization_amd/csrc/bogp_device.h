@@ -221,6 +221,18 @@ __device__ __forceinline__ double corr_profile(double s2, double pexp = 0.0) {
   return (1.0 + K + (K * K) * 0.3333333333333333) * exp(-K);
 }
 
+// d r / d x_k (corr_dx, gpr.py:600-661) from the radial scalars of the pair -- rv = corr_profile(s2), D = sqrt(s2) and e5 = exp(-sqrt(3) D) /
+// exp(-sqrt(5) D) for the two Matern kernels that read it; the same expressions as k_point_corr (kernels_fit.hip).  Shared by k_point_rhs
+// (kernels_point.hip) and k_point_path (kernels_point_path.hip).
+template <int KERNEL>
+__device__ __forceinline__ double point_dx_entry(double rv, double D, double e5, double theta_k, double diff) {
+  if (KERNEL == BOGP_KERNEL_ABSEXP) return -1.0 * rv * theta_k * (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
+  if (KERNEL == BOGP_KERNEL_SE) return -2 * rv * (theta_k * diff);
+  if (KERNEL == BOGP_KERNEL_MATERN32) return D > 0.0 ? (diff * theta_k / D) * (-3.0 * D * e5) : 0.0;
+  if (KERNEL == BOGP_KERNEL_MATERN52) return (-(5.0 / 3.0) * (1.0 + 2.23606797749979 * D) * e5) * (theta_k * diff);
+  return D > 0.0 ? -diff * theta_k / D * rv : 0.0;
+}
+
 // -h(D) such that dR0/dtheta_k = -(x_ik - x_jk)^2 * h  (gpr.py:736-770 corr_grad_theta):
 //   SE r; Matern-3/2 1.5 exp(-sqrt3 D); [extensions: Matern-5/2 (5/6)(1+sqrt5 D)exp(-sqrt5 D); Matern-1/2 r/(2D)]
 //   absolute_exponential: dR0/dtheta_k = -|x_ik - x_jk| * r  (:761-762) -- same h = r, first power of the distance

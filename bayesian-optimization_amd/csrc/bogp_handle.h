@@ -405,6 +405,10 @@ struct bogp_handle {
   double t_corr_ms = 0, t_contract_ms = 0, t_acq_ms = 0;
   int n_chunks = 0;
   bool timing_pending = false;  // the spans have not been read into the three times yet
+
+  // a sample-path call of the one-point path (bogp_point_eval_path / bogp_polish_path, kernels_point_path.hip)
+  bogp::DevBuf<double> dpt_path;   // its operands: omega (L d) | phase (L) | Wt (q L) | c (q N), member-major
+  bogp::DevBuf<int> dpt_member;    // the path of each of its B points
 };
 
 #define FAIL(h, code, ...)                              \

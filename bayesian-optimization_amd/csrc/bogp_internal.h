@@ -909,5 +909,24 @@ struct PointEhviConstrainedArgs {
   unsigned long long done_seq;
 };
 hipError_t launch_point_ehvi_constrained_finish(const PointEhviConstrainedArgs& a, int B, hipStream_t st);
+// value and input gradient of a single-objective sample path at B points (kernels_point_path.hip): ONE launch in place of
+// k_point_rhs + k_point_tri + a finish.  path_j(x) = beta - bt[j] + sum_n coef[j][n] r_n(x) + sum_l W[j][l] cos(omega_l . x + phase_l)
+struct PointPathArgs {
+  const double* X;       // N x d training points, row-major
+  const double* theta;   // d
+  const double* Xb;      // B x d points (device)
+  const int* member;     // [B] the path of each point, in [0, q)
+  const double* coef;    // [q][N] gamma - g_j, member-major; null: the prior paths beta + z_j (bt is not read)
+  const double* W;       // [q][L] weights times sqrt(2 sigma2 / L), member-major
+  const double* omega;   // [L][d]
+  const double* phase;   // [L]
+  double* out;           // [B][rec_stride]: path, 0, +-path, dpath (d), 0 (d), +-dpath (d) -- k_point_finish's record with q = 1
+  int N, d, L, rec_stride, minimize;
+  double beta;
+  double bt[16];         // b_j (BOGP_MAX_PATHS; not read for the prior paths)
+  unsigned long long* done_flag;  // as PointTriArgs
+  unsigned long long done_seq;
+};
+hipError_t launch_point_path(int kernel, const PointPathArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

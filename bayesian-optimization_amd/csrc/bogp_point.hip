@@ -2,7 +2,8 @@
 // bogp_point_eval_batch, bogp_gradient_batch, bogp_polish, and of its multi-objective finish (kernels_point_ehvi.hip):
 // bogp_point_eval_ehvi, bogp_polish_ehvi, and of its feasibility-weighted finish (kernels_point_constrained.hip):
 // bogp_point_eval_constrained, bogp_polish_constrained, and of the product of the two (kernels_point_ehvi_constrained.hip):
-// bogp_point_eval_ehvi_constrained, bogp_polish_ehvi_constrained.  See include/bogp.h for the contracts.
+// bogp_point_eval_ehvi_constrained, bogp_polish_ehvi_constrained, and of the one-launch evaluation of a posterior sample path
+// (kernels_point_path.hip): bogp_point_eval_path, bogp_polish_path.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -62,6 +63,7 @@ int ensure_counters(bogp_handle* h, size_t n) { return ensure_tickets(h, h->dpt_
 // What one evaluation computes at each of its points, whichever entry asks: q criteria and -- want_dacq -- their input gradients behind
 // k_point_finish, or the finish of an m-target model in its place (at most one of eh / cn / ec; they hold what that family alone knows:
 // cells and targets, or criteria and bounds, or cells and bounds).  The record then keeps k_point_finish's layout for q criteria, which EHVI fills like ONE.
+// `path`: a sample path's value and gradient instead, ONE launch of k_point_path in place of all three; the record is that of one criterion.
 struct PointCall {
   int q;
   const int* acq_id;
@@ -73,6 +75,7 @@ struct PointCall {
   const PointConstrainedArgs* cn;
   const PointEhviConstrainedArgs* ec;
   size_t mom_stride;  // doubles per point of the m-target finishes' second block, written behind the B records; 0: not wanted
+  const PointPathArgs* path;  // the staged operands of a sample-path call (its points, records and done word are filled in per launch)
 };
 
 // the EHVI request: a record sized like one criterion's with its gradient (the id itself is not evaluated)
@@ -115,6 +118,12 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, co
                      unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0) {
   hipStream_t st = h->stream;
   int e;
+  if (c.path) {  // no right-hand sides, no V, no finish
+    PointPathArgs pa = *c.path;
+    pa.Xb = dXb; pa.out = out; pa.rec_stride = pl.rec_stride; pa.done_flag = done_flag; pa.done_seq = done_seq;
+    HIPCHK(h, launch_point_path(h->kernel, pa, B, st));
+    return BOGP_OK;
+  }
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
   // cross-product epilogue against the packed V of the commit (kernels_point.hip, "MFMA flavour") instead of k_point_tri's
   // FP64-VALU loop.  "Enough" = the (64-column tile, 256-column group of V) workgroups fill the GPU's 512 slots one and a half
@@ -299,7 +308,7 @@ int point_eval_wait(bogp_handle* h, const PointPlan& pl, const PointCall& call, 
   // the finishing workgroups write straight into pinned host memory: one stream synchronisation, no copy command
   if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
   const double* dXb = nullptr;
-  if (B > 1 || d > BOGP_POINT_ARG_D) {
+  if (B > 1 || d > BOGP_POINT_ARG_D || call.path) {  // (k_point_path reads its points from device memory only)
     if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
     HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     dXb = h->dpt_Xb;
@@ -596,4 +605,116 @@ extern "C" int bogp_polish_ehvi_constrained(bogp_handle* h, const double* X0, in
   int e = ehvi_constrained_request(h, who, m_obj, C, lower, upper, n_con, lo, hi, &ec);
   if (e) return e;
   return polish_loop(h, who, ehvi_constrained_call(&ec, 0), X0, B, box_lo, box_hi, max_evals, pgtol, factr, Xout, fout, n_evals);
+}
+
+// ---- value and input gradient of a single-objective posterior sample path at B points (kernels_point_path.hip) -----------------------
+// path_j(x) = beta - b_j + r(x) . (gamma - g_j) + z_j(x) of bogp_sweep_thompson's draw: linear in r(x) plus a cosine sum, so ONE launch a
+// batch of points, no right-hand-side slab and no V.  What both entries refuse, in check_ready's and the Thompson entries' words where
+// they refuse the same; then the call's operands, formed on the host and uploaded ONCE: c_j = gamma - g_j and Wt = sqrt(2 sigma2 / L) W,
+// member-major, so that a point's workgroup reads one contiguous column of each.
+static int path_request(bogp_handle* h, const char* who, int B, const int* member, int q, int L, const double* omega, const double* phase,
+                        const double* weights, const double* coef, int minimize, PointPathArgs* pa) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior paths to draw", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (q < 1 || q > BOGP_MAX_PATHS) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d outside [1, %d]", who, q, BOGP_MAX_PATHS);
+  if (L < 16 || L > BOGP_MAX_FEATURES || L % 16 != 0)
+    FAIL(h, BOGP_ERR_INVALID, "%s: L = %d: a multiple of 16 in [16, %d] is required", who, L, BOGP_MAX_FEATURES);
+  if (B < 1 || B > BOGP_MAX_PATH_POINTS) FAIL(h, BOGP_ERR_INVALID, "%s: B = %d outside [1, %d]", who, B, BOGP_MAX_PATH_POINTS);
+  if (!member || !omega || !phase || !weights) FAIL(h, BOGP_ERR_INVALID, "%s: member, omega, phase and weights must be non-null", who);
+  for (int b = 0; b < B; ++b)
+    if (member[b] < 0 || member[b] >= q) FAIL(h, BOGP_ERR_INVALID, "%s: member[%d] = %d outside [0, %d)", who, b, member[b], q);
+  const int N = h->N, d = h->d;
+  const auto finite = [](const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(v[i])) return false;
+    return true;
+  };
+  if (!finite(omega, (size_t)L * d)) FAIL(h, BOGP_ERR_INVALID, "%s: omega has a non-finite entry", who);
+  if (!finite(phase, (size_t)L)) FAIL(h, BOGP_ERR_INVALID, "%s: phase has a non-finite entry", who);
+  if (!finite(weights, (size_t)L * q)) FAIL(h, BOGP_ERR_INVALID, "%s: weights has a non-finite entry", who);
+  if (coef && !finite(coef, (size_t)N * q + q)) FAIL(h, BOGP_ERR_INVALID, "%s: coef has a non-finite entry", who);
+  if (h->mode != BOGP_MODE_NOISELESS)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: %s mode: the reference pairs an unscaled r(x) with a rescaled R there (gpr.py:949-979), which is no Gaussian process's conditional law",
+         who, h->mode == BOGP_MODE_NOISY ? "noisy" : "noise-estimating");
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (h->n_t != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: one target only (the committed model has %d)", who, h->n_t);
+  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP || h->kernel == BOGP_KERNEL_MATERN_NU)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the %s kernel has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who,
+         h->kernel == BOGP_KERNEL_CUBIC ? "cubic" : (h->kernel == BOGP_KERNEL_GENEXP ? "generalized-exponential" : "general-nu Matern"));
+  if (d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  int e;
+  const size_t n_om = (size_t)L * d, n_w = (size_t)q * L, n_c = coef ? (size_t)q * N : 0;
+  if ((e = h->dpt_path.ensure(h, n_om + L + n_w + n_c))) return e;
+  if ((e = h->dpt_member.ensure(h, (size_t)B))) return e;
+  std::vector<double> hw(n_w), hc(n_c), hgamma(coef ? (size_t)N : 0);
+  if (coef) HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));  // gamma, read back once
+  const double scale = std::sqrt(2.0 * h->sigma2 / (double)L);  // bogp_sweep_thompson's own scaling of W
+  for (int j = 0; j < q; ++j)
+    for (int l = 0; l < L; ++l) hw[(size_t)j * L + l] = scale * weights[(size_t)l * q + j];
+  double* dom = h->dpt_path;
+  double* dph = dom + n_om;
+  double* dw = dph + L;
+  double* dc = dw + n_w;
+  HIPCHK(h, hipMemcpyAsync(dom, omega, n_om * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dph, phase, (size_t)L * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dw, hw.data(), n_w * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dpt_member, member, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  if (coef) {
+    HIPCHK(h, hipStreamSynchronize(st));  // gamma has arrived
+    for (int j = 0; j < q; ++j)
+      for (int n = 0; n < N; ++n) hc[(size_t)j * N + n] = hgamma[n] - coef[(size_t)n * q + j];
+    HIPCHK(h, hipMemcpyAsync(dc, hc.data(), n_c * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(h, hipStreamSynchronize(st));  // (the staging vectors and the caller's arrays are not needed past this point)
+  memset(pa, 0, sizeof(*pa));
+  pa->X = h->dX; pa->theta = h->dtheta; pa->member = h->dpt_member; pa->coef = coef ? dc : nullptr; pa->W = dw; pa->omega = dom; pa->phase = dph;
+  pa->N = N; pa->d = d; pa->L = L; pa->minimize = minimize ? 1 : 0; pa->beta = h->beta;
+  if (coef)
+    for (int j = 0; j < q; ++j) pa->bt[j] = coef[(size_t)N * q + j];
+  return BOGP_OK;
+}
+
+static PointCall path_call(const PointPathArgs* pa) {
+  static const int one_id = BOGP_ACQ_EI;  // a record sized like one criterion's with its gradient (the id itself is not evaluated)
+  return PointCall{1, &one_id, nullptr, 0.0, pa->minimize, true, nullptr, nullptr, nullptr, 0, pa};
+}
+
+extern "C" int bogp_point_eval_path(bogp_handle* h, const double* Xb, int B, const int* member, int q, int L, const double* omega,
+                                    const double* phase, const double* weights, const double* coef, int minimize, double* val_out,
+                                    double* grad_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_path";
+  if (!Xb || !val_out) FAIL(h, BOGP_ERR_INVALID, "%s: null points or null val_out", who);
+  PointPathArgs pa;
+  int e = path_request(h, who, B, member, q, L, omega, phase, weights, coef, minimize, &pa);
+  if (e) return e;
+  const int d = h->d;
+  const PointPlan pl = plan_of(h, B, 1, true);
+  if ((e = point_eval_wait(h, pl, path_call(&pa), Xb, B))) return e;
+  for (int b = 0; b < B; ++b) {
+    const double* o = h->hpin + (size_t)b * pl.rec_stride;
+    val_out[b] = o[0];
+    if (grad_out) memcpy(grad_out + (size_t)b * d, o + 3, (size_t)d * sizeof(double));
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_polish_path(bogp_handle* h, const double* X0, int B, const int* member, const double* lo, const double* hi, int q, int L,
+                                const double* omega, const double* phase, const double* weights, const double* coef, int minimize,
+                                int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_path";
+  if (!X0 || !lo || !hi || !Xout || !fout) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer", who);
+  PointPathArgs pa;
+  int e = path_request(h, who, B, member, q, L, omega, phase, weights, coef, minimize, &pa);
+  if (e) return e;
+  if ((e = polish_loop(h, who, path_call(&pa), X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals))) return e;
+  if (minimize)  // the loop climbs the criterion -path: back to the path's own sign
+    for (int b = 0; b < B; ++b) fout[b] = -1 * fout[b];
+  return BOGP_OK;
 }

@@ -37,15 +37,7 @@ namespace bogp {
 
 namespace {
 
-template <int KERNEL>
-__device__ __forceinline__ double point_dx_entry(double rv, double D, double e5, double theta_k, double diff) {
-  // d r / d x_k (corr_dx, gpr.py:600-661); the same expressions as k_point_corr (kernels_fit.hip)
-  if (KERNEL == BOGP_KERNEL_ABSEXP) return -1.0 * rv * theta_k * (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
-  if (KERNEL == BOGP_KERNEL_SE) return -2 * rv * (theta_k * diff);
-  if (KERNEL == BOGP_KERNEL_MATERN32) return D > 0.0 ? (diff * theta_k / D) * (-3.0 * D * e5) : 0.0;
-  if (KERNEL == BOGP_KERNEL_MATERN52) return (-(5.0 / 3.0) * (1.0 + 2.23606797749979 * D) * e5) * (theta_k * diff);
-  return D > 0.0 ? -diff * theta_k / D * rv : 0.0;
-}
+// (point_dx_entry, d r / d x_k, lives in bogp_device.h: k_point_path (kernels_point_path.hip) uses it too)
 
 // 64 training rows x 4 column slices per workgroup: every thread forms the weighted distance of its row (d terms, redundant
 // across the 4 slices -- cheaper than a shuffle), then its quarter of the row's NC entries for every pass.

@@ -130,7 +130,7 @@ def _strategy_of(masks, kw, crits=()) -> dict:
         return {}
     if any(optim.is_constrained(c) for c in crits):
         return {}
-    return {"strategy": _BATCH["strategy"]}
+    return dict(_BATCH)  # (the strategy; under install(thompson_polish=True) also polish=True)
 
 
 _ORIGINAL: dict = {}
@@ -660,7 +660,7 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
-            ehvi_thompson: bool = False):
+            ehvi_thompson: bool = False, thompson_polish: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -684,6 +684,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     "thompson": `optim.thompson_batch` -- one posterior sample path per point, each optimised over the candidates; the criteria
     supply model and direction only.  Fixed variables and constraints keep "topk" as under the believer; a model Thompson
     sampling refuses (a nugget or noise estimate, a polynomial trend, ...) raises NotImplementedError naming it.
+    `thompson_polish=True` (with `batch_strategy="thompson"`; alone it raises ValueError): every path's best rows are refined on the path
+    itself inside the search space's box (`optim.thompson_batch(polish=True)`, `bogp_polish_path`), so the proposals are points of the box.
 
     `ehvi_gradient=True` (an extension: the reference's EHVI has no gradient): the reference's `MOBO` with a device GP on a
     continuous space runs "BFGS", "sweep-BFGS" and "sweep-device-BFGS" on `bogp.EHVI(input_gradient=True)` -- the closed-form
@@ -786,9 +788,13 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         _EHVI["gradient"] = True
     if ehvi_thompson:
         _EHVI["thompson"] = True
+    if thompson_polish and batch_strategy != "thompson":
+        raise ValueError("thompson_polish=True refines the paths of batch_strategy='thompson'")
     _BATCH.clear()
     if batch_strategy != "topk":
         _BATCH["strategy"] = batch_strategy
+    if thompson_polish:
+        _BATCH["polish"] = True
     if restart_batch is not None:
         # the models `fmin` / the drivers build through the re-pointed GaussianProcess name fit with their MLE restarts in lock step
         # (surrogate.GaussianProcess(restart_batch=R)): `tell()` is most of a BO loop's wall time.  Opt-in: the

@@ -412,7 +412,8 @@ def sweep_topk_generated(criteria: Sequence, bounds, M: int, k: int, seed: int, 
 def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Optional[np.ndarray] = None, k: int = 8,
                  index_offset: Optional[int] = None, group=None, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
                  seed: Optional[int] = None, rank: Optional[int] = None, world: Optional[int] = None, masks=None, values=None,
-                 h: Optional[Callable] = None, g: Optional[Callable] = None, strategy: str = "topk"):
+                 h: Optional[Callable] = None, g: Optional[Callable] = None, strategy: str = "topk", polish: bool = False,
+                 n_starts: int = 8, max_iter: int = 50):
     """The q-point proposal of `ParallelBO._batch_arg_max_acquisition` (bayes_opt.py:100-115) in ONE posterior pass:
     q criteria (same model; they differ only in t / alpha) share (mu, MSE); each takes its best candidate that is
     neither already taken by an earlier criterion nor `np.isclose` to an evaluated point in `history`
@@ -430,12 +431,16 @@ def batch_argmax(criteria: Sequence, search_space, eval_budget: int, history: Op
     and `k` are not used then: a winner `np.isclose` to an evaluated point is left to the caller's padding, as the last
     fall-back above is.  "thompson" -- `thompson_batch`: one posterior sample path per criterion, each minimised (maximised) over
     the candidates as the criteria's `minimize` says; the criteria supply model and direction, their kind is not used, and
-    `history` and `k` keep their meaning above."""
+    `history` and `k` keep their meaning above; `polish`, `n_starts` and `max_iter` are `thompson_batch`'s (the local refinement of
+    every path behind its sweep) and belong to this strategy alone."""
+    if polish and strategy != "thompson":
+        raise ValueError("polish=True is the local refinement of strategy='thompson' (a criterion's own: optimizer='sweep+polish')")
     if strategy == "thompson":
         criteria = list(criteria)
+        more = dict(polish=True, n_starts=n_starts, max_iter=max_iter) if polish else {}
         return thompson_batch(criteria[0].model, search_space, eval_budget, len(criteria), Xs=Xs, design=design, seed=seed, history=history,
                               k=k, minimize=criteria[0].minimize, masks=masks, values=values, h=h, g=g, group=group, rank=rank, world=world,
-                              criteria=criteria)  # fmt: skip
+                              criteria=criteria, **more)  # fmt: skip
     if strategy == "believer":
         xs, fs = believer_batch(list(criteria), search_space, eval_budget, Xs=Xs, design=design, seed=seed, masks=masks, values=values,
                                 h=h, g=g, group=group, rank=rank, world=world)
@@ -633,10 +638,49 @@ def _thompson_picks(sizes, seed, k, hist, call):
             yield back, c, pick
 
 
+def _thompson_polished(model, eng, search_space, q, n_features, seed, hist, k, minimize, n_starts, max_iter):
+    """`thompson_batch(polish=True)` behind its checks: per call of at most 16 paths one sweep and ONE `polish_path` over every path's
+    first `n_starts` free rows; a path's list is its polished points, best first, then its unpolished rows in rank order."""
+    from . import thompson as _th
+
+    if n_starts < 1 or max_iter < 1:
+        raise ValueError("n_starts = %d, max_iter = %d: both at least 1" % (n_starts, max_iter))
+    bounds = np.array(search_space.bounds, dtype=float)
+    lo, hi = bounds[:, 0], bounds[:, 1]
+
+    def near(x, rows):
+        return len(rows) > 0 and bool(np.any(np.all(np.isclose(np.asarray(rows), x), axis=1)))
+
+    chosen_x, chosen_f = [], []
+    sizes = [min(_th.MAX_PATHS, q - a) for a in range(0, q, _th.MAX_PATHS)]
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, max(k, n_starts) + (0 if hist is None else len(hist)))))
+        dr = _th.draw(model, qb, n_features, sd)
+        out = eng.sweep_thompson(dr, minimize=minimize, k=kk)
+        idx, bx, bv = out["best_idx"], out["best_x"], out["best_val"]
+        free = [[r for r in range(kk) if idx[c, r] >= 0 and not (hist is not None and near(bx[c, r], hist))] for c in range(qb)]
+        starts = [(c, r) for c in range(qb) for r in free[c][:n_starts]]
+        xp, fp = np.empty((0, eng.d)), np.empty(0)
+        if starts:
+            xp, fp, _ = eng.polish_path(np.array([bx[c, r] for c, r in starts]), lo, hi, dr, out["coef"], [c for c, _ in starts],
+                                        minimize=minimize, max_evals=max_iter)
+        for c in range(qb):
+            mine = [i for i, (cc, _) in enumerate(starts) if cc == c]
+            mine.sort(key=lambda i: (fp[i] if minimize else -fp[i], i))  # best first, ties to the better sweep rank
+            cands = [(xp[i], float(fp[i])) for i in mine] + [(bx[c, r], float(-bv[c, r] if minimize else bv[c, r])) for r in free[c]]
+            if not cands:  # every listed row is an evaluated point: the argmax (the caller's check will pad)
+                cands = [(bx[c, 0], float(-bv[c, 0] if minimize else bv[c, 0]))]
+            seen = chosen_x if hist is None else list(hist) + chosen_x
+            x, f = next(((x, f) for x, f in cands if not near(x, seen)), cands[0])
+            chosen_x.append(np.asarray(x, dtype=float).tolist())
+            chosen_f.append(f)
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
                    Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None, k: int = 8,
                    minimize: bool = True, lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None,
-                   group=None, rank=None, world=None, criteria=None):
+                   group=None, rank=None, world=None, criteria=None, polish: bool = False, n_starts: int = 8, max_iter: int = 50):
     """A q-point proposal by Thompson sampling (`bogp_sweep_thompson`): q posterior sample paths of `model` (`bogp.thompson`:
     pathwise conditioning on `n_features` random Fourier features), each minimised -- maximised with `minimize=False` -- over the
     candidates.  ONE producer pass and one streaming pass serve 16 paths; the variance contraction never runs.  The candidates
@@ -645,8 +689,15 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
     to a row of `history` (`batch_argmax`'s rule), so the q proposals are q distinct rows.  More than 16 paths run in calls of 16
     with seeds derived from `seed` (`thompson.batch_seeds`).  Returns (xopt: tuple of q lists, fopt: tuple of q floats) in
     `batch_argmax`'s format; fopt is the path's value at its proposal.
+    `polish=True`: the sweep is followed by a local refinement ON THE PATH (`bogp_polish_path`: value and input gradient of a path
+    in one launch, `k_polish_step` behind it).  Every call sweeps with enough ranks for every path's first `n_starts` rows that are
+    not `np.isclose` to a row of `history`; ONE `polish_path` call refines them all inside the box `search_space.bounds` (B = paths x
+    n_starts, at most `max_iter` evaluations each); a path takes its best polished point, falls back down its polished list and then
+    to its unpolished pick when that point is `np.isclose` to a row of `history` or to an earlier path's proposal.  The proposals
+    are then points of the box, not candidate rows.
     Refused (NotImplementedError): a forest model, EHVI / several targets, a lift, fixed variables, constraints, polynomial
-    trends, more than one rank, the cubic and generalized-exponential kernels, the noisy and noise-estimating modes."""
+    trends, more than one rank, the cubic and generalized-exponential kernels, the noisy and noise-estimating modes; with
+    `polish=True` also the general-nu Matern kernel (no input-derivative)."""
     from . import thompson as _th
 
     if _forest.is_forest_model(model):
@@ -657,8 +708,13 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
         raise NotImplementedError("EHVI / several targets have no Thompson batches")
     if criteria is not None and any(is_constrained(c) for c in criteria):
         raise NotImplementedError("modelled constraints (bogp.Constrained) have no Thompson batches: strategy='topk' serves them")
-    _, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of, q, k)  # (state_of: not fitted, mode, trend, targets, kernel)
+    st, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of, q, k)  # (state_of: not fitted, mode, trend, targets, kernel)
+    if polish and st.kernel == _lib.KERNEL_MATERN_NU:
+        raise NotImplementedError("thompson_batch(polish=True) with the general-nu Matern kernel: its correlation has no input-derivative "
+                                  "(corr_dx leaves it undefined in the reference, gpr.py:655-658)")  # fmt: skip
     eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
+    if polish:
+        return _thompson_polished(model, eng, search_space, q, n_features, seed, hist, k, minimize, int(n_starts), int(max_iter))
 
     def call(qb, sd, kk):  # a path lists its ranks in order; every fall-back exhausted, it keeps the argmax
         out = eng.sweep_thompson(_th.draw(model, qb, n_features, sd), minimize=minimize, k=kk)

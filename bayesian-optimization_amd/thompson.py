@@ -184,6 +184,61 @@ def paths_numpy(model, dr, X, conditioned=True):
     return (mu[:, None] + z - r @ gt - bt).T, (gt, bt)
 
 
+def correlation_dx(st, A, B):
+    """d k(A_i, B_j) / d A_ik in the reference's expressions (corr_dx, gpr.py:600-661, the D = 0 conventions included), (len(A),
+    len(B), d); the five kernels that have one."""
+    diff = np.asarray(A, dtype=float)[:, None, :] - np.asarray(B, dtype=float)[None, :, :]
+    r = correlation(st, A, B)[:, :, None]
+    if st.kernel == _lib.KERNEL_ABSEXP:
+        return -r * st.theta * np.sign(diff)
+    if st.kernel == _lib.KERNEL_SE:
+        return -2.0 * r * (st.theta * diff)
+    D = np.sqrt((diff * diff * st.theta).sum(-1))[:, :, None]
+    if st.kernel == _lib.KERNEL_MATERN32:
+        return -3.0 * np.exp(-math.sqrt(3.0) * D) * (st.theta * diff)
+    if st.kernel == _lib.KERNEL_MATERN52:
+        return -(5.0 / 3.0) * (1.0 + math.sqrt(5.0) * D) * np.exp(-math.sqrt(5.0) * D) * (st.theta * diff)
+    if st.kernel == _lib.KERNEL_MATERN12:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(D > 0.0, -(st.theta * diff) / D * r, 0.0)
+    raise NotImplementedError("the correlation of kernel id %r has no input-derivative (corr_dx leaves it undefined in the reference, "
+                              "gpr.py:655-658)" % (st.kernel,))  # fmt: skip
+
+
+def path_grad_numpy(model, dr, X, members, conditioned=True, parts=False):
+    """The dense float64 restatement of `bogp_point_eval_path`: value (B,) and input gradient (B, d) of path members[b] at row b of
+    X, with `paths_numpy`'s own gt, bt:
+
+        v   = beta - bt_j + sum_n c_j[n] r_n(x) + sum_l Wt[l, j] cos(omega_l . x + phi_l),      c_j = gamma - gt_j, Wt = sqrt(2 sigma2 / L) W
+        g_k = sum_n c_j[n] d r_n / d x_k - sum_l Wt[l, j] sin(omega_l . x + phi_l) omega_lk
+
+    `parts=True` adds a dict of the sums of the ABSOLUTE terms: A_v (B,) of the value, A_g (B, d) of every gradient component, and the
+    conditioning and feature shares of each (cond_v, feat_v, cond_g, feat_g)."""
+    st = state_of(model)
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    members = np.asarray(members, dtype=int).ravel()
+    N, L = len(st.X), len(dr.phase)
+    Wt = math.sqrt(2.0 * st.sigma2 / L) * dr.weights[:, members]  # (L, B)
+    ph = X @ dr.omega.T + dr.phase  # (B, L)
+    if conditioned:
+        _, (gt, bt) = paths_numpy(st, dr, st.X[:1], True)
+        R = correlation(st, st.X, st.X) + np.diag(st.nugget)
+        c = (np.linalg.solve(R, st.y - st.beta)[:, None] - gt)[:, members]  # (N, B)
+        r, rdx = correlation(st, X, st.X), correlation_dx(st, X, st.X)
+        bt = bt[members]
+    else:
+        c, r, rdx, bt = np.zeros((N, len(X))), np.zeros((len(X), N)), np.zeros((len(X), N, X.shape[1])), np.zeros(len(X))
+    val = st.beta - bt + np.einsum("bn,nb->b", r, c) + np.einsum("bl,lb->b", np.cos(ph), Wt)
+    u = -np.sin(ph) * Wt.T  # (B, L)
+    grad = np.einsum("nb,bnk->bk", c, rdx) + u @ dr.omega
+    if not parts:
+        return val, grad
+    cond_v, feat_v = np.einsum("bn,nb->b", np.abs(r), np.abs(c)), np.abs(Wt).sum(axis=0)
+    cond_g, feat_g = np.einsum("nb,bnk->bk", np.abs(c), np.abs(rdx)), np.abs(Wt).T @ np.abs(dr.omega)
+    return val, grad, dict(A_v=abs(st.beta) + np.abs(bt) + cond_v + feat_v, A_g=cond_g + feat_g, cond_v=cond_v, feat_v=feat_v, cond_g=cond_g,
+                           feat_g=feat_g)  # fmt: skip
+
+
 def moments_numpy(model, X):
     """mu (M,) and MSE (M,) of the predictor the paths are conditioned on (gpr.py:486-510, unclipped), densely."""
     st = state_of(model)

@@ -864,6 +864,33 @@ int bogp_polish_ehvi_constrained(bogp_handle* h, const double* X0, int B, const 
                                  const double* lower, const double* upper, int n_con, const double* lo, const double* hi,
                                  int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals);
 
+/* ---- a posterior sample path and its input gradient at B points; the device polish of Thompson batches ----------------------------
+ * A single-objective path of bogp_sweep_thompson's draw,
+ *   path_j(x) = beta - b_j + r(x) . (gamma - g_j) + sqrt(2 sigma2 / L) sum_l W[l][j] cos(omega_l . x + phase_l)
+ * is linear in r(x) plus a cosine sum: value and gradient cost N d + L d operations a point and ONE launch a batch (csrc/
+ * kernels_point_path.hip) -- no variance, no L^-1, no N^2 term.  d r_n / d x_k is bogp_point_eval's (the reference's corr_dx, the
+ * D = 0 conventions included).  Point b follows path member[b]; identical inputs give identical bits, and a point's value and
+ * gradient do not depend on B, on where the point stands or on the members beside it.
+ *   omega, phase, weights   L x d, L, L x q: the arrays bogp_sweep_thompson took (q in 1 .. BOGP_MAX_PATHS, L as there)
+ *   coef                    (N + 1) x q, exactly what its coef_out returned (g, then b); NULL: the prior paths beta + z_j
+ *   member                  B ints in [0, q); B in 1 .. BOGP_MAX_PATH_POINTS
+ *   minimize                the polish climbs -path; values and gradients are returned in the path's OWN sign either way
+ *   `point_eval_path`       Xb: B x d (host).  val_out (B), grad_out (B x d, may be NULL).
+ *   `polish_path`           bogp_polish's loop, state, stop rules and read-back on this evaluation, two launches an iteration: X0, lo, hi
+ *                           (the box), max_evals, pgtol, factr, Xout, n_evals as there; fout[b] = path_member[b](Xout[b]), which is no
+ *                           worse, in the direction `minimize` names, than the path at X0[b] clipped into the box.
+ * The operands are formed on the host (c_j = gamma - g_j, the scaled weights) and uploaded once per call.
+ * BOGP_ERR_INVALID: no committed model, q, L or B out of range, a member outside [0, q), a null required array, a non-finite entry
+ * in omega, phase, weights or coef, lo > hi, max_evals <= 0.  BOGP_ERR_UNSUPPORTED: a forest on the handle; the noisy and
+ * noise-estimating modes; a polynomial basis; more than one target; the cubic, generalized-exponential and general-nu kernels (no
+ * corr_dx); d > BOGP_MAX_DIM; a lift; more than one rank.  Candidates and later sweeps are unaffected. */
+#define BOGP_MAX_PATH_POINTS 4096
+int bogp_point_eval_path(bogp_handle* h, const double* Xb, int B, const int* member, int q, int L, const double* omega, const double* phase,
+                         const double* weights, const double* coef, int minimize, double* val_out, double* grad_out);
+int bogp_polish_path(bogp_handle* h, const double* X0, int B, const int* member, const double* lo, const double* hi, int q, int L,
+                     const double* omega, const double* phase, const double* weights, const double* coef, int minimize, int max_evals,
+                     double pgtol, double factr, double* Xout, double* fout, int* n_evals);
+
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
  * this is the cross-rank half of the new inner maximiser behind acquisition/optim/__init__.py:55-153.  One process per
