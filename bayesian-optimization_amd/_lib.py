@@ -136,6 +136,10 @@ SIGNATURES = {
     "bogp_point_eval_path": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     "bogp_polish_path": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, _dp, _ip]),
+    "bogp_point_eval_path_hvi": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                           _dp, _dp, _dp, _dp]),
+    "bogp_polish_path_hvi": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp,
+                                       _dp, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1468,6 +1472,46 @@ class Engine:
         self._path_call(self._lib.bogp_polish_path, _ptr(X0), B, member.ctypes.data_as(_ip), _ptr(lo), _ptr(hi), q, L, _ptr(omega), _ptr(phase),
                         _ptr(weights), _ptr(coef), int(bool(minimize)), int(max_evals), float(pgtol), float(factr), _ptr(Xo), _ptr(fo),
                         ne.ctypes.data_as(_ip))  # fmt: skip
+        return Xo, fo, ne
+
+    def _path_hvi_operands(self, draw, coef, members, lower, upper, B):
+        """A joint-path call's operands as the entries take them: (member (B,) int32, m, q, L, omega, phase, weights, coef (N, q m), C,
+        lower, upper).  `coef`: what a `sweep_thompson_ehvi` returned for this draw."""
+        lower, upper = self._cells(lower, upper)
+        C_, m = lower.shape
+        L, omega, phase, weights, _ = self._thompson_draw(draw)
+        qm = weights.shape[1]
+        if qm % m:
+            raise ValueError("the draw has %d columns, no multiple of the %d targets of the cells" % (qm, m))
+        member = np.ascontiguousarray(members, dtype=np.int32).ravel()
+        if len(member) != B:
+            raise ValueError("members must name one batch member for each of the %d points" % B)
+        coef = _f64(coef)
+        if coef.shape != (self.N, qm):
+            raise ValueError("coef must be the (%d, %d) array of sweep_thompson_ehvi" % (self.N, qm))
+        return member.ctypes.data_as(_ip), int(m), qm // m, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(coef), int(C_), _ptr(lower), _ptr(upper)
+
+    def point_eval_path_hvi(self, X, draw, coef, members, lower, upper, jacobian: bool = True):
+        """The hypervolume improvement of JOINT sample paths of the committed multi-target model and its input gradient at the rows of `X`
+        (B x d) in ONE launch (bogp_point_eval_path_hvi): row b on batch member members[b] of `draw` (the arrays `sweep_thompson_ehvi`
+        took), conditioned by `coef` (what it returned), over the cells (lower, upper).  Returns (hvi (B,), grad (B, d), y (B, m): the
+        member's m path values, jac (B, m, d): their input gradients, or None with `jacobian=False`)."""
+        X = self._rows(X)
+        B, d = X.shape[0], self.d
+        ops = self._path_hvi_operands(draw, coef, members, lower, upper, B)
+        m = ops[1]
+        hvi, grad, y, jac = np.empty(B), np.empty((B, d)), np.empty((B, m)), np.empty((B, m, d)) if jacobian else None
+        self._path_call(self._lib.bogp_point_eval_path_hvi, _ptr(X), B, *ops, _ptr(hvi), _ptr(grad), _ptr(y), _ptr(jac))
+        return hvi, grad, y, jac
+
+    def polish_path_hvi(self, starts, lo, hi, draw, coef, members, lower, upper, max_evals: int = 50, pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local maximisation of the hypervolume improvement of joint sample paths inside the box
+        (bogp_polish_path_hvi): start b climbs the HVI of member members[b]'s draw; two launches an iteration.  Returns (points (B, d),
+        HVI (B,), evaluations used (B,)); HVI[b] is no smaller than at starts[b] clipped into the box."""
+        X0, lo, hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), lo, hi, "lo / hi")
+        ops = self._path_hvi_operands(draw, coef, members, lower, upper, B)
+        self._path_call(self._lib.bogp_polish_path_hvi, _ptr(X0), B, ops[0], _ptr(lo), _ptr(hi), *ops[1:], int(max_evals), float(pgtol),
+                        float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))  # fmt: skip
         return Xo, fo, ne
 
     feasibility_grad = staticmethod(feasibility_grad)

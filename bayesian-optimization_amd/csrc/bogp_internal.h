@@ -928,5 +928,27 @@ struct PointPathArgs {
   unsigned long long done_seq;
 };
 hipError_t launch_point_path(int kernel, const PointPathArgs& a, int B, hipStream_t st);
+// hypervolume improvement of a JOINT sample path of m objectives and its input gradient at B points (kernels_point_path_hvi.hip): ONE
+// launch forms y_t = path_{j,t}(x) = beta + sum_n coef[j m + t][n] r_n(x) + sum_l W[j m + t][l] cos(omega_l . x + phase_l), t < m, their
+// Jacobian, HVI(y) over the C cells and its gradient
+struct PointPathHviArgs {
+  const double* X;       // N x d training points, row-major
+  const double* theta;   // d
+  const double* Xb;      // B x d points (device)
+  const int* member;     // [B] the batch member of each point, in [0, q)
+  const double* coef;    // [q m][N] gamma_t - g_{j,t}, column-major in bogp_sweep_thompson_ehvi's column order j m + t
+  const double* W;       // [q m][L] weights times sqrt(2 sigma2_t / L), the same order
+  const double* omega;   // [L][d]
+  const double* phase;   // [L]
+  const double* lower;   // [C][m] cells (device)
+  const double* upper;
+  double* out;           // [B][rec_stride]: HVI, 0, HVI, grad (d), 0 (d), grad (d) -- k_point_finish's record with q = 1
+  double* mom;           // null or [B][mom_stride]: y (m), then J (m x d) where want_jac
+  int N, d, L, m, C, rec_stride, mom_stride, want_jac;
+  double beta;
+  unsigned long long* done_flag;  // as PointTriArgs
+  unsigned long long done_seq;
+};
+hipError_t launch_point_path_hvi(int kernel, const PointPathHviArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

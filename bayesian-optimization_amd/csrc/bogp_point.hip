@@ -3,7 +3,8 @@
 // bogp_point_eval_ehvi, bogp_polish_ehvi, and of its feasibility-weighted finish (kernels_point_constrained.hip):
 // bogp_point_eval_constrained, bogp_polish_constrained, and of the product of the two (kernels_point_ehvi_constrained.hip):
 // bogp_point_eval_ehvi_constrained, bogp_polish_ehvi_constrained, and of the one-launch evaluation of a posterior sample path
-// (kernels_point_path.hip): bogp_point_eval_path, bogp_polish_path.  See include/bogp.h for the contracts.
+// (kernels_point_path.hip): bogp_point_eval_path, bogp_polish_path, and of a JOINT path's hypervolume improvement
+// (kernels_point_path_hvi.hip): bogp_point_eval_path_hvi, bogp_polish_path_hvi.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -76,6 +77,7 @@ struct PointCall {
   const PointEhviConstrainedArgs* ec;
   size_t mom_stride;  // doubles per point of the m-target finishes' second block, written behind the B records; 0: not wanted
   const PointPathArgs* path;  // the staged operands of a sample-path call (its points, records and done word are filled in per launch)
+  const PointPathHviArgs* path_hvi;  // ... of a joint-path call: ONE launch of k_point_path_hvi; mom_stride doubles a point for y and J
 };
 
 // the EHVI request: a record sized like one criterion's with its gradient (the id itself is not evaluated)
@@ -122,6 +124,13 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, co
     PointPathArgs pa = *c.path;
     pa.Xb = dXb; pa.out = out; pa.rec_stride = pl.rec_stride; pa.done_flag = done_flag; pa.done_seq = done_seq;
     HIPCHK(h, launch_point_path(h->kernel, pa, B, st));
+    return BOGP_OK;
+  }
+  if (c.path_hvi) {
+    PointPathHviArgs pa = *c.path_hvi;
+    pa.Xb = dXb; pa.out = out; pa.rec_stride = pl.rec_stride; pa.done_flag = done_flag; pa.done_seq = done_seq;
+    pa.mom = c.mom_stride ? out + (size_t)B * pl.rec_stride : nullptr; pa.mom_stride = (int)c.mom_stride;
+    HIPCHK(h, launch_point_path_hvi(h->kernel, pa, B, st));
     return BOGP_OK;
   }
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
@@ -308,7 +317,7 @@ int point_eval_wait(bogp_handle* h, const PointPlan& pl, const PointCall& call, 
   // the finishing workgroups write straight into pinned host memory: one stream synchronisation, no copy command
   if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
   const double* dXb = nullptr;
-  if (B > 1 || d > BOGP_POINT_ARG_D || call.path) {  // (k_point_path reads its points from device memory only)
+  if (B > 1 || d > BOGP_POINT_ARG_D || call.path || call.path_hvi) {  // (the path kernels read their points from device memory only)
     if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
     HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     dXb = h->dpt_Xb;
@@ -717,4 +726,130 @@ extern "C" int bogp_polish_path(bogp_handle* h, const double* X0, int B, const i
   if (minimize)  // the loop climbs the criterion -path: back to the path's own sign
     for (int b = 0; b < B; ++b) fout[b] = -1 * fout[b];
   return BOGP_OK;
+}
+
+// ---- hypervolume improvement of a JOINT sample path and its input gradient at B points (kernels_point_path_hvi.hip) ------------------
+// Member j's m paths of bogp_sweep_thompson_ehvi's draw, path_{j,t}(x) = beta + r(x) . (gamma_t - g_{j,t}) + z_{j,t}(x), scored by the
+// hypervolume their vector adds over the cells: ONE launch a batch of points.  What both entries refuse: bogp_sweep_thompson_ehvi's
+// list in its words and order, with bogp_point_eval_path's where that one has more (B, member, coef, the general-nu kernel, d).  Then the
+// cells (ehvi_cells_resident: equal cells are not uploaded again) and the operands, formed on the host and uploaded ONCE: the columns
+// c_{j,t} = gamma_t - g_{j,t} and Wt = sqrt(2 sigma2_t / L) W, column-major in the column order j m + t, so that a point's workgroup reads
+// its member's m columns of each as m contiguous runs.
+static int path_hvi_request(bogp_handle* h, const char* who, int B, const int* member, int m, int q, int L, const double* omega,
+                            const double* phase, const double* weights, const double* coef, int C, const double* lower, const double* upper,
+                            PointPathHviArgs* pa) {
+  if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior paths to draw", who);
+  if (!h->committed) FAIL(h, BOGP_ERR_INVALID, "%s: no committed model: call bogp_commit first", who);
+  if (h->lift_D > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: a lift is set (bogp_lift_set): call bogp_lift_clear first", who);
+  if (h->p != 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: constant trend basis only (the committed basis has %d columns)", who, h->p);
+  if (h->n_t < 2) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has one target and so no front: bogp_point_eval_path serves it", who);
+  if (m != h->n_t) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d but the committed model has %d targets", who, m, h->n_t);
+  if (m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d outside [2, %d]", who, m, BOGP_MAX_TARGETS);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  if (q < 1 || q * m > BOGP_MAX_PATHS) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d members of %d targets: 1 <= q and q m <= %d columns", who, q, m, BOGP_MAX_PATHS);
+  if (L < 16 || L > BOGP_MAX_FEATURES || L % 16 != 0)
+    FAIL(h, BOGP_ERR_INVALID, "%s: L = %d: a multiple of 16 in [16, %d] is required", who, L, BOGP_MAX_FEATURES);
+  if (B < 1 || B > BOGP_MAX_PATH_POINTS) FAIL(h, BOGP_ERR_INVALID, "%s: B = %d outside [1, %d]", who, B, BOGP_MAX_PATH_POINTS);
+  if (!member || !omega || !phase || !weights || !coef) FAIL(h, BOGP_ERR_INVALID, "%s: member, omega, phase, weights and coef must be non-null", who);
+  for (int b = 0; b < B; ++b)
+    if (member[b] < 0 || member[b] >= q) FAIL(h, BOGP_ERR_INVALID, "%s: member[%d] = %d outside [0, %d)", who, b, member[b], q);
+  int e;
+  if ((e = ehvi_cells_resident(h, who, m, C, lower, upper))) return e;
+  const int N = h->N, d = h->d, Np = h->Np, qm = q * m;
+  const auto finite = [](const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(v[i])) return false;
+    return true;
+  };
+  if (!finite(omega, (size_t)L * d)) FAIL(h, BOGP_ERR_INVALID, "%s: omega has a non-finite entry", who);
+  if (!finite(phase, (size_t)L)) FAIL(h, BOGP_ERR_INVALID, "%s: phase has a non-finite entry", who);
+  if (!finite(weights, (size_t)L * qm)) FAIL(h, BOGP_ERR_INVALID, "%s: weights has a non-finite entry", who);
+  if (!finite(coef, (size_t)N * qm)) FAIL(h, BOGP_ERR_INVALID, "%s: coef has a non-finite entry", who);
+  if (h->mode != BOGP_MODE_NOISELESS)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: %s mode: the reference pairs an unscaled r(x) with a rescaled R there (gpr.py:949-979), which is no Gaussian process's conditional law",
+         who, h->mode == BOGP_MODE_NOISY ? "noisy" : "noise-estimating");
+  if (h->kernel == BOGP_KERNEL_CUBIC || h->kernel == BOGP_KERNEL_GENEXP)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: no spectral draw is defined for the %s kernel", who, h->kernel == BOGP_KERNEL_CUBIC ? "cubic" : "generalized-exponential");
+  if (h->kernel == BOGP_KERNEL_MATERN_NU)
+    FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the general-nu Matern kernel has no input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)", who);
+  if (d > BOGP_POINT_MAX_D) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: at most %d input dimensions", who, BOGP_POINT_MAX_D);
+  if (h->comm_world > 1) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: runs on one rank (the communicator has %d)", who, h->comm_world);
+
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  const size_t n_om = (size_t)L * d, n_w = (size_t)qm * L, n_c = (size_t)qm * N;
+  if ((e = h->dpt_path.ensure(h, n_om + L + n_w + n_c))) return e;
+  if ((e = h->dpt_member.ensure(h, (size_t)B))) return e;
+  std::vector<double> hw(n_w), hc(n_c), hgamma((size_t)m * Np);
+  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base.ptr, hgamma.size() * sizeof(double), hipMemcpyDeviceToHost, st));  // gamma_t, read back once
+  for (int t = 0; t < m; ++t) {
+    const double scale = std::sqrt(2.0 * h->sigma2_t[t] / (double)L);  // bogp_sweep_thompson_ehvi's own scaling of W
+    for (int j = 0; j < q; ++j)
+      for (int l = 0; l < L; ++l) hw[(size_t)(j * m + t) * L + l] = scale * weights[(size_t)l * qm + j * m + t];
+  }
+  double* dom = h->dpt_path;
+  double* dph = dom + n_om;
+  double* dw = dph + L;
+  double* dc = dw + n_w;
+  HIPCHK(h, hipMemcpyAsync(dom, omega, n_om * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dph, phase, (size_t)L * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(dw, hw.data(), n_w * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(h->dpt_member, member, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // gamma has arrived
+  for (int j = 0; j < q; ++j)
+    for (int t = 0; t < m; ++t) {
+      const int c = j * m + t;
+      for (int n = 0; n < N; ++n) hc[(size_t)c * N + n] = hgamma[(size_t)t * Np + n] - coef[(size_t)n * qm + c];
+    }
+  HIPCHK(h, hipMemcpyAsync(dc, hc.data(), n_c * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // (the staging vectors and the caller's arrays are not needed past this point)
+  memset(pa, 0, sizeof(*pa));
+  pa->X = h->dX; pa->theta = h->dtheta; pa->member = h->dpt_member; pa->coef = dc; pa->W = dw; pa->omega = dom; pa->phase = dph;
+  pa->lower = h->dehvi_cells; pa->upper = h->dehvi_cells + (size_t)C * m;
+  pa->N = N; pa->d = d; pa->L = L; pa->m = m; pa->C = C; pa->beta = h->beta;
+  return BOGP_OK;
+}
+
+static PointCall path_hvi_call(const PointPathHviArgs* pa, size_t mom_stride) {
+  static const int one_id = BOGP_ACQ_EI;  // a record sized like one criterion's with its gradient (the id itself is not evaluated)
+  return PointCall{1, &one_id, nullptr, 0.0, 0, true, nullptr, nullptr, nullptr, mom_stride, nullptr, pa};
+}
+
+extern "C" int bogp_point_eval_path_hvi(bogp_handle* h, const double* Xb, int B, const int* member, int m, int q, int L, const double* omega,
+                                        const double* phase, const double* weights, const double* coef, int C, const double* lower,
+                                        const double* upper, double* hvi_out, double* grad_out, double* y_out, double* jac_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_path_hvi";
+  if (!Xb || !hvi_out) FAIL(h, BOGP_ERR_INVALID, "%s: null points or null hvi_out", who);
+  PointPathHviArgs pa;
+  int e = path_hvi_request(h, who, B, member, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
+  if (e) return e;
+  const int d = h->d;
+  const size_t md = (size_t)m * d;
+  pa.want_jac = jac_out ? 1 : 0;
+  const size_t mom_stride = (y_out || jac_out) ? m + (jac_out ? md : 0) : 0;
+  const PointPlan pl = plan_of(h, B, 1, true);
+  if ((e = point_eval_wait(h, pl, path_hvi_call(&pa, mom_stride), Xb, B))) return e;
+  const double* mom = h->hpin + (size_t)B * pl.rec_stride;
+  for (int b = 0; b < B; ++b) {
+    const double* o = h->hpin + (size_t)b * pl.rec_stride;
+    hvi_out[b] = o[0];
+    if (grad_out) memcpy(grad_out + (size_t)b * d, o + 3, (size_t)d * sizeof(double));
+    if (y_out) memcpy(y_out + (size_t)b * m, mom + (size_t)b * mom_stride, (size_t)m * sizeof(double));
+    if (jac_out) memcpy(jac_out + (size_t)b * md, mom + (size_t)b * mom_stride + m, md * sizeof(double));
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_polish_path_hvi(bogp_handle* h, const double* X0, int B, const int* member, const double* lo, const double* hi, int m, int q,
+                                    int L, const double* omega, const double* phase, const double* weights, const double* coef, int C,
+                                    const double* lower, const double* upper, int max_evals, double pgtol, double factr, double* Xout,
+                                    double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_path_hvi";
+  if (!X0 || !lo || !hi || !Xout || !fout) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer", who);
+  PointPathHviArgs pa;
+  int e = path_hvi_request(h, who, B, member, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
+  if (e) return e;
+  return polish_loop(h, who, path_hvi_call(&pa, 0), X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }

@@ -235,7 +235,8 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
     if strategy == "thompson":
         # install(ehvi_thompson=True): one joint draw of the objectives per point; the criterion supplies model, reference point and cells
         xs, fs = optim.ehvi_thompson_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
-                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self))  # fmt: skip
+                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self),
+                                           **(dict(polish=True) if _EHVI.get("thompson_polish") else {}))  # fmt: skip
         return tuple(xs), tuple(fs)
     xs, fs = optim.ehvi_believer_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
                                        design=optim.DEVICE_DESIGNS.get(optimizer))  # fmt: skip
@@ -660,7 +661,7 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
-            ehvi_thompson: bool = False, thompson_polish: bool = False):
+            ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -743,7 +744,12 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     run's history, for a device GP, an inner optimiser of the sweep family, a continuous space, nothing fixed and no cheap h / g;
     every other configuration takes the route it took before.  No variance contraction runs: a batch costs about one EHVI sweep
     where the believer costs q.  A model that Thompson sampling refuses (a nugget or noise estimate, ...) raises
-    NotImplementedError naming it."""
+    NotImplementedError naming it.
+    `ehvi_thompson_polish=True` (with `ehvi_thompson=True`; alone it raises ValueError): every member's best improving rows are refined
+    on its own draw inside the search space's box (`optim.ehvi_thompson_batch(polish=True)`, `bogp_polish_path_hvi`), so the proposals
+    are points of the box."""
+    if ehvi_thompson_polish and not ehvi_thompson:
+        raise ValueError("ehvi_thompson_polish=True refines the members of ehvi_thompson=True")
     if ehvi_thompson and batch_strategy == "believer":
         raise ValueError("ehvi_thompson=True and batch_strategy='believer' name two batch strategies for one step: choose one")
     if constrained_mobo_batches not in ("topk", "believer"):
@@ -788,6 +794,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         _EHVI["gradient"] = True
     if ehvi_thompson:
         _EHVI["thompson"] = True
+    if ehvi_thompson_polish:
+        _EHVI["thompson_polish"] = True
     if thompson_polish and batch_strategy != "thompson":
         raise ValueError("thompson_polish=True refines the paths of batch_strategy='thompson'")
     _BATCH.clear()

@@ -783,10 +783,48 @@ def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def _ehvi_thompson_polished(model, eng, search_space, q, m, n_features, seed, hist, k, lower, upper, n_starts, max_iter):
+    """`ehvi_thompson_batch(polish=True)` behind its checks: per call of at most 16 // m members one sweep and ONE `polish_path_hvi` over
+    every member's first `n_starts` free improving rows; a member's list is its polished points, best first, then its unpolished rows
+    in `merge_ranks`' order."""
+    from . import thompson as _th
+
+    bounds = np.array(search_space.bounds, dtype=float)
+    lo, hi = bounds[:, 0], bounds[:, 1]
+
+    def near(x, rows):
+        return rows is not None and len(rows) > 0 and bool(np.any(np.all(np.isclose(np.asarray(rows), x), axis=1)))
+
+    chosen_x, chosen_f = [], []
+    per_call = _th.MAX_PATHS // m
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, max(k, n_starts) + (0 if hist is None else len(hist)) + len(chosen_x))))
+        dr = _th.draw_multi(model, qb, n_features, sd)
+        out = eng.sweep_thompson_ehvi(dr, qb, lower, upper, k=kk)
+        idx, bx, bv = out["best_idx"], out["best_x"], out["best_val"]
+        free = [[(w, r) for _, w, r in _th.merge_ranks(bv[c], idx[c], kk) if not near(bx[c, w, r], hist)] for c in range(qb)]
+        starts = [(c, r) for c in range(qb) for r in [r for w, r in free[c] if w == 0][:n_starts]]  # improving rows only: elsewhere the gradient is 0
+        xp, fp = np.empty((0, eng.d)), np.empty(0)
+        if starts:
+            xp, fp, _ = eng.polish_path_hvi(np.array([bx[c, 0, r] for c, r in starts]), lo, hi, dr, out["coef"], [c for c, _ in starts], lower,
+                                            upper, max_evals=max_iter)  # fmt: skip
+        for c in range(qb):
+            mine = sorted((i for i, (cc, _) in enumerate(starts) if cc == c), key=lambda i: (-fp[i], i))  # best first, ties to the better sweep rank
+            cands = [(xp[i], float(fp[i])) for i in mine] + [(bx[c, w, r], float(bv[c, w, r])) for w, r in free[c]]
+            if not cands:  # every listed row is an evaluated point: the first B rank (the caller's check will pad)
+                cands = [(bx[c, 1, 0], float(bv[c, 1, 0]))]
+            seen = chosen_x if hist is None else list(hist) + chosen_x
+            x, f = next(((x, f) for x, f in cands if not near(x, seen)), cands[0])
+            chosen_x.append(np.asarray(x, dtype=float).tolist())
+            chosen_f.append(f)
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
                         Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None, k: int = 8,
                         lift=None, masks=None, values=None, h: Optional[Callable] = None, g: Optional[Callable] = None, group=None,
-                        rank=None, world=None):
+                        rank=None, world=None, polish: bool = False, n_starts: int = 8, max_iter: int = 50):
     """A q-point proposal for a multi-objective run by Thompson sampling (`bogp_sweep_thompson_ehvi`): per proposed point ONE joint
     draw of the m objectives of `criterion.model` (`thompson.draw_multi`), and among the candidates the row whose DRAWN vector adds
     the most hypervolume to the front -- the row nearest to the region the front does not dominate (scaled Chebyshev distance)
@@ -797,8 +835,16 @@ def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_fea
     earlier member took and that is not `np.isclose` to a row of `history` (`thompson_batch`'s rule), so the q proposals are q
     distinct rows.  Returns (xopt: tuple of q lists, fopt: tuple of q floats) in `batch_argmax`'s format; fopt is the hypervolume
     the member's draw adds at its proposal (A), or minus its distance (B) where no listed row improved.
+    `polish=True`: the sweep is followed by a local refinement ON THE DRAW (`bogp_polish_path_hvi`: the m paths, their Jacobian, the
+    hypervolume improvement and its input gradient in one launch, `k_polish_step` behind it).  Every call sweeps with enough ranks
+    for every member's first `n_starts` improving rows (A ranks) that are not `np.isclose` to a row of `history`; ONE
+    `polish_path_hvi` call refines them all inside the box `search_space.bounds` (at most `max_iter` evaluations each); a member
+    takes its best polished point and falls back down its polished list, then to its unpolished rows, when that point is
+    `np.isclose` to a row of `history` or to an earlier proposal.  A member whose draw improves nowhere has only B rows (HVI = 0 and a
+    zero gradient there): it keeps its unpolished proposal.  The proposals are then points of the box, not candidate rows.
     TypeError: a criterion that is not `bogp.EHVI`.  Refused (NotImplementedError): `ConstrainedEHVI`, a forest model, a lift,
-    fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model; with
+    `polish=True` also the general-nu Matern kernel (no input-derivative)."""
     from . import thompson as _th
 
     if is_constrained_ehvi(criterion):
@@ -814,8 +860,16 @@ def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_fea
         raise ValueError("k = %d: every member lists at least one row" % k)
     if st.y.shape[1] != criterion.n_obj:
         raise ValueError("the model has %d targets, the criterion %d objectives" % (st.y.shape[1], criterion.n_obj))
+    if polish and st.kernel == _lib.KERNEL_MATERN_NU:
+        raise NotImplementedError("ehvi_thompson_batch(polish=True) with the general-nu Matern kernel: its correlation has no input-derivative "
+                                  "(corr_dx leaves it undefined in the reference, gpr.py:655-658)")  # fmt: skip
+    if polish and (int(n_starts) < 1 or int(max_iter) < 1):
+        raise ValueError("n_starts = %d, max_iter = %d: both at least 1" % (n_starts, max_iter))
     eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
     lower, upper = criterion.cell_lower_bounds, criterion.cell_upper_bounds
+    if polish:
+        return _ehvi_thompson_polished(model, eng, search_space, q, st.y.shape[1], n_features, seed, hist, k, lower, upper, int(n_starts),
+                                       int(max_iter))  # fmt: skip
 
     def call(qb, sd, kk):  # a member lists `merge_ranks`; with an empty list it keeps the first B rank
         out = eng.sweep_thompson_ehvi(_th.draw_multi(model, qb, n_features, sd), qb, lower, upper, k=kk)

@@ -469,6 +469,90 @@ def hvi_select_numpy(paths, lower, upper, sigma2, k=1):
     return dict(A=A, B=B, best_val=np.stack([va, vb], axis=1), best_idx=np.stack([ia, ib], axis=1))
 
 
+def _sum_16x16(part):
+    """The 256 thread partials (..., 256) added as the point kernels add them: 16 runs of 16 in order, then the 16 sums in order."""
+    runs = part.reshape(part.shape[:-1] + (16, 16))
+    for _ in range(2):
+        s = runs[..., 0]
+        for u in range(1, 16):
+            s = s + runs[..., u]
+        runs = s
+    return runs
+
+
+def hvi_scalarise_numpy(y, jac, lower, upper):
+    """Phase B of `k_point_path_hvi` (kernels_point_path_hvi.hip) in its own operations and order, from path values y (B, m) and their
+    Jacobians jac (B, m, d): the C cells dealt over 256 threads (thread t: cells t, t + 256, ... ascending), per cell
+
+        t_k = max(min(y_k, u_ck) - l_ck, 0);  pre_0 = 1, pre_{k+1} = pre_k t_k;  acc = acc + pre_m
+        suf_{m-1} = 1, suf_{k-1} = suf_k t_k;  w_k = w_k + pre_k suf_k  where l_ck < y_k < u_ck (both strict)
+
+    the thread partials added as `_sum_16x16` adds them, grad = w_0 J_0, then + w_t J_t with t ascending; a NaN among the m values:
+    HVI = -inf and a zero gradient.  Returns (hvi (B,), grad (B, d), w (B, m))."""
+    y, jac = np.atleast_2d(np.asarray(y, dtype=float)), np.asarray(jac, dtype=float)
+    lower, upper = np.atleast_2d(np.asarray(lower, dtype=float)), np.atleast_2d(np.asarray(upper, dtype=float))
+    B, m = y.shape
+    rounds = -(-len(lower) // 256)
+    pad = np.zeros((rounds * 256 - len(lower), m))  # a cell [0, 0]^m adds +0.0 to acc and nothing to w: the thread has no such cell
+    lo, up = np.vstack([lower, pad]).reshape(rounds, 256, m), np.vstack([upper, pad]).reshape(rounds, 256, m)
+    acc, w = np.zeros((B, 256)), np.zeros((B, m, 256))
+    with np.errstate(invalid="ignore"):
+        for r in range(rounds):
+            t = [np.fmax(np.fmin(y[:, k, None], up[r, :, k]) - lo[r, :, k], 0.0) for k in range(m)]
+            pre = [np.ones((B, 256))]
+            for k in range(m):
+                pre.append(pre[k] * t[k])
+            acc = acc + pre[m]
+            suf = np.ones((B, 256))
+            for k in range(m - 1, -1, -1):
+                inside = (lo[r, :, k] < y[:, k, None]) & (y[:, k, None] < up[r, :, k])
+                w[:, k] = np.where(inside, w[:, k] + pre[k] * suf, w[:, k])
+                suf = suf * t[k]
+        hvi, w = _sum_16x16(acc), _sum_16x16(w)
+        grad = w[:, 0, None] * jac[:, 0]
+        for k in range(1, m):
+            grad = grad + w[:, k, None] * jac[:, k]
+    bad = np.isnan(y).any(axis=1)
+    hvi[bad], grad[bad] = -np.inf, 0.0
+    return hvi, grad, w
+
+
+def hvi_grad_numpy(model, dr, X, members, lower, upper, parts=False, from_device=None):
+    """The dense float64 restatement of `bogp_point_eval_path_hvi`: the hypervolume improvement (B,) of member members[b]'s joint draw
+    at row b of X over the cells (lower, upper), and its input gradient (B, d).  With `paths_multi_numpy`'s own gt:
+
+        y_t   = beta + sum_n c_{j,t}[n] r_n(x) + sum_l Wt[l, j m + t] cos(omega_l . x + phi_l),   c_{j,t} = gamma_t - gt_{j,t}, Wt = sqrt(2 sigma2_t / L) W
+        J_tk  = sum_n c_{j,t}[n] d r_n / d x_k - sum_l Wt[l, j m + t] sin(omega_l . x + phi_l) omega_lk        (`path_grad_numpy`'s derivative)
+        HVI   = sum_c prod_k max(0, min(y_k, u_ck) - l_ck),   grad = sum_t w_t J_t,   w_t = sum_c [l_ct < y_t < u_ct] prod_{i != t} t_i
+
+    the scalarisation by `hvi_scalarise_numpy`.  `parts=True` adds a dict: y (B, m), jac (B, m, d), w (B, m) and the sums of the ABSOLUTE
+    terms A_v (B, m) of every value and A_g (B, m, d) of every Jacobian entry.  `from_device=(y, jac)`: the scalarisation alone, on
+    values the device returned -- it then reproduces the device's HVI and gradient byte for byte."""
+    if from_device is not None:
+        hvi, grad, w = hvi_scalarise_numpy(from_device[0], from_device[1], lower, upper)
+        return (hvi, grad, dict(y=from_device[0], jac=from_device[1], w=w)) if parts else (hvi, grad)
+    st = state_of_multi(model)
+    X = np.atleast_2d(np.asarray(X, dtype=float))
+    members = np.asarray(members, dtype=int).ravel()
+    m, L = st.y.shape[1], len(dr.phase)
+    cols = members[:, None] * m + np.arange(m)  # (B, m)
+    Wt = (np.sqrt(2.0 * st.sigma2 / L) * dr.weights[:, cols])  # (L, B, m)
+    _, gt = paths_multi_numpy(st, dr, st.X[:1])
+    R = correlation(st, st.X, st.X) + np.diag(st.nugget)
+    c = np.linalg.solve(R, st.y - st.beta)[:, None, :] - gt[:, cols]  # (N, B, m)
+    ph = X @ dr.omega.T + dr.phase  # (B, L)
+    r, rdx = correlation(st, X, st.X), correlation_dx(st, X, st.X)
+    y = st.beta + np.einsum("bn,nbt->bt", r, c) + np.einsum("bl,lbt->bt", np.cos(ph), Wt)
+    u = -np.sin(ph)[:, :, None] * Wt.transpose(1, 0, 2)  # (B, L, m)
+    jac = np.einsum("nbt,bnk->btk", c, rdx) + np.einsum("blt,lk->btk", u, dr.omega)
+    hvi, grad, w = hvi_scalarise_numpy(y, jac, lower, upper)
+    if not parts:
+        return hvi, grad
+    A_v = abs(st.beta) + np.einsum("bn,nbt->bt", np.abs(r), np.abs(c)) + np.abs(Wt).sum(axis=0)
+    A_g = np.einsum("nbt,bnk->btk", np.abs(c), np.abs(rdx)) + np.einsum("lbt,lk->btk", np.abs(Wt), np.abs(dr.omega))
+    return hvi, grad, dict(y=y, jac=jac, w=w, A_v=A_v, A_g=A_g)
+
+
 def merge_ranks(best_val, best_idx, k=None):
     """A member's proposal list from its rankings (2, k'): the A ranks whose value is above -inf (rows whose drawn constraints
     hold, best objective first), then the B ranks (least violating first) whose row is not already listed; unfilled slots (-1) are

@@ -891,6 +891,37 @@ int bogp_polish_path(bogp_handle* h, const double* X0, int B, const int* member,
                      const double* omega, const double* phase, const double* weights, const double* coef, int minimize, int max_evals,
                      double pgtol, double factr, double* Xout, double* fout, int* n_evals);
 
+/* ---- the hypervolume improvement of a JOINT sample path and its input gradient at B points; the polish of multi-objective Thompson batches
+ * Member j of bogp_sweep_thompson_ehvi's draw holds the m objectives' paths over shared features,
+ *   y_t(x) = path_{j,t}(x) = beta + r(x) . (gamma_t - g_{j,t}) + sqrt(2 sigma2_t / L) sum_l W[l][j m + t] cos(omega_l . x + phase_l)
+ * and the criterion is HVI(y) = sum_c prod_k max(0, min(y_k, u_ck) - l_ck): continuous and piecewise multilinear in y, so
+ *   dHVI/dx = sum_t w_t dy_t/dx,   w_t = sum_c [l_ct < y_t < u_ct] prod_{i != t} max(0, min(y_i, u_ci) - l_ci)
+ * (both comparisons strict: on a cell face the one-sided derivative 0 is taken; the products over i != t come from prefix and suffix
+ * products, never from a division).  The m targets share r(x), dr/dx and every sin and cos, so ONE launch (csrc/
+ * kernels_point_path_hvi.hip) forms y, J = dy/dx, HVI and its gradient for about the cost of one single-path evaluation.  Given the
+ * returned y and J, HVI, w and the gradient follow byte for byte in the kernel's stated order (bogp.thompson.hvi_grad_numpy(from_device=)):
+ * no fused multiply-add is used there.  A NaN among the m values gives HVI = -inf and a zero gradient.  Point b follows member
+ * member[b]; a point's outputs do not depend on B, on where the point stands, on the members beside it or on which outputs are asked for.
+ *   m, q, L, omega, phase, weights   as bogp_sweep_thompson_ehvi took them (weights L x q m, column j m + t)
+ *   coef                    N x q m, exactly what its coef_out returned (g)
+ *   C, lower, upper         the cells, as there; cells equal to those this path left on the device are not checked or uploaded again
+ *   member                  B ints in [0, q); B in 1 .. BOGP_MAX_PATH_POINTS
+ *   `point_eval_path_hvi`   Xb: B x d (host).  hvi_out (B); grad_out (B x d), y_out (B x m), jac_out (B x m x d) may each be NULL.
+ *   `polish_path_hvi`       bogp_polish_path's loop, state, stop rules and read-back on this evaluation, two launches an iteration; HVI is
+ *                           always maximised: fout[b] = HVI of member[b]'s draw at Xout[b] >= that at X0[b] clipped into the box.  A
+ *                           start whose HVI is 0 has a zero gradient and comes back unchanged after one evaluation.
+ * BOGP_ERR_INVALID: no committed model, a model of one target, m != n_targets, q < 1 or q m > BOGP_MAX_PATHS, L, B or C out of range, a
+ * member outside [0, q), a null required array, a cell bound bogp_sweep_thompson_ehvi refuses, a non-finite entry in omega, phase,
+ * weights or coef, lo > hi, max_evals <= 0.  BOGP_ERR_UNSUPPORTED: a forest on the handle; a lift; a polynomial basis; the noisy and
+ * noise-estimating modes; the cubic and generalized-exponential kernels (no spectral draw) and the general-nu Matern kernel (no
+ * corr_dx); d > BOGP_MAX_DIM; more than one rank.  Candidates and later sweeps are unaffected. */
+int bogp_point_eval_path_hvi(bogp_handle* h, const double* Xb, int B, const int* member, int m, int q, int L, const double* omega,
+                             const double* phase, const double* weights, const double* coef, int C, const double* lower,
+                             const double* upper, double* hvi_out, double* grad_out, double* y_out, double* jac_out);
+int bogp_polish_path_hvi(bogp_handle* h, const double* X0, int B, const int* member, const double* lo, const double* hi, int m, int q, int L,
+                         const double* omega, const double* phase, const double* weights, const double* coef, int C, const double* lower,
+                         const double* upper, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals);
+
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
  * this is the cross-rank half of the new inner maximiser behind acquisition/optim/__init__.py:55-153.  One process per
