@@ -88,6 +88,8 @@ SIGNATURES = {
     "bogp_thompson_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_thompson_ehvi_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
+    "bogp_sweep_thompson_ehvi_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_thompson_ehvi_constrained_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_ehvi_grid_cells": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int64]),
     "bogp_sweep_believer_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _ip,
                                            _dp, _dp]),
@@ -955,6 +957,44 @@ class Engine:
         """Producer time, time of the draw at the training rows with its solves, k_thompson_ehvi time over the candidates (ms) and
         the chunks of the last sweep_thompson_ehvi (bogp_thompson_ehvi_last)."""
         return self._thompson_last(self._lib.bogp_thompson_ehvi_last)
+
+    def sweep_thompson_ehvi_constrained(self, draw, q: int, lower, upper, lo, hi, k: int = 1, return_values=False):
+        """Joint sample paths of the objectives and the modelled constraints of the committed multi-target model over the current
+        candidates, selected by the hypervolume the drawn vector adds to the feasible front where the drawn constraints hold
+        (bogp_sweep_thompson_ehvi_constrained): `q` batch members of m = m_obj + len(lo) targets, q m <= 16 columns, over the cells
+        (lower, upper) (C x m_obj each, as `sweep_ehvi_constrained` takes them, C >= 1) and the intervals [lo, hi].  `draw`: the
+        arrays of `bogp.thompson.draw_multi`, column j m + t.  Returns a dict: best_val / best_idx (q, 3, k) -- per member the k best
+        rows of A (the hypervolume improvement of a feasible draw where positive, else -inf), then of B (minus a feasible draw's
+        scaled distance to the improving region, else -inf), then of V (minus the largest scaled excess) -- best_x (q, 3, k, d),
+        coef (N, q m) and, with return_values, paths (q, m, M).  What the library refuses as unsupported raises NotImplementedError
+        with its message."""
+        lower, upper = _f64(lower), _f64(upper)
+        if lower.ndim != 2 or lower.shape != upper.shape:
+            raise ValueError("cell bounds must be two C x m_obj arrays of one shape")
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if len(hi) != len(lo):
+            raise ValueError("lo and hi hold one bound per constraint")
+        C_, m_obj = lower.shape
+        q, k, m = int(q), int(k), m_obj + len(lo)
+        L, omega, phase, weights, eps = self._thompson_draw(draw, q * m)
+        qa, ka = max(q, 1), max(k, 1)
+        best = np.empty((qa, 3, ka))
+        idx = np.empty((qa, 3, ka), dtype=np.int64)
+        bx = np.empty((qa, 3, ka, self.d))
+        paths = np.empty((qa, m, self.M)) if return_values else None
+        coef = np.empty((self.N, qa * m))
+        self._thompson_call(self._lib.bogp_sweep_thompson_ehvi_constrained, int(m_obj), q, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(eps),
+                            int(C_), _ptr(lower), _ptr(upper), len(lo), _ptr(lo), _ptr(hi), k, _ptr(best), idx.ctypes.data_as(_lp), _ptr(bx),
+                            _ptr(paths), _ptr(coef))  # fmt: skip
+        out = dict(best_val=best, best_idx=idx, best_x=bx, coef=coef)
+        if return_values:
+            out["paths"] = paths
+        return out
+
+    def thompson_ehvi_constrained_last(self) -> dict:
+        """Producer time, time of the draw at the training rows with its solves, k_thompson_ehvi_constrained time over the
+        candidates (ms) and the chunks of the last sweep_thompson_ehvi_constrained (bogp_thompson_ehvi_constrained_last)."""
+        return self._thompson_last(self._lib.bogp_thompson_ehvi_constrained_last)
 
     def sweep_believer_ehvi(self, front, ref_point, q: int, pending=None, believe_front=True, return_values=False):
         """Kriging-believer batch under EHVI over the current candidates (bogp_sweep_believer_ehvi): step j maximises EHVI on the m

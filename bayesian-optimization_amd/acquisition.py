@@ -545,8 +545,9 @@ class ConstrainedEHVI:
 
     `criterion(X)` returns one value per row, shape (M,), in one device pass; `criterion.sweep(k, return_values)` sweeps the engine's
     current candidates as `EHVI.sweep` does.  By default there is no input gradient (`return_dx=True` raises); the sweep helpers
-    serve it where they serve `EHVI`: alone in its sweep, on one rank.  Its one batch strategy is the Kriging believer of
-    `optim.constrained_ehvi_believer_batch` (`bogp_sweep_believer_ehvi_constrained`); every other batch entry refuses it by name.
+    serve it where they serve `EHVI`: alone in its sweep, on one rank.  Its batch strategies are the Kriging believer of
+    `optim.constrained_ehvi_believer_batch` (`bogp_sweep_believer_ehvi_constrained`) and the Thompson batches of
+    `optim.constrained_ehvi_thompson_batch` (`bogp_sweep_thompson_ehvi_constrained`); every other batch entry refuses it by name.
 
     `input_gradient=True` (an extension): `criterion(X, return_dx=True)` returns (values, dx) in the shapes
     `EHVI(input_gradient=True)` returns -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through

@@ -10,8 +10,10 @@
 // No contraction launch anywhere.
 // bogp_sweep_thompson_constrained (below): q members' joint paths of the m targets of a multi-target model -- the same four steps over
 // q m columns, k_thompson_constrained in step 3 and 2 q scores in step 4.
-// bogp_sweep_thompson_ehvi (last): the same joint paths of the m objectives, selected by the hypervolume improvement of the drawn
+// bogp_sweep_thompson_ehvi: the same joint paths of the m objectives, selected by the hypervolume improvement of the drawn
 // vector over the cells of the front -- k_thompson_ehvi in step 3.
+// bogp_sweep_thompson_ehvi_constrained (last): the joint paths of objectives and constraints, the hypervolume improvement among the
+// rows whose drawn constraints hold -- k_thompson_ehvi_constrained in step 3 and 3 q scores in step 4.
 // The steps are written once (begin_pass, upload_draw, solve_at_training_rows, for_each_chunk, winners); an entry keeps its refusals in
 // its own order, the host arithmetic between the steps and its kernel's arguments.
 #include <hip/hip_runtime.h>
@@ -507,4 +509,116 @@ extern "C" int bogp_sweep_thompson_ehvi(bogp_handle* h, int m, int q, int L, con
 
 extern "C" int bogp_thompson_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks) {
   return h ? read_last(h->the_last, corr_ms, solve_ms, paths_ms, n_chunks) : BOGP_ERR_INVALID;
+}
+
+// ---- Thompson batches for multi-objective runs under modelled constraints ------------------------------------------------------------
+// q batch members' JOINT paths of the m = m_obj + n_con targets of a multi-target model (bogp_sweep_ehvi_constrained's: targets
+// 0 .. m_obj - 1 the objectives, maximised as given, target m_obj + i a constraint feasible in [lo_i, hi_i]): the columns, the draw at the
+// training rows and gamma_t - g are the two entries' above; the selection is the hypervolume improvement of the drawn objectives over
+// the cells of the FEASIBLE front among the rows whose drawn constraints hold.
+//   1, 2  as above
+//   3  per candidate chunk: the producer with its store, then k_thompson_ehvi_constrained (kernels_thompson_ehvi_constrained.hip)
+//   4  the argmax / top-k tail over the 3 q scores (A_j: the hypervolume a feasible draw adds; B_j: minus a feasible draw's scaled
+//      distance to the region the front does not dominate; V_j: minus the draw's scaled violation)
+// ABI column and DEVICE column are both j m + t.
+extern "C" int bogp_sweep_thompson_ehvi_constrained(bogp_handle* h, int m_obj, int q, int L, const double* omega, const double* phase,
+                                                    const double* weights, const double* eps, int C, const double* lower, const double* upper,
+                                                    int n_con, const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx,
+                                                    double* best_x, double* paths_out, double* coef_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_sweep_thompson_ehvi_constrained";
+  int rc;
+  if ((rc = check_ready(h, who))) return rc;
+  if ((rc = refuse_lift(h, who))) return rc;
+  if ((rc = refuse_trend(h, who))) return rc;
+  const int m = h->n_t;
+  if (m < 2) FAIL(h, BOGP_ERR_INVALID, "%s: the committed model has one target and so neither a front nor a modelled constraint: bogp_sweep_thompson serves it", who);
+  if (m_obj < 2) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj = %d: at least two objectives (one objective goes to bogp_sweep_thompson_constrained)", who, m_obj);
+  if (n_con < 1) FAIL(h, BOGP_ERR_INVALID, "%s: n_con = %d: at least one constraint (none goes to bogp_sweep_thompson_ehvi)", who, n_con);
+  if (m_obj + n_con != m || m > BOGP_MAX_TARGETS)
+    FAIL(h, BOGP_ERR_INVALID, "%s: m_obj = %d and n_con = %d, but the committed model has %d targets (at most %d)", who, m_obj, n_con, m, BOGP_MAX_TARGETS);
+  if ((int)h->sigma2_t.size() < m) FAIL(h, BOGP_ERR_INVALID, "%s: the commit holds %d target variances", who, (int)h->sigma2_t.size());
+  if (q < 1 || q * m > BOGP_MAX_PATHS) FAIL(h, BOGP_ERR_INVALID, "%s: q = %d members of %d targets: 1 <= q and q m <= %d columns", who, q, m, BOGP_MAX_PATHS);
+  if ((rc = check_features_and_ranks(h, who, L, k))) return rc;
+  if (C < 1 || C > BOGP_MAX_EHVI_CELLS) FAIL(h, BOGP_ERR_INVALID, "%s: C = %d cells outside [1, %d]", who, C, BOGP_MAX_EHVI_CELLS);
+  if (!omega || !phase || !weights || !lower || !upper || !lo || !hi || !best_val || !best_idx)
+    FAIL(h, BOGP_ERR_INVALID, "%s: omega, phase, weights, lower, upper, lo, hi, best_val and best_idx must be non-null", who);
+  const size_t nb = (size_t)C * m_obj;
+  if ((rc = check_ehvi_cells(h, who, nb, lower, upper))) return rc;
+  if ((rc = check_constraint_bounds(h, who, n_con, lo, hi))) return rc;
+  const int N = h->N, Np = h->Np, qm = q * m;
+  if ((rc = check_draw_finite_and_mode(h, who, L, qm, omega, phase, weights, eps))) return rc;
+  if ((rc = refuse_kernel_lift_ranks(h, who))) return rc;
+  const int N4 = (N + 3) & ~3;
+  hipStream_t st = h->stream;
+  ThompsonPass P;
+  if ((rc = begin_pass(h, L, qm, 3 * q, true, &P))) return rc;
+  if ((rc = stage_ehvi_cells(h, lower, upper, nb, st))) return rc;
+  const int64_t M = h->M;
+  const bool ranked = k > 1;
+  // dacq_out: the [3 q][M] scores (k > 1), then the [q m][M] path values (on request)
+  const size_t n_scores = ranked ? (size_t)3 * q * M : 0, n_paths = paths_out ? (size_t)qm * M : 0;
+  if (n_scores + n_paths > 0)
+    if ((rc = h->dacq_out.ensure(h, n_scores + n_paths))) return rc;
+
+  // ---- the draw: W scaled per column by sqrt(2 sigma2_t / L) and padded to 16 columns
+  std::vector<double> hW((size_t)16 * L, 0.0);
+  for (int t = 0; t < m; ++t) {
+    const double scale = std::sqrt(2.0 * h->sigma2_t[t] / (double)L);
+    for (int l = 0; l < L; ++l)
+      for (int j = 0; j < q; ++j) hW[(size_t)l * 16 + j * m + t] = scale * weights[(size_t)l * qm + j * m + t];
+  }
+  if ((rc = upload_draw(h, P, L, omega, phase, hW, st))) return rc;
+
+  SpanTimer& tm = h->th_timer;
+  // ---- 1, 2: the draw at the training rows, plus what the nugget adds to an observation; R^-1 s for the q m columns
+  std::vector<double> hs((size_t)N * qm), ha((size_t)N * qm), hgamma((size_t)m * Np);
+  HIPCHK(h, hipMemcpyAsync(hgamma.data(), h->dgamma_base.ptr, hgamma.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  std::vector<ColNoise> noise;
+  if (eps && h->R_diag - 1.0 > 0.0)
+    for (int j = 0; j < q; ++j)
+      for (int t = 0; t < m; ++t) noise.push_back({std::sqrt(h->sigma2_t[t] * (h->R_diag - 1.0)), j * m + t});
+  if ((rc = solve_at_training_rows(h, P, L, qm, false, noise, eps, hs, ha, st))) return rc;
+  // ---- then gamma_t - g on the host
+  std::vector<double> hcoef((size_t)16 * N4, 0.0);
+  for (int j = 0; j < q; ++j)
+    for (int t = 0; t < m; ++t) {
+      const int c = j * m + t;
+      for (int n = 0; n < N; ++n) {
+        const double g = ha[(size_t)c * N + n];
+        hcoef[(size_t)n * 16 + c] = hgamma[(size_t)t * Np + n] - g;
+        if (coef_out) coef_out[(size_t)n * qm + c] = g;
+      }
+    }
+  HIPCHK(h, hipMemcpyAsync(P.coef, hcoef.data(), hcoef.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // (hcoef leaves scope)
+  int s1 = 0;
+  if ((rc = tm.mark(h, st, &s1))) return rc;
+  tm.span(TH_SOLVE, P.s0, s1);
+
+  // ---- 3: the candidate chunks
+  ThompsonEhviConstrainedArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.X = h->dXs; ca.d = h->d; ca.L = L; ca.N = N; ca.q = q; ca.m_obj = m_obj; ca.n_con = n_con; ca.omega = P.omega; ca.phase = P.phase;
+  ca.W = P.W; ca.rT = h->drT[0]; ca.ld = P.geo.Mc; ca.coef = P.coef; ca.beta = h->beta; ca.M = M;
+  for (int t = 0; t < m; ++t) ca.inv_sd[t] = 1.0 / std::sqrt(h->sigma2_t[t]);
+  for (int i = 0; i < n_con; ++i) {
+    ca.lo[i] = lo[i]; ca.hi[i] = hi[i];
+  }
+  ca.lower = h->dehvi_cells; ca.upper = h->dehvi_cells + nb; ca.C = C;
+  double* dscores = ranked ? h->dacq_out.ptr : nullptr;
+  double* dpaths = paths_out ? h->dacq_out.ptr + n_scores : nullptr;
+  ca.scores = dscores; ca.paths = dpaths;
+  ca.blk_val = h->dblk_val; ca.blk_idx = h->dblk_idx; ca.nblk_total = P.nblk_total;
+  if ((rc = for_each_chunk(h, P, true, st, ca, launch_thompson_ehvi_constrained))) return rc;
+
+  // ---- 4: the winners of the 3 q scores: [q][3][k], member j's A ranks, then its B ranks, then its V ranks
+  if (paths_out) HIPCHK(h, hipMemcpyAsync(paths_out, dpaths, (size_t)qm * M * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((rc = winners(h, P, 3 * q, k, dscores, best_val, best_idx, best_x, st))) return rc;
+  store_last(tm, P.geo.nchunk, &h->thec_last);
+  return BOGP_OK;
+}
+
+extern "C" int bogp_thompson_ehvi_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks) {
+  return h ? read_last(h->thec_last, corr_ms, solve_ms, paths_ms, n_chunks) : BOGP_ERR_INVALID;
 }

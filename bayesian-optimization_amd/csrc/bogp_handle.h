@@ -326,7 +326,7 @@ struct bogp_handle {
   // Thompson-sampling batches (bogp_api_thompson.hip)
   bogp::DevBuf<double> dth_small;  // omega | phase | W | coefficient block (-g, or gamma - g) | s, V s, R^-1 s of the call in flight
   bogp::SpanTimer th_timer;        // draw at X + solves, chunk producers, k_thompson / k_thompson_constrained / k_thompson_ehvi
-  bogp::ThompsonLast th_last, thc_last, the_last;  // of the last bogp_sweep_thompson / _constrained / _ehvi, all on th_timer's spans
+  bogp::ThompsonLast th_last, thc_last, the_last, thec_last;  // of the last bogp_sweep_thompson / _constrained / _ehvi / _ehvi_constrained, all on th_timer's spans
 
   // packed regression forest (bogp_api_forest.hip): the second model kind of a handle.  forest_T > 0 <=> a forest is set; it then
   // owns `d` (a handle carries a GP training set or a forest, never both)

@@ -488,6 +488,37 @@ struct ThompsonEhviArgs {
 };
 hipError_t launch_thompson_ehvi(const ThompsonEhviArgs& a, hipStream_t st);
 
+// q batch members' joint sample paths of the m_obj objectives and n_con constraints of a multi-target model over a chunk, selected by
+// the hypervolume improvement of the drawn vector where the drawn constraints hold (kernels_thompson_ehvi_constrained.hip): with
+// feas = every lo[i] <= path_{j,m_obj+i}(x) <= hi[i], A and B are k_thompson_ehvi's over the objectives where feas (else -inf) and
+// V = 0 - max_i(excess_i inv_sd[m_obj+i]); the cells are evaluated for the feasible pairs only.  One np.argmax record per score and 64
+// rows.  DEVICE column of (member j, target t): j m + t, the ABI's own.
+struct ThompsonEhviConstrainedArgs {
+  const double* X;        // [M][d] the candidates
+  int64_t row0, mcount;   // first row of this launch; rows it serves
+  int d, L, N, q;         // L: features, a multiple of 16
+  int m_obj, n_con;       // 2 <= m_obj, 1 <= n_con, m = m_obj + n_con <= 8, q m <= 16
+  const double* omega;    // [L][d]
+  const double* phase;    // [L]
+  const double* W;        // [L][16] weights times sqrt(2 sigma2_t / L), zero columns from q m on
+  const double* rT;       // [Np][ld] the chunk's correlation columns
+  int64_t ld;             // Mc: stride of rT
+  const double* coef;     // [ceil(N / 4) * 4][16] gamma_t - g_{j,t}, zero padded rows and columns
+  double beta;
+  double inv_sd[8];       // per target: 1 / sqrt(sigma2_t)
+  double lo[8], hi[8];    // per constraint: entry i belongs to target m_obj + i
+  const double* lower;    // [C][m_obj] cell bounds of the feasible front (device), finite
+  const double* upper;    // [C][m_obj] (+inf allowed)
+  int C;                  // >= 1
+  double* scores;         // [3 q][M] at the global row: rows 3 j, 3 j + 1, 3 j + 2 are A_j, B_j, V_j; or null
+  double* paths;          // [q m][M] at the global row, row j m + t; or null
+  int64_t M;
+  double* blk_val;        // [3 q][nblk_total]
+  int64_t* blk_idx;
+  int64_t blk_offset, nblk_total;
+};
+hipError_t launch_thompson_ehvi_constrained(const ThompsonEhviConstrainedArgs& a, hipStream_t st);
+
 // a packed regression forest over the current candidates (kernels_forest.hip): per-tree traversal -> mean / variance over
 // the trees -> the q criteria of acq_value -> per-block argmax records, one launch for all M rows
 struct ForestTree {  // one tree of the packed forest

@@ -208,7 +208,8 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
     method, which raises as it does without this package.
     After a tell() that carried constraint values (`install(constrained_mobo=True)`) the batch is
     `optim.constrained_ehvi_believer_batch` on `bogp.ConstrainedEHVI` under `install(constrained_mobo_batches="believer")` and the
-    same conditions (no cheap h / g); without that switch, and in every other configuration, it raises NotImplementedError."""
+    same conditions (no cheap h / g), `optim.constrained_ehvi_thompson_batch` with the run's history under
+    `install(constrained_mobo_thompson=True)`; without either switch, and in every other configuration, it raises NotImplementedError."""
     optimizer, budget = _effective(getattr(self, "_optimizer", None), None)
     kw = getattr(getattr(self, "_argmax_restart", None), "keywords", None) or {}
     if getattr(self, "_bogp_constraints", None) is not None:
@@ -221,6 +222,15 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
             criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
             xs, fs = optim.constrained_ehvi_believer_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
                                                            design=optim.DEVICE_DESIGNS.get(optimizer))  # fmt: skip
+            return tuple(xs), tuple(fs)
+        if (_CONSTRAINTS.get("mobo_batches") == "thompson" and _CONSTRAINTS.get("mobo") and not fixed and optimizer in _SWEEPS
+                and is_device_model(getattr(self, "model", None)) and optim.is_continuous(kw.get("search_space"))
+                and kw.get("h") is None and kw.get("g") is None):  # fmt: skip
+            # install(..., constrained_mobo_thompson=True): one joint draw of objectives and constraints per point, with the run's history
+            lo, hi = _constraint_bounds(self)
+            criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
+            xs, fs = optim.constrained_ehvi_thompson_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
+                                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self))  # fmt: skip
             return tuple(xs), tuple(fs)
         raise NotImplementedError("MOBO(n_point=q) under expensive constraints: constrained EHVI (bogp.ConstrainedEHVI) has no batch "
                                   "strategy; ask for one point at a time")  # fmt: skip
@@ -661,7 +671,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             restart_batch: int = None, batch_strategy: str = "topk", ehvi_gradient: bool = False, expensive_constraints: bool = False,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
-            ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False):
+            ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False,
+            constrained_mobo_thompson: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -738,6 +749,13 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     optimiser of the sweep family, a continuous space, nothing fixed and no cheap h / g; every other configuration raises as
     before.
 
+    `constrained_mobo_thompson=True` (with `constrained_mobo=True`; alone, or together with `constrained_mobo_batches="believer"`, it
+    raises ValueError): `MOBO(n_point=q)` after a tell() that carried constraint values proposes its q points by
+    `optim.constrained_ehvi_thompson_batch` -- per point one joint draw of the objectives and the constraints, and the candidate whose
+    drawn vector adds the most hypervolume to the feasible front among the rows whose drawn constraints hold (the least violating row
+    where they hold nowhere) -- with the run's history, under the believer's conditions.  No variance contraction runs.  A model that
+    Thompson sampling refuses (a nugget or noise estimate, ...) raises NotImplementedError naming it.
+
     `ehvi_thompson=True` (together with `batch_strategy="believer"` it raises ValueError): the reference's `MOBO(n_point=q)` proposes
     its q points by `optim.ehvi_thompson_batch` -- per point one joint draw of the objectives, and the candidate whose drawn vector
     adds the most hypervolume to the front (the one nearest to the non-dominated region where the draw improves nowhere) -- with the
@@ -756,6 +774,10 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         raise ValueError("constrained_mobo_batches must be 'topk' or 'believer', not %r" % (constrained_mobo_batches,))
     if constrained_mobo_batches == "believer" and not constrained_mobo:
         raise ValueError("constrained_mobo_batches='believer' needs constrained_mobo=True (it batches constrained EHVI)")
+    if constrained_mobo_thompson and not constrained_mobo:
+        raise ValueError("constrained_mobo_thompson=True needs constrained_mobo=True (it draws the objectives and the modelled constraints jointly)")
+    if constrained_mobo_thompson and constrained_mobo_batches == "believer":
+        raise ValueError("constrained_mobo_thompson=True and constrained_mobo_batches='believer' name two batch strategies for one step: choose one")
     if constrained_mobo and not expensive_constraints:
         raise ValueError("constrained_mobo=True needs expensive_constraints=True (it keeps the h_vals / g_vals of a multi-objective tell())")
     if constrained_mobo_gradient and not constrained_mobo:
@@ -787,6 +809,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["mobo_gradient"] = True
         if constrained_mobo_batches == "believer":
             _CONSTRAINTS["mobo_batches"] = "believer"
+        if constrained_mobo_thompson:
+            _CONSTRAINTS["mobo_batches"] = "thompson"
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

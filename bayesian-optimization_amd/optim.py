@@ -886,6 +886,59 @@ def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_fea
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def constrained_ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
+                                    Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None,
+                                    k: int = 8, lift=None, masks=None, values=None, h: Optional[Callable] = None,
+                                    g: Optional[Callable] = None, group=None, rank=None, world=None):
+    """A q-point proposal for a multi-objective run under modelled constraints by Thompson sampling
+    (`bogp_sweep_thompson_ehvi_constrained`): per proposed point ONE joint draw of the objectives and the constraints of
+    `criterion.model` (`thompson.draw_multi`), and among the candidates whose DRAWN constraints hold the row whose drawn objective
+    vector adds the most hypervolume to the feasible front (A) -- the feasible row nearest to the region that front does not dominate
+    where no feasible draw improves (B), and the least violating row where the draw is feasible nowhere (V).  `criterion`: one
+    `bogp.ConstrainedEHVI`; it supplies the model, the cells of its feasible front and the intervals.  A `feasibility_only` criterion
+    (no feasible observation, zero cells) passes the one cell [ref_point, +inf): every drawn vector that is feasible and above the
+    reference point improves, otherwise V decides -- no "probability of feasibility alone" mode is needed.  ONE producer pass and one
+    streaming pass serve `16 // m` members (m targets); more run in further calls with seeds derived from `seed`
+    (`thompson.batch_seeds`).  No variance contraction runs.  Candidates as in `believer_batch`.  Members are independent; every
+    member lists its `k` best rows (`thompson.merge_ranks`: A ranks, then B, then V) and takes the first that no earlier member took
+    and that is not `np.isclose` to a row of `history` (`thompson_batch`'s rule), so the q proposals are q distinct rows.  Returns
+    (xopt: tuple of q lists, fopt: tuple of q floats) in `batch_argmax`'s format; fopt is the score of the tier the pick came from.
+    TypeError: a criterion that is not `bogp.ConstrainedEHVI`.  Refused (NotImplementedError): a forest model, a lift, fixed
+    variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    from . import thompson as _th
+
+    if not is_constrained_ehvi(criterion):
+        raise TypeError("constrained_ehvi_thompson_batch takes a %s criterion (EHVI goes to ehvi_thompson_batch, bogp.Constrained to "
+                        "constrained_thompson_batch, a model alone to thompson_batch)" % _CEHVI)  # fmt: skip
+    model = criterion.model
+    if _forest.is_forest_model(model):
+        raise NotImplementedError("Thompson sampling draws paths of a Gaussian process: a forest model has no Thompson batches")
+    st, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of_multi, q, k, " under constrained EHVI")
+    if k < 1:
+        raise ValueError("k = %d: every member lists at least one row" % k)
+    m_obj, m = criterion.n_obj, st.y.shape[1]
+    if m != m_obj + len(criterion.lo):
+        raise ValueError("the model has %d targets, the criterion %d objectives and %d constraints" % (m, m_obj, len(criterion.lo)))
+    eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
+    lower, upper = criterion.cell_lower_bounds, criterion.cell_upper_bounds
+    if criterion.feasibility_only:  # no feasible observation: everything above the reference point improves
+        lower, upper = np.asarray(criterion.ref_point, dtype=float).reshape(1, m_obj), np.full((1, m_obj), np.inf)
+
+    def call(qb, sd, kk):  # a member lists `merge_ranks` over its three tiers; with an empty list it keeps the first V rank
+        out = eng.sweep_thompson_ehvi_constrained(_th.draw_multi(model, qb, n_features, sd), qb, lower, upper, criterion.lo, criterion.hi, k=kk)
+        idx, bx = out["best_idx"], out["best_x"]
+        return out, [([(gi, bx[c, which, r], (which, r)) for gi, which, r in _th.merge_ranks(out["best_val"][c], idx[c], kk)],
+                      (int(idx[c, 2, 0]), bx[c, 2, 0], (2, 0))) for c in range(qb)]  # fmt: skip
+
+    chosen_x, chosen_f = [], []
+    per_call = _th.MAX_PATHS // m
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    for out, c, (_, x, (which, r)) in _thompson_picks(sizes, seed, k, hist, call):
+        chosen_x.append(np.asarray(x, dtype=float).tolist())
+        chosen_f.append(float(out["best_val"][c, which, r]))
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def ehvi_believer_batch(criterion, search_space, eval_budget: int, q: int, Xs: Optional[np.ndarray] = None, design: Optional[str] = None,
                         seed: Optional[int] = None, pending=None, believe_front: bool = True, lift=None, masks=None, values=None,
                         h: Optional[Callable] = None, g: Optional[Callable] = None, group=None, rank=None, world=None):

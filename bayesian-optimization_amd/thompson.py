@@ -469,6 +469,32 @@ def hvi_select_numpy(paths, lower, upper, sigma2, k=1):
     return dict(A=A, B=B, best_val=np.stack([va, vb], axis=1), best_idx=np.stack([ia, ib], axis=1))
 
 
+def hvi_constrained_select_numpy(paths, n_obj, lower, upper, lo, hi, sigma2, k=1):
+    """The selection of `bogp_sweep_thompson_ehvi_constrained` on path values (q, m, M) -- targets 0 .. n_obj - 1 the objectives
+    (maximised) over the cells (lower, upper) (C x n_obj), targets n_obj .. m - 1 constraints feasible in [lo, hi] -- in the device's
+    own operations and order, from the pieces of `select_numpy` (the violation and the feasibility of the constraint columns) and
+    `hvi_select_numpy` (HVI and dist of the objective columns):
+
+        A = feas and HVI > 0 ? HVI : -inf,   B = feas ? 0.0 - dist : -inf,   V = 0.0 - viol,   a NaN among the m values: A = B = V = -inf
+
+    Returns a dict: A, B, V (q, M), feas (q, M), best_val / best_idx (q, 3, k): per member the ranking of A, then of B, then of V."""
+    paths = np.asarray(paths, dtype=float)
+    q, m, M = paths.shape
+    n_obj = int(n_obj)
+    sigma2 = np.asarray(sigma2, dtype=float).ravel()
+    if not 2 <= n_obj < m or len(sigma2) != m:
+        raise ValueError("n_obj = %d objectives among %d targets (at least two, and at least one constraint); sigma2 one value per target" % (n_obj, m))
+    # `select_numpy` reads its column 0 as an objective and the rest as constraints: the last objective stands in, its A is not used
+    con = select_numpy(paths[:, n_obj - 1 :], lo, hi, sigma2[n_obj - 1 :], minimize=False, k=1)
+    obj = hvi_select_numpy(paths[:, :n_obj], lower, upper, sigma2[:n_obj], k=1)
+    bad = np.isnan(paths).any(axis=1)
+    feas = con["feas"] & ~bad
+    A, B = np.where(feas, obj["A"], -np.inf), np.where(feas, obj["B"], -np.inf)
+    V = np.where(bad, -np.inf, con["B"])
+    ranks = [rank_numpy(s, int(k)) for s in (A, B, V)]
+    return dict(A=A, B=B, V=V, feas=feas, best_val=np.stack([r[0] for r in ranks], axis=1), best_idx=np.stack([r[1] for r in ranks], axis=1))
+
+
 def _sum_16x16(part):
     """The 256 thread partials (..., 256) added as the point kernels add them: 16 runs of 16 in order, then the 16 sums in order."""
     runs = part.reshape(part.shape[:-1] + (16, 16))
@@ -554,20 +580,17 @@ def hvi_grad_numpy(model, dr, X, members, lower, upper, parts=False, from_device
 
 
 def merge_ranks(best_val, best_idx, k=None):
-    """A member's proposal list from its rankings (2, k'): the A ranks whose value is above -inf (rows whose drawn constraints
-    hold, best objective first), then the B ranks (least violating first) whose row is not already listed; unfilled slots (-1) are
-    dropped and the list is cut to `k` (default k').  Returns a list of (row, which, rank): which = 0 for an A rank, 1 for a B rank."""
+    """A member's proposal list from its rankings (n_tiers, k'), tier after tier: the A ranks whose value is above -inf (rows whose
+    drawn constraints hold, best objective first), then the B ranks (least violating first) whose row is not already listed, then
+    those of every further tier (`hvi_constrained_select_numpy`'s V); unfilled slots (-1) are dropped and the list is cut to `k`
+    (default k').  Returns a list of (row, which, rank): which = 0 for an A rank, 1 for a B rank, ..."""
     best_val, best_idx = np.asarray(best_val), np.asarray(best_idx)
     k = best_val.shape[-1] if k is None else int(k)
     out, seen = [], set()
-    for r in range(best_val.shape[-1]):
-        gi = int(best_idx[0, r])
-        if gi >= 0 and best_val[0, r] > -np.inf and gi not in seen:
-            out.append((gi, 0, r))
-            seen.add(gi)
-    for r in range(best_val.shape[-1]):
-        gi = int(best_idx[1, r])
-        if gi >= 0 and best_val[1, r] > -np.inf and gi not in seen:
-            out.append((gi, 1, r))
-            seen.add(gi)
+    for which in range(best_val.shape[0]):
+        for r in range(best_val.shape[-1]):
+            gi = int(best_idx[which, r])
+            if gi >= 0 and best_val[which, r] > -np.inf and gi not in seen:
+                out.append((gi, which, r))
+                seen.add(gi)
     return out[:k]

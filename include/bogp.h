@@ -493,6 +493,51 @@ int bogp_sweep_thompson_ehvi(bogp_handle* h, int m, int q, int L, const double* 
                              int64_t* best_idx, double* best_x, double* paths_out, double* coef_out);
 int bogp_thompson_ehvi_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
 
+/* ---- sweep: Thompson-sampling batches for multi-objective runs under modelled constraints -------------------
+ * Joint sample paths of the objectives AND the modelled constraints, selected by the hypervolume a draw adds to the feasible front
+ * where its drawn constraints hold.  The model is bogp_sweep_ehvi_constrained's: a committed multi-target model with m = m_obj + n_con
+ * targets, m_obj >= 2, n_con >= 1, m <= BOGP_MAX_TARGETS; targets 0 .. m_obj - 1 are the objectives, maximised as given, target
+ * m_obj + i is a constraint that is feasible when lo_i <= c_i(x) <= hi_i; noiseless mode, constant basis.  A call carries q batch
+ * members, q m <= BOGP_MAX_PATHS columns (so q <= 5); column j m + t in weights, eps, paths_out and coef_out is member j's path of
+ * target t, formed exactly as bogp_sweep_thompson_constrained / bogp_sweep_thompson_ehvi form it.  The cells (l_c, u_c), c = 0 .. C - 1,
+ * are what bogp_sweep_ehvi_constrained takes: the cells of the FEASIBLE front, C x m_obj.  Selection per row x and member j, with
+ * y_k = path_{j,k}(x) for k < m_obj and c_i = path_{j,m_obj+i}(x):
+ *   e_i    = max(lo_i - c_i, c_i - hi_i, 0)
+ *   viol   = max_i (e_i inv_sd_{m_obj+i}),   inv_sd_t = 1 / sqrt(sigma2_t) (formed on the host)
+ *   feas   = every (lo_i <= c_i) and (c_i <= hi_i) holds
+ *   HVI    = sum_c prod_k max(0, min(y_k, u_ck) - l_ck)                         (bogp_sweep_thompson_ehvi's order, no fused multiply-add)
+ *   dist   = min_c max_k (max(l_ck - y_k, y_k - u_ck, 0) inv_sd_k)
+ *   A_j(x) = feas && HVI > 0 ? HVI : -inf      feasible by the draw and improving: the hypervolume added
+ *   B_j(x) = feas ? 0.0 - dist : -inf          feasible by the draw, not improving: the row nearest to the improving region
+ *   V_j(x) = 0.0 - viol                        every row: the least violating, for a member whose draw is feasible nowhere
+ * A row with a NaN among its m path values has A = B = V = -inf.  viol is bogp_sweep_thompson_constrained's arithmetic (comparisons
+ * and single products), HVI and dist are bogp_sweep_thompson_ehvi's arithmetic and order, so A, B and V follow from the returned path
+ * values exactly (bogp.thompson.hvi_constrained_select_numpy).  While no feasible observation exists, pass the one cell
+ * [reference point, +inf): every draw that is feasible and above the reference point improves, otherwise V decides -- no separate
+ * "probability of feasibility alone" mode is needed.
+ *   omega (L x d), phase (L), weights (L x q m), eps (N x q m or NULL = zeros): HOST arrays, row-major
+ *   lower / upper (C x m_obj, HOST, row-major): 1 <= C <= BOGP_MAX_EHVI_CELLS, lower finite, upper >= lower (+inf allowed)
+ *   lo / hi      n_con HOST values each, either may be infinite; NaN and hi < lo are invalid
+ *   best_val, best_idx (q x 3 x k): per member the k best rows of A, then of B, then of V, by bogp_sweep_topk's rules (first maximum,
+ *              ties to the lower index, slots beyond M are (-inf, -1));  best_x (q x 3 x k x d, may be NULL)
+ *   paths_out (q x m x M, may be NULL): the path values;  coef_out (N x q m, may be NULL): g
+ * Members are independent.  Per call: the draw at the training rows and one N x q m solve; per candidate chunk the correlation producer
+ * and k_thompson_ehvi_constrained (kernels_thompson_ehvi_constrained.hip: the siblings' matrix part, then the pass over the C cells for
+ * the (row, member) pairs that are feasible by the draw ONLY -- they are compacted across the workgroup first).  The variance
+ * contraction never runs.  The outputs are bit-identical for any BOGP_CHUNK_MB, with and without paths_out, and a member's do not
+ * depend on the members beside it; the path values are bogp_sweep_thompson_constrained's bits for the same columns.
+ * BOGP_ERR_UNSUPPORTED: a forest, a lift on the handle, a polynomial trend basis.  BOGP_ERR_INVALID: no committed model, no
+ * candidates, a model of one target, m_obj < 2, n_con < 1, m_obj + n_con != n_targets, q < 1 or q m > BOGP_MAX_PATHS, L or k out of
+ * range, C outside [1, BOGP_MAX_EHVI_CELLS], a null required array, a non-finite lower cell bound, a NaN upper cell bound, upper <
+ * lower, a NaN constraint bound, hi < lo, a non-finite entry in omega / phase / weights / eps.  BOGP_ERR_UNSUPPORTED: the noisy and
+ * noise-estimating modes, the cubic and generalized-exponential kernels, a communicator of more than one rank.
+ * `thompson_ehvi_constrained_last`: as bogp_thompson_last, of the last such call.                                          */
+int bogp_sweep_thompson_ehvi_constrained(bogp_handle* h, int m_obj, int q, int L, const double* omega, const double* phase,
+                                         const double* weights, const double* eps, int C, const double* lower, const double* upper,
+                                         int n_con, const double* lo, const double* hi, int k, double* best_val, int64_t* best_idx,
+                                         double* best_x, double* paths_out, double* coef_out);
+int bogp_thompson_ehvi_constrained_last(bogp_handle* h, double* corr_ms, double* solve_ms, double* paths_ms, int* n_chunks);
+
 /* ---- sweep: Kriging-believer batches for EHVI -------------------------------------------------------------
  * q proposals per call for a multi-objective run -- what the reference names and leaves open: `class MOBO: """EHVI with
  * Kriging believer"""` stands over `# TODO: implement the Kriging believer strategy` (mobo.py:168-178), and MOBO(n_point > 1)

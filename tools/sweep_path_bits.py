@@ -213,7 +213,7 @@ def case_batches(_lib, np, rng, what):
         for k in (1, 3):
             out = eng.sweep_thompson(dr, minimize=True, k=k, conditioned=True, return_values=k == 3)
             report(eng, "thompson/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"][0], out["coef"][1], out.get("paths"))
-    elif what in ("thompson-constrained", "thompson-ehvi"):  # m = 3 joint paths, q = 5 members (15 columns), L = 64, k = 1 and k = 3
+    elif what in ("thompson-constrained", "thompson-ehvi", "thompson-ehvi-constrained"):  # m = 3 joint paths, q = 5 members (15 columns), L = 64, k = 1 and k = 3
         d, m, q = 4, 3, 5
         X = rng.uniform(-2, 2, (N, d))
         Y = np.column_stack([2 * np.sin(X @ rng.normal(size=d) / np.sqrt(d)) + 0.1 * rng.normal(size=N) for _ in range(m)])
@@ -232,6 +232,12 @@ def case_batches(_lib, np, rng, what):
             upper = np.array([[top[0], top[1], np.inf], [top[0], np.inf, np.inf], [np.inf, top[1], np.inf], [np.inf, np.inf, np.inf]])
             out = eng.sweep_thompson_ehvi(dr, q, lower, upper, k=k, return_values=k == 3)
             report(eng, "thompson-ehvi/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"], out.get("paths"))
+        for k in (1, 3) if what == "thompson-ehvi-constrained" else ():  # the same paths: two objectives over 3 cells, the third target a constraint
+            ref, top = np.quantile(Y[:, :2], 0.3, axis=0), Y[:, :2].max(axis=0)
+            lower = np.array([[ref[0], top[1]], [top[0], ref[1]], [ref[0], ref[1]]])
+            upper = np.array([[top[0], np.inf], [np.inf, top[1]], [top[0], top[1]]])
+            out = eng.sweep_thompson_ehvi_constrained(dr, q, lower, upper, lo[1:], hi[1:], k=k, return_values=k == 3)
+            report(eng, "thompson-ehvi-constrained/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"], out.get("paths"))
         for k in (1, 3) if what == "thompson-constrained" else ():
             out = eng.sweep_thompson_constrained(dr, q, lo, hi, minimize=True, k=k, return_values=k == 3)
             report(eng, "thompson-constrained/k%d" % k, out["best_val"], out["best_idx"], out["best_x"], out["coef"], out.get("paths"))
@@ -305,6 +311,7 @@ CASES = collections.OrderedDict([
     ("lift", (case_batches, "lift", {"BOGP_CHUNK_MB": "8"})),
     ("thompson-constrained", (case_batches, "thompson-constrained", {"BOGP_CHUNK_MB": "8"})),  # (behind the older cases: their lines keep their place)
     ("thompson-ehvi", (case_batches, "thompson-ehvi", {"BOGP_CHUNK_MB": "8"})),
+    ("thompson-ehvi-constrained", (case_batches, "thompson-ehvi-constrained", {"BOGP_CHUNK_MB": "8"})),
 ])  # fmt: skip
 
 
