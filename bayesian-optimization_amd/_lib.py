@@ -142,6 +142,10 @@ SIGNATURES = {
                                            _dp, _dp, _dp, _dp]),
     "bogp_polish_path_hvi": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp,
                                        _dp, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
+    "bogp_point_eval_path_feasible": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                                C.c_int, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp]),
+    "bogp_polish_path_feasible": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp,
+                                            _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, _dp, _dp, _ip]),
     "bogp_comm_unique_id": (C.c_int, [C.c_char_p]),
     "bogp_comm_init": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "bogp_comm_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1551,6 +1555,57 @@ class Engine:
         X0, lo, hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), lo, hi, "lo / hi")
         ops = self._path_hvi_operands(draw, coef, members, lower, upper, B)
         self._path_call(self._lib.bogp_polish_path_hvi, _ptr(X0), B, ops[0], _ptr(lo), _ptr(hi), *ops[1:], int(max_evals), float(pgtol),
+                        float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))  # fmt: skip
+        return Xo, fo, ne
+
+    def _path_feasible_operands(self, draw, coef, members, lower, upper, plo, phi, minimize, rho, B):
+        """A constrained joint-path call's operands as the entries take them: (member (B,) int32, m_obj, q, L, omega, phase, weights, coef
+        (N, q m), C, lower, upper, n_con, plo, phi, minimize, rho) and m.  `lower`, `upper`: the cells over the objectives (C x m_obj, m_obj
+        >= 2) or None for ONE objective; `coef`: what the constrained sweep returned for this draw."""
+        plo, phi = _f64(plo).ravel(), _f64(phi).ravel()
+        if len(plo) != len(phi) or len(plo) < 1:
+            raise ValueError("plo and phi hold one polish bound per constraint")
+        if lower is None and upper is None:
+            C_, m_obj = 0, 1
+        else:
+            lower, upper = self._cells(lower, upper)
+            C_, m_obj = lower.shape
+        m = m_obj + len(plo)
+        L, omega, phase, weights, _ = self._thompson_draw(draw)
+        qm = weights.shape[1]
+        if qm % m:
+            raise ValueError("the draw has %d columns, no multiple of the %d targets (%d objectives, %d constraints)" % (qm, m, m_obj, len(plo)))
+        member = np.ascontiguousarray(members, dtype=np.int32).ravel()
+        if len(member) != B:
+            raise ValueError("members must name one batch member for each of the %d points" % B)
+        coef = _f64(coef)
+        if coef.shape != (self.N, qm):
+            raise ValueError("coef must be the (%d, %d) array of the constrained Thompson sweep" % (self.N, qm))
+        return (member.ctypes.data_as(_ip), int(m_obj), qm // m, L, _ptr(omega), _ptr(phase), _ptr(weights), _ptr(coef), int(C_), _ptr(lower),
+                _ptr(upper), len(plo), _ptr(plo), _ptr(phi), int(bool(minimize)), float(rho)), m  # fmt: skip
+
+    def point_eval_path_feasible(self, X, draw, coef, members, lower, upper, plo, phi, minimize=True, rho: float = 100.0, jacobian: bool = True):
+        """The merit "objective where the drawn constraints hold" of JOINT sample paths of the committed multi-target model and its input
+        gradient at the rows of `X` (B x d) in ONE launch (bogp_point_eval_path_feasible): F - rho sum_i (e_i / sd_i)^2, F the scaled
+        objective path (ONE objective: lower = upper = None; `minimize` applies) or the scaled hypervolume improvement over the cells
+        (lower, upper) (C x m_obj), e_i the excess of drawn constraint i over the POLISH bounds [plo, phi] (`thompson.tighten`).  Row b
+        on batch member members[b] of `draw`, conditioned by `coef` (what the constrained sweep returned).  Returns (merit (B,), grad
+        (B, d), y (B, m): the member's m path values, jac (B, m, d): their input gradients, or None with `jacobian=False`)."""
+        X = self._rows(X)
+        B, d = X.shape[0], self.d
+        ops, m = self._path_feasible_operands(draw, coef, members, lower, upper, plo, phi, minimize, rho, B)
+        merit, grad, y, jac = np.empty(B), np.empty((B, d)), np.empty((B, m)), np.empty((B, m, d)) if jacobian else None
+        self._path_call(self._lib.bogp_point_eval_path_feasible, _ptr(X), B, *ops, _ptr(merit), _ptr(grad), _ptr(y), _ptr(jac))
+        return merit, grad, y, jac
+
+    def polish_path_feasible(self, starts, lo, hi, draw, coef, members, lower, upper, plo, phi, minimize=True, rho: float = 100.0,
+                             max_evals: int = 50, pgtol: float = 1e-8, factr: float = 1e6):
+        """Lock-step multi-start local maximisation of `point_eval_path_feasible`'s merit inside the box [lo, hi]
+        (bogp_polish_path_feasible): start b climbs the merit of member members[b]'s draw; two launches an iteration.  Returns (points
+        (B, d), merit (B,), evaluations used (B,)); merit[b] is no smaller than at starts[b] clipped into the box."""
+        X0, lo, hi, B, Xo, fo, ne = self._polish_io(self._rows(starts), lo, hi, "lo / hi")
+        ops, _ = self._path_feasible_operands(draw, coef, members, lower, upper, plo, phi, minimize, rho, B)
+        self._path_call(self._lib.bogp_polish_path_feasible, _ptr(X0), B, ops[0], _ptr(lo), _ptr(hi), *ops[1:], int(max_evals), float(pgtol),
                         float(factr), _ptr(Xo), _ptr(fo), ne.ctypes.data_as(_ip))  # fmt: skip
         return Xo, fo, ne
 

@@ -981,5 +981,14 @@ struct PointPathHviArgs {
   unsigned long long done_seq;
 };
 hipError_t launch_point_path_hvi(int kernel, const PointPathHviArgs& a, int B, hipStream_t st);
+// the merit of a JOINT sample path of m_obj objectives and n_con constraints and its input gradient at B points
+// (kernels_point_path_feasible.hip): PointPathHviArgs' operands with m = m_obj + n_con columns a member and cells of m_obj columns (none
+// for m_obj = 1), and merit = F - rho sum_i (e_i inv_sd)^2 with e_i the excess of constraint i over the POLISH bounds [plo, phi]
+struct PointPathFeasibleArgs : PointPathHviArgs {  // out: merit, 0, merit, grad (d), 0 (d), grad (d)
+  int m_obj;                          // objectives: columns 0 .. m_obj - 1; the constraints are the columns m_obj .. m - 1
+  double plo[8], phi[8], inv_sd[8];   // per COLUMN t: the polish bounds (t >= m_obj) and 1 / sqrt(sigma2_t) (t >= m_obj; t = 0 for m_obj = 1)
+  double sgn, rho, f_scale;           // m_obj = 1: F = (sgn y_0) inv_sd[0], sgn = -1 when minimising; else F = HVI f_scale
+};
+hipError_t launch_point_path_feasible(int kernel, const PointPathFeasibleArgs& a, int B, hipStream_t st);
 
 }  // namespace bogp

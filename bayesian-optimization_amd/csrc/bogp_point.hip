@@ -4,7 +4,8 @@
 // bogp_point_eval_constrained, bogp_polish_constrained, and of the product of the two (kernels_point_ehvi_constrained.hip):
 // bogp_point_eval_ehvi_constrained, bogp_polish_ehvi_constrained, and of the one-launch evaluation of a posterior sample path
 // (kernels_point_path.hip): bogp_point_eval_path, bogp_polish_path, and of a JOINT path's hypervolume improvement
-// (kernels_point_path_hvi.hip): bogp_point_eval_path_hvi, bogp_polish_path_hvi.  See include/bogp.h for the contracts.
+// (kernels_point_path_hvi.hip): bogp_point_eval_path_hvi, bogp_polish_path_hvi, and of a joint path's merit under drawn constraints
+// (kernels_point_path_feasible.hip): bogp_point_eval_path_feasible, bogp_polish_path_feasible.  See include/bogp.h for the contracts.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -78,6 +79,7 @@ struct PointCall {
   size_t mom_stride;  // doubles per point of the m-target finishes' second block, written behind the B records; 0: not wanted
   const PointPathArgs* path;  // the staged operands of a sample-path call (its points, records and done word are filled in per launch)
   const PointPathHviArgs* path_hvi;  // ... of a joint-path call: ONE launch of k_point_path_hvi; mom_stride doubles a point for y and J
+  const PointPathFeasibleArgs* path_feas;  // ... of a joint path under constraints: ONE launch of k_point_path_feasible, the same blocks
 };
 
 // the EHVI request: a record sized like one criterion's with its gradient (the id itself is not evaluated)
@@ -131,6 +133,13 @@ int queue_point_eval(bogp_handle* h, const PointPlan& pl, const PointCall& c, co
     pa.Xb = dXb; pa.out = out; pa.rec_stride = pl.rec_stride; pa.done_flag = done_flag; pa.done_seq = done_seq;
     pa.mom = c.mom_stride ? out + (size_t)B * pl.rec_stride : nullptr; pa.mom_stride = (int)c.mom_stride;
     HIPCHK(h, launch_point_path_hvi(h->kernel, pa, B, st));
+    return BOGP_OK;
+  }
+  if (c.path_feas) {
+    PointPathFeasibleArgs pa = *c.path_feas;
+    pa.Xb = dXb; pa.out = out; pa.rec_stride = pl.rec_stride; pa.done_flag = done_flag; pa.done_seq = done_seq;
+    pa.mom = c.mom_stride ? out + (size_t)B * pl.rec_stride : nullptr; pa.mom_stride = (int)c.mom_stride;
+    HIPCHK(h, launch_point_path_feasible(h->kernel, pa, B, st));
     return BOGP_OK;
   }
   // Enough right-hand sides: C = V rhs is the candidate sweep's triangular product -- FP64 MFMA through k_contract16's
@@ -317,7 +326,7 @@ int point_eval_wait(bogp_handle* h, const PointPlan& pl, const PointCall& call, 
   // the finishing workgroups write straight into pinned host memory: one stream synchronisation, no copy command
   if ((e = h->hpin.ensure(h, std::max<size_t>(nrec + 8, 1024)))) return e;
   const double* dXb = nullptr;
-  if (B > 1 || d > BOGP_POINT_ARG_D || call.path || call.path_hvi) {  // (the path kernels read their points from device memory only)
+  if (B > 1 || d > BOGP_POINT_ARG_D || call.path || call.path_hvi || call.path_feas) {  // (the path kernels read their points from device memory only)
     if ((e = h->dpt_Xb.ensure(h, (size_t)B * d))) return e;
     HIPCHK(h, hipMemcpyAsync(h->dpt_Xb, Xb, (size_t)B * d * sizeof(double), hipMemcpyHostToDevice, st));
     dXb = h->dpt_Xb;
@@ -734,8 +743,9 @@ extern "C" int bogp_polish_path(bogp_handle* h, const double* X0, int B, const i
 // list in its words and order, with bogp_point_eval_path's where that one has more (B, member, coef, the general-nu kernel, d).  Then the
 // cells (ehvi_cells_resident: equal cells are not uploaded again) and the operands, formed on the host and uploaded ONCE: the columns
 // c_{j,t} = gamma_t - g_{j,t} and Wt = sqrt(2 sigma2_t / L) W, column-major in the column order j m + t, so that a point's workgroup reads
-// its member's m columns of each as m contiguous runs.
-static int path_hvi_request(bogp_handle* h, const char* who, int B, const int* member, int m, int q, int L, const double* omega,
+// its member's m columns of each as m contiguous runs.  `m_cells`: the columns of the cells -- m for the hypervolume of all m targets, the
+// objectives alone under constraints (bogp_point_eval_path_feasible), 0 for one objective, which has no cells (C = 0, lower = upper = NULL).
+static int path_hvi_request(bogp_handle* h, const char* who, int B, const int* member, int m, int m_cells, int q, int L, const double* omega,
                             const double* phase, const double* weights, const double* coef, int C, const double* lower, const double* upper,
                             PointPathHviArgs* pa) {
   if (h->forest_T > 0) FAIL(h, BOGP_ERR_UNSUPPORTED, "%s: the handle holds a forest, which has no posterior paths to draw", who);
@@ -754,7 +764,8 @@ static int path_hvi_request(bogp_handle* h, const char* who, int B, const int* m
   for (int b = 0; b < B; ++b)
     if (member[b] < 0 || member[b] >= q) FAIL(h, BOGP_ERR_INVALID, "%s: member[%d] = %d outside [0, %d)", who, b, member[b], q);
   int e;
-  if ((e = ehvi_cells_resident(h, who, m, C, lower, upper))) return e;
+  if (m_cells == 0 && (C != 0 || lower || upper)) FAIL(h, BOGP_ERR_INVALID, "%s: one objective has no cells: C = 0 and null lower, upper", who);
+  if (m_cells > 0 && (e = ehvi_cells_resident(h, who, m_cells, C, lower, upper))) return e;
   const int N = h->N, d = h->d, Np = h->Np, qm = q * m;
   const auto finite = [](const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i)
@@ -805,7 +816,7 @@ static int path_hvi_request(bogp_handle* h, const char* who, int B, const int* m
   HIPCHK(h, hipStreamSynchronize(st));  // (the staging vectors and the caller's arrays are not needed past this point)
   memset(pa, 0, sizeof(*pa));
   pa->X = h->dX; pa->theta = h->dtheta; pa->member = h->dpt_member; pa->coef = dc; pa->W = dw; pa->omega = dom; pa->phase = dph;
-  pa->lower = h->dehvi_cells; pa->upper = h->dehvi_cells + (size_t)C * m;
+  pa->lower = h->dehvi_cells; pa->upper = h->dehvi_cells + (size_t)C * m_cells;
   pa->N = N; pa->d = d; pa->L = L; pa->m = m; pa->C = C; pa->beta = h->beta;
   return BOGP_OK;
 }
@@ -822,7 +833,7 @@ extern "C" int bogp_point_eval_path_hvi(bogp_handle* h, const double* Xb, int B,
   const char* who = "bogp_point_eval_path_hvi";
   if (!Xb || !hvi_out) FAIL(h, BOGP_ERR_INVALID, "%s: null points or null hvi_out", who);
   PointPathHviArgs pa;
-  int e = path_hvi_request(h, who, B, member, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
+  int e = path_hvi_request(h, who, B, member, m, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
   if (e) return e;
   const int d = h->d;
   const size_t md = (size_t)m * d;
@@ -849,7 +860,84 @@ extern "C" int bogp_polish_path_hvi(bogp_handle* h, const double* X0, int B, con
   const char* who = "bogp_polish_path_hvi";
   if (!X0 || !lo || !hi || !Xout || !fout) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer", who);
   PointPathHviArgs pa;
-  int e = path_hvi_request(h, who, B, member, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
+  int e = path_hvi_request(h, who, B, member, m, m, q, L, omega, phase, weights, coef, C, lower, upper, &pa);
   if (e) return e;
   return polish_loop(h, who, path_hvi_call(&pa, 0), X0, B, lo, hi, max_evals, pgtol, factr, Xout, fout, n_evals);
+}
+
+// ---- the merit of a JOINT sample path under its drawn constraints and its input gradient at B points (kernels_point_path_feasible.hip) --
+// Member j's m = m_obj + n_con paths of bogp_sweep_thompson_constrained's (m_obj = 1) or bogp_sweep_thompson_ehvi_constrained's draw.  What
+// both entries refuse: path_hvi_request's list with the cells over the m_obj objective columns (none for one objective), before it the
+// split of the targets, behind it the polish bounds by the sweeps' own rule (check_constraint_bounds) and rho.  The kernel's constants
+// are formed here: inv_sd_t = 1 / sqrt(sigma2_t) as the sweeps form it, f_scale = prod_{k < m_obj} inv_sd_k, the bounds by column.
+static int path_feasible_request(bogp_handle* h, const char* who, int B, const int* member, int m_obj, int q, int L, const double* omega,
+                                 const double* phase, const double* weights, const double* coef, int C, const double* lower,
+                                 const double* upper, int n_con, const double* plo, const double* phi, int minimize, double rho,
+                                 PointPathFeasibleArgs* pa) {
+  if (m_obj < 1 || n_con < 1) FAIL(h, BOGP_ERR_INVALID, "%s: m_obj = %d objectives and n_con = %d constraints: at least one of each", who, m_obj, n_con);
+  if (!plo || !phi) FAIL(h, BOGP_ERR_INVALID, "%s: plo and phi must be non-null", who);
+  if (!(rho >= 0.0) || !std::isfinite(rho)) FAIL(h, BOGP_ERR_INVALID, "%s: rho = %g: a finite penalty weight >= 0 is required", who, rho);
+  const int m = m_obj + n_con;
+  if (m > BOGP_MAX_TARGETS) FAIL(h, BOGP_ERR_INVALID, "%s: m = %d outside [2, %d]", who, m, BOGP_MAX_TARGETS);  // (plo, phi hold n_con <= 7 values)
+  int e = check_constraint_bounds(h, who, n_con, plo, phi);  // before anything is staged
+  if (e) return e;
+  memset(pa, 0, sizeof(*pa));
+  if ((e = path_hvi_request(h, who, B, member, m, m_obj >= 2 ? m_obj : 0, q, L, omega, phase, weights, coef, C, lower, upper, pa))) return e;
+  pa->m_obj = m_obj;
+  pa->rho = rho;
+  pa->sgn = minimize && m_obj == 1 ? -1.0 : 1.0;
+  pa->f_scale = 1.0;
+  for (int t = 0; t < m; ++t) {
+    pa->inv_sd[t] = 1.0 / std::sqrt(h->sigma2_t[t]);
+    if (t < m_obj) pa->f_scale = pa->f_scale * pa->inv_sd[t];
+    pa->plo[t] = t < m_obj ? 0.0 : plo[t - m_obj];
+    pa->phi[t] = t < m_obj ? 0.0 : phi[t - m_obj];
+  }
+  return BOGP_OK;
+}
+
+static PointCall path_feasible_call(const PointPathFeasibleArgs* pa, size_t mom_stride) {
+  static const int one_id = BOGP_ACQ_EI;  // a record sized like one criterion's with its gradient (the id itself is not evaluated)
+  return PointCall{1, &one_id, nullptr, 0.0, 0, true, nullptr, nullptr, nullptr, mom_stride, nullptr, nullptr, pa};
+}
+
+extern "C" int bogp_point_eval_path_feasible(bogp_handle* h, const double* Xb, int B, const int* member, int m_obj, int q, int L,
+                                             const double* omega, const double* phase, const double* weights, const double* coef, int C,
+                                             const double* lower, const double* upper, int n_con, const double* plo, const double* phi,
+                                             int minimize, double rho, double* merit_out, double* grad_out, double* y_out, double* jac_out) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_point_eval_path_feasible";
+  if (!Xb || !merit_out) FAIL(h, BOGP_ERR_INVALID, "%s: null points or null merit_out", who);
+  PointPathFeasibleArgs pa;
+  int e = path_feasible_request(h, who, B, member, m_obj, q, L, omega, phase, weights, coef, C, lower, upper, n_con, plo, phi, minimize, rho, &pa);
+  if (e) return e;
+  const int d = h->d, m = pa.m;
+  const size_t md = (size_t)m * d;
+  pa.want_jac = jac_out ? 1 : 0;
+  const size_t mom_stride = (y_out || jac_out) ? m + (jac_out ? md : 0) : 0;
+  const PointPlan pl = plan_of(h, B, 1, true);
+  if ((e = point_eval_wait(h, pl, path_feasible_call(&pa, mom_stride), Xb, B))) return e;
+  const double* mom = h->hpin + (size_t)B * pl.rec_stride;
+  for (int b = 0; b < B; ++b) {
+    const double* o = h->hpin + (size_t)b * pl.rec_stride;
+    merit_out[b] = o[0];
+    if (grad_out) memcpy(grad_out + (size_t)b * d, o + 3, (size_t)d * sizeof(double));
+    if (y_out) memcpy(y_out + (size_t)b * m, mom + (size_t)b * mom_stride, (size_t)m * sizeof(double));
+    if (jac_out) memcpy(jac_out + (size_t)b * md, mom + (size_t)b * mom_stride + m, md * sizeof(double));
+  }
+  return BOGP_OK;
+}
+
+extern "C" int bogp_polish_path_feasible(bogp_handle* h, const double* X0, int B, const int* member, const double* box_lo, const double* box_hi,
+                                         int m_obj, int q, int L, const double* omega, const double* phase, const double* weights,
+                                         const double* coef, int C, const double* lower, const double* upper, int n_con, const double* plo,
+                                         const double* phi, int minimize, double rho, int max_evals, double pgtol, double factr, double* Xout,
+                                         double* fout, int* n_evals) {
+  if (!h) return BOGP_ERR_INVALID;
+  const char* who = "bogp_polish_path_feasible";
+  if (!X0 || !box_lo || !box_hi || !Xout || !fout) FAIL(h, BOGP_ERR_INVALID, "%s: null pointer", who);
+  PointPathFeasibleArgs pa;
+  int e = path_feasible_request(h, who, B, member, m_obj, q, L, omega, phase, weights, coef, C, lower, upper, n_con, plo, phi, minimize, rho, &pa);
+  if (e) return e;
+  return polish_loop(h, who, path_feasible_call(&pa, 0), X0, B, box_lo, box_hi, max_evals, pgtol, factr, Xout, fout, n_evals);
 }

@@ -115,7 +115,8 @@ def fused_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=N
         # install(constraint_thompson=True): one joint draw of objective and constraints per point; the criteria supply model, bounds
         # and direction only
         xs, fs = optim.constrained_thompson_batch(crits[0], kw["search_space"], int(budget or kw["eval_budget"]), n_point, design=design,
-                                                  history=_history_of(self))  # fmt: skip
+                                                  history=_history_of(self),
+                                                  **(dict(polish=True) if _CONSTRAINTS.get("thompson_polish") else {}))  # fmt: skip
         return tuple(xs), tuple(fs)
     k = int(min(32, n_point + 8))  # fall-backs: at most n_point - 1 taken by earlier criteria + a few history hits
     xs, fs = optim.batch_argmax(crits, kw["search_space"], int(budget or kw["eval_budget"]), history=_history_of(self), k=k,
@@ -230,7 +231,8 @@ def mobo_batch_arg_max_acquisition(self, n_point: int, return_dx: bool, fixed=No
             lo, hi = _constraint_bounds(self)
             criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
             xs, fs = optim.constrained_ehvi_thompson_batch(criterion, kw["search_space"], int(budget or kw["eval_budget"]), int(n_point),
-                                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self))  # fmt: skip
+                                                           design=optim.DEVICE_DESIGNS.get(optimizer), history=_history_of(self),
+                                                           **(dict(polish=True) if _CONSTRAINTS.get("mobo_thompson_polish") else {}))  # fmt: skip
             return tuple(xs), tuple(fs)
         raise NotImplementedError("MOBO(n_point=q) under expensive constraints: constrained EHVI (bogp.ConstrainedEHVI) has no batch "
                                   "strategy; ask for one point at a time")  # fmt: skip
@@ -672,7 +674,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             equality_tol: float = 0.1, constraint_gradient: bool = False, constraint_batches: str = "topk", constrained_mobo: bool = False,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
             ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False,
-            constrained_mobo_thompson: bool = False):
+            constrained_mobo_thompson: bool = False, constraint_thompson_polish: bool = False,
+            constrained_mobo_thompson_polish: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -727,6 +730,9 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     the constraints, the best drawn objective where the drawn constraints hold, the least violating row where they hold nowhere
     (Eriksson & Poloczek 2021) -- with the run's history; the criteria supply model, bounds and direction only.  A model that
     Thompson sampling refuses (a nugget or noise estimate, ...) raises NotImplementedError naming it.
+    `constraint_thompson_polish=True` (with `constraint_thompson=True`; alone it raises ValueError): every member's best rows are refined on
+    its own draw inside the search space's box (`optim.constrained_thompson_batch(polish=True)`, `bogp_polish_path_feasible`); a
+    polished point is proposed only where it ranks above its start on the true bounds.
 
     `constrained_mobo=True` (with `expensive_constraints=True`; alone it raises ValueError; an extension: `BaseMOBO.tell` leaves the
     values as a TODO, mobo.py:117-118): the reference's `MOBO` with a device GP keeps the `h_vals` / `g_vals` of its tell()
@@ -755,6 +761,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     drawn vector adds the most hypervolume to the feasible front among the rows whose drawn constraints hold (the least violating row
     where they hold nowhere) -- with the run's history, under the believer's conditions.  No variance contraction runs.  A model that
     Thompson sampling refuses (a nugget or noise estimate, ...) raises NotImplementedError naming it.
+    `constrained_mobo_thompson_polish=True` (with `constrained_mobo_thompson=True`; alone it raises ValueError): the same refinement for
+    these members (`optim.constrained_ehvi_thompson_batch(polish=True)`).
 
     `ehvi_thompson=True` (together with `batch_strategy="believer"` it raises ValueError): the reference's `MOBO(n_point=q)` proposes
     its q points by `optim.ehvi_thompson_batch` -- per point one joint draw of the objectives, and the candidate whose drawn vector
@@ -766,6 +774,10 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `ehvi_thompson_polish=True` (with `ehvi_thompson=True`; alone it raises ValueError): every member's best improving rows are refined
     on its own draw inside the search space's box (`optim.ehvi_thompson_batch(polish=True)`, `bogp_polish_path_hvi`), so the proposals
     are points of the box."""
+    if constraint_thompson_polish and not constraint_thompson:
+        raise ValueError("constraint_thompson_polish=True refines the members of constraint_thompson=True")
+    if constrained_mobo_thompson_polish and not constrained_mobo_thompson:
+        raise ValueError("constrained_mobo_thompson_polish=True refines the members of constrained_mobo_thompson=True")
     if ehvi_thompson_polish and not ehvi_thompson:
         raise ValueError("ehvi_thompson_polish=True refines the members of ehvi_thompson=True")
     if ehvi_thompson and batch_strategy == "believer":
@@ -811,6 +823,10 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["mobo_batches"] = "believer"
         if constrained_mobo_thompson:
             _CONSTRAINTS["mobo_batches"] = "thompson"
+        if constraint_thompson_polish:
+            _CONSTRAINTS["thompson_polish"] = True
+        if constrained_mobo_thompson_polish:
+            _CONSTRAINTS["mobo_thompson_polish"] = True
     if batch_strategy not in ("topk", "believer", "thompson"):
         raise ValueError("batch_strategy must be 'topk', 'believer' or 'thompson', not %r" % (batch_strategy,))
     _EHVI.clear()

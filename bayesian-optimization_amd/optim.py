@@ -730,10 +730,73 @@ def thompson_batch(model, search_space, eval_budget: int, q: int, n_features: in
     return tuple(chosen_x), tuple(chosen_f)
 
 
+def _constrained_thompson_polished(model, st, eng, search_space, q, m_obj, n_features, seed, hist, k, sweep, lo_c, hi_c, lower, upper,
+                                   minimize, n_starts, max_iter, penalty, margin):
+    """`constrained_thompson_batch(polish=True)` (m_obj = 1, lower = upper = None) and `constrained_ehvi_thompson_batch(polish=True)` behind
+    their checks: per call of at most 16 // m members one sweep (`sweep(dr, qb, kk)`), then ONE `polish_path_feasible` over every
+    member's first `n_starts` free rows of `merge_ranks`, whatever their tier, against the bounds tightened by `margin` prior standard
+    deviations, and one evaluation at the polished points for their path values.  A polished point is ranked by the sweep's own rule on
+    the TRUE bounds (tier, then score) and enters its member's list only where it ranks strictly above its start; the list is kept in
+    that order, so a member's proposal is never worse under the sweep's rule than without the polish."""
+    from . import thompson as _th
+
+    if n_starts < 1 or max_iter < 1:
+        raise ValueError("n_starts = %d, max_iter = %d: both at least 1" % (n_starts, max_iter))
+    if not (np.isfinite(penalty) and penalty >= 0 and np.isfinite(margin) and margin >= 0):
+        raise ValueError("penalty = %g, margin = %g: both finite and not negative" % (penalty, margin))
+    bounds = np.array(search_space.bounds, dtype=float)
+    blo, bhi = bounds[:, 0], bounds[:, 1]
+    m, n_tier = st.y.shape[1], 2 if m_obj == 1 else 3
+    plo, phi = _th.tighten(lo_c, hi_c, np.sqrt(np.asarray(st.sigma2, dtype=float)[m_obj:]), margin)
+
+    def near(x, rows):
+        return rows is not None and len(rows) > 0 and bool(np.any(np.all(np.isclose(np.asarray(rows), x), axis=1)))
+
+    def ranked(y):  # per row of y (B, m): (tier, score) by the sweep's rule on the true bounds -- a row with a NaN stays (0, -inf)
+        paths = np.ascontiguousarray(y.T)[None]
+        sel = (_th.select_numpy(paths, lo_c, hi_c, st.sigma2, minimize, 1) if m_obj == 1 else
+               _th.hvi_constrained_select_numpy(paths, m_obj, lower, upper, lo_c, hi_c, st.sigma2, 1))  # fmt: skip
+        scores = np.stack([sel[name][0] for name in "ABV"[:n_tier]])
+        tier = np.argmax(scores > -np.inf, axis=0)
+        return tier, scores[tier, np.arange(len(tier))]
+
+    chosen_x, chosen_f = [], []
+    per_call = _th.MAX_PATHS // m
+    sizes = [min(per_call, q - a) for a in range(0, q, per_call)]
+    for qb, sd in zip(sizes, _th.batch_seeds(seed, len(sizes))):
+        kk = int(max(1, min(_lib.MAX_TOPK, max(k, n_starts) + (0 if hist is None else len(hist)) + len(chosen_x))))
+        dr = _th.draw_multi(model, qb, n_features, sd)
+        out = sweep(dr, qb, kk)
+        idx, bx, bv = out["best_idx"], out["best_x"], out["best_val"]
+        free = [[(w, r) for _, w, r in _th.merge_ranks(bv[c], idx[c], kk) if not near(bx[c, w, r], hist)] for c in range(qb)]
+        starts = [(c, w, r) for c in range(qb) for w, r in free[c][:n_starts]]
+        if starts:
+            mem, ops = [c for c, _, _ in starts], (lower, upper, plo, phi)
+            xp, _, _ = eng.polish_path_feasible(np.array([bx[c, w, r] for c, w, r in starts]), blo, bhi, dr, out["coef"], mem, *ops,
+                                                minimize=minimize, rho=penalty, max_evals=max_iter)  # fmt: skip
+            yp = eng.point_eval_path_feasible(xp, dr, out["coef"], mem, *ops, minimize=minimize, rho=penalty, jacobian=False)[2]
+            tier, score = ranked(yp)
+        for c in range(qb):
+            cands = [(int(tier[i]), float(score[i]), xp[i], float(yp[i, 0])) for i, (cc, w, r) in enumerate(starts)
+                     if cc == c and np.isfinite(score[i]) and (tier[i], -score[i]) < (w, -bv[c, w, r])]  # strictly above its start
+            cands += [(w, float(bv[c, w, r]), bx[c, w, r], None) for w, r in free[c]]
+            cands.sort(key=lambda e: (e[0], -e[1]))  # (stable: a polished point before a row of its score)
+            if not cands:  # every listed row is an evaluated point: the first rank of the last tier (the caller's check will pad)
+                cands = [(n_tier - 1, float(bv[c, n_tier - 1, 0]), bx[c, n_tier - 1, 0], None)]
+            seen = chosen_x if hist is None else list(hist) + chosen_x
+            w, f, x, y0 = next((e for e in cands if not near(e[2], seen)), cands[0])
+            chosen_x.append(np.asarray(x, dtype=float).tolist())
+            if m_obj == 1:  # the objective path's own value, as without the polish
+                f = y0 if y0 is not None else (-f if minimize else f) if w == 0 else _th.objective_path_at(st, dr, out["coef"], c, x)
+            chosen_f.append(float(f))
+    return tuple(chosen_x), tuple(chosen_f)
+
+
 def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
                                Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None,
                                k: int = 8, lift=None, masks=None, values=None, h: Optional[Callable] = None,
-                               g: Optional[Callable] = None, group=None, rank=None, world=None):
+                               g: Optional[Callable] = None, group=None, rank=None, world=None, polish: bool = False, n_starts: int = 8,
+                               max_iter: int = 50, penalty: float = 100.0, margin: float = 0.05):
     """A q-point proposal under modelled constraints by Thompson sampling (`bogp_sweep_thompson_constrained`; Eriksson & Poloczek
     2021): per proposed point ONE joint draw of the objective and the constraints of `criterion.model` (`bogp.thompson`:
     `draw_multi`, independent weights over shared random Fourier features), and among the candidates the best objective value where
@@ -746,8 +809,17 @@ def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int
     to a row of `history` (`thompson_batch`'s rule), so the q proposals are q distinct rows.  Returns (xopt: tuple of q lists, fopt:
     tuple of q floats) in `batch_argmax`'s format; fopt is the objective path's value at the proposal (for a least violating row:
     that row of the dense restatement, `thompson.objective_path_at`).
+    `polish=True`: the sweep is followed by a local refinement ON THE DRAW (`bogp_polish_path_feasible`: the m paths, their Jacobian and
+    the merit "scaled objective minus `penalty` times the squared scaled excess of the drawn constraints" with its input gradient in one
+    launch, `k_polish_step` behind it).  ONE `polish_path_feasible` call refines every member's first `n_starts` free rows of its
+    list, whatever their tier, inside the box `search_space.bounds` (at most `max_iter` evaluations each) against the bounds tightened
+    by `margin` prior standard deviations (`thompson.tighten`): a quadratic penalty converges from outside.  A polished point is then
+    ranked by the sweep's own rule on the TRUE bounds from its drawn values and replaces its start only where it ranks strictly above
+    it (feasible before infeasible, then the better score), so no member proposes worse than without the polish.  The proposals are
+    then points of the box, not candidate rows.
     TypeError: a criterion that is not `bogp.Constrained`.  Refused (NotImplementedError): `ConstrainedEHVI`, a forest model, a
-    lift, fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    lift, fixed variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model; with
+    `polish=True` also the general-nu Matern kernel (no input-derivative)."""
     from . import thompson as _th
 
     if is_constrained_ehvi(criterion):
@@ -760,8 +832,17 @@ def constrained_thompson_batch(criterion, search_space, eval_budget: int, q: int
     st, q, k = _thompson_preamble(model, lift, masks, h, g, _th.state_of_multi, q, k, " under modelled constraints")  # (the model's among them)
     if k < 1:
         raise ValueError("k = %d: every member lists at least one row" % k)
+    if polish and st.kernel == _lib.KERNEL_MATERN_NU:
+        raise NotImplementedError("constrained_thompson_batch(polish=True) with the general-nu Matern kernel: its correlation has no "
+                                  "input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)")  # fmt: skip
     eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
     minimize = bool(criterion.minimize)
+    if polish:
+        def sweep(dr, qb, kk):
+            return eng.sweep_thompson_constrained(dr, qb, criterion.lo, criterion.hi, minimize=minimize, k=kk)
+
+        return _constrained_thompson_polished(model, st, eng, search_space, q, 1, n_features, seed, hist, k, sweep, criterion.lo, criterion.hi,
+                                              None, None, minimize, int(n_starts), int(max_iter), float(penalty), float(margin))  # fmt: skip
 
     def call(qb, sd, kk):  # a member lists `merge_ranks`; with an empty list it keeps the first B rank
         dr = _th.draw_multi(model, qb, n_features, sd)
@@ -889,7 +970,8 @@ def ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_fea
 def constrained_ehvi_thompson_batch(criterion, search_space, eval_budget: int, q: int, n_features: int = 1024, seed: Optional[int] = None,
                                     Xs: Optional[np.ndarray] = None, design: Optional[str] = None, history: Optional[np.ndarray] = None,
                                     k: int = 8, lift=None, masks=None, values=None, h: Optional[Callable] = None,
-                                    g: Optional[Callable] = None, group=None, rank=None, world=None):
+                                    g: Optional[Callable] = None, group=None, rank=None, world=None, polish: bool = False,
+                                    n_starts: int = 8, max_iter: int = 50, penalty: float = 100.0, margin: float = 0.05):
     """A q-point proposal for a multi-objective run under modelled constraints by Thompson sampling
     (`bogp_sweep_thompson_ehvi_constrained`): per proposed point ONE joint draw of the objectives and the constraints of
     `criterion.model` (`thompson.draw_multi`), and among the candidates whose DRAWN constraints hold the row whose drawn objective
@@ -903,8 +985,12 @@ def constrained_ehvi_thompson_batch(criterion, search_space, eval_budget: int, q
     member lists its `k` best rows (`thompson.merge_ranks`: A ranks, then B, then V) and takes the first that no earlier member took
     and that is not `np.isclose` to a row of `history` (`thompson_batch`'s rule), so the q proposals are q distinct rows.  Returns
     (xopt: tuple of q lists, fopt: tuple of q floats) in `batch_argmax`'s format; fopt is the score of the tier the pick came from.
+    `polish=True`: as in `constrained_thompson_batch`, with the scaled hypervolume improvement of the drawn objectives in the
+    objective's place (`bogp_polish_path_feasible`); a polished point is ranked over the three tiers on the true bounds and replaces
+    its start only where it ranks strictly above it.
     TypeError: a criterion that is not `bogp.ConstrainedEHVI`.  Refused (NotImplementedError): a forest model, a lift, fixed
-    variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model."""
+    variables, cheap constraints h / g, more than one rank, and what `thompson.state_of_multi` refuses of the model; with
+    `polish=True` also the general-nu Matern kernel (no input-derivative)."""
     from . import thompson as _th
 
     if not is_constrained_ehvi(criterion):
@@ -919,10 +1005,19 @@ def constrained_ehvi_thompson_batch(criterion, search_space, eval_budget: int, q
     m_obj, m = criterion.n_obj, st.y.shape[1]
     if m != m_obj + len(criterion.lo):
         raise ValueError("the model has %d targets, the criterion %d objectives and %d constraints" % (m, m_obj, len(criterion.lo)))
+    if polish and st.kernel == _lib.KERNEL_MATERN_NU:
+        raise NotImplementedError("constrained_ehvi_thompson_batch(polish=True) with the general-nu Matern kernel: its correlation has no "
+                                  "input-derivative (corr_dx leaves it undefined in the reference, gpr.py:655-658)")  # fmt: skip
     eng, hist = _thompson_stage(model, search_space, eval_budget, Xs, design, seed, history, group, rank, world)
     lower, upper = criterion.cell_lower_bounds, criterion.cell_upper_bounds
     if criterion.feasibility_only:  # no feasible observation: everything above the reference point improves
         lower, upper = np.asarray(criterion.ref_point, dtype=float).reshape(1, m_obj), np.full((1, m_obj), np.inf)
+    if polish:
+        def sweep(dr, qb, kk):
+            return eng.sweep_thompson_ehvi_constrained(dr, qb, lower, upper, criterion.lo, criterion.hi, k=kk)
+
+        return _constrained_thompson_polished(model, st, eng, search_space, q, m_obj, n_features, seed, hist, k, sweep, criterion.lo,
+                                              criterion.hi, lower, upper, False, int(n_starts), int(max_iter), float(penalty), float(margin))  # fmt: skip
 
     def call(qb, sd, kk):  # a member lists `merge_ranks` over its three tiers; with an empty list it keeps the first V rank
         out = eng.sweep_thompson_ehvi_constrained(_th.draw_multi(model, qb, n_features, sd), qb, lower, upper, criterion.lo, criterion.hi, k=kk)

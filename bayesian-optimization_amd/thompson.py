@@ -579,6 +579,91 @@ def hvi_grad_numpy(model, dr, X, members, lower, upper, parts=False, from_device
     return hvi, grad, dict(y=y, jac=jac, w=w, A_v=A_v, A_g=A_g)
 
 
+def tighten(lo, hi, sd, tau):
+    """The POLISH bounds of `feasible_merit_numpy` from the true intervals [lo, hi] (n_con,): plo = lo + tau sd, phi = hi - tau sd with sd
+    the constraints' prior standard deviations -- a quadratic penalty converges from outside the feasible set, so it is set against an
+    interval `tau` standard deviations inside the true one.  An interval narrower than 2 tau sd becomes its midpoint; infinite bounds
+    stay infinite.  Returns (plo, phi)."""
+    lo, hi, sd = np.asarray(lo, dtype=float).ravel(), np.asarray(hi, dtype=float).ravel(), np.asarray(sd, dtype=float).ravel()
+    plo, phi = lo + tau * sd, hi - tau * sd
+    with np.errstate(invalid="ignore"):
+        narrow = plo > phi
+        mid = 0.5 * lo + 0.5 * hi
+    return np.where(narrow, mid, plo), np.where(narrow, mid, phi)
+
+
+def feasible_scalarise_numpy(y, jac, n_obj, lower, upper, plo, phi, sigma2, minimize=True, rho=100.0):
+    """Phase B of `k_point_path_feasible` (kernels_point_path_feasible.hip) in its own operations and order, from path values y (B, m)
+    and their Jacobians jac (B, m, d); columns 0 .. n_obj - 1 the objectives, the rest constraints with polish bounds [plo, phi]:
+
+        i ascending:  d1 = plo_i - c_i, d2 = c_i - phi_i;  e = d1 > 0 ? d1 : 0;  up = d2 > e;  e = up ? d2 : e;  v = e inv_sd_i
+                      P = P + v v;  g = (2 v) inv_sd_i;  u_i = up ? g : 0 - g
+        n_obj = 1:    F = (s y_0) inv_sd_0, W_0 = s inv_sd_0                          (s = -1 when minimising)
+        n_obj >= 2:   (HVI, w) by `hvi_scalarise_numpy` over the objective columns;  F = HVI f_scale, W_t = w_t f_scale, f_scale = prod inv_sd_k
+        merit = F - rho P;   grad = W_0 J_0, + W_t J_t (t ascending), then - (rho u_i) J_{n_obj+i} (i ascending)
+
+    inv_sd = 1 / sqrt(sigma2) (m,); a NaN among the m values: merit = -inf and a zero gradient.  Returns (merit (B,), grad (B, d), a dict:
+    F, P (B,), W (B, n_obj), u (B, n_con))."""
+    y, jac = np.atleast_2d(np.asarray(y, dtype=float)), np.asarray(jac, dtype=float)
+    B, m = y.shape
+    n_obj = int(n_obj)
+    plo, phi = np.asarray(plo, dtype=float).ravel(), np.asarray(phi, dtype=float).ravel()
+    inv_sd = 1.0 / np.sqrt(np.asarray(sigma2, dtype=float).ravel())
+    if not 1 <= n_obj < m or len(plo) != m - n_obj or len(phi) != m - n_obj or len(inv_sd) != m:
+        raise ValueError("n_obj = %d objectives among %d targets; plo, phi one bound per constraint, sigma2 one value per target" % (n_obj, m))
+    P, u = np.zeros(B), np.zeros((B, m - n_obj))
+    with np.errstate(invalid="ignore"):
+        for i in range(m - n_obj):
+            c, isd = y[:, n_obj + i], inv_sd[n_obj + i]
+            d1, d2 = plo[i] - c, c - phi[i]
+            e = np.where(d1 > 0.0, d1, 0.0)
+            up = d2 > e
+            e = np.where(up, d2, e)
+            v = e * isd
+            P = P + v * v
+            g = (2.0 * v) * isd
+            u[:, i] = np.where(up, g, 0.0 - g)
+        if n_obj == 1:
+            s = -1.0 if minimize else 1.0
+            F, W = (s * y[:, 0]) * inv_sd[0], np.full((B, 1), s * inv_sd[0])
+        else:
+            f_scale = 1.0
+            for k in range(n_obj):
+                f_scale = f_scale * inv_sd[k]
+            hvi, _, w = hvi_scalarise_numpy(np.where(np.isnan(y[:, :n_obj]), 0.0, y[:, :n_obj]), jac[:, :n_obj], lower, upper)
+            F, W = hvi * f_scale, w * f_scale
+        merit = F - rho * P
+        grad = W[:, 0, None] * jac[:, 0]
+        for t in range(1, n_obj):
+            grad = grad + W[:, t, None] * jac[:, t]
+        for i in range(m - n_obj):
+            grad = grad - (rho * u[:, i])[:, None] * jac[:, n_obj + i]
+    bad = np.isnan(y).any(axis=1)
+    merit[bad], grad[bad] = -np.inf, 0.0
+    return merit, grad, dict(F=F, P=P, W=W, u=u)
+
+
+def feasible_merit_numpy(model, dr, X, members, n_obj, lower, upper, plo, phi, minimize=True, rho=100.0, parts=False, from_device=None,
+                         sigma2=None):
+    """The dense float64 restatement of `bogp_point_eval_path_feasible`: the merit (B,) of member members[b]'s joint draw of n_obj
+    objectives and the constraints at row b of X, and its input gradient (B, d):
+
+        merit = F - rho sum_i (e_i / sd_i)^2,   e_i = max(plo_i - c_i, c_i - phi_i, 0)       against the POLISH bounds (`tighten`)
+        F     = +-y_0 / sd_0  (n_obj = 1; lower = upper = None)   or   HVI(y_0 .. y_{n_obj-1}) / prod_k sd_k  over the cells (lower, upper)
+
+    y and J as `hvi_grad_numpy` restates them, the scalarisation by `feasible_scalarise_numpy`.  `parts=True` adds a dict: y (B, m), jac
+    (B, m, d), A_v, A_g (the sums of the absolute terms, `hvi_grad_numpy`'s) and F, P, W, u.  `from_device=(y, jac)` with `sigma2` (m,):
+    the scalarisation alone, on values the device returned -- it then reproduces the device's merit and gradient byte for byte."""
+    if from_device is not None:
+        merit, grad, p = feasible_scalarise_numpy(from_device[0], from_device[1], n_obj, lower, upper, plo, phi, sigma2, minimize, rho)
+        return (merit, grad, dict(p, y=from_device[0], jac=from_device[1])) if parts else (merit, grad)
+    st = state_of_multi(model)
+    m = st.y.shape[1]
+    _, _, p = hvi_grad_numpy(st, dr, X, members, np.zeros((1, m)), np.full((1, m), np.inf), parts=True)  # y, J and their absolute sums
+    merit, grad, ps = feasible_scalarise_numpy(p["y"], p["jac"], n_obj, lower, upper, plo, phi, st.sigma2 if sigma2 is None else sigma2, minimize, rho)
+    return (merit, grad, dict(ps, y=p["y"], jac=p["jac"], A_v=p["A_v"], A_g=p["A_g"])) if parts else (merit, grad)
+
+
 def merge_ranks(best_val, best_idx, k=None):
     """A member's proposal list from its rankings (n_tiers, k'), tier after tier: the A ranks whose value is above -inf (rows whose
     drawn constraints hold, best objective first), then the B ranks (least violating first) whose row is not already listed, then

@@ -967,6 +967,47 @@ int bogp_polish_path_hvi(bogp_handle* h, const double* X0, int B, const int* mem
                          const double* omega, const double* phase, const double* weights, const double* coef, int C, const double* lower,
                          const double* upper, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals);
 
+/* ---- the merit of a JOINT sample path under its drawn constraints and its input gradient at B points; the polish of the constrained
+ * Thompson batches.  Member j of bogp_sweep_thompson_constrained's (m_obj = 1) or bogp_sweep_thompson_ehvi_constrained's (m_obj >= 2) draw
+ * holds m = m_obj + n_con paths over shared features.  With y_k = path_{j,k}(x), k < m_obj, and c_i = path_{j,m_obj+i}(x), i < n_con:
+ *   e_i   = max(plo_i - c_i, c_i - phi_i, 0)
+ *   v_i   = e_i inv_sd_{m_obj+i}                       the sweeps' scaled excess, against the POLISH bounds plo, phi
+ *   P     = sum_i v_i v_i                              i ascending; continuously differentiable in c
+ *   F     = s y_0 inv_sd_0                             m_obj = 1; s = -1 when minimising, +1 otherwise
+ *   F     = HVI(y_0 .. y_{m_obj-1}) f_scale            m_obj >= 2; HVI over the C cells as bogp_point_eval_path_hvi forms it,
+ *                                                      f_scale = prod_{k < m_obj} inv_sd_k: rho is unit-free for every m_obj
+ *   merit = F - rho P                                  always MAXIMISED
+ *   d merit / dx = sum_t W_t dy_t/dx - sum_i (rho u_i) dc_i/dx,   W = s inv_sd_0 or w_t f_scale,   u_i = +-(2 v_i) inv_sd_{m_obj+i}
+ * (+ above phi_i, - below plo_i; the objective terms with t ascending, then the constraint terms with i ascending).  A quadratic penalty
+ * converges from OUTSIDE the feasible set, so the caller passes TIGHTENED bounds (bogp.thompson.tighten: plo = lo + tau sd, phi = hi - tau
+ * sd, the midpoint where the interval is narrower than 2 tau sd, infinite bounds kept); the library knows nothing of tau.  ONE launch
+ * (csrc/kernels_point_path_feasible.hip) forms y, J = dy/dx, the merit and its gradient; y and J are bogp_point_eval_path_hvi's bits for
+ * the same columns.  Given the returned y and J, merit and gradient follow byte for byte in the kernel's stated order
+ * (bogp.thompson.feasible_merit_numpy(from_device=)): no fused multiply-add is used there.  A NaN among the m values gives merit = -inf
+ * and a zero gradient.  A point's outputs do not depend on B, on where the point stands, on the members beside it or on which outputs are
+ * asked for.
+ *   m_obj, q, L, omega, phase, weights   as the sweep took them (weights L x q m, column j m + t);  coef: N x q m, its coef_out
+ *   C, lower, upper         m_obj >= 2: the cells (C x m_obj) as bogp_sweep_thompson_ehvi_constrained takes them; m_obj = 1: C = 0 and NULL
+ *   n_con, plo, phi         the polish bounds, n_con HOST values each, either may be infinite
+ *   minimize                m_obj = 1 only (ignored otherwise);  rho >= 0, finite
+ *   `point_eval_path_feasible`   Xb: B x d (host).  merit_out (B); grad_out (B x d), y_out (B x m), jac_out (B x m x d) may each be NULL.
+ *   `polish_path_feasible`  bogp_polish_path's loop, state, stop rules and read-back on this evaluation, two launches an iteration:
+ *                           fout[b] = the merit of member[b]'s draw at Xout[b] >= that at X0[b] clipped into [box_lo, box_hi].
+ * BOGP_ERR_INVALID: m_obj < 1, n_con < 1, null plo / phi, rho < 0 or not finite, no committed model, a model of one target, m_obj + n_con
+ * != n_targets, q < 1 or q m > BOGP_MAX_PATHS, L, B or C out of range (C != 0 or non-null cells with m_obj = 1), a member outside [0, q),
+ * a null required array, a cell bound the sweep refuses, a non-finite entry in omega, phase, weights or coef, a NaN polish bound, phi <
+ * plo, box_lo > box_hi, max_evals <= 0.  BOGP_ERR_UNSUPPORTED: a forest on the handle; a lift; a polynomial basis; the noisy and
+ * noise-estimating modes; the cubic and generalized-exponential kernels (no spectral draw) and the general-nu Matern kernel (no
+ * corr_dx); d > BOGP_MAX_DIM; more than one rank.  Candidates and later sweeps are unaffected. */
+int bogp_point_eval_path_feasible(bogp_handle* h, const double* Xb, int B, const int* member, int m_obj, int q, int L, const double* omega,
+                                  const double* phase, const double* weights, const double* coef, int C, const double* lower,
+                                  const double* upper, int n_con, const double* plo, const double* phi, int minimize, double rho,
+                                  double* merit_out, double* grad_out, double* y_out, double* jac_out);
+int bogp_polish_path_feasible(bogp_handle* h, const double* X0, int B, const int* member, const double* box_lo, const double* box_hi, int m_obj,
+                              int q, int L, const double* omega, const double* phase, const double* weights, const double* coef, int C,
+                              const double* lower, const double* upper, int n_con, const double* plo, const double* phi, int minimize,
+                              double rho, int max_evals, double pgtol, double factr, double* Xout, double* fout, int* n_evals);
+
 /* ---- multi-GPU: the one exchange step per sweep ------------------------------------------
  * Nothing like it exists in the reference (its only parallelism is joblib over the q criteria, bayes_opt.py:108-111);
  * this is the cross-rank half of the new inner maximiser behind acquisition/optim/__init__.py:55-153.  One process per
