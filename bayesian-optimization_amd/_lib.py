@@ -77,6 +77,7 @@ SIGNATURES = {
     "bogp_sweep": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, _dp, _lp, _dp]),
     "bogp_sweep_topk": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _lp]),
     "bogp_sweep_ehvi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp]),
+    "bogp_sweep_ehvi_grid": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_int, _dp, _ip, C.c_int, _dp, _lp, _dp, _dp, _dp]),
     "bogp_feasibility": (C.c_double, [C.c_double] * 5),
     "bogp_sweep_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_sweep_ehvi_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
@@ -704,6 +705,33 @@ class Engine:
         self._last_q, self._last_topk = -1, (-1, -1)
         self._check(self._lib.bogp_sweep_ehvi(self._h, int(m), int(C_), _ptr(lower), _ptr(upper), int(k), _ptr(best),
                                               idx.ctypes.data_as(_lp), _ptr(vals), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_moments:
+            out += (mu, mse)
+        return out
+
+    def sweep_ehvi_grid(self, grid, k: int = 1, return_values=False, return_moments=False):
+        """`sweep_ehvi` for the cells of `grid` (`bogp.pareto.hypercell_grid`: `edges`, `last_val`, `last_idx`), evaluated per axis
+        and not per cell (bogp_sweep_ehvi_grid): the same results, the values to rounding."""
+        edges = [_f64(e).ravel() for e in grid.edges]
+        m = len(edges) + 1
+        n_cells = np.array([len(e) - 1 for e in edges], dtype=np.int32)
+        flat = _f64(np.concatenate(edges))
+        last_val = _f64(grid.last_val).ravel()
+        last_idx = np.ascontiguousarray(grid.last_idx, dtype=np.int32).ravel()
+        if m < 2 or len(last_idx) < int(np.prod(n_cells, dtype=np.int64)):  # (what the library reads; it checks every value itself)
+            raise ValueError("a grid needs an axis and one last_idx entry per column")
+        best = np.empty(int(k))
+        idx = np.empty(int(k), dtype=np.int64)
+        vals = np.empty(self.M) if return_values else None
+        mu = np.empty((self.M, m)) if return_moments else None
+        mse = np.empty((self.M, m)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_ehvi_grid(self._h, int(m), n_cells.ctypes.data_as(_ip), _ptr(flat), len(last_val), _ptr(last_val),
+                                                   last_idx.ctypes.data_as(_ip), int(k), _ptr(best), idx.ctypes.data_as(_lp), _ptr(vals),
+                                                   _ptr(mu), _ptr(mse)))  # fmt: skip
         out = (best, idx)
         if return_values:
             out += (vals,)

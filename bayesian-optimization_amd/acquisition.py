@@ -320,14 +320,24 @@ class EHVI:
 
     The model may also be a `RandomForest` fitted on y (N, m) -- this package's or the reference's, as MOBO fits it on mixed
     spaces: rows then come in the reference's format (level labels in the categorical columns), and the forest walk and the
-    criterion are one device pass (`bogp_forest_sweep_ehvi`).  A forest whose outputs differ from `n_obj` is refused."""
+    criterion are one device pass (`bogp_forest_sweep_ehvi`).  A forest whose outputs differ from `n_obj` is refused.
+
+    `factored=True` (with `Y=`, Gaussian-process models only): the grid that the cells of `Y`'s front form is kept beside them
+    (`bogp.pareto.hypercell_grid`) and `sweep()` -- hence `criterion(X)` on the sweep route -- evaluates it per axis and not per
+    cell (`bogp_sweep_ehvi_grid`): the same values to rounding, faster on fronts of many cells.  The point path and the input
+    gradient keep the cells.  With `cells=` or `partitioning=` no grid is known: ValueError."""
 
     is_ehvi = True
     minimize = False  # (the sweep helpers read it off every criterion)
 
-    def __init__(self, model=None, ref_point=None, partitioning=None, Y=None, cells=None, input_gradient: bool = False):
+    def __init__(self, model=None, ref_point=None, partitioning=None, Y=None, cells=None, input_gradient: bool = False,
+                 factored: bool = False):
         if model is None:
             raise ValueError("model cannot be None")
+        if factored and _forest.is_forest_model(model):
+            raise NotImplementedError("EHVI(factored=True) takes a Gaussian process model: a forest's sweep evaluates the cells")
+        if factored and Y is None:
+            raise ValueError("EHVI(factored=True) needs Y=: cells= and partitioning= give cells whose grid is not known")
         if input_gradient and _forest.is_forest_model(model):
             raise NotImplementedError("a forest has no input gradient (the reference's RandomForest has none either): "
                                       "EHVI(input_gradient=True) takes a Gaussian process model")  # fmt: skip
@@ -338,6 +348,7 @@ class EHVI:
             raise ValueError("EHVI needs a ref_point")
         self.model = model
         self.ref_point = np.asarray(ref_point, dtype=float).ravel()
+        self.grid = None  # factored=True: the cells' grid form
         m = len(self.ref_point)
         pareto_Y = None
         if partitioning is not None:
@@ -353,10 +364,12 @@ class EHVI:
             if Y.shape[1] != m:
                 raise ValueError("The length of the reference point must match the number of outcomes. Got ref_point with "
                                  "%d elements, but expected %d." % (m, Y.shape[1]))  # fmt: skip
-            from .pareto import hypercell_bounds, pareto_front
+            from .pareto import hypercell_bounds, hypercell_grid, pareto_front
 
             pareto_Y = pareto_front(Y, self.ref_point)  # (as the reference's partitioning keeps only points above the reference point)
             lower, upper = hypercell_bounds(Y, self.ref_point)
+            if factored:
+                self.grid = hypercell_grid(Y, self.ref_point)
         else:
             lower, upper = (np.asarray(c, dtype=float) for c in cells)
         if pareto_Y is not None and len(pareto_Y) and not np.any(np.all(pareto_Y > self.ref_point, axis=1)):
@@ -384,6 +397,8 @@ class EHVI:
             return _forest.ehvi_sweep(self, k=k, return_values=return_values)
         if getattr(model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
+        if self.grid is not None:
+            return model.engine.sweep_ehvi_grid(self.grid, k=k, return_values=return_values)
         return model.engine.sweep_ehvi(self.cell_lower_bounds, self.cell_upper_bounds, k=k, return_values=return_values)
 
     def __call__(self, X, return_dx: bool = False):

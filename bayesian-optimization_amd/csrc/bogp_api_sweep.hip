@@ -800,6 +800,12 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
         ea.ehvi_out = h->dacq_out; ea.mu_out = rq.want_out ? h->dmu_out : nullptr; ea.mse_out = rq.want_out ? h->dmse_out : nullptr;
         ea.blk_val = h->dblk_val; ea.blk_idx = h->dblk_idx; ea.blk_offset = cx.blk_offset;
         HIPCHK(h, launch_ehvi(ea, st));
+      } else if (rq.eg) {  // ... the same criterion factored over the grid of the front's cells (kernels_ehvi_grid.hip)
+        EhviGridArgs eg = *rq.eg;
+        multi_target_chunk(h, cx, b, m0, mcount, eg);
+        eg.ehvi_out = h->dacq_out; eg.mu_out = rq.want_out ? h->dmu_out : nullptr; eg.mse_out = rq.want_out ? h->dmse_out : nullptr;
+        eg.blk_val = h->dblk_val; eg.blk_idx = h->dblk_idx; eg.blk_offset = cx.blk_offset;
+        HIPCHK(h, launch_ehvi_grid(eg, st));
       } else if (rq.cn) {  // ... or the q feasibility-weighted criteria of the m-target posterior (kernels_constrained.hip)
         ConstrainedArgs cn = *rq.cn;
         multi_target_chunk(h, cx, b, m0, mcount, cn);
@@ -1006,9 +1012,9 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   h->pilot_kind = BOGP_PRUNE_PILOT_NONE; h->pilot_rows = 0;
   int e;
   // the two single-target shortcuts (the multi-target requests -- bogp_sweep_ehvi: eh non-null, bogp_sweep_constrained: cn non-null,
-  // bogp_sweep_ehvi_constrained: ec non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
+  // bogp_sweep_ehvi_constrained: ec non-null, bogp_sweep_ehvi_grid: eg non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
   // with: the whole upload first (one launch reads every candidate)
-  const bool multi = rq.eh || rq.cn || rq.ec;
+  const bool multi = rq.eh || rq.cn || rq.ec || rq.eg;
   const bool small_batch = !multi && M <= 32 && h->p == 1;
   if (small_batch || (!multi && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
     if ((e = lazy_finish(h))) return e;

@@ -23,8 +23,8 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
                     double plugin, int minimize, double* mu, double* mse, double* dmu, double* dmse, double* acq, double* dacq);
 // bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
 // m-target EHVI of bogp_api_ehvi.hip, or -- cn non-null -- the feasibility-weighted criteria of bogp_api_constrained.hip, or -- ec
-// non-null -- the feasibility-weighted EHVI of bogp_api_ehvi_constrained.hip, all on the chunked path), and the reset of the winners a
-// sweep left on the device
+// non-null -- the feasibility-weighted EHVI of bogp_api_ehvi_constrained.hip, or -- eg non-null -- EHVI over the grid of the cells,
+// all on the chunked path), and the reset of the winners a sweep left on the device
 struct SweepRequest {
   bool want_out = false, want_acq_out = false;  // mu / MSE of every candidate into dmu_out / dmse_out (EHVI: M x m moments); the q x M values into dacq_out
   bool need_var = true, sync = true;            // false: the contraction is skipped (predict without eval_MSE); false: queued, not waited for
@@ -35,7 +35,8 @@ struct SweepRequest {
   const EhviArgs* eh = nullptr;
   const ConstrainedArgs* cn = nullptr;  // (q, acq_id, acq_par, plugin, minimize above are the criteria it weights)
   const ConstrainedEhviArgs* ec = nullptr;  // bogp_sweep_ehvi_constrained: EHVI of the objectives times the constraints' feasibility
-  int targets() const { return eh ? eh->m : cn ? cn->m : ec ? ec->m : 1; }  // moments per candidate in dmu_out / dmse_out
+  const EhviGridArgs* eg = nullptr;         // bogp_sweep_ehvi_grid: EHVI factored over the grid of the front's cells
+  int targets() const { return eh ? eh->m : cn ? cn->m : ec ? ec->m : eg ? eg->m : 1; }  // moments per candidate in dmu_out / dmse_out
 };
 int run_sweep(bogp_handle* h, const SweepRequest& rq);
 void invalidate_sweep_results(bogp_handle* h);
@@ -293,6 +294,8 @@ struct bogp_handle {
   bogp::DevBuf<double> dtopk_val;  // [q][k] winners of bogp_sweep_topk (device-resident between its passes)
   bogp::DevBuf<int64_t> dtopk_idx;
   bogp::DevBuf<double> dehvi_cells;  // bogp_sweep_ehvi: [lower C x m | upper C x m]
+  bogp::DevBuf<double> dehvi_grid;   // bogp_sweep_ehvi_grid: the E thresholds of a row's table (EhviGridArgs::pts)
+  bogp::DevBuf<int> dehvi_grid_idx;  // ... and last_idx [C]
   bogp::DevBuf<double> dpof_out;     // bogp_sweep_constrained: [M] probability of feasibility (pof_out requested)
   // host copy of the cells bogp_point_eval_ehvi / bogp_polish_ehvi left in dehvi_cells ([lower | upper], ehvi_host_C x ehvi_host_m): a call
   // with the same cells skips the upload.  Empty <=> unknown: every other writer of dehvi_cells clears it (ehvi_cells_forget)

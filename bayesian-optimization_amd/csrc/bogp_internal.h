@@ -247,6 +247,30 @@ struct EhviArgs : MultiTargetChunk {
 };
 hipError_t launch_ehvi(const EhviArgs& a, hipStream_t st);
 
+// the same criterion over the GRID the cells of a front form, factored per axis (kernels_ehvi_grid.hip): takes k_ehvi's place in the
+// chunk loop of bogp_sweep_ehvi_grid.  Axis k < m - 1 has n[k] intervals; the columns are row-major over (i_0 .. i_{m-2}), axis 0
+// slowest; column c's lower bound on the last axis is last_val[last_idx[c]].  A row's table has E = sum n[k] + V entries: entry
+// off[k] + i belongs to interval i of axis k, entry off[m - 1] + v to last_val[v]; pts[e] is entry e's threshold -- the interval's
+// (finite) lower edge or last_val[v] -- so interval i's upper edge is pts[e + 1] and the last interval of an axis ends at +inf.
+// (MultiTargetChunk's fields stay where they are, the comment above it says why; everything new stands behind them.)
+constexpr int EHVI_GRID_TABLE = 3072;  // doubles of LDS a workgroup's tables take: 12 entries per lane
+struct EhviGridArgs : MultiTargetChunk {
+  const double* pts;       // [E] (device)
+  const int* last_idx;     // [C] (device), each in [0, V)
+  int n[8], off[8];        // n[k], k < m - 1; off[k], k <= m - 1
+  int step[8];             // the lane group's size in the columns' mixed radix: digit k of axis k (what a lane adds per round)
+  int E, C;
+  int group;               // lanes that share a row: 16 (E <= 192) or 64
+  int tabled;              // E <= 12 group: the factors come from a table in LDS; else every column forms its own
+  double* ehvi_out;        // [M] (global index m0 + i)
+  double* mu_out;          // [M][m] or null
+  double* mse_out;         // [M][m] or null
+  double* blk_val;         // per-block partial argmax
+  int64_t* blk_idx;
+  int64_t blk_offset;
+};
+hipError_t launch_ehvi_grid(const EhviGridArgs& a, hipStream_t st);
+
 // q feasibility-weighted criteria of an m-target model over one chunk (kernels_constrained.hip): target 0 is the objective, targets
 // 1 .. m - 1 are constraints feasible in [lo_k, hi_k]; replaces AcqArgs / k_acquisition in the chunk loop of bogp_sweep_constrained
 struct ConstrainedArgs : MultiTargetChunk {

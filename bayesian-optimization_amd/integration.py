@@ -197,7 +197,9 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
                                              reduce_output=return_dx)  # fmt: skip
     if optimizer not in _SWEEPS or not served:
         return _ORIGINAL["mobo"](self, fixed=fixed, **kwargv)
-    criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float))
+    # install(ehvi_factored=True): the sweep evaluates the front's grid per axis (bogp_sweep_ehvi_grid) and not per cell
+    criterion = acquisition.EHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), Y=np.asarray(self.y, dtype=float),
+                                 **(dict(factored=True) if _EHVI.get("factored") else {}))  # fmt: skip
     return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
 
 
@@ -675,7 +677,7 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
             ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False,
             constrained_mobo_thompson: bool = False, constraint_thompson_polish: bool = False,
-            constrained_mobo_thompson_polish: bool = False):
+            constrained_mobo_thompson_polish: bool = False, ehvi_factored: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -764,6 +766,11 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     `constrained_mobo_thompson_polish=True` (with `constrained_mobo_thompson=True`; alone it raises ValueError): the same refinement for
     these members (`optim.constrained_ehvi_thompson_batch(polish=True)`).
 
+    `ehvi_factored=True`: the plain EHVI criterion of `MOBO` (a device GP, a continuous space, an optimiser of the sweep family) is
+    built with `factored=True`, so each sweep evaluates the grid of the front's cells per axis (`bogp_sweep_ehvi_grid`) and not per
+    cell: the same proposals to rounding, faster on fronts of many cells.  The forest, gradient, believer, Thompson and constrained
+    routes keep the cell loop.
+
     `ehvi_thompson=True` (together with `batch_strategy="believer"` it raises ValueError): the reference's `MOBO(n_point=q)` proposes
     its q points by `optim.ehvi_thompson_batch` -- per point one joint draw of the objectives, and the candidate whose drawn vector
     adds the most hypervolume to the front (the one nearest to the non-dominated region where the draw improves nowhere) -- with the
@@ -836,6 +843,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         _EHVI["thompson"] = True
     if ehvi_thompson_polish:
         _EHVI["thompson_polish"] = True
+    if ehvi_factored:
+        _EHVI["factored"] = True
     if thompson_polish and batch_strategy != "thompson":
         raise ValueError("thompson_polish=True refines the paths of batch_strategy='thompson'")
     _BATCH.clear()

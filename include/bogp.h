@@ -294,6 +294,27 @@ int bogp_sweep_topk(bogp_handle* h, int q, const int* acq_id, const double* acq_
 int bogp_sweep_ehvi(bogp_handle* h, int m, int C, const double* lower, const double* upper, int k, double* best_val,
                     int64_t* best_idx, double* ehvi_out, double* mu_out, double* mse_out);
 
+/* ---- sweep: the same criterion, factored over the grid of the front's cells -----------------------------
+ * bogp_sweep_ehvi's EHVI (analytic.py:176-274) for cells that form a grid, as those of a front do (bogp_ehvi_grid_cells, and
+ * pareto.hypercell_grid in Python): axis a < m - 1 is cut at edges_a[0] < .. < edges_a[n_a] = +inf into n_a intervals, the columns
+ * are the products of one interval per axis, row-major with axis 0 slowest, and column c is the cell
+ * [column] x [last_val[last_idx[c]], +inf).  Per candidate the factor of an interval, sd_a (G(lower) - G(upper)), is formed once
+ * per axis and interval and the factor of a last-axis value once per value -- sum n_a + V values of G instead of 2 m per cell --
+ * and EHVI = sum_c prod_a factor_a[i_a(c)] x factor_last[last_idx[c]].  The values agree with bogp_sweep_ehvi on the expanded cells to
+ * rounding (the same factors, another order of summation: it depends on m, n_a and V alone); mu_out / mse_out are its bytes.
+ *   m            targets of the committed model, 2 <= m <= BOGP_MAX_TARGETS
+ *   n_cells      (m - 1) intervals per axis, each >= 1; their product, the columns, is at most BOGP_MAX_EHVI_CELLS
+ *   edges        the axes' edges, concatenated: sum (n_a + 1) HOST doubles; per axis the first finite, strictly increasing, the
+ *                last +inf
+ *   V, last_val  1 <= V <= columns distinct lower bounds on the last axis, finite and strictly increasing
+ *   last_idx     (columns) indices into last_val
+ *   k, best_val, best_idx, ehvi_out, mu_out, mse_out: as bogp_sweep_ehvi
+ * Refusals: bogp_sweep_ehvi's, in its order, then BOGP_ERR_INVALID for a grid that breaks a rule above, the message naming the
+ * axis or the index.  The time of the kernel is reported as acquisition_ms by bogp_last_timing.                  */
+int bogp_sweep_ehvi_grid(bogp_handle* h, int m, const int* n_cells, const double* edges, int V, const double* last_val,
+                         const int32_t* last_idx, int k, double* best_val, int64_t* best_idx, double* ehvi_out, double* mu_out,
+                         double* mse_out);
+
 /* ---- sweep: modelled constraints, feasibility-weighted criteria ---------------------------------------
  * The reference accepts the values of expensive constraints and drops them (BaseBO.tell: base.py:328; BaseMOBO.tell:
  * mobo.py:117-118); its cheap callables h / g are handled by a penalty or a filter.  Here the committed model has m = n_targets
