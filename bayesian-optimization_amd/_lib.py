@@ -81,6 +81,8 @@ SIGNATURES = {
     "bogp_feasibility": (C.c_double, [C.c_double] * 5),
     "bogp_sweep_constrained": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_sweep_ehvi_constrained": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
+    "bogp_sweep_ehvi_constrained_grid": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_int, _dp, _ip, C.c_int, _dp, _dp, C.c_int, _dp, _lp, _dp, _dp,
+                                                   _dp, _dp]),
     "bogp_sweep_believer": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_int, _dp, C.c_int, _dp, _lp, _dp, _dp, _dp, _dp]),
     "bogp_believer_last": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "bogp_sweep_thompson": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _lp, _dp, _dp, _dp]),
@@ -712,9 +714,9 @@ class Engine:
             out += (mu, mse)
         return out
 
-    def sweep_ehvi_grid(self, grid, k: int = 1, return_values=False, return_moments=False):
-        """`sweep_ehvi` for the cells of `grid` (`bogp.pareto.hypercell_grid`: `edges`, `last_val`, `last_idx`), evaluated per axis
-        and not per cell (bogp_sweep_ehvi_grid): the same results, the values to rounding."""
+    @staticmethod
+    def _pack_grid(grid):
+        """(axes + 1, n_cells, the edges concatenated, last_val, last_idx) of a `bogp.pareto.hypercell_grid`, as the grid entries take them"""
         edges = [_f64(e).ravel() for e in grid.edges]
         m = len(edges) + 1
         n_cells = np.array([len(e) - 1 for e in edges], dtype=np.int32)
@@ -723,6 +725,12 @@ class Engine:
         last_idx = np.ascontiguousarray(grid.last_idx, dtype=np.int32).ravel()
         if m < 2 or len(last_idx) < int(np.prod(n_cells, dtype=np.int64)):  # (what the library reads; it checks every value itself)
             raise ValueError("a grid needs an axis and one last_idx entry per column")
+        return m, n_cells, flat, last_val, last_idx
+
+    def sweep_ehvi_grid(self, grid, k: int = 1, return_values=False, return_moments=False):
+        """`sweep_ehvi` for the cells of `grid` (`bogp.pareto.hypercell_grid`: `edges`, `last_val`, `last_idx`), evaluated per axis
+        and not per cell (bogp_sweep_ehvi_grid): the same results, the values to rounding."""
+        m, n_cells, flat, last_val, last_idx = self._pack_grid(grid)
         best = np.empty(int(k))
         idx = np.empty(int(k), dtype=np.int64)
         vals = np.empty(self.M) if return_values else None
@@ -793,6 +801,34 @@ class Engine:
         self._check(self._lib.bogp_sweep_ehvi_constrained(self._h, int(m), int(C_), _ptr(lower) if C_ else None, _ptr(upper) if C_ else None,
                                                           len(lo), _ptr(lo), _ptr(hi), int(k), _ptr(best), idx.ctypes.data_as(_lp),
                                                           _ptr(vals), _ptr(pof), _ptr(mu), _ptr(mse)))  # fmt: skip
+        out = (best, idx)
+        if return_values:
+            out += (vals,)
+        if return_pof:
+            out += (pof,)
+        if return_moments:
+            out += (mu, mse)
+        return out
+
+    def sweep_ehvi_constrained_grid(self, grid, lo, hi, k: int = 1, return_values=False, return_pof=False, return_moments=False):
+        """`sweep_ehvi_constrained` for the cells of `grid` (`bogp.pareto.hypercell_grid` of the feasible front, over the objectives),
+        EHVI evaluated per axis and only for the rows whose probability of feasibility is not 0 (bogp_sweep_ehvi_constrained_grid):
+        the same results, the values to rounding.  A grid has at least one cell: the probability of feasibility alone stays with
+        `sweep_ehvi_constrained` and its empty cell arrays."""
+        lo, hi = self._constraint_bounds(lo, hi)
+        m, n_cells, flat, last_val, last_idx = self._pack_grid(grid)
+        mt = m + len(lo)
+        best = np.empty(int(k))
+        idx = np.empty(int(k), dtype=np.int64)
+        vals = np.empty(self.M) if return_values else None
+        pof = np.empty(self.M) if return_pof else None
+        mu = np.empty((self.M, mt)) if return_moments else None
+        mse = np.empty((self.M, mt)) if return_moments else None
+        self._last_q, self._last_topk = -1, (-1, -1)
+        self._check(self._lib.bogp_sweep_ehvi_constrained_grid(self._h, int(m), n_cells.ctypes.data_as(_ip), _ptr(flat), len(last_val),
+                                                               _ptr(last_val), last_idx.ctypes.data_as(_ip), len(lo), _ptr(lo), _ptr(hi),
+                                                               int(k), _ptr(best), idx.ctypes.data_as(_lp), _ptr(vals), _ptr(pof), _ptr(mu),
+                                                               _ptr(mse)))  # fmt: skip
         out = (best, idx)
         if return_values:
             out += (vals,)

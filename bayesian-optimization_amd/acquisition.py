@@ -568,7 +568,13 @@ class ConstrainedEHVI:
     `EHVI(input_gradient=True)` returns -- one row: ((1,), (1, d)); M rows: ((M, 1), (M, d)) -- through
     `bogp_point_eval_ehvi_constrained` (EHVI's gradient and the gradient of the probability of feasibility multiplied on the device;
     a feasibility-only criterion has the gradient of that probability), `criterion(X)` for at most 64 rows takes the same call, and
-    `argmax_restart` serves "BFGS", "sweep-BFGS" and "sweep-device-BFGS" for it."""
+    `argmax_restart` serves "BFGS", "sweep-BFGS" and "sweep-device-BFGS" for it.
+
+    `factored=True`: with a feasible row, the grid that the cells of the feasible front form is kept beside them
+    (`bogp.pareto.hypercell_grid`, `grid`) and `sweep()` -- hence `criterion(X)` on the sweep route -- evaluates it per axis, and only for
+    the rows whose probability of feasibility is not 0 (`bogp_sweep_ehvi_constrained_grid`): the same values to rounding.  The point
+    path, the input gradient and the batch strategies keep the cells.  With no feasible row there is no grid and the criterion is the
+    probability of feasibility alone, as without it.  With `cells=` no grid is known: ValueError."""
 
     is_ehvi = True  # (the sweep helpers serve it through `.sweep()`, as they serve EHVI)
     is_constrained_ehvi = True  # ... and everything that does more than call `.sweep()` asks for this flag first
@@ -576,9 +582,12 @@ class ConstrainedEHVI:
     input_gradient = False
     minimize = False  # (the sweep helpers read it off every criterion)
 
-    def __init__(self, model=None, ref_point=None, lo=None, hi=None, Y=None, cells=None, input_gradient: bool = False):
+    def __init__(self, model=None, ref_point=None, lo=None, hi=None, Y=None, cells=None, input_gradient: bool = False,
+                 factored: bool = False):
         if model is None:
             raise ValueError("model cannot be None")
+        if factored and cells is not None:
+            raise ValueError("ConstrainedEHVI(factored=True) takes the model's rows or Y=: cells= gives cells whose grid is not known")
         self.input_gradient = bool(input_gradient)
         if _forest.is_forest_model(model):
             raise NotImplementedError("constrained EHVI (bogp.ConstrainedEHVI) takes a multi-target Gaussian process: a forest model is not served")
@@ -607,6 +616,7 @@ class ConstrainedEHVI:
         feasible = np.all((y[:, m:] >= self.lo) & (y[:, m:] <= self.hi), axis=1)
         self.n_feasible = int(feasible.sum())
         self.pareto_Y = None
+        self.grid = None  # factored=True and a feasible row: the cells' grid form
         self.from_cells = cells is not None  # (pareto_Y is None both for cells= and for "no feasible row": this tells them apart)
         if cells is not None:
             lower, upper = (np.atleast_2d(np.asarray(c, dtype=float)) for c in cells)
@@ -619,6 +629,10 @@ class ConstrainedEHVI:
 
                 self.pareto_Y = pareto_front(Y[feasible], self.ref_point)
                 lower, upper = (np.atleast_2d(b) for b in hypercell_bounds(Y[feasible], self.ref_point))
+                if factored:
+                    from .pareto import hypercell_grid
+
+                    self.grid = hypercell_grid(Y[feasible], self.ref_point)
             else:  # nothing to improve on yet: the probability of feasibility alone
                 lower = upper = np.zeros((0, m))
         if lower.shape != upper.shape or lower.shape[1] != m:
@@ -643,6 +657,8 @@ class ConstrainedEHVI:
         """The sweep over the engine's current candidates: (best (k,), idx (k,)[, values (M,)])."""
         if getattr(self.model, "_committed_par", None) is None:
             raise Exception("The model is not fitted yet!")
+        if self.grid is not None:
+            return self.model.engine.sweep_ehvi_constrained_grid(self.grid, self.lo, self.hi, k=int(k), return_values=return_values)
         return self.model.engine.sweep_ehvi_constrained(self.cell_lower_bounds, self.cell_upper_bounds, self.lo, self.hi, k=int(k),
                                                         return_values=return_values)  # fmt: skip
 

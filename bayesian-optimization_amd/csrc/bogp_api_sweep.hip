@@ -819,6 +819,13 @@ static int sweep_chunks(bogp_handle* h, SweepCtx& cx, int64_t c_begin, int64_t c
         ec.val_out = h->dacq_out; ec.mu_out = rq.want_out ? h->dmu_out : nullptr; ec.mse_out = rq.want_out ? h->dmse_out : nullptr;
         ec.blk_val = h->dblk_val; ec.blk_idx = h->dblk_idx; ec.blk_offset = cx.blk_offset;
         HIPCHK(h, launch_ehvi_constrained(ec, st));
+      } else if (rq.ecg) {  // ... the same criterion over the grid of the feasible front's cells (kernels_ehvi_constrained_grid.hip)
+        ConstrainedEhviGridArgs eg = *rq.ecg;  // (ConstrainedEhviArgs' field order)
+        eg.rT = h->drT[b]; eg.ss_part = h->dss_part; eg.w_part = h->dw_part[b]; eg.S = S; eg.nJ = cx.nJ_main; eg.Mc = Mc;
+        eg.mcount = mcount; eg.m0 = m0; eg.beta = h->beta; eg.G = h->G; eg.estimate_trend = h->estimate_trend;
+        eg.val_out = h->dacq_out; eg.mu_out = rq.want_out ? h->dmu_out : nullptr; eg.mse_out = rq.want_out ? h->dmse_out : nullptr;
+        eg.blk_val = h->dblk_val; eg.blk_idx = h->dblk_idx; eg.blk_offset = cx.blk_offset;
+        HIPCHK(h, launch_ehvi_constrained_grid(eg, st));
       } else {
         HIPCHK(h, launch_acquisition(aa, st));
       }
@@ -1012,9 +1019,9 @@ int bogp::run_sweep(bogp_handle* h, const SweepRequest& rq) {
   h->pilot_kind = BOGP_PRUNE_PILOT_NONE; h->pilot_rows = 0;
   int e;
   // the two single-target shortcuts (the multi-target requests -- bogp_sweep_ehvi: eh non-null, bogp_sweep_constrained: cn non-null,
-  // bogp_sweep_ehvi_constrained: ec non-null, bogp_sweep_ehvi_grid: eg non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
+  // bogp_sweep_ehvi_constrained: ec non-null, bogp_sweep_ehvi_grid: eg non-null, bogp_sweep_ehvi_constrained_grid: ecg non-null -- take neither: they always run the chunked path below); nothing to overlap a lazy upload
   // with: the whole upload first (one launch reads every candidate)
-  const bool multi = rq.eh || rq.cn || rq.ec || rq.eg;
+  const bool multi = rq.eh || rq.cn || rq.ec || rq.eg || rq.ecg;
   const bool small_batch = !multi && M <= 32 && h->p == 1;
   if (small_batch || (!multi && h->p == 1 && sweep_small_supported(Np, h->d, h->kernel))) {
     if ((e = lazy_finish(h))) return e;

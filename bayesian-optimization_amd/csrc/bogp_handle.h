@@ -24,7 +24,7 @@ int point_eval_host(bogp_handle* h, const char* who, const double* Xb, int B, in
 // bogp_api_sweep.hip: the posterior sweep over the current candidates (single-target criteria, or -- eh non-null -- the
 // m-target EHVI of bogp_api_ehvi.hip, or -- cn non-null -- the feasibility-weighted criteria of bogp_api_constrained.hip, or -- ec
 // non-null -- the feasibility-weighted EHVI of bogp_api_ehvi_constrained.hip, or -- eg non-null -- EHVI over the grid of the cells,
-// all on the chunked path), and the reset of the winners a sweep left on the device
+// or -- ecg non-null -- the feasibility-weighted EHVI over that grid, all on the chunked path), and the reset of the winners a sweep left on the device
 struct SweepRequest {
   bool want_out = false, want_acq_out = false;  // mu / MSE of every candidate into dmu_out / dmse_out (EHVI: M x m moments); the q x M values into dacq_out
   bool need_var = true, sync = true;            // false: the contraction is skipped (predict without eval_MSE); false: queued, not waited for
@@ -36,7 +36,8 @@ struct SweepRequest {
   const ConstrainedArgs* cn = nullptr;  // (q, acq_id, acq_par, plugin, minimize above are the criteria it weights)
   const ConstrainedEhviArgs* ec = nullptr;  // bogp_sweep_ehvi_constrained: EHVI of the objectives times the constraints' feasibility
   const EhviGridArgs* eg = nullptr;         // bogp_sweep_ehvi_grid: EHVI factored over the grid of the front's cells
-  int targets() const { return eh ? eh->m : cn ? cn->m : ec ? ec->m : eg ? eg->m : 1; }  // moments per candidate in dmu_out / dmse_out
+  const ConstrainedEhviGridArgs* ecg = nullptr;  // bogp_sweep_ehvi_constrained_grid: ec's criterion over eg's grid, on the live rows only
+  int targets() const { return eh ? eh->m : cn ? cn->m : ec ? ec->m : eg ? eg->m : ecg ? ecg->m : 1; }  // moments per candidate in dmu_out / dmse_out
 };
 int run_sweep(bogp_handle* h, const SweepRequest& rq);
 void invalidate_sweep_results(bogp_handle* h);
@@ -68,6 +69,11 @@ int check_ehvi_cells(bogp_handle* h, const char* who, size_t nb, const double* l
 int stage_ehvi_cells(bogp_handle* h, const double* lower, const double* upper, size_t nb, hipStream_t st);
 // bogp_api_constrained.hip: the n_con intervals of modelled constraints -- no NaN, hi >= lo (BOGP_ERR_INVALID)
 int check_constraint_bounds(bogp_handle* h, const char* who, int n_con, const double* lo, const double* hi);
+// bogp_api_ehvi_constrained.hip, shared with bogp_sweep_ehvi_constrained_grid (bogp_api_ehvi.hip): the first refusals of constrained EHVI
+// -- the handle's state, m_obj + n_con against the commit -- and its tail: run_sweep (rq.ec or rq.ecg set), the downloads, the k winners
+int check_ehvi_constrained_model(bogp_handle* h, const char* who, int m_obj, int n_con);
+int run_ehvi_constrained_sweep(bogp_handle* h, SweepRequest& rq, int m, int k, double* best_val, int64_t* best_idx, double* val_out,
+                               double* pof_out, double* mu_out, double* mse_out);
 #pragma GCC visibility pop
 // bogp_api_constrained.hip, shared with the point path: what every entry with modelled constraints refuses alike, from the target count
 // through the criteria down to the bounds (all BOGP_ERR_INVALID; hidden: the library's dynamic symbols stay the ones they were)

@@ -324,6 +324,40 @@ struct ConstrainedEhviArgs {
 };
 hipError_t launch_ehvi_constrained(const ConstrainedEhviArgs& a, hipStream_t st);
 
+// the same criterion over the grid of the feasible front's cells (kernels_ehvi_constrained_grid.hip): takes k_ehvi_constrained's place in
+// the chunk loop of bogp_sweep_ehvi_constrained_grid.  ConstrainedEhviArgs' fields in its order (its note holds here as well: phase 1 is
+// its loop over the training points) with EhviGridArgs' grid fields, over the m_obj objectives, where the cells stood -- and pof_out in
+// front of lo / hi: next to the grid fields it is loaded with them, in front of that loop, and k_ehvi_constrained_grid<3, 4, 64, false>
+// gets a 36-byte stack frame.  A grid has at least one column: the feasibility-only criterion (C == 0) stays with ConstrainedEhviArgs.
+struct ConstrainedEhviGridArgs {
+  const double* rT;       // [Np][Mc] the chunk's correlation columns (read for the m means)
+  const double* gamma;    // [m][ld_gamma] the targets' gamma columns
+  int ld_gamma, N;        // Np; training points summed over
+  int64_t Mc, mcount, m0;
+  const double* ss_part;  // [nJ][Mc]
+  const double* w_part;   // [S][Mc] (constant trend with estimate_trend only)
+  int S, nJ;
+  double beta, G;
+  int estimate_trend;
+  int m, m_obj;           // targets, 3 .. BOGP_MAX_TARGETS; objectives among them, 2 .. m - 1
+  double sigma2[8];       // per target
+  double* mu_out;         // [M][m] or null
+  double* mse_out;        // [M][m] or null
+  double* pof_out;        // [M] or null
+  double lo[8], hi[8];    // per constraint: entry j belongs to target m_obj + j
+  const double* pts;      // [E] (device): EhviGridArgs' fields from here, m_obj in m's place
+  const int* last_idx;    // [C] (device), each in [0, V)
+  int n[8], off[8];       // n[k], k < m_obj - 1; off[k], k <= m_obj - 1
+  int step[8];
+  int E, C;
+  int group, tabled;
+  double* val_out;        // [M] (global index m0 + i)
+  double* blk_val;        // per-block partial argmax
+  int64_t* blk_idx;
+  int64_t blk_offset;
+};
+hipError_t launch_ehvi_constrained_grid(const ConstrainedEhviGridArgs& a, hipStream_t st);
+
 // one Kriging-believer pass over a chunk (kernels_believer.hip): the rank-one downdate of the running variance by the believed point p,
 // c(x) = (k(x, p) - r(x) . a + u(x) u(p) - sum_k c_k(x) c_k(p)) / sqrt(pivot), s(x) -= sigma2 c(x)^2, and -- for the pass in front of a
 // step -- that step's criterion on (mu, max(0, s)) with the per-block argmax records k_argmax_final reads (one record per 64 rows)

@@ -32,22 +32,10 @@
 // GS / 2, GS / 4, .. 1 (p_l + p_{l xor d}: every lane holds the same bits after each stage).
 // np.argmax order over the rows (first maximum, NaN maximal) into the per-block records, as k_ehvi.
 #include "bogp_device.h"
+#include "bogp_ehvi_grid_row.h"
 #include "bogp_internal.h"
 
 namespace bogp {
-
-// axis of table entry e: the number of off[1 .. MT - 1] that are <= e (MT - 1: the last axis' values); *end: where its axis' entries end
-template <int MT>
-__device__ __forceinline__ int grid_axis_of(const EhviGridArgs& a, int e, int* end) {
-  int k = 0;
-  *end = a.E;
-#pragma unroll
-  for (int j = MT - 1; j >= 1; --j) {
-    k += e >= a.off[j] ? 1 : 0;
-    if (e < a.off[j]) *end = a.off[j];
-  }
-  return k;
-}
 
 template <int MT, int GS, bool TABLED>
 __global__ __launch_bounds__(256) void k_ehvi_grid(EhviGridArgs a) {
@@ -80,75 +68,14 @@ __global__ __launch_bounds__(256) void k_ehvi_grid(EhviGridArgs a) {
   }
   // ---- 2. the criterion, a group of GS lanes per row
   const int grp = tid / GS, l = tid % GS;
-  const int E = a.E, C = a.C, off_last = a.off[MT - 1];
   double* const tab = s_tab + (TABLED ? grp * TCAP : 0);
-  int d0[MT - 1];  // the digits of column l: the lane's first column, the same for every row
-  {
-    int rem = l;
-#pragma unroll
-    for (int k = MT - 2; k >= 0; --k) {
-      d0[k] = rem % a.n[k];
-      rem /= a.n[k];
-    }
-  }
+  int d0[MT - 1];
+  grid_first_digits<MT>(a, l, d0);
   __syncthreads();
-  for (int it = 0; it < GS; ++it) {
+  for (int it = 0; it < GS; ++it) {  // steps A, B, C and the butterfly: bogp_ehvi_grid_row.h
     const int row = it * NG + grp;
-    if constexpr (TABLED) {
-      for (int e = l; e < E; e += GS) {  // A
-        int end;
-        const int k = grid_axis_of<MT>(a, e, &end);
-        const double sd = s_sd[k * 256 + row];
-        const double gv = ehvi_G((a.pts[e] - s_mu[k * 256 + row]) / sd);
-        tab[e] = e >= off_last ? sd * gv : gv;
-      }
-      __syncthreads();
-      for (int e = l; e < off_last; e += GS) {  // B
-        int end;
-        const int k = grid_axis_of<MT>(a, e, &end);
-        const double g0 = tab[e];
-        const double g1 = e + 1 < end ? tab[e + 1] : 0.0;
-        const double t = s_sd[k * 256 + row] * (g0 - g1);
-        tab[e] = t;
-      }
-      __syncthreads();
-    }
-    double acc = 0.0;
-    int dg[MT - 1];
-#pragma unroll
-    for (int k = 0; k < MT - 1; ++k) dg[k] = d0[k];
-    for (int c = l; c < C; c += GS) {  // C
-      double p = 1.0;
-      double tl;
-      if constexpr (TABLED) {
-#pragma unroll
-        for (int k = 0; k < MT - 1; ++k) p *= tab[a.off[k] + dg[k]];
-        tl = tab[off_last + a.last_idx[c]];
-      } else {
-#pragma unroll
-        for (int k = 0; k < MT - 1; ++k) {
-          const int e = a.off[k] + dg[k];
-          const double mu = s_mu[k * 256 + row], sd = s_sd[k * 256 + row];
-          const double g0 = ehvi_G((a.pts[e] - mu) / sd);
-          const double g1 = dg[k] + 1 < a.n[k] ? ehvi_G((a.pts[e + 1] - mu) / sd) : 0.0;
-          p *= sd * (g0 - g1);
-        }
-        const double mu = s_mu[(MT - 1) * 256 + row], sd = s_sd[(MT - 1) * 256 + row];
-        tl = sd * ehvi_G((a.pts[off_last + a.last_idx[c]] - mu) / sd);
-      }
-      acc += p * tl;
-      int carry = 0;  // the digits of column c + GS
-#pragma unroll
-      for (int k = MT - 2; k >= 0; --k) {
-        int v = dg[k] + a.step[k] + carry;
-        carry = v >= a.n[k] ? 1 : 0;
-        dg[k] = v - (carry ? a.n[k] : 0);
-      }
-    }
-#pragma unroll
-    for (int dist = GS / 2; dist >= 1; dist >>= 1) acc += shfl_xor_f64(acc, dist);
+    const double acc = ehvi_grid_row<MT, GS, TABLED, 256>(a, tab, s_mu + row, s_sd + row, l, d0);
     if (l == 0) s_val[row] = acc;
-    if constexpr (TABLED) __syncthreads();  // the next row's entries overwrite this table
   }
   __syncthreads();
   // ---- 3. values and the block's record, a lane per row

@@ -180,7 +180,10 @@ def mobo_create_acquisition(self, fixed=None, **kwargv):
             raise NotImplementedError("optimizer=%r under expensive constraints of a multi-objective run: constrained EHVI "
                                       "(bogp.ConstrainedEHVI) is served by the sweep family only %s; the constraint values are not dropped "
                                       "silently" % (optimizer, _SWEEPS))  # fmt: skip
-        criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi)
+        # install(constrained_mobo_factored=True): the sweep evaluates the feasible front's grid per axis, on the rows that can be feasible
+        # (bogp_sweep_ehvi_constrained_grid), and not every cell for every row
+        criterion = acquisition.ConstrainedEHVI(model=self.model, ref_point=np.asarray(self.ref_point, dtype=float), lo=lo, hi=hi,
+                                                **(dict(factored=True) if _CONSTRAINTS.get("mobo_factored") else {}))  # fmt: skip
         return _ORIGINAL["partial_argument"](functools.partial(criterion), self.search_space.var_name, fixed, reduce_output=False)
     if getattr(self, "_optimizer", None) in ("sweep", "sweep-device") and _forest.is_forest_model(getattr(self, "model", None)):
         # a RandomForest fitted on y (N, n_obj) (this package's or the reference's), on any space a forest sweep serves: the
@@ -677,7 +680,7 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             constrained_mobo_gradient: bool = False, constrained_mobo_batches: str = "topk", constraint_thompson: bool = False,
             ehvi_thompson: bool = False, thompson_polish: bool = False, ehvi_thompson_polish: bool = False,
             constrained_mobo_thompson: bool = False, constraint_thompson_polish: bool = False,
-            constrained_mobo_thompson_polish: bool = False, ehvi_factored: bool = False):
+            constrained_mobo_thompson_polish: bool = False, ehvi_factored: bool = False, constrained_mobo_factored: bool = False):
     """Re-point the reference's extension points at this package (see the module docstring).  `bayes_optim` is the
     imported reference package (default: `import bayes_optim`).  Returns `uninstall()`.  Idempotent.
 
@@ -771,6 +774,11 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
     cell: the same proposals to rounding, faster on fronts of many cells.  The forest, gradient, believer, Thompson and constrained
     routes keep the cell loop.
 
+    `constrained_mobo_factored=True` (with `constrained_mobo=True`; alone it raises ValueError): the constrained criterion of the sweep
+    family is built with `factored=True`, so each sweep evaluates the grid of the feasible front's cells per axis and only for the
+    candidates whose probability of feasibility is not 0 (`bogp_sweep_ehvi_constrained_grid`): the same proposals to rounding.  The
+    gradient, believer and Thompson routes keep the cell loop.
+
     `ehvi_thompson=True` (together with `batch_strategy="believer"` it raises ValueError): the reference's `MOBO(n_point=q)` proposes
     its q points by `optim.ehvi_thompson_batch` -- per point one joint draw of the objectives, and the candidate whose drawn vector
     adds the most hypervolume to the front (the one nearest to the non-dominated region where the draw improves nowhere) -- with the
@@ -799,6 +807,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
         raise ValueError("constrained_mobo_thompson=True and constrained_mobo_batches='believer' name two batch strategies for one step: choose one")
     if constrained_mobo and not expensive_constraints:
         raise ValueError("constrained_mobo=True needs expensive_constraints=True (it keeps the h_vals / g_vals of a multi-objective tell())")
+    if constrained_mobo_factored and not constrained_mobo:
+        raise ValueError("constrained_mobo_factored=True needs constrained_mobo=True (it is constrained EHVI over the grid of the feasible front's cells)")
     if constrained_mobo_gradient and not constrained_mobo:
         raise ValueError("constrained_mobo_gradient=True needs constrained_mobo=True (it is the input gradient of constrained EHVI)")
     if constraint_batches not in ("topk", "believer"):
@@ -826,6 +836,8 @@ def install(bayes_optim=None, fuse_batch: bool = True, reroute_bfgs: str = None,
             _CONSTRAINTS["mobo"] = True
         if constrained_mobo_gradient:
             _CONSTRAINTS["mobo_gradient"] = True
+        if constrained_mobo_factored:
+            _CONSTRAINTS["mobo_factored"] = True
         if constrained_mobo_batches == "believer":
             _CONSTRAINTS["mobo_batches"] = "believer"
         if constrained_mobo_thompson:

@@ -369,6 +369,20 @@ int bogp_sweep_ehvi_constrained(bogp_handle* h, int m_obj, int C, const double* 
                                 const double* hi, int k, double* best_val, int64_t* best_idx, double* val_out, double* pof_out,
                                 double* mu_out, double* mse_out);
 
+/* bogp_sweep_ehvi_constrained over the GRID the cells form (bogp_sweep_ehvi_grid's arguments, over the m_obj objectives: m_obj - 1
+ * axes), C >= 1 by construction.  E is bogp_sweep_ehvi_grid's factored sum in its order -- it depends on m_obj, n_a and V alone, never
+ * on which other rows are feasible -- and is formed only for the rows with P != 0: the kernel lists them per 256 rows and a group of
+ * lanes takes one listed row at a time, so rows with P == 0 cost nothing wherever they stand.  value = +0.0 where P == 0.0, else E * P.
+ * The values agree with bogp_sweep_ehvi_constrained on the expanded cells to rounding; pof_out / mu_out / mse_out are its bytes.
+ *   m_obj, n_con, lo, hi, k, best_val, best_idx, val_out, pof_out, mu_out, mse_out: as bogp_sweep_ehvi_constrained
+ *   n_cells, edges, V, last_val, last_idx: as bogp_sweep_ehvi_grid, with m_obj in m's place
+ * Refusals: bogp_sweep_ehvi_constrained's, in its order (without those of the cells), then bogp_sweep_ehvi_grid's for the grid.  The
+ * feasibility-only criterion (no cell) stays with bogp_sweep_ehvi_constrained (C == 0).  The time of the kernel is reported as
+ * acquisition_ms by bogp_last_timing.                                                                                     */
+int bogp_sweep_ehvi_constrained_grid(bogp_handle* h, int m_obj, const int* n_cells, const double* edges, int V, const double* last_val,
+                                     const int32_t* last_idx, int n_con, const double* lo, const double* hi, int k, double* best_val,
+                                     int64_t* best_idx, double* val_out, double* pof_out, double* mu_out, double* mse_out);
+
 /* ---- sweep: Kriging-believer batches ------------------------------------------------------------------
  * q proposals per call from q criteria, where step j sees the variance conditioned on the points believed before it
  * (Ginsbourger, Le Riche, Carraro 2010).  The reference has no such strategy: ParallelBO's q criteria share one posterior
